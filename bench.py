@@ -6,10 +6,21 @@ Workload (BASELINE.json configs[1]): B = 64 synthetic 512x512 mono spectrogram t
 resident in HBM) -> image decode -> InverseMelScale (SGD 200) -> Griffin-Lim 32 -> int16 PCM, all in
 HIP kernels through librfx.so.  One "step" = one such batch.  value = tiles/s over all ranks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python bench.py --workload forward        # configs[2] alone: audio -> mel images (MFMA roofline)
     python bench.py --workload decode-stereo64 --gpus 8   # configs[3]: 512 stereo tiles, Griffin-Lim 64, sharded
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`,
+`ms_per_step` = wall time of one timed step, the spread of the K steps, `config`).  Everything else it
+can measure - the objects listed below, the configs[2] forward measurement carried as `"forward"`, the
+per-stage and roofline legs of `--workload forward` / `decode-stereo64` and the CPU baselines - runs
+only with `--full`, after the timed region (each keeps its `--no-*` switch there).
+
+`--dump-outputs DIR` writes what the timed path returned in its LAST step, as float32 `DIR/<name>.npy`
+(`pcm` for the decode workloads, `image` for forward; at most 64 MB in all, a fixed seeded sample of
+rows beyond that).  Inputs and step seeds depend on the arguments only, so two builds run with the
+same arguments can be compared output for output.
 
 `--gpus N` with N > 1 outside a torch.distributed launch re-launches this script under
 `torch.distributed.run` with N ranks (one process per GPU, backend nccl = RCCL); `n_gpus` on the JSON
@@ -17,9 +28,8 @@ line is the number of ranks that answered an RCCL all_reduce, not the flag.  Cli
 the headline workload gives every GPU its own 64 tiles (weak scaling, no data-path collective; the only
 collectives are the timing barrier and the max-over-ranks reduction); `decode-stereo64` shards a FIXED
 batch of 512 stereo clips over the ranks with `riffusion.batch_shard.shard_range` (strong scaling).
-The headline line also carries the configs[2] forward measurement as a `"forward"` object.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line with `--full`:
   roofline     - the dominant kernel (rfx::gl_iter_kernel<2>, one Griffin-Lim iteration over the
                  batch): algorithmic bytes per launch = 20 B x 8821 bins x 512 frames x 64 tiles
                  (|S| 4 B + tprev 8 B read + 8 B written per bin and iteration)
@@ -29,7 +39,8 @@ Extra objects on the JSON line:
   other_configs - `stereo64`: one GPU's share of BASELINE.json configs[3] (64 stereo clips, Griffin-Lim 64) through the product entry
                  point with its own canonical-bytes roofline; `batch_sweep`: the decode step at B = 16 ... 128 (the run partition of
                  rfx_griffinlim keeps every resident workgroup slot busy whatever B is).  After the timed region; context only.
-  ms_per_step_min / median / max, shader_clock - the K timed steps one by one and the sclk the chip held meanwhile.
+  shader_clock - the sclk the chip held during the timed steps (their spread, ms_per_step_min / median / max /
+                 series, is on every line: one event per step inside the timed region).
   other_sample_rates - the same decode step, and the forward path, at 48 kHz (n_fft 19200 / win 4800 / hop 480) and
                  22.05 kHz (8820 / 2205 / 220): the row-family kernels of csrc/rfx_fam.hip, measured after the
                  timed region; context only.
@@ -55,18 +66,23 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other measurement (roofline and stage legs, single-tile latency, other "
+                         "sample rates and configs, the embedded forward line, CPU baselines); a plain run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--batch", type=int, default=64, help="tiles per GPU per step")
     ap.add_argument("--iters", type=int, default=32, help="Griffin-Lim iterations")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baselines")
     ap.add_argument("--workload", choices=["decode", "forward", "decode-stereo64"], default="decode",
                     help="decode = the headline (configs[1], tiles -> audio); forward = configs[2] (audio -> mel images); "
                          "decode-stereo64 = configs[3] (512 stereo tiles, Griffin-Lim 64, sharded over the ranks)")
     ap.add_argument("--global-clips", type=int, default=512, help="decode-stereo64: clips in the sharded batch")
-    ap.add_argument("--no-forward", action="store_true", help="skip the embedded configs[2] forward measurement")
-    ap.add_argument("--no-other-rates", action="store_true", help="skip the embedded 48 kHz decode measurement (row-family Griffin-Lim engine)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the embedded configs[3] share (64 stereo clips, Griffin-Lim 64) and the batch-shape sweep")
+    ap.add_argument("--no-forward", action="store_true", help="with --full: skip the embedded configs[2] forward measurement")
+    ap.add_argument("--no-other-rates", action="store_true", help="with --full: skip the embedded 48 kHz decode measurement (row-family Griffin-Lim engine)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the embedded configs[3] share (64 stereo clips, Griffin-Lim 64) and the batch-shape sweep")
     ap.add_argument("--host-input", action="store_true",
                     help="decode-stereo64: the timed calls take the tiles from HOST memory (the reference's API is host images in, host "
                          "audio out); uploads run chunk by chunk through pinned memory on a side stream (batch_shard.ChunkSource)")
@@ -74,7 +90,10 @@ def parse():
                     help="ms_per_step of the same command at --gpus 1: an N > 1 line then carries `vs_n1` (weak scaling: t1 / tN)")
     ap.add_argument("--gather", choices=["none", "rank0", "all"], default="none",
                     help="decode-stereo64: which clips a rank returns (own shard / everything on rank 0 / everything everywhere)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def relaunch_distributed(n_gpus: int) -> int:
@@ -384,6 +403,33 @@ def cpu_baseline(iters: int, threads_cap: int = 16, min_seconds: float = 10.0, m
     }
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: every array as float32 `directory/<name>.npy` (int16 PCM and uint8 images convert exactly).  The files
+    together stay within DUMP_BUDGET_BYTES: an array larger than its share keeps a fixed, seeded sample of its rows (leading axis,
+    in order; of its elements if one row is already too large), so two builds run with the same arguments write the same entries."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        a = a.reshape(1) if a.ndim == 0 else a
+        note = "all rows"
+        if 4 * a.size > share:
+            rng = np.random.default_rng(20240807)
+            rows = share // (4 * (a.size // a.shape[0]))
+            if rows >= 1:
+                a = a[np.sort(rng.choice(a.shape[0], rows, replace=False))]
+                note = f"seeded sample of {rows} rows"
+            else:
+                a = a.reshape(-1)[np.sort(rng.choice(a.size, share // 4, replace=False))]
+                note = f"seeded sample of {a.size} elements"
+        out = a.astype(np.float32)
+        np.save(os.path.join(directory, name + ".npy"), out)
+        print(f"[bench] {name}: {out.shape} float32 ({note}) -> {os.path.join(directory, name + '.npy')}", file=sys.stderr, flush=True)
+
+
 FORWARD_KERNEL_SOURCES = ("rfx_stft.hip", "rfx_core.h", "rfx_frame.hip.h", "rfx_kernels.h", "rfx_codec.hip")
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense fp32 matrix peak
 
@@ -426,9 +472,10 @@ def forward_cpu_baseline(threads_cap: int = 16, min_seconds: float = 10.0):
                       f"mel matmul + uint8 quantisation), {dt:.1f} s, {threads} threads of {os.cpu_count()} logical cores"}
 
 
-def forward_measure(args, world, rank, dev, distributed, with_cpu):
+def forward_measure(args, world, rank, dev, distributed, with_cpu, full=True, dump=False):
     """BASELINE.json configs[2]: B waveforms -> STFT -> MFMA mel GEMM -> uint8 image, per rank.
-    Returns the result object on rank 0 (None elsewhere); every rank takes part in the timed region."""
+    Returns the result object on rank 0 (None elsewhere); every rank takes part in the timed region.  The per-stage timings
+    and the roofline run only when `full`; `dump` writes the images of the last timed step (--dump-outputs)."""
     from riffusion import _hip
     from riffusion.spectrogram_params import SpectrogramParams
     from riffusion.util import image_util
@@ -463,7 +510,32 @@ def forward_measure(args, world, rank, dev, distributed, with_cpu):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     assert img.shape == (B, N_MELS, N_FRAMES, 3)
+    if rank == 0 and dump and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image": img})
+    del img
+    images_per_s = world * B * args.steps / elapsed
+    out = None
     if rank == 0:
+        out = {
+            "metric": "spectrogram_images_per_sec_forward",
+            "value": round(images_per_s, 1),
+            "unit": "images/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": f"batch={B} synthetic waveforms of {L} samples -> fused STFT / |X| / banded mel kernel -> uint8 image "
+                                   "(BASELINE.json configs[2]); waveforms resident in HBM",
+                       "batch_per_gpu": B, "global_batch": world * B,
+                       "parallelism": f"clips sharded over {world} GPU(s), no data-path collective"},
+            "audio_sec_per_sec": round(images_per_s * L / SR, 1),
+        }
+    if rank == 0 and full:
         def timed(fn, reps=5):  # one call per measurement, drained before and after: no overlap between launches
             tot = 0.0
             for _ in range(reps):
@@ -484,7 +556,6 @@ def forward_measure(args, world, rank, dev, distributed, with_cpu):
         del mag
         melscale_ms, _ = timed(lambda: plan.mel_scale(lin))          # standalone MelScale member: pack + MFMA GEMM
         del lin
-        images_per_s = world * B * args.steps / elapsed
         # the fused kernel reads the waveform and writes the mel amplitudes: its algorithmic HBM bytes are tiny, the
         # transform itself (fp32 VALU butterflies) is what takes the time
         alg_bytes = 4.0 * B * (L + N_MELS * N_FRAMES)
@@ -520,24 +591,7 @@ def forward_measure(args, world, rank, dev, distributed, with_cpu):
             if b:
                 roof["binding"] = b
         k_exec = executed_mel_k()
-        out = {
-            "metric": "spectrogram_images_per_sec_forward",
-            "value": round(images_per_s, 1),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"batch={B} synthetic waveforms of {L} samples -> fused STFT / |X| / banded mel kernel -> uint8 image "
-                                   "(BASELINE.json configs[2]); waveforms resident in HBM",
-                       "batch_per_gpu": B, "global_batch": world * B,
-                       "parallelism": f"clips sharded over {world} GPU(s), no data-path collective"},
-            "audio_sec_per_sec": round(images_per_s * L / SR, 1),
+        out.update({
             "roofline": roof,
             "stages": {"image_from_waveform_ms": round(one_call_ms, 3), "stft_mel_fused_ms": round(mel_ms, 3), "image_encode_ms": round(enc_ms, 3),
                        "note": "a timed step is ONE rfx_image_from_waveform call (forward kernel with the maximum taken on the fly -> encoder reading "
@@ -547,11 +601,10 @@ def forward_measure(args, world, rank, dev, distributed, with_cpu):
             "standalone_members": {"spectrogram_stft_ms": round(stft_ms, 3), "mel_scale_pack_plus_mfma_gemm_ms": round(melscale_ms, 3),
                                    "mfma_gemm_executed_k": k_exec,
                                    "note": "MelScale on (B, n_stft, T) input = layout pack + fp32-MFMA GEMM over the non-zero K blocks"},
-        }
+        })
         if with_cpu:
             out["cpu_baseline"] = forward_cpu_baseline()
-        return out
-    return None
+    return out
 
 
 def og_beat_cli(dev, reps: int = 5):
@@ -631,7 +684,28 @@ def stereo64_main(args, world, rank, dev, distributed):
         elapsed = float(tmax.item())
     lo, hi = batch_shard.result_rows(N, group, args.gather)
     assert pcm.shape == (hi - lo, L, 2) and pcm.dtype == np.int16
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pcm": pcm})
     del pcm
+    ms_per_step = elapsed / args.steps * 1e3
+    tiles_per_s = N * args.steps / elapsed
+    pcm_mb = N * L * 2 * 2 / 1e6
+    out = {
+        "metric": "stereo_spectrogram_tiles_per_sec_griffinlim64", "value": round(tiles_per_s, 2), "unit": "tiles/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{N} synthetic stereo 512x512 uint8 tiles -> image decode -> InverseMelScale SGD-200 -> Griffin-Lim 64 "
+                               f"-> int16 PCM in host memory (BASELINE.json configs[3]), tiles {'in HOST memory' if args.host_input else 'resident in HBM'} when the timed region starts, "
+                               f"clips sharded over the ranks with shard_range, gather={args.gather!r}"
+                               + {"none": " (every rank returns its own clips; no data-path collective)",
+                                  "rank0": f" (one RCCL gather of {pcm_mb:.0f} MB int16 PCM to rank 0)",
+                                  "all": f" (one RCCL all_gather_into_tensor of {pcm_mb:.0f} MB int16 PCM)"}[args.gather],
+                   "global_batch": N, "clips_per_gpu": -(-N // world), "griffin_lim_iters": 64, "gather": args.gather,
+                   "parallelism": f"clips sharded over {world} GPU(s)"},
+        "audio_sec_per_sec": round(tiles_per_s * L / SR, 1),
+    }
+    if not args.full:
+        return out if rank == 0 else None
 
     # ---- stage leg (outside the timed region, every rank takes part in the collective) ----------------------------------
     def wall(fn, reps=2):
@@ -662,9 +736,6 @@ def stereo64_main(args, world, rank, dev, distributed):
     del shard, pinned
     if rank != 0:
         return None
-    ms_per_step = elapsed / args.steps * 1e3
-    tiles_per_s = N * args.steps / elapsed
-    pcm_mb = N * L * 2 * 2 / 1e6
     stages = {"compute_ms": round(compute_ms, 3), "compute_plus_d2h_ms": round(host_ms, 3),
               "d2h_exposed_ms": round(max(0.0, host_ms - compute_ms), 3),
               "host_in_host_out_ms": round(host_in_ms, 3), "h2d_exposed_ms": round(max(0.0, host_in_ms - host_ms), 3),
@@ -674,21 +745,7 @@ def stereo64_main(args, world, rank, dev, distributed):
                       "call returning host PCM (chunk copies on a side stream behind the compute, pinned memory); host_in_host_out = the same call "
                       "fed from a pageable HOST array (uploads staged through pinned memory on a side stream, chunk k+1 under chunk k); d2h_own_shard_raw = the whole "
                       "shard in one un-overlapped pinned copy; collectives move the own shard (int16, as bytes) into one preallocated tensor"}
-    out = {
-        "metric": "stereo_spectrogram_tiles_per_sec_griffinlim64", "value": round(tiles_per_s, 2), "unit": "tiles/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{N} synthetic stereo 512x512 uint8 tiles -> image decode -> InverseMelScale SGD-200 -> Griffin-Lim 64 "
-                               f"-> int16 PCM in host memory (BASELINE.json configs[3]), tiles {'in HOST memory' if args.host_input else 'resident in HBM'} when the timed region starts, "
-                               f"clips sharded over the ranks with shard_range, gather={args.gather!r}"
-                               + {"none": " (every rank returns its own clips; no data-path collective)",
-                                  "rank0": f" (one RCCL gather of {pcm_mb:.0f} MB int16 PCM to rank 0)",
-                                  "all": f" (one RCCL all_gather_into_tensor of {pcm_mb:.0f} MB int16 PCM)"}[args.gather],
-                   "global_batch": N, "clips_per_gpu": -(-N // world), "griffin_lim_iters": 64, "gather": args.gather,
-                   "parallelism": f"clips sharded over {world} GPU(s)"},
-        "audio_sec_per_sec": round(tiles_per_s * L / SR, 1),
-        "stages": stages,
-    }
+    out["stages"] = stages
     if eighth_ms is not None:
         # 8-GPU step = the slowest rank's shard (N/8 clips incl. its overlapped D2H) + the collective, if one was asked for.
         # The collective is priced from the xGMI figures of MI355X_MICROARCH.md (7 links x ~153 GB/s per GPU, ~75 % achievable):
@@ -741,7 +798,8 @@ def main():
             dist.destroy_process_group()
 
     if args.workload == "forward":
-        return finish(forward_measure(args, world, rank, dev, distributed, world == 1 and not args.no_cpu_baseline))
+        return finish(forward_measure(args, world, rank, dev, distributed, args.full and world == 1 and not args.no_cpu_baseline,
+                                      full=args.full, dump=True))
     if args.workload == "decode-stereo64":
         return finish(stereo64_main(args, world, rank, dev, distributed))
 
@@ -758,8 +816,9 @@ def main():
     # synthetic tiles of SURVEY.md 8(d), a different seed per rank, resident in HBM before timing
     rng = np.random.default_rng(20240807 + rank)
     tiles = torch.from_numpy(rng.integers(0, 256, size=(B, N_MELS, T, 3), dtype=np.uint8)).to(dev)
-    lut = torch.from_numpy(image_util.decode_lut(0.25, 30e6)).to(dev)
-    gl_ws = torch.empty(plan.lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), dtype=torch.uint8, device=dev)
+    if args.full:  # (for the legs after the timed region)
+        lut = torch.from_numpy(image_util.decode_lut(0.25, 30e6)).to(dev)
+        gl_ws = torch.empty(plan.lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), dtype=torch.uint8, device=dev)
 
     def step(seed):
         # THE PRODUCT ENTRY POINT (round 6): what a caller of the reference's SpectrogramImageConverter.audio_from_spectrogram_image
@@ -784,11 +843,12 @@ def main():
 
     for w in range(args.warmup):
         step(w)
-    clock = ClockSampler(dev.index)
+    clock = ClockSampler(dev.index) if args.full else None
     # one event per step on the launch stream (no host sync inside the timed region): the spread of the K steps
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     sync_all()
-    clock.start()
+    if clock:
+        clock.start()
     t0 = time.perf_counter()
     marks[0].record()
     for k in range(args.steps):
@@ -796,7 +856,8 @@ def main():
         marks[k + 1].record()
     sync_all()
     elapsed = time.perf_counter() - t0
-    clock.stop()
+    if clock:
+        clock.stop()
     per_rank_ms = None
     if distributed:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -805,13 +866,15 @@ def main():
         per_rank_ms = [float(t.item()) / args.steps * 1e3 for t in every]
         elapsed = max(float(t.item()) for t in every)
     assert pcm.shape == (B, HOP * (T - 1), 1) and pcm.dtype == torch.int16 and int(pcm.abs().max()) > 30000
+    if rank == 0 and args.dump_outputs:  # what the last timed step returned, before anything else runs
+        dump_outputs(args.dump_outputs, {"pcm": pcm})
     step_series = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]  # in order: a trend is the chip warming up, an outlier is not
     per_step = sorted(step_series)
 
     # ---- roofline leg (outside the timed region): per-launch durations from HIP events on the stream
     roofline = None
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         ms = (ctypes.c_float * (args.iters + 1))()
         four_calls(999, launch_ms=ms)
         steady = [ms[i] for i in range(2, args.iters + 1)] or [ms[-1]]
@@ -915,7 +978,6 @@ def main():
             "ms_per_step_max": round(per_step[-1], 3),
             "ms_per_step_max_over_min": round(per_step[-1] / per_step[0], 4),
             "ms_per_step_series": [round(v, 3) for v in step_series],
-            "shader_clock": clock.summary(),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -931,9 +993,9 @@ def main():
                 "parallelism": f"clips sharded over {world} GPU(s), no data-path collective",
             },
             "audio_sec_per_sec": round(tiles_per_s * HOP * (T - 1) / SR, 1),
-            "roofline": roofline,
-            "stages": extra,
         }
+        if args.full:
+            out.update({"shader_clock": clock.summary(), "roofline": roofline, "stages": extra})
         if per_rank_ms is not None:
             out["per_rank_ms"] = {"min": round(min(per_rank_ms), 3), "max": round(max(per_rank_ms), 3), "by_rank": [round(v, 3) for v in per_rank_ms]}
         if args.n1_ms:
@@ -942,7 +1004,7 @@ def main():
                             "note": "weak scaling: every rank converts its own batch; speedup = N x t1 / tN"}
     # ---- the one-tile-per-request case (reference server.py:152-164): uint8 tile in HBM -> int16 PCM on the host, one call
     latency = None
-    if rank == 0:
+    if rank == 0 and args.full:
         latency = {}
         for name, stereo in (("mono", False), ("stereo", True)):
             conv1 = SpectrogramImageConverter(SpectrogramParams(stereo=stereo, num_griffin_lim_iters=args.iters), device=str(dev))
@@ -959,7 +1021,7 @@ def main():
     # ---- the same decode step at 48 kHz (cli.py:43 takes the sample rate from the input file; spectrogram_params.py:62-81 derives
     # n_fft 19200 / win 4800 / hop 480 from it): Griffin-Lim on the row-family kernels (csrc/rfx_fam.hip).  Context, not the headline.
     other = None
-    if rank == 0 and world == 1 and not args.no_other_rates:
+    if rank == 0 and world == 1 and args.full and not args.no_other_rates:
         other = {}
         for rate in (48000, 22050):
             p2 = SpectrogramParams(sample_rate=rate, num_griffin_lim_iters=args.iters)
@@ -1006,7 +1068,7 @@ def main():
     # entry point (uint8 tiles resident in HBM -> int16 PCM on the device), and the decode step over batch shapes that do not
     # divide the chip's 512 resident Griffin-Lim workgroups (cli.py:172-204 feeds arbitrary file counts per batch)
     other_cfg = None
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_other_configs:
         from riffusion.spectrogram_image_converter import SpectrogramImageConverter as _SIC
 
         other_cfg = {}
@@ -1098,17 +1160,18 @@ def main():
 
     # ---- configs[2] (audio -> mel image) measured in the same run and carried on the same line
     fwd = None
-    if not args.no_forward:
+    if args.full and not args.no_forward:
         fwd = forward_measure(args, world, rank, dev, distributed, with_cpu=False)
     if rank == 0:
-        out["single_tile_latency"] = latency
+        if latency is not None:
+            out["single_tile_latency"] = latency
         if other is not None:
             out["other_sample_rates"] = other
         if other_cfg is not None:
             out["other_configs"] = other_cfg
         if fwd is not None:
             out["forward"] = {k: fwd[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "config", "roofline", "stages")}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.iters)
     finish(out if rank == 0 else None)
 

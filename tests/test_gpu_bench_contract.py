@@ -1,7 +1,7 @@
 """
 bench.py's output contract, exercised on the GPU with a small batch: exactly ONE line on stdout, valid JSON with the keys the
-driver reads, the `roofline` / `forward` objects, and the same through a torch.distributed.run launch (RCCL, one rank) - whose
-communicator start-up banner must not reach stdout.
+driver reads, the `roofline` / `forward` objects of a --full run, and the same through a torch.distributed.run launch (RCCL, one
+rank) - whose communicator start-up banner must not reach stdout; a plain run's line and its --dump-outputs files.
 """
 import json
 import os
@@ -27,7 +27,7 @@ def _one_json_line(proc):
 
 def test_headline_line_small_batch():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--batch", "4", "--iters", "32",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     d = _one_json_line(p)
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["unit"] == "tiles/s" and d["higher_is_better"] is True
     assert d["metric"] == "spectrogram_tiles_per_sec_griffinlim32" and d["dtype"] == "f32" and d["vs_baseline"] is None
@@ -83,7 +83,7 @@ def test_distributed_launch_one_rank_keeps_stdout_clean():
 
 def test_sharded_stereo_workload_small():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "decode-stereo64", "--global-clips", "4", "--steps", "1",
-                        "--warmup", "0"], capture_output=True, text=True, timeout=600)
+                        "--warmup", "0", "--full"], capture_output=True, text=True, timeout=600)
     d = _one_json_line(p)
     assert d["scaling"] == "strong" and d["config"]["griffin_lim_iters"] == 64 and d["config"]["global_batch"] == 4 and d["value"] > 0
     assert d["config"]["gather"] == "none" and {"compute_ms", "compute_plus_d2h_ms", "d2h_exposed_ms", "d2h_own_shard_raw_ms",
@@ -93,3 +93,25 @@ def test_sharded_stereo_workload_small():
                         "--warmup", "0", "--host-input"], capture_output=True, text=True, timeout=600)
     d = _one_json_line(p)
     assert "HOST memory" in d["config"]["workload"] and d["value"] > 0
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and the spread of the timed steps, nothing measured outside them; with
+    --dump-outputs the PCM of the last timed step lands in DIR/pcm.npy (float32), the same entries on a second run."""
+    import numpy as np
+
+    got = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        d = _one_json_line(p)
+        assert REQUIRED <= set(d) and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "tiles/s"
+        assert d["metric"] == "spectrogram_tiles_per_sec_griffinlim32" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert abs(d["value"] - 4 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01 and len(d["ms_per_step_series"]) == 2
+        assert not {"roofline", "stages", "forward", "cpu_baseline", "single_tile_latency", "other_sample_rates", "other_configs",
+                    "shader_clock"} & set(d)
+        pcm = np.load(tmp_path / run / "pcm.npy")
+        assert pcm.dtype == np.float32 and pcm.shape == (4, 441 * 511, 1)
+        assert np.array_equal(pcm, np.round(pcm)) and np.abs(pcm).max() > 30000 and np.abs(pcm).max() <= 32768
+        got.append(pcm)
+    assert np.array_equal(got[0], got[1])

@@ -428,6 +428,41 @@ def test_bench_gpus_flag_relaunches_n_ranks(repo_root, monkeypatch):
     assert e.value.code == 17
 
 
+def test_bench_dump_outputs_stays_within_budget_and_is_reproducible(repo_root, monkeypatch, tmp_path):
+    """--dump-outputs: float32 files, exact for int16 PCM; an output beyond the budget keeps the same seeded rows every time."""
+    import importlib
+
+    monkeypatch.syspath_prepend(repo_root)
+    bench = importlib.import_module("bench")
+    pcm = torch.from_numpy(np.random.default_rng(3).integers(-32768, 32768, size=(16, 1000, 1), dtype=np.int16))
+    bench.dump_outputs(str(tmp_path / "all"), {"pcm": pcm})
+    whole = np.load(tmp_path / "all" / "pcm.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, pcm.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 5 * 4000 + 100)  # five rows fit
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"pcm": pcm})
+    a, b = np.load(tmp_path / "a" / "pcm.npy"), np.load(tmp_path / "b" / "pcm.npy")
+    assert a.shape == (5, 1000, 1) and a.nbytes <= bench.DUMP_BUDGET_BYTES and np.array_equal(a, b)
+    assert all(any(np.array_equal(r, w) for w in whole) for r in a)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2000)  # not one row: a sample of the elements
+    bench.dump_outputs(str(tmp_path / "c"), {"pcm": pcm})
+    c = np.load(tmp_path / "c" / "pcm.npy")
+    assert c.shape == (500,) and np.isin(c, whole).all()
+
+
+def test_bench_steps_must_be_positive(repo_root, monkeypatch):
+    import importlib
+
+    monkeypatch.syspath_prepend(repo_root)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.steps == 3 and args.full and args.dump_outputs == "out"
+
+
 def test_plan_options_are_validated_before_any_device_call(repo_root):
     """rfx_plan_options as the Python layer fills it: unknown gl_form / frame_engine names are refused on the host, and the
     structure keeps the layout include/rfx.h declares (struct_size first, int32 fields after it)."""

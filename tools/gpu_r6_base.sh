@@ -5,4 +5,4 @@ python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || { ec
 tail -1 $OUT/smoke.txt
 timeout 1200 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log
 grep -E "passed|failed" $OUT/pytest_gpu.log | tail -2
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err; cut -c1-600 $OUT/bench.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err; cut -c1-600 $OUT/bench.json

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_round6.py tests/test_gpu_round6_rang
 if [ "$1" != "quick" ]; then
 timeout 1500 python -m pytest tests -m gpu -q --deselect tests/test_gpu_round6.py --deselect tests/test_gpu_round6_range.py > $OUT/pytest_gpu.log 2>&1; echo "all rc=$?"; grep -E "^FAILED|^ERROR|passed|failed" $OUT/pytest_gpu.log | tail -30 | cut -c1-300
 fi
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -3 $OUT/bench.err; python - <<PY
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -3 $OUT/bench.err; python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))
 print({k: d[k] for k in ("value", "ms_per_step", "ms_per_step_min", "ms_per_step_median", "ms_per_step_max", "ms_per_step_max_over_min")})

@@ -11,9 +11,9 @@ timeout 1500 python -m pytest tests -m gpu -x -q -s > $OUT/pytest_gpu.log 2>&1; 
 grep -E "passed|failed" $OUT/pytest_gpu.log | tail -2
 grep -E "dB|rel-L2|convergence|re-projection|plan cache" $OUT/pytest_gpu.log > $OUT/gpu_parity_figures.txt; wc -l $OUT/gpu_parity_figures.txt
 grep -q "rc=0" $OUT/pytest_gpu.log || { echo "GPU tests failed: no bench, no profiles"; tail -5 $OUT/pytest_gpu.log; exit 1; }
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err; cut -c1-400 $OUT/bench.json
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-forward --no-other-rates > $OUT/bench_rccl1.json 2> $OUT/bench_rccl1.err; cut -c1-200 $OUT/bench_rccl1.json
-timeout 600 python bench.py --workload decode-stereo64 --global-clips 512 --steps 1 --warmup 1 --host-input > $OUT/bench_stereo64_host_input.json 2> $OUT/bench_stereo64.err; cut -c1-300 $OUT/bench_stereo64_host_input.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err; cut -c1-400 $OUT/bench.json
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-forward --no-other-rates > $OUT/bench_rccl1.json 2> $OUT/bench_rccl1.err; cut -c1-200 $OUT/bench_rccl1.json
+timeout 600 python bench.py --full --workload decode-stereo64 --global-clips 512 --steps 1 --warmup 1 --host-input > $OUT/bench_stereo64_host_input.json 2> $OUT/bench_stereo64.err; cut -c1-300 $OUT/bench_stereo64_host_input.json
 RATES=${RATES:-48000,32000,24000,22050,16000,11025,8000,44100} timeout 600 python tools/probe_generic.py 2>&1 | grep -v amdgpu.ids > $OUT/engine_probe.txt; cat $OUT/engine_probe.txt
 RATES=48000,32000,24000,22050,16000,8000 timeout 300 python tools/probe_fwd_rate.py 2>&1 | tail -1 > $OUT/forward_rates.txt; cat $OUT/forward_rates.txt
 bash tools/profile_round.sh > $OUT/profile_round.log 2>&1; tail -14 $OUT/profile_round.log | cut -c1-260
