@@ -309,6 +309,40 @@ int rfx_image_encode_u8(const float* d_mel, int N, int M, int T, int stereo, con
  * zero.  d_clip_peak (N floats) receives max|x| per clip. */
 int rfx_pcm16(const float* d_wave, int N, int C, int L, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* stream);
 
+/* ---- int16 post-processing: riffusion/util/audio_util.py apply_filters and stitch_segments on the device ----------------
+ * Both are CPython `audioop` integer arithmetic (mul, add, rms, max on 16-bit samples), reproduced byte for byte.
+ *
+ * rfx_pcm16_apply_filters: apply_filters(segment, compression=False) - apply_gain(-12 - dBFS), then normalize(headroom=0.1) -
+ * on every clip of d_pcm_in (N, L, C) int16 (channels interleaved, as the bytes audioop sees) -> d_pcm_out, same shape; in place
+ * when d_pcm_out == d_pcm_in.  d_gain_by_rms and d_boost_by_peak are two tables of 32769 doubles built on the host with
+ * pydub's own expressions (audio_util.filter_gain_by_rms / filter_boost_by_peak): the gain factor for each audioop.rms value
+ * (entry 0 = inf, dBFS = -inf) and the normalisation factor for each peak after that gain (entry 0 = 1.0).  The device
+ * evaluates no pow or log.  Exactness: the result equals audioop's whenever L * C < 2^23 (audioop.rms sums the squares in
+ * double, exact up to 2^53); larger clips are refused.  Workspace: rfx_pcm16_filters_workspace_bytes(N, L, C). */
+size_t rfx_pcm16_filters_workspace_bytes(int N, int L, int C);
+int rfx_pcm16_apply_filters(const int16_t* d_pcm_in, int N, int L, int C, const double* d_gain_by_rms, const double* d_boost_by_peak,
+                            int16_t* d_pcm_out, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* rfx_pcm16_stitch: stitch_segments of the N clips of d_pcm (N, L, C) int16 -> d_out (out_frames, C) int16, as described by
+ * the pieces of audio_util.stitch_plan (pydub's millisecond arithmetic of AudioSegment.append, resolved on the host).  Piece k
+ * covers output frames [out_start_k, out_start_{k+1}) (the last one up to out_frames); frame out_start + t is source a at
+ * frame a_off + t (kind 0), or audioop.add(audioop.mul(a, a_gain), audioop.mul(b, b_gain)) (kind 1); a source is clip
+ * a_clip / b_clip of d_pcm, or silence when that index is negative.  h_pieces (host) is checked against N, L and out_frames
+ * before anything is launched; d_pieces is the same table in device memory. */
+typedef struct {
+  int64_t out_start;
+  int64_t a_off;
+  int64_t b_off;
+  double a_gain;
+  double b_gain;
+  int32_t a_clip;
+  int32_t b_clip;
+  int32_t kind;
+  int32_t reserved;
+} rfx_stitch_piece;
+int rfx_pcm16_stitch(const int16_t* d_pcm, int N, int L, int C, const rfx_stitch_piece* h_pieces, const rfx_stitch_piece* d_pieces,
+                     int n_pieces, int64_t out_frames, int16_t* d_out, void* stream);
+
 /* ---- inverse, all the way from the image: SpectrogramImageConverter.audio_from_spectrogram_image's device half
  * (spectrogram_image_converter.py:54-91: image_util.spectrogram_from_image, audio_from_spectrogram -> waveform_from_mel_amplitudes
  * on the image's (C, n_mels, T) tensor, audio_util.audio_from_waveform).  d_img (N, n_mels, T, 3) uint8 -> d_pcm_out (N, L, C) int16,

@@ -11,6 +11,7 @@
 
 #include "../../include/rfx.h"
 #include "rfx_kernels.h"
+#include "rfx_pcm_core.h"
 
 using namespace rfx;
 
@@ -1726,6 +1727,48 @@ int rfx_pcm16(const float* d_wave, int N, int C, int L, int normalize, float* d_
   RFX_ON_DEVICE(dev);
   if (normalize) RFX_HIP(launch_clip_max(d_wave, d_clip_peak, N, (size_t)C * L, true, (hipStream_t)stream));
   RFX_HIP(launch_pcm16(d_wave, d_clip_peak, d_pcm_out, N, L, C, normalize, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+size_t rfx_pcm16_filters_workspace_bytes(int N, int L, int C) {
+  if (N <= 0 || L <= 0 || C <= 0) return 0;
+  return pcm_filters_workspace_bytes(N, L, C);
+}
+
+int rfx_pcm16_apply_filters(const int16_t* d_pcm_in, int N, int L, int C, const double* d_gain_by_rms, const double* d_boost_by_peak,
+                            int16_t* d_pcm_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!d_pcm_in || !d_gain_by_rms || !d_boost_by_peak || !d_pcm_out || !d_workspace || N <= 0 || L <= 0 || C <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters: bad argument");
+  if ((int64_t)L * C >= ((int64_t)1 << 23))
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_pcm16_apply_filters: L * C >= 2^23 (audioop.rms is exact only below that)");
+  if (workspace_bytes < pcm_filters_workspace_bytes(N, L, C)) return fail(RFX_ERR_WORKSPACE, "rfx_pcm16_apply_filters: workspace too small");
+  int dev;
+  if (int rc = device_of(d_pcm_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_pcm_filters(d_pcm_in, N, L, C, d_gain_by_rms, d_boost_by_peak, d_pcm_out, d_workspace, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+int rfx_pcm16_stitch(const int16_t* d_pcm, int N, int L, int C, const rfx_stitch_piece* h_pieces, const rfx_stitch_piece* d_pieces,
+                     int n_pieces, int64_t out_frames, int16_t* d_out, void* stream) {
+  static_assert(sizeof(rfx_stitch_piece) == sizeof(PcmPiece), "rfx_stitch_piece is PcmPiece (rfx_pcm_core.h)");
+  if (!d_pcm || !h_pieces || !d_pieces || !d_out || N <= 0 || L <= 0 || C <= 0 || n_pieces <= 0 || out_frames <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_stitch: bad argument");
+  // every read the kernel will make stays inside the batch: checked here, on the host table
+  if (h_pieces[0].out_start != 0) return fail(RFX_ERR_INVALID, "rfx_pcm16_stitch: the first piece must start at frame 0");
+  for (int k = 0; k < n_pieces; ++k) {
+    const rfx_stitch_piece& p = h_pieces[k];
+    const int64_t next = k + 1 < n_pieces ? h_pieces[k + 1].out_start : out_frames;
+    const int64_t count = next - p.out_start;
+    bool ok = count > 0 && (p.kind == 0 || p.kind == 1);
+    ok = ok && (p.a_clip < 0 || (p.a_clip < N && p.a_off >= 0 && p.a_off + count <= L));
+    ok = ok && (p.kind == 0 || p.b_clip < 0 || (p.b_clip < N && p.b_off >= 0 && p.b_off + count <= L));
+    if (!ok) return fail(RFX_ERR_INVALID, "rfx_pcm16_stitch: piece " + std::to_string(k) + " is empty or reads outside the batch");
+  }
+  int dev;
+  if (int rc = device_of(d_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_pcm_stitch(d_pcm, L, C, d_pieces, n_pieces, out_frames, d_out, (hipStream_t)stream));
   return RFX_OK;
 }
 

@@ -384,5 +384,12 @@ hipError_t launch_image_encode(const float* mel, const float* clip_max, const fl
 hipError_t launch_image_encode_tm(const float* mel_tm, const unsigned* max_keys, int keys_per_image, const float* clip_max_in, const float* thr,
                                   uint8_t* img, float* clip_max_out, int N, int M, int Mpad, int T, int C, hipStream_t s);
 hipError_t launch_pcm16(const float* wave, const float* clip_peak, int16_t* pcm, int N, int L, int C, int normalize, hipStream_t s);
+// int16 post-processing (rfx_pcm.hip, arithmetic in rfx_pcm_core.h): apply_filters(compression=False) per clip of an (N, L, C)
+// batch (in place when out == in), and the stitch of N clips of L frames from the host planner's pieces (PcmPiece[n_pieces])
+size_t pcm_filters_workspace_bytes(int N, int L, int C);
+hipError_t launch_pcm_filters(const int16_t* in, int N, int L, int C, const double* gain_by_rms, const double* boost_by_peak,
+                              int16_t* out, void* workspace, hipStream_t s);
+hipError_t launch_pcm_stitch(const int16_t* pcm, int64_t L, int C, const void* pieces, int n_pieces, int64_t frames, int16_t* out,
+                             hipStream_t s);
 
 }  // namespace rfx

@@ -15,6 +15,7 @@ import os
 import threading
 import typing as T
 
+import numpy as np
 import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -139,6 +140,9 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_image_from_waveform_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "rfx_image_from_waveform": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_pcm16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rfx_pcm16_filters_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rfx_pcm16_apply_filters": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_pcm16_stitch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]),
 }
 
 
@@ -705,6 +709,57 @@ class Plan:
         peak = torch.zeros((N,), dtype=torch.float32, device=wave.device)
         check(self.lib.rfx_pcm16(wave.data_ptr(), N, channels, L, int(normalize), peak.data_ptr(), pcm.data_ptr(), self._stream()))
         return pcm, peak
+
+    # ---- int16 post-processing (rfx_pcm.hip): audio_util.apply_filters / stitch_segments on the device ----------------------
+    def filter_tables(self) -> T.Tuple[torch.Tensor, torch.Tensor]:
+        """The two host-built tables of rfx_pcm16_apply_filters (gain by rms, boost by peak), uploaded once per plan."""
+        from riffusion.util import audio_util
+
+        return (self.device_constant(("pcm_gain_by_rms",), lambda: audio_util.filter_gain_by_rms().copy()),
+                self.device_constant(("pcm_boost_by_peak", 0.1), lambda: audio_util.filter_boost_by_peak().copy()))
+
+    def apply_filters(self, pcm: torch.Tensor, out: T.Optional[torch.Tensor] = None) -> torch.Tensor:
+        """audio_util.apply_filters(compression=False) on every clip of an (N, L, C) int16 batch on this device, byte for byte
+        (audioop's arithmetic; clips of L * C < 2^23 samples).  `out`: destination of the same shape, `pcm` itself for in place;
+        otherwise a fresh tensor."""
+        from riffusion.util import audio_util
+
+        if pcm.dtype != torch.int16 or pcm.dim() != 3:
+            raise ValueError(f"expected an (N, L, C) int16 batch, got {tuple(pcm.shape)} {pcm.dtype}")
+        N, L, C = pcm.shape
+        if L * C >= audio_util.FILTER_EXACT_SAMPLES:
+            raise ValueError(f"clips of {L} x {C} samples: the device filters are exact below 2^23 samples per clip")
+        if out is not None and out.data_ptr() == pcm.data_ptr() and not pcm.is_contiguous():
+            raise ValueError("in place needs a contiguous batch")
+        src = self._chk(pcm)
+        if out is None:
+            out = torch.empty_like(src)
+        elif out.device != self.device or out.dtype != torch.int16 or tuple(out.shape) != (N, L, C) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int16 tensor of shape {(N, L, C)} on {self.device}")
+        if N == 0:
+            return out
+        gain, boost = self.filter_tables()
+        with self._workspace(self.lib.rfx_pcm16_filters_workspace_bytes(N, L, C)) as ws:
+            check(self.lib.rfx_pcm16_apply_filters(src.data_ptr(), N, L, C, gain.data_ptr(), boost.data_ptr(), out.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    def stitch(self, pcm: torch.Tensor, frame_rate: int, crossfade_s: float) -> torch.Tensor:
+        """audio_util.stitch_segments of the N clips of an (N, L, C) int16 batch on this device -> (frames, C) int16, byte for
+        byte: audio_util.stitch_plan resolves pydub's millisecond arithmetic on the host, one kernel writes the samples."""
+        from riffusion.util import audio_util
+
+        if pcm.dtype != torch.int16 or pcm.dim() != 3:
+            raise ValueError(f"expected an (N, L, C) int16 batch, got {tuple(pcm.shape)} {pcm.dtype}")
+        pcm = self._chk(pcm)
+        N, L, C = pcm.shape
+        pieces, frames = audio_util.stitch_plan(N, L, frame_rate, crossfade_s)
+        host = torch.from_numpy(pieces.view(np.uint8))
+        dev = host.to(self.device)
+        out = torch.empty((frames, C), dtype=torch.int16, device=self.device)
+        check(self.lib.rfx_pcm16_stitch(pcm.data_ptr(), N, L, C, host.data_ptr(), dev.data_ptr(), len(pieces), frames, out.data_ptr(),
+                                        self._stream()))
+        return out
 
 
 # Plans are cached, least recently used first out: a plan pins its tables on the device (the dense filterbank alone is

@@ -137,8 +137,11 @@ class SpectrogramConverter:
         waveform = self._waveform_from_mel(plan, amplitudes_mel)
         # peak-normalise + int16 truncation on the device (audio_util.py:22-28), one D2H of int16
         pcm, _ = plan.pcm16(waveform, channels=waveform.shape[0], normalize=True)
+        host_filters = apply_filters and pcm.shape[1] * pcm.shape[2] >= audio_util.FILTER_EXACT_SAMPLES
+        if apply_filters and not host_filters:  # audio_util.apply_filters on the device, same bytes (rfx_pcm16_apply_filters)
+            plan.apply_filters(pcm, out=pcm)
         segment = audio_util.segment_from_pcm16(pcm[0].cpu().numpy(), self.p.sample_rate)
-        if apply_filters:
+        if host_filters:  # a clip of 2^23 samples or more: audioop's double sum of squares is no longer exact to mirror
             segment = audio_util.apply_filters(segment, compression=False)
         return segment
 

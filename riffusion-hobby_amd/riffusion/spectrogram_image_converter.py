@@ -57,16 +57,77 @@ class SpectrogramImageConverter:
         apply_filters: bool = True,
         max_value: float = 30e6,
     ) -> T.Any:
-        """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference)."""
+        """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference).  The filters
+        (audio_util.apply_filters, compression=False) run on the device: same bytes."""
         pcm = self.audio_from_spectrogram_images(
-            np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value
+            np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters
         )
-        segment = audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
-        if apply_filters:
-            segment = audio_util.apply_filters(segment, compression=False)
-        return segment
+        return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
 
     # ---- batch entry points ------------------------------------------------------------------------------
+    def _filter_pcm(self, plan: T.Any, pcm: torch.Tensor) -> torch.Tensor:
+        """audio_util.apply_filters on each clip of an (n, L, C) int16 device batch, in place: on the device where its arithmetic
+        equals audioop's (L * C < 2^23), otherwise on the host, clip by clip."""
+        _, L, C = pcm.shape
+        if L * C < audio_util.FILTER_EXACT_SAMPLES:
+            return plan.apply_filters(pcm, out=pcm)
+        host = pcm.cpu().numpy()
+        for i in range(host.shape[0]):
+            seg = audio_util.apply_filters(audio_util.PcmSegment(host[i], self.p.sample_rate), compression=False)
+            host[i] = seg.get_array_of_samples().reshape(L, C)
+        pcm.copy_(torch.from_numpy(host))
+        return pcm
+
+    def audio_from_spectrogram_image_sequence(
+        self,
+        images: T.Any,
+        crossfade_s: float = 0.2,
+        apply_filters: bool = True,
+        max_value: float = 30e6,
+        seed: T.Optional[int] = None,
+        tiles_per_call: int = 64,
+        return_device: bool = False,
+    ) -> T.Any:
+        """
+        A sequence of tiles -> ONE audio segment: every tile decoded (`audio_from_spectrogram_images`), filtered
+        (`apply_filters`, on the device) and the clips joined with `crossfade_s` of crossfade - the reference's audio-to-audio
+        (crossfade 0.2 s) and interpolation (crossfade 0) consumers, streamlit/tasks/audio_to_audio.py:323-324 and
+        interpolation.py:177-181.  Byte for byte
+        `audio_util.stitch_segments([audio_util.apply_filters(clip) for clip in audio_from_spectrogram_images(images, seed=seed)],
+        crossfade_s)`; the stitch runs on the device too (rfx_pcm16_stitch, from audio_util.stitch_plan's pieces).
+        `images`: what `audio_from_spectrogram_images` takes, or a sequence of PIL images of one size.  Raises append's ValueError
+        when the crossfade is longer than a clip; one tile gives that clip.  Returns a pydub segment when pydub is importable,
+        else a PcmSegment; with `return_device=True` the (frames, C) int16 tensor on the GPU.  All clips are stitched in this
+        process: there is no `group`.
+        """
+        if isinstance(images, (list, tuple)):
+            images = np.stack([np.asarray(image_util.rgb_array_from_image(im)) if isinstance(im, Image.Image) else np.asarray(im)
+                               for im in images])
+        n = int(images.shape[0])
+        if n < 1:
+            raise ValueError("audio_from_spectrogram_image_sequence needs at least one image")
+        plan = self.converter._plan()
+        L = plan.lib.rfx_griffinlim_output_samples(plan.handle, int(images.shape[2]))
+        C = 2 if self.p.stereo else 1
+        try:  # the lengths alone decide whether the stitch can be planned: before any GPU work
+            audio_util.stitch_plan(n, L, self.p.sample_rate, crossfade_s)
+            on_device = True
+        except audio_util.StitchNotPlannable:  # a crossfade that reaches into the previous one: pydub's own loop, on the host
+            on_device = False
+        pcm = self.audio_from_spectrogram_images(images, max_value=max_value, seed=seed, tiles_per_call=tiles_per_call,
+                                                 return_device=True, apply_filters=apply_filters)
+        if n == 1:
+            joined = pcm[0]
+        elif on_device:
+            joined = plan.stitch(pcm, self.p.sample_rate, crossfade_s)
+        else:
+            segs = [audio_util.PcmSegment(clip, self.p.sample_rate) for clip in pcm.cpu().numpy()]
+            joined = torch.from_numpy(audio_util.stitch_segments(segs, crossfade_s).get_array_of_samples().reshape(-1, C).copy())
+            joined = joined.to(plan.device)
+        if return_device:
+            return joined
+        return audio_util.segment_from_pcm16(joined.cpu().numpy(), self.p.sample_rate)
+
     def spectrogram_images_from_waveforms(self, waveforms: torch.Tensor) -> T.Tuple[T.List[Image.Image], np.ndarray]:
         """(N, C, samples) float waveforms at int16 scale -> N RGB images and their float32 MAX_VALUEs."""
         conv = self.converter
@@ -107,6 +168,7 @@ class SpectrogramImageConverter:
         return_device: bool = False,
         validate: T.Optional[bool] = None,
         return_range_flag: bool = False,
+        apply_filters: bool = False,
     ) -> T.Union[np.ndarray, torch.Tensor, T.Tuple[torch.Tensor, torch.Tensor]]:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -141,11 +203,17 @@ class SpectrogramImageConverter:
         the clip's global row, and nothing in the kernels' arithmetic depends on the batch a clip travels in).  Without one the
         seed is drawn from torch's global generator, like the reference's random starts (in a group: pass a seed, or seed
         torch identically on every rank).
+        `apply_filters=True` gives every clip the reference's post-processing (audio_util.apply_filters, compression=False:
+        gain to -12 dBFS, peak normalisation with 0.1 dB headroom) on the device, byte for byte, before the clip leaves the GPU
+        (rfx_pcm16_apply_filters; clips of 2^23 samples or more - over three minutes - are filtered on the host instead).  It
+        works per clip, so a clip's bytes still do not depend on the chunking or the sharding; not with `return_waveform`.
         """
         from riffusion import batch_shard
 
         if tiles_per_call < 1:
             raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        if return_waveform and apply_filters:
+            raise ValueError("apply_filters works on int16 PCM: it does not go with return_waveform=True")
         if return_range_flag and not return_device:
             raise ValueError("return_range_flag goes with return_device=True (a host result raises on a failed range check instead)")
         if gather is None:
@@ -196,6 +264,8 @@ class SpectrogramImageConverter:
                     dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
                     out = plan.audio_from_image(source.get(i), self.p.stereo, lut, self.p.num_griffin_lim_iters, 0.99, seed=base_seed,
                                                 normalize=True, out=dst, clip_base=a, magnitude_hint=max_value)[0]
+                    if apply_filters:
+                        out = self._filter_pcm(plan, out)
                 # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them
                 source.prefetch(i + 1)
                 sink.put(a - lo, b - lo, out)

@@ -16,7 +16,9 @@ reference's; the numpy restatements below it are used only where audioop is gone
 tests/test_host_logic.py pins them against audioop bit for bit.  What remains from memory is
 pydub 0.25.1's glue around those calls (which audioop function, which factor), cited per method.
 """
+import functools
 import io
+import math
 import typing as T
 
 import numpy as np
@@ -319,6 +321,169 @@ def stitch_segments(segments: T.Sequence[T.Any], crossfade_s: float) -> T.Any:
     for seg in segments[1:]:
         out = out.append(seg, crossfade=crossfade_ms)
     return out
+
+
+# ---- the same two operations on the device (riffusion/_hip.py Plan.apply_filters / Plan.stitch, csrc/rfx_pcm.hip) -------------
+# The device reproduces the audioop arithmetic above byte for byte.  What it cannot reproduce bit for bit - Python's pow and
+# log - is tabulated here, and what is pydub's millisecond bookkeeping - the lengths of append's slices and fades - is planned
+# here, from lengths alone.
+
+FILTER_TABLE_SIZE = 32769  # audioop.rms and audioop.max of 16-bit samples lie in 0..32768
+FILTER_EXACT_SAMPLES = 1 << 23  # the device filters equal audioop's while a clip holds fewer samples (L * C) than this
+
+
+@functools.lru_cache(maxsize=None)
+def filter_gain_by_rms() -> np.ndarray:
+    """Factor of apply_gain(-12 - dBFS) for every audioop.rms value, with PcmSegment's expressions (dBFS = -inf for rms 0:
+    entry 0 is inf)."""
+    out = np.empty(FILTER_TABLE_SIZE, dtype=np.float64)
+    for rms in range(FILTER_TABLE_SIZE):
+        dbfs = float("-inf") if rms == 0 else 20.0 * math.log(rms / PcmSegment.max_possible_amplitude, 10)
+        out[rms] = 10 ** (float(-12 - dbfs) / 20)
+    out.flags.writeable = False
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def filter_boost_by_peak(headroom: float = 0.1) -> np.ndarray:
+    """Factor of normalize(headroom) for every audioop.max value, with PcmSegment's expressions (a silent segment is returned
+    unchanged: entry 0 is 1.0)."""
+    out = np.empty(FILTER_TABLE_SIZE, dtype=np.float64)
+    out[0] = 1.0
+    target_peak = PcmSegment.max_possible_amplitude * (10 ** (-float(headroom) / 20))
+    for peak in range(1, FILTER_TABLE_SIZE):
+        out[peak] = 10 ** (float(20 * math.log(target_peak / peak, 10)) / 20)
+    out.flags.writeable = False
+    return out
+
+
+# one piece of a stitched output: include/rfx.h rfx_stitch_piece (csrc/rfx_pcm_core.h PcmPiece)
+STITCH_PIECE_DTYPE = np.dtype([("out_start", "<i8"), ("a_off", "<i8"), ("b_off", "<i8"), ("a_gain", "<f8"), ("b_gain", "<f8"),
+                               ("a_clip", "<i4"), ("b_clip", "<i4"), ("kind", "<i4"), ("reserved", "<i4")])
+
+
+class StitchNotPlannable(NotImplementedError):
+    """A crossfade that reaches back into the previous crossfade (clips shorter than about two crossfades): the pieces of one
+    pass cannot describe it."""
+
+
+def stitch_plan(n_clips: int, frames: int, frame_rate: int, crossfade_s: float) -> T.Tuple[np.ndarray, int]:
+    """
+    `stitch_segments` of `n_clips` clips of `frames` frames each, planned from the lengths alone: the pieces the device stitch
+    (rfx_pcm16_stitch) writes the output from, and the output's length in frames.  It follows PcmSegment.append step by step -
+    lengths rounded to whole milliseconds, slices at int(ms * (rate / 1000.0)), frames past the last whole millisecond dropped,
+    silence where a slice runs past the data, fades of more than 100 ms stepped once per millisecond and shorter ones once per
+    frame - and every gain is evaluated here, with append's own `from_power + scale_step * i`.  Raises append's ValueError when
+    the crossfade is longer than a clip, and StitchNotPlannable when a crossfade would read a previous one.
+    """
+    n_clips, frames, rate = int(n_clips), int(frames), int(frame_rate)
+    if n_clips < 1 or frames < 1 or rate < 1:
+        raise ValueError("stitch_plan needs at least one clip of at least one frame")
+    crossfade = int(crossfade_s * 1000)
+    if crossfade < 0:
+        raise ValueError(f"crossfade must not be negative, got {crossfade_s}")
+    per_ms = rate / 1000.0
+
+    def len_ms(n: int) -> int:  # PcmSegment.__len__
+        return int(round(1000.0 * (n / float(rate))))
+
+    def pos(ms: int) -> int:  # PcmSegment._parse_position of a position in [0, len]
+        return int(ms * per_ms)
+
+    def check_missing(missing: int) -> None:  # PcmSegment._slice_ms
+        if missing > 2 * per_ms:
+            raise ValueError(f"slice is missing {missing} frames (pydub: TooManyMissingFrames)")
+
+    def fade(n: int, from_gain: float, to_gain: float) -> T.Tuple[int, np.ndarray, np.ndarray]:
+        """PcmSegment._fade of an n-frame slice: (output frames, first frame of each gain step, gain of each step)."""
+        duration = len_ms(n)
+        from_power = 10 ** (float(from_gain) / 20)
+        gain_delta = 10 ** (float(to_gain) / 20) - from_power
+        if duration > 100:
+            scale_step = gain_delta / duration
+            starts = (np.arange(duration, dtype=np.float64) * per_ms).astype(np.int64)
+            for i in range(duration):  # each one-millisecond slice s[i:i+1] is padded with silence where it runs past the data
+                check_missing(max(0, pos(i + 1) - pos(i)) - max(0, min(pos(i + 1), n) - pos(i)))
+            return pos(duration), starts, from_power + scale_step * np.arange(duration, dtype=np.float64)
+        fade_frames = duration * per_ms
+        scale_step = gain_delta / fade_frames if fade_frames else 0.0
+        count = min(int(fade_frames), n)  # s[i:i+1] past the data is empty here: no padding
+        return count, np.arange(count, dtype=np.int64), from_power + scale_step * np.arange(count, dtype=np.float64)
+
+    # the output so far: ("copy", start, length, clip, offset) runs (clip -1: silence) and ("fade", start, length, pieces) blocks
+    out: T.List[T.Tuple[T.Any, ...]] = [("copy", 0, frames, 0, 0)]
+    total = frames
+    for k in range(1, n_clips):
+        if not crossfade:
+            out.append(("copy", total, frames, k, 0))
+            total += frames
+            continue
+        A, A2 = len_ms(total), len_ms(frames)
+        if crossfade > A:
+            raise ValueError(f"Crossfade is longer than the original AudioSegment ({crossfade}ms > {A}ms)")
+        if crossfade > A2:
+            raise ValueError(f"Crossfade is longer than the appended AudioSegment ({crossfade}ms > {A2}ms)")
+        b1, bA = pos(A - crossfade), pos(A)  # head = out[:b1]; fade-out slice s1 = out[b1:bA], silence past `total`
+        n1 = max(0, bA - b1)
+        check_missing(n1 - max(0, min(bA, total) - b1))
+        cf, bA2 = pos(crossfade), pos(A2)  # fade-in slice s2 = seg[:cf]; tail = seg[cf:bA2]
+        check_missing(cf - min(cf, frames))
+        if bA2 > cf:
+            check_missing((bA2 - cf) - max(0, min(bA2, frames) - cf))
+        xo, starts_o, gains_o = fade(n1, 0, -120)
+        xi, starts_i, gains_i = fade(cf, -120, 0)
+        n = min(xo, xi)  # overlay: the fade-in is added over the first n frames, the result keeps the fade-out's length
+        # the fade-out reads these runs of `out` (positions relative to b1)
+        src_a: T.List[T.Tuple[int, int, int, int]] = []  # (first, length, clip, offset of that first frame)
+        while out and out[-1][1] + out[-1][2] > b1:
+            entry = out.pop()
+            if entry[0] == "fade":
+                raise StitchNotPlannable("a crossfade longer than half a clip reaches into the previous crossfade")
+            _, start, length, clip, off = entry
+            if start < b1:  # the head keeps the first part of this run
+                out.append(("copy", start, b1 - start, clip, off))
+                off, length, start = off + (b1 - start), length - (b1 - start), b1
+            src_a.append((start - b1, length, clip, off))
+        src_a.reverse()
+        if xo:
+            edges = [e for first, length, _, _ in src_a for e in (first, first + length)]
+            bounds = [starts_o, starts_i[starts_i < n], np.array(edges + [n1, n, cf, frames], dtype=np.int64)]
+            p0 = np.unique(np.concatenate(bounds))
+            p0 = p0[(p0 >= 0) & (p0 < xo)]
+            if not len(p0) or p0[0] != 0:
+                p0 = np.concatenate([np.zeros(1, np.int64), p0])
+            pieces = np.zeros(len(p0), dtype=STITCH_PIECE_DTYPE)
+            pieces["out_start"] = b1 + p0
+            pieces["kind"] = 1
+            pieces["a_gain"] = gains_o[np.searchsorted(starts_o, p0, side="right") - 1]
+            pieces["a_clip"] = -1
+            for first, length, clip, off in src_a:  # s1[j] = out[b1 + j] while that exists, silence after
+                sel = (p0 >= first) & (p0 < first + length) & (p0 < n1) & (clip >= 0)
+                pieces["a_clip"][sel] = clip
+                pieces["a_off"][sel] = off + (p0[sel] - first)
+            inb = p0 < n
+            if len(starts_i):
+                pieces["b_gain"][inb] = gains_i[np.searchsorted(starts_i, p0[inb], side="right") - 1]
+            has_b = inb & (p0 < min(cf, frames))  # s2[j] = seg[j], silence past the clip and past the slice
+            pieces["b_clip"] = np.where(has_b, k, -1)
+            pieces["b_off"] = np.where(has_b, p0, 0)
+            out.append(("fade", b1, xo, pieces))
+        total = b1 + xo
+        if bA2 > cf:
+            if min(bA2, frames) > cf:
+                out.append(("copy", total, min(bA2, frames) - cf, k, cf))
+            if bA2 > frames:
+                out.append(("copy", total + max(0, frames - cf), bA2 - max(cf, frames), -1, 0))
+            total += bA2 - cf
+    parts = []
+    for entry in out:
+        if entry[0] == "fade":
+            parts.append(entry[3])
+        elif entry[2] > 0:
+            piece = np.zeros(1, dtype=STITCH_PIECE_DTYPE)
+            piece["out_start"], piece["a_clip"], piece["a_off"], piece["b_clip"] = entry[1], entry[3], entry[4], -1
+            parts.append(piece)
+    return np.concatenate(parts), total
 
 
 def overlay_segments(segments: T.Sequence[T.Any]) -> T.Any:
