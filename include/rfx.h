@@ -343,6 +343,45 @@ typedef struct {
 int rfx_pcm16_stitch(const int16_t* d_pcm, int N, int L, int C, const rfx_stitch_piece* h_pieces, const rfx_stitch_piece* d_pieces,
                      int n_pieces, int64_t out_frames, int16_t* d_out, void* stream);
 
+/* rfx_pcm16_apply_filters_compressed: apply_filters(segment, compression=True) on every clip of d_pcm_in (N, L, C) int16 ->
+ * d_pcm_out (in place when equal): normalize(0.1), apply_gain(-10 - dBFS), pydub 0.25.1 compress_dynamic_range, then exactly
+ * rfx_pcm16_apply_filters.  Byte for byte audioop's result, for clips of L * C < 2^23 samples (larger ones are refused):
+ *   - the window rms values come from exact int64 prefix sums (audioop's double sums are exact below 2^53);
+ *   - the attenuation recurrence takes pydub's steps - one IEEE add or subtract, compares, selects - on the host-built tables
+ *     of audio_util.compress_tables (every log is evaluated by the host), so its state is bitwise pydub's in both forms;
+ *   - the factor 10^(-att/20) is the device's exp10, which may differ from Python's 10 ** y (libm pow) in its last bits.
+ *     Every product x2 * g within `margin` of an integer is flagged (with a factor error of a few ulp, a product of at most
+ *     2^15 moves by less than 2^-35: 2^-30 is ample) and recomputed on the host with pow, as CPython's float ** does.
+ * The call therefore synchronises `stream` once, to read the flag count (the compression=False entries never do).  When more
+ * than flag_capacity samples were flagged, n_flagged says how many and d_pcm_out is left unwritten (d_pcm_in is intact, also
+ * in place): redo the batch on the host, or again with a larger list.  Workspace: rfx_pcm16_compress_filters_workspace_bytes. */
+typedef enum {
+  RFX_COMPRESS_SEQUENTIAL = 0,  /* one lane per clip runs all L steps: the definition */
+  RFX_COMPRESS_CHUNKED = 1      /* one lane per chunk of a clip, repair rounds until every chunk starts from its predecessor's
+                                   end: the same states, bit for bit */
+} rfx_compress_form;
+typedef struct {
+  uint32_t struct_size;          /* sizeof(rfx_compress_options) */
+  int32_t form;                  /* rfx_compress_form */
+  int32_t look_frames;           /* int(attack ms * rate / 1000): the rms window */
+  int32_t chunk_frames;          /* chunked form: frames per chunk (0 = default); raised until a clip has at most 2048 chunks */
+  const double* d_gain10_by_rms; /* audio_util.filter_gain_by_rms(-10) */
+  const double* d_gain12_by_rms; /* audio_util.filter_gain_by_rms() */
+  const double* d_boost_by_peak; /* audio_util.filter_boost_by_peak(0.1) */
+  const uint8_t* d_above;        /* audio_util.compress_tables: above, max_att, inc, dec (32769 entries each) */
+  const double* d_max_att;
+  const double* d_inc;
+  const double* d_dec;
+  double margin;                 /* flag products within this distance of an integer (>= 0; 0.5 or more flags every one) */
+  void* d_flags;                 /* flag_capacity entries of 24 bytes (device memory) */
+  int64_t flag_capacity;
+  int32_t* d_rounds;             /* optional (NULL): N ints, the repair rounds each clip took (0 for the sequential form) */
+  int64_t n_flagged;             /* out: samples flagged by this call */
+} rfx_compress_options;
+size_t rfx_pcm16_compress_filters_workspace_bytes(int N, int L, int C);
+int rfx_pcm16_apply_filters_compressed(const int16_t* d_pcm_in, int N, int L, int C, rfx_compress_options* options, int16_t* d_pcm_out,
+                                       void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- inverse, all the way from the image: SpectrogramImageConverter.audio_from_spectrogram_image's device half
  * (spectrogram_image_converter.py:54-91: image_util.spectrogram_from_image, audio_from_spectrogram -> waveform_from_mel_amplitudes
  * on the image's (C, n_mels, T) tensor, audio_util.audio_from_waveform).  d_img (N, n_mels, T, 3) uint8 -> d_pcm_out (N, L, C) int16,

@@ -11,6 +11,7 @@
 
 #include "../../include/rfx.h"
 #include "rfx_kernels.h"
+#include "rfx_compress_core.h"
 #include "rfx_pcm_core.h"
 
 using namespace rfx;
@@ -1769,6 +1770,57 @@ int rfx_pcm16_stitch(const int16_t* d_pcm, int N, int L, int C, const rfx_stitch
   if (int rc = device_of(d_out, &dev)) return rc;
   RFX_ON_DEVICE(dev);
   RFX_HIP(launch_pcm_stitch(d_pcm, L, C, d_pieces, n_pieces, out_frames, d_out, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+size_t rfx_pcm16_compress_filters_workspace_bytes(int N, int L, int C) {
+  if (N <= 0 || L <= 0 || C <= 0) return 0;
+  return cmp_workspace_layout(N, L, C).total;
+}
+
+int rfx_pcm16_apply_filters_compressed(const int16_t* d_pcm_in, int N, int L, int C, rfx_compress_options* o, int16_t* d_pcm_out,
+                                       void* d_workspace, size_t workspace_bytes, void* stream) {
+  static_assert(sizeof(CmpFlag) == 24, "rfx_compress_options.d_flags entries are CmpFlag (rfx_compress_core.h)");
+  if (!d_pcm_in || !o || !d_pcm_out || !d_workspace || N <= 0 || L <= 0 || C <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters_compressed: bad argument");
+  if (o->struct_size != sizeof(rfx_compress_options))
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters_compressed: options->struct_size is not sizeof(rfx_compress_options)");
+  if (!o->d_gain10_by_rms || !o->d_gain12_by_rms || !o->d_boost_by_peak || !o->d_above || !o->d_max_att || !o->d_inc || !o->d_dec)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters_compressed: a table is missing");
+  if ((o->form != RFX_COMPRESS_SEQUENTIAL && o->form != RFX_COMPRESS_CHUNKED) || o->look_frames < 0 || o->chunk_frames < 0 ||
+      !(o->margin >= 0.0) || o->flag_capacity < 0 || (o->flag_capacity > 0 && !o->d_flags))
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters_compressed: bad option");
+  if ((int64_t)L * C >= ((int64_t)1 << 23))
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_pcm16_apply_filters_compressed: L * C >= 2^23 (audioop.rms is exact only below that)");
+  const CmpLayout w = cmp_workspace_layout(N, L, C);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_pcm16_apply_filters_compressed: workspace too small");
+  int dev;
+  if (int rc = device_of(d_pcm_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  const hipStream_t s = (hipStream_t)stream;
+  RFX_HIP(launch_cmp_compress(d_pcm_in, N, L, C, o->d_boost_by_peak, o->d_gain10_by_rms, o->d_above, o->d_max_att, o->d_inc, o->d_dec,
+                              o->look_frames, o->form, o->chunk_frames, o->margin, o->d_flags, o->flag_capacity, o->d_rounds, d_workspace, s));
+  // the one synchronisation of this path: how many products need the host's pow
+  unsigned long long n = 0;
+  RFX_HIP(hipMemcpyAsync(&n, (char*)d_workspace + w.count, sizeof n, hipMemcpyDeviceToHost, s));
+  RFX_HIP(hipStreamSynchronize(s));
+  o->n_flagged = (int64_t)n;
+  if ((int64_t)n > o->flag_capacity) return RFX_OK;  // documented: d_pcm_out is not written, the caller redoes the batch on the host
+  int16_t* x3 = reinterpret_cast<int16_t*>((char*)d_workspace + w.x3);
+  if (n > 0) {
+    std::vector<CmpFlag> h(n);
+    RFX_HIP(hipMemcpyAsync(h.data(), o->d_flags, n * sizeof(CmpFlag), hipMemcpyDeviceToHost, s));
+    RFX_HIP(hipStreamSynchronize(s));
+    const int64_t total = (int64_t)N * L * C;
+    for (CmpFlag& f : h) {
+      if (f.index < 0 || f.index >= total) return fail(RFX_ERR_HIP, "rfx_pcm16_apply_filters_compressed: corrupt flag list");
+      f.value = pcm_mul(f.x2, cmp_gain_host(f.att));
+    }
+    RFX_HIP(hipMemcpyAsync(o->d_flags, h.data(), n * sizeof(CmpFlag), hipMemcpyHostToDevice, s));
+    RFX_HIP(launch_cmp_scatter(o->d_flags, (int64_t)n, x3, s));
+    RFX_HIP(hipStreamSynchronize(s));  // h is released on return
+  }
+  RFX_HIP(launch_pcm_filters(x3, N, L, C, o->d_gain12_by_rms, o->d_boost_by_peak, d_pcm_out, (char*)d_workspace + w.filters, s));
   return RFX_OK;
 }
 

@@ -391,5 +391,25 @@ hipError_t launch_pcm_filters(const int16_t* in, int N, int L, int C, const doub
                               int16_t* out, void* workspace, hipStream_t s);
 hipError_t launch_pcm_stitch(const int16_t* pcm, int64_t L, int C, const void* pieces, int n_pieces, int64_t frames, int16_t* out,
                              hipStream_t s);
+// the filters' statistics pass on its own: partials[clip * pcm_splits(count) + part] over clips of `count` samples
+struct PcmPartial {  // one statistics workgroup's share of a clip
+  int64_t sumsq;
+  int32_t xmax, xmin;
+};
+int pcm_splits(int64_t count);
+hipError_t launch_pcm_stats(const int16_t* in, int N, int64_t count, PcmPartial* partials, hipStream_t s);
+// apply_filters(compression=True) up to the compressor's output (rfx_compress.hip, arithmetic in rfx_compress_core.h):
+// normalize, gain to -10 dBFS, window rms, the attenuation recurrence (form 0 sequential, 1 chunked), and the apply with its
+// flags, into the workspace's x3 (the input is not written); the caller patches the flagged samples and runs
+// launch_pcm_filters from x3 to its output.  Layout of the workspace: cmp_workspace_layout.
+struct CmpLayout {
+  size_t partials, factors, traj, rms, x3, count, filters, total;  // byte offsets, and the size
+};
+CmpLayout cmp_workspace_layout(int N, int L, int C);
+hipError_t launch_cmp_compress(const int16_t* in, int N, int L, int C, const double* boost_by_peak, const double* gain10_by_rms,
+                               const uint8_t* above, const double* max_att, const double* inc, const double* dec, int look_frames,
+                               int form, int chunk_frames, double margin, void* flags, int64_t flag_capacity, int32_t* rounds,
+                               void* workspace, hipStream_t s);
+hipError_t launch_cmp_scatter(const void* flags, int64_t n, int16_t* out, hipStream_t s);
 
 }  // namespace rfx

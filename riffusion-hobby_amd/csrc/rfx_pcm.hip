@@ -18,17 +18,12 @@ constexpr int kPcmThreads = 256;
 constexpr int64_t kPcmSplitSamples = 32768;  // samples of one clip per statistics workgroup (64 KB of int16)
 constexpr int kPcmMaxSplits = 64;
 
-struct PcmPartial {  // one statistics workgroup's share of a clip
-  int64_t sumsq;
-  int32_t xmax, xmin;
-};
+}  // namespace
 
 int pcm_splits(int64_t count) {
   int64_t s = (count + kPcmSplitSamples - 1) / kPcmSplitSamples;
   return (int)(s < 1 ? 1 : (s > kPcmMaxSplits ? kPcmMaxSplits : s));
 }
-
-}  // namespace
 
 // ---- statistics: workgroup (clip, part) reduces samples [begin, end) of the clip; 16-byte loads over the aligned middle
 __global__ void __launch_bounds__(kPcmThreads) pcm_stats_kernel(const int16_t* __restrict__ pcm, int64_t count, int splits,
@@ -171,6 +166,12 @@ hipError_t launch_pcm_filters(const int16_t* in, int N, int L, int C, const doub
   if ((reinterpret_cast<uintptr_t>(in) & 1) || ((reinterpret_cast<uintptr_t>(in) ^ reinterpret_cast<uintptr_t>(out)) & 15)) head = total;
   if (head > total) head = total;
   hipLaunchKernelGGL(pcm_apply_kernel, dim3(pcm_grid((total - head + 7) / 8)), dim3(kPcmThreads), 0, s, in, out, total, count, factors, head);
+  return hipGetLastError();
+}
+
+hipError_t launch_pcm_stats(const int16_t* in, int N, int64_t count, PcmPartial* partials, hipStream_t s) {
+  const int splits = pcm_splits(count);
+  hipLaunchKernelGGL(pcm_stats_kernel, dim3((unsigned)N * splits), dim3(kPcmThreads), 0, s, in, count, splits, partials);
   return hipGetLastError();
 }
 

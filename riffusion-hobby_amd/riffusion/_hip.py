@@ -53,6 +53,23 @@ class RfxPlanOptions(ctypes.Structure):
                 ("frame_engine", ctypes.c_int32), ("plan_layout", ctypes.c_int32), ("imel_form", ctypes.c_int32)]
 
 
+class RfxCompressOptions(ctypes.Structure):
+    """rfx_compress_options of include/rfx.h: rfx_pcm16_apply_filters_compressed's tables, form and flag list."""
+
+    _fields_ = [("struct_size", ctypes.c_uint32), ("form", ctypes.c_int32), ("look_frames", ctypes.c_int32),
+                ("chunk_frames", ctypes.c_int32), ("d_gain10_by_rms", ctypes.c_void_p), ("d_gain12_by_rms", ctypes.c_void_p),
+                ("d_boost_by_peak", ctypes.c_void_p), ("d_above", ctypes.c_void_p), ("d_max_att", ctypes.c_void_p),
+                ("d_inc", ctypes.c_void_p), ("d_dec", ctypes.c_void_p), ("margin", ctypes.c_double), ("d_flags", ctypes.c_void_p),
+                ("flag_capacity", ctypes.c_int64), ("d_rounds", ctypes.c_void_p), ("n_flagged", ctypes.c_int64)]
+
+
+# rfx_compress_form: the recurrence of compress_dynamic_range; chunked is the measured faster form (DESIGN.md 4.4)
+COMPRESS_FORMS = {"sequential": 0, "chunked": 1}
+# products x2 * 10^(-att/20) closer than this to an integer are recomputed with the host's pow (include/rfx.h)
+COMPRESS_MARGIN = 2.0 ** -30
+COMPRESS_FLAG_BYTES = 24
+
+
 class RfxCallOptions(ctypes.Structure):
     """rfx_call_options of include/rfx.h (round 6): per-call options of the inverse entry points."""
 
@@ -143,6 +160,9 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_pcm16_filters_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rfx_pcm16_apply_filters": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_pcm16_stitch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]),
+    "rfx_pcm16_compress_filters_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rfx_pcm16_apply_filters_compressed": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(RfxCompressOptions), c_void_p, c_void_p,
+                                                   c_size_t, c_void_p]),
 }
 
 
@@ -334,6 +354,7 @@ class Plan:
             raise ValueError(f"imel_form must be one of {sorted(IMEL_FORMS)}, got {imel_form!r}")
         self.gl_form = gl_form
         self.device = device
+        self.sample_rate = int(params.sample_rate)
         self.n_fft, self.win_length, self.hop_length = params.n_fft, params.win_length, params.hop_length
         self.n_stft = self.n_fft // 2 + 1
         self.n_mels = params.num_frequencies
@@ -718,10 +739,30 @@ class Plan:
         return (self.device_constant(("pcm_gain_by_rms",), lambda: audio_util.filter_gain_by_rms().copy()),
                 self.device_constant(("pcm_boost_by_peak", 0.1), lambda: audio_util.filter_boost_by_peak().copy()))
 
-    def apply_filters(self, pcm: torch.Tensor, out: T.Optional[torch.Tensor] = None) -> torch.Tensor:
-        """audio_util.apply_filters(compression=False) on every clip of an (N, L, C) int16 batch on this device, byte for byte
+    def compress_tables(self) -> T.Tuple[int, T.Tuple[torch.Tensor, ...]]:
+        """look_frames and the device copies of audio_util.compress_tables at this plan's rate (pydub's defaults), and the
+        -10 dBFS gain table: uploaded once per plan."""
+        from riffusion.util import audio_util
+
+        rate = self.sample_rate
+        look = audio_util.compress_tables(rate)[0]
+        tabs = tuple(self.device_constant(("pcm_compress", rate, i), lambda i=i: audio_util.compress_tables(rate)[i].copy())
+                     for i in range(1, 5))
+        gain10 = self.device_constant(("pcm_gain_by_rms", -10), lambda: audio_util.filter_gain_by_rms(-10).copy())
+        return look, tabs + (gain10,)
+
+    def apply_filters(self, pcm: torch.Tensor, out: T.Optional[torch.Tensor] = None, compression: bool = False, *,
+                      compress_form: str = "chunked", chunk_frames: int = 0, margin: float = COMPRESS_MARGIN,
+                      flag_capacity: int = 1 << 16, stats: T.Optional[dict] = None) -> torch.Tensor:
+        """audio_util.apply_filters(compression) on every clip of an (N, L, C) int16 batch on this device, byte for byte
         (audioop's arithmetic; clips of L * C < 2^23 samples).  `out`: destination of the same shape, `pcm` itself for in place;
-        otherwise a fresh tensor."""
+        otherwise a fresh tensor.
+
+        compression=True (rfx_pcm16_apply_filters_compressed, at this plan's sample rate): `compress_form` "chunked" or
+        "sequential" and `chunk_frames` choose how the compressor's recurrence runs (same bytes); products within `margin` of an
+        integer are recomputed with the host's pow, at most `flag_capacity` of them per call - beyond that the batch is filtered
+        on the host.  This path synchronises the stream once (the flag count).  `stats`, when given, receives "n_flagged",
+        "host_fallback" and "rounds" (the repair rounds per clip, a device tensor)."""
         from riffusion.util import audio_util
 
         if pcm.dtype != torch.int16 or pcm.dim() != 3:
@@ -739,9 +780,36 @@ class Plan:
         if N == 0:
             return out
         gain, boost = self.filter_tables()
+        if compression:
+            return self._apply_filters_compressed(src, out, gain, boost, compress_form, chunk_frames, margin, flag_capacity, stats)
         with self._workspace(self.lib.rfx_pcm16_filters_workspace_bytes(N, L, C)) as ws:
             check(self.lib.rfx_pcm16_apply_filters(src.data_ptr(), N, L, C, gain.data_ptr(), boost.data_ptr(), out.data_ptr(),
                                                    ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    def _apply_filters_compressed(self, src: torch.Tensor, out: torch.Tensor, gain12: torch.Tensor, boost: torch.Tensor, form: str,
+                                  chunk_frames: int, margin: float, flag_capacity: int, stats: T.Optional[dict]) -> torch.Tensor:
+        from riffusion.util import audio_util
+
+        if form not in COMPRESS_FORMS:
+            raise ValueError(f"compress_form must be one of {sorted(COMPRESS_FORMS)}, got {form!r}")
+        N, L, C = src.shape
+        look, (above, max_att, inc, dec, gain10) = self.compress_tables()
+        flags = torch.empty(max(1, flag_capacity) * COMPRESS_FLAG_BYTES, dtype=torch.uint8, device=self.device)
+        rounds = torch.zeros(N, dtype=torch.int32, device=self.device)
+        o = RfxCompressOptions(ctypes.sizeof(RfxCompressOptions), COMPRESS_FORMS[form], look, int(chunk_frames), gain10.data_ptr(),
+                               gain12.data_ptr(), boost.data_ptr(), above.data_ptr(), max_att.data_ptr(), inc.data_ptr(),
+                               dec.data_ptr(), float(margin), flags.data_ptr(), int(flag_capacity), rounds.data_ptr(), 0)
+        with self._workspace(self.lib.rfx_pcm16_compress_filters_workspace_bytes(N, L, C)) as ws:
+            check(self.lib.rfx_pcm16_apply_filters_compressed(src.data_ptr(), N, L, C, ctypes.byref(o), out.data_ptr(), ws.data_ptr(),
+                                                              ws.numel(), self._stream()))
+        fallback = o.n_flagged > flag_capacity
+        if fallback:  # the flag list overflowed: out is unwritten and src intact - this batch is filtered on the host
+            host = src.cpu().numpy()
+            res = np.stack([audio_util.apply_filters(audio_util.PcmSegment(c, self.sample_rate), compression=True)._data for c in host])
+            out.copy_(torch.from_numpy(res))
+        if stats is not None:
+            stats.update(n_flagged=int(o.n_flagged), host_fallback=bool(fallback), rounds=rounds)
         return out
 
     def stitch(self, pcm: torch.Tensor, frame_rate: int, crossfade_s: float) -> torch.Tensor:

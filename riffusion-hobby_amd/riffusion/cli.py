@@ -98,10 +98,13 @@ def _rank_device(device: str) -> str:
 
 
 def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 64, no_filters: bool = False,
-                          device: str = "cuda") -> None:
+                          compression: bool = False, device: str = "cuda") -> None:
     """Decode every *.png of a directory, `batch_size` same-width tiles per GPU call.  Each clip then gets the same
     post-processing as `image-to-audio` (audio_util.apply_filters, reference spectrogram_image_converter.py:65-91, run on the
-    device) unless --no-filters is given."""
+    device) unless --no-filters is given; --compression adds the filters' dynamic range compression (apply_filters with
+    compression=True, also on the device)."""
+    if compression and no_filters:
+        raise ValueError("--compression is a mode of the filters: it does not go with --no-filters")
     os.makedirs(output_dir, exist_ok=True)
     device = _rank_device(device)
     paths = _rank_slice(sorted(glob.glob(os.path.join(image_dir, "*.png"))))
@@ -118,7 +121,7 @@ def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 
                 with Image.open(p) as im:
                     tiles.append(image_util.rgb_array_from_image(im))
             # the filters run on the device, clip by clip, before the batch leaves it (same bytes as audio_util.apply_filters)
-            pcm = converter.audio_from_spectrogram_images(np.stack(tiles), apply_filters=not no_filters)
+            pcm = converter.audio_from_spectrogram_images(np.stack(tiles), apply_filters=not no_filters, compression=compression)
             for path, samples in zip(chunk, pcm):
                 segment = audio_util.PcmSegment(samples, params.sample_rate)
                 out = os.path.join(output_dir, os.path.splitext(os.path.basename(path))[0] + ".wav")

@@ -65,15 +65,15 @@ class SpectrogramImageConverter:
         return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
 
     # ---- batch entry points ------------------------------------------------------------------------------
-    def _filter_pcm(self, plan: T.Any, pcm: torch.Tensor) -> torch.Tensor:
+    def _filter_pcm(self, plan: T.Any, pcm: torch.Tensor, compression: bool = False) -> torch.Tensor:
         """audio_util.apply_filters on each clip of an (n, L, C) int16 device batch, in place: on the device where its arithmetic
         equals audioop's (L * C < 2^23), otherwise on the host, clip by clip."""
         _, L, C = pcm.shape
         if L * C < audio_util.FILTER_EXACT_SAMPLES:
-            return plan.apply_filters(pcm, out=pcm)
+            return plan.apply_filters(pcm, out=pcm, compression=compression)
         host = pcm.cpu().numpy()
         for i in range(host.shape[0]):
-            seg = audio_util.apply_filters(audio_util.PcmSegment(host[i], self.p.sample_rate), compression=False)
+            seg = audio_util.apply_filters(audio_util.PcmSegment(host[i], self.p.sample_rate), compression=compression)
             host[i] = seg.get_array_of_samples().reshape(L, C)
         pcm.copy_(torch.from_numpy(host))
         return pcm
@@ -87,14 +87,15 @@ class SpectrogramImageConverter:
         seed: T.Optional[int] = None,
         tiles_per_call: int = 64,
         return_device: bool = False,
+        compression: bool = False,
     ) -> T.Any:
         """
         A sequence of tiles -> ONE audio segment: every tile decoded (`audio_from_spectrogram_images`), filtered
         (`apply_filters`, on the device) and the clips joined with `crossfade_s` of crossfade - the reference's audio-to-audio
         (crossfade 0.2 s) and interpolation (crossfade 0) consumers, streamlit/tasks/audio_to_audio.py:323-324 and
         interpolation.py:177-181.  Byte for byte
-        `audio_util.stitch_segments([audio_util.apply_filters(clip) for clip in audio_from_spectrogram_images(images, seed=seed)],
-        crossfade_s)`; the stitch runs on the device too (rfx_pcm16_stitch, from audio_util.stitch_plan's pieces).
+        `audio_util.stitch_segments([audio_util.apply_filters(clip, compression) for clip in
+        audio_from_spectrogram_images(images, seed=seed)], crossfade_s)`; the stitch runs on the device too (rfx_pcm16_stitch, from audio_util.stitch_plan's pieces).
         `images`: what `audio_from_spectrogram_images` takes, or a sequence of PIL images of one size.  Raises append's ValueError
         when the crossfade is longer than a clip; one tile gives that clip.  Returns a pydub segment when pydub is importable,
         else a PcmSegment; with `return_device=True` the (frames, C) int16 tensor on the GPU.  All clips are stitched in this
@@ -115,7 +116,7 @@ class SpectrogramImageConverter:
         except audio_util.StitchNotPlannable:  # a crossfade that reaches into the previous one: pydub's own loop, on the host
             on_device = False
         pcm = self.audio_from_spectrogram_images(images, max_value=max_value, seed=seed, tiles_per_call=tiles_per_call,
-                                                 return_device=True, apply_filters=apply_filters)
+                                                 return_device=True, apply_filters=apply_filters, compression=compression)
         if n == 1:
             joined = pcm[0]
         elif on_device:
@@ -169,6 +170,7 @@ class SpectrogramImageConverter:
         validate: T.Optional[bool] = None,
         return_range_flag: bool = False,
         apply_filters: bool = False,
+        compression: bool = False,
     ) -> T.Union[np.ndarray, torch.Tensor, T.Tuple[torch.Tensor, torch.Tensor]]:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -207,11 +209,16 @@ class SpectrogramImageConverter:
         gain to -12 dBFS, peak normalisation with 0.1 dB headroom) on the device, byte for byte, before the clip leaves the GPU
         (rfx_pcm16_apply_filters; clips of 2^23 samples or more - over three minutes - are filtered on the host instead).  It
         works per clip, so a clip's bytes still do not depend on the chunking or the sharding; not with `return_waveform`.
+        `compression=True` (only with `apply_filters=True`) is apply_filters(compression=True): normalize, gain to -10 dBFS and
+        pydub's compress_dynamic_range first, on the device as well (rfx_pcm16_apply_filters_compressed, which synchronises the
+        stream once per chunk of `tiles_per_call` clips).
         """
         from riffusion import batch_shard
 
         if tiles_per_call < 1:
             raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        if compression and not apply_filters:
+            raise ValueError("compression=True is a mode of the filters: it needs apply_filters=True")
         if return_waveform and apply_filters:
             raise ValueError("apply_filters works on int16 PCM: it does not go with return_waveform=True")
         if return_range_flag and not return_device:
@@ -265,7 +272,7 @@ class SpectrogramImageConverter:
                     out = plan.audio_from_image(source.get(i), self.p.stereo, lut, self.p.num_griffin_lim_iters, 0.99, seed=base_seed,
                                                 normalize=True, out=dst, clip_base=a, magnitude_hint=max_value)[0]
                     if apply_filters:
-                        out = self._filter_pcm(plan, out)
+                        out = self._filter_pcm(plan, out, compression)
                 # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them
                 source.prefetch(i + 1)
                 sink.put(a - lo, b - lo, out)

@@ -163,6 +163,15 @@ class PcmSegment:
         target_peak = self.max_possible_amplitude * (10 ** (-float(headroom) / 20))
         return self.apply_gain(20 * math.log(target_peak / peak, 10))
 
+    def compress_dynamic_range(self, threshold: float = -20.0, ratio: float = 4.0, attack: float = 5.0,
+                               release: float = 50.0) -> "PcmSegment":
+        """pydub.effects.compress_dynamic_range (pydub 0.25.1), the same integers: the rms of the `look_frames` input frames
+        before each frame (audioop.rms: exact int64 window sums, floor(sqrt(s / n)) in double), pydub's attenuation recurrence
+        over the values tabulated by rms (compress_tables), and audioop.mul of each frame by 10 ** (-attenuation / 20)."""
+        look, above, max_att, inc, dec = compress_tables(self.frame_rate, threshold, ratio, attack, release)
+        att = compress_attenuation(compress_window_rms(self._data, look), above, max_att, inc, dec)
+        return PcmSegment(compress_apply(self._data, att), self.frame_rate)
+
     # ---- joining clips (pydub AudioSegment.append / fade / overlay), used by stitch_segments / overlay_segments
     def _frames_of_ms(self, ms: float) -> int:
         return int(ms * (self.frame_rate / 1000.0))
@@ -298,10 +307,13 @@ def audio_from_waveform(samples: np.ndarray, sample_rate: int, normalize: bool =
 def apply_filters(segment: T.Any, compression: bool = False) -> T.Any:
     """Gain to -12 dBFS and peak normalisation with 0.1 dB headroom (reference audio_util.py:39-72): pydub /
     audioop integer filters on the host.  pydub segments go through pydub itself; PcmSegment carries a
-    copy of the two filters on the same audioop calls."""
+    copy of the filters on the same audioop calls, compress_dynamic_range included (compression=True: normalize, gain to
+    -10 dBFS and the compressor first)."""
     if isinstance(segment, PcmSegment):
         if compression:
-            raise NotImplementedError("dynamic range compression needs pydub (the hot path calls compression=False)")
+            segment = segment.normalize(headroom=0.1)
+            segment = segment.apply_gain(-10 - segment.dBFS)
+            segment = segment.compress_dynamic_range(threshold=-20.0, ratio=4.0, attack=5.0, release=50.0)
         return segment.apply_gain(-12 - segment.dBFS).normalize(headroom=0.1)
     pydub = _pydub()
     if pydub is None:
@@ -333,14 +345,94 @@ FILTER_EXACT_SAMPLES = 1 << 23  # the device filters equal audioop's while a cli
 
 
 @functools.lru_cache(maxsize=None)
-def filter_gain_by_rms() -> np.ndarray:
-    """Factor of apply_gain(-12 - dBFS) for every audioop.rms value, with PcmSegment's expressions (dBFS = -inf for rms 0:
-    entry 0 is inf)."""
+def filter_gain_by_rms(target: float = -12) -> np.ndarray:
+    """Factor of apply_gain(target - dBFS) for every audioop.rms value, with PcmSegment's expressions (dBFS = -inf for rms 0:
+    entry 0 is inf).  apply_filters uses -12, and -10 before the compressor."""
     out = np.empty(FILTER_TABLE_SIZE, dtype=np.float64)
     for rms in range(FILTER_TABLE_SIZE):
         dbfs = float("-inf") if rms == 0 else 20.0 * math.log(rms / PcmSegment.max_possible_amplitude, 10)
-        out[rms] = 10 ** (float(-12 - dbfs) / 20)
+        out[rms] = 10 ** (float(target - dbfs) / 20)
     out.flags.writeable = False
+    return out
+
+
+# ---- compress_dynamic_range (pydub 0.25.1 effects.py), split at the one sequential part: every window rms is known before the
+# loop (the windows read the compressor's input), so only the attenuation recurrence runs frame after frame.
+
+@functools.lru_cache(maxsize=None)
+def compress_tables(frame_rate: int, threshold: float = -20.0, ratio: float = 4.0, attack: float = 5.0,
+                    release: float = 50.0) -> T.Tuple[int, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """(look_frames, above, max_att, inc, dec) of compress_dynamic_range at this frame rate: for every audioop.rms value
+    0..32768 of a window, pydub's own expressions - above = rms > thresh_rms, max_attenuation = (1 - 1 / ratio) *
+    db_over_threshold(rms), and its per-frame attack increment and release decrement.  The device indexes these tables and
+    evaluates no log."""
+    thresh_rms = PcmSegment.max_possible_amplitude * (10 ** (float(threshold) / 20))  # max_possible_amplitude * db_to_float
+    attack_frames = attack * (frame_rate / 1000.0)  # seg.frame_count(ms=attack)
+    release_frames = release * (frame_rate / 1000.0)
+    look_frames = int(attack_frames)
+    above = np.zeros(FILTER_TABLE_SIZE, dtype=np.uint8)
+    max_att, inc, dec = (np.empty(FILTER_TABLE_SIZE, dtype=np.float64) for _ in range(3))
+    for rms in range(FILTER_TABLE_SIZE):
+        if rms == 0:
+            db_over = 0.0
+        else:
+            db = 20 * math.log(float(rms / thresh_rms), 10)  # ratio_to_db
+            db_over = max(db, 0)
+        m = (1 - (1.0 / ratio)) * db_over
+        above[rms] = rms > thresh_rms
+        max_att[rms], inc[rms], dec[rms] = m, m / attack_frames, m / release_frames
+    for t in (above, max_att, inc, dec):
+        t.flags.writeable = False
+    return look_frames, above, max_att, inc, dec
+
+
+def compress_window_rms(x: np.ndarray, look_frames: int) -> np.ndarray:
+    """audioop.rms of seg.get_sample_slice(i - look_frames, i) for every frame i of an (L, C) int16 clip: frames
+    [max(0, i - look), i), channels interleaved, 0 for an empty window.  The window sums are exact int64 prefix differences
+    (audioop sums the squares in double, exact below 2^53)."""
+    L, C = x.shape
+    energy = (x.astype(np.int64) ** 2).sum(axis=1)
+    prefix = np.zeros(L + 1, dtype=np.int64)
+    np.cumsum(energy, out=prefix[1:])
+    i = np.arange(L, dtype=np.int64)
+    lo = np.maximum(i - look_frames, 0)
+    n = (i - lo) * C
+    s = (prefix[i] - prefix[lo]).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rms = np.sqrt(s / n.astype(np.float64))
+    return np.where(n > 0, rms, 0.0).astype(np.uint32)
+
+
+def compress_attenuation(rms: np.ndarray, above: np.ndarray, max_att: np.ndarray, inc: np.ndarray, dec: np.ndarray) -> np.ndarray:
+    """pydub's attenuation recurrence over the per-frame window rms values -> the attenuation after each frame (float64).
+    Python's min / max: min(a, m) is a unless m < a, max(a, 0) is a unless 0 > a."""
+    above_l, m_l, inc_l, dec_l = (above.astype(bool).tolist(), max_att.tolist(), inc.tolist(), dec.tolist())
+    att = 0.0
+    out = []
+    append = out.append
+    for r in rms.tolist():
+        m = m_l[r]
+        if above_l[r] and att <= m:
+            att = att + inc_l[r]
+            att = min(att, m)
+        else:
+            att = att - dec_l[r]
+            att = max(att, 0)
+        append(att)
+    return np.array(out, dtype=np.float64)
+
+
+def compress_apply(x: np.ndarray, att: np.ndarray) -> np.ndarray:
+    """Each frame of an (L, C) int16 clip whose attenuation is not 0.0 -> audioop.mul(frame, 2, db_to_float(-attenuation)),
+    the factor 10 ** (-attenuation / 20) evaluated by Python."""
+    out = x.copy()
+    idx = np.flatnonzero(att != 0.0)
+    if idx.size == 0:
+        return out
+    factors = np.array([10 ** (float(-a) / 20) for a in att[idx].tolist()], dtype=np.float64)
+    v = x[idx].astype(np.float64) * factors[:, None]
+    v = np.where(v > 32767.0, 32767.0, np.where(v < -32768.0, -32768.0, v))
+    out[idx] = np.floor(v).astype(np.int16)
     return out
 
 
