@@ -630,20 +630,13 @@ struct WvChunk {
   static constexpr int NT = NP - NF;
   c2 spec[NP];
   c2 mask[NT > 0 ? NT : 1];
-  float a0, s0, a1, s1;  // a1, s1 unused in unit form
-  float m0;              // scaled mel target of filter g
   float C, G;            // the momentum buffer of the group's bin i is C + G i, in units of the STEP (-lr x gradient scale folded in)
 };
 
 template <int NP, int NF, bool UF>
-__device__ __forceinline__ void wv_load(WvChunk<NP, NF, UF>& k, int g, const ImelArgs& a, int frame, int b, int t, unsigned rbase) {
+__device__ __forceinline__ void wv_load(WvChunk<NP, NF, UF>& k, int g, const ImelArgs& a, int frame, unsigned rbase) {
   const ImelTables& tb = a.tb;
   const int f0 = tb.grp_start[g], n = tb.grp_start[g + 1] - f0;
-  k.a0 = tb.lin[g];
-  k.s0 = tb.lin[a.M + g];
-  k.a1 = tb.lin[2 * a.M + g];
-  k.s1 = tb.lin[3 * a.M + g];
-  k.m0 = a.sc * a.mel[((size_t)b * a.M + g) * a.T + t];
   k.C = 0.f;
   k.G = 0.f;
 #pragma unroll
@@ -658,8 +651,8 @@ __device__ __forceinline__ void wv_load(WvChunk<NP, NF, UF>& k, int g, const Ime
   }
 }
 // The step is written phase by phase ACROSS chunks - the compiler keeps the source order of independent instructions: the
-// packed sums of two chunks advance together (four accumulator chains), the scalar tails of four chunks at a time, and the
-// update forms all of a chunk's step pairs before it applies them.
+// packed sums of two chunks advance together (four accumulator chains), the scalar chains of a chunk pair share packed
+// instructions (round 7, imel_wave_kernel), and the update forms all of a chunk's step pairs before it applies them.
 template <int NPA, int NFA, int NPB, int NFB, bool UFA, bool UFB>
 __device__ __forceinline__ void wv_sums2(const WvChunk<NPA, NFA, UFA>& ka, const WvChunk<NPB, NFB, UFB>& kb, c2& SA, c2& QA, c2& SB, c2& QB) {
   static_assert(NPA >= 2 && NPB >= 2, "every chunk holds at least two pairs");
@@ -675,16 +668,51 @@ __device__ __forceinline__ void wv_sums2(const WvChunk<NPA, NFA, UFA>& ka, const
     if (p < NPB) QB = __builtin_elementwise_fma(bc2((float)p), kb.spec[p], QB);
   }
 }
-// step of the pair p: v_p = (vx, vy) + p (w2, w2) with vx = C, vy = C + G, w2 = 2 G
+// step of the pair p: v_p = (C, C + G) + 2p (G, G) - the same bits as p (2 G, 2 G): a power of two commutes with the product, so the
+// chunk needs no w2 = G + G
 template <int NP, int NF, bool UF>
-__device__ __forceinline__ void wv_update(WvChunk<NP, NF, UF>& k, float vx, float vy, float w2) {
-  const c2 base = c2{vx, vy}, s2 = bc2(w2);
+__device__ __forceinline__ void wv_update(WvChunk<NP, NF, UF>& k, float vy) {
+  const c2 base = c2{k.C, vy}, g2 = bc2(k.G);
   c2 v[NP];
   v[0] = base;
 #pragma unroll
-  for (int p = 1; p < NP; ++p) v[p] = __builtin_elementwise_fma(bc2((float)p), s2, base);
+  for (int p = 1; p < NP; ++p) v[p] = __builtin_elementwise_fma(bc2((float)(2 * p)), g2, base);
 #pragma unroll
   for (int p = 0; p < NP; ++p) k.spec[p] = p < NF ? pk_add_clamp(k.spec[p], v[p]) : pk_fma_clamp(k.spec[p], v[p], k.mask[p < NF ? 0 : p - NF]);
+}
+// s = x + y as one plain instruction: two of them feeding the halves of a pair are otherwise merged into a v_pk_add_f32 whose
+// operands the compiler first gathers with two moves
+__device__ __forceinline__ float wv_add(float x, float y) {
+  float s;
+  asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(x), "v"(y));
+  return s;
+}
+// q = 2 h + y as the three-address v_fma_f32 (the two-address v_fmac would need a copy of y to land q in a pair half)
+__device__ __forceinline__ float wv_fma2(float h, float y) {
+  float q;
+  asm("v_fma_f32 %0, 2.0, %1, %2" : "=v"(q) : "v"(h), "v"(y));
+  return q;
+}
+// (x.y, y.x): the high half of one register pair and the low half of the next in one instruction
+__device__ __forceinline__ c2 wv_gather(c2 x, c2 y) {
+  c2 r;
+  asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,0]" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+// The line coefficients and mel targets of the chunk pair (2 j, 2 j + 1), one chunk per half: the per-group scalar chain of a step
+// (A and B, residual, loss, gradient line) runs on both chunks of the pair in one packed instruction (round 7)
+struct WvLines {
+  c2 a0, s0, a1, s1;  // a1, s1 unused in unit form
+  c2 m0;              // scaled mel target of filter g, for the group of each chunk
+};
+__device__ __forceinline__ void wv_load_lines(WvLines& l, int c, int lane, const ImelArgs& a, int b, int t) {
+  const ImelTables& tb = a.tb;
+  const int g0 = imel_wave_group(c, lane), g1 = imel_wave_group(c + 1, lane);
+  l.a0 = c2{tb.lin[g0], tb.lin[g1]};
+  l.s0 = c2{tb.lin[a.M + g0], tb.lin[a.M + g1]};
+  l.a1 = c2{tb.lin[2 * a.M + g0], tb.lin[2 * a.M + g1]};
+  l.s1 = c2{tb.lin[3 * a.M + g0], tb.lin[3 * a.M + g1]};
+  l.m0 = c2{a.sc * a.mel[((size_t)b * a.M + g0) * a.T + t], a.sc * a.mel[((size_t)b * a.M + g1) * a.T + t]};
 }
 // the chunk's bins, unscaled, into the frame's LDS stage (bin order: entry f - f_lo)
 template <int NP, int NF, bool UF>
@@ -868,8 +896,6 @@ __global__ void __launch_bounds__(kImelThreads) __attribute__((amdgpu_waves_per_
 }
 
 #define RFX_WV_CHUNKS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
-#define RFX_WV_LO(X) X(0) X(1) X(2) X(3)
-#define RFX_WV_HI(X) X(4) X(5) X(6) X(7)
 
 template <bool UFH>  // unit form in the upper four chunks (triangles without area normalisation); false: both weights everywhere
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) imel_wave_kernel(ImelArgs a) {
@@ -890,92 +916,99 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   RFX_WV_DECL(0, false) RFX_WV_DECL(1, false) RFX_WV_DECL(2, false) RFX_WV_DECL(3, false)
   RFX_WV_DECL(4, UFH) RFX_WV_DECL(5, UFH) RFX_WV_DECL(6, UFH) RFX_WV_DECL(7, UFH)
 #undef RFX_WV_DECL
-#define RFX_WV_LOAD(c) wv_load(k##c, imel_wave_group(c, lane), a, frame, b, t, rbase);
+#define RFX_WV_LOAD(c) wv_load(k##c, imel_wave_group(c, lane), a, frame, rbase);
   RFX_WV_CHUNKS(RFX_WV_LOAD)
 #undef RFX_WV_LOAD
+  WvLines l0, l1, l2, l3;
+  wv_load_lines(l0, 0, lane, a, b, t);
+  wv_load_lines(l1, 2, lane, a, b, t);
+  wv_load_lines(l2, 4, lane, a, b, t);
+  wv_load_lines(l3, 6, lane, a, b, t);
 
   const float nl = -(a.lr * (-2.0f / (float)(a.C * a.T)));  // the step in units of the gradient scale -2 / (C T), see imel_group_body
   const unsigned mom_s = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, a.momentum));
   __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the zeroed loss words (one wave per workgroup: no barrier needed)
 
   for (int it = 0; it < steps; ++it) {
-    float A0, A1, A2, A3, A4, A5, A6, A7, B0, B1, B2, B3, B4, B5, B6, B7;
-    {  // group sums of chunks 0 - 3 (both weights), then 4 - 7 (unit form: B = S - A)
-      c2 S0, Q0, S1, Q1, S2, Q2, S3, Q3;
+    // Round 7: every scalar of the chain below that a chunk has once per group is computed for the chunk PAIR (2 j, 2 j + 1) in
+    // one packed instruction (the pairs are X01, X23, X45, X67, chunk 2 j in .x).  Contraction is off: each operation is written
+    // as the one instruction the plain form of rounds 4 - 6 compiled to, so the bits are those of rounds 4 - 6.
+#pragma clang fp contract(off)
+    c2 sP01, sP23, sP45, sP67, qP01, qP23, qP45, qP67;
+    {  // packed group sums (S = sum x, Q as in wv_sums2), then their scalar tails s = S.x + S.y, q = 2 (Q.x + Q.y) + S.y: the halves
+       // of ONE register pair meet here, so these stay plain and land in the halves of the chunk pair's registers
+      c2 S0, Q0, S1, Q1, S2, Q2, S3, Q3, S4, Q4, S5, Q5, S6, Q6, S7, Q7;
       wv_sums2(k0, k1, S0, Q0, S1, Q1);
       wv_sums2(k2, k3, S2, Q2, S3, Q3);
-#define RFX_WV_T1(c) const float s##c = S##c.x + S##c.y, h##c = Q##c.x + Q##c.y;
-#define RFX_WV_T2(c) const float q##c = fmaf(2.f, h##c, S##c.y), e##c = k##c.a0 * s##c, g##c = k##c.a1 * s##c;
-#define RFX_WV_T3(c) A##c = fmaf(k##c.s0, q##c, e##c); B##c = fmaf(k##c.s1, q##c, g##c);
-      RFX_WV_LO(RFX_WV_T1) RFX_WV_LO(RFX_WV_T2) RFX_WV_LO(RFX_WV_T3)
-#undef RFX_WV_T2
-#undef RFX_WV_T3
-    }
-    {
-      c2 S4, Q4, S5, Q5, S6, Q6, S7, Q7;
       wv_sums2(k4, k5, S4, Q4, S5, Q5);
       wv_sums2(k6, k7, S6, Q6, S7, Q7);
-#define RFX_WV_T2(c) const float q##c = fmaf(2.f, h##c, S##c.y), e##c = k##c.a0 * s##c;
-#define RFX_WV_T3(c) A##c = fmaf(k##c.s0, q##c, e##c);
-#define RFX_WV_T4(c) B##c = UFH ? s##c - A##c : fmaf(k##c.s1, q##c, k##c.a1 * s##c);
-      RFX_WV_HI(RFX_WV_T1) RFX_WV_HI(RFX_WV_T2) RFX_WV_HI(RFX_WV_T3) RFX_WV_HI(RFX_WV_T4)
-#undef RFX_WV_T1
-#undef RFX_WV_T2
-#undef RFX_WV_T3
-#undef RFX_WV_T4
+#define RFX_WV_T(c0, c1) sP##c0##c1 = c2{wv_add(S##c0.x, S##c0.y), wv_add(S##c1.x, S##c1.y)}; \
+      qP##c0##c1 = c2{wv_fma2(Q##c0.x + Q##c0.y, S##c0.y), wv_fma2(Q##c1.x + Q##c1.y, S##c1.y)};
+      RFX_WV_T(0, 1) RFX_WV_T(2, 3) RFX_WV_T(4, 5) RFX_WV_T(6, 7)
+#undef RFX_WV_T
     }
+    // A = a0 s + s0 q, B = a1 s + s1 q (unit form, chunks 4 - 7: B = s - A)
+    const c2 A01 = __builtin_elementwise_fma(l0.s0, qP01, l0.a0 * sP01), A23 = __builtin_elementwise_fma(l1.s0, qP23, l1.a0 * sP23),
+             A45 = __builtin_elementwise_fma(l2.s0, qP45, l2.a0 * sP45), A67 = __builtin_elementwise_fma(l3.s0, qP67, l3.a0 * sP67);
+    const c2 B01 = __builtin_elementwise_fma(l0.s1, qP01, l0.a1 * sP01), B23 = __builtin_elementwise_fma(l1.s1, qP23, l1.a1 * sP23);
+    const c2 B45 = UFH ? sP45 - A45 : __builtin_elementwise_fma(l2.s1, qP45, l2.a1 * sP45);
+    const c2 B67 = UFH ? sP67 - A67 : __builtin_elementwise_fma(l3.s1, qP67, l3.a1 * sP67);
     // B of group g - 1: the previous lane of an even chunk (wave_shr), the next lane of an odd one (wave_shl); the end lane's
     // predecessor is the previous chunk's group in the lane itself.  Residual of filter g: d0 = (mel_g - A_g) - B_{g-1}
-#define RFX_WV_R1(c) const float r##c = k##c.m0 - A##c;
-    RFX_WV_CHUNKS(RFX_WV_R1)
-#undef RFX_WV_R1
-    const float p0 = wave_shift<kDppWaveShr1>(0.f, B0), p1 = wave_shift<kDppWaveShl1>(B0, B1), p2 = wave_shift<kDppWaveShr1>(B1, B2),
-                p3 = wave_shift<kDppWaveShl1>(B2, B3), p4 = wave_shift<kDppWaveShr1>(B3, B4), p5 = wave_shift<kDppWaveShl1>(B4, B5),
-                p6 = wave_shift<kDppWaveShr1>(B5, B6), p7 = wave_shift<kDppWaveShl1>(B6, B7);
-#define RFX_WV_R2(c) const float d0##c = r##c - p##c;
-    RFX_WV_CHUNKS(RFX_WV_R2)
-#undef RFX_WV_R2
+    // The shifts write over the B they take `old` from (the end lane's value), so p_c lands in the register of B_{c-1}: one chunk
+    // off the pairing.  The subtractions stay plain and pair the residuals again (a packed form costs a move per shift)
+    const c2 r01 = l0.m0 - A01, r23 = l1.m0 - A23, r45 = l2.m0 - A45, r67 = l3.m0 - A67;
+    const c2 d01 = c2{r01.x - wave_shift<kDppWaveShr1>(0.f, B01.x), r01.y - wave_shift<kDppWaveShl1>(B01.x, B01.y)},
+             d23 = c2{r23.x - wave_shift<kDppWaveShr1>(B01.y, B23.x), r23.y - wave_shift<kDppWaveShl1>(B23.x, B23.y)},
+             d45 = c2{r45.x - wave_shift<kDppWaveShr1>(B23.y, B45.x), r45.y - wave_shift<kDppWaveShl1>(B45.x, B45.y)},
+             d67 = c2{r67.x - wave_shift<kDppWaveShr1>(B45.y, B67.x), r67.y - wave_shift<kDppWaveShl1>(B67.x, B67.y)};
 #ifndef RFX_ABL_IMEL_NO_LOSS
-    {  // every filter's residual is owned exactly once; the loss history is kept in the reference's units
-#define RFX_WV_L1(c) const float u##c = a.un * d0##c;
-      RFX_WV_CHUNKS(RFX_WV_L1)
-#undef RFX_WV_L1
-      const float sqa = fmaf(u6, u6, fmaf(u4, u4, fmaf(u2, u2, u0 * u0))), sqb = fmaf(u7, u7, fmaf(u5, u5, fmaf(u3, u3, u1 * u1)));
+    {  // every filter's residual is owned exactly once; the loss history is kept in the reference's units.  The even chunks
+       // accumulate in .x, the odd ones in .y, in the order of rounds 4 - 6
+      const c2 un2 = bc2(a.un);
+      const c2 u01 = un2 * d01, u23 = un2 * d23, u45 = un2 * d45, u67 = un2 * d67;
+      const c2 sq = __builtin_elementwise_fma(u67, u67, __builtin_elementwise_fma(u45, u45, __builtin_elementwise_fma(u23, u23, u01 * u01)));
       // one ds_add_f32 of all 64 lanes into the step's word: the LDS unit adds them (written as asm: the compiler's atomic
       // optimizer would replace a uniform-address atomic by a 64-trip v_readlane loop on the VALU)
-      asm volatile("ds_add_f32 %0, %1" ::"v"(part_lds + 4u * (unsigned)it), "v"(sqa + sqb) : "memory");
+      asm volatile("ds_add_f32 %0, %1" ::"v"(part_lds + 4u * (unsigned)it), "v"(sq.x + sq.y) : "memory");
     }
 #endif
     // From here on the residuals carry the step factor -lr g (n = -lr g d): everything below is linear in them, so the buffer
     // line (C, G) is kept in step units and needs no further scaling
-#define RFX_WV_N0(c) const float n0##c = nl * d0##c;
-    RFX_WV_CHUNKS(RFX_WV_N0)
-#undef RFX_WV_N0
+    const c2 nl2 = bc2(nl);
+    const c2 n001 = nl2 * d01, n023 = nl2 * d23, n045 = nl2 * d45, n067 = nl2 * d67;
     // residual of filter g + 1 = that of the next group: the next lane of an even chunk, the previous lane of an odd one, the
     // following chunk's in the end lane; filter 512 does not exist (chunk 7, lane 0: zero)
-    const float n10 = wave_shift<kDppWaveShl1>(n01, n00), n11 = wave_shift<kDppWaveShr1>(n02, n01), n12 = wave_shift<kDppWaveShl1>(n03, n02),
-                n13 = wave_shift<kDppWaveShr1>(n04, n03), n14 = wave_shift<kDppWaveShl1>(n05, n04), n15 = wave_shift<kDppWaveShr1>(n06, n05),
-                n16 = wave_shift<kDppWaveShl1>(n07, n06), n17 = wave_shift<kDppWaveShr1>(0.f, n07);
-    // gradient line of every chunk: bin i of the group gets cc + st i (both weights: chunks 0 - 3; unit form: 4 - 7)
-    const float dd4 = n04 - n14, dd5 = n05 - n15, dd6 = n06 - n16, dd7 = n07 - n17;
-    const float x0 = n00 * k0.a0, x1 = n01 * k1.a0, x2 = n02 * k2.a0, x3 = n03 * k3.a0;
-    const float y0 = n00 * k0.s0, y1 = n01 * k1.s0, y2 = n02 * k2.s0, y3 = n03 * k3.s0;
-    const float cc0 = fmaf(n10, k0.a1, x0), cc1 = fmaf(n11, k1.a1, x1), cc2 = fmaf(n12, k2.a1, x2), cc3 = fmaf(n13, k3.a1, x3);
-    const float st0 = fmaf(n10, k0.s1, y0), st1 = fmaf(n11, k1.s1, y1), st2 = fmaf(n12, k2.s1, y2), st3 = fmaf(n13, k3.s1, y3);
-#define RFX_WV_G0(c) const float cc##c = UFH ? fmaf(dd##c, k##c.a0, n1##c) : fmaf(n1##c, k##c.a1, n0##c * k##c.a0), \
-                                 st##c = UFH ? dd##c * k##c.s0 : fmaf(n1##c, k##c.s1, n0##c * k##c.s0);
-    RFX_WV_HI(RFX_WV_G0)
-#undef RFX_WV_G0
+    // (the shifts' `old` values of a pair, (n0_{2j+1}, n0_{2j+2}), straddle two register pairs: one v_pk_mov_b32 gathers them)
+    const c2 o01 = wv_gather(n001, n023), o23 = wv_gather(n023, n045), o45 = wv_gather(n045, n067), o67 = wv_gather(n067, bc2(0.f));
+    const c2 n101 = c2{wave_shift<kDppWaveShl1>(o01.x, n001.x), wave_shift<kDppWaveShr1>(o01.y, n001.y)},
+             n123 = c2{wave_shift<kDppWaveShl1>(o23.x, n023.x), wave_shift<kDppWaveShr1>(o23.y, n023.y)},
+             n145 = c2{wave_shift<kDppWaveShl1>(o45.x, n045.x), wave_shift<kDppWaveShr1>(o45.y, n045.y)},
+             n167 = c2{wave_shift<kDppWaveShl1>(o67.x, n067.x), wave_shift<kDppWaveShr1>(o67.y, n067.y)};
+    // gradient line of every chunk: bin i of the group gets cc + st i (both weights: chunks 0 - 3; unit form: 4 - 7, with
+    // dd = n0 - n1 formed as fma(nl, d0, -n1), the contraction rounds 4 - 6 compiled it to)
+    const c2 cc01 = __builtin_elementwise_fma(n101, l0.a1, n001 * l0.a0), st01 = __builtin_elementwise_fma(n101, l0.s1, n001 * l0.s0);
+    const c2 cc23 = __builtin_elementwise_fma(n123, l1.a1, n023 * l1.a0), st23 = __builtin_elementwise_fma(n123, l1.s1, n023 * l1.s0);
+    c2 cc45, st45, cc67, st67;
+    if (UFH) {
+      const c2 dd45 = __builtin_elementwise_fma(nl2, d45, -n145), dd67 = __builtin_elementwise_fma(nl2, d67, -n167);
+      cc45 = __builtin_elementwise_fma(dd45, l2.a0, n145);
+      st45 = dd45 * l2.s0;
+      cc67 = __builtin_elementwise_fma(dd67, l3.a0, n167);
+      st67 = dd67 * l3.s0;
+    } else {
+      cc45 = __builtin_elementwise_fma(n145, l2.a1, n045 * l2.a0);
+      st45 = __builtin_elementwise_fma(n145, l2.s1, n045 * l2.s0);
+      cc67 = __builtin_elementwise_fma(n167, l3.a1, n067 * l3.a0);
+      st67 = __builtin_elementwise_fma(n167, l3.s1, n067 * l3.s0);
+    }
     // torch.optim.SGD: buf.mul_(momentum).add_(grad) for every bin of the group at once - the buffer line (C, G), in place -
-    // then the step of the pair p: (C, C + G) + p (2 G, 2 G)
-#define RFX_WV_G1(c) fma_in_place(k##c.C, mom_s, cc##c); fma_in_place(k##c.G, mom_s, st##c);
-#define RFX_WV_G3(c) const float vx##c = k##c.C, vy##c = k##c.C + k##c.G, w2##c = k##c.G + k##c.G;
-    RFX_WV_CHUNKS(RFX_WV_G1) RFX_WV_CHUNKS(RFX_WV_G3)
-#undef RFX_WV_G1
-#undef RFX_WV_G3
-#define RFX_WV_UPDATE(c) wv_update(k##c, vx##c, vy##c, w2##c);
-    RFX_WV_CHUNKS(RFX_WV_UPDATE)
-#undef RFX_WV_UPDATE
+    // then the step of the pair p: (C, C + G) + 2p (G, G).  (C, G) stay per chunk: the pair (C, C + G) the update reads must
+    // sit in one register pair
+#define RFX_WV_G(c, cc, st) fma_in_place(k##c.C, mom_s, cc); fma_in_place(k##c.G, mom_s, st); wv_update(k##c, k##c.C + k##c.G);
+    RFX_WV_G(0, cc01.x, st01.x) RFX_WV_G(1, cc01.y, st01.y) RFX_WV_G(2, cc23.x, st23.x) RFX_WV_G(3, cc23.y, st23.y)
+    RFX_WV_G(4, cc45.x, st45.x) RFX_WV_G(5, cc45.y, st45.y) RFX_WV_G(6, cc67.x, st67.x) RFX_WV_G(7, cc67.y, st67.y)
+#undef RFX_WV_G
   }
 
   // the frame leaves through the LDS stage (imel_emit_frame): active bins parked in bin order, then one walk over the positions
@@ -993,8 +1026,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
 }
 #undef RFX_WV_CHUNKS
-#undef RFX_WV_LO
-#undef RFX_WV_HI
 #endif  // RFX_IMEL_PK
 
 // one workgroup per clip: replays the reference's stopping rule on the clip-mean loss.  Thread (g, i) sums
