@@ -382,6 +382,32 @@ size_t rfx_pcm16_compress_filters_workspace_bytes(int N, int L, int C);
 int rfx_pcm16_apply_filters_compressed(const int16_t* d_pcm_in, int N, int L, int C, rfx_compress_options* options, int16_t* d_pcm_out,
                                        void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- image resize: the bytes of Pillow's Image.resize(size, resample) on RGB uint8 tiles ---------------------------------------
+ * The reference's audio-to-audio task widens each clip's tile to a multiple of 32 (scale_image_to_32_stride, BICUBIC), the
+ * pipeline's preprocess_image shrinks a tile to a multiple of 32 (LANCZOS), and the task shrinks the pipeline's output back to
+ * the clip's size (BICUBIC).  The algorithm is Pillow's 8-bit convolution resample (libImaging/Resample.c): per output column
+ * (row) a window of input taps with weights from the filter, normalised in double and rounded to 22 fractional bits; each output
+ * byte is clamp((2^21 + sum in * k) >> 22, 0, 255) in int32.  The horizontal pass runs first into a uint8 intermediate, then the
+ * vertical pass; a pass whose size does not change is skipped, and equal sizes copy.  The result equals Image.resize byte for
+ * byte.  Filters take PIL.Image.Resampling's values; NEAREST, BOX and HAMMING are not implemented.  Sizes are 1 .. 16384.
+ *
+ * rfx_image_resize_coefficients, host only (no GPU): the table of one axis, in_size -> out_size.  h_bounds receives 2 * out_size
+ * ints (first tap, tap count), h_kk out_size * ksize ints (the fixed-point weights; capacity = entries h_kk holds).  Returns
+ * ksize; with both pointers NULL it writes nothing and returns ksize.
+ * rfx_image_resize_u8: d_in (N, H, W, 3) -> d_out (N, out_h, out_w, 3), both uint8 on one device.  d_bounds_x / d_kk_x are the
+ * device copy of the table W -> out_w (may be NULL when out_w == W), d_bounds_y / d_kk_y that of H -> out_h (NULL when
+ * out_h == H).  Workspace: rfx_image_resize_workspace_bytes, 0 unless both sizes change (the uint8 intermediate). */
+typedef enum {
+  RFX_RESIZE_LANCZOS = 1,
+  RFX_RESIZE_BILINEAR = 2,
+  RFX_RESIZE_BICUBIC = 3
+} rfx_resize_filter;
+int rfx_image_resize_coefficients(int in_size, int out_size, int filter, int32_t* h_bounds, int32_t* h_kk, int capacity);
+size_t rfx_image_resize_workspace_bytes(int N, int H, int W, int out_h, int out_w, int filter);
+int rfx_image_resize_u8(const uint8_t* d_in, int N, int H, int W, int out_h, int out_w, int filter, const int32_t* d_bounds_x,
+                        const int32_t* d_kk_x, const int32_t* d_bounds_y, const int32_t* d_kk_y, uint8_t* d_out, void* d_workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ---- inverse, all the way from the image: SpectrogramImageConverter.audio_from_spectrogram_image's device half
  * (spectrogram_image_converter.py:54-91: image_util.spectrogram_from_image, audio_from_spectrogram -> waveform_from_mel_amplitudes
  * on the image's (C, n_mels, T) tensor, audio_util.audio_from_waveform).  d_img (N, n_mels, T, 3) uint8 -> d_pcm_out (N, L, C) int16,

@@ -13,6 +13,7 @@
 #include "rfx_kernels.h"
 #include "rfx_compress_core.h"
 #include "rfx_pcm_core.h"
+#include "rfx_resize_core.h"
 
 using namespace rfx;
 
@@ -1770,6 +1771,47 @@ int rfx_pcm16_stitch(const int16_t* d_pcm, int N, int L, int C, const rfx_stitch
   if (int rc = device_of(d_out, &dev)) return rc;
   RFX_ON_DEVICE(dev);
   RFX_HIP(launch_pcm_stitch(d_pcm, L, C, d_pieces, n_pieces, out_frames, d_out, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+static bool resize_args_ok(int N, int H, int W, int out_h, int out_w, int filter) {
+  const auto in_range = [](int v) { return v >= 1 && v <= kRszMaxSize; };
+  return N >= 1 && in_range(H) && in_range(W) && in_range(out_h) && in_range(out_w) && rsz_support(filter) > 0.0;
+}
+
+int rfx_image_resize_coefficients(int in_size, int out_size, int filter, int32_t* h_bounds, int32_t* h_kk, int capacity) {
+  if (in_size < 1 || in_size > kRszMaxSize || out_size < 1 || out_size > kRszMaxSize || rsz_support(filter) == 0.0)
+    return fail(RFX_ERR_INVALID, "rfx_image_resize_coefficients: sizes must be in [1, 16384] and the filter RFX_RESIZE_LANCZOS, "
+                                 "_BILINEAR or _BICUBIC");
+  const int ksize = rsz_ksize(in_size, out_size, filter);
+  if (!h_bounds && !h_kk) return ksize;
+  if (!h_bounds || !h_kk) return fail(RFX_ERR_INVALID, "rfx_image_resize_coefficients: h_bounds and h_kk go together");
+  if ((int64_t)capacity < (int64_t)out_size * ksize)
+    return fail(RFX_ERR_WORKSPACE, "rfx_image_resize_coefficients: h_kk holds fewer than out_size * ksize entries");
+  std::vector<double> w(ksize);
+  return rsz_coefficients(in_size, out_size, filter, h_bounds, h_kk, w.data());
+}
+
+size_t rfx_image_resize_workspace_bytes(int N, int H, int W, int out_h, int out_w, int filter) {
+  if (!resize_args_ok(N, H, W, out_h, out_w, filter)) return 0;
+  return resize_workspace_bytes(N, H, W, out_h, out_w);
+}
+
+int rfx_image_resize_u8(const uint8_t* d_in, int N, int H, int W, int out_h, int out_w, int filter, const int32_t* d_bounds_x,
+                        const int32_t* d_kk_x, const int32_t* d_bounds_y, const int32_t* d_kk_y, uint8_t* d_out, void* d_workspace,
+                        size_t workspace_bytes, void* stream) {
+  if (!d_in || !d_out || !resize_args_ok(N, H, W, out_h, out_w, filter))
+    return fail(RFX_ERR_INVALID, "rfx_image_resize_u8: bad argument (N >= 1, sizes in [1, 16384], filter RFX_RESIZE_LANCZOS, "
+                                 "_BILINEAR or _BICUBIC)");
+  if (out_w != W && (!d_bounds_x || !d_kk_x)) return fail(RFX_ERR_INVALID, "rfx_image_resize_u8: the width changes: need d_bounds_x, d_kk_x");
+  if (out_h != H && (!d_bounds_y || !d_kk_y)) return fail(RFX_ERR_INVALID, "rfx_image_resize_u8: the height changes: need d_bounds_y, d_kk_y");
+  const size_t need = resize_workspace_bytes(N, H, W, out_h, out_w);
+  if (need && (!d_workspace || workspace_bytes < need)) return fail(RFX_ERR_WORKSPACE, "rfx_image_resize_u8: workspace too small");
+  int dev;
+  if (int rc = device_of(d_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_resize(d_in, N, H, W, out_h, out_w, d_bounds_x, d_kk_x, rsz_ksize(W, out_w, filter), d_bounds_y, d_kk_y,
+                        rsz_ksize(H, out_h, filter), d_out, d_workspace, (hipStream_t)stream));
   return RFX_OK;
 }
 

@@ -412,4 +412,11 @@ hipError_t launch_cmp_compress(const int16_t* in, int N, int L, int C, const dou
                                void* workspace, hipStream_t s);
 hipError_t launch_cmp_scatter(const void* flags, int64_t n, int16_t* out, hipStream_t s);
 
+// PIL.Image.resize of (N, H, W, 3) uint8 tiles (rfx_resize.hip, arithmetic in rfx_resize_core.h): the horizontal pass when
+// OW != W, into the workspace when the vertical pass follows (OH != H), then the vertical pass; a copy when neither size changes.
+size_t resize_workspace_bytes(int N, int H, int W, int OH, int OW);
+hipError_t launch_resize(const uint8_t* in, int N, int H, int W, int OH, int OW, const int32_t* bounds_x, const int32_t* kk_x,
+                         int ksize_x, const int32_t* bounds_y, const int32_t* kk_y, int ksize_y, uint8_t* out, void* workspace,
+                         hipStream_t s);
+
 }  // namespace rfx

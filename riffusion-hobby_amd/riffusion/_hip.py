@@ -163,7 +163,29 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_pcm16_compress_filters_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rfx_pcm16_apply_filters_compressed": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(RfxCompressOptions), c_void_p, c_void_p,
                                                    c_size_t, c_void_p]),
+    "rfx_image_resize_coefficients": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
+    "rfx_image_resize_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rfx_image_resize_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]),
 }
+
+# PIL.Image.Resampling values of the filters rfx_image_resize_u8 implements (rfx_resize_filter)
+RESIZE_FILTERS = {1: "LANCZOS", 2: "BILINEAR", 3: "BICUBIC"}
+
+
+def resize_coefficients(in_size: int, out_size: int, resample: int) -> np.ndarray:
+    """rfx_image_resize_coefficients (host only, no GPU): one axis's table as int32 [2 * out_size bounds | out_size * ksize
+    fixed-point weights] - Pillow's Resample.c coefficients, bit for bit."""
+    lib = load_library()
+    ksize = lib.rfx_image_resize_coefficients(int(in_size), int(out_size), int(resample), None, None, 0)
+    if ksize < 0:
+        check(ksize)
+    table = np.zeros(2 * out_size + out_size * ksize, dtype=np.int32)
+    rc = lib.rfx_image_resize_coefficients(int(in_size), int(out_size), int(resample), table.ctypes.data,
+                                           table.ctypes.data + 8 * out_size, out_size * ksize)
+    if rc < 0:
+        check(rc)
+    return table
 
 
 def library_path() -> str:
@@ -635,6 +657,35 @@ class Plan:
         mx = torch.empty((N,), dtype=torch.float32, device=mel.device)
         check(self.lib.rfx_image_encode_u8(mel.data_ptr(), N, M, Tn, int(stereo), thresholds.data_ptr(), mx.data_ptr(), img.data_ptr(), self._stream()))
         return img, mx
+
+    def resize_images(self, img_u8: torch.Tensor, out_h: int, out_w: int, resample: int) -> torch.Tensor:
+        """PIL.Image.resize((out_w, out_h), resample) of every (H, W, 3) uint8 tile of an (N, H, W, 3) batch on this device, byte
+        for byte (rfx_image_resize_u8; resample: PIL's LANCZOS, BILINEAR or BICUBIC).  Each axis's table is built on the host once
+        per (in, out, filter) and kept on the device like the decode LUT."""
+        if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
+            raise ValueError("expected (N, H, W, 3) uint8 images")
+        resample, out_h, out_w = int(resample), int(out_h), int(out_w)
+        if resample not in RESIZE_FILTERS:
+            raise ValueError(f"resample must be one of PIL's {sorted(RESIZE_FILTERS.values())} ({sorted(RESIZE_FILTERS)}), got {resample}")
+        img = self._chk(img_u8)
+        N, H, W, _ = img.shape
+        out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=self.device)
+        if N == 0:
+            return out
+
+        def table(n_in: int, n_out: int) -> T.Tuple[T.Optional[int], T.Optional[int]]:
+            if n_in == n_out:
+                return None, None
+            t = self.device_constant(("resize", n_in, n_out, resample), lambda: resize_coefficients(n_in, n_out, resample))
+            return t.data_ptr(), t.data_ptr() + 8 * n_out
+
+        bx, kx = table(W, out_w)
+        by, ky = table(H, out_h)
+        need = self.lib.rfx_image_resize_workspace_bytes(N, H, W, out_h, out_w, resample)
+        with self._workspace(max(need, 1)) as ws:
+            check(self.lib.rfx_image_resize_u8(img.data_ptr(), N, H, W, out_h, out_w, resample, bx, kx, by, ky, out.data_ptr(),
+                                               ws.data_ptr(), ws.numel(), self._stream()))
+        return out
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
                           row_base: int = 0, magnitude_hint: float = 0.0) -> torch.Tensor:

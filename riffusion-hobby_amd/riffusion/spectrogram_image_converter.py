@@ -88,6 +88,7 @@ class SpectrogramImageConverter:
         tiles_per_call: int = 64,
         return_device: bool = False,
         compression: bool = False,
+        size: T.Optional[T.Tuple[int, int]] = None,
     ) -> T.Any:
         """
         A sequence of tiles -> ONE audio segment: every tile decoded (`audio_from_spectrogram_images`), filtered
@@ -100,15 +101,25 @@ class SpectrogramImageConverter:
         when the crossfade is longer than a clip; one tile gives that clip.  Returns a pydub segment when pydub is importable,
         else a PcmSegment; with `return_device=True` the (frames, C) int16 tensor on the GPU.  All clips are stitched in this
         process: there is no `group`.
+        `size=(width, height)`: every tile is first resized as `Image.resize(size, Image.BICUBIC)` does, on the device (see
+        `audio_from_spectrogram_images`); the stitch is planned for the clips of that width.  Tiles of different sizes in a list
+        (without `size`) are decoded one by one, each with the random starts of its index in the sequence, and stitched on the
+        host.
         """
         if isinstance(images, (list, tuple)):
-            images = np.stack([np.asarray(image_util.rgb_array_from_image(im)) if isinstance(im, Image.Image) else np.asarray(im)
-                               for im in images])
+            arrays = [np.asarray(image_util.rgb_array_from_image(im)) if isinstance(im, Image.Image) else np.asarray(im)
+                      for im in images]
+            if len({a.shape for a in arrays}) > 1:
+                if size is None:
+                    return self._image_sequence_mixed(arrays, crossfade_s, apply_filters, max_value, seed, return_device, compression)
+                images, size = torch.cat([self.resize_images(a[None], size) for a in arrays]), None
+            else:
+                images = np.stack(arrays)
         n = int(images.shape[0])
         if n < 1:
             raise ValueError("audio_from_spectrogram_image_sequence needs at least one image")
         plan = self.converter._plan()
-        L = plan.lib.rfx_griffinlim_output_samples(plan.handle, int(images.shape[2]))
+        L = plan.lib.rfx_griffinlim_output_samples(plan.handle, int(size[0]) if size is not None else int(images.shape[2]))
         C = 2 if self.p.stereo else 1
         try:  # the lengths alone decide whether the stitch can be planned: before any GPU work
             audio_util.stitch_plan(n, L, self.p.sample_rate, crossfade_s)
@@ -116,7 +127,7 @@ class SpectrogramImageConverter:
         except audio_util.StitchNotPlannable:  # a crossfade that reaches into the previous one: pydub's own loop, on the host
             on_device = False
         pcm = self.audio_from_spectrogram_images(images, max_value=max_value, seed=seed, tiles_per_call=tiles_per_call,
-                                                 return_device=True, apply_filters=apply_filters, compression=compression)
+                                                 return_device=True, apply_filters=apply_filters, compression=compression, size=size)
         if n == 1:
             joined = pcm[0]
         elif on_device:
@@ -129,8 +140,37 @@ class SpectrogramImageConverter:
             return joined
         return audio_util.segment_from_pcm16(joined.cpu().numpy(), self.p.sample_rate)
 
-    def spectrogram_images_from_waveforms(self, waveforms: torch.Tensor) -> T.Tuple[T.List[Image.Image], np.ndarray]:
-        """(N, C, samples) float waveforms at int16 scale -> N RGB images and their float32 MAX_VALUEs."""
+    def _image_sequence_mixed(self, arrays: T.List[np.ndarray], crossfade_s: float, apply_filters: bool, max_value: float,
+                              seed: T.Optional[int], return_device: bool, compression: bool) -> T.Any:
+        """audio_from_spectrogram_image_sequence of tiles whose widths differ: clip i is decoded alone with the random starts of
+        row i (clip_base), as it would be in one batch, filtered on the device, and the clips are stitched on the host."""
+        if compression and not apply_filters:
+            raise ValueError("compression=True is a mode of the filters: it needs apply_filters=True")
+        conv = self.converter
+        plan = conv._plan()
+        power, max_value = float(self.p.power_for_image), float(max_value)
+        if not (max_value > 0.0 and max_value < float("inf")):
+            raise ValueError(f"max_value must be a positive finite number, got {max_value}")
+        lut = plan.device_constant(("decode_lut", power, max_value), lambda: image_util.decode_lut(power, max_value))
+        base_seed = conv._seed(seed)
+        segs = []
+        for i, a in enumerate(arrays):
+            tile = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))[None].to(plan.device)
+            pcm = plan.audio_from_image(tile, self.p.stereo, lut, self.p.num_griffin_lim_iters, 0.99, seed=base_seed, normalize=True,
+                                        clip_base=i, magnitude_hint=max_value)[0]
+            if apply_filters:
+                pcm = self._filter_pcm(plan, pcm, compression)
+            segs.append(audio_util.PcmSegment(pcm[0].cpu().numpy(), self.p.sample_rate))
+        C = 2 if self.p.stereo else 1
+        joined = audio_util.stitch_segments(segs, crossfade_s).get_array_of_samples().reshape(-1, C)
+        if return_device:
+            return torch.from_numpy(joined.copy()).to(plan.device)
+        return audio_util.segment_from_pcm16(joined, self.p.sample_rate)
+
+    def spectrogram_images_from_waveforms(self, waveforms: torch.Tensor, return_device: bool = False) -> T.Tuple[T.Any, T.Any]:
+        """(N, C, samples) float waveforms at int16 scale -> N RGB images and their float32 MAX_VALUEs.  With
+        `return_device=True` the (N, n_mels, T, 3) uint8 tensor and the (N,) float32 maxima as they are on the GPU (no copy, no
+        synchronisation): the encode side of audio-to-audio's device chain."""
         conv = self.converter
         plan = conv._plan()
         N, C, L = waveforms.shape
@@ -140,8 +180,41 @@ class SpectrogramImageConverter:
         thr = plan.device_constant(("encode_thresholds", power), lambda: image_util.encode_thresholds(power))
         # one call (rfx_image_from_waveform): the mel amplitudes go from the forward kernel to the encoder without the (N*C, M, T) tensor
         img, mx = plan.image_from_waveform(waveforms.reshape(N * C, L).to(conv.device, torch.float32), self.p.stereo, thr)
+        if return_device:
+            return img, mx
         img_np, mx_np = img.cpu().numpy(), mx.cpu().numpy()
         return [Image.fromarray(a, mode="RGB") for a in img_np], mx_np
+
+    # ---- resizing tiles on the device: PIL.Image.resize, byte for byte (rfx_image_resize_u8) --------------------------------
+    def resize_images(self, images: T.Any, size: T.Tuple[int, int], resample: int = Image.BICUBIC) -> torch.Tensor:
+        """
+        (N, H, W, 3) uint8 tiles (a tensor on any device, or an array) -> (N, height, width, 3) uint8 tensor on the converter's
+        device, byte-equal to `[Image.fromarray(t).resize(size, resample) for t in images]`; `size` is PIL's (width, height) and
+        `resample` one of Image.BICUBIC, Image.LANCZOS, Image.BILINEAR (Pillow's 8-bit convolution resample, libImaging/Resample.c).
+        Every tile is resized on its own: a tile's bytes do not depend on the batch it travels in.
+        """
+        plan = self.converter._plan()
+        imgs = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
+        width, height = int(size[0]), int(size[1])
+        return plan.resize_images(imgs.to(plan.device), height, width, int(resample))
+
+    def scale_images_to_32_stride(self, images: T.Any) -> torch.Tensor:
+        """The reference's `scale_image_to_32_stride` (streamlit/tasks/audio_to_audio.py:419-425) on every tile: BICUBIC to the
+        next multiple of 32 on both axes (501 x 512 -> 512 x 512 for a 5 s clip at 44.1 kHz); tiles already there are copied."""
+        _, H, W, _ = images.shape
+        return self.resize_images(images, (int(np.ceil(W / 32) * 32), int(np.ceil(H / 32) * 32)), Image.BICUBIC)
+
+    def pipeline_input_from_images(self, images: T.Any) -> torch.Tensor:
+        """
+        The diffusion pipeline's `preprocess_image` (riffusion_pipeline.py:439-452) on the device: a LANCZOS resize of every
+        tile to the floor multiple of 32 (a copy for tiles already there), `/ 255` in float32, `2x - 1`, NCHW.  (N, H, W, 3)
+        uint8 -> (N, 3, H', W') float32, bitwise the reference's values: a pixel's value depends on its byte alone, so it is
+        read from a 256-entry table built with the reference's own numpy / torch operations.
+        """
+        _, H, W, _ = images.shape
+        x = self.resize_images(images, (W - W % 32, H - H % 32), Image.LANCZOS)
+        lut = self.converter._plan().device_constant(("pipeline_input_lut",), image_util.pipeline_input_lut)
+        return lut[x.long()].permute(0, 3, 1, 2).contiguous()
 
     @staticmethod
     def quantize_pipeline_images(images: torch.Tensor) -> torch.Tensor:
@@ -171,6 +244,7 @@ class SpectrogramImageConverter:
         return_range_flag: bool = False,
         apply_filters: bool = False,
         compression: bool = False,
+        size: T.Optional[T.Tuple[int, int]] = None,
     ) -> T.Union[np.ndarray, torch.Tensor, T.Tuple[torch.Tensor, torch.Tensor]]:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -212,6 +286,10 @@ class SpectrogramImageConverter:
         `compression=True` (only with `apply_filters=True`) is apply_filters(compression=True): normalize, gain to -10 dBFS and
         pydub's compress_dynamic_range first, on the device as well (rfx_pcm16_apply_filters_compressed, which synchronises the
         stream once per chunk of `tiles_per_call` clips).
+        `size=(width, height)` first resizes every tile as `Image.resize(size, Image.BICUBIC)` does, on the device (after the
+        quantisation of a float input) - audio-to-audio's step back from the pipeline's 512-wide output to the clip's own width
+        (streamlit/tasks/audio_to_audio.py:287).  The clip length then follows that width; the resize is per tile, so a clip's
+        bytes still do not depend on the chunking or the sharding.
         """
         from riffusion import batch_shard
 
@@ -244,7 +322,9 @@ class SpectrogramImageConverter:
             imgs = self.quantize_pipeline_images(imgs)
         n_total = imgs.shape[0]
         C = 2 if self.p.stereo else 1
-        L = plan.lib.rfx_griffinlim_output_samples(plan.handle, int(imgs.shape[2]))
+        if size is not None:
+            size = (int(size[0]), int(size[1]))
+        L = plan.lib.rfx_griffinlim_output_samples(plan.handle, size[0] if size is not None else int(imgs.shape[2]))
         base_seed = conv._seed(seed)
         power, max_value = float(self.p.power_for_image), float(max_value)
         if not (max_value > 0.0 and max_value < float("inf")):
@@ -263,13 +343,16 @@ class SpectrogramImageConverter:
             source = batch_shard.ChunkSource(imgs, bounds, plan.device)
             # (the scratch space - 1.7 GB for 64 mono tiles - comes from the plan's arena: the same buffer chunk after chunk and call after call)
             for i, (a, b) in enumerate(bounds):
+                tiles = source.get(i)
+                if size is not None:
+                    tiles = plan.resize_images(tiles, size[1], size[0], Image.BICUBIC)
                 if return_waveform:
-                    mel = plan.image_decode(source.get(i), self.p.stereo, lut)
+                    mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value)
                     out = wave.reshape(b - a, C, -1)
                 else:  # uint8 tiles -> int16 PCM in one call (rfx_audio_from_image_u8_ex), same bytes as the three calls above + pcm16
                     dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
-                    out = plan.audio_from_image(source.get(i), self.p.stereo, lut, self.p.num_griffin_lim_iters, 0.99, seed=base_seed,
+                    out = plan.audio_from_image(tiles, self.p.stereo, lut, self.p.num_griffin_lim_iters, 0.99, seed=base_seed,
                                                 normalize=True, out=dst, clip_base=a, magnitude_hint=max_value)[0]
                     if apply_filters:
                         out = self._filter_pcm(plan, out, compression)

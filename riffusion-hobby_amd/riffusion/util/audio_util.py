@@ -256,6 +256,11 @@ class PcmSegment:
             np.concatenate([self._slice_ms(None, -crossfade)._data, xf._data, seg._slice_ms(crossfade, None)._data]), self.frame_rate
         )
 
+    @classmethod
+    def silent(cls, duration: float = 1000, frame_rate: int = 11025) -> "PcmSegment":
+        """pydub AudioSegment.silent: int(frame_rate * (duration / 1000.0)) frames of mono silence (11025 Hz by default)."""
+        return cls(np.zeros(int(frame_rate * (duration / 1000.0)), dtype=np.int16), frame_rate)
+
     def export(self, out_f: T.Any, format: str = "wav") -> T.Any:
         if format != "wav":
             raise NotImplementedError("PcmSegment exports wav only; install pydub + ffmpeg for other formats")
@@ -333,6 +338,45 @@ def stitch_segments(segments: T.Sequence[T.Any], crossfade_s: float) -> T.Any:
     for seg in segments[1:]:
         out = out.append(seg, crossfade=crossfade_ms)
     return out
+
+
+def clip_start_times(duration_s: float, clip_duration_s: float = 5.0, overlap_duration_s: float = 0.2,
+                     start_time_s: float = 0.0, max_duration_s: float = 20.0) -> np.ndarray:
+    """The clip start times (s) of the reference's audio-to-audio task (streamlit/tasks/audio_to_audio.py:94-101, with its
+    defaults: 5 s clips overlapping by 0.2 s, the first 20 s of the track): `duration_s` is the track's `duration_seconds`."""
+    duration = min(max_duration_s, duration_s - start_time_s)
+    increment_s = clip_duration_s - overlap_duration_s
+    return start_time_s + np.arange(0, duration - clip_duration_s, increment_s)
+
+
+def slice_audio_into_clips(segment: T.Any, clip_start_times: T.Sequence[float], clip_duration_s: float) -> T.List[T.Any]:
+    """
+    The reference's slice_audio_into_clips (streamlit/tasks/audio_to_audio.py:396-416) on a PcmSegment or a pydub segment:
+    clip i is segment[int(t_i * 1000) : int(t_i * 1000) + int(clip_duration_s * 1000)] in integer milliseconds, as the
+    reference truncates them (the fourth start of np.arange(0, 20, 4.8) is 14 399 ms).  A full 5 s clip at 44.1 kHz holds
+    220 500 frames.
+
+    The last clip's silence branch is kept AS THE REFERENCE HAS IT (its own comment: "I don't think this is working properly"):
+    a last clip shorter than the clip duration gets `append(AudioSegment.silent(silence_ms))` with append's default crossfade of
+    100 ms, so less than 100 ms of missing audio raises append's ValueError, and more is crossfaded into the clip's end
+    instead of being added after it.  This port reproduces that; it does not fix it.
+    """
+    pydub = None if isinstance(segment, PcmSegment) else _pydub()
+    clips: T.List[T.Any] = []
+    for i, clip_start_time_s in enumerate(clip_start_times):
+        clip_start_time_ms = int(clip_start_time_s * 1000)
+        clip_duration_ms = int(clip_duration_s * 1000)
+        if pydub is None:
+            clip = segment._slice_ms(clip_start_time_ms, clip_start_time_ms + clip_duration_ms)
+        else:
+            clip = segment[clip_start_time_ms : clip_start_time_ms + clip_duration_ms]
+        if i == len(clip_start_times) - 1:
+            silence_ms = clip_duration_ms - int(clip.duration_seconds * 1000)
+            if silence_ms > 0:
+                silence = PcmSegment.silent(duration=silence_ms) if pydub is None else pydub.AudioSegment.silent(duration=silence_ms)
+                clip = clip.append(silence)
+        clips.append(clip)
+    return clips
 
 
 # ---- the same two operations on the device (riffusion/_hip.py Plan.apply_filters / Plan.stitch, csrc/rfx_pcm.hip) -------------

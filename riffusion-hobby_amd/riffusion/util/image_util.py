@@ -33,6 +33,16 @@ def decode_lut(power: float = 0.25, max_value: float = 30e6) -> np.ndarray:
     return np.ascontiguousarray(p, dtype=np.float32)
 
 
+@functools.lru_cache(maxsize=1)
+def pipeline_input_lut() -> np.ndarray:
+    """The value riffusion_pipeline.py:447-452 (preprocess_image) gives each pixel byte: numpy's float32 `/ 255.0`, then torch's
+    float32 `2.0 * x - 1.0` - the reference's own operations, on the 256 possible bytes."""
+    import torch
+
+    p = np.arange(256, dtype=np.uint8).astype(np.float32) / 255.0
+    return (2.0 * torch.from_numpy(p) - 1.0).numpy()
+
+
 def _quantise_ratio(ratio: np.ndarray, power: float) -> np.ndarray:
     """numpy's own chain from image_util.py:32-41 applied to float32 ratios x/max."""
     d = np.power(ratio, power)
