@@ -263,8 +263,17 @@ static int grid_for(size_t total) {
 }
 
 hipError_t launch_image_decode(const uint8_t* img, const float* lut, float* out, int N, int H, int W, int C, hipStream_t s) {
-  hipLaunchKernelGGL(image_decode_kernel, dim3((unsigned)((size_t)N * H)), dim3(256), 0, s, img, lut, out, H, W, C);
-  return hipGetLastError();
+  // a dispatch holds fewer than 2^32 work-items per dimension: 256 x N x H reaches that at 32 768 images of 512 rows, where the
+  // launch reports no error but the later images are never decoded - launch at most 65535 x 256 rows at a time
+  const int per = H >= 65535 * 256 ? 1 : 65535 * 256 / H;
+  for (int n0 = 0; n0 < N; n0 += per) {
+    const int n = N - n0 < per ? N - n0 : per;
+    hipLaunchKernelGGL(image_decode_kernel, dim3((unsigned)((size_t)n * H)), dim3(256), 0, s, img + (size_t)n0 * H * W * 3, lut,
+                       out + (size_t)n0 * C * H * W, H, W, C);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 hipError_t launch_clip_max(const float* x, float* out, int nclips, size_t count, bool abs_value, hipStream_t s) {
   unsigned* keys = reinterpret_cast<unsigned*>(out);
