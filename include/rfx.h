@@ -136,6 +136,33 @@ int rfx_debug_gl_partition(int slots, int B, int T, int64_t* run_starts, int cap
 /* the two internal exponents of "Numeric range" above for a largest magnitude max_abs (mel_units != 0: max_abs is a mel amplitude,
  * the Griffin-Lim exponent is then taken for max(max_abs, 1) x 2), without a GPU (tests) */
 int rfx_debug_range_exponents(float max_abs, int mel_units, int* sgd_exponent, int* gl_exponent);
+/* What rfx_plan_create_ex would decide for these parameters, this filterbank (h_melfb: n_stft x n_mels floats on the host, may be
+ * NULL) and these options (NULL = defaults), without a plan or a GPU (tests): the same host code fills the plan's tables.  Set
+ * report->struct_size = sizeof(rfx_plan_bank_report).  A geometry the library refuses returns the error of rfx_plan_create_ex. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t engine;          /* as rfx_plan_griffinlim_engine answers */
+  int32_t frame_stride;    /* as rfx_plan_frame_stride answers */
+  int32_t imel_ok;         /* the bank is banded: rfx_inverse_mel serves it (imel_why says why not) */
+  int32_t imel_kernel;     /* as rfx_plan_imel_kernel answers at params->max_mel_iters (-1: no bank, or not banded) */
+  int32_t fast_ok;         /* kernel family the bank's groups admit: 2 / 3 per-wave budgets, 5 line form, 1 uniform, 0 none */
+  int32_t unit_form;       /* as rfx_plan_imel_unit_form answers */
+  int32_t wave_ok;         /* the wave kernel serves the bank */
+  int32_t line_from;       /* groups below this index are not lines */
+  int32_t f_lo, f_hi;      /* bins with a non-zero filterbank row: [f_lo, f_hi) */
+  int32_t nnz;             /* non-zero band entries */
+  int32_t fwd_ok;          /* the fused forward path serves the bank */
+  int32_t fwd_product;     /* ... in its product form (0: table form) */
+  int32_t fwd_packed;      /* ... with the packed tables of the default-bank kernel */
+  uint32_t fwd_kb_mask;    /* product form: bit kb set when a thread's slot kb contributes */
+  int32_t fwd_prod_arr;    /* product form: floats between the two product arrays */
+  int32_t band_rows, Mpad; /* band tables: rows (longest band, rounded up to 8) and columns (n_mels rounded up to 64) */
+  int32_t n_kblocks;       /* non-zero 32-position K blocks of the slot-ordered bank (specialised engine) */
+  double line_tolerance;   /* a group is a line when no bin leaves its fitted line by more than this fraction of the group's largest weight */
+  double line_deviation;   /* the largest such fraction over all non-empty groups (-1: the bank has no group structure) */
+  char imel_why[96];
+} rfx_plan_bank_report;
+int rfx_debug_plan_bank(const rfx_params* params, const float* h_melfb, const rfx_plan_options* options, rfx_plan_bank_report* report);
 /* frames torch.stft(center=True, pad_mode="reflect") makes of Lw samples: 1 + (Lw + 2*(n_fft/2) - n_fft) / hop, i.e.
  * 1 + Lw/hop for even n_fft and 1 + (Lw-1)/hop for odd n_fft; 0 when Lw <= n_fft/2 (the reference raises there).
  * Every forward entry point below produces exactly this many frames. */

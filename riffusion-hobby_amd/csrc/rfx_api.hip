@@ -6,6 +6,7 @@
 #include <string.h>
 #include <stdlib.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -13,6 +14,7 @@
 #include "rfx_kernels.h"
 #include "rfx_compress_core.h"
 #include "rfx_pcm_core.h"
+#include "rfx_plan_core.h"
 #include "rfx_resize_core.h"
 
 using namespace rfx;
@@ -31,6 +33,23 @@ int fail(int code, const std::string& msg) {
   } while (0)
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// device copy of a host array: every allocation of plan creation (the plan's destructor frees them)
+template <class D, class T>
+hipError_t upload(D** d_out, const T* src, size_t n) {
+  const size_t bytes = n * sizeof(T);
+  hipError_t e = hipMalloc((void**)d_out, bytes ? bytes : sizeof(T));
+  if (e == hipSuccess && bytes) e = hipMemcpy(*d_out, src, bytes, hipMemcpyHostToDevice);
+  return e;
+}
+template <class D, class T>
+hipError_t upload(D** d_out, const std::vector<T>& v) {
+  return upload(d_out, v.data(), v.size());
+}
+
+struct PlanRelease {  // releases the half-built plan if a step of rfx_plan_create_ex fails
+  void operator()(rfx_plan* p) const { rfx_plan_destroy(p); }
+};
 
 // Every entry point runs on the device that owns its plan (or its buffers) and leaves the calling thread's
 // current device as it found it: torch tracks the current device per thread, and one process may hold plans
@@ -97,7 +116,7 @@ struct rfx_plan {
   int num_cus;
   int n_stft;
   int gl_wgs_per_cu = 1;    // resident Griffin-Lim workgroups per CU on this device (occupancy query at creation)
-  int imel_variant = 0;     // debugging override read once at creation: 0 = best, 1 = uniform groups, 2 = general
+  int imel_variant = 0;     // debugging override read once at creation: 0 = best, 1 = uniform groups, 2 = general, 3 = best one-frame kernel
   unsigned long long* timing = nullptr;  // RFX_TIMING builds only
   cf* d_tw1 = nullptr;      // [21][441]
   cf* d_tw2 = nullptr;      // [21][21]
@@ -112,7 +131,6 @@ struct rfx_plan {
   std::string imel_why;
   ImelTables imel{};
   void* d_imel_blob = nullptr;
-  int* d_bin_pos = nullptr;        // [n_stft] primary slot position, [n_stft] duplicate (-1)
   // fused forward path (banded mel projection inside the STFT kernel), valid when fwd_ok
   bool fwd_ok = false;
   float* d_band_wt = nullptr;      // [band_rows][Mpad]
@@ -128,7 +146,7 @@ struct rfx_plan {
   int fwd_run_skew = RFX_FWD_RUN_SKEW;  // per mille of the run length the first-dispatched workgroups of the forward kernel take on top (RFX_FWD_SKEW in ablation builds)
   int fwd_run_cap = 64;            // longest run of frames one workgroup of the product-form kernel walks (RFX_FWD_RUN, read at creation)
   // generic-geometry path (rfx_generic.hip): everything but n_fft = 17640 / win = 4410 / hop = 441
-  bool gl_latency_mode = true;     // small batches use the per-frame Griffin-Lim kernels (RFX_GL_LATENCY_MODE=0 disables)
+  bool gl_latency_mode = true;     // small batches use the per-frame Griffin-Lim kernels (RFX_GL_LATENCY_MODE=0 disables, in ablation builds)
   int gl_latency_frames_per_slot = 6;  // ... up to this many frames per resident workgroup slot (RFX_GL_LATENCY_FRAMES).  4 until round 6;
                                        // runs are whole groups of 16 frames now, so the run form costs a batch below nine tiles what it costs
                                        // eight (3.4 - 3.7 ms per Griffin-Lim 32) and the per-frame form, linear in the batch, wins up to six
@@ -217,10 +235,18 @@ static inline const char* abl_env(const char* name) {
   return nullptr;
 #endif
 }
+static int abl_int(const char* name, int unset) {
+  const char* e = abl_env(name);
+  return e ? atoi(e) : unset;
+}
+// an override that must be positive: `fallback` for anything else that was given, 0 when the variable is not set
+static int abl_positive(const char* name, int fallback) {
+  const char* e = abl_env(name);
+  return !e ? 0 : atoi(e) > 0 ? atoi(e) : fallback;
+}
 
-int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const float* h_melfb, int device,
-                       const rfx_plan_options* options, rfx_plan** out_plan) {
-  if (!params || !out_plan || !h_window) return fail(RFX_ERR_INVALID, "rfx_plan_create: null argument");
+// rfx_plan_options as the library reads them: defaults, then the caller's (possibly shorter) struct, validated
+static int resolve_options(const rfx_plan_options* options, rfx_plan_options* out) {
   rfx_plan_options opt{};
   opt.struct_size = sizeof(rfx_plan_options);
   if (options) {
@@ -236,545 +262,148 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
     if (opt.imel_form < RFX_IMEL_FORM_AUTO || opt.imel_form > RFX_IMEL_FORM_GROUPS)
       return fail(RFX_ERR_INVALID, "rfx_plan_create_ex: imel_form must be RFX_IMEL_FORM_AUTO or RFX_IMEL_FORM_GROUPS");
   }
-  const bool generic = params->n_fft != kNfft || params->win_length != kWin || params->hop_length != kHop ||
-                       opt.plan_layout == RFX_LAYOUT_GENERIC;
-  GenGeom gg{};
-  if (generic) {
-    // any geometry torch.stft accepts (0 < hop, 0 < win <= n_fft) whose FFT length factors into the implemented radices
-    if (params->n_fft < 2 || params->hop_length < 1 || params->win_length < 1 || params->win_length > params->n_fft)
-      return fail(RFX_ERR_INVALID, "rfx_plan_create: need 0 < hop_length, 0 < win_length <= n_fft");
-    gg.n_fft = params->n_fft;
-    gg.win = params->win_length;
-    gg.hop = params->hop_length;
-    gg.n_stft = params->n_fft / 2 + 1;
-    gg.even = params->n_fft % 2 == 0;
-    gg.nc = gg.even ? params->n_fft / 2 : params->n_fft;
-    gg.left = (params->n_fft - params->win_length) / 2;
-    gen_frame_layout(gg);
-    gg.fs = (gg.n_stft + 63) / 64 * 64;
-    gg.nhi = gg.nc / kGenTwLo + 1;
-    gg.nhi2 = gg.nc / kGenTwLo + 2;
-    if (gg.nc > kGenMaxNc)
-      return fail(RFX_ERR_UNSUPPORTED, "rfx_plan_create: n_fft = " + std::to_string(params->n_fft) + ": the frame's FFT buffer (" +
-                  std::to_string(gg.nc) + " complex numbers) does not fit the 160 KiB of LDS of a CU");
-    if (!gen_factor(gg.nc, gg.radix, &gg.nstages))
-      return fail(RFX_ERR_UNSUPPORTED, "rfx_plan_create: FFT length " + std::to_string(gg.nc) + " (from n_fft = " + std::to_string(params->n_fft) +
-                  ") has a prime factor above 13; implemented radices: 2, 3, 4, 5, 7, 11, 13");
-    // threads per workgroup: measured on MI355X, the engine is latency bound and more waves win over fuller rounds
-    // (48 kHz, 64 tiles x 32 iterations: 512 threads 121 ms, 384: 134, 320 - the count gen_pick_threads prefers: 155, 256: 163)
-    gg.nthr = 512;
-    if (const char* e = abl_env("RFX_GEN_THREADS")) { const int v = atoi(e); if (v >= 64 && v <= 512 && v % 64 == 0) gg.nthr = v; }
-    {  // LDS padding: keep as many workgroups per CU as the unpadded buffer allows
-      const size_t tables = sizeof(cf) * (2 * (size_t)kGenTwLo + gg.nhi + gg.nhi2);
-      const size_t plain = sizeof(cf) * (size_t)gg.nc + tables + 512;
-      int per_cu = (int)((160u * 1024u) / plain);
-      if (per_cu < 1) per_cu = 1;
-      if (per_cu > 1024 / gg.nthr) per_cu = 1024 / gg.nthr;
-      const size_t room = (160u * 1024u) / per_cu - tables - 512;
-      gg.pad_shift = gen_pick_pad(gg, (int)(room / sizeof(cf)));
-      if (const char* e = abl_env("RFX_GEN_PAD")) { const int v = atoi(e); if (v == 0 || (v >= 3 && v <= 8)) gg.pad_shift = v; }
-      if (gen_lds_bytes(gg) > 160u * 1024u) gg.pad_shift = 0;
-      if (gen_lds_bytes(gg) > 160u * 1024u)
-        return fail(RFX_ERR_UNSUPPORTED, "rfx_plan_create: n_fft = " + std::to_string(params->n_fft) + ": the frame's FFT buffer and twiddle tables (" +
-                    std::to_string(gen_lds_bytes(gg)) + " bytes) do not fit the 160 KiB of LDS of a CU (largest supported: n_fft about 39000 when "
-                    "even, 19500 when odd)");
-    }
-  }
-  // Griffin-Lim of the geometries with n_fft = 40 h, win_length = 10 h (the default 400 / 100 ms at 48 / 32 / 24 / 16 / 8 kHz)
-  // runs on the row-family kernels; the generic engine keeps everything else of the plan (layouts, forward path)
-  FamGeom fam{};
-  bool fam_ok = generic && opt.frame_engine != RFX_ENGINE_GENERIC &&
-                fam_make_geom(params->n_fft, params->win_length, params->hop_length, &fam);
-  if (fam_ok) {
-    // pad the rows by up to seven elements (bank spread of the row-to-row accesses) as long as that costs no resident workgroup
-    const size_t plain = fam_lds_bytes(fam) + fam_static_lds_bytes(fam);
-    int per_cu = (int)((160u * 1024u) / plain);
-    if (per_cu > 1024 / fam.nthr) per_cu = 1024 / fam.nthr;
-    if (per_cu < 1) fam_ok = false;
-    for (int pad = 7; fam_ok && pad > 0; --pad) {
-      FamGeom t = fam;
-      t.rs = fam.h + pad;
-      if (fam_row_stride_even(fam) && t.rs % 2) continue;
-      if ((fam_lds_bytes(t) + fam_static_lds_bytes(t)) * per_cu <= 160u * 1024u) { fam = t; break; }
-    }
-  }
+  *out = opt;
+  return RFX_OK;
+}
+
+// the overrides that change a decision of rfx_plan_core.h, passed to it as values
+static PlanOverrides plan_overrides() {
+  PlanOverrides ov;
+  ov.gen_threads = abl_int("RFX_GEN_THREADS", 0);
+  ov.gen_pad = abl_int("RFX_GEN_PAD", -1);
+  ov.fwd_table_form = abl_env("RFX_FWD_V1") != nullptr;
+  return ov;
+}
+
+int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const float* h_melfb, int device,
+                       const rfx_plan_options* options, rfx_plan** out_plan) {
+  if (!params || !out_plan || !h_window) return fail(RFX_ERR_INVALID, "rfx_plan_create: null argument");
+  // 1, 2: the options, then the geometry and its frame engine (host only)
+  rfx_plan_options opt;
+  if (const int rc = resolve_options(options, &opt)) return rc;
+  const PlanOverrides ov = plan_overrides();
+  PlanGeometry geo;
+  std::string err;
+  if (const int rc = plan_geometry(*params, opt, ov, &geo, &err)) return fail(rc, err);
+  const GenGeom& gg = geo.gg;
+  // 3, 4: the device - CU count, per-device kernel attributes (dynamic LDS above 64 KB), occupancy
   RFX_ON_DEVICE(device);
-  rfx_plan* pl = new rfx_plan();
-  struct Guard {  // releases the half-built plan if any step below fails
-    rfx_plan* p;
-    ~Guard() { if (p) rfx_plan_destroy(p); }
-  } guard{pl};
+  std::unique_ptr<rfx_plan, PlanRelease> pl(new rfx_plan());
   pl->p = *params;
   pl->device = device;
-  pl->n_stft = params->n_fft / 2 + 1;
-  pl->generic = generic;
+  pl->n_stft = geo.n_stft;
+  pl->generic = geo.generic;
   pl->gg = gg;
-  pl->frame_stride = generic ? gg.fs : kFrameStride;
-  const int F = pl->n_stft;  // linear bins
+  pl->frame_stride = geo.frame_stride;
+  pl->gl_form = opt.gl_form;
   hipDeviceProp_t prop;
   RFX_HIP(hipGetDeviceProperties(&prop, device));
   pl->num_cus = prop.multiProcessorCount;
-  // per-device kernel attributes (dynamic LDS above 64 KB) and occupancy; environment knobs are read here,
-  // once, never on the hot calls
   RFX_HIP(prepare_frame_kernels());
-  if (generic) RFX_HIP(prepare_generic_kernels(gg));
-  if (fam_ok) {
-    RFX_HIP(prepare_fam_kernels(fam));
-    pl->fam = fam;
-    pl->fam_wgs_per_cu = fam_blocks_per_cu(fam);
-    if (const char* e = abl_env("RFX_FAM_WGS_PER_CU")) pl->fam_wgs_per_cu = atoi(e) > 0 ? atoi(e) : 1;
+  if (geo.generic) RFX_HIP(prepare_generic_kernels(gg));
+  if (geo.fam_ok) {
+    RFX_HIP(prepare_fam_kernels(geo.fam));
+    pl->fam = geo.fam;
+    pl->fam_wgs_per_cu = fam_blocks_per_cu(geo.fam);
   }
   pl->gl_wgs_per_cu = gl_blocks_per_cu();
-  if (const char* e = abl_env("RFX_GL_WGS_PER_CU")) pl->gl_wgs_per_cu = atoi(e) > 0 ? atoi(e) : 1;
+  // 5: the remaining ablation overrides, read here, once, never on the hot calls.  The Griffin-Lim form a call takes is decided by
+  // the options; the environment only changes what RFX_GL_FORM_AUTO / the default threshold mean
+  if (const int v = abl_positive("RFX_FAM_WGS_PER_CU", 1)) pl->fam_wgs_per_cu = v;
+  if (const int v = abl_positive("RFX_GL_WGS_PER_CU", 1)) pl->gl_wgs_per_cu = v;
   pl->imel_variant = abl_env("RFX_IMEL_GENERAL") ? 2 : abl_env("RFX_IMEL_UNIFORM") ? 1 : abl_env("RFX_IMEL_NO_PAIR") ? 3 : 0;  // 3: best one-frame kernel
-  // which Griffin-Lim device form a call takes: the options of rfx_plan_create_ex decide; the environment (read here, once)
-  // only changes what RFX_GL_FORM_AUTO / the default threshold mean, for experiments
-  if (const char* e = abl_env("RFX_GL_LATENCY_MODE")) pl->gl_latency_mode = atoi(e) != 0;
-  if (const char* e = abl_env("RFX_GL_LATENCY_FRAMES")) pl->gl_latency_frames_per_slot = atoi(e) > 0 ? atoi(e) : 6;
-  pl->gl_form = opt.gl_form;
+  pl->gl_latency_mode = abl_int("RFX_GL_LATENCY_MODE", 1) != 0;
+  if (const int v = abl_positive("RFX_GL_LATENCY_FRAMES", 6)) pl->gl_latency_frames_per_slot = v;
   if (opt.gl_frames_per_slot > 0) pl->gl_latency_frames_per_slot = opt.gl_frames_per_slot;
+  const bool fwd_unfused = abl_env("RFX_FWD_UNFUSED") != nullptr;
+  const int fwd_run_cap = abl_positive("RFX_FWD_RUN", 64), fwd_run_skew = abl_int("RFX_FWD_SKEW", pl->fwd_run_skew);
 #if defined(RFX_TIMING) || defined(RFX_WGCLOCK)
   if (const char* e = getenv("RFX_TIMING_PTR")) pl->timing = (unsigned long long*)strtoull(e, nullptr, 0);
 #endif
-
-  const double PI2 = 6.283185307179586476925286766559;
-  std::vector<cf> tw1(21 * kHop), tw2(21 * 21);
-  for (int k1 = 0; k1 < 21; ++k1)
-    for (int n = 0; n < kHop; ++n) {
-      const long long e = ((long long)k1 * (n + 6615)) % kNfft;
-      tw1[k1 * kHop + n] = cf{(float)cos(PI2 * (double)e / kNfft), (float)(-sin(PI2 * (double)e / kNfft))};
-    }
-  for (int i = 0; i < 21; ++i)
-    for (int j = 0; j < 21; ++j) {
-      const int e = (i * j) % kHop;
-      tw2[i * 21 + j] = cf{(float)cos(PI2 * e / (double)kHop), (float)(-sin(PI2 * e / (double)kHop))};
-    }
-  RFX_HIP(hipMalloc(&pl->d_tw1, tw1.size() * sizeof(cf)));
-  RFX_HIP(hipMalloc(&pl->d_tw2, tw2.size() * sizeof(cf)));
-  RFX_HIP(hipMalloc(&pl->d_win, (size_t)params->win_length * sizeof(float)));
-  RFX_HIP(hipMemcpy(pl->d_tw1, tw1.data(), tw1.size() * sizeof(cf), hipMemcpyHostToDevice));
-  RFX_HIP(hipMemcpy(pl->d_tw2, tw2.data(), tw2.size() * sizeof(cf), hipMemcpyHostToDevice));
-  RFX_HIP(hipMemcpy(pl->d_win, h_window, (size_t)params->win_length * sizeof(float), hipMemcpyHostToDevice));
-  if (generic) {
-    // two-level twiddle tables of the Stockham passes (base nc) and of the real <-> packed split (base n_fft)
-    std::vector<cf> t(2 * kGenTwLo + gg.nhi + gg.nhi2);
-    cf* lo = t.data();
-    cf* hi = lo + kGenTwLo;
-    cf* lo2 = hi + gg.nhi;
-    cf* hi2 = lo2 + kGenTwLo;
-    auto root = [&](long long num, long long den) {
-      const double a = -PI2 * (double)(num % den) / (double)den;
-      return cf{(float)cos(a), (float)sin(a)};
-    };
-    for (int i = 0; i < kGenTwLo; ++i) { lo[i] = root(i, gg.nc); lo2[i] = root(i, gg.n_fft); }
-    for (int i = 0; i < gg.nhi; ++i) hi[i] = root((long long)i * kGenTwLo, gg.nc);
-    for (int i = 0; i < gg.nhi2; ++i) hi2[i] = root((long long)i * kGenTwLo, gg.n_fft);
-    RFX_HIP(hipMalloc(&pl->d_gen_tables, t.size() * sizeof(cf)));
-    RFX_HIP(hipMemcpy(pl->d_gen_tables, t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice));
+  // 6: window and twiddles of the engines this plan runs on
+  RFX_HIP(upload(&pl->d_tw1, spec_twiddles1()));
+  RFX_HIP(upload(&pl->d_tw2, spec_twiddles2()));
+  RFX_HIP(upload(&pl->d_win, h_window, (size_t)params->win_length));
+  if (geo.generic) {
+    RFX_HIP(upload(&pl->d_gen_tables, gen_two_level_twiddles(gg)));
+    RFX_HIP(upload(&pl->d_gen_rev, gen_rev_table(gg)));
+    RFX_HIP(upload(&pl->d_gen_tw, gen_pass_twiddles(gg)));
     cf* d = (cf*)pl->d_gen_tables;
     pl->gt.lo = d;
     pl->gt.hi = d + kGenTwLo;
     pl->gt.lo2 = d + kGenTwLo + gg.nhi;
     pl->gt.hi2 = d + 2 * kGenTwLo + gg.nhi;
     pl->gt.win = pl->d_win;
-    std::vector<int> rev(gg.nc);
-    for (int k = 0; k < gg.nc; ++k) rev[k] = gen_ipad(gen_digit_reverse(gg, k), gg.pad_shift);  // LDS position incl. padding
-    RFX_HIP(hipMalloc(&pl->d_gen_rev, rev.size() * sizeof(int)));
-    RFX_HIP(hipMemcpy(pl->d_gen_rev, rev.data(), rev.size() * sizeof(int), hipMemcpyHostToDevice));
     pl->gt.rev = pl->d_gen_rev;
-    // exact twiddles of every pass (double precision, rounded once)
-    std::vector<cf> twt((size_t)gen_tw_table_elems(gg) + 1);
-    for (int s2 = 0, L = gg.nc; s2 < gg.nstages; ++s2) {
-      const int R = gg.radix[s2], m = L / R, off = gen_tw_table_offset(gg, s2);
-      for (int i = 0; i < m; ++i)
-        for (int q = 1; q < R; ++q) {
-          const double ang = -PI2 * (double)(((long long)i * q) % L) / (double)L;
-          twt[(size_t)off + (size_t)i * (R - 1) + q - 1] = cf{(float)cos(ang), (float)sin(ang)};
-        }
-      L = m;
-    }
-    RFX_HIP(hipMalloc(&pl->d_gen_tw, twt.size() * sizeof(cf)));
-    RFX_HIP(hipMemcpy(pl->d_gen_tw, twt.data(), twt.size() * sizeof(cf), hipMemcpyHostToDevice));
     pl->gt.tw = pl->d_gen_tw;
   }
-  if (fam_ok) {
-    const FamGeom& f = pl->fam;
-    std::vector<cf> tw((size_t)f.rows * f.h + (size_t)f.rb * (f.ra - 1));
-    for (int k1 = 0; k1 < f.rows; ++k1)
-      for (int n = 0; n < f.h; ++n) {  // g(n)^k1 = exp(-2 pi i k1 (n + left) / n_fft); left = 15 h in the 40 h family
-        const long long e = ((long long)k1 * (n + f.left)) % f.n_fft;
-        tw[(size_t)k1 * f.h + n] = cf{(float)cos(PI2 * (double)e / f.n_fft), (float)(-sin(PI2 * (double)e / f.n_fft))};
-      }
-    cf* twa = tw.data() + (size_t)f.rows * f.h;
-    for (int i = 0; i < f.rb; ++i)
-      for (int q = 1; q < f.ra; ++q) {
-        const int e = (i * q) % f.h;
-        twa[(size_t)(q - 1) * f.rb + i] = cf{(float)cos(PI2 * e / (double)f.h), (float)(-sin(PI2 * e / (double)f.h))};
-      }
-    RFX_HIP(hipMalloc(&pl->d_fam_tw, tw.size() * sizeof(cf)));
-    RFX_HIP(hipMemcpy(pl->d_fam_tw, tw.data(), tw.size() * sizeof(cf), hipMemcpyHostToDevice));
-    std::vector<int> binof((size_t)f.fsf, -1);
-    for (int k1 = 0; k1 < f.rows; ++k1)
-      for (int q = 0; q < f.ra; ++q)
-        for (int s2 = 0; s2 < f.rb; ++s2) binof[(size_t)s2 * f.nthr + k1 * f.ra + q] = fam_slot_bin(f, k1, q, s2, nullptr);
-    RFX_HIP(hipMalloc(&pl->d_fam_binof, binof.size() * sizeof(int)));
-    RFX_HIP(hipMemcpy(pl->d_fam_binof, binof.data(), binof.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (geo.fam_ok) {
+    RFX_HIP(upload(&pl->d_fam_tw, fam_twiddles(geo.fam)));
+    RFX_HIP(upload(&pl->d_fam_binof, fam_bin_of(geo.fam)));
     pl->fam_ok = true;
   }
-
   if (h_melfb) {
-    const int M = params->n_mels;
+    const int F = geo.n_stft, M = params->n_mels;
     if (M <= 0) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be positive");
-    RFX_HIP(hipMalloc(&pl->d_melfb, (size_t)F * M * sizeof(float)));
-    RFX_HIP(hipMemcpy(pl->d_melfb, h_melfb, (size_t)F * M * sizeof(float), hipMemcpyHostToDevice));
-    // slot-ordered copy: row of slot position p = filterbank row of its bin for PRIMARY slots, zero for
-    // the 440 duplicate slots and the 3 padding positions, so a GEMM over slot order equals the
-    // reference's GEMM over bins up to summation order
-    const int Mp = (M + 127) / 128 * 128;  // columns padded to the GEMM's 128-row tile: aligned, test-free loads
-    pl->melfb_cols = Mp;
-    if (!generic) {
-    std::vector<float> fbs((size_t)kFrameStride * Mp, 0.f);
-    std::vector<char> seen(F, 0);
-    for (int k1 = 0; k1 < 21; ++k1)
-      for (int ka = 0; ka < 21; ++ka)
-        for (int kb = 0; kb < 21; ++kb) {
-          bool cj;
-          const int bin = slot_bin(k1, ka, kb, &cj);
-          if (seen[bin]) continue;
-          seen[bin] = 1;
-          const int pos = slot_pos_f(k1 * 21 + ka, kb);
-          memcpy(&fbs[(size_t)pos * Mp], &h_melfb[(size_t)bin * M], M * sizeof(float));
-        }
-    RFX_HIP(hipMalloc(&pl->d_melfb_slots, fbs.size() * sizeof(float)));
-    RFX_HIP(hipMemcpy(pl->d_melfb_slots, fbs.data(), fbs.size() * sizeof(float), hipMemcpyHostToDevice));
-    // K blocks (32 slot positions) with at least one non-zero filterbank row
-    std::vector<int> kb;
-    for (int blk = 0; blk < kFrameStride / 32; ++blk) {
-      bool nz = false;
-      for (int r = blk * 32; r < blk * 32 + 32 && !nz; ++r)
-        for (int m = 0; m < M; ++m)
-          if (fbs[(size_t)r * Mp + m] != 0.f) { nz = true; break; }
-      if (nz) kb.push_back(blk);
+    // 7: everything the filterbank decides (host only)
+    const PlanBank bank = plan_bank(geo, M, h_melfb, opt, ov);
+    // 8: upload
+    RFX_HIP(upload(&pl->d_melfb, h_melfb, (size_t)F * M));
+    if (!geo.generic) {
+      RFX_HIP(upload(&pl->d_melfb_slots, bank.fbs));
+      RFX_HIP(upload(&pl->d_kblocks, bank.kblocks));
     }
-    pl->n_kblocks = (int)kb.size();
-    RFX_HIP(hipMalloc(&pl->d_kblocks, (kb.size() + 1) * sizeof(int)));
-    RFX_HIP(hipMemcpy(pl->d_kblocks, kb.data(), kb.size() * sizeof(int), hipMemcpyHostToDevice));
-    }  // !generic
-
-    // ---- banded tables for InverseMelScale: every bin feeds at most two ADJACENT mel filters and
-    // every filter's support is one contiguous run of bins (true for torchaudio's triangular banks)
-    std::vector<int> bin_m0(F, -1), band_lo(M, 0), band_hi(M, 0), csr_ptr(M + 1, 0);
-    std::vector<float> bin_w0(F, 0.f), bin_w1(F, 0.f), csr_w;
-    bool ok = true;
-    std::string why;
-    int f_lo = F, f_hi = 0;
-    for (int f = 0; f < F && ok; ++f) {
-      int first = -1, cnt = 0, last = -1;
-      for (int m = 0; m < M; ++m)
-        if (h_melfb[(size_t)f * M + m] != 0.f) { if (first < 0) first = m; last = m; ++cnt; }
-      if (cnt == 0) continue;
-      if (cnt > 2 || last - first != cnt - 1) { ok = false; why = "a linear bin feeds more than two adjacent mel filters"; break; }
-      bin_m0[f] = first;
-      bin_w0[f] = h_melfb[(size_t)f * M + first];
-      bin_w1[f] = cnt == 2 ? h_melfb[(size_t)f * M + first + 1] : 0.f;
-      f_lo = f < f_lo ? f : f_lo;
-      f_hi = f + 1;
+    if (bank.fwd_ok) {
+      RFX_HIP(upload(&pl->d_band_wt, bank.wt));
+      if (!geo.generic) RFX_HIP(upload(&pl->d_band_addr, bank.addr));
+      RFX_HIP(upload(&pl->d_band_lo, bank.lo_len));
     }
-    for (int m = 0; m < M && ok; ++m) {
-      int lo = -1, hi = -1;
-      for (int f = 0; f < F; ++f)
-        if (h_melfb[(size_t)f * M + m] != 0.f) { if (lo < 0) lo = f; hi = f + 1; }
-      if (lo < 0) { lo = hi = (f_lo < F ? f_lo : 0); }
-      for (int f = lo; f < hi; ++f)
-        if (h_melfb[(size_t)f * M + m] == 0.f) { ok = false; why = "a mel filter's support is not contiguous"; break; }
-      band_lo[m] = lo;
-      band_hi[m] = hi;
-      csr_ptr[m] = (int)csr_w.size();
-      for (int f = lo; f < hi; ++f) csr_w.push_back(h_melfb[(size_t)f * M + m]);
+    if (bank.prod_ok) {  // d_slot_idx: padtab | seg | tab_at | packed tables
+      std::vector<int> idx(bank.padtab);
+      idx.insert(idx.end(), bank.seg.begin(), bank.seg.end());
+      idx.insert(idx.end(), bank.tab_at.begin(), bank.tab_at.end());
+      if (bank.packed) pl->fwd_packed_off = (int)idx.size();
+      idx.insert(idx.end(), bank.pk.begin(), bank.pk.end());
+      RFX_HIP(upload(&pl->d_slot_tab, bank.tab));
+      RFX_HIP(upload(&pl->d_slot_idx, idx));
     }
-    csr_ptr[M] = (int)csr_w.size();
-    if (ok && (f_hi <= f_lo)) { ok = false; why = "empty filterbank"; }
-    if (ok && (f_hi - f_lo > 36 * 256)) { ok = false; why = "more than 9216 active bins"; }
-    if (ok && M > 1024) { ok = false; why = "more than 1024 mel filters"; }
-    std::vector<int> bin_pos(F, -1), bin_pos2(F, -1);
-    if (generic)
-      for (int f = 0; f < F; ++f) bin_pos[f] = f;  // plain bin-ordered frames
-    else
-    for (int k1 = 0; k1 < 21; ++k1)
-      for (int ka = 0; ka < 21; ++ka)
-        for (int kbq = 0; kbq < 21; ++kbq) {
-          bool cj;
-          const int bin = slot_bin(k1, ka, kbq, &cj);
-          const int pos = slot_pos_f(k1 * 21 + ka, kbq);
-          if (bin_pos[bin] < 0) bin_pos[bin] = pos; else bin_pos2[bin] = pos;
-        }
-    // group formulation (fast kernel): active bins contiguous with no zero row inside, first-filter index
-    // non-decreasing, and the per-thread pairing (short group t, long group M-1-t) fits 8 + 24 registers
-    std::vector<int> grp_start(M + 1, 0);
-    bool fast = ok && M <= 512;
-    int fast_code = 0;
-    bool unit_form = false, wave_ok = false;
-    int line_from_out = 0;  // groups below it are not lines (rfx_kernels.h, ImelTables::line_from)
-    std::vector<float> lin;
-    if (fast) {
-      int prev = 0;
-      for (int f = f_lo; f < f_hi && fast; ++f) {
-        if (bin_m0[f] < 0 || bin_m0[f] < prev) { fast = false; break; }
-        prev = bin_m0[f];
-      }
-      if (fast) {
-        std::vector<int> cnt(M, 0);
-        for (int f = f_lo; f < f_hi; ++f) cnt[bin_m0[f]]++;
-        int acc = f_lo;
-        for (int g2 = 0; g2 < M; ++g2) { grp_start[g2] = acc; acc += cnt[g2]; }
-        grp_start[M] = acc;
-        // which register budgets the bank's groups fit: thread role t2 owns the long group M-1-t2 and the short group t2
-        auto fits = [&](const int* lo_cap, const int* hi_cap) {
-          for (int t2 = 0; t2 < 256; ++t2) {
-            const int gH = M - 1 - t2, gL = t2 < M - 256 ? t2 : -1;
-            if (gH >= 0 && cnt[gH] > hi_cap[t2 >> 6]) return false;
-            if (gL >= 0 && cnt[gL] > lo_cap[t2 >> 6]) return false;
-            if (gL >= 0 && gH >= 0 && gL >= gH) return false;
-          }
-          return true;
-        };
-        // weights as a LINE per group: on a uniform bin grid a triangular filter's weight is linear in the bin index between two
-        // centres, w0 = a0 + s0 i, w1 = a1 + s1 i for the group's i-th bin (least-squares line in double, checked per bin).  The
-        // tolerance is RELATIVE to the group's largest weight (an area-normalised bank has weights ~1e-2: an absolute 1e-6 would
-        // admit 1e-4 relative there).  Measured on the reference's banks (tests/test_round5_cpu.py): 0.72e-7 of the group maximum
-        // for htk / no norm, 1.16e-7 for slaney - one ulp of the largest weight; 4e-7 leaves a factor of three.
-        // line_from = the lowest group from which every group is a line (group 0 of a bank whose first filter rises over several
-        // bins holds that rising edge AND its own falling one: a kink)
-        lin.assign(4 * (size_t)M, 0.f);
-        int line_from = 0;
-        for (int g2 = 0; g2 < M; ++g2) {
-          const int n = cnt[g2], f0 = grp_start[g2];
-          if (n == 0) continue;
-          for (int which = 0; which < 2; ++which) {
-            const std::vector<float>& w = which ? bin_w1 : bin_w0;
-            double sx = 0, sy = 0, sxx = 0, sxy = 0;
-            for (int i = 0; i < n; ++i) { sx += i; sy += w[f0 + i]; sxx += (double)i * i; sxy += (double)i * w[f0 + i]; }
-            const double den = n * sxx - sx * sx;
-            const double slope = n > 1 ? (n * sxy - sx * sy) / den : 0.0, icpt = (sy - slope * sx) / n;
-            const float af = (float)icpt, sf = (float)slope;
-            double wmax = 0;
-            for (int i = 0; i < n; ++i) wmax = fmax(wmax, fabs((double)w[f0 + i]));
-            for (int i = 0; i < n; ++i)
-              if (fabs((double)af + (double)sf * i - (double)w[f0 + i]) > 4e-7 * wmax) line_from = g2 + 1;
-            lin[(size_t)(2 * which) * M + g2] = af;
-            lin[(size_t)(2 * which + 1) * M + g2] = sf;
-          }
-        }
-        const int uni_lo[4] = {8, 8, 8, 8}, uni_hi[4] = {24, 24, 24, 24};
-        // per-wave budgets of imel_group_kernel_perwave (rfx_kernels.h): the default bank's exact set, then the wide set; banks
-        // whose groups are too long for either (max_frequency above ~11 kHz at 512 filters - the reference's own round-trip test
-        // uses 20 Hz .. 20 kHz, test/spectrogram_converter_test.py:46-53 - or fewer filters) take the line-form group kernel
-        // (round 5: imel_line_kernel_perwave, code 5) when their LONG groups M-256 .. M-1 are lines; they ran on the general LDS
-        // kernel until then: 169 ms per 64 tiles against 4.5 for the default bank
-        // (a long group that is NOT a line - group 0 of a bank with at most 256 filters - moves into its thread's free table-form slot)
-        auto fits_line = [&]() {
-          for (int t2 = 0; t2 < 256; ++t2) {
-            const int gH = M - 1 - t2, gL = t2 < M - 256 ? t2 : -1, c = t2 >> 6;
-            if (gH >= 0 && gH < line_from) {
-              if (gL >= 0 || cnt[gH] > rfx::kImelLoCapLine[c]) return false;
-            } else if (gH >= 0 && cnt[gH] > rfx::kImelHiCapLine[c]) return false;
-            if (gL >= 0 && cnt[gL] > rfx::kImelLoCapLine[c]) return false;
-            if (gL >= 0 && gH >= 0 && gL >= gH) return false;
-          }
-          return true;
-        };
-        const bool line_set = fits_line();
-        line_from_out = line_from;
-        fast_code = fits(rfx::kImelLoCap, rfx::kImelHiCap) ? 2 : fits(rfx::kImelLoCapWide, rfx::kImelHiCapWide) ? 3 : line_set ? 5 : fits(uni_lo, uni_hi) ? 1 : 0;
-        fast = fast_code != 0;
-        // unit form of the gradient (rfx_imel.hip): the long groups M-256 .. M-1 must have w0 + w1 == 1 per bin (triangular
-        // filters, no area normalisation), the last one w1 == 0 throughout (there is no filter M)
-        unit_form = fast_code >= 2;
-        for (int f = f_lo; f < f_hi && unit_form; ++f) {
-          const int g2 = bin_m0[f];
-          if (g2 < M - 256) continue;
-          if (g2 == M - 1) unit_form = bin_w1[f] == 0.f;
-          else unit_form = fabsf(bin_w0[f] + bin_w1[f] - 1.f) <= 1e-6f;
-        }
-        // wave kernel (rfx_imel.hip::imel_wave_kernel): 512 groups dealt to 64 lanes in eight chunks whose budgets must hold every
-        // group, every group a line; with the unit form (no area normalisation) the upper four chunks need one weight only
-        wave_ok = RFX_IMEL_WAVE && opt.imel_form == RFX_IMEL_FORM_AUTO && fast_code == 2 && M == 64 * rfx::kImelWaveChunks && line_from == 0;
-        for (int c = 0; c < rfx::kImelWaveChunks && wave_ok; ++c)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int n = cnt[rfx::imel_wave_group(c, lane)];
-            if (n > 2 * rfx::kImelWavePairs[c] || n < 2 * rfx::kImelWaveFullPairs[c]) wave_ok = false;
-          }
-      }
+    // 9: the plan's fields
+    pl->melfb_cols = bank.melfb_cols;
+    pl->n_kblocks = (int)bank.kblocks.size();
+    pl->imel_ok = bank.ok;
+    pl->imel_why = bank.why;
+    pl->fwd_ok = bank.fwd_ok;
+    pl->band_rows = bank.band_rows;
+    pl->Mpad = bank.Mpad;
+    if (bank.prod_ok) {
+      pl->fwd_kb_mask = bank.mask;
+      pl->fwd_prod_arr = bank.arr;
     }
-    pl->imel_ok = ok;
-    pl->imel_why = why;
-    // ---- fused forward path: per-filter band tables, weights transposed so that lane m reads row i coalesced
-    if (ok && (generic || M <= 2 * kThreads)) {
-      const int Mpad = (M + 63) / 64 * 64;
-      int rows = 1;
-      for (int m = 0; m < M; ++m) rows = band_hi[m] - band_lo[m] > rows ? band_hi[m] - band_lo[m] : rows;
-      rows = (rows + 7) / 8 * 8;  // the kernel reads eight rows per step
-      std::vector<float> wt((size_t)rows * Mpad, 0.f);
-      std::vector<int> lo_len(2 * (size_t)Mpad, 0);
-      for (int m = 0; m < M; ++m) {
-        lo_len[m] = band_lo[m];
-        lo_len[Mpad + m] = band_hi[m] - band_lo[m];
-        for (int f = band_lo[m]; f < band_hi[m]; ++f) wt[(size_t)(f - band_lo[m]) * Mpad + m] = h_melfb[(size_t)f * M + m];
-      }
-      RFX_HIP(hipMalloc(&pl->d_band_wt, wt.size() * sizeof(float)));
-      RFX_HIP(hipMemcpy(pl->d_band_wt, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
-      if (!generic) {  // where the fused kernel finds bin f in LDS: float view of the cube, primary slot of the bin
-        std::vector<int> addr((size_t)rows * Mpad, 0);
-        for (int m = 0; m < M; ++m)
-          for (int f = band_lo[m]; f < band_hi[m]; ++f) {
-            const int k = (f % 40 > 20) ? kNfft - f : f;  // bins with residue 21..39 live in conjugate slots
-            const int k1 = k % 40, kp = k / 40;
-            addr[(size_t)(f - band_lo[m]) * Mpad + m] = 2 * cube_at(k1, kp % 21, 0) + kp / 21;
-          }
-        RFX_HIP(hipMalloc(&pl->d_band_addr, addr.size() * sizeof(int)));
-        RFX_HIP(hipMemcpy(pl->d_band_addr, addr.data(), addr.size() * sizeof(int), hipMemcpyHostToDevice));
-      }
-      RFX_HIP(hipMalloc(&pl->d_band_lo, lo_len.size() * sizeof(int)));
-      RFX_HIP(hipMemcpy(pl->d_band_lo, lo_len.data(), lo_len.size() * sizeof(int), hipMemcpyHostToDevice));
-      pl->band_rows = rows;
-      pl->Mpad = Mpad;
-      pl->fwd_ok = true;
-      // product form of the fused kernel (stft_mel2_kernel).  Needs the group structure of the bank: active bins contiguous,
-      // first-filter index non-decreasing, so that filter m = (w1 products of group m-1) + (w0 products of group m).
-      // Its sum phase gives every thread one filter and the first wave a second one: Mpad <= kThreads + 64 (banks of up to 512
-      // filters); wider banks keep the table form (stft_mel_kernel), which handles two filters per thread up to 2 * kThreads.
-      if (!generic && Mpad <= kThreads + 64 && abl_env("RFX_FWD_V1") == nullptr) {
-        bool v2 = true;
-        std::vector<int> cnt(M, 0), gfirst(M, 0);
-        int prev = 0;
-        for (int f = f_lo; f < f_hi && v2; ++f) {
-          if (bin_m0[f] < prev) v2 = false;
-          else { prev = bin_m0[f]; cnt[prev]++; }
-        }
-        // (a zero row inside [f_lo, f_hi) has bin_m0 == -1 < prev and lands here as "not monotone")
-        // LDS layout in floats: [0, kQPad) one dump float per lane, [kQPad, G[M]) the w0 products group by group, then at the distance
-        // `arr` the same again for w1 - its dump floats [arr, arr + kQPad) sit behind the w0 array, its products at arr + G[g].
-        // (Rounds 3-4 put the dump floats behind both arrays: the w1 dump stores of a non-contributing slot then aimed past the cube
-        // for banks beyond 6000 padded bins and relied on the LDS range check dropping them.)
-        std::vector<int> G(M + 1, kQPad);  // padded position of group g
-        for (int g2 = 0, acc = f_lo; g2 < M; ++g2) { gfirst[g2] = acc; acc += cnt[g2]; G[g2 + 1] = G[g2] + (cnt[g2] + 3) / 4 * 4; }
-        // the packed tables of the default-bank kernel want the second array at a compile-time distance: the gap behind G[M] is never read
-        const bool packed_ok = G[M] <= kMelProdArr;
-        const int arr = packed_ok ? kMelProdArr : G[M];
-        const int dump0 = 0;
-        if (v2 && arr + G[M] + 16 > 2 * kCubeElems) v2 = false;  // (a short segment's four unconditional 16-byte reads may run 12 floats past the last group)
-        // every filter must equal its two group sums exactly: check weights against the dense bank
-        for (int m = 0; m < M && v2; ++m)
-          for (int f = band_lo[m]; f < band_hi[m] && v2; ++f) {
-            const float want = h_melfb[(size_t)f * M + m];
-            v2 = (bin_m0[f] == m && bin_w0[f] == want) || (bin_m0[f] == m - 1 && bin_w1[f] == want);
-          }
-        std::vector<int> pads;
-        for (int g2 = 0; g2 < M; ++g2)
-          for (int p = G[g2] + cnt[g2]; p < G[g2 + 1]; ++p) pads.push_back(p);
-        if ((int)pads.size() > kMelPadsPerThread * kHop) v2 = false;
-        if (v2) {
-          struct SlotEntry { float w0, w1; };
-          std::vector<SlotEntry> tab(21 * (size_t)kQPad, SlotEntry{0.f, 0.f});
-          std::vector<int> tab_at(21 * (size_t)kQPad);
-          for (int kb = 0; kb < 21; ++kb)
-            for (int qp = 0; qp < kQPad; ++qp) tab_at[(size_t)kb * kQPad + qp] = dump0 + qp;
-          std::vector<char> seen(F, 0);
-          unsigned mask = 0;
-          for (int k1 = 0; k1 < 21; ++k1)
-            for (int ka = 0; ka < 21; ++ka)
-              for (int kb = 0; kb < 21; ++kb) {
-                bool cj;
-                const int bin = slot_bin(k1, ka, kb, &cj);
-                if (seen[bin]) continue;  // the duplicate slot of a bin contributes nothing
-                seen[bin] = 1;
-                if (bin < f_lo || bin >= f_hi) continue;
-                const int g2 = bin_m0[bin];
-                tab[(size_t)kb * kQPad + slot_qp(k1 * 21 + ka)] = SlotEntry{bin_w0[bin], bin_w1[bin]};
-                tab_at[(size_t)kb * kQPad + slot_qp(k1 * 21 + ka)] = G[g2] + (bin - gfirst[g2]);
-                mask |= 1u << kb;
-              }
-          std::vector<int> padtab((size_t)kMelPadsPerThread * kQPad);
-          for (int i = 0; i < kMelPadsPerThread; ++i)
-            for (int qp = 0; qp < kQPad; ++qp) padtab[(size_t)i * kQPad + qp] = dump0 + qp;
-          for (size_t i = 0; i < pads.size(); ++i) padtab[(i / kHop) * kQPad + slot_qp((int)(i % kHop))] = pads[i];
-          std::vector<int> seg(2 * (size_t)Mpad, 0);  // (first float << 4) | 16-byte reads; groups hold at most 60 bins here
-          for (int m = 0; m < M && v2; ++m) {
-            if (cnt[m] > 60) v2 = false;
-            if (m > 0) seg[m] = ((arr + G[m - 1]) << 4) | ((cnt[m - 1] + 3) / 4);  // rising: w1 products of group m-1
-            seg[(size_t)Mpad + m] = (G[m] << 4) | ((cnt[m] + 3) / 4);              // falling: w0 products of group m
-          }
-          if (v2) {
-          // packed copies for the default-bank kernel (rfx_kernels.h: pk_at / pk_pad / pk_seg)
-          std::vector<unsigned> pk;
-          const bool packed = packed_ok && (mask & ~rfx::kKbMaskLow) == 0 && G[M] * 4 <= 65536;  // (16-bit byte addresses of the first array)
-          if (packed) {
-            pk.assign(5 * (size_t)kQPad + 2 * (size_t)kQPad + 2 * (size_t)Mpad, 0u);
-            int kbs[10], n = 0;
-            for (int kb = 0; kb < 21; ++kb)
-              if ((rfx::kKbMaskLow >> kb) & 1u) kbs[n++] = kb;
-            for (int i = 0; i < 5; ++i)
-              for (int qp = 0; qp < kQPad; ++qp)
-                pk[(size_t)i * kQPad + qp] = (unsigned)(4 * tab_at[(size_t)kbs[2 * i] * kQPad + qp]) | ((unsigned)(4 * tab_at[(size_t)kbs[2 * i + 1] * kQPad + qp]) << 16);
-            unsigned* pkpad = pk.data() + 5 * (size_t)kQPad;
-            for (int qp = 0; qp < kQPad; ++qp)
-              for (int w = 0; w < 2; ++w)
-                pkpad[2 * qp + w] = (unsigned)(4 * padtab[(size_t)(2 * w) * kQPad + qp]) | ((unsigned)(4 * padtab[(size_t)(2 * w + 1) * kQPad + qp]) << 16);
-            unsigned* pkseg = pkpad + 2 * (size_t)kQPad;
-            for (int m = 0; m < Mpad; ++m) {
-              pkseg[2 * m] = (unsigned)seg[m];
-              pkseg[2 * m + 1] = (unsigned)seg[(size_t)Mpad + m];
-            }
-          }
-          RFX_HIP(hipMalloc(&pl->d_slot_tab, tab.size() * sizeof(SlotEntry)));
-          RFX_HIP(hipMemcpy(pl->d_slot_tab, tab.data(), tab.size() * sizeof(SlotEntry), hipMemcpyHostToDevice));
-          RFX_HIP(hipMalloc(&pl->d_slot_idx, (padtab.size() + seg.size() + tab_at.size() + pk.size()) * sizeof(int)));
-          RFX_HIP(hipMemcpy(pl->d_slot_idx, padtab.data(), padtab.size() * sizeof(int), hipMemcpyHostToDevice));
-          RFX_HIP(hipMemcpy(pl->d_slot_idx + padtab.size(), seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice));
-          RFX_HIP(hipMemcpy(pl->d_slot_idx + padtab.size() + seg.size(), tab_at.data(), tab_at.size() * sizeof(int), hipMemcpyHostToDevice));
-          if (packed) {
-            RFX_HIP(hipMemcpy(pl->d_slot_idx + padtab.size() + seg.size() + tab_at.size(), pk.data(), pk.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-            pl->fwd_packed_off = (int)(padtab.size() + seg.size() + tab_at.size());
-          }
-          pl->fwd_kb_mask = mask;
-          pl->fwd_prod_arr = arr;
-          }
-        }
-      }
-      pl->fwd_unfused = abl_env("RFX_FWD_UNFUSED") != nullptr;
-      if (const char* e = abl_env("RFX_FWD_RUN")) pl->fwd_run_cap = atoi(e) > 0 ? atoi(e) : 64;
-      if (const char* e = abl_env("RFX_FWD_SKEW")) pl->fwd_run_skew = atoi(e);
+    if (bank.fwd_ok) {
+      pl->fwd_unfused = fwd_unfused;
+      if (fwd_run_cap) pl->fwd_run_cap = fwd_run_cap;
+      pl->fwd_run_skew = fwd_run_skew;
     }
-    if (ok) {
-      // one device blob: csr_w | csr_ptr | band_lo | bin_m0 | bin_w0 | bin_w1 | bin_pos | bin_pos2
-      const size_t nnz = csr_w.size();
-      size_t off = 0;
-      auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-      const size_t o_w = take(nnz * 4), o_ptr = take((M + 1) * 4), o_lo = take(M * 4), o_m0 = take(F * 4),
-                   o_w0 = take(F * 4), o_w1 = take(F * 4), o_p = take(F * 4), o_p2 = take(F * 4),
-                   o_gs = take((M + 1) * 4), o_lin = take(4 * (size_t)M * 4), o_pb = take((size_t)pl->frame_stride * 4);
-      std::vector<char> blob(off);
-      memcpy(&blob[o_w], csr_w.data(), nnz * 4);
-      memcpy(&blob[o_ptr], csr_ptr.data(), (M + 1) * 4);
-      memcpy(&blob[o_lo], band_lo.data(), M * 4);
-      memcpy(&blob[o_m0], bin_m0.data(), F * 4);
-      memcpy(&blob[o_w0], bin_w0.data(), F * 4);
-      memcpy(&blob[o_w1], bin_w1.data(), F * 4);
-      memcpy(&blob[o_p], bin_pos.data(), F * 4);
-      memcpy(&blob[o_p2], bin_pos2.data(), F * 4);
-      memcpy(&blob[o_gs], grp_start.data(), (M + 1) * 4);
-      {  // output position -> bin (a bin with two slots appears at both; padding positions hold zeros)
-        std::vector<int> pos_bin((size_t)pl->frame_stride, -1);
-        for (int f = 0; f < F; ++f) {
-          if (bin_pos[f] >= 0) pos_bin[bin_pos[f]] = f;
-          if (bin_pos2[f] >= 0) pos_bin[bin_pos2[f]] = f;
-        }
-        memcpy(&blob[o_pb], pos_bin.data(), pos_bin.size() * 4);
-      }
-      if (fast && lin.size() == 4 * (size_t)M) memcpy(&blob[o_lin], lin.data(), 4 * (size_t)M * 4);
-      RFX_HIP(hipMalloc(&pl->d_imel_blob, off));
-      RFX_HIP(hipMemcpy(pl->d_imel_blob, blob.data(), off, hipMemcpyHostToDevice));
-      char* d = (char*)pl->d_imel_blob;
+    if (bank.ok) {
+      // one device blob, every table on a 256-byte boundary: csr_w | csr_ptr | band_lo | bin_m0 | bin_w0 | bin_w1 | bin_pos | bin_pos2 |
+      // grp_start | lin (zeros unless a group kernel reads it) | pos_bin
+      std::vector<char> blob;
+      auto put = [&](const void* src, size_t bytes, size_t copy) {
+        const size_t o = blob.size();
+        blob.resize(o + align_up(bytes, 256), 0);
+        if (copy) memcpy(&blob[o], src, copy);
+        return o;
+      };
+      auto ints = [&](const std::vector<int>& v, size_t n) { return put(v.data(), n * 4, n * 4); };
+      auto floats = [&](const std::vector<float>& v, size_t n) { return put(v.data(), n * 4, n * 4); };
+      const size_t o_w = floats(bank.csr_w, bank.csr_w.size()), o_ptr = ints(bank.csr_ptr, M + 1), o_lo = ints(bank.band_lo, M),
+                   o_m0 = ints(bank.bin_m0, F), o_w0 = floats(bank.bin_w0, F), o_w1 = floats(bank.bin_w1, F), o_p = ints(bank.bin_pos, F),
+                   o_p2 = ints(bank.bin_pos2, F), o_gs = ints(bank.grp_start, M + 1),
+                   o_lin = put(bank.lin.data(), 4 * (size_t)M * 4, bank.imel.fast_ok ? 4 * (size_t)M * 4 : 0),
+                   o_pb = ints(bank.pos_bin, bank.pos_bin.size());
+      RFX_HIP(upload(&pl->d_imel_blob, blob));
+      const char* d = (const char*)pl->d_imel_blob;
+      pl->imel = bank.imel;
       pl->imel.csr_w = (const float*)(d + o_w);
       pl->imel.csr_ptr = (const int*)(d + o_ptr);
       pl->imel.band_lo = (const int*)(d + o_lo);
@@ -785,18 +414,54 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
       pl->imel.bin_pos2 = (const int*)(d + o_p2);
       pl->imel.pos_bin = (const int*)(d + o_pb);
       pl->imel.grp_start = (const int*)(d + o_gs);
-      pl->imel.fast_ok = fast ? fast_code : 0;
-      pl->imel.unit_form = fast && unit_form ? 1 : 0;
       pl->imel.lin = (const float*)(d + o_lin);
-      pl->imel.wave_ok = fast && wave_ok ? 1 : 0;
-      pl->imel.line_from = line_from_out;
-      pl->imel.f_lo = f_lo;
-      pl->imel.f_hi = f_hi;
-      pl->imel.nnz = (int)nnz;
     }
   }
-  guard.p = nullptr;
-  *out_plan = pl;
+  *out_plan = pl.release();
+  return RFX_OK;
+}
+
+int rfx_debug_plan_bank(const rfx_params* params, const float* h_melfb, const rfx_plan_options* options, rfx_plan_bank_report* report) {
+  if (!params || !report) return fail(RFX_ERR_INVALID, "rfx_debug_plan_bank: null argument");
+  if (report->struct_size < 2 * sizeof(uint32_t) || report->struct_size > sizeof(rfx_plan_bank_report))
+    return fail(RFX_ERR_INVALID, "rfx_debug_plan_bank: report->struct_size does not describe an rfx_plan_bank_report this library knows");
+  rfx_plan_options opt;
+  if (const int rc = resolve_options(options, &opt)) return rc;
+  const PlanOverrides ov = plan_overrides();
+  PlanGeometry geo;
+  std::string err;
+  if (const int rc = plan_geometry(*params, opt, ov, &geo, &err)) return fail(rc, err);
+  rfx_plan_bank_report r{};
+  r.struct_size = report->struct_size;
+  r.engine = geo.engine();
+  r.frame_stride = geo.frame_stride;
+  r.imel_kernel = -1;
+  r.line_tolerance = kImelLineTol;
+  r.line_deviation = -1.0;
+  if (h_melfb) {
+    if (params->n_mels <= 0) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be positive");
+    const PlanBank bank = plan_bank(geo, params->n_mels, h_melfb, opt, ov);
+    r.imel_ok = bank.ok;
+    snprintf(r.imel_why, sizeof(r.imel_why), "%s", bank.why.c_str());
+    if (bank.ok) r.imel_kernel = rfx::imel_kernel_choice(bank.imel, params->n_mels, params->max_mel_iters, 0);
+    r.fast_ok = bank.imel.fast_ok;
+    r.unit_form = bank.imel.unit_form;
+    r.wave_ok = bank.imel.wave_ok;
+    r.line_from = bank.imel.line_from;
+    r.f_lo = bank.imel.f_lo;
+    r.f_hi = bank.imel.f_hi;
+    r.nnz = bank.imel.nnz;
+    r.fwd_ok = bank.fwd_ok;
+    r.fwd_product = bank.prod_ok;
+    r.fwd_packed = bank.packed;
+    r.fwd_kb_mask = bank.mask;
+    r.fwd_prod_arr = bank.arr;
+    r.band_rows = bank.band_rows;
+    r.Mpad = bank.Mpad;
+    r.n_kblocks = (int32_t)bank.kblocks.size();
+    r.line_deviation = bank.line_dev;
+  }
+  memcpy(report, &r, r.struct_size);
   return RFX_OK;
 }
 

@@ -53,6 +53,17 @@ class RfxPlanOptions(ctypes.Structure):
                 ("frame_engine", ctypes.c_int32), ("plan_layout", ctypes.c_int32), ("imel_form", ctypes.c_int32)]
 
 
+class RfxPlanBankReport(ctypes.Structure):
+    """rfx_plan_bank_report of include/rfx.h: what plan creation decides for a parameter set and a filterbank (tests, no GPU)."""
+
+    _fields_ = ([("struct_size", ctypes.c_uint32)]
+                + [(n, ctypes.c_int32) for n in ("engine", "frame_stride", "imel_ok", "imel_kernel", "fast_ok", "unit_form", "wave_ok",
+                                                 "line_from", "f_lo", "f_hi", "nnz", "fwd_ok", "fwd_product", "fwd_packed")]
+                + [("fwd_kb_mask", ctypes.c_uint32)]
+                + [(n, ctypes.c_int32) for n in ("fwd_prod_arr", "band_rows", "Mpad", "n_kblocks")]
+                + [("line_tolerance", ctypes.c_double), ("line_deviation", ctypes.c_double), ("imel_why", ctypes.c_char * 96)])
+
+
 class RfxCompressOptions(ctypes.Structure):
     """rfx_compress_options of include/rfx.h: rfx_pcm16_apply_filters_compressed's tables, form and flag list."""
 
@@ -111,6 +122,7 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_debug_run_start": (ctypes.c_int64, [ctypes.c_int64] * 6),
     "rfx_debug_gl_partition": (c_int, [c_int, c_int, c_int, c_void_p, c_int]),
     "rfx_debug_range_exponents": (c_int, [c_float, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "rfx_debug_plan_bank": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, ctypes.POINTER(RfxPlanBankReport)]),
     "rfx_stft_frames": (c_int, [c_void_p, c_int]),
     "rfx_plan_imel_kernel": (c_int, [c_void_p]),
     "rfx_plan_imel_unit_form": (c_int, [c_void_p]),

@@ -51,3 +51,26 @@ def mask_ill_conditioned_bins(O, mag: torch.Tensor, op, angles0: torch.Tensor, n
         mag[bad] = 0.0
         total += n
     return mag, total
+
+
+def plan_bank_report(op, fb="oracle", frame_engine: str = "auto", plan_layout: str = "auto", imel_form: str = "auto"):
+    """rfx_debug_plan_bank (include/rfx.h, no GPU): what rfx_plan_create_ex decides for the oracle parameter set `op`, its
+    filterbank as the oracle builds it (or the (n_stft, n_mels) float32 tensor `fb`, or None for a plan without one) and the
+    given plan options.  Raises RfxError where plan creation refuses the geometry."""
+    import ctypes
+
+    import riffusion_oracle as O
+    from riffusion import _hip
+
+    lib = _hip.load_library()
+    if isinstance(fb, str):
+        fb = O.mel_filterbank(op)
+    if fb is not None:
+        fb = fb.to(torch.float32).contiguous()
+        assert tuple(fb.shape) == (op.n_stft, op.num_frequencies)
+    cp = _hip.RfxParams(op.sample_rate, op.n_fft, op.win_length, op.hop_length, op.num_frequencies, op.max_mel_iters)
+    opt = _hip.RfxPlanOptions(ctypes.sizeof(_hip.RfxPlanOptions), 0, 0, _hip.FRAME_ENGINES[frame_engine], _hip.PLAN_LAYOUTS[plan_layout],
+                              _hip.IMEL_FORMS[imel_form])
+    report = _hip.RfxPlanBankReport(struct_size=ctypes.sizeof(_hip.RfxPlanBankReport))
+    _hip.check(lib.rfx_debug_plan_bank(ctypes.byref(cp), fb.data_ptr() if fb is not None else None, ctypes.byref(opt), ctypes.byref(report)))
+    return report

@@ -35,7 +35,10 @@ def _bank(p):
 
 
 def test_weights_of_the_long_groups_sum_to_one_for_the_default_bank_only():
-    """What rfx_plan_create checks before it enables the unit form (rfx_plan_imel_unit_form)."""
+    """What rfx_plan_create checks before it enables the unit form (rfx_plan_imel_unit_form): restated here, and as the library's
+    own analysis decides it (rfx_debug_plan_bank, csrc/rfx_plan_core.h::bank_sgd_admission) for the same two banks."""
+    from helpers import plan_bank_report
+
     for norm, expect in ((None, True), ("slaney", False)):
         p = O.OracleParams(mel_scale_norm=norm)
         fb, act, first, w0, w1 = _bank(p)
@@ -47,6 +50,7 @@ def test_weights_of_the_long_groups_sum_to_one_for_the_default_bank_only():
                 continue
             ok = ok and ((w1[f] == 0) if g == M - 1 else abs(float(w0[f]) + float(w1[f]) - 1.0) <= 1e-6)
         assert ok == expect, norm
+        assert bool(plan_bank_report(p).unit_form) == ok, norm
 
 
 @pytest.mark.parametrize("unit_form", [False, True])

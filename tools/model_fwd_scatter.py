@@ -1,7 +1,7 @@
 """LDS bank model of stft_mel2_kernel's product exchange (no GPU): per wave-instruction conflict cycles of the scatter
 (`ds_write_b32`: two groups of 32 lanes, bank = dword address mod 32) and of the segment reads (`ds_read_b128`: four groups of
 16 lanes, bank = dword address mod 64, four banks per lane), for a given placement G[g] of the filter groups in the product
-array (rfx_api.hip: `G`, `tab_at`, `seg`).  MI355X_MICROARCH.md, section LDS, is the rule book.
+array (rfx_plan_core.h::bank_forward_products: `G`, `tab_at`, `seg`).  MI355X_MICROARCH.md, section LDS, is the rule book.
 
   python tools/model_fwd_scatter.py             # the plan's dense placement against the searched one
 """
@@ -110,7 +110,7 @@ def positions(G, gfirst, cnt):
 
 
 def dense_placement(cnt):
-    G = KQ + np.concatenate([[0], np.cumsum((cnt + 3) // 4 * 4)])  # the groups follow the dump floats (rfx_api.hip: G[0] = kQPad)
+    G = KQ + np.concatenate([[0], np.cumsum((cnt + 3) // 4 * 4)])  # the groups follow the dump floats (rfx_plan_core.h::bank_forward_products: G[0] = kQPad)
     return G[:-1], int(G[-1])
 
 
