@@ -1,0 +1,187 @@
+// rfx_api_codec.hip - the C ABI of librfx.so (include/rfx.h), the entry points that take no plan: image decode / encode, int16 PCM,
+// its filters, compressor and stitch, and the image resize.  They run on the device that owns their output buffer.
+#include "rfx_api.h"
+#include "rfx_compress_core.h"
+#include "rfx_pcm_core.h"
+#include "rfx_resize_core.h"
+
+using namespace rfx;
+
+// device that owns a caller buffer (the codec entry points take no plan)
+static int device_of(const void* d_ptr, int* device) {
+  hipPointerAttribute_t attr;
+  const hipError_t e = hipPointerGetAttributes(&attr, d_ptr);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(RFX_ERR_INVALID, std::string("not a device pointer: ") + hipGetErrorString(e));
+  }
+  *device = attr.device;
+  return RFX_OK;
+}
+
+int rfx_image_decode_u8(const uint8_t* d_img, int N, int H, int W, int stereo, const float* d_lut256, float* d_mel_out,
+                        void* stream) {
+  if (!d_img || !d_lut256 || !d_mel_out || N <= 0 || H <= 0 || W <= 0) return fail(RFX_ERR_INVALID, "rfx_image_decode_u8: bad argument");
+  int dev;
+  if (int rc = device_of(d_mel_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_image_decode(d_img, d_lut256, d_mel_out, N, H, W, stereo ? 2 : 1, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+int rfx_image_encode_u8(const float* d_mel, int N, int M, int T, int stereo, const float* d_thresholds255, float* d_clip_max,
+                        uint8_t* d_img_out, void* stream) {
+  if (!d_mel || !d_thresholds255 || !d_clip_max || !d_img_out || N <= 0 || M <= 0 || T <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_image_encode_u8: bad argument");
+  int dev;
+  if (int rc = device_of(d_img_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  const int C = stereo ? 2 : 1;
+  RFX_HIP(launch_clip_max(d_mel, d_clip_max, N, (size_t)C * M * T, false, (hipStream_t)stream));
+  RFX_HIP(launch_image_encode(d_mel, d_clip_max, d_thresholds255, d_img_out, N, M, T, C, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+int rfx_pcm16(const float* d_wave, int N, int C, int L, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* stream) {
+  if (!d_wave || !d_clip_peak || !d_pcm_out || N <= 0 || C <= 0 || L <= 0) return fail(RFX_ERR_INVALID, "rfx_pcm16: bad argument");
+  int dev;
+  if (int rc = device_of(d_pcm_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  if (normalize) RFX_HIP(launch_clip_max(d_wave, d_clip_peak, N, (size_t)C * L, true, (hipStream_t)stream));
+  RFX_HIP(launch_pcm16(d_wave, d_clip_peak, d_pcm_out, N, L, C, normalize, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+size_t rfx_pcm16_filters_workspace_bytes(int N, int L, int C) {
+  if (N <= 0 || L <= 0 || C <= 0) return 0;
+  return pcm_filters_workspace_bytes(N, L, C);
+}
+
+int rfx_pcm16_apply_filters(const int16_t* d_pcm_in, int N, int L, int C, const double* d_gain_by_rms, const double* d_boost_by_peak,
+                            int16_t* d_pcm_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!d_pcm_in || !d_gain_by_rms || !d_boost_by_peak || !d_pcm_out || !d_workspace || N <= 0 || L <= 0 || C <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters: bad argument");
+  if ((int64_t)L * C >= ((int64_t)1 << 23))
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_pcm16_apply_filters: L * C >= 2^23 (audioop.rms is exact only below that)");
+  if (workspace_bytes < pcm_filters_workspace_bytes(N, L, C)) return fail(RFX_ERR_WORKSPACE, "rfx_pcm16_apply_filters: workspace too small");
+  int dev;
+  if (int rc = device_of(d_pcm_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_pcm_filters(d_pcm_in, N, L, C, d_gain_by_rms, d_boost_by_peak, d_pcm_out, d_workspace, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+int rfx_pcm16_stitch(const int16_t* d_pcm, int N, int L, int C, const rfx_stitch_piece* h_pieces, const rfx_stitch_piece* d_pieces,
+                     int n_pieces, int64_t out_frames, int16_t* d_out, void* stream) {
+  static_assert(sizeof(rfx_stitch_piece) == sizeof(PcmPiece), "rfx_stitch_piece is PcmPiece (rfx_pcm_core.h)");
+  if (!d_pcm || !h_pieces || !d_pieces || !d_out || N <= 0 || L <= 0 || C <= 0 || n_pieces <= 0 || out_frames <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_stitch: bad argument");
+  // every read the kernel will make stays inside the batch: checked here, on the host table
+  if (h_pieces[0].out_start != 0) return fail(RFX_ERR_INVALID, "rfx_pcm16_stitch: the first piece must start at frame 0");
+  for (int k = 0; k < n_pieces; ++k) {
+    const rfx_stitch_piece& p = h_pieces[k];
+    const int64_t next = k + 1 < n_pieces ? h_pieces[k + 1].out_start : out_frames;
+    const int64_t count = next - p.out_start;
+    bool ok = count > 0 && (p.kind == 0 || p.kind == 1);
+    ok = ok && (p.a_clip < 0 || (p.a_clip < N && p.a_off >= 0 && p.a_off + count <= L));
+    ok = ok && (p.kind == 0 || p.b_clip < 0 || (p.b_clip < N && p.b_off >= 0 && p.b_off + count <= L));
+    if (!ok) return fail(RFX_ERR_INVALID, "rfx_pcm16_stitch: piece " + std::to_string(k) + " is empty or reads outside the batch");
+  }
+  int dev;
+  if (int rc = device_of(d_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_pcm_stitch(d_pcm, L, C, d_pieces, n_pieces, out_frames, d_out, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+static bool resize_args_ok(int N, int H, int W, int out_h, int out_w, int filter) {
+  const auto in_range = [](int v) { return v >= 1 && v <= kRszMaxSize; };
+  return N >= 1 && in_range(H) && in_range(W) && in_range(out_h) && in_range(out_w) && rsz_support(filter) > 0.0;
+}
+
+int rfx_image_resize_coefficients(int in_size, int out_size, int filter, int32_t* h_bounds, int32_t* h_kk, int capacity) {
+  if (in_size < 1 || in_size > kRszMaxSize || out_size < 1 || out_size > kRszMaxSize || rsz_support(filter) == 0.0)
+    return fail(RFX_ERR_INVALID, "rfx_image_resize_coefficients: sizes must be in [1, 16384] and the filter RFX_RESIZE_LANCZOS, "
+                                 "_BILINEAR or _BICUBIC");
+  const int ksize = rsz_ksize(in_size, out_size, filter);
+  if (!h_bounds && !h_kk) return ksize;
+  if (!h_bounds || !h_kk) return fail(RFX_ERR_INVALID, "rfx_image_resize_coefficients: h_bounds and h_kk go together");
+  if ((int64_t)capacity < (int64_t)out_size * ksize)
+    return fail(RFX_ERR_WORKSPACE, "rfx_image_resize_coefficients: h_kk holds fewer than out_size * ksize entries");
+  std::vector<double> w(ksize);
+  return rsz_coefficients(in_size, out_size, filter, h_bounds, h_kk, w.data());
+}
+
+size_t rfx_image_resize_workspace_bytes(int N, int H, int W, int out_h, int out_w, int filter) {
+  if (!resize_args_ok(N, H, W, out_h, out_w, filter)) return 0;
+  return resize_workspace_bytes(N, H, W, out_h, out_w);
+}
+
+int rfx_image_resize_u8(const uint8_t* d_in, int N, int H, int W, int out_h, int out_w, int filter, const int32_t* d_bounds_x,
+                        const int32_t* d_kk_x, const int32_t* d_bounds_y, const int32_t* d_kk_y, uint8_t* d_out, void* d_workspace,
+                        size_t workspace_bytes, void* stream) {
+  if (!d_in || !d_out || !resize_args_ok(N, H, W, out_h, out_w, filter))
+    return fail(RFX_ERR_INVALID, "rfx_image_resize_u8: bad argument (N >= 1, sizes in [1, 16384], filter RFX_RESIZE_LANCZOS, "
+                                 "_BILINEAR or _BICUBIC)");
+  if (out_w != W && (!d_bounds_x || !d_kk_x)) return fail(RFX_ERR_INVALID, "rfx_image_resize_u8: the width changes: need d_bounds_x, d_kk_x");
+  if (out_h != H && (!d_bounds_y || !d_kk_y)) return fail(RFX_ERR_INVALID, "rfx_image_resize_u8: the height changes: need d_bounds_y, d_kk_y");
+  const size_t need = resize_workspace_bytes(N, H, W, out_h, out_w);
+  if (need && (!d_workspace || workspace_bytes < need)) return fail(RFX_ERR_WORKSPACE, "rfx_image_resize_u8: workspace too small");
+  int dev;
+  if (int rc = device_of(d_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_resize(d_in, N, H, W, out_h, out_w, d_bounds_x, d_kk_x, rsz_ksize(W, out_w, filter), d_bounds_y, d_kk_y,
+                        rsz_ksize(H, out_h, filter), d_out, d_workspace, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+size_t rfx_pcm16_compress_filters_workspace_bytes(int N, int L, int C) {
+  if (N <= 0 || L <= 0 || C <= 0) return 0;
+  return cmp_workspace_layout(N, L, C).total;
+}
+
+int rfx_pcm16_apply_filters_compressed(const int16_t* d_pcm_in, int N, int L, int C, rfx_compress_options* o, int16_t* d_pcm_out,
+                                       void* d_workspace, size_t workspace_bytes, void* stream) {
+  static_assert(sizeof(CmpFlag) == 24, "rfx_compress_options.d_flags entries are CmpFlag (rfx_compress_core.h)");
+  if (!d_pcm_in || !o || !d_pcm_out || !d_workspace || N <= 0 || L <= 0 || C <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters_compressed: bad argument");
+  if (o->struct_size != sizeof(rfx_compress_options))
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters_compressed: options->struct_size is not sizeof(rfx_compress_options)");
+  if (!o->d_gain10_by_rms || !o->d_gain12_by_rms || !o->d_boost_by_peak || !o->d_above || !o->d_max_att || !o->d_inc || !o->d_dec)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters_compressed: a table is missing");
+  if ((o->form != RFX_COMPRESS_SEQUENTIAL && o->form != RFX_COMPRESS_CHUNKED) || o->look_frames < 0 || o->chunk_frames < 0 ||
+      !(o->margin >= 0.0) || o->flag_capacity < 0 || (o->flag_capacity > 0 && !o->d_flags))
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_apply_filters_compressed: bad option");
+  if ((int64_t)L * C >= ((int64_t)1 << 23))
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_pcm16_apply_filters_compressed: L * C >= 2^23 (audioop.rms is exact only below that)");
+  const CmpLayout w = cmp_workspace_layout(N, L, C);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_pcm16_apply_filters_compressed: workspace too small");
+  int dev;
+  if (int rc = device_of(d_pcm_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  const hipStream_t s = (hipStream_t)stream;
+  RFX_HIP(launch_cmp_compress(d_pcm_in, N, L, C, o->d_boost_by_peak, o->d_gain10_by_rms, o->d_above, o->d_max_att, o->d_inc, o->d_dec,
+                              o->look_frames, o->form, o->chunk_frames, o->margin, o->d_flags, o->flag_capacity, o->d_rounds, d_workspace, s));
+  // the one synchronisation of this path: how many products need the host's pow
+  unsigned long long n = 0;
+  RFX_HIP(hipMemcpyAsync(&n, (char*)d_workspace + w.count, sizeof n, hipMemcpyDeviceToHost, s));
+  RFX_HIP(hipStreamSynchronize(s));
+  o->n_flagged = (int64_t)n;
+  if ((int64_t)n > o->flag_capacity) return RFX_OK;  // documented: d_pcm_out is not written, the caller redoes the batch on the host
+  int16_t* x3 = reinterpret_cast<int16_t*>((char*)d_workspace + w.x3);
+  if (n > 0) {
+    std::vector<CmpFlag> h(n);
+    RFX_HIP(hipMemcpyAsync(h.data(), o->d_flags, n * sizeof(CmpFlag), hipMemcpyDeviceToHost, s));
+    RFX_HIP(hipStreamSynchronize(s));
+    const int64_t total = (int64_t)N * L * C;
+    for (CmpFlag& f : h) {
+      if (f.index < 0 || f.index >= total) return fail(RFX_ERR_HIP, "rfx_pcm16_apply_filters_compressed: corrupt flag list");
+      f.value = pcm_mul(f.x2, cmp_gain_host(f.att));
+    }
+    RFX_HIP(hipMemcpyAsync(o->d_flags, h.data(), n * sizeof(CmpFlag), hipMemcpyHostToDevice, s));
+    RFX_HIP(launch_cmp_scatter(o->d_flags, (int64_t)n, x3, s));
+    RFX_HIP(hipStreamSynchronize(s));  // h is released on return
+  }
+  RFX_HIP(launch_pcm_filters(x3, N, L, C, o->d_gain12_by_rms, o->d_boost_by_peak, d_pcm_out, (char*)d_workspace + w.filters, s));
+  return RFX_OK;
+}

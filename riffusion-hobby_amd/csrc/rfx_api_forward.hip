@@ -1,0 +1,313 @@
+// rfx_api_forward.hip - the C ABI of librfx.so (include/rfx.h), forward half: layout conversion, STFT, the mel projections and
+// the image of a waveform.  Host code only: the drivers that sequence the kernels.
+#include "rfx_api.h"
+
+using namespace rfx;
+
+// the forward transform of a row-family plan (rfx_fam.hip): everything but the outputs of the mode that is launched
+static FamFwdArgs fam_fwd_args(const rfx_plan* plan, const float* d_wave, int B, int Lw) {
+  const FamGeom& f = plan->fam;
+  FamFwdArgs fa{};
+  fa.g = f;
+  fa.wave = d_wave;
+  fa.wave_stride = (size_t)Lw;
+  fa.Lw = Lw;
+  fa.fs_plain = plan->gg.fs;
+  fa.tw1 = plan->d_fam_tw;
+  fa.twa = plan->d_fam_tw + (size_t)f.rows * f.h;
+  fa.win = plan->d_win;
+  fa.B = B;
+  fa.T = stft_frames(plan, Lw);
+  return fa;
+}
+
+int rfx_pack_magnitudes(const rfx_plan* plan, const float* d_lin_bft, int B, int T, float* d_slots, void* stream) {
+  if (!plan || !d_lin_bft || !d_slots || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_pack_magnitudes: bad argument");
+  RFX_ON_DEVICE(plan->device);
+  if (plan->generic) RFX_HIP(launch_gen_pack(d_lin_bft, d_slots, false, B, plan->n_stft, T, plan->gg.fs, (hipStream_t)stream));
+  else RFX_HIP(launch_pack_mag(d_lin_bft, d_slots, B, T, (hipStream_t)stream));
+  return RFX_OK;
+}
+int rfx_pack_complex(const rfx_plan* plan, const void* d_bft, int B, int T, void* d_slots, void* stream) {
+  if (!plan || !d_bft || !d_slots || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_pack_complex: bad argument");
+  RFX_ON_DEVICE(plan->device);
+  if (plan->generic) RFX_HIP(launch_gen_pack(d_bft, d_slots, true, B, plan->n_stft, T, plan->gg.fs, (hipStream_t)stream));
+  else RFX_HIP(launch_pack_angles((const cf*)d_bft, (cf*)d_slots, B, T, (hipStream_t)stream));
+  return RFX_OK;
+}
+int rfx_unpack_complex(const rfx_plan* plan, const void* d_slots, int B, int T, void* d_bft, void* stream) {
+  if (!plan || !d_bft || !d_slots || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_unpack_complex: bad argument");
+  RFX_ON_DEVICE(plan->device);
+  if (plan->generic) RFX_HIP(launch_gen_unpack(d_slots, d_bft, true, B, plan->n_stft, T, plan->gg.fs, (hipStream_t)stream));
+  else RFX_HIP(launch_unpack_complex((const cf*)d_slots, (cf*)d_bft, B, T, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+int rfx_unpack_magnitudes(const rfx_plan* plan, const float* d_slots, int B, int T, float* d_bft, void* stream) {
+  if (!plan || !d_bft || !d_slots || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_unpack_magnitudes: bad argument");
+  RFX_ON_DEVICE(plan->device);
+  if (plan->generic) RFX_HIP(launch_gen_unpack(d_slots, d_bft, false, B, plan->n_stft, T, plan->gg.fs, (hipStream_t)stream));
+  else RFX_HIP(launch_unpack_mag(d_slots, d_bft, B, T, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+int rfx_stft(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots,
+             void* stream) {
+  if (!plan || !d_wave || B <= 0) return fail(RFX_ERR_INVALID, "rfx_stft: bad argument");
+  // torch.stft(center=True, pad_mode="reflect") raises when the pad n_fft/2 is not smaller than the input
+  if (Lw <= plan->p.n_fft / 2)
+    return fail(RFX_ERR_INVALID, "rfx_stft: reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
+  RFX_ON_DEVICE(plan->device);
+  if (plan->fam_ok) {  // row-family kernels (rfx_fam.hip), same plain layout as the generic engine's
+    FamFwdArgs fa = fam_fwd_args(plan, d_wave, B, Lw);
+    fa.mag = d_mag_slots;
+    fa.spec = (cf*)d_spec_slots;
+    const int nblocks = frame_blocks(fam_slot_count(plan), B, fa.T);
+    if (d_mag_slots) RFX_HIP(launch_fam_fwd(0, fa, nblocks, (hipStream_t)stream));
+    if (d_spec_slots) RFX_HIP(launch_fam_fwd(1, fa, nblocks, (hipStream_t)stream));
+    return RFX_OK;
+  }
+  if (plan->generic) {
+    GenStftArgs g{};
+    g.g = plan->gg;
+    g.tb = plan->gt;
+    g.wave = d_wave;
+    g.wave_stride = (size_t)Lw;
+    g.mag = d_mag_slots;
+    g.spec = (cf*)d_spec_slots;
+    g.B = B;
+    g.T = stft_frames(plan, Lw);
+    g.Lw = Lw;
+    if (d_mag_slots) RFX_HIP(launch_gen_stft(0, g, plan->num_cus, (hipStream_t)stream));
+    if (d_spec_slots) RFX_HIP(launch_gen_stft(1, g, plan->num_cus, (hipStream_t)stream));
+    return RFX_OK;
+  }
+  StftArgs a;
+  a.wave = d_wave;
+  a.mag = d_mag_slots;
+  a.spec = (cf*)d_spec_slots;
+  a.tw1 = plan->d_tw1;
+  a.tw2 = plan->d_tw2;
+  a.win = plan->d_win;
+  a.B = B;
+  a.Lw = Lw;
+  a.T = 1 + Lw / kHop;
+  const long long frames = (long long)B * a.T;
+  int fpb = (int)((frames + 2LL * plan->num_cus - 1) / (2LL * plan->num_cus));
+  if (fpb < 1) fpb = 1;
+  if (fpb > 16) fpb = 16;
+  a.frames_per_block = fpb;
+  RFX_HIP(launch_stft(a, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+// ---- mel projection -------------------------------------------------------------------------------------------------------------
+// Magnitudes [B*T][frame_stride], then - generic plans - the frame-major mel amplitudes [B*T][Mpad].  The fused kernel of the
+// specialised engine keeps the magnitudes on chip: its scratch is the frame-major amplitudes alone.
+struct MelLayout {
+  size_t mag, mel_tm, total;
+};
+static MelLayout mel_layout(const rfx_plan* plan, int B, int T, bool mag_on_chip) {
+  MelLayout l{};
+  if (B <= 0 || T <= 0) return l;
+  const size_t nf = (size_t)B * T;
+  Carve c;
+  l.mag = c.take(mag_on_chip ? 0 : nf * plan->frame_stride * sizeof(float));
+  l.mel_tm = c.take(plan->generic || mag_on_chip ? nf * plan->Mpad * sizeof(float) : 0);
+  l.total = c.at;
+  return l;
+}
+static MelLayout mel_forward_layout(const rfx_plan* plan, int B, int Lw) {
+  if (Lw <= plan->p.n_fft / 2) return MelLayout{};
+  return mel_layout(plan, B, stft_frames(plan, Lw), !plan->generic && plan->fwd_ok && !plan->fwd_unfused);
+}
+size_t rfx_mel_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? mel_forward_layout(plan, B, Lw).total : 0; }
+size_t rfx_mel_scale_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? mel_layout(plan, B, T, false).total : 0; }
+
+// does the plan's forward path leave the mel amplitudes frame-major ([B*T][Mpad]) in the workspace before transposing them?
+static bool forward_has_frame_major(const rfx_plan* plan) { return plan->generic ? plan->fwd_ok : (plan->fwd_ok && !plan->fwd_unfused); }
+
+// specialised engine: the MFMA GEMM over slot-ordered magnitudes [B*T][kFrameStride] -> (B, M, T)
+static int mel_gemm(const rfx_plan* plan, const float* mag, int B, int T, float* d_mel_out, hipStream_t stream) {
+  MelArgs a;
+  a.mag = mag;
+  a.fbs = plan->d_melfb_slots;
+  a.kblocks = plan->d_kblocks;
+  a.n_kblocks = plan->n_kblocks;
+  a.out = d_mel_out;
+  a.M = plan->p.n_mels;
+  a.Mp = plan->melfb_cols;
+  a.T = T;
+  a.N = B * T;
+  RFX_HIP(launch_mel_gemm(a, stream));
+  return RFX_OK;
+}
+// generic plans: the banded projection of plain magnitudes (mag null: mel_tm holds the amplitudes already) and, where the caller
+// wants the tensor, the transpose to (B, M, T)
+static int gen_mel(const rfx_plan* plan, const float* mag, float* mel_tm, int B, int T, float* d_mel_out, hipStream_t stream) {
+  if (mag)
+    RFX_HIP(launch_gen_mel(mag, mel_tm, plan->d_band_wt, plan->d_band_lo, plan->d_band_lo + plan->Mpad, (long long)B * T, plan->gg.fs,
+                           plan->p.n_mels, plan->Mpad, plan->imel.f_lo, plan->imel.f_hi, stream));
+  if (d_mel_out) RFX_HIP(launch_mel_transpose(mel_tm, d_mel_out, B, T, plan->p.n_mels, plan->Mpad, stream));
+  return RFX_OK;
+}
+
+// rfx_mel_from_waveform, and the front half of rfx_image_from_waveform: there d_mel_out is null (no (B, M, T) copy is made),
+// *mel_tm_out receives the frame-major amplitudes and - where the kernel can take it on the fly - max_keys the keys of the maxima its
+// workgroups formed, *keys_per_row of them for every row, rows in order (0: it did not; up to T per row: image_keys_bytes)
+static int mel_forward(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mel_out, void* d_workspace, size_t workspace_bytes,
+                       void* stream_, float** mel_tm_out, unsigned* max_keys, int max_group, int* keys_per_row) {
+  if (!plan || !d_wave || !d_workspace || (!d_mel_out && !mel_tm_out)) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform: null argument");
+  if (!plan->d_melfb) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform: plan was created without a mel filterbank");
+  const MelLayout w = mel_forward_layout(plan, B, Lw);
+  if (workspace_bytes < w.total || Lw <= plan->p.n_fft / 2)
+    return fail(Lw <= plan->p.n_fft / 2 ? RFX_ERR_INVALID : RFX_ERR_WORKSPACE, "rfx_mel_from_waveform: input too short or workspace too small");
+  RFX_ON_DEVICE(plan->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  float* mag = (float*)((char*)d_workspace + w.mag);
+  float* mel_tm = (float*)((char*)d_workspace + w.mel_tm);
+  const int T = stft_frames(plan, Lw);
+  if (plan->generic) {
+    if (!plan->fwd_ok) return fail(RFX_ERR_UNSUPPORTED, "rfx_mel_from_waveform: filterbank is not banded: " + plan->imel_why);
+    const bool fused = plan->fam_ok && !plan->fwd_unfused;
+    if (fused) {  // row family: transform and banded projection in one kernel, |X| stays on chip
+      FamFwdArgs fa = fam_fwd_args(plan, d_wave, B, Lw);
+      fa.mel_tm = mel_tm;
+      fa.band_wt = plan->d_band_wt;
+      fa.band_lo = plan->d_band_lo;
+      fa.band_len = plan->d_band_lo + plan->Mpad;
+      fa.M = plan->p.n_mels;
+      fa.Mpad = plan->Mpad;
+      RFX_HIP(launch_fam_fwd(2, fa, frame_blocks(fam_slot_count(plan), B, T), stream));
+    } else if (int rc = rfx_stft(plan, d_wave, B, Lw, mag, nullptr, stream)) {
+      return rc;
+    }
+    if (mel_tm_out) *mel_tm_out = mel_tm;
+    return gen_mel(plan, fused ? nullptr : mag, mel_tm, B, T, d_mel_out, stream);
+  }
+  if (plan->fwd_ok && !plan->fwd_unfused) {
+    StftMelArgs f;
+    f.wave = d_wave;
+    f.mel = d_mel_out;
+    f.mel_tm = mel_tm;
+    f.tw1 = plan->d_tw1;
+    f.tw2 = plan->d_tw2;
+    f.win = plan->d_win;
+    f.band_wt = plan->d_band_wt;
+    f.band_addr = plan->d_band_addr;
+    f.band_lo = plan->d_band_lo;
+    f.band_len = plan->d_band_lo + plan->Mpad;
+    f.B = B;
+    f.Lw = Lw;
+    f.T = T;
+    f.M = plan->p.n_mels;
+    f.Mpad = plan->Mpad;
+    f.f_lo = plan->imel.f_lo;
+    f.f_hi = plan->imel.f_hi;
+    f.slot_tab = plan->d_slot_tab;
+    f.pad_tab = plan->d_slot_idx;
+    f.filt_seg = plan->d_slot_idx ? plan->d_slot_idx + (size_t)kMelPadsPerThread * kQPad : nullptr;
+    f.slot_at = plan->d_slot_idx ? f.filt_seg + 2 * (size_t)plan->Mpad : nullptr;
+    f.prod_arr = plan->fwd_prod_arr;
+    f.kb_mask = plan->fwd_kb_mask;
+    f.pk_at = plan->fwd_packed_off ? reinterpret_cast<const unsigned*>(plan->d_slot_idx + plan->fwd_packed_off) : nullptr;
+    f.pk_pad = f.pk_at ? f.pk_at + 5 * (size_t)kQPad : nullptr;
+    f.pk_seg = f.pk_at ? f.pk_pad + 2 * (size_t)kQPad : nullptr;
+    f.max_keys = plan->d_slot_tab ? max_keys : nullptr;  // (the product-form kernel takes the maximum on the fly)
+    f.max_group = max_group > 0 ? max_group : 1;
+    if (mel_tm_out) *mel_tm_out = f.mel_tm;
+    // runs of consecutive frames: every resident workgroup slot of the chip gets one run when the batch allows it (the
+    // product-form kernel carries a sliding input window along a run), at most 64 frames, at least 1
+    const long long frames = (long long)B * f.T;
+    const int cap = plan->d_slot_tab ? plan->fwd_run_cap : 16;
+    int fpb = (int)((frames + 2LL * plan->num_cus - 1) / (2LL * plan->num_cus));
+    f.frames_per_block = fpb < 1 ? 1 : fpb > cap ? cap : fpb;
+    {  // unequal runs by dispatch order (StftMelArgs::run_skew), only in the shape it was measured in: one wave of workgroups, two per CU
+      const int chunks = (f.T + f.frames_per_block - 1) / f.frames_per_block;
+      const bool shape_ok = plan->d_slot_tab && chunks % 2 == 0 && chunks * f.frames_per_block == f.T && (long long)B * chunks == 2LL * plan->num_cus;
+      const int d = (int)((long long)f.frames_per_block * plan->fwd_run_skew / 1000);
+      f.run_skew = shape_ok && d > 0 && d < f.frames_per_block ? d : 0;
+      if (keys_per_row) *keys_per_row = f.max_keys ? chunks : 0;
+    }
+    RFX_HIP(launch_stft_mel(f, stream));
+    return RFX_OK;
+  }
+  if (!d_mel_out) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform: this plan's forward path has no frame-major stage");
+  if (int rc = rfx_stft(plan, d_wave, B, Lw, mag, nullptr, stream)) return rc;
+  return mel_gemm(plan, mag, B, T, d_mel_out, stream);
+}
+
+int rfx_mel_from_waveform(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mel_out, void* d_workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (!d_mel_out) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform: null argument");
+  return mel_forward(plan, d_wave, B, Lw, d_mel_out, d_workspace, workspace_bytes, stream, nullptr, nullptr, 1, nullptr);
+}
+
+// ---- spectrogram_image_from_audio's device half (spectrogram_image_converter.py:30-51: spectrogram_from_audio, then
+// image_util.image_from_spectrogram): waveforms -> mel amplitudes -> uint8 image without the (B, M, T) tensor in between.
+// The forward path's workspace, then the keys of its maxima - the forward kernel leaves one per workgroup, at most one workgroup
+// per frame - and, for a plan without a frame-major stage, the (B, M, T) tensor.
+struct ImageFwdLayout {
+  size_t keys, mel, total;  // keys is also the size of the forward path's part, which starts the workspace
+};
+static ImageFwdLayout image_from_waveform_layout(const rfx_plan* plan, int N, int stereo, int Lw) {
+  ImageFwdLayout l{};
+  if (N <= 0) return l;
+  const int B = N * (stereo ? 2 : 1);
+  Carve c;
+  c.at = mel_forward_layout(plan, B, Lw).total;
+  if (!c.at) return l;
+  const size_t T = (size_t)stft_frames(plan, Lw);
+  l.keys = c.take((size_t)B * T * sizeof(unsigned));
+  l.mel = c.take(forward_has_frame_major(plan) ? 0 : (size_t)B * plan->p.n_mels * T * sizeof(float));
+  l.total = c.at;
+  return l;
+}
+size_t rfx_image_from_waveform_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw) {
+  return plan ? image_from_waveform_layout(plan, N, stereo, Lw).total : 0;
+}
+
+int rfx_image_from_waveform(const rfx_plan* plan, const float* d_wave, int N, int stereo, int Lw, const float* d_thresholds255,
+                            float* d_clip_max, uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!plan || !d_wave || !d_thresholds255 || !d_clip_max || !d_img_out || !d_workspace || N <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_image_from_waveform: bad argument");
+  if (!plan->d_melfb) return fail(RFX_ERR_INVALID, "rfx_image_from_waveform: plan was created without a mel filterbank");
+  if (Lw <= plan->p.n_fft / 2) return fail(RFX_ERR_INVALID, "rfx_image_from_waveform: input too short");
+  const ImageFwdLayout w = image_from_waveform_layout(plan, N, stereo, Lw);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_image_from_waveform: workspace too small");
+  RFX_ON_DEVICE(plan->device);
+  const int C = stereo ? 2 : 1, B = N * C, T = stft_frames(plan, Lw), M = plan->p.n_mels;
+  unsigned* keys = reinterpret_cast<unsigned*>((char*)d_workspace + w.keys);
+  if (!forward_has_frame_major(plan)) {  // (dense-GEMM fall-back of a non-banded bank: the two calls, the tensor in the workspace)
+    float* mel = reinterpret_cast<float*>((char*)d_workspace + w.mel);
+    if (int rc = rfx_mel_from_waveform(plan, d_wave, B, Lw, mel, d_workspace, w.keys, stream)) return rc;
+    return rfx_image_encode_u8(mel, N, M, T, stereo, d_thresholds255, d_clip_max, d_img_out, stream);
+  }
+  float* mel_tm = nullptr;
+  int keys_per_row = 0;  // (round 6: one key per workgroup of the forward kernel, every one written by the launch: nothing to zero)
+  if (int rc = mel_forward(plan, d_wave, B, Lw, nullptr, d_workspace, w.keys, stream, &mel_tm, keys, C, &keys_per_row)) return rc;
+  // (a kernel that does not take the maximum on the fly: one pass over the frame-major amplitudes; their padding columns are zero
+  // and mel amplitudes are not negative)
+  if (!keys_per_row) RFX_HIP(launch_clip_max(mel_tm, reinterpret_cast<float*>(keys), N, (size_t)C * T * plan->Mpad, false, (hipStream_t)stream));
+  RFX_HIP(launch_image_encode_tm(mel_tm, keys_per_row ? keys : nullptr, C * keys_per_row, keys_per_row ? nullptr : reinterpret_cast<const float*>(keys),
+                                 d_thresholds255, d_img_out, d_clip_max, N, M, plan->Mpad, T, C, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+int rfx_mel_scale(const rfx_plan* plan, const float* d_lin_bft, int B, int T, float* d_mel_out, void* d_workspace,
+                  size_t workspace_bytes, void* stream_) {
+  if (!plan || !d_lin_bft || !d_mel_out || !d_workspace || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_mel_scale: bad argument");
+  if (!plan->d_melfb) return fail(RFX_ERR_INVALID, "rfx_mel_scale: plan was created without a mel filterbank");
+  const MelLayout w = mel_layout(plan, B, T, false);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_mel_scale: workspace too small");
+  RFX_ON_DEVICE(plan->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  float* mag = (float*)((char*)d_workspace + w.mag);
+  if (plan->generic) {
+    if (!plan->fwd_ok) return fail(RFX_ERR_UNSUPPORTED, "rfx_mel_scale: filterbank is not banded: " + plan->imel_why);
+    RFX_HIP(launch_gen_pack(d_lin_bft, mag, false, B, plan->n_stft, T, plan->gg.fs, stream));
+    return gen_mel(plan, mag, (float*)((char*)d_workspace + w.mel_tm), B, T, d_mel_out, stream);
+  }
+  RFX_HIP(launch_pack_mag(d_lin_bft, mag, B, T, stream));
+  return mel_gemm(plan, mag, B, T, d_mel_out, stream);
+}

@@ -1,0 +1,636 @@
+// rfx_api_inverse.hip - the C ABI of librfx.so (include/rfx.h), inverse half: Griffin-Lim on the three frame engines,
+// InverseMelScale, and the fused calls made of them.  Host code only: the drivers that sequence the kernels.
+#include "rfx_api.h"
+
+using namespace rfx;
+
+namespace {
+// Per-launch times of a Griffin-Lim call, from HIP events recorded on the launch stream (bench.py's roofline leg).  Without an
+// array to fill every member does nothing and nothing is allocated; the events are released on every exit path.
+class LaunchTimer {
+  float* h_ms_;
+  int n_;  // launches: n_ + 1 events
+  std::vector<hipEvent_t> ev_;
+
+ public:
+  LaunchTimer(float* h_launch_ms, int n_launches) : h_ms_(h_launch_ms), n_(n_launches) {}
+  ~LaunchTimer() {
+    for (hipEvent_t e : ev_) (void)hipEventDestroy(e);
+  }
+  LaunchTimer(const LaunchTimer&) = delete;
+  LaunchTimer& operator=(const LaunchTimer&) = delete;
+  hipError_t begin(hipStream_t stream) {
+    if (!h_ms_) return hipSuccess;
+    ev_.reserve((size_t)n_ + 1);
+    for (int i = 0; i <= n_; ++i) {
+      hipEvent_t e;
+      const hipError_t rc = hipEventCreate(&e);
+      if (rc != hipSuccess) return rc;
+      ev_.push_back(e);
+    }
+    return hipEventRecord(ev_[0], stream);
+  }
+  hipError_t mark(int launch, hipStream_t stream) { return h_ms_ ? hipEventRecord(ev_[launch + 1], stream) : hipSuccess; }
+  hipError_t finish() {  // waits for the last marked launch
+    if (!h_ms_) return hipSuccess;
+    hipError_t rc = hipEventSynchronize(ev_[n_]);
+    for (int i = 0; i < n_ && rc == hipSuccess; ++i) rc = hipEventElapsedTime(&h_ms_[i], ev_[i], ev_[i + 1]);
+    return rc;
+  }
+};
+}  // namespace
+
+namespace rfx {
+__global__ void out_scale_kernel(const float* __restrict__ win, float* __restrict__ out, int T, int L) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= L) return;
+  // frames t with 0 <= p - 441 t + 2205 < 4410
+  int tlo = (p + 2205 - (kWin - 1) + kHop - 1) / kHop;  // ceil, numerator may be negative
+  if (p + 2205 - (kWin - 1) < 0) tlo = 0;
+  int thi = (p + 2205) / kHop;
+  if (thi > T - 1) thi = T - 1;
+  float env = 0.f;
+  for (int t = tlo; t <= thi; ++t) {
+    const float w = win[p - kHop * t + 2205];
+    env = fmaf(w, w, env);
+  }
+  out[p] = (2.0f / (float)kNfft) / env;
+}
+}  // namespace rfx
+
+static long long gl_slot_count(const rfx_plan* plan) { return (long long)plan->num_cus * plan->gl_wgs_per_cu; }
+// [B][2] floats of scales + [B] key words (launch_range_scale)
+static size_t range_table_bytes(int B) { return (size_t)B * 3 * sizeof(float); }
+
+// ---- Griffin-Lim ----------------------------------------------------------------------------------------------------------------
+// Small batches take the per-frame kernels (rfx_gl.hip: gl_frame_kernel + gl_fold_kernel): up to gl_latency_frames_per_slot (six)
+// frames per resident workgroup slot, and one stair further (below), where the run-based kernel (whole groups of 16 frames per
+// workgroup) would leave most of the chip idle.
+static bool gl_use_latency_mode(const rfx_plan* plan, int B, int T) {
+  if (plan->gl_form == RFX_GL_FORM_RUNS) return false;
+  if (plan->gl_form == RFX_GL_FORM_FRAMES) return true;
+  if (!plan->gl_latency_mode) return false;
+  const long long nframes = (long long)B * T, slots = gl_slot_count(plan);
+  if (nframes <= (long long)plan->gl_latency_frames_per_slot * slots) return true;
+  // one stair further (round 6): as soon as the batch has more groups than the chip has CUs some CU walks two 16-frame runs and the
+  // launch lasts as long as if all did (5.6 ms per Griffin-Lim 32 for nine tiles, 3.7 for eight); the per-frame form still beats
+  // that up to ten frames per slot (5.0 / 5.2 ms for nine / ten tiles: profiles/r06_griffinlim_forms_by_batch.txt)
+  const long long groups = (long long)B * rfx::gl_groups_per_row(T);
+  return groups > plan->num_cus && groups <= slots && 3 * nframes <= 5LL * plan->gl_latency_frames_per_slot * slots;
+}
+
+// The runs of one launch of the run-based Griffin-Lim kernel: at most one run per resident workgroup slot of the chip (a launch of
+// 520 workgroups on 512 slots runs eight of them alone in a second wave: the ceil(slots / B) runs per clip of rounds 1-4 did that
+// for every B that does not divide the slot count).
+// Round 6: the unit of the partition is the GROUP (kGlGroup = 16 consecutive frames of a row, rfx_kernels.h): runs are whole groups,
+// at most one run per slot and never more runs than groups.  A clip's bits no longer depend on the partition at all (every group
+// boundary splits the overlap-add chains, inside a run as between runs), so the partition is free to follow the chip and the batch.
+struct GlPartition { int runs, h, w1, w2; };
+static GlPartition gl_partition_for(long long slots, int B, int T) {
+  const long long N = (long long)B * rfx::gl_groups_per_row(T);
+  long long nruns = N;
+  if (nruns > slots) nruns = slots;
+  if (nruns < 1) nruns = 1;
+  // N = q runs + r: the FIRST r runs take q + 1 groups, the others q (gl_run_start with weights q + 1 / q is exact: W_total = N).
+  // First, because blocks 0 .. num_cus - 1 are the workgroups the dispatcher places first, one per CU, and the earlier workgroup
+  // of a CU wins its issue arbitration: it runs ~12 % faster than the partner that joins it (profiles/r05_wgclock_dispatch_order.txt:
+  // 659 against 746 us for 64 frames each), so the extra group of a batch that is not a whole number of groups per slot (B = 65:
+  // 32 runs of 80 frames among 480 of 64) lands where there is slack.  (The per-mille skew of round 5 is gone with it: it never
+  // moved the step, same file.)
+  const long long q = N / nruns, r = N - q * nruns;
+  return GlPartition{(int)nruns, (int)r, (int)(q + 1), (int)q};
+}
+static GlPartition gl_partition(const rfx_plan* plan, int B, int T) { return gl_partition_for(gl_slot_count(plan), B, T); }
+static int report_run_starts(const GlPartition& p, int B, int T, int64_t* run_starts, int capacity) {
+  if (run_starts)
+    for (int b = 0; b <= p.runs && b < capacity; ++b) run_starts[b] = rfx::gl_run_start_frame(b, p.runs, B, T, p.h, p.w1, p.w2);
+  return p.runs;
+}
+
+// (`which` selected a per-launch skew until round 6; every launch of a call has the same partition now)
+int rfx_griffinlim_runs(const rfx_plan* plan, int B, int T, int which, int64_t* run_starts, int capacity) {
+  (void)which;
+  if (!plan || B <= 0 || T < 2 || plan->generic) return 0;
+  return report_run_starts(gl_partition(plan, B, T), B, T, run_starts, capacity);
+}
+
+int64_t rfx_debug_run_start(int64_t b, int64_t runs, int64_t n_frames, int64_t h, int64_t w1, int64_t w2) {
+  return rfx::gl_run_start(b, runs, n_frames, h, w1, w2);
+}
+
+int rfx_debug_gl_partition(int slots, int B, int T, int64_t* run_starts, int capacity) {
+  if (slots <= 0 || B <= 0 || T < 2) return 0;
+  return report_run_starts(gl_partition_for(slots, B, T), B, T, run_starts, capacity);
+}
+
+int rfx_debug_range_exponents(float max_abs, int mel_units, int* sgd_exponent, int* gl_exponent) {
+  if (!sgd_exponent || !gl_exponent) return fail(RFX_ERR_INVALID, "rfx_debug_range_exponents: null argument");
+  int k = 0;
+  if (max_abs > 0.f) {
+    if (max_abs < __builtin_inff()) (void)frexpf(max_abs, &k);
+    else k = 129;
+  }
+  rfx::range_exponents(k, mel_units, sgd_exponent, gl_exponent);
+  return RFX_OK;
+}
+
+int rfx_griffinlim_form(const rfx_plan* plan, int B, int T) {
+  if (!plan || B <= 0 || T < 2) return RFX_GL_FORM_AUTO;
+  if (plan->generic) return RFX_GL_FORM_FRAMES;  // the generic engine has one form: frame kernels + fold
+  return gl_use_latency_mode(plan, B, T) ? RFX_GL_FORM_FRAMES : RFX_GL_FORM_RUNS;
+}
+
+// Specialised engine: three generations (x_{k-1}, x_k, x_{k+1}) of the two parity audio buffers, the istft normalisation table,
+// the synthesis frames of the per-frame form, and the call's own row-scale table (GlArgs::row_scale).  No spectral state is kept
+// between iterations (see rfx_gl.hip).
+struct GlLayout {
+  size_t audio, scale, frames, row_scale, total;
+  int Lpad;
+};
+static GlLayout gl_layout(const rfx_plan* plan, int B, int T) {
+  GlLayout l{};
+  if (B <= 0 || T < 2) return l;
+  l.Lpad = (int)align_up((size_t)kHop * (T - 1), 64);
+  Carve c;
+  l.audio = c.take(6 * (size_t)B * l.Lpad * sizeof(float));
+  l.scale = c.take((size_t)l.Lpad * sizeof(float));
+  l.frames = c.take(gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
+  l.row_scale = c.take(range_table_bytes(B));
+  l.total = c.at;
+  return l;
+}
+
+// torch.istft(center=True, length=None) returns n_fft + hop*(T-1) - 2*(n_fft/2) samples: hop*(T-1), plus one when n_fft is odd
+static int gen_out_len(const GenGeom& g, int T) { return g.hop * (T - 1) + (g.n_fft & 1); }
+
+// Generic engine: the windowed synthesis frames, three generations of the audio estimate (x_{k-1}, x_k read; x_{k+1} written) and
+// the window envelope of the fold, [Lpad]; on a row family the magnitudes re-ordered into slot order; the row-scale table
+struct GenGlLayout {
+  size_t frames, audio, repacked, row_scale, total;
+  int Lpad;
+};
+static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T) {
+  GenGlLayout l{};
+  if (B <= 0 || T < 2) return l;
+  const GenGeom& g = plan->gg;
+  const size_t nf = (size_t)B * T;
+  l.Lpad = (int)align_up((size_t)gen_out_len(g, T), 64);
+  Carve c;
+  l.frames = c.take(nf * g.fpitch * sizeof(float));
+  l.audio = c.take((3 * (size_t)B + 1) * l.Lpad * sizeof(float));
+  l.repacked = c.take(plan->fam_ok ? nf * plan->fam.fsf * sizeof(float) : 0);
+  l.row_scale = c.take(range_table_bytes(B));
+  l.total = c.at;
+  return l;
+}
+
+size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) {
+  if (!plan) return 0;
+  return plan->generic ? gen_gl_layout(plan, B, T).total : gl_layout(plan, B, T).total;
+}
+
+// rfx_call_options as the entry points below see them (NULL / short struct = defaults)
+struct CallOpt {
+  uint64_t row_base = 0;
+  float magnitude_hint = 0.f;
+};
+static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who) {
+  *out = CallOpt{};
+  if (!o) return RFX_OK;
+  if (o->struct_size < offsetof(rfx_call_options, row_base) + sizeof(uint64_t))
+    return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.struct_size is not set");
+  if (o->flags != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.flags must be 0");
+  out->row_base = o->row_base;
+  if (o->struct_size >= offsetof(rfx_call_options, magnitude_hint) + sizeof(float)) out->magnitude_hint = o->magnitude_hint;
+  if (!(out->magnitude_hint >= 0.f) || out->magnitude_hint > 3.0e38f)
+    return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.magnitude_hint must be a finite value >= 0");
+  return RFX_OK;
+}
+
+// One checked Griffin-Lim call, as every engine and form is given it
+struct GlCall {
+  const float* S;
+  const cf* angles0;
+  const float* row_scale;  // null: the driver fills the table of its own workspace (gl_row_scale)
+  float hint, mom;
+  uint64_t seed, frame_base;
+  int B, T, L, n_iter;
+  float* out;
+  char* ws;
+  size_t ws_bytes;
+  hipStream_t stream;
+};
+// ... and the fields that all four argument blocks have
+template <class Args>
+static void set_gl_args(Args& a, const GlCall& c) {
+  a.S = c.S;
+  a.angles0 = c.angles0;
+  a.row_scale = c.row_scale;
+  a.mom = c.mom;
+  a.seed = c.seed;
+  a.frame_base = c.frame_base;
+  a.B = c.B;
+  a.T = c.T;
+  a.L = c.L;
+}
+// numeric range of the rows: from the caller's hint, else from the magnitudes themselves (one pass over them).  A fused call
+// brings the table its SGD stage wrote.
+static int gl_row_scale(GlCall& c, size_t per_row, float* table) {
+  if (c.row_scale) return RFX_OK;
+  RFX_HIP(launch_range_scale(c.S, per_row, c.B, c.hint, (unsigned*)(table + 2 * (size_t)c.B), nullptr, table, 1, 0, c.stream));
+  c.row_scale = table;
+  return RFX_OK;
+}
+
+// Generic engine and row family: a frame kernel, then the fold, per iteration.
+// mag_in_fam_slots (rfx_waveform_from_mel on a row-family plan): c.S already holds the family kernels' slot order [B*T][fsf] -
+// InverseMelScale wrote it that way - so the once-per-call re-ordering of the plain frames is left out
+static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots, LaunchTimer& timer) {
+  const GenGeom& g = plan->gg;
+  const int B = c.B, T = c.T, L = c.L;
+  const bool fam = plan->fam_ok;
+  const GenGlLayout w = gen_gl_layout(plan, B, T);
+  if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
+  float* frames = (float*)(c.ws + w.frames);
+  float* gen[3];
+  for (int i = 0; i < 3; ++i) gen[i] = (float*)(c.ws + w.audio) + (size_t)i * B * w.Lpad;
+  float* env = (float*)(c.ws + w.audio) + (size_t)3 * B * w.Lpad;
+  const size_t per_row = (size_t)T * ((fam && mag_in_fam_slots) ? (size_t)plan->fam.fsf : (size_t)g.fs);
+  if (int rc = gl_row_scale(c, per_row, (float*)(c.ws + w.row_scale))) return rc;
+  RFX_HIP(launch_gen_env(plan->d_win, env, g, T, L, c.stream));
+  // padded frame rows (gen_frame_layout): the kernels write the window samples only, the fold reads the padding as zeros
+  if (g.fshift > 0) RFX_HIP(hipMemsetAsync(frames, 0, (size_t)B * T * g.fpitch * sizeof(float), c.stream));
+  RFX_HIP(timer.begin(c.stream));
+  // x_it lives in gen[it % 2]; gen[2] holds d_it = x_it - m x_{it-1} (d_0 = x_0), the momentum term of the reference's
+  // `rebuilt - m * tprev` applied in the time domain: the fold of iteration it forms it next to x_it and launch it + 1 analyses it,
+  // so the kernels run their one-signal mode for every iteration (half the audio loads, same bits); it == 0 synthesises the
+  // initial estimate from S * angles0
+  FamGlArgs fa{};
+  GenGlArgs ga{};
+  int nblocks = 0;
+  if (fam) {
+    const FamGeom& f = plan->fam;
+    if (!mag_in_fam_slots) {
+      float* repacked = (float*)(c.ws + w.repacked);
+      RFX_HIP(launch_fam_repack(c.S, repacked, plan->d_fam_binof, (long long)B * T, g.fs, f.fsf, f.n_stft, c.stream));
+      c.S = repacked;
+    }
+    set_gl_args(fa, c);
+    fa.g = f;
+    fa.fs_plain = g.fs;
+    fa.x_cur = gen[2];
+    fa.audio_stride = (size_t)w.Lpad;
+    fa.frames = frames;
+    fa.fpitch = g.fpitch;
+    fa.fshift = g.fshift;
+    fa.tw1 = plan->d_fam_tw;
+    fa.twa = plan->d_fam_tw + (size_t)f.rows * f.h;
+    fa.win = plan->d_win;
+    nblocks = frame_blocks(fam_slot_count(plan), B, T);
+  } else {
+    set_gl_args(ga, c);
+    ga.g = g;
+    ga.tb = plan->gt;
+    ga.x_cur = gen[2];
+    ga.audio_stride = (size_t)w.Lpad;
+    ga.frames = frames;
+  }
+  for (int it = 0; it <= c.n_iter; ++it) {
+    const int mode = it == 0 ? 0 : 1;
+    RFX_HIP(fam ? launch_fam_gl(mode, fa, nblocks, c.stream) : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
+    const bool last = it == c.n_iter;
+    RFX_HIP(launch_gen_fold(frames, env, last ? c.out : gen[it % 2], g, B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
+                            it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale));
+    RFX_HIP(timer.mark(it, c.stream));
+  }
+  RFX_HIP(timer.finish());
+  return RFX_OK;
+}
+
+// Specialised engine: the per-frame form (frame kernel + fold per iteration) or the run form (one kernel per iteration)
+static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) {
+  const int B = c.B, T = c.T, L = c.L;
+  const GlLayout w = gl_layout(plan, B, T);
+  if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
+  float* gen[3][2];  // x_k lives in generation k % 3
+  for (int i = 0; i < 3; ++i)
+    for (int p = 0; p < 2; ++p) gen[i][p] = (float*)(c.ws + w.audio) + (size_t)(2 * i + p) * B * w.Lpad;
+  float* scale = (float*)(c.ws + w.scale);
+  hipLaunchKernelGGL(out_scale_kernel, dim3((L + 255) / 256), dim3(256), 0, c.stream, plan->d_win, scale, T, L);
+  RFX_HIP(hipGetLastError());
+  if (int rc = gl_row_scale(c, (size_t)T * kFrameStride, (float*)(c.ws + w.row_scale))) return rc;
+
+  if (gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
+    GlFrameArgs fa;
+    set_gl_args(fa, c);
+    fa.frames = (float*)(c.ws + w.frames);
+    fa.tw1 = plan->d_tw1;
+    fa.tw2 = plan->d_tw2;
+    fa.win = plan->d_win;
+    fa.Lpad = w.Lpad;
+    const int nblocks = frame_blocks(gl_slot_count(plan), B, T);
+    RFX_HIP(timer.begin(c.stream));
+    for (int it = 0; it <= c.n_iter; ++it) {
+      fa.audio_in = gen[(it + 2) % 3][0];    // x_{it-1}
+      fa.audio_prev = gen[(it + 1) % 3][0];  // x_{it-2}
+      RFX_HIP(launch_gl_frame(it == 0 ? 0 : it == 1 ? 1 : 2, fa, nblocks, c.stream));
+      const bool last = it == c.n_iter;
+      RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream));
+      RFX_HIP(timer.mark(it, c.stream));
+    }
+    RFX_HIP(timer.finish());
+    return RFX_OK;
+  }
+
+  GlArgs g;
+  set_gl_args(g, c);
+  g.out_scale = scale;
+  g.tw1 = plan->d_tw1;
+  g.tw2 = plan->d_tw2;
+  g.win = plan->d_win;
+  g.Lpad = w.Lpad;
+  g.timing = plan->timing;
+  // runs: the batch's B*T frames, counted clip after clip, are cut into one run per resident workgroup slot (gl_partition)
+  const GlPartition part = gl_partition(plan, B, T);
+  g.run_h = part.h;
+  g.run_w1 = part.w1;
+  g.run_w2 = part.w2;
+  auto set_io = [&](int k_in, int k_prev, int k_out) {
+    for (int p = 0; p < 2; ++p) {
+      g.audio_in[p] = gen[k_in][p];
+      g.audio_prev[p] = gen[k_prev][p];
+      g.audio_out[p] = gen[k_out][p];
+    }
+  };
+  RFX_HIP(timer.begin(c.stream));
+  for (int it = 0; it <= c.n_iter; ++it) {
+    // iteration `it` analyses x_{it-1} - m*x_{it-2} and writes x_it; MODE 0 reads nothing and writes x_0
+    if (it == 0) set_io(1, 2, 0);
+    else set_io((it - 1) % 3, (it + 1) % 3 /* == (it-2) mod 3 */, it % 3);
+#ifdef RFX_WGCLOCK
+    g.launch = it;
+#endif
+    RFX_HIP(launch_gl_iter(it == 0 ? 0 : it == 1 ? 1 : 2, g, part.runs, c.stream));
+    RFX_HIP(timer.mark(it, c.stream));
+  }
+  const int last = c.n_iter % 3;
+  RFX_HIP(launch_gl_combine(gen[last][0], gen[last][1], c.out, B, L, w.Lpad, c.stream));
+  RFX_HIP(timer.finish());
+  return RFX_OK;
+}
+
+static int griffinlim_impl(const rfx_plan* plan, const float* d_mag_slots, const void* d_angles0_slots, uint64_t seed, int B,
+                           int T, int n_iter, float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes,
+                           void* stream, float* h_launch_ms, const CallOpt& opt, bool mag_in_fam_slots = false,
+                           const float* d_row_scale = nullptr) {
+  if (!plan || !d_mag_slots || !d_wave_out || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_griffinlim: null argument");
+  if (B <= 0 || T < 2 || n_iter < 0) return fail(RFX_ERR_INVALID, "rfx_griffinlim: bad shape");
+  if ((long long)B * T > 0x7fffffffLL) return fail(RFX_ERR_INVALID, "rfx_griffinlim: more than 2^31 - 1 frames in one call");
+  if (!(momentum >= 0.f && momentum < 1.f)) return fail(RFX_ERR_INVALID, "rfx_griffinlim: momentum must be in [0, 1)");
+  // every iteration re-analyses the estimate with torch.stft(center=True, reflect): the reference raises there unless the signal
+  // is longer than the n_fft/2 padding
+  const int L = rfx_griffinlim_output_samples(plan, T);
+  if (n_iter > 0 && L <= plan->p.n_fft / 2)
+    return fail(RFX_ERR_INVALID,
+                plan->generic ? "rfx_griffinlim: Padding size should be less than the corresponding input dimension (reflect padding " +
+                                    std::to_string(plan->p.n_fft / 2) + " needs more than that many samples)"
+                              : "rfx_griffinlim: Padding size should be less than the corresponding input dimension "
+                                "(reflect padding 8820 needs more than 8820 samples, i.e. at least 22 frames)");
+  RFX_ON_DEVICE(plan->device);
+  GlCall c{d_mag_slots, (const cf*)d_angles0_slots, d_row_scale, opt.magnitude_hint, momentum / (1.f + momentum), seed,
+           opt.row_base * (uint64_t)T, B, T, L, n_iter, d_wave_out, (char*)d_workspace, workspace_bytes, (hipStream_t)stream};
+  LaunchTimer timer(h_launch_ms, n_iter + 1);
+  return plan->generic ? gen_griffinlim(plan, c, mag_in_fam_slots, timer) : spec_griffinlim(plan, c, timer);
+}
+
+int rfx_griffinlim(const rfx_plan* plan, const float* d_mag_slots, const void* d_angles0_slots, uint64_t seed, int B,
+                   int T, int n_iter, float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes,
+                   void* stream) {
+  return griffinlim_impl(plan, d_mag_slots, d_angles0_slots, seed, B, T, n_iter, momentum, d_wave_out, d_workspace,
+                         workspace_bytes, stream, nullptr, CallOpt{});
+}
+
+int rfx_griffinlim_ex(const rfx_plan* plan, const float* d_mag_slots, const void* d_angles0_slots, uint64_t seed, int B,
+                      int T, int n_iter, float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes,
+                      void* stream, const rfx_call_options* options, float* h_launch_ms) {
+  CallOpt opt;
+  if (int rc = read_call_options(options, &opt, "rfx_griffinlim_ex")) return rc;
+  return griffinlim_impl(plan, d_mag_slots, d_angles0_slots, seed, B, T, n_iter, momentum, d_wave_out, d_workspace,
+                         workspace_bytes, stream, h_launch_ms, opt);
+}
+
+int rfx_griffinlim_timed(const rfx_plan* plan, const float* d_mag_slots, const void* d_angles0_slots, uint64_t seed, int B,
+                         int T, int n_iter, float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes,
+                         void* stream, float* h_launch_ms) {
+  if (!h_launch_ms) return fail(RFX_ERR_INVALID, "rfx_griffinlim_timed: null timing array");
+  return griffinlim_impl(plan, d_mag_slots, d_angles0_slots, seed, B, T, n_iter, momentum, d_wave_out, d_workspace,
+                         workspace_bytes, stream, h_launch_ms, CallOpt{});
+}
+
+// ---- InverseMelScale ------------------------------------------------------------------------------------------------------------
+// the loss history [B*T][max_mel_iters], the clips' stopping steps and the any-early word behind them, the clips' range table
+struct ImelLayout {
+  size_t hist, it_stop, clip_scale, total;
+};
+static ImelLayout inverse_mel_layout(const rfx_plan* plan, int B, int T) {
+  ImelLayout l{};
+  if (B <= 0 || T <= 0) return l;
+  Carve c;
+  l.hist = c.take((size_t)B * T * plan->p.max_mel_iters * sizeof(float));
+  l.it_stop = c.take((size_t)(B + 1) * sizeof(int));
+  l.clip_scale = c.take(range_table_bytes(B));
+  l.total = c.at;
+  return l;
+}
+size_t rfx_inverse_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? inverse_mel_layout(plan, B, T).total : 0; }
+
+// can InverseMelScale write a row-family plan's frames straight in the family kernels' slot order?  (Every kernel that leaves
+// through imel_emit_frame can: the output order is just its pos_bin table.  The general LDS kernel stores bin by bin.)
+static bool imel_can_emit_fam_slots(const rfx_plan* plan) {
+  return plan->generic && plan->fam_ok && plan->imel_ok && plan->d_fam_binof &&
+         rfx::imel_kernel_choice(plan->imel, plan->p.n_mels, plan->p.max_mel_iters, plan->imel_variant) != 0;
+}
+
+static int inverse_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, const float* d_spec0,
+                            uint64_t seed, float* d_mag_slots, void* d_workspace, size_t workspace_bytes, void* stream_, bool fam_slots,
+                            const CallOpt& opt, float* d_gl_row_scale = nullptr) {
+  if (!plan || !d_mel || !d_mag_slots || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_inverse_mel: null argument");
+  if (!plan->d_melfb) return fail(RFX_ERR_INVALID, "rfx_inverse_mel: plan was created without a mel filterbank");
+  if (!plan->imel_ok) return fail(RFX_ERR_UNSUPPORTED, "rfx_inverse_mel: filterbank is not banded: " + plan->imel_why);
+  if (B <= 0 || T <= 0 || channels_per_clip <= 0 || B % channels_per_clip)
+    return fail(RFX_ERR_INVALID, "rfx_inverse_mel: batch must be a multiple of channels_per_clip");
+  if (opt.row_base % (uint64_t)channels_per_clip)
+    return fail(RFX_ERR_INVALID, "rfx_inverse_mel: rfx_call_options.row_base must be a multiple of channels_per_clip (clips are not split)");
+  const ImelLayout w = inverse_mel_layout(plan, B, T);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_inverse_mel: workspace too small");
+  RFX_ON_DEVICE(plan->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const int nclips = B / channels_per_clip;
+  char* ws = (char*)d_workspace;
+  float* hist = (float*)(ws + w.hist);
+  int* it_stop = (int*)(ws + w.it_stop);
+  int* any_early = it_stop + nclips;
+  RFX_HIP(hipMemsetAsync(any_early, 0, sizeof(int), stream));
+  // numeric range: the power of two each clip's SGD state is held in (and, for the fused call, the Griffin-Lim rows' factors),
+  // from the caller's hint or the clip's largest mel amplitude
+  float* clip_scale = (float*)(ws + w.clip_scale);
+  RFX_HIP(launch_range_scale(d_mel, (size_t)channels_per_clip * plan->p.n_mels * T, nclips, opt.magnitude_hint, (unsigned*)(clip_scale + 2 * (size_t)nclips),
+                             clip_scale, d_gl_row_scale, channels_per_clip, 1, stream));
+  ImelArgs a;
+  a.clip_scale = clip_scale;
+  a.sc = a.un = 0.f;
+  a.tb = plan->imel;
+  a.mel = d_mel;
+  a.spec0 = d_spec0;
+  a.out_slots = d_mag_slots;
+  a.loss_hist = hist;
+  a.it_limit = nullptr;
+  a.B = B;
+  a.M = plan->p.n_mels;
+  a.T = T;
+  a.C = channels_per_clip;
+  a.n_stft = plan->n_stft;
+  a.out_stride = plan->frame_stride;
+  a.plain = plan->generic ? 1 : 0;
+  if (fam_slots) {  // (imel_can_emit_fam_slots: the frame's positions are the family kernels' slots)
+    a.tb.pos_bin = plan->d_fam_binof;
+    a.out_stride = plan->fam.fsf;
+  }
+  a.max_iter = plan->p.max_mel_iters;
+  a.lr = 0.1f;        // sgdargs=None -> {"lr": 0.1, "momentum": 0.9} (torchaudio 0.13 InverseMelScale)
+  a.momentum = 0.9f;
+  a.seed = seed;
+  a.frame_base = opt.row_base * (uint64_t)T;
+  if (a.max_iter <= 0) return fail(RFX_ERR_INVALID, "rfx_inverse_mel: max_mel_iters must be positive");
+  RFX_HIP(launch_imel(a, plan->imel_variant, stream));
+  // reproduce the reference's early exit (tolerance_loss 1e-5, tolerance_change 1e-8,
+  // spectrogram_converter.py:94-95): scan the clip losses, then re-run stopped clips for it_stop steps
+  RFX_HIP(launch_imel_scan(hist, it_stop, any_early, nclips, channels_per_clip, T, a.max_iter, 1e-5f, 1e-8f, stream));
+  a.it_limit = it_stop;
+  RFX_HIP(launch_imel(a, plan->imel_variant, stream));
+  return RFX_OK;
+}
+
+int rfx_inverse_mel(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, const float* d_spec0,
+                    uint64_t seed, float* d_mag_slots, void* d_workspace, size_t workspace_bytes, void* stream_) {
+  return inverse_mel_impl(plan, d_mel, B, T, channels_per_clip, d_spec0, seed, d_mag_slots, d_workspace, workspace_bytes, stream_, false, CallOpt{});
+}
+
+int rfx_inverse_mel_ex(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, const float* d_spec0,
+                       uint64_t seed, float* d_mag_slots, void* d_workspace, size_t workspace_bytes, void* stream_,
+                       const rfx_call_options* options) {
+  CallOpt opt;
+  if (int rc = read_call_options(options, &opt, "rfx_inverse_mel_ex")) return rc;
+  return inverse_mel_impl(plan, d_mel, B, T, channels_per_clip, d_spec0, seed, d_mag_slots, d_workspace, workspace_bytes, stream_, false, opt);
+}
+
+// ---- SpectrogramConverter.waveform_from_mel_amplitudes in one call (spectrogram_converter.py:187-204: inverse_mel_scaler, then
+// inverse_spectrogram_func).  rfx_inverse_mel into the head of the workspace, rfx_griffinlim from there: the same two launches
+// sequences, the same seeds (seed for the SGD start, seed + 1 for the phases, as the Python layer always called them), the linear
+// magnitudes never leave the library.
+// The linear magnitudes, the Griffin-Lim rows' range table (written by the SGD stage's range pass), then the two stages' own
+// workspaces on top of each other.  A row-family plan's magnitudes go from the SGD kernel to the Griffin-Lim kernels in THEIR slot
+// order (fam_slots): the once-per-call re-ordering of plain frames (0.75 ms and 2.5 GB of traffic per 64 tiles at 48 kHz) exists
+// only for callers of the two entry points.
+struct WaveFromMelLayout {
+  size_t lin, row_scale, rest, total;
+  bool fam_slots;
+};
+static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, int T) {
+  WaveFromMelLayout l{};
+  const size_t imel = rfx_inverse_mel_workspace_bytes(plan, B, T), gl = rfx_griffinlim_workspace_bytes(plan, B, T);
+  if (!imel || !gl) return l;
+  l.fam_slots = imel_can_emit_fam_slots(plan);
+  Carve c;
+  l.lin = c.take((size_t)B * T * (l.fam_slots ? (size_t)plan->fam.fsf : (size_t)plan->frame_stride) * sizeof(float));
+  l.row_scale = c.take(range_table_bytes(B));
+  l.rest = c.at;
+  l.total = l.rest + (imel > gl ? imel : gl);
+  return l;
+}
+size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T).total : 0; }
+
+static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
+                                 float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream, const CallOpt& opt) {
+  if (!plan || !d_mel || !d_wave_out || !d_workspace || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_waveform_from_mel: bad argument");
+  const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T);
+  if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_waveform_from_mel: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
+  char* ws = (char*)d_workspace;
+  float* lin = reinterpret_cast<float*>(ws + w.lin);
+  float* row_scale = reinterpret_cast<float*>(ws + w.row_scale);
+  if (int rc = inverse_mel_impl(plan, d_mel, B, T, channels_per_clip, nullptr, seed, lin, ws + w.rest, workspace_bytes - w.rest, stream, w.fam_slots, opt, row_scale)) return rc;
+  return griffinlim_impl(plan, lin, nullptr, seed + 1, B, T, n_iter, momentum, d_wave_out, ws + w.rest, workspace_bytes - w.rest, stream, nullptr, opt, w.fam_slots, row_scale);
+}
+
+int rfx_waveform_from_mel(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
+                          float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return waveform_from_mel_impl(plan, d_mel, B, T, channels_per_clip, seed, n_iter, momentum, d_wave_out, d_workspace, workspace_bytes, stream, CallOpt{});
+}
+
+int rfx_waveform_from_mel_ex(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
+                             float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream,
+                             const rfx_call_options* options) {
+  CallOpt opt;
+  if (int rc = read_call_options(options, &opt, "rfx_waveform_from_mel_ex")) return rc;
+  return waveform_from_mel_impl(plan, d_mel, B, T, channels_per_clip, seed, n_iter, momentum, d_wave_out, d_workspace, workspace_bytes, stream, opt);
+}
+
+// ---- SpectrogramImageConverter.audio_from_spectrogram_image's device half in one call (spectrogram_image_converter.py:54-91:
+// image_util.spectrogram_from_image, SpectrogramConverter.audio_from_spectrogram -> waveform_from_mel_amplitudes on the image's
+// (C, n_mels, T) tensor, audio_util.audio_from_waveform): uint8 tiles in, int16 PCM out.  The three entry points it is made of,
+// in their order, with the same seeds: same bytes.
+// The decoded mel amplitudes, the waveform, then rfx_waveform_from_mel's workspace.
+struct AudioFromImageLayout {
+  size_t mel, wave, rest, total;
+};
+static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N, int stereo, int T) {
+  AudioFromImageLayout l{};
+  if (N <= 0 || T <= 0) return l;
+  const int B = N * (stereo ? 2 : 1);
+  const size_t inner = waveform_from_mel_layout(plan, B, T).total;
+  if (!inner) return l;
+  Carve c;
+  l.mel = c.take((size_t)B * plan->p.n_mels * T * sizeof(float));
+  l.wave = c.take((size_t)B * rfx_griffinlim_output_samples(plan, T) * sizeof(float));
+  l.rest = c.at;
+  l.total = l.rest + inner;
+  return l;
+}
+size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
+  return plan ? audio_from_image_layout(plan, N, stereo, T).total : 0;
+}
+
+static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
+                                int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
+                                size_t workspace_bytes, void* stream, const CallOpt& opt) {
+  if (!plan || !d_img || !d_lut256 || !d_clip_peak || !d_pcm_out || !d_workspace || N <= 0 || T <= 0)
+    return fail(RFX_ERR_INVALID, "rfx_audio_from_image_u8: bad argument");
+  const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T);
+  if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_audio_from_image_u8: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
+  const int C = stereo ? 2 : 1, B = N * C, M = plan->p.n_mels, L = rfx_griffinlim_output_samples(plan, T);
+  char* ws = (char*)d_workspace;
+  float* mel = reinterpret_cast<float*>(ws + w.mel);
+  float* wave = reinterpret_cast<float*>(ws + w.wave);
+  if (int rc = rfx_image_decode_u8(d_img, N, M, T, stereo, d_lut256, mel, stream)) return rc;
+  // (a clip is one image: its channels share the SGD loss mean and the peak normalisation)
+  if (int rc = waveform_from_mel_impl(plan, mel, B, T, C, seed, n_iter, momentum, wave, ws + w.rest, workspace_bytes - w.rest, stream, opt)) return rc;
+  return rfx_pcm16(wave, N, C, L, normalize, d_clip_peak, d_pcm_out, stream);
+}
+
+int rfx_audio_from_image_u8(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
+                            int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
+                            size_t workspace_bytes, void* stream) {
+  return audio_from_image_impl(plan, d_img, N, T, stereo, d_lut256, seed, n_iter, momentum, normalize, d_clip_peak, d_pcm_out, d_workspace,
+                               workspace_bytes, stream, CallOpt{});
+}
+
+int rfx_audio_from_image_u8_ex(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
+                               int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
+                               size_t workspace_bytes, void* stream, const rfx_call_options* options) {
+  CallOpt opt;
+  if (int rc = read_call_options(options, &opt, "rfx_audio_from_image_u8_ex")) return rc;
+  return audio_from_image_impl(plan, d_img, N, T, stereo, d_lut256, seed, n_iter, momentum, normalize, d_clip_peak, d_pcm_out, d_workspace,
+                               workspace_bytes, stream, opt);
+}

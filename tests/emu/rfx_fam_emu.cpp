@@ -158,7 +158,7 @@ int emu_fam_geom(int n_fft, int win, int hop, int* out6) {
 }
 }
 
-// Griffin-Lim of one clip exactly as the kernels of rfx_fam.hip + gen_fold_kernel run it (rfx_api.hip::gen_griffinlim): launch
+// Griffin-Lim of one clip exactly as the kernels of rfx_fam.hip + gen_fold_kernel run it (rfx_api_inverse.hip::gen_griffinlim): launch
 // 0 synthesises S * angles0, launch it >= 1 analyses x_{it-1} - m x_{it-2} (momentum applied in the time domain), projects every
 // slot, synthesises; the windowed frames are overlap-added and divided by the window envelope.  Host arithmetic (exact sqrt and
 // divide in gl_project where the device uses v_rsq_f32).

@@ -481,7 +481,11 @@ def test_plan_options_are_validated_before_any_device_call(repo_root):
     assert "RFX_LAYOUT_AUTO = 0" in header and "RFX_LAYOUT_GENERIC = 1" in header and "int32_t plan_layout;" in header
     assert "RFX_IMEL_FORM_AUTO = 0" in header and "RFX_IMEL_FORM_GROUPS = 1" in header and "int32_t imel_form;" in header
     # the release library reads no environment variable: every getenv of the C++ side sits behind RFX_ABLATION / RFX_TIMING
-    api = open(os.path.join(repo_root, "riffusion-hobby_amd", "csrc", "rfx_api.hip")).read()
+    # (every .hip and .h of csrc/, not the API units alone)
+    csrc = os.path.join(repo_root, "riffusion-hobby_amd", "csrc")
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert any(f.endswith(".hip") for f in sources) and any(f.endswith(".h") for f in sources)
+    api = "".join(open(os.path.join(csrc, f)).read() for f in sources)
     assert api.count("getenv(") == 2 and "#ifdef RFX_ABLATION\n  return getenv(name);" in api and 'getenv("RFX_TIMING_PTR")' in api
     for kw in ({"gl_form": "sometimes"}, {"frame_engine": "fastest"}, {"plan_layout": "dense"}, {"imel_form": "fast"}):
         with pytest.raises(ValueError):

@@ -147,7 +147,7 @@ def _lib():
 def test_run_partition_by_dispatch_order_is_a_partition(B, T, skew):
     """rfx_kernels.h::gl_run_start (through the C ABI, no GPU): the runs of a launch tile the frames exactly, in order, the first
     h of them longer by 2 * skew per mille of the mean than the others, none shorter than 11 frames when the host's admission rule
-    (csrc/rfx_api.hip::gl_partition) lets the skew through - so a hop block (10 frames) is shared by at most two runs."""
+    (csrc/rfx_api_inverse.hip::gl_partition) lets the skew through - so a hop block (10 frames) is shared by at most two runs."""
     lib = _lib()
     runs, h, N = 512, 256, B * T
     admitted = N // 10 >= runs and (N * (1000 - skew)) // (1000 * runs) >= 11
