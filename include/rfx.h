@@ -271,6 +271,15 @@ size_t rfx_image_from_waveform_workspace_bytes(const rfx_plan* plan, int N, int 
 int rfx_image_from_waveform(const rfx_plan* plan, const float* d_wave, int N, int stereo, int Lw, const float* d_thresholds255,
                             float* d_clip_max, uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* The same from int16 PCM: the N clips of Lw frames that start at the frame offsets `starts` of one recording d_pcm (frames,
+ * in_channels) int16 - see rfx_pcm16_clips_to_waveform below for the arguments and what is checked - are gathered into the
+ * workspace and converted: exactly rfx_pcm16_clips_to_waveform (out_channels = stereo ? 2 : 1) followed by
+ * rfx_image_from_waveform, same bytes.  N == 0 is a no-op. */
+size_t rfx_image_from_pcm16_clips_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw);
+int rfx_image_from_pcm16_clips(const rfx_plan* plan, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts,
+                               const int64_t* d_starts, int N, int Lw, int stereo, const float* d_thresholds255, float* d_clip_max,
+                               uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Standalone torchaudio.transforms.MelScale.forward (spectrogram_converter.py:185) for callers that hold linear
  * magnitudes in the reference's (B, n_stft, T) layout: packs them into slots and runs the same MFMA projection.
  * Workspace: rfx_mel_scale_workspace_bytes. */
@@ -434,6 +443,37 @@ size_t rfx_image_resize_workspace_bytes(int N, int H, int W, int out_h, int out_
 int rfx_image_resize_u8(const uint8_t* d_in, int N, int H, int W, int out_h, int out_w, int filter, const int32_t* d_bounds_x,
                         const int32_t* d_kk_x, const int32_t* d_bounds_y, const int32_t* d_kk_y, uint8_t* d_out, void* d_workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ---- int16 front end of the encode: pydub's set_frame_rate / set_channels and the clip slicing on the device -------------------
+ * What the reference does on the host before every encode (cli.py:132-193, streamlit/tasks/audio_to_audio.py): AudioSegment
+ * .set_channels (audioop.tomono(data, 2, 0.5, 0.5) / audioop.tostereo(data, 2, 1, 1)), .set_frame_rate
+ * (audioop.ratecv(data, 2, channels, inrate, outrate, None): linear interpolation, weights 1 / 0, a fresh state), the slice into
+ * clips and the int16 -> float32 (channels, samples) array.  Reproduced byte for byte.
+ *
+ * Exactness of the resample.  With a = in_rate / g, b = out_rate / g, g = gcd(in_rate, out_rate), L input frames give
+ * K = floor((L - 1) * b / a) + 1 output frames; output k reads input frames n_k - 2 and n_k - 1 (frame -1 is zero),
+ * n_k = 1 + ceil(k * a / b), with the weights d_k = (n_k - 1) * b - k * a and b - d_k, and is
+ * trunc(((x[n_k - 2] << 16) * d_k + (x[n_k - 1] << 16) * (b - d_k)) / b) >> 16.  audioop evaluates the numerator and the division
+ * in double: the numerator is exact below 2^53 and the truncated quotient is then the integer quotient, which holds for every
+ * int16 input while b < 2^21.  Both reduced rates must therefore stay below 2^20; other pairs are refused
+ * (RFX_ERR_UNSUPPORTED).  Every common pair passes (48000 <-> 44100 reduces to 160 <-> 147).  Equal rates copy (or only mix).
+ * Not implemented: a carried ratecv state, weights other than 1 / 0, more than two channels.  All frame indices are 64-bit.
+ *
+ * rfx_pcm16_resample_frames, host only (no GPU): K for in_frames >= 1.
+ * rfx_pcm16_resample: d_in (in_frames, in_channels) int16 interleaved -> d_out (out_frames, out_channels) int16, with
+ *   out_frames = K.  When the channel counts differ (1 -> 2 or 2 -> 1) the mix is applied to the stored frames FIRST and the
+ *   mixed recording is resampled: set_channels, then set_frame_rate - the batch CLI's order.  Pointers are frame-aligned
+ *   (2 * channels bytes); d_in and d_out must not overlap.
+ * rfx_pcm16_clips_to_waveform: clip i = frames [starts[i], starts[i] + Lw) of d_pcm (frames, in_channels) int16 ->
+ *   d_wave_out rows i * out_channels + c, (N * out_channels, Lw) float32 - the layout rfx_image_from_waveform reads; the
+ *   conversion is exact.  A channel mix is applied AFTER the slice, as spectrogram_image_from_audio's set_channels is.  Clips
+ *   may overlap.  h_starts (host) is checked against frames and Lw before anything is launched; d_starts is the same table in
+ *   device memory.  N == 0 is a no-op. */
+int rfx_pcm16_resample_frames(int64_t in_frames, int in_rate, int out_rate, int64_t* out_frames);
+int rfx_pcm16_resample(const int16_t* d_in, int64_t in_frames, int in_channels, int in_rate, int out_channels, int out_rate,
+                       int16_t* d_out, int64_t out_frames, void* stream);
+int rfx_pcm16_clips_to_waveform(const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts, const int64_t* d_starts,
+                                int N, int Lw, int out_channels, float* d_wave_out, void* stream);
 
 /* ---- inverse, all the way from the image: SpectrogramImageConverter.audio_from_spectrogram_image's device half
  * (spectrogram_image_converter.py:54-91: image_util.spectrogram_from_image, audio_from_spectrogram -> waveform_from_mel_amplitudes

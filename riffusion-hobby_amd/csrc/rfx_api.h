@@ -47,6 +47,9 @@ struct DeviceGuard {
 #define RFX_ON_DEVICE(dev)   \
   DeviceGuard guard_((dev)); \
   if (guard_.err != hipSuccess) return fail(RFX_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
+// the argument checks the two clip-gather entries share (rfx_api_codec.hip)
+int check_pcm_clips(const char* who, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts, int N, int Lw,
+                    int out_channels);
 }  // namespace rfx
 
 #ifndef RFX_FWD_RUN_SKEW

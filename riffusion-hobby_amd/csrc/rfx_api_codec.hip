@@ -1,8 +1,10 @@
 // rfx_api_codec.hip - the C ABI of librfx.so (include/rfx.h), the entry points that take no plan: image decode / encode, int16 PCM,
-// its filters, compressor and stitch, and the image resize.  They run on the device that owns their output buffer.
+// its filters, compressor and stitch, the image resize, and the int16 front end of the encode (resample, channel mix, clip
+// gather).  They run on the device that owns their output buffer.
 #include "rfx_api.h"
 #include "rfx_compress_core.h"
 #include "rfx_pcm_core.h"
+#include "rfx_pcm_in_core.h"
 #include "rfx_resize_core.h"
 
 using namespace rfx;
@@ -183,5 +185,80 @@ int rfx_pcm16_apply_filters_compressed(const int16_t* d_pcm_in, int N, int L, in
     RFX_HIP(hipStreamSynchronize(s));  // h is released on return
   }
   RFX_HIP(launch_pcm_filters(x3, N, L, C, o->d_gain12_by_rms, o->d_boost_by_peak, d_pcm_out, (char*)d_workspace + w.filters, s));
+  return RFX_OK;
+}
+
+// ---- int16 front end of the encode (rfx_pcm_in.hip) -----------------------------------------------------------------------------
+// the reduced rates of a conversion, or an error: both rates positive, both reduced rates below 2^20 (rfx_pcm_in_core.h)
+static int resample_rates(const char* who, int in_rate, int out_rate, RatecvRates* r) {
+  if (in_rate <= 0 || out_rate <= 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rates must be positive");
+  *r = ratecv_rates(in_rate, out_rate);
+  if (r->a >= kRatecvRateLimit || r->b >= kRatecvRateLimit)
+    return fail(RFX_ERR_UNSUPPORTED, std::string(who) + ": reduced rates " + std::to_string(r->a) + " -> " + std::to_string(r->b) +
+                                         " (rate / gcd) must stay below 2^20: audioop's double division is only then the exact quotient");
+  return RFX_OK;
+}
+static bool channels_ok(int c) { return c == 1 || c == 2; }
+static bool frame_aligned(const void* p, int channels) { return reinterpret_cast<uintptr_t>(p) % (2 * (size_t)channels) == 0; }
+
+int rfx_pcm16_resample_frames(int64_t in_frames, int in_rate, int out_rate, int64_t* out_frames) {
+  if (in_frames <= 0 || !out_frames) return fail(RFX_ERR_INVALID, "rfx_pcm16_resample_frames: bad argument (in_frames >= 1, out_frames not NULL)");
+  RatecvRates r;
+  if (int rc = resample_rates("rfx_pcm16_resample_frames", in_rate, out_rate, &r)) return rc;
+  if (in_frames > INT64_MAX / kRatecvRateLimit) return fail(RFX_ERR_INVALID, "rfx_pcm16_resample_frames: in_frames too large");
+  *out_frames = ratecv_out_frames(in_frames, r);
+  return RFX_OK;
+}
+
+int rfx_pcm16_resample(const int16_t* d_in, int64_t in_frames, int in_channels, int in_rate, int out_channels, int out_rate,
+                       int16_t* d_out, int64_t out_frames, void* stream) {
+  if (in_frames <= 0) return fail(RFX_ERR_INVALID, "rfx_pcm16_resample: in_frames must be positive");
+  if (!channels_ok(in_channels) || !channels_ok(out_channels)) return fail(RFX_ERR_INVALID, "rfx_pcm16_resample: channel counts must be 1 or 2");
+  int64_t K = 0;
+  if (int rc = rfx_pcm16_resample_frames(in_frames, in_rate, out_rate, &K)) return rc;
+  if (out_frames != K)
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_resample: out_frames is " + std::to_string(out_frames) + ", " + std::to_string(in_frames) +
+                                     " frames give " + std::to_string(K) + " (rfx_pcm16_resample_frames)");
+  // one thread per run of kRatecvRun output frames, 256 threads per workgroup, at most 2^31 - 1 workgroups in a launch
+  if (K > ((int64_t)INT32_MAX - 1) * 256 * kRatecvRun)
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_pcm16_resample: " + std::to_string(K) + " output frames are more than one launch holds; resample in pieces");
+  if (!d_in || !d_out) return fail(RFX_ERR_INVALID, "rfx_pcm16_resample: null pointer");
+  if (!frame_aligned(d_in, in_channels) || !frame_aligned(d_out, out_channels))
+    return fail(RFX_ERR_INVALID, "rfx_pcm16_resample: pointers must be aligned to a frame (2 * channels bytes)");
+  int dev;
+  if (int rc = device_of(d_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_pcm_ratecv(d_in, in_channels, in_rate, out_channels, out_rate, d_out, K, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+namespace rfx {
+// what rfx_pcm16_clips_to_waveform and rfx_image_from_pcm16_clips check before any launch (N > 0): sizes, channel counts, and -
+// on the host copy of the starts - that every clip lies inside the recording; then the recording's pointer and its alignment
+int check_pcm_clips(const char* who, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts, int N, int Lw,
+                    int out_channels) {
+  if (frames <= 0 || Lw <= 0) return fail(RFX_ERR_INVALID, std::string(who) + ": frames and Lw must be positive");
+  if (!channels_ok(in_channels) || !channels_ok(out_channels)) return fail(RFX_ERR_INVALID, std::string(who) + ": channel counts must be 1 or 2");
+  if (!h_starts) return fail(RFX_ERR_INVALID, std::string(who) + ": h_starts is NULL");
+  for (int i = 0; i < N; ++i)
+    if (h_starts[i] < 0 || h_starts[i] > frames - Lw)
+      return fail(RFX_ERR_INVALID, std::string(who) + ": clip " + std::to_string(i) + " (frames " + std::to_string(h_starts[i]) + " + " +
+                                       std::to_string(Lw) + ") reaches outside the recording of " + std::to_string(frames) + " frames");
+  if (!d_pcm) return fail(RFX_ERR_INVALID, std::string(who) + ": null pointer");
+  if (!frame_aligned(d_pcm, in_channels)) return fail(RFX_ERR_INVALID, std::string(who) + ": d_pcm must be aligned to a frame (2 * channels bytes)");
+  return RFX_OK;
+}
+}  // namespace rfx
+
+int rfx_pcm16_clips_to_waveform(const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts, const int64_t* d_starts,
+                                int N, int Lw, int out_channels, float* d_wave_out, void* stream) {
+  if (N < 0) return fail(RFX_ERR_INVALID, "rfx_pcm16_clips_to_waveform: N is negative");
+  if (N == 0) return RFX_OK;
+  if (int rc = check_pcm_clips("rfx_pcm16_clips_to_waveform", d_pcm, frames, in_channels, h_starts, N, Lw, out_channels)) return rc;
+  if (!d_starts || !d_wave_out) return fail(RFX_ERR_INVALID, "rfx_pcm16_clips_to_waveform: null pointer");
+  int dev;
+  if (int rc = device_of(d_wave_out, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_pcm_clips(d_pcm, in_channels, d_starts, N, Lw, out_channels, d_wave_out, (hipStream_t)stream));
   return RFX_OK;
 }

@@ -1,5 +1,5 @@
 // rfx_api_forward.hip - the C ABI of librfx.so (include/rfx.h), forward half: layout conversion, STFT, the mel projections and
-// the image of a waveform.  Host code only: the drivers that sequence the kernels.
+// the image of a waveform or of int16 clips.  Host code only: the drivers that sequence the kernels.
 #include "rfx_api.h"
 
 using namespace rfx;
@@ -292,6 +292,46 @@ int rfx_image_from_waveform(const rfx_plan* plan, const float* d_wave, int N, in
   RFX_HIP(launch_image_encode_tm(mel_tm, keys_per_row ? keys : nullptr, C * keys_per_row, keys_per_row ? nullptr : reinterpret_cast<const float*>(keys),
                                  d_thresholds255, d_img_out, d_clip_max, N, M, plan->Mpad, T, C, (hipStream_t)stream));
   return RFX_OK;
+}
+
+// ---- the same from int16 clips of one recording (rfx_pcm_in.hip): the gathered (N*C, Lw) float32 rows, then the workspace of
+// rfx_image_from_waveform
+struct ImagePcmLayout {
+  size_t wave, fwd, fwd_bytes, total;
+};
+static ImagePcmLayout image_from_pcm16_clips_layout(const rfx_plan* plan, int N, int stereo, int Lw) {
+  ImagePcmLayout l{};
+  if (N <= 0 || Lw <= 0) return l;
+  l.fwd_bytes = image_from_waveform_layout(plan, N, stereo, Lw).total;
+  if (!l.fwd_bytes) return l;
+  Carve c;
+  l.wave = c.take((size_t)N * (stereo ? 2 : 1) * Lw * sizeof(float));
+  l.fwd = c.take(l.fwd_bytes);
+  l.total = c.at;
+  return l;
+}
+size_t rfx_image_from_pcm16_clips_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw) {
+  return plan ? image_from_pcm16_clips_layout(plan, N, stereo, Lw).total : 0;
+}
+
+int rfx_image_from_pcm16_clips(const rfx_plan* plan, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts,
+                               const int64_t* d_starts, int N, int Lw, int stereo, const float* d_thresholds255, float* d_clip_max,
+                               uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (N < 0) return fail(RFX_ERR_INVALID, "rfx_image_from_pcm16_clips: N is negative");
+  if (N == 0) return RFX_OK;
+  const int C = stereo ? 2 : 1;
+  if (int rc = check_pcm_clips("rfx_image_from_pcm16_clips", d_pcm, frames, in_channels, h_starts, N, Lw, C)) return rc;
+  if (!plan || !d_starts || !d_thresholds255 || !d_clip_max || !d_img_out || !d_workspace)
+    return fail(RFX_ERR_INVALID, "rfx_image_from_pcm16_clips: null pointer");
+  if (Lw <= plan->p.n_fft / 2) return fail(RFX_ERR_INVALID, "rfx_image_from_pcm16_clips: clips too short");
+  const ImagePcmLayout w = image_from_pcm16_clips_layout(plan, N, stereo, Lw);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_image_from_pcm16_clips: workspace too small");
+  float* wave = reinterpret_cast<float*>((char*)d_workspace + w.wave);
+  {
+    RFX_ON_DEVICE(plan->device);
+    RFX_HIP(launch_pcm_clips(d_pcm, in_channels, d_starts, N, Lw, C, wave, (hipStream_t)stream));
+  }
+  return rfx_image_from_waveform(plan, wave, N, stereo, Lw, d_thresholds255, d_clip_max, d_img_out, (char*)d_workspace + w.fwd, w.fwd_bytes, stream);
 }
 
 int rfx_mel_scale(const rfx_plan* plan, const float* d_lin_bft, int B, int T, float* d_mel_out, void* d_workspace,

@@ -419,4 +419,12 @@ hipError_t launch_resize(const uint8_t* in, int N, int H, int W, int OH, int OW,
                          int ksize_x, const int32_t* bounds_y, const int32_t* kk_y, int ksize_y, uint8_t* out, void* workspace,
                          hipStream_t s);
 
+// int16 front end of the encode (rfx_pcm_in.hip, arithmetic in rfx_pcm_in_core.h).  launch_pcm_ratecv: the (L, C_in) recording
+// `in`, mixed to C_out channels, then audioop.ratecv to the K = ratecv_out_frames(L, ...) frames of `out`; both pointers are
+// frame-aligned.  launch_pcm_clips: N clips of Lw frames at the frame offsets `starts` (device memory) of `pcm`, mixed to C_out
+// channels after the slice -> wave (N * C_out, Lw) float32.  Channel counts are 1 or 2; the callers have checked every bound.
+hipError_t launch_pcm_ratecv(const int16_t* in, int C_in, int64_t in_rate, int C_out, int64_t out_rate, int16_t* out, int64_t K,
+                             hipStream_t s);
+hipError_t launch_pcm_clips(const int16_t* pcm, int C_in, const int64_t* starts, int N, int64_t Lw, int C_out, float* wave, hipStream_t s);
+
 }  // namespace rfx

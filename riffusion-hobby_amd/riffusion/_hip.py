@@ -179,6 +179,12 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_image_resize_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rfx_image_resize_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_pcm16_resample_frames": (c_int, [ctypes.c_int64, c_int, c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "rfx_pcm16_resample": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p]),
+    "rfx_pcm16_clips_to_waveform": (c_int, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rfx_image_from_pcm16_clips_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_image_from_pcm16_clips": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 # PIL.Image.Resampling values of the filters rfx_image_resize_u8 implements (rfx_resize_filter)
@@ -198,6 +204,17 @@ def resize_coefficients(in_size: int, out_size: int, resample: int) -> np.ndarra
     if rc < 0:
         check(rc)
     return table
+
+
+CLIP_FRAMES_MAX = (1 << 31) - 1  # Lw of the clip entries is a C int
+
+
+def resample_frames(in_frames: int, in_rate: int, out_rate: int) -> int:
+    """rfx_pcm16_resample_frames (host only, no GPU): frames audioop.ratecv makes of `in_frames` frames; refuses rate pairs
+    whose reduced rates reach 2^20."""
+    out = ctypes.c_int64(0)
+    check(load_library().rfx_pcm16_resample_frames(int(in_frames), int(in_rate), int(out_rate), ctypes.byref(out)))
+    return int(out.value)
 
 
 def library_path() -> str:
@@ -891,6 +908,75 @@ class Plan:
         check(self.lib.rfx_pcm16_stitch(pcm.data_ptr(), N, L, C, host.data_ptr(), dev.data_ptr(), len(pieces), frames, out.data_ptr(),
                                         self._stream()))
         return out
+
+
+    # ---- int16 front end of the encode (rfx_pcm_in.hip): set_channels / set_frame_rate and the clip slicing on the device ---------
+    def _chk_pcm(self, pcm: torch.Tensor) -> torch.Tensor:
+        if pcm.dtype != torch.int16 or pcm.dim() != 2 or pcm.shape[1] not in (1, 2):
+            raise ValueError(f"expected a (frames, 1 or 2) int16 recording, got {tuple(pcm.shape)} {pcm.dtype}")
+        return self._chk(pcm)
+
+    def resample_pcm(self, pcm: torch.Tensor, in_rate: int, out_rate: int, out_channels: T.Optional[int] = None) -> torch.Tensor:
+        """PcmSegment / pydub `.set_channels(out_channels).set_frame_rate(out_rate)` of a (frames, C) int16 recording on this
+        device, byte for byte (rfx_pcm16_resample: audioop.tomono / tostereo on the stored frames, then audioop.ratecv) ->
+        (out_frames, out_channels) int16.  Equal rates only mix (or copy)."""
+        pcm = self._chk_pcm(pcm)
+        L, C = pcm.shape
+        C_out = C if out_channels is None else int(out_channels)
+        if C_out not in (1, 2):
+            raise ValueError(f"out_channels must be 1 or 2, got {out_channels}")
+        if L == 0:  # audioop.ratecv of no frames
+            return torch.empty((0, C_out), dtype=torch.int16, device=self.device)
+        K = resample_frames(L, in_rate, out_rate)
+        out = torch.empty((K, C_out), dtype=torch.int16, device=self.device)
+        check(self.lib.rfx_pcm16_resample(pcm.data_ptr(), L, C, int(in_rate), C_out, int(out_rate), out.data_ptr(), K, self._stream()))
+        return out
+
+    def _clip_starts(self, starts: T.Any, Lw: int) -> T.Tuple[torch.Tensor, torch.Tensor]:
+        if not 0 < int(Lw) <= CLIP_FRAMES_MAX:  # the C entries take Lw as an int
+            raise ValueError(f"clips must hold 1 .. {CLIP_FRAMES_MAX} frames, got {Lw}")
+        host = torch.as_tensor(np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1)))
+        return host, host.to(self.device)
+
+    def clips_to_waveform(self, pcm: torch.Tensor, starts: T.Any, Lw: int, out_channels: int) -> torch.Tensor:
+        """Clips of `Lw` frames at the frame offsets `starts` of a (frames, C) int16 recording on this device, mixed to
+        `out_channels` after the slice -> (N * out_channels, Lw) float32: what
+        `np.array([c.get_array_of_samples() for c in clip.set_channels(out_channels).split_to_mono()]).astype(np.float32)` gives
+        for every clip, bit for bit (rfx_pcm16_clips_to_waveform).  A clip outside the recording is refused before any launch."""
+        pcm = self._chk_pcm(pcm)
+        L, C = pcm.shape
+        host, dev = self._clip_starts(starts, Lw)
+        N = int(host.numel())
+        out = torch.empty((N * int(out_channels), int(Lw)), dtype=torch.float32, device=self.device)
+        check(self.lib.rfx_pcm16_clips_to_waveform(pcm.data_ptr(), L, C, host.data_ptr(), dev.data_ptr(), N, int(Lw), int(out_channels),
+                                                   out.data_ptr(), self._stream()))
+        return out
+
+    def image_from_pcm_clips(self, pcm: torch.Tensor, starts: T.Any, Lw: int, stereo: bool, thresholds: torch.Tensor):
+        """`clips_to_waveform` (to 2 channels when `stereo`, else 1) + `image_from_waveform` in one call
+        (rfx_image_from_pcm16_clips), same bytes: (frames, C) int16 -> ((N, n_mels, T, 3) uint8, per-clip max (N,)).  The float
+        waveforms live in the call's workspace only."""
+        pcm = self._chk_pcm(pcm)
+        thresholds = self._chk(thresholds, torch.float32)
+        L, C = pcm.shape
+        Lw = int(Lw)
+        host, dev = self._clip_starts(starts, Lw)
+        N = int(host.numel())
+        if Lw <= self.n_fft // 2:
+            raise RuntimeError(
+                f"Argument #4: Padding size should be less than the corresponding input dimension, "
+                f"but got: padding ({self.n_fft // 2}, {self.n_fft // 2}) at dimension 2 of input {[N * (2 if stereo else 1), Lw]}"
+            )
+        Tn = self.lib.rfx_stft_frames(self.handle, Lw)
+        img = torch.empty((N, self.n_mels, Tn, 3), dtype=torch.uint8, device=self.device)
+        mx = torch.empty((N,), dtype=torch.float32, device=self.device)
+        if N == 0:
+            return img, mx
+        with self._workspace(self.lib.rfx_image_from_pcm16_clips_workspace_bytes(self.handle, N, int(stereo), Lw)) as ws:
+            check(self.lib.rfx_image_from_pcm16_clips(self.handle, pcm.data_ptr(), L, C, host.data_ptr(), dev.data_ptr(), N, Lw, int(stereo),
+                                                      thresholds.data_ptr(), mx.data_ptr(), img.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      self._stream()))
+        return img, mx
 
 
 # Plans are cached, least recently used first out: a plan pins its tables on the device (the dense filterbank alone is

@@ -129,13 +129,27 @@ def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 
             print(f"Wrote {len(chunk)} clips to {output_dir}")
 
 
+def _device_convertible(seg: T.Any, sample_rate: int) -> bool:
+    """Can Plan.resample_pcm stand in for seg.set_channels(...).set_frame_rate(sample_rate)?  16-bit mono or stereo, a rate pair
+    whose reduced rates stay below 2^20 (include/rfx.h), and a length the clip entry's int holds; anything else keeps the host path."""
+    import math
+
+    if seg.sample_width != 2 or seg.channels not in (1, 2):
+        return False
+    g = math.gcd(int(seg.frame_rate), int(sample_rate))
+    if max(int(seg.frame_rate), int(sample_rate)) // g >= audio_util.RATECV_RATE_LIMIT:
+        return False
+    return 0 < audio_util.ratecv_frames(int(seg.frame_count()), int(seg.frame_rate), int(sample_rate)) < (1 << 31)
+
+
 def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: str = "jpg", step_size_ms: int = 10,
                           num_frequencies: int = 512, min_frequency: int = 0, max_frequency: int = 10000,
                           power_for_image: float = 0.25, mono: bool = False, sample_rate: int = 44100, device: str = "cuda",
                           num_threads: int = 0, limit: int = -1, batch_size: int = 64) -> None:
     """Process audio clips into spectrogram images in batch (reference cli.py:134-204, same flags and defaults: stereo
     tiles unless --mono, files resampled to --sample-rate, unreadable files skipped, jpg output).  Instead of one clip
-    per thread-pool task (`num_threads` is accepted and ignored) same-length clips go to the GPU `batch_size` at a time."""
+    per thread-pool task (`num_threads` is accepted and ignored) same-length clips go to the GPU `batch_size` at a time.  A file
+    whose channel count or rate differs is mixed and resampled on the device (Plan.resample_pcm), same bytes as pydub's."""
     import torch
 
     os.makedirs(output_dir, exist_ok=True)
@@ -151,8 +165,8 @@ def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: s
     converter = SpectrogramImageConverter(params=params, device=device)
     channels = 1 if mono else 2
     # Streaming: files are decoded one at a time and grouped by sample count (a GPU call needs equal lengths); a group is
-    # converted and released as soon as it holds `batch_size` clips, and when the waveforms held in host memory pass
-    # `max_pending_bytes` the LARGEST group is flushed early - a directory of long clips of many different lengths never
+    # converted and released as soon as it holds `batch_size` clips, and when the waveforms held - in host memory, or in device
+    # memory for files that were converted there: one budget for both - pass `max_pending_bytes` the LARGEST group is flushed early - a directory of long clips of many different lengths never
     # sits in RAM as a whole (the reference streams one file per thread-pool task, cli.py:172-204).
     max_pending_bytes = 2 << 30
     pending: T.Dict[int, T.List[T.Tuple[str, np.ndarray]]] = {}
@@ -162,7 +176,12 @@ def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: s
         nonlocal pending_bytes
         chunk = pending.pop(n_samples)
         pending_bytes -= sum(w.nbytes for _, w in chunk)
-        images, max_values = converter.spectrogram_images_from_waveforms(torch.from_numpy(np.stack([w for _, w in chunk])))
+        if all(isinstance(w, np.ndarray) for _, w in chunk):  # files that matched: one host stack, one upload
+            batch = torch.from_numpy(np.stack([w for _, w in chunk]))
+        else:  # a file converted on the device left its waveform there: the host ones of its group join it
+            plan = converter.converter._plan()
+            batch = torch.stack([w if isinstance(w, torch.Tensor) else torch.from_numpy(w).to(plan.device) for _, w in chunk])
+        images, max_values = converter.spectrogram_images_from_waveforms(batch)
         for (path, _), image, mx in zip(chunk, images, max_values):
             exif_data = params.to_exif()
             exif_data[SpectrogramParams.ExifTags.MAX_VALUE.value] = float(mx)
@@ -176,11 +195,20 @@ def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: s
             seg = _load_segment(path)
         except Exception:  # the reference skips files it cannot read (cli.py:176-179)
             continue
-        if seg.channels != channels:
-            seg = seg.set_channels(channels)
-        if seg.frame_rate != params.sample_rate:
-            seg = seg.set_frame_rate(params.sample_rate)
-        wave = np.array([c.get_array_of_samples() for c in seg.split_to_mono()]).astype(np.float32)
+        if (seg.channels != channels or seg.frame_rate != params.sample_rate) and _device_convertible(seg, params.sample_rate):
+            # set_channels, then set_frame_rate (reference cli.py:181-187) on the device, byte for byte: the int16 samples go up
+            # once and come back as the (channels, samples) float32 waveform, which stays there until its group is converted
+            plan = converter.converter._plan()
+            data = np.asarray(seg.get_array_of_samples(), dtype=np.int16).reshape(-1, seg.channels)
+            pcm = plan.resample_pcm(torch.from_numpy(np.ascontiguousarray(data)).to(plan.device), int(seg.frame_rate), params.sample_rate,
+                                    out_channels=channels)
+            wave = plan.clips_to_waveform(pcm, [0], int(pcm.shape[0]), channels)
+        else:
+            if seg.channels != channels:  # (more than two channels: pydub's own reduction, on the host)
+                seg = seg.set_channels(channels)
+            if seg.frame_rate != params.sample_rate:
+                seg = seg.set_frame_rate(params.sample_rate)
+            wave = np.array([c.get_array_of_samples() for c in seg.split_to_mono()]).astype(np.float32)
         del seg
         group = pending.setdefault(wave.shape[1], [])
         group.append((path, wave))

@@ -185,6 +185,61 @@ class SpectrogramImageConverter:
         img_np, mx_np = img.cpu().numpy(), mx.cpu().numpy()
         return [Image.fromarray(a, mode="RGB") for a in img_np], mx_np
 
+    def spectrogram_images_from_audio_clips(self, segment: T.Any, clip_start_times: T.Sequence[float], clip_duration_s: float,
+                                            return_device: bool = False) -> T.Tuple[T.Any, T.Any]:
+        """
+        One int16 track -> the spectrogram images of its clips: `[spectrogram_image_from_audio(c) for c in
+        slice_audio_into_clips(segment.set_frame_rate(params.sample_rate), clip_start_times, clip_duration_s)]`, same image
+        bytes and MAX_VALUEs, with the integer DSP on the device.  The track is uploaded once as int16; when its rate differs
+        from the params' it is resampled there (Plan.resample_pcm: audioop.ratecv, byte for byte); `audio_util.clip_frame_ranges`
+        resolves the reference's millisecond slicing to frame offsets, and one call gathers the clips - overlaps included - mixes
+        them to the params' channel count and converts them (Plan.image_from_pcm_clips).  A clip that nothing on the device
+        describes - the last clip when it takes the reference's silence branch, a slice cut short by the track's end - is built
+        by `slice_audio_into_clips` on the host, append's ValueError for less than 100 ms of missing audio included, and
+        converted in a call of its own: it has its own length and hence its own tile width.
+        Returns what `spectrogram_images_from_waveforms` returns: the N images and their float32 MAX_VALUEs in the order of
+        `clip_start_times`; with `return_device=True` the (N, n_mels, T, 3) uint8 tensor and the (N,) maxima on the GPU - or,
+        when a host-built clip has another width, a list of N (n_mels, T_i, 3) tensors and the (N,) maxima.
+        """
+        conv = self.converter
+        plan = conv._plan()
+        if segment.sample_width != 2 or segment.channels not in (1, 2):
+            raise ValueError("spectrogram_images_from_audio_clips takes 16-bit mono or stereo audio")
+        n = len(clip_start_times)
+        C = 2 if self.p.stereo else 1
+        data = np.asarray(segment.get_array_of_samples(), dtype=np.int16).reshape(-1, segment.channels)
+        pcm = torch.from_numpy(np.ascontiguousarray(data)).to(plan.device)
+        if int(segment.frame_rate) != self.p.sample_rate:
+            pcm = plan.resample_pcm(pcm, int(segment.frame_rate), self.p.sample_rate)
+        r = audio_util.clip_frame_ranges(int(pcm.shape[0]), self.p.sample_rate, clip_start_times, clip_duration_s)
+        power = float(self.p.power_for_image)
+        thr = plan.device_constant(("encode_thresholds", power), lambda: image_util.encode_thresholds(power))
+        tiles: T.List[T.Any] = [None] * n
+        maxima = torch.empty(n, dtype=torch.float32, device=plan.device)
+        if len(r.index):
+            img, mx = plan.image_from_pcm_clips(pcm, r.starts, r.frames, self.p.stereo, thr)
+            index = torch.from_numpy(r.index).to(plan.device)
+            maxima[index] = mx
+            for j, i in enumerate(r.index):
+                tiles[i] = img[j]
+        if len(r.host_index):
+            # the track as the host path would see it after set_frame_rate (the device's bytes are audioop's)
+            track = segment if int(segment.frame_rate) == self.p.sample_rate else audio_util.PcmSegment(pcm.cpu().numpy(), self.p.sample_rate)
+            clips = audio_util.slice_audio_into_clips(track, clip_start_times, clip_duration_s)
+            for i in r.host_index:
+                clip = clips[i].set_channels(C)
+                wave = np.array([c.get_array_of_samples() for c in clip.split_to_mono()]).astype(np.float32)
+                img, mx = self.spectrogram_images_from_waveforms(torch.from_numpy(wave)[None], return_device=True)
+                tiles[i], maxima[i] = img[0], mx[0]
+        same_width = len({int(t.shape[1]) for t in tiles}) <= 1
+        if return_device:
+            if not same_width:
+                return tiles, maxima
+            if n and len(r.index) == n:
+                return img, maxima
+            return (torch.stack(tiles) if n else torch.empty((0, plan.n_mels, 0, 3), dtype=torch.uint8, device=plan.device)), maxima
+        return [Image.fromarray(t.cpu().numpy(), mode="RGB") for t in tiles], maxima.cpu().numpy()
+
     # ---- resizing tiles on the device: PIL.Image.resize, byte for byte (rfx_image_resize_u8) --------------------------------
     def resize_images(self, images: T.Any, size: T.Tuple[int, int], resample: int = Image.BICUBIC) -> torch.Tensor:
         """

@@ -7,7 +7,7 @@ is installed the functions return real `pydub.AudioSegment`s exactly like the re
 not (this image has no pydub) they return `PcmSegment`, a small stand-in that offers the part of the
 AudioSegment interface the spectrogram path and its callers touch (frame_rate, channels,
 sample_width, split_to_mono, get_array_of_samples, set_channels, set_frame_rate, duration_seconds,
-rms / dBFS / max, apply_gain, append with crossfade, overlay, export to wav).
+rms / dBFS / max, apply_gain, append with crossfade, overlay, export to wav).  set_frame_rate has a restatement of its own (ratecv_np).
 
 pydub.AudioSegment is a thin layer over CPython's `audioop` C module (mul, rms, max, tomono,
 tostereo, ratecv, add).  `PcmSegment` calls the same `audioop` functions when the interpreter still
@@ -115,7 +115,7 @@ class PcmSegment:
         if int(frame_rate) == self.frame_rate:
             return self
         if _audioop is None:
-            raise NotImplementedError("resampling needs CPython's audioop module (or pydub)")
+            return PcmSegment(ratecv_np(self._data, self.frame_rate, int(frame_rate)), int(frame_rate))
         raw, _ = _audioop.ratecv(self._bytes(), 2, self.channels, self.frame_rate, int(frame_rate), None)
         return self._spawn(raw, frame_rate=int(frame_rate))
 
@@ -277,6 +277,90 @@ class PcmSegment:
         if data.dtype != np.int16:
             raise NotImplementedError("only 16-bit PCM wav files are supported without pydub")
         return cls(data, rate)
+
+
+RATECV_RATE_LIMIT = 1 << 20  # reduced rates (rate / gcd) below this: audioop's double division is then the exact quotient
+
+
+def ratecv_frames(in_frames: int, in_rate: int, out_rate: int) -> int:
+    """Frames audioop.ratecv(data, 2, C, in_rate, out_rate, None) returns for `in_frames` frames."""
+    g = math.gcd(int(in_rate), int(out_rate))
+    a, b = int(in_rate) // g, int(out_rate) // g
+    return 0 if in_frames <= 0 else (int(in_frames) - 1) * b // a + 1
+
+
+def ratecv_np(x: np.ndarray, in_rate: int, out_rate: int) -> np.ndarray:
+    """audioop.ratecv(data, 2, C, in_rate, out_rate, None)[0] on (L, C) int16 frames, in closed form: with a = in_rate / g,
+    b = out_rate / g, output k is emitted when n_k = 1 + ceil(k a / b) input frames are consumed, with audioop's counter at
+    d_k = (n_k - 1) b - k a, and is trunc(((x[n_k - 2] << 16) d_k + (x[n_k - 1] << 16) (b - d_k)) / b) >> 16 (x[-1] = 0).  audioop
+    divides in double; while b < 2^21 that is the integer quotient taken here, so reduced rates of 2^20 or more are refused
+    (csrc/rfx_pcm_in_core.h states the same arithmetic for the device)."""
+    x = np.asarray(x)
+    if x.ndim == 1:
+        x = x[:, None]
+    if x.dtype != np.int16:
+        raise TypeError("ratecv_np resamples int16 frames")
+    if int(in_rate) <= 0 or int(out_rate) <= 0:
+        raise ValueError("sampling rate not > 0")  # audioop's message
+    g = math.gcd(int(in_rate), int(out_rate))
+    a, b = int(in_rate) // g, int(out_rate) // g
+    if a >= RATECV_RATE_LIMIT or b >= RATECV_RATE_LIMIT:
+        raise ValueError(f"reduced rates {a} -> {b} must stay below 2^20")
+    L, C = x.shape
+    K = ratecv_frames(L, in_rate, out_rate)
+    if K == 0:
+        return np.zeros((0, C), dtype=np.int16)
+    k = np.arange(K, dtype=np.int64)
+    n = 1 + (k * a + b - 1) // b
+    d = ((n - 1) * b - k * a)[:, None]
+    wide = np.concatenate([np.zeros((1, C), np.int64), x.astype(np.int64) << 16])  # wide[j + 1] = x[j] << 16
+    num = wide[n - 1] * d + wide[n] * (b - d)
+    q = np.where(num >= 0, num // b, -((-num) // b))  # truncation toward zero
+    return (q >> 16).astype(np.int16)
+
+
+class ClipRanges(T.NamedTuple):
+    """clip_frame_ranges' answer.  `index`: positions in clip_start_times of the clips that lie wholly inside the track and are
+    `frames` long, `starts` their first frames; `host_index`: the other clips (a slice that reaches the track's end, a length
+    that the millisecond arithmetic makes one frame off) - slice_audio_into_clips builds those; `last_short`: the last clip
+    takes the reference's silence branch (it is then in `host_index`)."""
+
+    index: np.ndarray
+    starts: np.ndarray
+    frames: int
+    host_index: np.ndarray
+    last_short: bool
+
+
+def clip_frame_ranges(segment_frames: int, frame_rate: int, clip_start_times: T.Sequence[float], clip_duration_s: float) -> ClipRanges:
+    """The frames `slice_audio_into_clips` cuts, from lengths alone (as stitch_plan plans a stitch): clip i is
+    PcmSegment._slice_ms(int(t_i * 1000), int(t_i * 1000) + int(clip_duration_s * 1000)) - bounds clipped to the track's length
+    rounded to whole milliseconds, positions int(ms * (rate / 1000.0)) - and the last clip gets silence appended when
+    int(its duration * 1000) falls short of the clip duration.  `frames` is the length of a clip that nothing cuts short,
+    int(duration_ms * (rate / 1000.0)) for a start at 0 (220 500 for 5 s at 44.1 kHz)."""
+    frames_total, rate = int(segment_frames), int(frame_rate)
+    per_ms = rate / 1000.0
+    length_ms = int(round(1000.0 * (frames_total / float(rate))))  # PcmSegment.__len__
+    duration_ms = int(clip_duration_s * 1000)
+    Lw = int(duration_ms * per_ms)
+    n = len(clip_start_times)
+    index, starts, host = [], [], []
+    last_short = False
+    for i, t in enumerate(clip_start_times):
+        start_ms = int(t * 1000)
+        lo, hi = min(start_ms, length_ms), min(start_ms + duration_ms, length_ms)
+        a, b = int(lo * per_ms), int(hi * per_ms)
+        whole = start_ms >= 0 and b > a and b <= frames_total and b - a == Lw and hi == start_ms + duration_ms
+        if i == n - 1:
+            got = max(0, b - a)  # with its padding
+            if duration_ms - int((got / float(rate)) * 1000) > 0:
+                last_short, whole = True, False
+        if whole:
+            index.append(i)
+            starts.append(a)
+        else:
+            host.append(i)
+    return ClipRanges(np.array(index, dtype=np.int64), np.array(starts, dtype=np.int64), Lw, np.array(host, dtype=np.int64), last_short)
 
 
 def pcm16_from_waveform(samples: np.ndarray, normalize: bool = False) -> np.ndarray:
