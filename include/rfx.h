@@ -222,6 +222,33 @@ int rfx_unpack_complex(const rfx_plan* plan, const void* d_slots, int B, int T, 
 int rfx_stft(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots,
              void* stream);
 
+/* ---- quality of a decode: the two sums of spectral convergence, || |STFT(x)| - S || / || S ||, per row --------------------------
+ * d_wave (B, L) float32, L = rfx_griffinlim_output_samples(plan, T) (its STFT has exactly T frames; L must exceed n_fft/2, as for
+ * rfx_stft); d_mag_slots: the target S, magnitudes in slot layout, B * T frames (what rfx_inverse_mel writes and rfx_griffinlim
+ * reads).  For row r, d_sums_out[2 r] = sum (a - m)^2 and d_sums_out[2 r + 1] = sum m^2 over every one of the n_stft bins of every
+ * one of the T frames exactly once (padding positions and the second copy of the 440 bins the specialised layout stores twice are
+ * not counted): a = the magnitude rfx_stft gives for the row (formed in the workspace), m = the target.  a - m is formed in double
+ * from the two float32 values (exact); squares and sums are double: magnitudes up to the 1e33 of "Numeric range" square to 1e66.
+ * Spectral convergence of a row is sqrt(sums[0] / sums[1]); of a clip, sqrt of the ratio of its channels' added sums.  Two sums,
+ * not a ratio, so that the caller pools rows exactly and decides what a silent target (sum m^2 == 0) means.
+ * Deterministic and batch-invariant: a row's reduction is one fixed tree whose shape depends on (T, plan) alone - no atomics,
+ * nothing depends on B, on the row's place in the call or on the launch grid - so a row's 16 bytes are the same alone and in any
+ * batch.  Each sum is within n * 2^-52 (relative; n = n_stft * T) of the exact sum of its float32 inputs.
+ * Against the CPU oracle (oracle/riffusion_oracle.py spectral_convergence: torch.stft and both norms in float32) the value differs by
+ * the ORACLE's float32 error: on 4-iteration Griffin-Lim results of 64-column ranges of the five golden tiles the oracle's own
+ * float32-vs-float64 distance for the figure was measured at 1.3e-6 .. 8.8e-6 relative on one host and 4e-7 .. 6.0e-5 on another
+ * (it moves with the input and with the host's torch build and thread count), while this entry's value sat 4e-9 .. 1.2e-8 from the
+ * float64 figure.  The test therefore measures the oracle's distance on its own inputs in the same run and allows 2 times the
+ * largest: this library's figure and the oracle's float32 figure each lie within that distance of the float64 figure - this one far
+ * closer, its transform being float32 as well but its sums double - hence within twice of it of each other.
+ * All three frame engines.  The rows are walked in groups, so the workspace is bounded whatever B is: the magnitudes of
+ * max(1, 128 MiB / (T * frame_stride * 4 bytes)) rows plus 16 bytes per four frames of them - at most 128 MiB + 64 KiB + 512
+ * bytes, or one row's magnitudes (and partial sums) when a row alone is larger.  B == 0 is a no-op.  d_mag_slots and d_workspace
+ * must be 16-byte aligned.  Row and element offsets are 64-bit: B past 65535 and slot offsets past 2^31 elements are served. */
+size_t rfx_spectral_error_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_spectral_error(const rfx_plan* plan, const float* d_wave /* (B, L) */, const float* d_mag_slots, int B, int T,
+                       double* d_sums_out /* (B, 2) */, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- inverse: torchaudio.transforms.GriffinLim(n_iter, momentum=0.99, rand_init=True, power=1)
  * spectrogram_converter.py:62-73, called at :204.
  * d_mag_slots: magnitudes in slot layout; d_angles0_slots: optional injected initial angles

@@ -1,5 +1,6 @@
 // rfx_api_forward.hip - the C ABI of librfx.so (include/rfx.h), forward half: layout conversion, STFT, the mel projections and
-// the image of a waveform or of int16 clips.  Host code only: the drivers that sequence the kernels.
+// the image of a waveform or of int16 clips, and the spectral error of a decode.  Host code only: the drivers that sequence
+// the kernels.
 #include "rfx_api.h"
 
 using namespace rfx;
@@ -350,4 +351,57 @@ int rfx_mel_scale(const rfx_plan* plan, const float* d_lin_bft, int B, int T, fl
   }
   RFX_HIP(launch_pack_mag(d_lin_bft, mag, B, T, stream));
   return mel_gemm(plan, mag, B, T, d_mel_out, stream);
+}
+
+// ---- spectral error of a decode: how far the magnitudes of a waveform are from the magnitudes it was made from -----------------
+// The plan's own forward transform of the rows into the workspace (rfx_stft: any of the three frame engines), then the reduction
+// of rfx_quality.hip over that tensor and the target.  The rows are walked in groups of whole rows whose magnitudes fill at most
+// kQualGroupBytes (at least one row), so the workspace does not grow with the batch: the transformed magnitudes of a group, then
+// the group's partial sums.  A row's result does not depend on the group it falls in (rfx_quality_core.h).
+constexpr size_t kQualGroupBytes = (size_t)128 << 20;
+struct SpectralErrorLayout {
+  size_t mag, partials, total;
+  int group_rows;
+};
+static SpectralErrorLayout spectral_error_layout(const rfx_plan* plan, int B, int T) {
+  SpectralErrorLayout l{};
+  if (B <= 0 || T < 2) return l;
+  const size_t row_bytes = (size_t)T * plan->frame_stride * sizeof(float);
+  size_t rows = kQualGroupBytes / row_bytes;
+  rows = rows < 1 ? 1 : rows > (size_t)B ? (size_t)B : rows;
+  l.group_rows = (int)rows;
+  Carve c;
+  l.mag = c.take(rows * row_bytes);
+  l.partials = c.take(qual_partials_bytes(l.group_rows, T));
+  l.total = c.at;
+  return l;
+}
+size_t rfx_spectral_error_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? spectral_error_layout(plan, B, T).total : 0; }
+
+int rfx_spectral_error(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out,
+                       void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (B < 0) return fail(RFX_ERR_INVALID, "rfx_spectral_error: B is negative");
+  if (B == 0) return RFX_OK;
+  if (!plan || !d_wave || !d_mag_slots || !d_sums_out || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_spectral_error: null argument");
+  if (T < 2) return fail(RFX_ERR_INVALID, "rfx_spectral_error: T must be at least 2");
+  const int L = rfx_griffinlim_output_samples(plan, T);
+  if (L <= plan->p.n_fft / 2 || stft_frames(plan, L) != T)
+    return fail(RFX_ERR_INVALID, "rfx_spectral_error: the " + std::to_string(L) + " samples of " + std::to_string(T) +
+                                     " frames are not more than the forward transform's reflect padding, n_fft/2 = " + std::to_string(plan->p.n_fft / 2));
+  if (((uintptr_t)d_mag_slots | (uintptr_t)d_workspace) & 15 || ((uintptr_t)d_sums_out & 7) || (plan->frame_stride & 3))
+    return fail(RFX_ERR_INVALID, "rfx_spectral_error: d_mag_slots and d_workspace must be 16-byte aligned, d_sums_out 8-byte aligned");
+  const SpectralErrorLayout w = spectral_error_layout(plan, B, T);
+  if (workspace_bytes < w.total)
+    return fail(RFX_ERR_WORKSPACE, "rfx_spectral_error: workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(w.total) + " needed)");
+  RFX_ON_DEVICE(plan->device);
+  float* mag = reinterpret_cast<float*>((char*)d_workspace + w.mag);
+  void* partials = (char*)d_workspace + w.partials;
+  const size_t row_elems = (size_t)T * plan->frame_stride;
+  for (int r0 = 0; r0 < B; r0 += w.group_rows) {
+    const int rows = B - r0 < w.group_rows ? B - r0 : w.group_rows;
+    if (int rc = rfx_stft(plan, d_wave + (size_t)r0 * L, rows, L, mag, nullptr, stream)) return rc;
+    RFX_HIP(launch_spectral_sums(mag, d_mag_slots + (size_t)r0 * row_elems, rows, T, plan->frame_stride, plan->n_stft, plan->generic, partials,
+                                 d_sums_out + 2 * (size_t)r0, (hipStream_t)stream));
+  }
+  return RFX_OK;
 }

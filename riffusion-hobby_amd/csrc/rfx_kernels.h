@@ -427,4 +427,12 @@ hipError_t launch_pcm_ratecv(const int16_t* in, int C_in, int64_t in_rate, int C
                              hipStream_t s);
 hipError_t launch_pcm_clips(const int16_t* pcm, int C_in, const int64_t* starts, int N, int64_t Lw, int C_out, float* wave, hipStream_t s);
 
+// spectral error (rfx_quality.hip, arithmetic and reduction shape in rfx_quality_core.h): `rows` rows of T frames of `a` and `m`,
+// fs floats per frame (a multiple of four; both tensors 16-byte aligned) -> sums[2 r] = sum (a - m)^2, sums[2 r + 1] = sum m^2
+// in double over the n_stft bins of every frame, each once (plain: bin-ordered frames, else the specialised slot layout).  Two
+// launches: one workgroup per four frames into `partials` (qual_partials_bytes), then one per row.  rows * ceil(T / 4) < 2^31.
+size_t qual_partials_bytes(int rows, int T);
+hipError_t launch_spectral_sums(const float* a, const float* m, int rows, int T, int fs, int n_stft, bool plain, void* partials, double* sums,
+                                hipStream_t s);
+
 }  // namespace rfx

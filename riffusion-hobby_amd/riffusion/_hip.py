@@ -131,6 +131,8 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_pack_complex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "rfx_unpack_complex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "rfx_stft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rfx_spectral_error_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_spectral_error": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_griffinlim_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_output_samples": (c_int, [c_void_p, c_int]),
     "rfx_griffinlim": (
@@ -581,6 +583,26 @@ class Plan:
             )
         )
         return out
+
+    def spectral_error(self, wave: torch.Tensor, mag_slots: torch.Tensor, B: int, Tn: int) -> torch.Tensor:
+        """rfx_spectral_error: (B, L) waveforms, L = the samples Griffin-Lim makes of Tn frames, against magnitudes in slot layout
+        -> (B, 2) float64, per row sum (|STFT(wave)| - mag)^2 and sum mag^2 over every bin of every frame once.  A row's two
+        sums do not depend on the batch it is computed in.  Spectral convergence is sqrt(sums[:, 0] / sums[:, 1])."""
+        wave = self._chk(wave, torch.float32)
+        mag_slots = self._chk(mag_slots, torch.float32)
+        B, Tn = int(B), int(Tn)
+        L = self.lib.rfx_griffinlim_output_samples(self.handle, Tn)
+        if tuple(wave.shape) != (B, L):
+            raise ValueError(f"{B} rows of {Tn} frames are waveforms of shape {(B, L)}, got {tuple(wave.shape)}")
+        if mag_slots.numel() < B * Tn * self.frame_stride:
+            raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
+        sums = torch.empty((B, 2), dtype=torch.float64, device=self.device)
+        if B == 0:
+            return sums
+        with self._workspace(max(1, self.lib.rfx_spectral_error_workspace_bytes(self.handle, B, Tn))) as ws:
+            check(self.lib.rfx_spectral_error(self.handle, wave.data_ptr(), mag_slots.data_ptr(), B, Tn, sums.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), self._stream()))
+        return sums
 
     def unpack_magnitudes(self, slots: torch.Tensor, B: int, Tn: int) -> torch.Tensor:
         slots = self._chk(slots, torch.float32)

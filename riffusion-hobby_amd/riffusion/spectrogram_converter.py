@@ -171,17 +171,43 @@ class SpectrogramConverter:
 
     def _waveform_from_mel(self, plan: T.Any, amplitudes_mel: torch.Tensor, *, spec0: T.Optional[torch.Tensor] = None,
                            angles0: T.Optional[torch.Tensor] = None, seed: T.Optional[int] = None,
-                           channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0) -> torch.Tensor:
+                           channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0,
+                           return_slots: bool = False) -> T.Any:
         """`waveform_from_mel_amplitudes` on a plan the caller already holds (the batch entry points fetch it once per call,
-        not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild)."""
+        not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild).
+        `return_slots=True` runs the two inverse stages separately - same bits as the one call - and returns
+        (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares."""
         mel = amplitudes_mel.to(self.device)
         B, _, Tn = mel.shape
         cpc = B if channels_per_clip is None else channels_per_clip
         s = self._seed(seed)
-        if spec0 is None and angles0 is None:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
+        if spec0 is None and angles0 is None and not return_slots:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
             return plan.waveform_from_mel(mel, cpc, self.p.num_griffin_lim_iters, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         spec0 = spec0.to(self.device) if spec0 is not None else None
         lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         a0 = plan.pack_complex(angles0.to(self.device)) if angles0 is not None else None
-        return plan.griffinlim(lin_slots, B, Tn, self.p.num_griffin_lim_iters, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
+        wave = plan.griffinlim(lin_slots, B, Tn, self.p.num_griffin_lim_iters, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
                                magnitude_hint=magnitude_hint)
+        return (wave, lin_slots) if return_slots else wave
+
+    # ---- quality of a decode ------------------------------------------------------------------------
+    @staticmethod
+    def convergence_from_sums(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+        """sqrt(num / den) of the two sums of `Plan.spectral_error` (float64).  A silent target (den == 0) gives 0.0 where the
+        waveform's spectrum is silent too (num == 0), else inf."""
+        ratio = torch.sqrt(num / torch.where(den > 0, den, torch.ones_like(den)))
+        silent = torch.where(num > 0, torch.full_like(num, float("inf")), torch.zeros_like(num))
+        return torch.where(den > 0, ratio, silent)
+
+    def spectral_convergence(self, waveform: torch.Tensor, magnitudes: torch.Tensor) -> torch.Tensor:
+        """
+        || |STFT(waveform)| - magnitudes || / || magnitudes || per row, on the device: (B, L) float32 waveforms - L the length
+        Griffin-Lim gives T frames, hop * (T - 1) - and (B, n_stft, T) float32 magnitudes in the reference's layout -> (B,) float64.
+        The one quality figure of a Griffin-Lim result that does not depend on its random start.  Deterministic: a row's value
+        is the same alone and in any batch (rfx_spectral_error).
+        """
+        plan = self._plan()
+        mag = magnitudes.to(self.device)
+        B, _, Tn = mag.shape
+        sums = plan.spectral_error(waveform.to(self.device), plan.pack_magnitudes(mag), B, Tn)
+        return self.convergence_from_sums(sums[:, 0], sums[:, 1])

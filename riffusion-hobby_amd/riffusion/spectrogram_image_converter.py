@@ -89,6 +89,7 @@ class SpectrogramImageConverter:
         return_device: bool = False,
         compression: bool = False,
         size: T.Optional[T.Tuple[int, int]] = None,
+        return_error: bool = False,
     ) -> T.Any:
         """
         A sequence of tiles -> ONE audio segment: every tile decoded (`audio_from_spectrogram_images`), filtered
@@ -105,12 +106,17 @@ class SpectrogramImageConverter:
         `audio_from_spectrogram_images`); the stitch is planned for the clips of that width.  Tiles of different sizes in a list
         (without `size`) are decoded one by one, each with the random starts of its index in the sequence, and stitched on the
         host.
+        `return_error=True` returns (segment, errors): the per-clip spectral convergence of `audio_from_spectrogram_images`
+        ((n,) float64; a device tensor with `return_device=True`); the segment's bytes do not change.  Not for tiles of
+        different sizes without `size`.
         """
         if isinstance(images, (list, tuple)):
             arrays = [np.asarray(image_util.rgb_array_from_image(im)) if isinstance(im, Image.Image) else np.asarray(im)
                       for im in images]
             if len({a.shape for a in arrays}) > 1:
                 if size is None:
+                    if return_error:
+                        raise ValueError("return_error needs tiles of one size (or `size`): clips decoded one by one carry no error figure")
                     return self._image_sequence_mixed(arrays, crossfade_s, apply_filters, max_value, seed, return_device, compression)
                 images, size = torch.cat([self.resize_images(a[None], size) for a in arrays]), None
             else:
@@ -127,7 +133,13 @@ class SpectrogramImageConverter:
         except audio_util.StitchNotPlannable:  # a crossfade that reaches into the previous one: pydub's own loop, on the host
             on_device = False
         pcm = self.audio_from_spectrogram_images(images, max_value=max_value, seed=seed, tiles_per_call=tiles_per_call,
-                                                 return_device=True, apply_filters=apply_filters, compression=compression, size=size)
+                                                 return_device=True, apply_filters=apply_filters, compression=compression, size=size,
+                                                 return_error=return_error)
+        errors = None
+        if return_error:
+            pcm, errors = pcm
+            if not return_device:
+                errors = errors.cpu().numpy()
         if n == 1:
             joined = pcm[0]
         elif on_device:
@@ -136,9 +148,9 @@ class SpectrogramImageConverter:
             segs = [audio_util.PcmSegment(clip, self.p.sample_rate) for clip in pcm.cpu().numpy()]
             joined = torch.from_numpy(audio_util.stitch_segments(segs, crossfade_s).get_array_of_samples().reshape(-1, C).copy())
             joined = joined.to(plan.device)
-        if return_device:
-            return joined
-        return audio_util.segment_from_pcm16(joined.cpu().numpy(), self.p.sample_rate)
+        if not return_device:
+            joined = audio_util.segment_from_pcm16(joined.cpu().numpy(), self.p.sample_rate)
+        return (joined, errors) if return_error else joined
 
     def _image_sequence_mixed(self, arrays: T.List[np.ndarray], crossfade_s: float, apply_filters: bool, max_value: float,
                               seed: T.Optional[int], return_device: bool, compression: bool) -> T.Any:
@@ -300,7 +312,8 @@ class SpectrogramImageConverter:
         apply_filters: bool = False,
         compression: bool = False,
         size: T.Optional[T.Tuple[int, int]] = None,
-    ) -> T.Union[np.ndarray, torch.Tensor, T.Tuple[torch.Tensor, torch.Tensor]]:
+        return_error: bool = False,
+    ) -> T.Any:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
         float waveforms); a numpy array on the host, or with `return_device=True` a tensor that never left the GPU.
@@ -345,6 +358,14 @@ class SpectrogramImageConverter:
         quantisation of a float input) - audio-to-audio's step back from the pipeline's 512-wide output to the clip's own width
         (streamlit/tasks/audio_to_audio.py:287).  The clip length then follows that width; the resize is per tile, so a clip's
         bytes still do not depend on the chunking or the sharding.
+        `return_error=True` returns (result, errors): `errors` is the (n,) float64 spectral convergence of every clip,
+        sqrt(sum over the clip's channels of || |STFT(x)| - S ||^2 / sum over them of || S ||^2), of the float waveform x
+        Griffin-Lim produced against the linear magnitudes S InverseMelScale handed it - before peak normalisation and int16
+        truncation; a numpy array, or with `return_device=True` a tensor on the GPU (then `(result, errors)` comes before
+        `return_range_flag`'s flag: `(result, errors, range_ok)`).  The chunk then goes through the separate stages (decode,
+        InverseMelScale, Griffin-Lim, `Plan.spectral_error`, PCM) instead of the one fused call: `result` is byte for byte the
+        result without the flag, and a clip's error does not depend on `tiles_per_call` (rfx_spectral_error is batch-invariant).
+        A silent target gives 0.0 (silent audio) or inf.  Not with `group`.
         """
         from riffusion import batch_shard
 
@@ -356,6 +377,8 @@ class SpectrogramImageConverter:
             raise ValueError("apply_filters works on int16 PCM: it does not go with return_waveform=True")
         if return_range_flag and not return_device:
             raise ValueError("return_range_flag goes with return_device=True (a host result raises on a failed range check instead)")
+        if return_error and group is not None:
+            raise ValueError("return_error does not go with `group`: the errors of a sharded batch are not gathered")
         if gather is None:
             gather = batch_shard.default_gather(group)
         if gather not in batch_shard.GATHER_MODES:
@@ -392,6 +415,8 @@ class SpectrogramImageConverter:
         # a shard that takes part in a collective stays on the device until the collective has run
         collective = world > 1 and gather != "none"
 
+        error_sums: T.List[torch.Tensor] = []  # return_error: per chunk the (clips, 2) sums, a clip's channels added
+
         def convert(lo: int, hi: int) -> torch.Tensor:
             sink = batch_shard.ChunkSink(hi - lo, row_shape, dtype, plan.device, to_host=not (collective or return_device))
             bounds = [(a, min(hi, a + tiles_per_call)) for a in range(lo, hi, tiles_per_call)]  # bounded working set: |S| alone is 19 MB per tile-channel
@@ -401,7 +426,18 @@ class SpectrogramImageConverter:
                 tiles = source.get(i)
                 if size is not None:
                     tiles = plan.resize_images(tiles, size[1], size[0], Image.BICUBIC)
-                if return_waveform:
+                if return_error:  # the stages one by one (same bytes as the fused calls below): the error needs both ends of Griffin-Lim
+                    mel = plan.image_decode(tiles, self.p.stereo, lut)
+                    wave, lin_slots = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C,
+                                                              magnitude_hint=max_value, return_slots=True)
+                    error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1])).reshape(b - a, C, 2).sum(1))
+                    if return_waveform:
+                        out = wave.reshape(b - a, C, -1)
+                    else:
+                        out = plan.pcm16(wave, C, normalize=True, out=sink.rows(a - lo, b - lo))[0]
+                        if apply_filters:
+                            out = self._filter_pcm(plan, out, compression)
+                elif return_waveform:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value)
                     out = wave.reshape(b - a, C, -1)
@@ -417,6 +453,10 @@ class SpectrogramImageConverter:
             return sink.finish()  # a rank with an empty shard still joins the collective with 0 rows
 
         result = batch_shard.sharded_map(convert, n_total, group, gather)
+        errors = None
+        if return_error:
+            sums = torch.cat(error_sums) if error_sums else torch.zeros((0, 2), dtype=torch.float64, device=plan.device)
+            errors = conv.convergence_from_sums(sums[:, 0], sums[:, 1])
         if return_device:
             if range_ok is not None:
                 # nothing on this path ever synchronises, so the deferred check cannot raise here: out-of-range (or NaN) input
@@ -427,6 +467,8 @@ class SpectrogramImageConverter:
             # attribute: slicing / .to() / a gather make a new tensor without it - read it from the tensor this call returned.
             flag = range_ok if range_ok is not None else torch.ones((), dtype=torch.bool, device=result.device)
             result.range_ok = flag
+            if return_error:
+                return (result, errors, flag) if return_range_flag else (result, errors)
             return (result, flag) if return_range_flag else result
         if result.is_cuda:
             host = torch.empty(result.shape, dtype=result.dtype, pin_memory=True)  # gathered batch: one pinned copy
@@ -435,4 +477,4 @@ class SpectrogramImageConverter:
             result = host
         if range_ok is not None and not bool(range_ok):  # the stream has been synchronised above / by the sink: no extra wait
             raise ValueError(range_msg)
-        return result.numpy()
+        return (result.numpy(), errors.cpu().numpy()) if return_error else result.numpy()
