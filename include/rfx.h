@@ -163,6 +163,23 @@ typedef struct {
   char imel_why[96];
 } rfx_plan_bank_report;
 int rfx_debug_plan_bank(const rfx_params* params, const float* h_melfb, const rfx_plan_options* options, rfx_plan_bank_report* report);
+/* Whether the closed-form InverseMelScale (rfx_inverse_mel_lstsq below) serves this filterbank, and the factor tables its kernels
+ * read, without a plan or a GPU (tests): the same host code fills the plan's tables.  Set report->struct_size =
+ * sizeof(rfx_lstsq_bank_report) and the two table pointers (NULL, or n_mels floats each on the host; written when ok).
+ * Not ok, with the reason in `why`: the bank is not banded (a bin feeds more than two filters, or two that are not adjacent), or a
+ * pivot of the L D L^T factorisation of fb^T fb (double) is <= 2^-20 times its diagonal entry - singular or nearly so, e.g. an
+ * all-zero filter or the reference's bank at num_frequencies = 1024. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t ok;
+  double min_pivot_ratio;  /* smallest pivot / diagonal entry seen, up to and including a refused pivot */
+  int32_t min_pivot;       /* its index (-1: the bank is not banded, nothing was factored) */
+  int32_t reserved;
+  float* h_neg_l;          /* out, optional: -L[m + 1][m] for m = 0 .. n_mels - 2, then 0 */
+  float* h_inv_d;          /* out, optional: 1 / D[m] */
+  char why[160];
+} rfx_lstsq_bank_report;
+int rfx_debug_lstsq_bank(const rfx_params* params, const float* h_melfb, rfx_lstsq_bank_report* report);
 /* frames torch.stft(center=True, pad_mode="reflect") makes of Lw samples: 1 + (Lw + 2*(n_fft/2) - n_fft) / hop, i.e.
  * 1 + Lw/hop for even n_fft and 1 + (Lw-1)/hop for odd n_fft; 0 when Lw <= n_fft/2 (the reference raises there).
  * Every forward entry point below produces exactly this many frames. */
@@ -200,9 +217,12 @@ int rfx_stft_frames(const rfx_plan* plan, int Lw);
  * their U[0,1) start whatever max_value is (reproduced), and below |a| = 1e-8 in the input's units the `+ 1e-16` guard becomes
  * visible: there this library's guard, rsq(|a|^2 + 1e-32), differs from the reference's 1 / (|a| + 1e-16) by up to 41 %
  * (at |a| = 1e-16) in the LENGTH of the phase factor - never in its direction, and it is exactly 0 for a = 0 in both. */
+/* rfx_call_options.flags.  RFX_CALL_INVERSE_MEL_LSTSQ: the fused calls rfx_waveform_from_mel_ex and rfx_audio_from_image_u8_ex run
+ * rfx_inverse_mel_lstsq in place of the SGD.  rfx_inverse_mel_ex and rfx_griffinlim_ex refuse any non-zero flag. */
+#define RFX_CALL_INVERSE_MEL_LSTSQ 1u
 typedef struct {
   uint32_t struct_size;
-  uint32_t flags;           /* must be 0 */
+  uint32_t flags;           /* 0 or RFX_CALL_* bits */
   uint64_t row_base;
   float magnitude_hint;
   float reserved;           /* must be 0 */
@@ -341,6 +361,28 @@ int rfx_inverse_mel_ex(const rfx_plan* plan, const float* d_mel, int B, int T, i
                        uint64_t seed, float* d_mag_slots, void* d_workspace, size_t workspace_bytes, void* stream,
                        const rfx_call_options* options);
 
+/* ---- inverse, closed form: torchaudio >= 2.1's InverseMelScale, relu(torch.linalg.lstsq(fb.T[None], mel, driver="gels").solution)
+ * - the minimum-norm least-squares solution, clamped at zero.  Opt-in: rfx_inverse_mel above stays the default.
+ * For a bank whose bins feed at most two adjacent filters G = fb^T fb is symmetric tridiagonal and the answer is
+ * x = relu(fb G^-1 mel): per frame one n_mels-unknown tridiagonal solve (L D L^T factored in double at plan creation, the two
+ * sweeps in float32, one fmaf per step in a fixed order) and a two-tap expansion, max(0, fmaf(w1, y[m0 + 1], w0 * y[m0])).
+ * rfx_plan_lstsq_ok: 1 when the plan's bank admits it (rfx_debug_lstsq_bank says why not, without a GPU); on any other plan the
+ * entry returns RFX_ERR_INVALID with that reason.
+ * d_mel (B, n_mels, T) -> d_mag_slots: linear magnitudes in slot layout, ready for rfx_griffinlim, every position of every frame
+ * written: padding positions and the bins no filter reaches are exactly 0.0 (the minimum-norm answer), both copies of a bin the
+ * specialised layout stores twice are equal.  No seed, no channels_per_clip, no start: a frame's result is a function of that
+ * frame's mel column and the plan alone - not of B, the row, the batch it travels in or the launch grid.
+ * What differs from the SGD by construction: the bins outside the bank are zeros where the SGD leaves its U[0,1) start, and
+ * nothing couples a clip's channels and frames (the SGD's stopping rule reads a loss mean over the whole clip).
+ * Held against torch's float64 lstsq at no more than twice the distance of torch's own float32 "gels" (measured: 6e-8 against
+ * 1.4e-7 relative L2).  Scale: every step is linear, so an input times 2^n gives the output times 2^n bit for bit while no
+ * intermediate leaves float32's normal range - magnitudes between about 1e-30 and 1e30 for the reference's banks.
+ * d_mag_slots must be 16-byte aligned.  Row and element offsets are 64-bit.  Workspace: B * n_mels * T floats. */
+int rfx_plan_lstsq_ok(const rfx_plan* plan);
+size_t rfx_inverse_mel_lstsq_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_inverse_mel_lstsq(const rfx_plan* plan, const float* d_mel, int B, int T, float* d_mag_slots, void* d_workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- inverse, in one call: SpectrogramConverter.waveform_from_mel_amplitudes, spectrogram_converter.py:187-204
  * (`self.inverse_mel_scaler(amplitudes_mel)` :201 then `self.inverse_spectrogram_func(amplitudes_linear)` :204).
  * d_mel (B, n_mels, T) -> d_wave_out (B, rfx_griffinlim_output_samples(plan, T)); clips of `channels_per_clip` rows as in
@@ -350,6 +392,10 @@ size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T)
 int rfx_waveform_from_mel(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                           float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* With RFX_CALL_INVERSE_MEL_LSTSQ in options->flags: exactly rfx_inverse_mel_lstsq followed by rfx_griffinlim_ex with the same
+ * options - same bits; the phases still come from seed + 1 and row_base, the Griffin-Lim range from magnitude_hint or the linear
+ * magnitudes.  A plan that is not rfx_plan_lstsq_ok is refused (RFX_ERR_INVALID, with the reason) before anything is launched.
+ * rfx_audio_from_image_u8_ex reads the flag in the same way.  The workspace queries cover both forms. */
 int rfx_waveform_from_mel_ex(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                              float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream,
                              const rfx_call_options* options);

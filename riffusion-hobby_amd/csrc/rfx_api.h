@@ -78,6 +78,10 @@ struct rfx_plan {
   std::string imel_why;
   rfx::ImelTables imel{};
   void* d_imel_blob = nullptr;
+  // closed-form InverseMelScale (rfx_imel_lstsq.hip): the factor tables of fb^T fb, uploaded when the bank admits them
+  bool lstsq_ok = false;
+  std::string lstsq_why;
+  rfx::LsqTables lstsq{};
   // fused forward path (banded mel projection inside the STFT kernel), valid when fwd_ok
   bool fwd_ok = false;
   float* d_band_wt = nullptr;      // [band_rows][Mpad]

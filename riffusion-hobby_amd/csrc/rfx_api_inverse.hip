@@ -1,5 +1,7 @@
 // rfx_api_inverse.hip - the C ABI of librfx.so (include/rfx.h), inverse half: Griffin-Lim on the three frame engines,
 // InverseMelScale, and the fused calls made of them.  Host code only: the drivers that sequence the kernels.
+#include <algorithm>
+
 #include "rfx_api.h"
 
 using namespace rfx;
@@ -193,13 +195,18 @@ size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) {
 struct CallOpt {
   uint64_t row_base = 0;
   float magnitude_hint = 0.f;
+  bool lstsq = false;  // RFX_CALL_INVERSE_MEL_LSTSQ (the fused calls)
 };
-static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who) {
+// allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves)
+static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who, uint32_t allowed_flags = 0) {
   *out = CallOpt{};
   if (!o) return RFX_OK;
   if (o->struct_size < offsetof(rfx_call_options, row_base) + sizeof(uint64_t))
     return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.struct_size is not set");
-  if (o->flags != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.flags must be 0");
+  if (o->flags & ~allowed_flags)
+    return fail(RFX_ERR_INVALID, std::string(who) + (allowed_flags ? ": rfx_call_options.flags has a bit this entry point does not know"
+                                                                   : ": rfx_call_options.flags must be 0"));
+  out->lstsq = (o->flags & RFX_CALL_INVERSE_MEL_LSTSQ) != 0;
   out->row_base = o->row_base;
   if (o->struct_size >= offsetof(rfx_call_options, magnitude_hint) + sizeof(float)) out->magnitude_hint = o->magnitude_hint;
   if (!(out->magnitude_hint >= 0.f) || out->magnitude_hint > 3.0e38f)
@@ -524,6 +531,44 @@ int rfx_inverse_mel_ex(const rfx_plan* plan, const float* d_mel, int B, int T, i
   return inverse_mel_impl(plan, d_mel, B, T, channels_per_clip, d_spec0, seed, d_mag_slots, d_workspace, workspace_bytes, stream_, false, opt);
 }
 
+// ---- InverseMelScale, closed form (rfx_imel_lstsq.hip): the tridiagonal solve into the workspace, then the expansion -----------------
+struct LstsqLayout {
+  size_t zy, total;  // (B, n_mels, T) floats: the forward sweep's z, then y in place
+};
+static LstsqLayout inverse_mel_lstsq_layout(const rfx_plan* plan, int B, int T) {
+  LstsqLayout l{};
+  if (!plan->lstsq_ok || B <= 0 || T <= 0) return l;
+  Carve c;
+  l.zy = c.take((size_t)B * plan->p.n_mels * T * sizeof(float));
+  l.total = c.at;
+  return l;
+}
+size_t rfx_inverse_mel_lstsq_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? inverse_mel_lstsq_layout(plan, B, T).total : 0; }
+
+// what every entry that takes the closed form checks before it launches anything
+static int lstsq_refusal(const rfx_plan* plan, const char* who) {
+  if (plan->lstsq_ok) return RFX_OK;
+  return fail(RFX_ERR_INVALID, std::string(who) + ": the closed-form InverseMelScale does not serve this plan: " + plan->lstsq_why);
+}
+
+int rfx_inverse_mel_lstsq(const rfx_plan* plan, const float* d_mel, int B, int T, float* d_mag_slots, void* d_workspace,
+                          size_t workspace_bytes, void* stream_) {
+  if (!plan || !d_mel || !d_mag_slots || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_inverse_mel_lstsq: null argument");
+  if (int rc = lstsq_refusal(plan, "rfx_inverse_mel_lstsq")) return rc;
+  if (B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_inverse_mel_lstsq: bad shape");
+  if ((long long)B * T > 0x7fffffffLL) return fail(RFX_ERR_INVALID, "rfx_inverse_mel_lstsq: more than 2^31 - 1 frames in one call");
+  if (((uintptr_t)d_mag_slots & 15) || (plan->frame_stride & 3))
+    return fail(RFX_ERR_INVALID, "rfx_inverse_mel_lstsq: d_mag_slots must be 16-byte aligned");
+  const LstsqLayout w = inverse_mel_lstsq_layout(plan, B, T);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_inverse_mel_lstsq: workspace too small");
+  RFX_ON_DEVICE(plan->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  float* zy = (float*)((char*)d_workspace + w.zy);
+  RFX_HIP(launch_lsq_solve(plan->lstsq, d_mel, zy, B, plan->p.n_mels, T, stream));
+  RFX_HIP(launch_lsq_expand(plan->lstsq, zy, d_mag_slots, B, plan->p.n_mels, T, plan->frame_stride, stream));
+  return RFX_OK;
+}
+
 // ---- SpectrogramConverter.waveform_from_mel_amplitudes in one call (spectrogram_converter.py:187-204: inverse_mel_scaler, then
 // inverse_spectrogram_func).  rfx_inverse_mel into the head of the workspace, rfx_griffinlim from there: the same two launches
 // sequences, the same seeds (seed for the SGD start, seed + 1 for the phases, as the Python layer always called them), the linear
@@ -540,12 +585,15 @@ static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, i
   WaveFromMelLayout l{};
   const size_t imel = rfx_inverse_mel_workspace_bytes(plan, B, T), gl = rfx_griffinlim_workspace_bytes(plan, B, T);
   if (!imel || !gl) return l;
+  const size_t lstsq = inverse_mel_lstsq_layout(plan, B, T).total;
   l.fam_slots = imel_can_emit_fam_slots(plan);
+  // one layout for both forms of InverseMelScale: the closed form writes plain frames also on a row-family plan
+  const size_t per_frame = l.fam_slots && plan->fam.fsf > plan->frame_stride ? (size_t)plan->fam.fsf : (size_t)plan->frame_stride;
   Carve c;
-  l.lin = c.take((size_t)B * T * (l.fam_slots ? (size_t)plan->fam.fsf : (size_t)plan->frame_stride) * sizeof(float));
+  l.lin = c.take((size_t)B * T * per_frame * sizeof(float));
   l.row_scale = c.take(range_table_bytes(B));
   l.rest = c.at;
-  l.total = l.rest + (imel > gl ? imel : gl);
+  l.total = l.rest + std::max(std::max(imel, gl), lstsq);
   return l;
 }
 size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T).total : 0; }
@@ -553,12 +601,18 @@ size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T)
 static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                                  float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream, const CallOpt& opt) {
   if (!plan || !d_mel || !d_wave_out || !d_workspace || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_waveform_from_mel: bad argument");
+  if (opt.lstsq)
+    if (int rc = lstsq_refusal(plan, "rfx_waveform_from_mel")) return rc;
   const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T);
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_waveform_from_mel: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
   char* ws = (char*)d_workspace;
   float* lin = reinterpret_cast<float*>(ws + w.lin);
   float* row_scale = reinterpret_cast<float*>(ws + w.row_scale);
+  if (opt.lstsq) {  // rfx_inverse_mel_lstsq, then rfx_griffinlim_ex: plain frames, the rows' range from the hint or the magnitudes
+    if (int rc = rfx_inverse_mel_lstsq(plan, d_mel, B, T, lin, ws + w.rest, workspace_bytes - w.rest, stream)) return rc;
+    return griffinlim_impl(plan, lin, nullptr, seed + 1, B, T, n_iter, momentum, d_wave_out, ws + w.rest, workspace_bytes - w.rest, stream, nullptr, opt);
+  }
   if (int rc = inverse_mel_impl(plan, d_mel, B, T, channels_per_clip, nullptr, seed, lin, ws + w.rest, workspace_bytes - w.rest, stream, w.fam_slots, opt, row_scale)) return rc;
   return griffinlim_impl(plan, lin, nullptr, seed + 1, B, T, n_iter, momentum, d_wave_out, ws + w.rest, workspace_bytes - w.rest, stream, nullptr, opt, w.fam_slots, row_scale);
 }
@@ -572,7 +626,7 @@ int rfx_waveform_from_mel_ex(const rfx_plan* plan, const float* d_mel, int B, in
                              float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream,
                              const rfx_call_options* options) {
   CallOpt opt;
-  if (int rc = read_call_options(options, &opt, "rfx_waveform_from_mel_ex")) return rc;
+  if (int rc = read_call_options(options, &opt, "rfx_waveform_from_mel_ex", RFX_CALL_INVERSE_MEL_LSTSQ)) return rc;
   return waveform_from_mel_impl(plan, d_mel, B, T, channels_per_clip, seed, n_iter, momentum, d_wave_out, d_workspace, workspace_bytes, stream, opt);
 }
 
@@ -606,6 +660,8 @@ static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int
                                 size_t workspace_bytes, void* stream, const CallOpt& opt) {
   if (!plan || !d_img || !d_lut256 || !d_clip_peak || !d_pcm_out || !d_workspace || N <= 0 || T <= 0)
     return fail(RFX_ERR_INVALID, "rfx_audio_from_image_u8: bad argument");
+  if (opt.lstsq)
+    if (int rc = lstsq_refusal(plan, "rfx_audio_from_image_u8")) return rc;
   const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T);
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_audio_from_image_u8: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
@@ -630,7 +686,7 @@ int rfx_audio_from_image_u8_ex(const rfx_plan* plan, const uint8_t* d_img, int N
                                int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
                                size_t workspace_bytes, void* stream, const rfx_call_options* options) {
   CallOpt opt;
-  if (int rc = read_call_options(options, &opt, "rfx_audio_from_image_u8_ex")) return rc;
+  if (int rc = read_call_options(options, &opt, "rfx_audio_from_image_u8_ex", RFX_CALL_INVERSE_MEL_LSTSQ)) return rc;
   return audio_from_image_impl(plan, d_img, N, T, stereo, d_lut256, seed, n_iter, momentum, normalize, d_clip_peak, d_pcm_out, d_workspace,
                                workspace_bytes, stream, opt);
 }

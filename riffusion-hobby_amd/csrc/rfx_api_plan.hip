@@ -253,8 +253,50 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
       pl->imel.grp_start = (const int*)(d + o_gs);
       pl->imel.lin = (const float*)(d + o_lin);
     }
+    // closed-form InverseMelScale: the factor tables, only for a bank that admits them (rfx_plan_lstsq_ok)
+    const LstsqBank lsq = bank_lstsq(bank);
+    pl->lstsq_ok = lsq.ok;
+    pl->lstsq_why = lsq.why;
+    if (lsq.ok) {
+      float *d_nl, *d_inv_d, *d_w0, *d_w1;
+      int* d_m0;
+      RFX_HIP(upload(pl.get(), &d_nl, lsq.nl));
+      RFX_HIP(upload(pl.get(), &d_inv_d, lsq.inv_d));
+      RFX_HIP(upload(pl.get(), &d_m0, lsq.pos_m0));
+      RFX_HIP(upload(pl.get(), &d_w0, lsq.pos_w0));
+      RFX_HIP(upload(pl.get(), &d_w1, lsq.pos_w1));
+      pl->lstsq = LsqTables{d_nl, d_inv_d, d_m0, d_w0, d_w1};
+    }
+  } else {
+    pl->lstsq_why = "plan was created without a mel filterbank";
   }
   *out_plan = pl.release();
+  return RFX_OK;
+}
+
+int rfx_plan_lstsq_ok(const rfx_plan* plan) { return plan && plan->lstsq_ok ? 1 : 0; }
+
+int rfx_debug_lstsq_bank(const rfx_params* params, const float* h_melfb, rfx_lstsq_bank_report* report) {
+  if (!params || !h_melfb || !report) return fail(RFX_ERR_INVALID, "rfx_debug_lstsq_bank: null argument");
+  if (report->struct_size < 2 * sizeof(uint32_t) || report->struct_size > sizeof(rfx_lstsq_bank_report))
+    return fail(RFX_ERR_INVALID, "rfx_debug_lstsq_bank: report->struct_size does not describe an rfx_lstsq_bank_report this library knows");
+  if (params->n_mels <= 0) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be positive");
+  rfx_plan_options opt;
+  if (const int rc = resolve_options(nullptr, &opt)) return rc;
+  const PlanOverrides ov = plan_overrides();
+  PlanGeometry geo;
+  std::string err;
+  if (const int rc = plan_geometry(*params, opt, ov, &geo, &err)) return fail(rc, err);
+  const LstsqBank lsq = bank_lstsq(plan_bank(geo, params->n_mels, h_melfb, opt, ov));
+  rfx_lstsq_bank_report r{};
+  memcpy(&r, report, report->struct_size);  // (the caller's table pointers)
+  r.ok = lsq.ok;
+  r.min_pivot = lsq.min_pivot;
+  r.min_pivot_ratio = lsq.min_pivot_ratio;
+  snprintf(r.why, sizeof(r.why), "%s", lsq.why.c_str());
+  if (lsq.ok && r.h_neg_l) memcpy(r.h_neg_l, lsq.nl.data(), lsq.nl.size() * sizeof(float));
+  if (lsq.ok && r.h_inv_d) memcpy(r.h_inv_d, lsq.inv_d.data(), lsq.inv_d.size() * sizeof(float));
+  memcpy(report, &r, r.struct_size);
   return RFX_OK;
 }
 

@@ -435,4 +435,19 @@ size_t qual_partials_bytes(int rows, int T);
 hipError_t launch_spectral_sums(const float* a, const float* m, int rows, int T, int fs, int n_stft, bool plain, void* partials, double* sums,
                                 hipStream_t s);
 
+// closed-form InverseMelScale (rfx_imel_lstsq.hip, arithmetic in rfx_imel_lstsq_core.h).  The plan's tables: the float32
+// L D L^T factors of fb^T fb - nl[m] = -L[m + 1][m] (nl[M - 1] = 0), inv_d[m] = 1 / D[m] - and, for every position of an output
+// frame, its bin's first filter and two weights (a position that holds no bin, or a bin no filter reaches: M, 0, 0).
+struct LsqTables {
+  const float* nl;      // [M]
+  const float* inv_d;   // [M]
+  const int* pos_m0;    // [frame stride]
+  const float* pos_w0;  // [frame stride]
+  const float* pos_w1;  // [frame stride]
+};
+// mel (B, M, T) -> zy (B, M, T): y = G^-1 mel, one lane per frame (the forward sweep's z is held in zy on the way)
+hipError_t launch_lsq_solve(const LsqTables& tb, const float* mel, float* zy, int B, int M, int T, hipStream_t s);
+// y (B, M, T) -> out [B * T][stride] (stride a multiple of four, out 16-byte aligned): max(0, w0 y[m0] + w1 y[m0 + 1]) per position
+hipError_t launch_lsq_expand(const LsqTables& tb, const float* y, float* out, int B, int M, int T, int stride, hipStream_t s);
+
 }  // namespace rfx

@@ -4,6 +4,7 @@
 // rfx_debug_plan_bank runs the same functions without a GPU (tests/test_plan_selection.py).
 #pragma once
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <string>
@@ -518,6 +519,80 @@ inline void bank_forward_products(PlanBank& b, const float* fb, bool table_form)
     pkseg[2 * m] = (unsigned)b.seg[m];
     pkseg[2 * m + 1] = (unsigned)b.seg[(size_t)Mpad + m];
   }
+}
+
+// ---- closed-form InverseMelScale (rfx_imel_lstsq.hip): the factor tables of G = fb^T fb -----------------------------------------
+// In a banded bank every bin touches at most two ADJACENT filters, so G is symmetric tridiagonal: diagonal d[m] = sum w(f, m)^2,
+// off-diagonal e[m] = sum w(f, m) w(f, m + 1), both in double from the float32 weights.  G = L D L^T with L unit lower bidiagonal:
+// D[0] = d[0], l[m] = e[m] / D[m], D[m + 1] = d[m + 1] - l[m] e[m].  The kernels read nl[m] = -l[m] (nl[M - 1] = 0) and
+// inv_d[m] = 1 / D[m], rounded once to float32.  A pivot D[m] <= 2^-20 d[m] refuses the bank: G is singular or nearly so (an
+// empty filter, or filters that cannot be told apart on this bin grid), which torch.linalg.lstsq's "gels" does not support either.
+constexpr double kLsqPivotFloor = 1.0 / 1048576.0;  // 2^-20
+struct LstsqBank {
+  bool ok = false;
+  std::string why;
+  double min_pivot_ratio = 0.0;  // smallest D[m] / d[m] seen (up to and including a refused pivot); 0 when no factorisation was tried
+  int min_pivot = -1;            // its index
+  std::vector<float> nl, inv_d;  // [M]
+  // per position of an output frame (PlanBank::pos_bin order): first filter and weights of the bin it holds; a position without
+  // a bin and a bin without a filter point at the zero the kernel keeps behind y: (M, 0, 0)
+  std::vector<int> pos_m0;
+  std::vector<float> pos_w0, pos_w1;
+};
+inline LstsqBank bank_lstsq(const PlanBank& b) {
+  LstsqBank q;
+  const int F = b.F, M = b.M;
+  if (!b.ok) {
+    q.why = "the filterbank is not banded: " + b.why;
+    return q;
+  }
+  std::vector<double> d(M, 0.0), e(M, 0.0);
+  for (int f = 0; f < F; ++f) {
+    const int m = b.bin_m0[f];
+    if (m < 0) continue;
+    const double w0 = b.bin_w0[f], w1 = b.bin_w1[f];
+    d[m] += w0 * w0;
+    if (m + 1 < M) {
+      d[m + 1] += w1 * w1;
+      e[m] += w0 * w1;
+    }
+  }
+  q.nl.assign(M, 0.f);
+  q.inv_d.assign(M, 0.f);
+  q.min_pivot_ratio = INFINITY;
+  double D = d[0];
+  for (int m = 0; m < M; ++m) {
+    const double ratio = d[m] > 0.0 ? D / d[m] : 0.0;
+    if (ratio < q.min_pivot_ratio) { q.min_pivot_ratio = ratio; q.min_pivot = m; }
+    if (!(D > kLsqPivotFloor * d[m])) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "pivot %d of the LDL^T factorisation of fb^T fb is %.3g times its diagonal entry %.3g: singular or nearly so",
+               m, ratio, d[m]);
+      q.why = msg;
+      q.nl.clear();
+      q.inv_d.clear();
+      return q;
+    }
+    q.inv_d[m] = (float)(1.0 / D);
+    if (m + 1 < M) {
+      const double l = e[m] / D;
+      q.nl[m] = (float)(-l);
+      D = d[m + 1] - l * e[m];
+    }
+  }
+  const size_t P = b.pos_bin.size();
+  q.pos_m0.assign(P, M);
+  q.pos_w0.assign(P, 0.f);
+  q.pos_w1.assign(P, 0.f);
+  for (size_t p = 0; p < P; ++p) {
+    const int f = b.pos_bin[p];
+    if (f < 0 || b.bin_m0[f] < 0) continue;
+    q.pos_m0[p] = b.bin_m0[f];
+    q.pos_w0[p] = b.bin_w0[f];
+    q.pos_w1[p] = b.bin_w1[f];
+  }
+  q.ok = true;
+  return q;
 }
 
 // everything plan creation derives from a dense filterbank fb [n_stft][n_mels] (n_mels > 0)

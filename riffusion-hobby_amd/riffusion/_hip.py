@@ -88,10 +88,41 @@ class RfxCallOptions(ctypes.Structure):
                 ("magnitude_hint", ctypes.c_float), ("reserved", ctypes.c_float)]
 
 
-def call_options(row_base: int = 0, magnitude_hint: float = 0.0) -> RfxCallOptions:
+CALL_INVERSE_MEL_LSTSQ = 1  # RFX_CALL_INVERSE_MEL_LSTSQ
+INVERSE_MEL_FORMS = ("sgd", "lstsq")  # the `inverse_mel` keyword of the converters
+
+
+def call_options(row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False) -> RfxCallOptions:
+    """`lstsq`: the fused inverse calls run the closed-form InverseMelScale (rfx_inverse_mel_lstsq) in place of the SGD."""
     if row_base < 0:
         raise ValueError("row_base must be >= 0")
-    return RfxCallOptions(ctypes.sizeof(RfxCallOptions), 0, int(row_base), float(magnitude_hint), 0.0)
+    return RfxCallOptions(ctypes.sizeof(RfxCallOptions), CALL_INVERSE_MEL_LSTSQ if lstsq else 0, int(row_base), float(magnitude_hint), 0.0)
+
+
+def check_inverse_mel(inverse_mel: str) -> bool:
+    """True for "lstsq", False for "sgd"; anything else raises."""
+    if inverse_mel not in INVERSE_MEL_FORMS:
+        raise ValueError(f"inverse_mel must be one of {list(INVERSE_MEL_FORMS)}, got {inverse_mel!r}")
+    return inverse_mel == "lstsq"
+
+
+class RfxLstsqBankReport(ctypes.Structure):
+    """rfx_lstsq_bank_report of include/rfx.h: whether the closed-form InverseMelScale serves a filterbank, and its factor tables."""
+
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ok", ctypes.c_int32), ("min_pivot_ratio", ctypes.c_double), ("min_pivot", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("h_neg_l", ctypes.c_void_p), ("h_inv_d", ctypes.c_void_p), ("why", ctypes.c_char * 160)]
+
+
+def lstsq_bank_report(cp: RfxParams, melfb: torch.Tensor, tables: bool = False):
+    """rfx_debug_lstsq_bank (host only, no GPU) for the (n_stft, n_mels) float32 filterbank `melfb`: the report and, with
+    `tables`, the two float32 factor tables (None when the bank is refused)."""
+    melfb = melfb.to(torch.float32).contiguous()
+    report = RfxLstsqBankReport(struct_size=ctypes.sizeof(RfxLstsqBankReport))
+    neg_l, inv_d = np.zeros(cp.n_mels, np.float32), np.zeros(cp.n_mels, np.float32)
+    if tables:
+        report.h_neg_l, report.h_inv_d = neg_l.ctypes.data, inv_d.ctypes.data
+    check(load_library().rfx_debug_lstsq_bank(ctypes.byref(cp), melfb.data_ptr(), ctypes.byref(report)))
+    return (report, (neg_l, inv_d) if report.ok else None) if tables else report
 
 
 GL_FORMS = {"auto": 0, "runs": 1, "frames": 2}  # rfx_gl_form
@@ -123,6 +154,10 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_debug_gl_partition": (c_int, [c_int, c_int, c_int, c_void_p, c_int]),
     "rfx_debug_range_exponents": (c_int, [c_float, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "rfx_debug_plan_bank": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, ctypes.POINTER(RfxPlanBankReport)]),
+    "rfx_debug_lstsq_bank": (c_int, [ctypes.POINTER(RfxParams), c_void_p, ctypes.POINTER(RfxLstsqBankReport)]),
+    "rfx_plan_lstsq_ok": (c_int, [c_void_p]),
+    "rfx_inverse_mel_lstsq_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_inverse_mel_lstsq": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_stft_frames": (c_int, [c_void_p, c_int]),
     "rfx_plan_imel_kernel": (c_int, [c_void_p]),
     "rfx_plan_imel_unit_form": (c_int, [c_void_p]),
@@ -435,6 +470,8 @@ class Plan:
         self.frame_stride = self.lib.rfx_plan_frame_stride(self.handle)
         self.generic = bool(self.lib.rfx_plan_is_generic(self.handle))
         self.griffinlim_engine = GL_ENGINE_NAMES[self.lib.rfx_plan_griffinlim_engine(self.handle)]
+        self._cparams = cp
+        self.lstsq_ok = bool(self.lib.rfx_plan_lstsq_ok(self.handle))
         self.arena = WorkspaceArena(device, max_idle=max(1, int(os.environ.get("RFX_ARENA_IDLE", "4"))))
         self._consts: "collections.OrderedDict[T.Any, torch.Tensor]" = collections.OrderedDict()
         self._consts_lock = threading.Lock()
@@ -682,6 +719,26 @@ class Plan:
             )
         return out
 
+    def require_lstsq(self) -> None:
+        """Raises ValueError with the library's reason when the closed-form InverseMelScale does not serve this plan's bank
+        (host only: nothing is queued on the GPU)."""
+        if not self.lstsq_ok:
+            why = lstsq_bank_report(self._cparams, self.melfb).why.decode()
+            raise ValueError(f'inverse_mel="lstsq" does not serve this filterbank: {why}')
+
+    def inverse_mel_lstsq(self, mel: torch.Tensor) -> torch.Tensor:
+        """InverseMelScale, closed form (torchaudio >= 2.1: relu of the minimum-norm least-squares solution): (B, n_mels, T) ->
+        linear magnitudes in slot layout (B*T, stride).  No seed: a frame's result depends on its mel column and the plan alone."""
+        self.require_lstsq()
+        mel = self._chk(mel, torch.float32)
+        B, M, Tn = mel.shape
+        if M != self.n_mels:
+            raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")  # torchaudio's message
+        out = torch.empty((B * Tn, self.frame_stride), dtype=torch.float32, device=mel.device)
+        with self._workspace(max(1, self.lib.rfx_inverse_mel_lstsq_workspace_bytes(self.handle, B, Tn))) as ws:
+            check(self.lib.rfx_inverse_mel_lstsq(self.handle, mel.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
     # ---- codecs (no plan state needed, kept here for one binding site) -------------------------
     def image_decode(self, img_u8: torch.Tensor, stereo: bool, lut: torch.Tensor) -> torch.Tensor:
         """(N, H, W, 3) uint8 -> (N*C, H, W) float32."""
@@ -739,15 +796,17 @@ class Plan:
         return out
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
-                          row_base: int = 0, magnitude_hint: float = 0.0) -> torch.Tensor:
+                          row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False) -> torch.Tensor:
         """spectrogram_converter.py:187-204 in one call: (B, n_mels, T) -> (B, hop * (T - 1)); `inverse_mel` (seed) + `griffinlim`
-        (seed + 1), same bits, the linear magnitudes stay in the workspace."""
+        (seed + 1), same bits, the linear magnitudes stay in the workspace.  `lstsq`: `inverse_mel_lstsq` in place of the SGD."""
+        if lstsq:
+            self.require_lstsq()
         mel = self._chk(mel, torch.float32)
         B, M, Tn = mel.shape
         if M != self.n_mels:
             raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")  # torchaudio's message
         out = torch.empty((B, self.lib.rfx_griffinlim_output_samples(self.handle, Tn)), dtype=torch.float32, device=mel.device)
-        opt = call_options(row_base, magnitude_hint)
+        opt = call_options(row_base, magnitude_hint, lstsq)
         with self._workspace(self.lib.rfx_waveform_from_mel_workspace_bytes(self.handle, B, Tn)) as ws:
             check(self.lib.rfx_waveform_from_mel_ex(self.handle, mel.data_ptr(), B, Tn, channels_per_clip, seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
@@ -760,13 +819,15 @@ class Plan:
 
     def audio_from_image(self, img: torch.Tensor, stereo: bool, lut: torch.Tensor, n_iter: int, momentum: float = 0.99, seed: int = 0,
                          normalize: bool = True, out: T.Optional[torch.Tensor] = None, workspace: T.Optional[torch.Tensor] = None,
-                         clip_base: int = 0, magnitude_hint: float = 0.0):
+                         clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False):
         """spectrogram_image_converter.py:54-91 on the device in one call: (N, n_mels, T, 3) uint8 -> ((N, L, C) int16, per-clip peak (N,));
         `image_decode` + `waveform_from_mel` (clips of C rows) + `pcm16`, same bytes.  `out` as in `pcm16`.  `clip_base`: index of
         the call's first image in the caller's whole batch (row_base = clip_base * C); `magnitude_hint`: the image path's
-        max_value (the largest entry of `lut`)."""
+        max_value (the largest entry of `lut`); `lstsq`: the closed-form InverseMelScale in place of the SGD."""
         if img.dtype != torch.uint8 or img.dim() != 4:
             raise ValueError("expected (N, H, W, 3) uint8 images")
+        if lstsq:
+            self.require_lstsq()
         img = self._chk(img)
         lut = self._chk(lut, torch.float32)
         N, H, W, ch = img.shape
@@ -785,9 +846,9 @@ class Plan:
         if ws is None or ws.numel() < need:
             with self._workspace(need) as borrowed:
                 return self.audio_from_image(img, stereo, lut, n_iter, momentum, seed, normalize, out=pcm, workspace=borrowed,
-                                             clip_base=clip_base, magnitude_hint=magnitude_hint)
+                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq)
         peak = torch.zeros((N,), dtype=torch.float32, device=img.device)
-        opt = call_options(clip_base * C, magnitude_hint)
+        opt = call_options(clip_base * C, magnitude_hint, lstsq)
         check(self.lib.rfx_audio_from_image_u8_ex(self.handle, img.data_ptr(), N, W, int(stereo), lut.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                   int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return pcm, peak

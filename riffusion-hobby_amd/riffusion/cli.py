@@ -61,11 +61,12 @@ def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_freque
     print(f"Wrote {image}")
 
 
-def image_to_audio(*, image: str, audio: str, device: str = "cuda") -> None:
+def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd") -> None:
+    """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD."""
     pil_image = Image.open(image)
     params = _params_from_image(pil_image)
     converter = SpectrogramImageConverter(params=params, device=device)
-    segment = converter.audio_from_spectrogram_image(pil_image, apply_filters=True)
+    segment = converter.audio_from_spectrogram_image(pil_image, apply_filters=True, inverse_mel=inverse_mel)
     segment.export(audio, format=os.path.splitext(audio)[1][1:] or "wav")
     print(f"Wrote {audio} ({segment.duration_seconds:.2f} seconds)")
 
@@ -98,11 +99,11 @@ def _rank_device(device: str) -> str:
 
 
 def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 64, no_filters: bool = False,
-                          compression: bool = False, device: str = "cuda") -> None:
+                          compression: bool = False, device: str = "cuda", inverse_mel: str = "sgd") -> None:
     """Decode every *.png of a directory, `batch_size` same-width tiles per GPU call.  Each clip then gets the same
     post-processing as `image-to-audio` (audio_util.apply_filters, reference spectrogram_image_converter.py:65-91, run on the
     device) unless --no-filters is given; --compression adds the filters' dynamic range compression (apply_filters with
-    compression=True, also on the device)."""
+    compression=True, also on the device); --inverse-mel lstsq takes the closed-form InverseMelScale instead of the SGD."""
     if compression and no_filters:
         raise ValueError("--compression is a mode of the filters: it does not go with --no-filters")
     os.makedirs(output_dir, exist_ok=True)
@@ -121,7 +122,8 @@ def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 
                 with Image.open(p) as im:
                     tiles.append(image_util.rgb_array_from_image(im))
             # the filters run on the device, clip by clip, before the batch leaves it (same bytes as audio_util.apply_filters)
-            pcm = converter.audio_from_spectrogram_images(np.stack(tiles), apply_filters=not no_filters, compression=compression)
+            pcm = converter.audio_from_spectrogram_images(np.stack(tiles), apply_filters=not no_filters, compression=compression,
+                                                          inverse_mel=inverse_mel)
             for path, samples in zip(chunk, pcm):
                 segment = audio_util.PcmSegment(samples, params.sample_rate)
                 out = os.path.join(output_dir, os.path.splitext(os.path.basename(path))[0] + ".wav")
@@ -230,6 +232,9 @@ _COMMANDS: T.Dict[str, T.Callable[..., None]] = {
 }
 
 
+_CHOICES = {"inverse_mel": ("sgd", "lstsq")}  # arguments that take one of a few words
+
+
 def build_parser() -> argparse.ArgumentParser:
     import inspect
 
@@ -244,7 +249,7 @@ def build_parser() -> argparse.ArgumentParser:
             elif isinstance(spec.default, bool):
                 sp.add_argument(flag, action="store_true", default=spec.default)
             else:
-                sp.add_argument(flag, type=type(spec.default), default=spec.default)
+                sp.add_argument(flag, type=type(spec.default), default=spec.default, choices=_CHOICES.get(arg))
     return parser
 
 

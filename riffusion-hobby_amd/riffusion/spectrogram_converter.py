@@ -158,6 +158,7 @@ class SpectrogramConverter:
         angles0: T.Optional[torch.Tensor] = None,
         seed: T.Optional[int] = None,
         channels_per_clip: T.Optional[int] = None,
+        inverse_mel: str = "sgd",
     ) -> torch.Tensor:
         """
         (B, n_mels, T) -> (B, hop*(T-1)).  The reference treats the whole batch as ONE clip (the SGD
@@ -165,26 +166,40 @@ class SpectrogramConverter:
         rows form a clip (default: all of them, like the reference).  `spec0` (B, T, n_stft) and
         `angles0` (B, n_stft, T) inject the two random initialisations (tests); otherwise they are drawn
         on the device from `seed` / torch's global generator.
+        `inverse_mel="lstsq"` takes torchaudio >= 2.1's InverseMelScale - relu of the minimum-norm least-squares solution, in
+        closed form on the device (rfx_inverse_mel_lstsq) - in place of the SGD: no random start (`spec0` is refused), no
+        coupling of rows; a bank it does not serve raises ValueError with the library's reason.
         """
         return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
-                                       channels_per_clip=channels_per_clip)
+                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel)
 
     def _waveform_from_mel(self, plan: T.Any, amplitudes_mel: torch.Tensor, *, spec0: T.Optional[torch.Tensor] = None,
                            angles0: T.Optional[torch.Tensor] = None, seed: T.Optional[int] = None,
                            channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0,
-                           return_slots: bool = False) -> T.Any:
+                           return_slots: bool = False, inverse_mel: str = "sgd") -> T.Any:
         """`waveform_from_mel_amplitudes` on a plan the caller already holds (the batch entry points fetch it once per call,
         not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild).
         `return_slots=True` runs the two inverse stages separately - same bits as the one call - and returns
         (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares."""
+        from riffusion import _hip
+
+        lstsq = _hip.check_inverse_mel(inverse_mel)
+        if lstsq:
+            if spec0 is not None:
+                raise ValueError('inverse_mel="lstsq" has no random start: spec0 does not go with it')
+            plan.require_lstsq()
         mel = amplitudes_mel.to(self.device)
         B, _, Tn = mel.shape
         cpc = B if channels_per_clip is None else channels_per_clip
         s = self._seed(seed)
         if spec0 is None and angles0 is None and not return_slots:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
-            return plan.waveform_from_mel(mel, cpc, self.p.num_griffin_lim_iters, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
+            return plan.waveform_from_mel(mel, cpc, self.p.num_griffin_lim_iters, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint,
+                                          lstsq=lstsq)
         spec0 = spec0.to(self.device) if spec0 is not None else None
-        lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
+        if lstsq:
+            lin_slots = plan.inverse_mel_lstsq(mel)
+        else:
+            lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         a0 = plan.pack_complex(angles0.to(self.device)) if angles0 is not None else None
         wave = plan.griffinlim(lin_slots, B, Tn, self.p.num_griffin_lim_iters, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
                                magnitude_hint=magnitude_hint)

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from riffusion import _hip
 from riffusion.spectrogram_converter import SpectrogramConverter
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import audio_util, image_util
@@ -56,11 +57,15 @@ class SpectrogramImageConverter:
         image: Image.Image,
         apply_filters: bool = True,
         max_value: float = 30e6,
+        *,
+        inverse_mel: str = "sgd",
     ) -> T.Any:
         """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference).  The filters
-        (audio_util.apply_filters, compression=False) run on the device: same bytes."""
+        (audio_util.apply_filters, compression=False) run on the device: same bytes.  `inverse_mel`: "sgd" (default) or
+        "lstsq", as in `audio_from_spectrogram_images`."""
         pcm = self.audio_from_spectrogram_images(
-            np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters
+            np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters,
+            inverse_mel=inverse_mel,
         )
         return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
 
@@ -90,6 +95,8 @@ class SpectrogramImageConverter:
         compression: bool = False,
         size: T.Optional[T.Tuple[int, int]] = None,
         return_error: bool = False,
+        *,
+        inverse_mel: str = "sgd",
     ) -> T.Any:
         """
         A sequence of tiles -> ONE audio segment: every tile decoded (`audio_from_spectrogram_images`), filtered
@@ -109,7 +116,9 @@ class SpectrogramImageConverter:
         `return_error=True` returns (segment, errors): the per-clip spectral convergence of `audio_from_spectrogram_images`
         ((n,) float64; a device tensor with `return_device=True`); the segment's bytes do not change.  Not for tiles of
         different sizes without `size`.
+        `inverse_mel`: "sgd" (default) or "lstsq", as in `audio_from_spectrogram_images`.
         """
+        _hip.check_inverse_mel(inverse_mel)
         if isinstance(images, (list, tuple)):
             arrays = [np.asarray(image_util.rgb_array_from_image(im)) if isinstance(im, Image.Image) else np.asarray(im)
                       for im in images]
@@ -117,7 +126,8 @@ class SpectrogramImageConverter:
                 if size is None:
                     if return_error:
                         raise ValueError("return_error needs tiles of one size (or `size`): clips decoded one by one carry no error figure")
-                    return self._image_sequence_mixed(arrays, crossfade_s, apply_filters, max_value, seed, return_device, compression)
+                    return self._image_sequence_mixed(arrays, crossfade_s, apply_filters, max_value, seed, return_device, compression,
+                                                      inverse_mel=inverse_mel)
                 images, size = torch.cat([self.resize_images(a[None], size) for a in arrays]), None
             else:
                 images = np.stack(arrays)
@@ -134,7 +144,7 @@ class SpectrogramImageConverter:
             on_device = False
         pcm = self.audio_from_spectrogram_images(images, max_value=max_value, seed=seed, tiles_per_call=tiles_per_call,
                                                  return_device=True, apply_filters=apply_filters, compression=compression, size=size,
-                                                 return_error=return_error)
+                                                 return_error=return_error, inverse_mel=inverse_mel)
         errors = None
         if return_error:
             pcm, errors = pcm
@@ -153,13 +163,16 @@ class SpectrogramImageConverter:
         return (joined, errors) if return_error else joined
 
     def _image_sequence_mixed(self, arrays: T.List[np.ndarray], crossfade_s: float, apply_filters: bool, max_value: float,
-                              seed: T.Optional[int], return_device: bool, compression: bool) -> T.Any:
+                              seed: T.Optional[int], return_device: bool, compression: bool, inverse_mel: str = "sgd") -> T.Any:
         """audio_from_spectrogram_image_sequence of tiles whose widths differ: clip i is decoded alone with the random starts of
         row i (clip_base), as it would be in one batch, filtered on the device, and the clips are stitched on the host."""
         if compression and not apply_filters:
             raise ValueError("compression=True is a mode of the filters: it needs apply_filters=True")
         conv = self.converter
         plan = conv._plan()
+        lstsq = _hip.check_inverse_mel(inverse_mel)
+        if lstsq:
+            plan.require_lstsq()
         power, max_value = float(self.p.power_for_image), float(max_value)
         if not (max_value > 0.0 and max_value < float("inf")):
             raise ValueError(f"max_value must be a positive finite number, got {max_value}")
@@ -169,7 +182,7 @@ class SpectrogramImageConverter:
         for i, a in enumerate(arrays):
             tile = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))[None].to(plan.device)
             pcm = plan.audio_from_image(tile, self.p.stereo, lut, self.p.num_griffin_lim_iters, 0.99, seed=base_seed, normalize=True,
-                                        clip_base=i, magnitude_hint=max_value)[0]
+                                        clip_base=i, magnitude_hint=max_value, lstsq=lstsq)[0]
             if apply_filters:
                 pcm = self._filter_pcm(plan, pcm, compression)
             segs.append(audio_util.PcmSegment(pcm[0].cpu().numpy(), self.p.sample_rate))
@@ -313,6 +326,8 @@ class SpectrogramImageConverter:
         compression: bool = False,
         size: T.Optional[T.Tuple[int, int]] = None,
         return_error: bool = False,
+        *,
+        inverse_mel: str = "sgd",
     ) -> T.Any:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -366,8 +381,16 @@ class SpectrogramImageConverter:
         InverseMelScale, Griffin-Lim, `Plan.spectral_error`, PCM) instead of the one fused call: `result` is byte for byte the
         result without the flag, and a clip's error does not depend on `tiles_per_call` (rfx_spectral_error is batch-invariant).
         A silent target gives 0.0 (silent audio) or inf.  Not with `group`.
+        `inverse_mel="lstsq"` takes torchaudio >= 2.1's InverseMelScale - relu of the minimum-norm least-squares solution,
+        computed in closed form on the device (rfx_inverse_mel_lstsq) - in place of the SGD ("sgd", the default: the bytes
+        of every release so far).  It needs no iterations and no random start, the bins outside the bank are zeros, and a clip's
+        audio still depends on (the clip, the seed, its index) alone: Griffin-Lim's phases come from the seed as before.  Works
+        with every other option.  A bank it does not serve (`Plan.lstsq_ok`) raises ValueError with the library's reason before
+        any GPU work; any other value raises ValueError.
         """
         from riffusion import batch_shard
+
+        lstsq = _hip.check_inverse_mel(inverse_mel)
 
         if tiles_per_call < 1:
             raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
@@ -385,6 +408,8 @@ class SpectrogramImageConverter:
             raise ValueError(f"gather must be one of {batch_shard.GATHER_MODES}, got {gather!r}")
         conv = self.converter
         plan = conv._plan()
+        if lstsq:
+            plan.require_lstsq()
         imgs = torch.as_tensor(np.ascontiguousarray(images_u8) if isinstance(images_u8, np.ndarray) else images_u8)
         range_msg = ("float images must be the pipeline's [0, 1] output (riffusion_pipeline.py:427-431); "
                      "pass 0..255 pixel values as uint8")
@@ -429,7 +454,7 @@ class SpectrogramImageConverter:
                 if return_error:  # the stages one by one (same bytes as the fused calls below): the error needs both ends of Griffin-Lim
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave, lin_slots = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C,
-                                                              magnitude_hint=max_value, return_slots=True)
+                                                              magnitude_hint=max_value, return_slots=True, inverse_mel=inverse_mel)
                     error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1])).reshape(b - a, C, 2).sum(1))
                     if return_waveform:
                         out = wave.reshape(b - a, C, -1)
@@ -439,12 +464,13 @@ class SpectrogramImageConverter:
                             out = self._filter_pcm(plan, out, compression)
                 elif return_waveform:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
-                    wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value)
+                    wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value,
+                                                   inverse_mel=inverse_mel)
                     out = wave.reshape(b - a, C, -1)
                 else:  # uint8 tiles -> int16 PCM in one call (rfx_audio_from_image_u8_ex), same bytes as the three calls above + pcm16
                     dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
                     out = plan.audio_from_image(tiles, self.p.stereo, lut, self.p.num_griffin_lim_iters, 0.99, seed=base_seed,
-                                                normalize=True, out=dst, clip_base=a, magnitude_hint=max_value)[0]
+                                                normalize=True, out=dst, clip_base=a, magnitude_hint=max_value, lstsq=lstsq)[0]
                     if apply_filters:
                         out = self._filter_pcm(plan, out, compression)
                 # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them
