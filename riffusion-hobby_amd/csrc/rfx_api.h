@@ -63,7 +63,7 @@ struct rfx_plan {
   int num_cus;
   int n_stft;
   int gl_wgs_per_cu = 1;    // resident Griffin-Lim workgroups per CU on this device (occupancy query at creation)
-  int imel_variant = 0;     // debugging override read once at creation: 0 = best, 1 = uniform groups, 2 = general, 3 = best one-frame kernel
+  rfx::ImelVariant imel_variant = rfx::kImelVariantBest;  // debugging override read once at creation
   unsigned long long* timing = nullptr;  // RFX_TIMING builds only
   rfx::cf* d_tw1 = nullptr;      // [21][441]
   rfx::cf* d_tw2 = nullptr;      // [21][21]

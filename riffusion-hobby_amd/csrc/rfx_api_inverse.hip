@@ -455,7 +455,7 @@ size_t rfx_inverse_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { ret
 // through imel_emit_frame can: the output order is just its pos_bin table.  The general LDS kernel stores bin by bin.)
 static bool imel_can_emit_fam_slots(const rfx_plan* plan) {
   return plan->generic && plan->fam_ok && plan->imel_ok && plan->d_fam_binof &&
-         rfx::imel_kernel_choice(plan->imel, plan->p.n_mels, plan->p.max_mel_iters, plan->imel_variant) != 0;
+         rfx::imel_kernel_choice(plan->imel, plan->p.n_mels, plan->p.max_mel_iters, plan->imel_variant) != rfx::kImelKernelGeneral;
 }
 
 static int inverse_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, const float* d_spec0,

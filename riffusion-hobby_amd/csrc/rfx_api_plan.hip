@@ -40,8 +40,8 @@ int rfx_plan_frame_stride(const rfx_plan* plan) { return plan ? plan->frame_stri
 int rfx_plan_is_generic(const rfx_plan* plan) { return plan && plan->generic ? 1 : 0; }
 int rfx_plan_griffinlim_engine(const rfx_plan* plan) { return !plan ? -1 : !plan->generic ? 0 : plan->fam_ok ? 2 : 1; }
 int rfx_plan_imel_unit_form(const rfx_plan* plan) {
-  if (!plan || !plan->d_melfb || !plan->imel_ok || (plan->imel_variant != 0 && plan->imel_variant != 3)) return 0;
-  return plan->imel.fast_ok >= 2 ? plan->imel.unit_form : 0;
+  if (!plan || !plan->d_melfb || !plan->imel_ok || plan->imel_variant != rfx::kImelVariantBest) return 0;
+  return plan->imel.unit_form;  // (set for the per-wave and line-form families only: bank_sgd_admission)
 }
 
 int rfx_plan_imel_kernel(const rfx_plan* plan) {
@@ -148,7 +148,7 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
   // the options; the environment only changes what RFX_GL_FORM_AUTO / the default threshold mean
   if (const int v = abl_positive("RFX_FAM_WGS_PER_CU", 1)) pl->fam_wgs_per_cu = v;
   if (const int v = abl_positive("RFX_GL_WGS_PER_CU", 1)) pl->gl_wgs_per_cu = v;
-  pl->imel_variant = abl_env("RFX_IMEL_GENERAL") ? 2 : abl_env("RFX_IMEL_UNIFORM") ? 1 : abl_env("RFX_IMEL_NO_PAIR") ? 3 : 0;  // 3: best one-frame kernel
+  pl->imel_variant = abl_env("RFX_IMEL_GENERAL") ? rfx::kImelVariantGeneral : abl_env("RFX_IMEL_UNIFORM") ? rfx::kImelVariantUniform : rfx::kImelVariantBest;
   pl->gl_latency_mode = abl_int("RFX_GL_LATENCY_MODE", 1) != 0;
   if (const int v = abl_positive("RFX_GL_LATENCY_FRAMES", 6)) pl->gl_latency_frames_per_slot = v;
   if (opt.gl_frames_per_slot > 0) pl->gl_latency_frames_per_slot = opt.gl_frames_per_slot;
@@ -322,7 +322,7 @@ int rfx_debug_plan_bank(const rfx_params* params, const float* h_melfb, const rf
     const PlanBank bank = plan_bank(geo, params->n_mels, h_melfb, opt, ov);
     r.imel_ok = bank.ok;
     snprintf(r.imel_why, sizeof(r.imel_why), "%s", bank.why.c_str());
-    if (bank.ok) r.imel_kernel = rfx::imel_kernel_choice(bank.imel, params->n_mels, params->max_mel_iters, 0);
+    if (bank.ok) r.imel_kernel = rfx::imel_kernel_choice(bank.imel, params->n_mels, params->max_mel_iters, rfx::kImelVariantBest);
     r.fast_ok = bank.imel.fast_ok;
     r.unit_form = bank.imel.unit_form;
     r.wave_ok = bank.imel.wave_ok;

@@ -11,7 +11,7 @@ namespace rfx {
 
 // Per-row numeric range of Griffin-Lim (round 6): row r of a call analyses its signal times row_scale[2 r] (a power of two that
 // brings the row's magnitudes to about 2^25) and projects with eps^2 = row_scale[2 r + 1] (rfx_core.h::gl_project); written by
-// range_scale_kernel (rfx_imel.hip) from the data or the caller's magnitude_hint.  A null table means {1, 1e-32}.
+// launch_range_scale (rfx_range.hip) from the data or the caller's magnitude_hint.  A null table means {1, 1e-32}.
 struct GlArgs {
   const float* S;             // [B*T][kFrameStride] magnitudes, slot_pos_f order
   const float* row_scale;     // [B][2] or null
@@ -178,12 +178,12 @@ constexpr int kImelHiCap[4] = {23, 16, 12, 9};
 // so its low groups are longer, and its top groups reach 26 bins)
 constexpr int kImelLoCapWide[4] = {5, 3, 5, 6};
 constexpr int kImelHiCapWide[4] = {26, 17, 12, 9};
-// a third set (round 5) for the LINE-FORM group kernel (rfx_imel.hip::imel_line_kernel_perwave): the long groups keep one register
+// a third set (round 5) for the LINE-FORM group kernel (rfx_imel_groups.hip::imel_line_kernel_perwave): the long groups keep one register
 // per bin (weights and momentum buffer are lines per group), so a thread can hold 62 of them - 512 filters up to the Nyquist
 // frequency (group sizes 1.5 .. 61 bins), htk or slaney scale, or 256 / 384 filters over the default 0 - 10 kHz
 constexpr int kImelLoCapLine[4] = {6, 5, 7, 11};
 constexpr int kImelHiCapLine[4] = {62, 40, 26, 18};
-// Wave kernel (round 4, rfx_imel.hip::imel_wave_kernel): ONE wave per frame.  The 512 groups are dealt to the 64 lanes in eight
+// Wave kernel (round 4, rfx_imel_wave.hip::imel_wave_kernel): ONE wave per frame.  The 512 groups are dealt to the 64 lanes in eight
 // chunks of 64 consecutive groups, even chunks in lane order and odd chunks reversed (group 64 c + lane / 64 c + 63 - lane), so a
 // lane's bin count is within 4 % of the mean although group sizes grow 12-fold over the bank, and every group's neighbours sit
 // in the adjacent lane (a DPP wave shift) or, at the chunk seams, in the lane itself.  Budget per chunk in register PAIRS:
@@ -193,9 +193,23 @@ constexpr int kImelWavePairs[kImelWaveChunks] = {2, 2, 3, 3, 5, 6, 8, 12};
 // per-lane 0 / 1 mask for the slots a shorter group leaves empty
 constexpr int kImelWaveFullPairs[kImelWaveChunks] = {0, 1, 1, 2, 3, 4, 5, 8};
 RFX_HD int imel_wave_group(int chunk, int lane) { return (chunk & 1) ? 64 * chunk + 63 - lane : 64 * chunk + lane; }
-#ifndef RFX_IMEL_WAVE
-#define RFX_IMEL_WAVE 1  // 0: build without selecting the wave kernel (A/B against the group kernels)
-#endif
+
+// The SGD kernel families.  The values are public: rfx_plan_imel_kernel and rfx_bank_report::imel_kernel return them, and
+// rfx_bank_report::fast_ok (include/rfx.h) is ImelTables::fast_ok.
+enum ImelKernel : int {
+  kImelKernelGeneral = 0,      // any banded filterbank: spec and weights in LDS (rfx_imel.hip)
+  kImelKernelUniform = 1,      // group formulation, <8, 24> bins per thread in every wave (rfx_imel_groups.hip)
+  kImelKernelPerWave = 2,      // group formulation, per-wave budgets kImelLoCap / kImelHiCap
+  kImelKernelPerWaveWide = 3,  // ... kImelLoCapWide / kImelHiCapWide
+  kImelKernelWave = 4,         // one wave per frame (rfx_imel_wave.hip); never a value of fast_ok: ImelTables::wave_ok admits it
+  kImelKernelLine = 5,         // group formulation with the long groups as lines, kImelLoCapLine / kImelHiCapLine
+};
+// debugging override of the choice (-DRFX_ABLATION builds: RFX_IMEL_UNIFORM, RFX_IMEL_GENERAL)
+enum ImelVariant : int {
+  kImelVariantBest = 0,     // the best kernel the bank admits
+  kImelVariantUniform = 1,  // the uniform group kernel where its budget holds the bank, else the general kernel
+  kImelVariantGeneral = 2,  // the general kernel
+};
 
 // banded InverseMelScale SGD (torchaudio 0.13 semantics), one workgroup per frame
 struct ImelTables {
@@ -211,8 +225,8 @@ struct ImelTables {
   const int* grp_start;  // [M+1] first bin of group g (bins whose first filter is g), fast path only
   int f_lo, f_hi;        // bins with a non-zero filterbank row: [f_lo, f_hi)
   int nnz;
-  int fast_ok;           // 0: general kernel; 1: group formulation with <8, 24> bins per thread; 2: per-wave budgets (default set) fit too;
-                         // 3: only the wide per-wave set fits; 5: the line-form group kernel's set (long groups as lines)
+  int fast_ok;           // the group-kernel family the bank's groups admit, as an ImelKernel: kImelKernelPerWave where the default set
+                         // fits, else ...PerWaveWide, else ...Line, else ...Uniform, else ...General (none)
   int unit_form;         // 1: in every long group (the top 256) a bin's two weights sum to one (to 1e-6) - the last group, whose second
                          // filter does not exist, carries w1 == 0: the per-wave kernels compute the gradient as d1 + (d0 - d1) w0
   const float* lin;      // [4][M] a0 | s0 | a1 | s1: within group g the weights are w0 = a0 + s0 i, w1 = a1 + s1 i for the group's i-th bin
@@ -226,7 +240,7 @@ struct ImelArgs {
   const float* mel;      // [B][M][T]
   const float* spec0;    // optional [B][T][n_stft] injected init (reference layout), else seeded RNG
   float* out_slots;      // [B*T][kFrameStride]
-  const float* clip_scale;  // [nclips][2] {2^-e, 2^e}: the power of two the clip's SGD state is held in (range_scale_kernel), null = 2^-60
+  const float* clip_scale;  // [nclips][2] {2^-e, 2^e}: the power of two the clip's SGD state is held in (launch_range_scale), null = 2^-60
   float sc, un;             // the frame's pair, set inside the kernels (imel_set_scale)
   float* loss_hist;      // [B*T][max_iter] per-frame sum_m diff^2 before each step
   const int* it_limit;   // optional [nclips] number of steps to run (fix-up pass), NULL = max_iter
@@ -239,11 +253,12 @@ struct ImelArgs {
   unsigned long long seed;
   unsigned long long frame_base;  // rfx_call_options::row_base * T: frame f of this call draws its start from key (seed, frame_base + f)
 };
-hipError_t launch_imel(const ImelArgs& a, int variant, hipStream_t stream);  // variant: 0 best, 1 uniform groups, 2 general
-// the kernel launch_imel runs: 4 wave, 5 line-form groups, 2 / 3 per-wave group budgets, 1 uniform groups, 0 general LDS kernel
-// (every one but 0 leaves through imel_emit_frame: its output order is the pos_bin table)
-int imel_kernel_choice(const ImelTables& tb, int M, int max_iter, int variant);
-// scans loss_hist for the early-stop condition; it_stop[clip] = steps the reference would have run
+hipError_t launch_imel(const ImelArgs& a, ImelVariant variant, hipStream_t stream);
+// the families' own launchers (rfx_imel_groups.hip: every group kernel; rfx_imel_wave.hip), called by launch_imel
+hipError_t launch_imel_groups(const ImelArgs& a, ImelKernel kernel, hipStream_t stream);
+hipError_t launch_imel_wave(const ImelArgs& a, hipStream_t stream);
+// the kernel launch_imel runs (every one but the general kernel leaves through imel_emit_frame: its output order is the pos_bin table)
+ImelKernel imel_kernel_choice(const ImelTables& tb, int M, int max_iter, ImelVariant variant);
 // Numeric range (round 6, include/rfx.h): one workgroup per group of `count` contiguous floats of x (a clip's mel amplitudes, or a
 // row's magnitudes) takes max |x| - or `hint` when > 0, without reading x - and writes the powers of two the kernels work in:
 //   imel_scale[g] = {2^-e, 2^e}, e = max(k + 35, 30) for max in [2^(k-1), 2^k)     (nullable)
@@ -261,6 +276,7 @@ RFX_HD void range_exponents(int k, int mel_units, int* e, int* j) {
 // keys: [groups] scratch words
 hipError_t launch_range_scale(const float* x, size_t count, int groups, float hint, unsigned* keys, float* imel_scale, float* gl_scale, int rows,
                               int mel_units, hipStream_t stream);
+// scans loss_hist for the early-stop condition; it_stop[clip] = steps the reference would have run
 hipError_t launch_imel_scan(const float* loss_hist, int* it_stop, int* any_early, int nclips, int C, int T, int max_iter,
                             float tol_loss, float tol_change, hipStream_t stream);
 

@@ -381,22 +381,27 @@ inline bool groups_fit_line(const PlanBank& b) {
 }
 
 // Which SGD kernel family the bank admits (ImelTables::fast_ok), the gradient's unit form and the wave kernel.
-// Per-wave budgets of imel_group_kernel_perwave (rfx_kernels.h): the default bank's exact set (2), then the wide set (3); banks
-// whose groups are too long for either (max_frequency above ~11 kHz at 512 filters - the reference's own round-trip test
-// uses 20 Hz .. 20 kHz, test/spectrogram_converter_test.py:46-53 - or fewer filters) take the line-form group kernel
-// (round 5: imel_line_kernel_perwave, code 5) when their LONG groups M-256 .. M-1 are lines; they ran on the general LDS
-// kernel until then: 169 ms per 64 tiles against 4.5 for the default bank.  Then the uniform budget (1), else the general kernel (0).
+// Per-wave budgets of imel_group_kernel_perwave (rfx_kernels.h): the default bank's exact set (kImelKernelPerWave), then the wide
+// set (kImelKernelPerWaveWide); banks whose groups are too long for either (max_frequency above ~11 kHz at 512 filters - the
+// reference's own round-trip test uses 20 Hz .. 20 kHz, test/spectrogram_converter_test.py:46-53 - or fewer filters) take the
+// line-form group kernel (round 5: imel_line_kernel_perwave, kImelKernelLine) when their LONG groups M-256 .. M-1 are lines; they
+// ran on the general LDS kernel until then: 169 ms per 64 tiles against 4.5 for the default bank.  Then the uniform budget
+// (kImelKernelUniform), else the general kernel.
 inline void bank_sgd_admission(PlanBank& b, int imel_form) {
   if (!b.ok) return;
   const int M = b.M;
-  int fast_code = 0;
+  ImelKernel fast_code = kImelKernelGeneral;
   bool unit_form = false, wave_ok = false;
   if (b.grouped) {
     const int uni_lo[4] = {8, 8, 8, 8}, uni_hi[4] = {24, 24, 24, 24};
-    fast_code = groups_fit(b, kImelLoCap, kImelHiCap) ? 2 : groups_fit(b, kImelLoCapWide, kImelHiCapWide) ? 3 : groups_fit_line(b) ? 5 : groups_fit(b, uni_lo, uni_hi) ? 1 : 0;
+    fast_code = groups_fit(b, kImelLoCap, kImelHiCap)           ? kImelKernelPerWave
+                : groups_fit(b, kImelLoCapWide, kImelHiCapWide) ? kImelKernelPerWaveWide
+                : groups_fit_line(b)                            ? kImelKernelLine
+                : groups_fit(b, uni_lo, uni_hi)                 ? kImelKernelUniform
+                                                                : kImelKernelGeneral;
     // unit form of the gradient: the long groups M-256 .. M-1 must have w0 + w1 == 1 per bin (triangular
     // filters, no area normalisation), the last one w1 == 0 throughout (there is no filter M)
-    unit_form = fast_code >= 2;
+    unit_form = fast_code != kImelKernelGeneral && fast_code != kImelKernelUniform;
     for (int f = b.f_lo; f < b.f_hi && unit_form; ++f) {
       const int g = b.bin_m0[f];
       if (g < M - 256) continue;
@@ -405,7 +410,7 @@ inline void bank_sgd_admission(PlanBank& b, int imel_form) {
     }
     // wave kernel (imel_wave_kernel): 512 groups dealt to 64 lanes in eight chunks whose budgets must hold every
     // group, every group a line; with the unit form (no area normalisation) the upper four chunks need one weight only
-    wave_ok = RFX_IMEL_WAVE && imel_form == RFX_IMEL_FORM_AUTO && fast_code == 2 && M == 64 * kImelWaveChunks && b.line_from == 0;
+    wave_ok = imel_form == RFX_IMEL_FORM_AUTO && fast_code == kImelKernelPerWave && M == 64 * kImelWaveChunks && b.line_from == 0;
     for (int c = 0; c < kImelWaveChunks && wave_ok; ++c)
       for (int lane = 0; lane < 64; ++lane) {
         const int n = b.cnt[imel_wave_group(c, lane)];

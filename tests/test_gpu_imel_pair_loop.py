@@ -1,5 +1,5 @@
 """
-InverseMelScale wave kernel with the chunks' scalar chains paired (rfx_imel.hip, imel_wave_kernel) on the device:
+InverseMelScale wave kernel with the chunks' scalar chains paired (rfx_imel_wave.hip, imel_wave_kernel) on the device:
   * the htk bank (unit form) and the slaney-normalised bank (both weights) take the wave kernel and stay within 1e-5 rel-L2 of the
     group kernels (imel_form="groups", another factorisation of the same SGD);
   * a clip whose targets and start are all zero stops early (its loss is zero at the first step): the scan and the fix-up launch

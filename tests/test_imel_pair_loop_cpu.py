@@ -1,5 +1,5 @@
 """
-The InverseMelScale wave kernel's SGD step with the chunks' scalar chains paired (rfx_imel.hip, imel_wave_kernel): what the
+The InverseMelScale wave kernel's SGD step with the chunks' scalar chains paired (rfx_imel_wave.hip, imel_wave_kernel): what the
 compiler made of it, read from the ISA hipcc emits for gfx950 (no GPU needed).  The per-group scalars of chunks 2j and 2j + 1
 (A / B, residual, loss terms, gradient line) run as one v_pk_*_f32; the shifts and the pair tails stay plain.  Held here, for both
 instantiations (unit form and both weights):
@@ -30,7 +30,7 @@ def asm():
 
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        subprocess.run([HIPCC, *isa_resources.FLAGS, "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "rfx_imel.hip")], check=True,
+        subprocess.run([HIPCC, *isa_resources.FLAGS, "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "rfx_imel_wave.hip")], check=True,
                        capture_output=True, cwd=CSRC)
         return open(out).read()
 

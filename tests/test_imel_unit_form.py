@@ -1,5 +1,5 @@
 """
-CPU check of the arithmetic the InverseMelScale group kernel uses since round 3 (csrc/rfx_imel.hip): state scaled by 2^-60 so
+CPU check of the arithmetic the InverseMelScale group kernel uses since round 3 (csrc/rfx_imel.hip.h, rfx_imel_groups.hip): state scaled by 2^-60 so
 that the clamp at zero is the FMA's [0, 1] output clamp, and the gradient of the long groups in unit form
 d0 w0 + d1 w1 = d1 + (d0 - d1) w0, valid where a bin's two filterbank weights sum to one.  A float32 numpy restatement of the
 kernel's step (group sums A / B, residuals from the neighbours' sums, momentum buffer in units of the gradient scale) is run

@@ -1,5 +1,5 @@
 """
-CPU check of the formulation the InverseMelScale WAVE kernel uses (csrc/rfx_imel.hip::imel_wave_kernel, round 4): one wave per
+CPU check of the formulation the InverseMelScale WAVE kernel uses (csrc/rfx_imel_wave.hip::imel_wave_kernel, round 4): one wave per
 frame, the 512 groups dealt to 64 lanes in eight chunks (even chunks in lane order, odd chunks reversed), neighbours through
 wave shifts whose end lane takes the adjacent chunk's value of the lane itself, weights as a LINE per group
 (w0 = a0 + s0 i, w1 = a1 + s1 i) so that A = a0 S + s0 Q with S = sum x, Q = sum i x; the momentum buffer of a group's bins is

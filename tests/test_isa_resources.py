@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "riffusion-hobby_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FILES = ("rfx_stft.hip", "rfx_gl.hip", "rfx_imel.hip", "rfx_fam.hip")
+FILES = ("rfx_stft.hip", "rfx_gl.hip", "rfx_imel_wave.hip", "rfx_fam.hip")
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 
@@ -77,10 +77,10 @@ def test_forward_and_sgd_kernels_hold_no_scratch(asm):
     # the mel half of the kernel cost: profiles/r05_forward_ablation.txt)
     loads = [l for l in frame_loop(asm["rfx_stft.hip"], fwd[0]) if re.match(r"\s+buffer_load", l)]
     assert 26 <= len(loads) <= 30, len(loads)
-    wave = kernel_symbols(asm["rfx_imel.hip"], r"imel_wave_kernel")
+    wave = kernel_symbols(asm["rfx_imel_wave.hip"], r"imel_wave_kernel")
     assert len(wave) == 2
     for sym in wave:
-        assert scratch_bytes(asm["rfx_imel.hip"], sym) == 0, sym
+        assert scratch_bytes(asm["rfx_imel_wave.hip"], sym) == 0, sym
 
 
 def test_griffinlim_frame_loops_touch_no_scratch(asm):

@@ -2,7 +2,7 @@
 Round 5, CPU side (no GPU needed).
 
 * the line the InverseMelScale wave kernel uses instead of a weight table (rfx_plan_core.h::bank_groups, wave-kernel admission;
-  rfx_imel.hip::imel_wave_kernel) stays within one ulp of a group's LARGEST weight on the reference's banks - the plan's gate is
+  rfx_imel_wave.hip::imel_wave_kernel) stays within one ulp of a group's LARGEST weight on the reference's banks - the plan's gate is
   relative to that maximum (4e-7), not an absolute 1e-6 that an area-normalised bank (weights ~1e-2) would pass at 1e-4 relative;
 * host logic added in round 5: per-device plan cache bound, the one-time warning for `group` without `gather`, ChunkSource.prefetch;
 * the run partition of the Griffin-Lim launches (rfx_kernels.h::gl_run_start through the C ABI): a partition of the frames for
