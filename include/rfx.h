@@ -517,6 +517,31 @@ int rfx_image_resize_u8(const uint8_t* d_in, int N, int H, int W, int out_h, int
                         const int32_t* d_kk_x, const int32_t* d_bounds_y, const int32_t* d_kk_y, uint8_t* d_out, void* d_workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- JPEG: the scan of Pillow's Image.save(f, "JPEG", quality=q) of an RGB uint8 tile, on the device -------------------------
+ * The reference writes every spectrogram tile as a JPEG (cli.py's image_extension="jpg", server.py).  Pillow's defaults are
+ * libjpeg's baseline encoder: YCbCr 4:2:0 (MCUs of 16 x 16 pixels, blocks Y00 Y01 Y10 Y11 Cb Cr), the Annex K quantisation tables
+ * scaled by the quality, the slow integer DCT, the Annex K Huffman tables, no restart markers - integer arithmetic throughout,
+ * reproduced byte for byte.  The device writes the entropy-coded scan and EOI; everything before it (SOI, APP0, APP1 with the
+ * EXIF, DQT, SOF0, DHT, SOS) does not depend on the pixels and is the caller's (riffusion.util.image_util.jpeg_header).
+ * Not implemented: other subsamplings, optimised Huffman tables, progressive scans, greyscale.
+ *
+ * rfx_jpeg_quant_tables, host only (no GPU): the two tables of `quality` (1 .. 100; anything else is RFX_ERR_UNSUPPORTED), 64
+ *   entries each in natural (row-major) order, 1 .. 255 - what DQT carries in zigzag order and d_qtables in natural order.
+ * rfx_jpeg_scan_capacity: bytes one image's scan and EOI take at most (0 for sizes outside 1 .. 65535).  A block codes to at
+ *   most 22 bits of DC (the longest DC code, 11 bits, and 11 value bits) and 63 x 26 bits of AC (the longest AC code, 16 bits,
+ *   and 10 value bits): 1660 bits; the blocks, rounded up to a byte, could all be 0xFF bytes and double with the stuffing, and EOI
+ *   adds 2: 2 * ceil(1660 * 6 * ceil(W / 16) * ceil(H / 16) / 8) + 2.
+ * rfx_jpeg_encode_u8: d_rgb (N, H, W, 3) uint8 -> image n's scan at d_scan + n * capacity, capacity = rfx_jpeg_scan_capacity,
+ *   and its length in d_scan_bytes[n] (never above the capacity; bytes past it are not written).  d_qtables: the two tables as
+ *   (2, 64) uint16 in device memory.  d_workspace holds rfx_jpeg_encode_workspace_bytes (0 for arguments the call refuses).
+ *   H or W above 65535, a capacity that an int32 does not hold, or more blocks than one launch takes are RFX_ERR_UNSUPPORTED,
+ *   refused before anything is launched.  All launches go to `stream`; nothing synchronises. */
+int rfx_jpeg_quant_tables(int quality, uint16_t* h_luma64, uint16_t* h_chroma64);
+size_t rfx_jpeg_scan_capacity(int H, int W);
+size_t rfx_jpeg_encode_workspace_bytes(int N, int H, int W);
+int rfx_jpeg_encode_u8(const uint8_t* d_rgb, int N, int H, int W, const uint16_t* d_qtables, uint8_t* d_scan, int32_t* d_scan_bytes,
+                       void* d_workspace, void* stream);
+
 /* ---- int16 front end of the encode: pydub's set_frame_rate / set_channels and the clip slicing on the device -------------------
  * What the reference does on the host before every encode (cli.py:132-193, streamlit/tasks/audio_to_audio.py): AudioSegment
  * .set_channels (audioop.tomono(data, 2, 0.5, 0.5) / audioop.tostereo(data, 2, 1, 1)), .set_frame_rate

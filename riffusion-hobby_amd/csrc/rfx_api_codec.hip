@@ -1,8 +1,9 @@
 // rfx_api_codec.hip - the C ABI of librfx.so (include/rfx.h), the entry points that take no plan: image decode / encode, int16 PCM,
-// its filters, compressor and stitch, the image resize, and the int16 front end of the encode (resample, channel mix, clip
-// gather).  They run on the device that owns their output buffer.
+// its filters, compressor and stitch, the image resize, the JPEG scan, and the int16 front end of the encode (resample, channel
+// mix, clip gather).  They run on the device that owns their output buffer.
 #include "rfx_api.h"
 #include "rfx_compress_core.h"
+#include "rfx_jpeg_core.h"
 #include "rfx_pcm_core.h"
 #include "rfx_pcm_in_core.h"
 #include "rfx_resize_core.h"
@@ -134,6 +135,49 @@ int rfx_image_resize_u8(const uint8_t* d_in, int N, int H, int W, int out_h, int
   RFX_ON_DEVICE(dev);
   RFX_HIP(launch_resize(d_in, N, H, W, out_h, out_w, d_bounds_x, d_kk_x, rsz_ksize(W, out_w, filter), d_bounds_y, d_kk_y,
                         rsz_ksize(H, out_h, filter), d_out, d_workspace, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+// ---- JPEG scan (rfx_jpeg.hip) ----------------------------------------------------------------------------------------------------
+int rfx_jpeg_quant_tables(int quality, uint16_t* h_luma64, uint16_t* h_chroma64) {
+  if (!h_luma64 || !h_chroma64) return fail(RFX_ERR_INVALID, "rfx_jpeg_quant_tables: null pointer");
+  if (quality < 1 || quality > 100)
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_jpeg_quant_tables: quality " + std::to_string(quality) + " is outside 1 .. 100");
+  jpg_quant_tables(quality, h_luma64, h_chroma64);
+  return RFX_OK;
+}
+
+static bool jpeg_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= kJpgMaxSize && W <= kJpgMaxSize; }
+// what keeps an encode inside its index types: the scan's length is an int32, and the kernels take one thread per block / per
+// 16-byte chunk, 256 to a workgroup, at most 2^31 - 1 workgroups
+static const char* jpeg_batch_limit(int N, int H, int W) {
+  const JpgGeom g = jpg_geom(H, W);
+  if (jpg_scan_capacity(g) > (uint64_t)INT32_MAX) return "one image's scan capacity does not fit the int32 of d_scan_bytes";
+  const uint64_t per_launch = (uint64_t)INT32_MAX * 256;
+  const uint64_t chunks = (jpg_unstuffed_capacity(g) + 31) / 16;
+  if ((uint64_t)N * (uint64_t)g.blocks > per_launch || (uint64_t)N * chunks > per_launch) return "more blocks than one launch takes; encode in pieces";
+  return nullptr;
+}
+
+size_t rfx_jpeg_scan_capacity(int H, int W) { return jpeg_size_ok(H, W) ? (size_t)jpg_scan_capacity(jpg_geom(H, W)) : 0; }
+
+size_t rfx_jpeg_encode_workspace_bytes(int N, int H, int W) {
+  if (N < 1 || !jpeg_size_ok(H, W) || jpeg_batch_limit(N, H, W)) return 0;
+  return jpeg_workspace_layout(N, H, W).total;
+}
+
+int rfx_jpeg_encode_u8(const uint8_t* d_rgb, int N, int H, int W, const uint16_t* d_qtables, uint8_t* d_scan, int32_t* d_scan_bytes,
+                       void* d_workspace, void* stream) {
+  if (N < 1 || H < 1 || W < 1) return fail(RFX_ERR_INVALID, "rfx_jpeg_encode_u8: N, H and W must be positive");
+  if (!jpeg_size_ok(H, W))
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_jpeg_encode_u8: " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): a JPEG holds at most 65535 rows and columns");
+  if (const char* why = jpeg_batch_limit(N, H, W)) return fail(RFX_ERR_UNSUPPORTED, std::string("rfx_jpeg_encode_u8: ") + why);
+  if (!d_rgb || !d_qtables || !d_scan || !d_scan_bytes || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_jpeg_encode_u8: null pointer");
+  int dev;
+  if (int rc = device_of(d_scan, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_jpeg_encode(d_rgb, N, H, W, d_qtables, d_scan, (size_t)jpg_scan_capacity(jpg_geom(H, W)), d_scan_bytes, d_workspace,
+                             (hipStream_t)stream));
   return RFX_OK;
 }
 

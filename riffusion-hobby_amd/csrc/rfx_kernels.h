@@ -435,6 +435,17 @@ hipError_t launch_resize(const uint8_t* in, int N, int H, int W, int OH, int OW,
                          int ksize_x, const int32_t* bounds_y, const int32_t* kk_y, int ksize_y, uint8_t* out, void* workspace,
                          hipStream_t s);
 
+// baseline JPEG scans of (N, H, W, 3) uint8 tiles (rfx_jpeg.hip, arithmetic in rfx_jpeg_core.h): image n's entropy-coded scan
+// and EOI at scan + n * capacity, its length in scan_bytes[n].  qtables: (2, 64) uint16, natural order.  The caller has checked
+// the sizes (1 .. 65535, N * blocks and N * chunks within one launch).
+struct JpgLayout {
+  size_t coef, acbits, bitoff, bit_total, unstuffed, ffpre, total;  // byte offsets, and the size
+  size_t unstuffed_per_image, chunks_per_image;                    // bytes (a multiple of 16) and 16-byte chunks of one image's stream
+};
+JpgLayout jpeg_workspace_layout(int N, int H, int W);
+hipError_t launch_jpeg_encode(const uint8_t* rgb, int N, int H, int W, const uint16_t* qtables, uint8_t* scan, size_t capacity,
+                              int32_t* scan_bytes, void* workspace, hipStream_t s);
+
 // int16 front end of the encode (rfx_pcm_in.hip, arithmetic in rfx_pcm_in_core.h).  launch_pcm_ratecv: the (L, C_in) recording
 // `in`, mixed to C_out channels, then audioop.ratecv to the K = ratecv_out_frames(L, ...) frames of `out`; both pointers are
 // frame-aligned.  launch_pcm_clips: N clips of Lw frames at the frame offsets `starts` (device memory) of `pcm`, mixed to C_out

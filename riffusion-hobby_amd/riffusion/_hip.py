@@ -222,6 +222,10 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_image_from_pcm16_clips_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "rfx_image_from_pcm16_clips": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_jpeg_quant_tables": (c_int, [c_int, c_void_p, c_void_p]),
+    "rfx_jpeg_scan_capacity": (c_size_t, [c_int, c_int]),
+    "rfx_jpeg_encode_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rfx_jpeg_encode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # PIL.Image.Resampling values of the filters rfx_image_resize_u8 implements (rfx_resize_filter)
@@ -241,6 +245,14 @@ def resize_coefficients(in_size: int, out_size: int, resample: int) -> np.ndarra
     if rc < 0:
         check(rc)
     return table
+
+
+def jpeg_quant_tables(quality: int) -> np.ndarray:
+    """rfx_jpeg_quant_tables (host only, no GPU): libjpeg's two quantisation tables of `quality` (1 .. 100, else RfxError) as
+    (2, 64) uint16 in natural order, luma first - what Pillow's `Image.save(f, "JPEG", quality=quality)` uses."""
+    tables = np.zeros((2, 64), dtype=np.uint16)
+    check(load_library().rfx_jpeg_quant_tables(int(quality), tables.ctypes.data, tables.ctypes.data + 128))
+    return tables
 
 
 CLIP_FRAMES_MAX = (1 << 31) - 1  # Lw of the clip entries is a C int
@@ -794,6 +806,36 @@ class Plan:
             check(self.lib.rfx_image_resize_u8(img.data_ptr(), N, H, W, out_h, out_w, resample, bx, kx, by, ky, out.data_ptr(),
                                                ws.data_ptr(), ws.numel(), self._stream()))
         return out
+
+    def jpeg_scans(self, img_u8: torch.Tensor, quality: int = 75) -> T.List[bytes]:
+        """The entropy-coded scan and EOI of every (H, W, 3) uint8 tile of an (N, H, W, 3) batch as Pillow's
+        `Image.save(f, "JPEG", quality=quality)` writes them (rfx_jpeg_encode_u8) -> N `bytes`; a file is
+        `image_util.jpeg_header(...)` + its scan.  The sizes are read once (the call's one synchronisation), then the used bytes of
+        all scans come down in one copy.  Scans and scratch space come from the plan's arena."""
+        if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
+            raise ValueError("expected (N, H, W, 3) uint8 images")
+        img = self._chk(img_u8)
+        N, H, W, _ = img.shape
+        if N == 0:
+            return []
+        qt = self.device_constant(("jpeg_qtables", int(quality)), lambda: jpeg_quant_tables(quality).view(np.int16))
+        cap = self.lib.rfx_jpeg_scan_capacity(H, W)
+        need = self.lib.rfx_jpeg_encode_workspace_bytes(N, H, W)
+        if cap == 0 or need == 0:  # a size the library refuses: its own words (nothing is launched)
+            check(self.lib.rfx_jpeg_encode_u8(img.data_ptr(), N, H, W, qt.data_ptr(), None, None, None, self._stream()))
+            raise RfxError(f"rfx_jpeg_encode_u8 took a {H} x {W} image it reports no capacity for")
+        need = (need + 255) // 256 * 256
+        sizes_d = torch.empty((N,), dtype=torch.int32, device=self.device)
+        with self._workspace(need + N * cap) as ws:
+            check(self.lib.rfx_jpeg_encode_u8(img.data_ptr(), N, H, W, qt.data_ptr(), ws.data_ptr() + need, sizes_d.data_ptr(), ws.data_ptr(),
+                                              self._stream()))
+            sizes = [int(v) for v in sizes_d.cpu()]
+            if min(sizes) < 2 or max(sizes) > cap:
+                raise RfxError(f"rfx_jpeg_encode_u8 reported scan sizes outside 2 .. {cap}")
+            scans = ws[need:need + N * cap].view(N, cap)
+            packed = torch.cat([scans[n, :size] for n, size in enumerate(sizes)]).cpu().numpy().tobytes()
+        ends = np.cumsum(sizes)
+        return [packed[int(e) - size:int(e)] for e, size in zip(ends, sizes)]
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
                           row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False) -> torch.Tensor:

@@ -149,7 +149,8 @@ def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: s
                           power_for_image: float = 0.25, mono: bool = False, sample_rate: int = 44100, device: str = "cuda",
                           num_threads: int = 0, limit: int = -1, batch_size: int = 64) -> None:
     """Process audio clips into spectrogram images in batch (reference cli.py:134-204, same flags and defaults: stereo
-    tiles unless --mono, files resampled to --sample-rate, unreadable files skipped, jpg output).  Instead of one clip
+    tiles unless --mono, files resampled to --sample-rate, unreadable files skipped, jpg output - encoded on the device, the same
+    bytes as Pillow's; png is written by Pillow on the host).  Instead of one clip
     per thread-pool task (`num_threads` is accepted and ignored) same-length clips go to the GPU `batch_size` at a time.  A file
     whose channel count or rate differs is mixed and resampled on the device (Plan.resample_pcm), same bytes as pydub's."""
     import torch
@@ -183,6 +184,13 @@ def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: s
         else:  # a file converted on the device left its waveform there: the host ones of its group join it
             plan = converter.converter._plan()
             batch = torch.stack([w if isinstance(w, torch.Tensor) else torch.from_numpy(w).to(plan.device) for _, w in chunk])
+        if image_format == "JPEG":  # encoded on the device: the bytes of the image.save below, and only they are downloaded
+            files, _ = converter.spectrogram_images_from_waveforms(batch, as_jpeg=True)
+            for (path, _), data in zip(chunk, files):
+                with open(os.path.join(output_dir, os.path.splitext(os.path.basename(path))[0] + "." + image_extension), "wb") as f:
+                    f.write(data)
+            print(f"Wrote {len(chunk)} images to {output_dir}")
+            return
         images, max_values = converter.spectrogram_images_from_waveforms(batch)
         for (path, _), image, mx in zip(chunk, images, max_values):
             exif_data = params.to_exif()

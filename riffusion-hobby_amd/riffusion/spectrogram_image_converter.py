@@ -192,10 +192,15 @@ class SpectrogramImageConverter:
             return torch.from_numpy(joined.copy()).to(plan.device)
         return audio_util.segment_from_pcm16(joined, self.p.sample_rate)
 
-    def spectrogram_images_from_waveforms(self, waveforms: torch.Tensor, return_device: bool = False) -> T.Tuple[T.Any, T.Any]:
+    def spectrogram_images_from_waveforms(self, waveforms: torch.Tensor, return_device: bool = False, *,
+                                          as_jpeg: bool = False) -> T.Tuple[T.Any, T.Any]:
         """(N, C, samples) float waveforms at int16 scale -> N RGB images and their float32 MAX_VALUEs.  With
         `return_device=True` the (N, n_mels, T, 3) uint8 tensor and the (N,) float32 maxima as they are on the GPU (no copy, no
-        synchronisation): the encode side of audio-to-audio's device chain."""
+        synchronisation): the encode side of audio-to-audio's device chain.  With `as_jpeg=True` the images come back as N JPEG
+        files (`bytes`), encoded on the device (`jpeg_bytes_from_images`), each with the params and its MAX_VALUE as EXIF: the
+        bytes of `image.save(f, exif=image.getexif(), format="JPEG")` on `spectrogram_image_from_audio`'s image."""
+        if as_jpeg and return_device:
+            raise ValueError("as_jpeg returns files on the host: it does not go with return_device=True")
         conv = self.converter
         plan = conv._plan()
         N, C, L = waveforms.shape
@@ -207,11 +212,64 @@ class SpectrogramImageConverter:
         img, mx = plan.image_from_waveform(waveforms.reshape(N * C, L).to(conv.device, torch.float32), self.p.stereo, thr)
         if return_device:
             return img, mx
+        if as_jpeg:
+            mx_np = mx.cpu().numpy()
+            return self.jpeg_bytes_from_images(img, exif=[self.exif_with_max_value(v) for v in mx_np]), mx_np
         img_np, mx_np = img.cpu().numpy(), mx.cpu().numpy()
         return [Image.fromarray(a, mode="RGB") for a in img_np], mx_np
 
+    # ---- JPEG files from tiles on the device: Pillow's Image.save(f, "JPEG"), byte for byte (rfx_jpeg_encode_u8) ----------------
+    def exif_with_max_value(self, max_value: float) -> Image.Exif:
+        """The EXIF `spectrogram_image_from_audio` attaches to a tile: the params and the tile's MAX_VALUE."""
+        exif_data = self.p.to_exif()
+        exif_data[SpectrogramParams.ExifTags.MAX_VALUE.value] = float(max_value)
+        exif = Image.Exif()
+        exif.update(exif_data.items())
+        return exif
+
+    def jpeg_bytes_from_images(self, images: T.Any, exif: T.Any = None, quality: int = 75, *, subsampling: T.Any = None,
+                               optimize: T.Any = None, progressive: T.Any = None, tiles_per_call: int = 64) -> T.List[bytes]:
+        """
+        (N, H, W, 3) uint8 tiles (a tensor on any device, or an array) -> N JPEG files as `bytes`, byte-equal to
+        `Image.fromarray(t).save(f, "JPEG", quality=quality, exif=e)`: baseline, 4:2:0, libjpeg's tables for `quality` (1 .. 100)
+        and the standard Huffman tables.  The colour conversion, the DCT, the quantisation and the entropy coding run on the
+        device (rfx_jpeg_encode_u8) and only the coded bytes are downloaded; the header is built on the host
+        (`image_util.jpeg_header`).  `exif`: None, one `Image.Exif` (or its bytes) for every tile, or a sequence of N.
+        Pillow's `subsampling`, `optimize` and `progressive` are not implemented: giving one raises ValueError.  The tiles are
+        encoded `tiles_per_call` at a time: the scans' worst-case buffer is about 2.5 MB per 512 x 512 tile.
+        """
+        for name, value in (("subsampling", subsampling), ("optimize", optimize), ("progressive", progressive)):
+            if value is not None:
+                raise ValueError(f"jpeg_bytes_from_images writes Pillow's default baseline 4:2:0 files only: `{name}` is not implemented")
+        if tiles_per_call < 1:
+            raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        quality = int(quality)
+        if not 1 <= quality <= 100:
+            raise ValueError(f"quality must be in 1 .. 100, got {quality}")
+        plan = self.converter._plan()
+        if not isinstance(images, torch.Tensor):
+            images = np.ascontiguousarray(images)
+            images = images if images.flags.writeable else images.copy()  # (torch takes no read-only arrays, such as a PIL image's)
+        imgs = torch.as_tensor(images)
+        if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[-1] != 3:
+            raise ValueError("expected (N, H, W, 3) uint8 images")
+        N, H, W, _ = imgs.shape
+        if exif is None or isinstance(exif, (Image.Exif, bytes, bytearray)):
+            exifs = [image_util.jpeg_exif_bytes(exif)] * N
+        else:
+            exifs = [image_util.jpeg_exif_bytes(e) for e in exif]
+            if len(exifs) != N:
+                raise ValueError(f"{N} images need {N} EXIF entries (or one for all), got {len(exifs)}")
+        head, tail = image_util.jpeg_header_parts(W, H, quality, _hip.jpeg_quant_tables(quality))
+        files: T.List[bytes] = []
+        for lo in range(0, N, tiles_per_call):
+            chunk = imgs[lo:lo + tiles_per_call]
+            for e, scan in zip(exifs[lo:lo + tiles_per_call], plan.jpeg_scans(chunk.to(plan.device), quality)):
+                files.append(b"".join((head, image_util._jpeg_segment(0xE1, e) if e else b"", tail, scan)))
+        return files
+
     def spectrogram_images_from_audio_clips(self, segment: T.Any, clip_start_times: T.Sequence[float], clip_duration_s: float,
-                                            return_device: bool = False) -> T.Tuple[T.Any, T.Any]:
+                                            return_device: bool = False, *, as_jpeg: bool = False) -> T.Tuple[T.Any, T.Any]:
         """
         One int16 track -> the spectrogram images of its clips: `[spectrogram_image_from_audio(c) for c in
         slice_audio_into_clips(segment.set_frame_rate(params.sample_rate), clip_start_times, clip_duration_s)]`, same image
@@ -224,8 +282,12 @@ class SpectrogramImageConverter:
         converted in a call of its own: it has its own length and hence its own tile width.
         Returns what `spectrogram_images_from_waveforms` returns: the N images and their float32 MAX_VALUEs in the order of
         `clip_start_times`; with `return_device=True` the (N, n_mels, T, 3) uint8 tensor and the (N,) maxima on the GPU - or,
-        when a host-built clip has another width, a list of N (n_mels, T_i, 3) tensors and the (N,) maxima.
+        when a host-built clip has another width, a list of N (n_mels, T_i, 3) tensors and the (N,) maxima.  With `as_jpeg=True`
+        the N images come back as JPEG files (`bytes`) encoded on the device, each with the params and its MAX_VALUE as EXIF, as
+        from `spectrogram_images_from_waveforms`.
         """
+        if as_jpeg and return_device:
+            raise ValueError("as_jpeg returns files on the host: it does not go with return_device=True")
         conv = self.converter
         plan = conv._plan()
         if segment.sample_width != 2 or segment.channels not in (1, 2):
@@ -263,6 +325,14 @@ class SpectrogramImageConverter:
             if n and len(r.index) == n:
                 return img, maxima
             return (torch.stack(tiles) if n else torch.empty((0, plan.n_mels, 0, 3), dtype=torch.uint8, device=plan.device)), maxima
+        if as_jpeg:
+            mx_np = maxima.cpu().numpy()
+            exifs = [self.exif_with_max_value(v) for v in mx_np]
+            if n and len(r.index) == n:
+                return self.jpeg_bytes_from_images(img, exif=exifs), mx_np
+            if same_width:
+                return (self.jpeg_bytes_from_images(torch.stack(tiles), exif=exifs) if n else []), mx_np
+            return [self.jpeg_bytes_from_images(t[None], exif=e)[0] for t, e in zip(tiles, exifs)], mx_np
         return [Image.fromarray(t.cpu().numpy(), mode="RGB") for t in tiles], maxima.cpu().numpy()
 
     # ---- resizing tiles on the device: PIL.Image.resize, byte for byte (rfx_image_resize_u8) --------------------------------

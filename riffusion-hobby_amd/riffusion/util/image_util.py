@@ -15,6 +15,7 @@ bit-exact to the reference given the same float input; the numpy functions below
 tables so host and device agree byte for byte.
 """
 import functools
+import struct
 import typing as T
 
 import numpy as np
@@ -122,3 +123,70 @@ def exif_from_image(pil_image: Image.Image) -> T.Dict[str, T.Any]:
     if exif is None or len(exif) == 0:
         return {}
     return {SpectrogramParams.ExifTags(key).name: val for key, val in exif.items()}
+
+
+# ---- JPEG: everything of a file that does not depend on the pixels (the device writes the scan: rfx_jpeg_encode_u8) ----------
+# ITU T.81 Annex K.3, the tables libjpeg (and so Pillow, without `optimize`) puts into DHT: (class << 4 | id, BITS, HUFFVAL)
+JPEG_HUFFMAN_TABLES: T.Tuple[T.Tuple[int, bytes, bytes], ...] = (
+    (0x00, bytes([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]), bytes(range(12))),
+    (0x10, bytes([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D]), bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a"
+        "434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aa"
+        "b2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")),
+    (0x01, bytes([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]), bytes(range(12))),
+    (0x11, bytes([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77]), bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a"
+        "434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aa"
+        "b2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
+)
+# zigzag position -> natural (row-major) index: DQT carries a table in zigzag order
+JPEG_NATURAL_ORDER = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+                      28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
+                      47, 55, 62, 63)
+JPEG_MAX_SIZE = 65535
+
+
+def _jpeg_segment(marker: int, payload: bytes) -> bytes:
+    if len(payload) + 2 > 65535:
+        raise ValueError(f"JPEG segment FF{marker:02X} of {len(payload)} bytes is longer than a marker segment holds")
+    return struct.pack(">BBH", 0xFF, marker, len(payload) + 2) + payload
+
+
+def jpeg_exif_bytes(exif: T.Any) -> bytes:
+    """What Pillow's JPEG writer makes of its `exif` argument: an `Image.Exif` as `tobytes()`, bytes as they are, None as none."""
+    if exif is None:
+        return b""
+    return exif.tobytes() if isinstance(exif, Image.Exif) else bytes(exif)
+
+
+def jpeg_header_parts(width: int, height: int, quality: int = 75, qtables: T.Optional[np.ndarray] = None) -> T.Tuple[bytes, bytes]:
+    """`jpeg_header` without the EXIF: (what comes before APP1, what comes after it) - the same for every tile of a batch."""
+    width, height = int(width), int(height)
+    if not (1 <= width <= JPEG_MAX_SIZE and 1 <= height <= JPEG_MAX_SIZE):
+        raise ValueError(f"a JPEG holds 1 .. {JPEG_MAX_SIZE} rows and columns, got {width} x {height}")
+    if qtables is None:
+        from riffusion import _hip
+
+        qtables = _hip.jpeg_quant_tables(quality)
+    qtables = np.asarray(qtables)
+    if qtables.shape != (2, 64) or qtables.min() < 1 or qtables.max() > 255:
+        raise ValueError("qtables must be (2, 64) with entries in 1 .. 255")
+    head = b"\xff\xd8" + _jpeg_segment(0xE0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    out = [_jpeg_segment(0xDB, bytes([i]) + bytes(int(qtables[i][n]) for n in JPEG_NATURAL_ORDER)) for i in range(2)]
+    # 8 bits, three components: Y 2 x 2 with table 0, Cb and Cr 1 x 1 with table 1
+    out.append(_jpeg_segment(0xC0, struct.pack(">BHHB", 8, height, width, 3) + bytes([1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1])))
+    for tc_th, bits, vals in JPEG_HUFFMAN_TABLES:
+        out.append(_jpeg_segment(0xC4, bytes([tc_th]) + bits + vals))
+    out.append(_jpeg_segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
+    return head, b"".join(out)
+
+
+def jpeg_header(width: int, height: int, quality: int = 75, exif_bytes: bytes = b"", qtables: T.Optional[np.ndarray] = None) -> bytes:
+    """
+    The bytes of `Image.save(f, "JPEG", quality=quality, exif=...)` of an RGB image up to the scan: SOI, APP0 (JFIF 1.01, no
+    units, density 1:1), APP1 with `exif_bytes` (`Image.Exif.tobytes()`, which starts with b"Exif\\0\\0"; empty: no APP1), the two
+    quantisation tables, SOF0 (4:2:0), the four Huffman tables, SOS.  `qtables`: the (2, 64) tables in natural order; by
+    default those of `quality` from the library (rfx_jpeg_quant_tables, host only).
+    """
+    head, tail = jpeg_header_parts(width, height, quality, qtables)
+    return head + (_jpeg_segment(0xE1, bytes(exif_bytes)) if exif_bytes else b"") + tail
