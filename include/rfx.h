@@ -542,6 +542,35 @@ size_t rfx_jpeg_encode_workspace_bytes(int N, int H, int W);
 int rfx_jpeg_encode_u8(const uint8_t* d_rgb, int N, int H, int W, const uint16_t* d_qtables, uint8_t* d_scan, int32_t* d_scan_bytes,
                        void* d_workspace, void* stream);
 
+/* ---- JPEG decode: np.asarray(Image.open(f).convert("RGB")) of a baseline JPEG tile, on the device ------------------------------
+ * The other direction: files of the corpus to (N, H, W, 3) uint8 tiles, the pixels Pillow (libjpeg-turbo, the v6b API) decodes,
+ * byte for byte - Huffman decoding, jpeg_idct_islow, h2v2_fancy_upsample (plain replication for W <= 4, as libjpeg chooses) and
+ * ycc_rgb_convert are integer arithmetic throughout.  Taken: 8-bit baseline (SOF0), three components Y Cb Cr sampled 2x2, 1x1,
+ * 1x1, one interleaved scan, no restart interval, any Huffman tables (so `optimize=True` files too).  Everything before the scan
+ * is the caller's to parse (riffusion.util.image_util.jpeg_parse), which also keeps every other kind of file on the host.
+ * The scan is decoded in parallel: its bit stream, without the stuffed zeros, is cut into subsequences of 1024 bits, one thread
+ * each, 256 at a time in one workgroup per image; every thread decodes from the state its predecessor left, in rounds, until no
+ * state changes (self-synchronisation), and a last pass writes the coefficients.  No workgroup waits for another one.
+ *
+ * rfx_jpeg_decode_u8: image n's entropy-coded bytes - what follows the SOS header, up to and not including EOI - are
+ *   d_scans[offsets[n] .. offsets[n + 1]); h_scan_offsets (host) and d_scan_offsets (device memory) are the same N + 1 int64,
+ *   not decreasing, the first not negative; d_scans is aligned to 16 bytes and holds offsets[N] bytes.  All images are H x W.
+ *   d_qtables: (N, 2, 64) uint16, each image's luma and chroma table in natural (row-major) order.  d_huff: (N, 4, 272) uint8, each
+ *   image's DC luma, AC luma, DC chroma and AC chroma table as DHT carries it: BITS[16], then HUFFVAL padded to 256.
+ *   d_rgb: (N, H, W, 3) uint8.  d_status: (N) int32, one per image:
+ *     0 decoded; 1 a marker inside the scan (0xFF followed by anything but 0x00, or as the last byte); 2 a Huffman table that is
+ *     no prefix code of at most 256 symbols; 3 the scan ends inside a block; 4 bits that are no code of the table, or a DC size
+ *     above 11 / an AC size above 10; 5 a run past coefficient 63; 6 blocks missing at the end of the scan, or more than 7 bits
+ *     left over after the last block.  With several causes the largest is reported.
+ *   An image with a non-zero status has undefined pixels; the others of the call are not affected.  No read leaves d_scans'
+ *   offsets[N] bytes or the workspace, whatever the bytes are.  d_workspace holds rfx_jpeg_decode_workspace_bytes(N, H, W,
+ *   offsets[N] - offsets[0]) (0 for arguments the call refuses).  H or W above 65535, a scan longer than 2^28 - 64 bytes, or more
+ *   blocks or pixels than one launch takes (N * 6 * ceil(W / 16) * ceil(H / 16) or N * H * W above (2^31 - 1) * 256) are
+ *   RFX_ERR_UNSUPPORTED, refused before anything is launched.  All launches go to `stream`; nothing synchronises. */
+size_t rfx_jpeg_decode_workspace_bytes(int N, int H, int W, size_t total_scan_bytes);
+int rfx_jpeg_decode_u8(const uint8_t* d_scans, const int64_t* h_scan_offsets, const int64_t* d_scan_offsets, int N, int H, int W,
+                       const uint16_t* d_qtables, const uint8_t* d_huff, uint8_t* d_rgb, int32_t* d_status, void* d_workspace, void* stream);
+
 /* ---- int16 front end of the encode: pydub's set_frame_rate / set_channels and the clip slicing on the device -------------------
  * What the reference does on the host before every encode (cli.py:132-193, streamlit/tasks/audio_to_audio.py): AudioSegment
  * .set_channels (audioop.tomono(data, 2, 0.5, 0.5) / audioop.tostereo(data, 2, 1, 1)), .set_frame_rate

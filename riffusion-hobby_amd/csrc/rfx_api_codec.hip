@@ -1,9 +1,10 @@
 // rfx_api_codec.hip - the C ABI of librfx.so (include/rfx.h), the entry points that take no plan: image decode / encode, int16 PCM,
-// its filters, compressor and stitch, the image resize, the JPEG scan, and the int16 front end of the encode (resample, channel
+// its filters, compressor and stitch, the image resize, the JPEG scan and its decode, and the int16 front end of the encode (resample, channel
 // mix, clip gather).  They run on the device that owns their output buffer.
 #include "rfx_api.h"
 #include "rfx_compress_core.h"
 #include "rfx_jpeg_core.h"
+#include "rfx_jpeg_dec_core.h"
 #include "rfx_pcm_core.h"
 #include "rfx_pcm_in_core.h"
 #include "rfx_resize_core.h"
@@ -178,6 +179,47 @@ int rfx_jpeg_encode_u8(const uint8_t* d_rgb, int N, int H, int W, const uint16_t
   RFX_ON_DEVICE(dev);
   RFX_HIP(launch_jpeg_encode(d_rgb, N, H, W, d_qtables, d_scan, (size_t)jpg_scan_capacity(jpg_geom(H, W)), d_scan_bytes, d_workspace,
                              (hipStream_t)stream));
+  return RFX_OK;
+}
+
+// ---- JPEG decode (rfx_jpeg_dec.hip) -----------------------------------------------------------------------------------------------
+// what keeps a decode inside its index types: one thread per block and per pixel, 256 to a workgroup, at most 2^31 - 1 workgroups
+static const char* jpeg_decode_batch_limit(int N, int H, int W) {
+  const uint64_t per_launch = (uint64_t)INT32_MAX * 256;
+  if ((uint64_t)N * (uint64_t)jpg_geom(H, W).blocks > per_launch || (uint64_t)N * (uint64_t)H * (uint64_t)W > per_launch)
+    return "more blocks or pixels than one launch takes; decode in pieces";
+  return nullptr;
+}
+
+size_t rfx_jpeg_decode_workspace_bytes(int N, int H, int W, size_t total_scan_bytes) {
+  if (N < 1 || !jpeg_size_ok(H, W) || jpeg_decode_batch_limit(N, H, W) || total_scan_bytes > (size_t)N * (size_t)kJpdMaxScanBytes) return 0;
+  return jpeg_decode_workspace_layout(N, H, W, total_scan_bytes).total;
+}
+
+int rfx_jpeg_decode_u8(const uint8_t* d_scans, const int64_t* h_scan_offsets, const int64_t* d_scan_offsets, int N, int H, int W,
+                       const uint16_t* d_qtables, const uint8_t* d_huff, uint8_t* d_rgb, int32_t* d_status, void* d_workspace, void* stream) {
+  if (N < 1 || H < 1 || W < 1) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: N, H and W must be positive");
+  if (!jpeg_size_ok(H, W))
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_jpeg_decode_u8: " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): a JPEG holds at most 65535 rows and columns");
+  if (const char* why = jpeg_decode_batch_limit(N, H, W)) return fail(RFX_ERR_UNSUPPORTED, std::string("rfx_jpeg_decode_u8: ") + why);
+  if (!h_scan_offsets) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: h_scan_offsets is NULL");
+  if (h_scan_offsets[0] < 0) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: the first scan offset is negative");
+  int64_t longest = 0;
+  for (int n = 0; n < N; ++n) {
+    const int64_t bytes = h_scan_offsets[n + 1] - h_scan_offsets[n];
+    if (bytes < 0) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: scan offsets must not decrease (image " + std::to_string(n) + ")");
+    if (bytes > kJpdMaxScanBytes)
+      return fail(RFX_ERR_UNSUPPORTED, "rfx_jpeg_decode_u8: the scan of image " + std::to_string(n) + " is longer than 2^28 - 64 bytes");
+    longest = bytes > longest ? bytes : longest;
+  }
+  if (!d_scans || !d_scan_offsets || !d_qtables || !d_huff || !d_rgb || !d_status || !d_workspace)
+    return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: null pointer");
+  if (reinterpret_cast<uintptr_t>(d_scans) % 16) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: d_scans must be aligned to 16 bytes");
+  int dev;
+  if (int rc = device_of(d_rgb, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_jpeg_decode(d_scans, d_scan_offsets, longest, (size_t)(h_scan_offsets[N] - h_scan_offsets[0]), N, H, W, d_qtables, d_huff, d_rgb,
+                             d_status, d_workspace, (hipStream_t)stream));
   return RFX_OK;
 }
 

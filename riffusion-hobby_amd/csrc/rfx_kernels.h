@@ -446,6 +446,19 @@ JpgLayout jpeg_workspace_layout(int N, int H, int W);
 hipError_t launch_jpeg_encode(const uint8_t* rgb, int N, int H, int W, const uint16_t* qtables, uint8_t* scan, size_t capacity,
                               int32_t* scan_bytes, void* workspace, hipStream_t s);
 
+// baseline JPEG scans to (N, H, W, 3) uint8 tiles (rfx_jpeg_dec.hip, arithmetic in rfx_jpeg_dec_core.h): image n's entropy-coded
+// bytes are scans[offsets[n] .. offsets[n + 1]) (offsets: N + 1 int64 in device memory; scans 16-byte aligned), its tables
+// qtables[n] (2, 64) uint16 in natural order and huff[n] (4, 272) uint8; status[n] receives 0 or a kJpd* code.  The caller has
+// checked the sizes (1 .. 65535, N * blocks and N * H * W within one launch, every scan at most kJpdMaxScanBytes);
+// max_scan_bytes is the longest scan, total_scan_bytes = offsets[N] - offsets[0].
+struct JpdLayout {
+  size_t unstuffed, pre, ulen, coef, planes, total;  // byte offsets, and the size
+  size_t coef_bytes;                                 // the coefficients: cleared before every decode
+};
+JpdLayout jpeg_decode_workspace_layout(int N, int H, int W, size_t total_scan_bytes);
+hipError_t launch_jpeg_decode(const uint8_t* scans, const int64_t* offsets, int64_t max_scan_bytes, size_t total_scan_bytes, int N, int H, int W,
+                              const uint16_t* qtables, const uint8_t* huff, uint8_t* rgb, int32_t* status, void* workspace, hipStream_t s);
+
 // int16 front end of the encode (rfx_pcm_in.hip, arithmetic in rfx_pcm_in_core.h).  launch_pcm_ratecv: the (L, C_in) recording
 // `in`, mixed to C_out channels, then audioop.ratecv to the K = ratecv_out_frames(L, ...) frames of `out`; both pointers are
 // frame-aligned.  launch_pcm_clips: N clips of Lw frames at the frame offsets `starts` (device memory) of `pcm`, mixed to C_out

@@ -226,6 +226,9 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_jpeg_scan_capacity": (c_size_t, [c_int, c_int]),
     "rfx_jpeg_encode_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rfx_jpeg_encode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rfx_jpeg_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t]),
+    "rfx_jpeg_decode_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
 }
 
 # PIL.Image.Resampling values of the filters rfx_image_resize_u8 implements (rfx_resize_filter)
@@ -836,6 +839,40 @@ class Plan:
             packed = torch.cat([scans[n, :size] for n, size in enumerate(sizes)]).cpu().numpy().tobytes()
         ends = np.cumsum(sizes)
         return [packed[int(e) - size:int(e)] for e, size in zip(ends, sizes)]
+
+    def jpeg_decode(self, scans: T.Sequence[bytes], H: int, W: int, qtables: np.ndarray, huffman: np.ndarray) -> T.Tuple[torch.Tensor, np.ndarray]:
+        """N baseline 4:2:0 JPEG scans of H x W images (the entropy-coded bytes between the SOS header and EOI, with each image's
+        (2, 64) quantisation tables in natural order and (4, 272) Huffman tables: `image_util.jpeg_parse`) -> the (N, H, W, 3) uint8
+        pixels Pillow decodes, on this device, and the (N,) int32 status of every image (rfx_jpeg_decode_u8; 0: decoded, anything
+        else: that image's pixels are undefined).  Offsets, tables and scans go up in one copy; reading the status is the call's
+        one synchronisation."""
+        N = len(scans)
+        qtables = np.ascontiguousarray(qtables, dtype=np.uint16).reshape(N, 2, 64)
+        huffman = np.ascontiguousarray(huffman, dtype=np.uint8).reshape(N, 4, 272)
+        out = torch.empty((N, int(H), int(W), 3), dtype=torch.uint8, device=self.device)
+        if N == 0:
+            return out, np.zeros(0, np.int32)
+        offsets = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in scans], out=offsets[1:])
+        total = int(offsets[-1])
+        need = self.lib.rfx_jpeg_decode_workspace_bytes(N, int(H), int(W), total)
+        # one upload: [offsets | qtables | huffman | scans], the scans on a 16-byte boundary
+        parts = [offsets.view(np.uint8), qtables.reshape(-1).view(np.uint8), huffman.reshape(-1)]
+        head = sum(p.size for p in parts)
+        pad = -head % 16
+        host = np.concatenate(parts + [np.zeros(pad, np.uint8), np.frombuffer(b"".join(scans), np.uint8)])
+        up = torch.from_numpy(host).to(self.device)
+        base = up.data_ptr()
+        status = torch.empty((N,), dtype=torch.int32, device=self.device)
+        if need == 0:  # arguments the library refuses: its own words (nothing is launched)
+            check(self.lib.rfx_jpeg_decode_u8(base + head + pad, offsets.ctypes.data, base, N, int(H), int(W), base + offsets.nbytes,
+                                              base + offsets.nbytes + qtables.nbytes, out.data_ptr(), status.data_ptr(), None, self._stream()))
+            raise RfxError(f"rfx_jpeg_decode_u8 took {N} {H} x {W} images it reports no workspace for")
+        with self._workspace(need) as ws:
+            check(self.lib.rfx_jpeg_decode_u8(base + head + pad, offsets.ctypes.data, base, N, int(H), int(W), base + offsets.nbytes,
+                                              base + offsets.nbytes + qtables.nbytes, out.data_ptr(), status.data_ptr(), ws.data_ptr(), self._stream()))
+            status_np = status.cpu().numpy()
+        return out, status_np
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
                           row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False) -> torch.Tensor:

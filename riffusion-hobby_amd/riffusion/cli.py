@@ -98,32 +98,63 @@ def _rank_device(device: str) -> str:
     return device
 
 
+def _tile_groups(paths: T.Sequence[str], image_extension: str) -> T.Dict[T.Tuple[SpectrogramParams, T.Tuple[int, int]], T.List[str]]:
+    """Image files by (params from their EXIF, (width, height)): the tiles of one GPU call share both.  A jpg's size and EXIF come
+    from the bytes before its scan (image_util.jpeg_parse), without opening it as an image; a file that does not parse is opened."""
+    groups: T.Dict[T.Tuple[SpectrogramParams, T.Tuple[int, int]], T.List[str]] = {}
+    for path in paths:
+        if image_extension != "png":
+            with open(path, "rb") as f:
+                info = image_util.jpeg_parse(f.read())
+            if info.width and info.height:
+                exif = Image.Exif()
+                if info.exif:
+                    exif.load(info.exif)
+                try:
+                    params = SpectrogramParams.from_exif(exif=exif)
+                except (KeyError, AttributeError):
+                    print("WARNING: Could not find spectrogram parameters in exif data. Using defaults.")
+                    params = SpectrogramParams()
+                groups.setdefault((params, (info.width, info.height)), []).append(path)
+                continue
+        with Image.open(path) as im:
+            groups.setdefault((_params_from_image(im), im.size), []).append(path)
+    return groups
+
+
+def _load_tiles(converter: SpectrogramImageConverter, chunk: T.Sequence[str], image_extension: str) -> T.Any:
+    """The (N, H, W, 3) uint8 tiles of one chunk of same-size files, opened by Pillow one by one and stacked on the host.
+    jpg / jpeg files could be decoded on the device instead (`converter.images_from_jpeg_bytes(files, return_device=True)`: the
+    same pixels, and only the coded bytes are uploaded); they stay on this route until tools/probe_jpeg_decode.py has written
+    profiles/jpeg_decode.txt and the device route is faster there on both of its sets."""
+    tiles = []
+    for p in chunk:
+        with Image.open(p) as im:
+            tiles.append(image_util.rgb_array_from_image(im))
+    return np.stack(tiles)
+
+
 def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 64, no_filters: bool = False,
-                          compression: bool = False, device: str = "cuda", inverse_mel: str = "sgd") -> None:
-    """Decode every *.png of a directory, `batch_size` same-width tiles per GPU call.  Each clip then gets the same
+                          compression: bool = False, device: str = "cuda", inverse_mel: str = "sgd", image_extension: str = "png") -> None:
+    """Decode every *.png (or, with --image-extension jpg / jpeg, every file of that extension) of a directory, `batch_size`
+    same-width tiles per GPU call.  Each clip then gets the same
     post-processing as `image-to-audio` (audio_util.apply_filters, reference spectrogram_image_converter.py:65-91, run on the
     device) unless --no-filters is given; --compression adds the filters' dynamic range compression (apply_filters with
     compression=True, also on the device); --inverse-mel lstsq takes the closed-form InverseMelScale instead of the SGD."""
     if compression and no_filters:
         raise ValueError("--compression is a mode of the filters: it does not go with --no-filters")
+    if image_extension not in ("png", "jpg", "jpeg"):
+        raise ValueError(f"--image-extension must be png, jpg or jpeg, got {image_extension}")
     os.makedirs(output_dir, exist_ok=True)
     device = _rank_device(device)
-    paths = _rank_slice(sorted(glob.glob(os.path.join(image_dir, "*.png"))))
-    groups: T.Dict[T.Tuple[SpectrogramParams, T.Tuple[int, int]], T.List[str]] = {}
-    for path in paths:
-        with Image.open(path) as im:
-            groups.setdefault((_params_from_image(im), im.size), []).append(path)
-    for (params, _size), members in groups.items():
+    paths = _rank_slice(sorted(glob.glob(os.path.join(image_dir, "*." + image_extension))))
+    for (params, _size), members in _tile_groups(paths, image_extension).items():
         converter = SpectrogramImageConverter(params=params, device=device)
         for i in range(0, len(members), batch_size):
             chunk = members[i : i + batch_size]
-            tiles = []
-            for p in chunk:
-                with Image.open(p) as im:
-                    tiles.append(image_util.rgb_array_from_image(im))
             # the filters run on the device, clip by clip, before the batch leaves it (same bytes as audio_util.apply_filters)
-            pcm = converter.audio_from_spectrogram_images(np.stack(tiles), apply_filters=not no_filters, compression=compression,
-                                                          inverse_mel=inverse_mel)
+            pcm = converter.audio_from_spectrogram_images(_load_tiles(converter, chunk, image_extension), apply_filters=not no_filters,
+                                                          compression=compression, inverse_mel=inverse_mel)
             for path, samples in zip(chunk, pcm):
                 segment = audio_util.PcmSegment(samples, params.sample_rate)
                 out = os.path.join(output_dir, os.path.splitext(os.path.basename(path))[0] + ".wav")

@@ -268,6 +268,57 @@ class SpectrogramImageConverter:
                 files.append(b"".join((head, image_util._jpeg_segment(0xE1, e) if e else b"", tail, scan)))
         return files
 
+    # ---- tiles from JPEG files, decoded on the device: np.asarray(Image.open(f).convert("RGB")), byte for byte (rfx_jpeg_decode_u8) --
+    def images_from_jpeg_bytes(self, files: T.Sequence[bytes], return_device: bool = False, tiles_per_call: int = 64) -> T.Tuple[T.Any, T.List[Image.Exif]]:
+        """
+        N image files as `bytes` -> (their (H, W, 3) uint8 tiles, their EXIF as `Image.Exif`).  A baseline 4:2:0 JPEG
+        (`image_util.jpeg_parse(...).ok_for_device`: what Pillow's default `save` and `jpeg_bytes_from_images` write, `optimize=True`
+        included) is decoded on the device, `tiles_per_call` files of one size at a time, to the pixels Pillow gives; only the coded
+        bytes are uploaded.  Every other file - progressive, greyscale, other subsamplings, restart markers, not a JPEG - and every
+        file whose scan the device reports as damaged is opened by Pillow on the host (`image_util.rgb_array_from_image`), with
+        Pillow's own exceptions for files it cannot read.  The tiles come back as one (N, H, W, 3) batch when all files have one
+        size, else as a list of N; numpy arrays, or tensors on the device with `return_device=True`.
+        """
+        import io
+
+        if tiles_per_call < 1:
+            raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        files = [bytes(f) for f in files]
+        plan = self.converter._plan()
+        infos = [image_util.jpeg_parse(f) for f in files]
+        tiles: T.List[T.Any] = [None] * len(files)
+        exifs: T.List[T.Any] = [None] * len(files)
+        by_size: T.Dict[T.Tuple[int, int], T.List[int]] = {}
+        for i, info in enumerate(infos):
+            if info.ok_for_device:
+                by_size.setdefault((info.height, info.width), []).append(i)
+        whole = None  # the one device batch that is the whole result, if there is one
+        for (H, W), members in by_size.items():
+            for lo in range(0, len(members), tiles_per_call):
+                idx = members[lo:lo + tiles_per_call]
+                rgb, status = plan.jpeg_decode([files[i][infos[i].scan[0]:infos[i].scan[1]] for i in idx], H, W,
+                                               np.stack([infos[i].qtables for i in idx]), np.stack([infos[i].huffman for i in idx]))
+                if len(idx) == len(files) and not status.any():
+                    whole = rgb
+                batch = rgb if return_device else rgb.cpu().numpy()
+                for j, i in enumerate(idx):
+                    if status[j] == 0:
+                        tiles[i] = batch[j]
+                        exifs[i] = Image.Exif()
+                        if infos[i].exif:
+                            exifs[i].load(infos[i].exif)
+        for i, data in enumerate(files):
+            if tiles[i] is None:  # the host route
+                with Image.open(io.BytesIO(data)) as im:
+                    arr = image_util.rgb_array_from_image(im)
+                    exifs[i] = im.getexif()
+                tiles[i] = torch.from_numpy(arr).to(plan.device) if return_device else arr
+        if whole is not None:
+            return (whole if return_device else whole.cpu().numpy()), exifs
+        if len(files) and len({tuple(t.shape) for t in tiles}) == 1:
+            return (torch.stack(tiles) if return_device else np.stack(tiles)), exifs
+        return tiles, exifs
+
     def spectrogram_images_from_audio_clips(self, segment: T.Any, clip_start_times: T.Sequence[float], clip_duration_s: float,
                                             return_device: bool = False, *, as_jpeg: bool = False) -> T.Tuple[T.Any, T.Any]:
         """

@@ -15,6 +15,7 @@ bit-exact to the reference given the same float input; the numpy functions below
 tables so host and device agree byte for byte.
 """
 import functools
+import re
 import struct
 import typing as T
 
@@ -190,3 +191,151 @@ def jpeg_header(width: int, height: int, quality: int = 75, exif_bytes: bytes = 
     """
     head, tail = jpeg_header_parts(width, height, quality, qtables)
     return head + (_jpeg_segment(0xE1, bytes(exif_bytes)) if exif_bytes else b"") + tail
+
+
+# ---- JPEG: what a decoder needs of a file before its scan (the device decodes the scan: rfx_jpeg_decode_u8) -------------------
+class JpegInfo(T.NamedTuple):
+    """`jpeg_parse`'s result.  `qtables`: (2, 64) uint16 in natural order, the luma component's table and the chroma components';
+    `huffman`: (4, 272) uint8, BITS[16] + HUFFVAL[256] of the luma DC, luma AC, chroma DC and chroma AC tables; `scan`: the byte
+    range of the entropy-coded data, after the SOS header and up to (not including) the marker that ends it; `exif`: the APP1
+    payload as Pillow keeps it in `info["exif"]` (b"" when the file has none).  Fields the file does not reach are None / 0."""
+    width: int
+    height: int
+    qtables: T.Optional[np.ndarray]
+    huffman: T.Optional[np.ndarray]
+    scan: T.Tuple[int, int]
+    exif: bytes
+    ok_for_device: bool
+    reason: str
+
+
+_JPEG_SCAN_END = re.compile(rb"\xff[^\x00]")
+_JPEG_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential",
+                   0xC6: "differential progressive", 0xC7: "differential lossless", 0xC9: "arithmetic coding",
+                   0xCA: "progressive, arithmetic coding", 0xCB: "lossless, arithmetic coding", 0xCD: "differential, arithmetic coding",
+                   0xCE: "differential progressive, arithmetic coding", 0xCF: "differential lossless, arithmetic coding"}
+
+
+def jpeg_parse(data: bytes) -> JpegInfo:
+    """
+    Walks the markers of a JPEG file up to the end of its first scan.  `ok_for_device` says whether rfx_jpeg_decode_u8 takes the
+    file - 8-bit baseline (SOF0), three components Y Cb Cr sampled 2x2, 1x1, 1x1, one interleaved scan with Cb and Cr on the same
+    tables, 8-bit quantisation tables, no restart interval - and `reason` why not: progressive and other processes, greyscale,
+    CMYK, other subsamplings, restart markers, further scans, an Adobe marker (it may declare RGB), a file that ends without
+    EOI, and any marker structure that does not parse.  Never raises for `bytes`.
+    """
+    data = bytes(data)
+    width = height = 0
+    exif = b""
+    qt: T.Dict[int, np.ndarray] = {}
+    ht: T.Dict[int, np.ndarray] = {}
+
+    def result(reason: str, qtables: T.Any = None, huffman: T.Any = None, scan: T.Tuple[int, int] = (0, 0)) -> JpegInfo:
+        return JpegInfo(width, height, qtables, huffman, scan, exif, not reason, reason)
+
+    if data[:2] != b"\xff\xd8":
+        return result("not a JPEG: no SOI")
+    natural = np.asarray(JPEG_NATURAL_ORDER)
+    problems: T.List[str] = []  # what keeps the file on the host, found before the scan
+    frame: T.Optional[T.List[T.Tuple[int, int, int]]] = None  # (id, sampling, table) of every component
+    at, n = 2, len(data)
+    while True:
+        if at + 2 > n or data[at] != 0xFF:
+            return result("malformed: no marker where one must be")
+        marker = data[at + 1]
+        if marker == 0xFF:  # a fill byte
+            at += 1
+            continue
+        if marker == 0x01 or 0xD0 <= marker <= 0xD7:
+            at += 2
+            continue
+        if marker == 0xD9:
+            return result("malformed: EOI before any scan")
+        if at + 4 > n:
+            return result("malformed: truncated marker segment")
+        length = int.from_bytes(data[at + 2:at + 4], "big")
+        if length < 2 or at + 2 + length > n:
+            return result("malformed: marker segment passes the end of the file")
+        seg = data[at + 4:at + 2 + length]
+        at += 2 + length
+        if marker == 0xE1 and seg[:6] == b"Exif\0\0":
+            exif = exif + seg[6:] if exif else seg  # (Pillow joins the payloads of a split EXIF)
+        elif marker == 0xEE and seg[:5] == b"Adobe":
+            problems.append("an Adobe marker: the colour transform is the host's to decide")
+        elif marker == 0xDB:
+            while seg:
+                pq, tq = seg[0] >> 4, seg[0] & 15
+                if pq > 1 or tq > 3 or len(seg) < 1 + 64 * (pq + 1):
+                    return result("malformed: DQT")
+                if pq:
+                    problems.append("a 16-bit quantisation table")
+                    seg = seg[129:]
+                    continue
+                table = np.zeros(64, np.uint16)
+                table[natural] = np.frombuffer(seg, np.uint8, 64, 1)
+                qt[tq] = table
+                seg = seg[65:]
+        elif marker == 0xC4:
+            while seg:
+                if len(seg) < 17:
+                    return result("malformed: DHT")
+                count = sum(seg[1:17])
+                if (seg[0] >> 4) > 1 or (seg[0] & 15) > 3 or count > 256 or len(seg) < 17 + count:
+                    return result("malformed: DHT")
+                code = 0
+                for length_bits, codes in enumerate(seg[1:17], 1):
+                    code = (code + codes) << 1
+                    if code > (2 << length_bits):
+                        return result("malformed: DHT is no prefix code")
+                table = np.zeros(272, np.uint8)
+                table[:16 + count] = np.frombuffer(seg, np.uint8, 16 + count, 1)
+                ht[seg[0]] = table
+                seg = seg[17 + count:]
+        elif marker == 0xDD:
+            if len(seg) != 2:
+                return result("malformed: DRI")
+            if seg != b"\0\0":
+                problems.append("a restart interval")
+        elif marker == 0xC0 or marker in _JPEG_SOF_NAMES:
+            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5] or frame is not None:
+                return result("malformed: SOF")
+            height, width = int.from_bytes(seg[1:3], "big"), int.from_bytes(seg[3:5], "big")
+            frame = [(seg[6 + 3 * i], seg[7 + 3 * i], seg[8 + 3 * i]) for i in range(seg[5])]
+            if marker != 0xC0:
+                problems.append(f"not baseline: {_JPEG_SOF_NAMES[marker]}")
+            elif seg[0] != 8:
+                problems.append(f"{seg[0]}-bit samples")
+            if len(frame) == 1:
+                problems.append("greyscale")
+            elif len(frame) != 3:
+                problems.append(f"{len(frame)} components")
+            elif [c[1] for c in frame] != [0x22, 0x11, 0x11]:
+                problems.append("a subsampling other than 4:2:0")
+            elif [c[0] for c in frame] != [1, 2, 3]:
+                problems.append("component ids other than 1, 2, 3: the colour space is the host's to decide")
+            if width == 0 or height == 0:
+                problems.append("an empty frame or a DNL height")
+        elif marker == 0xDA:
+            break
+    if frame is None:
+        return result("malformed: a scan before any frame")
+    start = at
+    found = _JPEG_SCAN_END.search(data, start)
+    end = found.start() if found else n
+    if problems:
+        return result(problems[0], scan=(start, end))
+    if len(seg) != 10 or seg[0] != 3 or [seg[1], seg[3], seg[5]] != [1, 2, 3]:
+        return result("a scan that does not interleave the three components", scan=(start, end))
+    if seg[7:10] != bytes([0, 63, 0]):
+        return result("a scan that is not a whole sequential one", scan=(start, end))
+    if seg[4] != seg[6] or frame[1][2] != frame[2][2]:
+        return result("Cb and Cr on different tables", scan=(start, end))
+    selectors = (seg[2] >> 4, 0x10 | (seg[2] & 15), seg[4] >> 4, 0x10 | (seg[4] & 15))
+    if any(s not in ht for s in selectors) or frame[0][2] not in qt or frame[1][2] not in qt:
+        return result("malformed: the scan names a table the file does not define", scan=(start, end))
+    if found is None:
+        return result("the file ends without EOI", scan=(start, end))
+    if found.group()[1] != 0xD9:
+        what = "restart markers" if 0xD0 <= found.group()[1] <= 0xD7 else "a marker other than EOI after the first scan"
+        return result(what, scan=(start, end))
+    return result("", np.stack([qt[frame[0][2]], qt[frame[1][2]]]), np.stack([ht[s] for s in selectors]), (start, end))
