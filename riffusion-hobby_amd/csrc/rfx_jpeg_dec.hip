@@ -336,26 +336,6 @@ __global__ void __launch_bounds__(kJpdThreads) jpd_pixels_kernel(int64_t total, 
   rgb[t * 3 + 2] = px[2];
 }
 
-JpdLayout jpeg_decode_workspace_layout(int N, int H, int W, size_t total_scan_bytes) {
-  JpdLayout l{};
-  if (N <= 0 || H <= 0 || W <= 0 || H > kJpgMaxSize || W > kJpgMaxSize) return l;
-  const JpgGeom g = jpg_geom(H, W);
-  size_t at = 0;
-  const auto take = [&at](size_t bytes) {
-    const size_t o = at;
-    at += (bytes + 255) / 256 * 256;
-    return o;
-  };
-  l.unstuffed = take((size_t)jpd_region_offset((int64_t)total_scan_bytes, 0, N) + 64);
-  l.pre = take(((total_scan_bytes + 15) / 16 + 2 * (size_t)N + 2) * sizeof(uint32_t));
-  l.ulen = take((size_t)N * sizeof(uint32_t));
-  l.coef_bytes = (size_t)N * (size_t)g.blocks * 64 * sizeof(int16_t);
-  l.coef = take(l.coef_bytes);
-  l.planes = take((size_t)N * (size_t)jpd_plane_bytes(g));
-  l.total = at;
-  return l;
-}
-
 hipError_t launch_jpeg_decode(const uint8_t* scans, const int64_t* offsets, int64_t max_scan_bytes, size_t total_scan_bytes, int N, int H, int W,
                               const uint16_t* qtables, const uint8_t* huff, uint8_t* rgb, int32_t* status, void* workspace, hipStream_t s) {
   const JpgGeom g = jpg_geom(H, W);

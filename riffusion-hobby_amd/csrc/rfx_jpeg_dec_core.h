@@ -18,6 +18,7 @@
 //     an image of at most two chroma columns (W <= 4) gets h2v2_upsample instead, every chroma sample repeated 2 x 2;
 //   * jdcolor.c's ycc_rgb_convert with its 16-bit fixed-point tables.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rfx_jpeg_core.h"
@@ -47,6 +48,36 @@ constexpr int kJpdLutBits = 9;
 // a peek loads are always inside it.
 RFX_JPG_HD int64_t jpd_region_offset(int64_t off, int64_t off0, int64_t n) { return ((off - off0 + 15) & ~(int64_t)15) + 64 * n; }
 RFX_JPG_HD int64_t jpd_chunk_offset(int64_t off, int64_t off0, int64_t n) { return ((off & ~(int64_t)15) - (off0 & ~(int64_t)15)) / 16 + 2 * n; }
+
+// the planes of one image: Y (16 mcu_h, 16 mcu_w), then Cb and Cr (8 mcu_h, 8 mcu_w) each
+RFX_JPG_HD int64_t jpd_plane_bytes(const JpgGeom& g) { return 384 * g.mcus; }
+
+// the decode's workspace (host arithmetic; the launcher, the C ABI's size query and the host emulator all take it from here):
+// every image's unstuffed region, the chunk tables (`pre`: the zeros dropped before each 16-byte chunk), the unstuffed lengths,
+// the coefficients (N, blocks, 64) int16 and the planes, each on a 256-byte boundary.  total_scan_bytes = offsets[N] - offsets[0].
+struct JpdLayout {
+  size_t unstuffed, pre, ulen, coef, planes, total;  // byte offsets, and the size
+  size_t coef_bytes;                                 // the coefficients: cleared before every decode
+};
+inline JpdLayout jpeg_decode_workspace_layout(int N, int H, int W, size_t total_scan_bytes) {
+  JpdLayout l{};
+  if (N <= 0 || H <= 0 || W <= 0 || H > kJpgMaxSize || W > kJpgMaxSize) return l;
+  const JpgGeom g = jpg_geom(H, W);
+  size_t at = 0;
+  const auto take = [&at](size_t bytes) {
+    const size_t o = at;
+    at += (bytes + 255) / 256 * 256;
+    return o;
+  };
+  l.unstuffed = take((size_t)jpd_region_offset((int64_t)total_scan_bytes, 0, N) + 64);
+  l.pre = take(((total_scan_bytes + 15) / 16 + 2 * (size_t)N + 2) * sizeof(uint32_t));
+  l.ulen = take((size_t)N * sizeof(uint32_t));
+  l.coef_bytes = (size_t)N * (size_t)g.blocks * 64 * sizeof(int16_t);
+  l.coef = take(l.coef_bytes);
+  l.planes = take((size_t)N * (size_t)jpd_plane_bytes(g));
+  l.total = at;
+  return l;
+}
 
 // ---- Huffman tables -------------------------------------------------------------------------------------------------------------
 // jdhuff.c's derived table: maxcode[l] the largest code of length l (-1: none), valoff[l] = index of its first symbol - its
@@ -237,8 +268,6 @@ RFX_JPG_HD void jpd_dequant_idct(int* c, Q q) {
 }
 
 // ---- samples -> pixels ------------------------------------------------------------------------------------------------------------
-// the planes of one image: Y (16 mcu_h, 16 mcu_w), then Cb and Cr (8 mcu_h, 8 mcu_w) each
-RFX_JPG_HD int64_t jpd_plane_bytes(const JpgGeom& g) { return 384 * g.mcus; }
 
 // one chroma sample of output pixel (x, y), plane c (8 mcu_h rows of cstride)
 template <typename Px>

@@ -6,6 +6,7 @@
 #include "rfx_core.h"
 #include "rfx_gen_core.h"
 #include "rfx_fam_core.h"
+#include "rfx_jpeg_dec_core.h"
 
 namespace rfx {
 
@@ -451,11 +452,7 @@ hipError_t launch_jpeg_encode(const uint8_t* rgb, int N, int H, int W, const uin
 // qtables[n] (2, 64) uint16 in natural order and huff[n] (4, 272) uint8; status[n] receives 0 or a kJpd* code.  The caller has
 // checked the sizes (1 .. 65535, N * blocks and N * H * W within one launch, every scan at most kJpdMaxScanBytes);
 // max_scan_bytes is the longest scan, total_scan_bytes = offsets[N] - offsets[0].
-struct JpdLayout {
-  size_t unstuffed, pre, ulen, coef, planes, total;  // byte offsets, and the size
-  size_t coef_bytes;                                 // the coefficients: cleared before every decode
-};
-JpdLayout jpeg_decode_workspace_layout(int N, int H, int W, size_t total_scan_bytes);
+// JpdLayout and jpeg_decode_workspace_layout: rfx_jpeg_dec_core.h (host inline, shared with the host emulator).
 hipError_t launch_jpeg_decode(const uint8_t* scans, const int64_t* offsets, int64_t max_scan_bytes, size_t total_scan_bytes, int N, int H, int W,
                               const uint16_t* qtables, const uint8_t* huff, uint8_t* rgb, int32_t* status, void* workspace, hipStream_t s);
 

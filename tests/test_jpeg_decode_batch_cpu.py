@@ -1,0 +1,574 @@
+"""
+The JPEG decoder's packed batch on the CPU: the cases of tests/test_gpu_jpeg_decode_seams.py - files from tests/jpeg_scan_writer.py
+whose codewords, stuffed bytes and scan ends fall on the seams of the kernels (16-byte chunks shared by images, the 1024-chunk pass
+of the unstuff scan, subsequences, groups, the 1024-MCU pass of the DC scan) - through emu_jpeg_decode_batch, which indexes stages
+1 and 2 as the kernels do, as a shared library and as the stand-alone sanitizer program.  Statuses are the expected ones, pixels
+equal the single-image emulator's of every scan decoded alone, and the coefficients, lengths and unstuffed bytes in the emulated
+workspace equal what the writer wrote.  Every case asserts, from the writer's log or from the bytes, that it reaches its edge.
+The writer itself is checked first: Pillow opens its picture files and the single-image emulator returns Pillow's pixels.
+"""
+import ctypes
+import functools
+import os
+import subprocess
+import typing as T
+
+import numpy as np
+import pytest
+
+import jpeg_scan_writer as jw
+from riffusion import _hip
+from riffusion.util import image_util
+from test_jpeg_cpu import CONTENTS, STEREO_PNG, _golden, _random
+from test_jpeg_decode_cpu import SMALL, _emu, _sanitizer_program, emu_decode, pillow_jpeg, pillow_pixels
+
+
+# ---- the emulator's batch entry ---------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=1)
+def emu():
+    lib = _emu()
+    lib.emu_jpeg_dec_layout.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]
+    lib.emu_jpeg_dec_layout.restype = None
+    for f in (lib.emu_jpeg_dec_region_offset, lib.emu_jpeg_dec_chunk_offset):
+        f.argtypes, f.restype = [ctypes.c_int64] * 3, ctypes.c_int64
+    lib.emu_jpeg_decode_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 5
+    return lib
+
+
+def sub_bits():
+    return emu().emu_jpeg_dec_sub_bits()
+
+
+def group_bits():
+    return emu().emu_jpeg_dec_group() * sub_bits()
+
+
+class Layout(T.NamedTuple):
+    unstuffed: int
+    pre: int
+    ulen: int
+    coef: int
+    planes: int
+    total: int
+    coef_bytes: int
+
+
+def layout(N, H, W, total_scan_bytes):
+    out = np.zeros(7, np.int64)
+    emu().emu_jpeg_dec_layout(N, H, W, total_scan_bytes, out.ctypes.data)
+    return Layout(*(int(v) for v in out))
+
+
+class Case(T.NamedTuple):
+    """one call of the entry.  blocks[n]: what the writer coded (None: a Pillow file or no scan); unstuffed[n]: the writer's
+    stream (None: not known); files[n]: the whole file when Pillow is the reference of its pixels, else None (the emulator is)."""
+    name: str
+    H: int
+    W: int
+    scans: T.List[bytes]
+    blocks: T.List[T.Optional[np.ndarray]]
+    unstuffed: T.List[T.Optional[bytes]]
+    files: T.List[T.Optional[bytes]]
+    qtables: np.ndarray
+    huffman: np.ndarray
+    off0: int
+    status: T.List[int]
+
+    @property
+    def offsets(self):
+        return np.cumsum([self.off0] + [len(s) for s in self.scans]).astype(np.int64)
+
+    def buffer(self, tail=0):
+        """the scans back to back behind off0 bytes of 0xFF; `tail` bytes of 0x00 after offsets[N]"""
+        return b"\xff" * self.off0 + b"".join(self.scans) + b"\0" * tail
+
+
+class Image(T.NamedTuple):
+    scan: bytes
+    blocks: T.Optional[np.ndarray]
+    unstuffed: T.Optional[bytes]
+    file: T.Optional[bytes]
+    qtables: np.ndarray
+    huffman: np.ndarray
+    status: int = 0
+
+
+def case(name, H, W, images, off0=0):
+    return Case(name, H, W, [i.scan for i in images], [i.blocks for i in images], [i.unstuffed for i in images], [i.file for i in images],
+                np.stack([i.qtables for i in images]).astype(np.uint16), np.stack([i.huffman for i in images]).astype(np.uint8), off0,
+                [i.status for i in images])
+
+
+Q75 = functools.lru_cache(maxsize=None)(lambda: _hip.jpeg_quant_tables(75))
+ANNEX_K, STRESS, ONES = jw.annex_k_tables(), jw.stress_tables(), jw.ones_tables()
+# the stress images' quantisation tables: all 1, which keeps jpeg_idct_islow's 32-bit sums of 63 terms of 1023 from overflowing
+# (with a picture's tables they would: libjpeg lets them wrap, the host emulator under a sanitizer must not)
+QONE = np.ones((2, 64), np.uint16)
+
+
+def written(blocks, H, W, huffman, picture=False, qtables=None):
+    """an image from the writer; picture: Pillow decodes the file and is the reference of its pixels"""
+    if qtables is None:
+        qtables = QONE if huffman is not ANNEX_K else Q75()
+    data, log = jw.write_jpeg(blocks, H, W, qtables, huffman)
+    return Image(log.scan, np.asarray(blocks), log.unstuffed, data if picture else None, qtables, huffman), log
+
+
+def pillow_image(data):
+    info = image_util.jpeg_parse(data)
+    assert info.ok_for_device
+    return Image(data[info.scan[0]:info.scan[1]], None, None, data, info.qtables, info.huffman)
+
+
+def mcus_of(H, W):
+    return ((H + 15) // 16) * ((W + 15) // 16)
+
+
+def stress_blocks(H, W, size=10):
+    """every AC term the largest of `size` bits (value bits all 1), DC values 1023 / -1024 in turn per component: differences
+    of +-2047, size 11"""
+    blocks = np.full((6 * mcus_of(H, W), 64), (1 << size) - 1, np.int64)
+    turn = np.zeros(3, np.int64)
+    for b in range(len(blocks)):
+        comp = 0 if b % 6 < 4 else b % 6 - 3
+        blocks[b, 0] = -1024 if turn[comp] & 1 else 1023
+        turn[comp] += 1
+    return blocks
+
+
+def steer(blocks, huffman, targets, pick):
+    """Moves symbols onto chosen bit positions.  For every target in turn: pick(log, target) names a symbol that starts at or
+    after it; as many 26-bit AC symbols before that one as it is bits late (size 10 after a run of 0 in the stress tables)
+    become 25-bit ones (size 9), each of which brings it one bit forward.  Returns the log of the final scan."""
+    blocks, floor = blocks, -1
+    for target in targets:
+        log = jw.write_scan(blocks, huffman)
+        i = pick(log, target)
+        late, j = int(log.pos[i] - target), i
+        assert late >= 0
+        while late:
+            j -= 1
+            assert j >= 0 and log.pos[j] > floor, "not enough symbols to shorten"
+            if log.k[j] > 0 and log.nbits[j] == 26:
+                blocks[log.block[j], log.k[j]] = 511
+                late -= 1
+        floor = target
+    return jw.write_scan(blocks, huffman)
+
+
+def first_long_ac(log, target):
+    return int(np.flatnonzero((log.pos >= target) & (log.k >= 1) & (log.k <= 60) & (log.nbits == 26))[0])
+
+
+def state_at(log, bit):
+    """(block of the MCU, zigzag index) of the first symbol that starts at or after `bit`: the state a subsequence that starts
+    at `bit` is decoded from"""
+    i = int(np.searchsorted(log.pos, bit))
+    return int(log.block[i] % 6), int(log.k[i])
+
+
+# ---- the cases --------------------------------------------------------------------------------------------------------------------
+def e1_eob_only():
+    H = W = 512
+    img, log = written(np.zeros((6 * mcus_of(H, W), 64), np.int64), H, W, ANNEX_K)
+    S = sub_bits()
+    starts = dict(zip(log.pos.tolist(), zip((log.block % 6).tolist(), log.k.tolist())))
+    assert log.total_bits == 32 * 1024 and all(starts[p] == (0, 0) for p in range(0, log.total_bits, S))  # every subsequence starts an MCU
+    assert S % 32 == 0  # ... and holds S / 32 MCUs of six blocks: the block counts the scan adds up
+    return case("E1", H, W, [img])
+
+
+def e2_long_blocks():
+    H, W = 64, 160
+    img, log = written(stress_blocks(H, W), H, W, STRESS)
+    S = sub_bits()
+    ends = log.pos[np.flatnonzero(np.diff(log.block))] // S  # the subsequence in which each block's last symbol starts
+    nsub = -(-log.total_bits // S)
+    assert len(set(range(nsub)) - set(ends.tolist()) - {nsub - 1}) > 0  # a subsequence without a block end
+    assert any(min(state_at(log, i * S)) > 0 for i in range(1, nsub))  # a boundary state with k != 0 and blk != 0
+    return case("E2", H, W, [img])
+
+
+def e3_group_seam(variant):
+    H, W = 64, 304
+    G = group_bits()
+    at = {"starts_at_G-1": G - 1, "ends_at_G": G, "starts_at_G-27": G - 27}[variant]
+    blocks = stress_blocks(H, W)
+    log = steer(blocks, STRESS, [at, at + G], first_long_ac)
+    assert log.total_bits > 2 * G  # three groups
+    for seam in (G, 2 * G):
+        i = int(np.flatnonzero(log.pos == seam + at - G)[0])  # a symbol starts there
+        if variant != "ends_at_G":
+            assert log.nbits[i] == 26
+        assert state_at(log, seam)[1] != 0  # the carried state is inside a block
+    img, log2 = written(blocks, H, W, STRESS)
+    assert log2.scan == log.scan
+    return case("E3_" + variant, H, W, [img])
+
+
+def e4_tail(variant):
+    S, G = sub_bits(), group_bits()
+    H, W = (16, 432) if variant == "multiple_of_G" else (16, 48)
+    blocks = stress_blocks(H, W)
+    unit = G if variant == "multiple_of_G" else S
+    last = lambda log, target: len(log.pos) - 1  # noqa: E731
+    natural = jw.write_scan(blocks, STRESS)
+    # the last symbol (26 bits): 10 bits before a multiple of the unit (16 bits behind it), or 26 bits before (none)
+    back = 10 if variant == "short_tail" else 26
+    target = int(natural.pos[-1] + back) // unit * unit - back
+    log = steer(blocks, STRESS, [target], last)
+    bits = 8 * len(log.unstuffed)
+    if variant == "short_tail":
+        assert 1 <= bits % S <= 26 and log.pos[-1] < bits // S * S  # nothing starts in the last subsequence
+    else:
+        assert bits % unit == 0 and bits == log.total_bits
+    img, _ = written(blocks, H, W, STRESS)
+    return case("E4_" + variant, H, W, [img])
+
+
+def e5_runs():
+    H = W = 32
+    rng = np.random.default_rng(55)
+    images = []
+    for huffman in (ANNEX_K, STRESS):
+        blocks = np.zeros((6 * mcus_of(H, W), 64), np.int64)
+        blocks[:, 0] = rng.integers(-40, 40, len(blocks))
+        for b in range(len(blocks)):
+            kind = b % 6
+            if kind == 0:
+                blocks[b, 63] = rng.choice([-3, 1, 100])  # the only AC term: coefficient 63, after three ZRL and a run of 14
+            elif kind == 1:
+                blocks[b, 1:] = rng.integers(1, 30, 63) * rng.choice([-1, 1], 63)  # every term coded: ends at 63 without EOB
+            elif kind in (2, 3, 4):
+                blocks[b, 16 * (kind - 1)] = rng.choice([-1, 5, -200])  # a lone term at 16, 32, 48
+        img, log = written(blocks, H, W, huffman, qtables=QONE)
+        sym = lambda i: (int(log.block[i]), int(log.k[i]))  # noqa: E731
+        syms = [sym(i) for i in range(len(log.pos))]
+        assert [s for s in syms if s[0] == 0] == [(0, 0), (0, 1), (0, 17), (0, 33), (0, 49)]  # DC, ZRL x 3, 14 / size: no EOB
+        assert [s for s in syms if s[0] == 1][-1] == (1, 63) and syms[syms.index((1, 63)) + 1] == (2, 0)  # ... then the next DC
+        assert [s for s in syms if s[0] == 3] == [(3, 0), (3, 1), (3, 17), (3, 33)]  # DC, ZRL, 15 / size at 32, EOB
+        images.append(img)
+    return case("E5", H, W, images)
+
+
+def e6_dc_extremes():
+    H = W = 32
+    blocks = np.zeros((6 * mcus_of(H, W), 64), np.int64)
+    for rows in (np.arange(len(blocks)) % 6 < 4, np.arange(len(blocks)) % 6 == 4, np.arange(len(blocks)) % 6 == 5):
+        blocks[rows, 0] = 2047 * (1 - np.arange(rows.sum()) % 2)  # 2047, 0, 2047, ... per component: differences of +2047 / -2047
+    img, log = written(blocks, H, W, STRESS)
+    assert (log.nbits[log.k == 0] == 27).all()  # a 16-bit code and 11 value bits, every block
+    return case("E6", H, W, [img])
+
+
+def _picture(tile, huffman=None):
+    tile = np.ascontiguousarray(tile)
+    img, _ = written(jw.picture_blocks(tile, Q75()), tile.shape[0], tile.shape[1], ANNEX_K if huffman is None else huffman, picture=True)
+    return img
+
+
+def e7_mixed_tables():
+    H, W = 64, 96
+    crop = _golden(STEREO_PNG)[200:200 + H, 300:300 + W]
+    stress, _ = written(stress_blocks(H, W), H, W, STRESS)
+    optimised = pillow_image(pillow_jpeg(crop[::-1], 75, optimize=True))
+    assert optimised.huffman.tobytes() not in (ANNEX_K.tobytes(), STRESS.tobytes())
+    return case("E7", H, W, [_picture(crop), stress, optimised])
+
+
+def u1_pair_on_a_chunk_seam(pattern):
+    H, W = 16, 48
+    img, log = written(stress_blocks(H, W), H, W, STRESS)
+    want = {"FF|00": b"\xff\x00", "FF00|FF00": b"\xff\x00\xff\x00"}[pattern]
+    i = img.scan.index(want, 16)
+    off0 = (15 - i) % 16 if pattern == "FF|00" else (14 - i) % 16
+    c = case("U1_" + pattern, H, W, [img], off0)
+    buf = c.buffer()
+    seam = (off0 + i + 15) // 16 * 16
+    if pattern == "FF|00":
+        assert buf[seam - 1] == 0xFF and buf[seam] == 0
+    else:
+        assert buf[seam - 2:seam + 2] == b"\xff\x00\xff\x00"
+    return c
+
+
+def u2_pass_seam():
+    H, W = 32, 96
+    chunk, per_pass = 16, emu().emu_jpeg_dec_scan_threads()
+    seam = chunk * per_pass  # relative to lo & ~15
+    for seed in range(64):  # the sizes of the first blocks' terms move the bytes: look for a pair whose 0xFF is the last byte of the first pass
+        blocks = stress_blocks(H, W)
+        blocks[:12, 1:] = (1 << np.random.default_rng(seed).integers(1, 11, (12, 63))) - 1
+        img, log = written(blocks, H, W, STRESS)
+        found = [i for i in range(seam - 16, seam - 1) if img.scan[i:i + 2] == b"\xff\x00"]
+        if len(img.scan) > seam + 64 and found:
+            break
+    else:
+        raise AssertionError("no seed puts a stuffed pair on the pass seam")
+    off0 = seam - 1 - found[-1]
+    c = case("U2", H, W, [img], off0)
+    buf = c.buffer()
+    assert 1 <= off0 <= 15 and buf[seam - 1] == 0xFF and buf[seam] == 0  # lo unaligned; the pair straddles the seam
+    assert b"\xff\x00" in buf[off0:seam - 1] and b"\xff\x00" in buf[seam + 1:]  # ... and stuffed bytes on both sides
+    return c
+
+
+@functools.lru_cache(maxsize=1)
+def _abc():
+    """16 x 16: A ends FF 00 (its last value bits and the padding are 1s); B begins 00 (luma DC "00", AC 0/1 "00", a 0 value
+    bit, twice); C is ordinary"""
+    H = W = 16
+    a, _ = written(stress_blocks(H, W), H, W, STRESS)
+    blocks = np.zeros((6, 64), np.int64)
+    blocks[0, 1:9] = -1
+    blocks[1:, 0] = [3, -7, 20, 5, -9]
+    b, _ = written(blocks, H, W, ANNEX_K)
+    c = _picture(_golden(STEREO_PNG)[100:116, 40:56])
+    assert a.scan.endswith(b"\xff\x00") and b.scan[0] == 0
+    return a, b, c
+
+
+def u3_neighbours(order, seam_at):
+    a, b, c = _abc()
+    if order == "A'BC":
+        a = a._replace(scan=a.scan[:-1], status=1)  # a dangling 0xFF; the stream without its stuffed zeros is A's
+        assert a.scan[-1] == 0xFF
+    images = {"ABC": [a, b, c], "BAC": [b, a, c], "A'BC": [a, b, c]}[order]
+    end_of_a = sum(len(i.scan) for i in images[:images.index(a) + 1])
+    off0 = (seam_at - end_of_a) % 16
+    cs = case(f"U3_{order}_{seam_at}", 16, 16, images, off0)
+    assert (off0 + end_of_a) % 16 == seam_at  # A's last byte and its neighbour's first: in one chunk (8) or in two (0)
+    return cs
+
+
+def u4_first_offset(off0):
+    a, b, c = _abc()
+    tail = a._replace(scan=a.scan[:-1], status=1)  # ends 0xFF: the 0x00 behind offsets[N] is not its stuffed zero
+    cs = case(f"U4_{off0}", 16, 16, [b, c, tail], off0)
+    buf = cs.buffer(tail=24)
+    assert (off0 == 0 or buf[off0 - 1] == 0xFF) and buf[off0] == 0 and buf[cs.offsets[-1] - 1] == 0xFF and buf[cs.offsets[-1]] == 0
+    return cs
+
+
+def u5_empty_scan(where):
+    a, b, c = _abc()
+    d, _ = written(stress_blocks(16, 16, size=3), 16, 16, STRESS)
+    images = [a, b, c, d]
+    images.insert(where, Image(b"", None, b"", None, Q75(), ANNEX_K, status=6))
+    cs = case(f"U5_{where}", 16, 16, images, 3)
+    assert cs.offsets[where] == cs.offsets[where + 1]
+    return cs
+
+
+def u6_mostly_stuffing():
+    H = W = 16
+    blocks = np.ones((6, 64), np.int64)
+    blocks[:, 0] = [1, 2, 3, 4, 1, 1]  # every difference +1
+    img, log = written(blocks, H, W, ONES)
+    assert img.scan.count(b"\xff\x00") >= 0.45 * len(img.scan)
+    return case("U6", H, W, [img], 7)
+
+
+def u7_many_tiny():
+    H = W = 8
+    rng = np.random.default_rng(77)
+    images = []
+    for n in range(300):
+        blocks = np.zeros((6, 64), np.int64)
+        blocks[:4, 0] = n - 150  # a DC of its own: two images swapped show
+        if n % 3 == 2:
+            blocks[:, 1:1 + n % 4] = rng.integers(-7, 8, (6, n % 4))
+        blocks[4:, 0] = rng.integers(-20, 20, 2)
+        images.append(written(blocks, H, W, ANNEX_K)[0])
+    cs = case("U7", H, W, images, 9)
+    sizes, off = np.diff(cs.offsets), cs.offsets
+    assert sizes.min() >= 4 and sizes.max() <= 40 and len({i.blocks[0, 0] for i in images}) == 300
+    assert any(off[n] // 16 == (off[n + 2] - 1) // 16 for n in range(298))  # two whole images inside one chunk
+    assert any(off[n + 1] % 16 and off[n + 1] // 16 == off[n + 3] // 16 for n in range(297))  # a chunk shared by four
+    return cs
+
+
+def d1_dc_passes(W):
+    H = 16
+    mcus = mcus_of(H, W)
+    images = []
+    for seed in (1, 2):
+        rng = np.random.default_rng(seed * 1000 + W)
+        blocks = np.zeros((6 * mcus, 64), np.int64)
+        for comp, rows in enumerate((np.arange(6 * mcus) % 6 < 4, np.arange(6 * mcus) % 6 == 4, np.arange(6 * mcus) % 6 == 5)):
+            n = int(rows.sum())
+            steps = rng.integers(1, 6, n) * rng.choice([-1, 1], n)
+            walk = np.zeros(n, np.int64)
+            v = 0
+            for i, s in enumerate(steps.tolist()):  # a walk that never stands still and stays where samples do not clip
+                v = v + s if abs(v + s) <= 50 else v - s
+                walk[i] = v
+            blocks[rows, 0] = walk
+        img, log = written(blocks, H, W, ANNEX_K, picture=True)
+        assert mcus > 1024 and (np.diff(blocks[np.arange(6 * mcus) % 6 < 4, 0]) != 0).all() and blocks[0, 0] != 0
+        images.append(img)
+    assert mcus in (1025, 2049)
+    return case(f"D1_{W}", H, W, images, 5)
+
+
+def p1_small(h, w):
+    return case(f"P1_{h}x{w}", h, w, [pillow_image(pillow_jpeg(_random(h, w), q)) for q in (50, 90)], 1)
+
+
+BUILDERS = {
+    "E1": e1_eob_only,
+    "E2": e2_long_blocks,
+    **{f"E3_{v}": functools.partial(e3_group_seam, v) for v in ("starts_at_G-1", "ends_at_G", "starts_at_G-27")},
+    **{f"E4_{v}": functools.partial(e4_tail, v) for v in ("short_tail", "multiple_of_S", "multiple_of_G")},
+    "E5": e5_runs,
+    "E6": e6_dc_extremes,
+    "E7": e7_mixed_tables,
+    **{f"U1_{p}": functools.partial(u1_pair_on_a_chunk_seam, p) for p in ("FF|00", "FF00|FF00")},
+    "U2": u2_pass_seam,
+    **{f"U3_{o}_{s}": functools.partial(u3_neighbours, o, s) for o in ("ABC", "BAC", "A'BC") for s in (8, 0)},
+    **{f"U4_{o}": functools.partial(u4_first_offset, o) for o in (0, 16, 5, 37)},
+    **{f"U5_{w}": functools.partial(u5_empty_scan, w) for w in (0, 2, 4)},
+    "U6": u6_mostly_stuffing,
+    "U7": u7_many_tiny,
+    **{f"D1_{w}": functools.partial(d1_dc_passes, w) for w in (16400, 32784)},
+    **{f"P1_{h}x{w}": functools.partial(p1_small, h, w) for h, w in SMALL},
+}
+
+
+@functools.lru_cache(maxsize=None)
+def build_case(name) -> Case:
+    c = BUILDERS[name]()
+    assert c.name == name
+    return c
+
+
+# ---- decoding a case on the host --------------------------------------------------------------------------------------------------
+class Decoded(T.NamedTuple):
+    status: np.ndarray
+    rgb: np.ndarray
+    workspace: np.ndarray
+
+
+def emu_batch(c: Case) -> Decoded:
+    scans = np.frombuffer(c.buffer(), np.uint8).copy()  # exactly offsets[N] bytes
+    off, N = c.offsets, len(c.scans)
+    lay = layout(N, c.H, c.W, int(off[-1] - off[0]))
+    rgb, status = np.zeros((N, c.H, c.W, 3), np.uint8), np.full(N, -1, np.int32)
+    workspace = np.full(lay.total, 0xA5, np.uint8)  # whatever the device's memory held before
+    qt, huff = np.ascontiguousarray(c.qtables), np.ascontiguousarray(c.huffman)
+    rc = emu().emu_jpeg_decode_batch(scans.ctypes.data, off.ctypes.data, N, c.H, c.W, qt.ctypes.data, huff.ctypes.data, rgb.ctypes.data,
+                                     status.ctypes.data, workspace.ctypes.data)
+    assert rc == 0
+    return Decoded(status, rgb, workspace)
+
+
+def sanitized_batch(c: Case, tmp_path) -> Decoded:
+    off, N = c.offsets, len(c.scans)
+    src, dst = os.path.join(tmp_path, "case.bin"), os.path.join(tmp_path, "out.bin")
+    with open(src, "wb") as f:
+        f.write(np.array([N, c.H, c.W], np.int32).tobytes() + off.tobytes() + np.ascontiguousarray(c.qtables).tobytes())
+        f.write(np.ascontiguousarray(c.huffman).tobytes() + c.buffer())
+    done = subprocess.run([_sanitizer_program(), "batch", src, dst], capture_output=True, text=True)
+    assert done.returncode == 0, done.stderr[-2000:]  # a sanitizer report ends the program with another code
+    assert done.stdout.strip() == "batch 0"
+    out = np.fromfile(dst, np.uint8)
+    pixels = N * c.H * c.W * 3
+    return Decoded(out[:4 * N].view(np.int32), out[4 * N:4 * N + pixels].reshape(N, c.H, c.W, 3), out[4 * N + pixels:])
+
+
+@functools.lru_cache(maxsize=None)
+def alone(scan, H, W, qtables, huffman):
+    """(status, pixels) of one scan through the single-image emulator"""
+    buf, out = np.frombuffer(scan, np.uint8).copy(), np.zeros((H, W, 3), np.uint8)
+    qt, huff = np.frombuffer(qtables, np.uint16).copy(), np.frombuffer(huffman, np.uint8).copy()
+    return _emu().emu_jpeg_decode_u8(buf.ctypes.data, buf.size, H, W, qt.ctypes.data, huff.ctypes.data, out.ctypes.data, None), out
+
+
+def check_stages(c: Case, got: Decoded, stages=("unstuffed", "coef"), who="emulator"):
+    """the lengths and unstuffed regions, then the coefficients, of a workspace against what the writer wrote"""
+    off, N = c.offsets, len(c.scans)
+    lay = layout(N, c.H, c.W, int(off[-1] - off[0]))
+    ws = np.asarray(got.workspace)
+    assert ws.size == lay.total
+    if "unstuffed" in stages:
+        ulen = ws[lay.ulen:lay.ulen + 4 * N].view(np.uint32)
+        for n in range(N):
+            if c.unstuffed[n] is None:
+                continue
+            assert ulen[n] == len(c.unstuffed[n]), f"{c.name}: {who}: unstuff scan stage: ulen[{n}] = {ulen[n]}, written {len(c.unstuffed[n])}"
+            at = lay.unstuffed + emu().emu_jpeg_dec_region_offset(int(off[n]), int(off[0]), n)
+            assert ws[at:at + ulen[n]].tobytes() == c.unstuffed[n], f"{c.name}: {who}: unstuff stage: the region of image {n} differs"
+    if "coef" in stages:
+        per = 6 * mcus_of(c.H, c.W) * 64
+        coef = ws[lay.coef:lay.coef + lay.coef_bytes].view(np.int16).reshape(N, per)
+        for n in range(N):
+            if c.blocks[n] is not None and c.status[n] == 0:
+                assert np.array_equal(coef[n], jw.natural_coefficients(c.blocks[n]).ravel()), \
+                    f"{c.name}: {who}: entropy / DC scan stage: the coefficients of image {n} differ"
+
+
+# ---- the writer, before it is a reference -----------------------------------------------------------------------------------------
+PICTURES = {"stereo_crop_64x96": lambda: _golden(STEREO_PNG)[200:264, 300:396], "og_beat_crop_23x37": lambda: CONTENTS["og_beat"]()[40:63, 100:137],
+            "stereo_crop_9x17": lambda: _golden(STEREO_PNG)[300:309, 17:34], "og_beat_crop_128x80": lambda: CONTENTS["og_beat"]()[256:384, 200:280]}
+
+
+@pytest.mark.parametrize("name", sorted(PICTURES))
+@pytest.mark.parametrize("tables", ["annex_k", "stress"])
+def test_pillow_and_the_emulator_decode_the_writers_pictures(name, tables):
+    tile = np.ascontiguousarray(PICTURES[name]())
+    blocks = jw.picture_blocks(tile, Q75())
+    data, log = jw.write_jpeg(blocks, tile.shape[0], tile.shape[1], Q75(), ANNEX_K if tables == "annex_k" else STRESS)
+    want = pillow_pixels(data)
+    assert want.shape == tile.shape and np.abs(want.astype(int) - tile).mean() < 12  # the picture, not noise
+    info = image_util.jpeg_parse(data)
+    assert info.ok_for_device and data[info.scan[0]:info.scan[1]] == log.scan and np.array_equal(info.qtables, Q75())
+    status, got, _, _ = emu_decode(data)
+    assert status == 0 and np.array_equal(got, want)
+    assert log.unstuffed.replace(b"\xff", b"\xff\x00") == log.scan and 0 <= 8 * len(log.unstuffed) - log.total_bits < 8
+
+
+def test_the_writer_refuses_values_outside_baseline():
+    blocks = np.zeros((6, 64), np.int64)
+    for at, value in ((0, 2048), (0, -2048), (5, 1024), (63, -1024)):
+        bad = blocks.copy()
+        bad[2, at] = value
+        with pytest.raises(ValueError):
+            jw.write_jpeg(bad, 16, 16, Q75(), ANNEX_K)
+    blocks[2, 0], blocks[3, 0], blocks[2, 5] = 1023, -1024, -1023  # differences of +1023, -2047
+    jw.write_jpeg(blocks, 16, 16, Q75(), ANNEX_K)
+
+
+def test_the_stress_tables_are_what_the_cases_need():
+    for tables in (STRESS, ONES, ANNEX_K):
+        for t in tables:
+            jw.canonical_codes(t)  # a prefix code
+    dc, ac = jw.canonical_codes(STRESS[0]), jw.canonical_codes(STRESS[1])
+    assert ac[0xFA][1] == 16 and ac[0x0A][1] == 16 and dc[11][1] == 16 == max(length for _, length in dc.values())
+    lengths = {length for _, length in ac.values()}
+    assert 9 in lengths and 10 in lengths
+    # the decoder's derivation accepts them: an EOB-only image decodes with status 0
+    for tables in (STRESS, ONES):
+        img, _ = written(np.zeros((6, 64), np.int64), 16, 16, tables)
+        assert alone(img.scan, 16, 16, img.qtables.tobytes(), tables.tobytes())[0] == 0
+
+
+# ---- the batch path ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(BUILDERS))
+def test_batch_emulation_equals_the_writer_and_the_single_image_emulator(name, tmp_path):
+    c = build_case(name)
+    for who, got in (("emulator", emu_batch(c)), ("sanitizer program", sanitized_batch(c, str(tmp_path)))):
+        assert got.status.tolist() == c.status, (name, who)
+        check_stages(c, got, who=who)
+        for n, scan in enumerate(c.scans):
+            status, want = alone(scan, c.H, c.W, c.qtables[n].tobytes(), c.huffman[n].tobytes())
+            assert status == c.status[n], (name, n)
+            if status == 0:
+                assert np.array_equal(got.rgb[n], want), (name, who, n)
+                if c.files[n] is not None:
+                    assert np.array_equal(want, pillow_pixels(c.files[n])), (name, n)
+
+
+@pytest.mark.parametrize("off0", [16, 5, 37])
+def test_first_offset_changes_nothing(off0):
+    base, moved = emu_batch(build_case("U4_0")), emu_batch(build_case(f"U4_{off0}"))
+    assert np.array_equal(base.status, moved.status) and np.array_equal(base.rgb, moved.rgb)
