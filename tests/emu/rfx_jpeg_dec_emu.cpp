@@ -8,7 +8,8 @@
 // (RFX_JPD_EMU_MAIN: a stand-alone program) sees any read past them.  emu_jpeg_decode_batch is the packed batch: N scans back to
 // back at any byte offsets, stages 1 and 2 indexed as the two unstuff kernels index them (the aligned first chunk, the chunk
 // tables at jpd_chunk_offset, the regions at jpd_region_offset, the bytes outside [lo, hi) masked, the 1024-chunk passes and
-// their carry) inside one workspace of the device's layout, so that the regions can be compared with the device's.
+// their carry, the copy's grid of min(chunk groups of the longest scan, 64) workgroups whose threads stride over an image's
+// chunks) inside one workspace of the device's layout, so that the regions can be compared with the device's.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -21,12 +22,15 @@ using namespace rfx;
 namespace {
 constexpr int kEmuChunk = 16;           // rfx_jpeg_dec.hip's kJpdChunk
 constexpr int kEmuScanThreads = 1024;   // ... and kJpdScanThreads: the chunks of one pass of the unstuff scan
+constexpr int kEmuThreads = 256;        // ... kJpdThreads: the threads of one workgroup of jpd_unstuff_kernel
+constexpr int kEmuUnstuffGridY = 64;    // ... and the most workgroups launch_jpeg_decode gives one image there
 }  // namespace
 
 namespace {
 
 // stages 3 .. 7 of one image: words - its unstuffed region (the stream of ulen bytes, rounded up to a word, and two words more),
 // coef (blocks, 64) and planes (jpd_plane_bytes) - its parts of the workspace.  status: what stages 1 and 2 found.
+// With several causes the status is the largest of them, as the kernels' atomicMax leaves it.
 int decode_unstuffed(const uint32_t* words, int64_t ulen, int status, int H, int W, const uint16_t* qtables, const uint8_t* huff, int16_t* coef,
                      uint8_t* planes, uint8_t* rgb, int32_t* info) {
   const JpgGeom g = jpg_geom(H, W);
@@ -37,14 +41,17 @@ int decode_unstuffed(const uint32_t* words, int64_t ulen, int status, int H, int
   };
   // 3. tables
   std::vector<JpdHuff> tables(4);
+  bool bad_table = false;
+  const auto flag = [&status](int cause) { status = cause > status ? cause : status; };
   for (int t = 0; t < 4; ++t) {
-    if (!jpd_huff_derive(huff + t * kJpdHuffBytes, &tables[t])) status = kJpdBadTable;
+    if (!jpd_huff_derive(huff + t * kJpdHuffBytes, &tables[t])) bad_table = true;
     std::memcpy(tables[t].huffval, huff + t * kJpdHuffBytes + 16, 256);
   }
   std::memset(coef, 0, (size_t)g.blocks * 64 * sizeof(int16_t));
   const int64_t nsub = ((int64_t)total_bits + kJpdSubBits - 1) / kJpdSubBits;
   int32_t rounds_max = 0, rounds_sum = 0, groups = 0;
-  if (status != kJpdBadTable) {
+  if (bad_table) flag(kJpdBadTable);  // (the entropy kernel returns here: no coefficient is written)
+  if (!bad_table) {
     for (int t = 0; t < 4; ++t)
       for (int i = 0; i < (1 << kJpdLutBits); ++i) tables[t].lut[i] = jpd_huff_lut_entry(tables[t], i);
     // 4. the groups of subsequences
@@ -103,13 +110,13 @@ int decode_unstuffed(const uint32_t* words, int64_t ulen, int status, int H, int
         int err;
         const JpdState end = jpd_decode_span<false>(tables.data(), peek, in, span_end(i), total_bits, room,
                                              [&](int64_t b, int k, int v) { out[b * 64 + kJpgNatural[k]] = (int16_t)v; }, &nb, &err);
-        if (err != kJpdOk && status == kJpdOk) status = err;
-        if (err == kJpdOk && nb == room && total_bits - end.p > 7 && status == kJpdOk) status = kJpdLeftOver;
+        if (err != kJpdOk) flag(err);
+        else if (nb == room && total_bits - end.p > 7) flag(kJpdLeftOver);
       }
       block_base = at;
       carry = exit_state[n - 1];
     }
-    if (block_base < g.blocks && status == kJpdOk) status = kJpdLeftOver;
+    if (block_base < g.blocks) flag(kJpdLeftOver);
   }
   if (info) {
     info[0] = rounds_max;
@@ -195,6 +202,8 @@ int emu_jpeg_decode_u8(const uint8_t* scan_in, int64_t scan_bytes, int H, int W,
 }
 
 int emu_jpeg_dec_scan_threads() { return kEmuScanThreads; }
+// the chunks one trip of jpd_unstuff_kernel's grid copies at most: an image with more sends its threads round again
+int emu_jpeg_dec_unstuff_trip_chunks() { return kEmuUnstuffGridY * kEmuThreads; }
 
 // the six offsets of the device's workspace and its size: out[0 .. 6] = unstuffed, pre, ulen, coef, planes, total, coef_bytes
 void emu_jpeg_dec_layout(int N, int H, int W, int64_t total_scan_bytes, int64_t* out) {
@@ -214,8 +223,14 @@ int64_t emu_jpeg_dec_chunk_offset(int64_t off, int64_t off0, int64_t n) { return
 int emu_jpeg_decode_batch(const uint8_t* scans, const int64_t* offsets, int N, int H, int W, const uint16_t* qtables, const uint8_t* huff,
                           uint8_t* rgb, int32_t* status, uint8_t* workspace) {
   if (N < 1 || H < 1 || W < 1 || H > kJpgMaxSize || W > kJpgMaxSize || offsets[0] < 0) return -1;
-  for (int n = 0; n < N; ++n)
+  int64_t longest = 0;
+  for (int n = 0; n < N; ++n) {
     if (offsets[n + 1] < offsets[n] || offsets[n + 1] - offsets[n] > kJpdMaxScanBytes) return -1;
+    longest = offsets[n + 1] - offsets[n] > longest ? offsets[n + 1] - offsets[n] : longest;
+  }
+  // launch_jpeg_decode's gridDim.y of jpd_unstuff_kernel: the call's longest scan decides it for every image
+  const int64_t chunk_groups = (longest / kEmuChunk + 2 + kEmuThreads - 1) / kEmuThreads;
+  const int64_t grid_y = chunk_groups < kEmuUnstuffGridY ? chunk_groups : kEmuUnstuffGridY;
   const JpgGeom g = jpg_geom(H, W);
   const int64_t total = offsets[N], off0 = offsets[0];
   const JpdLayout l = jpeg_decode_workspace_layout(N, H, W, (size_t)(total - off0));
@@ -268,18 +283,19 @@ int emu_jpeg_decode_batch(const uint8_t* scans, const int64_t* offsets, int N, i
     const int64_t lo = offsets[n], hi = offsets[n + 1], first = lo & ~(int64_t)15;
     const int64_t chunks = (hi - first + kEmuChunk - 1) / kEmuChunk;
     const uint32_t* p = pre + jpd_chunk_offset(lo, off0, n);
-    // 2. jpd_unstuff_kernel
+    // 2. jpd_unstuff_kernel: every thread of the image's grid_y workgroups, striding by the grid
     uint8_t* out = unstuffed + jpd_region_offset(lo, off0, n);
-    for (int64_t c = 0; c < chunks; ++c) {
-      const int64_t at = first + c * kEmuChunk;
-      const Chunk v = load_chunk(at, lo, hi);
-      int64_t o = (at > lo ? at - lo : 0) - (int64_t)p[c];
-      uint8_t before = v.prev;
-      for (int i = 0; i < kEmuChunk; ++i) {
-        if (at + i >= lo && at + i < hi && !(before == 0xFF && v.b[i] == 0)) out[o++] = v.b[i];
-        before = v.b[i];
+    for (int64_t thread = 0; thread < grid_y * kEmuThreads; ++thread)
+      for (int64_t c = thread; c < chunks; c += grid_y * kEmuThreads) {
+        const int64_t at = first + c * kEmuChunk;
+        const Chunk v = load_chunk(at, lo, hi);
+        int64_t o = (at > lo ? at - lo : 0) - (int64_t)p[c];
+        uint8_t before = v.prev;
+        for (int i = 0; i < kEmuChunk; ++i) {
+          if (at + i >= lo && at + i < hi && !(before == 0xFF && v.b[i] == 0)) out[o++] = v.b[i];
+          before = v.b[i];
+        }
       }
-    }
     // 3 .. 7: the image's region as the entropy kernel loads it - words past the region read as 0, the bytes of its last
     // words that stage 2 did not write as they are
     const int64_t region_words = ((int64_t)ulen[n] + 3) / 4 + 2;

@@ -6,6 +6,9 @@ of the unstuff scan, subsequences, groups, the 1024-MCU pass of the DC scan) - t
 equal the single-image emulator's of every scan decoded alone, and the coefficients, lengths and unstuffed bytes in the emulated
 workspace equal what the writer wrote.  Every case asserts, from the writer's log or from the bytes, that it reaches its edge.
 The writer itself is checked first: Pillow opens its picture files and the single-image emulator returns Pillow's pixels.
+The large cases L1-L6 are the CPU twins of tests/test_gpu_jpeg_decode_large.py: scans longer than one trip of the copy kernel's
+grid and than eight entropy groups, 64 images in one call, bad Huffman tables, the refusals before launch, the workspace's
+previous contents.  Their builders assert their edges here, where no GPU is needed, and print what they reach.
 """
 import ctypes
 import functools
@@ -20,7 +23,7 @@ import jpeg_scan_writer as jw
 from riffusion import _hip
 from riffusion.util import image_util
 from test_jpeg_cpu import CONTENTS, STEREO_PNG, _golden, _random
-from test_jpeg_decode_cpu import SMALL, _emu, _sanitizer_program, emu_decode, pillow_jpeg, pillow_pixels
+from test_jpeg_decode_cpu import DAMAGE_TILES, SMALL, _emu, _sanitizer_program, damaged_scans, emu_decode, pillow_jpeg, pillow_pixels
 
 
 # ---- the emulator's batch entry ---------------------------------------------------------------------------------------------------
@@ -31,6 +34,7 @@ def emu():
     lib.emu_jpeg_dec_layout.restype = None
     for f in (lib.emu_jpeg_dec_region_offset, lib.emu_jpeg_dec_chunk_offset):
         f.argtypes, f.restype = [ctypes.c_int64] * 3, ctypes.c_int64
+    lib.emu_jpeg_dec_unstuff_trip_chunks.restype = ctypes.c_int
     lib.emu_jpeg_decode_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 5
     return lib
 
@@ -449,12 +453,12 @@ class Decoded(T.NamedTuple):
     workspace: np.ndarray
 
 
-def emu_batch(c: Case) -> Decoded:
+def emu_batch(c: Case, fill=0xA5) -> Decoded:
     scans = np.frombuffer(c.buffer(), np.uint8).copy()  # exactly offsets[N] bytes
     off, N = c.offsets, len(c.scans)
     lay = layout(N, c.H, c.W, int(off[-1] - off[0]))
     rgb, status = np.zeros((N, c.H, c.W, 3), np.uint8), np.full(N, -1, np.int32)
-    workspace = np.full(lay.total, 0xA5, np.uint8)  # whatever the device's memory held before
+    workspace = np.full(lay.total, fill, np.uint8)  # whatever the device's memory held before
     qt, huff = np.ascontiguousarray(c.qtables), np.ascontiguousarray(c.huffman)
     rc = emu().emu_jpeg_decode_batch(scans.ctypes.data, off.ctypes.data, N, c.H, c.W, qt.ctypes.data, huff.ctypes.data, rgb.ctypes.data,
                                      status.ctypes.data, workspace.ctypes.data)
@@ -553,9 +557,9 @@ def test_the_stress_tables_are_what_the_cases_need():
 
 
 # ---- the batch path ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(BUILDERS))
-def test_batch_emulation_equals_the_writer_and_the_single_image_emulator(name, tmp_path):
-    c = build_case(name)
+def check_on_the_emulator(c: Case, tmp_path):
+    """the case through the batch emulator and the sanitizer program: statuses, stages, pixels"""
+    name = c.name
     for who, got in (("emulator", emu_batch(c)), ("sanitizer program", sanitized_batch(c, str(tmp_path)))):
         assert got.status.tolist() == c.status, (name, who)
         check_stages(c, got, who=who)
@@ -568,7 +572,243 @@ def test_batch_emulation_equals_the_writer_and_the_single_image_emulator(name, t
                     assert np.array_equal(want, pillow_pixels(c.files[n])), (name, n)
 
 
+@pytest.mark.parametrize("name", list(BUILDERS))
+def test_batch_emulation_equals_the_writer_and_the_single_image_emulator(name, tmp_path):
+    check_on_the_emulator(build_case(name), tmp_path)
+
+
 @pytest.mark.parametrize("off0", [16, 5, 37])
 def test_first_offset_changes_nothing(off0):
     base, moved = emu_batch(build_case("U4_0")), emu_batch(build_case(f"U4_{off0}"))
     assert np.array_equal(base.status, moved.status) and np.array_equal(base.rgb, moved.rgb)
+
+
+# ---- the large cases (tests/test_gpu_jpeg_decode_large.py runs the same ones on the device) ---------------------------------------
+# jpd_unstuff_kernel runs min(chunk groups of the call's longest scan, 64) workgroups of 256 threads per image, a 16-byte chunk
+# per thread: a scan of more bytes than this sends the threads round their loop a second time
+UNSTUFF_TRIP_BYTES = 64 * 256 * 16
+MANY_GROUPS = 8  # entropy groups (of 256 subsequences) a long scan must exceed
+MAX_SCAN_BYTES = (1 << 28) - 64  # kJpdMaxScanBytes
+
+
+def subsequences(unstuffed_bytes):
+    return -(-8 * unstuffed_bytes // sub_bits())
+
+
+def reach(c: Case, quiet=False):
+    """per image (scan bytes, trips of the copy kernel's grid, entropy groups), printed with the call's chunk groups"""
+    longest = max(len(s) for s in c.scans)
+    chunk_groups = (longest // 16 + 2 + 255) // 256
+    per = []
+    for n, scan in enumerate(c.scans):
+        unstuffed = c.unstuffed[n] if c.unstuffed[n] is not None else scan.replace(b"\xff\x00", b"\xff")
+        chunks = -(-(c.offsets[n + 1] - (c.offsets[n] & ~15)) // 16)
+        per.append((len(scan), int(-(-chunks // (min(chunk_groups, 64) * 256))), -(-subsequences(len(unstuffed)) // 256)))
+    if not quiet:
+        shown = per if len(per) <= 8 else f"{len(per)} images, the largest of each: {tuple(max(v) for v in zip(*per))}"
+        print(f"{c.name}: chunk groups of the call {chunk_groups} (the grid takes {min(chunk_groups, 64)});",
+              "per image (scan bytes, trips of the copy grid, entropy groups):", shown)
+    return per
+
+
+def assert_long(c: Case, n):
+    """image n of the case is a long scan: a second trip of the copy kernel's grid and more than eight entropy groups"""
+    assert emu().emu_jpeg_dec_unstuff_trip_chunks() * 16 == UNSTUFF_TRIP_BYTES and emu().emu_jpeg_dec_group() == 256
+    scan, unstuffed = c.scans[n], c.unstuffed[n]
+    assert len(scan) > 64 * 256 * 16 and subsequences(len(unstuffed)) > 8 * 256
+    _, trips, groups = reach(c, quiet=True)[n]
+    assert trips >= 2 and groups > MANY_GROUPS
+    assert min(len(s) for s in c.scans) < 4096  # ... beside an image that idles through that grid
+
+
+def sound_pillow_image(data):
+    """a Pillow file whose scan is sound: its unstuffed stream is the scan without the zeros behind 0xFF"""
+    img = pillow_image(data)
+    assert b"\xff" not in img.scan.replace(b"\xff\x00", b"")
+    return img._replace(unstuffed=img.scan.replace(b"\xff\x00", b"\xff"))
+
+
+@functools.lru_cache(maxsize=1)
+def _l1_images():
+    size = 384
+    noise = _random(size, size)
+    return size, [sound_pillow_image(pillow_jpeg(noise, 100)), sound_pillow_image(pillow_jpeg(noise, 75)),
+                  sound_pillow_image(pillow_jpeg(np.zeros((size, size, 3), np.uint8), 100))]
+
+
+def l1_long_pillow_scan(where):
+    size, images = _l1_images()
+    c = case("L1_" + where, size, size, images if where == "first" else images[::-1], 0 if where == "first" else 9)
+    assert_long(c, 0 if where == "first" else 2)
+    assert len({i.qtables.tobytes() for i in images}) == 2  # quality 100 and quality 75 in one call
+    return c
+
+
+def l2_long_writer_scan():
+    H = W = 240  # the smallest (from 240 x 240 in steps of 16) whose stress scan is longer than one trip of the copy grid
+    long_, log = written(stress_blocks(H, W), H, W, STRESS)
+    short, _ = written(np.zeros((6 * mcus_of(H, W), 64), np.int64), H, W, ANNEX_K, picture=True)
+    c = case("L2", H, W, [short, long_], 5)
+    assert_long(c, 1)
+    # blocks longer than a subsequence in every group: each group has a subsequence in which no block ends
+    S, nsub = sub_bits(), subsequences(len(log.unstuffed))
+    ends = set((log.pos[np.flatnonzero(np.diff(log.block))] // S).tolist())
+    for first in range(0, nsub, 256):
+        assert set(range(first, min(first + 256, nsub - 1))) - ends, first
+    return c
+
+
+L3_PLACES = (0, 31, 63)  # of the damaged scans
+L3_QUALITIES = (1, 30, 75, 95, 100)
+
+
+@functools.lru_cache(maxsize=1)
+def l3_sound_images():
+    """64 images of 64 x 96: five qualities, standard and optimised tables, three contents, each on a cycle of its own"""
+    a = _random(64, 96)
+    contents = [a, np.ascontiguousarray(a[::-1, ::-1] ^ 0x5A), np.repeat(a[:, :, :1] // 2, 3, axis=2)]  # test_gpu_jpeg_decode._three
+    images = [sound_pillow_image(pillow_jpeg(contents[i % 3], L3_QUALITIES[i % 5], optimize=bool(i % 2))) for i in range(64)]
+    assert len({(i.qtables.tobytes(), i.huffman.tobytes(), i.scan) for i in images}) == 30
+    assert len({i.huffman.tobytes() for i in images}) > 2 and len({i.qtables.tobytes() for i in images}) == 5
+    return images
+
+
+def l3_sound():
+    return case("L3_sound", 64, 96, l3_sound_images(), 0)
+
+
+def l3_with_damage():
+    """places 0, 31 and 63: damaged scans of DAMAGE_TILES' tiles (test_jpeg_decode_cpu.py), with their own tables.  Those tiles
+    have other sizes than 64 x 96: the call's size is one more thing that is wrong with them.  status 1 stands for "not 0"."""
+    images = list(l3_sound_images())
+    picks = (("og_beat", "an all-0xFF tail"), ("random_62x33", "one byte flipped mid-scan"), ("random_32x40", "truncated at a third"))
+    for place, (tile, what) in zip(L3_PLACES, picks):
+        assert tile in DAMAGE_TILES
+        data = pillow_jpeg(CONTENTS[tile](), DAMAGE_TILES[tile])
+        info = image_util.jpeg_parse(data)
+        images[place] = Image(damaged_scans(data[info.scan[0]:info.scan[1]])[what], None, None, None, info.qtables, info.huffman, status=1)
+    return case("L3", 64, 96, images, 0)
+
+
+def one_image(c: Case, n) -> Case:
+    return Case(f"{c.name}[{n}]", c.H, c.W, [c.scans[n]], [c.blocks[n]], [c.unstuffed[n]], [c.files[n]], c.qtables[n:n + 1], c.huffman[n:n + 1], 0,
+                [c.status[n]])
+
+
+BAD_TABLES = ("over-subscribed", "257_codes")
+
+
+def bad_table(kind):
+    """(16,) BITS no decoder can derive codes from"""
+    bits = np.zeros(16, np.uint8)
+    if kind == "over-subscribed":
+        bits[0] = 3  # three codes of one bit
+    else:
+        bits[7], bits[8] = 128, 129  # 128 of the 256 codes of 8 bits, 129 of the 256 left of 9: 257 symbols
+        code = 0
+        for length in range(1, 17):
+            code = (code + int(bits[length - 1])) << 1
+            assert code <= 2 << length  # no length over-subscribed
+        assert int(bits.sum()) == 257
+    return bits
+
+
+def l4_bad_table(kind, which):
+    h, w = 23, 37
+    images = [sound_pillow_image(pillow_jpeg(t, q)) for t, q in zip((_random(h, w), _random(h, w)[::-1], _random(h, w) ^ 0x33), (75, 90, 50))]
+    huffman = images[1].huffman.copy()
+    huffman[which, :16] = bad_table(kind)
+    images[1] = images[1]._replace(huffman=huffman, file=None, unstuffed=None, status=2)
+    return case(f"L4_{kind}_{which}", h, w, images, 0)
+
+
+def s1_the_largest_of_several_causes():
+    """include/rfx.h: "With several causes the largest is reported."  Scans whose causes are known from how they are made:
+    0: a stress scan cut inside a block - it ends inside a block (3) and blocks are missing (6);
+    1: a 16 x 16 scan less its last byte, a stuffed zero, as a 32 x 32 image - a dangling 0xFF (1) and blocks missing (6);
+    2: a sound scan and a dangling 0xFF (1) with a Huffman table that is no prefix code (2);
+    3: a sound picture."""
+    H = W = 32
+    whole, log = written(stress_blocks(H, W), H, W, STRESS)
+    i = int(np.flatnonzero((log.block == 13) & (log.k == 30))[0])  # a symbol in the middle of block 13
+    cut = log.unstuffed[:int(log.pos[i]) // 8]
+    assert cut[-1] != 0xFF and log.pos[i] // 8 * 8 > log.pos[np.flatnonzero(log.block == 13)[0]]  # no marker; the cut is inside the block
+    inside = whole._replace(scan=cut.replace(b"\xff", b"\xff\x00"), blocks=None, unstuffed=cut, status=6)
+    a = _abc()[0]
+    dangling = a._replace(scan=a.scan[:-1], blocks=None, status=6)
+    sound = sound_pillow_image(pillow_jpeg(_random(H, W), 75))
+    huffman = sound.huffman.copy()
+    huffman[1, :16] = bad_table("over-subscribed")
+    both = sound._replace(scan=sound.scan + b"\xff", huffman=huffman, file=None, unstuffed=sound.unstuffed + b"\xff", status=2)
+    assert a.scan.endswith(b"\xff\x00") and mcus_of(H, W) > 1
+    return case("S1", H, W, [inside, dangling, both, sound], 3)
+
+
+def emulator_blocks(c: Case, host: Decoded) -> Case:
+    """the case with the emulator's coefficients as the reference of the images the writer did not write (Pillow's files: the
+    emulator's pixels of them are compared with Pillow's), so that check_stages compares a device's coefficients with them"""
+    N = len(c.scans)
+    lay = layout(N, c.H, c.W, int(c.offsets[-1] - c.offsets[0]))
+    coef = np.asarray(host.workspace)[lay.coef:lay.coef + lay.coef_bytes].view(np.int16).reshape(N, -1, 64)
+    return c._replace(blocks=[b if b is not None or c.status[n] != 0 else coef[n][:, jw.ZIGZAG].astype(np.int64) for n, b in enumerate(c.blocks)])
+
+
+LARGE = {
+    "L1_first": functools.partial(l1_long_pillow_scan, "first"),
+    "L1_last": functools.partial(l1_long_pillow_scan, "last"),
+    "L2": l2_long_writer_scan,
+    "S1": s1_the_largest_of_several_causes,
+    **{f"L4_{k}_{t}": functools.partial(l4_bad_table, k, t) for k in BAD_TABLES for t in range(4)},
+}
+
+
+@functools.lru_cache(maxsize=None)
+def build_large(name) -> Case:
+    c = {**LARGE, "L3": l3_with_damage, "L3_sound": l3_sound}[name]()
+    assert c.name == name
+    return c
+
+
+@pytest.mark.parametrize("name", list(LARGE))
+def test_large_cases_on_the_emulator(name, tmp_path):
+    """L1, L2, L4, S1: statuses as the case says, the unstuffed bytes and the writer's coefficients, pixels as Pillow's (stress
+    images: as the single-image emulator's)"""
+    c = build_large(name)
+    reach(c)
+    check_on_the_emulator(c, tmp_path)
+    host = emu_batch(c)
+    ref = emulator_blocks(c, host)  # (what the device's coefficients of Pillow's files are compared with)
+    assert all(b is not None for b, s in zip(ref.blocks, c.status) if s == 0)
+    check_stages(ref, host, stages=("coef",))
+
+
+def test_l3_an_image_decodes_the_same_alone_and_at_any_place_of_64():
+    c = build_large("L3")
+    reach(c)
+    whole = emu_batch(c)
+    assert np.flatnonzero(whole.status).tolist() == list(L3_PLACES), whole.status
+    for n in range(64):
+        single = emu_batch(one_image(c, n))
+        assert whole.status[n] == single.status[0] and np.array_equal(whole.rgb[n], single.rgb[0]), n
+        if n not in L3_PLACES:
+            assert np.array_equal(whole.rgb[n], pillow_pixels(c.files[n])), n
+    print("L3: statuses of the damaged scans:", whole.status[list(L3_PLACES)])
+
+
+def test_l5_refusals_before_anything_is_read():
+    """the emulator's entry refuses a scan of kJpdMaxScanBytes + 1 as the device's does, and the layout takes kJpdMaxScanBytes"""
+    canary = np.full(64, 0x5C, np.uint8)
+    buffers = [canary.copy() for _ in range(5)]
+    off = np.array([0, MAX_SCAN_BYTES + 1], np.int64)
+    rc = emu().emu_jpeg_decode_batch(buffers[0].ctypes.data, off.ctypes.data, 1, 8, 8, buffers[1].ctypes.data, buffers[1].ctypes.data,
+                                     buffers[2].ctypes.data, buffers[3].ctypes.data, buffers[4].ctypes.data)
+    assert rc == -1 and all(np.array_equal(b, canary) for b in buffers)
+    assert layout(1, 8, 8, MAX_SCAN_BYTES).total > MAX_SCAN_BYTES
+
+
+def test_l6_the_workspace_s_previous_contents_change_nothing():
+    c = build_large("L3_sound")
+    a, b = emu_batch(c, fill=0xA5), emu_batch(c, fill=0x00)
+    assert not a.status.any() and np.array_equal(a.status, b.status) and np.array_equal(a.rgb, b.rgb)
+    for n in range(64):
+        assert np.array_equal(a.rgb[n], pillow_pixels(c.files[n])), n
