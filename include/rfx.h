@@ -35,8 +35,9 @@ typedef enum {
   RFX_ERR_INVALID = -1,     /* bad argument / unsupported geometry */
   RFX_ERR_HIP = -2,         /* a HIP runtime call failed */
   RFX_ERR_WORKSPACE = -3,   /* workspace too small */
-  RFX_ERR_UNSUPPORTED = -4  /* FFT length with a prime factor above 13 or whose frame buffer exceeds the 160 KiB of LDS (n_fft above
-                               about 39 000); non-banded filterbank */
+  RFX_ERR_UNSUPPORTED = -4  /* FFT length with a prime factor above 13 without RFX_ENGINE_CHIRPZ, or whose frame buffer exceeds the 160 KiB
+                               of LDS (n_fft above about 39 000; on the chirp-z engine, whose buffer is twice as long, above 19 968
+                               when even and 9 983 when odd - the refusal states them); non-banded filterbank */
 } rfx_status;
 
 /* Mirrors the fields of riffusion/spectrogram_params.py:21-42 that the arithmetic depends on,
@@ -84,7 +85,11 @@ typedef enum {
 typedef enum {
   RFX_ENGINE_AUTO = 0,    /* the row-family kernels where n_fft = 40 h and win_length = 10 h with h in {80, 160, 240, 320, 441, 480}
                              (the default 400 / 100 ms at 8, 16, 24, 32, 44.1, 48 kHz; any hop), the generic FFT engine otherwise */
-  RFX_ENGINE_GENERIC = 1  /* always the generic FFT engine (cross-checks) */
+  RFX_ENGINE_GENERIC = 1, /* always the generic FFT engine (cross-checks) */
+  RFX_ENGINE_CHIRPZ = 2   /* as RFX_ENGINE_AUTO, and a geometry AUTO refuses because its FFT length (n_fft / 2 when n_fft is even, n_fft
+                             when odd) has a prime factor above 13 runs on the chirp-z engine: Bluestein's algorithm, two mixed-radix
+                             FFTs of the smallest factorable length >= 2 x FFT length - 1 per transform, in LDS.  Every
+                             entry point serves such a plan.  A geometry AUTO accepts is planned exactly as under AUTO. */
 } rfx_frame_engine;
 
 /* Which plan (layouts + kernels) a parameter set gets */
@@ -118,7 +123,8 @@ typedef struct {
 /* rfx_plan_create with options (NULL = defaults = rfx_plan_create). */
 int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const float* h_melfb, int device,
                        const rfx_plan_options* options, rfx_plan** out_plan);
-/* the engine rfx_griffinlim runs on for this plan: 0 = specialised (17640 / 4410 / 441), 1 = generic FFT engine, 2 = row family */
+/* the engine rfx_griffinlim runs on for this plan: 0 = specialised (17640 / 4410 / 441), 1 = generic FFT engine, 2 = row family,
+ * 3 = chirp-z (the forward STFT of such a plan runs on it as well) */
 int rfx_plan_griffinlim_engine(const rfx_plan* plan);
 /* the form (RFX_GL_FORM_RUNS / _FRAMES) an rfx_griffinlim call of B x T frames takes on this plan */
 int rfx_griffinlim_form(const rfx_plan* plan, int B, int T);
@@ -161,6 +167,10 @@ typedef struct {
   double line_tolerance;   /* a group is a line when no bin leaves its fitted line by more than this fraction of the group's largest weight */
   double line_deviation;   /* the largest such fraction over all non-empty groups (-1: the bank has no group structure) */
   char imel_why[96];
+  int32_t fft_length;      /* generic plans: complex FFT length of a frame (n_fft / 2 when n_fft is even, n_fft when odd), else 0 */
+  int32_t pass_length;     /* ... and the length the radix passes run at: the same, or the chirp-z engine's convolution length */
+  int32_t czt_chirp_elems; /* chirp-z engine: entries of the chirp table and ... */
+  int32_t czt_h_elems;     /* ... of H in the LDS layout of the pass_length buffer (padding included), as plan creation builds them; else 0 */
 } rfx_plan_bank_report;
 int rfx_debug_plan_bank(const rfx_params* params, const float* h_melfb, const rfx_plan_options* options, rfx_plan_bank_report* report);
 /* Whether the closed-form InverseMelScale (rfx_inverse_mel_lstsq below) serves this filterbank, and the factor tables its kernels

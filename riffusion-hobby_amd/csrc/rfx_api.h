@@ -110,6 +110,10 @@ struct rfx_plan {
   int* d_gen_rev = nullptr;
   rfx::cf* d_gen_tw = nullptr;
   int frame_stride = rfx::kFrameStride;
+  // chirp-z engine (rfx_czt.hip) on top of a generic plan: FFT lengths with a prime factor above 13, opt-in (RFX_ENGINE_CHIRPZ)
+  bool czt = false;
+  rfx::cf* d_czt_c = nullptr;  // [gg.nc] chirp
+  rfx::cf* d_czt_h = nullptr;  // [gen_ibuf_elems(gg.np, gg.pad_shift)] H in the buffer's LDS layout
   // row-family Griffin-Lim (rfx_fam.hip) on top of a generic plan: n_fft = 40 h, win_length = 10 h
   bool fam_ok = false;
   rfx::FamGeom fam{};

@@ -79,6 +79,11 @@ int rfx_stft(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_
     g.B = B;
     g.T = stft_frames(plan, Lw);
     g.Lw = Lw;
+    if (plan->czt) {
+      if (d_mag_slots) RFX_HIP(launch_czt_stft(0, g, plan->d_czt_c, plan->d_czt_h, plan->num_cus, (hipStream_t)stream));
+      if (d_spec_slots) RFX_HIP(launch_czt_stft(1, g, plan->d_czt_c, plan->d_czt_h, plan->num_cus, (hipStream_t)stream));
+      return RFX_OK;
+    }
     if (d_mag_slots) RFX_HIP(launch_gen_stft(0, g, plan->num_cus, (hipStream_t)stream));
     if (d_spec_slots) RFX_HIP(launch_gen_stft(1, g, plan->num_cus, (hipStream_t)stream));
     return RFX_OK;

@@ -304,7 +304,9 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   }
   for (int it = 0; it <= c.n_iter; ++it) {
     const int mode = it == 0 ? 0 : 1;
-    RFX_HIP(fam ? launch_fam_gl(mode, fa, nblocks, c.stream) : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
+    RFX_HIP(fam         ? launch_fam_gl(mode, fa, nblocks, c.stream)
+            : plan->czt ? launch_czt_gl(mode, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
+                        : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
     const bool last = it == c.n_iter;
     RFX_HIP(launch_gen_fold(frames, env, last ? c.out : gen[it % 2], g, B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
                             it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale));

@@ -38,7 +38,7 @@ int rfx_frame_stride(void) { return kFrameStride; }
 int rfx_num_bins(void) { return kBins; }
 int rfx_plan_frame_stride(const rfx_plan* plan) { return plan ? plan->frame_stride : 0; }
 int rfx_plan_is_generic(const rfx_plan* plan) { return plan && plan->generic ? 1 : 0; }
-int rfx_plan_griffinlim_engine(const rfx_plan* plan) { return !plan ? -1 : !plan->generic ? 0 : plan->fam_ok ? 2 : 1; }
+int rfx_plan_griffinlim_engine(const rfx_plan* plan) { return !plan ? -1 : !plan->generic ? 0 : plan->fam_ok ? 2 : plan->czt ? 3 : 1; }
 int rfx_plan_imel_unit_form(const rfx_plan* plan) {
   if (!plan || !plan->d_melfb || !plan->imel_ok || plan->imel_variant != rfx::kImelVariantBest) return 0;
   return plan->imel.unit_form;  // (set for the per-wave and line-form families only: bank_sgd_admission)
@@ -92,8 +92,8 @@ static int resolve_options(const rfx_plan_options* options, rfx_plan_options* ou
     memcpy(&opt, options, options->struct_size);
     if (opt.gl_form < RFX_GL_FORM_AUTO || opt.gl_form > RFX_GL_FORM_FRAMES || opt.gl_frames_per_slot < 0)
       return fail(RFX_ERR_INVALID, "rfx_plan_create_ex: gl_form must be RFX_GL_FORM_AUTO / _RUNS / _FRAMES, gl_frames_per_slot >= 0");
-    if (opt.frame_engine < RFX_ENGINE_AUTO || opt.frame_engine > RFX_ENGINE_GENERIC)
-      return fail(RFX_ERR_INVALID, "rfx_plan_create_ex: frame_engine must be RFX_ENGINE_AUTO or RFX_ENGINE_GENERIC");
+    if (opt.frame_engine < RFX_ENGINE_AUTO || opt.frame_engine > RFX_ENGINE_CHIRPZ)
+      return fail(RFX_ERR_INVALID, "rfx_plan_create_ex: frame_engine must be RFX_ENGINE_AUTO, RFX_ENGINE_GENERIC or RFX_ENGINE_CHIRPZ");
     if (opt.plan_layout < RFX_LAYOUT_AUTO || opt.plan_layout > RFX_LAYOUT_GENERIC)
       return fail(RFX_ERR_INVALID, "rfx_plan_create_ex: plan_layout must be RFX_LAYOUT_AUTO or RFX_LAYOUT_GENERIC");
     if (opt.imel_form < RFX_IMEL_FORM_AUTO || opt.imel_form > RFX_IMEL_FORM_GROUPS)
@@ -137,7 +137,8 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
   RFX_HIP(hipGetDeviceProperties(&prop, device));
   pl->num_cus = prop.multiProcessorCount;
   RFX_HIP(prepare_frame_kernels());
-  if (geo.generic) RFX_HIP(prepare_generic_kernels(gg));
+  if (geo.generic && !geo.czt) RFX_HIP(prepare_generic_kernels(gg));
+  if (geo.czt) RFX_HIP(prepare_czt_kernels(gg));
   if (geo.fam_ok) {
     RFX_HIP(prepare_fam_kernels(geo.fam));
     pl->fam = geo.fam;
@@ -161,10 +162,19 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
   RFX_HIP(upload(pl.get(), &pl->d_tw1, spec_twiddles1()));
   RFX_HIP(upload(pl.get(), &pl->d_tw2, spec_twiddles2()));
   RFX_HIP(upload(pl.get(), &pl->d_win, h_window, (size_t)params->win_length));
-  if (geo.generic) {
+  if (geo.czt) {  // the passes' tables at the convolution length, the chirp and H; no digit-reversal table: the result is in natural order
+    const CztPlanTables ct = czt_plan_tables(gg);
+    RFX_HIP(upload(pl.get(), &pl->d_gen_tables, ct.two_level));
+    RFX_HIP(upload(pl.get(), &pl->d_gen_tw, ct.pass_tw));
+    RFX_HIP(upload(pl.get(), &pl->d_czt_c, ct.c));
+    RFX_HIP(upload(pl.get(), &pl->d_czt_h, ct.h));
+    pl->czt = true;
+  } else if (geo.generic) {
     RFX_HIP(upload(pl.get(), &pl->d_gen_tables, gen_two_level_twiddles(gg)));
     RFX_HIP(upload(pl.get(), &pl->d_gen_rev, gen_rev_table(gg)));
     RFX_HIP(upload(pl.get(), &pl->d_gen_tw, gen_pass_twiddles(gg)));
+  }
+  if (geo.generic) {
     cf* d = (cf*)pl->d_gen_tables;
     pl->gt.lo = d;
     pl->gt.hi = d + kGenTwLo;
@@ -317,6 +327,15 @@ int rfx_debug_plan_bank(const rfx_params* params, const float* h_melfb, const rf
   r.imel_kernel = -1;
   r.line_tolerance = kImelLineTol;
   r.line_deviation = -1.0;
+  if (geo.generic) {
+    r.fft_length = geo.gg.nc;
+    r.pass_length = geo.gg.np;
+  }
+  if (geo.czt) {
+    const CztPlanTables ct = czt_plan_tables(geo.gg);
+    r.czt_chirp_elems = (int32_t)ct.c.size();
+    r.czt_h_elems = (int32_t)ct.h.size();
+  }
   if (h_melfb) {
     if (params->n_mels <= 0) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be positive");
     const PlanBank bank = plan_bank(geo, params->n_mels, h_melfb, opt, ov);

@@ -58,6 +58,10 @@ struct GenGeom {
   // gen_frame_layout found a shift that lets the fold read 16 bytes at a time (hop a multiple of four but the window length or its
   // offset in the padded signal not: 22.05 kHz, 2205 / 1103): then the row is padded with >= 3 zeros on either side
   int fpitch, fshift;
+  // length of the radix passes: nc on the mixed-radix engines; on the chirp-z engine (rfx_czt_core.h) the convolution length >= 2 nc - 1,
+  // and radix / nstages / nhi / pad_shift then describe THAT length.  Last: code that fills a GenGeom field by field and never reads np
+  // (the mixed-radix kernels, their emulator) is untouched by it
+  int np;
 };
 // Frame-buffer layout for the overlap-add (gen_fold4_kernel): output sample p reads frame t at j = p + n_fft / 2 - left - hop t.  Four
 // consecutive p (p % 4 == 0) read 16 aligned bytes from every frame iff hop % 4 == 0 and (n_fft / 2 - left + fshift) % 4 == 0 and

@@ -329,6 +329,12 @@ hipError_t launch_gen_pack(const void* bft, void* frames, bool complex_, int B, 
 hipError_t launch_gen_unpack(const void* frames, void* bft, bool complex_, int B, int F, int T, int fs, hipStream_t stream);
 hipError_t launch_gen_mel(const float* mag, float* mel_tm, const float* band_wt, const int* band_lo, const int* band_len, long long nframes,
                           int fs, int M, int Mpad, int f_lo, int f_hi, hipStream_t stream);  // [f_lo, f_hi): bins with a non-zero filterbank row
+// ---- chirp-z engine (rfx_czt.hip, rfx_czt_core.h): the generic engine's frame kernels for FFT lengths with a prime factor above 13.
+// Same argument blocks (g.np = the convolution length, tb.lo / hi / tw / g.radix of that length), plus the chirp [g.nc] and H [LDS layout
+// of the g.np-point buffer]; fold, envelope, pack, unpack and mel are the generic engine's
+hipError_t prepare_czt_kernels(const GenGeom& g);
+hipError_t launch_czt_stft(int mode, const GenStftArgs& a, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);  // mode 0 mag, 1 spec
+hipError_t launch_czt_gl(int mode, const GenGlArgs& a, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);      // modes as launch_gen_gl
 hipError_t launch_mel_transpose(const float* mel_tm, float* mel, int B, int T, int M, int Mpad, hipStream_t stream);
 
 // ---- row-family Griffin-Lim (rfx_fam.hip): n_fft = 40 h, win_length = 10 h; frames are folded by launch_gen_fold

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/rfx.h"
+#include "rfx_czt_core.h"
 #include "rfx_kernels.h"
 
 namespace rfx {
@@ -30,7 +31,8 @@ struct PlanGeometry {
   FamGeom fam{};
   int n_stft = 0;
   int frame_stride = kFrameStride;
-  int engine() const { return !generic ? 0 : fam_ok ? 2 : 1; }  // as rfx_plan_griffinlim_engine answers
+  bool czt = false;      // chirp-z engine on top of the generic plan: gg.np > gg.nc (RFX_ENGINE_CHIRPZ and an unfactorable length)
+  int engine() const { return !generic ? 0 : fam_ok ? 2 : czt ? 3 : 1; }  // as rfx_plan_griffinlim_engine answers
 };
 
 inline int plan_geometry(const rfx_params& p, const rfx_plan_options& opt, const PlanOverrides& ov, PlanGeometry* out, std::string* err) {
@@ -60,10 +62,28 @@ inline int plan_geometry(const rfx_params& p, const rfx_plan_options& opt, const
              " complex numbers) does not fit the 160 KiB of LDS of a CU";
       return RFX_ERR_UNSUPPORTED;
     }
+    gg.np = gg.nc;
     if (!gen_factor(gg.nc, gg.radix, &gg.nstages)) {
-      *err = "rfx_plan_create: FFT length " + std::to_string(gg.nc) + " (from n_fft = " + std::to_string(p.n_fft) +
-             ") has a prime factor above 13; implemented radices: 2, 3, 4, 5, 7, 11, 13";
-      return RFX_ERR_UNSUPPORTED;
+      if (opt.frame_engine != RFX_ENGINE_CHIRPZ) {
+        *err = "rfx_plan_create: FFT length " + std::to_string(gg.nc) + " (from n_fft = " + std::to_string(p.n_fft) +
+               ") has a prime factor above 13; implemented radices: 2, 3, 4, 5, 7, 11, 13 (rfx_plan_options.frame_engine = RFX_ENGINE_CHIRPZ "
+               "runs such lengths on the chirp-z engine)";
+        return RFX_ERR_UNSUPPORTED;
+      }
+      // chirp-z engine: the passes run at the convolution length np >= 2 nc - 1; the buffer of np complex numbers and the tables must
+      // fit the LDS of a CU
+      if (!czt_fits(gg.nc)) {
+        const int lim = czt_max_nc();
+        *err = "rfx_plan_create: n_fft = " + std::to_string(p.n_fft) + ": the chirp-z engine's convolution buffer (at least " +
+               std::to_string(2 * gg.nc - 1) + " complex numbers for an FFT length of " + std::to_string(gg.nc) +
+               ") and its twiddle tables do not fit the 160 KiB of LDS of a CU (largest supported: n_fft " + std::to_string(2 * lim) +
+               " when even, " + std::to_string(lim % 2 ? lim : lim - 1) + " when odd)";
+        return RFX_ERR_UNSUPPORTED;
+      }
+      gg.np = czt_pass_len(gg.nc, gg.radix, &gg.nstages);
+      gg.nhi = czt_nhi(gg.np);
+      gg.nhi2 = czt_nhi2(gg.nc);
+      g.czt = true;
     }
     // threads per workgroup: measured on MI355X, the engine is latency bound and more waves win over fuller rounds
     // (48 kHz, 64 tiles x 32 iterations: 512 threads 121 ms, 384: 134, 320 - the count gen_pick_threads prefers: 155, 256: 163)
@@ -71,15 +91,23 @@ inline int plan_geometry(const rfx_params& p, const rfx_plan_options& opt, const
     if (ov.gen_threads >= 64 && ov.gen_threads <= 512 && ov.gen_threads % 64 == 0) gg.nthr = ov.gen_threads;
     // LDS padding: keep as many workgroups per CU as the unpadded buffer allows
     const size_t tables = sizeof(cf) * (2 * (size_t)kGenTwLo + gg.nhi + gg.nhi2);
-    const size_t plain = sizeof(cf) * (size_t)gg.nc + tables + 512;
+    const size_t plain = sizeof(cf) * (size_t)gg.np + tables + 512;
     int per_cu = (int)((160u * 1024u) / plain);
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 1024 / gg.nthr) per_cu = 1024 / gg.nthr;
-    const size_t room = (160u * 1024u) / per_cu - tables - 512;
-    gg.pad_shift = gen_pick_pad(gg, (int)(room / sizeof(cf)));
+    const size_t plain_room = (160u * 1024u) / per_cu;
+    const size_t room = plain_room > tables + 512 ? plain_room - tables - 512 : 0;
+    gg.pad_shift = gen_pick_pad(g.czt ? czt_pass_geom(gg) : gg, (int)(room / sizeof(cf)));
     if (ov.gen_pad == 0 || (ov.gen_pad >= 3 && ov.gen_pad <= 8)) gg.pad_shift = ov.gen_pad;
-    if (gen_lds_bytes(gg) > 160u * 1024u) gg.pad_shift = 0;
-    if (gen_lds_bytes(gg) > 160u * 1024u) {
+    if (g.czt) {
+      if (czt_lds_bytes(gg) > kCztLdsLimit) gg.pad_shift = 0;
+      if (czt_lds_bytes(gg) > kCztLdsLimit) {  // (czt_fits said otherwise: the two must share czt_lds_bytes_of)
+        *err = "rfx_plan_create: n_fft = " + std::to_string(p.n_fft) + ": the chirp-z engine's buffer and tables (" + std::to_string(czt_lds_bytes(gg)) +
+               " bytes) do not fit the 160 KiB of LDS of a CU";
+        return RFX_ERR_UNSUPPORTED;
+      }
+    } else if (gen_lds_bytes(gg) > 160u * 1024u) gg.pad_shift = 0;
+    if (!g.czt && gen_lds_bytes(gg) > 160u * 1024u) {
       *err = "rfx_plan_create: n_fft = " + std::to_string(p.n_fft) + ": the frame's FFT buffer and twiddle tables (" +
              std::to_string(gen_lds_bytes(gg)) + " bytes) do not fit the 160 KiB of LDS of a CU (largest supported: n_fft about 39000 when "
              "even, 19500 when odd)";
@@ -90,7 +118,7 @@ inline int plan_geometry(const rfx_params& p, const rfx_plan_options& opt, const
   // Griffin-Lim of the geometries with n_fft = 40 h, win_length = 10 h (the default 400 / 100 ms at 48 / 32 / 24 / 16 / 8 kHz)
   // runs on the row-family kernels; the generic engine keeps everything else of the plan (layouts, forward path)
   FamGeom& fam = g.fam;
-  g.fam_ok = g.generic && opt.frame_engine != RFX_ENGINE_GENERIC && fam_make_geom(p.n_fft, p.win_length, p.hop_length, &fam);
+  g.fam_ok = g.generic && !g.czt && opt.frame_engine != RFX_ENGINE_GENERIC && fam_make_geom(p.n_fft, p.win_length, p.hop_length, &fam);
   if (g.fam_ok) {
     // pad the rows by up to seven elements (bank spread of the row-to-row accesses) as long as that costs no resident workgroup
     const size_t plain = fam_lds_bytes(fam) + fam_static_lds_bytes(fam);
@@ -178,6 +206,15 @@ inline std::vector<cf> fam_twiddles(const FamGeom& f) {  // [rows][h] g(n')^k1, 
       twa[(size_t)(q - 1) * f.rb + i] = cf{(float)cos(kPi2 * e / (double)f.h), (float)(-sin(kPi2 * e / (double)f.h))};
     }
   return tw;
+}
+// chirp-z engine: the chirp and H (czt_tables), the passes' tables at the convolution length
+struct CztPlanTables {
+  std::vector<cf> two_level, pass_tw, c, h;
+};
+inline CztPlanTables czt_plan_tables(const GenGeom& gg) {
+  const GenGeom pg = czt_pass_geom(gg);  // lo / hi base np [nhi], lo2 / hi2 base n_fft [nhi2]
+  CztTables t = czt_tables(gg);
+  return CztPlanTables{gen_two_level_twiddles(pg), gen_pass_twiddles(pg), std::move(t.c), std::move(t.h)};
 }
 inline std::vector<int> fam_bin_of(const FamGeom& f) {  // [fsf] bin held by each position of the slot-ordered magnitudes (-1: padding)
   std::vector<int> binof((size_t)f.fsf, -1);

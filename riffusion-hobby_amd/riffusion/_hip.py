@@ -61,7 +61,8 @@ class RfxPlanBankReport(ctypes.Structure):
                                                  "line_from", "f_lo", "f_hi", "nnz", "fwd_ok", "fwd_product", "fwd_packed")]
                 + [("fwd_kb_mask", ctypes.c_uint32)]
                 + [(n, ctypes.c_int32) for n in ("fwd_prod_arr", "band_rows", "Mpad", "n_kblocks")]
-                + [("line_tolerance", ctypes.c_double), ("line_deviation", ctypes.c_double), ("imel_why", ctypes.c_char * 96)])
+                + [("line_tolerance", ctypes.c_double), ("line_deviation", ctypes.c_double), ("imel_why", ctypes.c_char * 96)]
+                + [(n, ctypes.c_int32) for n in ("fft_length", "pass_length", "czt_chirp_elems", "czt_h_elems")])
 
 
 class RfxCompressOptions(ctypes.Structure):
@@ -129,7 +130,9 @@ GL_FORMS = {"auto": 0, "runs": 1, "frames": 2}  # rfx_gl_form
 FRAME_ENGINES = {"auto": 0, "generic": 1}       # rfx_frame_engine
 PLAN_LAYOUTS = {"auto": 0, "generic": 1}        # rfx_plan_layout
 IMEL_FORMS = {"auto": 0, "groups": 1}           # rfx_imel_form
-GL_ENGINE_NAMES = {0: "specialised", 1: "generic", 2: "row-family"}  # rfx_plan_griffinlim_engine
+# opt-in engines beside them (rfx_frame_engine): "chirp-z" runs FFT lengths with a prime factor above 13, which "auto" refuses
+OPT_IN_FRAME_ENGINES = {"chirp-z": 2}
+GL_ENGINE_NAMES = {0: "specialised", 1: "generic", 2: "row-family", 3: "chirp-z"}  # rfx_plan_griffinlim_engine
 
 
 class RfxError(RuntimeError):
@@ -449,8 +452,9 @@ class Plan:
         self.lib = load_library()
         if gl_form not in GL_FORMS:
             raise ValueError(f"gl_form must be one of {sorted(GL_FORMS)}, got {gl_form!r}")
-        if frame_engine not in FRAME_ENGINES:
-            raise ValueError(f"frame_engine must be one of {sorted(FRAME_ENGINES)}, got {frame_engine!r}")
+        engines = {**FRAME_ENGINES, **OPT_IN_FRAME_ENGINES}
+        if frame_engine not in engines:
+            raise ValueError(f"frame_engine must be one of {sorted(engines)}, got {frame_engine!r}")
         if plan_layout not in PLAN_LAYOUTS:
             raise ValueError(f"plan_layout must be one of {sorted(PLAN_LAYOUTS)}, got {plan_layout!r}")
         if imel_form not in IMEL_FORMS:
@@ -474,7 +478,7 @@ class Plan:
         cp = RfxParams(params.sample_rate, self.n_fft, self.win_length, self.hop_length, self.n_mels, params.max_mel_iters)
         handle = c_void_p()
         self.device = device = resolve_device(device)
-        opt = RfxPlanOptions(ctypes.sizeof(RfxPlanOptions), GL_FORMS[gl_form], 0, FRAME_ENGINES[frame_engine], PLAN_LAYOUTS[plan_layout],
+        opt = RfxPlanOptions(ctypes.sizeof(RfxPlanOptions), GL_FORMS[gl_form], 0, engines[frame_engine], PLAN_LAYOUTS[plan_layout],
                              IMEL_FORMS[imel_form])
         check(
             self.lib.rfx_plan_create_ex(
@@ -1168,7 +1172,8 @@ def get_plan(params: T.Any, device: T.Union[str, torch.device], gl_form: str = "
     `gl_form` picks the Griffin-Lim device form (rfx_plan_options.gl_form): "auto" (per call, from the batch
     shape), "runs" (always the run-based fused kernel) or "frames" (always the per-frame kernel + fold);
     `frame_engine` = "generic" keeps Griffin-Lim of the 40 h / 10 h geometries (48 kHz ...) on the generic FFT engine
-    instead of the row-family kernels (rfx_plan_options.frame_engine; cross-checks); `plan_layout` = "generic" builds the
+    instead of the row-family kernels (rfx_plan_options.frame_engine; cross-checks), "chirp-z" plans as "auto" and runs
+    the geometries "auto" refuses - an FFT length with a prime factor above 13 - on the chirp-z engine; `plan_layout` = "generic" builds the
     generic plan also for the default geometry (rfx_plan_options.plan_layout; cross-checks of the specialised engine);
     `imel_form` = "groups" keeps InverseMelScale on the group kernels where "auto" takes the wave kernel
     (rfx_plan_options.imel_form; cross-checks)."""

@@ -48,24 +48,26 @@ def _params_from_image(image: Image.Image) -> SpectrogramParams:
 
 def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_frequencies: int = 512, min_frequency: int = 0,
                    max_frequency: int = 10000, window_duration_ms: int = 100, padded_duration_ms: int = 400,
-                   power_for_image: float = 0.25, stereo: bool = False, device: str = "cuda") -> None:
+                   power_for_image: float = 0.25, stereo: bool = False, device: str = "cuda", frame_engine: str = "auto") -> None:
+    """Encode one clip; --frame-engine chirp-z runs a sample rate / padded duration whose FFT length has a prime factor above 13."""
     segment = _load_segment(audio)
     params = SpectrogramParams(
         sample_rate=segment.frame_rate, stereo=stereo, window_duration_ms=window_duration_ms,
         padded_duration_ms=padded_duration_ms, step_size_ms=step_size_ms, min_frequency=min_frequency,
         max_frequency=max_frequency, num_frequencies=num_frequencies, power_for_image=power_for_image,
     )
-    converter = SpectrogramImageConverter(params=params, device=device)
+    converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
     pil_image = converter.spectrogram_image_from_audio(segment)
     pil_image.save(image, exif=pil_image.getexif(), format="PNG")
     print(f"Wrote {image}")
 
 
-def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd") -> None:
-    """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD."""
+def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto") -> None:
+    """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD,
+    --frame-engine chirp-z runs parameters whose FFT length has a prime factor above 13 (refused otherwise)."""
     pil_image = Image.open(image)
     params = _params_from_image(pil_image)
-    converter = SpectrogramImageConverter(params=params, device=device)
+    converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
     segment = converter.audio_from_spectrogram_image(pil_image, apply_filters=True, inverse_mel=inverse_mel)
     segment.export(audio, format=os.path.splitext(audio)[1][1:] or "wav")
     print(f"Wrote {audio} ({segment.duration_seconds:.2f} seconds)")
@@ -135,12 +137,14 @@ def _load_tiles(converter: SpectrogramImageConverter, chunk: T.Sequence[str], im
 
 
 def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 64, no_filters: bool = False,
-                          compression: bool = False, device: str = "cuda", inverse_mel: str = "sgd", image_extension: str = "png") -> None:
+                          compression: bool = False, device: str = "cuda", inverse_mel: str = "sgd", image_extension: str = "png",
+                          frame_engine: str = "auto") -> None:
     """Decode every *.png (or, with --image-extension jpg / jpeg, every file of that extension) of a directory, `batch_size`
     same-width tiles per GPU call.  Each clip then gets the same
     post-processing as `image-to-audio` (audio_util.apply_filters, reference spectrogram_image_converter.py:65-91, run on the
     device) unless --no-filters is given; --compression adds the filters' dynamic range compression (apply_filters with
-    compression=True, also on the device); --inverse-mel lstsq takes the closed-form InverseMelScale instead of the SGD."""
+    compression=True, also on the device); --inverse-mel lstsq takes the closed-form InverseMelScale instead of the SGD;
+    --frame-engine chirp-z decodes tiles whose parameters give an FFT length with a prime factor above 13."""
     if compression and no_filters:
         raise ValueError("--compression is a mode of the filters: it does not go with --no-filters")
     if image_extension not in ("png", "jpg", "jpeg"):
@@ -149,7 +153,7 @@ def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 
     device = _rank_device(device)
     paths = _rank_slice(sorted(glob.glob(os.path.join(image_dir, "*." + image_extension))))
     for (params, _size), members in _tile_groups(paths, image_extension).items():
-        converter = SpectrogramImageConverter(params=params, device=device)
+        converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
         for i in range(0, len(members), batch_size):
             chunk = members[i : i + batch_size]
             # the filters run on the device, clip by clip, before the batch leaves it (same bytes as audio_util.apply_filters)
@@ -178,12 +182,13 @@ def _device_convertible(seg: T.Any, sample_rate: int) -> bool:
 def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: str = "jpg", step_size_ms: int = 10,
                           num_frequencies: int = 512, min_frequency: int = 0, max_frequency: int = 10000,
                           power_for_image: float = 0.25, mono: bool = False, sample_rate: int = 44100, device: str = "cuda",
-                          num_threads: int = 0, limit: int = -1, batch_size: int = 64) -> None:
+                          num_threads: int = 0, limit: int = -1, batch_size: int = 64, frame_engine: str = "auto") -> None:
     """Process audio clips into spectrogram images in batch (reference cli.py:134-204, same flags and defaults: stereo
     tiles unless --mono, files resampled to --sample-rate, unreadable files skipped, jpg output - encoded on the device, the same
     bytes as Pillow's; png is written by Pillow on the host).  Instead of one clip
     per thread-pool task (`num_threads` is accepted and ignored) same-length clips go to the GPU `batch_size` at a time.  A file
-    whose channel count or rate differs is mixed and resampled on the device (Plan.resample_pcm), same bytes as pydub's."""
+    whose channel count or rate differs is mixed and resampled on the device (Plan.resample_pcm), same bytes as pydub's.
+    --frame-engine chirp-z runs a --sample-rate whose FFT length has a prime factor above 13."""
     import torch
 
     os.makedirs(output_dir, exist_ok=True)
@@ -196,7 +201,7 @@ def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: s
     params = SpectrogramParams(step_size_ms=step_size_ms, num_frequencies=num_frequencies, min_frequency=min_frequency,
                                max_frequency=max_frequency, power_for_image=power_for_image, stereo=not mono,
                                sample_rate=sample_rate)
-    converter = SpectrogramImageConverter(params=params, device=device)
+    converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
     channels = 1 if mono else 2
     # Streaming: files are decoded one at a time and grouped by sample count (a GPU call needs equal lengths); a group is
     # converted and released as soon as it holds `batch_size` clips, and when the waveforms held - in host memory, or in device
@@ -271,7 +276,7 @@ _COMMANDS: T.Dict[str, T.Callable[..., None]] = {
 }
 
 
-_CHOICES = {"inverse_mel": ("sgd", "lstsq")}  # arguments that take one of a few words
+_CHOICES = {"inverse_mel": ("sgd", "lstsq"), "frame_engine": ("auto", "chirp-z")}  # arguments that take one of a few words
 
 
 def build_parser() -> argparse.ArgumentParser:

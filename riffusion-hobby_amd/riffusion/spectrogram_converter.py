@@ -45,8 +45,11 @@ class _HipOp:
 
 
 class SpectrogramConverter:
-    def __init__(self, params: SpectrogramParams, device: str = "cuda"):
+    def __init__(self, params: SpectrogramParams, device: str = "cuda", *, frame_engine: str = "auto"):
+        """`frame_engine="chirp-z"` (not in the reference) runs parameter sets whose FFT length has a prime factor above 13 - which
+        "auto" refuses with the library's reason - on the chirp-z engine; every other parameter set is planned as under "auto"."""
         self.p = params
+        self.frame_engine = frame_engine
         self.device = torch_util.check_device(device)
         if device.lower().startswith("mps"):
             warnings.warn(
@@ -69,7 +72,7 @@ class SpectrogramConverter:
                 f"SpectrogramConverter(device={self.device!r}): this build runs on the MI355X only "
                 "(HIP kernels through librfx.so); there is no CPU implementation"
             )
-        return _hip.get_plan(self.p, self.device)
+        return _hip.get_plan(self.p, self.device, frame_engine=self.frame_engine)
 
     @property
     def _channels_per_clip(self) -> int:

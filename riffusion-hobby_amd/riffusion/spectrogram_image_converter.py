@@ -22,10 +22,11 @@ from riffusion.util import audio_util, image_util
 
 
 class SpectrogramImageConverter:
-    def __init__(self, params: SpectrogramParams, device: str = "cuda"):
+    def __init__(self, params: SpectrogramParams, device: str = "cuda", *, frame_engine: str = "auto"):
+        """`frame_engine="chirp-z"`: as SpectrogramConverter's - parameter sets "auto" refuses for their FFT length run on the chirp-z engine."""
         self.p = params
         self.device = device
-        self.converter = SpectrogramConverter(params=params, device=device)
+        self.converter = SpectrogramConverter(params=params, device=device, frame_engine=frame_engine)
 
     # ---- reference API: one clip per call -------------------------------------------------------------
     def spectrogram_image_from_audio(self, segment: T.Any) -> Image.Image:
