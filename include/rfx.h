@@ -226,7 +226,9 @@ int rfx_stft_frames(const rfx_plan* plan, int Lw);
  * absolute (loss < 1e-5, |change| < 1e-8: tiny spectrograms stop after one step - reproduced), the bins no filter reaches keep
  * their U[0,1) start whatever max_value is (reproduced), and below |a| = 1e-8 in the input's units the `+ 1e-16` guard becomes
  * visible: there this library's guard, rsq(|a|^2 + 1e-32), differs from the reference's 1 / (|a| + 1e-16) by up to 41 %
- * (at |a| = 1e-16) in the LENGTH of the phase factor - never in its direction, and it is exactly 0 for a = 0 in both. */
+ * (at |a| = 1e-16) in the LENGTH of the phase factor - never in its direction, and it is exactly 0 for a = 0 in both.
+ * A guide (rfx_guided_call_options below) is brought into that range by an exact power of two of its own, taken from each row's
+ * peak: only the direction of its STFT matters, guide x 2^n gives the same output bytes, and the guard stays invisible for it. */
 /* rfx_call_options.flags.  RFX_CALL_INVERSE_MEL_LSTSQ: the fused calls rfx_waveform_from_mel_ex and rfx_audio_from_image_u8_ex run
  * rfx_inverse_mel_lstsq in place of the SGD.  rfx_inverse_mel_ex and rfx_griffinlim_ex refuse any non-zero flag. */
 #define RFX_CALL_INVERSE_MEL_LSTSQ 1u
@@ -235,8 +237,45 @@ typedef struct {
   uint32_t flags;           /* 0 or RFX_CALL_* bits */
   uint64_t row_base;
   float magnitude_hint;
-  float reserved;           /* must be 0 */
+  float reserved;           /* must be 0 (checked) */
 } rfx_call_options;
+
+/* rfx_call_options grown at its tail: the guide of a phase-guided Griffin-Lim start.  The same struct on the wire - every *_ex
+ * entry point takes either through its `const rfx_call_options*` and tells them apart by struct_size - under a second name, so that
+ * a caller built against the 24-byte struct keeps its type and, passing that size, exactly its behaviour.  Set struct_size =
+ * sizeof(rfx_guided_call_options); the first five fields are rfx_call_options' own.
+ *
+ * d_guide != NULL: Griffin-Lim starts every row of the call from the phase of a waveform the caller already has (in an audio-to-audio
+ * workflow: the source clip) instead of random phases.  d_guide: (B, guide_samples) float32 on the plan's device, row r at
+ * d_guide + r * guide_stride (elements; >= guide_samples), any units, 4-byte aligned (16-byte aligned rows are read 16 bytes a lane).
+ * For row r of a call with T frames, L = rfx_griffinlim_output_samples(plan, T):
+ *   fit    g_r = the guide row cut to L samples, or zero-padded at its end to L; its STFT then has exactly T frames;
+ *   start  angles0 = G / |G| with G the plan's STFT of g_r (what rfx_stft computes), 0 where G == 0; the rest is the reference's
+ *          Griffin-Lim unchanged: n_iter iterations, tprev = 0 in the first, then the final ISTFT - what the oracle's
+ *          griffinlim(S, p, angles0=G / (G.abs() + 1e-16), n_iter) computes.  On the device the first launch of the call analyses the
+ *          staged guide (a = STFT(g_r); ISTFT(|S| a / |a|)) in place of synthesising from drawn phases: the same number of launches,
+ *          rfx_griffinlim_ex's h_launch_ms keeps its n_iter + 1 entries ([0] includes the staging).
+ * No randomness: a guided row's result does not depend on seed, on row_base or on the batch it travels in.  Scale: see "Numeric
+ * range" above.  Digital silence stays what the mathematics makes of it: a wholly silent guide row gives a silent output row (a zero
+ * start is a fixed point of the iteration, in the reference as here), and a zero-padded tail starts silent and is filled by the
+ * iterations from the leakage of the neighbouring frames; no noise is injected and nothing falls back to a random start.  NaN / Inf
+ * in a guide: garbage in, garbage out, like the magnitudes.
+ * Limits: guidance is all rows of a call or none; a guide together with d_angles0_slots, guide_samples <= 0, guide_stride <
+ * guide_samples or a pointer off 4-byte alignment is RFX_ERR_INVALID before any launch; so is L <= n_fft / 2 even at n_iter == 0 (the
+ * guide is analysed with the reflect padding; the message is rfx_griffinlim's).  Honoured by rfx_griffinlim_ex,
+ * rfx_waveform_from_mel_ex and rfx_audio_from_image_u8_ex (B = N x channels rows, clip after clip, as the mel rows);
+ * rfx_inverse_mel_ex refuses a guide.  No workspace query grows: the guide is staged in audio buffers the first launch leaves free. */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t flags;
+  uint64_t row_base;
+  float magnitude_hint;
+  float reserved;           /* must be 0 */
+  const float* d_guide;     /* NULL: not guided (the call is rfx_call_options' call) */
+  int64_t guide_stride;     /* elements between guide rows */
+  int32_t guide_samples;    /* samples per guide row */
+  int32_t reserved2;        /* must be 0 */
+} rfx_guided_call_options;
 
 /* ---- layout converters ------------------------------------------------------------------- */
 /* (B, n_stft, T) float32 magnitudes -> slots (float32) */

@@ -196,9 +196,13 @@ struct CallOpt {
   uint64_t row_base = 0;
   float magnitude_hint = 0.f;
   bool lstsq = false;  // RFX_CALL_INVERSE_MEL_LSTSQ (the fused calls)
+  // rfx_guided_call_options: the guide waveforms of a guided Griffin-Lim start (null: the start is drawn or injected)
+  const float* guide = nullptr;
+  int64_t guide_stride = 0;
+  int guide_samples = 0;
 };
-// allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves)
-static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who, uint32_t allowed_flags = 0) {
+// allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves); takes_guide: it runs Griffin-Lim
+static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who, uint32_t allowed_flags = 0, bool takes_guide = false) {
   *out = CallOpt{};
   if (!o) return RFX_OK;
   if (o->struct_size < offsetof(rfx_call_options, row_base) + sizeof(uint64_t))
@@ -211,6 +215,23 @@ static int read_call_options(const rfx_call_options* o, CallOpt* out, const char
   if (o->struct_size >= offsetof(rfx_call_options, magnitude_hint) + sizeof(float)) out->magnitude_hint = o->magnitude_hint;
   if (!(out->magnitude_hint >= 0.f) || out->magnitude_hint > 3.0e38f)
     return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.magnitude_hint must be a finite value >= 0");
+  if (o->struct_size >= offsetof(rfx_call_options, reserved) + sizeof(float) && !(o->reserved == 0.f))
+    return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.reserved must be 0");
+  // the guided tail (rfx_guided_call_options: the same struct, grown; a caller that passes the short size has none)
+  if (o->struct_size >= offsetof(rfx_guided_call_options, reserved2) + sizeof(int32_t)) {
+    const rfx_guided_call_options* g = reinterpret_cast<const rfx_guided_call_options*>(o);
+    if (g->reserved2 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_guided_call_options.reserved2 must be 0");
+    if (g->d_guide) {
+      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and takes no guide (d_guide must be NULL)");
+      if (g->guide_samples <= 0) return fail(RFX_ERR_INVALID, std::string(who) + ": guide_samples must be positive when d_guide is given");
+      if (g->guide_stride < (int64_t)g->guide_samples)
+        return fail(RFX_ERR_INVALID, std::string(who) + ": guide_stride (elements between rows) must be at least guide_samples");
+      if ((uintptr_t)g->d_guide & (sizeof(float) - 1)) return fail(RFX_ERR_INVALID, std::string(who) + ": d_guide must be aligned to 4 bytes");
+      out->guide = g->d_guide;
+      out->guide_stride = g->guide_stride;
+      out->guide_samples = g->guide_samples;
+    }
+  }
   return RFX_OK;
 }
 
@@ -226,6 +247,9 @@ struct GlCall {
   char* ws;
   size_t ws_bytes;
   hipStream_t stream;
+  const float* guide;  // null, or (B, guide_samples) rows guide_stride apart: launch 0 is MODE 1 on the staged guide (rfx_guide.hip)
+  int64_t guide_stride;
+  int guide_samples;
 };
 // ... and the fields that all four argument blocks have
 template <class Args>
@@ -246,6 +270,15 @@ static int gl_row_scale(GlCall& c, size_t per_row, float* table) {
   if (c.row_scale) return RFX_OK;
   RFX_HIP(launch_range_scale(c.S, per_row, c.B, c.hint, (unsigned*)(table + 2 * (size_t)c.B), nullptr, table, 1, 0, c.stream));
   c.row_scale = table;
+  return RFX_OK;
+}
+
+// A guided call's staging, after the row-scale table is written and before launch 0: the fitted, ranged guide into `dst`, the
+// buffer launch 0 analyses (Lpad floats per row), zeros into `zero` (the run form's other parity buffer; else null).  `peaks`: any
+// audio buffer of the call that launch 0 neither reads nor writes.  pre_scaled: the engine's kernels analyse their buffer as it is
+// (the fold applies row_scale[2 r]); the specialised engine's multiply by it, and the staged values are divided by it.
+static int gl_stage_guide(const GlCall& c, int Lpad, bool pre_scaled, float* peaks, float* dst, float* zero) {
+  RFX_HIP(launch_guide_stage(c.guide, c.guide_stride, c.guide_samples, c.B, c.L, Lpad, pre_scaled ? nullptr : c.row_scale, peaks, dst, zero, c.stream));
   return RFX_OK;
 }
 
@@ -271,7 +304,10 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   // x_it lives in gen[it % 2]; gen[2] holds d_it = x_it - m x_{it-1} (d_0 = x_0), the momentum term of the reference's
   // `rebuilt - m * tprev` applied in the time domain: the fold of iteration it forms it next to x_it and launch it + 1 analyses it,
   // so the kernels run their one-signal mode for every iteration (half the audio loads, same bits); it == 0 synthesises the
-  // initial estimate from S * angles0
+  // initial estimate from S * angles0 - or, guided, analyses the staged guide in gen[2] like any later launch (gen[1] is free until
+  // the fold of launch 1: the staging's scratch)
+  if (c.guide)
+    if (int rc = gl_stage_guide(c, w.Lpad, true, gen[1], gen[2], nullptr)) return rc;
   FamGlArgs fa{};
   GenGlArgs ga{};
   int nblocks = 0;
@@ -303,7 +339,7 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
     ga.frames = frames;
   }
   for (int it = 0; it <= c.n_iter; ++it) {
-    const int mode = it == 0 ? 0 : 1;
+    const int mode = it == 0 && !c.guide ? 0 : 1;
     RFX_HIP(fam         ? launch_fam_gl(mode, fa, nblocks, c.stream)
             : plan->czt ? launch_czt_gl(mode, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
                         : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
@@ -339,10 +375,13 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
     fa.Lpad = w.Lpad;
     const int nblocks = frame_blocks(gl_slot_count(plan), B, T);
     RFX_HIP(timer.begin(c.stream));
+    // guided: launch 0 is MODE 1 on the guide, staged where it reads its input (gen[2][0]; gen[1][0] is free until launch 1's fold)
+    if (c.guide)
+      if (int rc = gl_stage_guide(c, w.Lpad, false, gen[1][0], gen[2][0], nullptr)) return rc;
     for (int it = 0; it <= c.n_iter; ++it) {
       fa.audio_in = gen[(it + 2) % 3][0];    // x_{it-1}
       fa.audio_prev = gen[(it + 1) % 3][0];  // x_{it-2}
-      RFX_HIP(launch_gl_frame(it == 0 ? 0 : it == 1 ? 1 : 2, fa, nblocks, c.stream));
+      RFX_HIP(launch_gl_frame(it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2, fa, nblocks, c.stream));
       const bool last = it == c.n_iter;
       RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream));
       RFX_HIP(timer.mark(it, c.stream));
@@ -372,6 +411,10 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
     }
   };
   RFX_HIP(timer.begin(c.stream));
+  // guided: launch 0 is MODE 1 on the guide, staged as the generation it reads (parity 0 the guide, parity 1 zeros: the kernel adds
+  // the two); generation 2 is free until launch 2 writes it
+  if (c.guide)
+    if (int rc = gl_stage_guide(c, w.Lpad, false, gen[2][0], gen[1][0], gen[1][1])) return rc;
   for (int it = 0; it <= c.n_iter; ++it) {
     // iteration `it` analyses x_{it-1} - m*x_{it-2} and writes x_it; MODE 0 reads nothing and writes x_0
     if (it == 0) set_io(1, 2, 0);
@@ -379,12 +422,29 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
 #ifdef RFX_WGCLOCK
     g.launch = it;
 #endif
-    RFX_HIP(launch_gl_iter(it == 0 ? 0 : it == 1 ? 1 : 2, g, part.runs, c.stream));
+    RFX_HIP(launch_gl_iter(it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2, g, part.runs, c.stream));
     RFX_HIP(timer.mark(it, c.stream));
   }
   const int last = c.n_iter % 3;
   RFX_HIP(launch_gl_combine(gen[last][0], gen[last][1], c.out, B, L, w.Lpad, c.stream));
   RFX_HIP(timer.finish());
+  return RFX_OK;
+}
+
+// every iteration re-analyses the estimate with torch.stft(center=True, reflect): the reference raises there unless the signal is
+// longer than the n_fft/2 padding.  A guided call analyses its guide that way even with no iteration.
+static int reflect_refusal(const rfx_plan* plan) {
+  return fail(RFX_ERR_INVALID,
+              plan->generic ? "rfx_griffinlim: Padding size should be less than the corresponding input dimension (reflect padding " +
+                                  std::to_string(plan->p.n_fft / 2) + " needs more than that many samples)"
+                            : "rfx_griffinlim: Padding size should be less than the corresponding input dimension "
+                              "(reflect padding 8820 needs more than 8820 samples, i.e. at least 22 frames)");
+}
+// what every entry that takes a guide checks before it launches anything
+static int guide_refusal(const rfx_plan* plan, const CallOpt& opt, int T, bool has_angles0, const char* who) {
+  if (!opt.guide) return RFX_OK;
+  if (has_angles0) return fail(RFX_ERR_INVALID, std::string(who) + ": a guide and d_angles0_slots are two starts: give one");
+  if (T >= 2 && rfx_griffinlim_output_samples(plan, T) <= plan->p.n_fft / 2) return reflect_refusal(plan);
   return RFX_OK;
 }
 
@@ -396,18 +456,13 @@ static int griffinlim_impl(const rfx_plan* plan, const float* d_mag_slots, const
   if (B <= 0 || T < 2 || n_iter < 0) return fail(RFX_ERR_INVALID, "rfx_griffinlim: bad shape");
   if ((long long)B * T > 0x7fffffffLL) return fail(RFX_ERR_INVALID, "rfx_griffinlim: more than 2^31 - 1 frames in one call");
   if (!(momentum >= 0.f && momentum < 1.f)) return fail(RFX_ERR_INVALID, "rfx_griffinlim: momentum must be in [0, 1)");
-  // every iteration re-analyses the estimate with torch.stft(center=True, reflect): the reference raises there unless the signal
-  // is longer than the n_fft/2 padding
   const int L = rfx_griffinlim_output_samples(plan, T);
-  if (n_iter > 0 && L <= plan->p.n_fft / 2)
-    return fail(RFX_ERR_INVALID,
-                plan->generic ? "rfx_griffinlim: Padding size should be less than the corresponding input dimension (reflect padding " +
-                                    std::to_string(plan->p.n_fft / 2) + " needs more than that many samples)"
-                              : "rfx_griffinlim: Padding size should be less than the corresponding input dimension "
-                                "(reflect padding 8820 needs more than 8820 samples, i.e. at least 22 frames)");
+  if (n_iter > 0 && L <= plan->p.n_fft / 2) return reflect_refusal(plan);
+  if (int rc = guide_refusal(plan, opt, T, d_angles0_slots != nullptr, "rfx_griffinlim")) return rc;
   RFX_ON_DEVICE(plan->device);
   GlCall c{d_mag_slots, (const cf*)d_angles0_slots, d_row_scale, opt.magnitude_hint, momentum / (1.f + momentum), seed,
-           opt.row_base * (uint64_t)T, B, T, L, n_iter, d_wave_out, (char*)d_workspace, workspace_bytes, (hipStream_t)stream};
+           opt.row_base * (uint64_t)T, B, T, L, n_iter, d_wave_out, (char*)d_workspace, workspace_bytes, (hipStream_t)stream,
+           opt.guide, opt.guide_stride, opt.guide_samples};
   LaunchTimer timer(h_launch_ms, n_iter + 1);
   return plan->generic ? gen_griffinlim(plan, c, mag_in_fam_slots, timer) : spec_griffinlim(plan, c, timer);
 }
@@ -423,7 +478,7 @@ int rfx_griffinlim_ex(const rfx_plan* plan, const float* d_mag_slots, const void
                       int T, int n_iter, float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes,
                       void* stream, const rfx_call_options* options, float* h_launch_ms) {
   CallOpt opt;
-  if (int rc = read_call_options(options, &opt, "rfx_griffinlim_ex")) return rc;
+  if (int rc = read_call_options(options, &opt, "rfx_griffinlim_ex", 0, true)) return rc;
   return griffinlim_impl(plan, d_mag_slots, d_angles0_slots, seed, B, T, n_iter, momentum, d_wave_out, d_workspace,
                          workspace_bytes, stream, h_launch_ms, opt);
 }
@@ -605,6 +660,7 @@ static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int 
   if (!plan || !d_mel || !d_wave_out || !d_workspace || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_waveform_from_mel: bad argument");
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_waveform_from_mel")) return rc;
+  if (int rc = guide_refusal(plan, opt, T, false, "rfx_waveform_from_mel")) return rc;
   const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T);
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_waveform_from_mel: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
@@ -628,7 +684,7 @@ int rfx_waveform_from_mel_ex(const rfx_plan* plan, const float* d_mel, int B, in
                              float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream,
                              const rfx_call_options* options) {
   CallOpt opt;
-  if (int rc = read_call_options(options, &opt, "rfx_waveform_from_mel_ex", RFX_CALL_INVERSE_MEL_LSTSQ)) return rc;
+  if (int rc = read_call_options(options, &opt, "rfx_waveform_from_mel_ex", RFX_CALL_INVERSE_MEL_LSTSQ, true)) return rc;
   return waveform_from_mel_impl(plan, d_mel, B, T, channels_per_clip, seed, n_iter, momentum, d_wave_out, d_workspace, workspace_bytes, stream, opt);
 }
 
@@ -664,6 +720,7 @@ static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int
     return fail(RFX_ERR_INVALID, "rfx_audio_from_image_u8: bad argument");
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_audio_from_image_u8")) return rc;
+  if (int rc = guide_refusal(plan, opt, T, false, "rfx_audio_from_image_u8")) return rc;
   const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T);
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_audio_from_image_u8: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
@@ -688,7 +745,7 @@ int rfx_audio_from_image_u8_ex(const rfx_plan* plan, const uint8_t* d_img, int N
                                int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
                                size_t workspace_bytes, void* stream, const rfx_call_options* options) {
   CallOpt opt;
-  if (int rc = read_call_options(options, &opt, "rfx_audio_from_image_u8_ex", RFX_CALL_INVERSE_MEL_LSTSQ)) return rc;
+  if (int rc = read_call_options(options, &opt, "rfx_audio_from_image_u8_ex", RFX_CALL_INVERSE_MEL_LSTSQ, true)) return rc;
   return audio_from_image_impl(plan, d_img, N, T, stereo, d_lut256, seed, n_iter, momentum, normalize, d_clip_peak, d_pcm_out, d_workspace,
                                workspace_bytes, stream, opt);
 }

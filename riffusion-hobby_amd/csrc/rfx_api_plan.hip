@@ -33,7 +33,7 @@ int rfx::fail(int code, const std::string& msg) {
 }
 
 const char* rfx_last_error(void) { return g_err.c_str(); }
-int rfx_version(void) { return 1; }
+int rfx_version(void) { return 2; }  // 2: rfx_guided_call_options; rfx_call_options.reserved is checked
 int rfx_frame_stride(void) { return kFrameStride; }
 int rfx_num_bins(void) { return kBins; }
 int rfx_plan_frame_stride(const rfx_plan* plan) { return plan ? plan->frame_stride : 0; }

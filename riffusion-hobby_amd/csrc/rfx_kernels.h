@@ -478,6 +478,14 @@ size_t qual_partials_bytes(int rows, int T);
 hipError_t launch_spectral_sums(const float* a, const float* m, int rows, int T, int fs, int n_stft, bool plain, void* partials, double* sums,
                                 hipStream_t s);
 
+// guide staging of a guided Griffin-Lim call (rfx_guide.hip, arithmetic in rfx_guide_core.h): row r of guide (B rows of
+// guide_samples floats, `stride` elements apart), cut or zero-padded to L samples and times the power of two that brings its peak
+// to 2^15, divided by row_scale[2 r] when a table is given (the specialised engine's kernels multiply by it), into dst[r][Lpad];
+// zero[r][Lpad] (nullable) is zeroed.  peaks: scratch of B * guide_chunks(Lpad) floats (rfx_guide_core.h; fewer than B * Lpad).
+// Lpad a multiple of 64, dst and zero 16-byte aligned; the guide needs float alignment only.
+hipError_t launch_guide_stage(const float* guide, long long stride, int guide_samples, int B, int L, int Lpad, const float* row_scale,
+                              float* peaks, float* dst, float* zero, hipStream_t stream);
+
 // closed-form InverseMelScale (rfx_imel_lstsq.hip, arithmetic in rfx_imel_lstsq_core.h).  The plan's tables: the float32
 // L D L^T factors of fb^T fb - nl[m] = -L[m + 1][m] (nl[M - 1] = 0), inv_d[m] = 1 / D[m] - and, for every position of an output
 // frame, its bin's first filter and two weights (a position that holds no bin, or a bin no filter reaches: M, 0, 0).

@@ -100,6 +100,28 @@ def call_options(row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = F
     return RfxCallOptions(ctypes.sizeof(RfxCallOptions), CALL_INVERSE_MEL_LSTSQ if lstsq else 0, int(row_base), float(magnitude_hint), 0.0)
 
 
+class RfxGuidedCallOptions(ctypes.Structure):
+    """rfx_guided_call_options of include/rfx.h: rfx_call_options grown at its tail by the guide of a phase-guided Griffin-Lim start."""
+
+    _fields_ = RfxCallOptions._fields_ + [("d_guide", ctypes.c_void_p), ("guide_stride", ctypes.c_int64),
+                                          ("guide_samples", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
+
+
+def guided_call_options(guide: T.Optional[torch.Tensor], rows: int, row_base: int = 0, magnitude_hint: float = 0.0,
+                        lstsq: bool = False) -> T.Union[RfxCallOptions, RfxGuidedCallOptions]:
+    """`call_options`, with the guide of a guided call: a (rows, Lg) float32 device tensor whose samples are contiguous (rows may be
+    strided); None gives the plain options.  The caller keeps `guide` alive until the call is issued."""
+    o = call_options(row_base, magnitude_hint, lstsq)
+    if guide is None:
+        return o
+    if guide.dtype != torch.float32 or guide.dim() != 2 or guide.shape[0] != rows or guide.shape[1] < 1:
+        raise ValueError(f"guide must be a ({rows}, Lg) float32 tensor with Lg >= 1, got {tuple(guide.shape)} {guide.dtype}")
+    if guide.stride(1) != 1 or (rows > 1 and guide.stride(0) < guide.shape[1]):
+        raise ValueError("guide rows must be contiguous runs of samples that do not overlap")
+    return RfxGuidedCallOptions(ctypes.sizeof(RfxGuidedCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, guide.data_ptr(),
+                                guide.stride(0) if rows > 1 else guide.shape[1], guide.shape[1], 0)
+
+
 def check_inverse_mel(inverse_mel: str) -> bool:
     """True for "lstsq", False for "sgd"; anything else raises."""
     if inverse_mel not in INVERSE_MEL_FORMS:
@@ -540,6 +562,15 @@ class Plan:
             raise RfxError(f"tensor on {t.device} handed to a plan that lives on {self.device}")
         return (t if dtype is None else t.to(dtype)).contiguous()
 
+    def _chk_guide(self, guide: torch.Tensor) -> torch.Tensor:
+        """a guide as the library reads it: float32 on the plan's device, samples contiguous (a strided view of rows is passed as it is)"""
+        if guide.device != self.device:
+            raise ValueError(f"tensor on {guide.device}, plan on {self.device}")
+        if guide.dtype != torch.float32 or guide.dim() != 2:
+            raise ValueError(f"guide must be a (rows, Lg) float32 tensor, got {tuple(guide.shape)} {guide.dtype}")
+        ok = guide.stride(1) == 1 and (guide.shape[0] == 1 or guide.stride(0) >= guide.shape[1])
+        return guide if ok else guide.contiguous()
+
     def _stream(self) -> int:
         return current_stream(self.device)
 
@@ -603,13 +634,21 @@ class Plan:
         launch_ms: T.Optional[T.Any] = None,
         row_base: int = 0,
         magnitude_hint: float = 0.0,
+        guide: T.Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
         """GriffinLim on magnitudes in slot layout -> (B, samples).  `row_base`: index of the call's first row in the caller's
         whole batch (the random phases of row r are drawn from (seed, row_base + r): chunked and sharded batches get the starts
-        of the single call); `magnitude_hint`: an upper bound of the magnitudes if the caller knows one (rfx_call_options)."""
+        of the single call); `magnitude_hint`: an upper bound of the magnitudes if the caller knows one (rfx_call_options).
+        `guide`: (B, Lg) float32 waveforms on the plan's device, any units; every row starts from the phase of its guide's STFT
+        (the row cut or zero-padded to the output length) instead of random phases (rfx_guided_call_options): no randomness,
+        `seed` and `row_base` then change nothing."""
         mag_slots = self._chk(mag_slots, torch.float32)
         if angles0_slots is not None:
             angles0_slots = self._chk(angles0_slots, torch.complex64)
+        if guide is not None:
+            if angles0_slots is not None:
+                raise ValueError("a guide and angles0_slots are two starts: give one")
+            guide = self._chk_guide(guide)
         if mag_slots.numel() < B * Tn * self.frame_stride:
             raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
         need = self.lib.rfx_griffinlim_workspace_bytes(self.handle, B, Tn)
@@ -617,9 +656,9 @@ class Plan:
             workspace = self._chk(workspace)
         if workspace is None or workspace.numel() < need:  # no (or too small a) caller-owned workspace: the plan's arena
             with self._workspace(need) as ws:
-                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint)
+                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide)
         out = torch.empty((B, self.lib.rfx_griffinlim_output_samples(self.handle, Tn)), dtype=torch.float32, device=mag_slots.device)
-        opt = call_options(row_base, magnitude_hint)
+        opt = guided_call_options(guide, B, row_base, magnitude_hint)
         check(
             self.lib.rfx_griffinlim_ex(
                 self.handle,
@@ -879,9 +918,11 @@ class Plan:
         return out, status_np
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
-                          row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False) -> torch.Tensor:
+                          row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False,
+                          guide: T.Optional[torch.Tensor] = None) -> torch.Tensor:
         """spectrogram_converter.py:187-204 in one call: (B, n_mels, T) -> (B, hop * (T - 1)); `inverse_mel` (seed) + `griffinlim`
-        (seed + 1), same bits, the linear magnitudes stay in the workspace.  `lstsq`: `inverse_mel_lstsq` in place of the SGD."""
+        (seed + 1), same bits, the linear magnitudes stay in the workspace.  `lstsq`: `inverse_mel_lstsq` in place of the SGD.
+        `guide`: (B, Lg) float32 waveforms, as in `griffinlim`."""
         if lstsq:
             self.require_lstsq()
         mel = self._chk(mel, torch.float32)
@@ -889,7 +930,9 @@ class Plan:
         if M != self.n_mels:
             raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")  # torchaudio's message
         out = torch.empty((B, self.lib.rfx_griffinlim_output_samples(self.handle, Tn)), dtype=torch.float32, device=mel.device)
-        opt = call_options(row_base, magnitude_hint, lstsq)
+        if guide is not None:
+            guide = self._chk_guide(guide)
+        opt = guided_call_options(guide, B, row_base, magnitude_hint, lstsq)
         with self._workspace(self.lib.rfx_waveform_from_mel_workspace_bytes(self.handle, B, Tn)) as ws:
             check(self.lib.rfx_waveform_from_mel_ex(self.handle, mel.data_ptr(), B, Tn, channels_per_clip, seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
@@ -902,11 +945,12 @@ class Plan:
 
     def audio_from_image(self, img: torch.Tensor, stereo: bool, lut: torch.Tensor, n_iter: int, momentum: float = 0.99, seed: int = 0,
                          normalize: bool = True, out: T.Optional[torch.Tensor] = None, workspace: T.Optional[torch.Tensor] = None,
-                         clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False):
+                         clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None):
         """spectrogram_image_converter.py:54-91 on the device in one call: (N, n_mels, T, 3) uint8 -> ((N, L, C) int16, per-clip peak (N,));
         `image_decode` + `waveform_from_mel` (clips of C rows) + `pcm16`, same bytes.  `out` as in `pcm16`.  `clip_base`: index of
         the call's first image in the caller's whole batch (row_base = clip_base * C); `magnitude_hint`: the image path's
-        max_value (the largest entry of `lut`); `lstsq`: the closed-form InverseMelScale in place of the SGD."""
+        max_value (the largest entry of `lut`); `lstsq`: the closed-form InverseMelScale in place of the SGD; `guide`: (N * C, Lg)
+        float32 waveforms, image after image and channel after channel, as in `griffinlim`."""
         if img.dtype != torch.uint8 or img.dim() != 4:
             raise ValueError("expected (N, H, W, 3) uint8 images")
         if lstsq:
@@ -929,9 +973,11 @@ class Plan:
         if ws is None or ws.numel() < need:
             with self._workspace(need) as borrowed:
                 return self.audio_from_image(img, stereo, lut, n_iter, momentum, seed, normalize, out=pcm, workspace=borrowed,
-                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq)
+                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide)
         peak = torch.zeros((N,), dtype=torch.float32, device=img.device)
-        opt = call_options(clip_base * C, magnitude_hint, lstsq)
+        if guide is not None:
+            guide = self._chk_guide(guide)
+        opt = guided_call_options(guide, N * C, clip_base * C, magnitude_hint, lstsq)
         check(self.lib.rfx_audio_from_image_u8_ex(self.handle, img.data_ptr(), N, W, int(stereo), lut.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                   int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return pcm, peak

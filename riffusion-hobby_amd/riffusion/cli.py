@@ -62,13 +62,19 @@ def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_freque
     print(f"Wrote {image}")
 
 
-def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto") -> None:
+def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto",
+                   guide_audio: str = "", griffin_lim_iters: int = -1) -> None:
     """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD,
-    --frame-engine chirp-z runs parameters whose FFT length has a prime factor above 13 (refused otherwise)."""
+    --frame-engine chirp-z runs parameters whose FFT length has a prime factor above 13 (refused otherwise).
+    --guide-audio FILE starts Griffin-Lim from the phase of that clip (audio-to-audio: the clip the tile was made of; it must be at
+    the tile's sample rate) instead of random phases, --griffin-lim-iters N runs N iterations instead of the params' 32 (a guided
+    decode needs 0 to 4)."""
     pil_image = Image.open(image)
     params = _params_from_image(pil_image)
     converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
-    segment = converter.audio_from_spectrogram_image(pil_image, apply_filters=True, inverse_mel=inverse_mel)
+    segment = converter.audio_from_spectrogram_image(pil_image, apply_filters=True, inverse_mel=inverse_mel,
+                                                     guide_segment=_load_segment(guide_audio) if guide_audio else None,
+                                                     griffin_lim_iters=griffin_lim_iters if griffin_lim_iters >= 0 else None)
     segment.export(audio, format=os.path.splitext(audio)[1][1:] or "wav")
     print(f"Wrote {audio} ({segment.duration_seconds:.2f} seconds)")
 

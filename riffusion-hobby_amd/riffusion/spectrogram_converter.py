@@ -162,6 +162,7 @@ class SpectrogramConverter:
         seed: T.Optional[int] = None,
         channels_per_clip: T.Optional[int] = None,
         inverse_mel: str = "sgd",
+        guide: T.Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
         """
         (B, n_mels, T) -> (B, hop*(T-1)).  The reference treats the whole batch as ONE clip (the SGD
@@ -172,18 +173,26 @@ class SpectrogramConverter:
         `inverse_mel="lstsq"` takes torchaudio >= 2.1's InverseMelScale - relu of the minimum-norm least-squares solution, in
         closed form on the device (rfx_inverse_mel_lstsq) - in place of the SGD: no random start (`spec0` is refused), no
         coupling of rows; a bank it does not serve raises ValueError with the library's reason.
+        `guide`: (B, Lg) float32 waveforms, any units; Griffin-Lim starts every row from the phase of its guide's STFT (the row
+        cut or zero-padded at its end to hop*(T-1) samples) instead of random phases - in an audio-to-audio workflow the source
+        clip, whose phase is nearly right already.  No randomness is left in Griffin-Lim then; a silent guide row gives a silent
+        row.  Not together with `angles0`: they are two starts.
         """
+        if guide is not None and angles0 is not None:
+            raise ValueError("guide and angles0 are two starts of Griffin-Lim: give one")
         return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
-                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel)
+                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide)
 
     def _waveform_from_mel(self, plan: T.Any, amplitudes_mel: torch.Tensor, *, spec0: T.Optional[torch.Tensor] = None,
                            angles0: T.Optional[torch.Tensor] = None, seed: T.Optional[int] = None,
                            channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0,
-                           return_slots: bool = False, inverse_mel: str = "sgd") -> T.Any:
+                           return_slots: bool = False, inverse_mel: str = "sgd", guide: T.Optional[torch.Tensor] = None,
+                           n_iter: T.Optional[int] = None) -> T.Any:
         """`waveform_from_mel_amplitudes` on a plan the caller already holds (the batch entry points fetch it once per call,
         not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild).
         `return_slots=True` runs the two inverse stages separately - same bits as the one call - and returns
-        (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares."""
+        (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares.  `guide`: (B, Lg) float32 guide
+        waveforms (`waveform_from_mel_amplitudes`); `n_iter`: Griffin-Lim iterations in place of the params'."""
         from riffusion import _hip
 
         lstsq = _hip.check_inverse_mel(inverse_mel)
@@ -195,17 +204,20 @@ class SpectrogramConverter:
         B, _, Tn = mel.shape
         cpc = B if channels_per_clip is None else channels_per_clip
         s = self._seed(seed)
+        n_iter = self.p.num_griffin_lim_iters if n_iter is None else int(n_iter)
+        if guide is not None:
+            guide = guide.to(self.device, torch.float32)
         if spec0 is None and angles0 is None and not return_slots:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
-            return plan.waveform_from_mel(mel, cpc, self.p.num_griffin_lim_iters, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint,
-                                          lstsq=lstsq)
+            return plan.waveform_from_mel(mel, cpc, n_iter, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint,
+                                          lstsq=lstsq, guide=guide)
         spec0 = spec0.to(self.device) if spec0 is not None else None
         if lstsq:
             lin_slots = plan.inverse_mel_lstsq(mel)
         else:
             lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         a0 = plan.pack_complex(angles0.to(self.device)) if angles0 is not None else None
-        wave = plan.griffinlim(lin_slots, B, Tn, self.p.num_griffin_lim_iters, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
-                               magnitude_hint=magnitude_hint)
+        wave = plan.griffinlim(lin_slots, B, Tn, n_iter, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
+                               magnitude_hint=magnitude_hint, guide=guide)
         return (wave, lin_slots) if return_slots else wave
 
     # ---- quality of a decode ------------------------------------------------------------------------

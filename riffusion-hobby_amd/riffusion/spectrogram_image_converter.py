@@ -60,13 +60,26 @@ class SpectrogramImageConverter:
         max_value: float = 30e6,
         *,
         inverse_mel: str = "sgd",
+        guide_segment: T.Any = None,
+        griffin_lim_iters: T.Optional[int] = None,
     ) -> T.Any:
         """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference).  The filters
         (audio_util.apply_filters, compression=False) run on the device: same bytes.  `inverse_mel`: "sgd" (default) or
-        "lstsq", as in `audio_from_spectrogram_images`."""
+        "lstsq", as in `audio_from_spectrogram_images`.  `guide_segment`: a PcmSegment or pydub segment at the params' sample
+        rate (ValueError otherwise) whose phase starts Griffin-Lim - the clip the tile was made of, in audio-to-audio; mono
+        guides both channels of a stereo tile, more channels than the tile's are mixed down.  `griffin_lim_iters`: iterations for
+        this call in place of the params' (a guided decode needs few).  Both as in `audio_from_spectrogram_images`."""
+        guides = None
+        if guide_segment is not None:
+            if int(guide_segment.frame_rate) != self.p.sample_rate:
+                raise ValueError(f"guide_segment is at {guide_segment.frame_rate} Hz, the params say {self.p.sample_rate} Hz: resample it first")
+            C = 2 if self.p.stereo else 1
+            if guide_segment.channels > C:
+                guide_segment = guide_segment.set_channels(C)
+            guides = np.array([c.get_array_of_samples() for c in guide_segment.split_to_mono()]).astype(np.float32)[None]
         pcm = self.audio_from_spectrogram_images(
             np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters,
-            inverse_mel=inverse_mel,
+            inverse_mel=inverse_mel, guide_waveforms=guides, griffin_lim_iters=griffin_lim_iters,
         )
         return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
 
@@ -450,6 +463,8 @@ class SpectrogramImageConverter:
         return_error: bool = False,
         *,
         inverse_mel: str = "sgd",
+        guide_waveforms: T.Any = None,
+        griffin_lim_iters: T.Optional[int] = None,
     ) -> T.Any:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -509,6 +524,15 @@ class SpectrogramImageConverter:
         audio still depends on (the clip, the seed, its index) alone: Griffin-Lim's phases come from the seed as before.  Works
         with every other option.  A bank it does not serve (`Plan.lstsq_ok`) raises ValueError with the library's reason before
         any GPU work; any other value raises ValueError.
+        `guide_waveforms`: (N, C, Lg) float32 or int16 waveforms, an array or a tensor on any device, in any units - tile i's
+        Griffin-Lim starts from the phase of guide i's STFT instead of random phases (rfx_guided_call_options).  In an
+        audio-to-audio workflow the guides are the source clips the tiles were made of: their phase is nearly right already, and
+        a guided decode at 0 to 4 iterations reconstructs better than the random start at 32 (README: phase-guided decode).  C is
+        the tiles' channel count, or 1: a mono guide serves both channels of a stereo tile.  A guide is cut, or zero-padded at
+        its end, to the clip length; a silent guide row gives a silent row, a padded tail starts silent and is filled by the
+        iterations.  Guides are chunked and sharded with their tiles and go with every other option; Griffin-Lim then has no
+        randomness (with "lstsq" the whole decode has none).
+        `griffin_lim_iters`: Griffin-Lim iterations of this call in place of `params.num_griffin_lim_iters`, guided or not.
         """
         from riffusion import batch_shard
 
@@ -547,6 +571,24 @@ class SpectrogramImageConverter:
             imgs = self.quantize_pipeline_images(imgs)
         n_total = imgs.shape[0]
         C = 2 if self.p.stereo else 1
+        n_iter = self.p.num_griffin_lim_iters if griffin_lim_iters is None else int(griffin_lim_iters)
+        if n_iter < 0:
+            raise ValueError(f"griffin_lim_iters must be >= 0, got {griffin_lim_iters}")
+        guides = None
+        if guide_waveforms is not None:
+            guides = torch.as_tensor(np.ascontiguousarray(guide_waveforms) if isinstance(guide_waveforms, np.ndarray) else guide_waveforms)
+            if guides.dim() != 3 or guides.shape[0] != n_total or guides.shape[1] not in (1, C) or guides.shape[2] < 1:
+                raise ValueError(f"guide_waveforms must be ({n_total}, {C} or 1, samples), got {tuple(guides.shape)}")
+            if guides.dtype not in (torch.float32, torch.int16):
+                raise ValueError(f"guide_waveforms must be float32 or int16, got {guides.dtype}")
+
+        def guide_rows(a: int, b: int) -> T.Optional[torch.Tensor]:
+            """the guides of tiles [a, b) as the (rows, Lg) float32 device tensor of the chunk's clip-channels"""
+            if guides is None:
+                return None
+            g = guides[a:b].to(plan.device, torch.float32)
+            return g.expand(b - a, C, g.shape[2]).reshape((b - a) * C, g.shape[2])
+
         if size is not None:
             size = (int(size[0]), int(size[1]))
         L = plan.lib.rfx_griffinlim_output_samples(plan.handle, size[0] if size is not None else int(imgs.shape[2]))
@@ -576,7 +618,8 @@ class SpectrogramImageConverter:
                 if return_error:  # the stages one by one (same bytes as the fused calls below): the error needs both ends of Griffin-Lim
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave, lin_slots = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C,
-                                                              magnitude_hint=max_value, return_slots=True, inverse_mel=inverse_mel)
+                                                              magnitude_hint=max_value, return_slots=True, inverse_mel=inverse_mel,
+                                                              guide=guide_rows(a, b), n_iter=n_iter)
                     error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1])).reshape(b - a, C, 2).sum(1))
                     if return_waveform:
                         out = wave.reshape(b - a, C, -1)
@@ -587,12 +630,13 @@ class SpectrogramImageConverter:
                 elif return_waveform:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value,
-                                                   inverse_mel=inverse_mel)
+                                                   inverse_mel=inverse_mel, guide=guide_rows(a, b), n_iter=n_iter)
                     out = wave.reshape(b - a, C, -1)
                 else:  # uint8 tiles -> int16 PCM in one call (rfx_audio_from_image_u8_ex), same bytes as the three calls above + pcm16
                     dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
-                    out = plan.audio_from_image(tiles, self.p.stereo, lut, self.p.num_griffin_lim_iters, 0.99, seed=base_seed,
-                                                normalize=True, out=dst, clip_base=a, magnitude_hint=max_value, lstsq=lstsq)[0]
+                    out = plan.audio_from_image(tiles, self.p.stereo, lut, n_iter, 0.99, seed=base_seed,
+                                                normalize=True, out=dst, clip_base=a, magnitude_hint=max_value, lstsq=lstsq,
+                                                guide=guide_rows(a, b))[0]
                     if apply_filters:
                         out = self._filter_pcm(plan, out, compression)
                 # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them
