@@ -128,6 +128,8 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
 int rfx_plan_griffinlim_engine(const rfx_plan* plan);
 /* the form (RFX_GL_FORM_RUNS / _FRAMES) an rfx_griffinlim call of B x T frames takes on this plan */
 int rfx_griffinlim_form(const rfx_plan* plan, int B, int T);
+/* (A call with held frames - rfx_held_call_options.d_hold_frames - always takes RFX_GL_FORM_FRAMES on the specialised engine, whatever
+ * the plan's gl_form or this rule says: the run form keeps no frame buffer to hold frames in.  Both forms give a clip the same bits.) */
 /* How one launch of the run-based form cuts the call's B*T frames (counted clip after clip) into runs, one per workgroup: returns
  * the number of runs and, if run_starts != NULL, writes min(runs + 1, capacity) run boundaries (run b = frames
  * [run_starts[b], run_starts[b + 1])).  which = 0: the first (synthesis-only) launch, 1: the iterations.  0 for a generic plan.
@@ -277,6 +279,43 @@ typedef struct {
   int32_t reserved2;        /* must be 0 */
 } rfx_guided_call_options;
 
+/* rfx_guided_call_options grown once more, by the same mechanism (struct_size = sizeof(rfx_held_call_options); the first nine fields
+ * are rfx_guided_call_options' own): HELD FRAMES.  A guided call uses the guide as a start and every iteration may move every frame;
+ * where part of the clip is known audio (a continuation's left part, the kept spans of a partial regeneration, two known ends) the
+ * frames of that part can be held at the guide's phase instead.
+ *
+ * d_hold_frames != NULL: (B, 2) int32 {head, tail} per row on the plan's device, 4-byte aligned.  Frame t of a row with T frames is
+ * held iff t < h or t >= T - l, h = clamp(head, 0, T), l = clamp(tail, 0, T - h): any int32 pair is legal, device data is clamped, not
+ * validated.  In the reference's loop, after `angles = angles.div(angles.abs().add(1e-16))`, angles[..., held] = a0[..., held] with a0
+ * the guided start's angles; everything else stays as it is (tprev = rebuilt for all frames).  Exact consequences:
+ *   (0, 0) for a row gives that row the bytes of the guided call (d_hold_frames == NULL);
+ *   h + l == T gives that row the bytes of the guided call with n_iter == 0, whatever n_iter is;
+ *   a sample covered only by held frames (every frame whose window reaches it is held) has at any n_iter the bytes it has at n_iter == 0.
+ * A row's bytes depend on its magnitudes, its guide row and its pair alone - not on the other rows' pairs, its place in the batch, seed
+ * or row_base.  Only the phase is held: the magnitudes stay the call's.
+ * On the device the synthesis frame of a held frame is written once, by the first launch, and only read afterwards: the call compacts
+ * the free frames into a list in its workspace (three small launches, no host read, no synchronisation, nothing allocated) and launches
+ * 1 .. n_iter walk that list, so a held call does less work in proportion to what it holds.  h_launch_ms keeps n_iter + 1 entries, [0]
+ * including the staging and the compaction.
+ * Workspace: the *_held_workspace_bytes twin of the entry's query (the frame list, B T + a few int32, and on the specialised engine
+ * the frame buffer of the per-frame form: a held call always takes that form, see rfx_griffinlim_form); at least the unheld query.
+ * RFX_ERR_INVALID before any launch: d_hold_frames without d_guide, a pointer off 4-byte alignment, reserved3 != 0;
+ * RFX_ERR_WORKSPACE: a workspace below the held query.  Honoured by the three entries that honour a guide; rfx_inverse_mel_ex refuses
+ * it. */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t flags;
+  uint64_t row_base;
+  float magnitude_hint;
+  float reserved;           /* must be 0 */
+  const float* d_guide;
+  int64_t guide_stride;
+  int32_t guide_samples;
+  int32_t reserved2;        /* must be 0 */
+  const int32_t* d_hold_frames; /* NULL: nothing held (the call is rfx_guided_call_options' call) */
+  uint64_t reserved3;       /* must be 0 */
+} rfx_held_call_options;
+
 /* ---- layout converters ------------------------------------------------------------------- */
 /* (B, n_stft, T) float32 magnitudes -> slots (float32) */
 int rfx_pack_magnitudes(const rfx_plan* plan, const float* d_lin_bft, int B, int T, float* d_slots, void* stream);
@@ -326,6 +365,8 @@ int rfx_spectral_error(const rfx_plan* plan, const float* d_wave /* (B, L) */, c
  * per-frame kernel + fold (two launches per iteration, every frame its own workgroup) for the few-tiles-per-request case;
  * the workspace query below accounts for whichever the shape will take. */
 size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T);
+/* ... of a call with held frames (rfx_held_call_options.d_hold_frames != NULL) */
+size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T);
 /* samples per clip rfx_griffinlim writes for T frames: what torch.istft(center=True, length=None) returns,
  * hop*(T-1), plus one when n_fft is odd */
 int rfx_griffinlim_output_samples(const rfx_plan* plan, int T);
@@ -438,6 +479,7 @@ int rfx_inverse_mel_lstsq(const rfx_plan* plan, const float* d_mel, int B, int T
  * rfx_inverse_mel; both random starts from `seed` (the SGD start from seed, the phases from seed + 1).  Exactly rfx_inverse_mel
  * followed by rfx_griffinlim - same bits - with the linear magnitudes kept inside the workspace. */
 size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T);
+size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T);  /* with held frames (rfx_held_call_options) */
 int rfx_waveform_from_mel(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                           float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream);
 
@@ -658,6 +700,7 @@ int rfx_pcm16_clips_to_waveform(const int16_t* d_pcm, int64_t frames, int in_cha
  * rfx_image_decode_u8, rfx_waveform_from_mel (clips of C rows, `seed`), rfx_pcm16 - same bytes - with the tensors in between
  * kept inside the workspace. */
 size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);
+size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* with held frames (rfx_held_call_options) */
 int rfx_audio_from_image_u8(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                             int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
                             size_t workspace_bytes, void* stream);

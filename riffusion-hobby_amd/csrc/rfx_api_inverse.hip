@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "rfx_api.h"
+#include "rfx_guide_core.h"
 
 using namespace rfx;
 
@@ -144,20 +145,23 @@ int rfx_griffinlim_form(const rfx_plan* plan, int B, int T) {
 
 // Specialised engine: three generations (x_{k-1}, x_k, x_{k+1}) of the two parity audio buffers, the istft normalisation table,
 // the synthesis frames of the per-frame form, and the call's own row-scale table (GlArgs::row_scale).  No spectral state is kept
-// between iterations (see rfx_gl.hip).
+// between iterations (see rfx_gl.hip).  held (a call with rfx_held_call_options.d_hold_frames): always the per-frame form and its frame
+// buffer, and the free-frame list behind everything an unheld call has.
 struct GlLayout {
-  size_t audio, scale, frames, row_scale, total;
+  size_t audio, scale, frames, row_scale, list, total;
   int Lpad;
 };
-static GlLayout gl_layout(const rfx_plan* plan, int B, int T) {
+static size_t hold_list_bytes(int B, int T) { return hold_list_words(B, T) * sizeof(int32_t); }
+static GlLayout gl_layout(const rfx_plan* plan, int B, int T, bool held = false) {
   GlLayout l{};
   if (B <= 0 || T < 2) return l;
   l.Lpad = (int)align_up((size_t)kHop * (T - 1), 64);
   Carve c;
   l.audio = c.take(6 * (size_t)B * l.Lpad * sizeof(float));
   l.scale = c.take((size_t)l.Lpad * sizeof(float));
-  l.frames = c.take(gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
+  l.frames = c.take(held || gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
   l.row_scale = c.take(range_table_bytes(B));
+  l.list = c.take(held ? hold_list_bytes(B, T) : 0);
   l.total = c.at;
   return l;
 }
@@ -166,12 +170,13 @@ static GlLayout gl_layout(const rfx_plan* plan, int B, int T) {
 static int gen_out_len(const GenGeom& g, int T) { return g.hop * (T - 1) + (g.n_fft & 1); }
 
 // Generic engine: the windowed synthesis frames, three generations of the audio estimate (x_{k-1}, x_k read; x_{k+1} written) and
-// the window envelope of the fold, [Lpad]; on a row family the magnitudes re-ordered into slot order; the row-scale table
+// the window envelope of the fold, [Lpad]; on a row family the magnitudes re-ordered into slot order; the row-scale table; held: the
+// free-frame list
 struct GenGlLayout {
-  size_t frames, audio, repacked, row_scale, total;
+  size_t frames, audio, repacked, row_scale, list, total;
   int Lpad;
 };
-static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T) {
+static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T, bool held = false) {
   GenGlLayout l{};
   if (B <= 0 || T < 2) return l;
   const GenGeom& g = plan->gg;
@@ -182,14 +187,17 @@ static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T) {
   l.audio = c.take((3 * (size_t)B + 1) * l.Lpad * sizeof(float));
   l.repacked = c.take(plan->fam_ok ? nf * plan->fam.fsf * sizeof(float) : 0);
   l.row_scale = c.take(range_table_bytes(B));
+  l.list = c.take(held ? hold_list_bytes(B, T) : 0);
   l.total = c.at;
   return l;
 }
 
-size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) {
+static size_t griffinlim_workspace(const rfx_plan* plan, int B, int T, bool held) {
   if (!plan) return 0;
-  return plan->generic ? gen_gl_layout(plan, B, T).total : gl_layout(plan, B, T).total;
+  return plan->generic ? gen_gl_layout(plan, B, T, held).total : gl_layout(plan, B, T, held).total;
 }
+size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, false); }
+size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, true); }
 
 // rfx_call_options as the entry points below see them (NULL / short struct = defaults)
 struct CallOpt {
@@ -200,6 +208,8 @@ struct CallOpt {
   const float* guide = nullptr;
   int64_t guide_stride = 0;
   int guide_samples = 0;
+  // rfx_held_call_options: (B, 2) {head, tail} of the frames held at the guide's phase (null: a guided call holds nothing)
+  const int32_t* hold = nullptr;
 };
 // allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves); takes_guide: it runs Griffin-Lim
 static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who, uint32_t allowed_flags = 0, bool takes_guide = false) {
@@ -232,6 +242,17 @@ static int read_call_options(const rfx_call_options* o, CallOpt* out, const char
       out->guide_samples = g->guide_samples;
     }
   }
+  // the held tail (rfx_held_call_options: grown once more)
+  if (o->struct_size >= offsetof(rfx_held_call_options, reserved3) + sizeof(uint64_t)) {
+    const rfx_held_call_options* h = reinterpret_cast<const rfx_held_call_options*>(o);
+    if (h->reserved3 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_held_call_options.reserved3 must be 0");
+    if (h->d_hold_frames) {
+      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and holds no frames (d_hold_frames must be NULL)");
+      if (!out->guide) return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_frames needs a guide to hold the frames at (d_guide is NULL)");
+      if ((uintptr_t)h->d_hold_frames & (sizeof(int32_t) - 1)) return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_frames must be aligned to 4 bytes");
+      out->hold = h->d_hold_frames;
+    }
+  }
   return RFX_OK;
 }
 
@@ -250,6 +271,8 @@ struct GlCall {
   const float* guide;  // null, or (B, guide_samples) rows guide_stride apart: launch 0 is MODE 1 on the staged guide (rfx_guide.hip)
   int64_t guide_stride;
   int guide_samples;
+  const int32_t* hold;  // null, or (B, 2) {head, tail}: launches 1 .. n_iter walk the free-frame list (rfx_guide_core.h) and leave the held
+                        // frames' synthesis frames as launch 0 wrote them
 };
 // ... and the fields that all four argument blocks have
 template <class Args>
@@ -289,7 +312,7 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   const GenGeom& g = plan->gg;
   const int B = c.B, T = c.T, L = c.L;
   const bool fam = plan->fam_ok;
-  const GenGlLayout w = gen_gl_layout(plan, B, T);
+  const GenGlLayout w = gen_gl_layout(plan, B, T, c.hold != nullptr);
   if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   float* frames = (float*)(c.ws + w.frames);
   float* gen[3];
@@ -308,6 +331,10 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   // the fold of launch 1: the staging's scratch)
   if (c.guide)
     if (int rc = gl_stage_guide(c, w.Lpad, true, gen[1], gen[2], nullptr)) return rc;
+  // held: nothing but the frame kernels writes `frames` from here on (the fold reads them), so what launch 0 writes for a held frame
+  // is what every later fold reads
+  int* list = (int*)(c.ws + w.list);
+  if (c.hold) RFX_HIP(launch_hold_list(c.hold, B, T, list, c.stream));
   FamGlArgs fa{};
   GenGlArgs ga{};
   int nblocks = 0;
@@ -340,9 +367,14 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   }
   for (int it = 0; it <= c.n_iter; ++it) {
     const int mode = it == 0 && !c.guide ? 0 : 1;
-    RFX_HIP(fam         ? launch_fam_gl(mode, fa, nblocks, c.stream)
-            : plan->czt ? launch_czt_gl(mode, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
-                        : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
+    if (c.hold && it > 0)
+      RFX_HIP(fam         ? launch_fam_gl_list(fa, list, nblocks, c.stream)
+              : plan->czt ? launch_czt_gl_list(ga, list, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
+                          : launch_gen_gl_list(ga, list, plan->num_cus, c.stream));
+    else
+      RFX_HIP(fam         ? launch_fam_gl(mode, fa, nblocks, c.stream)
+              : plan->czt ? launch_czt_gl(mode, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
+                          : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
     const bool last = it == c.n_iter;
     RFX_HIP(launch_gen_fold(frames, env, last ? c.out : gen[it % 2], g, B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
                             it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale));
@@ -355,7 +387,7 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
 // Specialised engine: the per-frame form (frame kernel + fold per iteration) or the run form (one kernel per iteration)
 static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) {
   const int B = c.B, T = c.T, L = c.L;
-  const GlLayout w = gl_layout(plan, B, T);
+  const GlLayout w = gl_layout(plan, B, T, c.hold != nullptr);
   if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   float* gen[3][2];  // x_k lives in generation k % 3
   for (int i = 0; i < 3; ++i)
@@ -365,7 +397,7 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
   RFX_HIP(hipGetLastError());
   if (int rc = gl_row_scale(c, (size_t)T * kFrameStride, (float*)(c.ws + w.row_scale))) return rc;
 
-  if (gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
+  if (c.hold || gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
     GlFrameArgs fa;
     set_gl_args(fa, c);
     fa.frames = (float*)(c.ws + w.frames);
@@ -378,10 +410,14 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
     // guided: launch 0 is MODE 1 on the guide, staged where it reads its input (gen[2][0]; gen[1][0] is free until launch 1's fold)
     if (c.guide)
       if (int rc = gl_stage_guide(c, w.Lpad, false, gen[1][0], gen[2][0], nullptr)) return rc;
+    // held: only the frame kernel writes fa.frames; launches 1 .. n_iter skip the held frames, whose entries stay launch 0's
+    int* list = (int*)(c.ws + w.list);
+    if (c.hold) RFX_HIP(launch_hold_list(c.hold, B, T, list, c.stream));
     for (int it = 0; it <= c.n_iter; ++it) {
       fa.audio_in = gen[(it + 2) % 3][0];    // x_{it-1}
       fa.audio_prev = gen[(it + 1) % 3][0];  // x_{it-2}
-      RFX_HIP(launch_gl_frame(it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2, fa, nblocks, c.stream));
+      if (c.hold && it > 0) RFX_HIP(launch_gl_frame_list(it == 1 ? 1 : 2, fa, list, nblocks, c.stream));
+      else RFX_HIP(launch_gl_frame(it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2, fa, nblocks, c.stream));
       const bool last = it == c.n_iter;
       RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream));
       RFX_HIP(timer.mark(it, c.stream));
@@ -462,7 +498,7 @@ static int griffinlim_impl(const rfx_plan* plan, const float* d_mag_slots, const
   RFX_ON_DEVICE(plan->device);
   GlCall c{d_mag_slots, (const cf*)d_angles0_slots, d_row_scale, opt.magnitude_hint, momentum / (1.f + momentum), seed,
            opt.row_base * (uint64_t)T, B, T, L, n_iter, d_wave_out, (char*)d_workspace, workspace_bytes, (hipStream_t)stream,
-           opt.guide, opt.guide_stride, opt.guide_samples};
+           opt.guide, opt.guide_stride, opt.guide_samples, opt.hold};
   LaunchTimer timer(h_launch_ms, n_iter + 1);
   return plan->generic ? gen_griffinlim(plan, c, mag_in_fam_slots, timer) : spec_griffinlim(plan, c, timer);
 }
@@ -638,9 +674,9 @@ struct WaveFromMelLayout {
   size_t lin, row_scale, rest, total;
   bool fam_slots;
 };
-static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, int T) {
+static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, int T, bool held = false) {
   WaveFromMelLayout l{};
-  const size_t imel = rfx_inverse_mel_workspace_bytes(plan, B, T), gl = rfx_griffinlim_workspace_bytes(plan, B, T);
+  const size_t imel = rfx_inverse_mel_workspace_bytes(plan, B, T), gl = griffinlim_workspace(plan, B, T, held);
   if (!imel || !gl) return l;
   const size_t lstsq = inverse_mel_lstsq_layout(plan, B, T).total;
   l.fam_slots = imel_can_emit_fam_slots(plan);
@@ -654,6 +690,7 @@ static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, i
   return l;
 }
 size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T).total : 0; }
+size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, true).total : 0; }
 
 static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                                  float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream, const CallOpt& opt) {
@@ -661,7 +698,7 @@ static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int 
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_waveform_from_mel")) return rc;
   if (int rc = guide_refusal(plan, opt, T, false, "rfx_waveform_from_mel")) return rc;
-  const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T);
+  const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T, opt.hold != nullptr);
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_waveform_from_mel: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
   char* ws = (char*)d_workspace;
@@ -696,11 +733,11 @@ int rfx_waveform_from_mel_ex(const rfx_plan* plan, const float* d_mel, int B, in
 struct AudioFromImageLayout {
   size_t mel, wave, rest, total;
 };
-static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N, int stereo, int T) {
+static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N, int stereo, int T, bool held = false) {
   AudioFromImageLayout l{};
   if (N <= 0 || T <= 0) return l;
   const int B = N * (stereo ? 2 : 1);
-  const size_t inner = waveform_from_mel_layout(plan, B, T).total;
+  const size_t inner = waveform_from_mel_layout(plan, B, T, held).total;
   if (!inner) return l;
   Carve c;
   l.mel = c.take((size_t)B * plan->p.n_mels * T * sizeof(float));
@@ -712,6 +749,9 @@ static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N,
 size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
   return plan ? audio_from_image_layout(plan, N, stereo, T).total : 0;
 }
+size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
+  return plan ? audio_from_image_layout(plan, N, stereo, T, true).total : 0;
+}
 
 static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                                 int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
@@ -721,7 +761,7 @@ static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_audio_from_image_u8")) return rc;
   if (int rc = guide_refusal(plan, opt, T, false, "rfx_audio_from_image_u8")) return rc;
-  const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T);
+  const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T, opt.hold != nullptr);
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_audio_from_image_u8: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
   const int C = stereo ? 2 : 1, B = N * C, M = plan->p.n_mels, L = rfx_griffinlim_output_samples(plan, T);

@@ -8,6 +8,11 @@
 //                      convolution, conj chirp x window -> synthesis frame -> HBM (gen_fold_kernel overlap-adds)
 // The chirp c [nc] and H [buffer layout] are read from global memory (L2-resident: 8 (nc + np) bytes), in batches ahead of the
 // LDS traffic that depends on them.  Bit-reproducible (no atomics).
+// This file is compiled twice: as itself, and as rfx_czt_list.hip (`#define RFX_CZT_LIST_TU 1`, then this file), which holds only
+// the Griffin-Lim kernels that walk a held call's free-frame list (rfx_guide_core.h) and their launcher.
+#ifndef RFX_CZT_LIST_TU
+#define RFX_CZT_LIST_TU 0
+#endif
 #include <hip/hip_runtime.h>
 
 #include "rfx_czt_core.h"
@@ -130,6 +135,7 @@ struct CztTab {
   const cf* h;  // [gen_ibuf_elems(np, pad_shift)] spectrum of the wrapped conjugate chirp / np, in the buffer's layout
 };
 
+#if !RFX_CZT_LIST_TU
 // ---- forward: frame fr of clip b is centred on sample hop*fr of the reflect-padded waveform (torch.stft center=True)
 enum CztStftMode { kCztMag = 0, kCztSpec = 1 };
 
@@ -182,11 +188,18 @@ czt_stft_kernel(GenStftArgs a, CztTab ct) {
   }
 }
 
+#endif  // !RFX_CZT_LIST_TU
+
 // ---- Griffin-Lim, one iteration for one frame per trip.  MODE 0: Z = S * angles0 (injected or drawn) -> synthesis;
 // MODE 1: analysis of x_cur (the fold forms d = x_k - m x_{k-1}); MODE 2: analysis of x_cur - m x_prev
+// RFX_CZT_LIST_TU (a held call's launches 1 .. n_iter): trip i of the loop takes frame list[i], list[B T] trips in all
 template <int MODE, int MAXR>
 __global__ void __launch_bounds__(kCztThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+#if RFX_CZT_LIST_TU
+czt_gl_list_kernel(GenGlArgs a, CztTab ct, const int* __restrict__ list) {
+#else
 czt_gl_kernel(GenGlArgs a, CztTab ct) {
+#endif
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const GenGeom& g = a.g;
   const CztLds l = czt_lds(smem, g, a.tb);
@@ -194,7 +207,13 @@ czt_gl_kernel(GenGlArgs a, CztTab ct) {
   const float scale = 1.0f / (float)g.nc;  // even: z = IFFT_nc(Z) ; odd: x = Re IFFT_n(Z)
   const int npairs = gen_pair_count(g);
   const int nthr = (int)blockDim.x;
+#if RFX_CZT_LIST_TU
+  const long long ntrips = list[nframes];
+  for (long long trip = blockIdx.x; trip < ntrips; trip += gridDim.x) {
+    const long long fr = list[trip];
+#else
   for (long long fr = blockIdx.x; fr < nframes; fr += gridDim.x) {
+#endif
     const int clip = (int)(fr / a.T), t = (int)(fr - (long long)clip * a.T);
     const float eps2 = a.row_scale ? a.row_scale[2 * clip + 1] : 1e-32f;
     (void)eps2;
@@ -306,6 +325,21 @@ static int czt_grid(const GenGeom& g, int num_cus, long long nframes) {
   return (int)(n < nframes ? n : nframes);
 }
 
+#if RFX_CZT_LIST_TU
+using CztGlListFn = void (*)(GenGlArgs, CztTab, const int*);
+static CztGlListFn czt_gl_list_fn(const GenGeom& g) {
+  const int c = gen_radix_class(g.radix, g.nstages);
+  return c == 5 ? czt_gl_list_kernel<1, 5> : c == 7 ? czt_gl_list_kernel<1, 7> : czt_gl_list_kernel<1, 13>;
+}
+hipError_t prepare_czt_list_kernels(const GenGeom& g) {
+  return hipFuncSetAttribute((const void*)czt_gl_list_fn(g), hipFuncAttributeMaxDynamicSharedMemorySize, (int)czt_lds_bytes(g));
+}
+hipError_t launch_czt_gl_list(const GenGlArgs& a, const int* list, const cf* chirp, const cf* h, int num_cus, hipStream_t stream) {
+  const int grid = czt_grid(a.g, num_cus, (long long)a.B * a.T);
+  hipLaunchKernelGGL(czt_gl_list_fn(a.g), dim3(grid), dim3(a.g.nthr), czt_lds_bytes(a.g), stream, a, CztTab{chirp, h}, list);
+  return hipGetLastError();
+}
+#else
 // kernels by (mode, radix class of the pass length)
 using CztStftFn = void (*)(GenStftArgs, CztTab);
 using CztGlFn = void (*)(GenGlArgs, CztTab);
@@ -356,5 +390,6 @@ hipError_t launch_czt_gl(int mode, const GenGlArgs& a, const cf* chirp, const cf
   hipLaunchKernelGGL(czt_gl_fn(a.g, mode), dim3(grid), dim3(a.g.nthr), czt_lds_bytes(a.g), stream, a, CztTab{chirp, h});
   return hipGetLastError();
 }
+#endif  // RFX_CZT_LIST_TU
 
 }  // namespace rfx

@@ -145,162 +145,12 @@ gen_stft_kernel(GenStftArgs a) {
 
 // ---- Griffin-Lim, one iteration for one frame per trip.  MODE 0: Z = S * angles0 (injected or drawn) -> synthesis;
 // MODE 1: analysis of x_0 (no momentum term yet); MODE 2: analysis of x_k - m x_{k-1}.
-template <int MODE, int MAXR>
-__global__ void __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(MAXR <= 7 ? 4 : 2)))
-gen_gl_kernel(GenGlArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const GenGeom& g = a.g;
-  const GenLds l = gen_lds(smem, g, a.tb);
-  const long long nframes = (long long)a.B * a.T;
-  const int half = g.n_fft / 2;
-  const float scale = 1.0f / (float)g.nc;  // even: z = IFFT_nc(Z) ; odd: x = Re IFFT_n(Z)
-  const int npairs = gen_pair_count(g);
-#ifdef RFX_GEN_TIMING
-  unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = wall_clock64();
-  int nfr = 0;
-#define GSTAMP(i) do { unsigned long long now_ = wall_clock64(); tacc[i] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define GSTAMP(i) ((void)0)
-#endif
-  for (long long fr = blockIdx.x; fr < nframes; fr += gridDim.x) {
-    const int clip = (int)(fr / a.T), t = (int)(fr - (long long)clip * a.T);
-    const float eps2 = a.row_scale ? a.row_scale[2 * clip + 1] : 1e-32f;
-    (void)eps2;
-    const size_t base = (size_t)fr * g.fs;
-    const float* __restrict__ S = a.S + base;
-    __syncthreads();  // the previous frame's output loop is done with the buffer
-    GSTAMP(0);
-    if (MODE == 0) {
-      auto X = [&](int k) {
-        cf ang;
-        if (a.angles0) ang = a.angles0[base + k];
-        else ang = rand_unit_pair(rand_frame_key(a.seed, a.frame_base + (unsigned long long)fr), k);
-        const float s = S[k];
-        return cf{s * ang.re, s * ang.im};
-      };
-      for (int k = threadIdx.x; k < g.nc; k += blockDim.x) l.a[a.tb.rev[k]] = gen_split_inverse(g, X, l.lo2, l.hi2, k);
-    } else {
-      // windowed, zero-padded frame of x_k - m x_{k-1} (reflect-padded like torch.stft center=True), packed two reals per
-      // complex when n_fft is even.  Only the elements the window covers need loads ([n_lo, n_hi): a quarter of the frame at
-      // the reference's 100 / 400 ms); the rest is zeroed.  Loads are batched - all of a batch's global loads, then its LDS
-      // stores - so that a thread waits for HBM / L2 once per batch, not once per element.
-      const float* __restrict__ xc = a.x_cur + (size_t)clip * a.audio_stride;
-      const float* __restrict__ xp = a.x_prev + (size_t)clip * a.audio_stride;
-      const int nthr = (int)blockDim.x;
-      const int per = g.even ? 2 : 1;
-      const int n_lo = g.left / per, n_hi = (g.left + g.win + per - 1) / per;
-      for (int n = threadIdx.x; n < g.nc; n += nthr)
-        if (n < n_lo || n >= n_hi) l.a[gen_ipad(n, g.pad_shift)] = cf{0.f, 0.f};
-      constexpr int UL = 5;
-      for (int n0 = n_lo + (int)threadIdx.x; n0 < n_hi; n0 += UL * nthr) {
-        float xs[UL][2], ps[UL][2], ws[UL][2];
-#pragma unroll
-        for (int u = 0; u < UL; ++u)
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            xs[u][e] = ps[u][e] = ws[u][e] = 0.f;
-            const int n = n0 + u * nthr;
-            if (e < per && n < n_hi) {
-              const int i = per * n + e;  // position inside the padded frame
-              const int j = i - g.left;   // position inside the window
-              if (j >= 0 && j < g.win) {
-                const int p = reflect_index(g.hop * t + i - half, a.L);
-                xs[u][e] = xc[p];
-                if (MODE == 2) ps[u][e] = xp[p];
-                ws[u][e] = a.tb.win[j];
-              }
-            }
-          }
-#pragma unroll
-        for (int u = 0; u < UL; ++u) {
-          const int n = n0 + u * nthr;
-          if (n < n_hi)
-            l.a[gen_ipad(n, g.pad_shift)] = cf{fmaf(-a.mom, ps[u][0], xs[u][0]) * ws[u][0], fmaf(-a.mom, ps[u][1], xs[u][1]) * ws[u][1]};
-        }
-      }
-      __syncthreads();
-      GSTAMP(1);
-      gen_fft<false, MAXR>(g, l, a.tb.tw);  // ends with a barrier; spectrum digit-reversed in l.a
-      GSTAMP(2);
-      {
-        // split / projection / merge, pairwise in place (gen_pair_compute).  Batches of UP pairs per thread: first every
-        // global load of the batch (LDS positions from the digit-reversal table, |S| from HBM), then the LDS reads that depend
-        // on them, the arithmetic, the stores - one global round trip and one LDS round trip per batch.
-        constexpr int UP = 5;
-        const int kc_of0 = g.even ? g.nc : 0;
-        for (int k0 = threadIdx.x; k0 < npairs; k0 += UP * nthr) {
-          GenPair pr[UP];
-          int pk[UP], pc[UP];
-#pragma unroll
-          for (int u = 0; u < UP; ++u) {
-            const int k = k0 + u * nthr;
-            const bool ok = k < npairs;
-            const int kk = ok ? k : 0;
-            const int kc = g.even ? g.nc - kk : (kk == 0 ? 0 : g.n_fft - kk);  // partner ELEMENT (odd n_fft: the mirror element)
-            pr[u].k = kk;
-            pk[u] = a.tb.rev[kk];
-            pc[u] = a.tb.rev[kc == kc_of0 && g.even ? 0 : kc];
-            pr[u].sk = S[kk];
-            pr[u].sc = g.even ? S[kc] : 0.f;  // even, k == 0: bin nc
-          }
-#pragma unroll
-          for (int u = 0; u < UP; ++u) {
-            pr[u].zk = l.a[pk[u]];
-            pr[u].zc = g.even ? l.a[pc[u]] : pr[u].zk;
-          }
-#pragma unroll
-          for (int u = 0; u < UP; ++u) gen_pair_compute(pr[u], g, l.lo2, l.hi2, eps2);
-#pragma unroll
-          for (int u = 0; u < UP; ++u) {
-            const int k = k0 + u * nthr;
-            if (k < npairs) {
-              l.a[pk[u]] = pr[u].zk;
-              const bool partner = g.even ? (k != 0 && k != g.nc - k) : k != 0;
-              if (partner) l.a[pc[u]] = pr[u].zc;
-            }
-          }
-        }
-      }
-    }
-#ifdef RFX_GEN_TIMING
-    __syncthreads();
-#endif
-    GSTAMP(3);
-    const cf* z = gen_fft<true, MAXR>(g, l, a.tb.tw);  // starts with a barrier
-    GSTAMP(4);
-    float* __restrict__ out = a.frames + (size_t)fr * g.fpitch + g.fshift;
-    {
-      constexpr int UO = 5;  // window samples fetched per batch before the stores
-      const int nthr = (int)blockDim.x;
-      for (int j0 = threadIdx.x; j0 < g.win; j0 += UO * nthr) {
-        float wv[UO], zv[UO];
-#pragma unroll
-        for (int u = 0; u < UO; ++u) {
-          const int j = j0 + u * nthr;
-          const int jj = j < g.win ? j : 0;
-          const int i = jj + g.left;
-          wv[u] = a.tb.win[jj];
-          const cf zz = z[gen_ipad(g.even ? i >> 1 : i, g.pad_shift)];
-          zv[u] = (g.even && (i & 1)) ? zz.im : zz.re;
-        }
-#pragma unroll
-        for (int u = 0; u < UO; ++u) {
-          const int j = j0 + u * nthr;
-          if (j < g.win) out[j] = zv[u] * scale * wv[u];
-        }
-      }
-    }
-    GSTAMP(5);
-#ifdef RFX_GEN_TIMING
-    ++nfr;
-#endif
-  }
-#ifdef RFX_GEN_TIMING
-  if (MODE == 2 && blockIdx.x == 7 && threadIdx.x == 0)
-    printf("gen_gl timing (100 MHz ticks per frame, %d frames): barrier-wait %.1f load %.1f fwd %.1f pair %.1f inv %.1f out %.1f\n", nfr,
-           (double)tacc[0] / nfr, (double)tacc[1] / nfr, (double)tacc[2] / nfr, (double)tacc[3] / nfr, (double)tacc[4] / nfr, (double)tacc[5] / nfr);
-#endif
-}
+#define RFX_GLK_LIST 0
+#include "rfx_gen_gl_kernel.hip.h"
+#undef RFX_GLK_LIST
+#define RFX_GLK_LIST 1
+#include "rfx_gen_gl_kernel.hip.h"
+#undef RFX_GLK_LIST
 
 // overlap-add of the windowed frames and division by the window envelope (torch.istft center=True, length = hop*(T-1)):
 // sample p of the output sits at P = p + n_fft/2 of the padded signal; frame t contributes its window sample
@@ -476,6 +326,11 @@ static GenGlFn gen_gl_fn(const GenGeom& g, int mode) {
   const int c = gen_radix_class(g.radix, g.nstages);
   return c == 5 ? gen_gl_fn<5>(mode) : c == 7 ? gen_gl_fn<7>(mode) : gen_gl_fn<13>(mode);
 }
+using GenGlListFn = void (*)(GenGlArgs, const int*);
+static GenGlListFn gen_gl_list_fn(const GenGeom& g) {
+  const int c = gen_radix_class(g.radix, g.nstages);
+  return c == 5 ? gen_gl_list_kernel<1, 5> : c == 7 ? gen_gl_list_kernel<1, 7> : gen_gl_list_kernel<1, 13>;
+}
 
 hipError_t prepare_generic_kernels(const GenGeom& g) {
   const int lds = (int)gen_lds_bytes(g);
@@ -484,7 +339,7 @@ hipError_t prepare_generic_kernels(const GenGeom& g) {
     if ((e = hipFuncSetAttribute((const void*)gen_stft_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   for (int mode = 0; mode < 3; ++mode)
     if ((e = hipFuncSetAttribute((const void*)gen_gl_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  return hipSuccess;
+  return hipFuncSetAttribute((const void*)gen_gl_list_fn(g), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 hipError_t launch_gen_stft(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream) {
@@ -496,6 +351,12 @@ hipError_t launch_gen_stft(int mode, const GenStftArgs& a, int num_cus, hipStrea
 hipError_t launch_gen_gl(int mode, const GenGlArgs& a, int num_cus, hipStream_t stream) {
   const int grid = gen_grid(a.g, num_cus, (long long)a.B * a.T);
   hipLaunchKernelGGL(gen_gl_fn(a.g, mode), dim3(grid), dim3(a.g.nthr), gen_lds_bytes(a.g), stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_gl_list(const GenGlArgs& a, const int* list, int num_cus, hipStream_t stream) {
+  const int grid = gen_grid(a.g, num_cus, (long long)a.B * a.T);
+  hipLaunchKernelGGL(gen_gl_list_fn(a.g), dim3(grid), dim3(a.g.nthr), gen_lds_bytes(a.g), stream, a, list);
   return hipGetLastError();
 }
 

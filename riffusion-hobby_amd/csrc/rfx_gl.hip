@@ -354,82 +354,12 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int kFramePitch = 4416;  // 4410 samples per synthesis frame, rounded up to whole 64-byte lines
 
-template <int MODE>
-__global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_frame_kernel(GlFrameArgs g) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const ThreadId t = thread_id();
-  const FrameCtx f = frame_ctx(smem, t, g.tw1, g.tw2);
-  const rsrc_t win = make_rsrc(g.win, kWin * 4);
-  const unsigned npr4 = (unsigned)t.npr * 4u;
-  const unsigned q16 = (unsigned)slot_qp(t.npr) * 16u;
-  float wv[10];
-#pragma unroll
-  for (int j = 0; j < 10; ++j) wv[j] = ld1(win, npr4, (unsigned)j * (kHop * 4u));
-  Tw1 tw1;
-  if (MODE != 0) load_tw1(tw1, f);
-  __syncthreads();  // tw2 table in LDS
-
-  const long long nframes = (long long)g.B * g.T;
-  for (long long gf = blockIdx.x; gf < nframes; gf += gridDim.x) {
-    const int clip = (int)(gf / g.T), fr = (int)(gf - (long long)clip * g.T);
-    const size_t clip_slots = (size_t)g.T * kFrameStride;
-    const rsrc_t Ssrc = make_rsrc(g.S + clip * clip_slots, clip_slots * sizeof(float));
-    const unsigned foff = (unsigned)fr * (kFrameStride * 4u);
-    cf R[21];
-    MagRegs mag;
-    if (MODE != 0) {
-      const rsrc_t in = make_rsrc(g.audio_in + (size_t)clip * g.Lpad, (size_t)g.L * 4);
-      const rsrc_t pv = make_rsrc(g.audio_prev + (size_t)clip * g.Lpad, (size_t)g.L * 4);
-      const float ks = g.row_scale ? g.row_scale[2 * clip] : 1.f, eps2 = g.row_scale ? g.row_scale[2 * clip + 1] : 1e-32f;
-      float u[10];
-#pragma unroll
-      for (int j = 0; j < 10; ++j) {
-        const unsigned p4 = (unsigned)reflect_index((fr + j - kHalfHops) * kHop + t.npr, g.L) * 4u;
-        float x = ld1(in, p4, 0);
-        if (MODE == 2) x = fmaf(-g.mom, ld1(pv, p4, 0), x);
-        u[j] = (x * ks) * wv[j];  // (the run kernel scales when the sample enters its sliding window: same two products)
-      }
-      frame_forward_tw(u, R, f, t, tw1, [&] { mag_issue(mag, Ssrc, foff, q16); });
-#pragma unroll
-      for (int kb = 0; kb < 21; ++kb) R[kb] = gl_project(R[kb], mag_at(mag, kb), eps2);
-    } else {
-      mag_issue(mag, Ssrc, foff, q16);
-      if (g.angles0) {
-        const rsrc_t init = make_rsrc(g.angles0 + clip * clip_slots, clip_slots * sizeof(cf));
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-          const v4f v = ld4<RFX_STREAM_AUX>(init, q16, 2u * foff + (unsigned)i * (kQPad * 16u));
-          R[2 * i] = cf{v.x, v.y};
-          R[2 * i + 1] = cf{v.z, v.w};
-        }
-        const v2f w = ld2<RFX_STREAM_AUX>(init, q16 >> 1, 2u * foff + 20u * kQPad * 8u);
-        R[20] = cf{w.x, w.y};
-      } else {
-        const unsigned rng_key = rand_frame_key(g.seed, g.frame_base + (unsigned long long)clip * g.T + fr);  // same stream as gl_iter_kernel
-#pragma unroll
-        for (int kb = 0; kb < 21; ++kb) {
-          bool cj;
-          const int bin = slot_bin(t.k1, t.idx, kb, &cj);
-          const cf r = rand_unit_pair(rng_key, bin);
-          R[kb] = cf{r.re, cj ? -r.im : r.im};
-        }
-      }
-#pragma unroll
-      for (int kb = 0; kb < 21; ++kb) {
-        const float s = mag_at(mag, kb);
-        R[kb] = cf{s * R[kb].re, s * R[kb].im};
-      }
-    }
-    float y[10];
-    frame_inverse_tw(R, y, f, t, tw1);
-    if (t.active) {
-      float* __restrict__ out = g.frames + (size_t)gf * kFramePitch + t.npr;
-#pragma unroll
-      for (int j = 0; j < 10; ++j) out[j * kHop] = y[j];  // un-windowed: the fold forms the run kernel's fma chains
-    }
-    __syncthreads();  // the next frame's first LDS stores overwrite rows other waves are still gathering in P1'
-  }
-}
+#define RFX_GLK_LIST 0
+#include "rfx_gl_frame_kernel.hip.h"
+#undef RFX_GLK_LIST
+#define RFX_GLK_LIST 1
+#include "rfx_gl_frame_kernel.hip.h"
+#undef RFX_GLK_LIST
 
 // x[clip][p]: overlap-add of the frames t = blk-4 .. blk+5 that cover hop block blk = p / 441, in the run kernel's arithmetic
 // (round 6, kGlGroup in rfx_kernels.h): an fma chain y w + acc in increasing t, split where a group boundary of the row falls
@@ -463,6 +393,12 @@ hipError_t launch_gl_frame(int mode, const GlFrameArgs& g, int nblocks, hipStrea
     case 1: hipLaunchKernelGGL(gl_frame_kernel<1>, dim3(nblocks), dim3(kThreads), lds, stream, g); break;
     default: hipLaunchKernelGGL(gl_frame_kernel<2>, dim3(nblocks), dim3(kThreads), lds, stream, g); break;
   }
+  return hipGetLastError();
+}
+hipError_t launch_gl_frame_list(int mode, const GlFrameArgs& g, const int* list, int nblocks, hipStream_t stream) {
+  const size_t lds = kFrameDynLdsBytes;
+  if (mode == 1) hipLaunchKernelGGL(gl_frame_list_kernel<1>, dim3(nblocks), dim3(kThreads), lds, stream, g, list);
+  else hipLaunchKernelGGL(gl_frame_list_kernel<2>, dim3(nblocks), dim3(kThreads), lds, stream, g, list);
   return hipGetLastError();
 }
 hipError_t launch_gl_fold(const float* frames, const float* win, const float* scale, float* out, int B, int T, int L, size_t out_stride, hipStream_t stream) {
@@ -500,7 +436,9 @@ hipError_t prepare_gl_kernels() {
   if ((e = hipFuncSetAttribute((const void*)gl_iter_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)gl_frame_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)gl_frame_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
-  return hipFuncSetAttribute((const void*)gl_frame_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes);
+  if ((e = hipFuncSetAttribute((const void*)gl_frame_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute((const void*)gl_frame_list_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
+  return hipFuncSetAttribute((const void*)gl_frame_list_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes);
 }
 
 int gl_blocks_per_cu() {

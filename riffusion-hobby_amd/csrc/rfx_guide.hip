@@ -2,6 +2,7 @@
 // (B, guide_samples) rows, fitted to the call's L samples and brought into the kernels' numeric range by exact powers of two, into
 // the audio buffer the call's first launch analyses.  Arithmetic and the shape of the peak reduction: rfx_guide_core.h.
 // Two launches over (chunk, row): the chunks' peaks, then the scaled copy.
+// Below them: the compaction of a held call's free frames into the list its launches 1 .. n_iter walk (rfx_held_call_options).
 #include <hip/hip_runtime.h>
 
 #include "rfx_guide_core.h"
@@ -99,6 +100,102 @@ hipError_t launch_guide_stage(const float* guide, long long stride, int guide_sa
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// ---- the free-frame list of a held call (rfx_guide_core.h): counts per chunk of rows, a scan over the chunks, the fill ----------------
+namespace {
+// exclusive prefix sum of one value per thread of a kHoldThreads workgroup; *total: the workgroup's sum.  lds: kHoldThreads / 64 ints
+__device__ __forceinline__ int hold_block_scan(int v, int* lds, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int up = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += up;
+  }
+  __syncthreads();  // (a previous call's readers are done with lds)
+  if (lane == 63) lds[wave] = incl;
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < kHoldThreads / 64; ++w) {
+    if (w < wave) before += lds[w];
+    all += lds[w];
+  }
+  *total = all;
+  return before + incl - v;
+}
+}  // namespace
+
+// list[chunk_offsets_at + chunk] = free frames of the chunk's rows
+__global__ void __launch_bounds__(kHoldThreads) hold_count_kernel(const int32_t* __restrict__ hold, long long B, int T, int* __restrict__ list) {
+  __shared__ int lds[kHoldThreads / 64];
+  const long long chunk = blockIdx.x;
+  int n = 0;
+#pragma unroll
+  for (int e = 0; e < kHoldRowsPerThread; ++e) n += hold_row_span(hold, hold_thread_row(chunk, threadIdx.x, e), B, T).count;
+  int total;
+  (void)hold_block_scan(n, lds, &total);
+  if (threadIdx.x == 0) list[hold_chunk_offsets_at(B, T) + chunk] = total;
+}
+
+// one workgroup: the chunks' counts become their exclusive offsets, in place; the count of all free frames to its place
+__global__ void __launch_bounds__(kHoldThreads) hold_scan_kernel(long long B, int T, int* __restrict__ list) {
+  __shared__ int lds[kHoldThreads / 64];
+  int* __restrict__ offs = list + hold_chunk_offsets_at(B, T);
+  const long long chunks = hold_chunks(B);
+  int carry = 0;
+  for (long long c0 = 0; c0 < chunks; c0 += kHoldThreads) {
+    const long long c = c0 + threadIdx.x;
+    const int v = c < chunks ? offs[c] : 0;
+    int total;
+    const int before = hold_block_scan(v, lds, &total);
+    if (c < chunks) offs[c] = carry + before;
+    carry += total;
+  }
+  if (threadIdx.x == 0) list[hold_count_at(B, T)] = carry;
+}
+
+// the chunk's rows write their free frames' indices from the chunk's offset on: a wave per row, lanes along the row's span
+__global__ void __launch_bounds__(kHoldThreads) hold_fill_kernel(const int32_t* __restrict__ hold, long long B, int T, int* __restrict__ list) {
+  __shared__ int lds[kHoldThreads / 64];
+  __shared__ int row_first[kHoldChunkRows], row_count[kHoldChunkRows], row_at[kHoldChunkRows];
+  const long long chunk = blockIdx.x;
+  HoldSpan s[kHoldRowsPerThread];
+  int n = 0;
+#pragma unroll
+  for (int e = 0; e < kHoldRowsPerThread; ++e) {
+    s[e] = hold_row_span(hold, hold_thread_row(chunk, threadIdx.x, e), B, T);
+    n += s[e].count;
+  }
+  int total;
+  int at = list[hold_chunk_offsets_at(B, T) + chunk] + hold_block_scan(n, lds, &total);
+#pragma unroll
+  for (int e = 0; e < kHoldRowsPerThread; ++e) {
+    const int r = threadIdx.x * kHoldRowsPerThread + e;
+    row_first[r] = s[e].first;
+    row_count[r] = s[e].count;
+    row_at[r] = at;
+    at += s[e].count;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  for (int r = threadIdx.x >> 6; r < kHoldChunkRows; r += kHoldThreads / 64) {
+    const long long row = chunk * kHoldChunkRows + r;
+    const HoldSpan sp{row_first[r], row_count[r]};  // (count 0 behind the batch)
+    for (int i = lane; i < sp.count; i += 64) list[(size_t)row_at[r] + i] = hold_list_entry(row, T, sp, i);
+  }
+}
+
+hipError_t launch_hold_list(const int32_t* hold, int B, int T, int* list, hipStream_t stream) {
+  const unsigned chunks = (unsigned)hold_chunks(B);
+  hipLaunchKernelGGL(hold_count_kernel, dim3(chunks), dim3(kHoldThreads), 0, stream, hold, (long long)B, T, list);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hold_scan_kernel, dim3(1), dim3(kHoldThreads), 0, stream, (long long)B, T, list);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(hold_fill_kernel, dim3(chunks), dim3(kHoldThreads), 0, stream, hold, (long long)B, T, list);
+  return hipGetLastError();
 }
 
 }  // namespace rfx

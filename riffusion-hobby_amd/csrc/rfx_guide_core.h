@@ -1,5 +1,6 @@
 // rfx_guide_core.h - arithmetic of the guide staging (rfx_guide.hip), written once for the gfx950 kernels (hipcc) and the host
-// emulator of the CPU tests (tests/emu/rfx_guide_emu.cpp, g++).
+// emulators of the CPU tests (tests/emu/rfx_guide_emu.cpp, tests/emu/rfx_hold_emu.cpp, g++).  Below the staging: the held frames of a
+// guided call and the list of the frames that are not held.
 //
 // A guided Griffin-Lim call (include/rfx.h: rfx_guided_call_options) starts from the phase of a caller's waveform instead of random
 // phases: its first launch is MODE 1 - a = STFT(x), normalise, ISTFT(|S| a / |a|) - with x the guide.  Staging brings row r of the
@@ -59,5 +60,45 @@ RFX_HD GuideScale guide_scale(float peak, float ks) {
   return s;
 }
 RFX_HD float guide_apply(float x, const GuideScale& s) { return ((x * s.a) * s.b) * s.c; }
+
+// ---- held frames (include/rfx.h: rfx_held_call_options) -----------------------------------------------------------------------------
+// A guided call may hold the first `head` and the last `tail` frames of a row at the guide's phase: after every projection the
+// angles of a held frame are set back to a0, so its synthesis frame IFFT(|S_t| a0_t) is what launch 0 wrote, at every iteration.
+// Launches 1 .. n_iter therefore walk a list of the FREE frames only and leave the held frames' entries of the frame buffer alone.
+// Any int32 pair is legal: h = clamp(head, 0, T), l = clamp(tail, 0, T - h); the free frames of a row are t in [h, T - l).
+struct HoldSpan {
+  int first, count;  // the free frames of a row: first <= t < first + count
+};
+RFX_HD HoldSpan hold_free_span(int head, int tail, int T) {
+  const int h = head < 0 ? 0 : head > T ? T : head;
+  const int rest = T - h;
+  const int l = tail < 0 ? 0 : tail > rest ? rest : tail;
+  return HoldSpan{h, rest - l};
+}
+RFX_HD bool hold_is_held(int t, int head, int tail, int T) {
+  const HoldSpan s = hold_free_span(head, tail, T);
+  return t < s.first || t >= s.first + s.count;
+}
+
+// The free-frame list: the global indices row T + t of the free frames, increasing, in list[0 .. count), and the count itself at
+// list[B T] (a fixed place: the frame kernels read it without knowing it).  Built by three launches over CHUNKS of kHoldChunkRows
+// rows (rfx_guide.hip): the chunks' free counts, one workgroup's exclusive scan over them, the fill.  Thread `tid` of a chunk's
+// workgroup owns the kHoldRowsPerThread consecutive rows from hold_thread_row; the chunks' offsets live behind the count.
+// B T < 2^31 (the entry points check it), so every count and offset fits an int; products with T are formed in 64 bits.
+constexpr int kHoldThreads = 256;
+constexpr int kHoldRowsPerThread = 4;
+constexpr int kHoldChunkRows = kHoldThreads * kHoldRowsPerThread;
+RFX_HD long long hold_chunks(long long B) { return (B + kHoldChunkRows - 1) / kHoldChunkRows; }
+RFX_HD long long hold_thread_row(long long chunk, int tid, int e) { return chunk * kHoldChunkRows + (long long)tid * kHoldRowsPerThread + e; }
+RFX_HD long long hold_count_at(long long B, int T) { return B * T; }
+RFX_HD long long hold_chunk_offsets_at(long long B, int T) { return B * T + 1; }
+// int32 words of the list, its count and the chunk offsets, rounded up to whole 16 bytes
+RFX_HD size_t hold_list_words(long long B, int T) { return (size_t)((B * T + 1 + hold_chunks(B) + 3) / 4 * 4); }
+// the free frames of row `row`, or none behind the batch
+RFX_HD HoldSpan hold_row_span(const int32_t* hold, long long row, long long B, int T) {
+  return row < B ? hold_free_span(hold[2 * row], hold[2 * row + 1], T) : HoldSpan{0, 0};
+}
+// entry i of a row's part of the list
+RFX_HD int hold_list_entry(long long row, int T, const HoldSpan& s, int i) { return (int)(row * T + s.first + i); }
 
 }  // namespace rfx

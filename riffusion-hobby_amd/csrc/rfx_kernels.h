@@ -93,6 +93,9 @@ struct GlFrameArgs {
   unsigned long long frame_base;  // as GlArgs::frame_base
 };
 hipError_t launch_gl_frame(int mode, const GlFrameArgs& g, int nblocks, hipStream_t stream);
+// the same over the free-frame list of a held call (launch_hold_list): trip i of the grid-stride loop takes frame list[i], the trip
+// count is list[B T].  Modes 1 and 2; the grid is the unlisted launch's (the host does not know the count)
+hipError_t launch_gl_frame_list(int mode, const GlFrameArgs& g, const int* list, int nblocks, hipStream_t stream);
 hipError_t launch_gl_fold(const float* frames, const float* win, const float* scale, float* out, int B, int T, int L, size_t out_stride, hipStream_t stream);
 size_t gl_frame_buffer_bytes(int B, int T);
 
@@ -321,6 +324,7 @@ hipError_t prepare_generic_kernels(const GenGeom& g);
 size_t gen_lds_bytes(const GenGeom& g);
 hipError_t launch_gen_stft(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream);  // mode 0 mag, 1 spec
 hipError_t launch_gen_gl(int mode, const GenGlArgs& a, int num_cus, hipStream_t stream);      // mode 0 init, 1 first iteration, 2 iteration
+hipError_t launch_gen_gl_list(const GenGlArgs& a, const int* list, int num_cus, hipStream_t stream);  // mode 1 over a free-frame list (launch_gl_frame_list)
 hipError_t launch_gen_env(const float* win, float* env, const GenGeom& g, int T, int L, hipStream_t stream);  // env[p] = sum_t w[j]^2, once per call
 hipError_t launch_gen_fold(const float* frames, const float* env, float* out, const GenGeom& g, int B, int T, int L, size_t out_stride,
                            hipStream_t stream, const float* prev = nullptr, float* dout = nullptr, float mom = 0.f,
@@ -335,6 +339,9 @@ hipError_t launch_gen_mel(const float* mag, float* mel_tm, const float* band_wt,
 hipError_t prepare_czt_kernels(const GenGeom& g);
 hipError_t launch_czt_stft(int mode, const GenStftArgs& a, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);  // mode 0 mag, 1 spec
 hipError_t launch_czt_gl(int mode, const GenGlArgs& a, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);      // modes as launch_gen_gl
+// mode 1 over a free-frame list (launch_gl_frame_list); a translation unit of their own (rfx_czt_list.hip)
+hipError_t prepare_czt_list_kernels(const GenGeom& g);
+hipError_t launch_czt_gl_list(const GenGlArgs& a, const int* list, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);
 hipError_t launch_mel_transpose(const float* mel_tm, float* mel, int B, int T, int M, int Mpad, hipStream_t stream);
 
 // ---- row-family Griffin-Lim (rfx_fam.hip): n_fft = 40 h, win_length = 10 h; frames are folded by launch_gen_fold
@@ -386,6 +393,7 @@ size_t fam_static_lds_bytes(const FamGeom& g);  // static: the pass-A twiddles w
 int fam_blocks_per_cu(const FamGeom& g);
 bool fam_row_stride_even(const FamGeom& g);     // the kernels use 16-byte LDS accesses in pass B: rows must start 16-byte aligned
 hipError_t launch_fam_gl(int mode, const FamGlArgs& a, int nblocks, hipStream_t stream);  // mode 0 init, 1 first iteration, 2 iteration
+hipError_t launch_fam_gl_list(const FamGlArgs& a, const int* list, int nblocks, hipStream_t stream);  // modes 1 / 2 over a free-frame list (launch_gl_frame_list)
 hipError_t launch_fam_repack(const float* plain, float* slots, const int* bin_of, long long nframes, int fs_plain, int fsf, int n_stft,
                              hipStream_t stream);
 
@@ -485,6 +493,10 @@ hipError_t launch_spectral_sums(const float* a, const float* m, int rows, int T,
 // Lpad a multiple of 64, dst and zero 16-byte aligned; the guide needs float alignment only.
 hipError_t launch_guide_stage(const float* guide, long long stride, int guide_samples, int B, int L, int Lpad, const float* row_scale,
                               float* peaks, float* dst, float* zero, hipStream_t stream);
+// the free-frame list of a held call (rfx_guide_core.h): hold = (B, 2) {head, tail} per row, any values (clamped); list =
+// hold_list_words(B, T) ints: the indices row T + t of the frames that are not held, increasing, their count at list[B T], the
+// compaction's chunk offsets behind it.  Three launches, no atomics, nothing read back.
+hipError_t launch_hold_list(const int32_t* hold, int B, int T, int* list, hipStream_t stream);
 
 // closed-form InverseMelScale (rfx_imel_lstsq.hip, arithmetic in rfx_imel_lstsq_core.h).  The plan's tables: the float32
 // L D L^T factors of fb^T fb - nl[m] = -L[m + 1][m] (nl[M - 1] = 0), inv_d[m] = 1 / D[m] - and, for every position of an output

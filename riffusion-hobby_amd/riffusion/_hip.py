@@ -122,6 +122,29 @@ def guided_call_options(guide: T.Optional[torch.Tensor], rows: int, row_base: in
                                 guide.stride(0) if rows > 1 else guide.shape[1], guide.shape[1], 0)
 
 
+class RfxHeldCallOptions(ctypes.Structure):
+    """rfx_held_call_options of include/rfx.h: rfx_guided_call_options grown at its tail by the frames a guided call holds."""
+
+    _fields_ = RfxGuidedCallOptions._fields_ + [("d_hold_frames", ctypes.c_void_p), ("reserved3", ctypes.c_uint64)]
+
+
+def held_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], rows: int, row_base: int = 0,
+                      magnitude_hint: float = 0.0, lstsq: bool = False):
+    """`guided_call_options`, with the held frames of a held call: `hold` a contiguous (rows, 2) int32 tensor of {head, tail} on the
+    guide's device; None gives the guided (or plain) options.  The caller keeps both tensors alive until the call is issued."""
+    o = guided_call_options(guide, rows, row_base, magnitude_hint, lstsq)
+    if hold is None:
+        return o
+    if guide is None:
+        raise ValueError("hold needs a guide: the frames are held at the guide's phase")
+    if hold.dtype != torch.int32 or tuple(hold.shape) != (rows, 2) or not hold.is_contiguous():
+        raise ValueError(f"hold must be a contiguous ({rows}, 2) int32 tensor of (head, tail) frames, got {tuple(hold.shape)} {hold.dtype}")
+    if hold.device != guide.device:
+        raise ValueError(f"hold on {hold.device}, guide on {guide.device}")
+    return RfxHeldCallOptions(ctypes.sizeof(RfxHeldCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, o.d_guide, o.guide_stride,
+                              o.guide_samples, 0, hold.data_ptr(), 0)
+
+
 def check_inverse_mel(inverse_mel: str) -> bool:
     """True for "lstsq", False for "sgd"; anything else raises."""
     if inverse_mel not in INVERSE_MEL_FORMS:
@@ -194,6 +217,7 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_spectral_error_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_error": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_griffinlim_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_griffinlim_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_output_samples": (c_int, [c_void_p, c_int]),
     "rfx_griffinlim": (
         c_int,
@@ -223,9 +247,11 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_image_decode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rfx_image_encode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rfx_audio_from_image_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_audio_from_image_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "rfx_audio_from_image_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_audio_from_image_u8_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rfx_waveform_from_mel_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_waveform_from_mel_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_waveform_from_mel_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rfx_waveform_from_mel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_image_from_waveform_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
@@ -571,6 +597,16 @@ class Plan:
         ok = guide.stride(1) == 1 and (guide.shape[0] == 1 or guide.stride(0) >= guide.shape[1])
         return guide if ok else guide.contiguous()
 
+    def _chk_hold(self, hold: torch.Tensor, guide: T.Optional[torch.Tensor], rows: int) -> torch.Tensor:
+        """held frames as the library reads them: a contiguous (rows, 2) int32 tensor on the plan's device; they need a guide"""
+        if guide is None:
+            raise ValueError("hold needs a guide: the frames are held at the guide's phase")
+        if hold.device != self.device:
+            raise ValueError(f"tensor on {hold.device}, plan on {self.device}")
+        if hold.dtype != torch.int32 or tuple(hold.shape) != (rows, 2):
+            raise ValueError(f"hold must be a ({rows}, 2) int32 tensor of (head, tail) frames, got {tuple(hold.shape)} {hold.dtype}")
+        return hold.contiguous()
+
     def _stream(self) -> int:
         return current_stream(self.device)
 
@@ -635,13 +671,15 @@ class Plan:
         row_base: int = 0,
         magnitude_hint: float = 0.0,
         guide: T.Optional[torch.Tensor] = None,
+        hold: T.Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
         """GriffinLim on magnitudes in slot layout -> (B, samples).  `row_base`: index of the call's first row in the caller's
         whole batch (the random phases of row r are drawn from (seed, row_base + r): chunked and sharded batches get the starts
         of the single call); `magnitude_hint`: an upper bound of the magnitudes if the caller knows one (rfx_call_options).
         `guide`: (B, Lg) float32 waveforms on the plan's device, any units; every row starts from the phase of its guide's STFT
         (the row cut or zero-padded to the output length) instead of random phases (rfx_guided_call_options): no randomness,
-        `seed` and `row_base` then change nothing."""
+        `seed` and `row_base` then change nothing.  `hold`: (B, 2) int32 {head, tail} on the plan's device, with a guide: the
+        first `head` and last `tail` frames of a row keep the guide's phase through the iterations (rfx_held_call_options)."""
         mag_slots = self._chk(mag_slots, torch.float32)
         if angles0_slots is not None:
             angles0_slots = self._chk(angles0_slots, torch.complex64)
@@ -649,16 +687,18 @@ class Plan:
             if angles0_slots is not None:
                 raise ValueError("a guide and angles0_slots are two starts: give one")
             guide = self._chk_guide(guide)
+        if hold is not None:
+            hold = self._chk_hold(hold, guide, B)
         if mag_slots.numel() < B * Tn * self.frame_stride:
             raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
-        need = self.lib.rfx_griffinlim_workspace_bytes(self.handle, B, Tn)
+        need = (self.lib.rfx_griffinlim_held_workspace_bytes if hold is not None else self.lib.rfx_griffinlim_workspace_bytes)(self.handle, B, Tn)
         if workspace is not None:
             workspace = self._chk(workspace)
         if workspace is None or workspace.numel() < need:  # no (or too small a) caller-owned workspace: the plan's arena
             with self._workspace(need) as ws:
-                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide)
+                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide, hold)
         out = torch.empty((B, self.lib.rfx_griffinlim_output_samples(self.handle, Tn)), dtype=torch.float32, device=mag_slots.device)
-        opt = guided_call_options(guide, B, row_base, magnitude_hint)
+        opt = held_call_options(guide, hold, B, row_base, magnitude_hint)
         check(
             self.lib.rfx_griffinlim_ex(
                 self.handle,
@@ -919,10 +959,10 @@ class Plan:
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
                           row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False,
-                          guide: T.Optional[torch.Tensor] = None) -> torch.Tensor:
+                          guide: T.Optional[torch.Tensor] = None, hold: T.Optional[torch.Tensor] = None) -> torch.Tensor:
         """spectrogram_converter.py:187-204 in one call: (B, n_mels, T) -> (B, hop * (T - 1)); `inverse_mel` (seed) + `griffinlim`
         (seed + 1), same bits, the linear magnitudes stay in the workspace.  `lstsq`: `inverse_mel_lstsq` in place of the SGD.
-        `guide`: (B, Lg) float32 waveforms, as in `griffinlim`."""
+        `guide`: (B, Lg) float32 waveforms, `hold`: (B, 2) int32 held frames, as in `griffinlim`."""
         if lstsq:
             self.require_lstsq()
         mel = self._chk(mel, torch.float32)
@@ -932,8 +972,11 @@ class Plan:
         out = torch.empty((B, self.lib.rfx_griffinlim_output_samples(self.handle, Tn)), dtype=torch.float32, device=mel.device)
         if guide is not None:
             guide = self._chk_guide(guide)
-        opt = guided_call_options(guide, B, row_base, magnitude_hint, lstsq)
-        with self._workspace(self.lib.rfx_waveform_from_mel_workspace_bytes(self.handle, B, Tn)) as ws:
+        if hold is not None:
+            hold = self._chk_hold(hold, guide, B)
+        opt = held_call_options(guide, hold, B, row_base, magnitude_hint, lstsq)
+        query = self.lib.rfx_waveform_from_mel_held_workspace_bytes if hold is not None else self.lib.rfx_waveform_from_mel_workspace_bytes
+        with self._workspace(query(self.handle, B, Tn)) as ws:
             check(self.lib.rfx_waveform_from_mel_ex(self.handle, mel.data_ptr(), B, Tn, channels_per_clip, seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return out
@@ -945,12 +988,14 @@ class Plan:
 
     def audio_from_image(self, img: torch.Tensor, stereo: bool, lut: torch.Tensor, n_iter: int, momentum: float = 0.99, seed: int = 0,
                          normalize: bool = True, out: T.Optional[torch.Tensor] = None, workspace: T.Optional[torch.Tensor] = None,
-                         clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None):
+                         clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None,
+                         hold: T.Optional[torch.Tensor] = None):
         """spectrogram_image_converter.py:54-91 on the device in one call: (N, n_mels, T, 3) uint8 -> ((N, L, C) int16, per-clip peak (N,));
         `image_decode` + `waveform_from_mel` (clips of C rows) + `pcm16`, same bytes.  `out` as in `pcm16`.  `clip_base`: index of
         the call's first image in the caller's whole batch (row_base = clip_base * C); `magnitude_hint`: the image path's
         max_value (the largest entry of `lut`); `lstsq`: the closed-form InverseMelScale in place of the SGD; `guide`: (N * C, Lg)
-        float32 waveforms, image after image and channel after channel, as in `griffinlim`."""
+        float32 waveforms, image after image and channel after channel, as in `griffinlim`; `hold`: (N * C, 2) int32 held frames, row
+        for row with the guide."""
         if img.dtype != torch.uint8 or img.dim() != 4:
             raise ValueError("expected (N, H, W, 3) uint8 images")
         if lstsq:
@@ -968,16 +1013,19 @@ class Plan:
             pcm = out
         else:
             pcm = torch.empty((N, L, C), dtype=torch.int16, device=img.device)
-        need = self.lib.rfx_audio_from_image_workspace_bytes(self.handle, N, int(stereo), W)
+        need = (self.lib.rfx_audio_from_image_held_workspace_bytes if hold is not None else self.lib.rfx_audio_from_image_workspace_bytes)(
+            self.handle, N, int(stereo), W)
         ws = self._chk(workspace) if workspace is not None else None
         if ws is None or ws.numel() < need:
             with self._workspace(need) as borrowed:
                 return self.audio_from_image(img, stereo, lut, n_iter, momentum, seed, normalize, out=pcm, workspace=borrowed,
-                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide)
+                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold)
         peak = torch.zeros((N,), dtype=torch.float32, device=img.device)
         if guide is not None:
             guide = self._chk_guide(guide)
-        opt = guided_call_options(guide, N * C, clip_base * C, magnitude_hint, lstsq)
+        if hold is not None:
+            hold = self._chk_hold(hold, guide, N * C)
+        opt = held_call_options(guide, hold, N * C, clip_base * C, magnitude_hint, lstsq)
         check(self.lib.rfx_audio_from_image_u8_ex(self.handle, img.data_ptr(), N, W, int(stereo), lut.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                   int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return pcm, peak

@@ -63,18 +63,26 @@ def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_freque
 
 
 def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto",
-                   guide_audio: str = "", griffin_lim_iters: int = -1) -> None:
+                   guide_audio: str = "", griffin_lim_iters: int = -1, hold_head_ms: int = 0, hold_tail_ms: int = 0) -> None:
     """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD,
     --frame-engine chirp-z runs parameters whose FFT length has a prime factor above 13 (refused otherwise).
     --guide-audio FILE starts Griffin-Lim from the phase of that clip (audio-to-audio: the clip the tile was made of; it must be at
     the tile's sample rate) instead of random phases, --griffin-lim-iters N runs N iterations instead of the params' 32 (a guided
-    decode needs 0 to 4)."""
+    decode needs 0 to 4).  --hold-head-ms N / --hold-tail-ms N, with --guide-audio: the first / last N milliseconds of the clip are
+    known audio (a continuation's left part, the ends around a re-drawn middle) - the frames whose windows lie wholly inside them keep
+    the guide's phase through the iterations instead of only starting from it."""
+    if (hold_head_ms or hold_tail_ms) and not guide_audio:
+        raise ValueError("--hold-head-ms / --hold-tail-ms need --guide-audio: the frames are held at the guide's phase")
+    if hold_head_ms < 0 or hold_tail_ms < 0:
+        raise ValueError("--hold-head-ms / --hold-tail-ms must be >= 0")
     pil_image = Image.open(image)
     params = _params_from_image(pil_image)
     converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
     segment = converter.audio_from_spectrogram_image(pil_image, apply_filters=True, inverse_mel=inverse_mel,
                                                      guide_segment=_load_segment(guide_audio) if guide_audio else None,
-                                                     griffin_lim_iters=griffin_lim_iters if griffin_lim_iters >= 0 else None)
+                                                     griffin_lim_iters=griffin_lim_iters if griffin_lim_iters >= 0 else None,
+                                                     hold_frames=params.hold_frames_for(hold_head_ms / 1000.0, hold_tail_ms / 1000.0)
+                                                     if hold_head_ms or hold_tail_ms else None)
     segment.export(audio, format=os.path.splitext(audio)[1][1:] or "wav")
     print(f"Wrote {audio} ({segment.duration_seconds:.2f} seconds)")
 
@@ -304,8 +312,14 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv: T.Optional[T.Sequence[str]] = None) -> None:
-    args = vars(build_parser().parse_args(argv))
+    parser = build_parser()
+    args = vars(parser.parse_args(argv))
     command = args.pop("command")
+    if command == "image-to-audio" and (args["hold_head_ms"] or args["hold_tail_ms"]):
+        if not args["guide_audio"]:
+            parser.error("--hold-head-ms / --hold-tail-ms need --guide-audio: the frames are held at the guide's phase")
+        if args["hold_head_ms"] < 0 or args["hold_tail_ms"] < 0:
+            parser.error("--hold-head-ms / --hold-tail-ms must be >= 0")
     _COMMANDS[command](**args)
 
 

@@ -44,6 +44,19 @@ class _HipOp:
         return f"<rfx HIP op {self._name} on {self._owner.device}>"
 
 
+def hold_rows(hold_frames: T.Any, n: int, frames: int) -> torch.Tensor:
+    """`hold_frames` as the (n, 2) int32 host tensor of {head, tail} the library reads: a `(head, tail)` pair serves all n entries,
+    an (n, 2) integer array or tensor gives each its own; values are clamped to [0, frames]."""
+    h = torch.as_tensor(np.asarray(hold_frames) if not isinstance(hold_frames, torch.Tensor) else hold_frames).cpu()
+    if h.is_floating_point() or h.is_complex() or h.dtype == torch.bool:
+        raise ValueError(f"hold_frames must be integers, got {h.dtype}")
+    if h.dim() == 1 and h.shape[0] == 2:
+        h = h.reshape(1, 2).expand(n, 2)
+    if h.dim() != 2 or tuple(h.shape) != (n, 2):
+        raise ValueError(f"hold_frames must be a (head, tail) pair or ({n}, 2) integers, got {tuple(h.shape)}")
+    return h.to(torch.int64).clamp(0, frames).to(torch.int32).contiguous()
+
+
 class SpectrogramConverter:
     def __init__(self, params: SpectrogramParams, device: str = "cuda", *, frame_engine: str = "auto"):
         """`frame_engine="chirp-z"` (not in the reference) runs parameter sets whose FFT length has a prime factor above 13 - which
@@ -163,6 +176,7 @@ class SpectrogramConverter:
         channels_per_clip: T.Optional[int] = None,
         inverse_mel: str = "sgd",
         guide: T.Optional[torch.Tensor] = None,
+        hold_frames: T.Any = None,
     ) -> torch.Tensor:
         """
         (B, n_mels, T) -> (B, hop*(T-1)).  The reference treats the whole batch as ONE clip (the SGD
@@ -177,22 +191,37 @@ class SpectrogramConverter:
         cut or zero-padded at its end to hop*(T-1) samples) instead of random phases - in an audio-to-audio workflow the source
         clip, whose phase is nearly right already.  No randomness is left in Griffin-Lim then; a silent guide row gives a silent
         row.  Not together with `angles0`: they are two starts.
+        `hold_frames`: with a guide, a `(head, tail)` pair for all rows or a (B, 2) integer array or tensor: the first `head` and
+        the last `tail` frames of a row keep the guide's phase through every iteration instead of only starting from it
+        (rfx_held_call_options) - the part of a clip that is known audio does not move.  `hold_frames_for` turns seconds of known
+        audio into the pair.  Values are clamped to the frame count.
         """
         if guide is not None and angles0 is not None:
             raise ValueError("guide and angles0 are two starts of Griffin-Lim: give one")
+        hold = None
+        if hold_frames is not None:
+            if guide is None:
+                raise ValueError("hold_frames needs a guide: the frames are held at the guide's phase")
+            hold = hold_rows(hold_frames, int(amplitudes_mel.shape[0]), int(amplitudes_mel.shape[-1]))
         return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
-                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide)
+                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, hold=hold)
+
+    def hold_frames_for(self, head_s: float = 0.0, tail_s: float = 0.0) -> T.Tuple[int, int]:
+        """`SpectrogramParams.hold_frames_for` of this converter's params: the `hold_frames` pair for `head_s` / `tail_s` seconds
+        of known audio at a clip's two ends."""
+        return self.p.hold_frames_for(head_s, tail_s)
 
     def _waveform_from_mel(self, plan: T.Any, amplitudes_mel: torch.Tensor, *, spec0: T.Optional[torch.Tensor] = None,
                            angles0: T.Optional[torch.Tensor] = None, seed: T.Optional[int] = None,
                            channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0,
                            return_slots: bool = False, inverse_mel: str = "sgd", guide: T.Optional[torch.Tensor] = None,
-                           n_iter: T.Optional[int] = None) -> T.Any:
+                           n_iter: T.Optional[int] = None, hold: T.Optional[torch.Tensor] = None) -> T.Any:
         """`waveform_from_mel_amplitudes` on a plan the caller already holds (the batch entry points fetch it once per call,
         not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild).
         `return_slots=True` runs the two inverse stages separately - same bits as the one call - and returns
         (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares.  `guide`: (B, Lg) float32 guide
-        waveforms (`waveform_from_mel_amplitudes`); `n_iter`: Griffin-Lim iterations in place of the params'."""
+        waveforms (`waveform_from_mel_amplitudes`); `n_iter`: Griffin-Lim iterations in place of the params'; `hold`: (B, 2)
+        int32 held frames of a guided call (`hold_rows`)."""
         from riffusion import _hip
 
         lstsq = _hip.check_inverse_mel(inverse_mel)
@@ -207,9 +236,11 @@ class SpectrogramConverter:
         n_iter = self.p.num_griffin_lim_iters if n_iter is None else int(n_iter)
         if guide is not None:
             guide = guide.to(self.device, torch.float32)
+        if hold is not None:
+            hold = hold.to(self.device)
         if spec0 is None and angles0 is None and not return_slots:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
             return plan.waveform_from_mel(mel, cpc, n_iter, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint,
-                                          lstsq=lstsq, guide=guide)
+                                          lstsq=lstsq, guide=guide, hold=hold)
         spec0 = spec0.to(self.device) if spec0 is not None else None
         if lstsq:
             lin_slots = plan.inverse_mel_lstsq(mel)
@@ -217,7 +248,7 @@ class SpectrogramConverter:
             lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         a0 = plan.pack_complex(angles0.to(self.device)) if angles0 is not None else None
         wave = plan.griffinlim(lin_slots, B, Tn, n_iter, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
-                               magnitude_hint=magnitude_hint, guide=guide)
+                               magnitude_hint=magnitude_hint, guide=guide, hold=hold)
         return (wave, lin_slots) if return_slots else wave
 
     # ---- quality of a decode ------------------------------------------------------------------------

@@ -16,7 +16,7 @@ import torch
 from PIL import Image
 
 from riffusion import _hip
-from riffusion.spectrogram_converter import SpectrogramConverter
+from riffusion.spectrogram_converter import SpectrogramConverter, hold_rows
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import audio_util, image_util
 
@@ -62,13 +62,18 @@ class SpectrogramImageConverter:
         inverse_mel: str = "sgd",
         guide_segment: T.Any = None,
         griffin_lim_iters: T.Optional[int] = None,
+        hold_frames: T.Optional[T.Tuple[int, int]] = None,
     ) -> T.Any:
         """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference).  The filters
         (audio_util.apply_filters, compression=False) run on the device: same bytes.  `inverse_mel`: "sgd" (default) or
         "lstsq", as in `audio_from_spectrogram_images`.  `guide_segment`: a PcmSegment or pydub segment at the params' sample
         rate (ValueError otherwise) whose phase starts Griffin-Lim - the clip the tile was made of, in audio-to-audio; mono
         guides both channels of a stereo tile, more channels than the tile's are mixed down.  `griffin_lim_iters`: iterations for
-        this call in place of the params' (a guided decode needs few).  Both as in `audio_from_spectrogram_images`."""
+        this call in place of the params' (a guided decode needs few).  `hold_frames`: with a guide, the `(head, tail)` frames at
+        the clip's two ends that keep the guide's phase through the iterations (`hold_frames_for` turns seconds of known audio
+        into the pair).  All as in `audio_from_spectrogram_images`."""
+        if hold_frames is not None and guide_segment is None:
+            raise ValueError("hold_frames needs a guide: the frames are held at the guide's phase")
         guides = None
         if guide_segment is not None:
             if int(guide_segment.frame_rate) != self.p.sample_rate:
@@ -79,9 +84,14 @@ class SpectrogramImageConverter:
             guides = np.array([c.get_array_of_samples() for c in guide_segment.split_to_mono()]).astype(np.float32)[None]
         pcm = self.audio_from_spectrogram_images(
             np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters,
-            inverse_mel=inverse_mel, guide_waveforms=guides, griffin_lim_iters=griffin_lim_iters,
+            inverse_mel=inverse_mel, guide_waveforms=guides, griffin_lim_iters=griffin_lim_iters, hold_frames=hold_frames,
         )
         return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
+
+    def hold_frames_for(self, head_s: float = 0.0, tail_s: float = 0.0) -> T.Tuple[int, int]:
+        """`SpectrogramParams.hold_frames_for` of this converter's params: the `hold_frames` pair for `head_s` / `tail_s` seconds
+        of known audio at a clip's two ends."""
+        return self.p.hold_frames_for(head_s, tail_s)
 
     # ---- batch entry points ------------------------------------------------------------------------------
     def _filter_pcm(self, plan: T.Any, pcm: torch.Tensor, compression: bool = False) -> torch.Tensor:
@@ -465,6 +475,7 @@ class SpectrogramImageConverter:
         inverse_mel: str = "sgd",
         guide_waveforms: T.Any = None,
         griffin_lim_iters: T.Optional[int] = None,
+        hold_frames: T.Any = None,
     ) -> T.Any:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -533,6 +544,12 @@ class SpectrogramImageConverter:
         iterations.  Guides are chunked and sharded with their tiles and go with every other option; Griffin-Lim then has no
         randomness (with "lstsq" the whole decode has none).
         `griffin_lim_iters`: Griffin-Lim iterations of this call in place of `params.num_griffin_lim_iters`, guided or not.
+        `hold_frames`: with guides, a `(head, tail)` pair for all clips or an (N, 2) integer array or tensor: the first `head` and
+        the last `tail` frames of clip i (both channel rows) keep guide i's phase through every iteration instead of only starting
+        from it (rfx_held_call_options), so known audio at a clip's ends - a continuation's left part, the kept ends of a partial
+        regeneration - does not move, and costs no iteration work.  `hold_frames_for(head_s, tail_s)` gives the pair for seconds of
+        known audio; values are clamped to the tiles' frame count.  Without guides: ValueError.  Chunks and shards slice it like
+        the guides.
         """
         from riffusion import batch_shard
 
@@ -582,6 +599,19 @@ class SpectrogramImageConverter:
             if guides.dtype not in (torch.float32, torch.int16):
                 raise ValueError(f"guide_waveforms must be float32 or int16, got {guides.dtype}")
 
+        holds = None
+        if hold_frames is not None:
+            if guides is None:
+                raise ValueError("hold_frames needs guide_waveforms: the frames are held at the guides' phase")
+            holds = hold_rows(hold_frames, n_total, int(size[0]) if size is not None else int(imgs.shape[2]))
+
+        def held_rows(a: int, b: int) -> T.Optional[torch.Tensor]:
+            """the held frames of tiles [a, b) as the (rows, 2) int32 device tensor of the chunk's clip-channels: a clip's pair for each
+            of its channel rows"""
+            if holds is None:
+                return None
+            return holds[a:b].to(plan.device).repeat_interleave(C, dim=0).contiguous()
+
         def guide_rows(a: int, b: int) -> T.Optional[torch.Tensor]:
             """the guides of tiles [a, b) as the (rows, Lg) float32 device tensor of the chunk's clip-channels"""
             if guides is None:
@@ -619,7 +649,7 @@ class SpectrogramImageConverter:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave, lin_slots = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C,
                                                               magnitude_hint=max_value, return_slots=True, inverse_mel=inverse_mel,
-                                                              guide=guide_rows(a, b), n_iter=n_iter)
+                                                              guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b))
                     error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1])).reshape(b - a, C, 2).sum(1))
                     if return_waveform:
                         out = wave.reshape(b - a, C, -1)
@@ -630,13 +660,13 @@ class SpectrogramImageConverter:
                 elif return_waveform:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value,
-                                                   inverse_mel=inverse_mel, guide=guide_rows(a, b), n_iter=n_iter)
+                                                   inverse_mel=inverse_mel, guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b))
                     out = wave.reshape(b - a, C, -1)
                 else:  # uint8 tiles -> int16 PCM in one call (rfx_audio_from_image_u8_ex), same bytes as the three calls above + pcm16
                     dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
                     out = plan.audio_from_image(tiles, self.p.stereo, lut, n_iter, 0.99, seed=base_seed,
                                                 normalize=True, out=dst, clip_base=a, magnitude_hint=max_value, lstsq=lstsq,
-                                                guide=guide_rows(a, b))[0]
+                                                guide=guide_rows(a, b), hold=held_rows(a, b))[0]
                     if apply_filters:
                         out = self._filter_pcm(plan, out, compression)
                 # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them

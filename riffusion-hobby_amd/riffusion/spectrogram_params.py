@@ -81,6 +81,19 @@ class SpectrogramParams:
     def hop_length(self) -> int:
         return _ms_to_samples(self.step_size_ms, self.sample_rate)
 
+    def hold_frames_for(self, head_s: float = 0.0, tail_s: float = 0.0) -> T.Tuple[int, int]:
+        """(head, tail): how many frames at the start and at the end of a clip lie wholly inside known audio, when its first
+        `head_s` and its last `tail_s` seconds are known - the `hold_frames` of a held decode.  Frame t's window covers the samples
+        [hop t - win / 2, hop t + win / 2) of the clip (the reflected padding beyond an end counts as that end), so n known
+        samples at an end hold 0 frames if n < win_length // 2, else (n - win_length // 2) // hop_length + 1.  Not clamped to a
+        frame count: the callers clamp to the tile's."""
+
+        def frames(seconds: float) -> int:
+            n = int(seconds * self.sample_rate)
+            return 0 if n < self.win_length // 2 else (n - self.win_length // 2) // self.hop_length + 1
+
+        return frames(head_s), frames(tail_s)
+
     def to_exif(self) -> T.Dict[int, T.Any]:
         out: T.Dict[int, T.Any] = {}
         for field, tag, cast in _EXIF_LAYOUT:
