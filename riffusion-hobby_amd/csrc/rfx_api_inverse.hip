@@ -143,7 +143,7 @@ int rfx_griffinlim_form(const rfx_plan* plan, int B, int T) {
   return gl_use_latency_mode(plan, B, T) ? RFX_GL_FORM_FRAMES : RFX_GL_FORM_RUNS;
 }
 
-// Specialised engine: three generations (x_{k-1}, x_k, x_{k+1}) of the two parity audio buffers, the istft normalisation table,
+// Specialised engine: three generations (x_{k-1}, x_k, x_{k+1}) of the run form's two audio buffers (rfx_gl.hip), the istft normalisation table,
 // the synthesis frames of the per-frame form, and the call's own row-scale table (GlArgs::row_scale).  No spectral state is kept
 // between iterations (see rfx_gl.hip).  held (a call with rfx_held_call_options.d_hold_frames): always the per-frame form and its frame
 // buffer, and the free-frame list behind everything an unheld call has.
@@ -447,8 +447,8 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
     }
   };
   RFX_HIP(timer.begin(c.stream));
-  // guided: launch 0 is MODE 1 on the guide, staged as the generation it reads (parity 0 the guide, parity 1 zeros: the kernel adds
-  // the two); generation 2 is free until launch 2 writes it
+  // guided: launch 0 is MODE 1 on the guide, staged as the generation it reads (buffer 0 the guide, buffer 1 zeros: the kernel adds
+  // the two around its run boundaries); generation 2 is free until launch 2 writes it
   if (c.guide)
     if (int rc = gl_stage_guide(c, w.Lpad, false, gen[2][0], gen[1][0], gen[1][1])) return rc;
   for (int it = 0; it <= c.n_iter; ++it) {
@@ -462,7 +462,7 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
     RFX_HIP(timer.mark(it, c.stream));
   }
   const int last = c.n_iter % 3;
-  RFX_HIP(launch_gl_combine(gen[last][0], gen[last][1], c.out, B, L, w.Lpad, c.stream));
+  RFX_HIP(launch_gl_combine(gen[last][0], gen[last][1], c.out, g, part.runs, c.stream));
   RFX_HIP(timer.finish());
   return RFX_OK;
 }

@@ -20,12 +20,19 @@
 //   MODE 2 (iter)  : a = STFT(x_k - m x_{k-1})                 -> normalise -> ISTFT -> x_{k+1}
 // A workgroup walks a run of consecutive frames of one clip-channel, so that the 10-way overlap-add
 // of torch.istft is a register sliding window (thread n' owns sample n' of every hop block) and the
-// only cross-workgroup traffic is the 9-block halo at each end of a run.  Halo blocks are never
-// combined with atomics: partial sums go to one of two parity audio buffers and the reader adds the
-// two.  Round 6: the parity is that of the frame's GROUP (kGlGroup = 16 consecutive frames of a row,
-// rfx_kernels.h) and the nine blocks across EVERY group boundary are split into two partial sums -
-// inside a run exactly as between two runs - so a clip's bits do not depend on where the launch's run
-// boundaries fall (on the batch the clip is converted in), and the per-frame form's fold reproduces them.
+// only cross-workgroup traffic is the 9-block halo at each end of a run.  Round 6: the nine blocks across
+// EVERY boundary between two GROUPS (kGlGroup = 16 consecutive frames of a row, rfx_kernels.h) are the sum
+// of two partial chains, lo s + hi s - inside a run exactly as between two runs - so a clip's bits do not
+// depend on where the launch's run boundaries fall (on the batch the clip is converted in), and the
+// per-frame form's fold reproduces them.
+// Halo blocks are never combined with atomics.  A generation x_k has two audio buffers:
+//   buffer 0 holds every block; buffer 1 holds only what a run adds to the nine blocks it shares with the
+//   PREVIOUS run of its row (the previous run's share of them is in buffer 0).
+// A reader adds the two for exactly those blocks - the ones whose ten frames straddle a boundary of its own
+// run: every launch of a call has the same partition - and takes buffer 0 alone everywhere else; nothing is
+// ever written to, or read from, buffer 1 outside them.  At a group boundary INSIDE a run the same thread
+// owns both chains: it stores the old group's nine partial sums to buffer 0, restarts its chains, and when
+// each of those blocks completes it fetches its own partial back (past L1), adds, and stores the sum over it.
 #define RFX_PK 1  // packed fp32 butterflies (rfx_core.h)
 #include "rfx_frame.hip.h"
 #include "rfx_kernels.h"
@@ -64,6 +71,14 @@ __device__ __forceinline__ void mag_issue_part(MagRegs& m, rsrc_t S, unsigned fo
   for (int i = lo; i < hi; ++i) m.s4[i] = ld4<RFX_STREAM_AUX>(S, q16, foff + (unsigned)i * (kQPad * 16u));
   if (PART == 1) m.tail = ld1<RFX_STREAM_AUX>(S, q16 >> 2, foff + 20u * kQPad * 4u);
 }
+// a + b with b a product that must stay a product: lo s + hi s of a block cut at a group boundary is two products and one sum, in
+// the run form's merge as in the fold of the per-frame form (gl_fold_kernel)
+__device__ __forceinline__ float add_unfused(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+constexpr int kAuxL2 = 16;  // gfx950 cache-policy bit "sc1" on a load: past the CU's L1, served by L2
+
 __device__ __forceinline__ float mag_at(const MagRegs& m, int kb) { return kb < 20 ? m.s4[kb >> 2][kb & 3] : m.tail; }
 
 template <int MODE>
@@ -113,19 +128,29 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
   const rsrc_t init = make_rsrc(have_init ? (const void*)(g.angles0 + clip * clip_slots) : (const void*)g.S,
                                 clip_slots * sizeof(cf));
   const rsrc_t in0 = make_rsrc(g.audio_in[0] + (size_t)clip * g.Lpad, (size_t)g.L * 4);
-  const rsrc_t in1 = make_rsrc(g.audio_in[1] + (size_t)clip * g.Lpad, (size_t)g.L * 4);
   const rsrc_t pv0 = make_rsrc(g.audio_prev[0] + (size_t)clip * g.Lpad, (size_t)g.L * 4);
-  const rsrc_t pv1 = make_rsrc(g.audio_prev[1] + (size_t)clip * g.Lpad, (size_t)g.L * 4);
   // numeric range (round 6): the row's analysis input times a power of two, eps^2 in those units (GlArgs::row_scale)
   const float ks = g.row_scale ? g.row_scale[2 * clip] : 1.f, eps2 = g.row_scale ? g.row_scale[2 * clip + 1] : 1e-32f;
   (void)ks;
   (void)eps2;
-  // the group of the frame being synthesised: [tg0, tg1], its partial sums go to the buffer of its parity (outA), explicit zeros
-  // for blocks no other group touches to the other one (outB); t0 is a group start (runs are whole groups)
-  int tg0 = t0, tg1 = min(g.T - 1, t0 + kGlGroup - 1);
-  const int par = (t0 / kGlGroup) & 1;
-  rsrc_t outA = make_rsrc(g.audio_out[par] + (size_t)clip * g.Lpad, (size_t)g.L * 4);
-  rsrc_t outB = make_rsrc(g.audio_out[par ^ 1] + (size_t)clip * g.Lpad, (size_t)g.L * 4);
+  const rsrc_t out0 = make_rsrc(g.audio_out[0] + (size_t)clip * g.Lpad, (size_t)g.L * 4);
+  const rsrc_t out1 = make_rsrc(g.audio_out[1] + (size_t)clip * g.Lpad, (size_t)g.L * 4);
+  // The segment's neighbours in its row: another run's frames before t0 / after t1 (a segment that starts inside its row starts
+  // its run; t0 is a group start: runs are whole groups).  The nine blocks across such a boundary, [t0 - 5, t0 + 3] and
+  // [t1 - 4, t1 + 4], are the only ones with something in buffer 1 (the header comment) - in this launch's output and, the
+  // partition being the call's, in the generations it reads.
+  // The frame loop stays one straight piece of code (it sits at 128 VGPRs; branches around single loads made hipcc spill into
+  // it): a buffer-1 read goes through a WINDOW descriptor over just those nine blocks, with the thread's byte offset counted from
+  // the window's start.  Outside the window - before it the offset wraps to 4 G - the range check of the buffer load answers 0.f
+  // and nothing is fetched: `a0 + a1` is then `a0 + 0.f`, the sum every reader has always formed for such a block.  The check is
+  // per thread, as it must be for a block beyond the row's end, which is the mirror image of samples of two other blocks.
+  const bool lead = t0 > 0, trail = t1 < g.T - 1;
+  auto window = [&](const float* buf1, bool on, int first_blk, unsigned* off) {
+    const int end_blk = min(first_blk + 9, nblk);
+    *off = (unsigned)first_blk * (kHop * 4u);
+    return make_rsrc(buf1 + (size_t)clip * g.Lpad + (size_t)first_blk * kHop, on ? (size_t)(end_blk - first_blk) * (kHop * 4u) : 0);
+  };
+  int tg0 = t0;  // first frame of the group being synthesised
 
   float acc[10];
 #pragma unroll
@@ -133,16 +158,22 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
 
   // analysis input d = x_k - m*x_{k-1} of thread n' for hop blocks fr-5 .. fr+4: a register sliding
   // window like `acc` (the reflect-padded signal is a fixed function of the padded position, so the
-  // value a frame needs for block beta is the one its predecessor loaded): 4 loads per frame, not 40
+  // value a frame needs for block beta is the one its predecessor loaded): 4 loads per frame, not 40 (2 of them, at most, fetch)
   // The next frame's new sample is REQUESTED before the synthesis barrier and COMBINED after it (at the top of the next trip):
   // with the sum formed where the loads are issued, hipcc put it - and an `s_waitcnt vmcnt(0)` for all 35 requests of the phase,
   // twiddles and window included - in front of the barrier (seen in the ISA, round 4), which is not what "in flight across the
   // barrier" means.  (Measured on one box: 24.5-25.1 ms with the wait, 24.6-25.0 without - the requests had landed by then.)
+  // The nine values the first frame needs can only meet the leading window (a trailing one is at least 16 frames away); the loop's
+  // requests, blocks t0 + 5 .. t1 + 5, only the trailing one - or, mirrored at the end of the row (no trailing run then), the
+  // leading one again.
+  unsigned w_off;
+  rsrc_t in1 = window(g.audio_in[1], lead, t0 - kHalfHops, &w_off);
+  rsrc_t pv1 = window(g.audio_prev[1], lead, t0 - kHalfHops, &w_off);
   struct DRaw { float a0, a1, p0, p1; };
   auto request_d = [&](int blk) {
     const unsigned p4 = (unsigned)reflect_index(blk * kHop + t.npr, g.L) * 4u;
-    DRaw r{ld1(in0, p4, 0), ld1(in1, p4, 0), 0.f, 0.f};
-    if (MODE == 2) { r.p0 = ld1(pv0, p4, 0); r.p1 = ld1(pv1, p4, 0); }
+    DRaw r{ld1(in0, p4, 0), ld1(in1, p4 - w_off, 0), 0.f, 0.f};
+    if (MODE == 2) { r.p0 = ld1(pv0, p4, 0); r.p1 = ld1(pv1, p4 - w_off, 0); }
     return r;
   };
   auto combine_d = [&](const DRaw& r) {
@@ -156,28 +187,38 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
   if (MODE != 0) {
 #pragma unroll
     for (int j = 1; j < 10; ++j) d[j] = load_d(t0 + j - 1 - kHalfHops);  // blocks of frame t0-1 shifted in below
+    if (trail) {
+      in1 = window(g.audio_in[1], true, t1 - 4, &w_off);
+      pv1 = window(g.audio_prev[1], true, t1 - 4, &w_off);
+    }
     d_next = request_d(t0 + 9 - kHalfHops);
   }
   (void)d_next;
 
-  // a finished hop block: value * istft normalisation -> this run's parity buffer (and an explicit zero
-  // in the other one when no neighbouring run contributes to the block)
+  // a hop block leaves, finished or as the partial sum of the frames up to a boundary, times istft's normalisation: to buffer 1
+  // if it is this run's share of a block it has in common with the row's previous run, else to buffer 0
   auto emit_scaled = [&](int blk, float scaled) {
     if (blk < 0 || blk >= nblk || !t.active) return;  // blk is wave-uniform
-    const unsigned boff = (unsigned)blk * (kHop * 4u);
-    const bool full = (max(blk - 4, 0) >= tg0) && (min(blk + 5, g.T - 1) <= tg1);
-    st1(scaled, outA, npr4, boff);
-    if (full) st1(0.f, outB, npr4, boff);
+    st1(scaled, lead && blk <= t0 + 3 ? out1 : out0, npr4, (unsigned)blk * (kHop * 4u));
   };
   auto scale_of = [&](int blk) {
     return (blk >= 0 && blk < nblk) ? ld1(scl, npr4, (unsigned)blk * (kHop * 4u)) : 0.f;
   };
-  auto emit = [&](int blk, float val) { emit_scaled(blk, val * scale_of(blk)); };
+  // The first nine blocks a group inside the run finishes, [tg0 - 5, tg0 + 3], began in the group before it: this thread stored
+  // that group's partial sum to buffer 0 at the boundary and takes it back here - past L1 (sc1: served by L2), which may hold the
+  // line as it was before the store - through a descriptor of that one block; for every other block the descriptor is empty and
+  // the load answers 0.f without fetching: the sum below is lo s + hi s with lo = 0, as gl_fold_kernel forms it
+  auto reload_partial = [&](int blk) {
+    const bool on = tg0 > t0 && blk <= tg0 + 3 && blk >= 0 && blk < nblk;  // (every caller's blk is >= tg0 - 5)
+    const rsrc_t w = make_rsrc(g.audio_out[0] + (size_t)clip * g.Lpad + (size_t)max(blk, 0) * kHop, on ? kHop * 4u : 0u);
+    return ld1<kAuxL2>(w, npr4, 0);
+  };
+  auto emit = [&](int blk, float val) { emit_scaled(blk, add_unfused(reload_partial(blk), val * scale_of(blk))); };
   // gfx950 retires VMEM loads and stores in issue order: a store issued at the end of a frame would sit
   // in front of the next frame's first loads and expose its write latency.  The finished block is
   // therefore parked in a register and stored after the next frame's analysis barrier, where a long
   // LDS/VALU stretch follows; its normalisation factor is fetched across the synthesis barrier.
-  float pend_val = 0.f, pend_scale = 0.f;
+  float pend_val = 0.f, pend_scale = 0.f, pend_lo = 0.f;
   int pend_blk = -1;
 
 #ifdef RFX_TIMING
@@ -190,8 +231,8 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
   for (int fr = t0; fr <= t1; ++fr) {
     if ((fr & (kGlGroup - 1)) == 0 && fr != t0) {
       // ---- group boundary inside the run (wave-uniform): what the end of a run does - the parked block (complete, of the old
-      // group) and the partial sums of the nine blocks across the cut leave for the old group's buffer; the new group starts its
-      // own chains from zero in the other one
+      // group) and the partial sums of the nine blocks across the cut leave for buffer 0; the new group starts its own chains
+      // from zero and adds the stored partial to each of the nine when it completes (reload_partial)
       asm volatile("; RFX_ONCE_PER_GROUP_BEGIN");  // (markers for tools/isa_mix.py: this block runs once per kGlGroup frames)
       emit_scaled(pend_blk, pend_val);
       pend_blk = -1;
@@ -201,10 +242,6 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
         acc[j] = 0.f;
       }
       tg0 = fr;
-      tg1 = min(g.T - 1, fr + kGlGroup - 1);
-      const rsrc_t tmp = outA;
-      outA = outB;
-      outB = tmp;
       asm volatile("; RFX_ONCE_PER_GROUP_END");
     }
     const unsigned foff = (unsigned)fr * (kFrameStride * 4u);
@@ -293,6 +330,7 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
                     load_window();
                     if (MODE != 0) d_next = request_d(fr + 10 - kHalfHops);
                     pend_scale = scale_of(fr - kHalfHops);
+                    pend_lo = reload_partial(fr - kHalfHops);
                   },
                   [&] { RFX_STAMP(5); }, [&](int i) { RFX_STAMP(8 + i); });
 #else
@@ -303,7 +341,7 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
     for (int j = 0; j < 10; ++j) acc[j] = fmaf(y[j], wv[j], acc[j]);
 #ifdef RFX_PREFETCH_D
     if (MODE != 0) {
-      pend_val = acc[0] * pend_scale;
+      pend_val = add_unfused(pend_lo, acc[0] * pend_scale);
       pend_blk = fr - kHalfHops;
     } else {
       emit(fr - kHalfHops, acc[0]);
@@ -350,7 +388,8 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_iter_kernel(GlArgs
 // writes the frame's 4410 windowed synthesis samples to a frame buffer; gl_fold_kernel then overlap-adds the (up to) ten
 // frames that cover a sample and applies torch.istft's envelope division.  Twice the launches and 35 KB of extra traffic
 // per frame, but 512 workgroups per clip-channel: one iteration of a single tile takes ~25 us instead of ~90 us.
-// Chosen by the host for B*T <= 4 frames per resident workgroup slot (RFX_GL_LATENCY_MODE=0 disables).
+// Chosen by the host (rfx_api_inverse.hip::gl_use_latency_mode) for up to rfx_plan_options.gl_frames_per_slot (default six)
+// frames per resident workgroup slot and one stair further; rfx_plan_options.gl_form forces either form.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int kFramePitch = 4416;  // 4410 samples per synthesis frame, rounded up to whole 64-byte lines
 
@@ -363,7 +402,7 @@ constexpr int kFramePitch = 4416;  // 4410 samples per synthesis frame, rounded 
 
 // x[clip][p]: overlap-add of the frames t = blk-4 .. blk+5 that cover hop block blk = p / 441, in the run kernel's arithmetic
 // (round 6, kGlGroup in rfx_kernels.h): an fma chain y w + acc in increasing t, split where a group boundary of the row falls
-// inside the block's frames, each side scaled by istft's normalisation, then added - the two parity buffers of gl_iter_kernel.
+// inside the block's frames, each side scaled by istft's normalisation, then added - gl_iter_kernel's two partial sums of the block.
 // Both forms give a clip the same bits (tests/test_gpu_round6.py).
 __global__ void __launch_bounds__(256) gl_fold_kernel(const float* __restrict__ frames, const float* __restrict__ win,
                                                       const float* __restrict__ scale, float* __restrict__ out, int T, int L, size_t out_stride) {
@@ -407,14 +446,18 @@ hipError_t launch_gl_fold(const float* frames, const float* win, const float* sc
 }
 size_t gl_frame_buffer_bytes(int B, int T) { return (size_t)B * T * kFramePitch * sizeof(float); }
 
-// wave[b][p] = A0 + A1 : fold the two parity buffers into the caller's (B, L) tensor
-__global__ void gl_combine_kernel(const float* a0, const float* a1, float* out, int L, int Lpad, size_t total) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    const size_t b = i / L, p = i - b * L;
-    out[i] = a0[b * Lpad + p] + a1[b * Lpad + p];
-  }
+// wave[b][p]: the last generation into the caller's (B, L) tensor by gl_iter_kernel's reader rule - buffer 0, plus buffer 1 in the
+// nine blocks across a boundary between two runs of the row.  One workgroup per hop block of a row.
+__global__ void __launch_bounds__(256) gl_combine_kernel(const float* __restrict__ a0, const float* __restrict__ a1, float* __restrict__ out,
+                                                         int B, int T, int L, int Lpad, int runs, int run_h, int run_w1, int run_w2) {
+  const int nblk = T - 1;
+  const int row = blockIdx.x / nblk, blk = blockIdx.x - row * nblk;
+  // the group boundary whose nine blocks [c - 5, c + 3] hold blk, if there is one
+  const int c = (blk + kHalfHops) & ~(kGlGroup - 1);
+  const long long ng = gl_groups_per_row(T);
+  const bool two = c > 0 && c < T && blk <= c + 3 && gl_is_run_start(row * ng + c / kGlGroup, runs, B * ng, run_h, run_w1, run_w2);
+  const size_t src = (size_t)row * Lpad + (size_t)blk * kHop, dst = (size_t)row * L + (size_t)blk * kHop;
+  for (int n = threadIdx.x; n < kHop; n += blockDim.x) out[dst + n] = two ? a0[src + n] + a1[src + n] : a0[src + n];
 }
 
 hipError_t launch_gl_iter(int mode, const GlArgs& g, int nblocks, hipStream_t stream) {
@@ -447,11 +490,10 @@ int gl_blocks_per_cu() {
   return n;
 }
 
-hipError_t launch_gl_combine(const float* a0, const float* a1, float* out, int B, int L, int Lpad, hipStream_t stream) {
-  const size_t total = (size_t)B * L;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(gl_combine_kernel, dim3(blocks), dim3(256), 0, stream, a0, a1, out, L, Lpad, total);
+hipError_t launch_gl_combine(const float* a0, const float* a1, float* out, const GlArgs& g, int nblocks, hipStream_t stream) {
+  // B (T - 1) workgroups: below 2^31, as B T is (checked by the host)
+  hipLaunchKernelGGL(gl_combine_kernel, dim3((unsigned)g.B * (unsigned)(g.T - 1)), dim3(256), 0, stream, a0, a1, out, g.B, g.T, g.L, g.Lpad,
+                     nblocks, g.run_h, g.run_w1, g.run_w2);
   return hipGetLastError();
 }
 

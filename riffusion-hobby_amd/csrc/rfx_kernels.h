@@ -17,8 +17,9 @@ struct GlArgs {
   const float* S;             // [B*T][kFrameStride] magnitudes, slot_pos_f order
   const float* row_scale;     // [B][2] or null
   const cf* angles0;          // optional injected initial angles, slot_pos_c order (MODE 0)
-  const float* audio_in[2];   // parity partial sums of x_k, the current estimate, [B][Lpad]
-  const float* audio_prev[2]; // parity partial sums of x_{k-1} (MODE 2)
+  const float* audio_in[2];   // x_k, the current estimate, [B][Lpad]: [0] every block, [1] what a run adds to the nine blocks it
+                              // shares with the previous run of its row - written and read there only (rfx_gl.hip)
+  const float* audio_prev[2]; // x_{k-1} (MODE 2)
   float* audio_out[2];        // x_{k+1}
   const float* out_scale;     // [L]  (2/N) / window-envelope  (torch.istft's division by sum w^2)
   const cf* tw1;              // [21][441]
@@ -69,12 +70,22 @@ RFX_HD long long gl_run_start_frame(long long b, long long runs, int B, int T, l
   return row * T + (u - row * ng) * kGlGroup;
 }
 
+// is group u (counted row after row, as in gl_run_start_frame) the first one of a run?  Run b starts at group floor(N W_b / W_t),
+// W_b increasing in b: the first run that starts at or behind u is the first one with N W_b >= u W_t, i.e. W_b >= ceil(u W_t / N)
+RFX_HD bool gl_is_run_start(long long u, long long runs, long long N, long long h, long long w1, long long w2) {
+  const long long ht = runs < h ? runs : h, Wt = w1 * ht + w2 * (runs - ht);
+  const long long W = (u * Wt + N - 1) / N;
+  const long long b = W <= w1 * ht ? (W + w1 - 1) / w1 : ht + (W - w1 * ht + w2 - 1) / w2;
+  return b < runs && gl_run_start(b, runs, N, h, w1, w2) == u;
+}
+
 hipError_t launch_gl_iter(int mode, const GlArgs& g, int nblocks, hipStream_t stream);
 // per-device set-up, called by rfx_plan_create with the plan's device current
 hipError_t prepare_frame_kernels();  // dynamic-LDS attributes of the STFT and Griffin-Lim kernels
 hipError_t prepare_gl_kernels();
 int gl_blocks_per_cu();  // resident Griffin-Lim workgroups per CU on the current device (occupancy query)
-hipError_t launch_gl_combine(const float* a0, const float* a1, float* out, int B, int L, int Lpad, hipStream_t stream);
+// the two buffers of the last generation -> out (B, L); g and nblocks: the call's launch_gl_iter arguments (the partition)
+hipError_t launch_gl_combine(const float* a0, const float* a1, float* out, const GlArgs& g, int nblocks, hipStream_t stream);
 
 // small-batch (latency) form: one frame per unit of work, synthesis frames to a buffer, then a fold
 struct GlFrameArgs {
