@@ -130,6 +130,8 @@ int rfx_plan_griffinlim_engine(const rfx_plan* plan);
 int rfx_griffinlim_form(const rfx_plan* plan, int B, int T);
 /* (A call with held frames - rfx_held_call_options.d_hold_frames - always takes RFX_GL_FORM_FRAMES on the specialised engine, whatever
  * the plan's gl_form or this rule says: the run form keeps no frame buffer to hold frames in.  Both forms give a clip the same bits.) */
+/* (A masked call - rfx_masked_call_options.d_hold_bins - always takes RFX_GL_FORM_FRAMES on the specialised engine as well, whatever
+ * the plan's gl_form or this rule says: the run form keeps two parity buffers per generation and sums them at run seams.) */
 /* How one launch of the run-based form cuts the call's B*T frames (counted clip after clip) into runs, one per workgroup: returns
  * the number of runs and, if run_starts != NULL, writes min(runs + 1, capacity) run boundaries (run b = frames
  * [run_starts[b], run_starts[b + 1])).  which = 0: the first (synthesis-only) launch, 1: the iterations.  0 for a generic plan.
@@ -316,6 +318,66 @@ typedef struct {
   uint64_t reserved3;       /* must be 0 */
 } rfx_held_call_options;
 
+/* rfx_held_call_options grown once more, by the same mechanism (struct_size = sizeof(rfx_masked_call_options); the first eleven
+ * fields are rfx_held_call_options' own): MASKED CALLS.  Held frames keep whole frames; a partial regeneration that keeps the
+ * source where a mask image is dark (a frequency band, a time-frequency pattern) knows the source's phase in BINS of frames.
+ *
+ * d_hold_bins != NULL: (B, T, hold_words) uint32 on the plan's device, 4-byte aligned, hold_words == rfx_hold_mask_words(plan) =
+ * ceil(n_stft / 32) (276 for the default geometry).  Bin b of frame t of row r is held iff bit b & 31 of word b >> 5 of that frame is
+ * set; bits at or above n_stft in the last word are ignored (they need not be zero).  rfx_hold_bins_from_bands below makes the mask
+ * from a per-mel-band mask.  In the reference's loop, after `angles = angles.div(angles.abs().add(1e-16))`,
+ * angles = torch.where(held, a0, angles) with held the (B, n_stft, T) boolean and a0 the guided start's angles; everything else stays
+ * as it is (tprev = rebuilt for all bins, the momentum term, the final ISTFT).  Only the phase is held: the magnitudes stay the call's.
+ * On the device the hold is applied through its linearity: with S_held = S in the held bins and 0 elsewhere, S_free = S - S_held and
+ * c = ISTFT(S_held a0), every iterate is x_k = ISTFT(S_free proj(STFT(x_{k-1}) - m STFT(x_{k-2}))) + c with x_0 = ISTFT(S a0): the
+ * iterations run on magnitudes that are zero in the held bins and the constant audio c is added to each generation as it is folded.
+ * In float64 the two forms agree to 1e-14; in float32 they round differently (within a few dB of each other against float64).
+ * Exact consequences (values compare with ==; the + c turns a -0.0 sample into +0.0, so these are not bit comparisons unless stated):
+ *   n_iter == 0: the guided call's bytes, whatever the mask;
+ *   an all-zero mask row: that row equals the guided call's row at the same n_iter, on the same form;
+ *   an all-ones mask row: that row equals the guided call's row at n_iter == 0, whatever n_iter is;
+ *   a row depends on its magnitudes, its guide row and its mask row alone - not on the other rows, its place in the batch, seed or
+ *   row_base: bit for bit.
+ * Launches: the guide's staging, the split X = S_held, one more first-launch-class launch and fold (c), the guided call's first
+ * launch on S, the split X = S_free, then launches 1 .. n_iter on X; n_iter == 0 skips the splits and c.  A mask removes no
+ * iteration work (a frame whose every bin is held still runs).  h_launch_ms keeps n_iter + 1 entries, [0] including the staging, the
+ * split and the c launch.  On the specialised engine a masked call always takes RFX_GL_FORM_FRAMES (see rfx_griffinlim_form).
+ * Workspace: the *_masked_workspace_bytes twin of the entry's query (the per-frame form's frame buffer, one more magnitude array X,
+ * and c: B rows of audio); at least the unmasked query.
+ * RFX_ERR_INVALID before any launch, the output untouched: d_hold_bins without d_guide; together with d_hold_frames (in this version:
+ * fully set frames in the mask express the same hold); together with d_angles0_slots; hold_words != rfx_hold_mask_words(plan); a
+ * pointer off 4-byte alignment; reserved4 != 0.  RFX_ERR_WORKSPACE: a workspace below the masked query.  Honoured by
+ * rfx_griffinlim_ex, rfx_waveform_from_mel_ex and rfx_audio_from_image_u8_ex (rows clip after clip, as the mel rows);
+ * rfx_inverse_mel_ex refuses it.  A caller passing any of the three shorter struct sizes keeps exactly its behaviour and bytes. */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t flags;
+  uint64_t row_base;
+  float magnitude_hint;
+  float reserved;           /* must be 0 */
+  const float* d_guide;
+  int64_t guide_stride;
+  int32_t guide_samples;
+  int32_t reserved2;        /* must be 0 */
+  const int32_t* d_hold_frames;
+  uint64_t reserved3;       /* must be 0 */
+  const uint32_t* d_hold_bins; /* NULL: no bins held (the call is rfx_held_call_options' call) */
+  int32_t hold_words;       /* words per frame of d_hold_bins: rfx_hold_mask_words(plan) */
+  int32_t reserved4;        /* must be 0 */
+} rfx_masked_call_options;
+
+/* words per frame of a masked call's d_hold_bins: ceil(n_stft / 32); 0 for a NULL plan */
+int rfx_hold_mask_words(const rfx_plan* plan);
+/* A per-mel-band mask, in the layout of the mel tensor, to the bin mask of rfx_masked_call_options.  d_bands: (B, n_mels, T) uint8,
+ * nonzero = held; d_hold_bins_out: (B, T, rfx_hold_mask_words(plan)) uint32.  For bin f let [lo_f, hi_f] be the first and last band
+ * with a nonzero weight in the plan's filterbank at row f: bin f of frame t is held iff that range exists and every band in it is held
+ * at t.  A bin no filter reaches is never held (it carries no information from the tile).  Every bit of every word is written; the
+ * unused tail bits of the last word as 0.  The plan needs its filterbank (RFX_ERR_INVALID without). */
+int rfx_hold_bins_from_bands(const rfx_plan* plan, const uint8_t* d_bands, int B, int T, uint32_t* d_hold_bins_out, void* stream);
+/* [lo_f, hi_f] of every bin as plan creation computes them, without a GPU (as rfx_debug_plan_bank): lo, hi hold n_stft int16 each;
+ * lo = hi = -1 for a bin with no band.  h_melfb: (n_stft, n_mels) float32. */
+int rfx_debug_bin_bands(const rfx_params* params, const float* h_melfb, int16_t* lo, int16_t* hi);
+
 /* ---- layout converters ------------------------------------------------------------------- */
 /* (B, n_stft, T) float32 magnitudes -> slots (float32) */
 int rfx_pack_magnitudes(const rfx_plan* plan, const float* d_lin_bft, int B, int T, float* d_slots, void* stream);
@@ -367,6 +429,8 @@ int rfx_spectral_error(const rfx_plan* plan, const float* d_wave /* (B, L) */, c
 size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T);
 /* ... of a call with held frames (rfx_held_call_options.d_hold_frames != NULL) */
 size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T);
+/* ... of a masked call (rfx_masked_call_options.d_hold_bins != NULL) */
+size_t rfx_griffinlim_masked_workspace_bytes(const rfx_plan* plan, int B, int T);
 /* samples per clip rfx_griffinlim writes for T frames: what torch.istft(center=True, length=None) returns,
  * hop*(T-1), plus one when n_fft is odd */
 int rfx_griffinlim_output_samples(const rfx_plan* plan, int T);
@@ -480,6 +544,7 @@ int rfx_inverse_mel_lstsq(const rfx_plan* plan, const float* d_mel, int B, int T
  * followed by rfx_griffinlim - same bits - with the linear magnitudes kept inside the workspace. */
 size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T);
 size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T);  /* with held frames (rfx_held_call_options) */
+size_t rfx_waveform_from_mel_masked_workspace_bytes(const rfx_plan* plan, int B, int T);  /* masked (rfx_masked_call_options) */
 int rfx_waveform_from_mel(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                           float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream);
 
@@ -701,6 +766,7 @@ int rfx_pcm16_clips_to_waveform(const int16_t* d_pcm, int64_t frames, int in_cha
  * kept inside the workspace. */
 size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);
 size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* with held frames (rfx_held_call_options) */
+size_t rfx_audio_from_image_masked_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* masked (rfx_masked_call_options) */
 int rfx_audio_from_image_u8(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                             int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
                             size_t workspace_bytes, void* stream);

@@ -70,6 +70,7 @@ struct rfx_plan {
   float* d_win = nullptr;   // [4410]
   float* d_melfb_slots = nullptr;  // [kFrameStride][n_mels]: filterbank rows permuted to slot order
   float* d_melfb = nullptr;        // [n_stft][n_mels] as given
+  int16_t* d_bin_bands = nullptr;  // [2 n_stft] first / last band of each bin, -1: none (bin_bands; rfx_hold_bins_from_bands)
   int* d_kblocks = nullptr;        // non-zero 32-position K blocks of d_melfb_slots
   int n_kblocks = 0;
   int melfb_cols = 0;              // columns of d_melfb_slots (n_mels rounded up to 128)

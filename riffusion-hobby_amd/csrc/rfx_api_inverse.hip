@@ -4,6 +4,7 @@
 
 #include "rfx_api.h"
 #include "rfx_guide_core.h"
+#include "rfx_holdmask_core.h"
 
 using namespace rfx;
 
@@ -146,22 +147,27 @@ int rfx_griffinlim_form(const rfx_plan* plan, int B, int T) {
 // Specialised engine: three generations (x_{k-1}, x_k, x_{k+1}) of the run form's two audio buffers (rfx_gl.hip), the istft normalisation table,
 // the synthesis frames of the per-frame form, and the call's own row-scale table (GlArgs::row_scale).  No spectral state is kept
 // between iterations (see rfx_gl.hip).  held (a call with rfx_held_call_options.d_hold_frames): always the per-frame form and its frame
-// buffer, and the free-frame list behind everything an unheld call has.
+// buffer, and the free-frame list behind everything an unheld call has.  masked (rfx_masked_call_options.d_hold_bins): the
+// per-frame form as well, and behind everything else the second magnitude array X and the constant audio c (rfx_holdmask_core.h).
+enum GlKind { kGlPlain = 0, kGlHeld = 1, kGlMasked = 2 };
 struct GlLayout {
-  size_t audio, scale, frames, row_scale, list, total;
+  size_t audio, scale, frames, row_scale, list, xmag, cadd, total;
   int Lpad;
 };
 static size_t hold_list_bytes(int B, int T) { return hold_list_words(B, T) * sizeof(int32_t); }
-static GlLayout gl_layout(const rfx_plan* plan, int B, int T, bool held = false) {
+static GlLayout gl_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlPlain) {
+  const bool held = kind == kGlHeld, masked = kind == kGlMasked;
   GlLayout l{};
   if (B <= 0 || T < 2) return l;
   l.Lpad = (int)align_up((size_t)kHop * (T - 1), 64);
   Carve c;
   l.audio = c.take(6 * (size_t)B * l.Lpad * sizeof(float));
   l.scale = c.take((size_t)l.Lpad * sizeof(float));
-  l.frames = c.take(held || gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
+  l.frames = c.take(held || masked || gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
   l.row_scale = c.take(range_table_bytes(B));
   l.list = c.take(held ? hold_list_bytes(B, T) : 0);
+  l.xmag = c.take(masked ? (size_t)B * T * kFrameStride * sizeof(float) : 0);
+  l.cadd = c.take(masked ? (size_t)B * l.Lpad * sizeof(float) : 0);
   l.total = c.at;
   return l;
 }
@@ -171,12 +177,13 @@ static int gen_out_len(const GenGeom& g, int T) { return g.hop * (T - 1) + (g.n_
 
 // Generic engine: the windowed synthesis frames, three generations of the audio estimate (x_{k-1}, x_k read; x_{k+1} written) and
 // the window envelope of the fold, [Lpad]; on a row family the magnitudes re-ordered into slot order; the row-scale table; held: the
-// free-frame list
+// free-frame list; masked: X (in the order the frame kernels read: the family's slot order on a row family) and c
 struct GenGlLayout {
-  size_t frames, audio, repacked, row_scale, list, total;
+  size_t frames, audio, repacked, row_scale, list, xmag, cadd, total;
   int Lpad;
 };
-static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T, bool held = false) {
+static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlPlain) {
+  const bool held = kind == kGlHeld, masked = kind == kGlMasked;
   GenGlLayout l{};
   if (B <= 0 || T < 2) return l;
   const GenGeom& g = plan->gg;
@@ -188,16 +195,19 @@ static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T, bool held =
   l.repacked = c.take(plan->fam_ok ? nf * plan->fam.fsf * sizeof(float) : 0);
   l.row_scale = c.take(range_table_bytes(B));
   l.list = c.take(held ? hold_list_bytes(B, T) : 0);
+  l.xmag = c.take(masked ? nf * (plan->fam_ok ? (size_t)plan->fam.fsf : (size_t)g.fs) * sizeof(float) : 0);
+  l.cadd = c.take(masked ? (size_t)B * l.Lpad * sizeof(float) : 0);
   l.total = c.at;
   return l;
 }
 
-static size_t griffinlim_workspace(const rfx_plan* plan, int B, int T, bool held) {
+static size_t griffinlim_workspace(const rfx_plan* plan, int B, int T, GlKind kind) {
   if (!plan) return 0;
-  return plan->generic ? gen_gl_layout(plan, B, T, held).total : gl_layout(plan, B, T, held).total;
+  return plan->generic ? gen_gl_layout(plan, B, T, kind).total : gl_layout(plan, B, T, kind).total;
 }
-size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, false); }
-size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, true); }
+size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlPlain); }
+size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlHeld); }
+size_t rfx_griffinlim_masked_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlMasked); }
 
 // rfx_call_options as the entry points below see them (NULL / short struct = defaults)
 struct CallOpt {
@@ -210,6 +220,10 @@ struct CallOpt {
   int guide_samples = 0;
   // rfx_held_call_options: (B, 2) {head, tail} of the frames held at the guide's phase (null: a guided call holds nothing)
   const int32_t* hold = nullptr;
+  // rfx_masked_call_options: (B, T, mask_words) bit mask of the bins held at the guide's phase (null: no bins held)
+  const uint32_t* mask = nullptr;
+  int mask_words = 0;
+  GlKind kind() const { return mask ? kGlMasked : hold ? kGlHeld : kGlPlain; }
 };
 // allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves); takes_guide: it runs Griffin-Lim
 static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who, uint32_t allowed_flags = 0, bool takes_guide = false) {
@@ -253,6 +267,20 @@ static int read_call_options(const rfx_call_options* o, CallOpt* out, const char
       out->hold = h->d_hold_frames;
     }
   }
+  // the masked tail (rfx_masked_call_options: grown a third time)
+  if (o->struct_size >= offsetof(rfx_masked_call_options, reserved4) + sizeof(int32_t)) {
+    const rfx_masked_call_options* m = reinterpret_cast<const rfx_masked_call_options*>(o);
+    if (m->reserved4 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_masked_call_options.reserved4 must be 0");
+    if (m->d_hold_bins) {
+      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and holds no bins (d_hold_bins must be NULL)");
+      if (!out->guide) return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_bins needs a guide to hold the bins at (d_guide is NULL)");
+      if (out->hold)
+        return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_bins together with d_hold_frames is not served: set the held frames' bits in the mask");
+      if ((uintptr_t)m->d_hold_bins & (sizeof(uint32_t) - 1)) return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_bins must be aligned to 4 bytes");
+      out->mask = m->d_hold_bins;
+      out->mask_words = m->hold_words;
+    }
+  }
   return RFX_OK;
 }
 
@@ -273,6 +301,7 @@ struct GlCall {
   int guide_samples;
   const int32_t* hold;  // null, or (B, 2) {head, tail}: launches 1 .. n_iter walk the free-frame list (rfx_guide_core.h) and leave the held
                         // frames' synthesis frames as launch 0 wrote them
+  const uint32_t* mask;  // null, or (B, T, ceil(n_stft / 32)) held bins: launches 1 .. n_iter read S_free and every fold adds c = ISTFT(S_held a0)
 };
 // ... and the fields that all four argument blocks have
 template <class Args>
@@ -312,7 +341,7 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   const GenGeom& g = plan->gg;
   const int B = c.B, T = c.T, L = c.L;
   const bool fam = plan->fam_ok;
-  const GenGlLayout w = gen_gl_layout(plan, B, T, c.hold != nullptr);
+  const GenGlLayout w = gen_gl_layout(plan, B, T, c.mask ? kGlMasked : c.hold ? kGlHeld : kGlPlain);
   if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   float* frames = (float*)(c.ws + w.frames);
   float* gen[3];
@@ -365,8 +394,29 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
     ga.audio_stride = (size_t)w.Lpad;
     ga.frames = frames;
   }
+  // masked (rfx_holdmask_core.h): X = S_held, one more MODE 1 launch on the staged guide and its fold give c = ISTFT(S_held a0) in the
+  // generations' units; launch 0 then runs on the full S as a guided call's does (the same bytes), and launches 1 .. n_iter on
+  // X = S_free, every fold adding c before it stores x and forms d.  The split acts on the order the frame kernels read.
+  const bool masked = c.mask && c.n_iter > 0;
+  float* X = (float*)(c.ws + w.xmag);
+  float* cadd = (float*)(c.ws + w.cadd);
+  const int x_layout = fam ? kHoldMaskTable : kHoldMaskPlain, x_stride = fam ? plan->fam.fsf : g.fs;
+  auto set_S = [&](const float* S) { fa.S = ga.S = S; };
+  if (masked) {
+    RFX_HIP(launch_holdmask_split(x_layout, c.S, X, c.mask, plan->d_fam_binof, B, T, x_stride, plan->n_stft, true, c.stream));
+    set_S(X);
+    RFX_HIP(fam         ? launch_fam_gl(1, fa, nblocks, c.stream)
+            : plan->czt ? launch_czt_gl(1, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
+                        : launch_gen_gl(1, ga, plan->num_cus, c.stream));
+    RFX_HIP(launch_gen_fold(frames, env, cadd, g, B, T, L, (size_t)w.Lpad, c.stream));
+    set_S(c.S);
+  }
   for (int it = 0; it <= c.n_iter; ++it) {
     const int mode = it == 0 && !c.guide ? 0 : 1;
+    if (masked && it == 1) {
+      RFX_HIP(launch_holdmask_split(x_layout, c.S, X, c.mask, plan->d_fam_binof, B, T, x_stride, plan->n_stft, false, c.stream));
+      set_S(X);
+    }
     if (c.hold && it > 0)
       RFX_HIP(fam         ? launch_fam_gl_list(fa, list, nblocks, c.stream)
               : plan->czt ? launch_czt_gl_list(ga, list, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
@@ -377,7 +427,8 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
                           : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
     const bool last = it == c.n_iter;
     RFX_HIP(launch_gen_fold(frames, env, last ? c.out : gen[it % 2], g, B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
-                            it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale));
+                            it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale,
+                            masked && it > 0 ? cadd : nullptr, (size_t)w.Lpad));
     RFX_HIP(timer.mark(it, c.stream));
   }
   RFX_HIP(timer.finish());
@@ -387,7 +438,7 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
 // Specialised engine: the per-frame form (frame kernel + fold per iteration) or the run form (one kernel per iteration)
 static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) {
   const int B = c.B, T = c.T, L = c.L;
-  const GlLayout w = gl_layout(plan, B, T, c.hold != nullptr);
+  const GlLayout w = gl_layout(plan, B, T, c.mask ? kGlMasked : c.hold ? kGlHeld : kGlPlain);
   if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   float* gen[3][2];  // x_k lives in generation k % 3
   for (int i = 0; i < 3; ++i)
@@ -397,7 +448,7 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
   RFX_HIP(hipGetLastError());
   if (int rc = gl_row_scale(c, (size_t)T * kFrameStride, (float*)(c.ws + w.row_scale))) return rc;
 
-  if (c.hold || gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
+  if (c.hold || c.mask || gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
     GlFrameArgs fa;
     set_gl_args(fa, c);
     fa.frames = (float*)(c.ws + w.frames);
@@ -413,13 +464,31 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
     // held: only the frame kernel writes fa.frames; launches 1 .. n_iter skip the held frames, whose entries stay launch 0's
     int* list = (int*)(c.ws + w.list);
     if (c.hold) RFX_HIP(launch_hold_list(c.hold, B, T, list, c.stream));
+    // masked: as in gen_griffinlim - c from X = S_held and the staged guide, launch 0 on S, launches 1 .. n_iter on X = S_free, + c in every fold
+    const bool masked = c.mask && c.n_iter > 0;
+    float* X = (float*)(c.ws + w.xmag);
+    float* cadd = (float*)(c.ws + w.cadd);
+    if (masked) {
+      RFX_HIP(launch_holdmask_split(kHoldMaskSpec, c.S, X, c.mask, nullptr, B, T, kFrameStride, kBins, true, c.stream));
+      fa.S = X;
+      fa.audio_in = gen[2][0];
+      fa.audio_prev = gen[1][0];
+      RFX_HIP(launch_gl_frame(1, fa, nblocks, c.stream));
+      RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, cadd, B, T, L, (size_t)w.Lpad, c.stream));
+      fa.S = c.S;
+    }
     for (int it = 0; it <= c.n_iter; ++it) {
+      if (masked && it == 1) {
+        RFX_HIP(launch_holdmask_split(kHoldMaskSpec, c.S, X, c.mask, nullptr, B, T, kFrameStride, kBins, false, c.stream));
+        fa.S = X;
+      }
       fa.audio_in = gen[(it + 2) % 3][0];    // x_{it-1}
       fa.audio_prev = gen[(it + 1) % 3][0];  // x_{it-2}
       if (c.hold && it > 0) RFX_HIP(launch_gl_frame_list(it == 1 ? 1 : 2, fa, list, nblocks, c.stream));
       else RFX_HIP(launch_gl_frame(it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2, fa, nblocks, c.stream));
       const bool last = it == c.n_iter;
-      RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream));
+      RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
+                             masked && it > 0 ? cadd : nullptr, (size_t)w.Lpad));
       RFX_HIP(timer.mark(it, c.stream));
     }
     RFX_HIP(timer.finish());
@@ -480,6 +549,8 @@ static int reflect_refusal(const rfx_plan* plan) {
 static int guide_refusal(const rfx_plan* plan, const CallOpt& opt, int T, bool has_angles0, const char* who) {
   if (!opt.guide) return RFX_OK;
   if (has_angles0) return fail(RFX_ERR_INVALID, std::string(who) + ": a guide and d_angles0_slots are two starts: give one");
+  if (opt.mask && opt.mask_words != rfx_hold_mask_words(plan))
+    return fail(RFX_ERR_INVALID, std::string(who) + ": hold_words must be rfx_hold_mask_words(plan) = " + std::to_string(rfx_hold_mask_words(plan)));
   if (T >= 2 && rfx_griffinlim_output_samples(plan, T) <= plan->p.n_fft / 2) return reflect_refusal(plan);
   return RFX_OK;
 }
@@ -498,7 +569,7 @@ static int griffinlim_impl(const rfx_plan* plan, const float* d_mag_slots, const
   RFX_ON_DEVICE(plan->device);
   GlCall c{d_mag_slots, (const cf*)d_angles0_slots, d_row_scale, opt.magnitude_hint, momentum / (1.f + momentum), seed,
            opt.row_base * (uint64_t)T, B, T, L, n_iter, d_wave_out, (char*)d_workspace, workspace_bytes, (hipStream_t)stream,
-           opt.guide, opt.guide_stride, opt.guide_samples, opt.hold};
+           opt.guide, opt.guide_stride, opt.guide_samples, opt.hold, opt.mask};
   LaunchTimer timer(h_launch_ms, n_iter + 1);
   return plan->generic ? gen_griffinlim(plan, c, mag_in_fam_slots, timer) : spec_griffinlim(plan, c, timer);
 }
@@ -525,6 +596,19 @@ int rfx_griffinlim_timed(const rfx_plan* plan, const float* d_mag_slots, const v
   if (!h_launch_ms) return fail(RFX_ERR_INVALID, "rfx_griffinlim_timed: null timing array");
   return griffinlim_impl(plan, d_mag_slots, d_angles0_slots, seed, B, T, n_iter, momentum, d_wave_out, d_workspace,
                          workspace_bytes, stream, h_launch_ms, CallOpt{});
+}
+
+// a per-mel-band mask to the bin mask of a masked call (rfx_holdmask_core.h), by the bins' band ranges uploaded with the plan
+int rfx_hold_bins_from_bands(const rfx_plan* plan, const uint8_t* d_bands, int B, int T, uint32_t* d_hold_bins_out, void* stream) {
+  if (!plan || !d_bands || !d_hold_bins_out) return fail(RFX_ERR_INVALID, "rfx_hold_bins_from_bands: null argument");
+  if (!plan->d_bin_bands) return fail(RFX_ERR_INVALID, "rfx_hold_bins_from_bands: plan was created without a mel filterbank");
+  if (B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_hold_bins_from_bands: bad shape");
+  if ((long long)B * T > 0x7fffffffLL) return fail(RFX_ERR_INVALID, "rfx_hold_bins_from_bands: more than 2^31 - 1 frames in one call");
+  if ((uintptr_t)d_hold_bins_out & (sizeof(uint32_t) - 1)) return fail(RFX_ERR_INVALID, "rfx_hold_bins_from_bands: d_hold_bins_out must be aligned to 4 bytes");
+  RFX_ON_DEVICE(plan->device);
+  RFX_HIP(launch_holdmask_bands(d_bands, plan->d_bin_bands, plan->d_bin_bands + plan->n_stft, d_hold_bins_out, B, plan->p.n_mels, T, plan->n_stft,
+                                (hipStream_t)stream));
+  return RFX_OK;
 }
 
 // ---- InverseMelScale ------------------------------------------------------------------------------------------------------------
@@ -674,9 +758,9 @@ struct WaveFromMelLayout {
   size_t lin, row_scale, rest, total;
   bool fam_slots;
 };
-static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, int T, bool held = false) {
+static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlPlain) {
   WaveFromMelLayout l{};
-  const size_t imel = rfx_inverse_mel_workspace_bytes(plan, B, T), gl = griffinlim_workspace(plan, B, T, held);
+  const size_t imel = rfx_inverse_mel_workspace_bytes(plan, B, T), gl = griffinlim_workspace(plan, B, T, kind);
   if (!imel || !gl) return l;
   const size_t lstsq = inverse_mel_lstsq_layout(plan, B, T).total;
   l.fam_slots = imel_can_emit_fam_slots(plan);
@@ -690,7 +774,8 @@ static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, i
   return l;
 }
 size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T).total : 0; }
-size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, true).total : 0; }
+size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlHeld).total : 0; }
+size_t rfx_waveform_from_mel_masked_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlMasked).total : 0; }
 
 static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                                  float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream, const CallOpt& opt) {
@@ -698,7 +783,7 @@ static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int 
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_waveform_from_mel")) return rc;
   if (int rc = guide_refusal(plan, opt, T, false, "rfx_waveform_from_mel")) return rc;
-  const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T, opt.hold != nullptr);
+  const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T, opt.kind());
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_waveform_from_mel: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
   char* ws = (char*)d_workspace;
@@ -733,11 +818,11 @@ int rfx_waveform_from_mel_ex(const rfx_plan* plan, const float* d_mel, int B, in
 struct AudioFromImageLayout {
   size_t mel, wave, rest, total;
 };
-static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N, int stereo, int T, bool held = false) {
+static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N, int stereo, int T, GlKind kind = kGlPlain) {
   AudioFromImageLayout l{};
   if (N <= 0 || T <= 0) return l;
   const int B = N * (stereo ? 2 : 1);
-  const size_t inner = waveform_from_mel_layout(plan, B, T, held).total;
+  const size_t inner = waveform_from_mel_layout(plan, B, T, kind).total;
   if (!inner) return l;
   Carve c;
   l.mel = c.take((size_t)B * plan->p.n_mels * T * sizeof(float));
@@ -750,7 +835,10 @@ size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int ste
   return plan ? audio_from_image_layout(plan, N, stereo, T).total : 0;
 }
 size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
-  return plan ? audio_from_image_layout(plan, N, stereo, T, true).total : 0;
+  return plan ? audio_from_image_layout(plan, N, stereo, T, kGlHeld).total : 0;
+}
+size_t rfx_audio_from_image_masked_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
+  return plan ? audio_from_image_layout(plan, N, stereo, T, kGlMasked).total : 0;
 }
 
 static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
@@ -761,7 +849,7 @@ static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_audio_from_image_u8")) return rc;
   if (int rc = guide_refusal(plan, opt, T, false, "rfx_audio_from_image_u8")) return rc;
-  const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T, opt.hold != nullptr);
+  const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T, opt.kind());
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_audio_from_image_u8: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
   const int C = stereo ? 2 : 1, B = N * C, M = plan->p.n_mels, L = rfx_griffinlim_output_samples(plan, T);

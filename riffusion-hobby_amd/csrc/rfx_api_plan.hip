@@ -196,7 +196,9 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
     // 7: everything the filterbank decides (host only)
     const PlanBank bank = plan_bank(geo, M, h_melfb, opt, ov);
     // 8: upload
+    if (M > 32767) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be below 32768");
     RFX_HIP(upload(pl.get(), &pl->d_melfb, h_melfb, (size_t)F * M));
+    RFX_HIP(upload(pl.get(), &pl->d_bin_bands, bin_bands(F, M, h_melfb)));
     if (!geo.generic) {
       RFX_HIP(upload(pl.get(), &pl->d_melfb_slots, bank.fbs));
       RFX_HIP(upload(pl.get(), &pl->d_kblocks, bank.kblocks));
@@ -308,6 +310,22 @@ int rfx_debug_lstsq_bank(const rfx_params* params, const float* h_melfb, rfx_lst
   if (lsq.ok && r.h_neg_l) memcpy(r.h_neg_l, lsq.nl.data(), lsq.nl.size() * sizeof(float));
   if (lsq.ok && r.h_inv_d) memcpy(r.h_inv_d, lsq.inv_d.data(), lsq.inv_d.size() * sizeof(float));
   memcpy(report, &r, r.struct_size);
+  return RFX_OK;
+}
+
+int rfx_hold_mask_words(const rfx_plan* plan) { return plan ? (plan->n_stft + 31) / 32 : 0; }
+
+int rfx_debug_bin_bands(const rfx_params* params, const float* h_melfb, int16_t* lo, int16_t* hi) {
+  if (!params || !h_melfb || !lo || !hi) return fail(RFX_ERR_INVALID, "rfx_debug_bin_bands: null argument");
+  if (params->n_mels <= 0 || params->n_mels > 32767) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be positive and below 32768");
+  rfx_plan_options opt;
+  if (const int rc = resolve_options(nullptr, &opt)) return rc;
+  PlanGeometry geo;
+  std::string err;
+  if (const int rc = plan_geometry(*params, opt, plan_overrides(), &geo, &err)) return fail(rc, err);
+  const std::vector<int16_t> v = bin_bands(geo.n_stft, params->n_mels, h_melfb);
+  memcpy(lo, v.data(), (size_t)geo.n_stft * sizeof(int16_t));
+  memcpy(hi, v.data() + geo.n_stft, (size_t)geo.n_stft * sizeof(int16_t));
   return RFX_OK;
 }
 

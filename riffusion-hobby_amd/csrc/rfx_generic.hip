@@ -180,10 +180,12 @@ __global__ void __launch_bounds__(256) gen_env_kernel(const float* __restrict__ 
 // `prev`; d = x_{k+1} when prev is null: the first iteration has no momentum term).  The Griffin-Lim kernel then fetches one
 // value per window sample instead of two and needs ten registers less across its last phase; the fold has x_{k+1} in a register
 // anyway.  Same fma as the kernel used to do: same bits.
+// ADD (a masked call, rfx_holdmask_core.h): x_{k+1} gets the call's constant audio c before it is stored and before d is formed.
+template <bool ADD>
 __global__ void __launch_bounds__(256) gen_fold_kernel(const float* __restrict__ frames, const float* __restrict__ env,
                                                        float* __restrict__ out, GenGeom g, int B, int T, int L, size_t out_stride,
                                                        const float* __restrict__ prev, float* __restrict__ dout, float mom,
-                                                       const float* __restrict__ row_scale) {
+                                                       const float* __restrict__ row_scale, const float* __restrict__ addend, size_t addend_stride) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
   if (p >= L) return;
@@ -192,15 +194,17 @@ __global__ void __launch_bounds__(256) gen_fold_kernel(const float* __restrict__
   gen_fold_range(g, q, T, tlo, thi);
   float acc = 0.f;
   for (int t = tlo; t <= thi; ++t) acc += frames[((size_t)b * T + t) * g.fpitch + g.fshift + (q - g.hop * t)];
-  const float x = acc / env[p];
+  float x = acc / env[p];
+  if (ADD) x += addend[(size_t)b * addend_stride + p];
   out[(size_t)b * out_stride + p] = x;
   const float ks = row_scale ? row_scale[2 * b] : 1.f;  // a power of two (GlArgs::row_scale)
   if (dout) dout[(size_t)b * out_stride + p] = ks * (prev ? fmaf(-mom, prev[(size_t)b * out_stride + p], x) : x);
 }
+template <bool ADD>
 __global__ void __launch_bounds__(256) gen_fold4_kernel(const float* __restrict__ frames, const float* __restrict__ env,
                                                         float* __restrict__ out, GenGeom g, int B, int T, int L, size_t out_stride,
                                                         const float* __restrict__ prev, float* __restrict__ dout, float mom,
-                                                        const float* __restrict__ row_scale) {
+                                                        const float* __restrict__ row_scale, const float* __restrict__ addend, size_t addend_stride) {
   using v4 = float __attribute__((ext_vector_type(4)));
   const int p = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
   const int b = blockIdx.y;
@@ -216,7 +220,8 @@ __global__ void __launch_bounds__(256) gen_fold4_kernel(const float* __restrict_
   v4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int t = tlo; t <= thi; ++t) acc += *reinterpret_cast<const v4*>(frames + ((size_t)b * T + t) * g.fpitch + g.fshift + (q - g.hop * t));
   const v4 e = *reinterpret_cast<const v4*>(env + p);
-  const v4 x = v4{acc.x / e.x, acc.y / e.y, acc.z / e.z, acc.w / e.w};
+  v4 x = v4{acc.x / e.x, acc.y / e.y, acc.z / e.z, acc.w / e.w};
+  if (ADD) x += *reinterpret_cast<const v4*>(addend + (size_t)b * addend_stride + p);
   *reinterpret_cast<v4*>(out + (size_t)b * out_stride + p) = x;
   if (dout) {
     v4 d = x;
@@ -365,12 +370,17 @@ hipError_t launch_gen_env(const float* win, float* env, const GenGeom& g, int T,
   return hipGetLastError();
 }
 hipError_t launch_gen_fold(const float* frames, const float* env, float* out, const GenGeom& g, int B, int T, int L, size_t out_stride,
-                           hipStream_t stream, const float* prev, float* dout, float mom, const float* row_scale) {
+                           hipStream_t stream, const float* prev, float* dout, float mom, const float* row_scale, const float* addend,
+                           size_t addend_stride) {
   const bool vec = g.fpitch % 4 == 0 && g.hop % 4 == 0 && (g.n_fft / 2 - g.left + g.fshift) % 4 == 0 && L % 4 == 0 && out_stride % 4 == 0 &&
                    (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && (reinterpret_cast<uintptr_t>(env) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(prev) & 15) == 0 && (reinterpret_cast<uintptr_t>(dout) & 15) == 0;
-  if (vec) hipLaunchKernelGGL(gen_fold4_kernel, dim3((L / 4 + 255) / 256, B), dim3(256), 0, stream, frames, env, out, g, B, T, L, out_stride, prev, dout, mom, row_scale);
-  else hipLaunchKernelGGL(gen_fold_kernel, dim3((L + 255) / 256, B), dim3(256), 0, stream, frames, env, out, g, B, T, L, out_stride, prev, dout, mom, row_scale);
+                   (reinterpret_cast<uintptr_t>(prev) & 15) == 0 && (reinterpret_cast<uintptr_t>(dout) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(addend) & 15) == 0 && addend_stride % 4 == 0;
+  const dim3 grid4((L / 4 + 255) / 256, B), grid1((L + 255) / 256, B);
+  if (vec && addend) hipLaunchKernelGGL(gen_fold4_kernel<true>, grid4, dim3(256), 0, stream, frames, env, out, g, B, T, L, out_stride, prev, dout, mom, row_scale, addend, addend_stride);
+  else if (vec) hipLaunchKernelGGL(gen_fold4_kernel<false>, grid4, dim3(256), 0, stream, frames, env, out, g, B, T, L, out_stride, prev, dout, mom, row_scale, addend, addend_stride);
+  else if (addend) hipLaunchKernelGGL(gen_fold_kernel<true>, grid1, dim3(256), 0, stream, frames, env, out, g, B, T, L, out_stride, prev, dout, mom, row_scale, addend, addend_stride);
+  else hipLaunchKernelGGL(gen_fold_kernel<false>, grid1, dim3(256), 0, stream, frames, env, out, g, B, T, L, out_stride, prev, dout, mom, row_scale, addend, addend_stride);
   return hipGetLastError();
 }
 

@@ -404,8 +404,11 @@ constexpr int kFramePitch = 4416;  // 4410 samples per synthesis frame, rounded 
 // (round 6, kGlGroup in rfx_kernels.h): an fma chain y w + acc in increasing t, split where a group boundary of the row falls
 // inside the block's frames, each side scaled by istft's normalisation, then added - gl_iter_kernel's two partial sums of the block.
 // Both forms give a clip the same bits (tests/test_gpu_round6.py).
+// ADD (a masked call, rfx_holdmask_core.h): the call's constant audio c is added to the folded sample before it is stored.
+template <bool ADD>
 __global__ void __launch_bounds__(256) gl_fold_kernel(const float* __restrict__ frames, const float* __restrict__ win,
-                                                      const float* __restrict__ scale, float* __restrict__ out, int T, int L, size_t out_stride) {
+                                                      const float* __restrict__ scale, float* __restrict__ out, int T, int L, size_t out_stride,
+                                                      const float* __restrict__ addend, size_t addend_stride) {
 #pragma clang fp contract(off)  // lo s + hi s below is two products and a sum, as in the run form (two stores and a load apart there)
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const int clip = blockIdx.y;
@@ -422,7 +425,8 @@ __global__ void __launch_bounds__(256) gl_fold_kernel(const float* __restrict__ 
   }
   const float s = scale[p];
   const float a = lo * s, b = hi * s;  // (HIP's __fmul_rn is a plain product the compiler may contract: the pragma above is what keeps these apart)
-  out[(size_t)clip * out_stride + p] = a + b;
+  const float x = a + b;
+  out[(size_t)clip * out_stride + p] = ADD ? x + addend[(size_t)clip * addend_stride + p] : x;
 }
 
 hipError_t launch_gl_frame(int mode, const GlFrameArgs& g, int nblocks, hipStream_t stream) {
@@ -440,8 +444,10 @@ hipError_t launch_gl_frame_list(int mode, const GlFrameArgs& g, const int* list,
   else hipLaunchKernelGGL(gl_frame_list_kernel<2>, dim3(nblocks), dim3(kThreads), lds, stream, g, list);
   return hipGetLastError();
 }
-hipError_t launch_gl_fold(const float* frames, const float* win, const float* scale, float* out, int B, int T, int L, size_t out_stride, hipStream_t stream) {
-  hipLaunchKernelGGL(gl_fold_kernel, dim3((L + 255) / 256, B), dim3(256), 0, stream, frames, win, scale, out, T, L, out_stride);
+hipError_t launch_gl_fold(const float* frames, const float* win, const float* scale, float* out, int B, int T, int L, size_t out_stride, hipStream_t stream,
+                          const float* addend, size_t addend_stride) {
+  if (addend) hipLaunchKernelGGL(gl_fold_kernel<true>, dim3((L + 255) / 256, B), dim3(256), 0, stream, frames, win, scale, out, T, L, out_stride, addend, addend_stride);
+  else hipLaunchKernelGGL(gl_fold_kernel<false>, dim3((L + 255) / 256, B), dim3(256), 0, stream, frames, win, scale, out, T, L, out_stride, addend, addend_stride);
   return hipGetLastError();
 }
 size_t gl_frame_buffer_bytes(int B, int T) { return (size_t)B * T * kFramePitch * sizeof(float); }

@@ -107,7 +107,9 @@ hipError_t launch_gl_frame(int mode, const GlFrameArgs& g, int nblocks, hipStrea
 // the same over the free-frame list of a held call (launch_hold_list): trip i of the grid-stride loop takes frame list[i], the trip
 // count is list[B T].  Modes 1 and 2; the grid is the unlisted launch's (the host does not know the count)
 hipError_t launch_gl_frame_list(int mode, const GlFrameArgs& g, const int* list, int nblocks, hipStream_t stream);
-hipError_t launch_gl_fold(const float* frames, const float* win, const float* scale, float* out, int B, int T, int L, size_t out_stride, hipStream_t stream);
+// addend (nullable; a masked call's constant audio, rows addend_stride apart): added to the folded sample before it is stored
+hipError_t launch_gl_fold(const float* frames, const float* win, const float* scale, float* out, int B, int T, int L, size_t out_stride, hipStream_t stream,
+                          const float* addend = nullptr, size_t addend_stride = 0);
 size_t gl_frame_buffer_bytes(int B, int T);
 
 // layout conversion between the reference's (B, n_stft, T) tensors and slot-major frames
@@ -339,7 +341,8 @@ hipError_t launch_gen_gl_list(const GenGlArgs& a, const int* list, int num_cus, 
 hipError_t launch_gen_env(const float* win, float* env, const GenGeom& g, int T, int L, hipStream_t stream);  // env[p] = sum_t w[j]^2, once per call
 hipError_t launch_gen_fold(const float* frames, const float* env, float* out, const GenGeom& g, int B, int T, int L, size_t out_stride,
                            hipStream_t stream, const float* prev = nullptr, float* dout = nullptr, float mom = 0.f,
-                           const float* row_scale = nullptr);  // L output samples per clip; dout = (x - mom prev) * row_scale[2 b]
+                           const float* row_scale = nullptr,  // L output samples per clip; dout = (x - mom prev) * row_scale[2 b]
+                           const float* addend = nullptr, size_t addend_stride = 0);  // masked call: x += addend[b][p] before out and dout
 hipError_t launch_gen_pack(const void* bft, void* frames, bool complex_, int B, int F, int T, int fs, hipStream_t stream);
 hipError_t launch_gen_unpack(const void* frames, void* bft, bool complex_, int B, int F, int T, int fs, hipStream_t stream);
 hipError_t launch_gen_mel(const float* mag, float* mel_tm, const float* band_wt, const int* band_lo, const int* band_len, long long nframes,
@@ -508,6 +511,14 @@ hipError_t launch_guide_stage(const float* guide, long long stride, int guide_sa
 // hold_list_words(B, T) ints: the indices row T + t of the frames that are not held, increasing, their count at list[B T], the
 // compaction's chunk offsets behind it.  Three launches, no atomics, nothing read back.
 hipError_t launch_hold_list(const int32_t* hold, int B, int T, int* list, hipStream_t stream);
+// a masked Griffin-Lim call (rfx_holdmask.hip, arithmetic in rfx_holdmask_core.h): X = S where the position's bin is held
+// (want_held) or free, 0 elsewhere and in the padding.  layout: kHoldMaskSpec / kHoldMaskPlain / kHoldMaskTable (bin_of: the table
+// of the last, [stride]); S and X: [B*T][stride]; mask: (B, T, ceil(n_stft / 32)) uint32
+hipError_t launch_holdmask_split(int layout, const float* S, float* X, const uint32_t* mask, const int* bin_of, int B, int T, int stride,
+                                 int n_stft, bool want_held, hipStream_t stream);
+// bands (B, M, T) uint8, nonzero = held -> the bin mask; lo / hi [n_stft]: first and last band of each bin (-1: none)
+hipError_t launch_holdmask_bands(const uint8_t* bands, const int16_t* lo, const int16_t* hi, uint32_t* out, int B, int M, int T, int n_stft,
+                                 hipStream_t stream);
 
 // closed-form InverseMelScale (rfx_imel_lstsq.hip, arithmetic in rfx_imel_lstsq_core.h).  The plan's tables: the float32
 // L D L^T factors of fb^T fb - nl[m] = -L[m + 1][m] (nl[M - 1] = 0), inv_d[m] = 1 / D[m] - and, for every position of an output

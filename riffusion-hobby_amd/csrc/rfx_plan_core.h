@@ -225,6 +225,19 @@ inline std::vector<int> fam_bin_of(const FamGeom& f) {  // [fsf] bin held by eac
 }
 
 // ---- filterbank analysis ---------------------------------------------------------------------------------------------------
+// [2 F]: for every bin the first band with a nonzero weight (lo, [0, F)) and the last (hi, [F, 2 F)); -1 / -1 for a bin no filter
+// reaches.  What rfx_hold_bins_from_bands expands a per-band mask by (rfx_holdmask_core.h); n_mels < 2^15.
+inline std::vector<int16_t> bin_bands(int F, int M, const float* fb) {
+  std::vector<int16_t> v((size_t)2 * F, (int16_t)-1);
+  for (int f = 0; f < F; ++f)
+    for (int m = 0; m < M; ++m)
+      if (fb[(size_t)f * M + m] != 0.f) {
+        if (v[f] < 0) v[f] = (int16_t)m;
+        v[(size_t)F + f] = (int16_t)m;
+      }
+  return v;
+}
+
 struct SlotEntry { float w0, w1; };
 constexpr double kImelLineTol = 4e-7;  // of a group's largest weight: see bank_groups
 

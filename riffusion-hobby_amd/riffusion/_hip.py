@@ -145,6 +145,35 @@ def held_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Te
                               o.guide_samples, 0, hold.data_ptr(), 0)
 
 
+_MASK_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)  # a bit mask's words
+
+
+class RfxMaskedCallOptions(ctypes.Structure):
+    """rfx_masked_call_options of include/rfx.h: rfx_held_call_options grown at its tail by the bins a guided call holds."""
+
+    _fields_ = RfxHeldCallOptions._fields_ + [("d_hold_bins", ctypes.c_void_p), ("hold_words", ctypes.c_int32), ("reserved4", ctypes.c_int32)]
+
+
+def masked_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
+                        row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False):
+    """`held_call_options`, with the held bins of a masked call: `hold_bins` a contiguous (rows, T, words) int32 (or uint32) tensor on
+    the guide's device, bin b of a frame held iff bit b & 31 of word b >> 5 is set; None gives the held (or guided, or plain)
+    options.  The caller keeps the tensors alive until the call is issued."""
+    o = held_call_options(guide, hold, rows, row_base, magnitude_hint, lstsq)
+    if hold_bins is None:
+        return o
+    if guide is None:
+        raise ValueError("hold_bins needs a guide: the bins are held at the guide's phase")
+    if hold is not None:
+        raise ValueError("hold_bins together with hold is not served: set the held frames' bits in the mask")
+    if hold_bins.dtype not in _MASK_DTYPES or hold_bins.dim() != 3 or hold_bins.shape[0] != rows or not hold_bins.is_contiguous():
+        raise ValueError(f"hold_bins must be a contiguous ({rows}, T, words) int32 tensor of bit masks, got {tuple(hold_bins.shape)} {hold_bins.dtype}")
+    if hold_bins.device != guide.device:
+        raise ValueError(f"hold_bins on {hold_bins.device}, guide on {guide.device}")
+    return RfxMaskedCallOptions(ctypes.sizeof(RfxMaskedCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, o.d_guide, o.guide_stride,
+                                o.guide_samples, 0, None, 0, hold_bins.data_ptr(), int(hold_bins.shape[2]), 0)
+
+
 def check_inverse_mel(inverse_mel: str) -> bool:
     """True for "lstsq", False for "sgd"; anything else raises."""
     if inverse_mel not in INVERSE_MEL_FORMS:
@@ -169,6 +198,16 @@ def lstsq_bank_report(cp: RfxParams, melfb: torch.Tensor, tables: bool = False):
         report.h_neg_l, report.h_inv_d = neg_l.ctypes.data, inv_d.ctypes.data
     check(load_library().rfx_debug_lstsq_bank(ctypes.byref(cp), melfb.data_ptr(), ctypes.byref(report)))
     return (report, (neg_l, inv_d) if report.ok else None) if tables else report
+
+
+def bin_bands(cp: RfxParams, melfb: torch.Tensor) -> T.Tuple[np.ndarray, np.ndarray]:
+    """rfx_debug_bin_bands (host only, no GPU) for the (n_stft, n_mels) float32 filterbank `melfb`: per linear bin the first and the
+    last mel band with a nonzero weight, (n_stft,) int16 each, -1 / -1 for a bin no filter reaches - what `Plan.hold_bins_from_bands`
+    expands a band mask by."""
+    melfb = melfb.to(torch.float32).contiguous()
+    lo, hi = np.zeros(melfb.shape[0], np.int16), np.zeros(melfb.shape[0], np.int16)
+    check(load_library().rfx_debug_bin_bands(ctypes.byref(cp), melfb.data_ptr(), lo.ctypes.data, hi.ctypes.data))
+    return lo, hi
 
 
 GL_FORMS = {"auto": 0, "runs": 1, "frames": 2}  # rfx_gl_form
@@ -218,6 +257,10 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_spectral_error": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_griffinlim_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_griffinlim_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_hold_mask_words": (c_int, [c_void_p]),
+    "rfx_hold_bins_from_bands": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "rfx_debug_bin_bands": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p]),
     "rfx_griffinlim_output_samples": (c_int, [c_void_p, c_int]),
     "rfx_griffinlim": (
         c_int,
@@ -248,10 +291,12 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_image_encode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rfx_audio_from_image_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "rfx_audio_from_image_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_audio_from_image_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "rfx_audio_from_image_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_audio_from_image_u8_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rfx_waveform_from_mel_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_waveform_from_mel_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_waveform_from_mel_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_waveform_from_mel_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rfx_waveform_from_mel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_image_from_waveform_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
@@ -607,6 +652,38 @@ class Plan:
             raise ValueError(f"hold must be a ({rows}, 2) int32 tensor of (head, tail) frames, got {tuple(hold.shape)} {hold.dtype}")
         return hold.contiguous()
 
+    def _chk_hold_bins(self, hold_bins: torch.Tensor, guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], rows: int, Tn: int) -> torch.Tensor:
+        """held bins as the library reads them: a contiguous (rows, Tn, hold_mask_words) int32 tensor of bit masks on the plan's device;
+        they need a guide and exclude `hold`"""
+        if guide is None:
+            raise ValueError("hold_bins needs a guide: the bins are held at the guide's phase")
+        if hold is not None:
+            raise ValueError("hold_bins together with hold is not served: set the held frames' bits in the mask")
+        if hold_bins.device != self.device:
+            raise ValueError(f"tensor on {hold_bins.device}, plan on {self.device}")
+        want = (rows, Tn, self.hold_mask_words)
+        if hold_bins.dtype not in _MASK_DTYPES or tuple(hold_bins.shape) != want:
+            raise ValueError(f"hold_bins must be a {want} int32 tensor of bit masks, got {tuple(hold_bins.shape)} {hold_bins.dtype}")
+        return hold_bins.contiguous()
+
+    @property
+    def hold_mask_words(self) -> int:
+        """words per frame of a masked call's bit mask: ceil(n_stft / 32) (rfx_hold_mask_words)"""
+        return int(self.lib.rfx_hold_mask_words(self.handle))
+
+    def hold_bins_from_bands(self, bands: torch.Tensor) -> torch.Tensor:
+        """rfx_hold_bins_from_bands: a (B, n_mels, T) bool / uint8 per-band mask (nonzero = held), in the layout of the mel tensor,
+        to the (B, T, hold_mask_words) int32 bin mask of `hold_bins=`: a bin is held where every band that reaches it is."""
+        if bands.dim() != 3 or bands.shape[1] != self.n_mels:
+            raise ValueError(f"expected a (B, {self.n_mels}, T) band mask, got {tuple(bands.shape)}")
+        if bands.dtype == torch.bool:
+            bands = bands.to(torch.uint8)
+        bands = self._chk(bands, torch.uint8)
+        B, _, Tn = bands.shape
+        out = torch.empty((B, Tn, self.hold_mask_words), dtype=torch.int32, device=self.device)
+        check(self.lib.rfx_hold_bins_from_bands(self.handle, bands.data_ptr(), B, Tn, out.data_ptr(), self._stream()))
+        return out
+
     def _stream(self) -> int:
         return current_stream(self.device)
 
@@ -672,6 +749,7 @@ class Plan:
         magnitude_hint: float = 0.0,
         guide: T.Optional[torch.Tensor] = None,
         hold: T.Optional[torch.Tensor] = None,
+        hold_bins: T.Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
         """GriffinLim on magnitudes in slot layout -> (B, samples).  `row_base`: index of the call's first row in the caller's
         whole batch (the random phases of row r are drawn from (seed, row_base + r): chunked and sharded batches get the starts
@@ -679,7 +757,9 @@ class Plan:
         `guide`: (B, Lg) float32 waveforms on the plan's device, any units; every row starts from the phase of its guide's STFT
         (the row cut or zero-padded to the output length) instead of random phases (rfx_guided_call_options): no randomness,
         `seed` and `row_base` then change nothing.  `hold`: (B, 2) int32 {head, tail} on the plan's device, with a guide: the
-        first `head` and last `tail` frames of a row keep the guide's phase through the iterations (rfx_held_call_options)."""
+        first `head` and last `tail` frames of a row keep the guide's phase through the iterations (rfx_held_call_options).
+        `hold_bins`: (B, Tn, hold_mask_words) int32 bit masks on the plan's device, with a guide and without `hold`: the set bins of
+        every frame keep the guide's phase (rfx_masked_call_options; `hold_bins_from_bands` makes them from a mel-band mask)."""
         mag_slots = self._chk(mag_slots, torch.float32)
         if angles0_slots is not None:
             angles0_slots = self._chk(angles0_slots, torch.complex64)
@@ -689,16 +769,19 @@ class Plan:
             guide = self._chk_guide(guide)
         if hold is not None:
             hold = self._chk_hold(hold, guide, B)
+        if hold_bins is not None:
+            hold_bins = self._chk_hold_bins(hold_bins, guide, hold, B, Tn)
         if mag_slots.numel() < B * Tn * self.frame_stride:
             raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
-        need = (self.lib.rfx_griffinlim_held_workspace_bytes if hold is not None else self.lib.rfx_griffinlim_workspace_bytes)(self.handle, B, Tn)
+        need = (self.lib.rfx_griffinlim_masked_workspace_bytes if hold_bins is not None else
+                self.lib.rfx_griffinlim_held_workspace_bytes if hold is not None else self.lib.rfx_griffinlim_workspace_bytes)(self.handle, B, Tn)
         if workspace is not None:
             workspace = self._chk(workspace)
         if workspace is None or workspace.numel() < need:  # no (or too small a) caller-owned workspace: the plan's arena
             with self._workspace(need) as ws:
-                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide, hold)
+                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide, hold, hold_bins)
         out = torch.empty((B, self.lib.rfx_griffinlim_output_samples(self.handle, Tn)), dtype=torch.float32, device=mag_slots.device)
-        opt = held_call_options(guide, hold, B, row_base, magnitude_hint)
+        opt = masked_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint)
         check(
             self.lib.rfx_griffinlim_ex(
                 self.handle,
@@ -959,10 +1042,12 @@ class Plan:
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
                           row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False,
-                          guide: T.Optional[torch.Tensor] = None, hold: T.Optional[torch.Tensor] = None) -> torch.Tensor:
+                          guide: T.Optional[torch.Tensor] = None, hold: T.Optional[torch.Tensor] = None,
+                          hold_bins: T.Optional[torch.Tensor] = None) -> torch.Tensor:
         """spectrogram_converter.py:187-204 in one call: (B, n_mels, T) -> (B, hop * (T - 1)); `inverse_mel` (seed) + `griffinlim`
         (seed + 1), same bits, the linear magnitudes stay in the workspace.  `lstsq`: `inverse_mel_lstsq` in place of the SGD.
-        `guide`: (B, Lg) float32 waveforms, `hold`: (B, 2) int32 held frames, as in `griffinlim`."""
+        `guide`: (B, Lg) float32 waveforms, `hold`: (B, 2) int32 held frames, `hold_bins`: (B, T, hold_mask_words) int32 held bins, as in
+        `griffinlim`."""
         if lstsq:
             self.require_lstsq()
         mel = self._chk(mel, torch.float32)
@@ -974,8 +1059,11 @@ class Plan:
             guide = self._chk_guide(guide)
         if hold is not None:
             hold = self._chk_hold(hold, guide, B)
-        opt = held_call_options(guide, hold, B, row_base, magnitude_hint, lstsq)
-        query = self.lib.rfx_waveform_from_mel_held_workspace_bytes if hold is not None else self.lib.rfx_waveform_from_mel_workspace_bytes
+        if hold_bins is not None:
+            hold_bins = self._chk_hold_bins(hold_bins, guide, hold, B, Tn)
+        opt = masked_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, lstsq)
+        query = (self.lib.rfx_waveform_from_mel_masked_workspace_bytes if hold_bins is not None else
+                 self.lib.rfx_waveform_from_mel_held_workspace_bytes if hold is not None else self.lib.rfx_waveform_from_mel_workspace_bytes)
         with self._workspace(query(self.handle, B, Tn)) as ws:
             check(self.lib.rfx_waveform_from_mel_ex(self.handle, mel.data_ptr(), B, Tn, channels_per_clip, seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
@@ -989,13 +1077,13 @@ class Plan:
     def audio_from_image(self, img: torch.Tensor, stereo: bool, lut: torch.Tensor, n_iter: int, momentum: float = 0.99, seed: int = 0,
                          normalize: bool = True, out: T.Optional[torch.Tensor] = None, workspace: T.Optional[torch.Tensor] = None,
                          clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None,
-                         hold: T.Optional[torch.Tensor] = None):
+                         hold: T.Optional[torch.Tensor] = None, hold_bins: T.Optional[torch.Tensor] = None):
         """spectrogram_image_converter.py:54-91 on the device in one call: (N, n_mels, T, 3) uint8 -> ((N, L, C) int16, per-clip peak (N,));
         `image_decode` + `waveform_from_mel` (clips of C rows) + `pcm16`, same bytes.  `out` as in `pcm16`.  `clip_base`: index of
         the call's first image in the caller's whole batch (row_base = clip_base * C); `magnitude_hint`: the image path's
         max_value (the largest entry of `lut`); `lstsq`: the closed-form InverseMelScale in place of the SGD; `guide`: (N * C, Lg)
         float32 waveforms, image after image and channel after channel, as in `griffinlim`; `hold`: (N * C, 2) int32 held frames, row
-        for row with the guide."""
+        for row with the guide; `hold_bins`: (N * C, T, hold_mask_words) int32 held bins, row for row as well."""
         if img.dtype != torch.uint8 or img.dim() != 4:
             raise ValueError("expected (N, H, W, 3) uint8 images")
         if lstsq:
@@ -1013,19 +1101,22 @@ class Plan:
             pcm = out
         else:
             pcm = torch.empty((N, L, C), dtype=torch.int16, device=img.device)
-        need = (self.lib.rfx_audio_from_image_held_workspace_bytes if hold is not None else self.lib.rfx_audio_from_image_workspace_bytes)(
+        need = (self.lib.rfx_audio_from_image_masked_workspace_bytes if hold_bins is not None else
+                self.lib.rfx_audio_from_image_held_workspace_bytes if hold is not None else self.lib.rfx_audio_from_image_workspace_bytes)(
             self.handle, N, int(stereo), W)
         ws = self._chk(workspace) if workspace is not None else None
         if ws is None or ws.numel() < need:
             with self._workspace(need) as borrowed:
                 return self.audio_from_image(img, stereo, lut, n_iter, momentum, seed, normalize, out=pcm, workspace=borrowed,
-                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold)
+                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins)
         peak = torch.zeros((N,), dtype=torch.float32, device=img.device)
         if guide is not None:
             guide = self._chk_guide(guide)
         if hold is not None:
             hold = self._chk_hold(hold, guide, N * C)
-        opt = held_call_options(guide, hold, N * C, clip_base * C, magnitude_hint, lstsq)
+        if hold_bins is not None:
+            hold_bins = self._chk_hold_bins(hold_bins, guide, hold, N * C, W)
+        opt = masked_call_options(guide, hold, hold_bins, N * C, clip_base * C, magnitude_hint, lstsq)
         check(self.lib.rfx_audio_from_image_u8_ex(self.handle, img.data_ptr(), N, W, int(stereo), lut.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                   int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return pcm, peak

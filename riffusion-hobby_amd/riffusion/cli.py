@@ -63,14 +63,21 @@ def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_freque
 
 
 def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto",
-                   guide_audio: str = "", griffin_lim_iters: int = -1, hold_head_ms: int = 0, hold_tail_ms: int = 0) -> None:
+                   guide_audio: str = "", griffin_lim_iters: int = -1, hold_head_ms: int = 0, hold_tail_ms: int = 0,
+                   hold_mask: str = "", hold_keep_threshold: float = 0.5) -> None:
     """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD,
     --frame-engine chirp-z runs parameters whose FFT length has a prime factor above 13 (refused otherwise).
     --guide-audio FILE starts Griffin-Lim from the phase of that clip (audio-to-audio: the clip the tile was made of; it must be at
     the tile's sample rate) instead of random phases, --griffin-lim-iters N runs N iterations instead of the params' 32 (a guided
     decode needs 0 to 4).  --hold-head-ms N / --hold-tail-ms N, with --guide-audio: the first / last N milliseconds of the clip are
     known audio (a continuation's left part, the ends around a re-drawn middle) - the frames whose windows lie wholly inside them keep
-    the guide's phase through the iterations instead of only starting from it."""
+    the guide's phase through the iterations instead of only starting from it.  --hold-mask MASK.png, with --guide-audio: a mask image
+    of the tile's size as the reference's mask_image (black is kept, white is repainted) - the kept region keeps the guide's phase
+    through the iterations; a pixel is kept where 1 - L / 255 >= --hold-keep-threshold (0.5).  Not together with the two above."""
+    if hold_mask and not guide_audio:
+        raise ValueError("--hold-mask needs --guide-audio: the bins are held at the guide's phase")
+    if hold_mask and (hold_head_ms or hold_tail_ms):
+        raise ValueError("--hold-mask does not go with --hold-head-ms / --hold-tail-ms: paint the held frames' columns black in the mask")
     if (hold_head_ms or hold_tail_ms) and not guide_audio:
         raise ValueError("--hold-head-ms / --hold-tail-ms need --guide-audio: the frames are held at the guide's phase")
     if hold_head_ms < 0 or hold_tail_ms < 0:
@@ -82,7 +89,9 @@ def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel:
                                                      guide_segment=_load_segment(guide_audio) if guide_audio else None,
                                                      griffin_lim_iters=griffin_lim_iters if griffin_lim_iters >= 0 else None,
                                                      hold_frames=params.hold_frames_for(hold_head_ms / 1000.0, hold_tail_ms / 1000.0)
-                                                     if hold_head_ms or hold_tail_ms else None)
+                                                     if hold_head_ms or hold_tail_ms else None,
+                                                     hold_mask=image_util.hold_mask_from_image(Image.open(hold_mask), hold_keep_threshold)
+                                                     if hold_mask else None)
     segment.export(audio, format=os.path.splitext(audio)[1][1:] or "wav")
     print(f"Wrote {audio} ({segment.duration_seconds:.2f} seconds)")
 
@@ -320,6 +329,13 @@ def main(argv: T.Optional[T.Sequence[str]] = None) -> None:
             parser.error("--hold-head-ms / --hold-tail-ms need --guide-audio: the frames are held at the guide's phase")
         if args["hold_head_ms"] < 0 or args["hold_tail_ms"] < 0:
             parser.error("--hold-head-ms / --hold-tail-ms must be >= 0")
+    if command == "image-to-audio" and args["hold_mask"]:
+        if not args["guide_audio"]:
+            parser.error("--hold-mask needs --guide-audio: the bins are held at the guide's phase")
+        if args["hold_head_ms"] or args["hold_tail_ms"]:
+            parser.error("--hold-mask does not go with --hold-head-ms / --hold-tail-ms")
+        if not 0.0 <= args["hold_keep_threshold"] <= 1.0:
+            parser.error("--hold-keep-threshold must be in [0, 1]")
     _COMMANDS[command](**args)
 
 

@@ -57,6 +57,20 @@ def hold_rows(hold_frames: T.Any, n: int, frames: int) -> torch.Tensor:
     return h.to(torch.int64).clamp(0, frames).to(torch.int32).contiguous()
 
 
+def hold_mask_rows(hold_mask: T.Any, n: int, n_mels: int, frames: int) -> torch.Tensor:
+    """`hold_mask` as the (n, n_mels, frames) uint8 tensor (nonzero = held, spectrogram orientation: band 0 first) the library
+    expands to bins: one (n_mels, frames) array or tensor serves all n entries, an (n, n_mels, frames) one gives each its own.
+    The tensor stays on the device it came on."""
+    m = torch.as_tensor(np.ascontiguousarray(hold_mask) if isinstance(hold_mask, np.ndarray) else hold_mask)
+    if m.is_complex():
+        raise ValueError(f"hold_mask must be boolean or real, got {m.dtype}")
+    if m.dim() == 2:
+        m = m[None].expand(n, *m.shape)
+    if tuple(m.shape) != (n, n_mels, frames):
+        raise ValueError(f"hold_mask must be ({n_mels}, {frames}) or ({n}, {n_mels}, {frames}), got {tuple(m.shape)}")
+    return (m != 0).to(torch.uint8)
+
+
 class SpectrogramConverter:
     def __init__(self, params: SpectrogramParams, device: str = "cuda", *, frame_engine: str = "auto"):
         """`frame_engine="chirp-z"` (not in the reference) runs parameter sets whose FFT length has a prime factor above 13 - which
@@ -177,6 +191,7 @@ class SpectrogramConverter:
         inverse_mel: str = "sgd",
         guide: T.Optional[torch.Tensor] = None,
         hold_frames: T.Any = None,
+        hold_mask: T.Any = None,
     ) -> torch.Tensor:
         """
         (B, n_mels, T) -> (B, hop*(T-1)).  The reference treats the whole batch as ONE clip (the SGD
@@ -195,6 +210,9 @@ class SpectrogramConverter:
         the last `tail` frames of a row keep the guide's phase through every iteration instead of only starting from it
         (rfx_held_call_options) - the part of a clip that is known audio does not move.  `hold_frames_for` turns seconds of known
         audio into the pair.  Values are clamped to the frame count.
+        `hold_mask`: with a guide and without `hold_frames`, a (B, n_mels, T) boolean (or nonzero = held) array or tensor in the
+        layout of the mel tensor: the linear bins every one of whose mel bands is held at a frame keep the guide's phase there
+        through every iteration (rfx_masked_call_options) - the kept region of a partial regeneration under a mask image.
         """
         if guide is not None and angles0 is not None:
             raise ValueError("guide and angles0 are two starts of Griffin-Lim: give one")
@@ -203,8 +221,15 @@ class SpectrogramConverter:
             if guide is None:
                 raise ValueError("hold_frames needs a guide: the frames are held at the guide's phase")
             hold = hold_rows(hold_frames, int(amplitudes_mel.shape[0]), int(amplitudes_mel.shape[-1]))
+        bands = None
+        if hold_mask is not None:
+            if guide is None:
+                raise ValueError("hold_mask needs a guide: the bins are held at the guide's phase")
+            if hold is not None:
+                raise ValueError("hold_frames together with hold_mask is not served: set the held frames' columns in the mask")
+            bands = hold_mask_rows(hold_mask, int(amplitudes_mel.shape[0]), int(amplitudes_mel.shape[1]), int(amplitudes_mel.shape[-1]))
         return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
-                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, hold=hold)
+                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, hold=hold, hold_bands=bands)
 
     def hold_frames_for(self, head_s: float = 0.0, tail_s: float = 0.0) -> T.Tuple[int, int]:
         """`SpectrogramParams.hold_frames_for` of this converter's params: the `hold_frames` pair for `head_s` / `tail_s` seconds
@@ -215,13 +240,15 @@ class SpectrogramConverter:
                            angles0: T.Optional[torch.Tensor] = None, seed: T.Optional[int] = None,
                            channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0,
                            return_slots: bool = False, inverse_mel: str = "sgd", guide: T.Optional[torch.Tensor] = None,
-                           n_iter: T.Optional[int] = None, hold: T.Optional[torch.Tensor] = None) -> T.Any:
+                           n_iter: T.Optional[int] = None, hold: T.Optional[torch.Tensor] = None,
+                           hold_bands: T.Optional[torch.Tensor] = None) -> T.Any:
         """`waveform_from_mel_amplitudes` on a plan the caller already holds (the batch entry points fetch it once per call,
         not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild).
         `return_slots=True` runs the two inverse stages separately - same bits as the one call - and returns
         (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares.  `guide`: (B, Lg) float32 guide
         waveforms (`waveform_from_mel_amplitudes`); `n_iter`: Griffin-Lim iterations in place of the params'; `hold`: (B, 2)
-        int32 held frames of a guided call (`hold_rows`)."""
+        int32 held frames of a guided call (`hold_rows`); `hold_bands`: (B, n_mels, T) uint8 held mel bands of a masked call
+        (`hold_mask_rows`), expanded to bins on the device."""
         from riffusion import _hip
 
         lstsq = _hip.check_inverse_mel(inverse_mel)
@@ -238,9 +265,10 @@ class SpectrogramConverter:
             guide = guide.to(self.device, torch.float32)
         if hold is not None:
             hold = hold.to(self.device)
+        hold_bins = plan.hold_bins_from_bands(hold_bands.to(self.device)) if hold_bands is not None else None
         if spec0 is None and angles0 is None and not return_slots:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
             return plan.waveform_from_mel(mel, cpc, n_iter, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint,
-                                          lstsq=lstsq, guide=guide, hold=hold)
+                                          lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins)
         spec0 = spec0.to(self.device) if spec0 is not None else None
         if lstsq:
             lin_slots = plan.inverse_mel_lstsq(mel)
@@ -248,7 +276,7 @@ class SpectrogramConverter:
             lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         a0 = plan.pack_complex(angles0.to(self.device)) if angles0 is not None else None
         wave = plan.griffinlim(lin_slots, B, Tn, n_iter, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
-                               magnitude_hint=magnitude_hint, guide=guide, hold=hold)
+                               magnitude_hint=magnitude_hint, guide=guide, hold=hold, hold_bins=hold_bins)
         return (wave, lin_slots) if return_slots else wave
 
     # ---- quality of a decode ------------------------------------------------------------------------

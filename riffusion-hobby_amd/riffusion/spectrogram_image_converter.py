@@ -16,7 +16,7 @@ import torch
 from PIL import Image
 
 from riffusion import _hip
-from riffusion.spectrogram_converter import SpectrogramConverter, hold_rows
+from riffusion.spectrogram_converter import SpectrogramConverter, hold_mask_rows, hold_rows
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import audio_util, image_util
 
@@ -63,6 +63,7 @@ class SpectrogramImageConverter:
         guide_segment: T.Any = None,
         griffin_lim_iters: T.Optional[int] = None,
         hold_frames: T.Optional[T.Tuple[int, int]] = None,
+        hold_mask: T.Any = None,
     ) -> T.Any:
         """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference).  The filters
         (audio_util.apply_filters, compression=False) run on the device: same bytes.  `inverse_mel`: "sgd" (default) or
@@ -71,9 +72,13 @@ class SpectrogramImageConverter:
         guides both channels of a stereo tile, more channels than the tile's are mixed down.  `griffin_lim_iters`: iterations for
         this call in place of the params' (a guided decode needs few).  `hold_frames`: with a guide, the `(head, tail)` frames at
         the clip's two ends that keep the guide's phase through the iterations (`hold_frames_for` turns seconds of known audio
-        into the pair).  All as in `audio_from_spectrogram_images`."""
+        into the pair).  `hold_mask`: with a guide, a mask image of the tile's size (black is kept, as the reference's `mask_image`)
+        or an (n_mels, W) boolean array: the kept region keeps the guide's phase through the iterations.  All as in
+        `audio_from_spectrogram_images`."""
         if hold_frames is not None and guide_segment is None:
             raise ValueError("hold_frames needs a guide: the frames are held at the guide's phase")
+        if hold_mask is not None and guide_segment is None:
+            raise ValueError("hold_mask needs a guide: the bins are held at the guide's phase")
         guides = None
         if guide_segment is not None:
             if int(guide_segment.frame_rate) != self.p.sample_rate:
@@ -85,6 +90,7 @@ class SpectrogramImageConverter:
         pcm = self.audio_from_spectrogram_images(
             np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters,
             inverse_mel=inverse_mel, guide_waveforms=guides, griffin_lim_iters=griffin_lim_iters, hold_frames=hold_frames,
+            hold_mask=hold_mask,
         )
         return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
 
@@ -121,6 +127,9 @@ class SpectrogramImageConverter:
         return_error: bool = False,
         *,
         inverse_mel: str = "sgd",
+        guide_waveforms: T.Any = None,
+        griffin_lim_iters: T.Optional[int] = None,
+        hold_mask: T.Any = None,
     ) -> T.Any:
         """
         A sequence of tiles -> ONE audio segment: every tile decoded (`audio_from_spectrogram_images`), filtered
@@ -141,8 +150,12 @@ class SpectrogramImageConverter:
         ((n,) float64; a device tensor with `return_device=True`); the segment's bytes do not change.  Not for tiles of
         different sizes without `size`.
         `inverse_mel`: "sgd" (default) or "lstsq", as in `audio_from_spectrogram_images`.
+        `guide_waveforms`, `griffin_lim_iters`, `hold_mask`: the guides of a phase-guided decode, its iterations and the kept
+        region of a partial regeneration, as in `audio_from_spectrogram_images`; not for tiles of different sizes without `size`.
         """
         _hip.check_inverse_mel(inverse_mel)
+        if hold_mask is not None and guide_waveforms is None:
+            raise ValueError("hold_mask needs guide_waveforms: the bins are held at the guides' phase")
         if isinstance(images, (list, tuple)):
             arrays = [np.asarray(image_util.rgb_array_from_image(im)) if isinstance(im, Image.Image) else np.asarray(im)
                       for im in images]
@@ -150,6 +163,8 @@ class SpectrogramImageConverter:
                 if size is None:
                     if return_error:
                         raise ValueError("return_error needs tiles of one size (or `size`): clips decoded one by one carry no error figure")
+                    if guide_waveforms is not None or griffin_lim_iters is not None:
+                        raise ValueError("guide_waveforms / griffin_lim_iters need tiles of one size (or `size`)")
                     return self._image_sequence_mixed(arrays, crossfade_s, apply_filters, max_value, seed, return_device, compression,
                                                       inverse_mel=inverse_mel)
                 images, size = torch.cat([self.resize_images(a[None], size) for a in arrays]), None
@@ -168,7 +183,8 @@ class SpectrogramImageConverter:
             on_device = False
         pcm = self.audio_from_spectrogram_images(images, max_value=max_value, seed=seed, tiles_per_call=tiles_per_call,
                                                  return_device=True, apply_filters=apply_filters, compression=compression, size=size,
-                                                 return_error=return_error, inverse_mel=inverse_mel)
+                                                 return_error=return_error, inverse_mel=inverse_mel, guide_waveforms=guide_waveforms,
+                                                 griffin_lim_iters=griffin_lim_iters, hold_mask=hold_mask)
         errors = None
         if return_error:
             pcm, errors = pcm
@@ -476,6 +492,7 @@ class SpectrogramImageConverter:
         guide_waveforms: T.Any = None,
         griffin_lim_iters: T.Optional[int] = None,
         hold_frames: T.Any = None,
+        hold_mask: T.Any = None,
     ) -> T.Any:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -550,6 +567,14 @@ class SpectrogramImageConverter:
         regeneration - does not move, and costs no iteration work.  `hold_frames_for(head_s, tail_s)` gives the pair for seconds of
         known audio; values are clamped to the tiles' frame count.  Without guides: ValueError.  Chunks and shards slice it like
         the guides.
+        `hold_mask`: with guides and without `hold_frames`, the kept region of a partial regeneration (rfx_masked_call_options):
+        a PIL mask image as the reference's `mask_image` - black is kept, white is repainted (`image_util.hold_mask_from_image`,
+        no resizing: the caller resizes it to the tiles' size) - or one (n_mels, W) boolean array for all clips, or an
+        (N, n_mels, W) array or tensor on any device, in spectrogram orientation (band 0 first), nonzero = held.  The linear bins
+        every one of whose mel bands is held at a frame keep guide i's phase there through every iteration, on both channel rows
+        of a stereo clip; the magnitudes stay the tiles'.  With `size=`, W is `size[0]`.  A mask removes no iteration work.
+        Without guides, with `hold_frames`, or in another shape: ValueError before any GPU work.  Chunks and shards slice it like
+        the guides.
         """
         from riffusion import batch_shard
 
@@ -605,6 +630,26 @@ class SpectrogramImageConverter:
                 raise ValueError("hold_frames needs guide_waveforms: the frames are held at the guides' phase")
             holds = hold_rows(hold_frames, n_total, int(size[0]) if size is not None else int(imgs.shape[2]))
 
+        bands = None
+        if hold_mask is not None:
+            if guides is None:
+                raise ValueError("hold_mask needs guide_waveforms: the bins are held at the guides' phase")
+            if holds is not None:
+                raise ValueError("hold_frames together with hold_mask is not served: set the held frames' columns in the mask")
+            if isinstance(hold_mask, Image.Image):
+                hold_mask = image_util.hold_mask_from_image(hold_mask)
+            bands = hold_mask_rows(hold_mask, n_total, plan.n_mels, int(size[0]) if size is not None else int(imgs.shape[2]))
+
+        def held_bins(a: int, b: int) -> T.Optional[torch.Tensor]:
+            """the held bins of tiles [a, b) as the (rows, T, words) device bit mask of the chunk's clip-channels: a clip's mask for
+            each of its channel rows"""
+            if bands is None:
+                return None
+            return plan.hold_bins_from_bands(bands[a:b].to(plan.device)).repeat_interleave(C, dim=0).contiguous()
+
+        def held_bands(a: int, b: int) -> T.Optional[torch.Tensor]:
+            return None if bands is None else bands[a:b].to(plan.device).repeat_interleave(C, dim=0).contiguous()
+
         def held_rows(a: int, b: int) -> T.Optional[torch.Tensor]:
             """the held frames of tiles [a, b) as the (rows, 2) int32 device tensor of the chunk's clip-channels: a clip's pair for each
             of its channel rows"""
@@ -649,7 +694,8 @@ class SpectrogramImageConverter:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave, lin_slots = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C,
                                                               magnitude_hint=max_value, return_slots=True, inverse_mel=inverse_mel,
-                                                              guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b))
+                                                              guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b),
+                                                              hold_bands=held_bands(a, b))
                     error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1])).reshape(b - a, C, 2).sum(1))
                     if return_waveform:
                         out = wave.reshape(b - a, C, -1)
@@ -660,13 +706,14 @@ class SpectrogramImageConverter:
                 elif return_waveform:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value,
-                                                   inverse_mel=inverse_mel, guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b))
+                                                   inverse_mel=inverse_mel, guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b),
+                                                   hold_bands=held_bands(a, b))
                     out = wave.reshape(b - a, C, -1)
                 else:  # uint8 tiles -> int16 PCM in one call (rfx_audio_from_image_u8_ex), same bytes as the three calls above + pcm16
                     dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
                     out = plan.audio_from_image(tiles, self.p.stereo, lut, n_iter, 0.99, seed=base_seed,
                                                 normalize=True, out=dst, clip_base=a, magnitude_hint=max_value, lstsq=lstsq,
-                                                guide=guide_rows(a, b), hold=held_rows(a, b))[0]
+                                                guide=guide_rows(a, b), hold=held_rows(a, b), hold_bins=held_bins(a, b))[0]
                     if apply_filters:
                         out = self._filter_pcm(plan, out, compression)
                 # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them

@@ -118,6 +118,17 @@ def spectrogram_from_image(
     return np.ascontiguousarray(lut[planes.transpose(2, 0, 1)])
 
 
+def hold_mask_from_image(mask_image: Image.Image, keep_threshold: float = 0.5) -> np.ndarray:
+    """A partial regeneration's mask image -> (n_mels, T) bool, True where the source is kept, in spectrogram orientation (band 0
+    first: Y flipped, as `spectrogram_from_image` does).  The reference's convention (riffusion_pipeline.py:455-477): white is
+    repainted, black is kept, and the latents are blended with 1 - mask; a pixel is held where 1 - L / 255 >= keep_threshold, L its
+    luminance (`convert("L")`).  No resizing: the caller brings the mask to the tile's size."""
+    if not (0.0 <= float(keep_threshold) <= 1.0):
+        raise ValueError(f"keep_threshold must be in [0, 1], got {keep_threshold}")
+    lum = np.asarray(mask_image.convert("L"), dtype=np.float64)[::-1]
+    return np.ascontiguousarray(1.0 - lum / 255.0 >= float(keep_threshold))
+
+
 def exif_from_image(pil_image: Image.Image) -> T.Dict[str, T.Any]:
     """EXIF of a spectrogram image as {tag name: value} (image_util.py:113-122)."""
     exif = pil_image.getexif()
