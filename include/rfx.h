@@ -132,6 +132,8 @@ int rfx_griffinlim_form(const rfx_plan* plan, int B, int T);
  * the plan's gl_form or this rule says: the run form keeps no frame buffer to hold frames in.  Both forms give a clip the same bits.) */
 /* (A masked call - rfx_masked_call_options.d_hold_bins - always takes RFX_GL_FORM_FRAMES on the specialised engine as well, whatever
  * the plan's gl_form or this rule says: the run form keeps two parity buffers per generation and sums them at run seams.) */
+/* (A loop call - rfx_loop_call_options.loop - always takes RFX_GL_FORM_FRAMES on the specialised engine too: the run form's
+ * sliding window and run seams are not looped.) */
 /* How one launch of the run-based form cuts the call's B*T frames (counted clip after clip) into runs, one per workgroup: returns
  * the number of runs and, if run_starts != NULL, writes min(runs + 1, capacity) run boundaries (run b = frames
  * [run_starts[b], run_starts[b + 1])).  which = 0: the first (synthesis-only) launch, 1: the iterations.  0 for a generic plan.
@@ -366,6 +368,51 @@ typedef struct {
   int32_t reserved4;        /* must be 0 */
 } rfx_masked_call_options;
 
+/* rfx_masked_call_options grown once more, by the same mechanism (struct_size = sizeof(rfx_loop_call_options); the first fourteen
+ * fields are rfx_masked_call_options' own): LOOP CALLS.  loop == 1: the row's T columns are the STFT of a signal with period
+ * P = hop T that runs from its end into its start - the tile is a loop, and the decode has no seam at the loop point.
+ *
+ * Definition.  h = n_fft / 2 (integer division), left = (n_fft - win_length) / 2, w the plan's window zero-padded to n_fft:
+ *   analysis   frame t, element i is x[(hop t + i - h) mod P] w[i], followed by the plan's real FFT - torch.stft(center=False) of
+ *              x[P - h:] || x || x[:n_fft - h] with the last frame dropped;
+ *   synthesis  y[m] = (sum of w[i] frame_t[i] over hop t + i - h = m mod P) / env[m], env[m] the same sum of w[i]^2;
+ *              P samples per row, for even and odd n_fft alike: rfx_griffinlim_loop_output_samples(plan, T) = hop T.
+ * The loop is torchaudio's functional.griffinlim unchanged - the random start, the momentum with tprev = 0 first, the 1e-16 guard,
+ * the final synthesis - with these two transforms in the place of torch.stft(center=True, reflect) and torch.istft.  env depends on
+ * m mod hop alone and is never small (3.75 to 1e-6 at the default geometry): there is no n_fft / 2 edge zone.
+ * On the device: the first launch (S angles0 -> frames) is the unlooped call's; launches 1 .. n_iter read their input modulo P
+ * (compile-time variants of the frame kernels), and every fold is circular: a sample sums its covering frames as one chain from the
+ * oldest covering frame on, the same chain wherever in the period it lies, times 1 / env from a hop-entry table made once per call.
+ * Exact consequences, bit for bit: columns (and injected angles) rolled by k give the audio rolled by k hop; a row depends on its
+ * magnitudes, its start and - through the random start only - on seed and row_base + its index, not on the batch.
+ * A guide (d_guide) is allowed: it is fitted to P samples by the guided call's rule and its start is G / |G| of the circular STFT.
+ * On the specialised engine a loop call always takes RFX_GL_FORM_FRAMES (the run form's sliding window and seams are not looped);
+ * the chirp-z engine refuses a loop call (RFX_ERR_UNSUPPORTED).  h_launch_ms keeps n_iter + 1 entries.
+ * Workspace: the *_loop_workspace_bytes twin of the entry's query.
+ * RFX_ERR_INVALID before any launch, the output untouched: loop > 1; reserved5 != 0; loop together with d_hold_frames or
+ * d_hold_bins; hop T < n_fft (a frame must cover the period at most once: T >= 40 at the default geometry, the smallest T is in the
+ * message).  RFX_ERR_WORKSPACE: a workspace below the loop query.  Honoured by rfx_griffinlim_ex, rfx_waveform_from_mel_ex and
+ * rfx_audio_from_image_u8_ex (hop T samples / PCM frames per row then); rfx_inverse_mel_ex refuses it.  A caller passing any of the
+ * four shorter struct sizes keeps exactly its behaviour and bytes. */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t flags;
+  uint64_t row_base;
+  float magnitude_hint;
+  float reserved;           /* must be 0 */
+  const float* d_guide;
+  int64_t guide_stride;
+  int32_t guide_samples;
+  int32_t reserved2;        /* must be 0 */
+  const int32_t* d_hold_frames;
+  uint64_t reserved3;       /* must be 0 */
+  const uint32_t* d_hold_bins;
+  int32_t hold_words;
+  int32_t reserved4;        /* must be 0 */
+  uint32_t loop;            /* 0: the call is rfx_masked_call_options' call; 1: a loop call */
+  uint32_t reserved5;       /* must be 0 */
+} rfx_loop_call_options;
+
 /* words per frame of a masked call's d_hold_bins: ceil(n_stft / 32); 0 for a NULL plan */
 int rfx_hold_mask_words(const rfx_plan* plan);
 /* A per-mel-band mask, in the layout of the mel tensor, to the bin mask of rfx_masked_call_options.  d_bands: (B, n_mels, T) uint8,
@@ -431,6 +478,13 @@ size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T);
 size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T);
 /* ... of a masked call (rfx_masked_call_options.d_hold_bins != NULL) */
 size_t rfx_griffinlim_masked_workspace_bytes(const rfx_plan* plan, int B, int T);
+/* ... of a loop call (rfx_loop_call_options.loop == 1); 0 where the call would be refused (hop T < n_fft, the chirp-z engine) */
+size_t rfx_griffinlim_loop_workspace_bytes(const rfx_plan* plan, int B, int T);
+/* samples per row a loop call writes for T frames: the period hop T; 0 for a NULL plan or T <= 0 */
+int rfx_griffinlim_loop_output_samples(const rfx_plan* plan, int T);
+/* the frame-count rule of a loop call, without a plan or a GPU (tests): RFX_OK, or the RFX_ERR_INVALID a loop call of T frames at
+ * these parameters gets, with its message */
+int rfx_debug_loop_frames(const rfx_params* params, int T);
 /* samples per clip rfx_griffinlim writes for T frames: what torch.istft(center=True, length=None) returns,
  * hop*(T-1), plus one when n_fft is odd */
 int rfx_griffinlim_output_samples(const rfx_plan* plan, int T);
@@ -545,6 +599,7 @@ int rfx_inverse_mel_lstsq(const rfx_plan* plan, const float* d_mel, int B, int T
 size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T);
 size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T);  /* with held frames (rfx_held_call_options) */
 size_t rfx_waveform_from_mel_masked_workspace_bytes(const rfx_plan* plan, int B, int T);  /* masked (rfx_masked_call_options) */
+size_t rfx_waveform_from_mel_loop_workspace_bytes(const rfx_plan* plan, int B, int T);    /* loop (rfx_loop_call_options) */
 int rfx_waveform_from_mel(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                           float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream);
 
@@ -767,6 +822,7 @@ int rfx_pcm16_clips_to_waveform(const int16_t* d_pcm, int64_t frames, int in_cha
 size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);
 size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* with held frames (rfx_held_call_options) */
 size_t rfx_audio_from_image_masked_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* masked (rfx_masked_call_options) */
+size_t rfx_audio_from_image_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);    /* loop (rfx_loop_call_options) */
 int rfx_audio_from_image_u8(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                             int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
                             size_t workspace_bytes, void* stream);

@@ -5,6 +5,7 @@
 #include "rfx_api.h"
 #include "rfx_guide_core.h"
 #include "rfx_holdmask_core.h"
+#include "rfx_loop_core.h"
 
 using namespace rfx;
 
@@ -149,21 +150,24 @@ int rfx_griffinlim_form(const rfx_plan* plan, int B, int T) {
 // between iterations (see rfx_gl.hip).  held (a call with rfx_held_call_options.d_hold_frames): always the per-frame form and its frame
 // buffer, and the free-frame list behind everything an unheld call has.  masked (rfx_masked_call_options.d_hold_bins): the
 // per-frame form as well, and behind everything else the second magnitude array X and the constant audio c (rfx_holdmask_core.h).
-enum GlKind { kGlPlain = 0, kGlHeld = 1, kGlMasked = 2 };
+// loop (rfx_loop_call_options.loop): the per-frame form, audio rows of the period's hop T samples, and the hop-entry reciprocal envelope
+// where the unlooped call keeps its normalisation table; no layout (total 0) for a T the call refuses.
+enum GlKind { kGlPlain = 0, kGlHeld = 1, kGlMasked = 2, kGlLoop = 3 };
 struct GlLayout {
   size_t audio, scale, frames, row_scale, list, xmag, cadd, total;
   int Lpad;
 };
 static size_t hold_list_bytes(int B, int T) { return hold_list_words(B, T) * sizeof(int32_t); }
 static GlLayout gl_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlPlain) {
-  const bool held = kind == kGlHeld, masked = kind == kGlMasked;
+  const bool held = kind == kGlHeld, masked = kind == kGlMasked, loop = kind == kGlLoop;
   GlLayout l{};
   if (B <= 0 || T < 2) return l;
-  l.Lpad = (int)align_up((size_t)kHop * (T - 1), 64);
+  if (loop && !loop_valid(kHop, T, kNfft)) return l;
+  l.Lpad = (int)align_up((size_t)kHop * (loop ? T : T - 1), 64);
   Carve c;
   l.audio = c.take(6 * (size_t)B * l.Lpad * sizeof(float));
   l.scale = c.take((size_t)l.Lpad * sizeof(float));
-  l.frames = c.take(held || masked || gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
+  l.frames = c.take(held || masked || loop || gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
   l.row_scale = c.take(range_table_bytes(B));
   l.list = c.take(held ? hold_list_bytes(B, T) : 0);
   l.xmag = c.take(masked ? (size_t)B * T * kFrameStride * sizeof(float) : 0);
@@ -183,12 +187,13 @@ struct GenGlLayout {
   int Lpad;
 };
 static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlPlain) {
-  const bool held = kind == kGlHeld, masked = kind == kGlMasked;
+  const bool held = kind == kGlHeld, masked = kind == kGlMasked, loop = kind == kGlLoop;
   GenGlLayout l{};
   if (B <= 0 || T < 2) return l;
   const GenGeom& g = plan->gg;
+  if (loop && (plan->czt || !loop_valid(g.hop, T, g.n_fft))) return l;
   const size_t nf = (size_t)B * T;
-  l.Lpad = (int)align_up((size_t)gen_out_len(g, T), 64);
+  l.Lpad = (int)align_up(loop ? (size_t)g.hop * T : (size_t)gen_out_len(g, T), 64);
   Carve c;
   l.frames = c.take(nf * g.fpitch * sizeof(float));
   l.audio = c.take((3 * (size_t)B + 1) * l.Lpad * sizeof(float));
@@ -208,6 +213,15 @@ static size_t griffinlim_workspace(const rfx_plan* plan, int B, int T, GlKind ki
 size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlPlain); }
 size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlHeld); }
 size_t rfx_griffinlim_masked_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlMasked); }
+size_t rfx_griffinlim_loop_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlLoop); }
+int rfx_griffinlim_loop_output_samples(const rfx_plan* plan, int T) {
+  if (!plan || T <= 0 || (long long)plan->p.hop_length * T > 0x7fffffffLL) return 0;
+  return plan->p.hop_length * T;
+}
+// samples per row of a call
+static int gl_out_samples(const rfx_plan* plan, int T, bool loop) {
+  return loop ? rfx_griffinlim_loop_output_samples(plan, T) : rfx_griffinlim_output_samples(plan, T);
+}
 
 // rfx_call_options as the entry points below see them (NULL / short struct = defaults)
 struct CallOpt {
@@ -223,7 +237,9 @@ struct CallOpt {
   // rfx_masked_call_options: (B, T, mask_words) bit mask of the bins held at the guide's phase (null: no bins held)
   const uint32_t* mask = nullptr;
   int mask_words = 0;
-  GlKind kind() const { return mask ? kGlMasked : hold ? kGlHeld : kGlPlain; }
+  // rfx_loop_call_options: the row's T columns are one period of a loop (rfx_loop_core.h)
+  bool loop = false;
+  GlKind kind() const { return loop ? kGlLoop : mask ? kGlMasked : hold ? kGlHeld : kGlPlain; }
 };
 // allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves); takes_guide: it runs Griffin-Lim
 static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who, uint32_t allowed_flags = 0, bool takes_guide = false) {
@@ -281,6 +297,18 @@ static int read_call_options(const rfx_call_options* o, CallOpt* out, const char
       out->mask_words = m->hold_words;
     }
   }
+  // the loop tail (rfx_loop_call_options: grown a fourth time)
+  if (o->struct_size >= offsetof(rfx_loop_call_options, reserved5) + sizeof(uint32_t)) {
+    const rfx_loop_call_options* l = reinterpret_cast<const rfx_loop_call_options*>(o);
+    if (l->reserved5 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_loop_call_options.reserved5 must be 0");
+    if (l->loop > 1) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_loop_call_options.loop must be 0 or 1");
+    if (l->loop) {
+      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and decodes no loop (loop must be 0)");
+      if (out->hold || out->mask)
+        return fail(RFX_ERR_INVALID, std::string(who) + ": loop together with d_hold_frames or d_hold_bins is not served");
+      out->loop = true;
+    }
+  }
   return RFX_OK;
 }
 
@@ -302,6 +330,7 @@ struct GlCall {
   const int32_t* hold;  // null, or (B, 2) {head, tail}: launches 1 .. n_iter walk the free-frame list (rfx_guide_core.h) and leave the held
                         // frames' synthesis frames as launch 0 wrote them
   const uint32_t* mask;  // null, or (B, T, ceil(n_stft / 32)) held bins: launches 1 .. n_iter read S_free and every fold adds c = ISTFT(S_held a0)
+  bool loop;  // L = hop T is the row's period: launches that read audio read it modulo L, every fold is circular (rfx_loop_core.h)
 };
 // ... and the fields that all four argument blocks have
 template <class Args>
@@ -341,7 +370,7 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   const GenGeom& g = plan->gg;
   const int B = c.B, T = c.T, L = c.L;
   const bool fam = plan->fam_ok;
-  const GenGlLayout w = gen_gl_layout(plan, B, T, c.mask ? kGlMasked : c.hold ? kGlHeld : kGlPlain);
+  const GenGlLayout w = gen_gl_layout(plan, B, T, c.loop ? kGlLoop : c.mask ? kGlMasked : c.hold ? kGlHeld : kGlPlain);
   if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   float* frames = (float*)(c.ws + w.frames);
   float* gen[3];
@@ -349,7 +378,9 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   float* env = (float*)(c.ws + w.audio) + (size_t)3 * B * w.Lpad;
   const size_t per_row = (size_t)T * ((fam && mag_in_fam_slots) ? (size_t)plan->fam.fsf : (size_t)g.fs);
   if (int rc = gl_row_scale(c, per_row, (float*)(c.ws + w.row_scale))) return rc;
-  RFX_HIP(launch_gen_env(plan->d_win, env, g, T, L, c.stream));
+  // (a loop call keeps the hop-entry reciprocal circular envelope there)
+  if (c.loop) RFX_HIP(launch_loop_renv(plan->d_win, env, g.n_fft, g.win, g.hop, 1.f, c.stream));
+  else RFX_HIP(launch_gen_env(plan->d_win, env, g, T, L, c.stream));
   // padded frame rows (gen_frame_layout): the kernels write the window samples only, the fold reads the padding as zeros
   if (g.fshift > 0) RFX_HIP(hipMemsetAsync(frames, 0, (size_t)B * T * g.fpitch * sizeof(float), c.stream));
   RFX_HIP(timer.begin(c.stream));
@@ -421,14 +452,20 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
       RFX_HIP(fam         ? launch_fam_gl_list(fa, list, nblocks, c.stream)
               : plan->czt ? launch_czt_gl_list(ga, list, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
                           : launch_gen_gl_list(ga, list, plan->num_cus, c.stream));
+    else if (c.loop && mode == 1)  // (never a chirp-z plan: refused before the driver)
+      RFX_HIP(fam ? launch_fam_gl_loop(fa, nblocks, c.stream) : launch_gen_gl_loop(ga, plan->num_cus, c.stream));
     else
       RFX_HIP(fam         ? launch_fam_gl(mode, fa, nblocks, c.stream)
               : plan->czt ? launch_czt_gl(mode, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
                           : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
     const bool last = it == c.n_iter;
-    RFX_HIP(launch_gen_fold(frames, env, last ? c.out : gen[it % 2], g, B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
-                            it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale,
-                            masked && it > 0 ? cadd : nullptr, (size_t)w.Lpad));
+    if (c.loop)
+      RFX_HIP(launch_gen_loop_fold(frames, env, last ? c.out : gen[it % 2], g, B, T, last ? (size_t)L : (size_t)w.Lpad, c.stream,
+                                   it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale));
+    else
+      RFX_HIP(launch_gen_fold(frames, env, last ? c.out : gen[it % 2], g, B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
+                              it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale,
+                              masked && it > 0 ? cadd : nullptr, (size_t)w.Lpad));
     RFX_HIP(timer.mark(it, c.stream));
   }
   RFX_HIP(timer.finish());
@@ -438,17 +475,21 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
 // Specialised engine: the per-frame form (frame kernel + fold per iteration) or the run form (one kernel per iteration)
 static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) {
   const int B = c.B, T = c.T, L = c.L;
-  const GlLayout w = gl_layout(plan, B, T, c.mask ? kGlMasked : c.hold ? kGlHeld : kGlPlain);
+  const GlLayout w = gl_layout(plan, B, T, c.loop ? kGlLoop : c.mask ? kGlMasked : c.hold ? kGlHeld : kGlPlain);
   if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   float* gen[3][2];  // x_k lives in generation k % 3
   for (int i = 0; i < 3; ++i)
     for (int p = 0; p < 2; ++p) gen[i][p] = (float*)(c.ws + w.audio) + (size_t)(2 * i + p) * B * w.Lpad;
   float* scale = (float*)(c.ws + w.scale);
-  hipLaunchKernelGGL(out_scale_kernel, dim3((L + 255) / 256), dim3(256), 0, c.stream, plan->d_win, scale, T, L);
-  RFX_HIP(hipGetLastError());
+  // (a loop call keeps the hop-entry table (2 / N) / env of the circular envelope there)
+  if (c.loop) RFX_HIP(launch_loop_renv(plan->d_win, scale, kNfft, kWin, kHop, 2.0f / (float)kNfft, c.stream));
+  else {
+    hipLaunchKernelGGL(out_scale_kernel, dim3((L + 255) / 256), dim3(256), 0, c.stream, plan->d_win, scale, T, L);
+    RFX_HIP(hipGetLastError());
+  }
   if (int rc = gl_row_scale(c, (size_t)T * kFrameStride, (float*)(c.ws + w.row_scale))) return rc;
 
-  if (c.hold || c.mask || gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
+  if (c.hold || c.mask || c.loop || gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
     GlFrameArgs fa;
     set_gl_args(fa, c);
     fa.frames = (float*)(c.ws + w.frames);
@@ -484,11 +525,16 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
       }
       fa.audio_in = gen[(it + 2) % 3][0];    // x_{it-1}
       fa.audio_prev = gen[(it + 1) % 3][0];  // x_{it-2}
+      const int mode = it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2;
       if (c.hold && it > 0) RFX_HIP(launch_gl_frame_list(it == 1 ? 1 : 2, fa, list, nblocks, c.stream));
-      else RFX_HIP(launch_gl_frame(it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2, fa, nblocks, c.stream));
+      else if (c.loop && mode != 0) RFX_HIP(launch_gl_frame_loop(mode, fa, nblocks, c.stream));
+      else RFX_HIP(launch_gl_frame(mode, fa, nblocks, c.stream));
       const bool last = it == c.n_iter;
-      RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
-                             masked && it > 0 ? cadd : nullptr, (size_t)w.Lpad));
+      if (c.loop)
+        RFX_HIP(launch_gl_loop_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, last ? (size_t)L : (size_t)w.Lpad, c.stream));
+      else
+        RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
+                               masked && it > 0 ? cadd : nullptr, (size_t)w.Lpad));
       RFX_HIP(timer.mark(it, c.stream));
     }
     RFX_HIP(timer.finish());
@@ -551,25 +597,44 @@ static int guide_refusal(const rfx_plan* plan, const CallOpt& opt, int T, bool h
   if (has_angles0) return fail(RFX_ERR_INVALID, std::string(who) + ": a guide and d_angles0_slots are two starts: give one");
   if (opt.mask && opt.mask_words != rfx_hold_mask_words(plan))
     return fail(RFX_ERR_INVALID, std::string(who) + ": hold_words must be rfx_hold_mask_words(plan) = " + std::to_string(rfx_hold_mask_words(plan)));
-  if (T >= 2 && rfx_griffinlim_output_samples(plan, T) <= plan->p.n_fft / 2) return reflect_refusal(plan);
+  if (!opt.loop && T >= 2 && rfx_griffinlim_output_samples(plan, T) <= plan->p.n_fft / 2) return reflect_refusal(plan);
   return RFX_OK;
+}
+// ... and every entry that decodes a loop
+static int loop_frames_refusal(int hop, int n_fft, int T, const char* who) {
+  if (loop_valid(hop, T, n_fft)) return RFX_OK;
+  return fail(RFX_ERR_INVALID, std::string(who) + ": a loop call needs hop_length * T >= n_fft (a frame covers the period at most once): at least " +
+                                   std::to_string(loop_min_frames(hop, n_fft)) + " frames, got " + std::to_string(T));
+}
+static int loop_refusal(const rfx_plan* plan, const CallOpt& opt, int T, const char* who) {
+  if (!opt.loop) return RFX_OK;
+  if (plan->czt)
+    return fail(RFX_ERR_UNSUPPORTED, std::string(who) + ": a loop call is not served on the chirp-z engine (its frame kernels have no circular variant)");
+  return loop_frames_refusal(plan->p.hop_length, plan->p.n_fft, T, who);
+}
+int rfx_debug_loop_frames(const rfx_params* params, int T) {
+  if (!params || params->hop_length <= 0 || params->n_fft <= 0) return fail(RFX_ERR_INVALID, "rfx_debug_loop_frames: bad argument");
+  return loop_frames_refusal(params->hop_length, params->n_fft, T, "rfx_debug_loop_frames");
 }
 
 static int griffinlim_impl(const rfx_plan* plan, const float* d_mag_slots, const void* d_angles0_slots, uint64_t seed, int B,
                            int T, int n_iter, float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes,
                            void* stream, float* h_launch_ms, const CallOpt& opt, bool mag_in_fam_slots = false,
                            const float* d_row_scale = nullptr) {
+  // (a loop call this plan or this T cannot serve has no workspace to bring: its refusal comes first)
+  if (plan)
+    if (int rc = loop_refusal(plan, opt, T, "rfx_griffinlim")) return rc;
   if (!plan || !d_mag_slots || !d_wave_out || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_griffinlim: null argument");
   if (B <= 0 || T < 2 || n_iter < 0) return fail(RFX_ERR_INVALID, "rfx_griffinlim: bad shape");
   if ((long long)B * T > 0x7fffffffLL) return fail(RFX_ERR_INVALID, "rfx_griffinlim: more than 2^31 - 1 frames in one call");
   if (!(momentum >= 0.f && momentum < 1.f)) return fail(RFX_ERR_INVALID, "rfx_griffinlim: momentum must be in [0, 1)");
-  const int L = rfx_griffinlim_output_samples(plan, T);
-  if (n_iter > 0 && L <= plan->p.n_fft / 2) return reflect_refusal(plan);
+  const int L = gl_out_samples(plan, T, opt.loop);
+  if (!opt.loop && n_iter > 0 && L <= plan->p.n_fft / 2) return reflect_refusal(plan);
   if (int rc = guide_refusal(plan, opt, T, d_angles0_slots != nullptr, "rfx_griffinlim")) return rc;
   RFX_ON_DEVICE(plan->device);
   GlCall c{d_mag_slots, (const cf*)d_angles0_slots, d_row_scale, opt.magnitude_hint, momentum / (1.f + momentum), seed,
            opt.row_base * (uint64_t)T, B, T, L, n_iter, d_wave_out, (char*)d_workspace, workspace_bytes, (hipStream_t)stream,
-           opt.guide, opt.guide_stride, opt.guide_samples, opt.hold, opt.mask};
+           opt.guide, opt.guide_stride, opt.guide_samples, opt.hold, opt.mask, opt.loop};
   LaunchTimer timer(h_launch_ms, n_iter + 1);
   return plan->generic ? gen_griffinlim(plan, c, mag_in_fam_slots, timer) : spec_griffinlim(plan, c, timer);
 }
@@ -776,9 +841,12 @@ static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, i
 size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T).total : 0; }
 size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlHeld).total : 0; }
 size_t rfx_waveform_from_mel_masked_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlMasked).total : 0; }
+size_t rfx_waveform_from_mel_loop_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlLoop).total : 0; }
 
 static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                                  float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream, const CallOpt& opt) {
+  if (plan)
+    if (int rc = loop_refusal(plan, opt, T, "rfx_waveform_from_mel")) return rc;
   if (!plan || !d_mel || !d_wave_out || !d_workspace || B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, "rfx_waveform_from_mel: bad argument");
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_waveform_from_mel")) return rc;
@@ -826,7 +894,7 @@ static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N,
   if (!inner) return l;
   Carve c;
   l.mel = c.take((size_t)B * plan->p.n_mels * T * sizeof(float));
-  l.wave = c.take((size_t)B * rfx_griffinlim_output_samples(plan, T) * sizeof(float));
+  l.wave = c.take((size_t)B * gl_out_samples(plan, T, kind == kGlLoop) * sizeof(float));
   l.rest = c.at;
   l.total = l.rest + inner;
   return l;
@@ -840,10 +908,15 @@ size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, in
 size_t rfx_audio_from_image_masked_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
   return plan ? audio_from_image_layout(plan, N, stereo, T, kGlMasked).total : 0;
 }
+size_t rfx_audio_from_image_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
+  return plan ? audio_from_image_layout(plan, N, stereo, T, kGlLoop).total : 0;
+}
 
 static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                                 int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
                                 size_t workspace_bytes, void* stream, const CallOpt& opt) {
+  if (plan)
+    if (int rc = loop_refusal(plan, opt, T, "rfx_audio_from_image_u8")) return rc;
   if (!plan || !d_img || !d_lut256 || !d_clip_peak || !d_pcm_out || !d_workspace || N <= 0 || T <= 0)
     return fail(RFX_ERR_INVALID, "rfx_audio_from_image_u8: bad argument");
   if (opt.lstsq)
@@ -852,7 +925,7 @@ static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int
   const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T, opt.kind());
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_audio_from_image_u8: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
-  const int C = stereo ? 2 : 1, B = N * C, M = plan->p.n_mels, L = rfx_griffinlim_output_samples(plan, T);
+  const int C = stereo ? 2 : 1, B = N * C, M = plan->p.n_mels, L = gl_out_samples(plan, T, opt.loop);
   char* ws = (char*)d_workspace;
   float* mel = reinterpret_cast<float*>(ws + w.mel);
   float* wave = reinterpret_cast<float*>(ws + w.wave);

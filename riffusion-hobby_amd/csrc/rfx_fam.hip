@@ -33,6 +33,7 @@
 #include "rfx_fam_core.h"
 #include "rfx_frame.hip.h"  // buffer-descriptor loads / stores (SRD in SGPRs + one 32-bit lane offset: no 64-bit per-lane addresses)
 #include "rfx_kernels.h"
+#include "rfx_loop_core.h"
 
 namespace rfx {
 
@@ -126,6 +127,11 @@ struct FamTwA {
 #undef RFX_GLK_LIST
 #define RFX_GLK_LIST 1
 #include "rfx_fam_gl_kernel.hip.h"
+#undef RFX_GLK_LIST
+#define RFX_GLK_LIST 0
+#define RFX_GLK_LOOP 1
+#include "rfx_fam_gl_kernel.hip.h"
+#undef RFX_GLK_LOOP
 #undef RFX_GLK_LIST
 
 #if RFX_FAM_TU == 0
@@ -312,6 +318,18 @@ FamGlListFn fam_gl_list_fn_packed(const FamGeom& g) {
     default: return nullptr;
   }
 }
+// ... and over a loop call's period (launches 1 .. n_iter)
+FamGlFn fam_gl_loop_fn_packed(const FamGeom& g) {
+  if (g.nrad == 20) return g.h == 441 ? fam_gl_loop_kernel<1, 21, 21, 20> : nullptr;  // 22.05 kHz
+  switch (g.h) {
+    case 80: return fam_gl_loop_kernel<1, 10, 8>;
+    case 160: return fam_gl_loop_kernel<1, 16, 10>;
+    case 240: return fam_gl_loop_kernel<1, 16, 15>;
+    case 320: return fam_gl_loop_kernel<1, 20, 16>;
+    case 441: return fam_gl_loop_kernel<1, 21, 21>;
+    default: return nullptr;
+  }
+}
 // unit 1: the packed Griffin-Lim kernels (every geometry but 48 kHz)
 FamGlFn fam_gl_fn_packed(const FamGeom& g, int mode) {
   if (g.nrad == 20) return g.h == 441 ? fam_fn<21, 21, 20>(mode) : nullptr;  // 22.05 kHz
@@ -363,6 +381,25 @@ static FamGlListFn fam_list_fn(const FamGeom& g) {
     default: return nullptr;
   }
 }
+FamGlFn fam_gl_loop_fn_packed(const FamGeom& g);  // rfx_fam_pk.hip
+static FamGlFn fam_loop_fn(const FamGeom& g) {
+#if !defined(RFX_NO_PK) && !defined(RFX_FAM_PK)
+  if (g.h != 480) return fam_gl_loop_fn_packed(g);
+#else
+  if (g.nrad == 20) return g.h == 441 ? fam_gl_loop_kernel<1, 21, 21, 20> : nullptr;  // 22.05 kHz
+#endif
+  switch (g.h) {
+#if defined(RFX_NO_PK) || defined(RFX_FAM_PK)
+    case 80: return fam_gl_loop_kernel<1, 10, 8>;
+    case 160: return fam_gl_loop_kernel<1, 16, 10>;
+    case 240: return fam_gl_loop_kernel<1, 16, 15>;
+    case 320: return fam_gl_loop_kernel<1, 20, 16>;
+    case 441: return fam_gl_loop_kernel<1, 21, 21>;
+#endif
+    case 480: return fam_gl_loop_kernel<1, 24, 20>;
+    default: return nullptr;
+  }
+}
 
 using FamFwdFn = void (*)(FamFwdArgs);
 template <int RA, int RB, int NR = 40>
@@ -398,6 +435,9 @@ hipError_t prepare_fam_kernels(const FamGeom& g) {
     const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fam_lds_bytes(g));
     if (e != hipSuccess) return e;
   }
+  const FamGlFn pfn = fam_loop_fn(g);
+  if (!pfn) return hipErrorInvalidValue;
+  if (const hipError_t e = hipFuncSetAttribute((const void*)pfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fam_lds_bytes(g)); e != hipSuccess) return e;
   const FamGlListFn lfn = fam_list_fn(g);
   if (!lfn) return hipErrorInvalidValue;
   return hipFuncSetAttribute((const void*)lfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fam_lds_bytes(g));
@@ -416,6 +456,11 @@ hipError_t launch_fam_gl(int mode, const FamGlArgs& a, int nblocks, hipStream_t 
 
 hipError_t launch_fam_gl_list(const FamGlArgs& a, const int* list, int nblocks, hipStream_t stream) {
   hipLaunchKernelGGL(fam_list_fn(a.g), dim3(nblocks), dim3(a.g.nthr), fam_lds_bytes(a.g), stream, a, list);
+  return hipGetLastError();
+}
+
+hipError_t launch_fam_gl_loop(const FamGlArgs& a, int nblocks, hipStream_t stream) {
+  hipLaunchKernelGGL(fam_loop_fn(a.g), dim3(nblocks), dim3(a.g.nthr), fam_lds_bytes(a.g), stream, a);
   return hipGetLastError();
 }
 

@@ -4,9 +4,19 @@
 //   RFX_GLK_LIST 1  fam_gl_list_kernel<MODE, RA, RB, NR, TU>  trip i of the loop takes frame list[i], list[B T] trips in all, and the next
 //                                                              frame's prefetch follows the list: launches 1 .. n_iter of a held call
 //                                                              (include/rfx.h: rfx_held_call_options; the list: rfx_guide_core.h)
-// One text, chosen at compile time: no branch on the form inside either kernel.
+//   RFX_GLK_LOOP 1  fam_gl_loop_kernel<MODE, RA, RB, NR, TU>  (with RFX_GLK_LIST 0) a loop call's launches 1 .. n_iter (include/rfx.h:
+//                                                              rfx_loop_call_options): the analysis input is read modulo the period
+//                                                              a.L = hop T (rfx_loop_core.h) instead of reflected
+// One text, chosen at compile time: no branch on the form inside any of the kernels.
+#if RFX_GLK_LOOP
+#define RFX_GLK_POS(p, L) loop_wrap(p, L)
+#else
+#define RFX_GLK_POS(p, L) reflect_index(p, L)
+#endif
 template <int MODE, int RA, int RB, int NR = 40, int TU = RFX_FAM_TU>
-#if RFX_GLK_LIST
+#if RFX_GLK_LOOP
+__global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu_waves_per_eu(4))) fam_gl_loop_kernel(FamGlArgs a) {
+#elif RFX_GLK_LIST
 __global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu_waves_per_eu(4))) fam_gl_list_kernel(FamGlArgs a, const int* __restrict__ list) {
 #else
 __global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu_waves_per_eu(4))) fam_gl_kernel(FamGlArgs a) {
@@ -73,7 +83,7 @@ __global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu
     const int clip = (int)(gf / a.T), fr = (int)(gf - (long long)clip * a.T);
     const rsrc_t xc = make_rsrc(a.x_cur + (size_t)clip * a.audio_stride, (size_t)a.L * sizeof(float));
 #pragma unroll
-    for (int j = 0; j < WH; ++j) u[j] = ld1(xc, (unsigned)reflect_index(a.g.hop * fr + a.g.off + j * H + npr, a.L) * 4u, 0);
+    for (int j = 0; j < WH; ++j) u[j] = ld1(xc, (unsigned)RFX_GLK_POS(a.g.hop * fr + a.g.off + j * H + npr, a.L) * 4u, 0);
   };
   auto window_samples = [&] {
 #pragma unroll
@@ -212,3 +222,4 @@ __global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu
            (double)tacc[6] / nfr, (double)tacc[0] / nfr);
 #endif
 }
+#undef RFX_GLK_POS

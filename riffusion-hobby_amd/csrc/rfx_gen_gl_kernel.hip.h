@@ -3,10 +3,19 @@
 //                                                    always compiled to)
 //   RFX_GLK_LIST 1  gen_gl_list_kernel<MODE, MAXR>  trip i of the loop takes frame list[i], list[B T] trips in all: launches 1 .. n_iter of a
 //                                                    held call (include/rfx.h: rfx_held_call_options; the list: rfx_guide_core.h)
-// One text, chosen at compile time: no branch on the form inside either kernel.
+//   RFX_GLK_LOOP 1  gen_gl_loop_kernel<MODE, MAXR>  (with RFX_GLK_LIST 0) a loop call's launches 1 .. n_iter (include/rfx.h: rfx_loop_call_options):
+//                                                    the analysis input is read modulo the period a.L = hop T (rfx_loop_core.h) instead of reflected
+// One text, chosen at compile time: no branch on the form inside any of the kernels.
+#if RFX_GLK_LOOP
+#define RFX_GLK_POS(p, L) loop_wrap(p, L)
+#else
+#define RFX_GLK_POS(p, L) reflect_index(p, L)
+#endif
 template <int MODE, int MAXR>
 __global__ void __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(MAXR <= 7 ? 4 : 2)))
-#if RFX_GLK_LIST
+#if RFX_GLK_LOOP
+gen_gl_loop_kernel(GenGlArgs a) {
+#elif RFX_GLK_LIST
 gen_gl_list_kernel(GenGlArgs a, const int* __restrict__ list) {
 #else
 gen_gl_kernel(GenGlArgs a) {
@@ -73,7 +82,7 @@ gen_gl_kernel(GenGlArgs a) {
               const int i = per * n + e;  // position inside the padded frame
               const int j = i - g.left;   // position inside the window
               if (j >= 0 && j < g.win) {
-                const int p = reflect_index(g.hop * t + i - half, a.L);
+                const int p = RFX_GLK_POS(g.hop * t + i - half, a.L);
                 xs[u][e] = xc[p];
                 if (MODE == 2) ps[u][e] = xp[p];
                 ws[u][e] = a.tb.win[j];
@@ -170,3 +179,4 @@ gen_gl_kernel(GenGlArgs a) {
            (double)tacc[0] / nfr, (double)tacc[1] / nfr, (double)tacc[2] / nfr, (double)tacc[3] / nfr, (double)tacc[4] / nfr, (double)tacc[5] / nfr);
 #endif
 }
+#undef RFX_GLK_POS

@@ -16,6 +16,7 @@
 
 #include "rfx_gen_core.h"
 #include "rfx_kernels.h"
+#include "rfx_loop_core.h"
 
 namespace rfx {
 
@@ -151,6 +152,11 @@ gen_stft_kernel(GenStftArgs a) {
 #define RFX_GLK_LIST 1
 #include "rfx_gen_gl_kernel.hip.h"
 #undef RFX_GLK_LIST
+#define RFX_GLK_LIST 0
+#define RFX_GLK_LOOP 1
+#include "rfx_gen_gl_kernel.hip.h"
+#undef RFX_GLK_LOOP
+#undef RFX_GLK_LIST
 
 // overlap-add of the windowed frames and division by the window envelope (torch.istft center=True, length = hop*(T-1)):
 // sample p of the output sits at P = p + n_fft/2 of the padded signal; frame t contributes its window sample
@@ -231,6 +237,53 @@ __global__ void __launch_bounds__(256) gen_fold4_kernel(const float* __restrict_
     }
     const float ks = row_scale ? row_scale[2 * b] : 1.f;
     *reinterpret_cast<v4*>(dout + (size_t)b * out_stride + p) = v4{ks * d.x, ks * d.y, ks * d.z, ks * d.w};
+  }
+}
+
+// ---- loop call (rfx_loop_core.h): the circular folds of the generic engine and the row family.  Output sample m < P = hop T sums the
+// window samples j = q - hop t, q = m + n_fft / 2 - left, of its UNWRAPPED covering frames t = tlo .. thi (loop_fold_range), frame
+// t mod T each, as one chain from the oldest on - the same chain wherever in the period m lies - and multiplies by the reciprocal
+// circular envelope renv[m mod hop] (launch_loop_renv, once per call).  Second output d and row_scale as in gen_fold_kernel.  The
+// 4-wide form under gen_fold4_kernel's conditions: with hop a multiple of four the samples of a group share m mod hop's block and
+// their frames, or read the zero padding of a row.
+__global__ void __launch_bounds__(256) gen_loop_fold_kernel(const float* __restrict__ frames, const float* __restrict__ renv,
+                                                            float* __restrict__ out, GenGeom g, int B, int T, int P, size_t out_stride,
+                                                            const float* __restrict__ prev, float* __restrict__ dout, float mom,
+                                                            const float* __restrict__ row_scale) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  if (m >= P) return;
+  const float acc = loop_fold_sum(frames + (size_t)b * T * g.fpitch, (size_t)g.fpitch, g.fshift, m + g.n_fft / 2 - g.left, g.win, g.hop, T);
+  const float x = acc * renv[m % g.hop];
+  out[(size_t)b * out_stride + m] = x;
+  const float ks = row_scale ? row_scale[2 * b] : 1.f;
+  if (dout) dout[(size_t)b * out_stride + m] = ks * (prev ? fmaf(-mom, prev[(size_t)b * out_stride + m], x) : x);
+}
+__global__ void __launch_bounds__(256) gen_loop_fold4_kernel(const float* __restrict__ frames, const float* __restrict__ renv,
+                                                             float* __restrict__ out, GenGeom g, int B, int T, int P, size_t out_stride,
+                                                             const float* __restrict__ prev, float* __restrict__ dout, float mom,
+                                                             const float* __restrict__ row_scale) {
+  using v4 = float __attribute__((ext_vector_type(4)));
+  const int m = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
+  const int b = blockIdx.y;
+  if (m >= P) return;
+  const int q = m + g.n_fft / 2 - g.left;
+  int tlo, thi, tmp;
+  loop_fold_range(q, g.win, g.hop, tlo, tmp);
+  loop_fold_range(q + 3, g.win, g.hop, tmp, thi);
+  v4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int t = tlo; t <= thi; ++t)
+    acc += *reinterpret_cast<const v4*>(frames + ((size_t)b * T + loop_frame(t, T)) * g.fpitch + g.fshift + (q - g.hop * t));
+  const v4 x = acc * *reinterpret_cast<const v4*>(renv + m % g.hop);
+  *reinterpret_cast<v4*>(out + (size_t)b * out_stride + m) = x;
+  if (dout) {
+    v4 d = x;
+    if (prev) {
+      const v4 xp = *reinterpret_cast<const v4*>(prev + (size_t)b * out_stride + m);
+      d = v4{fmaf(-mom, xp.x, x.x), fmaf(-mom, xp.y, x.y), fmaf(-mom, xp.z, x.z), fmaf(-mom, xp.w, x.w)};
+    }
+    const float ks = row_scale ? row_scale[2 * b] : 1.f;
+    *reinterpret_cast<v4*>(dout + (size_t)b * out_stride + m) = v4{ks * d.x, ks * d.y, ks * d.z, ks * d.w};
   }
 }
 
@@ -337,9 +390,15 @@ static GenGlListFn gen_gl_list_fn(const GenGeom& g) {
   return c == 5 ? gen_gl_list_kernel<1, 5> : c == 7 ? gen_gl_list_kernel<1, 7> : gen_gl_list_kernel<1, 13>;
 }
 
+static GenGlFn gen_gl_loop_fn(const GenGeom& g) {
+  const int c = gen_radix_class(g.radix, g.nstages);
+  return c == 5 ? gen_gl_loop_kernel<1, 5> : c == 7 ? gen_gl_loop_kernel<1, 7> : gen_gl_loop_kernel<1, 13>;
+}
+
 hipError_t prepare_generic_kernels(const GenGeom& g) {
   const int lds = (int)gen_lds_bytes(g);
   hipError_t e;
+  if ((e = hipFuncSetAttribute((const void*)gen_gl_loop_fn(g), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   for (int mode = 0; mode < 2; ++mode)
     if ((e = hipFuncSetAttribute((const void*)gen_stft_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   for (int mode = 0; mode < 3; ++mode)
@@ -362,6 +421,23 @@ hipError_t launch_gen_gl(int mode, const GenGlArgs& a, int num_cus, hipStream_t 
 hipError_t launch_gen_gl_list(const GenGlArgs& a, const int* list, int num_cus, hipStream_t stream) {
   const int grid = gen_grid(a.g, num_cus, (long long)a.B * a.T);
   hipLaunchKernelGGL(gen_gl_list_fn(a.g), dim3(grid), dim3(a.g.nthr), gen_lds_bytes(a.g), stream, a, list);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_gl_loop(const GenGlArgs& a, int num_cus, hipStream_t stream) {
+  const int grid = gen_grid(a.g, num_cus, (long long)a.B * a.T);
+  hipLaunchKernelGGL(gen_gl_loop_fn(a.g), dim3(grid), dim3(a.g.nthr), gen_lds_bytes(a.g), stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_loop_fold(const float* frames, const float* renv, float* out, const GenGeom& g, int B, int T, size_t out_stride, hipStream_t stream,
+                                const float* prev, float* dout, float mom, const float* row_scale) {
+  const int P = g.hop * T;
+  const bool vec = g.fpitch % 4 == 0 && g.hop % 4 == 0 && (g.n_fft / 2 - g.left + g.fshift) % 4 == 0 && out_stride % 4 == 0 &&
+                   (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && (reinterpret_cast<uintptr_t>(renv) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(prev) & 15) == 0 && (reinterpret_cast<uintptr_t>(dout) & 15) == 0;
+  if (vec) hipLaunchKernelGGL(gen_loop_fold4_kernel, dim3((P / 4 + 255) / 256, B), dim3(256), 0, stream, frames, renv, out, g, B, T, P, out_stride, prev, dout, mom, row_scale);
+  else hipLaunchKernelGGL(gen_loop_fold_kernel, dim3((P + 255) / 256, B), dim3(256), 0, stream, frames, renv, out, g, B, T, P, out_stride, prev, dout, mom, row_scale);
   return hipGetLastError();
 }
 

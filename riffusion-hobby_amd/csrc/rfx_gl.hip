@@ -36,6 +36,7 @@
 #define RFX_PK 1  // packed fp32 butterflies (rfx_core.h)
 #include "rfx_frame.hip.h"
 #include "rfx_kernels.h"
+#include "rfx_loop_core.h"
 
 namespace rfx {
 
@@ -399,6 +400,11 @@ constexpr int kFramePitch = 4416;  // 4410 samples per synthesis frame, rounded 
 #define RFX_GLK_LIST 1
 #include "rfx_gl_frame_kernel.hip.h"
 #undef RFX_GLK_LIST
+#define RFX_GLK_LIST 0
+#define RFX_GLK_LOOP 1
+#include "rfx_gl_frame_kernel.hip.h"
+#undef RFX_GLK_LOOP
+#undef RFX_GLK_LIST
 
 // x[clip][p]: overlap-add of the frames t = blk-4 .. blk+5 that cover hop block blk = p / 441, in the run kernel's arithmetic
 // (round 6, kGlGroup in rfx_kernels.h): an fma chain y w + acc in increasing t, split where a group boundary of the row falls
@@ -427,6 +433,39 @@ __global__ void __launch_bounds__(256) gl_fold_kernel(const float* __restrict__ 
   const float a = lo * s, b = hi * s;  // (HIP's __fmul_rn is a plain product the compiler may contract: the pragma above is what keeps these apart)
   const float x = a + b;
   out[(size_t)clip * out_stride + p] = ADD ? x + addend[(size_t)clip * addend_stride + p] : x;
+}
+
+// ---- loop call (rfx_loop_core.h): the circular fold.  x[clip][m], m < P = 441 T: the ten frames t = blk - 4 .. blk + 5 (mod T) that cover hop
+// block blk = m / 441, as ONE fma chain y w + acc from the oldest covering frame on - the same chain wherever in the period the sample
+// lies, no group split - times the reciprocal circular envelope (2 / N) / env[m mod 441] of launch_loop_renv's table.
+__global__ void __launch_bounds__(256) gl_loop_fold_kernel(const float* __restrict__ frames, const float* __restrict__ win,
+                                                           const float* __restrict__ renv, float* __restrict__ out, int T, int P, size_t out_stride) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  const int clip = blockIdx.y;
+  if (m >= P) return;
+  const float acc = loop_fold_fma(frames + (size_t)clip * T * kFramePitch, kFramePitch, win, m + kNfft / 2 - (kNfft - kWin) / 2, kWin, kHop, T);
+  out[(size_t)clip * out_stride + m] = acc * renv[m % kHop];
+}
+// out[r] = scale / env[r], r < hop (rfx_loop_core.h::loop_env): once per loop call, every engine
+__global__ void __launch_bounds__(256) loop_renv_kernel(const float* __restrict__ win, float* __restrict__ out, int h, int left, int win_len, int hop,
+                                                        float scale) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < hop) out[r] = scale / loop_env(win, r, h, left, win_len, hop);
+}
+hipError_t launch_loop_renv(const float* win, float* out, int n_fft, int win_len, int hop, float scale, hipStream_t stream) {
+  hipLaunchKernelGGL(loop_renv_kernel, dim3((hop + 255) / 256), dim3(256), 0, stream, win, out, n_fft / 2, (n_fft - win_len) / 2, win_len, hop, scale);
+  return hipGetLastError();
+}
+hipError_t launch_gl_frame_loop(int mode, const GlFrameArgs& g, int nblocks, hipStream_t stream) {
+  const size_t lds = kFrameDynLdsBytes;
+  if (mode == 1) hipLaunchKernelGGL(gl_frame_loop_kernel<1>, dim3(nblocks), dim3(kThreads), lds, stream, g);
+  else hipLaunchKernelGGL(gl_frame_loop_kernel<2>, dim3(nblocks), dim3(kThreads), lds, stream, g);
+  return hipGetLastError();
+}
+hipError_t launch_gl_loop_fold(const float* frames, const float* win, const float* renv, float* out, int B, int T, size_t out_stride, hipStream_t stream) {
+  const int P = kHop * T;
+  hipLaunchKernelGGL(gl_loop_fold_kernel, dim3((P + 255) / 256, B), dim3(256), 0, stream, frames, win, renv, out, T, P, out_stride);
+  return hipGetLastError();
 }
 
 hipError_t launch_gl_frame(int mode, const GlFrameArgs& g, int nblocks, hipStream_t stream) {
@@ -487,6 +526,8 @@ hipError_t prepare_gl_kernels() {
   if ((e = hipFuncSetAttribute((const void*)gl_frame_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)gl_frame_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)gl_frame_list_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute((const void*)gl_frame_loop_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute((const void*)gl_frame_loop_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes)) != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)gl_frame_list_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes);
 }
 

@@ -3,9 +3,18 @@
 //                                                this instantiation compiles to the code it always compiled to)
 //   RFX_GLK_LIST 1  gl_frame_list_kernel<MODE>  trip i of the loop takes frame list[i], list[B T] trips in all: launches 1 .. n_iter of a
 //                                                held call (include/rfx.h: rfx_held_call_options; the list: rfx_guide_core.h)
-// One text, chosen at compile time: no branch on the form inside either kernel.
+//   RFX_GLK_LOOP 1  gl_frame_loop_kernel<MODE>  (with RFX_GLK_LIST 0) a loop call's launches 1 .. n_iter (include/rfx.h: rfx_loop_call_options): the
+//                                                analysis input is read modulo the period g.L = hop T (rfx_loop_core.h) instead of reflected
+// One text, chosen at compile time: no branch on the form inside any of the kernels.
+#if RFX_GLK_LOOP
+#define RFX_GLK_POS(p, L) loop_wrap(p, L)
+#else
+#define RFX_GLK_POS(p, L) reflect_index(p, L)
+#endif
 template <int MODE>
-#if RFX_GLK_LIST
+#if RFX_GLK_LOOP
+__global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_frame_loop_kernel(GlFrameArgs g) {
+#elif RFX_GLK_LIST
 __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_frame_list_kernel(GlFrameArgs g, const int* __restrict__ list) {
 #else
 __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_frame_kernel(GlFrameArgs g) {
@@ -44,7 +53,7 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_frame_kernel(GlFra
       float u[10];
 #pragma unroll
       for (int j = 0; j < 10; ++j) {
-        const unsigned p4 = (unsigned)reflect_index((fr + j - kHalfHops) * kHop + t.npr, g.L) * 4u;
+        const unsigned p4 = (unsigned)RFX_GLK_POS((fr + j - kHalfHops) * kHop + t.npr, g.L) * 4u;
         float x = ld1(in, p4, 0);
         if (MODE == 2) x = fmaf(-g.mom, ld1(pv, p4, 0), x);
         u[j] = (x * ks) * wv[j];  // (the run kernel scales when the sample enters its sliding window: same two products)
@@ -90,3 +99,4 @@ __global__ void __launch_bounds__(kThreads, RFX_MIN_WAVES) gl_frame_kernel(GlFra
     __syncthreads();  // the next frame's first LDS stores overwrite rows other waves are still gathering in P1'
   }
 }
+#undef RFX_GLK_POS

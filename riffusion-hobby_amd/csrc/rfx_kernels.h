@@ -111,6 +111,11 @@ hipError_t launch_gl_frame_list(int mode, const GlFrameArgs& g, const int* list,
 hipError_t launch_gl_fold(const float* frames, const float* win, const float* scale, float* out, int B, int T, int L, size_t out_stride, hipStream_t stream,
                           const float* addend = nullptr, size_t addend_stride = 0);
 size_t gl_frame_buffer_bytes(int B, int T);
+// a loop call (rfx_loop_core.h; include/rfx.h: rfx_loop_call_options): the frame kernels of modes 1 / 2 with the analysis input read
+// modulo the period g.L = hop T, the circular folds, and the hop-entry table out[r] = scale / env[r] they multiply by
+hipError_t launch_gl_frame_loop(int mode, const GlFrameArgs& g, int nblocks, hipStream_t stream);
+hipError_t launch_gl_loop_fold(const float* frames, const float* win, const float* renv, float* out, int B, int T, size_t out_stride, hipStream_t stream);
+hipError_t launch_loop_renv(const float* win, float* out, int n_fft, int win_len, int hop, float scale, hipStream_t stream);
 
 // layout conversion between the reference's (B, n_stft, T) tensors and slot-major frames
 hipError_t launch_pack_mag(const float* lin_bft, float* S_slots, int B, int T, hipStream_t stream);
@@ -343,6 +348,10 @@ hipError_t launch_gen_fold(const float* frames, const float* env, float* out, co
                            hipStream_t stream, const float* prev = nullptr, float* dout = nullptr, float mom = 0.f,
                            const float* row_scale = nullptr,  // L output samples per clip; dout = (x - mom prev) * row_scale[2 b]
                            const float* addend = nullptr, size_t addend_stride = 0);  // masked call: x += addend[b][p] before out and dout
+// loop call: mode 1 with the input read modulo a.L = hop T, and the circular fold (x, and d as launch_gen_fold forms it)
+hipError_t launch_gen_gl_loop(const GenGlArgs& a, int num_cus, hipStream_t stream);
+hipError_t launch_gen_loop_fold(const float* frames, const float* renv, float* out, const GenGeom& g, int B, int T, size_t out_stride, hipStream_t stream,
+                                const float* prev, float* dout, float mom, const float* row_scale);
 hipError_t launch_gen_pack(const void* bft, void* frames, bool complex_, int B, int F, int T, int fs, hipStream_t stream);
 hipError_t launch_gen_unpack(const void* frames, void* bft, bool complex_, int B, int F, int T, int fs, hipStream_t stream);
 hipError_t launch_gen_mel(const float* mag, float* mel_tm, const float* band_wt, const int* band_lo, const int* band_len, long long nframes,
@@ -408,6 +417,7 @@ int fam_blocks_per_cu(const FamGeom& g);
 bool fam_row_stride_even(const FamGeom& g);     // the kernels use 16-byte LDS accesses in pass B: rows must start 16-byte aligned
 hipError_t launch_fam_gl(int mode, const FamGlArgs& a, int nblocks, hipStream_t stream);  // mode 0 init, 1 first iteration, 2 iteration
 hipError_t launch_fam_gl_list(const FamGlArgs& a, const int* list, int nblocks, hipStream_t stream);  // modes 1 / 2 over a free-frame list (launch_gl_frame_list)
+hipError_t launch_fam_gl_loop(const FamGlArgs& a, int nblocks, hipStream_t stream);  // mode 1 of a loop call (launch_gl_frame_loop)
 hipError_t launch_fam_repack(const float* plain, float* slots, const int* bin_of, long long nframes, int fs_plain, int fsf, int n_stft,
                              hipStream_t stream);
 

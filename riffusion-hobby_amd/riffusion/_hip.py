@@ -174,6 +174,38 @@ def masked_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.
                                 o.guide_samples, 0, None, 0, hold_bins.data_ptr(), int(hold_bins.shape[2]), 0)
 
 
+class RfxLoopCallOptions(ctypes.Structure):
+    """rfx_loop_call_options of include/rfx.h: rfx_masked_call_options grown at its tail by the loop switch."""
+
+    _fields_ = RfxMaskedCallOptions._fields_ + [("loop", ctypes.c_uint32), ("reserved5", ctypes.c_uint32)]
+
+
+def loop_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
+                      row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, loop: bool = False):
+    """`masked_call_options`, with the loop switch of a loop call (the row's columns are one period: a clip's end runs into its
+    start); loop=False gives the masked (or held, guided, plain) options.  A loop holds nothing: `hold` and `hold_bins` must be None."""
+    if not loop:
+        return masked_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq)
+    if hold is not None or hold_bins is not None:
+        raise ValueError("loop together with hold or hold_bins is not served")
+    o = guided_call_options(guide, rows, row_base, magnitude_hint, lstsq)
+    g = o if guide is not None else None
+    return RfxLoopCallOptions(ctypes.sizeof(RfxLoopCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, g.d_guide if g else None,
+                              g.guide_stride if g else 0, g.guide_samples if g else 0, 0, None, 0, None, 0, 0, 1, 0)
+
+
+def loop_min_frames(hop_length: int, n_fft: int) -> int:
+    """the smallest T a loop call takes: hop_length * T >= n_fft, so that a frame covers the period at most once"""
+    return -(-int(n_fft) // int(hop_length))
+
+
+def check_loop_frames(hop_length: int, n_fft: int, Tn: int) -> None:
+    """ValueError for a loop call of Tn frames below `loop_min_frames` (the library's RFX_ERR_INVALID, raised before any device work)"""
+    need = loop_min_frames(hop_length, n_fft)
+    if Tn < need:
+        raise ValueError(f"a loop decode needs hop_length * T >= n_fft ({hop_length} * T >= {n_fft}): at least {need} frames, got {Tn}")
+
+
 def check_inverse_mel(inverse_mel: str) -> bool:
     """True for "lstsq", False for "sgd"; anything else raises."""
     if inverse_mel not in INVERSE_MEL_FORMS:
@@ -258,6 +290,9 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_griffinlim_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_griffinlim_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_griffinlim_loop_output_samples": (c_int, [c_void_p, c_int]),
+    "rfx_debug_loop_frames": (c_int, [c_void_p, c_int]),
     "rfx_hold_mask_words": (c_int, [c_void_p]),
     "rfx_hold_bins_from_bands": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "rfx_debug_bin_bands": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p]),
@@ -292,11 +327,13 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_audio_from_image_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "rfx_audio_from_image_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "rfx_audio_from_image_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_audio_from_image_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "rfx_audio_from_image_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_audio_from_image_u8_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rfx_waveform_from_mel_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_waveform_from_mel_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_waveform_from_mel_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_waveform_from_mel_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_waveform_from_mel_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rfx_waveform_from_mel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_image_from_waveform_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
@@ -734,6 +771,19 @@ class Plan:
         )
         return mag, spec, Tn
 
+    def output_samples(self, Tn: int, loop: bool = False) -> int:
+        """samples per row of a Griffin-Lim call of Tn frames: hop * (Tn - 1) (+ 1 for an odd n_fft), or the period hop * Tn of a loop call"""
+        return (self.lib.rfx_griffinlim_loop_output_samples if loop else self.lib.rfx_griffinlim_output_samples)(self.handle, Tn)
+
+    def _chk_loop(self, loop: bool, hold, hold_bins, Tn: int) -> None:
+        if not loop:
+            return
+        if hold is not None or hold_bins is not None:
+            raise ValueError("loop together with hold or hold_bins is not served")
+        if self.griffinlim_engine == "chirp-z":
+            raise ValueError("a loop decode is not served on the chirp-z engine (RFX_ERR_UNSUPPORTED)")
+        check_loop_frames(self.hop_length, self.n_fft, Tn)
+
     def griffinlim(
         self,
         mag_slots: torch.Tensor,
@@ -750,6 +800,7 @@ class Plan:
         guide: T.Optional[torch.Tensor] = None,
         hold: T.Optional[torch.Tensor] = None,
         hold_bins: T.Optional[torch.Tensor] = None,
+        loop: bool = False,
     ) -> torch.Tensor:
         """GriffinLim on magnitudes in slot layout -> (B, samples).  `row_base`: index of the call's first row in the caller's
         whole batch (the random phases of row r are drawn from (seed, row_base + r): chunked and sharded batches get the starts
@@ -759,8 +810,11 @@ class Plan:
         `seed` and `row_base` then change nothing.  `hold`: (B, 2) int32 {head, tail} on the plan's device, with a guide: the
         first `head` and last `tail` frames of a row keep the guide's phase through the iterations (rfx_held_call_options).
         `hold_bins`: (B, Tn, hold_mask_words) int32 bit masks on the plan's device, with a guide and without `hold`: the set bins of
-        every frame keep the guide's phase (rfx_masked_call_options; `hold_bins_from_bands` makes them from a mel-band mask)."""
+        every frame keep the guide's phase (rfx_masked_call_options; `hold_bins_from_bands` makes them from a mel-band mask).
+        `loop`: the Tn columns are one period of a loop (rfx_loop_call_options): circular transforms, (B, hop_length * Tn) samples whose
+        end runs into their start; without `hold` / `hold_bins`, Tn at least `loop_min_frames`."""
         mag_slots = self._chk(mag_slots, torch.float32)
+        self._chk_loop(loop, hold, hold_bins, Tn)
         if angles0_slots is not None:
             angles0_slots = self._chk(angles0_slots, torch.complex64)
         if guide is not None:
@@ -773,15 +827,15 @@ class Plan:
             hold_bins = self._chk_hold_bins(hold_bins, guide, hold, B, Tn)
         if mag_slots.numel() < B * Tn * self.frame_stride:
             raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
-        need = (self.lib.rfx_griffinlim_masked_workspace_bytes if hold_bins is not None else
+        need = (self.lib.rfx_griffinlim_loop_workspace_bytes if loop else self.lib.rfx_griffinlim_masked_workspace_bytes if hold_bins is not None else
                 self.lib.rfx_griffinlim_held_workspace_bytes if hold is not None else self.lib.rfx_griffinlim_workspace_bytes)(self.handle, B, Tn)
         if workspace is not None:
             workspace = self._chk(workspace)
         if workspace is None or workspace.numel() < need:  # no (or too small a) caller-owned workspace: the plan's arena
             with self._workspace(need) as ws:
-                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide, hold, hold_bins)
-        out = torch.empty((B, self.lib.rfx_griffinlim_output_samples(self.handle, Tn)), dtype=torch.float32, device=mag_slots.device)
-        opt = masked_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint)
+                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide, hold, hold_bins, loop)
+        out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mag_slots.device)
+        opt = loop_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, loop=loop)
         check(
             self.lib.rfx_griffinlim_ex(
                 self.handle,
@@ -1043,26 +1097,27 @@ class Plan:
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
                           row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False,
                           guide: T.Optional[torch.Tensor] = None, hold: T.Optional[torch.Tensor] = None,
-                          hold_bins: T.Optional[torch.Tensor] = None) -> torch.Tensor:
+                          hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False) -> torch.Tensor:
         """spectrogram_converter.py:187-204 in one call: (B, n_mels, T) -> (B, hop * (T - 1)); `inverse_mel` (seed) + `griffinlim`
         (seed + 1), same bits, the linear magnitudes stay in the workspace.  `lstsq`: `inverse_mel_lstsq` in place of the SGD.
         `guide`: (B, Lg) float32 waveforms, `hold`: (B, 2) int32 held frames, `hold_bins`: (B, T, hold_mask_words) int32 held bins, as in
-        `griffinlim`."""
+        `griffinlim`; `loop`: a loop decode, (B, hop * T) samples, as in `griffinlim`."""
         if lstsq:
             self.require_lstsq()
         mel = self._chk(mel, torch.float32)
         B, M, Tn = mel.shape
         if M != self.n_mels:
             raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")  # torchaudio's message
-        out = torch.empty((B, self.lib.rfx_griffinlim_output_samples(self.handle, Tn)), dtype=torch.float32, device=mel.device)
+        self._chk_loop(loop, hold, hold_bins, Tn)
+        out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mel.device)
         if guide is not None:
             guide = self._chk_guide(guide)
         if hold is not None:
             hold = self._chk_hold(hold, guide, B)
         if hold_bins is not None:
             hold_bins = self._chk_hold_bins(hold_bins, guide, hold, B, Tn)
-        opt = masked_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, lstsq)
-        query = (self.lib.rfx_waveform_from_mel_masked_workspace_bytes if hold_bins is not None else
+        opt = loop_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, lstsq, loop)
+        query = (self.lib.rfx_waveform_from_mel_loop_workspace_bytes if loop else self.lib.rfx_waveform_from_mel_masked_workspace_bytes if hold_bins is not None else
                  self.lib.rfx_waveform_from_mel_held_workspace_bytes if hold is not None else self.lib.rfx_waveform_from_mel_workspace_bytes)
         with self._workspace(query(self.handle, B, Tn)) as ws:
             check(self.lib.rfx_waveform_from_mel_ex(self.handle, mel.data_ptr(), B, Tn, channels_per_clip, seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
@@ -1077,13 +1132,14 @@ class Plan:
     def audio_from_image(self, img: torch.Tensor, stereo: bool, lut: torch.Tensor, n_iter: int, momentum: float = 0.99, seed: int = 0,
                          normalize: bool = True, out: T.Optional[torch.Tensor] = None, workspace: T.Optional[torch.Tensor] = None,
                          clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None,
-                         hold: T.Optional[torch.Tensor] = None, hold_bins: T.Optional[torch.Tensor] = None):
+                         hold: T.Optional[torch.Tensor] = None, hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False):
         """spectrogram_image_converter.py:54-91 on the device in one call: (N, n_mels, T, 3) uint8 -> ((N, L, C) int16, per-clip peak (N,));
         `image_decode` + `waveform_from_mel` (clips of C rows) + `pcm16`, same bytes.  `out` as in `pcm16`.  `clip_base`: index of
         the call's first image in the caller's whole batch (row_base = clip_base * C); `magnitude_hint`: the image path's
         max_value (the largest entry of `lut`); `lstsq`: the closed-form InverseMelScale in place of the SGD; `guide`: (N * C, Lg)
         float32 waveforms, image after image and channel after channel, as in `griffinlim`; `hold`: (N * C, 2) int32 held frames, row
-        for row with the guide; `hold_bins`: (N * C, T, hold_mask_words) int32 held bins, row for row as well."""
+        for row with the guide; `hold_bins`: (N * C, T, hold_mask_words) int32 held bins, row for row as well; `loop`: a loop decode,
+        L = hop * T PCM frames per clip, as in `griffinlim`."""
         if img.dtype != torch.uint8 or img.dim() != 4:
             raise ValueError("expected (N, H, W, 3) uint8 images")
         if lstsq:
@@ -1094,21 +1150,22 @@ class Plan:
         if ch != 3 or H != self.n_mels:
             raise ValueError(f"expected (N, {self.n_mels}, T, 3) uint8 images, got {tuple(img.shape)}")
         C = 2 if stereo else 1
-        L = self.lib.rfx_griffinlim_output_samples(self.handle, W)
+        self._chk_loop(loop, hold, hold_bins, W)
+        L = self.output_samples(W, loop)
         if out is not None:
             if out.device != self.device or out.dtype != torch.int16 or tuple(out.shape) != (N, L, C) or not out.is_contiguous():
                 raise ValueError(f"out must be a contiguous int16 tensor of shape {(N, L, C)} on {self.device}")
             pcm = out
         else:
             pcm = torch.empty((N, L, C), dtype=torch.int16, device=img.device)
-        need = (self.lib.rfx_audio_from_image_masked_workspace_bytes if hold_bins is not None else
+        need = (self.lib.rfx_audio_from_image_loop_workspace_bytes if loop else self.lib.rfx_audio_from_image_masked_workspace_bytes if hold_bins is not None else
                 self.lib.rfx_audio_from_image_held_workspace_bytes if hold is not None else self.lib.rfx_audio_from_image_workspace_bytes)(
             self.handle, N, int(stereo), W)
         ws = self._chk(workspace) if workspace is not None else None
         if ws is None or ws.numel() < need:
             with self._workspace(need) as borrowed:
                 return self.audio_from_image(img, stereo, lut, n_iter, momentum, seed, normalize, out=pcm, workspace=borrowed,
-                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins)
+                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop)
         peak = torch.zeros((N,), dtype=torch.float32, device=img.device)
         if guide is not None:
             guide = self._chk_guide(guide)
@@ -1116,7 +1173,7 @@ class Plan:
             hold = self._chk_hold(hold, guide, N * C)
         if hold_bins is not None:
             hold_bins = self._chk_hold_bins(hold_bins, guide, hold, N * C, W)
-        opt = masked_call_options(guide, hold, hold_bins, N * C, clip_base * C, magnitude_hint, lstsq)
+        opt = loop_call_options(guide, hold, hold_bins, N * C, clip_base * C, magnitude_hint, lstsq, loop)
         check(self.lib.rfx_audio_from_image_u8_ex(self.handle, img.data_ptr(), N, W, int(stereo), lut.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                   int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return pcm, peak

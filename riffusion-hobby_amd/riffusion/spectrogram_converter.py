@@ -160,11 +160,12 @@ class SpectrogramConverter:
         amplitudes_mel = self.mel_amplitudes_from_waveform(waveform_tensor)
         return amplitudes_mel.cpu().numpy()
 
-    def audio_from_spectrogram(self, spectrogram: np.ndarray, apply_filters: bool = True) -> T.Any:
-        """(channels, n_mels, T) mel amplitudes -> audio segment with that many channels."""
+    def audio_from_spectrogram(self, spectrogram: np.ndarray, apply_filters: bool = True, *, loop: bool = False) -> T.Any:
+        """(channels, n_mels, T) mel amplitudes -> audio segment with that many channels.  `loop`: a loop decode
+        (`waveform_from_mel_amplitudes`): hop*T samples whose end runs into their start."""
         amplitudes_mel = torch.from_numpy(np.ascontiguousarray(spectrogram)).to(self.device)
         plan = self._plan()
-        waveform = self._waveform_from_mel(plan, amplitudes_mel)
+        waveform = self._waveform_from_mel(plan, amplitudes_mel, loop=loop)
         # peak-normalise + int16 truncation on the device (audio_util.py:22-28), one D2H of int16
         pcm, _ = plan.pcm16(waveform, channels=waveform.shape[0], normalize=True)
         host_filters = apply_filters and pcm.shape[1] * pcm.shape[2] >= audio_util.FILTER_EXACT_SAMPLES
@@ -192,6 +193,7 @@ class SpectrogramConverter:
         guide: T.Optional[torch.Tensor] = None,
         hold_frames: T.Any = None,
         hold_mask: T.Any = None,
+        loop: bool = False,
     ) -> torch.Tensor:
         """
         (B, n_mels, T) -> (B, hop*(T-1)).  The reference treats the whole batch as ONE clip (the SGD
@@ -213,7 +215,12 @@ class SpectrogramConverter:
         `hold_mask`: with a guide and without `hold_frames`, a (B, n_mels, T) boolean (or nonzero = held) array or tensor in the
         layout of the mel tensor: the linear bins every one of whose mel bands is held at a frame keep the guide's phase there
         through every iteration (rfx_masked_call_options) - the kept region of a partial regeneration under a mask image.
+        `loop`: the T columns are one period of a loop (rfx_loop_call_options): Griffin-Lim runs on the circular STFT, the result
+        has hop*T samples and its end runs into its start - no click when the clip is played on repeat.  T must reach n_fft / hop
+        (40 at the defaults); not together with `hold_frames` or `hold_mask`.
         """
+        if loop and (hold_frames is not None or hold_mask is not None):
+            raise ValueError("loop together with hold_frames or hold_mask is not served")
         if guide is not None and angles0 is not None:
             raise ValueError("guide and angles0 are two starts of Griffin-Lim: give one")
         hold = None
@@ -229,7 +236,8 @@ class SpectrogramConverter:
                 raise ValueError("hold_frames together with hold_mask is not served: set the held frames' columns in the mask")
             bands = hold_mask_rows(hold_mask, int(amplitudes_mel.shape[0]), int(amplitudes_mel.shape[1]), int(amplitudes_mel.shape[-1]))
         return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
-                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, hold=hold, hold_bands=bands)
+                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, hold=hold, hold_bands=bands,
+                                       loop=loop)
 
     def hold_frames_for(self, head_s: float = 0.0, tail_s: float = 0.0) -> T.Tuple[int, int]:
         """`SpectrogramParams.hold_frames_for` of this converter's params: the `hold_frames` pair for `head_s` / `tail_s` seconds
@@ -241,15 +249,20 @@ class SpectrogramConverter:
                            channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0,
                            return_slots: bool = False, inverse_mel: str = "sgd", guide: T.Optional[torch.Tensor] = None,
                            n_iter: T.Optional[int] = None, hold: T.Optional[torch.Tensor] = None,
-                           hold_bands: T.Optional[torch.Tensor] = None) -> T.Any:
+                           hold_bands: T.Optional[torch.Tensor] = None, loop: bool = False) -> T.Any:
         """`waveform_from_mel_amplitudes` on a plan the caller already holds (the batch entry points fetch it once per call,
         not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild).
         `return_slots=True` runs the two inverse stages separately - same bits as the one call - and returns
         (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares.  `guide`: (B, Lg) float32 guide
         waveforms (`waveform_from_mel_amplitudes`); `n_iter`: Griffin-Lim iterations in place of the params'; `hold`: (B, 2)
         int32 held frames of a guided call (`hold_rows`); `hold_bands`: (B, n_mels, T) uint8 held mel bands of a masked call
-        (`hold_mask_rows`), expanded to bins on the device."""
+        (`hold_mask_rows`), expanded to bins on the device; `loop`: a loop decode (`waveform_from_mel_amplitudes`)."""
         from riffusion import _hip
+
+        if loop:
+            if hold is not None or hold_bands is not None:
+                raise ValueError("loop together with hold_frames or hold_mask is not served")
+            _hip.check_loop_frames(self.p.hop_length, self.p.n_fft, int(amplitudes_mel.shape[-1]))
 
         lstsq = _hip.check_inverse_mel(inverse_mel)
         if lstsq:
@@ -268,7 +281,7 @@ class SpectrogramConverter:
         hold_bins = plan.hold_bins_from_bands(hold_bands.to(self.device)) if hold_bands is not None else None
         if spec0 is None and angles0 is None and not return_slots:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
             return plan.waveform_from_mel(mel, cpc, n_iter, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint,
-                                          lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins)
+                                          lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop)
         spec0 = spec0.to(self.device) if spec0 is not None else None
         if lstsq:
             lin_slots = plan.inverse_mel_lstsq(mel)
@@ -276,7 +289,7 @@ class SpectrogramConverter:
             lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         a0 = plan.pack_complex(angles0.to(self.device)) if angles0 is not None else None
         wave = plan.griffinlim(lin_slots, B, Tn, n_iter, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
-                               magnitude_hint=magnitude_hint, guide=guide, hold=hold, hold_bins=hold_bins)
+                               magnitude_hint=magnitude_hint, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop)
         return (wave, lin_slots) if return_slots else wave
 
     # ---- quality of a decode ------------------------------------------------------------------------

@@ -64,6 +64,7 @@ class SpectrogramImageConverter:
         griffin_lim_iters: T.Optional[int] = None,
         hold_frames: T.Optional[T.Tuple[int, int]] = None,
         hold_mask: T.Any = None,
+        loop: bool = False,
     ) -> T.Any:
         """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference).  The filters
         (audio_util.apply_filters, compression=False) run on the device: same bytes.  `inverse_mel`: "sgd" (default) or
@@ -73,7 +74,8 @@ class SpectrogramImageConverter:
         this call in place of the params' (a guided decode needs few).  `hold_frames`: with a guide, the `(head, tail)` frames at
         the clip's two ends that keep the guide's phase through the iterations (`hold_frames_for` turns seconds of known audio
         into the pair).  `hold_mask`: with a guide, a mask image of the tile's size (black is kept, as the reference's `mask_image`)
-        or an (n_mels, W) boolean array: the kept region keeps the guide's phase through the iterations.  All as in
+        or an (n_mels, W) boolean array: the kept region keeps the guide's phase through the iterations.  `loop`: the tile is
+        one period of a loop: hop * W samples whose end runs into their start (not with `hold_frames` / `hold_mask`).  All as in
         `audio_from_spectrogram_images`."""
         if hold_frames is not None and guide_segment is None:
             raise ValueError("hold_frames needs a guide: the frames are held at the guide's phase")
@@ -90,7 +92,7 @@ class SpectrogramImageConverter:
         pcm = self.audio_from_spectrogram_images(
             np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters,
             inverse_mel=inverse_mel, guide_waveforms=guides, griffin_lim_iters=griffin_lim_iters, hold_frames=hold_frames,
-            hold_mask=hold_mask,
+            hold_mask=hold_mask, loop=loop,
         )
         return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
 
@@ -130,6 +132,7 @@ class SpectrogramImageConverter:
         guide_waveforms: T.Any = None,
         griffin_lim_iters: T.Optional[int] = None,
         hold_mask: T.Any = None,
+        loop: bool = False,
     ) -> T.Any:
         """
         A sequence of tiles -> ONE audio segment: every tile decoded (`audio_from_spectrogram_images`), filtered
@@ -154,6 +157,8 @@ class SpectrogramImageConverter:
         region of a partial regeneration, as in `audio_from_spectrogram_images`; not for tiles of different sizes without `size`.
         """
         _hip.check_inverse_mel(inverse_mel)
+        if loop:  # (`loop` is here to be refused: a sequence is stitched with crossfades, its clips do not repeat)
+            raise ValueError("loop does not go with a stitched sequence: decode loops with audio_from_spectrogram_images(loop=True)")
         if hold_mask is not None and guide_waveforms is None:
             raise ValueError("hold_mask needs guide_waveforms: the bins are held at the guides' phase")
         if isinstance(images, (list, tuple)):
@@ -493,6 +498,7 @@ class SpectrogramImageConverter:
         griffin_lim_iters: T.Optional[int] = None,
         hold_frames: T.Any = None,
         hold_mask: T.Any = None,
+        loop: bool = False,
     ) -> T.Any:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -575,10 +581,19 @@ class SpectrogramImageConverter:
         of a stereo clip; the magnitudes stay the tiles'.  With `size=`, W is `size[0]`.  A mask removes no iteration work.
         Without guides, with `hold_frames`, or in another shape: ValueError before any GPU work.  Chunks and shards slice it like
         the guides.
+        `loop=True`: every tile is one period of a loop (rfx_loop_call_options) - what the reference's web app plays on repeat.
+        Griffin-Lim runs on the circular STFT (frames modulo hop * W samples, circular overlap-add), a clip has hop * W samples
+        and its last sample runs into its first: no click at the loop point.  W (or `size[0]`) must reach n_fft / hop (40 columns
+        at the defaults).  Guides, `inverse_mel`, `apply_filters`, `tiles_per_call`, `group` and `size` work as without it; not
+        with `hold_frames`, `hold_mask` or `return_error` (the error entry analyses with the reflect-padded STFT): ValueError.
         """
         from riffusion import batch_shard
 
         lstsq = _hip.check_inverse_mel(inverse_mel)
+        if loop and (hold_frames is not None or hold_mask is not None):
+            raise ValueError("loop together with hold_frames or hold_mask is not served")
+        if loop and return_error:
+            raise ValueError("loop does not go with return_error=True: the spectral error is measured with the reflect-padded STFT")
 
         if tiles_per_call < 1:
             raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
@@ -666,7 +681,10 @@ class SpectrogramImageConverter:
 
         if size is not None:
             size = (int(size[0]), int(size[1]))
-        L = plan.lib.rfx_griffinlim_output_samples(plan.handle, size[0] if size is not None else int(imgs.shape[2]))
+        width = size[0] if size is not None else int(imgs.shape[2])
+        if loop:
+            _hip.check_loop_frames(plan.hop_length, plan.n_fft, width)
+        L = plan.output_samples(width, loop)
         base_seed = conv._seed(seed)
         power, max_value = float(self.p.power_for_image), float(max_value)
         if not (max_value > 0.0 and max_value < float("inf")):
@@ -707,13 +725,13 @@ class SpectrogramImageConverter:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value,
                                                    inverse_mel=inverse_mel, guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b),
-                                                   hold_bands=held_bands(a, b))
+                                                   hold_bands=held_bands(a, b), loop=loop)
                     out = wave.reshape(b - a, C, -1)
                 else:  # uint8 tiles -> int16 PCM in one call (rfx_audio_from_image_u8_ex), same bytes as the three calls above + pcm16
                     dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
                     out = plan.audio_from_image(tiles, self.p.stereo, lut, n_iter, 0.99, seed=base_seed,
                                                 normalize=True, out=dst, clip_base=a, magnitude_hint=max_value, lstsq=lstsq,
-                                                guide=guide_rows(a, b), hold=held_rows(a, b), hold_bins=held_bins(a, b))[0]
+                                                guide=guide_rows(a, b), hold=held_rows(a, b), hold_bins=held_bins(a, b), loop=loop)[0]
                     if apply_filters:
                         out = self._filter_pcm(plan, out, compression)
                 # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them
