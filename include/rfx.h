@@ -413,6 +413,69 @@ typedef struct {
   uint32_t reserved5;       /* must be 0 */
 } rfx_loop_call_options;
 
+/* rfx_loop_call_options grown once more, by the same mechanism (struct_size = sizeof(rfx_start_call_options); the first sixteen
+ * fields are rfx_loop_call_options' own): THE START.  Text-to-audio has no guide: only magnitudes exist, and the reference starts
+ * Griffin-Lim from U[0,1) phases.  start == 1 starts it from phases built from the magnitudes alone instead (single-pass spectrogram
+ * inversion with phase-vocoder peak tracking): no randomness, no guide, fewer iterations for the same spectral convergence at low
+ * iteration counts on tonal material (README).  A call with start == 1 is rfx_peak_start (below) on the call's magnitudes followed
+ * by the same call with those angles injected as d_angles0_slots - same bits; for the fused entries the magnitudes are the ones
+ * their InverseMelScale stage leaves in the workspace.  A row's bytes then depend on its magnitudes alone - not on seed (the
+ * InverseMelScale stage of a fused call still draws its own start from it), row_base, the other rows or its place in the batch.
+ * loop == 1 together with start == 1 is served: the first launch of a loop call is the unlooped call's, and both transforms centre
+ * frame t at hop t.  h_launch_ms keeps n_iter + 1 entries, [0] including the start.
+ * Workspace: the *_peak_workspace_bytes twin of the entry's query = that query plus the angles, B T frame_stride 8 bytes rounded up to
+ * 256, plus rfx_peak_start_workspace_bytes(plan, B, T); a loop call with start == 1 brings its loop query plus the same two terms.
+ * RFX_ERR_INVALID before any launch, the output untouched: start > 1; reserved6 != 0; start == 1 together with d_guide, with
+ * d_angles0_slots, with d_hold_frames or with d_hold_bins (each is a start, or needs the guide's).  RFX_ERR_UNSUPPORTED: a plan whose
+ * frame does not fit the LDS (rfx_peak_start).  RFX_ERR_WORKSPACE: a workspace below the twin.  Honoured by rfx_griffinlim_ex,
+ * rfx_waveform_from_mel_ex and rfx_audio_from_image_u8_ex; rfx_inverse_mel_ex refuses it.  A caller passing any of the five shorter
+ * struct sizes keeps exactly its behaviour and bytes.  (A new struct, not a flag bit: flags == 2 stays refused.) */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t flags;
+  uint64_t row_base;
+  float magnitude_hint;
+  float reserved;           /* must be 0 */
+  const float* d_guide;
+  int64_t guide_stride;
+  int32_t guide_samples;
+  int32_t reserved2;        /* must be 0 */
+  const int32_t* d_hold_frames;
+  uint64_t reserved3;       /* must be 0 */
+  const uint32_t* d_hold_bins;
+  int32_t hold_words;
+  int32_t reserved4;        /* must be 0 */
+  uint32_t loop;
+  uint32_t reserved5;       /* must be 0 */
+  uint32_t start;           /* 0: the call is rfx_loop_call_options' call; 1: the spectral-peak start */
+  uint32_t reserved6;       /* must be 0 */
+} rfx_start_call_options;
+
+/* ---- the spectral-peak start: initial angles for Griffin-Lim from the magnitudes alone ---------------------------------------------
+ * d_mag_slots: magnitudes in slot layout, B T frames (what rfx_pack_magnitudes and rfx_inverse_mel write); d_angles0_slots_out: B T
+ * frames of complex64 in the layout d_angles0_slots takes - what rfx_pack_complex produces: conjugate slots conjugated, both copies
+ * of the bins the specialised layout stores twice written, padding 0.  Row r is one clip-channel, m[k] the float32 magnitude of bin
+ * k = 0 .. F - 1 of frame t, F = n_stft, N = n_fft.
+ * Decisions, in float32 on the float32 inputs (exact: the same on every machine):
+ *   thr = 1e-5f * max_k m[k] (NaN entries skipped); k is a peak iff 1 <= k <= F - 2, m[k] > m[k-1], m[k] >= m[k+1] and m[k] > thr
+ *   (any comparison with a NaN is false); with the peaks p_0 < p_1 < ..., bin j belongs to p_i for the smallest i with
+ *   j <= (p_i + p_{i+1}) / 2 (integer division), to the last peak if there is none.
+ * Arithmetic, in double from the float32 inputs: with a, b, c = m[p-1], m[p], m[p+1], pos = p + clamp(0.5 (a - c) / (a - 2 b + c),
+ *   -0.5, 0.5).  Phase is counted in turns.  A frame with no peak has phase 0 everywhere and cuts the chain; the first frame of a
+ *   chain (t = 0, or after a frame with no peak) has phi[p] = 0 at every peak; otherwise, q being the peak of frame t - 1 that owns
+ *   bin p, phi_t[p] = frac(phi_{t-1}[q] + 0.5 (pos_{t-1}[q] + pos_t[p]) hop / N) (the factor hop / N is formed once, in double).
+ *   angles0[r, k, t] = (-1)^k (cos, sin)(2 pi phi_t[owner(k)]), cosine and sine formed in float32 from the fraction.  (Frames are
+ *   referenced to their first sample, n_fft / 2 before the centre: a centred sinusoid alternates in sign from bin to bin.)
+ * A row depends on its magnitudes alone.  Both copies of a bin the layout stores twice must be equal, as the library writes them.
+ * Three launches (owners per frame; the chain, one workgroup per row, sequential over its frames; angles per frame), nothing
+ * synchronises.  All three frame engines.  RFX_ERR_UNSUPPORTED, with the reason, for a plan whose frame does not fit the LDS:
+ * n_stft above 10240 (the chain keeps two doubles per bin in 160 KiB).  B == 0 is a no-op.  Row and element offsets are 64-bit.
+ * Workspace: B T n_stft (2 + 8) bytes, each part rounded up to 256 (the owner of every bin, position / phase of every peak); 0 for
+ * a NULL plan. */
+size_t rfx_peak_start_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_peak_start(const rfx_plan* plan, const float* d_mag_slots, int B, int T, void* d_angles0_slots_out, void* d_workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* words per frame of a masked call's d_hold_bins: ceil(n_stft / 32); 0 for a NULL plan */
 int rfx_hold_mask_words(const rfx_plan* plan);
 /* A per-mel-band mask, in the layout of the mel tensor, to the bin mask of rfx_masked_call_options.  d_bands: (B, n_mels, T) uint8,
@@ -480,6 +543,8 @@ size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T);
 size_t rfx_griffinlim_masked_workspace_bytes(const rfx_plan* plan, int B, int T);
 /* ... of a loop call (rfx_loop_call_options.loop == 1); 0 where the call would be refused (hop T < n_fft, the chirp-z engine) */
 size_t rfx_griffinlim_loop_workspace_bytes(const rfx_plan* plan, int B, int T);
+/* ... of a call with the spectral-peak start (rfx_start_call_options.start == 1): the unflagged query, the angles, the start's scratch */
+size_t rfx_griffinlim_peak_workspace_bytes(const rfx_plan* plan, int B, int T);
 /* samples per row a loop call writes for T frames: the period hop T; 0 for a NULL plan or T <= 0 */
 int rfx_griffinlim_loop_output_samples(const rfx_plan* plan, int T);
 /* the frame-count rule of a loop call, without a plan or a GPU (tests): RFX_OK, or the RFX_ERR_INVALID a loop call of T frames at
@@ -600,6 +665,7 @@ size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T)
 size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T);  /* with held frames (rfx_held_call_options) */
 size_t rfx_waveform_from_mel_masked_workspace_bytes(const rfx_plan* plan, int B, int T);  /* masked (rfx_masked_call_options) */
 size_t rfx_waveform_from_mel_loop_workspace_bytes(const rfx_plan* plan, int B, int T);    /* loop (rfx_loop_call_options) */
+size_t rfx_waveform_from_mel_peak_workspace_bytes(const rfx_plan* plan, int B, int T);    /* peak start (rfx_start_call_options) */
 int rfx_waveform_from_mel(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                           float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream);
 
@@ -823,6 +889,7 @@ size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int ste
 size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* with held frames (rfx_held_call_options) */
 size_t rfx_audio_from_image_masked_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* masked (rfx_masked_call_options) */
 size_t rfx_audio_from_image_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);    /* loop (rfx_loop_call_options) */
+size_t rfx_audio_from_image_peak_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);    /* peak start (rfx_start_call_options) */
 int rfx_audio_from_image_u8(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                             int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
                             size_t workspace_bytes, void* stream);

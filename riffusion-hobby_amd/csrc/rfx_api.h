@@ -136,6 +136,15 @@ inline int frame_blocks(long long slots, int B, int T) {
 }
 inline long long fam_slot_count(const rfx_plan* plan) { return (long long)plan->num_cus * plan->fam_wgs_per_cu; }
 
+// the spectral-peak start as the inverse entries use it (rfx_api_peak.hip): the refusal of a plan whose frame does not fit the LDS;
+// the bytes a call with that start brings on top of its query (the angles, then the start's scratch); the three launches, reading
+// magnitudes in `layout` (kHoldMaskSpec / kHoldMaskPlain / kHoldMaskTable) and writing angles as d_angles0_slots takes them
+int peak_refusal(const rfx_plan* plan, const char* who);
+size_t peak_scratch_bytes(const rfx_plan* plan, int B, int T);
+size_t peak_angles_bytes(const rfx_plan* plan, int B, int T);
+size_t peak_extra_bytes(const rfx_plan* plan, int B, int T);
+int peak_start_run(const rfx_plan* plan, int layout, const float* d_mag, int B, int T, void* d_angles, void* d_scratch, hipStream_t stream);
+
 // A workspace layout is a plain struct of byte offsets and `total`, returned by value from one function of (plan, shape): the
 // rfx_*_workspace_bytes query answers its total, the driver takes every pointer from its fields.  A shape the query answers 0
 // for gives the all-zero layout.  Carve deals the parts out: each starts on a 256-byte boundary.

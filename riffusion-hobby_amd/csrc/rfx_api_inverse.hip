@@ -6,6 +6,7 @@
 #include "rfx_guide_core.h"
 #include "rfx_holdmask_core.h"
 #include "rfx_loop_core.h"
+#include "rfx_peak_core.h"
 
 using namespace rfx;
 
@@ -15,6 +16,7 @@ namespace {
 class LaunchTimer {
   float* h_ms_;
   int n_;  // launches: n_ + 1 events
+  bool begun_ = false;
   std::vector<hipEvent_t> ev_;
 
  public:
@@ -25,7 +27,8 @@ class LaunchTimer {
   LaunchTimer(const LaunchTimer&) = delete;
   LaunchTimer& operator=(const LaunchTimer&) = delete;
   hipError_t begin(hipStream_t stream) {
-    if (!h_ms_) return hipSuccess;
+    if (!h_ms_ || begun_) return hipSuccess;  // (a call with the spectral-peak start begins before its start; the engine's begin then does nothing)
+    begun_ = true;
     ev_.reserve((size_t)n_ + 1);
     for (int i = 0; i <= n_; ++i) {
       hipEvent_t e;
@@ -214,6 +217,11 @@ size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) { retu
 size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlHeld); }
 size_t rfx_griffinlim_masked_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlMasked); }
 size_t rfx_griffinlim_loop_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlLoop); }
+// a call with the spectral-peak start: behind everything the call has without it, the angles and the start's scratch
+static size_t with_peak(const rfx_plan* plan, size_t base, int B, int T) { return base ? base + peak_extra_bytes(plan, B, T) : 0; }
+size_t rfx_griffinlim_peak_workspace_bytes(const rfx_plan* plan, int B, int T) {
+  return plan ? with_peak(plan, griffinlim_workspace(plan, B, T, kGlPlain), B, T) : 0;
+}
 int rfx_griffinlim_loop_output_samples(const rfx_plan* plan, int T) {
   if (!plan || T <= 0 || (long long)plan->p.hop_length * T > 0x7fffffffLL) return 0;
   return plan->p.hop_length * T;
@@ -239,6 +247,8 @@ struct CallOpt {
   int mask_words = 0;
   // rfx_loop_call_options: the row's T columns are one period of a loop (rfx_loop_core.h)
   bool loop = false;
+  // rfx_start_call_options: Griffin-Lim starts from the spectral-peak phases of the call's magnitudes (rfx_peak_core.h)
+  bool peak = false;
   GlKind kind() const { return loop ? kGlLoop : mask ? kGlMasked : hold ? kGlHeld : kGlPlain; }
 };
 // allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves); takes_guide: it runs Griffin-Lim
@@ -307,6 +317,19 @@ static int read_call_options(const rfx_call_options* o, CallOpt* out, const char
       if (out->hold || out->mask)
         return fail(RFX_ERR_INVALID, std::string(who) + ": loop together with d_hold_frames or d_hold_bins is not served");
       out->loop = true;
+    }
+  }
+  // the start tail (rfx_start_call_options: grown a fifth time)
+  if (o->struct_size >= offsetof(rfx_start_call_options, reserved6) + sizeof(uint32_t)) {
+    const rfx_start_call_options* st = reinterpret_cast<const rfx_start_call_options*>(o);
+    if (st->reserved6 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_start_call_options.reserved6 must be 0");
+    if (st->start > 1) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_start_call_options.start must be 0 or 1");
+    if (st->start) {
+      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and takes no start (start must be 0)");
+      if (out->mask) return fail(RFX_ERR_INVALID, std::string(who) + ": start == 1 together with d_hold_bins is not served (bins are held at a guide's phase)");
+      if (out->hold) return fail(RFX_ERR_INVALID, std::string(who) + ": start == 1 together with d_hold_frames is not served (frames are held at a guide's phase)");
+      if (out->guide) return fail(RFX_ERR_INVALID, std::string(who) + ": start == 1 and d_guide are two starts: give one");
+      out->peak = true;
     }
   }
   return RFX_OK;
@@ -631,11 +654,25 @@ static int griffinlim_impl(const rfx_plan* plan, const float* d_mag_slots, const
   const int L = gl_out_samples(plan, T, opt.loop);
   if (!opt.loop && n_iter > 0 && L <= plan->p.n_fft / 2) return reflect_refusal(plan);
   if (int rc = guide_refusal(plan, opt, T, d_angles0_slots != nullptr, "rfx_griffinlim")) return rc;
+  size_t gl_bytes = 0;
+  if (opt.peak) {
+    if (d_angles0_slots) return fail(RFX_ERR_INVALID, "rfx_griffinlim: start == 1 and d_angles0_slots are two starts: give one");
+    if (int rc = peak_refusal(plan, "rfx_griffinlim")) return rc;
+    gl_bytes = griffinlim_workspace(plan, B, T, opt.kind());
+    if (workspace_bytes < with_peak(plan, gl_bytes, B, T)) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
+  }
   RFX_ON_DEVICE(plan->device);
   GlCall c{d_mag_slots, (const cf*)d_angles0_slots, d_row_scale, opt.magnitude_hint, momentum / (1.f + momentum), seed,
            opt.row_base * (uint64_t)T, B, T, L, n_iter, d_wave_out, (char*)d_workspace, workspace_bytes, (hipStream_t)stream,
            opt.guide, opt.guide_stride, opt.guide_samples, opt.hold, opt.mask, opt.loop};
   LaunchTimer timer(h_launch_ms, n_iter + 1);
+  if (opt.peak) {  // rfx_peak_start into the angles behind the call's own workspace, then the call with those angles injected
+    RFX_HIP(timer.begin(c.stream));
+    char* angles = c.ws + gl_bytes;
+    const int layout = !plan->generic ? kHoldMaskSpec : plan->fam_ok && mag_in_fam_slots ? kHoldMaskTable : kHoldMaskPlain;
+    if (int rc = peak_start_run(plan, layout, c.S, B, T, angles, angles + peak_angles_bytes(plan, B, T), c.stream)) return rc;
+    c.angles0 = (const cf*)angles;
+  }
   return plan->generic ? gen_griffinlim(plan, c, mag_in_fam_slots, timer) : spec_griffinlim(plan, c, timer);
 }
 
@@ -651,6 +688,7 @@ int rfx_griffinlim_ex(const rfx_plan* plan, const float* d_mag_slots, const void
                       void* stream, const rfx_call_options* options, float* h_launch_ms) {
   CallOpt opt;
   if (int rc = read_call_options(options, &opt, "rfx_griffinlim_ex", 0, true)) return rc;
+  if (opt.peak && d_angles0_slots) return fail(RFX_ERR_INVALID, "rfx_griffinlim_ex: start == 1 and d_angles0_slots are two starts: give one");
   return griffinlim_impl(plan, d_mag_slots, d_angles0_slots, seed, B, T, n_iter, momentum, d_wave_out, d_workspace,
                          workspace_bytes, stream, h_launch_ms, opt);
 }
@@ -842,6 +880,9 @@ size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T)
 size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlHeld).total : 0; }
 size_t rfx_waveform_from_mel_masked_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlMasked).total : 0; }
 size_t rfx_waveform_from_mel_loop_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlLoop).total : 0; }
+size_t rfx_waveform_from_mel_peak_workspace_bytes(const rfx_plan* plan, int B, int T) {
+  return plan ? with_peak(plan, waveform_from_mel_layout(plan, B, T).total, B, T) : 0;
+}
 
 static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                                  float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream, const CallOpt& opt) {
@@ -853,7 +894,9 @@ static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int 
   if (int rc = guide_refusal(plan, opt, T, false, "rfx_waveform_from_mel")) return rc;
   const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T, opt.kind());
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_waveform_from_mel: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
-  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
+  if (opt.peak)
+    if (int rc = peak_refusal(plan, "rfx_waveform_from_mel")) return rc;
+  if (workspace_bytes < (opt.peak ? with_peak(plan, w.total, B, T) : w.total)) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
   char* ws = (char*)d_workspace;
   float* lin = reinterpret_cast<float*>(ws + w.lin);
   float* row_scale = reinterpret_cast<float*>(ws + w.row_scale);
@@ -911,6 +954,9 @@ size_t rfx_audio_from_image_masked_workspace_bytes(const rfx_plan* plan, int N, 
 size_t rfx_audio_from_image_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
   return plan ? audio_from_image_layout(plan, N, stereo, T, kGlLoop).total : 0;
 }
+size_t rfx_audio_from_image_peak_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
+  return plan ? with_peak(plan, audio_from_image_layout(plan, N, stereo, T).total, N * (stereo ? 2 : 1), T) : 0;
+}
 
 static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                                 int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
@@ -924,8 +970,11 @@ static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int
   if (int rc = guide_refusal(plan, opt, T, false, "rfx_audio_from_image_u8")) return rc;
   const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T, opt.kind());
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_audio_from_image_u8: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
-  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
-  const int C = stereo ? 2 : 1, B = N * C, M = plan->p.n_mels, L = gl_out_samples(plan, T, opt.loop);
+  const int C = stereo ? 2 : 1, B = N * C;
+  if (opt.peak)
+    if (int rc = peak_refusal(plan, "rfx_audio_from_image_u8")) return rc;
+  if (workspace_bytes < (opt.peak ? with_peak(plan, w.total, B, T) : w.total)) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
+  const int M = plan->p.n_mels, L = gl_out_samples(plan, T, opt.loop);
   char* ws = (char*)d_workspace;
   float* mel = reinterpret_cast<float*>(ws + w.mel);
   float* wave = reinterpret_cast<float*>(ws + w.wave);

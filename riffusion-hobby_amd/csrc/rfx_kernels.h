@@ -529,6 +529,13 @@ hipError_t launch_holdmask_split(int layout, const float* S, float* X, const uin
 // bands (B, M, T) uint8, nonzero = held -> the bin mask; lo / hi [n_stft]: first and last band of each bin (-1: none)
 hipError_t launch_holdmask_bands(const uint8_t* bands, const int16_t* lo, const int16_t* hi, uint32_t* out, int B, int M, int T, int n_stft,
                                  hipStream_t stream);
+// the spectral-peak start (rfx_peak.hip, arithmetic in rfx_peak_core.h): S [B*T][stride_in] magnitudes in `layout` (kHoldMaskSpec /
+// kHoldMaskPlain / kHoldMaskTable with bin_of) -> angles [B*T][stride_out] in the layout injected angles take (slot_pos_c order for
+// kHoldMaskSpec, plain otherwise).  own [B*T][n_stft] uint16 and val [B*T][n_stft] double are scratch.  The LDS a frame needs:
+size_t peak_owner_lds_bytes(int n_stft);
+size_t peak_chain_lds_bytes(int n_stft);
+hipError_t launch_peak_start(int layout, const float* S, const int* bin_of, int B, int T, int stride_in, int n_stft, int hop, int n_fft,
+                             uint16_t* own, double* val, cf* angles, int stride_out, hipStream_t stream);
 
 // closed-form InverseMelScale (rfx_imel_lstsq.hip, arithmetic in rfx_imel_lstsq_core.h).  The plan's tables: the float32
 // L D L^T factors of fb^T fb - nl[m] = -L[m + 1][m] (nl[M - 1] = 0), inv_d[m] = 1 / D[m] - and, for every position of an output

@@ -194,6 +194,41 @@ def loop_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Te
                               g.guide_stride if g else 0, g.guide_samples if g else 0, 0, None, 0, None, 0, 0, 1, 0)
 
 
+class RfxStartCallOptions(ctypes.Structure):
+    """rfx_start_call_options of include/rfx.h: rfx_loop_call_options grown at its tail by the choice of Griffin-Lim's start."""
+
+    _fields_ = RfxLoopCallOptions._fields_ + [("start", ctypes.c_uint32), ("reserved6", ctypes.c_uint32)]
+
+
+def start_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
+                       row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, loop: bool = False, peak_start: bool = False):
+    """`loop_call_options`, with the spectral-peak start (Griffin-Lim starts from phases built from the call's magnitudes, no
+    randomness and no guide); peak_start=False gives the loop (or masked, held, guided, plain) options.  The peak start is a start of
+    its own: `guide`, `hold` and `hold_bins` must be None."""
+    if not peak_start:
+        return loop_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq, loop)
+    if guide is not None or hold is not None or hold_bins is not None:
+        raise ValueError("peak_start together with guide, hold or hold_bins is not served: each is a start, or needs the guide's")
+    o = call_options(row_base, magnitude_hint, lstsq)
+    return RfxStartCallOptions(ctypes.sizeof(RfxStartCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, None, 0, 0, 0, None, 0, None, 0, 0,
+                               1 if loop else 0, 0, 1, 0)
+
+
+PHASE_STARTS = ("random", "peaks")
+
+
+def check_phase_start(phase_start: str, **others: T.Any) -> bool:
+    """True for "peaks", False for "random"; ValueError for anything else, and for "peaks" together with another start or a hold
+    (`others`: the caller's angles0 / guide / hold arguments by name, None when not given)"""
+    if phase_start not in PHASE_STARTS:
+        raise ValueError(f'phase_start must be one of {PHASE_STARTS}, got {phase_start!r}')
+    if phase_start == "peaks":
+        given = [name for name, v in others.items() if v is not None]
+        if given:
+            raise ValueError(f'phase_start="peaks" does not go with {", ".join(given)}: the peak start needs no guide and holds nothing')
+    return phase_start == "peaks"
+
+
 def loop_min_frames(hop_length: int, n_fft: int) -> int:
     """the smallest T a loop call takes: hop_length * T >= n_fft, so that a frame covers the period at most once"""
     return -(-int(n_fft) // int(hop_length))
@@ -291,6 +326,11 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_griffinlim_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_griffinlim_peak_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_waveform_from_mel_peak_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_audio_from_image_peak_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_peak_start_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_peak_start": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_griffinlim_loop_output_samples": (c_int, [c_void_p, c_int]),
     "rfx_debug_loop_frames": (c_int, [c_void_p, c_int]),
     "rfx_hold_mask_words": (c_int, [c_void_p]),
@@ -784,6 +824,34 @@ class Plan:
             raise ValueError("a loop decode is not served on the chirp-z engine (RFX_ERR_UNSUPPORTED)")
         check_loop_frames(self.hop_length, self.n_fft, Tn)
 
+    def _chk_peak(self, peak_start: bool, **others: T.Any) -> None:
+        if not peak_start:
+            return
+        given = [name for name, v in others.items() if v is not None]
+        if given:
+            raise ValueError(f"peak_start does not go with {', '.join(given)}: the peak start needs no guide and holds nothing")
+        if self.n_stft > 10240:
+            raise ValueError(f"the spectral-peak start is not served for n_stft = {self.n_stft} above 10240 (RFX_ERR_UNSUPPORTED: a frame must fit the LDS)")
+
+    def _peak_extra(self, B: int, Tn: int) -> int:
+        """bytes a call with the peak start brings on top of its workspace query: the angles and the start's scratch"""
+        return self.lib.rfx_griffinlim_peak_workspace_bytes(self.handle, B, Tn) - self.lib.rfx_griffinlim_workspace_bytes(self.handle, B, Tn)
+
+    def peak_start(self, mag_slots: torch.Tensor, B: int, Tn: int) -> torch.Tensor:
+        """rfx_peak_start: magnitudes in slot layout -> (B * Tn, frame_stride) complex64 initial angles in the layout `griffinlim`'s
+        `angles0_slots` takes (what `pack_complex` makes), built from the magnitudes alone: spectral peaks, their interpolated
+        frequencies integrated over the hop.  A row depends on its magnitudes only."""
+        mag_slots = self._chk(mag_slots, torch.float32)
+        self._chk_peak(True)
+        if mag_slots.numel() < B * Tn * self.frame_stride:
+            raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
+        out = torch.empty((B * Tn, self.frame_stride), dtype=torch.complex64, device=mag_slots.device)
+        if B == 0:
+            return out
+        with self._workspace(self.lib.rfx_peak_start_workspace_bytes(self.handle, B, Tn)) as ws:
+            check(self.lib.rfx_peak_start(self.handle, mag_slots.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
     def griffinlim(
         self,
         mag_slots: torch.Tensor,
@@ -801,6 +869,7 @@ class Plan:
         hold: T.Optional[torch.Tensor] = None,
         hold_bins: T.Optional[torch.Tensor] = None,
         loop: bool = False,
+        peak_start: bool = False,
     ) -> torch.Tensor:
         """GriffinLim on magnitudes in slot layout -> (B, samples).  `row_base`: index of the call's first row in the caller's
         whole batch (the random phases of row r are drawn from (seed, row_base + r): chunked and sharded batches get the starts
@@ -812,9 +881,12 @@ class Plan:
         `hold_bins`: (B, Tn, hold_mask_words) int32 bit masks on the plan's device, with a guide and without `hold`: the set bins of
         every frame keep the guide's phase (rfx_masked_call_options; `hold_bins_from_bands` makes them from a mel-band mask).
         `loop`: the Tn columns are one period of a loop (rfx_loop_call_options): circular transforms, (B, hop_length * Tn) samples whose
-        end runs into their start; without `hold` / `hold_bins`, Tn at least `loop_min_frames`."""
+        end runs into their start; without `hold` / `hold_bins`, Tn at least `loop_min_frames`.
+        `peak_start`: start from the spectral-peak phases of the magnitudes (rfx_start_call_options; `peak_start` below) instead of
+        random ones: no randomness, without `angles0_slots`, `guide`, `hold` or `hold_bins`."""
         mag_slots = self._chk(mag_slots, torch.float32)
         self._chk_loop(loop, hold, hold_bins, Tn)
+        self._chk_peak(peak_start, angles0_slots=angles0_slots, guide=guide, hold=hold, hold_bins=hold_bins)
         if angles0_slots is not None:
             angles0_slots = self._chk(angles0_slots, torch.complex64)
         if guide is not None:
@@ -829,13 +901,15 @@ class Plan:
             raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
         need = (self.lib.rfx_griffinlim_loop_workspace_bytes if loop else self.lib.rfx_griffinlim_masked_workspace_bytes if hold_bins is not None else
                 self.lib.rfx_griffinlim_held_workspace_bytes if hold is not None else self.lib.rfx_griffinlim_workspace_bytes)(self.handle, B, Tn)
+        if peak_start:
+            need += self._peak_extra(B, Tn)
         if workspace is not None:
             workspace = self._chk(workspace)
         if workspace is None or workspace.numel() < need:  # no (or too small a) caller-owned workspace: the plan's arena
             with self._workspace(need) as ws:
-                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide, hold, hold_bins, loop)
+                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide, hold, hold_bins, loop, peak_start)
         out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mag_slots.device)
-        opt = loop_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, loop=loop)
+        opt = start_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, loop=loop, peak_start=peak_start)
         check(
             self.lib.rfx_griffinlim_ex(
                 self.handle,
@@ -1097,11 +1171,12 @@ class Plan:
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
                           row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False,
                           guide: T.Optional[torch.Tensor] = None, hold: T.Optional[torch.Tensor] = None,
-                          hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False) -> torch.Tensor:
+                          hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False, peak_start: bool = False) -> torch.Tensor:
         """spectrogram_converter.py:187-204 in one call: (B, n_mels, T) -> (B, hop * (T - 1)); `inverse_mel` (seed) + `griffinlim`
         (seed + 1), same bits, the linear magnitudes stay in the workspace.  `lstsq`: `inverse_mel_lstsq` in place of the SGD.
         `guide`: (B, Lg) float32 waveforms, `hold`: (B, 2) int32 held frames, `hold_bins`: (B, T, hold_mask_words) int32 held bins, as in
-        `griffinlim`; `loop`: a loop decode, (B, hop * T) samples, as in `griffinlim`."""
+        `griffinlim`; `loop`: a loop decode, (B, hop * T) samples, as in `griffinlim`; `peak_start`: Griffin-Lim starts from the
+        spectral-peak phases of the linear magnitudes (`peak_start`), as in `griffinlim`."""
         if lstsq:
             self.require_lstsq()
         mel = self._chk(mel, torch.float32)
@@ -1109,6 +1184,7 @@ class Plan:
         if M != self.n_mels:
             raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")  # torchaudio's message
         self._chk_loop(loop, hold, hold_bins, Tn)
+        self._chk_peak(peak_start, guide=guide, hold=hold, hold_bins=hold_bins)
         out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mel.device)
         if guide is not None:
             guide = self._chk_guide(guide)
@@ -1116,10 +1192,10 @@ class Plan:
             hold = self._chk_hold(hold, guide, B)
         if hold_bins is not None:
             hold_bins = self._chk_hold_bins(hold_bins, guide, hold, B, Tn)
-        opt = loop_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, lstsq, loop)
+        opt = start_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, lstsq, loop, peak_start)
         query = (self.lib.rfx_waveform_from_mel_loop_workspace_bytes if loop else self.lib.rfx_waveform_from_mel_masked_workspace_bytes if hold_bins is not None else
                  self.lib.rfx_waveform_from_mel_held_workspace_bytes if hold is not None else self.lib.rfx_waveform_from_mel_workspace_bytes)
-        with self._workspace(query(self.handle, B, Tn)) as ws:
+        with self._workspace(query(self.handle, B, Tn) + (self._peak_extra(B, Tn) if peak_start else 0)) as ws:
             check(self.lib.rfx_waveform_from_mel_ex(self.handle, mel.data_ptr(), B, Tn, channels_per_clip, seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return out
@@ -1132,14 +1208,15 @@ class Plan:
     def audio_from_image(self, img: torch.Tensor, stereo: bool, lut: torch.Tensor, n_iter: int, momentum: float = 0.99, seed: int = 0,
                          normalize: bool = True, out: T.Optional[torch.Tensor] = None, workspace: T.Optional[torch.Tensor] = None,
                          clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None,
-                         hold: T.Optional[torch.Tensor] = None, hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False):
+                         hold: T.Optional[torch.Tensor] = None, hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False,
+                         peak_start: bool = False):
         """spectrogram_image_converter.py:54-91 on the device in one call: (N, n_mels, T, 3) uint8 -> ((N, L, C) int16, per-clip peak (N,));
         `image_decode` + `waveform_from_mel` (clips of C rows) + `pcm16`, same bytes.  `out` as in `pcm16`.  `clip_base`: index of
         the call's first image in the caller's whole batch (row_base = clip_base * C); `magnitude_hint`: the image path's
         max_value (the largest entry of `lut`); `lstsq`: the closed-form InverseMelScale in place of the SGD; `guide`: (N * C, Lg)
         float32 waveforms, image after image and channel after channel, as in `griffinlim`; `hold`: (N * C, 2) int32 held frames, row
         for row with the guide; `hold_bins`: (N * C, T, hold_mask_words) int32 held bins, row for row as well; `loop`: a loop decode,
-        L = hop * T PCM frames per clip, as in `griffinlim`."""
+        L = hop * T PCM frames per clip, as in `griffinlim`; `peak_start`: the spectral-peak start, as in `griffinlim`."""
         if img.dtype != torch.uint8 or img.dim() != 4:
             raise ValueError("expected (N, H, W, 3) uint8 images")
         if lstsq:
@@ -1151,6 +1228,7 @@ class Plan:
             raise ValueError(f"expected (N, {self.n_mels}, T, 3) uint8 images, got {tuple(img.shape)}")
         C = 2 if stereo else 1
         self._chk_loop(loop, hold, hold_bins, W)
+        self._chk_peak(peak_start, guide=guide, hold=hold, hold_bins=hold_bins)
         L = self.output_samples(W, loop)
         if out is not None:
             if out.device != self.device or out.dtype != torch.int16 or tuple(out.shape) != (N, L, C) or not out.is_contiguous():
@@ -1161,11 +1239,14 @@ class Plan:
         need = (self.lib.rfx_audio_from_image_loop_workspace_bytes if loop else self.lib.rfx_audio_from_image_masked_workspace_bytes if hold_bins is not None else
                 self.lib.rfx_audio_from_image_held_workspace_bytes if hold is not None else self.lib.rfx_audio_from_image_workspace_bytes)(
             self.handle, N, int(stereo), W)
+        if peak_start:
+            need += self._peak_extra(N * C, W)
         ws = self._chk(workspace) if workspace is not None else None
         if ws is None or ws.numel() < need:
             with self._workspace(need) as borrowed:
                 return self.audio_from_image(img, stereo, lut, n_iter, momentum, seed, normalize, out=pcm, workspace=borrowed,
-                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop)
+                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop,
+                                             peak_start=peak_start)
         peak = torch.zeros((N,), dtype=torch.float32, device=img.device)
         if guide is not None:
             guide = self._chk_guide(guide)
@@ -1173,7 +1254,7 @@ class Plan:
             hold = self._chk_hold(hold, guide, N * C)
         if hold_bins is not None:
             hold_bins = self._chk_hold_bins(hold_bins, guide, hold, N * C, W)
-        opt = loop_call_options(guide, hold, hold_bins, N * C, clip_base * C, magnitude_hint, lstsq, loop)
+        opt = start_call_options(guide, hold, hold_bins, N * C, clip_base * C, magnitude_hint, lstsq, loop, peak_start)
         check(self.lib.rfx_audio_from_image_u8_ex(self.handle, img.data_ptr(), N, W, int(stereo), lut.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                   int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return pcm, peak

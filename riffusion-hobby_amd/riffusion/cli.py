@@ -64,7 +64,7 @@ def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_freque
 
 def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto",
                    guide_audio: str = "", griffin_lim_iters: int = -1, hold_head_ms: int = 0, hold_tail_ms: int = 0,
-                   hold_mask: str = "", hold_keep_threshold: float = 0.5, loop: bool = False) -> None:
+                   hold_mask: str = "", hold_keep_threshold: float = 0.5, loop: bool = False, phase_start: str = "random") -> None:
     """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD,
     --frame-engine chirp-z runs parameters whose FFT length has a prime factor above 13 (refused otherwise).
     --guide-audio FILE starts Griffin-Lim from the phase of that clip (audio-to-audio: the clip the tile was made of; it must be at
@@ -75,7 +75,11 @@ def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel:
     of the tile's size as the reference's mask_image (black is kept, white is repainted) - the kept region keeps the guide's phase
     through the iterations; a pixel is kept where 1 - L / 255 >= --hold-keep-threshold (0.5).  Not together with the two above.
     --loop: the tile is a loop - Griffin-Lim runs on the circular STFT and the clip (hop * width samples) runs from its end into its
-    start without a click; the tile needs n_fft / hop columns (40 at the defaults).  Not with --hold-head-ms / --hold-tail-ms / --hold-mask."""
+    start without a click; the tile needs n_fft / hop columns (40 at the defaults).  Not with --hold-head-ms / --hold-tail-ms / --hold-mask.
+    --phase-start peaks starts Griffin-Lim from phases built from the tile's own magnitudes (spectral peaks, their frequencies
+    integrated over the hop) instead of random ones: for a tile without a guide and few --griffin-lim-iters.  Not with --guide-audio."""
+    if phase_start == "peaks" and guide_audio:
+        raise ValueError("--phase-start peaks does not go with --guide-audio: they are two starts")
     if loop and (hold_mask or hold_head_ms or hold_tail_ms):
         raise ValueError("--loop does not go with --hold-head-ms / --hold-tail-ms / --hold-mask")
     if hold_mask and not guide_audio:
@@ -95,7 +99,7 @@ def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel:
                                                      hold_frames=params.hold_frames_for(hold_head_ms / 1000.0, hold_tail_ms / 1000.0)
                                                      if hold_head_ms or hold_tail_ms else None,
                                                      hold_mask=image_util.hold_mask_from_image(Image.open(hold_mask), hold_keep_threshold)
-                                                     if hold_mask else None, loop=loop)
+                                                     if hold_mask else None, loop=loop, phase_start=phase_start)
     segment.export(audio, format=os.path.splitext(audio)[1][1:] or "wav")
     print(f"Wrote {audio} ({segment.duration_seconds:.2f} seconds)")
 
@@ -165,14 +169,17 @@ def _load_tiles(converter: SpectrogramImageConverter, chunk: T.Sequence[str], im
 
 def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 64, no_filters: bool = False,
                           compression: bool = False, device: str = "cuda", inverse_mel: str = "sgd", image_extension: str = "png",
-                          frame_engine: str = "auto", loop: bool = False) -> None:
+                          frame_engine: str = "auto", loop: bool = False, phase_start: str = "random", griffin_lim_iters: int = -1) -> None:
     """Decode every *.png (or, with --image-extension jpg / jpeg, every file of that extension) of a directory, `batch_size`
     same-width tiles per GPU call.  Each clip then gets the same
     post-processing as `image-to-audio` (audio_util.apply_filters, reference spectrogram_image_converter.py:65-91, run on the
     device) unless --no-filters is given; --compression adds the filters' dynamic range compression (apply_filters with
     compression=True, also on the device); --inverse-mel lstsq takes the closed-form InverseMelScale instead of the SGD;
     --frame-engine chirp-z decodes tiles whose parameters give an FFT length with a prime factor above 13; --loop decodes every
-    tile as a loop (see image-to-audio)."""
+    tile as a loop (see image-to-audio); --phase-start peaks starts Griffin-Lim from the tiles' spectral peaks instead of random
+    phases and --griffin-lim-iters N runs N iterations instead of the params' 32: the start is for decodes with few of them."""
+    if griffin_lim_iters < -1:
+        raise ValueError("--griffin-lim-iters must be >= 0")
     if compression and no_filters:
         raise ValueError("--compression is a mode of the filters: it does not go with --no-filters")
     if image_extension not in ("png", "jpg", "jpeg"):
@@ -186,7 +193,8 @@ def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 
             chunk = members[i : i + batch_size]
             # the filters run on the device, clip by clip, before the batch leaves it (same bytes as audio_util.apply_filters)
             pcm = converter.audio_from_spectrogram_images(_load_tiles(converter, chunk, image_extension), apply_filters=not no_filters,
-                                                          compression=compression, inverse_mel=inverse_mel, loop=loop)
+                                                          compression=compression, inverse_mel=inverse_mel, loop=loop, phase_start=phase_start,
+                                                          griffin_lim_iters=griffin_lim_iters if griffin_lim_iters >= 0 else None)
             for path, samples in zip(chunk, pcm):
                 segment = audio_util.PcmSegment(samples, params.sample_rate)
                 out = os.path.join(output_dir, os.path.splitext(os.path.basename(path))[0] + ".wav")
@@ -304,7 +312,7 @@ _COMMANDS: T.Dict[str, T.Callable[..., None]] = {
 }
 
 
-_CHOICES = {"inverse_mel": ("sgd", "lstsq"), "frame_engine": ("auto", "chirp-z")}  # arguments that take one of a few words
+_CHOICES = {"inverse_mel": ("sgd", "lstsq"), "frame_engine": ("auto", "chirp-z"), "phase_start": ("random", "peaks")}  # arguments that take one of a few words
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -343,6 +351,10 @@ def main(argv: T.Optional[T.Sequence[str]] = None) -> None:
             parser.error("--hold-keep-threshold must be in [0, 1]")
     if command == "image-to-audio" and args["loop"] and (args["hold_mask"] or args["hold_head_ms"] or args["hold_tail_ms"]):
         parser.error("--loop does not go with --hold-head-ms / --hold-tail-ms / --hold-mask")
+    if command == "image-to-audio" and args["phase_start"] == "peaks" and args["guide_audio"]:
+        parser.error("--phase-start peaks does not go with --guide-audio: they are two starts")
+    if command == "images-to-audio-batch" and args["griffin_lim_iters"] < -1:
+        parser.error("--griffin-lim-iters must be >= 0")
     _COMMANDS[command](**args)
 
 

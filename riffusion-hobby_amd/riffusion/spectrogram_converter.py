@@ -160,12 +160,17 @@ class SpectrogramConverter:
         amplitudes_mel = self.mel_amplitudes_from_waveform(waveform_tensor)
         return amplitudes_mel.cpu().numpy()
 
-    def audio_from_spectrogram(self, spectrogram: np.ndarray, apply_filters: bool = True, *, loop: bool = False) -> T.Any:
+    def audio_from_spectrogram(self, spectrogram: np.ndarray, apply_filters: bool = True, *, loop: bool = False,
+                               phase_start: str = "random") -> T.Any:
         """(channels, n_mels, T) mel amplitudes -> audio segment with that many channels.  `loop`: a loop decode
-        (`waveform_from_mel_amplitudes`): hop*T samples whose end runs into their start."""
+        (`waveform_from_mel_amplitudes`): hop*T samples whose end runs into their start.  `phase_start`: "random" (the reference) or
+        "peaks", Griffin-Lim's start built from the magnitudes (`waveform_from_mel_amplitudes`)."""
+        from riffusion import _hip
+
+        peaks = _hip.check_phase_start(phase_start)
         amplitudes_mel = torch.from_numpy(np.ascontiguousarray(spectrogram)).to(self.device)
         plan = self._plan()
-        waveform = self._waveform_from_mel(plan, amplitudes_mel, loop=loop)
+        waveform = self._waveform_from_mel(plan, amplitudes_mel, loop=loop, peak_start=peaks)
         # peak-normalise + int16 truncation on the device (audio_util.py:22-28), one D2H of int16
         pcm, _ = plan.pcm16(waveform, channels=waveform.shape[0], normalize=True)
         host_filters = apply_filters and pcm.shape[1] * pcm.shape[2] >= audio_util.FILTER_EXACT_SAMPLES
@@ -194,6 +199,7 @@ class SpectrogramConverter:
         hold_frames: T.Any = None,
         hold_mask: T.Any = None,
         loop: bool = False,
+        phase_start: str = "random",
     ) -> torch.Tensor:
         """
         (B, n_mels, T) -> (B, hop*(T-1)).  The reference treats the whole batch as ONE clip (the SGD
@@ -218,7 +224,14 @@ class SpectrogramConverter:
         `loop`: the T columns are one period of a loop (rfx_loop_call_options): Griffin-Lim runs on the circular STFT, the result
         has hop*T samples and its end runs into its start - no click when the clip is played on repeat.  T must reach n_fft / hop
         (40 at the defaults); not together with `hold_frames` or `hold_mask`.
+        `phase_start`: "random" (the reference's U[0,1) start) or "peaks": Griffin-Lim starts from phases built from the linear
+        magnitudes alone - the spectral peaks of every frame, their interpolated frequencies integrated over the hop
+        (rfx_start_call_options).  No guide and no randomness in Griffin-Lim; it needs fewer iterations for the same spectral
+        convergence at low iteration counts (README).  Not together with `angles0`, `guide`, `hold_frames` or `hold_mask`.
         """
+        from riffusion import _hip
+
+        peaks = _hip.check_phase_start(phase_start, angles0=angles0, guide=guide, hold_frames=hold_frames, hold_mask=hold_mask)
         if loop and (hold_frames is not None or hold_mask is not None):
             raise ValueError("loop together with hold_frames or hold_mask is not served")
         if guide is not None and angles0 is not None:
@@ -237,7 +250,7 @@ class SpectrogramConverter:
             bands = hold_mask_rows(hold_mask, int(amplitudes_mel.shape[0]), int(amplitudes_mel.shape[1]), int(amplitudes_mel.shape[-1]))
         return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
                                        channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, hold=hold, hold_bands=bands,
-                                       loop=loop)
+                                       loop=loop, peak_start=peaks)
 
     def hold_frames_for(self, head_s: float = 0.0, tail_s: float = 0.0) -> T.Tuple[int, int]:
         """`SpectrogramParams.hold_frames_for` of this converter's params: the `hold_frames` pair for `head_s` / `tail_s` seconds
@@ -249,15 +262,19 @@ class SpectrogramConverter:
                            channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0,
                            return_slots: bool = False, inverse_mel: str = "sgd", guide: T.Optional[torch.Tensor] = None,
                            n_iter: T.Optional[int] = None, hold: T.Optional[torch.Tensor] = None,
-                           hold_bands: T.Optional[torch.Tensor] = None, loop: bool = False) -> T.Any:
+                           hold_bands: T.Optional[torch.Tensor] = None, loop: bool = False, peak_start: bool = False) -> T.Any:
         """`waveform_from_mel_amplitudes` on a plan the caller already holds (the batch entry points fetch it once per call,
         not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild).
         `return_slots=True` runs the two inverse stages separately - same bits as the one call - and returns
         (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares.  `guide`: (B, Lg) float32 guide
         waveforms (`waveform_from_mel_amplitudes`); `n_iter`: Griffin-Lim iterations in place of the params'; `hold`: (B, 2)
         int32 held frames of a guided call (`hold_rows`); `hold_bands`: (B, n_mels, T) uint8 held mel bands of a masked call
-        (`hold_mask_rows`), expanded to bins on the device; `loop`: a loop decode (`waveform_from_mel_amplitudes`)."""
+        (`hold_mask_rows`), expanded to bins on the device; `loop`: a loop decode (`waveform_from_mel_amplitudes`); `peak_start`: the
+        spectral-peak start (`phase_start="peaks"`)."""
         from riffusion import _hip
+
+        if peak_start and (angles0 is not None or guide is not None or hold is not None or hold_bands is not None):
+            raise ValueError('phase_start="peaks" does not go with angles0, guide, hold_frames or hold_mask')
 
         if loop:
             if hold is not None or hold_bands is not None:
@@ -281,7 +298,7 @@ class SpectrogramConverter:
         hold_bins = plan.hold_bins_from_bands(hold_bands.to(self.device)) if hold_bands is not None else None
         if spec0 is None and angles0 is None and not return_slots:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
             return plan.waveform_from_mel(mel, cpc, n_iter, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint,
-                                          lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop)
+                                          lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop, peak_start=peak_start)
         spec0 = spec0.to(self.device) if spec0 is not None else None
         if lstsq:
             lin_slots = plan.inverse_mel_lstsq(mel)
@@ -289,7 +306,7 @@ class SpectrogramConverter:
             lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         a0 = plan.pack_complex(angles0.to(self.device)) if angles0 is not None else None
         wave = plan.griffinlim(lin_slots, B, Tn, n_iter, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
-                               magnitude_hint=magnitude_hint, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop)
+                               magnitude_hint=magnitude_hint, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop, peak_start=peak_start)
         return (wave, lin_slots) if return_slots else wave
 
     # ---- quality of a decode ------------------------------------------------------------------------

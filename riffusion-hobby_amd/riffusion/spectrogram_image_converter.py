@@ -65,6 +65,7 @@ class SpectrogramImageConverter:
         hold_frames: T.Optional[T.Tuple[int, int]] = None,
         hold_mask: T.Any = None,
         loop: bool = False,
+        phase_start: str = "random",
     ) -> T.Any:
         """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference).  The filters
         (audio_util.apply_filters, compression=False) run on the device: same bytes.  `inverse_mel`: "sgd" (default) or
@@ -75,8 +76,10 @@ class SpectrogramImageConverter:
         the clip's two ends that keep the guide's phase through the iterations (`hold_frames_for` turns seconds of known audio
         into the pair).  `hold_mask`: with a guide, a mask image of the tile's size (black is kept, as the reference's `mask_image`)
         or an (n_mels, W) boolean array: the kept region keeps the guide's phase through the iterations.  `loop`: the tile is
-        one period of a loop: hop * W samples whose end runs into their start (not with `hold_frames` / `hold_mask`).  All as in
-        `audio_from_spectrogram_images`."""
+        one period of a loop: hop * W samples whose end runs into their start (not with `hold_frames` / `hold_mask`).
+        `phase_start`: "random" (default) or "peaks", Griffin-Lim's start built from the tile's magnitudes (not with a guide).  All as
+        in `audio_from_spectrogram_images`."""
+        _hip.check_phase_start(phase_start, guide_segment=guide_segment, hold_frames=hold_frames, hold_mask=hold_mask)
         if hold_frames is not None and guide_segment is None:
             raise ValueError("hold_frames needs a guide: the frames are held at the guide's phase")
         if hold_mask is not None and guide_segment is None:
@@ -92,7 +95,7 @@ class SpectrogramImageConverter:
         pcm = self.audio_from_spectrogram_images(
             np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters,
             inverse_mel=inverse_mel, guide_waveforms=guides, griffin_lim_iters=griffin_lim_iters, hold_frames=hold_frames,
-            hold_mask=hold_mask, loop=loop,
+            hold_mask=hold_mask, loop=loop, phase_start=phase_start,
         )
         return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
 
@@ -133,6 +136,7 @@ class SpectrogramImageConverter:
         griffin_lim_iters: T.Optional[int] = None,
         hold_mask: T.Any = None,
         loop: bool = False,
+        phase_start: str = "random",
     ) -> T.Any:
         """
         A sequence of tiles -> ONE audio segment: every tile decoded (`audio_from_spectrogram_images`), filtered
@@ -155,8 +159,11 @@ class SpectrogramImageConverter:
         `inverse_mel`: "sgd" (default) or "lstsq", as in `audio_from_spectrogram_images`.
         `guide_waveforms`, `griffin_lim_iters`, `hold_mask`: the guides of a phase-guided decode, its iterations and the kept
         region of a partial regeneration, as in `audio_from_spectrogram_images`; not for tiles of different sizes without `size`.
+        `phase_start`: "random" (default) or "peaks", as in `audio_from_spectrogram_images`; not for tiles of different sizes
+        without `size`.
         """
         _hip.check_inverse_mel(inverse_mel)
+        peaks = _hip.check_phase_start(phase_start, guide_waveforms=guide_waveforms, hold_mask=hold_mask)
         if loop:  # (`loop` is here to be refused: a sequence is stitched with crossfades, its clips do not repeat)
             raise ValueError("loop does not go with a stitched sequence: decode loops with audio_from_spectrogram_images(loop=True)")
         if hold_mask is not None and guide_waveforms is None:
@@ -170,6 +177,8 @@ class SpectrogramImageConverter:
                         raise ValueError("return_error needs tiles of one size (or `size`): clips decoded one by one carry no error figure")
                     if guide_waveforms is not None or griffin_lim_iters is not None:
                         raise ValueError("guide_waveforms / griffin_lim_iters need tiles of one size (or `size`)")
+                    if peaks:
+                        raise ValueError('phase_start="peaks" needs tiles of one size (or `size`)')
                     return self._image_sequence_mixed(arrays, crossfade_s, apply_filters, max_value, seed, return_device, compression,
                                                       inverse_mel=inverse_mel)
                 images, size = torch.cat([self.resize_images(a[None], size) for a in arrays]), None
@@ -189,7 +198,7 @@ class SpectrogramImageConverter:
         pcm = self.audio_from_spectrogram_images(images, max_value=max_value, seed=seed, tiles_per_call=tiles_per_call,
                                                  return_device=True, apply_filters=apply_filters, compression=compression, size=size,
                                                  return_error=return_error, inverse_mel=inverse_mel, guide_waveforms=guide_waveforms,
-                                                 griffin_lim_iters=griffin_lim_iters, hold_mask=hold_mask)
+                                                 griffin_lim_iters=griffin_lim_iters, hold_mask=hold_mask, phase_start=phase_start)
         errors = None
         if return_error:
             pcm, errors = pcm
@@ -499,6 +508,7 @@ class SpectrogramImageConverter:
         hold_frames: T.Any = None,
         hold_mask: T.Any = None,
         loop: bool = False,
+        phase_start: str = "random",
     ) -> T.Any:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -586,10 +596,17 @@ class SpectrogramImageConverter:
         and its last sample runs into its first: no click at the loop point.  W (or `size[0]`) must reach n_fft / hop (40 columns
         at the defaults).  Guides, `inverse_mel`, `apply_filters`, `tiles_per_call`, `group` and `size` work as without it; not
         with `hold_frames`, `hold_mask` or `return_error` (the error entry analyses with the reflect-padded STFT): ValueError.
+        `phase_start`: "random" (default: the reference's U[0,1) phases from `seed`) or "peaks": Griffin-Lim starts every row from
+        phases built from its magnitudes alone - the spectral peaks of every frame, their interpolated frequencies integrated
+        over the hop (rfx_start_call_options) - so that a text-to-audio decode, which has no guide, needs fewer iterations:
+        combine it with a small `griffin_lim_iters` (README: what it saves and what it costs).  Griffin-Lim then has no
+        randomness (the SGD InverseMelScale still draws its start from `seed`); any `tiles_per_call` and sharding give the same
+        bytes.  Not with `guide_waveforms`, `hold_frames` or `hold_mask`; any other string: ValueError before any GPU work.
         """
         from riffusion import batch_shard
 
         lstsq = _hip.check_inverse_mel(inverse_mel)
+        peaks = _hip.check_phase_start(phase_start, guide_waveforms=guide_waveforms, hold_frames=hold_frames, hold_mask=hold_mask)
         if loop and (hold_frames is not None or hold_mask is not None):
             raise ValueError("loop together with hold_frames or hold_mask is not served")
         if loop and return_error:
@@ -713,7 +730,7 @@ class SpectrogramImageConverter:
                     wave, lin_slots = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C,
                                                               magnitude_hint=max_value, return_slots=True, inverse_mel=inverse_mel,
                                                               guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b),
-                                                              hold_bands=held_bands(a, b))
+                                                              hold_bands=held_bands(a, b), peak_start=peaks)
                     error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1])).reshape(b - a, C, 2).sum(1))
                     if return_waveform:
                         out = wave.reshape(b - a, C, -1)
@@ -725,13 +742,14 @@ class SpectrogramImageConverter:
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value,
                                                    inverse_mel=inverse_mel, guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b),
-                                                   hold_bands=held_bands(a, b), loop=loop)
+                                                   hold_bands=held_bands(a, b), loop=loop, peak_start=peaks)
                     out = wave.reshape(b - a, C, -1)
                 else:  # uint8 tiles -> int16 PCM in one call (rfx_audio_from_image_u8_ex), same bytes as the three calls above + pcm16
                     dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
                     out = plan.audio_from_image(tiles, self.p.stereo, lut, n_iter, 0.99, seed=base_seed,
                                                 normalize=True, out=dst, clip_base=a, magnitude_hint=max_value, lstsq=lstsq,
-                                                guide=guide_rows(a, b), hold=held_rows(a, b), hold_bins=held_bins(a, b), loop=loop)[0]
+                                                guide=guide_rows(a, b), hold=held_rows(a, b), hold_bins=held_bins(a, b), loop=loop,
+                                                peak_start=peaks)[0]
                     if apply_filters:
                         out = self._filter_pcm(plan, out, compression)
                 # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them
