@@ -156,13 +156,25 @@ int rfx_griffinlim_form(const rfx_plan* plan, int B, int T) {
 // loop (rfx_loop_call_options.loop): the per-frame form, audio rows of the period's hop T samples, and the hop-entry reciprocal envelope
 // where the unlooped call keeps its normalisation table; no layout (total 0) for a T the call refuses.
 enum GlKind { kGlPlain = 0, kGlHeld = 1, kGlMasked = 2, kGlLoop = 3 };
+// One struct for both engines (`scale`: the specialised engine only; `repacked`: the generic one only).  peak (a call with
+// rfx_start_call_options.start): behind everything the call has without it, the start's angles and scratch (rfx_api_peak.hip).
 struct GlLayout {
-  size_t audio, scale, frames, row_scale, list, xmag, cadd, total;
+  size_t audio, scale, frames, repacked, row_scale, list, xmag, cadd, angles, peak_scratch, total;
   int Lpad;
 };
 static size_t hold_list_bytes(int B, int T) { return hold_list_words(B, T) * sizeof(int32_t); }
-static GlLayout gl_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlPlain) {
-  const bool held = kind == kGlHeld, masked = kind == kGlMasked, loop = kind == kGlLoop;
+// the fields every kind has at its end, in both engines
+static void carve_gl_tail(Carve& c, GlLayout& l, const rfx_plan* plan, int B, int T, GlKind kind, bool peak, size_t xmag_stride) {
+  l.row_scale = c.take(range_table_bytes(B));
+  l.list = c.take(kind == kGlHeld ? hold_list_bytes(B, T) : 0);
+  l.xmag = c.take(kind == kGlMasked ? (size_t)B * T * xmag_stride * sizeof(float) : 0);
+  l.cadd = c.take(kind == kGlMasked ? (size_t)B * l.Lpad * sizeof(float) : 0);
+  l.angles = c.take(peak ? peak_angles_bytes(plan, B, T) : 0);
+  l.peak_scratch = c.take(peak ? peak_scratch_bytes(plan, B, T) : 0);
+  l.total = c.at;
+}
+static GlLayout gl_layout(const rfx_plan* plan, int B, int T, GlKind kind, bool peak) {
+  const bool loop = kind == kGlLoop;
   GlLayout l{};
   if (B <= 0 || T < 2) return l;
   if (loop && !loop_valid(kHop, T, kNfft)) return l;
@@ -170,12 +182,8 @@ static GlLayout gl_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlP
   Carve c;
   l.audio = c.take(6 * (size_t)B * l.Lpad * sizeof(float));
   l.scale = c.take((size_t)l.Lpad * sizeof(float));
-  l.frames = c.take(held || masked || loop || gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
-  l.row_scale = c.take(range_table_bytes(B));
-  l.list = c.take(held ? hold_list_bytes(B, T) : 0);
-  l.xmag = c.take(masked ? (size_t)B * T * kFrameStride * sizeof(float) : 0);
-  l.cadd = c.take(masked ? (size_t)B * l.Lpad * sizeof(float) : 0);
-  l.total = c.at;
+  l.frames = c.take(kind != kGlPlain || gl_use_latency_mode(plan, B, T) ? gl_frame_buffer_bytes(B, T) : 0);
+  carve_gl_tail(c, l, plan, B, T, kind, peak, kFrameStride);
   return l;
 }
 
@@ -185,13 +193,9 @@ static int gen_out_len(const GenGeom& g, int T) { return g.hop * (T - 1) + (g.n_
 // Generic engine: the windowed synthesis frames, three generations of the audio estimate (x_{k-1}, x_k read; x_{k+1} written) and
 // the window envelope of the fold, [Lpad]; on a row family the magnitudes re-ordered into slot order; the row-scale table; held: the
 // free-frame list; masked: X (in the order the frame kernels read: the family's slot order on a row family) and c
-struct GenGlLayout {
-  size_t frames, audio, repacked, row_scale, list, xmag, cadd, total;
-  int Lpad;
-};
-static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlPlain) {
-  const bool held = kind == kGlHeld, masked = kind == kGlMasked, loop = kind == kGlLoop;
-  GenGlLayout l{};
+static GlLayout gen_gl_layout(const rfx_plan* plan, int B, int T, GlKind kind, bool peak) {
+  const bool loop = kind == kGlLoop;
+  GlLayout l{};
   if (B <= 0 || T < 2) return l;
   const GenGeom& g = plan->gg;
   if (loop && (plan->czt || !loop_valid(g.hop, T, g.n_fft))) return l;
@@ -201,26 +205,11 @@ static GenGlLayout gen_gl_layout(const rfx_plan* plan, int B, int T, GlKind kind
   l.frames = c.take(nf * g.fpitch * sizeof(float));
   l.audio = c.take((3 * (size_t)B + 1) * l.Lpad * sizeof(float));
   l.repacked = c.take(plan->fam_ok ? nf * plan->fam.fsf * sizeof(float) : 0);
-  l.row_scale = c.take(range_table_bytes(B));
-  l.list = c.take(held ? hold_list_bytes(B, T) : 0);
-  l.xmag = c.take(masked ? nf * (plan->fam_ok ? (size_t)plan->fam.fsf : (size_t)g.fs) * sizeof(float) : 0);
-  l.cadd = c.take(masked ? (size_t)B * l.Lpad * sizeof(float) : 0);
-  l.total = c.at;
+  carve_gl_tail(c, l, plan, B, T, kind, peak, plan->fam_ok ? (size_t)plan->fam.fsf : (size_t)g.fs);
   return l;
 }
-
-static size_t griffinlim_workspace(const rfx_plan* plan, int B, int T, GlKind kind) {
-  if (!plan) return 0;
-  return plan->generic ? gen_gl_layout(plan, B, T, kind).total : gl_layout(plan, B, T, kind).total;
-}
-size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlPlain); }
-size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlHeld); }
-size_t rfx_griffinlim_masked_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlMasked); }
-size_t rfx_griffinlim_loop_workspace_bytes(const rfx_plan* plan, int B, int T) { return griffinlim_workspace(plan, B, T, kGlLoop); }
-// a call with the spectral-peak start: behind everything the call has without it, the angles and the start's scratch
-static size_t with_peak(const rfx_plan* plan, size_t base, int B, int T) { return base ? base + peak_extra_bytes(plan, B, T) : 0; }
-size_t rfx_griffinlim_peak_workspace_bytes(const rfx_plan* plan, int B, int T) {
-  return plan ? with_peak(plan, griffinlim_workspace(plan, B, T, kGlPlain), B, T) : 0;
+static GlLayout griffinlim_layout(const rfx_plan* plan, int B, int T, GlKind kind, bool peak) {
+  return plan->generic ? gen_gl_layout(plan, B, T, kind, peak) : gl_layout(plan, B, T, kind, peak);
 }
 int rfx_griffinlim_loop_output_samples(const rfx_plan* plan, int T) {
   if (!plan || T <= 0 || (long long)plan->p.hop_length * T > 0x7fffffffLL) return 0;
@@ -251,8 +240,46 @@ struct CallOpt {
   bool peak = false;
   GlKind kind() const { return loop ? kGlLoop : mask ? kGlMasked : hold ? kGlHeld : kGlPlain; }
 };
-// allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves); takes_guide: it runs Griffin-Lim
-static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who, uint32_t allowed_flags = 0, bool takes_guide = false) {
+// The grown tails of rfx_call_options, in the order they were added (each is the same struct, grown; a caller that passes a
+// shorter size has none of the later ones)
+enum { kTailGuide, kTailHold, kTailMask, kTailLoop, kTailStart, kTails };
+struct TailRead {
+  const char* bad = nullptr;      // a reserved field or a range: refused whether or not the option is set
+  bool set = false;
+  const char* bad_set = nullptr;  // of an option that is set: its pointer's alignment, the guide's geometry
+};
+// why an entry point that runs no Griffin-Lim refuses a tail that is set
+static const char* const kNoGriffinLim[kTails] = {
+    "takes no guide (d_guide must be NULL)", "holds no frames (d_hold_frames must be NULL)", "holds no bins (d_hold_bins must be NULL)",
+    "decodes no loop (loop must be 0)", "takes no start (start must be 0)"};
+// The combination rules: what the option of `tail` does not go with, among the options read before it
+static const char* rule_refusal(int tail, const CallOpt& o) {
+  switch (tail) {
+    case kTailHold:
+      if (!o.guide) return "d_hold_frames needs a guide to hold the frames at (d_guide is NULL)";
+      break;
+    case kTailMask:
+      if (!o.guide) return "d_hold_bins needs a guide to hold the bins at (d_guide is NULL)";
+      if (o.hold) return "d_hold_bins together with d_hold_frames is not served: set the held frames' bits in the mask";
+      break;
+    case kTailLoop:
+      if (o.hold || o.mask) return "loop together with d_hold_frames or d_hold_bins is not served";
+      break;
+    case kTailStart:
+      if (o.mask) return "start == 1 together with d_hold_bins is not served (bins are held at a guide's phase)";
+      if (o.hold) return "start == 1 together with d_hold_frames is not served (frames are held at a guide's phase)";
+      if (o.guide) return "start == 1 and d_guide are two starts: give one";
+      break;
+  }
+  return nullptr;
+}
+template <class Tail, class Field>
+static const Tail* tail_of(const rfx_call_options* o, Field Tail::*last) {  // null: the caller's struct ends before `last`
+  const Tail* t = reinterpret_cast<const Tail*>(o);
+  return o->struct_size >= (size_t)((const char*)&(t->*last) - (const char*)t) + sizeof(Field) ? t : nullptr;
+}
+// allowed_flags: the RFX_CALL_* bits this entry point reads (0 for the two stages themselves); runs_gl: it runs Griffin-Lim
+static int read_call_options(const rfx_call_options* o, CallOpt* out, const char* who, uint32_t allowed_flags = 0, bool runs_gl = false) {
   *out = CallOpt{};
   if (!o) return RFX_OK;
   if (o->struct_size < offsetof(rfx_call_options, row_base) + sizeof(uint64_t))
@@ -267,70 +294,57 @@ static int read_call_options(const rfx_call_options* o, CallOpt* out, const char
     return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.magnitude_hint must be a finite value >= 0");
   if (o->struct_size >= offsetof(rfx_call_options, reserved) + sizeof(float) && !(o->reserved == 0.f))
     return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_call_options.reserved must be 0");
-  // the guided tail (rfx_guided_call_options: the same struct, grown; a caller that passes the short size has none)
-  if (o->struct_size >= offsetof(rfx_guided_call_options, reserved2) + sizeof(int32_t)) {
-    const rfx_guided_call_options* g = reinterpret_cast<const rfx_guided_call_options*>(o);
-    if (g->reserved2 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_guided_call_options.reserved2 must be 0");
-    if (g->d_guide) {
-      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and takes no guide (d_guide must be NULL)");
-      if (g->guide_samples <= 0) return fail(RFX_ERR_INVALID, std::string(who) + ": guide_samples must be positive when d_guide is given");
-      if (g->guide_stride < (int64_t)g->guide_samples)
-        return fail(RFX_ERR_INVALID, std::string(who) + ": guide_stride (elements between rows) must be at least guide_samples");
-      if ((uintptr_t)g->d_guide & (sizeof(float) - 1)) return fail(RFX_ERR_INVALID, std::string(who) + ": d_guide must be aligned to 4 bytes");
+  TailRead tails[kTails];
+  if (const auto* g = tail_of(o, &rfx_guided_call_options::reserved2)) {
+    TailRead& t = tails[kTailGuide];
+    if (g->reserved2 != 0) t.bad = "rfx_guided_call_options.reserved2 must be 0";
+    if ((t.set = g->d_guide != nullptr)) {
+      t.bad_set = g->guide_samples <= 0                           ? "guide_samples must be positive when d_guide is given"
+                  : g->guide_stride < (int64_t)g->guide_samples   ? "guide_stride (elements between rows) must be at least guide_samples"
+                  : (uintptr_t)g->d_guide & (sizeof(float) - 1)   ? "d_guide must be aligned to 4 bytes"
+                                                                  : nullptr;
       out->guide = g->d_guide;
       out->guide_stride = g->guide_stride;
       out->guide_samples = g->guide_samples;
     }
   }
-  // the held tail (rfx_held_call_options: grown once more)
-  if (o->struct_size >= offsetof(rfx_held_call_options, reserved3) + sizeof(uint64_t)) {
-    const rfx_held_call_options* h = reinterpret_cast<const rfx_held_call_options*>(o);
-    if (h->reserved3 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_held_call_options.reserved3 must be 0");
-    if (h->d_hold_frames) {
-      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and holds no frames (d_hold_frames must be NULL)");
-      if (!out->guide) return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_frames needs a guide to hold the frames at (d_guide is NULL)");
-      if ((uintptr_t)h->d_hold_frames & (sizeof(int32_t) - 1)) return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_frames must be aligned to 4 bytes");
+  if (const auto* h = tail_of(o, &rfx_held_call_options::reserved3)) {
+    TailRead& t = tails[kTailHold];
+    if (h->reserved3 != 0) t.bad = "rfx_held_call_options.reserved3 must be 0";
+    if ((t.set = h->d_hold_frames != nullptr)) {
+      if ((uintptr_t)h->d_hold_frames & (sizeof(int32_t) - 1)) t.bad_set = "d_hold_frames must be aligned to 4 bytes";
       out->hold = h->d_hold_frames;
     }
   }
-  // the masked tail (rfx_masked_call_options: grown a third time)
-  if (o->struct_size >= offsetof(rfx_masked_call_options, reserved4) + sizeof(int32_t)) {
-    const rfx_masked_call_options* m = reinterpret_cast<const rfx_masked_call_options*>(o);
-    if (m->reserved4 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_masked_call_options.reserved4 must be 0");
-    if (m->d_hold_bins) {
-      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and holds no bins (d_hold_bins must be NULL)");
-      if (!out->guide) return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_bins needs a guide to hold the bins at (d_guide is NULL)");
-      if (out->hold)
-        return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_bins together with d_hold_frames is not served: set the held frames' bits in the mask");
-      if ((uintptr_t)m->d_hold_bins & (sizeof(uint32_t) - 1)) return fail(RFX_ERR_INVALID, std::string(who) + ": d_hold_bins must be aligned to 4 bytes");
+  if (const auto* m = tail_of(o, &rfx_masked_call_options::reserved4)) {
+    TailRead& t = tails[kTailMask];
+    if (m->reserved4 != 0) t.bad = "rfx_masked_call_options.reserved4 must be 0";
+    if ((t.set = m->d_hold_bins != nullptr)) {
+      if ((uintptr_t)m->d_hold_bins & (sizeof(uint32_t) - 1)) t.bad_set = "d_hold_bins must be aligned to 4 bytes";
       out->mask = m->d_hold_bins;
       out->mask_words = m->hold_words;
     }
   }
-  // the loop tail (rfx_loop_call_options: grown a fourth time)
-  if (o->struct_size >= offsetof(rfx_loop_call_options, reserved5) + sizeof(uint32_t)) {
-    const rfx_loop_call_options* l = reinterpret_cast<const rfx_loop_call_options*>(o);
-    if (l->reserved5 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_loop_call_options.reserved5 must be 0");
-    if (l->loop > 1) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_loop_call_options.loop must be 0 or 1");
-    if (l->loop) {
-      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and decodes no loop (loop must be 0)");
-      if (out->hold || out->mask)
-        return fail(RFX_ERR_INVALID, std::string(who) + ": loop together with d_hold_frames or d_hold_bins is not served");
-      out->loop = true;
-    }
+  if (const auto* l = tail_of(o, &rfx_loop_call_options::reserved5)) {
+    TailRead& t = tails[kTailLoop];
+    t.bad = l->reserved5 != 0 ? "rfx_loop_call_options.reserved5 must be 0" : l->loop > 1 ? "rfx_loop_call_options.loop must be 0 or 1" : nullptr;
+    t.set = out->loop = l->loop != 0;
   }
-  // the start tail (rfx_start_call_options: grown a fifth time)
-  if (o->struct_size >= offsetof(rfx_start_call_options, reserved6) + sizeof(uint32_t)) {
-    const rfx_start_call_options* st = reinterpret_cast<const rfx_start_call_options*>(o);
-    if (st->reserved6 != 0) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_start_call_options.reserved6 must be 0");
-    if (st->start > 1) return fail(RFX_ERR_INVALID, std::string(who) + ": rfx_start_call_options.start must be 0 or 1");
-    if (st->start) {
-      if (!takes_guide) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and takes no start (start must be 0)");
-      if (out->mask) return fail(RFX_ERR_INVALID, std::string(who) + ": start == 1 together with d_hold_bins is not served (bins are held at a guide's phase)");
-      if (out->hold) return fail(RFX_ERR_INVALID, std::string(who) + ": start == 1 together with d_hold_frames is not served (frames are held at a guide's phase)");
-      if (out->guide) return fail(RFX_ERR_INVALID, std::string(who) + ": start == 1 and d_guide are two starts: give one");
-      out->peak = true;
-    }
+  if (const auto* st = tail_of(o, &rfx_start_call_options::reserved6)) {
+    TailRead& t = tails[kTailStart];
+    t.bad = st->reserved6 != 0 ? "rfx_start_call_options.reserved6 must be 0" : st->start > 1 ? "rfx_start_call_options.start must be 0 or 1" : nullptr;
+    t.set = out->peak = st->start != 0;
+  }
+  // the refusals, tail after tail: a reserved field or a range; then, of an option that is set, an entry point that runs no
+  // Griffin-Lim, the combination rules, the option's own pointer
+  for (int i = 0; i < kTails; ++i) {
+    const TailRead& t = tails[i];
+    if (t.bad) return fail(RFX_ERR_INVALID, std::string(who) + ": " + t.bad);
+    if (!t.set) continue;
+    if (!runs_gl) return fail(RFX_ERR_INVALID, std::string(who) + ": this entry point runs no Griffin-Lim and " + kNoGriffinLim[i]);
+    const char* why = rule_refusal(i, *out);
+    if (!why) why = t.bad_set;
+    if (why) return fail(RFX_ERR_INVALID, std::string(who) + ": " + why);
   }
   return RFX_OK;
 }
@@ -340,20 +354,17 @@ struct GlCall {
   const float* S;
   const cf* angles0;
   const float* row_scale;  // null: the driver fills the table of its own workspace (gl_row_scale)
-  float hint, mom;
-  uint64_t seed, frame_base;
+  float mom;
+  uint64_t seed;
   int B, T, L, n_iter;
   float* out;
   char* ws;
-  size_t ws_bytes;
   hipStream_t stream;
-  const float* guide;  // null, or (B, guide_samples) rows guide_stride apart: launch 0 is MODE 1 on the staged guide (rfx_guide.hip)
-  int64_t guide_stride;
-  int guide_samples;
-  const int32_t* hold;  // null, or (B, 2) {head, tail}: launches 1 .. n_iter walk the free-frame list (rfx_guide_core.h) and leave the held
-                        // frames' synthesis frames as launch 0 wrote them
-  const uint32_t* mask;  // null, or (B, T, ceil(n_stft / 32)) held bins: launches 1 .. n_iter read S_free and every fold adds c = ISTFT(S_held a0)
-  bool loop;  // L = hop T is the row's period: launches that read audio read it modulo L, every fold is circular (rfx_loop_core.h)
+  // the call's extras.  guide: launch 0 is MODE 1 on the staged guide (rfx_guide.hip).  hold: launches 1 .. n_iter walk the
+  // free-frame list (rfx_guide_core.h) and leave the held frames' synthesis frames as launch 0 wrote them.  mask: launches
+  // 1 .. n_iter read S_free and every fold adds c = ISTFT(S_held a0).  loop: L = hop T is the row's period: launches that read
+  // audio read it modulo L, every fold is circular (rfx_loop_core.h)
+  CallOpt x;
 };
 // ... and the fields that all four argument blocks have
 template <class Args>
@@ -363,7 +374,7 @@ static void set_gl_args(Args& a, const GlCall& c) {
   a.row_scale = c.row_scale;
   a.mom = c.mom;
   a.seed = c.seed;
-  a.frame_base = c.frame_base;
+  a.frame_base = c.x.row_base * (uint64_t)c.T;
   a.B = c.B;
   a.T = c.T;
   a.L = c.L;
@@ -372,7 +383,7 @@ static void set_gl_args(Args& a, const GlCall& c) {
 // brings the table its SGD stage wrote.
 static int gl_row_scale(GlCall& c, size_t per_row, float* table) {
   if (c.row_scale) return RFX_OK;
-  RFX_HIP(launch_range_scale(c.S, per_row, c.B, c.hint, (unsigned*)(table + 2 * (size_t)c.B), nullptr, table, 1, 0, c.stream));
+  RFX_HIP(launch_range_scale(c.S, per_row, c.B, c.x.magnitude_hint, (unsigned*)(table + 2 * (size_t)c.B), nullptr, table, 1, 0, c.stream));
   c.row_scale = table;
   return RFX_OK;
 }
@@ -382,19 +393,17 @@ static int gl_row_scale(GlCall& c, size_t per_row, float* table) {
 // audio buffer of the call that launch 0 neither reads nor writes.  pre_scaled: the engine's kernels analyse their buffer as it is
 // (the fold applies row_scale[2 r]); the specialised engine's multiply by it, and the staged values are divided by it.
 static int gl_stage_guide(const GlCall& c, int Lpad, bool pre_scaled, float* peaks, float* dst, float* zero) {
-  RFX_HIP(launch_guide_stage(c.guide, c.guide_stride, c.guide_samples, c.B, c.L, Lpad, pre_scaled ? nullptr : c.row_scale, peaks, dst, zero, c.stream));
+  RFX_HIP(launch_guide_stage(c.x.guide, c.x.guide_stride, c.x.guide_samples, c.B, c.L, Lpad, pre_scaled ? nullptr : c.row_scale, peaks, dst, zero, c.stream));
   return RFX_OK;
 }
 
 // Generic engine and row family: a frame kernel, then the fold, per iteration.
 // mag_in_fam_slots (rfx_waveform_from_mel on a row-family plan): c.S already holds the family kernels' slot order [B*T][fsf] -
 // InverseMelScale wrote it that way - so the once-per-call re-ordering of the plain frames is left out
-static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots, LaunchTimer& timer) {
+static int gen_griffinlim(const rfx_plan* plan, GlCall& c, const GlLayout& w, bool mag_in_fam_slots, LaunchTimer& timer) {
   const GenGeom& g = plan->gg;
   const int B = c.B, T = c.T, L = c.L;
   const bool fam = plan->fam_ok;
-  const GenGlLayout w = gen_gl_layout(plan, B, T, c.loop ? kGlLoop : c.mask ? kGlMasked : c.hold ? kGlHeld : kGlPlain);
-  if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   float* frames = (float*)(c.ws + w.frames);
   float* gen[3];
   for (int i = 0; i < 3; ++i) gen[i] = (float*)(c.ws + w.audio) + (size_t)i * B * w.Lpad;
@@ -402,7 +411,7 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   const size_t per_row = (size_t)T * ((fam && mag_in_fam_slots) ? (size_t)plan->fam.fsf : (size_t)g.fs);
   if (int rc = gl_row_scale(c, per_row, (float*)(c.ws + w.row_scale))) return rc;
   // (a loop call keeps the hop-entry reciprocal circular envelope there)
-  if (c.loop) RFX_HIP(launch_loop_renv(plan->d_win, env, g.n_fft, g.win, g.hop, 1.f, c.stream));
+  if (c.x.loop) RFX_HIP(launch_loop_renv(plan->d_win, env, g.n_fft, g.win, g.hop, 1.f, c.stream));
   else RFX_HIP(launch_gen_env(plan->d_win, env, g, T, L, c.stream));
   // padded frame rows (gen_frame_layout): the kernels write the window samples only, the fold reads the padding as zeros
   if (g.fshift > 0) RFX_HIP(hipMemsetAsync(frames, 0, (size_t)B * T * g.fpitch * sizeof(float), c.stream));
@@ -412,12 +421,12 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   // so the kernels run their one-signal mode for every iteration (half the audio loads, same bits); it == 0 synthesises the
   // initial estimate from S * angles0 - or, guided, analyses the staged guide in gen[2] like any later launch (gen[1] is free until
   // the fold of launch 1: the staging's scratch)
-  if (c.guide)
+  if (c.x.guide)
     if (int rc = gl_stage_guide(c, w.Lpad, true, gen[1], gen[2], nullptr)) return rc;
   // held: nothing but the frame kernels writes `frames` from here on (the fold reads them), so what launch 0 writes for a held frame
   // is what every later fold reads
   int* list = (int*)(c.ws + w.list);
-  if (c.hold) RFX_HIP(launch_hold_list(c.hold, B, T, list, c.stream));
+  if (c.x.hold) RFX_HIP(launch_hold_list(c.x.hold, B, T, list, c.stream));
   FamGlArgs fa{};
   GenGlArgs ga{};
   int nblocks = 0;
@@ -451,13 +460,13 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
   // masked (rfx_holdmask_core.h): X = S_held, one more MODE 1 launch on the staged guide and its fold give c = ISTFT(S_held a0) in the
   // generations' units; launch 0 then runs on the full S as a guided call's does (the same bytes), and launches 1 .. n_iter on
   // X = S_free, every fold adding c before it stores x and forms d.  The split acts on the order the frame kernels read.
-  const bool masked = c.mask && c.n_iter > 0;
+  const bool masked = c.x.mask && c.n_iter > 0;
   float* X = (float*)(c.ws + w.xmag);
   float* cadd = (float*)(c.ws + w.cadd);
   const int x_layout = fam ? kHoldMaskTable : kHoldMaskPlain, x_stride = fam ? plan->fam.fsf : g.fs;
   auto set_S = [&](const float* S) { fa.S = ga.S = S; };
   if (masked) {
-    RFX_HIP(launch_holdmask_split(x_layout, c.S, X, c.mask, plan->d_fam_binof, B, T, x_stride, plan->n_stft, true, c.stream));
+    RFX_HIP(launch_holdmask_split(x_layout, c.S, X, c.x.mask, plan->d_fam_binof, B, T, x_stride, plan->n_stft, true, c.stream));
     set_S(X);
     RFX_HIP(fam         ? launch_fam_gl(1, fa, nblocks, c.stream)
             : plan->czt ? launch_czt_gl(1, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
@@ -466,23 +475,23 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
     set_S(c.S);
   }
   for (int it = 0; it <= c.n_iter; ++it) {
-    const int mode = it == 0 && !c.guide ? 0 : 1;
+    const int mode = it == 0 && !c.x.guide ? 0 : 1;
     if (masked && it == 1) {
-      RFX_HIP(launch_holdmask_split(x_layout, c.S, X, c.mask, plan->d_fam_binof, B, T, x_stride, plan->n_stft, false, c.stream));
+      RFX_HIP(launch_holdmask_split(x_layout, c.S, X, c.x.mask, plan->d_fam_binof, B, T, x_stride, plan->n_stft, false, c.stream));
       set_S(X);
     }
-    if (c.hold && it > 0)
+    if (c.x.hold && it > 0)
       RFX_HIP(fam         ? launch_fam_gl_list(fa, list, nblocks, c.stream)
               : plan->czt ? launch_czt_gl_list(ga, list, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
                           : launch_gen_gl_list(ga, list, plan->num_cus, c.stream));
-    else if (c.loop && mode == 1)  // (never a chirp-z plan: refused before the driver)
+    else if (c.x.loop && mode == 1)  // (never a chirp-z plan: refused before the driver)
       RFX_HIP(fam ? launch_fam_gl_loop(fa, nblocks, c.stream) : launch_gen_gl_loop(ga, plan->num_cus, c.stream));
     else
       RFX_HIP(fam         ? launch_fam_gl(mode, fa, nblocks, c.stream)
               : plan->czt ? launch_czt_gl(mode, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, c.stream)
                           : launch_gen_gl(mode, ga, plan->num_cus, c.stream));
     const bool last = it == c.n_iter;
-    if (c.loop)
+    if (c.x.loop)
       RFX_HIP(launch_gen_loop_fold(frames, env, last ? c.out : gen[it % 2], g, B, T, last ? (size_t)L : (size_t)w.Lpad, c.stream,
                                    it == 0 ? nullptr : gen[(it + 1) % 2], last ? nullptr : gen[2], c.mom, c.row_scale));
     else
@@ -496,23 +505,21 @@ static int gen_griffinlim(const rfx_plan* plan, GlCall& c, bool mag_in_fam_slots
 }
 
 // Specialised engine: the per-frame form (frame kernel + fold per iteration) or the run form (one kernel per iteration)
-static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) {
+static int spec_griffinlim(const rfx_plan* plan, GlCall& c, const GlLayout& w, LaunchTimer& timer) {
   const int B = c.B, T = c.T, L = c.L;
-  const GlLayout w = gl_layout(plan, B, T, c.loop ? kGlLoop : c.mask ? kGlMasked : c.hold ? kGlHeld : kGlPlain);
-  if (c.ws_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   float* gen[3][2];  // x_k lives in generation k % 3
   for (int i = 0; i < 3; ++i)
     for (int p = 0; p < 2; ++p) gen[i][p] = (float*)(c.ws + w.audio) + (size_t)(2 * i + p) * B * w.Lpad;
   float* scale = (float*)(c.ws + w.scale);
   // (a loop call keeps the hop-entry table (2 / N) / env of the circular envelope there)
-  if (c.loop) RFX_HIP(launch_loop_renv(plan->d_win, scale, kNfft, kWin, kHop, 2.0f / (float)kNfft, c.stream));
+  if (c.x.loop) RFX_HIP(launch_loop_renv(plan->d_win, scale, kNfft, kWin, kHop, 2.0f / (float)kNfft, c.stream));
   else {
     hipLaunchKernelGGL(out_scale_kernel, dim3((L + 255) / 256), dim3(256), 0, c.stream, plan->d_win, scale, T, L);
     RFX_HIP(hipGetLastError());
   }
   if (int rc = gl_row_scale(c, (size_t)T * kFrameStride, (float*)(c.ws + w.row_scale))) return rc;
 
-  if (c.hold || c.mask || c.loop || gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
+  if (c.x.kind() != kGlPlain || gl_use_latency_mode(plan, B, T)) {  // one folded buffer per generation: gen[k][0]
     GlFrameArgs fa;
     set_gl_args(fa, c);
     fa.frames = (float*)(c.ws + w.frames);
@@ -523,17 +530,17 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
     const int nblocks = frame_blocks(gl_slot_count(plan), B, T);
     RFX_HIP(timer.begin(c.stream));
     // guided: launch 0 is MODE 1 on the guide, staged where it reads its input (gen[2][0]; gen[1][0] is free until launch 1's fold)
-    if (c.guide)
+    if (c.x.guide)
       if (int rc = gl_stage_guide(c, w.Lpad, false, gen[1][0], gen[2][0], nullptr)) return rc;
     // held: only the frame kernel writes fa.frames; launches 1 .. n_iter skip the held frames, whose entries stay launch 0's
     int* list = (int*)(c.ws + w.list);
-    if (c.hold) RFX_HIP(launch_hold_list(c.hold, B, T, list, c.stream));
+    if (c.x.hold) RFX_HIP(launch_hold_list(c.x.hold, B, T, list, c.stream));
     // masked: as in gen_griffinlim - c from X = S_held and the staged guide, launch 0 on S, launches 1 .. n_iter on X = S_free, + c in every fold
-    const bool masked = c.mask && c.n_iter > 0;
+    const bool masked = c.x.mask && c.n_iter > 0;
     float* X = (float*)(c.ws + w.xmag);
     float* cadd = (float*)(c.ws + w.cadd);
     if (masked) {
-      RFX_HIP(launch_holdmask_split(kHoldMaskSpec, c.S, X, c.mask, nullptr, B, T, kFrameStride, kBins, true, c.stream));
+      RFX_HIP(launch_holdmask_split(kHoldMaskSpec, c.S, X, c.x.mask, nullptr, B, T, kFrameStride, kBins, true, c.stream));
       fa.S = X;
       fa.audio_in = gen[2][0];
       fa.audio_prev = gen[1][0];
@@ -543,17 +550,17 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
     }
     for (int it = 0; it <= c.n_iter; ++it) {
       if (masked && it == 1) {
-        RFX_HIP(launch_holdmask_split(kHoldMaskSpec, c.S, X, c.mask, nullptr, B, T, kFrameStride, kBins, false, c.stream));
+        RFX_HIP(launch_holdmask_split(kHoldMaskSpec, c.S, X, c.x.mask, nullptr, B, T, kFrameStride, kBins, false, c.stream));
         fa.S = X;
       }
       fa.audio_in = gen[(it + 2) % 3][0];    // x_{it-1}
       fa.audio_prev = gen[(it + 1) % 3][0];  // x_{it-2}
-      const int mode = it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2;
-      if (c.hold && it > 0) RFX_HIP(launch_gl_frame_list(it == 1 ? 1 : 2, fa, list, nblocks, c.stream));
-      else if (c.loop && mode != 0) RFX_HIP(launch_gl_frame_loop(mode, fa, nblocks, c.stream));
+      const int mode = it == 0 ? (c.x.guide ? 1 : 0) : it == 1 ? 1 : 2;
+      if (c.x.hold && it > 0) RFX_HIP(launch_gl_frame_list(it == 1 ? 1 : 2, fa, list, nblocks, c.stream));
+      else if (c.x.loop && mode != 0) RFX_HIP(launch_gl_frame_loop(mode, fa, nblocks, c.stream));
       else RFX_HIP(launch_gl_frame(mode, fa, nblocks, c.stream));
       const bool last = it == c.n_iter;
-      if (c.loop)
+      if (c.x.loop)
         RFX_HIP(launch_gl_loop_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, last ? (size_t)L : (size_t)w.Lpad, c.stream));
       else
         RFX_HIP(launch_gl_fold(fa.frames, plan->d_win, scale, last ? c.out : gen[it % 3][0], B, T, L, last ? (size_t)L : (size_t)w.Lpad, c.stream,
@@ -587,7 +594,7 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
   RFX_HIP(timer.begin(c.stream));
   // guided: launch 0 is MODE 1 on the guide, staged as the generation it reads (buffer 0 the guide, buffer 1 zeros: the kernel adds
   // the two around its run boundaries); generation 2 is free until launch 2 writes it
-  if (c.guide)
+  if (c.x.guide)
     if (int rc = gl_stage_guide(c, w.Lpad, false, gen[2][0], gen[1][0], gen[1][1])) return rc;
   for (int it = 0; it <= c.n_iter; ++it) {
     // iteration `it` analyses x_{it-1} - m*x_{it-2} and writes x_it; MODE 0 reads nothing and writes x_0
@@ -596,7 +603,7 @@ static int spec_griffinlim(const rfx_plan* plan, GlCall& c, LaunchTimer& timer) 
 #ifdef RFX_WGCLOCK
     g.launch = it;
 #endif
-    RFX_HIP(launch_gl_iter(it == 0 ? (c.guide ? 1 : 0) : it == 1 ? 1 : 2, g, part.runs, c.stream));
+    RFX_HIP(launch_gl_iter(it == 0 ? (c.x.guide ? 1 : 0) : it == 1 ? 1 : 2, g, part.runs, c.stream));
     RFX_HIP(timer.mark(it, c.stream));
   }
   const int last = c.n_iter % 3;
@@ -654,26 +661,21 @@ static int griffinlim_impl(const rfx_plan* plan, const float* d_mag_slots, const
   const int L = gl_out_samples(plan, T, opt.loop);
   if (!opt.loop && n_iter > 0 && L <= plan->p.n_fft / 2) return reflect_refusal(plan);
   if (int rc = guide_refusal(plan, opt, T, d_angles0_slots != nullptr, "rfx_griffinlim")) return rc;
-  size_t gl_bytes = 0;
-  if (opt.peak) {
-    if (d_angles0_slots) return fail(RFX_ERR_INVALID, "rfx_griffinlim: start == 1 and d_angles0_slots are two starts: give one");
+  if (opt.peak)
     if (int rc = peak_refusal(plan, "rfx_griffinlim")) return rc;
-    gl_bytes = griffinlim_workspace(plan, B, T, opt.kind());
-    if (workspace_bytes < with_peak(plan, gl_bytes, B, T)) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
-  }
+  const GlLayout w = griffinlim_layout(plan, B, T, opt.kind(), opt.peak);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_griffinlim: workspace too small");
   RFX_ON_DEVICE(plan->device);
-  GlCall c{d_mag_slots, (const cf*)d_angles0_slots, d_row_scale, opt.magnitude_hint, momentum / (1.f + momentum), seed,
-           opt.row_base * (uint64_t)T, B, T, L, n_iter, d_wave_out, (char*)d_workspace, workspace_bytes, (hipStream_t)stream,
-           opt.guide, opt.guide_stride, opt.guide_samples, opt.hold, opt.mask, opt.loop};
+  GlCall c{d_mag_slots, (const cf*)d_angles0_slots, d_row_scale, momentum / (1.f + momentum), seed, B, T, L, n_iter, d_wave_out,
+           (char*)d_workspace, (hipStream_t)stream, opt};
   LaunchTimer timer(h_launch_ms, n_iter + 1);
-  if (opt.peak) {  // rfx_peak_start into the angles behind the call's own workspace, then the call with those angles injected
+  if (opt.peak) {  // rfx_peak_start into the angles of the call's workspace, then the call with those angles injected
     RFX_HIP(timer.begin(c.stream));
-    char* angles = c.ws + gl_bytes;
     const int layout = !plan->generic ? kHoldMaskSpec : plan->fam_ok && mag_in_fam_slots ? kHoldMaskTable : kHoldMaskPlain;
-    if (int rc = peak_start_run(plan, layout, c.S, B, T, angles, angles + peak_angles_bytes(plan, B, T), c.stream)) return rc;
-    c.angles0 = (const cf*)angles;
+    if (int rc = peak_start_run(plan, layout, c.S, B, T, c.ws + w.angles, c.ws + w.peak_scratch, c.stream)) return rc;
+    c.angles0 = (const cf*)(c.ws + w.angles);
   }
-  return plan->generic ? gen_griffinlim(plan, c, mag_in_fam_slots, timer) : spec_griffinlim(plan, c, timer);
+  return plan->generic ? gen_griffinlim(plan, c, w, mag_in_fam_slots, timer) : spec_griffinlim(plan, c, w, timer);
 }
 
 int rfx_griffinlim(const rfx_plan* plan, const float* d_mag_slots, const void* d_angles0_slots, uint64_t seed, int B,
@@ -861,9 +863,9 @@ struct WaveFromMelLayout {
   size_t lin, row_scale, rest, total;
   bool fam_slots;
 };
-static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, int T, GlKind kind = kGlPlain) {
+static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, int T, GlKind kind, bool peak) {
   WaveFromMelLayout l{};
-  const size_t imel = rfx_inverse_mel_workspace_bytes(plan, B, T), gl = griffinlim_workspace(plan, B, T, kind);
+  const size_t imel = rfx_inverse_mel_workspace_bytes(plan, B, T), gl = griffinlim_layout(plan, B, T, kind, false).total;
   if (!imel || !gl) return l;
   const size_t lstsq = inverse_mel_lstsq_layout(plan, B, T).total;
   l.fam_slots = imel_can_emit_fam_slots(plan);
@@ -873,17 +875,10 @@ static WaveFromMelLayout waveform_from_mel_layout(const rfx_plan* plan, int B, i
   l.lin = c.take((size_t)B * T * per_frame * sizeof(float));
   l.row_scale = c.take(range_table_bytes(B));
   l.rest = c.at;
-  l.total = l.rest + std::max(std::max(imel, gl), lstsq);
+  // (the peak start's angles and scratch lie behind the Griffin-Lim stage's own bytes; the call brings them on top of the largest stage)
+  l.total = l.rest + std::max(std::max(imel, gl), lstsq) + (peak ? peak_extra_bytes(plan, B, T) : 0);
   return l;
 }
-size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T).total : 0; }
-size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlHeld).total : 0; }
-size_t rfx_waveform_from_mel_masked_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlMasked).total : 0; }
-size_t rfx_waveform_from_mel_loop_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? waveform_from_mel_layout(plan, B, T, kGlLoop).total : 0; }
-size_t rfx_waveform_from_mel_peak_workspace_bytes(const rfx_plan* plan, int B, int T) {
-  return plan ? with_peak(plan, waveform_from_mel_layout(plan, B, T).total, B, T) : 0;
-}
-
 static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                                  float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream, const CallOpt& opt) {
   if (plan)
@@ -892,11 +887,11 @@ static int waveform_from_mel_impl(const rfx_plan* plan, const float* d_mel, int 
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_waveform_from_mel")) return rc;
   if (int rc = guide_refusal(plan, opt, T, false, "rfx_waveform_from_mel")) return rc;
-  const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T, opt.kind());
+  const WaveFromMelLayout w = waveform_from_mel_layout(plan, B, T, opt.kind(), opt.peak);
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_waveform_from_mel: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   if (opt.peak)
     if (int rc = peak_refusal(plan, "rfx_waveform_from_mel")) return rc;
-  if (workspace_bytes < (opt.peak ? with_peak(plan, w.total, B, T) : w.total)) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_waveform_from_mel: workspace too small");
   char* ws = (char*)d_workspace;
   float* lin = reinterpret_cast<float*>(ws + w.lin);
   float* row_scale = reinterpret_cast<float*>(ws + w.row_scale);
@@ -929,11 +924,11 @@ int rfx_waveform_from_mel_ex(const rfx_plan* plan, const float* d_mel, int B, in
 struct AudioFromImageLayout {
   size_t mel, wave, rest, total;
 };
-static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N, int stereo, int T, GlKind kind = kGlPlain) {
+static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N, int stereo, int T, GlKind kind, bool peak) {
   AudioFromImageLayout l{};
   if (N <= 0 || T <= 0) return l;
   const int B = N * (stereo ? 2 : 1);
-  const size_t inner = waveform_from_mel_layout(plan, B, T, kind).total;
+  const size_t inner = waveform_from_mel_layout(plan, B, T, kind, peak).total;
   if (!inner) return l;
   Carve c;
   l.mel = c.take((size_t)B * plan->p.n_mels * T * sizeof(float));
@@ -942,21 +937,36 @@ static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N,
   l.total = l.rest + inner;
   return l;
 }
-size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
-  return plan ? audio_from_image_layout(plan, N, stereo, T).total : 0;
+// The workspace queries of the three entries: one sizing function, and the exported names (the ABI) as calls of it with constants.
+// rows: B, or N images of 1 + stereo rows
+enum Entry { kEntryGriffinLim, kEntryWaveformFromMel, kEntryAudioFromImage };
+static size_t inverse_workspace(const rfx_plan* plan, Entry entry, int rows, int stereo, int T, GlKind kind, bool peak) {
+  if (!plan) return 0;
+  return entry == kEntryGriffinLim        ? griffinlim_layout(plan, rows, T, kind, peak).total
+         : entry == kEntryWaveformFromMel ? waveform_from_mel_layout(plan, rows, T, kind, peak).total
+                                          : audio_from_image_layout(plan, rows, stereo, T, kind, peak).total;
 }
-size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
-  return plan ? audio_from_image_layout(plan, N, stereo, T, kGlHeld).total : 0;
-}
-size_t rfx_audio_from_image_masked_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
-  return plan ? audio_from_image_layout(plan, N, stereo, T, kGlMasked).total : 0;
-}
-size_t rfx_audio_from_image_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
-  return plan ? audio_from_image_layout(plan, N, stereo, T, kGlLoop).total : 0;
-}
-size_t rfx_audio_from_image_peak_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
-  return plan ? with_peak(plan, audio_from_image_layout(plan, N, stereo, T).total, N * (stereo ? 2 : 1), T) : 0;
-}
+#define RFX_QUERY(entry, name, kind, peak) \
+  size_t name(const rfx_plan* plan, int B, int T) { return inverse_workspace(plan, entry, B, 0, T, kind, peak); }
+#define RFX_IMAGE_QUERY(name, kind, peak) \
+  size_t name(const rfx_plan* plan, int N, int stereo, int T) { return inverse_workspace(plan, kEntryAudioFromImage, N, stereo, T, kind, peak); }
+RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_workspace_bytes, kGlPlain, false)
+RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_held_workspace_bytes, kGlHeld, false)
+RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_masked_workspace_bytes, kGlMasked, false)
+RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_loop_workspace_bytes, kGlLoop, false)
+RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_peak_workspace_bytes, kGlPlain, true)
+RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_workspace_bytes, kGlPlain, false)
+RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_held_workspace_bytes, kGlHeld, false)
+RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_masked_workspace_bytes, kGlMasked, false)
+RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_loop_workspace_bytes, kGlLoop, false)
+RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_peak_workspace_bytes, kGlPlain, true)
+RFX_IMAGE_QUERY(rfx_audio_from_image_workspace_bytes, kGlPlain, false)
+RFX_IMAGE_QUERY(rfx_audio_from_image_held_workspace_bytes, kGlHeld, false)
+RFX_IMAGE_QUERY(rfx_audio_from_image_masked_workspace_bytes, kGlMasked, false)
+RFX_IMAGE_QUERY(rfx_audio_from_image_loop_workspace_bytes, kGlLoop, false)
+RFX_IMAGE_QUERY(rfx_audio_from_image_peak_workspace_bytes, kGlPlain, true)
+#undef RFX_QUERY
+#undef RFX_IMAGE_QUERY
 
 static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                                 int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
@@ -968,12 +978,12 @@ static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int
   if (opt.lstsq)
     if (int rc = lstsq_refusal(plan, "rfx_audio_from_image_u8")) return rc;
   if (int rc = guide_refusal(plan, opt, T, false, "rfx_audio_from_image_u8")) return rc;
-  const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T, opt.kind());
+  const AudioFromImageLayout w = audio_from_image_layout(plan, N, stereo, T, opt.kind(), opt.peak);
   if (!w.total) return fail(RFX_ERR_UNSUPPORTED, "rfx_audio_from_image_u8: this plan cannot invert (see rfx_inverse_mel / rfx_griffinlim)");
   const int C = stereo ? 2 : 1, B = N * C;
   if (opt.peak)
     if (int rc = peak_refusal(plan, "rfx_audio_from_image_u8")) return rc;
-  if (workspace_bytes < (opt.peak ? with_peak(plan, w.total, B, T) : w.total)) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_audio_from_image_u8: workspace too small");
   const int M = plan->p.n_mels, L = gl_out_samples(plan, T, opt.loop);
   char* ws = (char*)d_workspace;
   float* mel = reinterpret_cast<float*>(ws + w.mel);

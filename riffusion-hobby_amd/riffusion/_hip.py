@@ -9,7 +9,9 @@ there is no CPU fallback anywhere in this package.
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
+import functools
 import math
 import os
 import threading
@@ -93,33 +95,11 @@ CALL_INVERSE_MEL_LSTSQ = 1  # RFX_CALL_INVERSE_MEL_LSTSQ
 INVERSE_MEL_FORMS = ("sgd", "lstsq")  # the `inverse_mel` keyword of the converters
 
 
-def call_options(row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False) -> RfxCallOptions:
-    """`lstsq`: the fused inverse calls run the closed-form InverseMelScale (rfx_inverse_mel_lstsq) in place of the SGD."""
-    if row_base < 0:
-        raise ValueError("row_base must be >= 0")
-    return RfxCallOptions(ctypes.sizeof(RfxCallOptions), CALL_INVERSE_MEL_LSTSQ if lstsq else 0, int(row_base), float(magnitude_hint), 0.0)
-
-
 class RfxGuidedCallOptions(ctypes.Structure):
     """rfx_guided_call_options of include/rfx.h: rfx_call_options grown at its tail by the guide of a phase-guided Griffin-Lim start."""
 
     _fields_ = RfxCallOptions._fields_ + [("d_guide", ctypes.c_void_p), ("guide_stride", ctypes.c_int64),
                                           ("guide_samples", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
-
-
-def guided_call_options(guide: T.Optional[torch.Tensor], rows: int, row_base: int = 0, magnitude_hint: float = 0.0,
-                        lstsq: bool = False) -> T.Union[RfxCallOptions, RfxGuidedCallOptions]:
-    """`call_options`, with the guide of a guided call: a (rows, Lg) float32 device tensor whose samples are contiguous (rows may be
-    strided); None gives the plain options.  The caller keeps `guide` alive until the call is issued."""
-    o = call_options(row_base, magnitude_hint, lstsq)
-    if guide is None:
-        return o
-    if guide.dtype != torch.float32 or guide.dim() != 2 or guide.shape[0] != rows or guide.shape[1] < 1:
-        raise ValueError(f"guide must be a ({rows}, Lg) float32 tensor with Lg >= 1, got {tuple(guide.shape)} {guide.dtype}")
-    if guide.stride(1) != 1 or (rows > 1 and guide.stride(0) < guide.shape[1]):
-        raise ValueError("guide rows must be contiguous runs of samples that do not overlap")
-    return RfxGuidedCallOptions(ctypes.sizeof(RfxGuidedCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, guide.data_ptr(),
-                                guide.stride(0) if rows > 1 else guide.shape[1], guide.shape[1], 0)
 
 
 class RfxHeldCallOptions(ctypes.Structure):
@@ -128,50 +108,10 @@ class RfxHeldCallOptions(ctypes.Structure):
     _fields_ = RfxGuidedCallOptions._fields_ + [("d_hold_frames", ctypes.c_void_p), ("reserved3", ctypes.c_uint64)]
 
 
-def held_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], rows: int, row_base: int = 0,
-                      magnitude_hint: float = 0.0, lstsq: bool = False):
-    """`guided_call_options`, with the held frames of a held call: `hold` a contiguous (rows, 2) int32 tensor of {head, tail} on the
-    guide's device; None gives the guided (or plain) options.  The caller keeps both tensors alive until the call is issued."""
-    o = guided_call_options(guide, rows, row_base, magnitude_hint, lstsq)
-    if hold is None:
-        return o
-    if guide is None:
-        raise ValueError("hold needs a guide: the frames are held at the guide's phase")
-    if hold.dtype != torch.int32 or tuple(hold.shape) != (rows, 2) or not hold.is_contiguous():
-        raise ValueError(f"hold must be a contiguous ({rows}, 2) int32 tensor of (head, tail) frames, got {tuple(hold.shape)} {hold.dtype}")
-    if hold.device != guide.device:
-        raise ValueError(f"hold on {hold.device}, guide on {guide.device}")
-    return RfxHeldCallOptions(ctypes.sizeof(RfxHeldCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, o.d_guide, o.guide_stride,
-                              o.guide_samples, 0, hold.data_ptr(), 0)
-
-
-_MASK_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)  # a bit mask's words
-
-
 class RfxMaskedCallOptions(ctypes.Structure):
     """rfx_masked_call_options of include/rfx.h: rfx_held_call_options grown at its tail by the bins a guided call holds."""
 
     _fields_ = RfxHeldCallOptions._fields_ + [("d_hold_bins", ctypes.c_void_p), ("hold_words", ctypes.c_int32), ("reserved4", ctypes.c_int32)]
-
-
-def masked_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
-                        row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False):
-    """`held_call_options`, with the held bins of a masked call: `hold_bins` a contiguous (rows, T, words) int32 (or uint32) tensor on
-    the guide's device, bin b of a frame held iff bit b & 31 of word b >> 5 is set; None gives the held (or guided, or plain)
-    options.  The caller keeps the tensors alive until the call is issued."""
-    o = held_call_options(guide, hold, rows, row_base, magnitude_hint, lstsq)
-    if hold_bins is None:
-        return o
-    if guide is None:
-        raise ValueError("hold_bins needs a guide: the bins are held at the guide's phase")
-    if hold is not None:
-        raise ValueError("hold_bins together with hold is not served: set the held frames' bits in the mask")
-    if hold_bins.dtype not in _MASK_DTYPES or hold_bins.dim() != 3 or hold_bins.shape[0] != rows or not hold_bins.is_contiguous():
-        raise ValueError(f"hold_bins must be a contiguous ({rows}, T, words) int32 tensor of bit masks, got {tuple(hold_bins.shape)} {hold_bins.dtype}")
-    if hold_bins.device != guide.device:
-        raise ValueError(f"hold_bins on {hold_bins.device}, guide on {guide.device}")
-    return RfxMaskedCallOptions(ctypes.sizeof(RfxMaskedCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, o.d_guide, o.guide_stride,
-                                o.guide_samples, 0, None, 0, hold_bins.data_ptr(), int(hold_bins.shape[2]), 0)
 
 
 class RfxLoopCallOptions(ctypes.Structure):
@@ -180,41 +120,124 @@ class RfxLoopCallOptions(ctypes.Structure):
     _fields_ = RfxMaskedCallOptions._fields_ + [("loop", ctypes.c_uint32), ("reserved5", ctypes.c_uint32)]
 
 
-def loop_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
-                      row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, loop: bool = False):
-    """`masked_call_options`, with the loop switch of a loop call (the row's columns are one period: a clip's end runs into its
-    start); loop=False gives the masked (or held, guided, plain) options.  A loop holds nothing: `hold` and `hold_bins` must be None."""
-    if not loop:
-        return masked_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq)
-    if hold is not None or hold_bins is not None:
-        raise ValueError("loop together with hold or hold_bins is not served")
-    o = guided_call_options(guide, rows, row_base, magnitude_hint, lstsq)
-    g = o if guide is not None else None
-    return RfxLoopCallOptions(ctypes.sizeof(RfxLoopCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, g.d_guide if g else None,
-                              g.guide_stride if g else 0, g.guide_samples if g else 0, 0, None, 0, None, 0, 0, 1, 0)
-
-
 class RfxStartCallOptions(ctypes.Structure):
     """rfx_start_call_options of include/rfx.h: rfx_loop_call_options grown at its tail by the choice of Griffin-Lim's start."""
 
     _fields_ = RfxLoopCallOptions._fields_ + [("start", ctypes.c_uint32), ("reserved6", ctypes.c_uint32)]
 
 
+def check_call_rules(wording: T.Mapping[str, T.Any], *only: str, loop: bool = False, peak_start: bool = False, **extras: T.Any) -> None:
+    """The combination rules of a Griffin-Lim call's extras, stated once for every Python layer (the library states them for the C
+    ABI: rule_refusal of csrc/rfx_api_inverse.hip).  `extras`: the caller's other starts and holds under its own argument names,
+    None when not given.  `wording`: the layer's message for each rule it checks (`{given}`: the names of the extras given);
+    under "roles", what the layer's names mean where they are not the library's own `angles0`, `guide`, `hold`, `hold_bins`.
+    `only`: the rules to check now, for a layer that has checks of its own between them (default: all of `wording`, in its order).
+    ValueError with the first broken rule's message."""
+    roles = wording.get("roles", {})
+    given = [name for name, value in extras.items() if value is not None]
+    if not given:  # (every rule is about an extra)
+        return
+    has = {roles.get(name, name) for name in given}
+    broken = {
+        "peak_start": peak_start,                                  # the peak start is a start of its own and holds nothing
+        "peak_and_guide": peak_start and "guide" in has,           # (the layers that know no other extra a peak start could meet)
+        "loop_holds": loop and bool(has & {"hold", "hold_bins"}),  # a loop holds nothing
+        "two_starts": {"guide", "angles0"} <= has,                 # a guide and injected angles are two starts
+        "hold_needs_guide": "hold" in has and "guide" not in has,  # frames and bins are held at a guide's phase
+        "bins_need_guide": "hold_bins" in has and "guide" not in has,
+        "bins_and_hold": {"hold", "hold_bins"} <= has,             # a mask and held frames exclude each other
+    }
+    for rule in only or [rule for rule in wording if rule != "roles"]:
+        if broken[rule]:
+            raise ValueError(wording[rule].format(given=", ".join(given)))
+
+
+_HOLD_WORDING = {"hold_needs_guide": "hold needs a guide: the frames are held at the guide's phase",
+                 "bins_need_guide": "hold_bins needs a guide: the bins are held at the guide's phase",
+                 "bins_and_hold": "hold_bins together with hold is not served: set the held frames' bits in the mask"}
+BUILDER_WORDING = {"peak_start": "peak_start together with guide, hold or hold_bins is not served: each is a start, or needs the guide's",
+                   "loop_holds": "loop together with hold or hold_bins is not served", **_HOLD_WORDING}
+PLAN_WORDING = {"roles": {"angles0_slots": "angles0"}, "loop_holds": BUILDER_WORDING["loop_holds"],
+                "peak_start": "peak_start does not go with {given}: the peak start needs no guide and holds nothing",
+                "two_starts": "a guide and angles0_slots are two starts: give one", **_HOLD_WORDING}
+
+_MASK_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)  # a bit mask's words
+
+
 def start_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
                        row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, loop: bool = False, peak_start: bool = False):
-    """`loop_call_options`, with the spectral-peak start (Griffin-Lim starts from phases built from the call's magnitudes, no
-    randomness and no guide); peak_start=False gives the loop (or masked, held, guided, plain) options.  The peak start is a start of
-    its own: `guide`, `hold` and `hold_bins` must be None."""
-    if not peak_start:
-        return loop_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq, loop)
-    if guide is not None or hold is not None or hold_bins is not None:
-        raise ValueError("peak_start together with guide, hold or hold_bins is not served: each is a start, or needs the guide's")
-    o = call_options(row_base, magnitude_hint, lstsq)
-    return RfxStartCallOptions(ctypes.sizeof(RfxStartCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0, None, 0, 0, 0, None, 0, None, 0, 0,
-                               1 if loop else 0, 0, 1, 0)
+    """The options of an inverse call, as the shortest of the structs above that holds what is given (the library reads a struct by
+    its size): RfxCallOptions for none of the extras, RfxGuidedCallOptions for a guide alone, and so on.
+    `lstsq`: the fused inverse calls run the closed-form InverseMelScale (rfx_inverse_mel_lstsq) in place of the SGD.
+    `guide`: a (rows, Lg) float32 device tensor whose samples are contiguous (rows may be strided).  `hold`: a contiguous (rows, 2)
+    int32 tensor of {head, tail} on the guide's device.  `hold_bins`: a contiguous (rows, T, words) int32 (or uint32) tensor on the
+    guide's device, bin b of a frame held iff bit b & 31 of word b >> 5 is set.  `loop`: the row's columns are one period (a clip's
+    end runs into its start).  `peak_start`: Griffin-Lim starts from phases built from the call's magnitudes.  Which of them go
+    together: `check_call_rules`.  The caller keeps the tensors alive until the call is issued."""
+    rules = functools.partial(check_call_rules, BUILDER_WORDING, loop=loop, peak_start=peak_start, guide=guide, hold=hold, hold_bins=hold_bins)
+    rules("peak_start", "loop_holds")
+    if row_base < 0:
+        raise ValueError("row_base must be >= 0")
+    cls: T.Any = RfxCallOptions
+    fields: T.Dict[str, T.Any] = dict(flags=CALL_INVERSE_MEL_LSTSQ if lstsq else 0, row_base=int(row_base), magnitude_hint=float(magnitude_hint))
+    if guide is not None:
+        if guide.dtype != torch.float32 or guide.dim() != 2 or guide.shape[0] != rows or guide.shape[1] < 1:
+            raise ValueError(f"guide must be a ({rows}, Lg) float32 tensor with Lg >= 1, got {tuple(guide.shape)} {guide.dtype}")
+        if guide.stride(1) != 1 or (rows > 1 and guide.stride(0) < guide.shape[1]):
+            raise ValueError("guide rows must be contiguous runs of samples that do not overlap")
+        cls = RfxGuidedCallOptions
+        fields.update(d_guide=guide.data_ptr(), guide_stride=guide.stride(0) if rows > 1 else guide.shape[1], guide_samples=guide.shape[1])
+    if hold is not None:
+        rules("hold_needs_guide")
+        if hold.dtype != torch.int32 or tuple(hold.shape) != (rows, 2) or not hold.is_contiguous():
+            raise ValueError(f"hold must be a contiguous ({rows}, 2) int32 tensor of (head, tail) frames, got {tuple(hold.shape)} {hold.dtype}")
+        if hold.device != guide.device:
+            raise ValueError(f"hold on {hold.device}, guide on {guide.device}")
+        cls = RfxHeldCallOptions
+        fields.update(d_hold_frames=hold.data_ptr())
+    if hold_bins is not None:
+        rules("bins_need_guide", "bins_and_hold")
+        if hold_bins.dtype not in _MASK_DTYPES or hold_bins.dim() != 3 or hold_bins.shape[0] != rows or not hold_bins.is_contiguous():
+            raise ValueError(f"hold_bins must be a contiguous ({rows}, T, words) int32 tensor of bit masks, got {tuple(hold_bins.shape)} {hold_bins.dtype}")
+        if hold_bins.device != guide.device:
+            raise ValueError(f"hold_bins on {hold_bins.device}, guide on {guide.device}")
+        cls = RfxMaskedCallOptions
+        fields.update(d_hold_bins=hold_bins.data_ptr(), hold_words=int(hold_bins.shape[2]))
+    if loop:
+        cls = RfxLoopCallOptions
+        fields.update(loop=1)
+    if peak_start:
+        cls = RfxStartCallOptions
+        fields.update(start=1)
+    return cls(struct_size=ctypes.sizeof(cls), **fields)
+
+
+# the builder's earlier names, each for the extras that existed when it was added
+def call_options(row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False) -> RfxCallOptions:
+    return start_call_options(None, None, None, 0, row_base, magnitude_hint, lstsq)
+
+
+def guided_call_options(guide: T.Optional[torch.Tensor], rows: int, row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False):
+    return start_call_options(guide, None, None, rows, row_base, magnitude_hint, lstsq)
+
+
+def held_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], rows: int, row_base: int = 0,
+                      magnitude_hint: float = 0.0, lstsq: bool = False):
+    return start_call_options(guide, hold, None, rows, row_base, magnitude_hint, lstsq)
+
+
+def masked_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
+                        row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False):
+    return start_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq)
+
+
+def loop_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
+                      row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, loop: bool = False):
+    return start_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq, loop)
 
 
 PHASE_STARTS = ("random", "peaks")
+PEAKS_WORDING = 'phase_start="peaks" does not go with {given}: the peak start needs no guide and holds nothing'
 
 
 def check_phase_start(phase_start: str, **others: T.Any) -> bool:
@@ -222,10 +245,7 @@ def check_phase_start(phase_start: str, **others: T.Any) -> bool:
     (`others`: the caller's angles0 / guide / hold arguments by name, None when not given)"""
     if phase_start not in PHASE_STARTS:
         raise ValueError(f'phase_start must be one of {PHASE_STARTS}, got {phase_start!r}')
-    if phase_start == "peaks":
-        given = [name for name, v in others.items() if v is not None]
-        if given:
-            raise ValueError(f'phase_start="peaks" does not go with {", ".join(given)}: the peak start needs no guide and holds nothing')
+    check_call_rules({"peak_start": PEAKS_WORDING}, peak_start=phase_start == "peaks", **others)
     return phase_start == "peaks"
 
 
@@ -719,23 +739,16 @@ class Plan:
         ok = guide.stride(1) == 1 and (guide.shape[0] == 1 or guide.stride(0) >= guide.shape[1])
         return guide if ok else guide.contiguous()
 
-    def _chk_hold(self, hold: torch.Tensor, guide: T.Optional[torch.Tensor], rows: int) -> torch.Tensor:
-        """held frames as the library reads them: a contiguous (rows, 2) int32 tensor on the plan's device; they need a guide"""
-        if guide is None:
-            raise ValueError("hold needs a guide: the frames are held at the guide's phase")
+    def _chk_hold(self, hold: torch.Tensor, rows: int) -> torch.Tensor:
+        """held frames as the library reads them: a contiguous (rows, 2) int32 tensor on the plan's device"""
         if hold.device != self.device:
             raise ValueError(f"tensor on {hold.device}, plan on {self.device}")
         if hold.dtype != torch.int32 or tuple(hold.shape) != (rows, 2):
             raise ValueError(f"hold must be a ({rows}, 2) int32 tensor of (head, tail) frames, got {tuple(hold.shape)} {hold.dtype}")
         return hold.contiguous()
 
-    def _chk_hold_bins(self, hold_bins: torch.Tensor, guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], rows: int, Tn: int) -> torch.Tensor:
-        """held bins as the library reads them: a contiguous (rows, Tn, hold_mask_words) int32 tensor of bit masks on the plan's device;
-        they need a guide and exclude `hold`"""
-        if guide is None:
-            raise ValueError("hold_bins needs a guide: the bins are held at the guide's phase")
-        if hold is not None:
-            raise ValueError("hold_bins together with hold is not served: set the held frames' bits in the mask")
+    def _chk_hold_bins(self, hold_bins: torch.Tensor, rows: int, Tn: int) -> torch.Tensor:
+        """held bins as the library reads them: a contiguous (rows, Tn, hold_mask_words) int32 tensor of bit masks on the plan's device"""
         if hold_bins.device != self.device:
             raise ValueError(f"tensor on {hold_bins.device}, plan on {self.device}")
         want = (rows, Tn, self.hold_mask_words)
@@ -815,34 +828,52 @@ class Plan:
         """samples per row of a Griffin-Lim call of Tn frames: hop * (Tn - 1) (+ 1 for an odd n_fft), or the period hop * Tn of a loop call"""
         return (self.lib.rfx_griffinlim_loop_output_samples if loop else self.lib.rfx_griffinlim_output_samples)(self.handle, Tn)
 
-    def _chk_loop(self, loop: bool, hold, hold_bins, Tn: int) -> None:
-        if not loop:
-            return
-        if hold is not None or hold_bins is not None:
-            raise ValueError("loop together with hold or hold_bins is not served")
-        if self.griffinlim_engine == "chirp-z":
-            raise ValueError("a loop decode is not served on the chirp-z engine (RFX_ERR_UNSUPPORTED)")
-        check_loop_frames(self.hop_length, self.n_fft, Tn)
-
-    def _chk_peak(self, peak_start: bool, **others: T.Any) -> None:
-        if not peak_start:
-            return
-        given = [name for name, v in others.items() if v is not None]
-        if given:
-            raise ValueError(f"peak_start does not go with {', '.join(given)}: the peak start needs no guide and holds nothing")
+    def _chk_peak_bins(self) -> None:
         if self.n_stft > 10240:
             raise ValueError(f"the spectral-peak start is not served for n_stft = {self.n_stft} above 10240 (RFX_ERR_UNSUPPORTED: a frame must fit the LDS)")
 
-    def _peak_extra(self, B: int, Tn: int) -> int:
-        """bytes a call with the peak start brings on top of its workspace query: the angles and the start's scratch"""
-        return self.lib.rfx_griffinlim_peak_workspace_bytes(self.handle, B, Tn) - self.lib.rfx_griffinlim_workspace_bytes(self.handle, B, Tn)
+    def _inverse_call(self, entry: str, shape: T.Tuple[int, ...], rows: int, Tn: int, row_base: int, magnitude_hint: float, lstsq: bool,
+                      guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], loop: bool,
+                      peak_start: bool, angles0_slots: T.Optional[torch.Tensor] = None) -> T.Tuple[T.Any, int, T.Optional[torch.Tensor]]:
+        """What `griffinlim`, `waveform_from_mel` and `audio_from_image` share: the combination rules and this plan's own refusals,
+        the extras' tensors as the library reads them, and from them (the call's options, its workspace need in bytes, the injected
+        angles as the library reads them).  `entry`: the C entry's name between rfx_ and _workspace_bytes, `shape`: its query's
+        arguments; `rows`: the call's Griffin-Lim rows."""
+        rules = functools.partial(check_call_rules, PLAN_WORDING, loop=loop, peak_start=peak_start, angles0_slots=angles0_slots, guide=guide, hold=hold,
+                                  hold_bins=hold_bins)
+        if loop:
+            rules("loop_holds")
+            if self.griffinlim_engine == "chirp-z":
+                raise ValueError("a loop decode is not served on the chirp-z engine (RFX_ERR_UNSUPPORTED)")
+            check_loop_frames(self.hop_length, self.n_fft, Tn)
+        if peak_start:
+            rules("peak_start")
+            self._chk_peak_bins()
+        if angles0_slots is not None:
+            angles0_slots = self._chk(angles0_slots, torch.complex64)
+        if guide is not None:
+            rules("two_starts")
+            guide = self._chk_guide(guide)
+        if hold is not None:
+            rules("hold_needs_guide")
+            hold = self._chk_hold(hold, rows)
+        if hold_bins is not None:
+            rules("bins_need_guide", "bins_and_hold")
+            hold_bins = self._chk_hold_bins(hold_bins, rows, Tn)
+        opt = start_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq, loop, peak_start)
+        opt.keepalive = (guide, hold, hold_bins)  # (a copy `_chk_*` made lives as long as the options that point at it)
+        kind = "loop_" if loop else "masked_" if hold_bins is not None else "held_" if hold is not None else "peak_" if peak_start else ""
+        need = getattr(self.lib, f"rfx_{entry}_{kind}workspace_bytes")(self.handle, *shape)
+        if loop and peak_start:  # (no query of its own: behind the loop call's bytes, the start's angles and scratch, each a 256-byte field)
+            need += -(-rows * Tn * self.frame_stride * 8 // 256) * 256 + self.lib.rfx_peak_start_workspace_bytes(self.handle, rows, Tn)
+        return opt, need, angles0_slots
 
     def peak_start(self, mag_slots: torch.Tensor, B: int, Tn: int) -> torch.Tensor:
         """rfx_peak_start: magnitudes in slot layout -> (B * Tn, frame_stride) complex64 initial angles in the layout `griffinlim`'s
         `angles0_slots` takes (what `pack_complex` makes), built from the magnitudes alone: spectral peaks, their interpolated
         frequencies integrated over the hop.  A row depends on its magnitudes only."""
         mag_slots = self._chk(mag_slots, torch.float32)
-        self._chk_peak(True)
+        self._chk_peak_bins()
         if mag_slots.numel() < B * Tn * self.frame_stride:
             raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
         out = torch.empty((B * Tn, self.frame_stride), dtype=torch.complex64, device=mag_slots.device)
@@ -885,49 +916,33 @@ class Plan:
         `peak_start`: start from the spectral-peak phases of the magnitudes (rfx_start_call_options; `peak_start` below) instead of
         random ones: no randomness, without `angles0_slots`, `guide`, `hold` or `hold_bins`."""
         mag_slots = self._chk(mag_slots, torch.float32)
-        self._chk_loop(loop, hold, hold_bins, Tn)
-        self._chk_peak(peak_start, angles0_slots=angles0_slots, guide=guide, hold=hold, hold_bins=hold_bins)
-        if angles0_slots is not None:
-            angles0_slots = self._chk(angles0_slots, torch.complex64)
-        if guide is not None:
-            if angles0_slots is not None:
-                raise ValueError("a guide and angles0_slots are two starts: give one")
-            guide = self._chk_guide(guide)
-        if hold is not None:
-            hold = self._chk_hold(hold, guide, B)
-        if hold_bins is not None:
-            hold_bins = self._chk_hold_bins(hold_bins, guide, hold, B, Tn)
+        opt, need, angles0_slots = self._inverse_call("griffinlim", (B, Tn), B, Tn, row_base, magnitude_hint, False, guide, hold, hold_bins, loop,
+                                                      peak_start, angles0_slots)
         if mag_slots.numel() < B * Tn * self.frame_stride:
             raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
-        need = (self.lib.rfx_griffinlim_loop_workspace_bytes if loop else self.lib.rfx_griffinlim_masked_workspace_bytes if hold_bins is not None else
-                self.lib.rfx_griffinlim_held_workspace_bytes if hold is not None else self.lib.rfx_griffinlim_workspace_bytes)(self.handle, B, Tn)
-        if peak_start:
-            need += self._peak_extra(B, Tn)
         if workspace is not None:
             workspace = self._chk(workspace)
-        if workspace is None or workspace.numel() < need:  # no (or too small a) caller-owned workspace: the plan's arena
-            with self._workspace(need) as ws:
-                return self.griffinlim(mag_slots, B, Tn, n_iter, momentum, angles0_slots, seed, ws, launch_ms, row_base, magnitude_hint, guide, hold, hold_bins, loop, peak_start)
         out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mag_slots.device)
-        opt = start_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, loop=loop, peak_start=peak_start)
-        check(
-            self.lib.rfx_griffinlim_ex(
-                self.handle,
-                mag_slots.data_ptr(),
-                angles0_slots.data_ptr() if angles0_slots is not None else None,
-                seed & 0xFFFFFFFFFFFFFFFF,
-                B,
-                Tn,
-                n_iter,
-                momentum,
-                out.data_ptr(),
-                workspace.data_ptr(),
-                workspace.numel(),
-                self._stream(),
-                ctypes.byref(opt),
-                ctypes.cast(launch_ms, c_void_p) if launch_ms is not None else None,  # ctypes float array of n_iter + 1 entries, filled after a stream sync
+        # no (or too small a) caller-owned workspace: the plan's arena
+        with (self._workspace(need) if workspace is None or workspace.numel() < need else contextlib.nullcontext(workspace)) as ws:
+            check(
+                self.lib.rfx_griffinlim_ex(
+                    self.handle,
+                    mag_slots.data_ptr(),
+                    angles0_slots.data_ptr() if angles0_slots is not None else None,
+                    seed & 0xFFFFFFFFFFFFFFFF,
+                    B,
+                    Tn,
+                    n_iter,
+                    momentum,
+                    out.data_ptr(),
+                    ws.data_ptr(),
+                    ws.numel(),
+                    self._stream(),
+                    ctypes.byref(opt),
+                    ctypes.cast(launch_ms, c_void_p) if launch_ms is not None else None,  # ctypes float array of n_iter + 1 entries, filled after a stream sync
+                )
             )
-        )
         return out
 
     def spectral_error(self, wave: torch.Tensor, mag_slots: torch.Tensor, B: int, Tn: int) -> torch.Tensor:
@@ -1183,19 +1198,9 @@ class Plan:
         B, M, Tn = mel.shape
         if M != self.n_mels:
             raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")  # torchaudio's message
-        self._chk_loop(loop, hold, hold_bins, Tn)
-        self._chk_peak(peak_start, guide=guide, hold=hold, hold_bins=hold_bins)
+        opt, need, _ = self._inverse_call("waveform_from_mel", (B, Tn), B, Tn, row_base, magnitude_hint, lstsq, guide, hold, hold_bins, loop, peak_start)
         out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mel.device)
-        if guide is not None:
-            guide = self._chk_guide(guide)
-        if hold is not None:
-            hold = self._chk_hold(hold, guide, B)
-        if hold_bins is not None:
-            hold_bins = self._chk_hold_bins(hold_bins, guide, hold, B, Tn)
-        opt = start_call_options(guide, hold, hold_bins, B, row_base, magnitude_hint, lstsq, loop, peak_start)
-        query = (self.lib.rfx_waveform_from_mel_loop_workspace_bytes if loop else self.lib.rfx_waveform_from_mel_masked_workspace_bytes if hold_bins is not None else
-                 self.lib.rfx_waveform_from_mel_held_workspace_bytes if hold is not None else self.lib.rfx_waveform_from_mel_workspace_bytes)
-        with self._workspace(query(self.handle, B, Tn) + (self._peak_extra(B, Tn) if peak_start else 0)) as ws:
+        with self._workspace(need) as ws:
             check(self.lib.rfx_waveform_from_mel_ex(self.handle, mel.data_ptr(), B, Tn, channels_per_clip, seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return out
@@ -1227,8 +1232,8 @@ class Plan:
         if ch != 3 or H != self.n_mels:
             raise ValueError(f"expected (N, {self.n_mels}, T, 3) uint8 images, got {tuple(img.shape)}")
         C = 2 if stereo else 1
-        self._chk_loop(loop, hold, hold_bins, W)
-        self._chk_peak(peak_start, guide=guide, hold=hold, hold_bins=hold_bins)
+        opt, need, _ = self._inverse_call("audio_from_image", (N, int(stereo), W), N * C, W, clip_base * C, magnitude_hint, lstsq, guide, hold, hold_bins,
+                                       loop, peak_start)
         L = self.output_samples(W, loop)
         if out is not None:
             if out.device != self.device or out.dtype != torch.int16 or tuple(out.shape) != (N, L, C) or not out.is_contiguous():
@@ -1236,27 +1241,12 @@ class Plan:
             pcm = out
         else:
             pcm = torch.empty((N, L, C), dtype=torch.int16, device=img.device)
-        need = (self.lib.rfx_audio_from_image_loop_workspace_bytes if loop else self.lib.rfx_audio_from_image_masked_workspace_bytes if hold_bins is not None else
-                self.lib.rfx_audio_from_image_held_workspace_bytes if hold is not None else self.lib.rfx_audio_from_image_workspace_bytes)(
-            self.handle, N, int(stereo), W)
-        if peak_start:
-            need += self._peak_extra(N * C, W)
-        ws = self._chk(workspace) if workspace is not None else None
-        if ws is None or ws.numel() < need:
-            with self._workspace(need) as borrowed:
-                return self.audio_from_image(img, stereo, lut, n_iter, momentum, seed, normalize, out=pcm, workspace=borrowed,
-                                             clip_base=clip_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop,
-                                             peak_start=peak_start)
+        if workspace is not None:
+            workspace = self._chk(workspace)
         peak = torch.zeros((N,), dtype=torch.float32, device=img.device)
-        if guide is not None:
-            guide = self._chk_guide(guide)
-        if hold is not None:
-            hold = self._chk_hold(hold, guide, N * C)
-        if hold_bins is not None:
-            hold_bins = self._chk_hold_bins(hold_bins, guide, hold, N * C, W)
-        opt = start_call_options(guide, hold, hold_bins, N * C, clip_base * C, magnitude_hint, lstsq, loop, peak_start)
-        check(self.lib.rfx_audio_from_image_u8_ex(self.handle, img.data_ptr(), N, W, int(stereo), lut.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
-                                                  int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
+        with (self._workspace(need) if workspace is None or workspace.numel() < need else contextlib.nullcontext(workspace)) as ws:
+            check(self.lib.rfx_audio_from_image_u8_ex(self.handle, img.data_ptr(), N, W, int(stereo), lut.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
+                                                      int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return pcm, peak
 
     def image_from_waveform(self, wave: torch.Tensor, stereo: bool, thresholds: torch.Tensor):

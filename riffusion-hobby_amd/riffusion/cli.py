@@ -62,6 +62,27 @@ def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_freque
     print(f"Wrote {image}")
 
 
+# the combination rules (`_hip.check_call_rules`) in the words of image-to-audio's flags
+_FLAG_WORDING = {
+    "roles": {"guide_audio": "guide", "hold_ms": "hold", "hold_mask": "hold_bins"},
+    "peak_and_guide": "--phase-start peaks does not go with --guide-audio: they are two starts",
+    "loop_holds": "--loop does not go with --hold-head-ms / --hold-tail-ms / --hold-mask",
+    "bins_need_guide": "--hold-mask needs --guide-audio: the bins are held at the guide's phase",
+    "bins_and_hold": "--hold-mask does not go with --hold-head-ms / --hold-tail-ms: paint the held frames' columns black in the mask",
+    "hold_needs_guide": "--hold-head-ms / --hold-tail-ms need --guide-audio: the frames are held at the guide's phase",
+}
+
+
+def _check_image_to_audio(*, guide_audio: str, hold_head_ms: int, hold_tail_ms: int, hold_mask: str, loop: bool, phase_start: str, **_: T.Any) -> None:
+    """ValueError for flags of image-to-audio that do not go together (the function raises it, the parser reports it)"""
+    from riffusion import _hip
+
+    _hip.check_call_rules(_FLAG_WORDING, loop=loop, peak_start=phase_start == "peaks", guide_audio=guide_audio or None,
+                          hold_ms=(hold_head_ms or hold_tail_ms) or None, hold_mask=hold_mask or None)
+    if hold_head_ms < 0 or hold_tail_ms < 0:
+        raise ValueError("--hold-head-ms / --hold-tail-ms must be >= 0")
+
+
 def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto",
                    guide_audio: str = "", griffin_lim_iters: int = -1, hold_head_ms: int = 0, hold_tail_ms: int = 0,
                    hold_mask: str = "", hold_keep_threshold: float = 0.5, loop: bool = False, phase_start: str = "random") -> None:
@@ -78,18 +99,8 @@ def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel:
     start without a click; the tile needs n_fft / hop columns (40 at the defaults).  Not with --hold-head-ms / --hold-tail-ms / --hold-mask.
     --phase-start peaks starts Griffin-Lim from phases built from the tile's own magnitudes (spectral peaks, their frequencies
     integrated over the hop) instead of random ones: for a tile without a guide and few --griffin-lim-iters.  Not with --guide-audio."""
-    if phase_start == "peaks" and guide_audio:
-        raise ValueError("--phase-start peaks does not go with --guide-audio: they are two starts")
-    if loop and (hold_mask or hold_head_ms or hold_tail_ms):
-        raise ValueError("--loop does not go with --hold-head-ms / --hold-tail-ms / --hold-mask")
-    if hold_mask and not guide_audio:
-        raise ValueError("--hold-mask needs --guide-audio: the bins are held at the guide's phase")
-    if hold_mask and (hold_head_ms or hold_tail_ms):
-        raise ValueError("--hold-mask does not go with --hold-head-ms / --hold-tail-ms: paint the held frames' columns black in the mask")
-    if (hold_head_ms or hold_tail_ms) and not guide_audio:
-        raise ValueError("--hold-head-ms / --hold-tail-ms need --guide-audio: the frames are held at the guide's phase")
-    if hold_head_ms < 0 or hold_tail_ms < 0:
-        raise ValueError("--hold-head-ms / --hold-tail-ms must be >= 0")
+    _check_image_to_audio(guide_audio=guide_audio, hold_head_ms=hold_head_ms, hold_tail_ms=hold_tail_ms, hold_mask=hold_mask, loop=loop,
+                          phase_start=phase_start)
     pil_image = Image.open(image)
     params = _params_from_image(pil_image)
     converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
@@ -337,22 +348,13 @@ def main(argv: T.Optional[T.Sequence[str]] = None) -> None:
     parser = build_parser()
     args = vars(parser.parse_args(argv))
     command = args.pop("command")
-    if command == "image-to-audio" and (args["hold_head_ms"] or args["hold_tail_ms"]):
-        if not args["guide_audio"]:
-            parser.error("--hold-head-ms / --hold-tail-ms need --guide-audio: the frames are held at the guide's phase")
-        if args["hold_head_ms"] < 0 or args["hold_tail_ms"] < 0:
-            parser.error("--hold-head-ms / --hold-tail-ms must be >= 0")
-    if command == "image-to-audio" and args["hold_mask"]:
-        if not args["guide_audio"]:
-            parser.error("--hold-mask needs --guide-audio: the bins are held at the guide's phase")
-        if args["hold_head_ms"] or args["hold_tail_ms"]:
-            parser.error("--hold-mask does not go with --hold-head-ms / --hold-tail-ms")
-        if not 0.0 <= args["hold_keep_threshold"] <= 1.0:
+    if command == "image-to-audio":
+        try:
+            _check_image_to_audio(**args)
+        except ValueError as e:
+            parser.error(str(e))
+        if args["hold_mask"] and not 0.0 <= args["hold_keep_threshold"] <= 1.0:
             parser.error("--hold-keep-threshold must be in [0, 1]")
-    if command == "image-to-audio" and args["loop"] and (args["hold_mask"] or args["hold_head_ms"] or args["hold_tail_ms"]):
-        parser.error("--loop does not go with --hold-head-ms / --hold-tail-ms / --hold-mask")
-    if command == "image-to-audio" and args["phase_start"] == "peaks" and args["guide_audio"]:
-        parser.error("--phase-start peaks does not go with --guide-audio: they are two starts")
     if command == "images-to-audio-batch" and args["griffin_lim_iters"] < -1:
         parser.error("--griffin-lim-iters must be >= 0")
     _COMMANDS[command](**args)

@@ -18,6 +18,7 @@ Every call is re-entrant: the converter holds immutable constants only (plans ar
 threads never share one) - the reference shares one converter across a thread pool (cli.py:172-204).  There is no CPU implementation: on a machine without a GPU the constructor still
 mirrors the reference's fallback warning, and any compute call raises.
 """
+import functools
 import typing as T
 import warnings
 
@@ -69,6 +70,18 @@ def hold_mask_rows(hold_mask: T.Any, n: int, n_mels: int, frames: int) -> torch.
     if tuple(m.shape) != (n, n_mels, frames):
         raise ValueError(f"hold_mask must be ({n_mels}, {frames}) or ({n}, {n_mels}, {frames}), got {tuple(m.shape)}")
     return (m != 0).to(torch.uint8)
+
+
+# the combination rules (`_hip.check_call_rules`) in the words of the converters' arguments
+CALL_WORDING = {
+    "roles": {"hold_frames": "hold", "hold_mask": "hold_bins", "guide_segment": "guide", "guide_waveforms": "guide"},
+    "peak_start": 'phase_start="peaks" does not go with {given}: the peak start needs no guide and holds nothing',
+    "loop_holds": "loop together with hold_frames or hold_mask is not served",
+    "two_starts": "guide and angles0 are two starts of Griffin-Lim: give one",
+    "hold_needs_guide": "hold_frames needs a guide: the frames are held at the guide's phase",
+    "bins_need_guide": "hold_mask needs a guide: the bins are held at the guide's phase",
+    "bins_and_hold": "hold_frames together with hold_mask is not served: set the held frames' columns in the mask",
+}
 
 
 class SpectrogramConverter:
@@ -231,23 +244,14 @@ class SpectrogramConverter:
         """
         from riffusion import _hip
 
-        peaks = _hip.check_phase_start(phase_start, angles0=angles0, guide=guide, hold_frames=hold_frames, hold_mask=hold_mask)
-        if loop and (hold_frames is not None or hold_mask is not None):
-            raise ValueError("loop together with hold_frames or hold_mask is not served")
-        if guide is not None and angles0 is not None:
-            raise ValueError("guide and angles0 are two starts of Griffin-Lim: give one")
-        hold = None
-        if hold_frames is not None:
-            if guide is None:
-                raise ValueError("hold_frames needs a guide: the frames are held at the guide's phase")
-            hold = hold_rows(hold_frames, int(amplitudes_mel.shape[0]), int(amplitudes_mel.shape[-1]))
-        bands = None
-        if hold_mask is not None:
-            if guide is None:
-                raise ValueError("hold_mask needs a guide: the bins are held at the guide's phase")
-            if hold is not None:
-                raise ValueError("hold_frames together with hold_mask is not served: set the held frames' columns in the mask")
-            bands = hold_mask_rows(hold_mask, int(amplitudes_mel.shape[0]), int(amplitudes_mel.shape[1]), int(amplitudes_mel.shape[-1]))
+        peaks = _hip.check_phase_start(phase_start)
+        rules = functools.partial(_hip.check_call_rules, CALL_WORDING, loop=loop, peak_start=peaks, angles0=angles0, guide=guide,
+                                  hold_frames=hold_frames, hold_mask=hold_mask)
+        rules("peak_start", "loop_holds", "two_starts", "hold_needs_guide")
+        B, n_mels, frames = int(amplitudes_mel.shape[0]), int(amplitudes_mel.shape[1]), int(amplitudes_mel.shape[-1])
+        hold = hold_rows(hold_frames, B, frames) if hold_frames is not None else None
+        rules("bins_need_guide", "bins_and_hold")
+        bands = hold_mask_rows(hold_mask, B, n_mels, frames) if hold_mask is not None else None
         return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
                                        channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, hold=hold, hold_bands=bands,
                                        loop=loop, peak_start=peaks)
@@ -273,12 +277,9 @@ class SpectrogramConverter:
         spectral-peak start (`phase_start="peaks"`)."""
         from riffusion import _hip
 
-        if peak_start and (angles0 is not None or guide is not None or hold is not None or hold_bands is not None):
-            raise ValueError('phase_start="peaks" does not go with angles0, guide, hold_frames or hold_mask')
-
+        _hip.check_call_rules(CALL_WORDING, "peak_start", "loop_holds", loop=loop, peak_start=peak_start, angles0=angles0, guide=guide,
+                              hold_frames=hold, hold_mask=hold_bands)
         if loop:
-            if hold is not None or hold_bands is not None:
-                raise ValueError("loop together with hold_frames or hold_mask is not served")
             _hip.check_loop_frames(self.p.hop_length, self.p.n_fft, int(amplitudes_mel.shape[-1]))
 
         lstsq = _hip.check_inverse_mel(inverse_mel)

@@ -9,6 +9,7 @@ and one D2H copy per batch, takes the diffusion pipeline's output tensors direct
 `torch.distributed` process group (one process per GPU; clips are independent, so the only
 collective is the final all_gather of the int16 PCM).
 """
+import functools
 import typing as T
 
 import numpy as np
@@ -16,9 +17,14 @@ import torch
 from PIL import Image
 
 from riffusion import _hip
-from riffusion.spectrogram_converter import SpectrogramConverter, hold_mask_rows, hold_rows
+from riffusion.spectrogram_converter import CALL_WORDING, SpectrogramConverter, hold_mask_rows, hold_rows
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import audio_util, image_util
+
+
+# ... and of the batch entry points, whose guides are `guide_waveforms`
+BATCH_WORDING = {**CALL_WORDING, "hold_needs_guide": "hold_frames needs guide_waveforms: the frames are held at the guides' phase",
+                 "bins_need_guide": "hold_mask needs guide_waveforms: the bins are held at the guides' phase"}
 
 
 class SpectrogramImageConverter:
@@ -79,11 +85,8 @@ class SpectrogramImageConverter:
         one period of a loop: hop * W samples whose end runs into their start (not with `hold_frames` / `hold_mask`).
         `phase_start`: "random" (default) or "peaks", Griffin-Lim's start built from the tile's magnitudes (not with a guide).  All as
         in `audio_from_spectrogram_images`."""
-        _hip.check_phase_start(phase_start, guide_segment=guide_segment, hold_frames=hold_frames, hold_mask=hold_mask)
-        if hold_frames is not None and guide_segment is None:
-            raise ValueError("hold_frames needs a guide: the frames are held at the guide's phase")
-        if hold_mask is not None and guide_segment is None:
-            raise ValueError("hold_mask needs a guide: the bins are held at the guide's phase")
+        _hip.check_call_rules(CALL_WORDING, "peak_start", "hold_needs_guide", "bins_need_guide", peak_start=_hip.check_phase_start(phase_start),
+                              guide_segment=guide_segment, hold_frames=hold_frames, hold_mask=hold_mask)
         guides = None
         if guide_segment is not None:
             if int(guide_segment.frame_rate) != self.p.sample_rate:
@@ -163,11 +166,12 @@ class SpectrogramImageConverter:
         without `size`.
         """
         _hip.check_inverse_mel(inverse_mel)
-        peaks = _hip.check_phase_start(phase_start, guide_waveforms=guide_waveforms, hold_mask=hold_mask)
+        peaks = _hip.check_phase_start(phase_start)
+        rules = functools.partial(_hip.check_call_rules, BATCH_WORDING, peak_start=peaks, guide_waveforms=guide_waveforms, hold_mask=hold_mask)
+        rules("peak_start")
         if loop:  # (`loop` is here to be refused: a sequence is stitched with crossfades, its clips do not repeat)
             raise ValueError("loop does not go with a stitched sequence: decode loops with audio_from_spectrogram_images(loop=True)")
-        if hold_mask is not None and guide_waveforms is None:
-            raise ValueError("hold_mask needs guide_waveforms: the bins are held at the guides' phase")
+        rules("bins_need_guide")
         if isinstance(images, (list, tuple)):
             arrays = [np.asarray(image_util.rgb_array_from_image(im)) if isinstance(im, Image.Image) else np.asarray(im)
                       for im in images]
@@ -606,9 +610,10 @@ class SpectrogramImageConverter:
         from riffusion import batch_shard
 
         lstsq = _hip.check_inverse_mel(inverse_mel)
-        peaks = _hip.check_phase_start(phase_start, guide_waveforms=guide_waveforms, hold_frames=hold_frames, hold_mask=hold_mask)
-        if loop and (hold_frames is not None or hold_mask is not None):
-            raise ValueError("loop together with hold_frames or hold_mask is not served")
+        peaks = _hip.check_phase_start(phase_start)
+        rules = functools.partial(_hip.check_call_rules, BATCH_WORDING, loop=loop, peak_start=peaks, guide_waveforms=guide_waveforms,
+                                  hold_frames=hold_frames, hold_mask=hold_mask)
+        rules("peak_start", "loop_holds")
         if loop and return_error:
             raise ValueError("loop does not go with return_error=True: the spectral error is measured with the reflect-padded STFT")
 
@@ -656,18 +661,11 @@ class SpectrogramImageConverter:
             if guides.dtype not in (torch.float32, torch.int16):
                 raise ValueError(f"guide_waveforms must be float32 or int16, got {guides.dtype}")
 
-        holds = None
-        if hold_frames is not None:
-            if guides is None:
-                raise ValueError("hold_frames needs guide_waveforms: the frames are held at the guides' phase")
-            holds = hold_rows(hold_frames, n_total, int(size[0]) if size is not None else int(imgs.shape[2]))
-
+        rules("hold_needs_guide")
+        holds = hold_rows(hold_frames, n_total, int(size[0]) if size is not None else int(imgs.shape[2])) if hold_frames is not None else None
+        rules("bins_need_guide", "bins_and_hold")
         bands = None
         if hold_mask is not None:
-            if guides is None:
-                raise ValueError("hold_mask needs guide_waveforms: the bins are held at the guides' phase")
-            if holds is not None:
-                raise ValueError("hold_frames together with hold_mask is not served: set the held frames' columns in the mask")
             if isinstance(hold_mask, Image.Image):
                 hold_mask = image_util.hold_mask_from_image(hold_mask)
             bands = hold_mask_rows(hold_mask, n_total, plan.n_mels, int(size[0]) if size is not None else int(imgs.shape[2]))
