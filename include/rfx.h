@@ -848,6 +848,42 @@ size_t rfx_jpeg_decode_workspace_bytes(int N, int H, int W, size_t total_scan_by
 int rfx_jpeg_decode_u8(const uint8_t* d_scans, const int64_t* h_scan_offsets, const int64_t* d_scan_offsets, int N, int H, int W,
                        const uint16_t* d_qtables, const uint8_t* d_huff, uint8_t* d_rgb, int32_t* d_status, void* d_workspace, void* stream);
 
+/* ---- PNG: a lossless tile's IDAT payload, on the device ----------------------------------------------------------------------------
+ * PNG is the reference's lossless tile format (audio-to-image, its seed images).  The device writes the zlib stream that is the
+ * payload of the one IDAT chunk, with its Adler-32, and the chunk's CRC-32; signature, IHDR, eXIf and IEND do not depend on the
+ * pixels and are the caller's (riffusion.util.image_util.png_file).  The stream is NOT the one zlib writes: zlib's LZ77 parse is
+ * sequential.  It is a run-length + Huffman deflate (zlib's Z_RLE class), every step a function of the tile alone (csrc/
+ * rfx_png_core.h states it in full): each row filtered with the one of PNG's five filters whose filtered bytes have the least sum of
+ * absolute values as int8 (ties to the lowest type); the filtered stream cut every 32 rows; inside a block every run of equal bytes
+ * as a literal and matches at distance 1 of up to 258 bytes; one dynamic-Huffman block per block with a literal/length code limited
+ * to 15 bits by a stated rule; blocks joined at bit granularity.  Any PNG reader gets the tile's pixels back; the file's size is
+ * that of Pillow's save(..., compress_type=zlib.Z_RLE).  Colour type 2 (RGB) or 0 (grey, for a tile whose three channels are equal
+ * at every pixel), bit depth 8, no interlace.
+ *
+ * rfx_png_stream_capacity: bytes one tile's stream takes at most, for channels 3 or 1 (0 for anything else, or sizes outside
+ *   1 .. 65535).  The filtered stream has S = H * (W * channels + 1) bytes in B = ceil(H / 32) blocks.  A token costs at most 15
+ *   bits per byte it covers: a literal is one code of at most 15 bits for 1 byte, a match at most 15 + 5 + 1 bits (length code,
+ *   extra bits, distance code) for at least 3.  A block's header is bounded by its field widths: 3 + 14 bits, 19 x 3 bits of
+ *   code-length code, and for each of its 287 lengths at most a 7-bit symbol with 7 extra bits: 4092 bits; its end-of-block adds
+ *   15.  With the 2 bytes of zlib header and the 4 of Adler-32: 2 + ceil((B * 4107 + 15 * S) / 8) + 4.  No stored or fixed-Huffman
+ *   block is needed for the bound.
+ * rfx_png_encode_u8: d_rgb (N, H, W, 3) uint8 -> tile n's stream at d_stream + n * capacity, capacity = rfx_png_stream_capacity(H,
+ *   W, mode == 1 ? 1 : 3); its length in d_stream_bytes[n] (never above the capacity; no byte past the length is written); the
+ *   CRC-32 of b"IDAT" + stream in d_crc[n]; what the tile was written with in d_channels[n].  mode 0: RGB.  mode 1: grey; a tile
+ *   that is not grey gets d_channels[n] = 0, d_stream_bytes[n] = 0 and no stream, the other tiles are not affected.  mode 2: grey
+ *   where R = G = B at every pixel, else RGB, decided on the device.  d_stream_bytes, d_crc and d_channels are N 32-bit words each,
+ *   aligned to 4 bytes.  d_workspace holds rfx_png_encode_workspace_bytes(N, H, W) (0 for arguments the call refuses), aligned to
+ *   256 bytes.  H or W above 65535, a capacity that an int32 does not hold, or more rows or stream pieces than one launch takes
+ *   (N * H or N * ceil(capacity / 256) above 2^31 - 1) are RFX_ERR_UNSUPPORTED, refused before anything is launched.  All launches
+ *   go to `stream`; nothing synchronises. */
+#define RFX_PNG_RGB 0
+#define RFX_PNG_GRAY 1
+#define RFX_PNG_AUTO 2
+size_t rfx_png_stream_capacity(int H, int W, int channels);
+size_t rfx_png_encode_workspace_bytes(int N, int H, int W);
+int rfx_png_encode_u8(const uint8_t* d_rgb, int N, int H, int W, int mode, uint8_t* d_stream, int32_t* d_stream_bytes, uint32_t* d_crc,
+                      int32_t* d_channels, void* d_workspace, void* stream);
+
 /* ---- int16 front end of the encode: pydub's set_frame_rate / set_channels and the clip slicing on the device -------------------
  * What the reference does on the host before every encode (cli.py:132-193, streamlit/tasks/audio_to_audio.py): AudioSegment
  * .set_channels (audioop.tomono(data, 2, 0.5, 0.5) / audioop.tostereo(data, 2, 1, 1)), .set_frame_rate

@@ -7,6 +7,7 @@
 #include "rfx_jpeg_dec_core.h"
 #include "rfx_pcm_core.h"
 #include "rfx_pcm_in_core.h"
+#include "rfx_png_core.h"
 #include "rfx_resize_core.h"
 
 using namespace rfx;
@@ -179,6 +180,48 @@ int rfx_jpeg_encode_u8(const uint8_t* d_rgb, int N, int H, int W, const uint16_t
   RFX_ON_DEVICE(dev);
   RFX_HIP(launch_jpeg_encode(d_rgb, N, H, W, d_qtables, d_scan, (size_t)jpg_scan_capacity(jpg_geom(H, W)), d_scan_bytes, d_workspace,
                              (hipStream_t)stream));
+  return RFX_OK;
+}
+
+// ---- PNG stream (rfx_png.hip) -------------------------------------------------------------------------------------------------------
+static bool png_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= kPngMaxSize && W <= kPngMaxSize; }
+// what keeps an encode inside its index types: the stream's length is an int32, and the kernels take one workgroup per row and
+// one thread per 256-byte piece of the stream, 256 to a workgroup, at most 2^31 - 1 workgroups
+static const char* png_batch_limit(int N, int H, int W) {
+  const uint64_t cap = png_stream_capacity(png_geom(H, W, 3));
+  if (cap > (uint64_t)INT32_MAX) return "one tile's stream capacity does not fit the int32 of d_stream_bytes";
+  if ((uint64_t)N * (uint64_t)H > (uint64_t)INT32_MAX || (uint64_t)N * ((cap + 255) / 256 + 256) > (uint64_t)INT32_MAX)
+    return "more rows or stream pieces than one launch takes; encode in pieces";
+  return nullptr;
+}
+
+size_t rfx_png_stream_capacity(int H, int W, int channels) {
+  if (!png_size_ok(H, W) || (channels != 1 && channels != 3)) return 0;
+  return (size_t)png_stream_capacity(png_geom(H, W, channels));
+}
+
+size_t rfx_png_encode_workspace_bytes(int N, int H, int W) {
+  if (N < 1 || !png_size_ok(H, W) || png_batch_limit(N, H, W)) return 0;
+  return png_workspace_layout(N, H, W).total;
+}
+
+int rfx_png_encode_u8(const uint8_t* d_rgb, int N, int H, int W, int mode, uint8_t* d_stream, int32_t* d_stream_bytes, uint32_t* d_crc,
+                      int32_t* d_channels, void* d_workspace, void* stream) {
+  if (N < 1 || H < 1 || W < 1) return fail(RFX_ERR_INVALID, "rfx_png_encode_u8: N, H and W must be positive");
+  if (mode != RFX_PNG_RGB && mode != RFX_PNG_GRAY && mode != RFX_PNG_AUTO)
+    return fail(RFX_ERR_INVALID, "rfx_png_encode_u8: mode must be RFX_PNG_RGB, RFX_PNG_GRAY or RFX_PNG_AUTO");
+  if (!png_size_ok(H, W))
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_png_encode_u8: " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): this entry takes at most 65535 rows and columns");
+  if (const char* why = png_batch_limit(N, H, W)) return fail(RFX_ERR_UNSUPPORTED, std::string("rfx_png_encode_u8: ") + why);
+  if (!d_rgb || !d_stream || !d_stream_bytes || !d_crc || !d_channels || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_png_encode_u8: null pointer");
+  if (reinterpret_cast<uintptr_t>(d_stream_bytes) % 4 || reinterpret_cast<uintptr_t>(d_crc) % 4 || reinterpret_cast<uintptr_t>(d_channels) % 4 ||
+      reinterpret_cast<uintptr_t>(d_workspace) % 256)
+    return fail(RFX_ERR_INVALID, "rfx_png_encode_u8: d_stream_bytes, d_crc and d_channels must be aligned to 4 bytes, d_workspace to 256");
+  int dev;
+  if (int rc = device_of(d_stream, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_png_encode(d_rgb, N, H, W, mode, d_stream, (size_t)png_stream_capacity(png_geom(H, W, mode == RFX_PNG_GRAY ? 1 : 3)),
+                            d_stream_bytes, d_crc, d_channels, d_workspace, (hipStream_t)stream));
   return RFX_OK;
 }
 

@@ -485,6 +485,18 @@ JpgLayout jpeg_workspace_layout(int N, int H, int W);
 hipError_t launch_jpeg_encode(const uint8_t* rgb, int N, int H, int W, const uint16_t* qtables, uint8_t* scan, size_t capacity,
                               int32_t* scan_bytes, void* workspace, hipStream_t s);
 
+// the zlib stream of a PNG's IDAT chunk for (N, H, W, 3) uint8 tiles (rfx_png.hip, the stream in rfx_png_core.h): tile n's stream
+// at stream + n * capacity, its length in stream_bytes[n], the CRC-32 of b"IDAT" + stream in crc[n], and in channels[n] what it was
+// written with: 3 (RGB), 1 (grey) or 0 (mode 1 met a colour tile: no stream).  mode: 0 RGB, 1 grey, 2 grey where R = G = B.  The
+// caller has checked the sizes (1 .. 65535, capacity within int32, N * H and N * pieces within one launch).
+struct PngLayout {
+  size_t colour, row_a, row_b, hist, table, hdr, hdr_bits, block_bits, filt, words, total;  // byte offsets, and the size
+  size_t words_per_tile, filt_per_tile;  // 32-bit words of one tile's stream (a multiple of 64), bytes of its filtered rows
+};
+PngLayout png_workspace_layout(int N, int H, int W);
+hipError_t launch_png_encode(const uint8_t* rgb, int N, int H, int W, int mode, uint8_t* stream, size_t capacity, int32_t* stream_bytes,
+                             uint32_t* crc, int32_t* channels, void* workspace, hipStream_t s);
+
 // baseline JPEG scans to (N, H, W, 3) uint8 tiles (rfx_jpeg_dec.hip, arithmetic in rfx_jpeg_dec_core.h): image n's entropy-coded
 // bytes are scans[offsets[n] .. offsets[n + 1]) (offsets: N + 1 int64 in device memory; scans 16-byte aligned), its tables
 // qtables[n] (2, 64) uint16 in natural order and huff[n] (4, 272) uint8; status[n] receives 0 or a kJpd* code.  The caller has

@@ -422,7 +422,13 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_jpeg_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t]),
     "rfx_jpeg_decode_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "rfx_png_stream_capacity": (c_size_t, [c_int, c_int, c_int]),
+    "rfx_png_encode_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rfx_png_encode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
+
+# rfx_png_encode_u8's modes (RFX_PNG_RGB, RFX_PNG_GRAY, RFX_PNG_AUTO)
+PNG_MODES = {"rgb": 0, "gray": 1, "auto": 2}
 
 # PIL.Image.Resampling values of the filters rfx_image_resize_u8 implements (rfx_resize_filter)
 RESIZE_FILTERS = {1: "LANCZOS", 2: "BILINEAR", 3: "BICUBIC"}
@@ -1148,6 +1154,40 @@ class Plan:
             packed = torch.cat([scans[n, :size] for n, size in enumerate(sizes)]).cpu().numpy().tobytes()
         ends = np.cumsum(sizes)
         return [packed[int(e) - size:int(e)] for e, size in zip(ends, sizes)]
+
+    def png_streams(self, img_u8: torch.Tensor, mode: str = "rgb") -> T.Tuple[T.List[bytes], np.ndarray, np.ndarray]:
+        """The IDAT payload (a zlib stream: run-length + Huffman deflate, csrc/rfx_png_core.h) of every (H, W, 3) uint8 tile of an
+        (N, H, W, 3) batch (rfx_png_encode_u8) -> (N `bytes`, the (N,) uint32 CRC-32 of b"IDAT" + stream, the (N,) int32 channels
+        each tile was written with: 3, 1, or 0 where mode "gray" met a colour tile, whose stream is empty).  A file is
+        `image_util.png_file(...)`.  mode: "rgb", "gray", or "auto" (grey where R = G = B, decided on the device).  The sizes, CRCs
+        and channels are read once (the call's one synchronisation), then the used bytes of all streams come down in one copy."""
+        if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
+            raise ValueError("expected (N, H, W, 3) uint8 images")
+        if mode not in PNG_MODES:
+            raise ValueError(f"mode must be one of {sorted(PNG_MODES)}, got {mode!r}")
+        img = self._chk(img_u8)
+        N, H, W, _ = img.shape
+        if N == 0:
+            return [], np.zeros(0, np.uint32), np.zeros(0, np.int32)
+        m = PNG_MODES[mode]
+        cap = self.lib.rfx_png_stream_capacity(H, W, 1 if m == 1 else 3)
+        need = self.lib.rfx_png_encode_workspace_bytes(N, H, W)
+        if cap == 0 or need == 0:  # a size the library refuses: its own words (nothing is launched)
+            check(self.lib.rfx_png_encode_u8(img.data_ptr(), N, H, W, m, None, None, None, None, None, self._stream()))
+            raise RfxError(f"rfx_png_encode_u8 took a {H} x {W} image it reports no capacity for")
+        need = (need + 255) // 256 * 256
+        meta_d = torch.empty((3, N), dtype=torch.int32, device=self.device)  # sizes, CRCs, channels
+        with self._workspace(need + N * cap) as ws:
+            check(self.lib.rfx_png_encode_u8(img.data_ptr(), N, H, W, m, ws.data_ptr() + need, meta_d[0].data_ptr(), meta_d[1].data_ptr(),
+                                             meta_d[2].data_ptr(), ws.data_ptr(), self._stream()))
+            meta = meta_d.cpu().numpy()
+            sizes = [int(v) for v in meta[0]]
+            if min(sizes) < 0 or max(sizes) > cap:
+                raise RfxError(f"rfx_png_encode_u8 reported stream sizes outside 0 .. {cap}")
+            streams = ws[need:need + N * cap].view(N, cap)
+            packed = torch.cat([streams[n, :size] for n, size in enumerate(sizes)]).cpu().numpy().tobytes()
+        ends = np.cumsum(sizes)
+        return [packed[int(e) - size:int(e)] for e, size in zip(ends, sizes)], meta[1].view(np.uint32).copy(), meta[2].copy()
 
     def jpeg_decode(self, scans: T.Sequence[bytes], H: int, W: int, qtables: np.ndarray, huffman: np.ndarray) -> T.Tuple[torch.Tensor, np.ndarray]:
         """N baseline 4:2:0 JPEG scans of H x W images (the entropy-coded bytes between the SOS header and EOI, with each image's

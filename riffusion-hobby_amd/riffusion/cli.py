@@ -48,8 +48,12 @@ def _params_from_image(image: Image.Image) -> SpectrogramParams:
 
 def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_frequencies: int = 512, min_frequency: int = 0,
                    max_frequency: int = 10000, window_duration_ms: int = 100, padded_duration_ms: int = 400,
-                   power_for_image: float = 0.25, stereo: bool = False, device: str = "cuda", frame_engine: str = "auto") -> None:
-    """Encode one clip; --frame-engine chirp-z runs a sample rate / padded duration whose FFT length has a prime factor above 13."""
+                   power_for_image: float = 0.25, stereo: bool = False, device: str = "cuda", frame_engine: str = "auto",
+                   png_writer: str = "pillow", png_mode: str = "rgb") -> None:
+    """Encode one clip; --frame-engine chirp-z runs a sample rate / padded duration whose FFT length has a prime factor above 13.
+    --png-writer device writes the PNG on the GPU (lossless: the same pixels and EXIF, not Pillow's bytes; the size of zlib's Z_RLE
+    strategy); with it --png-mode gray or auto writes a mono tile as greyscale, 0.63 of the RGB file."""
+    _check_png_flags(png_writer, png_mode)
     segment = _load_segment(audio)
     params = SpectrogramParams(
         sample_rate=segment.frame_rate, stereo=stereo, window_duration_ms=window_duration_ms,
@@ -58,8 +62,20 @@ def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_freque
     )
     converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
     pil_image = converter.spectrogram_image_from_audio(segment)
-    pil_image.save(image, exif=pil_image.getexif(), format="PNG")
+    if png_writer == "device":
+        data = converter.png_bytes_from_images(np.asarray(pil_image)[None], exif=pil_image.getexif(), mode=png_mode)[0]
+        with open(image, "wb") as f:
+            f.write(data)
+    else:
+        pil_image.save(image, exif=pil_image.getexif(), format="PNG")
     print(f"Wrote {image}")
+
+
+def _check_png_flags(png_writer: str, png_mode: str) -> None:
+    if png_writer not in _CHOICES["png_writer"] or png_mode not in _CHOICES["png_mode"]:
+        raise ValueError(f"--png-writer must be one of {_CHOICES['png_writer']} and --png-mode one of {_CHOICES['png_mode']}")
+    if png_writer == "pillow" and png_mode != "rgb":
+        raise ValueError("--png-mode gray / auto needs --png-writer device: Pillow's route writes the RGB tile as it is")
 
 
 # the combination rules (`_hip.check_call_rules`) in the words of image-to-audio's flags
@@ -229,15 +245,18 @@ def _device_convertible(seg: T.Any, sample_rate: int) -> bool:
 def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: str = "jpg", step_size_ms: int = 10,
                           num_frequencies: int = 512, min_frequency: int = 0, max_frequency: int = 10000,
                           power_for_image: float = 0.25, mono: bool = False, sample_rate: int = 44100, device: str = "cuda",
-                          num_threads: int = 0, limit: int = -1, batch_size: int = 64, frame_engine: str = "auto") -> None:
+                          num_threads: int = 0, limit: int = -1, batch_size: int = 64, frame_engine: str = "auto",
+                          png_writer: str = "pillow", png_mode: str = "rgb") -> None:
     """Process audio clips into spectrogram images in batch (reference cli.py:134-204, same flags and defaults: stereo
     tiles unless --mono, files resampled to --sample-rate, unreadable files skipped, jpg output - encoded on the device, the same
-    bytes as Pillow's; png is written by Pillow on the host).  Instead of one clip
+    bytes as Pillow's; png is written by Pillow on the host unless --png-writer device, which writes it on the GPU: lossless, the
+    same pixels and EXIF, not Pillow's bytes; --png-mode gray / auto then writes mono tiles as greyscale).  Instead of one clip
     per thread-pool task (`num_threads` is accepted and ignored) same-length clips go to the GPU `batch_size` at a time.  A file
     whose channel count or rate differs is mixed and resampled on the device (Plan.resample_pcm), same bytes as pydub's.
     --frame-engine chirp-z runs a --sample-rate whose FFT length has a prime factor above 13."""
     import torch
 
+    _check_png_flags(png_writer, png_mode)
     os.makedirs(output_dir, exist_ok=True)
     device = _rank_device(device)
     image_format = {"jpg": "JPEG", "jpeg": "JPEG", "png": "PNG"}[image_extension]
@@ -267,8 +286,11 @@ def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: s
         else:  # a file converted on the device left its waveform there: the host ones of its group join it
             plan = converter.converter._plan()
             batch = torch.stack([w if isinstance(w, torch.Tensor) else torch.from_numpy(w).to(plan.device) for _, w in chunk])
-        if image_format == "JPEG":  # encoded on the device: the bytes of the image.save below, and only they are downloaded
-            files, _ = converter.spectrogram_images_from_waveforms(batch, as_jpeg=True)
+        if image_format == "JPEG" or png_writer == "device":
+            if image_format == "JPEG":  # encoded on the device: the bytes of the image.save below, and only they are downloaded
+                files, _ = converter.spectrogram_images_from_waveforms(batch, as_jpeg=True)
+            else:  # written on the device: the pixels and EXIF of the image.save below in a stream of its own
+                files, _ = converter.spectrogram_images_from_waveforms(batch, as_png=True, png_mode=png_mode)
             for (path, _), data in zip(chunk, files):
                 with open(os.path.join(output_dir, os.path.splitext(os.path.basename(path))[0] + "." + image_extension), "wb") as f:
                     f.write(data)
@@ -323,7 +345,8 @@ _COMMANDS: T.Dict[str, T.Callable[..., None]] = {
 }
 
 
-_CHOICES = {"inverse_mel": ("sgd", "lstsq"), "frame_engine": ("auto", "chirp-z"), "phase_start": ("random", "peaks")}  # arguments that take one of a few words
+_CHOICES = {"inverse_mel": ("sgd", "lstsq"), "frame_engine": ("auto", "chirp-z"), "phase_start": ("random", "peaks"),
+            "png_writer": ("pillow", "device"), "png_mode": ("rgb", "gray", "auto")}  # arguments that take one of a few words
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -355,6 +378,11 @@ def main(argv: T.Optional[T.Sequence[str]] = None) -> None:
             parser.error(str(e))
         if args["hold_mask"] and not 0.0 <= args["hold_keep_threshold"] <= 1.0:
             parser.error("--hold-keep-threshold must be in [0, 1]")
+    if command in ("audio-to-image", "audio-to-images-batch"):
+        try:
+            _check_png_flags(args["png_writer"], args["png_mode"])
+        except ValueError as e:
+            parser.error(str(e))
     if command == "images-to-audio-batch" and args["griffin_lim_iters"] < -1:
         parser.error("--griffin-lim-iters must be >= 0")
     _COMMANDS[command](**args)

@@ -251,14 +251,15 @@ class SpectrogramImageConverter:
         return audio_util.segment_from_pcm16(joined, self.p.sample_rate)
 
     def spectrogram_images_from_waveforms(self, waveforms: torch.Tensor, return_device: bool = False, *,
-                                          as_jpeg: bool = False) -> T.Tuple[T.Any, T.Any]:
+                                          as_jpeg: bool = False, as_png: bool = False, png_mode: str = "rgb") -> T.Tuple[T.Any, T.Any]:
         """(N, C, samples) float waveforms at int16 scale -> N RGB images and their float32 MAX_VALUEs.  With
         `return_device=True` the (N, n_mels, T, 3) uint8 tensor and the (N,) float32 maxima as they are on the GPU (no copy, no
         synchronisation): the encode side of audio-to-audio's device chain.  With `as_jpeg=True` the images come back as N JPEG
         files (`bytes`), encoded on the device (`jpeg_bytes_from_images`), each with the params and its MAX_VALUE as EXIF: the
-        bytes of `image.save(f, exif=image.getexif(), format="JPEG")` on `spectrogram_image_from_audio`'s image."""
-        if as_jpeg and return_device:
-            raise ValueError("as_jpeg returns files on the host: it does not go with return_device=True")
+        bytes of `image.save(f, exif=image.getexif(), format="JPEG")` on `spectrogram_image_from_audio`'s image.  With
+        `as_png=True` they come back as N PNG files, lossless, written on the device (`png_bytes_from_images` with
+        `mode=png_mode`) with the same EXIF: any reader gets `spectrogram_image_from_audio`'s pixels back."""
+        self._check_file_outputs(as_jpeg, as_png, return_device)
         conv = self.converter
         plan = conv._plan()
         N, C, L = waveforms.shape
@@ -273,6 +274,9 @@ class SpectrogramImageConverter:
         if as_jpeg:
             mx_np = mx.cpu().numpy()
             return self.jpeg_bytes_from_images(img, exif=[self.exif_with_max_value(v) for v in mx_np]), mx_np
+        if as_png:
+            mx_np = mx.cpu().numpy()
+            return self.png_bytes_from_images(img, exif=[self.exif_with_max_value(v) for v in mx_np], mode=png_mode), mx_np
         img_np, mx_np = img.cpu().numpy(), mx.cpu().numpy()
         return [Image.fromarray(a, mode="RGB") for a in img_np], mx_np
 
@@ -324,6 +328,59 @@ class SpectrogramImageConverter:
             chunk = imgs[lo:lo + tiles_per_call]
             for e, scan in zip(exifs[lo:lo + tiles_per_call], plan.jpeg_scans(chunk.to(plan.device), quality)):
                 files.append(b"".join((head, image_util._jpeg_segment(0xE1, e) if e else b"", tail, scan)))
+        return files
+
+    # ---- PNG files from tiles on the device: lossless, the IDAT payload written there (rfx_png_encode_u8) --------------------------
+    @staticmethod
+    def _check_file_outputs(as_jpeg: bool, as_png: bool, return_device: bool) -> None:
+        if as_jpeg and as_png:
+            raise ValueError("as_jpeg and as_png both name the files to return: give one")
+        if (as_jpeg or as_png) and return_device:
+            raise ValueError(f"{'as_jpeg' if as_jpeg else 'as_png'} returns files on the host: it does not go with return_device=True")
+
+    def png_bytes_from_images(self, images: T.Any, exif: T.Any = None, *, mode: str = "rgb", tiles_per_call: int = 64,
+                              optimize: T.Any = None, compress_level: T.Any = None, compress_type: T.Any = None,
+                              bits: T.Any = None) -> T.List[bytes]:
+        """
+        (N, H, W, 3) uint8 tiles (a tensor on any device, or an array) -> N PNG files as `bytes`, lossless: `Image.open` gives
+        the tile's pixels and the EXIF back.  Filtering, the deflate stream (run-length + Huffman, the size of Pillow's
+        `compress_type=zlib.Z_RLE`; csrc/rfx_png_core.h), its Adler-32 and the IDAT chunk's CRC-32 are computed on the device
+        (rfx_png_encode_u8) and only the file's bytes are downloaded; the chunks around the payload are built on the host
+        (`image_util.png_file`) as Pillow lays them out.  The IDAT bytes are NOT zlib's: the file is not byte-equal to Pillow's.
+        `mode`: "rgb" writes colour type 2; "gray" colour type 0 (channel 0) and raises ValueError naming the first tile whose
+        channels differ; "auto" writes each tile grey where R = G = B at every pixel and RGB otherwise, decided on the device.
+        `exif`: None, one `Image.Exif` (or its bytes) for every tile, or a sequence of N.  Pillow's `optimize`, `compress_level`,
+        `compress_type` and `bits` are not implemented: giving one raises ValueError.  The tiles are encoded `tiles_per_call` at
+        a time: the streams' worst-case buffer and the scratch space are about 4 MB per 512 x 512 tile.
+        """
+        for name, value in (("optimize", optimize), ("compress_level", compress_level), ("compress_type", compress_type), ("bits", bits)):
+            if value is not None:
+                raise ValueError(f"png_bytes_from_images writes its own run-length + Huffman stream only: `{name}` is not implemented")
+        if tiles_per_call < 1:
+            raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        if mode not in _hip.PNG_MODES:
+            raise ValueError(f"mode must be one of {sorted(_hip.PNG_MODES)}, got {mode!r}")
+        plan = self.converter._plan()
+        if not isinstance(images, torch.Tensor):
+            images = np.ascontiguousarray(images)
+            images = images if images.flags.writeable else images.copy()  # (torch takes no read-only arrays, such as a PIL image's)
+        imgs = torch.as_tensor(images)
+        if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[-1] != 3:
+            raise ValueError("expected (N, H, W, 3) uint8 images")
+        N, H, W, _ = imgs.shape
+        if exif is None or isinstance(exif, (Image.Exif, bytes, bytearray)):
+            exifs = [image_util.png_exif_bytes(exif)] * N
+        else:
+            exifs = [image_util.png_exif_bytes(e) for e in exif]
+            if len(exifs) != N:
+                raise ValueError(f"{N} images need {N} EXIF entries (or one for all), got {len(exifs)}")
+        files: T.List[bytes] = []
+        for lo in range(0, N, tiles_per_call):
+            streams, crcs, channels = plan.png_streams(imgs[lo:lo + tiles_per_call].to(plan.device), mode)
+            for k, (stream, crc, ch) in enumerate(zip(streams, crcs, channels)):
+                if ch == 0:
+                    raise ValueError(f"mode='gray': tile {lo + k} is not grey (its channels differ); use mode='auto' or 'rgb'")
+                files.append(image_util.png_file(W, H, int(ch), stream, int(crc), exifs[lo + k]))
         return files
 
     # ---- tiles from JPEG files, decoded on the device: np.asarray(Image.open(f).convert("RGB")), byte for byte (rfx_jpeg_decode_u8) --
@@ -378,7 +435,8 @@ class SpectrogramImageConverter:
         return tiles, exifs
 
     def spectrogram_images_from_audio_clips(self, segment: T.Any, clip_start_times: T.Sequence[float], clip_duration_s: float,
-                                            return_device: bool = False, *, as_jpeg: bool = False) -> T.Tuple[T.Any, T.Any]:
+                                            return_device: bool = False, *, as_jpeg: bool = False, as_png: bool = False,
+                                            png_mode: str = "rgb") -> T.Tuple[T.Any, T.Any]:
         """
         One int16 track -> the spectrogram images of its clips: `[spectrogram_image_from_audio(c) for c in
         slice_audio_into_clips(segment.set_frame_rate(params.sample_rate), clip_start_times, clip_duration_s)]`, same image
@@ -393,10 +451,10 @@ class SpectrogramImageConverter:
         `clip_start_times`; with `return_device=True` the (N, n_mels, T, 3) uint8 tensor and the (N,) maxima on the GPU - or,
         when a host-built clip has another width, a list of N (n_mels, T_i, 3) tensors and the (N,) maxima.  With `as_jpeg=True`
         the N images come back as JPEG files (`bytes`) encoded on the device, each with the params and its MAX_VALUE as EXIF, as
-        from `spectrogram_images_from_waveforms`.
+        from `spectrogram_images_from_waveforms`; with `as_png=True` as PNG files written on the device (`png_mode`: the `mode`
+        of `png_bytes_from_images`).
         """
-        if as_jpeg and return_device:
-            raise ValueError("as_jpeg returns files on the host: it does not go with return_device=True")
+        self._check_file_outputs(as_jpeg, as_png, return_device)
         conv = self.converter
         plan = conv._plan()
         if segment.sample_width != 2 or segment.channels not in (1, 2):
@@ -434,14 +492,15 @@ class SpectrogramImageConverter:
             if n and len(r.index) == n:
                 return img, maxima
             return (torch.stack(tiles) if n else torch.empty((0, plan.n_mels, 0, 3), dtype=torch.uint8, device=plan.device)), maxima
-        if as_jpeg:
+        if as_jpeg or as_png:
+            encode = self.jpeg_bytes_from_images if as_jpeg else functools.partial(self.png_bytes_from_images, mode=png_mode)
             mx_np = maxima.cpu().numpy()
             exifs = [self.exif_with_max_value(v) for v in mx_np]
             if n and len(r.index) == n:
-                return self.jpeg_bytes_from_images(img, exif=exifs), mx_np
+                return encode(img, exif=exifs), mx_np
             if same_width:
-                return (self.jpeg_bytes_from_images(torch.stack(tiles), exif=exifs) if n else []), mx_np
-            return [self.jpeg_bytes_from_images(t[None], exif=e)[0] for t, e in zip(tiles, exifs)], mx_np
+                return (encode(torch.stack(tiles), exif=exifs) if n else []), mx_np
+            return [encode(t[None], exif=e)[0] for t, e in zip(tiles, exifs)], mx_np
         return [Image.fromarray(t.cpu().numpy(), mode="RGB") for t in tiles], maxima.cpu().numpy()
 
     # ---- resizing tiles on the device: PIL.Image.resize, byte for byte (rfx_image_resize_u8) --------------------------------

@@ -18,6 +18,7 @@ import functools
 import re
 import struct
 import typing as T
+import zlib
 
 import numpy as np
 from PIL import Image
@@ -202,6 +203,44 @@ def jpeg_header(width: int, height: int, quality: int = 75, exif_bytes: bytes = 
     """
     head, tail = jpeg_header_parts(width, height, quality, qtables)
     return head + (_jpeg_segment(0xE1, bytes(exif_bytes)) if exif_bytes else b"") + tail
+
+
+# ---- PNG: everything of a file but the IDAT payload (the device writes that and its CRC: rfx_png_encode_u8) --------------------
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_MAX_SIZE = 65535  # what rfx_png_encode_u8 takes per axis
+
+
+def _png_chunk(kind: bytes, payload: bytes, crc: T.Optional[int] = None) -> bytes:
+    if len(payload) >= 1 << 31:
+        raise ValueError(f"PNG chunk {kind!r} of {len(payload)} bytes is longer than a chunk holds")
+    return struct.pack(">I", len(payload)) + kind + payload + struct.pack(">I", zlib.crc32(kind + payload) if crc is None else int(crc) & 0xFFFFFFFF)
+
+
+def png_exif_bytes(exif: T.Any) -> bytes:
+    """What Pillow's PNG writer puts into eXIf for its `exif` argument: an `Image.Exif` as `tobytes()`, bytes as they are, either
+    without the b"Exif\\0\\0" prefix; None as none."""
+    data = jpeg_exif_bytes(exif)
+    return data[6:] if data.startswith(b"Exif\x00\x00") else data
+
+
+def png_file(width: int, height: int, channels: int, idat_stream: bytes, idat_crc: T.Optional[int] = None, exif_bytes: bytes = b"") -> bytes:
+    """
+    A PNG file around one IDAT payload, in the layout of Pillow's `Image.save(f, "PNG", exif=...)`: signature, IHDR (bit depth 8,
+    colour type 2 for `channels` 3 and 0 for 1, no interlace), eXIf with `exif_bytes` (a b"Exif\\0\\0" prefix is dropped; empty:
+    no chunk), one IDAT with `idat_stream` (a zlib stream of the filtered rows: rfx_png_encode_u8) and IEND.  `idat_crc`: the
+    CRC-32 of b"IDAT" + idat_stream when the caller has it (the device computes it); None: computed here.
+    """
+    width, height, channels = int(width), int(height), int(channels)
+    if not (1 <= width <= PNG_MAX_SIZE and 1 <= height <= PNG_MAX_SIZE):
+        raise ValueError(f"png_file writes 1 .. {PNG_MAX_SIZE} rows and columns, got {width} x {height}")
+    if channels not in (1, 3):
+        raise ValueError(f"channels must be 3 (RGB) or 1 (grey), got {channels}")
+    exif_bytes = bytes(exif_bytes)
+    if exif_bytes.startswith(b"Exif\x00\x00"):
+        exif_bytes = exif_bytes[6:]
+    ihdr = struct.pack(">IIBBBBB", width, height, 8, 2 if channels == 3 else 0, 0, 0, 0)
+    return b"".join((PNG_SIGNATURE, _png_chunk(b"IHDR", ihdr), _png_chunk(b"eXIf", exif_bytes) if exif_bytes else b"",
+                     _png_chunk(b"IDAT", bytes(idat_stream), idat_crc), _png_chunk(b"IEND", b"")))
 
 
 # ---- JPEG: what a decoder needs of a file before its scan (the device decodes the scan: rfx_jpeg_decode_u8) -------------------
