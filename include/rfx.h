@@ -529,6 +529,53 @@ size_t rfx_spectral_error_workspace_bytes(const rfx_plan* plan, int B, int T);
 int rfx_spectral_error(const rfx_plan* plan, const float* d_wave /* (B, L) */, const float* d_mag_slots, int B, int T,
                        double* d_sums_out /* (B, 2) */, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- LOOP ENCODE: the forward entries on the circular STFT - the analysis half of rfx_loop_call_options -------------------------
+ * A row of a *_loop forward entry is one period of a signal that runs from its end into its start: P = Lw samples, T = P / hop
+ * frames.  With h = n_fft / 2 (integer division) and w the plan's window zero-padded to n_fft, frame t, element i is
+ * x[(hop t + i - h) mod P] w[i]; the plan's real FFT follows.  This is the analysis a loop decode runs inside Griffin-Lim, so the
+ * rfx_griffinlim_loop_output_samples(plan, T) samples a loop decode writes are a legal row and give its T frames back, and a tile
+ * made this way closes: rolling a row by k hop rolls its columns by k, bit for bit.  A frame whose window lies inside [0, P) has the
+ * bytes the plain entry gives for the same samples; only the frames whose window reaches over an end differ (the plain entries read
+ * the reflected signal there, and make one frame more).
+ * Lw must be a positive multiple of hop_length and at least n_fft (the loop decode's rule, hop T >= n_fft: a frame covers the period
+ * at most once).  Any other Lw: RFX_ERR_INVALID before any launch, the outputs untouched, the message naming the nearest legal
+ * lengths below and above ("none" below the smallest one).  Everything else - layouts, outputs, workspace rules, batch invariance,
+ * the refusals - is the plain entry's.  On the device each entry runs the loop twin of the kernel its plain form runs, on all four
+ * frame engines: the same code with the sample position wrapped instead of reflected (the chirp-z engine still refuses a loop
+ * DECODE).  A workspace query answers 0 where the call would be refused; a fused loop entry gives exactly the bytes of its parts. */
+/* frames a loop forward call makes of rows of Lw samples: Lw / hop_length, or 0 where the call would be refused */
+int rfx_stft_loop_frames(const rfx_plan* plan, int Lw);
+/* the length rule of a loop forward call, without a plan or a GPU (tests): RFX_OK, or the RFX_ERR_INVALID a loop forward call on
+ * rows of Lw samples at these parameters gets, with its message */
+int rfx_debug_loop_samples(const rfx_params* params, int Lw);
+/* the nearest legal lengths that message names, as numbers (callers that state them in other units): *below the largest legal
+ * length <= Lw, 0 where there is none; *above the smallest one >= Lw.  For a legal Lw both are Lw. */
+int rfx_debug_loop_nearest_samples(const rfx_params* params, int Lw, int64_t* below, int64_t* above);
+/* rfx_stft on the circular STFT: d_wave (B, Lw) float32 -> T = rfx_stft_loop_frames(plan, Lw) frames per row.  Either output may be NULL. */
+int rfx_stft_loop(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots,
+                  void* stream);
+/* rfx_mel_from_waveform on the circular STFT: d_wave (B, Lw) -> d_mel_out (B, n_mels, T), T = rfx_stft_loop_frames(plan, Lw) */
+size_t rfx_mel_loop_workspace_bytes(const rfx_plan* plan, int B, int Lw);
+int rfx_mel_from_waveform_loop(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mel_out, void* d_workspace,
+                               size_t workspace_bytes, void* stream);
+/* rfx_image_from_waveform on the circular STFT: d_img_out (N, n_mels, T, 3).  Byte-identical to rfx_mel_from_waveform_loop followed
+ * by rfx_image_encode_u8, d_clip_max included. */
+size_t rfx_image_from_waveform_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw);
+int rfx_image_from_waveform_loop(const rfx_plan* plan, const float* d_wave, int N, int stereo, int Lw, const float* d_thresholds255,
+                                 float* d_clip_max, uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream);
+/* rfx_image_from_pcm16_clips on the circular STFT: exactly rfx_pcm16_clips_to_waveform followed by rfx_image_from_waveform_loop,
+ * same bytes.  N == 0 is a no-op. */
+size_t rfx_image_from_pcm16_clips_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw);
+int rfx_image_from_pcm16_clips_loop(const rfx_plan* plan, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts,
+                                    const int64_t* d_starts, int N, int Lw, int stereo, const float* d_thresholds255, float* d_clip_max,
+                                    uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream);
+/* rfx_spectral_error of a loop decode: d_wave (B, hop T) float32 - what a loop decode of T frames writes; a = the magnitude
+ * rfx_stft_loop gives for the row.  The same two double sums per row, the same fixed reduction tree, the same batch invariance and
+ * the same bounded workspace as the plain entry.  T must satisfy the loop decode's rule (rfx_debug_loop_frames). */
+size_t rfx_spectral_error_loop_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_spectral_error_loop(const rfx_plan* plan, const float* d_wave /* (B, hop T) */, const float* d_mag_slots, int B, int T,
+                            double* d_sums_out /* (B, 2) */, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- inverse: torchaudio.transforms.GriffinLim(n_iter, momentum=0.99, rand_init=True, power=1)
  * spectrogram_converter.py:62-73, called at :204.
  * d_mag_slots: magnitudes in slot layout; d_angles0_slots: optional injected initial angles

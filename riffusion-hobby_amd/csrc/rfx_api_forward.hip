@@ -2,11 +2,44 @@
 // the image of a waveform or of int16 clips, and the spectral error of a decode.  Host code only: the drivers that sequence
 // the kernels.
 #include "rfx_api.h"
+#include "rfx_loop_core.h"
 
 using namespace rfx;
 
+// ---- the two forms of every forward entry.  Plain: the row is reflect-padded by n_fft / 2 on both sides (torch.stft center=True) and
+// must be longer than that.  Loop (the *_loop entries; rfx_loop_core.h): the row is one period of exactly hop T samples and is read
+// modulo its length.  Each driver below is written once and takes the form as `loop`; the two differ in the frame count, the length
+// rule and the launcher (the loop twin of the same kernel).
+static int fwd_frames(const rfx_plan* plan, int Lw, bool loop) {
+  return loop ? loop_samples_frames(plan->p.hop_length, plan->p.n_fft, Lw) : stft_frames(plan, Lw);
+}
+static bool fwd_length_ok(const rfx_plan* plan, int Lw, bool loop) {
+  return loop ? loop_samples_valid(plan->p.hop_length, plan->p.n_fft, Lw) : Lw > plan->p.n_fft / 2;
+}
+// the refusal of a row length a loop forward call does not take, with the nearest lengths it does
+static int loop_samples_refusal(int hop, int n_fft, int Lw, const char* who) {
+  if (loop_samples_valid(hop, n_fft, Lw)) return RFX_OK;
+  const long long below = loop_samples_below(hop, n_fft, Lw), above = loop_samples_above(hop, n_fft, Lw);
+  return fail(RFX_ERR_INVALID, std::string(who) + ": a loop call takes rows of one whole period, hop_length * T samples with hop_length * T >= n_fft (hop_length " +
+                                   std::to_string(hop) + ", n_fft " + std::to_string(n_fft) + "), got " + std::to_string(Lw) + ": the nearest legal lengths are " +
+                                   (below ? std::to_string(below) + " (" + std::to_string(below / hop) + " frames)" : std::string("none")) + " below and " +
+                                   std::to_string(above) + " (" + std::to_string(above / hop) + " frames) above");
+}
+int rfx_debug_loop_samples(const rfx_params* params, int Lw) {
+  if (!params || params->hop_length <= 0 || params->n_fft <= 0) return fail(RFX_ERR_INVALID, "rfx_debug_loop_samples: bad argument");
+  return loop_samples_refusal(params->hop_length, params->n_fft, Lw, "rfx_debug_loop_samples");
+}
+int rfx_debug_loop_nearest_samples(const rfx_params* params, int Lw, int64_t* below, int64_t* above) {
+  if (!params || params->hop_length <= 0 || params->n_fft <= 0 || !below || !above)
+    return fail(RFX_ERR_INVALID, "rfx_debug_loop_nearest_samples: bad argument");
+  *below = loop_samples_below(params->hop_length, params->n_fft, Lw);
+  *above = loop_samples_above(params->hop_length, params->n_fft, Lw);
+  return RFX_OK;
+}
+int rfx_stft_loop_frames(const rfx_plan* plan, int Lw) { return plan ? fwd_frames(plan, Lw, true) : 0; }
+
 // the forward transform of a row-family plan (rfx_fam.hip): everything but the outputs of the mode that is launched
-static FamFwdArgs fam_fwd_args(const rfx_plan* plan, const float* d_wave, int B, int Lw) {
+static FamFwdArgs fam_fwd_args(const rfx_plan* plan, const float* d_wave, int B, int Lw, int T) {
   const FamGeom& f = plan->fam;
   FamFwdArgs fa{};
   fa.g = f;
@@ -18,7 +51,7 @@ static FamFwdArgs fam_fwd_args(const rfx_plan* plan, const float* d_wave, int B,
   fa.twa = plan->d_fam_tw + (size_t)f.rows * f.h;
   fa.win = plan->d_win;
   fa.B = B;
-  fa.T = stft_frames(plan, Lw);
+  fa.T = T;
   return fa;
 }
 
@@ -52,20 +85,24 @@ int rfx_unpack_magnitudes(const rfx_plan* plan, const float* d_slots, int B, int
   return RFX_OK;
 }
 
-int rfx_stft(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots,
-             void* stream) {
-  if (!plan || !d_wave || B <= 0) return fail(RFX_ERR_INVALID, "rfx_stft: bad argument");
-  // torch.stft(center=True, pad_mode="reflect") raises when the pad n_fft/2 is not smaller than the input
-  if (Lw <= plan->p.n_fft / 2)
+static int stft_run(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots, void* stream, bool loop) {
+  if (!plan || !d_wave || B <= 0) return fail(RFX_ERR_INVALID, loop ? "rfx_stft_loop: bad argument" : "rfx_stft: bad argument");
+  if (loop) {
+    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, "rfx_stft_loop")) return rc;
+  } else if (Lw <= plan->p.n_fft / 2) {
+    // torch.stft(center=True, pad_mode="reflect") raises when the pad n_fft/2 is not smaller than the input
     return fail(RFX_ERR_INVALID, "rfx_stft: reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
+  }
   RFX_ON_DEVICE(plan->device);
+  const int T = fwd_frames(plan, Lw, loop);
   if (plan->fam_ok) {  // row-family kernels (rfx_fam.hip), same plain layout as the generic engine's
-    FamFwdArgs fa = fam_fwd_args(plan, d_wave, B, Lw);
+    FamFwdArgs fa = fam_fwd_args(plan, d_wave, B, Lw, T);
     fa.mag = d_mag_slots;
     fa.spec = (cf*)d_spec_slots;
     const int nblocks = frame_blocks(fam_slot_count(plan), B, fa.T);
-    if (d_mag_slots) RFX_HIP(launch_fam_fwd(0, fa, nblocks, (hipStream_t)stream));
-    if (d_spec_slots) RFX_HIP(launch_fam_fwd(1, fa, nblocks, (hipStream_t)stream));
+    const auto launch = loop ? launch_fam_fwd_loop : launch_fam_fwd;
+    if (d_mag_slots) RFX_HIP(launch(0, fa, nblocks, (hipStream_t)stream));
+    if (d_spec_slots) RFX_HIP(launch(1, fa, nblocks, (hipStream_t)stream));
     return RFX_OK;
   }
   if (plan->generic) {
@@ -77,15 +114,17 @@ int rfx_stft(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_
     g.mag = d_mag_slots;
     g.spec = (cf*)d_spec_slots;
     g.B = B;
-    g.T = stft_frames(plan, Lw);
+    g.T = T;
     g.Lw = Lw;
     if (plan->czt) {
-      if (d_mag_slots) RFX_HIP(launch_czt_stft(0, g, plan->d_czt_c, plan->d_czt_h, plan->num_cus, (hipStream_t)stream));
-      if (d_spec_slots) RFX_HIP(launch_czt_stft(1, g, plan->d_czt_c, plan->d_czt_h, plan->num_cus, (hipStream_t)stream));
+      const auto launch = loop ? launch_czt_stft_loop : launch_czt_stft;
+      if (d_mag_slots) RFX_HIP(launch(0, g, plan->d_czt_c, plan->d_czt_h, plan->num_cus, (hipStream_t)stream));
+      if (d_spec_slots) RFX_HIP(launch(1, g, plan->d_czt_c, plan->d_czt_h, plan->num_cus, (hipStream_t)stream));
       return RFX_OK;
     }
-    if (d_mag_slots) RFX_HIP(launch_gen_stft(0, g, plan->num_cus, (hipStream_t)stream));
-    if (d_spec_slots) RFX_HIP(launch_gen_stft(1, g, plan->num_cus, (hipStream_t)stream));
+    const auto launch = loop ? launch_gen_stft_loop : launch_gen_stft;
+    if (d_mag_slots) RFX_HIP(launch(0, g, plan->num_cus, (hipStream_t)stream));
+    if (d_spec_slots) RFX_HIP(launch(1, g, plan->num_cus, (hipStream_t)stream));
     return RFX_OK;
   }
   StftArgs a;
@@ -97,14 +136,20 @@ int rfx_stft(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_
   a.win = plan->d_win;
   a.B = B;
   a.Lw = Lw;
-  a.T = 1 + Lw / kHop;
+  a.T = T;
   const long long frames = (long long)B * a.T;
   int fpb = (int)((frames + 2LL * plan->num_cus - 1) / (2LL * plan->num_cus));
   if (fpb < 1) fpb = 1;
   if (fpb > 16) fpb = 16;
   a.frames_per_block = fpb;
-  RFX_HIP(launch_stft(a, (hipStream_t)stream));
+  RFX_HIP(loop ? launch_stft_loop(a, (hipStream_t)stream) : launch_stft(a, (hipStream_t)stream));
   return RFX_OK;
+}
+int rfx_stft(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots, void* stream) {
+  return stft_run(plan, d_wave, B, Lw, d_mag_slots, d_spec_slots, stream, false);
+}
+int rfx_stft_loop(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots, void* stream) {
+  return stft_run(plan, d_wave, B, Lw, d_mag_slots, d_spec_slots, stream, true);
 }
 
 // ---- mel projection -------------------------------------------------------------------------------------------------------------
@@ -123,11 +168,12 @@ static MelLayout mel_layout(const rfx_plan* plan, int B, int T, bool mag_on_chip
   l.total = c.at;
   return l;
 }
-static MelLayout mel_forward_layout(const rfx_plan* plan, int B, int Lw) {
-  if (Lw <= plan->p.n_fft / 2) return MelLayout{};
-  return mel_layout(plan, B, stft_frames(plan, Lw), !plan->generic && plan->fwd_ok && !plan->fwd_unfused);
+static MelLayout mel_forward_layout(const rfx_plan* plan, int B, int Lw, bool loop) {
+  if (!fwd_length_ok(plan, Lw, loop)) return MelLayout{};
+  return mel_layout(plan, B, fwd_frames(plan, Lw, loop), !plan->generic && plan->fwd_ok && !plan->fwd_unfused);
 }
-size_t rfx_mel_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? mel_forward_layout(plan, B, Lw).total : 0; }
+size_t rfx_mel_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? mel_forward_layout(plan, B, Lw, false).total : 0; }
+size_t rfx_mel_loop_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? mel_forward_layout(plan, B, Lw, true).total : 0; }
 size_t rfx_mel_scale_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? mel_layout(plan, B, T, false).total : 0; }
 
 // does the plan's forward path leave the mel amplitudes frame-major ([B*T][Mpad]) in the workspace before transposing them?
@@ -161,31 +207,35 @@ static int gen_mel(const rfx_plan* plan, const float* mag, float* mel_tm, int B,
 // rfx_mel_from_waveform, and the front half of rfx_image_from_waveform: there d_mel_out is null (no (B, M, T) copy is made),
 // *mel_tm_out receives the frame-major amplitudes and - where the kernel can take it on the fly - max_keys the keys of the maxima its
 // workgroups formed, *keys_per_row of them for every row, rows in order (0: it did not; up to T per row: image_keys_bytes)
+// loop: the *_loop form of either (rows of one period, the loop twins of the same kernels)
 static int mel_forward(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mel_out, void* d_workspace, size_t workspace_bytes,
-                       void* stream_, float** mel_tm_out, unsigned* max_keys, int max_group, int* keys_per_row) {
-  if (!plan || !d_wave || !d_workspace || (!d_mel_out && !mel_tm_out)) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform: null argument");
-  if (!plan->d_melfb) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform: plan was created without a mel filterbank");
-  const MelLayout w = mel_forward_layout(plan, B, Lw);
-  if (workspace_bytes < w.total || Lw <= plan->p.n_fft / 2)
-    return fail(Lw <= plan->p.n_fft / 2 ? RFX_ERR_INVALID : RFX_ERR_WORKSPACE, "rfx_mel_from_waveform: input too short or workspace too small");
+                       void* stream_, float** mel_tm_out, unsigned* max_keys, int max_group, int* keys_per_row, bool loop) {
+  const std::string who = loop ? "rfx_mel_from_waveform_loop" : "rfx_mel_from_waveform";
+  if (!plan || !d_wave || !d_workspace || (!d_mel_out && !mel_tm_out)) return fail(RFX_ERR_INVALID, who + ": null argument");
+  if (!plan->d_melfb) return fail(RFX_ERR_INVALID, who + ": plan was created without a mel filterbank");
+  if (loop)
+    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who.c_str())) return rc;
+  const MelLayout w = mel_forward_layout(plan, B, Lw, loop);
+  if (workspace_bytes < w.total || !fwd_length_ok(plan, Lw, loop))
+    return fail(!fwd_length_ok(plan, Lw, loop) ? RFX_ERR_INVALID : RFX_ERR_WORKSPACE, who + ": input too short or workspace too small");
   RFX_ON_DEVICE(plan->device);
   hipStream_t stream = (hipStream_t)stream_;
   float* mag = (float*)((char*)d_workspace + w.mag);
   float* mel_tm = (float*)((char*)d_workspace + w.mel_tm);
-  const int T = stft_frames(plan, Lw);
+  const int T = fwd_frames(plan, Lw, loop);
   if (plan->generic) {
-    if (!plan->fwd_ok) return fail(RFX_ERR_UNSUPPORTED, "rfx_mel_from_waveform: filterbank is not banded: " + plan->imel_why);
+    if (!plan->fwd_ok) return fail(RFX_ERR_UNSUPPORTED, who + ": filterbank is not banded: " + plan->imel_why);
     const bool fused = plan->fam_ok && !plan->fwd_unfused;
     if (fused) {  // row family: transform and banded projection in one kernel, |X| stays on chip
-      FamFwdArgs fa = fam_fwd_args(plan, d_wave, B, Lw);
+      FamFwdArgs fa = fam_fwd_args(plan, d_wave, B, Lw, T);
       fa.mel_tm = mel_tm;
       fa.band_wt = plan->d_band_wt;
       fa.band_lo = plan->d_band_lo;
       fa.band_len = plan->d_band_lo + plan->Mpad;
       fa.M = plan->p.n_mels;
       fa.Mpad = plan->Mpad;
-      RFX_HIP(launch_fam_fwd(2, fa, frame_blocks(fam_slot_count(plan), B, T), stream));
-    } else if (int rc = rfx_stft(plan, d_wave, B, Lw, mag, nullptr, stream)) {
+      RFX_HIP((loop ? launch_fam_fwd_loop : launch_fam_fwd)(2, fa, frame_blocks(fam_slot_count(plan), B, T), stream));
+    } else if (int rc = stft_run(plan, d_wave, B, Lw, mag, nullptr, stream, loop)) {
       return rc;
     }
     if (mel_tm_out) *mel_tm_out = mel_tm;
@@ -235,18 +285,23 @@ static int mel_forward(const rfx_plan* plan, const float* d_wave, int B, int Lw,
       f.run_skew = shape_ok && d > 0 && d < f.frames_per_block ? d : 0;
       if (keys_per_row) *keys_per_row = f.max_keys ? chunks : 0;
     }
-    RFX_HIP(launch_stft_mel(f, stream));
+    RFX_HIP(loop ? launch_stft_mel_loop(f, stream) : launch_stft_mel(f, stream));
     return RFX_OK;
   }
-  if (!d_mel_out) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform: this plan's forward path has no frame-major stage");
-  if (int rc = rfx_stft(plan, d_wave, B, Lw, mag, nullptr, stream)) return rc;
+  if (!d_mel_out) return fail(RFX_ERR_INVALID, who + ": this plan's forward path has no frame-major stage");
+  if (int rc = stft_run(plan, d_wave, B, Lw, mag, nullptr, stream, loop)) return rc;
   return mel_gemm(plan, mag, B, T, d_mel_out, stream);
 }
 
 int rfx_mel_from_waveform(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mel_out, void* d_workspace,
                           size_t workspace_bytes, void* stream) {
   if (!d_mel_out) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform: null argument");
-  return mel_forward(plan, d_wave, B, Lw, d_mel_out, d_workspace, workspace_bytes, stream, nullptr, nullptr, 1, nullptr);
+  return mel_forward(plan, d_wave, B, Lw, d_mel_out, d_workspace, workspace_bytes, stream, nullptr, nullptr, 1, nullptr, false);
+}
+int rfx_mel_from_waveform_loop(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mel_out, void* d_workspace,
+                               size_t workspace_bytes, void* stream) {
+  if (!d_mel_out) return fail(RFX_ERR_INVALID, "rfx_mel_from_waveform_loop: null argument");
+  return mel_forward(plan, d_wave, B, Lw, d_mel_out, d_workspace, workspace_bytes, stream, nullptr, nullptr, 1, nullptr, true);
 }
 
 // ---- spectrogram_image_from_audio's device half (spectrogram_image_converter.py:30-51: spectrogram_from_audio, then
@@ -256,42 +311,50 @@ int rfx_mel_from_waveform(const rfx_plan* plan, const float* d_wave, int B, int 
 struct ImageFwdLayout {
   size_t keys, mel, total;  // keys is also the size of the forward path's part, which starts the workspace
 };
-static ImageFwdLayout image_from_waveform_layout(const rfx_plan* plan, int N, int stereo, int Lw) {
+static ImageFwdLayout image_from_waveform_layout(const rfx_plan* plan, int N, int stereo, int Lw, bool loop) {
   ImageFwdLayout l{};
   if (N <= 0) return l;
   const int B = N * (stereo ? 2 : 1);
   Carve c;
-  c.at = mel_forward_layout(plan, B, Lw).total;
+  c.at = mel_forward_layout(plan, B, Lw, loop).total;
   if (!c.at) return l;
-  const size_t T = (size_t)stft_frames(plan, Lw);
+  const size_t T = (size_t)fwd_frames(plan, Lw, loop);
   l.keys = c.take((size_t)B * T * sizeof(unsigned));
   l.mel = c.take(forward_has_frame_major(plan) ? 0 : (size_t)B * plan->p.n_mels * T * sizeof(float));
   l.total = c.at;
   return l;
 }
 size_t rfx_image_from_waveform_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw) {
-  return plan ? image_from_waveform_layout(plan, N, stereo, Lw).total : 0;
+  return plan ? image_from_waveform_layout(plan, N, stereo, Lw, false).total : 0;
+}
+size_t rfx_image_from_waveform_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw) {
+  return plan ? image_from_waveform_layout(plan, N, stereo, Lw, true).total : 0;
 }
 
-int rfx_image_from_waveform(const rfx_plan* plan, const float* d_wave, int N, int stereo, int Lw, const float* d_thresholds255,
-                            float* d_clip_max, uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+static int image_from_waveform_run(const rfx_plan* plan, const float* d_wave, int N, int stereo, int Lw, const float* d_thresholds255, float* d_clip_max,
+                                   uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream, bool loop) {
+  const std::string who = loop ? "rfx_image_from_waveform_loop" : "rfx_image_from_waveform";
   if (!plan || !d_wave || !d_thresholds255 || !d_clip_max || !d_img_out || !d_workspace || N <= 0)
-    return fail(RFX_ERR_INVALID, "rfx_image_from_waveform: bad argument");
-  if (!plan->d_melfb) return fail(RFX_ERR_INVALID, "rfx_image_from_waveform: plan was created without a mel filterbank");
-  if (Lw <= plan->p.n_fft / 2) return fail(RFX_ERR_INVALID, "rfx_image_from_waveform: input too short");
-  const ImageFwdLayout w = image_from_waveform_layout(plan, N, stereo, Lw);
-  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_image_from_waveform: workspace too small");
+    return fail(RFX_ERR_INVALID, who + ": bad argument");
+  if (!plan->d_melfb) return fail(RFX_ERR_INVALID, who + ": plan was created without a mel filterbank");
+  if (loop) {
+    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who.c_str())) return rc;
+  } else if (Lw <= plan->p.n_fft / 2) {
+    return fail(RFX_ERR_INVALID, "rfx_image_from_waveform: input too short");
+  }
+  const ImageFwdLayout w = image_from_waveform_layout(plan, N, stereo, Lw, loop);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, who + ": workspace too small");
   RFX_ON_DEVICE(plan->device);
-  const int C = stereo ? 2 : 1, B = N * C, T = stft_frames(plan, Lw), M = plan->p.n_mels;
+  const int C = stereo ? 2 : 1, B = N * C, T = fwd_frames(plan, Lw, loop), M = plan->p.n_mels;
   unsigned* keys = reinterpret_cast<unsigned*>((char*)d_workspace + w.keys);
   if (!forward_has_frame_major(plan)) {  // (dense-GEMM fall-back of a non-banded bank: the two calls, the tensor in the workspace)
     float* mel = reinterpret_cast<float*>((char*)d_workspace + w.mel);
-    if (int rc = rfx_mel_from_waveform(plan, d_wave, B, Lw, mel, d_workspace, w.keys, stream)) return rc;
+    if (int rc = mel_forward(plan, d_wave, B, Lw, mel, d_workspace, w.keys, stream, nullptr, nullptr, 1, nullptr, loop)) return rc;
     return rfx_image_encode_u8(mel, N, M, T, stereo, d_thresholds255, d_clip_max, d_img_out, stream);
   }
   float* mel_tm = nullptr;
   int keys_per_row = 0;  // (round 6: one key per workgroup of the forward kernel, every one written by the launch: nothing to zero)
-  if (int rc = mel_forward(plan, d_wave, B, Lw, nullptr, d_workspace, w.keys, stream, &mel_tm, keys, C, &keys_per_row)) return rc;
+  if (int rc = mel_forward(plan, d_wave, B, Lw, nullptr, d_workspace, w.keys, stream, &mel_tm, keys, C, &keys_per_row, loop)) return rc;
   // (a kernel that does not take the maximum on the fly: one pass over the frame-major amplitudes; their padding columns are zero
   // and mel amplitudes are not negative)
   if (!keys_per_row) RFX_HIP(launch_clip_max(mel_tm, reinterpret_cast<float*>(keys), N, (size_t)C * T * plan->Mpad, false, (hipStream_t)stream));
@@ -299,16 +362,24 @@ int rfx_image_from_waveform(const rfx_plan* plan, const float* d_wave, int N, in
                                  d_thresholds255, d_img_out, d_clip_max, N, M, plan->Mpad, T, C, (hipStream_t)stream));
   return RFX_OK;
 }
+int rfx_image_from_waveform(const rfx_plan* plan, const float* d_wave, int N, int stereo, int Lw, const float* d_thresholds255,
+                            float* d_clip_max, uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return image_from_waveform_run(plan, d_wave, N, stereo, Lw, d_thresholds255, d_clip_max, d_img_out, d_workspace, workspace_bytes, stream, false);
+}
+int rfx_image_from_waveform_loop(const rfx_plan* plan, const float* d_wave, int N, int stereo, int Lw, const float* d_thresholds255,
+                                 float* d_clip_max, uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return image_from_waveform_run(plan, d_wave, N, stereo, Lw, d_thresholds255, d_clip_max, d_img_out, d_workspace, workspace_bytes, stream, true);
+}
 
 // ---- the same from int16 clips of one recording (rfx_pcm_in.hip): the gathered (N*C, Lw) float32 rows, then the workspace of
 // rfx_image_from_waveform
 struct ImagePcmLayout {
   size_t wave, fwd, fwd_bytes, total;
 };
-static ImagePcmLayout image_from_pcm16_clips_layout(const rfx_plan* plan, int N, int stereo, int Lw) {
+static ImagePcmLayout image_from_pcm16_clips_layout(const rfx_plan* plan, int N, int stereo, int Lw, bool loop) {
   ImagePcmLayout l{};
   if (N <= 0 || Lw <= 0) return l;
-  l.fwd_bytes = image_from_waveform_layout(plan, N, stereo, Lw).total;
+  l.fwd_bytes = image_from_waveform_layout(plan, N, stereo, Lw, loop).total;
   if (!l.fwd_bytes) return l;
   Carve c;
   l.wave = c.take((size_t)N * (stereo ? 2 : 1) * Lw * sizeof(float));
@@ -317,27 +388,47 @@ static ImagePcmLayout image_from_pcm16_clips_layout(const rfx_plan* plan, int N,
   return l;
 }
 size_t rfx_image_from_pcm16_clips_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw) {
-  return plan ? image_from_pcm16_clips_layout(plan, N, stereo, Lw).total : 0;
+  return plan ? image_from_pcm16_clips_layout(plan, N, stereo, Lw, false).total : 0;
+}
+size_t rfx_image_from_pcm16_clips_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int Lw) {
+  return plan ? image_from_pcm16_clips_layout(plan, N, stereo, Lw, true).total : 0;
 }
 
-int rfx_image_from_pcm16_clips(const rfx_plan* plan, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts,
-                               const int64_t* d_starts, int N, int Lw, int stereo, const float* d_thresholds255, float* d_clip_max,
-                               uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream) {
-  if (N < 0) return fail(RFX_ERR_INVALID, "rfx_image_from_pcm16_clips: N is negative");
+static int image_from_pcm16_clips_run(const rfx_plan* plan, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts,
+                                      const int64_t* d_starts, int N, int Lw, int stereo, const float* d_thresholds255, float* d_clip_max,
+                                      uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream, bool loop) {
+  const std::string who = loop ? "rfx_image_from_pcm16_clips_loop" : "rfx_image_from_pcm16_clips";
+  if (N < 0) return fail(RFX_ERR_INVALID, who + ": N is negative");
   if (N == 0) return RFX_OK;
   const int C = stereo ? 2 : 1;
-  if (int rc = check_pcm_clips("rfx_image_from_pcm16_clips", d_pcm, frames, in_channels, h_starts, N, Lw, C)) return rc;
+  if (int rc = check_pcm_clips(who.c_str(), d_pcm, frames, in_channels, h_starts, N, Lw, C)) return rc;
   if (!plan || !d_starts || !d_thresholds255 || !d_clip_max || !d_img_out || !d_workspace)
-    return fail(RFX_ERR_INVALID, "rfx_image_from_pcm16_clips: null pointer");
-  if (Lw <= plan->p.n_fft / 2) return fail(RFX_ERR_INVALID, "rfx_image_from_pcm16_clips: clips too short");
-  const ImagePcmLayout w = image_from_pcm16_clips_layout(plan, N, stereo, Lw);
-  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, "rfx_image_from_pcm16_clips: workspace too small");
+    return fail(RFX_ERR_INVALID, who + ": null pointer");
+  if (loop) {
+    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who.c_str())) return rc;
+  } else if (Lw <= plan->p.n_fft / 2) {
+    return fail(RFX_ERR_INVALID, "rfx_image_from_pcm16_clips: clips too short");
+  }
+  const ImagePcmLayout w = image_from_pcm16_clips_layout(plan, N, stereo, Lw, loop);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, who + ": workspace too small");
   float* wave = reinterpret_cast<float*>((char*)d_workspace + w.wave);
   {
     RFX_ON_DEVICE(plan->device);
     RFX_HIP(launch_pcm_clips(d_pcm, in_channels, d_starts, N, Lw, C, wave, (hipStream_t)stream));
   }
-  return rfx_image_from_waveform(plan, wave, N, stereo, Lw, d_thresholds255, d_clip_max, d_img_out, (char*)d_workspace + w.fwd, w.fwd_bytes, stream);
+  return image_from_waveform_run(plan, wave, N, stereo, Lw, d_thresholds255, d_clip_max, d_img_out, (char*)d_workspace + w.fwd, w.fwd_bytes, stream, loop);
+}
+int rfx_image_from_pcm16_clips(const rfx_plan* plan, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts,
+                               const int64_t* d_starts, int N, int Lw, int stereo, const float* d_thresholds255, float* d_clip_max,
+                               uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return image_from_pcm16_clips_run(plan, d_pcm, frames, in_channels, h_starts, d_starts, N, Lw, stereo, d_thresholds255, d_clip_max, d_img_out, d_workspace,
+                                    workspace_bytes, stream, false);
+}
+int rfx_image_from_pcm16_clips_loop(const rfx_plan* plan, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts,
+                                    const int64_t* d_starts, int N, int Lw, int stereo, const float* d_thresholds255, float* d_clip_max,
+                                    uint8_t* d_img_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return image_from_pcm16_clips_run(plan, d_pcm, frames, in_channels, h_starts, d_starts, N, Lw, stereo, d_thresholds255, d_clip_max, d_img_out, d_workspace,
+                                    workspace_bytes, stream, true);
 }
 
 int rfx_mel_scale(const rfx_plan* plan, const float* d_lin_bft, int B, int T, float* d_mel_out, void* d_workspace,
@@ -368,9 +459,10 @@ struct SpectralErrorLayout {
   size_t mag, partials, total;
   int group_rows;
 };
-static SpectralErrorLayout spectral_error_layout(const rfx_plan* plan, int B, int T) {
+static SpectralErrorLayout spectral_error_layout(const rfx_plan* plan, int B, int T, bool loop) {
   SpectralErrorLayout l{};
   if (B <= 0 || T < 2) return l;
+  if (loop && (!loop_valid(plan->p.hop_length, T, plan->p.n_fft) || (long long)plan->p.hop_length * T > 0x7fffffffLL)) return l;
   const size_t row_bytes = (size_t)T * plan->frame_stride * sizeof(float);
   size_t rows = kQualGroupBytes / row_bytes;
   rows = rows < 1 ? 1 : rows > (size_t)B ? (size_t)B : rows;
@@ -381,32 +473,51 @@ static SpectralErrorLayout spectral_error_layout(const rfx_plan* plan, int B, in
   l.total = c.at;
   return l;
 }
-size_t rfx_spectral_error_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? spectral_error_layout(plan, B, T).total : 0; }
+size_t rfx_spectral_error_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? spectral_error_layout(plan, B, T, false).total : 0; }
+size_t rfx_spectral_error_loop_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? spectral_error_layout(plan, B, T, true).total : 0; }
 
-int rfx_spectral_error(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out,
-                       void* d_workspace, size_t workspace_bytes, void* stream) {
-  if (B < 0) return fail(RFX_ERR_INVALID, "rfx_spectral_error: B is negative");
+// loop: d_wave rows are the hop T samples of a loop decode, transformed by the loop forward call (stft_run)
+static int spectral_error_run(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out, void* d_workspace,
+                              size_t workspace_bytes, void* stream, bool loop) {
+  const std::string who = loop ? "rfx_spectral_error_loop" : "rfx_spectral_error";
+  if (B < 0) return fail(RFX_ERR_INVALID, who + ": B is negative");
   if (B == 0) return RFX_OK;
-  if (!plan || !d_wave || !d_mag_slots || !d_sums_out || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_spectral_error: null argument");
-  if (T < 2) return fail(RFX_ERR_INVALID, "rfx_spectral_error: T must be at least 2");
-  const int L = rfx_griffinlim_output_samples(plan, T);
-  if (L <= plan->p.n_fft / 2 || stft_frames(plan, L) != T)
-    return fail(RFX_ERR_INVALID, "rfx_spectral_error: the " + std::to_string(L) + " samples of " + std::to_string(T) +
-                                     " frames are not more than the forward transform's reflect padding, n_fft/2 = " + std::to_string(plan->p.n_fft / 2));
+  if (!plan || !d_wave || !d_mag_slots || !d_sums_out || !d_workspace) return fail(RFX_ERR_INVALID, who + ": null argument");
+  if (T < 2) return fail(RFX_ERR_INVALID, who + ": T must be at least 2");
+  int L;
+  if (loop) {
+    const long long P = (long long)plan->p.hop_length * T;
+    if (P > 0x7fffffffLL) return fail(RFX_ERR_INVALID, who + ": hop_length * T does not fit an int");
+    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, (int)P, who.c_str())) return rc;
+    L = (int)P;
+  } else {
+    L = rfx_griffinlim_output_samples(plan, T);
+    if (L <= plan->p.n_fft / 2 || stft_frames(plan, L) != T)
+      return fail(RFX_ERR_INVALID, "rfx_spectral_error: the " + std::to_string(L) + " samples of " + std::to_string(T) +
+                                       " frames are not more than the forward transform's reflect padding, n_fft/2 = " + std::to_string(plan->p.n_fft / 2));
+  }
   if (((uintptr_t)d_mag_slots | (uintptr_t)d_workspace) & 15 || ((uintptr_t)d_sums_out & 7) || (plan->frame_stride & 3))
-    return fail(RFX_ERR_INVALID, "rfx_spectral_error: d_mag_slots and d_workspace must be 16-byte aligned, d_sums_out 8-byte aligned");
-  const SpectralErrorLayout w = spectral_error_layout(plan, B, T);
+    return fail(RFX_ERR_INVALID, who + ": d_mag_slots and d_workspace must be 16-byte aligned, d_sums_out 8-byte aligned");
+  const SpectralErrorLayout w = spectral_error_layout(plan, B, T, loop);
   if (workspace_bytes < w.total)
-    return fail(RFX_ERR_WORKSPACE, "rfx_spectral_error: workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(w.total) + " needed)");
+    return fail(RFX_ERR_WORKSPACE, who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(w.total) + " needed)");
   RFX_ON_DEVICE(plan->device);
   float* mag = reinterpret_cast<float*>((char*)d_workspace + w.mag);
   void* partials = (char*)d_workspace + w.partials;
   const size_t row_elems = (size_t)T * plan->frame_stride;
   for (int r0 = 0; r0 < B; r0 += w.group_rows) {
     const int rows = B - r0 < w.group_rows ? B - r0 : w.group_rows;
-    if (int rc = rfx_stft(plan, d_wave + (size_t)r0 * L, rows, L, mag, nullptr, stream)) return rc;
+    if (int rc = stft_run(plan, d_wave + (size_t)r0 * L, rows, L, mag, nullptr, stream, loop)) return rc;
     RFX_HIP(launch_spectral_sums(mag, d_mag_slots + (size_t)r0 * row_elems, rows, T, plan->frame_stride, plan->n_stft, plan->generic, partials,
                                  d_sums_out + 2 * (size_t)r0, (hipStream_t)stream));
   }
   return RFX_OK;
+}
+int rfx_spectral_error(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out,
+                       void* d_workspace, size_t workspace_bytes, void* stream) {
+  return spectral_error_run(plan, d_wave, d_mag_slots, B, T, d_sums_out, d_workspace, workspace_bytes, stream, false);
+}
+int rfx_spectral_error_loop(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out,
+                            void* d_workspace, size_t workspace_bytes, void* stream) {
+  return spectral_error_run(plan, d_wave, d_mag_slots, B, T, d_sums_out, d_workspace, workspace_bytes, stream, true);
 }

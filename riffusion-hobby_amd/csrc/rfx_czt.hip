@@ -13,10 +13,16 @@
 #ifndef RFX_CZT_LIST_TU
 #define RFX_CZT_LIST_TU 0
 #endif
+// ... and a third time as rfx_czt_loop.hip (`#define RFX_CZT_LOOP_TU 1`, then this file), which holds only the forward kernels of a loop
+// call - czt_stft_loop_kernel, the row read modulo its length (include/rfx.h: rfx_stft_loop) - and their launcher.
+#ifndef RFX_CZT_LOOP_TU
+#define RFX_CZT_LOOP_TU 0
+#endif
 #include <hip/hip_runtime.h>
 
 #include "rfx_czt_core.h"
 #include "rfx_kernels.h"
+#include "rfx_loop_core.h"
 
 namespace rfx {
 
@@ -88,7 +94,8 @@ __device__ __forceinline__ void czt_conv(const GenGeom& g, const CztLds& l, cons
 
 // step 1 on the analysis frame t of x (- mom xp): windowed, zero-padded (reflect-padded signal like torch.stft center=True), packed
 // two reals per complex when n_fft is even, times the chirp.  Only the elements the window covers need loads; global loads of a
-// batch first, then its LDS stores.
+// batch first, then its LDS stores.  LOOP (czt_stft_loop_kernel): the row is one period of L samples, read modulo L (rfx_loop_core.h).
+template <bool LOOP = false>
 __device__ __forceinline__ void czt_load_frame(const GenGeom& g, cf* buf, const float* __restrict__ x, const float* __restrict__ xp, float mom, int L,
                                                int t, const float* __restrict__ win, const cf* __restrict__ c) {
   const int nthr = (int)blockDim.x, half = g.n_fft / 2;
@@ -111,7 +118,7 @@ __device__ __forceinline__ void czt_load_frame(const GenGeom& g, cf* buf, const 
           const int i = per * n + e;  // position inside the padded frame
           const int j = i - g.left;   // position inside the window
           if (j >= 0 && j < g.win) {
-            const int p = reflect_index(g.hop * t + i - half, L);
+            const int p = LOOP ? loop_read_index(g.hop * t + i - half, L) : reflect_index(g.hop * t + i - half, L);
             xs[u][e] = x[p];
             if (xp) ps[u][e] = xp[p];
             ws[u][e] = win[j];
@@ -139,57 +146,13 @@ struct CztTab {
 // ---- forward: frame fr of clip b is centred on sample hop*fr of the reflect-padded waveform (torch.stft center=True)
 enum CztStftMode { kCztMag = 0, kCztSpec = 1 };
 
-// (two waves per SIMD = 256 VGPRs for every radix class: a kernel holds the forward AND the inverse passes - the Griffin-Lim kernel
-// two of each - and under the generic engine's 128-register bound of the 2 / 3 / 5 / 7 classes the compiler spilled 180 - 370 bytes per
-// thread inside the frame loop, whatever the batch sizes below.  One 512-thread workgroup per CU then; the buffer of the lengths this
-// engine is for - 137 KB at n_fft 17028 - leaves no room for a second one anyway)
-template <int MODE, int MAXR>
-__global__ void __launch_bounds__(kCztThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-czt_stft_kernel(GenStftArgs a, CztTab ct) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const GenGeom& g = a.g;
-  const CztLds l = czt_lds(smem, g, a.tb);
-  const long long nframes = (long long)a.B * a.T;
-  const int nthr = (int)blockDim.x;
-  for (long long fr = blockIdx.x; fr < nframes; fr += gridDim.x) {
-    const int clip = (int)(fr / a.T), t = (int)(fr - (long long)clip * a.T);
-    __syncthreads();  // previous frame's epilogue is done with the buffer
-    czt_load_frame(g, l.a, a.wave + (size_t)clip * a.wave_stride, nullptr, 0.f, a.Lw, t, a.tb.win, ct.c);
-    czt_conv<MAXR>(g, l, a.tb.tw, ct.h);
-    const size_t base = (size_t)fr * g.fs;
-    constexpr int UB = RFX_CZT_BATCH;
-    for (int k0 = threadIdx.x; k0 < g.fs; k0 += UB * nthr) {
-      int ea[UB], eb[UB];
-      cf ca[UB], cb[UB], za[UB], zb[UB];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int k = k0 + u * nthr;
-        const int kk = k < g.n_stft ? k : 0;
-        ea[u] = czt_bin_elem_a(g, kk);
-        eb[u] = czt_bin_elem_b(g, kk);
-        ca[u] = ct.c[ea[u]];
-        cb[u] = ct.c[eb[u]];
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        za[u] = l.a[gen_ipad(ea[u], g.pad_shift)];
-        zb[u] = l.a[gen_ipad(eb[u], g.pad_shift)];
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int k = k0 + u * nthr;
-        if (k >= g.fs) continue;
-        cf X{0.f, 0.f};  // padding of the frame stride: keep it zero
-        if (k < g.n_stft) X = czt_bin_vals(g, za[u], ca[u], zb[u], cb[u], l.lo2, l.hi2, k);
-        if (MODE == kCztMag) a.mag[base + k] = sqrtf(fmaf(X.re, X.re, X.im * X.im));
-        if (MODE == kCztSpec) a.spec[base + k] = X;
-      }
-    }
-  }
-}
+#define RFX_FWDK_LOOP RFX_CZT_LOOP_TU  // this unit: czt_stft_kernel; rfx_czt_loop.hip: czt_stft_loop_kernel
+#include "rfx_czt_stft_kernel.hip.h"
+#undef RFX_FWDK_LOOP
 
 #endif  // !RFX_CZT_LIST_TU
 
+#if !RFX_CZT_LOOP_TU
 // ---- Griffin-Lim, one iteration for one frame per trip.  MODE 0: Z = S * angles0 (injected or drawn) -> synthesis;
 // MODE 1: analysis of x_cur (the fold forms d = x_k - m x_{k-1}); MODE 2: analysis of x_cur - m x_prev
 // RFX_CZT_LIST_TU (a held call's launches 1 .. n_iter): trip i of the loop takes frame list[i], list[B T] trips in all
@@ -313,6 +276,7 @@ czt_gl_kernel(GenGlArgs a, CztTab ct) {
     }
   }
 }
+#endif  // !RFX_CZT_LOOP_TU
 
 // --------------------------------------------------------------------------------------------------------------------
 static int czt_grid(const GenGeom& g, int num_cus, long long nframes) {
@@ -337,6 +301,32 @@ hipError_t prepare_czt_list_kernels(const GenGeom& g) {
 hipError_t launch_czt_gl_list(const GenGlArgs& a, const int* list, const cf* chirp, const cf* h, int num_cus, hipStream_t stream) {
   const int grid = czt_grid(a.g, num_cus, (long long)a.B * a.T);
   hipLaunchKernelGGL(czt_gl_list_fn(a.g), dim3(grid), dim3(a.g.nthr), czt_lds_bytes(a.g), stream, a, CztTab{chirp, h}, list);
+  return hipGetLastError();
+}
+#elif RFX_CZT_LOOP_TU
+// the forward kernels of a loop call by (mode, radix class of the pass length)
+using CztStftFn = void (*)(GenStftArgs, CztTab);
+template <int MAXR>
+static CztStftFn czt_stft_loop_fn(int mode) {
+  return mode == kCztMag ? czt_stft_loop_kernel<kCztMag, MAXR> : czt_stft_loop_kernel<kCztSpec, MAXR>;
+}
+static CztStftFn czt_stft_loop_fn(const GenGeom& g, int mode) {
+#ifdef RFX_CZT_CLASS
+  return czt_stft_loop_fn<RFX_CZT_CLASS>(mode);
+#else
+  const int c = gen_radix_class(g.radix, g.nstages);
+  return c == 5 ? czt_stft_loop_fn<5>(mode) : c == 7 ? czt_stft_loop_fn<7>(mode) : czt_stft_loop_fn<13>(mode);
+#endif
+}
+hipError_t prepare_czt_loop_kernels(const GenGeom& g) {
+  hipError_t e;
+  for (int mode = 0; mode < 2; ++mode)
+    if ((e = hipFuncSetAttribute((const void*)czt_stft_loop_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, (int)czt_lds_bytes(g))) != hipSuccess) return e;
+  return hipSuccess;
+}
+hipError_t launch_czt_stft_loop(int mode, const GenStftArgs& a, const cf* chirp, const cf* h, int num_cus, hipStream_t stream) {
+  const int grid = czt_grid(a.g, num_cus, (long long)a.B * a.T);
+  hipLaunchKernelGGL(czt_stft_loop_fn(a.g, mode), dim3(grid), dim3(a.g.nthr), czt_lds_bytes(a.g), stream, a, CztTab{chirp, h});
   return hipGetLastError();
 }
 #else

@@ -100,49 +100,12 @@ __device__ __forceinline__ cf* gen_fft(const GenGeom& g, const GenLds& l, const 
 // ---- forward: frame fr of clip b is centred on sample hop*fr of the reflect-padded waveform (torch.stft center=True)
 enum GenStftMode { kGenMag = 0, kGenSpec = 1 };
 
-// (Prefetching the next frame's samples and the epilogue's |S| / tprev into register slots across the passes was tried:
-// 229 -> 245-257 ms per 64 tiles at 48 kHz - the slot arrays spill.  The simple loops below stay.)
-// (four waves per SIMD = 128 VGPRs, so that two 512-thread workgroups share a CU: without the bound the compiler took 169
-// registers for the batched butterflies and the second workgroup no longer fitted - 121 -> 182 ms per 64 tiles at 48 kHz;
-// the O(R^2) radix-11 / 13 class keeps its larger budget)
-template <int MODE, int MAXR>
-__global__ void __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(MAXR <= 7 ? 4 : 2)))
-gen_stft_kernel(GenStftArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const GenGeom& g = a.g;
-  const GenLds l = gen_lds(smem, g, a.tb);
-  const long long nframes = (long long)a.B * a.T;
-  const int half = g.n_fft / 2;
-  for (long long fr = blockIdx.x; fr < nframes; fr += gridDim.x) {
-    const int clip = (int)(fr / a.T), t = (int)(fr - (long long)clip * a.T);
-    const float* __restrict__ x = a.wave + (size_t)clip * a.wave_stride;
-    __syncthreads();  // previous frame's epilogue is done with the buffers
-    // windowed, zero-padded frame, packed two reals per complex when n_fft is even
-    for (int n = threadIdx.x; n < g.nc; n += blockDim.x) {
-      float v[2] = {0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        if (!g.even && e == 1) break;
-        const int i = g.even ? 2 * n + e : n;  // position inside the padded frame
-        const int j = i - g.left;              // position inside the window
-        if (j >= 0 && j < g.win) v[e] = x[reflect_index(g.hop * t + i - half, a.Lw)] * a.tb.win[j];
-      }
-      l.a[RFX_GEN_INPLACE ? gen_ipad(n, g.pad_shift) : gen_pad(n)] = cf{v[0], v[1]};
-    }
-    const cf* Z = gen_fft<false, MAXR>(g, l, a.tb.tw);
-    const size_t base = (size_t)fr * g.fs;
-    for (int k = threadIdx.x; k < g.fs; k += blockDim.x) {
-      if (k >= g.n_stft) {  // padding of the frame stride: keep it zero
-        if (MODE == kGenMag) a.mag[base + k] = 0.f;
-        if (MODE == kGenSpec) a.spec[base + k] = cf{0.f, 0.f};
-        continue;
-      }
-      const cf X = gen_split_forward(g, Z, l.lo2, l.hi2, k, RFX_GEN_INPLACE ? a.tb.rev : nullptr);
-      if (MODE == kGenMag) a.mag[base + k] = sqrtf(fmaf(X.re, X.re, X.im * X.im));
-      if (MODE == kGenSpec) a.spec[base + k] = X;
-    }
-  }
-}
+#define RFX_FWDK_LOOP 0
+#include "rfx_gen_stft_kernel.hip.h"
+#undef RFX_FWDK_LOOP
+#define RFX_FWDK_LOOP 1
+#include "rfx_gen_stft_kernel.hip.h"
+#undef RFX_FWDK_LOOP
 
 // ---- Griffin-Lim, one iteration for one frame per trip.  MODE 0: Z = S * angles0 (injected or drawn) -> synthesis;
 // MODE 1: analysis of x_0 (no momentum term yet); MODE 2: analysis of x_k - m x_{k-1}.
@@ -376,6 +339,15 @@ static GenStftFn gen_stft_fn(const GenGeom& g, int mode) {
   const int c = gen_radix_class(g.radix, g.nstages);
   return c == 5 ? gen_stft_fn<5>(mode) : c == 7 ? gen_stft_fn<7>(mode) : gen_stft_fn<13>(mode);
 }
+// ... and their twins of a loop forward call
+template <int MAXR>
+static GenStftFn gen_stft_loop_fn(int mode) {
+  return mode == kGenMag ? gen_stft_loop_kernel<kGenMag, MAXR> : gen_stft_loop_kernel<kGenSpec, MAXR>;
+}
+static GenStftFn gen_stft_loop_fn(const GenGeom& g, int mode) {
+  const int c = gen_radix_class(g.radix, g.nstages);
+  return c == 5 ? gen_stft_loop_fn<5>(mode) : c == 7 ? gen_stft_loop_fn<7>(mode) : gen_stft_loop_fn<13>(mode);
+}
 template <int MAXR>
 static GenGlFn gen_gl_fn(int mode) {
   return mode == 0 ? gen_gl_kernel<0, MAXR> : mode == 1 ? gen_gl_kernel<1, MAXR> : gen_gl_kernel<2, MAXR>;
@@ -401,6 +373,8 @@ hipError_t prepare_generic_kernels(const GenGeom& g) {
   if ((e = hipFuncSetAttribute((const void*)gen_gl_loop_fn(g), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   for (int mode = 0; mode < 2; ++mode)
     if ((e = hipFuncSetAttribute((const void*)gen_stft_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
+  for (int mode = 0; mode < 2; ++mode)
+    if ((e = hipFuncSetAttribute((const void*)gen_stft_loop_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   for (int mode = 0; mode < 3; ++mode)
     if ((e = hipFuncSetAttribute((const void*)gen_gl_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)gen_gl_list_fn(g), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -409,6 +383,12 @@ hipError_t prepare_generic_kernels(const GenGeom& g) {
 hipError_t launch_gen_stft(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream) {
   const int grid = gen_grid(a.g, num_cus, (long long)a.B * a.T);
   hipLaunchKernelGGL(gen_stft_fn(a.g, mode), dim3(grid), dim3(a.g.nthr), gen_lds_bytes(a.g), stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_stft_loop(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream) {
+  const int grid = gen_grid(a.g, num_cus, (long long)a.B * a.T);
+  hipLaunchKernelGGL(gen_stft_loop_fn(a.g, mode), dim3(grid), dim3(a.g.nthr), gen_lds_bytes(a.g), stream, a);
   return hipGetLastError();
 }
 

@@ -134,6 +134,8 @@ struct StftArgs {
   int B, T, Lw, frames_per_block;
 };
 hipError_t launch_stft(const StftArgs& a, hipStream_t stream);
+// a loop forward call (include/rfx.h: rfx_stft_loop): Lw = hop T is the row's period, read modulo Lw (rfx_loop_core.h: loop_read_index)
+hipError_t launch_stft_loop(const StftArgs& a, hipStream_t stream);
 
 // fused forward path: waveform -> framed transform -> |X| -> banded mel projection, nothing but the (B, M, T) mel
 // amplitudes leaves the chip.  Valid for banded filterbanks (every filter's support one contiguous run of bins).
@@ -178,6 +180,7 @@ constexpr int kMelPadsPerThread = 4;
 constexpr unsigned kKbMaskLow = 0x1F001Fu, kKbMaskAll = 0x1FFFFFu;
 constexpr int kMelProdArr = 8192;  // floats between the w0 and the w1 product arrays whenever the first one ends below it (a compile-time LDS offset for the packed form)
 hipError_t launch_stft_mel(const StftMelArgs& a, hipStream_t stream);
+hipError_t launch_stft_mel_loop(const StftMelArgs& a, hipStream_t stream);  // a loop forward call: Lw = hop T, the row read modulo Lw
 
 // mel projection GEMM: out[b][m][t] = sum_p fbs[p][m] * mag[b*T+t][p]
 struct MelArgs {
@@ -341,6 +344,7 @@ struct GenGlArgs {
 hipError_t prepare_generic_kernels(const GenGeom& g);
 size_t gen_lds_bytes(const GenGeom& g);
 hipError_t launch_gen_stft(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream);  // mode 0 mag, 1 spec
+hipError_t launch_gen_stft_loop(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream);  // a loop forward call: Lw = hop T, the row read modulo Lw
 hipError_t launch_gen_gl(int mode, const GenGlArgs& a, int num_cus, hipStream_t stream);      // mode 0 init, 1 first iteration, 2 iteration
 hipError_t launch_gen_gl_list(const GenGlArgs& a, const int* list, int num_cus, hipStream_t stream);  // mode 1 over a free-frame list (launch_gl_frame_list)
 hipError_t launch_gen_env(const float* win, float* env, const GenGeom& g, int T, int L, hipStream_t stream);  // env[p] = sum_t w[j]^2, once per call
@@ -365,6 +369,9 @@ hipError_t launch_czt_gl(int mode, const GenGlArgs& a, const cf* chirp, const cf
 // mode 1 over a free-frame list (launch_gl_frame_list); a translation unit of their own (rfx_czt_list.hip)
 hipError_t prepare_czt_list_kernels(const GenGeom& g);
 hipError_t launch_czt_gl_list(const GenGlArgs& a, const int* list, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);
+// the forward kernels of a loop call (Lw = hop T, the row read modulo Lw); a translation unit of their own as well (rfx_czt_loop.hip)
+hipError_t prepare_czt_loop_kernels(const GenGeom& g);
+hipError_t launch_czt_stft_loop(int mode, const GenStftArgs& a, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);  // mode 0 mag, 1 spec
 hipError_t launch_mel_transpose(const float* mel_tm, float* mel, int B, int T, int M, int Mpad, hipStream_t stream);
 
 // ---- row-family Griffin-Lim (rfx_fam.hip): n_fft = 40 h, win_length = 10 h; frames are folded by launch_gen_fold
@@ -410,6 +417,7 @@ struct FamFwdArgs {
   int M, Mpad;
 };
 hipError_t launch_fam_fwd(int mode, const FamFwdArgs& a, int nblocks, hipStream_t stream);
+hipError_t launch_fam_fwd_loop(int mode, const FamFwdArgs& a, int nblocks, hipStream_t stream);  // a loop forward call: Lw = hop T, the row read modulo Lw
 hipError_t prepare_fam_kernels(const FamGeom& g);
 size_t fam_lds_bytes(const FamGeom& g);         // dynamic: the cube
 size_t fam_static_lds_bytes(const FamGeom& g);  // static: the pass-A twiddles where they fit

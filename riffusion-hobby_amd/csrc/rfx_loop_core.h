@@ -1,5 +1,6 @@
-// rfx_loop_core.h - index rules and envelope of a LOOP decode (include/rfx.h: rfx_loop_call_options), written once for the gfx950
-// kernels (hipcc) and the host emulator of the CPU tests (tests/emu/rfx_loop_emu.cpp, g++).
+// rfx_loop_core.h - index rules and envelope of a LOOP decode (include/rfx.h: rfx_loop_call_options) and the read position and length
+// rule of a LOOP ENCODE (rfx_stft_loop and the other *_loop forward entries), written once for the gfx950 kernels (hipcc) and the host
+// emulators of the CPU tests (tests/emu/rfx_loop_emu.cpp, tests/emu/rfx_loop_fwd_emu.cpp, g++).
 //
 // A loop call treats a row of T frames as the STFT of a signal with period P = hop T.  With h = n_fft / 2, left = (n_fft - win) / 2
 // and the window w zero-padded to n_fft:
@@ -27,6 +28,27 @@ RFX_HD int loop_wrap(int p, int P) {
   if (p < 0) p += P;
   if (p >= P) p -= P;
   return p;
+}
+
+// ---- LOOP ENCODE: the analysis above as the forward entries run it (include/rfx.h: rfx_stft_loop).  A forward frame kernel forms
+// the unwrapped position p = hop t + i - h of what it reads in its own way - the specialised engine as hop blocks t - 5 .. t + 4,
+// the others as window sample j at hop t + left + j - h - and reads the row at loop_read_index(p, P) where its plain twin reads
+// reflect_index(p, Lw).  That is the whole difference between the two.  With P >= n_fft and t in [0, T] (a run's prefetch looks one
+// frame past the row's end) every p lies in [-P, 2 P).
+RFX_HD int loop_read_index(int p, int P) { return loop_wrap(p, P); }
+
+// a loop forward call takes rows of exactly P samples: a positive multiple of hop, at least n_fft (the loop decode's rule:
+// P = hop T, loop_valid(hop, T, n_fft)); it makes P / hop frames
+RFX_HD bool loop_samples_valid(int hop, int n_fft, long long P) { return P > 0 && P % hop == 0 && P >= n_fft; }
+RFX_HD int loop_samples_frames(int hop, int n_fft, long long P) { return loop_samples_valid(hop, n_fft, P) ? (int)(P / hop) : 0; }
+// the nearest legal lengths: the largest one <= P (0: there is none) and the smallest one >= P
+RFX_HD long long loop_samples_below(int hop, int n_fft, long long P) {
+  const long long lo = (long long)hop * loop_min_frames(hop, n_fft);
+  return P < lo ? 0 : P / hop * hop;
+}
+RFX_HD long long loop_samples_above(int hop, int n_fft, long long P) {
+  const long long lo = (long long)hop * loop_min_frames(hop, n_fft);
+  return P <= lo ? lo : (P + hop - 1) / hop * hop;
 }
 
 // floor(a / b), b > 0

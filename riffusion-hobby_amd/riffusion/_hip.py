@@ -261,6 +261,31 @@ def check_loop_frames(hop_length: int, n_fft: int, Tn: int) -> None:
         raise ValueError(f"a loop decode needs hop_length * T >= n_fft ({hop_length} * T >= {n_fft}): at least {need} frames, got {Tn}")
 
 
+def check_loop_samples(hop_length: int, n_fft: int, samples: int) -> None:
+    """ValueError for rows of `samples` samples a loop forward call does not take - anything but a positive multiple of hop_length that
+    is at least n_fft: the library's own refusal (rfx_debug_loop_samples: RFX_ERR_INVALID with the nearest legal lengths below and
+    above), raised before any device work"""
+    lib = load_library()
+    samples = int(samples)
+    if not -2 ** 31 <= samples < 2 ** 31:
+        raise ValueError(f"a loop call's rows of {samples} samples do not fit the library's int")
+    cp = RfxParams(0, int(n_fft), 0, int(hop_length), 0, 0)
+    if lib.rfx_debug_loop_samples(ctypes.byref(cp), samples) != 0:
+        msg = lib.rfx_last_error()
+        raise ValueError(msg.decode() if msg else "rfx_debug_loop_samples refused the length")
+
+
+def loop_nearest_samples(hop_length: int, n_fft: int, samples: int) -> T.Tuple[int, int]:
+    """(below, above): the nearest row lengths a loop forward call takes, as the library states them (rfx_debug_loop_nearest_samples) -
+    the largest legal length <= samples (0: there is none) and the smallest one >= samples"""
+    cp = RfxParams(0, int(n_fft), 0, int(hop_length), 0, 0)
+    below, above = ctypes.c_int64(0), ctypes.c_int64(0)
+    if not -2 ** 31 <= int(samples) < 2 ** 31:
+        raise ValueError(f"a loop call's rows of {samples} samples do not fit the library's int")
+    check(load_library().rfx_debug_loop_nearest_samples(ctypes.byref(cp), int(samples), ctypes.byref(below), ctypes.byref(above)))
+    return int(below.value), int(above.value)
+
+
 def check_inverse_mel(inverse_mel: str) -> bool:
     """True for "lstsq", False for "sgd"; anything else raises."""
     if inverse_mel not in INVERSE_MEL_FORMS:
@@ -342,6 +367,20 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_stft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rfx_spectral_error_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_error": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # loop encode: the forward entries on the circular STFT
+    "rfx_stft_loop_frames": (c_int, [c_void_p, c_int]),
+    "rfx_debug_loop_samples": (c_int, [c_void_p, c_int]),
+    "rfx_debug_loop_nearest_samples": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "rfx_stft_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rfx_mel_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_mel_from_waveform_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_image_from_waveform_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_image_from_waveform_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_image_from_pcm16_clips_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_image_from_pcm16_clips_loop": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_spectral_error_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_spectral_error_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_griffinlim_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
@@ -805,20 +844,30 @@ class Plan:
         check(self.lib.rfx_unpack_complex(self.handle, slots.data_ptr(), B, Tn, out.data_ptr(), self._stream()))
         return out
 
-    def stft(self, wave: torch.Tensor, want_mag: bool, want_spec: bool):
-        wave = self._chk(wave, torch.float32)
-        B, Lw = wave.shape
+    def _forward_frames(self, Lw: int, shape: T.Sequence[int], loop: bool) -> int:
+        """frames a forward call makes of rows of Lw samples, or the call's refusal before any device work.  Plain: torch.stft's count,
+        1 + (Lw + 2*(n_fft//2) - n_fft) // hop, and its error for a row no longer than the reflect padding.  loop: the row is one
+        period of exactly hop * T samples, T = Lw // hop (`check_loop_samples`)."""
+        if loop:
+            check_loop_samples(self.hop_length, self.n_fft, Lw)
+            return self.lib.rfx_stft_loop_frames(self.handle, Lw)
         if Lw <= self.n_fft // 2:
             # same condition under which torch.stft(pad_mode="reflect") raises in the reference
             raise RuntimeError(
                 f"Argument #4: Padding size should be less than the corresponding input dimension, "
-                f"but got: padding ({self.n_fft // 2}, {self.n_fft // 2}) at dimension 2 of input {list(wave.shape)}"
+                f"but got: padding ({self.n_fft // 2}, {self.n_fft // 2}) at dimension 2 of input {list(shape)}"
             )
-        Tn = self.lib.rfx_stft_frames(self.handle, Lw)  # torch.stft's count: 1 + (Lw + 2*(n_fft//2) - n_fft) // hop
+        return self.lib.rfx_stft_frames(self.handle, Lw)
+
+    def stft(self, wave: torch.Tensor, want_mag: bool, want_spec: bool, loop: bool = False):
+        """rfx_stft, or with `loop` rfx_stft_loop: the rows are whole periods and the transform is circular"""
+        wave = self._chk(wave, torch.float32)
+        B, Lw = wave.shape
+        Tn = self._forward_frames(Lw, wave.shape, loop)
         mag = torch.empty((B * Tn, self.frame_stride), dtype=torch.float32, device=wave.device) if want_mag else None
         spec = torch.empty((B * Tn, self.frame_stride), dtype=torch.complex64, device=wave.device) if want_spec else None
         check(
-            self.lib.rfx_stft(
+            (self.lib.rfx_stft_loop if loop else self.lib.rfx_stft)(
                 self.handle,
                 wave.data_ptr(),
                 B,
@@ -951,14 +1000,17 @@ class Plan:
             )
         return out
 
-    def spectral_error(self, wave: torch.Tensor, mag_slots: torch.Tensor, B: int, Tn: int) -> torch.Tensor:
+    def spectral_error(self, wave: torch.Tensor, mag_slots: torch.Tensor, B: int, Tn: int, loop: bool = False) -> torch.Tensor:
         """rfx_spectral_error: (B, L) waveforms, L = the samples Griffin-Lim makes of Tn frames, against magnitudes in slot layout
         -> (B, 2) float64, per row sum (|STFT(wave)| - mag)^2 and sum mag^2 over every bin of every frame once.  A row's two
-        sums do not depend on the batch it is computed in.  Spectral convergence is sqrt(sums[:, 0] / sums[:, 1])."""
+        sums do not depend on the batch it is computed in.  Spectral convergence is sqrt(sums[:, 0] / sums[:, 1]).
+        loop (rfx_spectral_error_loop): the rows are the hop * Tn samples of a loop decode and the STFT is the circular one."""
         wave = self._chk(wave, torch.float32)
         mag_slots = self._chk(mag_slots, torch.float32)
         B, Tn = int(B), int(Tn)
-        L = self.lib.rfx_griffinlim_output_samples(self.handle, Tn)
+        if loop:
+            check_loop_frames(self.hop_length, self.n_fft, Tn)
+        L = self.output_samples(Tn, loop)
         if tuple(wave.shape) != (B, L):
             raise ValueError(f"{B} rows of {Tn} frames are waveforms of shape {(B, L)}, got {tuple(wave.shape)}")
         if mag_slots.numel() < B * Tn * self.frame_stride:
@@ -966,8 +1018,10 @@ class Plan:
         sums = torch.empty((B, 2), dtype=torch.float64, device=self.device)
         if B == 0:
             return sums
-        with self._workspace(max(1, self.lib.rfx_spectral_error_workspace_bytes(self.handle, B, Tn))) as ws:
-            check(self.lib.rfx_spectral_error(self.handle, wave.data_ptr(), mag_slots.data_ptr(), B, Tn, sums.data_ptr(), ws.data_ptr(),
+        query, entry = ((self.lib.rfx_spectral_error_loop_workspace_bytes, self.lib.rfx_spectral_error_loop) if loop
+                        else (self.lib.rfx_spectral_error_workspace_bytes, self.lib.rfx_spectral_error))
+        with self._workspace(max(1, query(self.handle, B, Tn))) as ws:
+            check(entry(self.handle, wave.data_ptr(), mag_slots.data_ptr(), B, Tn, sums.data_ptr(), ws.data_ptr(),
                                               ws.numel(), self._stream()))
         return sums
 
@@ -977,21 +1031,17 @@ class Plan:
         check(self.lib.rfx_unpack_magnitudes(self.handle, slots.data_ptr(), B, Tn, out.data_ptr(), self._stream()))
         return out
 
-    def mel_from_waveform(self, wave: torch.Tensor) -> torch.Tensor:
-        """spectrogram_converter.py:165-185 on the device: (B, Lw) -> (B, n_mels, T)."""
+    def mel_from_waveform(self, wave: torch.Tensor, loop: bool = False) -> torch.Tensor:
+        """spectrogram_converter.py:165-185 on the device: (B, Lw) -> (B, n_mels, T).  loop (rfx_mel_from_waveform_loop): the rows
+        are whole periods of hop * T samples and the transform is circular."""
         wave = self._chk(wave, torch.float32)
         B, Lw = wave.shape
-        if Lw <= self.n_fft // 2:
-            raise RuntimeError(
-                f"Argument #4: Padding size should be less than the corresponding input dimension, "
-                f"but got: padding ({self.n_fft // 2}, {self.n_fft // 2}) at dimension 2 of input {list(wave.shape)}"
-            )
-        Tn = self.lib.rfx_stft_frames(self.handle, Lw)
-        need = self.lib.rfx_mel_workspace_bytes(self.handle, B, Lw)
+        Tn = self._forward_frames(Lw, wave.shape, loop)
+        need = (self.lib.rfx_mel_loop_workspace_bytes if loop else self.lib.rfx_mel_workspace_bytes)(self.handle, B, Lw)
         out = torch.empty((B, self.n_mels, Tn), dtype=torch.float32, device=wave.device)
         with self._workspace(need) as ws:
             check(
-                self.lib.rfx_mel_from_waveform(
+                (self.lib.rfx_mel_from_waveform_loop if loop else self.lib.rfx_mel_from_waveform)(
                     self.handle, wave.data_ptr(), B, Lw, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()
                 )
             )
@@ -1289,27 +1339,25 @@ class Plan:
                                                       int(normalize), peak.data_ptr(), pcm.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
         return pcm, peak
 
-    def image_from_waveform(self, wave: torch.Tensor, stereo: bool, thresholds: torch.Tensor):
+    def image_from_waveform(self, wave: torch.Tensor, stereo: bool, thresholds: torch.Tensor, loop: bool = False):
         """spectrogram_image_converter.py:30-51 on the device: (N*C, Lw) float32 -> ((N, n_mels, T, 3) uint8, per-clip max (N,));
-        `mel_from_waveform` + `image_encode` in one call, byte for byte, without the (N*C, n_mels, T) tensor in between."""
+        `mel_from_waveform` + `image_encode` in one call, byte for byte, without the (N*C, n_mels, T) tensor in between.
+        loop (rfx_image_from_waveform_loop): the rows are whole periods of hop * T samples and the transform is circular."""
         wave = self._chk(wave, torch.float32)
         thresholds = self._chk(thresholds, torch.float32)
         C = 2 if stereo else 1
         NC, Lw = wave.shape
         if NC % C:
             raise ValueError("batch must be a multiple of the channel count")
-        if Lw <= self.n_fft // 2:
-            raise RuntimeError(
-                f"Argument #4: Padding size should be less than the corresponding input dimension, "
-                f"but got: padding ({self.n_fft // 2}, {self.n_fft // 2}) at dimension 2 of input {list(wave.shape)}"
-            )
+        Tn = self._forward_frames(Lw, wave.shape, loop)
         N = NC // C
-        Tn = self.lib.rfx_stft_frames(self.handle, Lw)
         img = torch.empty((N, self.n_mels, Tn, 3), dtype=torch.uint8, device=wave.device)
         mx = torch.empty((N,), dtype=torch.float32, device=wave.device)
-        with self._workspace(self.lib.rfx_image_from_waveform_workspace_bytes(self.handle, N, int(stereo), Lw)) as ws:
-            check(self.lib.rfx_image_from_waveform(self.handle, wave.data_ptr(), N, int(stereo), Lw, thresholds.data_ptr(), mx.data_ptr(),
-                                                   img.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        query, entry = ((self.lib.rfx_image_from_waveform_loop_workspace_bytes, self.lib.rfx_image_from_waveform_loop) if loop
+                        else (self.lib.rfx_image_from_waveform_workspace_bytes, self.lib.rfx_image_from_waveform))
+        with self._workspace(query(self.handle, N, int(stereo), Lw)) as ws:
+            check(entry(self.handle, wave.data_ptr(), N, int(stereo), Lw, thresholds.data_ptr(), mx.data_ptr(),
+                        img.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         return img, mx
 
     def pcm16(self, wave: torch.Tensor, channels: int, normalize: bool = True, out: T.Optional[torch.Tensor] = None):
@@ -1471,30 +1519,30 @@ class Plan:
                                                    out.data_ptr(), self._stream()))
         return out
 
-    def image_from_pcm_clips(self, pcm: torch.Tensor, starts: T.Any, Lw: int, stereo: bool, thresholds: torch.Tensor):
+    def image_from_pcm_clips(self, pcm: torch.Tensor, starts: T.Any, Lw: int, stereo: bool, thresholds: torch.Tensor, loop: bool = False):
         """`clips_to_waveform` (to 2 channels when `stereo`, else 1) + `image_from_waveform` in one call
         (rfx_image_from_pcm16_clips), same bytes: (frames, C) int16 -> ((N, n_mels, T, 3) uint8, per-clip max (N,)).  The float
-        waveforms live in the call's workspace only."""
+        waveforms live in the call's workspace only.  loop (rfx_image_from_pcm16_clips_loop): every clip is a whole period of
+        Lw = hop * T frames and the transform is circular."""
         pcm = self._chk_pcm(pcm)
         thresholds = self._chk(thresholds, torch.float32)
         L, C = pcm.shape
         Lw = int(Lw)
+        if loop:
+            check_loop_samples(self.hop_length, self.n_fft, Lw)
         host, dev = self._clip_starts(starts, Lw)
         N = int(host.numel())
-        if Lw <= self.n_fft // 2:
-            raise RuntimeError(
-                f"Argument #4: Padding size should be less than the corresponding input dimension, "
-                f"but got: padding ({self.n_fft // 2}, {self.n_fft // 2}) at dimension 2 of input {[N * (2 if stereo else 1), Lw]}"
-            )
-        Tn = self.lib.rfx_stft_frames(self.handle, Lw)
+        Tn = self._forward_frames(Lw, [N * (2 if stereo else 1), Lw], loop)
         img = torch.empty((N, self.n_mels, Tn, 3), dtype=torch.uint8, device=self.device)
         mx = torch.empty((N,), dtype=torch.float32, device=self.device)
         if N == 0:
             return img, mx
-        with self._workspace(self.lib.rfx_image_from_pcm16_clips_workspace_bytes(self.handle, N, int(stereo), Lw)) as ws:
-            check(self.lib.rfx_image_from_pcm16_clips(self.handle, pcm.data_ptr(), L, C, host.data_ptr(), dev.data_ptr(), N, Lw, int(stereo),
-                                                      thresholds.data_ptr(), mx.data_ptr(), img.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                      self._stream()))
+        query, entry = ((self.lib.rfx_image_from_pcm16_clips_loop_workspace_bytes, self.lib.rfx_image_from_pcm16_clips_loop) if loop
+                        else (self.lib.rfx_image_from_pcm16_clips_workspace_bytes, self.lib.rfx_image_from_pcm16_clips))
+        with self._workspace(query(self.handle, N, int(stereo), Lw)) as ws:
+            check(entry(self.handle, pcm.data_ptr(), L, C, host.data_ptr(), dev.data_ptr(), N, Lw, int(stereo),
+                        thresholds.data_ptr(), mx.data_ptr(), img.data_ptr(), ws.data_ptr(), ws.numel(),
+                        self._stream()))
         return img, mx
 
 

@@ -49,10 +49,13 @@ def _params_from_image(image: Image.Image) -> SpectrogramParams:
 def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_frequencies: int = 512, min_frequency: int = 0,
                    max_frequency: int = 10000, window_duration_ms: int = 100, padded_duration_ms: int = 400,
                    power_for_image: float = 0.25, stereo: bool = False, device: str = "cuda", frame_engine: str = "auto",
-                   png_writer: str = "pillow", png_mode: str = "rgb") -> None:
+                   png_writer: str = "pillow", png_mode: str = "rgb", loop: bool = False) -> None:
     """Encode one clip; --frame-engine chirp-z runs a sample rate / padded duration whose FFT length has a prime factor above 13.
     --png-writer device writes the PNG on the GPU (lossless: the same pixels and EXIF, not Pillow's bytes; the size of zlib's Z_RLE
-    strategy); with it --png-mode gray or auto writes a mono tile as greyscale, 0.63 of the RGB file."""
+    strategy); with it --png-mode gray or auto writes a mono tile as greyscale, 0.63 of the RGB file.
+    --loop: the clip is a loop - it is encoded on the circular STFT, its end running into its start, and gives one column per hop
+    (a 5.12 s clip at 44.1 kHz: 512 columns) that image-to-audio --loop decodes to the same length.  The clip must be a whole number of
+    hops long, at least the padded duration: any other length is refused with the nearest legal lengths; nothing is trimmed or padded."""
     _check_png_flags(png_writer, png_mode)
     segment = _load_segment(audio)
     params = SpectrogramParams(
@@ -61,7 +64,7 @@ def audio_to_image(*, audio: str, image: str, step_size_ms: int = 10, num_freque
         max_frequency=max_frequency, num_frequencies=num_frequencies, power_for_image=power_for_image,
     )
     converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
-    pil_image = converter.spectrogram_image_from_audio(segment)
+    pil_image = converter.spectrogram_image_from_audio(segment, loop=loop)
     if png_writer == "device":
         data = converter.png_bytes_from_images(np.asarray(pil_image)[None], exif=pil_image.getexif(), mode=png_mode)[0]
         with open(image, "wb") as f:
@@ -89,7 +92,8 @@ _FLAG_WORDING = {
 }
 
 
-def _check_image_to_audio(*, guide_audio: str, hold_head_ms: int, hold_tail_ms: int, hold_mask: str, loop: bool, phase_start: str, **_: T.Any) -> None:
+def _check_image_to_audio(*, guide_audio: str, hold_head_ms: int, hold_tail_ms: int, hold_mask: str, loop: bool, phase_start: str,
+                          print_error: bool = False, **_: T.Any) -> None:
     """ValueError for flags of image-to-audio that do not go together (the function raises it, the parser reports it)"""
     from riffusion import _hip
 
@@ -97,11 +101,14 @@ def _check_image_to_audio(*, guide_audio: str, hold_head_ms: int, hold_tail_ms: 
                           hold_ms=(hold_head_ms or hold_tail_ms) or None, hold_mask=hold_mask or None)
     if hold_head_ms < 0 or hold_tail_ms < 0:
         raise ValueError("--hold-head-ms / --hold-tail-ms must be >= 0")
+    if print_error and not loop:
+        raise ValueError("--print-error needs --loop: it prints the circular spectral convergence of a loop decode")
 
 
 def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto",
                    guide_audio: str = "", griffin_lim_iters: int = -1, hold_head_ms: int = 0, hold_tail_ms: int = 0,
-                   hold_mask: str = "", hold_keep_threshold: float = 0.5, loop: bool = False, phase_start: str = "random") -> None:
+                   hold_mask: str = "", hold_keep_threshold: float = 0.5, loop: bool = False, phase_start: str = "random",
+                   print_error: bool = False) -> None:
     """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD,
     --frame-engine chirp-z runs parameters whose FFT length has a prime factor above 13 (refused otherwise).
     --guide-audio FILE starts Griffin-Lim from the phase of that clip (audio-to-audio: the clip the tile was made of; it must be at
@@ -114,9 +121,11 @@ def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel:
     --loop: the tile is a loop - Griffin-Lim runs on the circular STFT and the clip (hop * width samples) runs from its end into its
     start without a click; the tile needs n_fft / hop columns (40 at the defaults).  Not with --hold-head-ms / --hold-tail-ms / --hold-mask.
     --phase-start peaks starts Griffin-Lim from phases built from the tile's own magnitudes (spectral peaks, their frequencies
-    integrated over the hop) instead of random ones: for a tile without a guide and few --griffin-lim-iters.  Not with --guide-audio."""
+    integrated over the hop) instead of random ones: for a tile without a guide and few --griffin-lim-iters.  Not with --guide-audio.
+    --print-error, with --loop: prints the decode's circular spectral convergence, || |STFT(x)| - S || / || S || of the clip Griffin-Lim
+    made against the magnitudes it was given, the STFT being the circular one of a loop encode, measured on the device."""
     _check_image_to_audio(guide_audio=guide_audio, hold_head_ms=hold_head_ms, hold_tail_ms=hold_tail_ms, hold_mask=hold_mask, loop=loop,
-                          phase_start=phase_start)
+                          phase_start=phase_start, print_error=print_error)
     pil_image = Image.open(image)
     params = _params_from_image(pil_image)
     converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
@@ -126,7 +135,10 @@ def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel:
                                                      hold_frames=params.hold_frames_for(hold_head_ms / 1000.0, hold_tail_ms / 1000.0)
                                                      if hold_head_ms or hold_tail_ms else None,
                                                      hold_mask=image_util.hold_mask_from_image(Image.open(hold_mask), hold_keep_threshold)
-                                                     if hold_mask else None, loop=loop, phase_start=phase_start)
+                                                     if hold_mask else None, loop=loop, phase_start=phase_start, return_loop_error=print_error)
+    if print_error:
+        segment, error = segment
+        print(f"Spectral convergence (circular STFT): {error:.6f}")
     segment.export(audio, format=os.path.splitext(audio)[1][1:] or "wav")
     print(f"Wrote {audio} ({segment.duration_seconds:.2f} seconds)")
 
@@ -385,6 +397,13 @@ def main(argv: T.Optional[T.Sequence[str]] = None) -> None:
             parser.error(str(e))
     if command == "images-to-audio-batch" and args["griffin_lim_iters"] < -1:
         parser.error("--griffin-lim-iters must be >= 0")
+    if command == "audio-to-image" and args["loop"]:
+        from riffusion.spectrogram_converter import LoopLengthError
+
+        try:  # (a clip that is no whole loop is a usage error: the message names the nearest lengths that are)
+            return audio_to_image(**args)
+        except LoopLengthError as e:
+            parser.error(str(e))
     _COMMANDS[command](**args)
 
 

@@ -84,6 +84,10 @@ CALL_WORDING = {
 }
 
 
+class LoopLengthError(ValueError):
+    """a clip that is no whole loop at the params: not a whole number of hops, or shorter than n_fft"""
+
+
 class SpectrogramConverter:
     def __init__(self, params: SpectrogramParams, device: str = "cuda", *, frame_engine: str = "auto"):
         """`frame_engine="chirp-z"` (not in the reference) runs parameter sets whose FFT length has a prime factor above 13 - which
@@ -163,14 +167,35 @@ class SpectrogramConverter:
         return int(torch.randint(0, 2**62, (1,)).item())
 
     # ---- numpy / pydub level (reference :101-163) -------------------------------------------------
-    def spectrogram_from_audio(self, audio: T.Any) -> np.ndarray:
-        """Audio segment -> (channels, n_mels, T) float32 mel amplitudes."""
+    def check_loop_samples(self, samples: int) -> None:
+        """ValueError for a clip of `samples` samples that is no whole loop at these params - a loop encode takes exactly hop * T
+        samples, hop * T >= n_fft, and trims or pads nothing - naming the nearest lengths that are, in samples and milliseconds."""
+        from riffusion import _hip
+
+        try:
+            _hip.check_loop_samples(self.p.hop_length, self.p.n_fft, samples)  # the library's rule decides
+        except ValueError:
+            hop, rate = self.p.hop_length, self.p.sample_rate
+            below, above = _hip.loop_nearest_samples(hop, self.p.n_fft, samples)
+
+            def ms(n: int) -> str:
+                return f"{n} samples ({n * 1000.0 / rate:.3f} ms)"
+
+            raise LoopLengthError(f"a loop clip is a whole number of hops (hop_length {hop}), at least n_fft = {self.p.n_fft} samples: got {ms(int(samples))}; "
+                                  f"the nearest legal lengths are {ms(below) if below else 'none'} below and {ms(above)} above; nothing is trimmed or "
+                                  "padded") from None
+
+    def spectrogram_from_audio(self, audio: T.Any, loop: bool = False) -> np.ndarray:
+        """Audio segment -> (channels, n_mels, T) float32 mel amplitudes.  `loop`: the segment is one period of a loop - exactly
+        hop * T samples (`check_loop_samples`) - and is encoded on the circular STFT (`mel_amplitudes_from_waveform`): T columns."""
         assert int(audio.frame_rate) == self.p.sample_rate, "Audio sample rate must match params"
         waveform = np.array([c.get_array_of_samples() for c in audio.split_to_mono()])
         if waveform.dtype != np.float32:
             waveform = waveform.astype(np.float32)
+        if loop:
+            self.check_loop_samples(waveform.shape[-1])
         waveform_tensor = torch.from_numpy(waveform).to(self.device)
-        amplitudes_mel = self.mel_amplitudes_from_waveform(waveform_tensor)
+        amplitudes_mel = self.mel_amplitudes_from_waveform(waveform_tensor, loop=loop)
         return amplitudes_mel.cpu().numpy()
 
     def audio_from_spectrogram(self, spectrogram: np.ndarray, apply_filters: bool = True, *, loop: bool = False,
@@ -195,9 +220,15 @@ class SpectrogramConverter:
         return segment
 
     # ---- torch level seam (reference :165-204) ----------------------------------------------------
-    def mel_amplitudes_from_waveform(self, waveform: torch.Tensor) -> torch.Tensor:
-        """(B, samples) -> (B, n_mels, T): framed transform, magnitude and mel GEMM without leaving the GPU."""
-        return self._plan().mel_from_waveform(waveform.to(self.device))
+    def mel_amplitudes_from_waveform(self, waveform: torch.Tensor, loop: bool = False) -> torch.Tensor:
+        """(B, samples) -> (B, n_mels, T): framed transform, magnitude and mel GEMM without leaving the GPU.
+        `loop`: every row is one period of a loop, exactly hop * T samples with hop * T >= n_fft (any other length raises
+        ValueError with the nearest legal lengths): the STFT is the circular one a loop decode runs - frame t, element i reads
+        sample (hop t + i - n_fft // 2) mod (hop T) - so the tile has T columns, closes at the loop point, and a loop decode's
+        output gives its T frames back.  Columns whose window lies inside the clip are bit for bit the plain encode's."""
+        if loop:
+            self.check_loop_samples(int(waveform.shape[-1]))
+        return self._plan().mel_from_waveform(waveform.to(self.device), loop=loop)
 
     def waveform_from_mel_amplitudes(
         self,
@@ -319,15 +350,16 @@ class SpectrogramConverter:
         silent = torch.where(num > 0, torch.full_like(num, float("inf")), torch.zeros_like(num))
         return torch.where(den > 0, ratio, silent)
 
-    def spectral_convergence(self, waveform: torch.Tensor, magnitudes: torch.Tensor) -> torch.Tensor:
+    def spectral_convergence(self, waveform: torch.Tensor, magnitudes: torch.Tensor, loop: bool = False) -> torch.Tensor:
         """
         || |STFT(waveform)| - magnitudes || / || magnitudes || per row, on the device: (B, L) float32 waveforms - L the length
         Griffin-Lim gives T frames, hop * (T - 1) - and (B, n_stft, T) float32 magnitudes in the reference's layout -> (B,) float64.
         The one quality figure of a Griffin-Lim result that does not depend on its random start.  Deterministic: a row's value
         is the same alone and in any batch (rfx_spectral_error).
+        `loop`: the waveforms are loop decodes, (B, hop * T), and the STFT is the circular one (rfx_spectral_error_loop).
         """
         plan = self._plan()
         mag = magnitudes.to(self.device)
         B, _, Tn = mag.shape
-        sums = plan.spectral_error(waveform.to(self.device), plan.pack_magnitudes(mag), B, Tn)
+        sums = plan.spectral_error(waveform.to(self.device), plan.pack_magnitudes(mag), B, Tn, loop=loop)
         return self.convergence_from_sums(sums[:, 0], sums[:, 1])

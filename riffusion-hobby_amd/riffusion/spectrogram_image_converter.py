@@ -35,8 +35,10 @@ class SpectrogramImageConverter:
         self.converter = SpectrogramConverter(params=params, device=device, frame_engine=frame_engine)
 
     # ---- reference API: one clip per call -------------------------------------------------------------
-    def spectrogram_image_from_audio(self, segment: T.Any) -> Image.Image:
-        """Audio segment -> spectrogram image carrying the params (and MAX_VALUE) as EXIF."""
+    def spectrogram_image_from_audio(self, segment: T.Any, loop: bool = False) -> Image.Image:
+        """Audio segment -> spectrogram image carrying the params (and MAX_VALUE) as EXIF.  `loop`: the segment is one period of a
+        loop, exactly hop * T samples (any other length raises ValueError with the nearest legal lengths: nothing is trimmed or
+        padded), and is encoded on the circular STFT (`spectrogram_images_from_waveforms`): a tile of T columns that closes."""
         assert int(segment.frame_rate) == self.p.sample_rate, "Sample rate mismatch"
 
         if self.p.stereo:
@@ -52,7 +54,7 @@ class SpectrogramImageConverter:
                 segment = segment.set_channels(1)
 
         waveform = np.array([c.get_array_of_samples() for c in segment.split_to_mono()]).astype(np.float32)
-        images, max_values = self.spectrogram_images_from_waveforms(torch.from_numpy(waveform)[None])
+        images, max_values = self.spectrogram_images_from_waveforms(torch.from_numpy(waveform)[None], loop=loop)
         image = images[0]
         exif_data = self.p.to_exif()
         exif_data[SpectrogramParams.ExifTags.MAX_VALUE.value] = float(max_values[0])
@@ -72,6 +74,7 @@ class SpectrogramImageConverter:
         hold_mask: T.Any = None,
         loop: bool = False,
         phase_start: str = "random",
+        return_loop_error: bool = False,
     ) -> T.Any:
         """Spectrogram image -> audio segment (the EXIF MAX_VALUE is not read back, like the reference).  The filters
         (audio_util.apply_filters, compression=False) run on the device: same bytes.  `inverse_mel`: "sgd" (default) or
@@ -84,7 +87,9 @@ class SpectrogramImageConverter:
         or an (n_mels, W) boolean array: the kept region keeps the guide's phase through the iterations.  `loop`: the tile is
         one period of a loop: hop * W samples whose end runs into their start (not with `hold_frames` / `hold_mask`).
         `phase_start`: "random" (default) or "peaks", Griffin-Lim's start built from the tile's magnitudes (not with a guide).  All as
-        in `audio_from_spectrogram_images`."""
+        in `audio_from_spectrogram_images`.  `return_loop_error=True` (only with `loop=True`, ValueError otherwise) returns
+        (segment, error): the clip's circular spectral convergence as a float, `audio_from_spectrogram_images`' `return_loop_error`;
+        same audio."""
         _hip.check_call_rules(CALL_WORDING, "peak_start", "hold_needs_guide", "bins_need_guide", peak_start=_hip.check_phase_start(phase_start),
                               guide_segment=guide_segment, hold_frames=hold_frames, hold_mask=hold_mask)
         guides = None
@@ -98,8 +103,10 @@ class SpectrogramImageConverter:
         pcm = self.audio_from_spectrogram_images(
             np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters,
             inverse_mel=inverse_mel, guide_waveforms=guides, griffin_lim_iters=griffin_lim_iters, hold_frames=hold_frames,
-            hold_mask=hold_mask, loop=loop, phase_start=phase_start,
+            hold_mask=hold_mask, loop=loop, phase_start=phase_start, return_loop_error=return_loop_error,
         )
+        if return_loop_error:
+            return audio_util.segment_from_pcm16(pcm[0][0], self.p.sample_rate), float(pcm[1][0])
         return audio_util.segment_from_pcm16(pcm[0], self.p.sample_rate)
 
     def hold_frames_for(self, head_s: float = 0.0, tail_s: float = 0.0) -> T.Tuple[int, int]:
@@ -251,24 +258,31 @@ class SpectrogramImageConverter:
         return audio_util.segment_from_pcm16(joined, self.p.sample_rate)
 
     def spectrogram_images_from_waveforms(self, waveforms: torch.Tensor, return_device: bool = False, *,
-                                          as_jpeg: bool = False, as_png: bool = False, png_mode: str = "rgb") -> T.Tuple[T.Any, T.Any]:
+                                          as_jpeg: bool = False, as_png: bool = False, png_mode: str = "rgb",
+                                          loop: bool = False) -> T.Tuple[T.Any, T.Any]:
         """(N, C, samples) float waveforms at int16 scale -> N RGB images and their float32 MAX_VALUEs.  With
         `return_device=True` the (N, n_mels, T, 3) uint8 tensor and the (N,) float32 maxima as they are on the GPU (no copy, no
         synchronisation): the encode side of audio-to-audio's device chain.  With `as_jpeg=True` the images come back as N JPEG
         files (`bytes`), encoded on the device (`jpeg_bytes_from_images`), each with the params and its MAX_VALUE as EXIF: the
         bytes of `image.save(f, exif=image.getexif(), format="JPEG")` on `spectrogram_image_from_audio`'s image.  With
         `as_png=True` they come back as N PNG files, lossless, written on the device (`png_bytes_from_images` with
-        `mode=png_mode`) with the same EXIF: any reader gets `spectrogram_image_from_audio`'s pixels back."""
+        `mode=png_mode`) with the same EXIF: any reader gets `spectrogram_image_from_audio`'s pixels back.
+        `loop=True`: every waveform is one period of a loop - exactly hop * T samples, hop * T >= n_fft; any other length raises
+        ValueError with the nearest legal lengths in samples and milliseconds, nothing is trimmed or padded - and the tiles are made
+        on the circular STFT (rfx_image_from_waveform_loop): T columns, column 0 follows column T - 1, and
+        `audio_from_spectrogram_images(loop=True)` decodes clips of the same hop * T samples.  Goes with every output form."""
         self._check_file_outputs(as_jpeg, as_png, return_device)
         conv = self.converter
         plan = conv._plan()
         N, C, L = waveforms.shape
         if C != (2 if self.p.stereo else 1):
             raise ValueError(f"expected {2 if self.p.stereo else 1} channel(s), got {C}")
+        if loop:
+            conv.check_loop_samples(int(L))
         power = float(self.p.power_for_image)
         thr = plan.device_constant(("encode_thresholds", power), lambda: image_util.encode_thresholds(power))
         # one call (rfx_image_from_waveform): the mel amplitudes go from the forward kernel to the encoder without the (N*C, M, T) tensor
-        img, mx = plan.image_from_waveform(waveforms.reshape(N * C, L).to(conv.device, torch.float32), self.p.stereo, thr)
+        img, mx = plan.image_from_waveform(waveforms.reshape(N * C, L).to(conv.device, torch.float32), self.p.stereo, thr, loop=loop)
         if return_device:
             return img, mx
         if as_jpeg:
@@ -436,7 +450,7 @@ class SpectrogramImageConverter:
 
     def spectrogram_images_from_audio_clips(self, segment: T.Any, clip_start_times: T.Sequence[float], clip_duration_s: float,
                                             return_device: bool = False, *, as_jpeg: bool = False, as_png: bool = False,
-                                            png_mode: str = "rgb") -> T.Tuple[T.Any, T.Any]:
+                                            png_mode: str = "rgb", loop: bool = False) -> T.Tuple[T.Any, T.Any]:
         """
         One int16 track -> the spectrogram images of its clips: `[spectrogram_image_from_audio(c) for c in
         slice_audio_into_clips(segment.set_frame_rate(params.sample_rate), clip_start_times, clip_duration_s)]`, same image
@@ -453,6 +467,10 @@ class SpectrogramImageConverter:
         the N images come back as JPEG files (`bytes`) encoded on the device, each with the params and its MAX_VALUE as EXIF, as
         from `spectrogram_images_from_waveforms`; with `as_png=True` as PNG files written on the device (`png_mode`: the `mode`
         of `png_bytes_from_images`).
+        `loop=True`: every clip is one period of a loop and is encoded on the circular STFT (rfx_image_from_pcm16_clips_loop).
+        The clips' length in frames at the params' rate - what the reference's millisecond slicing makes of `clip_duration_s` -
+        must be exactly hop * T, hop * T >= n_fft: any other length raises ValueError with the nearest legal lengths in samples and
+        milliseconds, and so does a clip the track does not hold in full (nothing is trimmed or padded with silence).
         """
         self._check_file_outputs(as_jpeg, as_png, return_device)
         conv = self.converter
@@ -466,12 +484,22 @@ class SpectrogramImageConverter:
         if int(segment.frame_rate) != self.p.sample_rate:
             pcm = plan.resample_pcm(pcm, int(segment.frame_rate), self.p.sample_rate)
         r = audio_util.clip_frame_ranges(int(pcm.shape[0]), self.p.sample_rate, clip_start_times, clip_duration_s)
+        if loop and n:
+            # a loop clip is the `frames` frames from the frame its start time falls on, all of them inside the track: the reference's
+            # silence branch - which a last clip of 5.12 s takes for one millisecond of float rounding - does not exist here
+            conv.check_loop_samples(int(r.frames))
+            starts = np.array([int(int(t * 1000) * (self.p.sample_rate / 1000.0)) for t in clip_start_times], dtype=np.int64)
+            for i, a in enumerate(starts):
+                if a < 0 or a + r.frames > int(pcm.shape[0]):
+                    raise ValueError(f"loop=True: clip {i} (frames {int(a)} .. {int(a) + int(r.frames)}) reaches past the track's end "
+                                     f"({int(pcm.shape[0])} frames); a loop clip is not padded with silence")
+            r = r._replace(index=np.arange(n, dtype=np.int64), starts=starts, host_index=np.array([], dtype=np.int64), last_short=False)
         power = float(self.p.power_for_image)
         thr = plan.device_constant(("encode_thresholds", power), lambda: image_util.encode_thresholds(power))
         tiles: T.List[T.Any] = [None] * n
         maxima = torch.empty(n, dtype=torch.float32, device=plan.device)
         if len(r.index):
-            img, mx = plan.image_from_pcm_clips(pcm, r.starts, r.frames, self.p.stereo, thr)
+            img, mx = plan.image_from_pcm_clips(pcm, r.starts, r.frames, self.p.stereo, thr, loop=loop)
             index = torch.from_numpy(r.index).to(plan.device)
             maxima[index] = mx
             for j, i in enumerate(r.index):
@@ -572,6 +600,7 @@ class SpectrogramImageConverter:
         hold_mask: T.Any = None,
         loop: bool = False,
         phase_start: str = "random",
+        return_loop_error: bool = False,
     ) -> T.Any:
         """
         (N, H, W, 3) RGB tiles -> (n, samples, C) int16 PCM (or, with `return_waveform`, the (n, C, samples)
@@ -659,6 +688,10 @@ class SpectrogramImageConverter:
         and its last sample runs into its first: no click at the loop point.  W (or `size[0]`) must reach n_fft / hop (40 columns
         at the defaults).  Guides, `inverse_mel`, `apply_filters`, `tiles_per_call`, `group` and `size` work as without it; not
         with `hold_frames`, `hold_mask` or `return_error` (the error entry analyses with the reflect-padded STFT): ValueError.
+        `return_loop_error=True` (only with `loop=True`: ValueError otherwise) is `return_error` for loop decodes: it returns
+        (result, errors) with every clip's CIRCULAR spectral convergence - the clip re-analysed by the circular STFT a loop encode
+        runs (rfx_spectral_error_loop) against the magnitudes Griffin-Lim was handed.  The chunk goes through the separate stages as
+        under `return_error`; `result` is byte for byte the result without the flag.  Not with `group`.
         `phase_start`: "random" (default: the reference's U[0,1) phases from `seed`) or "peaks": Griffin-Lim starts every row from
         phases built from its magnitudes alone - the spectral peaks of every frame, their interpolated frequencies integrated
         over the hop (rfx_start_call_options) - so that a text-to-audio decode, which has no guide, needs fewer iterations:
@@ -675,6 +708,9 @@ class SpectrogramImageConverter:
         rules("peak_start", "loop_holds")
         if loop and return_error:
             raise ValueError("loop does not go with return_error=True: the spectral error is measured with the reflect-padded STFT")
+        if return_loop_error and not loop:
+            raise ValueError("return_loop_error=True is the circular spectral error of a loop decode: it needs loop=True")
+        want_error = return_error or return_loop_error
 
         if tiles_per_call < 1:
             raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
@@ -684,8 +720,8 @@ class SpectrogramImageConverter:
             raise ValueError("apply_filters works on int16 PCM: it does not go with return_waveform=True")
         if return_range_flag and not return_device:
             raise ValueError("return_range_flag goes with return_device=True (a host result raises on a failed range check instead)")
-        if return_error and group is not None:
-            raise ValueError("return_error does not go with `group`: the errors of a sharded batch are not gathered")
+        if want_error and group is not None:
+            raise ValueError(f"{'return_error' if return_error else 'return_loop_error'} does not go with `group`: the errors of a sharded batch are not gathered")
         if gather is None:
             gather = batch_shard.default_gather(group)
         if gather not in batch_shard.GATHER_MODES:
@@ -782,13 +818,13 @@ class SpectrogramImageConverter:
                 tiles = source.get(i)
                 if size is not None:
                     tiles = plan.resize_images(tiles, size[1], size[0], Image.BICUBIC)
-                if return_error:  # the stages one by one (same bytes as the fused calls below): the error needs both ends of Griffin-Lim
+                if want_error:  # the stages one by one (same bytes as the fused calls below): the error needs both ends of Griffin-Lim
                     mel = plan.image_decode(tiles, self.p.stereo, lut)
                     wave, lin_slots = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C,
                                                               magnitude_hint=max_value, return_slots=True, inverse_mel=inverse_mel,
                                                               guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b),
-                                                              hold_bands=held_bands(a, b), peak_start=peaks)
-                    error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1])).reshape(b - a, C, 2).sum(1))
+                                                              hold_bands=held_bands(a, b), loop=loop, peak_start=peaks)
+                    error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1]), loop=loop).reshape(b - a, C, 2).sum(1))
                     if return_waveform:
                         out = wave.reshape(b - a, C, -1)
                     else:
@@ -816,7 +852,7 @@ class SpectrogramImageConverter:
 
         result = batch_shard.sharded_map(convert, n_total, group, gather)
         errors = None
-        if return_error:
+        if want_error:
             sums = torch.cat(error_sums) if error_sums else torch.zeros((0, 2), dtype=torch.float64, device=plan.device)
             errors = conv.convergence_from_sums(sums[:, 0], sums[:, 1])
         if return_device:
@@ -829,7 +865,7 @@ class SpectrogramImageConverter:
             # attribute: slicing / .to() / a gather make a new tensor without it - read it from the tensor this call returned.
             flag = range_ok if range_ok is not None else torch.ones((), dtype=torch.bool, device=result.device)
             result.range_ok = flag
-            if return_error:
+            if want_error:
                 return (result, errors, flag) if return_range_flag else (result, errors)
             return (result, flag) if return_range_flag else result
         if result.is_cuda:
@@ -839,4 +875,4 @@ class SpectrogramImageConverter:
             result = host
         if range_ok is not None and not bool(range_ok):  # the stream has been synchronised above / by the sink: no extra wait
             raise ValueError(range_msg)
-        return (result.numpy(), errors.cpu().numpy()) if return_error else result.numpy()
+        return (result.numpy(), errors.cpu().numpy()) if want_error else result.numpy()
