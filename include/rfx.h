@@ -301,8 +301,8 @@ typedef struct {
  * the free frames into a list in its workspace (three small launches, no host read, no synchronisation, nothing allocated) and launches
  * 1 .. n_iter walk that list, so a held call does less work in proportion to what it holds.  h_launch_ms keeps n_iter + 1 entries, [0]
  * including the staging and the compaction.
- * Workspace: the *_held_workspace_bytes twin of the entry's query (the frame list, B T + a few int32, and on the specialised engine
- * the frame buffer of the per-frame form: a held call always takes that form, see rfx_griffinlim_form); at least the unheld query.
+ * Workspace: the entry's *_workspace_bytes_ex query with the call's options (the frame list, B T + a few int32, and on the specialised
+ * engine the frame buffer of the per-frame form: a held call always takes that form, see rfx_griffinlim_form); at least the unheld query.
  * RFX_ERR_INVALID before any launch: d_hold_frames without d_guide, a pointer off 4-byte alignment, reserved3 != 0;
  * RFX_ERR_WORKSPACE: a workspace below the held query.  Honoured by the three entries that honour a guide; rfx_inverse_mel_ex refuses
  * it. */
@@ -344,8 +344,8 @@ typedef struct {
  * launch on S, the split X = S_free, then launches 1 .. n_iter on X; n_iter == 0 skips the splits and c.  A mask removes no
  * iteration work (a frame whose every bin is held still runs).  h_launch_ms keeps n_iter + 1 entries, [0] including the staging, the
  * split and the c launch.  On the specialised engine a masked call always takes RFX_GL_FORM_FRAMES (see rfx_griffinlim_form).
- * Workspace: the *_masked_workspace_bytes twin of the entry's query (the per-frame form's frame buffer, one more magnitude array X,
- * and c: B rows of audio); at least the unmasked query.
+ * Workspace: the entry's *_workspace_bytes_ex query with the call's options (the per-frame form's frame buffer, one more magnitude
+ * array X, and c: B rows of audio); at least the unmasked query.
  * RFX_ERR_INVALID before any launch, the output untouched: d_hold_bins without d_guide; together with d_hold_frames (in this version:
  * fully set frames in the mask express the same hold); together with d_angles0_slots; hold_words != rfx_hold_mask_words(plan); a
  * pointer off 4-byte alignment; reserved4 != 0.  RFX_ERR_WORKSPACE: a workspace below the masked query.  Honoured by
@@ -388,7 +388,7 @@ typedef struct {
  * A guide (d_guide) is allowed: it is fitted to P samples by the guided call's rule and its start is G / |G| of the circular STFT.
  * On the specialised engine a loop call always takes RFX_GL_FORM_FRAMES (the run form's sliding window and seams are not looped);
  * the chirp-z engine refuses a loop call (RFX_ERR_UNSUPPORTED).  h_launch_ms keeps n_iter + 1 entries.
- * Workspace: the *_loop_workspace_bytes twin of the entry's query.
+ * Workspace: the entry's *_workspace_bytes_ex query with the call's options; 0 for a call that is refused (chirp-z, hop T < n_fft).
  * RFX_ERR_INVALID before any launch, the output untouched: loop > 1; reserved5 != 0; loop together with d_hold_frames or
  * d_hold_bins; hop T < n_fft (a frame must cover the period at most once: T >= 40 at the default geometry, the smallest T is in the
  * message).  RFX_ERR_WORKSPACE: a workspace below the loop query.  Honoured by rfx_griffinlim_ex, rfx_waveform_from_mel_ex and
@@ -423,11 +423,11 @@ typedef struct {
  * InverseMelScale stage of a fused call still draws its own start from it), row_base, the other rows or its place in the batch.
  * loop == 1 together with start == 1 is served: the first launch of a loop call is the unlooped call's, and both transforms centre
  * frame t at hop t.  h_launch_ms keeps n_iter + 1 entries, [0] including the start.
- * Workspace: the *_peak_workspace_bytes twin of the entry's query = that query plus the angles, B T frame_stride 8 bytes rounded up to
- * 256, plus rfx_peak_start_workspace_bytes(plan, B, T); a loop call with start == 1 brings its loop query plus the same two terms.
+ * Workspace: the entry's *_workspace_bytes_ex query with the call's options (the call without the start, plus the angles and
+ * rfx_peak_start's own workspace); loop == 1 together with start == 1 is sized by the same query.
  * RFX_ERR_INVALID before any launch, the output untouched: start > 1; reserved6 != 0; start == 1 together with d_guide, with
  * d_angles0_slots, with d_hold_frames or with d_hold_bins (each is a start, or needs the guide's).  RFX_ERR_UNSUPPORTED: a plan whose
- * frame does not fit the LDS (rfx_peak_start).  RFX_ERR_WORKSPACE: a workspace below the twin.  Honoured by rfx_griffinlim_ex,
+ * frame does not fit the LDS (rfx_peak_start).  RFX_ERR_WORKSPACE: a workspace below the query.  Honoured by rfx_griffinlim_ex,
  * rfx_waveform_from_mel_ex and rfx_audio_from_image_u8_ex; rfx_inverse_mel_ex refuses it.  A caller passing any of the five shorter
  * struct sizes keeps exactly its behaviour and bytes.  (A new struct, not a flag bit: flags == 2 stays refused.) */
 typedef struct {
@@ -450,6 +450,16 @@ typedef struct {
   uint32_t start;           /* 0: the call is rfx_loop_call_options' call; 1: the spectral-peak start */
   uint32_t reserved6;       /* must be 0 */
 } rfx_start_call_options;
+
+/* The workspace of a call of rfx_griffinlim_ex, rfx_waveform_from_mel_ex or rfx_audio_from_image_u8_ex with these options: pass the
+ * call's own struct.  options is read exactly as the entry of the same name reads it (struct_size, flags, reserved fields, the
+ * combination rules, pointer alignment; device pointers are tested for NULL and alignment and never dereferenced; row_base and
+ * magnitude_hint do not enter the size).  Options the entry refuses give 0, with the entry's refusal in rfx_last_error under the
+ * query's name.  options == NULL is the plain query (rfx_griffinlim_workspace_bytes, ...).  0 also for a NULL plan and for a loop
+ * call the plan or T cannot serve (the chirp-z engine, hop T < n_fft). */
+size_t rfx_griffinlim_workspace_bytes_ex(const rfx_plan* plan, int B, int T, const rfx_call_options* options);
+size_t rfx_waveform_from_mel_workspace_bytes_ex(const rfx_plan* plan, int B, int T, const rfx_call_options* options);
+size_t rfx_audio_from_image_workspace_bytes_ex(const rfx_plan* plan, int N, int stereo, int T, const rfx_call_options* options);
 
 /* ---- the spectral-peak start: initial angles for Griffin-Lim from the magnitudes alone ---------------------------------------------
  * d_mag_slots: magnitudes in slot layout, B T frames (what rfx_pack_magnitudes and rfx_inverse_mel write); d_angles0_slots_out: B T
@@ -584,14 +594,7 @@ int rfx_spectral_error_loop(const rfx_plan* plan, const float* d_wave /* (B, hop
  * per-frame kernel + fold (two launches per iteration, every frame its own workgroup) for the few-tiles-per-request case;
  * the workspace query below accounts for whichever the shape will take. */
 size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T);
-/* ... of a call with held frames (rfx_held_call_options.d_hold_frames != NULL) */
-size_t rfx_griffinlim_held_workspace_bytes(const rfx_plan* plan, int B, int T);
-/* ... of a masked call (rfx_masked_call_options.d_hold_bins != NULL) */
-size_t rfx_griffinlim_masked_workspace_bytes(const rfx_plan* plan, int B, int T);
-/* ... of a loop call (rfx_loop_call_options.loop == 1); 0 where the call would be refused (hop T < n_fft, the chirp-z engine) */
-size_t rfx_griffinlim_loop_workspace_bytes(const rfx_plan* plan, int B, int T);
-/* ... of a call with the spectral-peak start (rfx_start_call_options.start == 1): the unflagged query, the angles, the start's scratch */
-size_t rfx_griffinlim_peak_workspace_bytes(const rfx_plan* plan, int B, int T);
+/* (of a call with options - held frames, a mask, a loop, the spectral-peak start: rfx_griffinlim_workspace_bytes_ex above) */
 /* samples per row a loop call writes for T frames: the period hop T; 0 for a NULL plan or T <= 0 */
 int rfx_griffinlim_loop_output_samples(const rfx_plan* plan, int T);
 /* the frame-count rule of a loop call, without a plan or a GPU (tests): RFX_OK, or the RFX_ERR_INVALID a loop call of T frames at
@@ -709,10 +712,6 @@ int rfx_inverse_mel_lstsq(const rfx_plan* plan, const float* d_mel, int B, int T
  * rfx_inverse_mel; both random starts from `seed` (the SGD start from seed, the phases from seed + 1).  Exactly rfx_inverse_mel
  * followed by rfx_griffinlim - same bits - with the linear magnitudes kept inside the workspace. */
 size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T);
-size_t rfx_waveform_from_mel_held_workspace_bytes(const rfx_plan* plan, int B, int T);  /* with held frames (rfx_held_call_options) */
-size_t rfx_waveform_from_mel_masked_workspace_bytes(const rfx_plan* plan, int B, int T);  /* masked (rfx_masked_call_options) */
-size_t rfx_waveform_from_mel_loop_workspace_bytes(const rfx_plan* plan, int B, int T);    /* loop (rfx_loop_call_options) */
-size_t rfx_waveform_from_mel_peak_workspace_bytes(const rfx_plan* plan, int B, int T);    /* peak start (rfx_start_call_options) */
 int rfx_waveform_from_mel(const rfx_plan* plan, const float* d_mel, int B, int T, int channels_per_clip, uint64_t seed, int n_iter,
                           float momentum, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream);
 
@@ -969,10 +968,6 @@ int rfx_pcm16_clips_to_waveform(const int16_t* d_pcm, int64_t frames, int in_cha
  * rfx_image_decode_u8, rfx_waveform_from_mel (clips of C rows, `seed`), rfx_pcm16 - same bytes - with the tensors in between
  * kept inside the workspace. */
 size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);
-size_t rfx_audio_from_image_held_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* with held frames (rfx_held_call_options) */
-size_t rfx_audio_from_image_masked_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);  /* masked (rfx_masked_call_options) */
-size_t rfx_audio_from_image_loop_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);    /* loop (rfx_loop_call_options) */
-size_t rfx_audio_from_image_peak_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T);    /* peak start (rfx_start_call_options) */
 int rfx_audio_from_image_u8(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                             int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,
                             size_t workspace_bytes, void* stream);

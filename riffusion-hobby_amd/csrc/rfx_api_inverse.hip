@@ -937,8 +937,9 @@ static AudioFromImageLayout audio_from_image_layout(const rfx_plan* plan, int N,
   l.total = l.rest + inner;
   return l;
 }
-// The workspace queries of the three entries: one sizing function, and the exported names (the ABI) as calls of it with constants.
-// rows: B, or N images of 1 + stereo rows
+// The workspace queries of the three entries: one sizing function, asked by the plain names for a call without options and by the
+// _ex names with the call's own options, read as the entry of the same name reads them (refused options: 0, and the refusal in
+// rfx_last_error).  rows: B, or N images of 1 + stereo rows
 enum Entry { kEntryGriffinLim, kEntryWaveformFromMel, kEntryAudioFromImage };
 static size_t inverse_workspace(const rfx_plan* plan, Entry entry, int rows, int stereo, int T, GlKind kind, bool peak) {
   if (!plan) return 0;
@@ -946,27 +947,25 @@ static size_t inverse_workspace(const rfx_plan* plan, Entry entry, int rows, int
          : entry == kEntryWaveformFromMel ? waveform_from_mel_layout(plan, rows, T, kind, peak).total
                                           : audio_from_image_layout(plan, rows, stereo, T, kind, peak).total;
 }
-#define RFX_QUERY(entry, name, kind, peak) \
-  size_t name(const rfx_plan* plan, int B, int T) { return inverse_workspace(plan, entry, B, 0, T, kind, peak); }
-#define RFX_IMAGE_QUERY(name, kind, peak) \
-  size_t name(const rfx_plan* plan, int N, int stereo, int T) { return inverse_workspace(plan, kEntryAudioFromImage, N, stereo, T, kind, peak); }
-RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_workspace_bytes, kGlPlain, false)
-RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_held_workspace_bytes, kGlHeld, false)
-RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_masked_workspace_bytes, kGlMasked, false)
-RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_loop_workspace_bytes, kGlLoop, false)
-RFX_QUERY(kEntryGriffinLim, rfx_griffinlim_peak_workspace_bytes, kGlPlain, true)
-RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_workspace_bytes, kGlPlain, false)
-RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_held_workspace_bytes, kGlHeld, false)
-RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_masked_workspace_bytes, kGlMasked, false)
-RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_loop_workspace_bytes, kGlLoop, false)
-RFX_QUERY(kEntryWaveformFromMel, rfx_waveform_from_mel_peak_workspace_bytes, kGlPlain, true)
-RFX_IMAGE_QUERY(rfx_audio_from_image_workspace_bytes, kGlPlain, false)
-RFX_IMAGE_QUERY(rfx_audio_from_image_held_workspace_bytes, kGlHeld, false)
-RFX_IMAGE_QUERY(rfx_audio_from_image_masked_workspace_bytes, kGlMasked, false)
-RFX_IMAGE_QUERY(rfx_audio_from_image_loop_workspace_bytes, kGlLoop, false)
-RFX_IMAGE_QUERY(rfx_audio_from_image_peak_workspace_bytes, kGlPlain, true)
-#undef RFX_QUERY
-#undef RFX_IMAGE_QUERY
+static size_t inverse_workspace_ex(const rfx_plan* plan, Entry entry, int rows, int stereo, int T, const rfx_call_options* options, const char* who) {
+  CallOpt opt;
+  if (read_call_options(options, &opt, who, entry == kEntryGriffinLim ? 0 : RFX_CALL_INVERSE_MEL_LSTSQ, true)) return 0;
+  return inverse_workspace(plan, entry, rows, stereo, T, opt.kind(), opt.peak);
+}
+size_t rfx_griffinlim_workspace_bytes_ex(const rfx_plan* plan, int B, int T, const rfx_call_options* options) {
+  return inverse_workspace_ex(plan, kEntryGriffinLim, B, 0, T, options, __func__);
+}
+size_t rfx_waveform_from_mel_workspace_bytes_ex(const rfx_plan* plan, int B, int T, const rfx_call_options* options) {
+  return inverse_workspace_ex(plan, kEntryWaveformFromMel, B, 0, T, options, __func__);
+}
+size_t rfx_audio_from_image_workspace_bytes_ex(const rfx_plan* plan, int N, int stereo, int T, const rfx_call_options* options) {
+  return inverse_workspace_ex(plan, kEntryAudioFromImage, N, stereo, T, options, __func__);
+}
+size_t rfx_griffinlim_workspace_bytes(const rfx_plan* plan, int B, int T) { return rfx_griffinlim_workspace_bytes_ex(plan, B, T, nullptr); }
+size_t rfx_waveform_from_mel_workspace_bytes(const rfx_plan* plan, int B, int T) { return rfx_waveform_from_mel_workspace_bytes_ex(plan, B, T, nullptr); }
+size_t rfx_audio_from_image_workspace_bytes(const rfx_plan* plan, int N, int stereo, int T) {
+  return rfx_audio_from_image_workspace_bytes_ex(plan, N, stereo, T, nullptr);
+}
 
 static int audio_from_image_impl(const rfx_plan* plan, const uint8_t* d_img, int N, int T, int stereo, const float* d_lut256, uint64_t seed,
                                 int n_iter, float momentum, int normalize, float* d_clip_peak, int16_t* d_pcm_out, void* d_workspace,

@@ -164,11 +164,12 @@ PLAN_WORDING = {"roles": {"angles0_slots": "angles0"}, "loop_holds": BUILDER_WOR
 _MASK_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)  # a bit mask's words
 
 
-def start_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
-                       row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, loop: bool = False, peak_start: bool = False):
+def call_options(*, rows: int = 0, row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None,
+                 hold: T.Optional[torch.Tensor] = None, hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False, peak_start: bool = False):
     """The options of an inverse call, as the shortest of the structs above that holds what is given (the library reads a struct by
     its size): RfxCallOptions for none of the extras, RfxGuidedCallOptions for a guide alone, and so on.
     `lstsq`: the fused inverse calls run the closed-form InverseMelScale (rfx_inverse_mel_lstsq) in place of the SGD.
+    `rows`: the call's Griffin-Lim rows, which the tensors are checked against.
     `guide`: a (rows, Lg) float32 device tensor whose samples are contiguous (rows may be strided).  `hold`: a contiguous (rows, 2)
     int32 tensor of {head, tail} on the guide's device.  `hold_bins`: a contiguous (rows, T, words) int32 (or uint32) tensor on the
     guide's device, bin b of a frame held iff bit b & 31 of word b >> 5 is set.  `loop`: the row's columns are one period (a clip's
@@ -210,30 +211,6 @@ def start_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.T
         cls = RfxStartCallOptions
         fields.update(start=1)
     return cls(struct_size=ctypes.sizeof(cls), **fields)
-
-
-# the builder's earlier names, each for the extras that existed when it was added
-def call_options(row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False) -> RfxCallOptions:
-    return start_call_options(None, None, None, 0, row_base, magnitude_hint, lstsq)
-
-
-def guided_call_options(guide: T.Optional[torch.Tensor], rows: int, row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False):
-    return start_call_options(guide, None, None, rows, row_base, magnitude_hint, lstsq)
-
-
-def held_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], rows: int, row_base: int = 0,
-                      magnitude_hint: float = 0.0, lstsq: bool = False):
-    return start_call_options(guide, hold, None, rows, row_base, magnitude_hint, lstsq)
-
-
-def masked_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
-                        row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False):
-    return start_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq)
-
-
-def loop_call_options(guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], rows: int,
-                      row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, loop: bool = False):
-    return start_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq, loop)
 
 
 PHASE_STARTS = ("random", "peaks")
@@ -382,12 +359,7 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_spectral_error_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_error_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_griffinlim_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_griffinlim_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_griffinlim_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_griffinlim_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_griffinlim_peak_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_waveform_from_mel_peak_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_audio_from_image_peak_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_griffinlim_workspace_bytes_ex": (c_size_t, [c_void_p, c_int, c_int, c_void_p]),
     "rfx_peak_start_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_peak_start": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_griffinlim_loop_output_samples": (c_int, [c_void_p, c_int]),
@@ -424,15 +396,11 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_image_decode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rfx_image_encode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rfx_audio_from_image_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
-    "rfx_audio_from_image_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
-    "rfx_audio_from_image_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
-    "rfx_audio_from_image_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "rfx_audio_from_image_workspace_bytes_ex": (c_size_t, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "rfx_audio_from_image_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_audio_from_image_u8_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rfx_waveform_from_mel_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_waveform_from_mel_held_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_waveform_from_mel_masked_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_waveform_from_mel_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_waveform_from_mel_workspace_bytes_ex": (c_size_t, [c_void_p, c_int, c_int, c_void_p]),
     "rfx_waveform_from_mel_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rfx_waveform_from_mel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_image_from_waveform_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
@@ -892,7 +860,7 @@ class Plan:
                       peak_start: bool, angles0_slots: T.Optional[torch.Tensor] = None) -> T.Tuple[T.Any, int, T.Optional[torch.Tensor]]:
         """What `griffinlim`, `waveform_from_mel` and `audio_from_image` share: the combination rules and this plan's own refusals,
         the extras' tensors as the library reads them, and from them (the call's options, its workspace need in bytes, the injected
-        angles as the library reads them).  `entry`: the C entry's name between rfx_ and _workspace_bytes, `shape`: its query's
+        angles as the library reads them).  `entry`: the C entry's name between rfx_ and _workspace_bytes_ex, `shape`: its query's
         arguments; `rows`: the call's Griffin-Lim rows."""
         rules = functools.partial(check_call_rules, PLAN_WORDING, loop=loop, peak_start=peak_start, angles0_slots=angles0_slots, guide=guide, hold=hold,
                                   hold_bins=hold_bins)
@@ -915,12 +883,11 @@ class Plan:
         if hold_bins is not None:
             rules("bins_need_guide", "bins_and_hold")
             hold_bins = self._chk_hold_bins(hold_bins, rows, Tn)
-        opt = start_call_options(guide, hold, hold_bins, rows, row_base, magnitude_hint, lstsq, loop, peak_start)
+        opt = call_options(rows=rows, row_base=row_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins,
+                           loop=loop, peak_start=peak_start)
         opt.keepalive = (guide, hold, hold_bins)  # (a copy `_chk_*` made lives as long as the options that point at it)
-        kind = "loop_" if loop else "masked_" if hold_bins is not None else "held_" if hold is not None else "peak_" if peak_start else ""
-        need = getattr(self.lib, f"rfx_{entry}_{kind}workspace_bytes")(self.handle, *shape)
-        if loop and peak_start:  # (no query of its own: behind the loop call's bytes, the start's angles and scratch, each a 256-byte field)
-            need += -(-rows * Tn * self.frame_stride * 8 // 256) * 256 + self.lib.rfx_peak_start_workspace_bytes(self.handle, rows, Tn)
+        # (0 for options the library refuses: the entry then reports its refusal itself)
+        need = getattr(self.lib, f"rfx_{entry}_workspace_bytes_ex")(self.handle, *shape, ctypes.byref(opt))
         return opt, need, angles0_slots
 
     def peak_start(self, mag_slots: torch.Tensor, B: int, Tn: int) -> torch.Tensor:
@@ -1079,7 +1046,7 @@ class Plan:
                 raise ValueError(f"spec0 must be (B, T, n_stft) = {(B, Tn, self.n_stft)}, got {tuple(spec0.shape)}")
         need = self.lib.rfx_inverse_mel_workspace_bytes(self.handle, B, Tn)
         out = torch.empty((B * Tn, self.frame_stride), dtype=torch.float32, device=mel.device)
-        opt = call_options(row_base, magnitude_hint)
+        opt = call_options(row_base=row_base, magnitude_hint=magnitude_hint)
         with self._workspace(need) as ws:
             check(
                 self.lib.rfx_inverse_mel_ex(

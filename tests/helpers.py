@@ -53,6 +53,38 @@ def mask_ill_conditioned_bins(O, mag: torch.Tensor, op, angles0: torch.Tensor, n
     return mag, total
 
 
+# option fields of `need` for a guided call, one with held frames and a masked one: dummy aligned addresses, a guide row of one sample
+GUIDE = dict(d_guide=0x1000, guide_stride=1, guide_samples=1)
+HELD = dict(GUIDE, d_hold_frames=0x1000)
+MASKED = dict(GUIDE, d_hold_bins=0x1000)
+
+
+def need(lib, entry: str, plan_handle, *shape: int, **fields) -> int:
+    """The workspace of a call of `entry` ("griffinlim", "waveform_from_mel", "audio_from_image") with the options `fields`
+    (rfx_start_call_options' own names; pointers as addresses, which the library never dereferences here): the entry's
+    rfx_*_workspace_bytes_ex query.  0 with the refusal in rfx_last_error for options the entry refuses."""
+    import ctypes
+
+    from riffusion import _hip
+
+    opt = _hip.RfxStartCallOptions(struct_size=ctypes.sizeof(_hip.RfxStartCallOptions), **fields)
+    return getattr(lib, f"rfx_{entry}_workspace_bytes_ex")(plan_handle, *shape, ctypes.byref(opt))
+
+
+def queries_refuse(lib, opt, word: bytes) -> bool:
+    """Each of the three rfx_*_workspace_bytes_ex queries answers 0 for the ctypes options `opt` (no plan is needed: the options are
+    read first) and leaves a refusal with `word` in rfx_last_error under its own name."""
+    import ctypes
+
+    for name, shape in (("rfx_griffinlim_workspace_bytes_ex", (1, 30)), ("rfx_waveform_from_mel_workspace_bytes_ex", (1, 30)),
+                        ("rfx_audio_from_image_workspace_bytes_ex", (1, 0, 30))):
+        if getattr(lib, name)(None, *shape, ctypes.byref(opt)) != 0 or not lib.rfx_last_error().startswith(name.encode() + b": "):
+            return False
+        if word not in lib.rfx_last_error():
+            return False
+    return True
+
+
 def plan_bank_report(op, fb="oracle", frame_engine: str = "auto", plan_layout: str = "auto", imel_form: str = "auto"):
     """rfx_debug_plan_bank (include/rfx.h, no GPU): what rfx_plan_create_ex decides for the oracle parameter set `op`, its
     filterbank as the oracle builds it (or the (n_stft, n_mels) float32 tensor `fb`, or None for a plan without one) and the

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
 from helpers import synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
@@ -191,3 +192,71 @@ def test_cli_other_sample_rates_and_batch_flags(golden_dir, tmp_path):
     cli.main(["audio-to-images-batch", "--audio-dir", str(clips), "--output-dir", str(tmp_path / "mono"), "--mono",
               "--image-extension", "png", "--limit", "1"])
     assert os.listdir(tmp_path / "mono") == ["a.png"]
+
+
+# ---- the workspace of an inverse call comes from the call's own options (rfx_*_workspace_bytes_ex) -----------------------------------------
+_EX_PLANS = {"specialised": dict(), "row-family-48k": dict(sample_rate=48000), "generic-11025": dict(sample_rate=11025, max_frequency=5512)}
+_EX_B, _EX_T = 2, 41  # the smallest loop of these geometries is 40 frames (41 at 11025 Hz), the reflect rule needs 22
+
+
+@pytest.mark.parametrize("what", ["loop+start", "loop+guide", "guide"])
+@pytest.mark.parametrize("name", sorted(_EX_PLANS))
+def test_workspace_query_by_options_is_sharp(name, what):
+    """Combinations that had no query of their own: the size the library answers for the call's options is the size the entry
+    asks for, to the byte - one byte less is RFX_ERR_WORKSPACE before any launch, the size itself runs."""
+    from riffusion import _hip
+    from riffusion.spectrogram_params import SpectrogramParams
+    from riffusion.util import image_util
+
+    plan = _hip.get_plan(SpectrogramParams(**_EX_PLANS[name]), "cuda")
+    assert plan.griffinlim_engine == name.rsplit("-", 1)[0] and plan.n_stft <= 10240
+    lib, B, T = plan.lib, _EX_B, _EX_T
+    loop = what.startswith("loop")
+    L = plan.output_samples(T, loop)
+    guide = synthetic_wave(B, L, seed=303).cuda()
+    guided = dict(d_guide=guide.data_ptr(), guide_stride=L, guide_samples=L)
+    fields = {"loop+start": dict(loop=1, start=1), "loop+guide": dict(guided, loop=1), "guide": guided}[what]
+    plain = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T)
+    need = helpers.need(lib, "griffinlim", plan.handle, B, T, **fields)
+    assert plain > 0 and helpers.need(lib, "griffinlim", plan.handle, B, T) == plain == lib.rfx_griffinlim_workspace_bytes_ex(plan.handle, B, T, None)
+    # a guide is staged in buffers the first launch leaves free: it adds nothing; the start's bytes lie behind the call's, looped or not
+    assert helpers.need(lib, "griffinlim", plan.handle, B, T, **guided) == plain
+    loop_need = helpers.need(lib, "griffinlim", plan.handle, B, T, loop=1)
+    assert helpers.need(lib, "griffinlim", plan.handle, B, T, **dict(guided, loop=1)) == loop_need > 0
+    assert helpers.need(lib, "griffinlim", plan.handle, B, T, loop=1, start=1) == loop_need + helpers.need(lib, "griffinlim", plan.handle, B, T, start=1) - plain
+    assert need == {"loop+start": helpers.need(lib, "griffinlim", plan.handle, B, T, loop=1, start=1), "loop+guide": loop_need, "guide": plain}[what]
+
+    opt = _hip.RfxStartCallOptions(struct_size=ctypes.sizeof(_hip.RfxStartCallOptions), **fields)
+    stream = _hip.current_stream(torch.device("cuda"))
+    S = plan.pack_magnitudes((torch.rand(B, plan.n_stft, T, generator=torch.Generator().manual_seed(11)) * 1000.0).cuda())
+
+    def sharp(run, need, out, sentinel):
+        ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        assert run(ws.data_ptr(), need - 1) == -3 and b"workspace too small" in lib.rfx_last_error()
+        torch.cuda.synchronize()
+        assert bool((out == sentinel).all())
+        assert run(ws.data_ptr(), need) == 0, lib.rfx_last_error()
+        torch.cuda.synchronize()
+        assert not bool((out == sentinel).all())
+
+    out = torch.full((B, L), 123.0, device="cuda")
+    sharp(lambda ws, n: lib.rfx_griffinlim_ex(plan.handle, S.data_ptr(), None, 5, B, T, 1, 0.99, out.data_ptr(), ws, n, stream, ctypes.byref(opt), None),
+          need, out, 123.0)
+    assert bool(torch.isfinite(out).all())
+    if name != "specialised" or what != "loop+start":
+        return
+    # the fused entries, on the default plan
+    mel = torch.rand(B, plan.n_mels, T, generator=torch.Generator().manual_seed(1)).cuda() * 1e6
+    need_w = helpers.need(lib, "waveform_from_mel", plan.handle, B, T, **fields)
+    assert need_w == helpers.need(lib, "waveform_from_mel", plan.handle, B, T, loop=1) + need - loop_need
+    out.fill_(123.0)
+    sharp(lambda ws, n: lib.rfx_waveform_from_mel_ex(plan.handle, mel.data_ptr(), B, T, 1, 3, 1, 0.99, out.data_ptr(), ws, n, stream, ctypes.byref(opt)),
+          need_w, out, 123.0)
+    need_a = helpers.need(lib, "audio_from_image", plan.handle, B, 0, T, **fields)
+    assert need_a == helpers.need(lib, "audio_from_image", plan.handle, B, 0, T, loop=1) + need - loop_need
+    tiles = torch.randint(0, 256, (B, plan.n_mels, T, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(2)).cuda()
+    lut = plan.device_constant(("decode_lut", 0.25, 30e6), lambda: image_util.decode_lut(0.25, 30e6))
+    pcm = torch.full((B, L, 1), 77, dtype=torch.int16, device="cuda")
+    peak = torch.zeros(B, device="cuda")
+    sharp(lambda ws, n: lib.rfx_audio_from_image_u8_ex(plan.handle, tiles.data_ptr(), B, T, 0, lut.data_ptr(), 3, 1, 0.99, 1, peak.data_ptr(), pcm.data_ptr(),
+                                                        ws, n, stream, ctypes.byref(opt)), need_a, pcm, 77)

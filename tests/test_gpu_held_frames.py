@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import held_oracle
+import helpers
 from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
@@ -213,13 +214,13 @@ def test_held_rows_past_65535_and_across_chunks(O):
 def test_held_workspace_queries_and_launch_times(O, name):
     p, plan, op, mag, S, guide, g, _ = _case(O, name)
     lib = plan.lib
-    unheld, held = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), lib.rfx_griffinlim_held_workspace_bytes(plan.handle, B, T)
+    unheld, held = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), helpers.need(lib, "griffinlim", plan.handle, B, T, **helpers.HELD)
     assert held >= unheld + 4 * (B * T + 1)
     if name == "specialised-runs":  # the frame buffer of the per-frame form on top
         frames_plan = _plan("specialised-frames")[1]
-        assert held == lib.rfx_griffinlim_held_workspace_bytes(frames_plan.handle, B, T) > unheld + B * T * 4410 * 4
-    assert lib.rfx_waveform_from_mel_held_workspace_bytes(plan.handle, B, T) >= lib.rfx_waveform_from_mel_workspace_bytes(plan.handle, B, T)
-    assert lib.rfx_audio_from_image_held_workspace_bytes(plan.handle, B, 0, T) >= lib.rfx_audio_from_image_workspace_bytes(plan.handle, B, 0, T)
+        assert held == helpers.need(lib, "griffinlim", frames_plan.handle, B, T, **helpers.HELD) > unheld + B * T * 4410 * 4
+    assert helpers.need(lib, "waveform_from_mel", plan.handle, B, T, **helpers.HELD) >= lib.rfx_waveform_from_mel_workspace_bytes(plan.handle, B, T)
+    assert helpers.need(lib, "audio_from_image", plan.handle, B, 0, T, **helpers.HELD) >= lib.rfx_audio_from_image_workspace_bytes(plan.handle, B, 0, T)
     ms = (ctypes.c_float * 4)(-1, -1, -1, -7)
     plan.griffinlim(S, B, T, 2, 0.99, guide=g, hold=_hold(HOLDS), launch_ms=ms)
     assert all(ms[i] > 0 for i in range(3)) and ms[3] == -7
@@ -232,7 +233,7 @@ def test_refusals_launch_nothing(O, name):
 
     p, plan, op, mag, S, guide, g, _ = _case(O, name)
     lib, L = plan.lib, g.shape[1]
-    unheld, held = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), lib.rfx_griffinlim_held_workspace_bytes(plan.handle, B, T)
+    unheld, held = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), helpers.need(lib, "griffinlim", plan.handle, B, T, **helpers.HELD)
     ws = torch.empty(held + 16, dtype=torch.uint8, device="cuda")
     stream = _hip.current_stream(torch.device("cuda"))
     out = torch.full((B, L), 123.0, device="cuda")
@@ -259,7 +260,7 @@ def test_refusals_launch_nothing(O, name):
     assert rc == -3
     # the fused entries check the held query too
     mel = torch.ones(B, plan.n_mels, T, device="cuda")
-    need = lib.rfx_waveform_from_mel_held_workspace_bytes(plan.handle, B, T)
+    need = helpers.need(lib, "waveform_from_mel", plan.handle, B, T, **helpers.HELD)
     ws2 = torch.empty(need, dtype=torch.uint8, device="cuda")
     opt = _hip.RfxHeldCallOptions(size, 0, 0, 0.0, 0.0, g.data_ptr(), L, L, 0, hold.data_ptr(), 0)
     assert lib.rfx_waveform_from_mel_ex(plan.handle, mel.data_ptr(), B, T, 1, 0, 2, 0.99, out.data_ptr(), ws2.data_ptr(), need - 1, stream, ctypes.byref(opt)) == -3

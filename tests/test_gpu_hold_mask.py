@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import mask_oracle
+import helpers
 from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
 from test_gpu_held_frames import B, CLIP2, ENGINES, T, _bits, _plan, _stft64
 
@@ -194,13 +195,13 @@ def test_masked_rows_past_65535():
 def test_masked_workspace_queries_and_launch_times(O, name):
     p, plan, op, mag, S, guide, g, _, held, bits = _case(O, name)
     lib = plan.lib
-    plain, masked = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), lib.rfx_griffinlim_masked_workspace_bytes(plan.handle, B, T)
+    plain, masked = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), helpers.need(lib, "griffinlim", plan.handle, B, T, **helpers.MASKED)
     L = g.shape[1]
     assert masked >= plain + 4 * (B * T * op.n_stft + B * L)  # X and c
     if name == "specialised-runs":  # the frame buffer of the per-frame form on top
-        assert masked == lib.rfx_griffinlim_masked_workspace_bytes(_plan("specialised-frames")[1].handle, B, T) > plain + B * T * 4410 * 4
-    assert lib.rfx_waveform_from_mel_masked_workspace_bytes(plan.handle, B, T) >= lib.rfx_waveform_from_mel_workspace_bytes(plan.handle, B, T)
-    assert lib.rfx_audio_from_image_masked_workspace_bytes(plan.handle, B, 0, T) >= lib.rfx_audio_from_image_workspace_bytes(plan.handle, B, 0, T)
+        assert masked == helpers.need(lib, "griffinlim", _plan("specialised-frames")[1].handle, B, T, **helpers.MASKED) > plain + B * T * 4410 * 4
+    assert helpers.need(lib, "waveform_from_mel", plan.handle, B, T, **helpers.MASKED) >= lib.rfx_waveform_from_mel_workspace_bytes(plan.handle, B, T)
+    assert helpers.need(lib, "audio_from_image", plan.handle, B, 0, T, **helpers.MASKED) >= lib.rfx_audio_from_image_workspace_bytes(plan.handle, B, 0, T)
     assert lib.rfx_hold_mask_words(plan.handle) == (op.n_stft + 31) // 32 == plan.hold_mask_words
     ms = (ctypes.c_float * 4)(-1, -1, -1, -7)
     plan.griffinlim(S, B, T, 2, 0.99, guide=g, hold_bins=bits, launch_ms=ms)
@@ -214,7 +215,7 @@ def test_refusals_launch_nothing(O, name):
 
     p, plan, op, mag, S, guide, g, _, held, bits = _case(O, name)
     lib, L = plan.lib, g.shape[1]
-    plain, masked = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), lib.rfx_griffinlim_masked_workspace_bytes(plan.handle, B, T)
+    plain, masked = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T), helpers.need(lib, "griffinlim", plan.handle, B, T, **helpers.MASKED)
     ws = torch.empty(masked + 16, dtype=torch.uint8, device="cuda")
     stream = _hip.current_stream(torch.device("cuda"))
     out = torch.full((B, L), 123.0, device="cuda")
@@ -249,7 +250,7 @@ def test_refusals_launch_nothing(O, name):
     assert rc == -3
     # the fused entries check the masked query too
     mel = torch.ones(B, plan.n_mels, T, device="cuda")
-    need = lib.rfx_waveform_from_mel_masked_workspace_bytes(plan.handle, B, T)
+    need = helpers.need(lib, "waveform_from_mel", plan.handle, B, T, **helpers.MASKED)
     ws2 = torch.empty(need, dtype=torch.uint8, device="cuda")
     opt = _hip.RfxMaskedCallOptions(size, 0, 0, 0.0, 0.0, g.data_ptr(), L, L, 0, None, 0, bits.data_ptr(), words, 0)
     assert lib.rfx_waveform_from_mel_ex(plan.handle, mel.data_ptr(), B, T, 1, 0, 2, 0.99, out.data_ptr(), ws2.data_ptr(), need - 1, stream, ctypes.byref(opt)) == -3

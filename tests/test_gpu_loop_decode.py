@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import loop_oracle
+import helpers
 from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
@@ -165,12 +166,12 @@ def test_loop_zero_in_the_grown_struct_is_the_masked_size_call(O, name):
     pairs = torch.tensor([[3, 2]] * B, dtype=torch.int32, device="cuda")
     bits = torch.zeros((B, T, plan.hold_mask_words), dtype=torch.int32, device="cuda")
     bits[:, :, :40] = -1
-    ws = torch.empty(lib.rfx_griffinlim_masked_workspace_bytes(plan.handle, B, T), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(helpers.need(lib, "griffinlim", plan.handle, B, T, **helpers.MASKED), dtype=torch.uint8, device="cuda")
     stream = _hip.current_stream(torch.device("cuda"))
     cases = {"plain": dict(), "guided": dict(guide=g), "held": dict(guide=g, hold=pairs), "masked": dict(guide=g, hold_bins=bits)}
     for what, kw in cases.items():
         want = plan.griffinlim(S, B, T, n_iter, 0.99, seed=6, **kw)
-        o = _hip.masked_call_options(kw.get("guide"), kw.get("hold"), kw.get("hold_bins"), B)
+        o = _hip.call_options(rows=B, **kw)
         grown = _hip.RfxLoopCallOptions(ctypes.sizeof(_hip.RfxLoopCallOptions), o.flags, o.row_base, o.magnitude_hint, 0.0,
                                         getattr(o, "d_guide", None), getattr(o, "guide_stride", 0), getattr(o, "guide_samples", 0), 0,
                                         getattr(o, "d_hold_frames", None), 0, getattr(o, "d_hold_bins", None), getattr(o, "hold_words", 0), 0, 0, 0)
@@ -186,12 +187,12 @@ def test_loop_zero_in_the_grown_struct_is_the_masked_size_call(O, name):
 def test_loop_workspace_queries_and_launch_times(O, name):
     p, plan, op, mag, a0, S, A = _case(O, name)
     lib = plan.lib
-    need = lib.rfx_griffinlim_loop_workspace_bytes(plan.handle, B, T)
+    need = helpers.need(lib, "griffinlim", plan.handle, B, T, loop=1)
     assert need > 0 and lib.rfx_griffinlim_loop_output_samples(plan.handle, T) == p.hop_length * T == plan.output_samples(T, True)
     assert need >= 4 * B * T * op.win_length  # the synthesis frames
-    assert lib.rfx_griffinlim_loop_workspace_bytes(plan.handle, B, loop_oracle.min_frames(op) - 1) == 0
-    assert lib.rfx_waveform_from_mel_loop_workspace_bytes(plan.handle, B, T) > need
-    assert lib.rfx_audio_from_image_loop_workspace_bytes(plan.handle, B, 0, T) > lib.rfx_waveform_from_mel_loop_workspace_bytes(plan.handle, B, T)
+    assert helpers.need(lib, "griffinlim", plan.handle, B, loop_oracle.min_frames(op) - 1, loop=1) == 0
+    assert helpers.need(lib, "waveform_from_mel", plan.handle, B, T, loop=1) > need
+    assert helpers.need(lib, "audio_from_image", plan.handle, B, 0, T, loop=1) > helpers.need(lib, "waveform_from_mel", plan.handle, B, T, loop=1)
     ms = (ctypes.c_float * 4)(-1, -1, -1, -7)
     plan.griffinlim(S, B, T, 2, 0.99, angles0_slots=A, loop=True, launch_ms=ms)
     assert all(ms[i] > 0 for i in range(3)) and ms[3] == -7
@@ -204,8 +205,8 @@ def test_refusals_launch_nothing(O, name):
 
     p, plan, op, mag, a0, S, A = _case(O, name)
     lib, P = plan.lib, p.hop_length * T
-    need = lib.rfx_griffinlim_loop_workspace_bytes(plan.handle, B, T)
-    ws = torch.empty(need + lib.rfx_griffinlim_masked_workspace_bytes(plan.handle, B, T), dtype=torch.uint8, device="cuda")
+    need = helpers.need(lib, "griffinlim", plan.handle, B, T, loop=1)
+    ws = torch.empty(need + helpers.need(lib, "griffinlim", plan.handle, B, T, **helpers.MASKED), dtype=torch.uint8, device="cuda")
     stream = _hip.current_stream(torch.device("cuda"))
     out = torch.full((B, P), 123.0, device="cuda")
     g = synthetic_wave(B, P, seed=202).cuda()
@@ -260,7 +261,7 @@ def test_the_chirp_z_engine_refuses_a_loop_call():
     p, plan = _plan("chirp-z-1009")
     lib = plan.lib
     assert p.hop_length * T >= p.n_fft  # the frame count is not what is refused
-    assert lib.rfx_griffinlim_loop_workspace_bytes(plan.handle, B, T) == 0 == lib.rfx_waveform_from_mel_loop_workspace_bytes(plan.handle, B, T)
+    assert helpers.need(lib, "griffinlim", plan.handle, B, T, loop=1) == 0 == helpers.need(lib, "waveform_from_mel", plan.handle, B, T, loop=1)
     S = torch.ones(B * T * plan.frame_stride, device="cuda")
     P = p.hop_length * T
     out = torch.full((B, P), 123.0, device="cuda")
@@ -307,13 +308,13 @@ def test_fused_loop_call_equals_its_parts(golden_dir, lstsq):
     assert unlooped.shape == (N, P - p.hop_length, C) and int(pcm1.abs().max()) > 30000
     # a workspace one byte below the loop query
     stream = _hip.current_stream(torch.device("cuda"))
-    opt = _hip.loop_call_options(None, None, None, N * C, lstsq=lstsq, loop=True)
-    need = lib.rfx_waveform_from_mel_loop_workspace_bytes(plan.handle, N * C, W)
+    opt = _hip.call_options(rows=N * C, lstsq=lstsq, loop=True)
+    need = helpers.need(lib, "waveform_from_mel", plan.handle, N * C, W, loop=1)
     ws = torch.empty(need, dtype=torch.uint8, device="cuda")
     out = torch.full((N * C, P), 123.0, device="cuda")
     assert lib.rfx_waveform_from_mel_ex(plan.handle, mel.data_ptr(), N * C, W, C, seed, n_iter, 0.99, out.data_ptr(), ws.data_ptr(), need - 1, stream,
                                         ctypes.byref(opt)) == -3
-    need = lib.rfx_audio_from_image_loop_workspace_bytes(plan.handle, N, 1, W)
+    need = helpers.need(lib, "audio_from_image", plan.handle, N, 1, W, loop=1)
     ws = torch.empty(need, dtype=torch.uint8, device="cuda")
     pcm = torch.full((N, P, C), 77, dtype=torch.int16, device="cuda")
     peak = torch.zeros(N, device="cuda")

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
 import peak_start_inputs as inputs
 import peak_start_oracle
 
@@ -231,7 +232,7 @@ def test_start_zero_changes_nothing_and_short_workspaces_are_refused(O, golden_d
     S = plan.pack_magnitudes(torch.from_numpy(np.nan_to_num(mag)).cuda())
     L = plan.output_samples(T)
     stream = _hip.current_stream(torch.device("cuda"))
-    need = lib.rfx_griffinlim_peak_workspace_bytes(plan.handle, B, T)
+    need = helpers.need(lib, "griffinlim", plan.handle, B, T, start=1)
     base = lib.rfx_griffinlim_workspace_bytes(plan.handle, B, T)
     angles_bytes = -(-B * T * plan.frame_stride * 8 // 256) * 256
     assert need == base + angles_bytes + lib.rfx_peak_start_workspace_bytes(plan.handle, B, T)
@@ -268,11 +269,11 @@ def test_start_zero_changes_nothing_and_short_workspaces_are_refused(O, golden_d
                                (start_opt(1, d_guide=g.data_ptr(), d_bins=bits.data_ptr()), None, b"d_hold_bins")):
         rc, out = call(opt, need, angles0)
         assert rc == -1 and word in lib.rfx_last_error() and bool((out == 123.0).all()), word
-    # the fused entries' twins
+    # the fused entries' queries
     mel = torch.rand(B, plan.n_mels, T, generator=torch.Generator().manual_seed(1)).cuda() * 1e6
     opt = start_opt(1)
     opt.row_base = 0
-    need_w = lib.rfx_waveform_from_mel_peak_workspace_bytes(plan.handle, B, T)
+    need_w = helpers.need(lib, "waveform_from_mel", plan.handle, B, T, start=1)
     assert need_w == lib.rfx_waveform_from_mel_workspace_bytes(plan.handle, B, T) + need - base
     ws_w = torch.empty(need_w, dtype=torch.uint8, device="cuda")
     out = torch.full((B, L), 123.0, device="cuda")
@@ -282,7 +283,7 @@ def test_start_zero_changes_nothing_and_short_workspaces_are_refused(O, golden_d
     assert bool((out == 123.0).all())
     assert lib.rfx_waveform_from_mel_ex(*args, need_w, stream, ctypes.byref(opt)) == 0
     assert _bits(out) == _bits(plan.waveform_from_mel(mel, 1, 2, 0.99, seed=3, peak_start=True))
-    need_a = lib.rfx_audio_from_image_peak_workspace_bytes(plan.handle, B, 0, T)
+    need_a = helpers.need(lib, "audio_from_image", plan.handle, B, 0, T, start=1)
     assert need_a == lib.rfx_audio_from_image_workspace_bytes(plan.handle, B, 0, T) + need - base
     ws_a = torch.empty(need_a, dtype=torch.uint8, device="cuda")
     tiles = torch.randint(0, 256, (B, plan.n_mels, T, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(2)).cuda()

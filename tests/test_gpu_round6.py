@@ -58,7 +58,7 @@ def test_pcm_is_independent_of_chunking_and_sharding(stereo, width):
     # ... and a different row_base IS a different draw (the key really is the global row)
     other, _ = plan.audio_from_image(dev_tiles[3:5], stereo, lut, conv.p.num_griffin_lim_iters, 0.99, seed=4242, clip_base=0, magnitude_hint=30e6)
     assert not np.array_equal(other.cpu().numpy(), whole[3:5])
-    assert _hip.call_options(3 * C).row_base == 3 * C
+    assert _hip.call_options(row_base=3 * C).row_base == 3 * C
 
 
 @pytest.mark.parametrize("rate", [48000, 22050, 11025])

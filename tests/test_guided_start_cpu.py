@@ -19,6 +19,8 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_guide_emu.cpp")
 CLIP2 = "clip_2_start_103694_ms_duration_5678_ms.wav"
@@ -235,14 +237,14 @@ def test_guided_options_layout_matches_the_header(repo_root, tmp_path):
 def test_guided_options_builder():
     from riffusion import _hip
 
-    assert isinstance(_hip.guided_call_options(None, 3, row_base=2), _hip.RfxCallOptions)
+    assert isinstance(_hip.call_options(rows=3, row_base=2), _hip.RfxCallOptions)
     g = torch.zeros(3, 50)
-    o = _hip.guided_call_options(g[:, :40], 3, row_base=2, magnitude_hint=5.0, lstsq=True)
+    o = _hip.call_options(guide=g[:, :40], rows=3, row_base=2, magnitude_hint=5.0, lstsq=True)
     assert (o.struct_size, o.flags, o.row_base, o.magnitude_hint) == (48, 1, 2, 5.0)
     assert (o.d_guide, o.guide_stride, o.guide_samples, o.reserved2) == (g.data_ptr(), 50, 40, 0)
     for bad in (g[:2], g.double(), g[:, ::2], g[0]):
         with pytest.raises(ValueError):
-            _hip.guided_call_options(bad, 3)
+            _hip.call_options(guide=bad, rows=3)
 
 
 def _guided(d_guide=0x1000, stride=100, samples=100, reserved=0.0, reserved2=0, size=None):
@@ -266,6 +268,7 @@ def test_guided_options_are_refused_before_any_device_work(lib, kw, word):
     assert lib.rfx_waveform_from_mel_ex(None, None, 1, 30, 1, 0, 1, 0.5, None, None, 0, None, ctypes.byref(opt)) == -1 and word in lib.rfx_last_error()
     assert lib.rfx_audio_from_image_u8_ex(None, None, 1, 30, 0, None, 0, 1, 0.5, 1, None, None, None, 0, None, ctypes.byref(opt)) == -1
     assert word in lib.rfx_last_error()
+    assert helpers.queries_refuse(lib, opt, word)
 
 
 def test_inverse_mel_refuses_a_guide_and_reserved_is_checked_on_the_short_struct(lib):

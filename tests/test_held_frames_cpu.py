@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import held_oracle
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_hold_emu.cpp")
@@ -197,16 +198,16 @@ def test_held_options_builder():
 
     g = torch.zeros(3, 50)
     hold = torch.tensor([[0, 0], [7, 3], [33, 0]], dtype=torch.int32)
-    assert isinstance(_hip.held_call_options(None, None, 3, row_base=2), _hip.RfxCallOptions)
-    assert isinstance(_hip.held_call_options(g, None, 3), _hip.RfxGuidedCallOptions)
-    o = _hip.held_call_options(g[:, :40], hold, 3, row_base=2, magnitude_hint=5.0, lstsq=True)
+    assert isinstance(_hip.call_options(rows=3, row_base=2), _hip.RfxCallOptions)
+    assert isinstance(_hip.call_options(guide=g, rows=3), _hip.RfxGuidedCallOptions)
+    o = _hip.call_options(guide=g[:, :40], hold=hold, rows=3, row_base=2, magnitude_hint=5.0, lstsq=True)
     assert (o.struct_size, o.flags, o.row_base, o.magnitude_hint) == (64, 1, 2, 5.0)
     assert (o.d_guide, o.guide_stride, o.guide_samples, o.reserved2, o.d_hold_frames, o.reserved3) == (g.data_ptr(), 50, 40, 0, hold.data_ptr(), 0)
     with pytest.raises(ValueError, match="needs a guide"):
-        _hip.held_call_options(None, hold, 3)
+        _hip.call_options(hold=hold, rows=3)
     for bad in (hold[:2], hold.long(), hold.t(), hold[:, :1], torch.zeros(3, 4, dtype=torch.int32)[:, ::2]):
         with pytest.raises(ValueError):
-            _hip.held_call_options(g, bad, 3)
+            _hip.call_options(guide=g, hold=bad, rows=3)
 
 
 def _held(d_guide=0x1000, d_hold=0x2000, reserved3=0, size=None):
@@ -228,6 +229,7 @@ def test_held_options_are_refused_before_any_device_work(lib, kw, word):
     assert lib.rfx_waveform_from_mel_ex(None, None, 1, 30, 1, 0, 1, 0.5, None, None, 0, None, ctypes.byref(opt)) == -1 and word in lib.rfx_last_error()
     assert lib.rfx_audio_from_image_u8_ex(None, None, 1, 30, 0, None, 0, 1, 0.5, 1, None, None, None, 0, None, ctypes.byref(opt)) == -1
     assert word in lib.rfx_last_error()
+    assert helpers.queries_refuse(lib, opt, word)
 
 
 def test_inverse_mel_refuses_held_frames_and_shorter_structs_ignore_the_tail(lib):
@@ -236,9 +238,9 @@ def test_inverse_mel_refuses_held_frames_and_shorter_structs_ignore_the_tail(lib
     # a valid held struct passes the options and fails on the null plan; the guided size ignores the tail
     assert _gl_ex(lib, _held()) == -1 and b"null argument" in lib.rfx_last_error()
     assert _gl_ex(lib, _held(reserved3=1, size=48)) == -1 and b"null argument" in lib.rfx_last_error()
-    # the held workspace queries answer 0 without a plan, like their drivers' own
-    assert lib.rfx_griffinlim_held_workspace_bytes(None, 3, 33) == 0 == lib.rfx_waveform_from_mel_held_workspace_bytes(None, 3, 33)
-    assert lib.rfx_audio_from_image_held_workspace_bytes(None, 3, 0, 33) == 0
+    # the workspace queries answer 0 for a held call without a plan, like their drivers' own
+    assert helpers.need(lib, "griffinlim", None, 3, 33, **helpers.HELD) == 0 == helpers.need(lib, "waveform_from_mel", None, 3, 33, **helpers.HELD)
+    assert helpers.need(lib, "audio_from_image", None, 3, 0, 33, **helpers.HELD) == 0
 
 
 def test_cli_hold_flags_need_a_guide(capsys):

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
 import mask_oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -308,20 +309,20 @@ def test_masked_options_builder():
     g = torch.zeros(3, 50)
     pairs = torch.zeros(3, 2, dtype=torch.int32)
     bits = torch.zeros(3, 33, 276, dtype=torch.int32)
-    assert isinstance(_hip.masked_call_options(None, None, None, 3, row_base=2), _hip.RfxCallOptions)
-    assert isinstance(_hip.masked_call_options(g, None, None, 3), _hip.RfxGuidedCallOptions)
-    assert isinstance(_hip.masked_call_options(g, pairs, None, 3), _hip.RfxHeldCallOptions)
-    o = _hip.masked_call_options(g[:, :40], None, bits, 3, row_base=2, magnitude_hint=5.0, lstsq=True)
+    assert isinstance(_hip.call_options(rows=3, row_base=2), _hip.RfxCallOptions)
+    assert isinstance(_hip.call_options(guide=g, rows=3), _hip.RfxGuidedCallOptions)
+    assert isinstance(_hip.call_options(guide=g, hold=pairs, rows=3), _hip.RfxHeldCallOptions)
+    o = _hip.call_options(guide=g[:, :40], hold_bins=bits, rows=3, row_base=2, magnitude_hint=5.0, lstsq=True)
     assert (o.struct_size, o.flags, o.row_base, o.magnitude_hint) == (80, 1, 2, 5.0)
     assert (o.d_guide, o.guide_stride, o.guide_samples, o.reserved2, o.d_hold_frames, o.reserved3) == (g.data_ptr(), 50, 40, 0, None, 0)
     assert (o.d_hold_bins, o.hold_words, o.reserved4) == (bits.data_ptr(), 276, 0)
     with pytest.raises(ValueError, match="needs a guide"):
-        _hip.masked_call_options(None, None, bits, 3)
+        _hip.call_options(hold_bins=bits, rows=3)
     with pytest.raises(ValueError, match="together with hold"):
-        _hip.masked_call_options(g, pairs, bits, 3)
+        _hip.call_options(guide=g, hold=pairs, hold_bins=bits, rows=3)
     for bad in (bits[:2], bits.long(), bits[:, :, ::2], bits[0], bits.float()):
         with pytest.raises(ValueError):
-            _hip.masked_call_options(g, None, bad, 3)
+            _hip.call_options(guide=g, hold_bins=bad, rows=3)
 
 
 def _masked(d_guide=0x1000, d_pairs=None, d_bins=0x3000, hold_words=276, reserved4=0, size=None):
@@ -344,6 +345,7 @@ def test_masked_options_are_refused_before_any_device_work(lib, kw, word):
     assert lib.rfx_waveform_from_mel_ex(None, None, 1, 30, 1, 0, 1, 0.5, None, None, 0, None, ctypes.byref(opt)) == -1 and word in lib.rfx_last_error()
     assert lib.rfx_audio_from_image_u8_ex(None, None, 1, 30, 0, None, 0, 1, 0.5, 1, None, None, None, 0, None, ctypes.byref(opt)) == -1
     assert word in lib.rfx_last_error()
+    assert helpers.queries_refuse(lib, opt, word)
 
 
 def test_inverse_mel_refuses_a_mask_and_shorter_structs_ignore_the_tail(lib):
@@ -353,9 +355,9 @@ def test_inverse_mel_refuses_a_mask_and_shorter_structs_ignore_the_tail(lib):
     assert _gl_ex(lib, _masked()) == -1 and b"null argument" in lib.rfx_last_error()
     for size in (24, 48, 64):
         assert _gl_ex(lib, _masked(reserved4=1, d_bins=0x3002, size=size)) == -1 and b"null argument" in lib.rfx_last_error(), size
-    # the masked workspace queries answer 0 without a plan, like their drivers' own
-    assert lib.rfx_griffinlim_masked_workspace_bytes(None, 3, 33) == 0 == lib.rfx_waveform_from_mel_masked_workspace_bytes(None, 3, 33)
-    assert lib.rfx_audio_from_image_masked_workspace_bytes(None, 3, 0, 33) == 0
+    # the workspace queries answer 0 for a masked call without a plan, like their drivers' own
+    assert helpers.need(lib, "griffinlim", None, 3, 33, **helpers.MASKED) == 0 == helpers.need(lib, "waveform_from_mel", None, 3, 33, **helpers.MASKED)
+    assert helpers.need(lib, "audio_from_image", None, 3, 0, 33, **helpers.MASKED) == 0
 
 
 def test_cli_hold_mask_needs_a_guide_and_excludes_the_span_flags(capsys):

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
 import loop_oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -264,16 +265,16 @@ def test_loop_options_builder():
     g = torch.zeros(3, 50)
     pairs = torch.zeros(3, 2, dtype=torch.int32)
     bits = torch.zeros(3, 33, 276, dtype=torch.int32)
-    assert isinstance(_hip.loop_call_options(None, None, None, 3, row_base=2), _hip.RfxCallOptions)
-    assert isinstance(_hip.loop_call_options(g, None, bits, 3), _hip.RfxMaskedCallOptions)
-    o = _hip.loop_call_options(None, None, None, 3, row_base=2, magnitude_hint=5.0, lstsq=True, loop=True)
+    assert isinstance(_hip.call_options(rows=3, row_base=2), _hip.RfxCallOptions)
+    assert isinstance(_hip.call_options(guide=g, hold_bins=bits, rows=3), _hip.RfxMaskedCallOptions)
+    o = _hip.call_options(rows=3, row_base=2, magnitude_hint=5.0, lstsq=True, loop=True)
     assert (o.struct_size, o.flags, o.row_base, o.magnitude_hint) == (88, 1, 2, 5.0)
     assert (o.d_guide, o.guide_stride, o.guide_samples, o.d_hold_frames, o.d_hold_bins, o.hold_words, o.loop, o.reserved5) == (None, 0, 0, None, None, 0, 1, 0)
-    o = _hip.loop_call_options(g[:, :40], None, None, 3, loop=True)
+    o = _hip.call_options(guide=g[:, :40], rows=3, loop=True)
     assert (o.d_guide, o.guide_stride, o.guide_samples, o.loop) == (g.data_ptr(), 50, 40, 1)
     for kw in (dict(hold=pairs), dict(hold_bins=bits)):
         with pytest.raises(ValueError, match="loop together with"):
-            _hip.loop_call_options(g, kw.get("hold"), kw.get("hold_bins"), 3, loop=True)
+            _hip.call_options(guide=g, rows=3, loop=True, **kw)
 
 
 def _loop(loop=1, reserved5=0, d_guide=None, d_pairs=None, d_bins=None, size=None):
@@ -297,6 +298,7 @@ def test_loop_options_are_refused_before_any_device_work(lib, kw, word):
     assert lib.rfx_waveform_from_mel_ex(None, None, 1, 41, 1, 0, 1, 0.5, None, None, 0, None, ctypes.byref(opt)) == -1 and word in lib.rfx_last_error()
     assert lib.rfx_audio_from_image_u8_ex(None, None, 1, 41, 0, None, 0, 1, 0.5, 1, None, None, None, 0, None, ctypes.byref(opt)) == -1
     assert word in lib.rfx_last_error()
+    assert helpers.queries_refuse(lib, opt, word)
 
 
 def test_inverse_mel_refuses_a_loop_and_shorter_structs_ignore_the_tail(lib):
@@ -311,9 +313,9 @@ def test_inverse_mel_refuses_a_loop_and_shorter_structs_ignore_the_tail(lib):
     from riffusion import _hip
 
     assert _gl_ex(lib, _hip.RfxCallOptions(24, 2, 0, 0.0, 0.0)) == -1 and b"flags" in lib.rfx_last_error()
-    # the loop queries answer 0 without a plan, like their drivers' own
-    assert lib.rfx_griffinlim_loop_workspace_bytes(None, 3, 41) == 0 == lib.rfx_waveform_from_mel_loop_workspace_bytes(None, 3, 41)
-    assert lib.rfx_audio_from_image_loop_workspace_bytes(None, 3, 0, 41) == 0 == lib.rfx_griffinlim_loop_output_samples(None, 41)
+    # the queries answer 0 for a loop call without a plan, like their drivers' own
+    assert helpers.need(lib, "griffinlim", None, 3, 41, loop=1) == 0 == helpers.need(lib, "waveform_from_mel", None, 3, 41, loop=1)
+    assert helpers.need(lib, "audio_from_image", None, 3, 0, 41, loop=1) == 0 == lib.rfx_griffinlim_loop_output_samples(None, 41)
 
 
 @pytest.mark.parametrize("rate,n_fft,win,hop,need", [(44100, 17640, 4410, 441, 40), (11025, 4410, 1102, 110, 41)])

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
 import peak_start_inputs as inputs
 import peak_start_oracle
 
@@ -235,15 +236,15 @@ def test_start_options_builder():
     from riffusion import _hip
 
     g = torch.zeros(3, 50)
-    assert isinstance(_hip.start_call_options(None, None, None, 3, row_base=2), _hip.RfxCallOptions)
-    assert isinstance(_hip.start_call_options(None, None, None, 3, loop=True), _hip.RfxLoopCallOptions)
-    o = _hip.start_call_options(None, None, None, 3, row_base=2, magnitude_hint=5.0, lstsq=True, peak_start=True)
+    assert isinstance(_hip.call_options(rows=3, row_base=2), _hip.RfxCallOptions)
+    assert isinstance(_hip.call_options(rows=3, loop=True), _hip.RfxLoopCallOptions)
+    o = _hip.call_options(rows=3, row_base=2, magnitude_hint=5.0, lstsq=True, peak_start=True)
     assert (o.struct_size, o.flags, o.row_base, o.magnitude_hint, o.loop, o.reserved5, o.start, o.reserved6) == (96, 1, 2, 5.0, 0, 0, 1, 0)
     assert (o.d_guide, o.d_hold_frames, o.d_hold_bins) == (None, None, None)
-    assert _hip.start_call_options(None, None, None, 3, loop=True, peak_start=True).loop == 1
+    assert _hip.call_options(rows=3, loop=True, peak_start=True).loop == 1
     for kw in (dict(guide=g), dict(guide=g, hold=torch.zeros(3, 2, dtype=torch.int32)), dict(guide=g, hold_bins=torch.zeros(3, 4, 51, dtype=torch.int32))):
         with pytest.raises(ValueError, match="peak_start together with"):
-            _hip.start_call_options(kw.get("guide"), kw.get("hold"), kw.get("hold_bins"), 3, peak_start=True)
+            _hip.call_options(rows=3, peak_start=True, **kw)
     assert _hip.check_phase_start("random", guide=g) is False and _hip.check_phase_start("peaks", guide=None) is True
     with pytest.raises(ValueError, match="phase_start must be one of"):
         _hip.check_phase_start("peak")
@@ -272,6 +273,7 @@ def test_start_options_are_refused_before_any_device_work(lib, kw, word):
     assert lib.rfx_waveform_from_mel_ex(None, None, 1, 41, 1, 0, 1, 0.5, None, None, 0, None, ctypes.byref(opt)) == -1 and word in lib.rfx_last_error()
     assert lib.rfx_audio_from_image_u8_ex(None, None, 1, 41, 0, None, 0, 1, 0.5, 1, None, None, None, 0, None, ctypes.byref(opt)) == -1
     assert word in lib.rfx_last_error()
+    assert helpers.queries_refuse(lib, opt, word)
 
 
 def test_injected_angles_inverse_mel_shorter_structs_and_queries(lib):
@@ -288,10 +290,24 @@ def test_injected_angles_inverse_mel_shorter_structs_and_queries(lib):
         assert _gl_ex(lib, _start(start=2, reserved6=9, size=size)) == -1 and b"null argument" in lib.rfx_last_error(), size
     # flags == 2 stays refused: the start is not a flag bit
     assert _gl_ex(lib, _hip.RfxCallOptions(24, 2, 0, 0.0, 0.0)) == -1 and b"flags" in lib.rfx_last_error()
-    # the twins answer 0 without a plan, like their drivers' own; the entry refuses a null plan and takes B == 0 only with one
-    assert lib.rfx_griffinlim_peak_workspace_bytes(None, 3, 41) == 0 == lib.rfx_waveform_from_mel_peak_workspace_bytes(None, 3, 41)
-    assert lib.rfx_audio_from_image_peak_workspace_bytes(None, 3, 0, 41) == 0 == lib.rfx_peak_start_workspace_bytes(None, 3, 41)
+    # the queries answer 0 for a call with the start without a plan, like their drivers' own; the entry refuses a null plan and
+    # takes B == 0 only with one
+    assert helpers.need(lib, "griffinlim", None, 3, 41, start=1) == 0 == helpers.need(lib, "waveform_from_mel", None, 3, 41, start=1)
+    assert helpers.need(lib, "audio_from_image", None, 3, 0, 41, start=1) == 0 == lib.rfx_peak_start_workspace_bytes(None, 3, 41)
     assert lib.rfx_peak_start(None, None, 0, 41, None, None, 0, None) == -1 and b"null argument" in lib.rfx_last_error()
+
+
+def test_valid_options_size_nothing_without_a_plan(lib):
+    """every served combination, and no options at all: 0 for a NULL plan, as the plain queries answer"""
+    for fields in ({}, helpers.GUIDE, helpers.HELD, helpers.MASKED, dict(loop=1), dict(helpers.GUIDE, loop=1), dict(start=1), dict(loop=1, start=1),
+                   dict(flags=1, loop=1, start=1, row_base=5, magnitude_hint=2.0)):
+        assert helpers.need(lib, "waveform_from_mel", None, 3, 41, **fields) == 0 == helpers.need(lib, "audio_from_image", None, 3, 1, 41, **fields)
+        if "flags" not in fields:
+            assert helpers.need(lib, "griffinlim", None, 3, 41, **fields) == 0
+    assert lib.rfx_griffinlim_workspace_bytes_ex(None, 3, 41, None) == 0 == lib.rfx_waveform_from_mel_workspace_bytes_ex(None, 3, 41, None)
+    assert lib.rfx_audio_from_image_workspace_bytes_ex(None, 3, 1, 41, None) == 0 == lib.rfx_griffinlim_workspace_bytes(None, 3, 41)
+    # Griffin-Lim itself reads no flag, as rfx_griffinlim_ex
+    assert helpers.need(lib, "griffinlim", None, 3, 41, flags=1) == 0 and lib.rfx_last_error().startswith(b"rfx_griffinlim_workspace_bytes_ex: rfx_call_options.flags")
 
 
 def test_cli_phase_start_flags(capsys):
