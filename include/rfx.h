@@ -930,6 +930,40 @@ size_t rfx_png_encode_workspace_bytes(int N, int H, int W);
 int rfx_png_encode_u8(const uint8_t* d_rgb, int N, int H, int W, int mode, uint8_t* d_stream, int32_t* d_stream_bytes, uint32_t* d_crc,
                       int32_t* d_channels, void* d_workspace, void* stream);
 
+/* ---- PNG decode: np.asarray(Image.open(f).convert("RGB")) of a PNG tile, on the device ------------------------------------------
+ * The other direction: files of the corpus to (N, H, W, 3) uint8 tiles, the pixels Pillow gives, byte for byte - inflate (RFC 1950
+ * / 1951: stored, fixed and dynamic blocks, the Adler-32), PNG's five row filters and the step to RGB (grey three times, RGB as
+ * is, RGBA without its alpha, palette[index]) are integer work throughout.  Taken: bit depth 8, colour type 0, 2, 3 or 6, no
+ * interlace, whatever wrote the stream (zlib at any level and strategy, rfx_png_encode_u8).  The chunks are the caller's to walk
+ * (riffusion.util.image_util.png_parse), which also keeps every other kind of file on the host.  A deflate stream is a chain, so
+ * the parallelism is across the files of a call: one wave per image inflates with the 32 KiB window as a ring in LDS, its lanes
+ * sharing table building, match copies and the write-out; one workgroup per image then unfilters row by row.  No workgroup
+ * waits for another one, and every loop ends with the input or output it consumes.
+ *
+ * rfx_png_decode_u8: image n's zlib stream - its IDAT payloads concatenated in file order - is d_streams[offsets[n] ..
+ *   offsets[n + 1]); h_stream_offsets (host) and d_stream_offsets (device memory) are the same N + 1 int64, not decreasing, the
+ *   first not negative; d_streams is aligned to 16 bytes and holds offsets[N] bytes.  All images are H x W of `color_type`.
+ *   d_palettes: (N, 256, 3) uint8 and d_palette_entries: (N) int32, each image's PLTE and its entry count; read for colour type 3
+ *   only (NULL otherwise).  d_rgb: (N, H, W, 3) uint8.  d_status: (N) int32, one per image, the first cause in stream order:
+ *     0 decoded; 1 the zlib header (CM, CINFO, FDICT, check bits); 2 block type 3, or a stored block's LEN != ~NLEN; 3 a dynamic
+ *     header that does not define two usable prefix codes (HLIT > 286, HDIST > 30, a repeat with nothing before it or past the
+ *     count, an over-subscribed code, an incomplete literal/length or code-length code, no end-of-block code, an incomplete
+ *     distance code other than a single code of one bit or no code at all, RFC 1951's block of literals only); 4 bits that are no code, length symbol 286 / 287, distance symbol 30 /
+ *     31; 5 a distance beyond the bytes produced so far; 6 the input ends inside the stream; 7 more output than H * (W * bpp + 1);
+ *     8 fewer bytes at the final block's end; 9 Adler-32 mismatch; 10 bytes left over behind the Adler-32; 11 a filter type above
+ *     4; 12 a palette index at or past the image's entry count.
+ *   Status 0 means the pixels are Pillow's; the decoder refuses what it is not sure zlib and Pillow take the same way (refusing
+ *   costs time, never correctness: the caller opens such a file with Pillow).  An image with a non-zero status has undefined
+ *   pixels; the others of the call are not affected.  No read leaves d_streams' offsets[N] bytes or the workspace, whatever the
+ *   bytes are.  d_workspace holds rfx_png_decode_workspace_bytes(N, H, W, color_type, offsets[N] - offsets[0]) (0 for arguments
+ *   the call refuses), aligned to 256 bytes.  H or W above 65535, a stream longer than 2^28 - 64 bytes, or more filtered bytes than
+ *   a launch indexes (N * H * (W * bpp + 1), each image rounded up to 256, above 2^63 - 1) are RFX_ERR_UNSUPPORTED, refused before
+ *   anything is launched.  All launches go to `stream`; nothing synchronises. */
+size_t rfx_png_decode_workspace_bytes(int N, int H, int W, int color_type, size_t total_stream_bytes);
+int rfx_png_decode_u8(const uint8_t* d_streams, const int64_t* h_stream_offsets, const int64_t* d_stream_offsets, int N, int H, int W,
+                      int color_type, const uint8_t* d_palettes, const int32_t* d_palette_entries, uint8_t* d_rgb, int32_t* d_status,
+                      void* d_workspace, void* stream);
+
 /* ---- int16 front end of the encode: pydub's set_frame_rate / set_channels and the clip slicing on the device -------------------
  * What the reference does on the host before every encode (cli.py:132-193, streamlit/tasks/audio_to_audio.py): AudioSegment
  * .set_channels (audioop.tomono(data, 2, 0.5, 0.5) / audioop.tostereo(data, 2, 1, 1)), .set_frame_rate

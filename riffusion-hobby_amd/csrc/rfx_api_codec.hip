@@ -1,5 +1,5 @@
 // rfx_api_codec.hip - the C ABI of librfx.so (include/rfx.h), the entry points that take no plan: image decode / encode, int16 PCM,
-// its filters, compressor and stitch, the image resize, the JPEG scan and its decode, and the int16 front end of the encode (resample, channel
+// its filters, compressor and stitch, the image resize, the JPEG scan and its decode, the PNG stream and its decode, and the int16 front end of the encode (resample, channel
 // mix, clip gather).  They run on the device that owns their output buffer.
 #include "rfx_api.h"
 #include "rfx_compress_core.h"
@@ -8,6 +8,7 @@
 #include "rfx_pcm_core.h"
 #include "rfx_pcm_in_core.h"
 #include "rfx_png_core.h"
+#include "rfx_png_dec_core.h"
 #include "rfx_resize_core.h"
 
 using namespace rfx;
@@ -263,6 +264,53 @@ int rfx_jpeg_decode_u8(const uint8_t* d_scans, const int64_t* h_scan_offsets, co
   RFX_ON_DEVICE(dev);
   RFX_HIP(launch_jpeg_decode(d_scans, d_scan_offsets, longest, (size_t)(h_scan_offsets[N] - h_scan_offsets[0]), N, H, W, d_qtables, d_huff, d_rgb,
                              d_status, d_workspace, (hipStream_t)stream));
+  return RFX_OK;
+}
+
+// ---- PNG decode (rfx_png_dec.hip) -------------------------------------------------------------------------------------------------
+static bool png_decode_type_ok(int color_type) { return pngd_bpp(color_type) != 0; }
+// what keeps a decode inside its index types: one workgroup per image, and byte positions in the workspace and in d_rgb are int64
+static const char* png_decode_batch_limit(int N, int H, int W, int color_type) {
+  const uint64_t per_image = (pngd_filtered_bytes(H, W, pngd_bpp(color_type)) + 255) / 256 * 256;
+  if (per_image > (uint64_t)INT64_MAX / (uint64_t)N) return "more filtered bytes than one launch indexes; decode in pieces";
+  return nullptr;
+}
+static bool png_decode_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= kPngdMaxSize && W <= kPngdMaxSize; }
+
+size_t rfx_png_decode_workspace_bytes(int N, int H, int W, int color_type, size_t total_stream_bytes) {
+  if (N < 1 || !png_decode_size_ok(H, W) || !png_decode_type_ok(color_type) || png_decode_batch_limit(N, H, W, color_type) ||
+      total_stream_bytes > (size_t)N * (size_t)kPngdMaxStreamBytes)
+    return 0;
+  return png_decode_workspace_layout(N, H, W, color_type).total;
+}
+
+int rfx_png_decode_u8(const uint8_t* d_streams, const int64_t* h_stream_offsets, const int64_t* d_stream_offsets, int N, int H, int W,
+                      int color_type, const uint8_t* d_palettes, const int32_t* d_palette_entries, uint8_t* d_rgb, int32_t* d_status,
+                      void* d_workspace, void* stream) {
+  if (N < 1 || H < 1 || W < 1) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: N, H and W must be positive");
+  if (!png_decode_type_ok(color_type)) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: color_type must be 0, 2, 3 or 6");
+  if (!png_decode_size_ok(H, W))
+    return fail(RFX_ERR_UNSUPPORTED, "rfx_png_decode_u8: " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): this entry takes at most 65535 rows and columns");
+  if (const char* why = png_decode_batch_limit(N, H, W, color_type)) return fail(RFX_ERR_UNSUPPORTED, std::string("rfx_png_decode_u8: ") + why);
+  if (!h_stream_offsets) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: h_stream_offsets is NULL");
+  if (h_stream_offsets[0] < 0) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: the first stream offset is negative");
+  for (int n = 0; n < N; ++n) {
+    const int64_t bytes = h_stream_offsets[n + 1] - h_stream_offsets[n];
+    if (bytes < 0) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: stream offsets must not decrease (image " + std::to_string(n) + ")");
+    if (bytes > kPngdMaxStreamBytes)
+      return fail(RFX_ERR_UNSUPPORTED, "rfx_png_decode_u8: the stream of image " + std::to_string(n) + " is longer than 2^28 - 64 bytes");
+  }
+  if (!d_streams || !d_stream_offsets || !d_rgb || !d_status || !d_workspace || (color_type == 3 && (!d_palettes || !d_palette_entries)))
+    return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: null pointer");
+  if (reinterpret_cast<uintptr_t>(d_streams) % 16) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: d_streams must be aligned to 16 bytes");
+  if (reinterpret_cast<uintptr_t>(d_workspace) % 256 || reinterpret_cast<uintptr_t>(d_status) % 4 || reinterpret_cast<uintptr_t>(d_stream_offsets) % 8 ||
+      (color_type == 3 && reinterpret_cast<uintptr_t>(d_palette_entries) % 4))
+    return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: d_workspace must be aligned to 256 bytes, d_stream_offsets to 8, d_status and d_palette_entries to 4");
+  int dev;
+  if (int rc = device_of(d_rgb, &dev)) return rc;
+  RFX_ON_DEVICE(dev);
+  RFX_HIP(launch_png_decode(d_streams, d_stream_offsets, N, H, W, color_type, d_palettes, d_palette_entries, d_rgb, d_status, d_workspace,
+                            (hipStream_t)stream));
   return RFX_OK;
 }
 

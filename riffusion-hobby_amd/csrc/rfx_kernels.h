@@ -514,6 +514,14 @@ hipError_t launch_png_encode(const uint8_t* rgb, int N, int H, int W, int mode, 
 hipError_t launch_jpeg_decode(const uint8_t* scans, const int64_t* offsets, int64_t max_scan_bytes, size_t total_scan_bytes, int N, int H, int W,
                               const uint16_t* qtables, const uint8_t* huff, uint8_t* rgb, int32_t* status, void* workspace, hipStream_t s);
 
+// zlib streams of PNG tiles to (N, H, W, 3) uint8 tiles (rfx_png_dec.hip, the decoder in rfx_png_dec_core.h): image n's
+// concatenated IDAT payloads are streams[offsets[n] .. offsets[n + 1]) (offsets: N + 1 int64 in device memory; streams 16-byte
+// aligned); colour type 0, 2, 3 or 6, for 3 with palettes (N, 256, 3) and palette_entries (N); status[n] receives 0 or a kPngd*
+// code.  The caller has checked the sizes (1 .. 65535, every stream at most kPngdMaxStreamBytes).  workspace: 256-byte aligned,
+// png_decode_workspace_layout (rfx_png_dec_core.h, host inline, shared with the host emulator).
+hipError_t launch_png_decode(const uint8_t* streams, const int64_t* offsets, int N, int H, int W, int color_type, const uint8_t* palettes,
+                             const int32_t* palette_entries, uint8_t* rgb, int32_t* status, void* workspace, hipStream_t s);
+
 // int16 front end of the encode (rfx_pcm_in.hip, arithmetic in rfx_pcm_in_core.h).  launch_pcm_ratecv: the (L, C_in) recording
 // `in`, mixed to C_out channels, then audioop.ratecv to the K = ratecv_out_frames(L, ...) frames of `out`; both pointers are
 // frame-aligned.  launch_pcm_clips: N clips of Lw frames at the frame offsets `starts` (device memory) of `pcm`, mixed to C_out

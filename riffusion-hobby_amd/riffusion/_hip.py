@@ -429,6 +429,9 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_jpeg_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t]),
     "rfx_jpeg_decode_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "rfx_png_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_size_t]),
+    "rfx_png_decode_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "rfx_png_stream_capacity": (c_size_t, [c_int, c_int, c_int]),
     "rfx_png_encode_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rfx_png_encode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -1237,6 +1240,53 @@ class Plan:
         with self._workspace(need) as ws:
             check(self.lib.rfx_jpeg_decode_u8(base + head + pad, offsets.ctypes.data, base, N, int(H), int(W), base + offsets.nbytes,
                                               base + offsets.nbytes + qtables.nbytes, out.data_ptr(), status.data_ptr(), ws.data_ptr(), self._stream()))
+            status_np = status.cpu().numpy()
+        return out, status_np
+
+    def png_decode(self, streams: T.Sequence[bytes], H: int, W: int, color_type: int, palettes: T.Optional[np.ndarray] = None,
+                   palette_entries: T.Optional[np.ndarray] = None) -> T.Tuple[torch.Tensor, np.ndarray]:
+        """N zlib streams of H x W PNG images of one colour type (0, 2, 3 or 6; bit depth 8, not interlaced) - each the file's IDAT
+        payloads concatenated: `image_util.png_parse` - with, for colour type 3, each image's (256, 3) palette and its entry count
+        -> the (N, H, W, 3) uint8 pixels Pillow's `convert("RGB")` gives, on this device, and the (N,) int32 status of every image
+        (rfx_png_decode_u8; 0: decoded, anything else: that image's pixels are undefined).  Offsets, palettes and streams go up in
+        one copy; reading the status is the call's one synchronisation."""
+        N = len(streams)
+        H, W, color_type = int(H), int(W), int(color_type)
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=self.device)
+        if N == 0:
+            return out, np.zeros(0, np.int32)
+        offsets = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in streams], out=offsets[1:])
+        total = int(offsets[-1])
+        parts = [offsets.view(np.uint8)]
+        pal_at = ent_at = 0
+        if color_type == 3:
+            if palettes is None or palette_entries is None:
+                raise ValueError("colour type 3 needs palettes and palette_entries")
+            pal = np.ascontiguousarray(palettes, dtype=np.uint8).reshape(N, 768)
+            ent = np.ascontiguousarray(palette_entries, dtype=np.int32).reshape(N)
+            ent_at = offsets.nbytes
+            pal_at = ent_at + ent.nbytes
+            parts += [ent.view(np.uint8), pal.reshape(-1)]
+        need = self.lib.rfx_png_decode_workspace_bytes(N, H, W, color_type, total)
+        # one upload: [offsets | palette entries | palettes | streams], the streams on a 16-byte boundary
+        head = sum(p.size for p in parts)
+        pad = -head % 16
+        host = np.concatenate(parts + [np.zeros(pad, np.uint8), np.frombuffer(b"".join(streams), np.uint8)])
+        up = torch.from_numpy(host).to(self.device)
+        base = up.data_ptr()
+        status = torch.empty((N,), dtype=torch.int32, device=self.device)
+
+        def call(workspace: T.Optional[int]) -> int:
+            return self.lib.rfx_png_decode_u8(base + head + pad, offsets.ctypes.data, base, N, H, W, color_type,
+                                              base + pal_at if color_type == 3 else None, base + ent_at if color_type == 3 else None,
+                                              out.data_ptr(), status.data_ptr(), workspace, self._stream())
+
+        if need == 0:  # arguments the library refuses: its own words (nothing is launched)
+            check(call(None))
+            raise RfxError(f"rfx_png_decode_u8 took {N} {H} x {W} images of colour type {color_type} it reports no workspace for")
+        with self._workspace(need) as ws:
+            check(call(ws.data_ptr()))
             status_np = status.cpu().numpy()
         return out, status_np
 

@@ -37,6 +37,31 @@ def _load_segment(path: str) -> T.Any:
     return audio_util.PcmSegment.from_wav(path)
 
 
+def _params_from_exif(exif: T.Any) -> SpectrogramParams:
+    try:
+        return SpectrogramParams.from_exif(exif=exif)
+    except (KeyError, AttributeError):
+        print("WARNING: Could not find spectrogram parameters in exif data. Using defaults.")
+        return SpectrogramParams()
+
+
+def _png_params_and_size(data: bytes) -> T.Optional[T.Tuple[SpectrogramParams, T.Tuple[int, int]]]:
+    """(params from the eXIf chunk, (width, height)) of a PNG file's bytes, from its chunks alone (image_util.png_parse); None
+    where the file is not one the device reads: the caller opens it as an image."""
+    info = image_util.png_parse(data)
+    if not info.ok_for_device:
+        return None
+    exif = Image.Exif()
+    if info.exif:
+        exif.load(info.exif)
+    return _params_from_exif(exif), (info.width, info.height)
+
+
+def _check_png_reader(png_reader: str) -> None:
+    if png_reader not in _CHOICES["png_reader"]:
+        raise ValueError(f"--png-reader must be one of {_CHOICES['png_reader']}, got {png_reader}")
+
+
 def _params_from_image(image: Image.Image) -> SpectrogramParams:
     """EXIF -> params, defaults when the image carries none (reference cli.py:77-87)."""
     try:
@@ -108,7 +133,7 @@ def _check_image_to_audio(*, guide_audio: str, hold_head_ms: int, hold_tail_ms: 
 def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel: str = "sgd", frame_engine: str = "auto",
                    guide_audio: str = "", griffin_lim_iters: int = -1, hold_head_ms: int = 0, hold_tail_ms: int = 0,
                    hold_mask: str = "", hold_keep_threshold: float = 0.5, loop: bool = False, phase_start: str = "random",
-                   print_error: bool = False) -> None:
+                   print_error: bool = False, png_reader: str = "pillow") -> None:
     """Decode one spectrogram image; --inverse-mel lstsq takes the closed-form InverseMelScale (torchaudio >= 2.1's) instead of the SGD,
     --frame-engine chirp-z runs parameters whose FFT length has a prime factor above 13 (refused otherwise).
     --guide-audio FILE starts Griffin-Lim from the phase of that clip (audio-to-audio: the clip the tile was made of; it must be at
@@ -123,12 +148,25 @@ def image_to_audio(*, image: str, audio: str, device: str = "cuda", inverse_mel:
     --phase-start peaks starts Griffin-Lim from phases built from the tile's own magnitudes (spectral peaks, their frequencies
     integrated over the hop) instead of random ones: for a tile without a guide and few --griffin-lim-iters.  Not with --guide-audio.
     --print-error, with --loop: prints the decode's circular spectral convergence, || |STFT(x)| - S || / || S || of the clip Griffin-Lim
-    made against the magnitudes it was given, the STFT being the circular one of a loop encode, measured on the device."""
+    made against the magnitudes it was given, the STFT being the circular one of a loop encode, measured on the device.
+    --png-reader device inflates and unfilters a PNG tile on the GPU (the same pixels and EXIF; only the file's bytes are uploaded);
+    a file the device does not read (16-bit, interlaced, not a PNG, a damaged stream) is opened by Pillow as with the default."""
+    _check_png_reader(png_reader)
     _check_image_to_audio(guide_audio=guide_audio, hold_head_ms=hold_head_ms, hold_tail_ms=hold_tail_ms, hold_mask=hold_mask, loop=loop,
                           phase_start=phase_start, print_error=print_error)
-    pil_image = Image.open(image)
-    params = _params_from_image(pil_image)
-    converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
+    parsed = None
+    if png_reader == "device":
+        with open(image, "rb") as f:
+            data = f.read()
+        parsed = _png_params_and_size(data)
+    if parsed is not None:
+        params = parsed[0]
+        converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
+        pil_image = converter.images_from_png_bytes([data], return_device=True)[0][0]  # the (H, W, 3) tile on the device
+    else:
+        pil_image = Image.open(image)
+        params = _params_from_image(pil_image)
+        converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
     segment = converter.audio_from_spectrogram_image(pil_image, apply_filters=True, inverse_mel=inverse_mel,
                                                      guide_segment=_load_segment(guide_audio) if guide_audio else None,
                                                      griffin_lim_iters=griffin_lim_iters if griffin_lim_iters >= 0 else None,
@@ -170,11 +208,17 @@ def _rank_device(device: str) -> str:
     return device
 
 
-def _tile_groups(paths: T.Sequence[str], image_extension: str) -> T.Dict[T.Tuple[SpectrogramParams, T.Tuple[int, int]], T.List[str]]:
+def _tile_groups(paths: T.Sequence[str], image_extension: str, png_reader: str = "pillow") -> T.Dict[T.Tuple[SpectrogramParams, T.Tuple[int, int]], T.List[str]]:
     """Image files by (params from their EXIF, (width, height)): the tiles of one GPU call share both.  A jpg's size and EXIF come
     from the bytes before its scan (image_util.jpeg_parse), without opening it as an image; a file that does not parse is opened."""
     groups: T.Dict[T.Tuple[SpectrogramParams, T.Tuple[int, int]], T.List[str]] = {}
     for path in paths:
+        if image_extension == "png" and png_reader == "device":  # (the same from the chunks, without opening the file as an image)
+            with open(path, "rb") as f:
+                parsed = _png_params_and_size(f.read())
+            if parsed is not None:
+                groups.setdefault(parsed, []).append(path)
+                continue
         if image_extension != "png":
             with open(path, "rb") as f:
                 info = image_util.jpeg_parse(f.read())
@@ -194,11 +238,18 @@ def _tile_groups(paths: T.Sequence[str], image_extension: str) -> T.Dict[T.Tuple
     return groups
 
 
-def _load_tiles(converter: SpectrogramImageConverter, chunk: T.Sequence[str], image_extension: str) -> T.Any:
+def _load_tiles(converter: SpectrogramImageConverter, chunk: T.Sequence[str], image_extension: str, png_reader: str = "pillow") -> T.Any:
     """The (N, H, W, 3) uint8 tiles of one chunk of same-size files, opened by Pillow one by one and stacked on the host.
     jpg / jpeg files could be decoded on the device instead (`converter.images_from_jpeg_bytes(files, return_device=True)`: the
     same pixels, and only the coded bytes are uploaded); they stay on this route until tools/probe_jpeg_decode.py has written
-    profiles/jpeg_decode.txt and the device route is faster there on both of its sets."""
+    profiles/jpeg_decode.txt and the device route is faster there on both of its sets.  `png_reader="device"` (--png-reader device):
+    the png files' bytes go to `converter.images_from_png_bytes(files, return_device=True)` instead and the tiles stay on the device."""
+    if image_extension == "png" and png_reader == "device":
+        files = []
+        for p in chunk:
+            with open(p, "rb") as f:
+                files.append(f.read())
+        return converter.images_from_png_bytes(files, return_device=True)[0]
     tiles = []
     for p in chunk:
         with Image.open(p) as im:
@@ -208,7 +259,8 @@ def _load_tiles(converter: SpectrogramImageConverter, chunk: T.Sequence[str], im
 
 def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 64, no_filters: bool = False,
                           compression: bool = False, device: str = "cuda", inverse_mel: str = "sgd", image_extension: str = "png",
-                          frame_engine: str = "auto", loop: bool = False, phase_start: str = "random", griffin_lim_iters: int = -1) -> None:
+                          frame_engine: str = "auto", loop: bool = False, phase_start: str = "random", griffin_lim_iters: int = -1,
+                          png_reader: str = "pillow") -> None:
     """Decode every *.png (or, with --image-extension jpg / jpeg, every file of that extension) of a directory, `batch_size`
     same-width tiles per GPU call.  Each clip then gets the same
     post-processing as `image-to-audio` (audio_util.apply_filters, reference spectrogram_image_converter.py:65-91, run on the
@@ -216,7 +268,10 @@ def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 
     compression=True, also on the device); --inverse-mel lstsq takes the closed-form InverseMelScale instead of the SGD;
     --frame-engine chirp-z decodes tiles whose parameters give an FFT length with a prime factor above 13; --loop decodes every
     tile as a loop (see image-to-audio); --phase-start peaks starts Griffin-Lim from the tiles' spectral peaks instead of random
-    phases and --griffin-lim-iters N runs N iterations instead of the params' 32: the start is for decodes with few of them."""
+    phases and --griffin-lim-iters N runs N iterations instead of the params' 32: the start is for decodes with few of them.
+    --png-reader device decodes the png files on the GPU (inflate, unfilter, to RGB: the same pixels, only the files' bytes are
+    uploaded); files the device does not read are opened by Pillow as with the default, pillow."""
+    _check_png_reader(png_reader)
     if griffin_lim_iters < -1:
         raise ValueError("--griffin-lim-iters must be >= 0")
     if compression and no_filters:
@@ -226,12 +281,12 @@ def images_to_audio_batch(*, image_dir: str, output_dir: str, batch_size: int = 
     os.makedirs(output_dir, exist_ok=True)
     device = _rank_device(device)
     paths = _rank_slice(sorted(glob.glob(os.path.join(image_dir, "*." + image_extension))))
-    for (params, _size), members in _tile_groups(paths, image_extension).items():
+    for (params, _size), members in _tile_groups(paths, image_extension, png_reader).items():
         converter = SpectrogramImageConverter(params=params, device=device, frame_engine=frame_engine)
         for i in range(0, len(members), batch_size):
             chunk = members[i : i + batch_size]
             # the filters run on the device, clip by clip, before the batch leaves it (same bytes as audio_util.apply_filters)
-            pcm = converter.audio_from_spectrogram_images(_load_tiles(converter, chunk, image_extension), apply_filters=not no_filters,
+            pcm = converter.audio_from_spectrogram_images(_load_tiles(converter, chunk, image_extension, png_reader), apply_filters=not no_filters,
                                                           compression=compression, inverse_mel=inverse_mel, loop=loop, phase_start=phase_start,
                                                           griffin_lim_iters=griffin_lim_iters if griffin_lim_iters >= 0 else None)
             for path, samples in zip(chunk, pcm):
@@ -358,7 +413,7 @@ _COMMANDS: T.Dict[str, T.Callable[..., None]] = {
 
 
 _CHOICES = {"inverse_mel": ("sgd", "lstsq"), "frame_engine": ("auto", "chirp-z"), "phase_start": ("random", "peaks"),
-            "png_writer": ("pillow", "device"), "png_mode": ("rgb", "gray", "auto")}  # arguments that take one of a few words
+            "png_writer": ("pillow", "device"), "png_mode": ("rgb", "gray", "auto"), "png_reader": ("pillow", "device")}  # arguments that take one of a few words
 
 
 def build_parser() -> argparse.ArgumentParser:

@@ -100,8 +100,10 @@ class SpectrogramImageConverter:
             if guide_segment.channels > C:
                 guide_segment = guide_segment.set_channels(C)
             guides = np.array([c.get_array_of_samples() for c in guide_segment.split_to_mono()]).astype(np.float32)[None]
+        # (a PIL image, or its (H, W, 3) uint8 tile as an array or a device tensor: what `images_from_png_bytes` returns)
+        tile = np.asarray(image_util.rgb_array_from_image(image)) if isinstance(image, Image.Image) else image
         pcm = self.audio_from_spectrogram_images(
-            np.asarray(image_util.rgb_array_from_image(image))[None], max_value=max_value, apply_filters=apply_filters,
+            tile[None], max_value=max_value, apply_filters=apply_filters,
             inverse_mel=inverse_mel, guide_waveforms=guides, griffin_lim_iters=griffin_lim_iters, hold_frames=hold_frames,
             hold_mask=hold_mask, loop=loop, phase_start=phase_start, return_loop_error=return_loop_error,
         )
@@ -427,6 +429,59 @@ class SpectrogramImageConverter:
                 idx = members[lo:lo + tiles_per_call]
                 rgb, status = plan.jpeg_decode([files[i][infos[i].scan[0]:infos[i].scan[1]] for i in idx], H, W,
                                                np.stack([infos[i].qtables for i in idx]), np.stack([infos[i].huffman for i in idx]))
+                if len(idx) == len(files) and not status.any():
+                    whole = rgb
+                batch = rgb if return_device else rgb.cpu().numpy()
+                for j, i in enumerate(idx):
+                    if status[j] == 0:
+                        tiles[i] = batch[j]
+                        exifs[i] = Image.Exif()
+                        if infos[i].exif:
+                            exifs[i].load(infos[i].exif)
+        for i, data in enumerate(files):
+            if tiles[i] is None:  # the host route
+                with Image.open(io.BytesIO(data)) as im:
+                    arr = image_util.rgb_array_from_image(im)
+                    exifs[i] = im.getexif()
+                tiles[i] = torch.from_numpy(arr).to(plan.device) if return_device else arr
+        if whole is not None:
+            return (whole if return_device else whole.cpu().numpy()), exifs
+        if len(files) and len({tuple(t.shape) for t in tiles}) == 1:
+            return (torch.stack(tiles) if return_device else np.stack(tiles)), exifs
+        return tiles, exifs
+
+    def images_from_png_bytes(self, files: T.Sequence[bytes], return_device: bool = False, tiles_per_call: int = 64) -> T.Tuple[T.Any, T.List[Image.Exif]]:
+        """
+        N image files as `bytes` -> (their (H, W, 3) uint8 tiles, their EXIF as `Image.Exif`): `images_from_jpeg_bytes` for PNG.
+        An 8-bit PNG of colour type 0, 2, 3 or 6 that is not interlaced (`image_util.png_parse(...).ok_for_device`: what Pillow's
+        `save` and `png_bytes_from_images` write) is inflated, unfiltered and converted on the device, `tiles_per_call` files of one
+        size and colour type at a time, to the pixels Pillow's `convert("RGB")` gives; only the IDAT bytes are uploaded.  Every other
+        file - 16-bit, interlaced, grey with alpha, APNG, a CRC mismatch, not a PNG - and every file whose stream the device reports
+        a status for is opened by Pillow on the host (`image_util.rgb_array_from_image`), with Pillow's own exceptions for files it
+        cannot read.  The tiles come back as one (N, H, W, 3) batch when all files have one size, else as a list of N; numpy
+        arrays, or tensors on the device with `return_device=True`.
+        """
+        import io
+
+        if tiles_per_call < 1:
+            raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        files = [bytes(f) for f in files]
+        plan = self.converter._plan()
+        infos = [image_util.png_parse(f) for f in files]
+        tiles: T.List[T.Any] = [None] * len(files)
+        exifs: T.List[T.Any] = [None] * len(files)
+        groups: T.Dict[T.Tuple[int, int, int], T.List[int]] = {}
+        for i, info in enumerate(infos):
+            if info.ok_for_device:
+                groups.setdefault((info.height, info.width, info.color_type), []).append(i)
+        whole = None  # the one device batch that is the whole result, if there is one
+        for (H, W, color_type), members in groups.items():
+            for lo in range(0, len(members), tiles_per_call):
+                idx = members[lo:lo + tiles_per_call]
+                streams = [b"".join(files[i][a:b] for a, b in infos[i].idat) for i in idx]
+                palettes = np.stack([infos[i].palette for i in idx]) if color_type == 3 else None
+                entries = np.array([infos[i].palette_entries for i in idx], dtype=np.int32) if color_type == 3 else None
+                rgb, status = plan.png_decode(streams, H, W, color_type, palettes, entries)
                 if len(idx) == len(files) and not status.any():
                     whole = rgb
                 batch = rgb if return_device else rgb.cpu().numpy()

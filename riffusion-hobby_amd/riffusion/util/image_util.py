@@ -389,3 +389,112 @@ def jpeg_parse(data: bytes) -> JpegInfo:
         what = "restart markers" if 0xD0 <= found.group()[1] <= 0xD7 else "a marker other than EOI after the first scan"
         return result(what, scan=(start, end))
     return result("", np.stack([qt[frame[0][2]], qt[frame[1][2]]]), np.stack([ht[s] for s in selectors]), (start, end))
+
+
+# ---- PNG: what a decoder needs of a file around its IDAT payloads (the device inflates and unfilters them: rfx_png_decode_u8) ----
+class PngInfo(T.NamedTuple):
+    """`png_parse`'s result.  `channels`: bytes per pixel of the filtered rows (1, 3, 1, 4 for colour types 0, 2, 3, 6; 0 for any
+    other); `palette`: (256, 3) uint8, the PLTE's entries and zeros behind them; `idat`: the byte ranges of the IDAT payloads in
+    file order (their concatenation is the zlib stream); `exif`: the eXIf payload (b"" when the file has none)."""
+    width: int
+    height: int
+    color_type: int
+    channels: int
+    palette: np.ndarray
+    palette_entries: int
+    idat: T.Tuple[T.Tuple[int, int], ...]
+    exif: bytes
+    ok_for_device: bool
+    reason: str
+
+
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 6: 4}
+_PNG_EXIF_TEXT_KEY = b"Raw profile type exif"
+
+
+def png_parse(data: bytes) -> PngInfo:
+    """
+    Walks the chunks of a PNG file.  `ok_for_device` says whether rfx_png_decode_u8 takes the file - IHDR first with bit depth 8,
+    colour type 0, 2, 3 or 6, no interlace; every chunk's CRC-32 right; the IDAT chunks consecutive; PLTE before IDAT for colour
+    type 3; IEND present - and `reason` why not: other depths, grey with alpha, Adam7, APNG chunks, an unknown critical chunk, an
+    EXIF kept in a text chunk (Pillow's `getexif` reads it, this parser does not), a CRC mismatch, a truncated file, not a PNG.
+    tRNS, gAMA, sRGB, iCCP, pHYs and other text chunks do not change what `convert("RGB")` returns and are skipped.  Never raises
+    for `bytes`.
+    """
+    data = bytes(data)
+    width = height = color_type = 0
+    palette = np.zeros((256, 3), dtype=np.uint8)
+    entries = 0
+    idat: T.List[T.Tuple[int, int]] = []
+    exif = b""
+
+    def result(reason: str) -> PngInfo:
+        return PngInfo(width, height, color_type, _PNG_CHANNELS.get(color_type, 0), palette, entries, tuple(idat), exif, not reason, reason)
+
+    if data[:8] != PNG_SIGNATURE:
+        return result("not a PNG: no signature")
+    problems: T.List[str] = []  # what keeps the file on the host, in file order
+    at, n = 8, len(data)
+    first, seen_idat, idat_closed, seen_plte, seen_iend, exif_text = True, False, False, False, False, False
+    while not seen_iend:
+        if at + 12 > n:
+            return result("truncated: the file ends before IEND")
+        length = struct.unpack(">I", data[at:at + 4])[0]
+        kind = data[at + 4:at + 8]
+        if length >= 1 << 31 or at + 12 + length > n:
+            return result(f"truncated: the file ends inside a {kind!r} chunk")
+        payload = data[at + 8:at + 8 + length]
+        if zlib.crc32(data[at + 4:at + 8 + length]) != struct.unpack(">I", data[at + 8 + length:at + 12 + length])[0]:
+            problems.append(f"CRC mismatch in a {kind!r} chunk")
+        if first:
+            if kind != b"IHDR" or length != 13:
+                return result("malformed: IHDR is not the first chunk")
+            width, height, depth, color_type, compression, filter_method, interlace = struct.unpack(">IIBBBBB", payload)
+            if depth != 8:
+                problems.append(f"bit depth {depth}")
+            if color_type == 4:
+                problems.append("colour type 4 (grey with alpha)")
+            elif color_type not in _PNG_CHANNELS:
+                problems.append(f"colour type {color_type}")
+            if compression != 0 or filter_method != 0:
+                problems.append("an unknown compression or filter method")
+            if interlace != 0:
+                problems.append("Adam7 interlace")
+            if not (1 <= width <= PNG_MAX_SIZE and 1 <= height <= PNG_MAX_SIZE):
+                problems.append(f"{width} x {height} pixels")
+            first = False
+        elif kind == b"IHDR":
+            problems.append("a second IHDR")
+        elif kind == b"IDAT":
+            if idat_closed:
+                problems.append("IDAT chunks that are not consecutive")
+            if color_type == 3 and not seen_plte:
+                problems.append("colour type 3 without PLTE before IDAT")
+            seen_idat = True
+            idat.append((at + 8, at + 8 + length))
+        elif kind == b"PLTE":
+            if seen_idat or seen_plte or length % 3 or length > 768 or length == 0:
+                problems.append("a PLTE chunk out of place or of a wrong length")
+            else:
+                entries = length // 3
+                palette[:entries] = np.frombuffer(payload, dtype=np.uint8).reshape(entries, 3)
+            seen_plte = True
+        elif kind == b"IEND":
+            seen_iend = True
+        elif kind in (b"acTL", b"fcTL", b"fdAT"):
+            problems.append("APNG chunks")
+        elif kind == b"eXIf":
+            exif = payload
+        elif kind in (b"tEXt", b"zTXt", b"iTXt"):
+            if payload.split(b"\x00", 1)[0] == _PNG_EXIF_TEXT_KEY:
+                exif_text = True
+        elif not kind[0] & 0x20:
+            problems.append(f"an unknown critical chunk {kind!r}")
+        if seen_idat and kind != b"IDAT":
+            idat_closed = True
+        at += 12 + length
+    if not idat:
+        problems.append("no IDAT chunk")
+    if exif_text and not exif:
+        problems.append("EXIF in a text chunk (Raw profile type exif)")
+    return result(problems[0] if problems else "")
