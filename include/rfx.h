@@ -657,6 +657,57 @@ size_t rfx_mel_scale_workspace_bytes(const rfx_plan* plan, int B, int T);
 int rfx_mel_scale(const rfx_plan* plan, const float* d_lin_bft, int B, int T, float* d_mel_out, void* d_workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ---- BACKWARD of the forward path: the gradients torch.autograd gives through Spectrogram(power=None), torch.abs and MelScale ------
+ * With h = n_fft / 2, left = (n_fft - win_length) / 2, w the window zero-padded to n_fft, a row x of Lw > h samples,
+ * T = rfx_stft_frames of Lw, X the row's complex STFT as rfx_stft computes it, and g_mel (n_mels, T) the incoming gradient:
+ *   1  bank adjoint       gS[k][t] = sum_m fb[k][m] g_mel[m][t], over the bands from the first to the last non-zero weight of bin k
+ *                         (the per-bin table of rfx_debug_mel_adjoint), in increasing m
+ *   2  magnitude adjoint  G[k][t] = gS[k][t] X[k][t] / |X[k][t]|, exactly 0 where |X| == 0 (torch's abs backward: a silent row has a
+ *                         zero, finite gradient).  For rfx_stft_backward G is the caller's complex gradient, dL/dRe + i dL/dIm.
+ *   3  frame adjoint      f_t[i] = sum_k Re G[k][t] cos(2 pi k i / n_fft) - Im G[k][t] sin(2 pi k i / n_fft): every one-sided bin
+ *                         with weight 1 (n_fft irfft of G with the interior bins halved); the imaginary parts of bin 0 and of the
+ *                         Nyquist bin of an even n_fft drop out.  Odd n_fft included.
+ *   4  adjoint fold       gp[q] = sum_t w[q - hop t] f_t[q - hop t] as ONE chain from the oldest covering frame on; sample j of the
+ *                         result is gp[h + j], plus gp[h - j] when 1 <= j <= h, plus gp[h + 2 (Lw - 1) - j] when
+ *                         Lw - 1 - h <= j <= Lw - 2 (the reflect padding folded back), added in that order.  No envelope division,
+ *                         no trimming, no atomics.
+ * On the device, per group of rows: [the fused call: rfx_stft of the rows, spectrum into the workspace;] one kernel writes the
+ * magnitude slots S' = weight[k] gS[k] / |X[k]| in the layout the plan's Griffin-Lim frame launch reads (slot order with its doubled
+ * 440 bins on the specialised engine, position = bin on the generic and chirp-z engines, the row family's own order) - for
+ * rfx_stft_backward the one-sided weights alone; the engine's existing first Griffin-Lim launch (MODE 0, per-frame form) synthesises
+ * S' times the spectrum itself (or the caller's gradient) frame by frame; the fold kernel gathers step 4 per output sample.  All
+ * four frame engines.  Range: S' = gS / |X| must be representable, i.e. |g| / |X| below 3e38 (|X| == 0 is served exactly).
+ * Contract of the three entries: B == 0 is a no-op.  Refusals - Lw <= n_fft / 2, a NULL pointer, a workspace or complex gradient
+ * that is not 16-byte aligned, a float tensor that is not 4-byte aligned, a workspace below the query - come before any launch and
+ * leave the output untouched.  Row and element offsets are 64-bit.  Deterministic, and a row's bytes depend on that row alone: every
+ * kernel works frame by frame or sample by sample, whatever B is and wherever the row's group falls.  BOUNDED WORKSPACE: the rows
+ * are walked in groups of max(1, 256 MiB / row bytes) whole rows, row bytes = T * (frame_stride * 8 [fused call only] + slot stride * 4 +
+ * frame pitch * 4) - 67 MB for a 512-frame row at the default geometry - so a query answers at most 256 MiB + 768 bytes, or one
+ * row's bytes when a row alone is larger; it answers 0 where the call would be refused.  The loop forms have no backward.
+ *
+ * rfx_stft_backward: steps 3 and 4.  d_grad_spec_slots: the complex gradient in slot layout - what rfx_pack_complex writes,
+ * conjugate slots conjugated, both slots of a doubled bin filled - B * T frames; d_grad_wave (B, Lw) float32.
+ * rfx_mel_scale_backward: step 1 alone, d_grad_mel (B, n_mels, T) -> d_grad_lin_bft in the reference's (B, n_stft, T) layout.  Its
+ * workspace query answers 0 and d_workspace may be NULL.
+ * rfx_mel_from_waveform_backward: the fused call, steps 1 to 4.  It re-analyses d_wave (B, Lw) - the caller saves the waveform only:
+ * at 64 stereo tiles a kept spectrum would be 2.3 GB - and never writes the (B, n_stft, T) tensor. */
+size_t rfx_stft_backward_workspace_bytes(const rfx_plan* plan, int B, int Lw);
+int rfx_stft_backward(const rfx_plan* plan, const void* d_grad_spec_slots, int B, int Lw, float* d_grad_wave, void* d_workspace,
+                      size_t workspace_bytes, void* stream);
+size_t rfx_mel_scale_backward_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_mel_scale_backward(const rfx_plan* plan, const float* d_grad_mel, int B, int T, float* d_grad_lin_bft, void* d_workspace,
+                           size_t workspace_bytes, void* stream);
+size_t rfx_mel_from_waveform_backward_workspace_bytes(const rfx_plan* plan, int B, int Lw);
+int rfx_mel_from_waveform_backward(const rfx_plan* plan, const float* d_wave, const float* d_grad_mel, int B, int Lw,
+                                   float* d_grad_wave, void* d_workspace, size_t workspace_bytes, void* stream);
+/* the per-bin adjoint table plan creation builds from a dense filterbank h_melfb [n_stft][n_mels] and uploads with the plan, without
+ * a GPU (tests): for bin k the first band with a non-zero weight h_first[k], the number of bands up to the last non-zero one
+ * h_count[k] (0: no band reaches the bin; 2 for a triangular bank, but taken from the bank) and their weights
+ * h_weights[k * capacity + i], zero past the count.  *width_out receives the largest count (at least 1); the three tables are
+ * nullable (a first call learns the width); a capacity below the width is refused. */
+int rfx_debug_mel_adjoint(const rfx_params* params, const float* h_melfb, int32_t* h_first, int32_t* h_count, float* h_weights,
+                          int capacity, int32_t* width_out);
+
 /* ---- inverse: torchaudio.transforms.InverseMelScale (SGD, max_iter = params.max_mel_iters,
  * tolerance_loss 1e-5, tolerance_change 1e-8, lr 0.1, momentum 0.9), spectrogram_converter.py:87-99,
  * called at :201.  d_mel (B, n_mels, T); the B rows are grouped into clips of `channels_per_clip`

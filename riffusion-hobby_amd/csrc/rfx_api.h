@@ -121,6 +121,16 @@ struct rfx_plan {
   rfx::cf* d_fam_tw = nullptr;      // [21][h] g(n')^k1, then [rb][ra-1] W_h^{i p}
   int* d_fam_binof = nullptr;  // [fsf] bin held by each position of the slot-ordered magnitudes (-1: padding)
   int fam_wgs_per_cu = 1;
+  // backward of the forward path (rfx_mel_bwd.hip): the position tables of the magnitude slots the plan's MODE 0 frame launch reads
+  // and of the spectrum its forward transform writes, and - with a filterbank - the per-bin adjoint table (rfx_mel_bwd_core.h)
+  int* d_mb_pos_bin = nullptr;   // [mb_sstride]
+  int* d_mb_xpos_bin = nullptr;  // [frame_stride]
+  int* d_mb_s2x = nullptr;       // [mb_sstride] position of the spectrum each magnitude slot goes with
+  int mb_sstride = 0;
+  int* d_mb_first = nullptr;     // [n_stft]
+  int* d_mb_count = nullptr;     // [n_stft]
+  float* d_mb_wt = nullptr;      // [n_stft][mb_width]
+  int mb_width = 0;
 };
 
 namespace rfx {

@@ -1,0 +1,189 @@
+// rfx_api_backward.hip - the C ABI of librfx.so (include/rfx.h), backward of the forward path: rfx_stft_backward,
+// rfx_mel_scale_backward and rfx_mel_from_waveform_backward.  Host code only: one layout, one driver.  Per group of rows the driver
+// queues
+//     [rfx_stft of the rows, spectrum into the workspace]          rfx_mel_from_waveform_backward only
+//     mel_bwd_spec_kernel   the magnitude slots S' (rfx_mel_bwd.hip)
+//     the engine's MODE 0 per-frame launch on (S', angles)          launch_gl_frame / launch_fam_gl / launch_gen_gl / launch_czt_gl
+//     mel_bwd_fold_kernel   the adjoint fold into the caller's rows
+// The rows are walked in groups of whole rows (as rfx_spectral_error walks them), so the workspace is bounded whatever B is, and
+// every kernel of the sequence works frame by frame or sample by sample: a row's bytes depend on that row alone.
+#include "rfx_api.h"
+#include "rfx_mel_bwd_core.h"
+
+using namespace rfx;
+
+constexpr size_t kMelBwdGroupBytes = (size_t)256 << 20;
+
+// The spectrum of the group's rows (the fused call only), their magnitude slots, their synthesis frames
+struct MelBwdLayout {
+  size_t spec, smag, frames, total;
+  int group_rows, T;
+};
+static size_t mel_bwd_frame_pitch(const rfx_plan* plan) { return plan->generic ? (size_t)plan->gg.fpitch : gl_frame_buffer_bytes(1, 1) / sizeof(float); }
+static MelBwdLayout mel_bwd_layout(const rfx_plan* plan, int B, int Lw, bool with_spec) {
+  MelBwdLayout l{};
+  if (B <= 0 || Lw <= plan->p.n_fft / 2) return l;
+  l.T = stft_frames(plan, Lw);
+  const size_t T = (size_t)l.T;
+  const size_t spec_row = with_spec ? T * plan->frame_stride * sizeof(cf) : 0, smag_row = T * plan->mb_sstride * sizeof(float),
+               frames_row = T * mel_bwd_frame_pitch(plan) * sizeof(float);
+  size_t rows = kMelBwdGroupBytes / (spec_row + smag_row + frames_row);
+  rows = rows < 1 ? 1 : rows > (size_t)B ? (size_t)B : rows;
+  l.group_rows = (int)rows;
+  Carve c;
+  l.spec = c.take(rows * spec_row);
+  l.smag = c.take(rows * smag_row);
+  l.frames = c.take(rows * frames_row);
+  l.total = c.at;
+  return l;
+}
+size_t rfx_stft_backward_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? mel_bwd_layout(plan, B, Lw, false).total : 0; }
+size_t rfx_mel_from_waveform_backward_workspace_bytes(const rfx_plan* plan, int B, int Lw) {
+  return plan && plan->d_mb_wt ? mel_bwd_layout(plan, B, Lw, true).total : 0;
+}
+size_t rfx_mel_scale_backward_workspace_bytes(const rfx_plan* plan, int B, int T) {
+  (void)plan, (void)B, (void)T;
+  return 0;  // step 1 alone needs no scratch
+}
+
+// the engine's MODE 0 per-frame launch: frames = synthesis of S * angles0, `rows` rows of T frames
+static int mel_bwd_frames(const rfx_plan* plan, const float* S, const cf* angles0, float* frames, int rows, int T, hipStream_t stream) {
+  if (!plan->generic) {
+    GlFrameArgs fa{};
+    fa.S = S;
+    fa.angles0 = angles0;
+    fa.frames = frames;
+    fa.tw1 = plan->d_tw1;
+    fa.tw2 = plan->d_tw2;
+    fa.win = plan->d_win;
+    fa.B = rows;
+    fa.T = T;
+    RFX_HIP(launch_gl_frame(0, fa, frame_blocks((long long)plan->num_cus * plan->gl_wgs_per_cu, rows, T), stream));
+    return RFX_OK;
+  }
+  const GenGeom& g = plan->gg;
+  // padded frame rows (gen_frame_layout): the kernels write the window samples only, the fold reads the padding as zeros
+  if (g.fshift > 0) RFX_HIP(hipMemsetAsync(frames, 0, (size_t)rows * T * g.fpitch * sizeof(float), stream));
+  if (plan->fam_ok) {
+    const FamGeom& f = plan->fam;
+    FamGlArgs fa{};
+    fa.g = f;
+    fa.S = S;
+    fa.angles0 = angles0;
+    fa.fs_plain = g.fs;
+    fa.frames = frames;
+    fa.fpitch = g.fpitch;
+    fa.fshift = g.fshift;
+    fa.tw1 = plan->d_fam_tw;
+    fa.twa = plan->d_fam_tw + (size_t)f.rows * f.h;
+    fa.win = plan->d_win;
+    fa.B = rows;
+    fa.T = T;
+    RFX_HIP(launch_fam_gl(0, fa, frame_blocks(fam_slot_count(plan), rows, T), stream));
+    return RFX_OK;
+  }
+  GenGlArgs ga{};
+  ga.g = g;
+  ga.tb = plan->gt;
+  ga.S = S;
+  ga.angles0 = angles0;
+  ga.frames = frames;
+  ga.B = rows;
+  ga.T = T;
+  RFX_HIP(plan->czt ? launch_czt_gl(0, ga, plan->d_czt_c, plan->d_czt_h, plan->num_cus, stream) : launch_gen_gl(0, ga, plan->num_cus, stream));
+  return RFX_OK;
+}
+
+// d_wave and d_grad_mel (the fused call) or d_grad_spec_slots (rfx_stft_backward)
+static int mel_bwd_run(const char* who, const rfx_plan* plan, const float* d_wave, const float* d_grad_mel, const void* d_grad_spec_slots, int B, int Lw,
+                       float* d_grad_wave, void* d_workspace, size_t workspace_bytes, void* stream_) {
+  const std::string w = who;
+  const bool fused = d_grad_spec_slots == nullptr;
+  if (B < 0) return fail(RFX_ERR_INVALID, w + ": B is negative");
+  if (B == 0) return RFX_OK;
+  if (!plan || !d_grad_wave || !d_workspace || (fused ? (!d_wave || !d_grad_mel) : false)) return fail(RFX_ERR_INVALID, w + ": null argument");
+  if (fused && !plan->d_mb_wt) return fail(RFX_ERR_INVALID, w + ": plan was created without a mel filterbank");
+  if (Lw <= plan->p.n_fft / 2)
+    return fail(RFX_ERR_INVALID, w + ": reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
+  if (((uintptr_t)d_workspace | (uintptr_t)d_grad_spec_slots) & 15 || ((uintptr_t)d_grad_wave | (uintptr_t)d_wave | (uintptr_t)d_grad_mel) & 3)
+    return fail(RFX_ERR_INVALID, w + ": d_workspace and d_grad_spec_slots must be 16-byte aligned, the float tensors 4-byte aligned");
+  if ((plan->mb_sstride & 3) || (plan->frame_stride & 1)) return fail(RFX_ERR_UNSUPPORTED, w + ": the plan's frame strides are not multiples of four");
+  const MelBwdLayout l = mel_bwd_layout(plan, B, Lw, fused);
+  if (workspace_bytes < l.total)
+    return fail(RFX_ERR_WORKSPACE, w + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(l.total) + " needed)");
+  RFX_ON_DEVICE(plan->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const int T = l.T, M = plan->p.n_mels;
+  cf* spec = reinterpret_cast<cf*>((char*)d_workspace + l.spec);
+  float* smag = reinterpret_cast<float*>((char*)d_workspace + l.smag);
+  float* frames = reinterpret_cast<float*>((char*)d_workspace + l.frames);
+  const size_t row_slots = (size_t)T * plan->frame_stride;
+  for (int r0 = 0; r0 < B; r0 += l.group_rows) {
+    const int rows = B - r0 < l.group_rows ? B - r0 : l.group_rows;
+    const cf* angles = fused ? spec : reinterpret_cast<const cf*>(d_grad_spec_slots) + (size_t)r0 * row_slots;
+    if (fused)
+      if (int rc = rfx_stft(plan, d_wave + (size_t)r0 * Lw, rows, Lw, nullptr, spec, stream_)) return rc;
+    MelBwdSpecArgs a{};
+    a.g_mel = fused ? d_grad_mel + (size_t)r0 * M * T : nullptr;
+    a.X = fused ? spec : nullptr;
+    a.S = smag;
+    a.pos_bin = plan->d_mb_pos_bin;
+    a.xpos_bin = plan->d_mb_xpos_bin;
+    a.s2x = plan->d_mb_s2x;
+    a.first = plan->d_mb_first;
+    a.count = plan->d_mb_count;
+    a.wt = plan->d_mb_wt;
+    a.width = plan->mb_width;
+    a.B = rows;
+    a.T = T;
+    a.M = fused ? M : 0;
+    a.n_stft = plan->n_stft;
+    a.n_fft = plan->p.n_fft;
+    a.xstride = plan->frame_stride;
+    a.sstride = plan->mb_sstride;
+    a.unit = mel_bwd_unit(plan->p.n_fft, !plan->generic);
+    RFX_HIP(launch_mel_bwd_spec(a, stream));
+    if (int rc = mel_bwd_frames(plan, smag, angles, frames, rows, T, stream)) return rc;
+    MelBwdFoldArgs f{};
+    f.frames = frames;
+    f.win = plan->generic ? nullptr : plan->d_win;
+    f.out = d_grad_wave + (size_t)r0 * Lw;
+    f.fpitch = (int)mel_bwd_frame_pitch(plan);
+    f.fshift = plan->generic ? plan->gg.fshift : 0;
+    f.left = (plan->p.n_fft - plan->p.win_length) / 2;
+    f.win_len = plan->p.win_length;
+    f.hop = plan->p.hop_length;
+    f.h = plan->p.n_fft / 2;
+    f.B = rows;
+    f.T = T;
+    f.Lw = Lw;
+    RFX_HIP(launch_mel_bwd_fold(f, stream));
+  }
+  return RFX_OK;
+}
+
+int rfx_stft_backward(const rfx_plan* plan, const void* d_grad_spec_slots, int B, int Lw, float* d_grad_wave, void* d_workspace,
+                      size_t workspace_bytes, void* stream) {
+  if (B > 0 && !d_grad_spec_slots) return fail(RFX_ERR_INVALID, "rfx_stft_backward: null argument");
+  return mel_bwd_run("rfx_stft_backward", plan, nullptr, nullptr, d_grad_spec_slots, B, Lw, d_grad_wave, d_workspace, workspace_bytes, stream);
+}
+
+int rfx_mel_from_waveform_backward(const rfx_plan* plan, const float* d_wave, const float* d_grad_mel, int B, int Lw, float* d_grad_wave,
+                                   void* d_workspace, size_t workspace_bytes, void* stream) {
+  return mel_bwd_run("rfx_mel_from_waveform_backward", plan, d_wave, d_grad_mel, nullptr, B, Lw, d_grad_wave, d_workspace, workspace_bytes, stream);
+}
+
+int rfx_mel_scale_backward(const rfx_plan* plan, const float* d_grad_mel, int B, int T, float* d_grad_lin_bft, void* d_workspace,
+                           size_t workspace_bytes, void* stream) {
+  (void)d_workspace, (void)workspace_bytes;
+  if (B < 0) return fail(RFX_ERR_INVALID, "rfx_mel_scale_backward: B is negative");
+  if (B == 0) return RFX_OK;
+  if (!plan || !d_grad_mel || !d_grad_lin_bft || T <= 0) return fail(RFX_ERR_INVALID, "rfx_mel_scale_backward: bad argument");
+  if (!plan->d_mb_wt) return fail(RFX_ERR_INVALID, "rfx_mel_scale_backward: plan was created without a mel filterbank");
+  if (((uintptr_t)d_grad_mel | (uintptr_t)d_grad_lin_bft) & 3) return fail(RFX_ERR_INVALID, "rfx_mel_scale_backward: the tensors must be 4-byte aligned");
+  if (plan->n_stft > 65535) return fail(RFX_ERR_UNSUPPORTED, "rfx_mel_scale_backward: more than 65535 linear bins");
+  RFX_ON_DEVICE(plan->device);
+  RFX_HIP(launch_mel_bwd_bank(d_grad_mel, d_grad_lin_bft, plan->d_mb_first, plan->d_mb_count, plan->d_mb_wt, plan->mb_width, B, plan->p.n_mels, T,
+                              plan->n_stft, (hipStream_t)stream));
+  return RFX_OK;
+}

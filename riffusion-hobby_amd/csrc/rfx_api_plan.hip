@@ -191,6 +191,13 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
     RFX_HIP(upload(pl.get(), &pl->d_fam_binof, fam_bin_of(geo.fam)));
     pl->fam_ok = true;
   }
+  {  // the position tables of the backward entries (rfx_mel_bwd.hip)
+    const MelBwdTables mb = mel_bwd_tables(geo);
+    pl->mb_sstride = mb.sstride;
+    RFX_HIP(upload(pl.get(), &pl->d_mb_pos_bin, mb.pos_bin));
+    RFX_HIP(upload(pl.get(), &pl->d_mb_xpos_bin, mb.xpos_bin));
+    RFX_HIP(upload(pl.get(), &pl->d_mb_s2x, mb.s2x));
+  }
   if (h_melfb) {
     const int F = geo.n_stft, M = params->n_mels;
     if (M <= 0) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be positive");
@@ -200,6 +207,10 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
     if (M > 32767) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be below 32768");
     RFX_HIP(upload(pl.get(), &pl->d_melfb, h_melfb, (size_t)F * M));
     RFX_HIP(upload(pl.get(), &pl->d_bin_bands, bin_bands(F, M, h_melfb)));
+    RFX_HIP(upload(pl.get(), &pl->d_mb_first, bank.adj.first));
+    RFX_HIP(upload(pl.get(), &pl->d_mb_count, bank.adj.count));
+    RFX_HIP(upload(pl.get(), &pl->d_mb_wt, bank.adj.wt));
+    pl->mb_width = bank.adj.width;
     if (!geo.generic) {
       RFX_HIP(upload(pl.get(), &pl->d_melfb_slots, bank.fbs));
       RFX_HIP(upload(pl.get(), &pl->d_kblocks, bank.kblocks));
@@ -327,6 +338,24 @@ int rfx_debug_bin_bands(const rfx_params* params, const float* h_melfb, int16_t*
   const std::vector<int16_t> v = bin_bands(geo.n_stft, params->n_mels, h_melfb);
   memcpy(lo, v.data(), (size_t)geo.n_stft * sizeof(int16_t));
   memcpy(hi, v.data() + geo.n_stft, (size_t)geo.n_stft * sizeof(int16_t));
+  return RFX_OK;
+}
+
+int rfx_debug_mel_adjoint(const rfx_params* params, const float* h_melfb, int32_t* h_first, int32_t* h_count, float* h_weights, int capacity,
+                           int32_t* width_out) {
+  if (!params || !h_melfb || !width_out) return fail(RFX_ERR_INVALID, "rfx_debug_mel_adjoint: null argument");
+  if (params->n_mels <= 0 || params->n_fft < 2) return fail(RFX_ERR_INVALID, "rfx_debug_mel_adjoint: n_mels and n_fft must be positive");
+  const int F = params->n_fft / 2 + 1;
+  const MelAdjoint adj = mel_adjoint_table(F, params->n_mels, h_melfb);  // what plan_bank keeps as PlanBank::adj
+  *width_out = adj.width;
+  if (h_first) memcpy(h_first, adj.first.data(), (size_t)F * sizeof(int32_t));
+  if (h_count) memcpy(h_count, adj.count.data(), (size_t)F * sizeof(int32_t));
+  if (h_weights) {
+    if (capacity < adj.width)
+      return fail(RFX_ERR_INVALID, "rfx_debug_mel_adjoint: the table has " + std::to_string(adj.width) + " weights per bin, capacity is " + std::to_string(capacity));
+    for (int k = 0; k < F; ++k)
+      for (int i = 0; i < capacity; ++i) h_weights[(size_t)k * capacity + i] = i < adj.width ? adj.wt[(size_t)k * adj.width + i] : 0.f;
+  }
   return RFX_OK;
 }
 

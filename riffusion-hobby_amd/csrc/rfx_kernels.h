@@ -580,4 +580,37 @@ hipError_t launch_lsq_solve(const LsqTables& tb, const float* mel, float* zy, in
 // y (B, M, T) -> out [B * T][stride] (stride a multiple of four, out 16-byte aligned): max(0, w0 y[m0] + w1 y[m0 + 1]) per position
 hipError_t launch_lsq_expand(const LsqTables& tb, const float* y, float* out, int B, int M, int T, int stride, hipStream_t s);
 
+// backward of the forward path (rfx_mel_bwd.hip, arithmetic in rfx_mel_bwd_core.h).  launch_mel_bwd_spec: the magnitude slots
+// S [B*T][sstride] a MODE 0 frame launch reads - weight[k] gS[k] / |X[k]| with gS from g_mel (B, M, T) through the adjoint table
+// (first / count [n_stft], wt [n_stft][width]) and X [B*T][xstride] the forward transform's spectrum, or, with g_mel and X null, the
+// one-sided weights alone.  pos_bin [sstride] / xpos_bin [xstride]: bin of each position of S / X, -1 for padding.  sstride a
+// multiple of four, xstride even; S and X 16-byte aligned.
+struct MelBwdSpecArgs {
+  const float* g_mel;
+  const cf* X;
+  float* S;
+  const int* pos_bin;
+  const int* xpos_bin;
+  const int* s2x;  // [sstride] position of X whose value magnitude slot p goes with (the frame launch multiplies the two), -1 for padding
+  const int* first;
+  const int* count;
+  const float* wt;
+  int width;
+  int B, T, M, n_stft, n_fft, xstride, sstride;
+  float unit;  // mel_bwd_unit
+};
+hipError_t launch_mel_bwd_spec(const MelBwdSpecArgs& a, hipStream_t stream);
+// step 1 alone: g_mel (B, M, T) -> out (B, n_stft, T)
+hipError_t launch_mel_bwd_bank(const float* g_mel, float* out_bft, const int* first, const int* count, const float* wt, int width, int B, int M,
+                               int T, int n_stft, hipStream_t stream);
+// the adjoint fold: frames [B*T][fpitch], window sample i of a frame at fshift + i -> out (B, Lw).  win: the plan's window where the
+// frames come un-windowed (specialised engine), null where the frame launch has applied it
+struct MelBwdFoldArgs {
+  const float* frames;
+  const float* win;
+  float* out;
+  int fpitch, fshift, left, win_len, hop, h, B, T, Lw;
+};
+hipError_t launch_mel_bwd_fold(const MelBwdFoldArgs& a, hipStream_t stream);
+
 }  // namespace rfx

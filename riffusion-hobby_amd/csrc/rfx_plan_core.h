@@ -13,6 +13,7 @@
 #include "../../include/rfx.h"
 #include "rfx_czt_core.h"
 #include "rfx_kernels.h"
+#include "rfx_mel_bwd_core.h"
 
 namespace rfx {
 
@@ -276,6 +277,8 @@ struct PlanBank {
   std::vector<unsigned> pk;
   unsigned mask = 0;
   int arr = 0;
+  // backward of the forward path: first band, count and weights of every bin (rfx_mel_bwd_core.h; any bank, banded or not)
+  MelAdjoint adj;
 };
 
 // banded tables for InverseMelScale: every bin feeds at most two ADJACENT mel filters and every filter's support is one
@@ -663,7 +666,36 @@ inline PlanBank plan_bank(const PlanGeometry& g, int n_mels, const float* fb, co
   bank_sgd_admission(b, opt.imel_form);
   bank_forward_bands(b, fb);
   bank_forward_products(b, fb, ov.fwd_table_form);
+  b.adj = mel_adjoint_table(b.F, b.M, fb);
   return b;
+}
+
+// ---- backward of the forward path: the position tables of a geometry (no filterbank needed) ----------------------------------------
+struct MelBwdTables {
+  int sstride = 0;                  // floats per frame of the magnitude slots the MODE 0 frame launch reads
+  std::vector<int> pos_bin;         // [sstride]
+  std::vector<int> xpos_bin;        // [frame_stride]: the spectrum the forward transform writes
+  std::vector<int> s2x;             // [sstride]: position of the spectrum the frame launch multiplies magnitude slot p by
+};
+inline MelBwdTables mel_bwd_tables(const PlanGeometry& g) {
+  MelBwdTables t;
+  if (!g.generic) {
+    t.sstride = kFrameStride;
+    t.pos_bin = mel_bwd_pos_bin_spec();
+    t.xpos_bin = mel_bwd_xpos_bin_spec();
+    t.s2x = mel_bwd_s2x_spec();
+    return t;
+  }
+  t.xpos_bin = mel_bwd_pos_bin_plain(g.n_stft, g.frame_stride);
+  if (g.fam_ok) {
+    t.sstride = g.fam.fsf;
+    t.pos_bin = fam_bin_of(g.fam);
+  } else {
+    t.sstride = g.frame_stride;
+    t.pos_bin = t.xpos_bin;
+  }
+  t.s2x = t.pos_bin;  // plain spectrum: position = bin (the row family's launch reads its angles by bin)
+  return t;
 }
 
 }  // namespace rfx

@@ -384,6 +384,14 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_mel_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_mel_from_waveform": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_mel_scale": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # backward of the forward path (riffusion/_autograd.py)
+    "rfx_stft_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_stft_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_mel_scale_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_mel_scale_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_mel_from_waveform_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_mel_from_waveform_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_debug_mel_adjoint": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int32)]),
     "rfx_inverse_mel_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_inverse_mel": (
         c_int,
@@ -1026,6 +1034,45 @@ class Plan:
         out = torch.empty((B, self.n_mels, Tn), dtype=torch.float32, device=lin_bft.device)
         with self._workspace(self.lib.rfx_mel_scale_workspace_bytes(self.handle, B, Tn)) as ws:
             check(self.lib.rfx_mel_scale(self.handle, lin_bft.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    # ---- backward of the forward path (include/rfx.h "BACKWARD of the forward path"; riffusion/_autograd.py) ----
+    def stft_backward(self, grad_spec_slots: torch.Tensor, B: int, Lw: int) -> torch.Tensor:
+        """rfx_stft_backward: the complex gradient of the STFT in slot layout (`pack_complex` of torch's (B, n_stft, T) gradient),
+        B * T frames with T = the frames of rows of Lw samples -> the (B, Lw) float32 gradient of the waveform."""
+        g = self._chk(grad_spec_slots, torch.complex64)
+        Tn = self._forward_frames(Lw, (B, Lw), False)
+        if g.numel() != B * Tn * self.frame_stride:
+            raise ValueError(f"expected {B} * {Tn} frames of {self.frame_stride} complex slots, got {tuple(g.shape)}")
+        out = torch.empty((B, Lw), dtype=torch.float32, device=self.device)
+        with self._workspace(self.lib.rfx_stft_backward_workspace_bytes(self.handle, B, Lw)) as ws:
+            check(self.lib.rfx_stft_backward(self.handle, g.data_ptr(), B, Lw, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    def mel_scale_backward(self, grad_mel: torch.Tensor) -> torch.Tensor:
+        """rfx_mel_scale_backward: (B, n_mels, T) -> (B, n_stft, T), the filterbank's adjoint"""
+        g = self._chk(grad_mel, torch.float32)
+        B, M, Tn = g.shape
+        if M != self.n_mels:
+            raise ValueError(f"expected {self.n_mels} mel bands, got {M}")
+        out = torch.empty((B, self.n_stft, Tn), dtype=torch.float32, device=self.device)
+        if B and Tn:
+            check(self.lib.rfx_mel_scale_backward(self.handle, g.data_ptr(), B, Tn, out.data_ptr(), None, 0, self._stream()))
+        return out
+
+    def mel_from_waveform_backward(self, wave: torch.Tensor, grad_mel: torch.Tensor) -> torch.Tensor:
+        """rfx_mel_from_waveform_backward: the (B, Lw) waveform `mel_from_waveform` was given and the (B, n_mels, T) gradient of
+        its result -> the (B, Lw) gradient of the waveform.  The spectrum is formed again in the workspace; nothing was kept."""
+        wave = self._chk(wave, torch.float32)
+        g = self._chk(grad_mel, torch.float32)
+        B, Lw = wave.shape
+        Tn = self._forward_frames(Lw, wave.shape, False)
+        if tuple(g.shape) != (B, self.n_mels, Tn):
+            raise ValueError(f"expected a ({B}, {self.n_mels}, {Tn}) gradient, got {tuple(g.shape)}")
+        out = torch.empty((B, Lw), dtype=torch.float32, device=self.device)
+        with self._workspace(self.lib.rfx_mel_from_waveform_backward_workspace_bytes(self.handle, B, Lw)) as ws:
+            check(self.lib.rfx_mel_from_waveform_backward(self.handle, wave.data_ptr(), g.data_ptr(), B, Lw, out.data_ptr(), ws.data_ptr(),
+                                                          ws.numel(), self._stream()))
         return out
 
     def inverse_mel(

@@ -13,6 +13,8 @@ builds (:47-99) are replaced by callables that run hand-written HIP kernels thro
 
 The two torch-level methods fuse these pairs so the (B, n_stft, T) intermediates of the reference are
 never materialised; the standalone callables exist for code that pokes at the members directly.
+The three forward members are differentiable, as the reference's are: with an input that requires grad they route through
+riffusion/_autograd.py and the gradient runs on the device; the inverse members and the loop encode are not.
 Every call is re-entrant: the converter holds immutable constants only (plans are cached per
 (params, device)), workspaces are checked out of the plan's arena per call (`_hip.WorkspaceArena`: two
 threads never share one) - the reference shares one converter across a thread pool (cli.py:172-204).  There is no CPU implementation: on a machine without a GPU the constructor still
@@ -25,6 +27,7 @@ import warnings
 import numpy as np
 import torch
 
+from riffusion import _autograd
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import audio_util, torch_util
 
@@ -128,6 +131,9 @@ class SpectrogramConverter:
         plan = self._plan()
         lead = waveform.shape[:-1]
         w = waveform.reshape(-1, waveform.shape[-1]).to(self.device)
+        if _autograd.wants_grad(w):  # differentiable as torchaudio's Spectrogram is: the gradient runs on the device (riffusion/_autograd.py)
+            spec = _autograd.stft(plan, w.to(torch.float32))
+            return spec.reshape(*lead, plan.n_stft, spec.shape[-1])
         _, spec, Tn = plan.stft(w, want_mag=False, want_spec=True)
         return plan.unpack_complex(spec, w.shape[0], Tn).reshape(*lead, plan.n_stft, Tn)
 
@@ -136,6 +142,8 @@ class SpectrogramConverter:
         plan = self._plan()
         lead = amplitudes.shape[:-2]
         x = amplitudes.reshape(-1, amplitudes.shape[-2], amplitudes.shape[-1]).to(self.device)
+        if _autograd.wants_grad(x):
+            return _autograd.mel_scale(plan, x.to(torch.float32)).reshape(*lead, plan.n_mels, x.shape[-1])
         return plan.mel_scale(x).reshape(*lead, plan.n_mels, x.shape[-1])
 
     def _inverse_mel_scale(
@@ -225,9 +233,18 @@ class SpectrogramConverter:
         `loop`: every row is one period of a loop, exactly hop * T samples with hop * T >= n_fft (any other length raises
         ValueError with the nearest legal lengths): the STFT is the circular one a loop decode runs - frame t, element i reads
         sample (hop t + i - n_fft // 2) mod (hop T) - so the tile has T columns, closes at the loop point, and a loop decode's
-        output gives its T frames back.  Columns whose window lies inside the clip are bit for bit the plain encode's."""
+        output gives its T frames back.  Columns whose window lies inside the clip are bit for bit the plain encode's.
+        Differentiable, as the reference's three forward modules are: when grad mode is on and `waveform` requires grad the result
+        carries a grad_fn whose backward runs on the device (rfx_mel_from_waveform_backward; only the waveform is saved, and a CPU
+        leaf's copy to the device is autograd's own).  The same bytes come out either way.  The loop encode has no backward yet:
+        `loop=True` on a waveform that requires grad raises RuntimeError instead of returning a constant."""
         if loop:
             self.check_loop_samples(int(waveform.shape[-1]))
+        if _autograd.wants_grad(waveform):
+            if loop:
+                raise RuntimeError("mel_amplitudes_from_waveform(loop=True): the loop encode has no backward yet; detach the waveform, "
+                                   "or encode without loop to differentiate")
+            return _autograd.mel_from_waveform(self._plan(), waveform.to(self.device).to(torch.float32))
         return self._plan().mel_from_waveform(waveform.to(self.device), loop=loop)
 
     def waveform_from_mel_amplitudes(
