@@ -141,6 +141,31 @@ int rfx_image_resize_u8(const uint8_t* d_in, int N, int H, int W, int out_h, int
   return RFX_OK;
 }
 
+// ---- what the four file-codec entries share ---------------------------------------------------------------------------------------
+static_assert(kJpgMaxSize == kPngMaxSize && kPngMaxSize == kPngdMaxSize, "axis_ok checks the codecs' one per-axis limit");
+static bool axis_ok(int H, int W) { return H >= 1 && W >= 1 && H <= kJpgMaxSize && W <= kJpgMaxSize; }
+static int refuse_size(const char* who, int H, int W, bool jpeg) {
+  return fail(RFX_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): " +
+                                       (jpeg ? "a JPEG holds at most 65535 rows and columns" : "this entry takes at most 65535 rows and columns"));
+}
+// the host copy of a decode's N + 1 offsets (`what`: "scan" or "stream"): there, not negative, not decreasing, no image longer than
+// max_bytes (2^28 - 64 for both decoders); *longest, when asked for, receives the longest image's bytes
+static int check_stream_offsets(const char* who, const char* what, const int64_t* h_offsets, int N, int64_t max_bytes, int64_t* longest) {
+  const std::string w(who), noun(what);
+  if (!h_offsets) return fail(RFX_ERR_INVALID, w + ": h_" + noun + "_offsets is NULL");
+  if (h_offsets[0] < 0) return fail(RFX_ERR_INVALID, w + ": the first " + noun + " offset is negative");
+  int64_t most = 0;
+  for (int n = 0; n < N; ++n) {
+    const int64_t bytes = h_offsets[n + 1] - h_offsets[n];
+    if (bytes < 0) return fail(RFX_ERR_INVALID, w + ": " + noun + " offsets must not decrease (image " + std::to_string(n) + ")");
+    if (bytes > max_bytes)
+      return fail(RFX_ERR_UNSUPPORTED, w + ": the " + noun + " of image " + std::to_string(n) + " is longer than 2^28 - 64 bytes");
+    most = bytes > most ? bytes : most;
+  }
+  if (longest) *longest = most;
+  return RFX_OK;
+}
+
 // ---- JPEG scan (rfx_jpeg.hip) ----------------------------------------------------------------------------------------------------
 int rfx_jpeg_quant_tables(int quality, uint16_t* h_luma64, uint16_t* h_chroma64) {
   if (!h_luma64 || !h_chroma64) return fail(RFX_ERR_INVALID, "rfx_jpeg_quant_tables: null pointer");
@@ -150,7 +175,6 @@ int rfx_jpeg_quant_tables(int quality, uint16_t* h_luma64, uint16_t* h_chroma64)
   return RFX_OK;
 }
 
-static bool jpeg_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= kJpgMaxSize && W <= kJpgMaxSize; }
 // what keeps an encode inside its index types: the scan's length is an int32, and the kernels take one thread per block / per
 // 16-byte chunk, 256 to a workgroup, at most 2^31 - 1 workgroups
 static const char* jpeg_batch_limit(int N, int H, int W) {
@@ -162,18 +186,17 @@ static const char* jpeg_batch_limit(int N, int H, int W) {
   return nullptr;
 }
 
-size_t rfx_jpeg_scan_capacity(int H, int W) { return jpeg_size_ok(H, W) ? (size_t)jpg_scan_capacity(jpg_geom(H, W)) : 0; }
+size_t rfx_jpeg_scan_capacity(int H, int W) { return axis_ok(H, W) ? (size_t)jpg_scan_capacity(jpg_geom(H, W)) : 0; }
 
 size_t rfx_jpeg_encode_workspace_bytes(int N, int H, int W) {
-  if (N < 1 || !jpeg_size_ok(H, W) || jpeg_batch_limit(N, H, W)) return 0;
+  if (N < 1 || !axis_ok(H, W) || jpeg_batch_limit(N, H, W)) return 0;
   return jpeg_workspace_layout(N, H, W).total;
 }
 
 int rfx_jpeg_encode_u8(const uint8_t* d_rgb, int N, int H, int W, const uint16_t* d_qtables, uint8_t* d_scan, int32_t* d_scan_bytes,
                        void* d_workspace, void* stream) {
   if (N < 1 || H < 1 || W < 1) return fail(RFX_ERR_INVALID, "rfx_jpeg_encode_u8: N, H and W must be positive");
-  if (!jpeg_size_ok(H, W))
-    return fail(RFX_ERR_UNSUPPORTED, "rfx_jpeg_encode_u8: " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): a JPEG holds at most 65535 rows and columns");
+  if (!axis_ok(H, W)) return refuse_size("rfx_jpeg_encode_u8", H, W, true);
   if (const char* why = jpeg_batch_limit(N, H, W)) return fail(RFX_ERR_UNSUPPORTED, std::string("rfx_jpeg_encode_u8: ") + why);
   if (!d_rgb || !d_qtables || !d_scan || !d_scan_bytes || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_jpeg_encode_u8: null pointer");
   int dev;
@@ -185,7 +208,6 @@ int rfx_jpeg_encode_u8(const uint8_t* d_rgb, int N, int H, int W, const uint16_t
 }
 
 // ---- PNG stream (rfx_png.hip) -------------------------------------------------------------------------------------------------------
-static bool png_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= kPngMaxSize && W <= kPngMaxSize; }
 // what keeps an encode inside its index types: the stream's length is an int32, and the kernels take one workgroup per row and
 // one thread per 256-byte piece of the stream, 256 to a workgroup, at most 2^31 - 1 workgroups
 static const char* png_batch_limit(int N, int H, int W) {
@@ -197,12 +219,12 @@ static const char* png_batch_limit(int N, int H, int W) {
 }
 
 size_t rfx_png_stream_capacity(int H, int W, int channels) {
-  if (!png_size_ok(H, W) || (channels != 1 && channels != 3)) return 0;
+  if (!axis_ok(H, W) || (channels != 1 && channels != 3)) return 0;
   return (size_t)png_stream_capacity(png_geom(H, W, channels));
 }
 
 size_t rfx_png_encode_workspace_bytes(int N, int H, int W) {
-  if (N < 1 || !png_size_ok(H, W) || png_batch_limit(N, H, W)) return 0;
+  if (N < 1 || !axis_ok(H, W) || png_batch_limit(N, H, W)) return 0;
   return png_workspace_layout(N, H, W).total;
 }
 
@@ -211,8 +233,7 @@ int rfx_png_encode_u8(const uint8_t* d_rgb, int N, int H, int W, int mode, uint8
   if (N < 1 || H < 1 || W < 1) return fail(RFX_ERR_INVALID, "rfx_png_encode_u8: N, H and W must be positive");
   if (mode != RFX_PNG_RGB && mode != RFX_PNG_GRAY && mode != RFX_PNG_AUTO)
     return fail(RFX_ERR_INVALID, "rfx_png_encode_u8: mode must be RFX_PNG_RGB, RFX_PNG_GRAY or RFX_PNG_AUTO");
-  if (!png_size_ok(H, W))
-    return fail(RFX_ERR_UNSUPPORTED, "rfx_png_encode_u8: " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): this entry takes at most 65535 rows and columns");
+  if (!axis_ok(H, W)) return refuse_size("rfx_png_encode_u8", H, W, false);
   if (const char* why = png_batch_limit(N, H, W)) return fail(RFX_ERR_UNSUPPORTED, std::string("rfx_png_encode_u8: ") + why);
   if (!d_rgb || !d_stream || !d_stream_bytes || !d_crc || !d_channels || !d_workspace) return fail(RFX_ERR_INVALID, "rfx_png_encode_u8: null pointer");
   if (reinterpret_cast<uintptr_t>(d_stream_bytes) % 4 || reinterpret_cast<uintptr_t>(d_crc) % 4 || reinterpret_cast<uintptr_t>(d_channels) % 4 ||
@@ -236,26 +257,17 @@ static const char* jpeg_decode_batch_limit(int N, int H, int W) {
 }
 
 size_t rfx_jpeg_decode_workspace_bytes(int N, int H, int W, size_t total_scan_bytes) {
-  if (N < 1 || !jpeg_size_ok(H, W) || jpeg_decode_batch_limit(N, H, W) || total_scan_bytes > (size_t)N * (size_t)kJpdMaxScanBytes) return 0;
+  if (N < 1 || !axis_ok(H, W) || jpeg_decode_batch_limit(N, H, W) || total_scan_bytes > (size_t)N * (size_t)kJpdMaxScanBytes) return 0;
   return jpeg_decode_workspace_layout(N, H, W, total_scan_bytes).total;
 }
 
 int rfx_jpeg_decode_u8(const uint8_t* d_scans, const int64_t* h_scan_offsets, const int64_t* d_scan_offsets, int N, int H, int W,
                        const uint16_t* d_qtables, const uint8_t* d_huff, uint8_t* d_rgb, int32_t* d_status, void* d_workspace, void* stream) {
   if (N < 1 || H < 1 || W < 1) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: N, H and W must be positive");
-  if (!jpeg_size_ok(H, W))
-    return fail(RFX_ERR_UNSUPPORTED, "rfx_jpeg_decode_u8: " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): a JPEG holds at most 65535 rows and columns");
+  if (!axis_ok(H, W)) return refuse_size("rfx_jpeg_decode_u8", H, W, true);
   if (const char* why = jpeg_decode_batch_limit(N, H, W)) return fail(RFX_ERR_UNSUPPORTED, std::string("rfx_jpeg_decode_u8: ") + why);
-  if (!h_scan_offsets) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: h_scan_offsets is NULL");
-  if (h_scan_offsets[0] < 0) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: the first scan offset is negative");
   int64_t longest = 0;
-  for (int n = 0; n < N; ++n) {
-    const int64_t bytes = h_scan_offsets[n + 1] - h_scan_offsets[n];
-    if (bytes < 0) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: scan offsets must not decrease (image " + std::to_string(n) + ")");
-    if (bytes > kJpdMaxScanBytes)
-      return fail(RFX_ERR_UNSUPPORTED, "rfx_jpeg_decode_u8: the scan of image " + std::to_string(n) + " is longer than 2^28 - 64 bytes");
-    longest = bytes > longest ? bytes : longest;
-  }
+  if (int rc = check_stream_offsets("rfx_jpeg_decode_u8", "scan", h_scan_offsets, N, kJpdMaxScanBytes, &longest)) return rc;
   if (!d_scans || !d_scan_offsets || !d_qtables || !d_huff || !d_rgb || !d_status || !d_workspace)
     return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: null pointer");
   if (reinterpret_cast<uintptr_t>(d_scans) % 16) return fail(RFX_ERR_INVALID, "rfx_jpeg_decode_u8: d_scans must be aligned to 16 bytes");
@@ -275,10 +287,9 @@ static const char* png_decode_batch_limit(int N, int H, int W, int color_type) {
   if (per_image > (uint64_t)INT64_MAX / (uint64_t)N) return "more filtered bytes than one launch indexes; decode in pieces";
   return nullptr;
 }
-static bool png_decode_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= kPngdMaxSize && W <= kPngdMaxSize; }
 
 size_t rfx_png_decode_workspace_bytes(int N, int H, int W, int color_type, size_t total_stream_bytes) {
-  if (N < 1 || !png_decode_size_ok(H, W) || !png_decode_type_ok(color_type) || png_decode_batch_limit(N, H, W, color_type) ||
+  if (N < 1 || !axis_ok(H, W) || !png_decode_type_ok(color_type) || png_decode_batch_limit(N, H, W, color_type) ||
       total_stream_bytes > (size_t)N * (size_t)kPngdMaxStreamBytes)
     return 0;
   return png_decode_workspace_layout(N, H, W, color_type).total;
@@ -289,17 +300,9 @@ int rfx_png_decode_u8(const uint8_t* d_streams, const int64_t* h_stream_offsets,
                       void* d_workspace, void* stream) {
   if (N < 1 || H < 1 || W < 1) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: N, H and W must be positive");
   if (!png_decode_type_ok(color_type)) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: color_type must be 0, 2, 3 or 6");
-  if (!png_decode_size_ok(H, W))
-    return fail(RFX_ERR_UNSUPPORTED, "rfx_png_decode_u8: " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): this entry takes at most 65535 rows and columns");
+  if (!axis_ok(H, W)) return refuse_size("rfx_png_decode_u8", H, W, false);
   if (const char* why = png_decode_batch_limit(N, H, W, color_type)) return fail(RFX_ERR_UNSUPPORTED, std::string("rfx_png_decode_u8: ") + why);
-  if (!h_stream_offsets) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: h_stream_offsets is NULL");
-  if (h_stream_offsets[0] < 0) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: the first stream offset is negative");
-  for (int n = 0; n < N; ++n) {
-    const int64_t bytes = h_stream_offsets[n + 1] - h_stream_offsets[n];
-    if (bytes < 0) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: stream offsets must not decrease (image " + std::to_string(n) + ")");
-    if (bytes > kPngdMaxStreamBytes)
-      return fail(RFX_ERR_UNSUPPORTED, "rfx_png_decode_u8: the stream of image " + std::to_string(n) + " is longer than 2^28 - 64 bytes");
-  }
+  if (int rc = check_stream_offsets("rfx_png_decode_u8", "stream", h_stream_offsets, N, kPngdMaxStreamBytes, nullptr)) return rc;
   if (!d_streams || !d_stream_offsets || !d_rgb || !d_status || !d_workspace || (color_type == 3 && (!d_palettes || !d_palette_entries)))
     return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: null pointer");
   if (reinterpret_cast<uintptr_t>(d_streams) % 16) return fail(RFX_ERR_INVALID, "rfx_png_decode_u8: d_streams must be aligned to 16 bytes");

@@ -475,6 +475,31 @@ def jpeg_quant_tables(quality: int) -> np.ndarray:
     return tables
 
 
+def check_tiles(img: torch.Tensor) -> torch.Tensor:
+    """`img` if it is an (N, H, W, 3) uint8 batch, on any device; ValueError otherwise."""
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] != 3:
+        raise ValueError("expected (N, H, W, 3) uint8 images")
+    return img
+
+
+def pack_streams(streams: T.Sequence[bytes], tables: T.Sequence[np.ndarray]) -> T.Tuple[np.ndarray, np.ndarray, T.List[int]]:
+    """What a file decode uploads in one copy: [offsets | tables | pad | streams] as one uint8 array - the N + 1 cumulative int64
+    offsets of the byte strings, each per-image table, the joined strings on a 16-byte boundary -> (array, offsets, every part's position)."""
+    offsets = np.zeros(len(streams) + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in streams], out=offsets[1:])
+    parts = [offsets.view(np.uint8)] + [np.ascontiguousarray(t).reshape(-1).view(np.uint8) for t in tables]
+    at = [0] + [int(v) for v in np.cumsum([p.size for p in parts])]
+    pad = -at[-1] % 16
+    at[-1] += pad
+    return np.concatenate(parts + [np.zeros(pad, np.uint8), np.frombuffer(b"".join(streams), np.uint8)]), offsets, at
+
+
+def split_packed(packed: bytes, sizes: T.Sequence[int]) -> T.List[bytes]:
+    """N byte strings of `sizes` bytes from their concatenation."""
+    ends = np.cumsum(sizes)
+    return [packed[int(e) - size:int(e)] for e, size in zip(ends, sizes)]
+
+
 CLIP_FRAMES_MAX = (1 << 31) - 1  # Lw of the clip entries is a C int
 
 
@@ -753,6 +778,18 @@ class Plan:
         if t.device != self.device:
             raise RfxError(f"tensor on {t.device} handed to a plan that lives on {self.device}")
         return (t if dtype is None else t.to(dtype)).contiguous()
+
+    def _chk_tiles(self, img: torch.Tensor) -> torch.Tensor:
+        """tiles as the codec entries read them: an (N, H, W, 3) uint8 batch (`check_tiles`), contiguous, on the plan's device"""
+        return self._chk(check_tiles(img))
+
+    def _pcm_out(self, out: T.Optional[torch.Tensor], shape: T.Tuple[int, int, int]) -> torch.Tensor:
+        """the (N, L, C) int16 destination of a PCM call: the caller's `out`, checked, or a fresh tensor"""
+        if out is None:
+            return torch.empty(shape, dtype=torch.int16, device=self.device)
+        if out.device != self.device or out.dtype != torch.int16 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int16 tensor of shape {shape} on {self.device}")
+        return out
 
     def _chk_guide(self, guide: torch.Tensor) -> torch.Tensor:
         """a guide as the library reads it: float32 on the plan's device, samples contiguous (a strided view of rows is passed as it is)"""
@@ -1139,9 +1176,7 @@ class Plan:
     # ---- codecs (no plan state needed, kept here for one binding site) -------------------------
     def image_decode(self, img_u8: torch.Tensor, stereo: bool, lut: torch.Tensor) -> torch.Tensor:
         """(N, H, W, 3) uint8 -> (N*C, H, W) float32."""
-        if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
-            raise ValueError("expected (N, H, W, 3) uint8 images")
-        img_u8 = self._chk(img_u8)
+        img_u8 = self._chk_tiles(img_u8)
         lut = self._chk(lut, torch.float32)
         N, H, W, _ = img_u8.shape
         C = 2 if stereo else 1
@@ -1167,12 +1202,10 @@ class Plan:
         """PIL.Image.resize((out_w, out_h), resample) of every (H, W, 3) uint8 tile of an (N, H, W, 3) batch on this device, byte
         for byte (rfx_image_resize_u8; resample: PIL's LANCZOS, BILINEAR or BICUBIC).  Each axis's table is built on the host once
         per (in, out, filter) and kept on the device like the decode LUT."""
-        if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
-            raise ValueError("expected (N, H, W, 3) uint8 images")
+        img = self._chk_tiles(img_u8)
         resample, out_h, out_w = int(resample), int(out_h), int(out_w)
         if resample not in RESIZE_FILTERS:
             raise ValueError(f"resample must be one of PIL's {sorted(RESIZE_FILTERS.values())} ({sorted(RESIZE_FILTERS)}), got {resample}")
-        img = self._chk(img_u8)
         N, H, W, _ = img.shape
         out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=self.device)
         if N == 0:
@@ -1192,14 +1225,18 @@ class Plan:
                                                ws.data_ptr(), ws.numel(), self._stream()))
         return out
 
+    @staticmethod
+    def _used_bytes(ws: torch.Tensor, need: int, cap: int, sizes: T.List[int]) -> T.List[bytes]:
+        """Image n's `sizes[n]` bytes at ws[need + n * cap], for every n: joined on the device, one copy down -> N `bytes`."""
+        rows = ws[need:need + len(sizes) * cap].view(len(sizes), cap)
+        return split_packed(torch.cat([rows[n, :size] for n, size in enumerate(sizes)]).cpu().numpy().tobytes(), sizes)
+
     def jpeg_scans(self, img_u8: torch.Tensor, quality: int = 75) -> T.List[bytes]:
         """The entropy-coded scan and EOI of every (H, W, 3) uint8 tile of an (N, H, W, 3) batch as Pillow's
         `Image.save(f, "JPEG", quality=quality)` writes them (rfx_jpeg_encode_u8) -> N `bytes`; a file is
         `image_util.jpeg_header(...)` + its scan.  The sizes are read once (the call's one synchronisation), then the used bytes of
         all scans come down in one copy.  Scans and scratch space come from the plan's arena."""
-        if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
-            raise ValueError("expected (N, H, W, 3) uint8 images")
-        img = self._chk(img_u8)
+        img = self._chk_tiles(img_u8)
         N, H, W, _ = img.shape
         if N == 0:
             return []
@@ -1217,10 +1254,7 @@ class Plan:
             sizes = [int(v) for v in sizes_d.cpu()]
             if min(sizes) < 2 or max(sizes) > cap:
                 raise RfxError(f"rfx_jpeg_encode_u8 reported scan sizes outside 2 .. {cap}")
-            scans = ws[need:need + N * cap].view(N, cap)
-            packed = torch.cat([scans[n, :size] for n, size in enumerate(sizes)]).cpu().numpy().tobytes()
-        ends = np.cumsum(sizes)
-        return [packed[int(e) - size:int(e)] for e, size in zip(ends, sizes)]
+            return self._used_bytes(ws, need, cap, sizes)
 
     def png_streams(self, img_u8: torch.Tensor, mode: str = "rgb") -> T.Tuple[T.List[bytes], np.ndarray, np.ndarray]:
         """The IDAT payload (a zlib stream: run-length + Huffman deflate, csrc/rfx_png_core.h) of every (H, W, 3) uint8 tile of an
@@ -1228,11 +1262,9 @@ class Plan:
         each tile was written with: 3, 1, or 0 where mode "gray" met a colour tile, whose stream is empty).  A file is
         `image_util.png_file(...)`.  mode: "rgb", "gray", or "auto" (grey where R = G = B, decided on the device).  The sizes, CRCs
         and channels are read once (the call's one synchronisation), then the used bytes of all streams come down in one copy."""
-        if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
-            raise ValueError("expected (N, H, W, 3) uint8 images")
+        img = self._chk_tiles(img_u8)
         if mode not in PNG_MODES:
             raise ValueError(f"mode must be one of {sorted(PNG_MODES)}, got {mode!r}")
-        img = self._chk(img_u8)
         N, H, W, _ = img.shape
         if N == 0:
             return [], np.zeros(0, np.uint32), np.zeros(0, np.int32)
@@ -1251,10 +1283,18 @@ class Plan:
             sizes = [int(v) for v in meta[0]]
             if min(sizes) < 0 or max(sizes) > cap:
                 raise RfxError(f"rfx_png_encode_u8 reported stream sizes outside 0 .. {cap}")
-            streams = ws[need:need + N * cap].view(N, cap)
-            packed = torch.cat([streams[n, :size] for n, size in enumerate(sizes)]).cpu().numpy().tobytes()
-        ends = np.cumsum(sizes)
-        return [packed[int(e) - size:int(e)] for e, size in zip(ends, sizes)], meta[1].view(np.uint32).copy(), meta[2].copy()
+            return self._used_bytes(ws, need, cap, sizes), meta[1].view(np.uint32).copy(), meta[2].copy()
+
+    def _run_decode(self, N: int, need: int, call: T.Callable[[int, T.Optional[int]], int], refused: str) -> np.ndarray:
+        """`call(d_status, d_workspace)`, a decode entry, on a borrowed workspace of `need` bytes -> the (N,) int32 status, read back.
+        `need == 0`: arguments the library refuses - its own words (nothing is launched), or `refused` should it take them."""
+        status = torch.empty((N,), dtype=torch.int32, device=self.device)
+        if need == 0:
+            check(call(status.data_ptr(), None))
+            raise RfxError(refused)
+        with self._workspace(need) as ws:
+            check(call(status.data_ptr(), ws.data_ptr()))
+            return status.cpu().numpy()
 
     def jpeg_decode(self, scans: T.Sequence[bytes], H: int, W: int, qtables: np.ndarray, huffman: np.ndarray) -> T.Tuple[torch.Tensor, np.ndarray]:
         """N baseline 4:2:0 JPEG scans of H x W images (the entropy-coded bytes between the SOS header and EOI, with each image's
@@ -1262,33 +1302,20 @@ class Plan:
         pixels Pillow decodes, on this device, and the (N,) int32 status of every image (rfx_jpeg_decode_u8; 0: decoded, anything
         else: that image's pixels are undefined).  Offsets, tables and scans go up in one copy; reading the status is the call's
         one synchronisation."""
-        N = len(scans)
+        N, H, W = len(scans), int(H), int(W)
         qtables = np.ascontiguousarray(qtables, dtype=np.uint16).reshape(N, 2, 64)
         huffman = np.ascontiguousarray(huffman, dtype=np.uint8).reshape(N, 4, 272)
-        out = torch.empty((N, int(H), int(W), 3), dtype=torch.uint8, device=self.device)
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=self.device)
         if N == 0:
             return out, np.zeros(0, np.int32)
-        offsets = np.zeros(N + 1, dtype=np.int64)
-        np.cumsum([len(s) for s in scans], out=offsets[1:])
-        total = int(offsets[-1])
-        need = self.lib.rfx_jpeg_decode_workspace_bytes(N, int(H), int(W), total)
-        # one upload: [offsets | qtables | huffman | scans], the scans on a 16-byte boundary
-        parts = [offsets.view(np.uint8), qtables.reshape(-1).view(np.uint8), huffman.reshape(-1)]
-        head = sum(p.size for p in parts)
-        pad = -head % 16
-        host = np.concatenate(parts + [np.zeros(pad, np.uint8), np.frombuffer(b"".join(scans), np.uint8)])
-        up = torch.from_numpy(host).to(self.device)
+        host, offsets, at = pack_streams(scans, [qtables, huffman])
+        up = torch.from_numpy(host).to(self.device)  # the one upload
         base = up.data_ptr()
-        status = torch.empty((N,), dtype=torch.int32, device=self.device)
-        if need == 0:  # arguments the library refuses: its own words (nothing is launched)
-            check(self.lib.rfx_jpeg_decode_u8(base + head + pad, offsets.ctypes.data, base, N, int(H), int(W), base + offsets.nbytes,
-                                              base + offsets.nbytes + qtables.nbytes, out.data_ptr(), status.data_ptr(), None, self._stream()))
-            raise RfxError(f"rfx_jpeg_decode_u8 took {N} {H} x {W} images it reports no workspace for")
-        with self._workspace(need) as ws:
-            check(self.lib.rfx_jpeg_decode_u8(base + head + pad, offsets.ctypes.data, base, N, int(H), int(W), base + offsets.nbytes,
-                                              base + offsets.nbytes + qtables.nbytes, out.data_ptr(), status.data_ptr(), ws.data_ptr(), self._stream()))
-            status_np = status.cpu().numpy()
-        return out, status_np
+        return out, self._run_decode(
+            N, self.lib.rfx_jpeg_decode_workspace_bytes(N, H, W, int(offsets[-1])),
+            lambda d_status, d_ws: self.lib.rfx_jpeg_decode_u8(base + at[3], offsets.ctypes.data, base, N, H, W, base + at[1], base + at[2],
+                                                               out.data_ptr(), d_status, d_ws, self._stream()),
+            f"rfx_jpeg_decode_u8 took {N} {H} x {W} images it reports no workspace for")
 
     def png_decode(self, streams: T.Sequence[bytes], H: int, W: int, color_type: int, palettes: T.Optional[np.ndarray] = None,
                    palette_entries: T.Optional[np.ndarray] = None) -> T.Tuple[torch.Tensor, np.ndarray]:
@@ -1302,40 +1329,20 @@ class Plan:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=self.device)
         if N == 0:
             return out, np.zeros(0, np.int32)
-        offsets = np.zeros(N + 1, dtype=np.int64)
-        np.cumsum([len(s) for s in streams], out=offsets[1:])
-        total = int(offsets[-1])
-        parts = [offsets.view(np.uint8)]
-        pal_at = ent_at = 0
+        tables: T.List[np.ndarray] = []  # colour type 3: [entries, palettes]
         if color_type == 3:
             if palettes is None or palette_entries is None:
                 raise ValueError("colour type 3 needs palettes and palette_entries")
-            pal = np.ascontiguousarray(palettes, dtype=np.uint8).reshape(N, 768)
-            ent = np.ascontiguousarray(palette_entries, dtype=np.int32).reshape(N)
-            ent_at = offsets.nbytes
-            pal_at = ent_at + ent.nbytes
-            parts += [ent.view(np.uint8), pal.reshape(-1)]
-        need = self.lib.rfx_png_decode_workspace_bytes(N, H, W, color_type, total)
-        # one upload: [offsets | palette entries | palettes | streams], the streams on a 16-byte boundary
-        head = sum(p.size for p in parts)
-        pad = -head % 16
-        host = np.concatenate(parts + [np.zeros(pad, np.uint8), np.frombuffer(b"".join(streams), np.uint8)])
-        up = torch.from_numpy(host).to(self.device)
+            tables = [np.ascontiguousarray(palette_entries, dtype=np.int32).reshape(N), np.ascontiguousarray(palettes, dtype=np.uint8).reshape(N, 768)]
+        host, offsets, at = pack_streams(streams, tables)
+        up = torch.from_numpy(host).to(self.device)  # the one upload
         base = up.data_ptr()
-        status = torch.empty((N,), dtype=torch.int32, device=self.device)
-
-        def call(workspace: T.Optional[int]) -> int:
-            return self.lib.rfx_png_decode_u8(base + head + pad, offsets.ctypes.data, base, N, H, W, color_type,
-                                              base + pal_at if color_type == 3 else None, base + ent_at if color_type == 3 else None,
-                                              out.data_ptr(), status.data_ptr(), workspace, self._stream())
-
-        if need == 0:  # arguments the library refuses: its own words (nothing is launched)
-            check(call(None))
-            raise RfxError(f"rfx_png_decode_u8 took {N} {H} x {W} images of colour type {color_type} it reports no workspace for")
-        with self._workspace(need) as ws:
-            check(call(ws.data_ptr()))
-            status_np = status.cpu().numpy()
-        return out, status_np
+        return out, self._run_decode(
+            N, self.lib.rfx_png_decode_workspace_bytes(N, H, W, color_type, int(offsets[-1])),
+            lambda d_status, d_ws: self.lib.rfx_png_decode_u8(base + at[-1], offsets.ctypes.data, base, N, H, W, color_type,
+                                                              base + at[2] if tables else None, base + at[1] if tables else None,
+                                                              out.data_ptr(), d_status, d_ws, self._stream()),
+            f"rfx_png_decode_u8 took {N} {H} x {W} images of colour type {color_type} it reports no workspace for")
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
                           row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False,
@@ -1376,25 +1383,18 @@ class Plan:
         float32 waveforms, image after image and channel after channel, as in `griffinlim`; `hold`: (N * C, 2) int32 held frames, row
         for row with the guide; `hold_bins`: (N * C, T, hold_mask_words) int32 held bins, row for row as well; `loop`: a loop decode,
         L = hop * T PCM frames per clip, as in `griffinlim`; `peak_start`: the spectral-peak start, as in `griffinlim`."""
-        if img.dtype != torch.uint8 or img.dim() != 4:
-            raise ValueError("expected (N, H, W, 3) uint8 images")
+        img = self._chk_tiles(img)
         if lstsq:
             self.require_lstsq()
-        img = self._chk(img)
         lut = self._chk(lut, torch.float32)
-        N, H, W, ch = img.shape
-        if ch != 3 or H != self.n_mels:
+        N, H, W, _ = img.shape
+        if H != self.n_mels:
             raise ValueError(f"expected (N, {self.n_mels}, T, 3) uint8 images, got {tuple(img.shape)}")
         C = 2 if stereo else 1
         opt, need, _ = self._inverse_call("audio_from_image", (N, int(stereo), W), N * C, W, clip_base * C, magnitude_hint, lstsq, guide, hold, hold_bins,
                                        loop, peak_start)
         L = self.output_samples(W, loop)
-        if out is not None:
-            if out.device != self.device or out.dtype != torch.int16 or tuple(out.shape) != (N, L, C) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int16 tensor of shape {(N, L, C)} on {self.device}")
-            pcm = out
-        else:
-            pcm = torch.empty((N, L, C), dtype=torch.int16, device=img.device)
+        pcm = self._pcm_out(out, (N, L, C))
         if workspace is not None:
             workspace = self._chk(workspace)
         peak = torch.zeros((N,), dtype=torch.float32, device=img.device)
@@ -1432,12 +1432,7 @@ class Plan:
         if NC % channels:
             raise ValueError("batch must be a multiple of the channel count")
         N = NC // channels
-        if out is not None:
-            if out.device != self.device or out.dtype != torch.int16 or tuple(out.shape) != (N, L, channels) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int16 tensor of shape {(N, L, channels)} on {self.device}")
-            pcm = out
-        else:
-            pcm = torch.empty((N, L, channels), dtype=torch.int16, device=wave.device)
+        pcm = self._pcm_out(out, (N, L, channels))
         peak = torch.zeros((N,), dtype=torch.float32, device=wave.device)
         check(self.lib.rfx_pcm16(wave.data_ptr(), N, channels, L, int(normalize), peak.data_ptr(), pcm.data_ptr(), self._stream()))
         return pcm, peak
@@ -1484,10 +1479,7 @@ class Plan:
         if out is not None and out.data_ptr() == pcm.data_ptr() and not pcm.is_contiguous():
             raise ValueError("in place needs a contiguous batch")
         src = self._chk(pcm)
-        if out is None:
-            out = torch.empty_like(src)
-        elif out.device != self.device or out.dtype != torch.int16 or tuple(out.shape) != (N, L, C) or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous int16 tensor of shape {(N, L, C)} on {self.device}")
+        out = self._pcm_out(out, (N, L, C))
         if N == 0:
             return out
         gain, boost = self.filter_tables()

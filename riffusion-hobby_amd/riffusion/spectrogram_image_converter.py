@@ -10,6 +10,7 @@ and one D2H copy per batch, takes the diffusion pipeline's output tensors direct
 collective is the final all_gather of the int16 PCM).
 """
 import functools
+import io
 import typing as T
 
 import numpy as np
@@ -25,6 +26,29 @@ from riffusion.util import audio_util, image_util
 # ... and of the batch entry points, whose guides are `guide_waveforms`
 BATCH_WORDING = {**CALL_WORDING, "hold_needs_guide": "hold_frames needs guide_waveforms: the frames are held at the guides' phase",
                  "bins_need_guide": "hold_mask needs guide_waveforms: the bins are held at the guides' phase"}
+
+
+class _FileFormat(T.NamedTuple):
+    """What `_images_from_files` needs to know of a file format."""
+    parse: T.Callable  # a file -> its info: `ok_for_device`, `exif` and what the two below read
+    key: T.Callable  # an info -> what the files of one device call share
+    decode: T.Callable  # (plan, the call's files, their infos, their key) -> (rgb, status)
+
+
+def _jpeg_group_decode(plan: T.Any, files: T.List[bytes], infos: T.List[T.Any], key: T.Tuple[int, int]) -> T.Tuple[torch.Tensor, np.ndarray]:
+    return plan.jpeg_decode([f[info.scan[0]:info.scan[1]] for f, info in zip(files, infos)], *key,
+                            np.stack([info.qtables for info in infos]), np.stack([info.huffman for info in infos]))
+
+
+def _png_group_decode(plan: T.Any, files: T.List[bytes], infos: T.List[T.Any], key: T.Tuple[int, int, int]) -> T.Tuple[torch.Tensor, np.ndarray]:
+    streams = [b"".join(f[a:b] for a, b in info.idat) for f, info in zip(files, infos)]
+    paletted = key[2] == 3
+    return plan.png_decode(streams, *key, np.stack([info.palette for info in infos]) if paletted else None,
+                           np.array([info.palette_entries for info in infos], dtype=np.int32) if paletted else None)
+
+
+_JPEG_FILES = _FileFormat(image_util.jpeg_parse, lambda info: (info.height, info.width), _jpeg_group_decode)
+_PNG_FILES = _FileFormat(image_util.png_parse, lambda info: (info.height, info.width, info.color_type), _png_group_decode)
 
 
 class SpectrogramImageConverter:
@@ -285,16 +309,22 @@ class SpectrogramImageConverter:
         thr = plan.device_constant(("encode_thresholds", power), lambda: image_util.encode_thresholds(power))
         # one call (rfx_image_from_waveform): the mel amplitudes go from the forward kernel to the encoder without the (N*C, M, T) tensor
         img, mx = plan.image_from_waveform(waveforms.reshape(N * C, L).to(conv.device, torch.float32), self.p.stereo, thr, loop=loop)
+        return self._deliver_tiles(img, mx, return_device, as_jpeg, as_png, png_mode)
+
+    def _deliver_tiles(self, tiles: T.Any, maxima: torch.Tensor, return_device: bool, as_jpeg: bool, as_png: bool, png_mode: str) -> T.Tuple[T.Any, T.Any]:
+        """Tiles on the device - one (N, n_mels, T, 3) batch, or a list of N tiles whose widths differ - and their (N,) maxima in
+        the form the caller asked for: as they are, as JPEG or PNG files with the params and MAX_VALUE as EXIF, or as PIL images."""
         if return_device:
-            return img, mx
-        if as_jpeg:
-            mx_np = mx.cpu().numpy()
-            return self.jpeg_bytes_from_images(img, exif=[self.exif_with_max_value(v) for v in mx_np]), mx_np
-        if as_png:
-            mx_np = mx.cpu().numpy()
-            return self.png_bytes_from_images(img, exif=[self.exif_with_max_value(v) for v in mx_np], mode=png_mode), mx_np
-        img_np, mx_np = img.cpu().numpy(), mx.cpu().numpy()
-        return [Image.fromarray(a, mode="RGB") for a in img_np], mx_np
+            return tiles, maxima
+        mx_np = maxima.cpu().numpy()
+        if as_jpeg or as_png:
+            encode = self.jpeg_bytes_from_images if as_jpeg else functools.partial(self.png_bytes_from_images, mode=png_mode)
+            exifs = [self.exif_with_max_value(v) for v in mx_np]
+            if isinstance(tiles, list):
+                return [encode(t[None], exif=e)[0] for t, e in zip(tiles, exifs)], mx_np
+            return (encode(tiles, exif=exifs) if len(exifs) else []), mx_np
+        host = [t.cpu().numpy() for t in tiles] if isinstance(tiles, list) else tiles.cpu().numpy()
+        return [Image.fromarray(a, mode="RGB") for a in host], mx_np
 
     # ---- JPEG files from tiles on the device: Pillow's Image.save(f, "JPEG"), byte for byte (rfx_jpeg_encode_u8) ----------------
     def exif_with_max_value(self, max_value: float) -> Image.Exif:
@@ -316,28 +346,14 @@ class SpectrogramImageConverter:
         Pillow's `subsampling`, `optimize` and `progressive` are not implemented: giving one raises ValueError.  The tiles are
         encoded `tiles_per_call` at a time: the scans' worst-case buffer is about 2.5 MB per 512 x 512 tile.
         """
-        for name, value in (("subsampling", subsampling), ("optimize", optimize), ("progressive", progressive)):
-            if value is not None:
-                raise ValueError(f"jpeg_bytes_from_images writes Pillow's default baseline 4:2:0 files only: `{name}` is not implemented")
-        if tiles_per_call < 1:
-            raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        imgs, exifs = self._tiles_to_encode(
+            images, exif, image_util.jpeg_exif_bytes, tiles_per_call, "jpeg_bytes_from_images writes Pillow's default baseline 4:2:0 files only",
+            subsampling=subsampling, optimize=optimize, progressive=progressive)
         quality = int(quality)
         if not 1 <= quality <= 100:
             raise ValueError(f"quality must be in 1 .. 100, got {quality}")
         plan = self.converter._plan()
-        if not isinstance(images, torch.Tensor):
-            images = np.ascontiguousarray(images)
-            images = images if images.flags.writeable else images.copy()  # (torch takes no read-only arrays, such as a PIL image's)
-        imgs = torch.as_tensor(images)
-        if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[-1] != 3:
-            raise ValueError("expected (N, H, W, 3) uint8 images")
         N, H, W, _ = imgs.shape
-        if exif is None or isinstance(exif, (Image.Exif, bytes, bytearray)):
-            exifs = [image_util.jpeg_exif_bytes(exif)] * N
-        else:
-            exifs = [image_util.jpeg_exif_bytes(e) for e in exif]
-            if len(exifs) != N:
-                raise ValueError(f"{N} images need {N} EXIF entries (or one for all), got {len(exifs)}")
         head, tail = image_util.jpeg_header_parts(W, H, quality, _hip.jpeg_quant_tables(quality))
         files: T.List[bytes] = []
         for lo in range(0, N, tiles_per_call):
@@ -345,6 +361,28 @@ class SpectrogramImageConverter:
             for e, scan in zip(exifs[lo:lo + tiles_per_call], plan.jpeg_scans(chunk.to(plan.device), quality)):
                 files.append(b"".join((head, image_util._jpeg_segment(0xE1, e) if e else b"", tail, scan)))
         return files
+
+    @staticmethod
+    def _tiles_to_encode(images: T.Any, exif: T.Any, exif_bytes: T.Callable[[T.Any], bytes], tiles_per_call: int, writes: str,
+                         **unimplemented: T.Any) -> T.Tuple[torch.Tensor, T.List[bytes]]:
+        """The front of `jpeg_bytes_from_images` / `png_bytes_from_images`: refuses the keywords of Pillow's the writer does not
+        implement and a `tiles_per_call` below 1 -> the checked (N, H, W, 3) uint8 tensor and `exif` as N `exif_bytes` strings."""
+        for name, value in unimplemented.items():
+            if value is not None:
+                raise ValueError(f"{writes}: `{name}` is not implemented")
+        if tiles_per_call < 1:
+            raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        if not isinstance(images, torch.Tensor):
+            images = np.ascontiguousarray(images)
+            images = images if images.flags.writeable else images.copy()  # (torch takes no read-only arrays, such as a PIL image's)
+        imgs = _hip.check_tiles(torch.as_tensor(images))
+        N = imgs.shape[0]
+        if exif is None or isinstance(exif, (Image.Exif, bytes, bytearray)):
+            return imgs, [exif_bytes(exif)] * N
+        exifs = [exif_bytes(e) for e in exif]
+        if len(exifs) != N:
+            raise ValueError(f"{N} images need {N} EXIF entries (or one for all), got {len(exifs)}")
+        return imgs, exifs
 
     # ---- PNG files from tiles on the device: lossless, the IDAT payload written there (rfx_png_encode_u8) --------------------------
     @staticmethod
@@ -369,27 +407,13 @@ class SpectrogramImageConverter:
         `compress_type` and `bits` are not implemented: giving one raises ValueError.  The tiles are encoded `tiles_per_call` at
         a time: the streams' worst-case buffer and the scratch space are about 4 MB per 512 x 512 tile.
         """
-        for name, value in (("optimize", optimize), ("compress_level", compress_level), ("compress_type", compress_type), ("bits", bits)):
-            if value is not None:
-                raise ValueError(f"png_bytes_from_images writes its own run-length + Huffman stream only: `{name}` is not implemented")
-        if tiles_per_call < 1:
-            raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
+        imgs, exifs = self._tiles_to_encode(
+            images, exif, image_util.png_exif_bytes, tiles_per_call, "png_bytes_from_images writes its own run-length + Huffman stream only",
+            optimize=optimize, compress_level=compress_level, compress_type=compress_type, bits=bits)
         if mode not in _hip.PNG_MODES:
             raise ValueError(f"mode must be one of {sorted(_hip.PNG_MODES)}, got {mode!r}")
         plan = self.converter._plan()
-        if not isinstance(images, torch.Tensor):
-            images = np.ascontiguousarray(images)
-            images = images if images.flags.writeable else images.copy()  # (torch takes no read-only arrays, such as a PIL image's)
-        imgs = torch.as_tensor(images)
-        if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[-1] != 3:
-            raise ValueError("expected (N, H, W, 3) uint8 images")
         N, H, W, _ = imgs.shape
-        if exif is None or isinstance(exif, (Image.Exif, bytes, bytearray)):
-            exifs = [image_util.png_exif_bytes(exif)] * N
-        else:
-            exifs = [image_util.png_exif_bytes(e) for e in exif]
-            if len(exifs) != N:
-                raise ValueError(f"{N} images need {N} EXIF entries (or one for all), got {len(exifs)}")
         files: T.List[bytes] = []
         for lo in range(0, N, tiles_per_call):
             streams, crcs, channels = plan.png_streams(imgs[lo:lo + tiles_per_call].to(plan.device), mode)
@@ -410,45 +434,7 @@ class SpectrogramImageConverter:
         Pillow's own exceptions for files it cannot read.  The tiles come back as one (N, H, W, 3) batch when all files have one
         size, else as a list of N; numpy arrays, or tensors on the device with `return_device=True`.
         """
-        import io
-
-        if tiles_per_call < 1:
-            raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
-        files = [bytes(f) for f in files]
-        plan = self.converter._plan()
-        infos = [image_util.jpeg_parse(f) for f in files]
-        tiles: T.List[T.Any] = [None] * len(files)
-        exifs: T.List[T.Any] = [None] * len(files)
-        by_size: T.Dict[T.Tuple[int, int], T.List[int]] = {}
-        for i, info in enumerate(infos):
-            if info.ok_for_device:
-                by_size.setdefault((info.height, info.width), []).append(i)
-        whole = None  # the one device batch that is the whole result, if there is one
-        for (H, W), members in by_size.items():
-            for lo in range(0, len(members), tiles_per_call):
-                idx = members[lo:lo + tiles_per_call]
-                rgb, status = plan.jpeg_decode([files[i][infos[i].scan[0]:infos[i].scan[1]] for i in idx], H, W,
-                                               np.stack([infos[i].qtables for i in idx]), np.stack([infos[i].huffman for i in idx]))
-                if len(idx) == len(files) and not status.any():
-                    whole = rgb
-                batch = rgb if return_device else rgb.cpu().numpy()
-                for j, i in enumerate(idx):
-                    if status[j] == 0:
-                        tiles[i] = batch[j]
-                        exifs[i] = Image.Exif()
-                        if infos[i].exif:
-                            exifs[i].load(infos[i].exif)
-        for i, data in enumerate(files):
-            if tiles[i] is None:  # the host route
-                with Image.open(io.BytesIO(data)) as im:
-                    arr = image_util.rgb_array_from_image(im)
-                    exifs[i] = im.getexif()
-                tiles[i] = torch.from_numpy(arr).to(plan.device) if return_device else arr
-        if whole is not None:
-            return (whole if return_device else whole.cpu().numpy()), exifs
-        if len(files) and len({tuple(t.shape) for t in tiles}) == 1:
-            return (torch.stack(tiles) if return_device else np.stack(tiles)), exifs
-        return tiles, exifs
+        return self._images_from_files(files, return_device, tiles_per_call, _JPEG_FILES)
 
     def images_from_png_bytes(self, files: T.Sequence[bytes], return_device: bool = False, tiles_per_call: int = 64) -> T.Tuple[T.Any, T.List[Image.Exif]]:
         """
@@ -461,27 +447,27 @@ class SpectrogramImageConverter:
         cannot read.  The tiles come back as one (N, H, W, 3) batch when all files have one size, else as a list of N; numpy
         arrays, or tensors on the device with `return_device=True`.
         """
-        import io
+        return self._images_from_files(files, return_device, tiles_per_call, _PNG_FILES)
 
+    def _images_from_files(self, files: T.Sequence[bytes], return_device: bool, tiles_per_call: int, fmt: _FileFormat) -> T.Tuple[T.Any, T.List[Image.Exif]]:
+        """`images_from_jpeg_bytes` / `images_from_png_bytes`: the files `fmt.parse` finds `ok_for_device` are decoded there,
+        `tiles_per_call` files of one `fmt.key` at a time; a file is the device's when its status is 0 and Pillow's otherwise."""
         if tiles_per_call < 1:
             raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
         files = [bytes(f) for f in files]
         plan = self.converter._plan()
-        infos = [image_util.png_parse(f) for f in files]
+        infos = [fmt.parse(f) for f in files]
         tiles: T.List[T.Any] = [None] * len(files)
         exifs: T.List[T.Any] = [None] * len(files)
-        groups: T.Dict[T.Tuple[int, int, int], T.List[int]] = {}
+        groups: T.Dict[T.Any, T.List[int]] = {}
         for i, info in enumerate(infos):
             if info.ok_for_device:
-                groups.setdefault((info.height, info.width, info.color_type), []).append(i)
+                groups.setdefault(fmt.key(info), []).append(i)
         whole = None  # the one device batch that is the whole result, if there is one
-        for (H, W, color_type), members in groups.items():
+        for key, members in groups.items():
             for lo in range(0, len(members), tiles_per_call):
                 idx = members[lo:lo + tiles_per_call]
-                streams = [b"".join(files[i][a:b] for a, b in infos[i].idat) for i in idx]
-                palettes = np.stack([infos[i].palette for i in idx]) if color_type == 3 else None
-                entries = np.array([infos[i].palette_entries for i in idx], dtype=np.int32) if color_type == 3 else None
-                rgb, status = plan.png_decode(streams, H, W, color_type, palettes, entries)
+                rgb, status = fmt.decode(plan, [files[i] for i in idx], [infos[i] for i in idx], key)
                 if len(idx) == len(files) and not status.any():
                     whole = rgb
                 batch = rgb if return_device else rgb.cpu().numpy()
@@ -568,23 +554,13 @@ class SpectrogramImageConverter:
                 wave = np.array([c.get_array_of_samples() for c in clip.split_to_mono()]).astype(np.float32)
                 img, mx = self.spectrogram_images_from_waveforms(torch.from_numpy(wave)[None], return_device=True)
                 tiles[i], maxima[i] = img[0], mx[0]
-        same_width = len({int(t.shape[1]) for t in tiles}) <= 1
-        if return_device:
-            if not same_width:
-                return tiles, maxima
-            if n and len(r.index) == n:
-                return img, maxima
-            return (torch.stack(tiles) if n else torch.empty((0, plan.n_mels, 0, 3), dtype=torch.uint8, device=plan.device)), maxima
-        if as_jpeg or as_png:
-            encode = self.jpeg_bytes_from_images if as_jpeg else functools.partial(self.png_bytes_from_images, mode=png_mode)
-            mx_np = maxima.cpu().numpy()
-            exifs = [self.exif_with_max_value(v) for v in mx_np]
-            if n and len(r.index) == n:
-                return encode(img, exif=exifs), mx_np
-            if same_width:
-                return (encode(torch.stack(tiles), exif=exifs) if n else []), mx_np
-            return [encode(t[None], exif=e)[0] for t, e in zip(tiles, exifs)], mx_np
-        return [Image.fromarray(t.cpu().numpy(), mode="RGB") for t in tiles], maxima.cpu().numpy()
+        if n == 0:
+            tiles = torch.empty((0, plan.n_mels, 0, 3), dtype=torch.uint8, device=plan.device)
+        elif len(r.index) == n:
+            tiles = img  # every clip came from the one device call: its batch as it is
+        elif len({int(t.shape[1]) for t in tiles}) == 1:
+            tiles = torch.stack(tiles)
+        return self._deliver_tiles(tiles, maxima, return_device, as_jpeg, as_png, png_mode)
 
     # ---- resizing tiles on the device: PIL.Image.resize, byte for byte (rfx_image_resize_u8) --------------------------------
     def resize_images(self, images: T.Any, size: T.Tuple[int, int], resample: int = Image.BICUBIC) -> torch.Tensor:
