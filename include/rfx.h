@@ -683,7 +683,8 @@ int rfx_mel_scale(const rfx_plan* plan, const float* d_lin_bft, int B, int T, fl
  * kernel works frame by frame or sample by sample, whatever B is and wherever the row's group falls.  BOUNDED WORKSPACE: the rows
  * are walked in groups of max(1, 256 MiB / row bytes) whole rows, row bytes = T * (frame_stride * 8 [fused call only] + slot stride * 4 +
  * frame pitch * 4) - 67 MB for a 512-frame row at the default geometry - so a query answers at most 256 MiB + 768 bytes, or one
- * row's bytes when a row alone is larger; it answers 0 where the call would be refused.  The loop forms have no backward.
+ * row's bytes when a row alone is larger; it answers 0 where the call would be refused.  The loop forms of these three have no backward: the loop STFT has one
+ * through the loss entries only (rfx_spectral_loss_backward_loop, "FUSED SPECTRAL LOSSES" below).
  *
  * rfx_stft_backward: steps 3 and 4.  d_grad_spec_slots: the complex gradient in slot layout - what rfx_pack_complex writes,
  * conjugate slots conjugated, both slots of a doubled bin filled - B * T frames; d_grad_wave (B, Lw) float32.
@@ -707,6 +708,54 @@ int rfx_mel_from_waveform_backward(const rfx_plan* plan, const float* d_wave, co
  * nullable (a first call learns the width); a capacity below the width is refused. */
 int rfx_debug_mel_adjoint(const rfx_params* params, const float* h_melfb, int32_t* h_first, int32_t* h_count, float* h_weights,
                           int capacity, int32_t* width_out);
+
+/* ---- FUSED SPECTRAL LOSSES with device gradients: spectral convergence and log-magnitude L1 of the multi-resolution STFT loss ---------
+ * Per row b of a (B, Lw) float32 waveform: T = rfx_stft_frames(Lw) (loop forms: Lw = hop T exactly, under the loop encode's length
+ * rule, T = rfx_stft_loop_frames(Lw)); X the row's complex STFT as rfx_stft (loop: rfx_stft_loop) computes it; a = |X| what that entry
+ * writes as magnitudes; m the target in slot layout, what rfx_pack_magnitudes writes; n = n_stft T bins, each counted once (the
+ * counting rule of rfx_spectral_error); f = log_floor.
+ * Forward, three double sums per row, d_sums_out (B, 3):
+ *   num = sum (a - m)^2        den = sum m^2        lsum = sum | ln max(a, f) - ln max(m, f) |
+ * num and den are bit for bit rfx_spectral_error's wherever that entry takes the shape: the same chunks, per-thread order and halving
+ * tree.  lsum rides the same tree, each term formed in double from the two float32 values.  log_floor == 0 means "no log term": lsum is
+ * 0 and no logarithm is evaluated.  A negative or non-finite floor, or 0 < f < 1e-18, is refused: 1 / f^2 must fit float32 in the
+ * backward.  The caller forms the losses from the sums: convergence = sqrt(num / den), log_magnitude = lsum / n.
+ * Backward.  With (g_sc, g_lg) the incoming gradients of the two losses of a row, d_coef (B, 2) float32 holds
+ *   c_sc = g_sc / sqrt(num den) when num > 0 and den > 0, else 0 (the zero subgradient of the norm; a silent target gets no gradient)
+ *   c_lg = g_lg / n
+ * (the Python layer computes them with torch operations on the device: nothing is read back) and
+ *   dL/da = c_sc (a - m) + c_lg sgn(ln max(a, f) - ln max(m, f)) [a >= f] / a        sgn(0) = 0; a == f passes (torch.clamp)
+ * followed by steps 2, 3 and 4 above: torch.abs's backward with its zero rule (a == 0 gives exactly 0), the frame adjoint and the
+ * adjoint fold.  For a loop row step 4 is the circular chain of the loop decode's fold: with q = j + h - left, sample j sums
+ * w[q - hop t] f_(t mod T)[q - hop t] over the unwrapped covering frames t = ceil((q - win_length + 1) / hop) .. floor(q / hop),
+ * oldest first - no envelope, no reflect partners; rolling the waveform and the target's columns by k hops rolls the gradient by
+ * k hop samples bit for bit.  The target receives no gradient.  These entries are the loop STFT's only backward: the loop forms of
+ * the forward entries above have none.
+ * On the device, per group of rows.  Forward: the plan's forward transform into the workspace, then rfx_spectral_error's reduction
+ * carrying the third sum (groups of 128 MiB of magnitudes).  Backward: rfx_mel_from_waveform_backward's sequence - re-analysis, one
+ * kernel writing the magnitude slots S' = weight[k] (dL/da) / a, each from the magnitude of the very complex value it will multiply
+ * (a = sqrtf(fmaf(re, re, im im)), the forward entries' own expression: the sign and a >= f are decided on the value the sums saw),
+ * the engine's MODE 0 frame launch on S' X, the fold kernel (the circular one for loop rows) - in groups of 256 MiB, the fused
+ * backward's row bytes.  All four frame engines, loop forms included (the chirp-z engine refuses a loop decode; its frame launch and
+ * its loop forward transform exist).  The (B, n_stft, T) tensor is never written.
+ * Contract: B == 0 is a no-op.  Refusals - a NULL pointer; d_mag_slots or the workspace not 16-byte aligned, d_sums_out not 8-byte,
+ * another tensor not 4-byte aligned; Lw <= n_fft / 2; for a loop form a length that is no whole period (the message names the nearest
+ * legal lengths); a bad floor; a workspace below the query - come before any launch and leave the output untouched; a size query
+ * answers 0 where the call would refuse.  Offsets are 64-bit.  Deterministic; a row's bytes depend on that row alone. */
+size_t rfx_spectral_loss_workspace_bytes(const rfx_plan* plan, int B, int Lw);
+int rfx_spectral_loss(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor,
+                      double* d_sums_out /* (B, 3) */, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t rfx_spectral_loss_loop_workspace_bytes(const rfx_plan* plan, int B, int Lw);
+int rfx_spectral_loss_loop(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor,
+                           double* d_sums_out /* (B, 3) */, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t rfx_spectral_loss_backward_workspace_bytes(const rfx_plan* plan, int B, int Lw);
+int rfx_spectral_loss_backward(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, const float* d_coef /* (B, 2) */,
+                               int B, int Lw, float log_floor, float* d_grad_wave, void* d_workspace, size_t workspace_bytes,
+                               void* stream);
+size_t rfx_spectral_loss_backward_loop_workspace_bytes(const rfx_plan* plan, int B, int Lw);
+int rfx_spectral_loss_backward_loop(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots,
+                                    const float* d_coef /* (B, 2) */, int B, int Lw, float log_floor, float* d_grad_wave,
+                                    void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- inverse: torchaudio.transforms.InverseMelScale (SGD, max_iter = params.max_mel_iters,
  * tolerance_loss 1e-5, tolerance_change 1e-8, lr 0.1, momentum 0.9), spectrogram_converter.py:87-99,

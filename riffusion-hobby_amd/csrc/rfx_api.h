@@ -144,6 +144,9 @@ inline int frame_blocks(long long slots, int B, int T) {
   const long long nframes = (long long)B * T;
   return (int)(nframes < slots ? nframes : slots);
 }
+// the refusal of a row length a loop forward call does not take, with the nearest lengths it does; RFX_OK for a legal one
+// (rfx_api_forward.hip; the loop loss backward of rfx_api_backward.hip words its refusal the same way)
+int loop_length_refusal(const rfx_plan* plan, int Lw, const char* who);
 inline long long fam_slot_count(const rfx_plan* plan) { return (long long)plan->num_cus * plan->fam_wgs_per_cu; }
 
 // the spectral-peak start as the inverse entries use it (rfx_api_peak.hip): the refusal of a plan whose frame does not fit the LDS;

@@ -9,6 +9,7 @@
 // every kernel of the sequence works frame by frame or sample by sample: a row's bytes depend on that row alone.
 #include "rfx_api.h"
 #include "rfx_mel_bwd_core.h"
+#include "rfx_spec_loss_core.h"
 
 using namespace rfx;
 
@@ -20,10 +21,11 @@ struct MelBwdLayout {
   int group_rows, T;
 };
 static size_t mel_bwd_frame_pitch(const rfx_plan* plan) { return plan->generic ? (size_t)plan->gg.fpitch : gl_frame_buffer_bytes(1, 1) / sizeof(float); }
-static MelBwdLayout mel_bwd_layout(const rfx_plan* plan, int B, int Lw, bool with_spec) {
+// ... of rows of T frames (the plain forms: T = stft_frames(Lw); the loop loss backward: T = Lw / hop)
+static MelBwdLayout mel_bwd_layout_frames(const rfx_plan* plan, int B, int frames, bool with_spec) {
   MelBwdLayout l{};
-  if (B <= 0 || Lw <= plan->p.n_fft / 2) return l;
-  l.T = stft_frames(plan, Lw);
+  if (B <= 0 || frames <= 0) return l;
+  l.T = frames;
   const size_t T = (size_t)l.T;
   const size_t spec_row = with_spec ? T * plan->frame_stride * sizeof(cf) : 0, smag_row = T * plan->mb_sstride * sizeof(float),
                frames_row = T * mel_bwd_frame_pitch(plan) * sizeof(float);
@@ -36,6 +38,10 @@ static MelBwdLayout mel_bwd_layout(const rfx_plan* plan, int B, int Lw, bool wit
   l.frames = c.take(rows * frames_row);
   l.total = c.at;
   return l;
+}
+static MelBwdLayout mel_bwd_layout(const rfx_plan* plan, int B, int Lw, bool with_spec) {
+  if (B <= 0 || Lw <= plan->p.n_fft / 2) return MelBwdLayout{};
+  return mel_bwd_layout_frames(plan, B, stft_frames(plan, Lw), with_spec);
 }
 size_t rfx_stft_backward_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? mel_bwd_layout(plan, B, Lw, false).total : 0; }
 size_t rfx_mel_from_waveform_backward_workspace_bytes(const rfx_plan* plan, int B, int Lw) {
@@ -186,4 +192,93 @@ int rfx_mel_scale_backward(const rfx_plan* plan, const float* d_grad_mel, int B,
   RFX_HIP(launch_mel_bwd_bank(d_grad_mel, d_grad_lin_bft, plan->d_mb_first, plan->d_mb_count, plan->d_mb_wt, plan->mb_width, B, plan->p.n_mels, T,
                               plan->n_stft, (hipStream_t)stream));
   return RFX_OK;
+}
+
+// ---- fused spectral losses, backward (rfx_spec_loss_core.h): rfx_mel_from_waveform_backward's sequence with another S' ---------------
+// Per group of rows: rfx_stft (loop: rfx_stft_loop) of the rows, spectrum into the workspace; spec_loss_slots_kernel writes the magnitude
+// slots from the spectrum, the target's slots and the rows' coefficients; the engine's MODE 0 frame launch on S' X (mel_bwd_frames, all
+// four engines - the chirp-z engine's too: it refuses a loop DECODE, its MODE 0 launch and its loop forward exist); the adjoint fold -
+// mel_bwd_fold_kernel as it is, or for a loop row the circular one.  The layout is the fused backward's at the form's frame count.
+static MelBwdLayout spectral_loss_backward_layout(const rfx_plan* plan, int B, int Lw, bool loop) {
+  if (!loop) return mel_bwd_layout(plan, B, Lw, true);
+  if (B <= 0 || !loop_samples_valid(plan->p.hop_length, plan->p.n_fft, Lw)) return MelBwdLayout{};
+  return mel_bwd_layout_frames(plan, B, loop_samples_frames(plan->p.hop_length, plan->p.n_fft, Lw), true);
+}
+size_t rfx_spectral_loss_backward_workspace_bytes(const rfx_plan* plan, int B, int Lw) {
+  return plan ? spectral_loss_backward_layout(plan, B, Lw, false).total : 0;
+}
+size_t rfx_spectral_loss_backward_loop_workspace_bytes(const rfx_plan* plan, int B, int Lw) {
+  return plan ? spectral_loss_backward_layout(plan, B, Lw, true).total : 0;
+}
+
+static int spectral_loss_backward_run(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, const float* d_coef, int B, int Lw,
+                                      float log_floor, float* d_grad_wave, void* d_workspace, size_t workspace_bytes, void* stream_, bool loop) {
+  const std::string w = loop ? "rfx_spectral_loss_backward_loop" : "rfx_spectral_loss_backward";
+  if (B < 0) return fail(RFX_ERR_INVALID, w + ": B is negative");
+  if (B == 0) return RFX_OK;
+  if (!plan || !d_wave || !d_mag_slots || !d_coef || !d_grad_wave || !d_workspace) return fail(RFX_ERR_INVALID, w + ": null argument");
+  if (loop) {
+    if (int rc = loop_length_refusal(plan, Lw, w.c_str())) return rc;
+  } else if (Lw <= plan->p.n_fft / 2) {
+    return fail(RFX_ERR_INVALID, w + ": reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
+  }
+  if (!spec_loss_floor_ok(log_floor))
+    return fail(RFX_ERR_INVALID, w + ": log_floor must be 0 (no log term) or a finite value of at least 1e-18, got " + std::to_string(log_floor));
+  if (((uintptr_t)d_workspace | (uintptr_t)d_mag_slots) & 15 || ((uintptr_t)d_grad_wave | (uintptr_t)d_wave | (uintptr_t)d_coef) & 3)
+    return fail(RFX_ERR_INVALID, w + ": d_workspace and d_mag_slots must be 16-byte aligned, the other float tensors 4-byte aligned");
+  if ((plan->mb_sstride & 3) || (plan->frame_stride & 3)) return fail(RFX_ERR_UNSUPPORTED, w + ": the plan's frame strides are not multiples of four");
+  const MelBwdLayout l = spectral_loss_backward_layout(plan, B, Lw, loop);
+  if (workspace_bytes < l.total)
+    return fail(RFX_ERR_WORKSPACE, w + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(l.total) + " needed)");
+  RFX_ON_DEVICE(plan->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const int T = l.T;
+  cf* spec = reinterpret_cast<cf*>((char*)d_workspace + l.spec);
+  float* smag = reinterpret_cast<float*>((char*)d_workspace + l.smag);
+  float* frames = reinterpret_cast<float*>((char*)d_workspace + l.frames);
+  const size_t row_slots = (size_t)T * plan->frame_stride;
+  for (int r0 = 0; r0 < B; r0 += l.group_rows) {
+    const int rows = B - r0 < l.group_rows ? B - r0 : l.group_rows;
+    if (int rc = (loop ? rfx_stft_loop : rfx_stft)(plan, d_wave + (size_t)r0 * Lw, rows, Lw, nullptr, spec, stream_)) return rc;
+    SpecLossSlotArgs a{};
+    a.X = spec;
+    a.target = d_mag_slots + (size_t)r0 * row_slots;
+    a.coef = d_coef + 2 * (size_t)r0;
+    a.S = smag;
+    a.pos_bin = plan->d_mb_pos_bin;
+    a.s2x = plan->d_mb_s2x;
+    a.B = rows;
+    a.T = T;
+    a.n_fft = plan->p.n_fft;
+    a.xstride = plan->frame_stride;
+    a.sstride = plan->mb_sstride;
+    a.target_by_bin = plan->generic;
+    a.unit = mel_bwd_unit(plan->p.n_fft, !plan->generic);
+    a.floor = log_floor;
+    RFX_HIP(launch_spec_loss_slots(a, stream));
+    if (int rc = mel_bwd_frames(plan, smag, spec, frames, rows, T, stream)) return rc;
+    MelBwdFoldArgs f{};
+    f.frames = frames;
+    f.win = plan->generic ? nullptr : plan->d_win;
+    f.out = d_grad_wave + (size_t)r0 * Lw;
+    f.fpitch = (int)mel_bwd_frame_pitch(plan);
+    f.fshift = plan->generic ? plan->gg.fshift : 0;
+    f.left = (plan->p.n_fft - plan->p.win_length) / 2;
+    f.win_len = plan->p.win_length;
+    f.hop = plan->p.hop_length;
+    f.h = plan->p.n_fft / 2;
+    f.B = rows;
+    f.T = T;
+    f.Lw = Lw;
+    RFX_HIP(loop ? launch_spec_loss_loop_fold(f, stream) : launch_mel_bwd_fold(f, stream));
+  }
+  return RFX_OK;
+}
+int rfx_spectral_loss_backward(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, const float* d_coef, int B, int Lw, float log_floor,
+                               float* d_grad_wave, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return spectral_loss_backward_run(plan, d_wave, d_mag_slots, d_coef, B, Lw, log_floor, d_grad_wave, d_workspace, workspace_bytes, stream, false);
+}
+int rfx_spectral_loss_backward_loop(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, const float* d_coef, int B, int Lw,
+                                    float log_floor, float* d_grad_wave, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return spectral_loss_backward_run(plan, d_wave, d_mag_slots, d_coef, B, Lw, log_floor, d_grad_wave, d_workspace, workspace_bytes, stream, true);
 }

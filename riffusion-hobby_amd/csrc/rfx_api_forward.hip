@@ -3,6 +3,7 @@
 // the kernels.
 #include "rfx_api.h"
 #include "rfx_loop_core.h"
+#include "rfx_spec_loss_core.h"
 
 using namespace rfx;
 
@@ -520,4 +521,70 @@ int rfx_spectral_error(const rfx_plan* plan, const float* d_wave, const float* d
 int rfx_spectral_error_loop(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out,
                             void* d_workspace, size_t workspace_bytes, void* stream) {
   return spectral_error_run(plan, d_wave, d_mag_slots, B, T, d_sums_out, d_workspace, workspace_bytes, stream, true);
+}
+
+// ---- fused spectral losses, forward: the three sums of rfx_spec_loss_core.h ----------------------------------------------------------
+// rfx_spectral_error's sequence on rows of any legal length Lw: the plan's forward transform of a group of rows into the workspace,
+// then the reduction with the third sum.  Groups of whole rows of at most kQualGroupBytes of magnitudes, as above.
+int rfx::loop_length_refusal(const rfx_plan* plan, int Lw, const char* who) {
+  return loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who);
+}
+struct SpectralLossLayout {
+  size_t mag, partials, total;
+  int group_rows, T;
+};
+static SpectralLossLayout spectral_loss_layout(const rfx_plan* plan, int B, int Lw, bool loop) {
+  SpectralLossLayout l{};
+  if (B <= 0 || !fwd_length_ok(plan, Lw, loop)) return l;
+  l.T = fwd_frames(plan, Lw, loop);
+  const size_t row_bytes = (size_t)l.T * plan->frame_stride * sizeof(float);
+  size_t rows = kQualGroupBytes / row_bytes;
+  rows = rows < 1 ? 1 : rows > (size_t)B ? (size_t)B : rows;
+  l.group_rows = (int)rows;
+  Carve c;
+  l.mag = c.take(rows * row_bytes);
+  l.partials = c.take(spec_loss_partials_bytes(l.group_rows, l.T));
+  l.total = c.at;
+  return l;
+}
+size_t rfx_spectral_loss_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? spectral_loss_layout(plan, B, Lw, false).total : 0; }
+size_t rfx_spectral_loss_loop_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? spectral_loss_layout(plan, B, Lw, true).total : 0; }
+
+static int spectral_loss_run(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor, double* d_sums_out,
+                             void* d_workspace, size_t workspace_bytes, void* stream, bool loop) {
+  const std::string who = loop ? "rfx_spectral_loss_loop" : "rfx_spectral_loss";
+  if (B < 0) return fail(RFX_ERR_INVALID, who + ": B is negative");
+  if (B == 0) return RFX_OK;
+  if (!plan || !d_wave || !d_mag_slots || !d_sums_out || !d_workspace) return fail(RFX_ERR_INVALID, who + ": null argument");
+  if (loop) {
+    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who.c_str())) return rc;
+  } else if (Lw <= plan->p.n_fft / 2) {
+    return fail(RFX_ERR_INVALID, who + ": reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
+  }
+  if (!spec_loss_floor_ok(log_floor))
+    return fail(RFX_ERR_INVALID, who + ": log_floor must be 0 (no log term) or a finite value of at least 1e-18, got " + std::to_string(log_floor));
+  if (((uintptr_t)d_mag_slots | (uintptr_t)d_workspace) & 15 || ((uintptr_t)d_sums_out & 7) || ((uintptr_t)d_wave & 3) || (plan->frame_stride & 3))
+    return fail(RFX_ERR_INVALID, who + ": d_mag_slots and d_workspace must be 16-byte aligned, d_sums_out 8-byte and d_wave 4-byte aligned");
+  const SpectralLossLayout w = spectral_loss_layout(plan, B, Lw, loop);
+  if (workspace_bytes < w.total)
+    return fail(RFX_ERR_WORKSPACE, who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(w.total) + " needed)");
+  RFX_ON_DEVICE(plan->device);
+  float* mag = reinterpret_cast<float*>((char*)d_workspace + w.mag);
+  void* partials = (char*)d_workspace + w.partials;
+  const size_t row_elems = (size_t)w.T * plan->frame_stride;
+  for (int r0 = 0; r0 < B; r0 += w.group_rows) {
+    const int rows = B - r0 < w.group_rows ? B - r0 : w.group_rows;
+    if (int rc = stft_run(plan, d_wave + (size_t)r0 * Lw, rows, Lw, mag, nullptr, stream, loop)) return rc;
+    RFX_HIP(launch_spec_loss_sums(mag, d_mag_slots + (size_t)r0 * row_elems, rows, w.T, plan->frame_stride, plan->n_stft, plan->generic, log_floor,
+                                  partials, d_sums_out + 3 * (size_t)r0, (hipStream_t)stream));
+  }
+  return RFX_OK;
+}
+int rfx_spectral_loss(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor, double* d_sums_out,
+                      void* d_workspace, size_t workspace_bytes, void* stream) {
+  return spectral_loss_run(plan, d_wave, d_mag_slots, B, Lw, log_floor, d_sums_out, d_workspace, workspace_bytes, stream, false);
+}
+int rfx_spectral_loss_loop(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor, double* d_sums_out,
+                           void* d_workspace, size_t workspace_bytes, void* stream) {
+  return spectral_loss_run(plan, d_wave, d_mag_slots, B, Lw, log_floor, d_sums_out, d_workspace, workspace_bytes, stream, true);
 }

@@ -613,4 +613,31 @@ struct MelBwdFoldArgs {
 };
 hipError_t launch_mel_bwd_fold(const MelBwdFoldArgs& a, hipStream_t stream);
 
+// fused spectral losses (arithmetic in rfx_spec_loss_core.h).  launch_spec_loss_sums (rfx_quality.hip): launch_spectral_sums with a
+// third sum, sums[3 r + 2] = sum | ln max(a, floor) - ln max(m, floor) | (floor == 0: no logarithm, 0); the first two are
+// launch_spectral_sums' bit for bit; partials: spec_loss_partials_bytes.
+size_t spec_loss_partials_bytes(int rows, int T);
+hipError_t launch_spec_loss_sums(const float* a, const float* m, int rows, int T, int fs, int n_stft, bool plain, float floor, void* partials, double* sums,
+                                 hipStream_t s);
+// launch_spec_loss_slots (rfx_mel_bwd.hip): the magnitude slots S [B*T][sstride] of a MODE 0 frame launch that takes the spectrum
+// X [B*T][xstride] itself as its angles - weight[k] (dL/da) / a per slot, from a = |the complex value the slot will multiply|, the
+// target's slot and the row's coefficients coef[2 b] = c_sc, coef[2 b + 1] = c_lg.  target: [B*T][xstride] in the plan's magnitude
+// layout (what rfx_pack_magnitudes writes): read at the slot's own position on the specialised engine, at the slot's bin
+// (target_by_bin) on the plain layouts.  sstride a multiple of four, xstride even; S, X and target 16-byte aligned.
+struct SpecLossSlotArgs {
+  const cf* X;
+  const float* target;
+  const float* coef;
+  float* S;
+  const int* pos_bin;  // [sstride] bin of each magnitude slot, -1 for padding
+  const int* s2x;      // [sstride] position of X the slot goes with
+  int B, T, n_fft, xstride, sstride;
+  bool target_by_bin;
+  float unit;   // mel_bwd_unit
+  float floor;  // 0: no log term
+};
+hipError_t launch_spec_loss_slots(const SpecLossSlotArgs& a, hipStream_t stream);
+// the circular adjoint fold of a loop row: MelBwdFoldArgs with Lw = hop T; no reflect partners, the chain of rfx_loop_core.h
+hipError_t launch_spec_loss_loop_fold(const MelBwdFoldArgs& a, hipStream_t stream);
+
 }  // namespace rfx

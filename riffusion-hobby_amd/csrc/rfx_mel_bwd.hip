@@ -15,6 +15,7 @@
 
 #include "rfx_kernels.h"
 #include "rfx_mel_bwd_core.h"
+#include "rfx_spec_loss_core.h"
 
 namespace rfx {
 
@@ -117,6 +118,110 @@ __global__ void __launch_bounds__(256) mel_bwd_fold_kernel(MelBwdFoldArgs a) {
     return;
   }
   for (int j = j0; j < j0 + 4 && j < a.Lw; ++j) out[j] = mel_bwd_sample<float>(j, a.h, a.Lw, gp);
+}
+
+// ---- fused spectral losses (rfx_spec_loss_core.h; include/rfx.h: rfx_spectral_loss_backward) ------------------------------------------
+// The second magnitude-slot kernel: mel_bwd_spec_kernel's structure with a per-bin loss in the place of the bank adjoint.  One frame per
+// trip.  Phase 1 has nothing to stage (no incoming-gradient column).  Phase 2: the spectrum, 16 bytes (two complex values) per lane in
+// the order it lies in memory; a[x] = |X[x]| of position x goes to LDS (every position has one writer).  Phase 3: the magnitude slots,
+// 16 bytes per lane: slot p takes a[s2x[p]] - the magnitude of the very complex value the frame launch will multiply it by - the
+// target's slot and the row's two coefficients, and writes weight[k] (dL/da) / a (padding: 0).  BY_BIN: the target lies bin-ordered
+// (plain layouts) and is read at the slot's bin; else it lies in the slots' own order and is read 16 bytes at a time.
+template <bool BY_BIN>
+__global__ void __launch_bounds__(kMelBwdThreads) spec_loss_slots_kernel(SpecLossSlotArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sl_lds[];
+  float* __restrict__ u = sl_lds;  // [xstride]
+  const long long nframes = (long long)a.B * a.T;
+  const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
+  for (long long fr = blockIdx.x; fr < nframes; fr += gridDim.x) {
+    const long long b = fr / a.T;
+    const float c_sc = a.coef[2 * b], c_lg = a.coef[2 * b + 1];
+    const float4* __restrict__ X4 = reinterpret_cast<const float4*>(a.X + (size_t)fr * a.xstride);
+    float2* __restrict__ u2 = reinterpret_cast<float2*>(u);
+    for (int i = tid; i < a.xstride / 2; i += nthr) {
+      const float4 v = X4[i];
+      u2[i] = float2{spec_loss_abs(v.x, v.y), spec_loss_abs(v.z, v.w)};
+    }
+    __syncthreads();
+    const float* __restrict__ M = a.target + (size_t)fr * a.xstride;
+    float4* __restrict__ S4 = reinterpret_cast<float4*>(a.S + (size_t)fr * a.sstride);
+    const int4* __restrict__ pb4 = reinterpret_cast<const int4*>(a.pos_bin);
+    const int4* __restrict__ sx4 = reinterpret_cast<const int4*>(a.s2x);
+    auto slot = [&](int k, int x, float m) {
+      return k < 0 || x < 0 ? 0.f : mel_bwd_bin_weight(k, a.n_fft, a.unit) * spec_loss_unit_scale(u[x], m, c_sc, c_lg, a.floor);
+    };
+    for (int i = tid; i < a.sstride / 4; i += nthr) {
+      const int4 k = pb4[i], x = sx4[i];
+      float4 m;
+      if (BY_BIN) m = float4{k.x < 0 ? 0.f : M[k.x], k.y < 0 ? 0.f : M[k.y], k.z < 0 ? 0.f : M[k.z], k.w < 0 ? 0.f : M[k.w]};
+      else m = reinterpret_cast<const float4*>(M)[i];
+      S4[i] = float4{slot(k.x, x.x, m.x), slot(k.y, x.y, m.y), slot(k.z, x.z, m.z), slot(k.w, x.w, m.w)};
+    }
+    __syncthreads();  // the next trip rewrites u
+  }
+}
+
+// The circular adjoint fold.  A thread folds the samples m0 .. m0 + 3 of row b, one chain each (spec_loss_loop_sample): an fma chain
+// y w + acc over un-windowed frames (a.win: specialised engine), a chain of sums over frames the launch has windowed.  VEC (windowed
+// frames; the host has checked the plain fold's conditions - fpitch, hop and h - left + fshift multiples of four, frames and out
+// 16-byte aligned; Lw = hop T is then a multiple of four too): the four samples share the frames from the oldest of the first to the
+// newest of the last and read each 16 bytes at a time - a sample outside a frame's window reads the zero padding of the frame's row
+// (x + 0 = x: the scalar sums, term for term).
+template <bool VEC>
+__global__ void __launch_bounds__(256) spec_loss_loop_fold_kernel(MelBwdFoldArgs a) {
+  using v4 = float __attribute__((ext_vector_type(4)));
+  const int m0 = 4 * (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const size_t b = blockIdx.y;
+  if (m0 >= a.Lw) return;
+  const float* __restrict__ rows = a.frames + b * a.T * (size_t)a.fpitch;
+  float* __restrict__ out = a.out + b * (size_t)a.Lw;
+  if (VEC) {
+    const int q = m0 + a.h - a.left;
+    int tlo, thi, tmp;
+    loop_fold_range(q, a.win_len, a.hop, tlo, tmp);
+    loop_fold_range(q + 3, a.win_len, a.hop, tmp, thi);
+    v4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int t = tlo; t <= thi; ++t)
+      acc += *reinterpret_cast<const v4*>(rows + (size_t)loop_frame(t, a.T) * a.fpitch + a.fshift + (q - a.hop * t));
+    *reinterpret_cast<v4*>(out + m0) = acc;
+    return;
+  }
+  for (int m = m0; m < m0 + 4 && m < a.Lw; ++m)
+    out[m] = spec_loss_loop_sample(rows, (size_t)a.fpitch, a.fshift, a.win, m, a.h, a.left, a.win_len, a.hop, a.T);
+}
+
+hipError_t launch_spec_loss_slots(const SpecLossSlotArgs& a, hipStream_t stream) {
+  const long long nframes = (long long)a.B * a.T;
+  if (nframes <= 0) return hipSuccess;
+  const size_t lds = sizeof(float) * (size_t)a.xstride;
+  const void* fn = a.target_by_bin ? (const void*)spec_loss_slots_kernel<true> : (const void*)spec_loss_slots_kernel<false>;
+  if (lds > 48u * 1024u) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const long long cap = 1 << 16;
+  const dim3 grid((unsigned)(nframes < cap ? nframes : cap));
+  if (a.target_by_bin) hipLaunchKernelGGL(spec_loss_slots_kernel<true>, grid, dim3(kMelBwdThreads), lds, stream, a);
+  else hipLaunchKernelGGL(spec_loss_slots_kernel<false>, grid, dim3(kMelBwdThreads), lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_spec_loss_loop_fold(const MelBwdFoldArgs& a, hipStream_t stream) {
+  if (a.B <= 0 || a.Lw <= 0) return hipSuccess;
+  const bool vec = !a.win && a.fpitch % 4 == 0 && a.hop % 4 == 0 && (a.h - a.left + a.fshift) % 4 == 0 &&
+                   (reinterpret_cast<uintptr_t>(a.frames) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
+  const unsigned gx = (unsigned)(((a.Lw + 3) / 4 + 255) / 256);
+  for (int b0 = 0; b0 < a.B; b0 += 65535) {  // blockIdx.y carries the row
+    MelBwdFoldArgs c = a;
+    c.B = a.B - b0 < 65535 ? a.B - b0 : 65535;
+    c.frames = a.frames + (size_t)b0 * a.T * a.fpitch;
+    c.out = a.out + (size_t)b0 * a.Lw;
+    if (vec) hipLaunchKernelGGL(spec_loss_loop_fold_kernel<true>, dim3(gx, c.B), dim3(256), 0, stream, c);
+    else hipLaunchKernelGGL(spec_loss_loop_fold_kernel<false>, dim3(gx, c.B), dim3(256), 0, stream, c);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_mel_bwd_spec(const MelBwdSpecArgs& a, hipStream_t stream) {

@@ -7,6 +7,10 @@ Three `torch.autograd.Function`s over a `_hip.Plan`.  Each forward makes the cal
 bytes - and saves the least it can: the fused function saves the waveform only (the backward re-analyses it; a kept spectrum
 would be 2.3 GB at 64 stereo tiles).  The backwards are `once_differentiable`: a double backward raises.
 The inverse members (InverseMelScale's SGD, Griffin-Lim) and the loop encode have no backward.
+
+A fourth function, `SpectralLossFunction`, is the pair of the multi-resolution STFT loss - spectral convergence and log-magnitude L1 -
+fused with the transform (include/rfx.h, "FUSED SPECTRAL LOSSES"): the forward leaves three double sums per row, the backward is the
+fused backward with another per-bin factor.  It serves the circular STFT too: the loop STFT's only backward.
 """
 import typing as T
 
@@ -64,6 +68,59 @@ class MelFromWaveformFunction(torch.autograd.Function):
     def backward(ctx: T.Any, grad: torch.Tensor) -> T.Tuple[None, torch.Tensor]:  # type: ignore[override]
         (wave,) = ctx.saved_tensors
         return None, ctx.plan.mel_from_waveform_backward(wave, grad)
+
+
+def convergence_from_sums(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """`SpectrogramConverter.convergence_from_sums` (the converter module imports this one)"""
+    from riffusion.spectrogram_converter import SpectrogramConverter
+
+    return SpectrogramConverter.convergence_from_sums(num, den)
+
+
+def loss_coefficients(sums: torch.Tensor, n: int, g_sc: torch.Tensor, g_lg: torch.Tensor, log_floor: float) -> torch.Tensor:
+    """the (B, 2) float32 coefficients rfx_spectral_loss_backward takes, from the saved sums and the incoming gradients, with torch
+    operations on the sums' device (nothing is read back): c_sc = g_sc / sqrt(num den) where num > 0 and den > 0, else 0 - the zero
+    subgradient torch.linalg.vector_norm gives at 0, and no gradient against a silent target - and c_lg = g_lg / n (0 without a floor)"""
+    num, den = sums[:, 0], sums[:, 1]
+    live = (num > 0) & (den > 0)
+    root = torch.sqrt(torch.where(live, num * den, torch.ones_like(num)))
+    c_sc = torch.where(live, g_sc.to(torch.float64) / root, torch.zeros_like(num))
+    c_lg = g_lg.to(torch.float64) / n if log_floor > 0 else torch.zeros_like(num)
+    return torch.stack([c_sc, c_lg], dim=1).to(torch.float32)
+
+
+class SpectralLossFunction(torch.autograd.Function):
+    """(B, Lw) float32 waveform, target magnitude slots -> (convergence, log_magnitude), each (B,) float64 (include/rfx.h, "FUSED
+    SPECTRAL LOSSES").  Saves the waveform and the (B, 3) sums and keeps a reference to the target slots; the backward forms the
+    per-row coefficients on the device and calls rfx_spectral_loss_backward, which re-analyses the waveform.  The target gets no
+    gradient: one that requires grad raises."""
+
+    @staticmethod
+    def forward(ctx: T.Any, plan: T.Any, wave: torch.Tensor, slots: torch.Tensor, log_floor: float, loop: bool,  # type: ignore[override]
+                n: int) -> T.Tuple[torch.Tensor, torch.Tensor]:
+        sums = plan.spectral_loss_sums(wave, slots, log_floor, loop)
+        ctx.plan, ctx.slots, ctx.log_floor, ctx.loop, ctx.n = plan, slots, log_floor, loop, n
+        ctx.save_for_backward(wave, sums)
+        return convergence_from_sums(sums[:, 0], sums[:, 1]), sums[:, 2] / n
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: T.Any, g_sc: torch.Tensor, g_lg: torch.Tensor):  # type: ignore[override]
+        wave, sums = ctx.saved_tensors
+        coef = loss_coefficients(sums, ctx.n, g_sc, g_lg, ctx.log_floor)
+        return None, ctx.plan.spectral_loss_backward(wave, ctx.slots, coef, ctx.log_floor, ctx.loop), None, None, None, None
+
+
+def spectral_losses(plan: T.Any, wave: torch.Tensor, slots: torch.Tensor, log_floor: float, loop: bool) -> T.Tuple[torch.Tensor, torch.Tensor]:
+    """(convergence, log_magnitude) of (B, Lw) `wave` against the target `slots`; log_floor 0.0: no log term (log_magnitude is all
+    zero).  With a waveform that requires grad the pair carries a grad_fn; otherwise the forward call alone, nothing saved."""
+    if isinstance(slots, torch.Tensor) and slots.requires_grad:
+        raise RuntimeError("spectral_losses: the target receives no gradient; detach it")
+    n = plan.n_stft * plan._forward_frames(int(wave.shape[-1]), wave.shape, loop)
+    if wants_grad(wave):
+        return SpectralLossFunction.apply(plan, wave, slots, log_floor, loop, n)
+    sums = plan.spectral_loss_sums(wave.detach(), slots, log_floor, loop)
+    return convergence_from_sums(sums[:, 0], sums[:, 1]), sums[:, 2] / n
 
 
 def stft(plan: T.Any, wave: torch.Tensor) -> torch.Tensor:

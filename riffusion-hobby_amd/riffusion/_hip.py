@@ -263,6 +263,19 @@ def loop_nearest_samples(hop_length: int, n_fft: int, samples: int) -> T.Tuple[i
     return int(below.value), int(above.value)
 
 
+def spectral_loss_floor(log_floor: T.Optional[float]) -> float:
+    """the log floor as the library takes it: None or 0 -> 0.0 ("no log term"), else the float32 nearest to it; ValueError for what
+    the library refuses - a negative or non-finite floor, or one below 1e-18 (1 / floor^2 must fit float32 in the backward)"""
+    if log_floor is None:
+        return 0.0
+    f = float(np.float32(log_floor))
+    if f == 0.0 and float(log_floor) == 0.0:
+        return 0.0
+    if not (np.isfinite(f) and f >= float(np.float32(1e-18))):
+        raise ValueError(f"log_floor must be None, 0 or a finite value of at least 1e-18, got {log_floor!r}")
+    return f
+
+
 def check_inverse_mel(inverse_mel: str) -> bool:
     """True for "lstsq", False for "sgd"; anything else raises."""
     if inverse_mel not in INVERSE_MEL_FORMS:
@@ -392,6 +405,17 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_mel_from_waveform_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_mel_from_waveform_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_debug_mel_adjoint": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int32)]),
+    # fused spectral losses (riffusion/_autograd.py: SpectralLossFunction)
+    "rfx_spectral_loss_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_spectral_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_spectral_loss_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_spectral_loss_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_spectral_loss_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_spectral_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
+    "rfx_spectral_loss_backward_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_spectral_loss_backward_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t,
+                                                c_void_p]),
     "rfx_inverse_mel_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_inverse_mel": (
         c_int,
@@ -1110,6 +1134,52 @@ class Plan:
         with self._workspace(self.lib.rfx_mel_from_waveform_backward_workspace_bytes(self.handle, B, Lw)) as ws:
             check(self.lib.rfx_mel_from_waveform_backward(self.handle, wave.data_ptr(), g.data_ptr(), B, Lw, out.data_ptr(), ws.data_ptr(),
                                                           ws.numel(), self._stream()))
+        return out
+
+    # ---- fused spectral losses (include/rfx.h "FUSED SPECTRAL LOSSES"; riffusion/_autograd.py: SpectralLossFunction) ----
+    def _loss_args(self, wave: torch.Tensor, mag_slots: torch.Tensor, loop: bool) -> T.Tuple[torch.Tensor, torch.Tensor, int, int, int]:
+        wave = self._chk(wave, torch.float32)
+        mag_slots = self._chk(mag_slots, torch.float32)
+        B, Lw = wave.shape
+        Tn = self._forward_frames(Lw, wave.shape, loop)
+        if mag_slots.numel() != B * Tn * self.frame_stride:
+            raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames are {B * Tn * self.frame_stride}")
+        return wave, mag_slots, B, Lw, Tn
+
+    def spectral_loss_sums(self, wave: torch.Tensor, mag_slots: torch.Tensor, log_floor: float = 0.0, loop: bool = False) -> torch.Tensor:
+        """rfx_spectral_loss: (B, Lw) waveforms against target magnitudes in slot layout (`pack_magnitudes`) -> (B, 3) float64, per row
+        sum (|STFT(wave)| - mag)^2, sum mag^2 and sum |ln max(|STFT(wave)|, log_floor) - ln max(mag, log_floor)| over every bin of
+        every frame once; the first two are `spectral_error`'s bits.  log_floor 0: no log term, the third sum is 0.
+        loop (rfx_spectral_loss_loop): the rows are whole periods of hop * T samples and the STFT is the circular one."""
+        wave, mag_slots, B, Lw, _ = self._loss_args(wave, mag_slots, loop)
+        f = spectral_loss_floor(log_floor)
+        sums = torch.empty((B, 3), dtype=torch.float64, device=self.device)
+        if B == 0:
+            return sums
+        query, entry = ((self.lib.rfx_spectral_loss_loop_workspace_bytes, self.lib.rfx_spectral_loss_loop) if loop
+                        else (self.lib.rfx_spectral_loss_workspace_bytes, self.lib.rfx_spectral_loss))
+        with self._workspace(max(1, query(self.handle, B, Lw))) as ws:
+            check(entry(self.handle, wave.data_ptr(), mag_slots.data_ptr(), B, Lw, f, sums.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return sums
+
+    def spectral_loss_backward(self, wave: torch.Tensor, mag_slots: torch.Tensor, coef: torch.Tensor, log_floor: float = 0.0,
+                               loop: bool = False) -> torch.Tensor:
+        """rfx_spectral_loss_backward: the waveform and target of `spectral_loss_sums` and the (B, 2) float32 coefficients
+        (c_sc, c_lg) of the rows -> the (B, Lw) float32 gradient of the waveform.  The spectrum is formed again in the workspace.
+        loop (rfx_spectral_loss_backward_loop): the circular STFT's backward."""
+        wave, mag_slots, B, Lw, _ = self._loss_args(wave, mag_slots, loop)
+        coef = self._chk(coef, torch.float32)
+        if tuple(coef.shape) != (B, 2):
+            raise ValueError(f"expected ({B}, 2) coefficients, got {tuple(coef.shape)}")
+        f = spectral_loss_floor(log_floor)
+        out = torch.empty((B, Lw), dtype=torch.float32, device=self.device)
+        if B == 0:
+            return out
+        query, entry = ((self.lib.rfx_spectral_loss_backward_loop_workspace_bytes, self.lib.rfx_spectral_loss_backward_loop) if loop
+                        else (self.lib.rfx_spectral_loss_backward_workspace_bytes, self.lib.rfx_spectral_loss_backward))
+        with self._workspace(max(1, query(self.handle, B, Lw))) as ws:
+            check(entry(self.handle, wave.data_ptr(), mag_slots.data_ptr(), coef.data_ptr(), B, Lw, f, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                        self._stream()))
         return out
 
     def inverse_mel(

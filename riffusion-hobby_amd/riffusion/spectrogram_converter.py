@@ -14,7 +14,8 @@ builds (:47-99) are replaced by callables that run hand-written HIP kernels thro
 The two torch-level methods fuse these pairs so the (B, n_stft, T) intermediates of the reference are
 never materialised; the standalone callables exist for code that pokes at the members directly.
 The three forward members are differentiable, as the reference's are: with an input that requires grad they route through
-riffusion/_autograd.py and the gradient runs on the device; the inverse members and the loop encode are not.
+riffusion/_autograd.py and the gradient runs on the device; the inverse members and the loop encode are not.  `spectral_losses`
+(not in the reference) is the spectral convergence / log-magnitude L1 pair fused with the transform, forward and backward, plain and loop.
 Every call is re-entrant: the converter holds immutable constants only (plans are cached per
 (params, device)), workspaces are checked out of the plan's arena per call (`_hip.WorkspaceArena`: two
 threads never share one) - the reference shares one converter across a thread pool (cli.py:172-204).  There is no CPU implementation: on a machine without a GPU the constructor still
@@ -85,6 +86,13 @@ CALL_WORDING = {
     "bins_need_guide": "hold_mask needs a guide: the bins are held at the guide's phase",
     "bins_and_hold": "hold_frames together with hold_mask is not served: set the held frames' columns in the mask",
 }
+
+
+class SpectralLosses(T.NamedTuple):
+    """what `SpectrogramConverter.spectral_losses` returns: (B,) float64 each; `log_magnitude` is None without a log floor"""
+
+    convergence: torch.Tensor
+    log_magnitude: T.Optional[torch.Tensor]
 
 
 class LoopLengthError(ValueError):
@@ -380,3 +388,42 @@ class SpectrogramConverter:
         B, _, Tn = mag.shape
         sums = plan.spectral_error(waveform.to(self.device), plan.pack_magnitudes(mag), B, Tn, loop=loop)
         return self.convergence_from_sums(sums[:, 0], sums[:, 1])
+
+    # ---- spectral losses for training through the codec ---------------------------------------------
+    def spectral_losses(self, waveform: torch.Tensor, magnitudes: T.Optional[torch.Tensor] = None, *,
+                        magnitude_slots: T.Optional[torch.Tensor] = None, log_floor: T.Optional[float] = None,
+                        loop: bool = False) -> SpectralLosses:
+        """
+        The pair of the multi-resolution STFT loss at this converter's parameters, fused with the transform on the device:
+        `convergence` = || |STFT(waveform)| - M || / || M || and `log_magnitude` = mean | ln max(|STFT(waveform)|, log_floor) -
+        ln max(M, log_floor) |, per row: (B, Lw) float32 waveforms -> a named pair of (B,) float64 tensors.  `log_magnitude` is None
+        when `log_floor` is None.  The target M is `magnitudes`, (B, n_stft, T) float32 in the reference's layout, or
+        `magnitude_slots`, what `plan.pack_magnitudes` returns for it - a training loop packs its constant target once.  It
+        receives no gradient: a target that requires grad raises.
+        With grad mode on and a waveform that requires grad the pair carries a grad_fn whose backward runs on the device
+        (rfx_spectral_loss_backward: the waveform and three sums per row are saved, the spectrum is formed again; the
+        (B, n_stft, T) tensor is never written).  Otherwise the forward call alone runs and nothing is saved.  `convergence` is
+        `spectral_convergence`'s value bit for bit where that member takes the length.  A multi-resolution loss is the sum of this
+        pair over several converters with different parameters.
+        `loop`: the rows are whole periods of exactly hop * T samples (`check_loop_samples`) and the STFT is the circular one; this
+        is the loop STFT's backward (`mel_amplitudes_from_waveform(loop=True)` has none).
+        """
+        from riffusion import _hip
+
+        if (magnitudes is None) == (magnitude_slots is None):
+            raise ValueError("spectral_losses takes the target once: magnitudes (B, n_stft, T) or magnitude_slots")
+        target = magnitudes if magnitudes is not None else magnitude_slots
+        if isinstance(target, torch.Tensor) and target.requires_grad:
+            raise RuntimeError("spectral_losses: the target receives no gradient; detach it")
+        if waveform.dim() != 2:
+            raise ValueError(f"spectral_losses takes (B, samples) waveforms, got {tuple(waveform.shape)}")
+        f = _hip.spectral_loss_floor(log_floor)
+        if log_floor is not None and f == 0.0:
+            raise ValueError("log_floor=0 leaves ln 0 in reach; pass None for no log term or a positive floor")
+        if loop:
+            self.check_loop_samples(int(waveform.shape[-1]))
+        plan = self._plan()
+        slots = plan.pack_magnitudes(magnitudes.to(self.device)) if magnitudes is not None else magnitude_slots.to(self.device)
+        w = waveform.to(self.device)
+        sc, lg = _autograd.spectral_losses(plan, w.to(torch.float32) if _autograd.wants_grad(w) else w, slots, f, loop)
+        return SpectralLosses(sc, lg if log_floor is not None else None)

@@ -1,0 +1,180 @@
+"""
+The fused spectral losses on the device: what a step of the loss pair costs, in time and in memory, next to the same loss composed from
+the differentiable members and torch operations, and next to the mel-domain forward + backward.
+
+    python tools/probe_spectral_loss.py [--runs 9] [--calls 3] [--batch 64] [--out profiles/spectral_loss.txt]     (on the GPU)
+
+64 mono clips of 5.11 s (225 351 samples, 512 frames each at the default parameters), forward + backward of
+sum_b convergence[b] + log_magnitude[b] against a constant target:
+  (a) fused     `SpectrogramConverter.spectral_losses(w, magnitude_slots=..., log_floor=f)`; the target is packed once, outside the step;
+  (b) composed  the same pair from `spectrogram_func(w).abs()` and torch operations (vector_norm, clamp, log, abs, mean), float32 as
+                torch would run it; the target's norm and its clamped logarithm are formed once, outside the step.  This runs on the
+                parent commit as well: it is the baseline;
+  (c) mel       `mel_amplitudes_from_waveform(w)` and the backward of 0.5 ||mel - target||^2, for scale.
+A sample is --calls steps back to back between two events; median of --runs samples after a warm-up of all three, the three alternating.
+Memory: torch.cuda.max_memory_allocated over one step, above what is allocated before it (waveform, target, constants).
+Then, at the shapes of tests/test_gpu_spectral_loss.py, the end-to-end figures of the gradient of each term against float64 autograd
+through the oracle's STFT - the log term's are recorded here and not gated (its 1 / a weighting makes them a property of the forward
+transform).  No ratio is fixed in advance.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for sub in ("riffusion-hobby_amd", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, sub))
+
+SEED, SAMPLES = 7, 225351
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=9)
+    ap.add_argument("--calls", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spectral_loss.txt"))
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+
+    from riffusion.spectrogram_converter import SpectrogramConverter
+    from riffusion.spectrogram_params import SpectrogramParams
+
+    assert torch.cuda.is_available(), "this probe measures on the GPU"
+
+    def event_ms(fn) -> float:
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(args.calls):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / args.calls
+
+    p = SpectrogramParams()
+    conv = SpectrogramConverter(p, device="cuda")
+    plan = conv._plan()
+    B = args.batch
+    rng = np.random.default_rng(SEED)
+    wave = torch.from_numpy((rng.standard_normal((B, SAMPLES)) * 8000).astype(np.float32)).cuda()
+    with torch.no_grad():
+        mag_slots, _, Tn = plan.stft(wave, want_mag=True, want_spec=False)
+        target = plan.unpack_magnitudes(mag_slots, B, Tn)
+        del mag_slots
+        target *= 0.5 + 1.5 * torch.rand(target.shape, generator=torch.Generator(device="cuda").manual_seed(SEED), device="cuda")
+        floor = float(np.float32(0.1 * float(target.median())))
+        slots = plan.pack_magnitudes(target)
+        target_norm = torch.linalg.vector_norm(target, dim=(1, 2))
+        target_log = torch.log(torch.clamp(target, min=floor))
+        mel_target = 0.5 * conv.mel_amplitudes_from_waveform(wave)
+
+    def fused():
+        w = wave.detach().requires_grad_(True)
+        out = conv.spectral_losses(w, magnitude_slots=slots, log_floor=floor)
+        (out.convergence.sum() + out.log_magnitude.sum()).backward()
+        return w.grad
+
+    def composed():
+        w = wave.detach().requires_grad_(True)
+        a = conv.spectrogram_func(w).abs()
+        sc = torch.linalg.vector_norm(a - target, dim=(1, 2)) / target_norm
+        lg = (torch.log(torch.clamp(a, min=floor)) - target_log).abs().mean(dim=(1, 2))
+        (sc.sum() + lg.sum()).backward()
+        return w.grad
+
+    def mel():
+        w = wave.detach().requires_grad_(True)
+        (0.5 * (conv.mel_amplitudes_from_waveform(w) - mel_target).pow(2).sum()).backward()
+        return w.grad
+
+    steps = {"(a) fused spectral_losses": fused, "(b) composed from spectrogram_func(w).abs()": composed, "(c) mel_amplitudes_from_waveform": mel}
+    grads = {key: f() for key, f in steps.items()}
+    torch.cuda.synchronize()
+    ga, gb = grads["(a) fused spectral_losses"].double(), grads["(b) composed from spectrogram_func(w).abs()"].double()
+    agree = float(10 * torch.log10(ga.pow(2).sum() / (ga - gb).pow(2).sum()))
+    del grads, ga, gb
+    peak = {}
+    for key, f in steps.items():
+        plan.release_workspaces()
+        torch.cuda.empty_cache()
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        f()
+        torch.cuda.synchronize()
+        peak[key] = torch.cuda.max_memory_allocated() - base
+    for f in steps.values():
+        f()
+    torch.cuda.synchronize()
+    samples = {key: [] for key in steps}
+    for _ in range(args.runs):
+        for key, f in steps.items():
+            samples[key].append(event_ms(f))
+    ms = {key: statistics.median(v) for key, v in samples.items()}
+    spread = {key: (max(v) - min(v)) / statistics.median(v) for key, v in samples.items()}
+    ka, kb, kc = list(steps)
+    lines = [
+        f"---- fused spectral losses: {B} mono clips of {SAMPLES} samples ({Tn} frames each), default parameters, forward + backward of "
+        f"sum convergence + log magnitude, log_floor {floor:.6g}; device {torch.cuda.get_device_name(0)}",
+        f"time: {args.calls} steps back to back per sample, median of {args.runs} samples after warm-up, events on the stream, the three alternating "
+        "(spread = (max - min) / median); memory: torch.cuda.max_memory_allocated over one step above the allocation before it",
+        "",
+    ]
+    for key in steps:
+        lines.append(f"{key:46s} {ms[key]:9.3f} ms ({100 * spread[key]:4.1f} %)   peak {peak[key] / 2**20:9.1f} MiB")
+    lines += [
+        "",
+        f"(a) / (b): {ms[ka] / ms[kb]:.3f} of the time, {peak[ka] / peak[kb]:.3f} of the memory; (a) / (c): {ms[ka] / ms[kc]:.2f} of the time; "
+        f"(a) {B / ms[ka] * 1000:.0f} clips per second",
+        f"the gradients of (a) and (b) agree to {agree:.1f} dB ((b) runs the loss in float32)",
+        "",
+    ]
+    del wave, target, slots, target_log, mel_target
+    torch.cuda.empty_cache()
+
+    # end-to-end figures at the test shapes, every engine, plain and loop: each term's gradient against float64 autograd
+    import riffusion_oracle as O
+    import spec_loss_oracle as SLO
+    from helpers import snr_db, synthetic_wave
+    from riffusion import _autograd, _hip
+    from test_gpu_loop_decode import ENGINES
+
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    lines.append("end to end against float64 autograd through the oracle's STFT, B = 3, T = 41 (dB; dev = the device, o32 = float32 torch):")
+    for name, (_, kw, plan_kw) in ENGINES.items():
+        pe = SpectrogramParams(**kw)
+        pl, op = _hip.get_plan(pe, "cuda", **plan_kw), O.params_from(pe)
+        for loop in (False, True):
+            Lw = pe.hop_length * 41 if loop else pe.hop_length * 40 + 17
+            w = synthetic_wave(3, Lw)
+            w[-1] = 0.0
+            x64 = SLO.stft(w, op, loop)
+            gen = torch.Generator().manual_seed(4321 + Lw)
+            tgt = x64.abs() * (0.5 + 1.5 * torch.rand(x64.shape, generator=gen, dtype=torch.float64))
+            tgt[-1] = torch.rand(tgt[-1].shape, generator=gen, dtype=torch.float64) * 1000.0
+            tgt = tgt.to(torch.float32)
+            f = float(np.float32(0.1 * float(x64[:-1].abs().median())))
+            sl = pl.pack_magnitudes(tgt.cuda())
+            ones, zeros = torch.ones(3, dtype=torch.float64), torch.zeros(3, dtype=torch.float64)
+            row = []
+            for what, g_sc, g_lg in (("convergence", ones, None), ("log", zeros, ones)):
+                fl = f if g_lg is not None else 0.0
+                sums = pl.spectral_loss_sums(w.cuda(), sl, fl, loop)
+                coef = _autograd.loss_coefficients(sums, op.n_stft * 41, g_sc.cuda(), (g_lg if g_lg is not None else zeros).cuda(), fl)
+                dev = pl.spectral_loss_backward(w.cuda(), sl, coef, fl, loop).cpu()
+                r64 = SLO.end_to_end(w, tgt, op, f if g_lg is not None else None, g_sc, g_lg, loop, torch.float64)[2]
+                r32 = SLO.end_to_end(w, tgt, op, f if g_lg is not None else None, g_sc, g_lg, loop, torch.float32)[2]
+                row.append(f"{what}: dev {snr_db(r64, dev):6.1f}, o32 {snr_db(r64, r32):6.1f}")
+            lines.append(f"  {name:16s} {'loop ' if loop else 'plain'}  " + ";  ".join(row))
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(text)
+
+
+if __name__ == "__main__":
+    main()
