@@ -757,6 +757,60 @@ int rfx_spectral_loss_backward_loop(const rfx_plan* plan, const float* d_wave, c
                                     const float* d_coef /* (B, 2) */, int B, int Lw, float log_floor, float* d_grad_wave,
                                     void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- INVERSE SPECTROGRAM: complex STFT -> audio (torchaudio.transforms.InverseSpectrogram), with its gradient -------------------------
+ * With h = n_fft / 2, N = n_fft, w the window zero-padded to N, X (B, n_stft, T) complex64 in slot layout (what rfx_pack_complex and
+ * rfx_stft write):
+ *   PLAIN   y = torch.istft(X, n_fft, hop, win_length, window, center=True, normalized=False, onesided=True), L =
+ *           rfx_griffinlim_output_samples(plan, T) samples per row.  It is the final synthesis of Griffin-Lim: per frame the N-point
+ *           c2r transform (it ignores the imaginary part of bin 0 and of the Nyquist bin of an even N), times w, overlap-added as
+ *           the engine's fold chains it, divided by the envelope env[p] = sum_t w^2[p - hop t] and trimmed by h.  The window must meet
+ *           torch.istft's own condition: env non-zero over the L samples.
+ *   LOOP    the circular synthesis of a loop decode (rfx_loop_call_options): frames and positions modulo the period hop T, hop T
+ *           samples per row, the hop-entry circular envelope.  Needs hop T >= n_fft; a chirp-z plan answers RFX_ERR_UNSUPPORTED.
+ * The entries do NOT split X into magnitudes and angles: the engine's first Griffin-Lim launch (MODE 0, per-frame form) runs on unit
+ * magnitude slots and takes X itself where a decode injects its start angles, then the engine's fold writes the caller's rows.  So a
+ * result need not equal rfx_griffinlim's at n_iter = 0 on (|X|, X / |X|) bit for bit - that route rounds |X| (X / |X|) - and is held to
+ * the parity rule instead: its error against float64 torch.istft is within 6 dB of float32 torch.istft's own.  RANGE: the map is
+ * linear, no range table is drawn and nothing is squared, so a result is X's scaled by the same power of two as long as
+ * n_stft max|X| stays below 2^127 and the samples above the subnormals (the tests hold X 2^+-40).  Non-finite input gives non-finite
+ * output in the rows that hold it.
+ *   BACKWARD  for an incoming g (B, L) float32 the gradient with respect to X, in torch's convention dL/dRe + i dL/dIm, is
+ *           G[k][t] = (c_k / N) sum_i w[i] u[hop t + i - h] e^(-2 pi i k i / N)
+ *           u[q] = g[q] / env[q + h] for 0 <= q < L and 0 outside - zero extension, not reflection; c_k = 1 for bin 0 and for the
+ *           Nyquist bin of an even N, else 2; the imaginary part of G is exactly 0 in the bins with c_k = 1.  Loop form:
+ *           u[q] = g[q] renv[q mod hop], the sample index modulo hop T - the circular analysis of rfx_stft_loop as it is.
+ * On the device, per group of rows, the backward stages u (one kernel, 16-byte stores: the envelope table of the engine's fold
+ * applied), runs the plan's forward frame transform on it under a third index rule beside reflect and wrap - the ZERO-EXTENSION twin of
+ * each engine's forward kernel, the same kernel text with a position outside [0, L) contributing an exact 0.0f; the loop form runs the
+ * circular transform of rfx_stft_loop as it is - and one epilogue kernel applies c_k / N and the zero-imaginary rule while it writes
+ * gradient slots in rfx_pack_complex's layout: conjugate slots conjugated, both slots of a doubled bin filled, padding 0.  All four
+ * frame engines (the chirp-z engine for the plain forms).  The twin's exact test is rfx_debug_istft_backward_padded below: the
+ * plain backward with u padded with zeros to the period P' = hop ceil((L + n_fft) / hop) and the circular transform in the twin's
+ * place gives the same bits (it computes about n_fft / hop frames per row for nothing).
+ * Contract of the four entries: B == 0 is a no-op.  Refusals - a NULL pointer; a spectrum, gradient-slot or workspace pointer that is
+ * not 16-byte aligned, a float tensor that is not 4-byte aligned; a T the form cannot serve (plain: no sample; loop: hop T < n_fft,
+ * the message names the fewest frames); a loop form on a chirp-z plan (RFX_ERR_UNSUPPORTED); a workspace below the query - come before
+ * any launch and leave the outputs untouched; a query answers 0 where the call would be refused.  Offsets are 64-bit.  BOUNDED
+ * WORKSPACE: rows are walked in groups of max(1, 256 MiB / row bytes) whole rows (at most 65535).  Deterministic, and a row's bytes
+ * depend on that row alone.
+ * d_spec_slots / d_grad_spec_slots: B * T frames of slots; d_wave_out / d_grad_wave: (B, L) float32, L the form's samples. */
+size_t rfx_istft_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_istft(const rfx_plan* plan, const void* d_spec_slots, int B, int T, float* d_wave_out, void* d_workspace, size_t workspace_bytes,
+              void* stream);
+size_t rfx_istft_loop_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_istft_loop(const rfx_plan* plan, const void* d_spec_slots, int B, int T, float* d_wave_out, void* d_workspace,
+                   size_t workspace_bytes, void* stream);
+size_t rfx_istft_backward_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_istft_backward(const rfx_plan* plan, const float* d_grad_wave, int B, int T, void* d_grad_spec_slots, void* d_workspace,
+                       size_t workspace_bytes, void* stream);
+size_t rfx_istft_backward_loop_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_istft_backward_loop(const rfx_plan* plan, const float* d_grad_wave, int B, int T, void* d_grad_spec_slots, void* d_workspace,
+                            size_t workspace_bytes, void* stream);
+/* rfx_istft_backward by the padded circular route (tests): same arguments, same contract, a larger workspace, the same bytes */
+size_t rfx_debug_istft_backward_padded_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_debug_istft_backward_padded(const rfx_plan* plan, const float* d_grad_wave, int B, int T, void* d_grad_spec_slots,
+                                    void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- inverse: torchaudio.transforms.InverseMelScale (SGD, max_iter = params.max_mel_iters,
  * tolerance_loss 1e-5, tolerance_change 1e-8, lr 0.1, momentum 0.9), spectrogram_converter.py:87-99,
  * called at :201.  d_mel (B, n_mels, T); the B rows are grouped into clips of `channels_per_clip`

@@ -133,7 +133,14 @@ struct rfx_plan {
   int mb_width = 0;
 };
 
+// the engine's MODE 0 per-frame launch as the backward entries and the inverse spectrogram drive it (rfx_api_backward.hip): `rows`
+// rows of T frames, frames = synthesis of S * angles0, mel_bwd_frame_pitch floats per frame
+size_t mel_bwd_frame_pitch(const rfx_plan* plan);
+int mel_bwd_frames(const rfx_plan* plan, const float* S, const rfx::cf* angles0, float* frames, int rows, int T, hipStream_t stream);
+
 namespace rfx {
+// the specialised engine's fold table out[p] = (2 / n_fft) / env[p + n_fft / 2], p < L (rfx_api_inverse.hip: out_scale_kernel)
+hipError_t launch_gl_out_scale(const float* win, float* out, int T, int L, hipStream_t stream);
 // torch.stft(center=True): the signal is reflect-padded by n_fft/2 on both sides, so a waveform of Lw samples gives
 // 1 + (Lw + 2*(n_fft/2) - n_fft) / hop frames: 1 + Lw/hop for even n_fft, 1 + (Lw - 1)/hop for odd n_fft
 inline int stft_frames(const rfx_plan* plan, int Lw) {
@@ -147,6 +154,8 @@ inline int frame_blocks(long long slots, int B, int T) {
 // the refusal of a row length a loop forward call does not take, with the nearest lengths it does; RFX_OK for a legal one
 // (rfx_api_forward.hip; the loop loss backward of rfx_api_backward.hip words its refusal the same way)
 int loop_length_refusal(const rfx_plan* plan, int Lw, const char* who);
+// the zero-extension twin of the plan's forward frame launch (rfx_api_forward.hip): rows of L samples, T frames, the complex spectrum
+int stft_zero_extended(const rfx_plan* plan, const float* d_rows, int B, int L, int T, void* d_spec_slots, void* stream);
 inline long long fam_slot_count(const rfx_plan* plan) { return (long long)plan->num_cus * plan->fam_wgs_per_cu; }
 
 // the spectral-peak start as the inverse entries use it (rfx_api_peak.hip): the refusal of a plan whose frame does not fit the LDS;

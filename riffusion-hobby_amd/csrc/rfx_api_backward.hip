@@ -20,7 +20,7 @@ struct MelBwdLayout {
   size_t spec, smag, frames, total;
   int group_rows, T;
 };
-static size_t mel_bwd_frame_pitch(const rfx_plan* plan) { return plan->generic ? (size_t)plan->gg.fpitch : gl_frame_buffer_bytes(1, 1) / sizeof(float); }
+size_t mel_bwd_frame_pitch(const rfx_plan* plan) { return plan->generic ? (size_t)plan->gg.fpitch : gl_frame_buffer_bytes(1, 1) / sizeof(float); }
 // ... of rows of T frames (the plain forms: T = stft_frames(Lw); the loop loss backward: T = Lw / hop)
 static MelBwdLayout mel_bwd_layout_frames(const rfx_plan* plan, int B, int frames, bool with_spec) {
   MelBwdLayout l{};
@@ -52,8 +52,8 @@ size_t rfx_mel_scale_backward_workspace_bytes(const rfx_plan* plan, int B, int T
   return 0;  // step 1 alone needs no scratch
 }
 
-// the engine's MODE 0 per-frame launch: frames = synthesis of S * angles0, `rows` rows of T frames
-static int mel_bwd_frames(const rfx_plan* plan, const float* S, const cf* angles0, float* frames, int rows, int T, hipStream_t stream) {
+// the engine's MODE 0 per-frame launch: frames = synthesis of S * angles0, `rows` rows of T frames (rfx_api_istft.hip runs it too)
+int mel_bwd_frames(const rfx_plan* plan, const float* S, const cf* angles0, float* frames, int rows, int T, hipStream_t stream) {
   if (!plan->generic) {
     GlFrameArgs fa{};
     fa.S = S;

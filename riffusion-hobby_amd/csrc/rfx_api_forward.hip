@@ -86,6 +86,8 @@ int rfx_unpack_magnitudes(const rfx_plan* plan, const float* d_slots, int B, int
   return RFX_OK;
 }
 
+enum FwdRule { kFwdReflect = 0, kFwdLoop = 1, kFwdZero = 2 };
+static int stft_launch(const rfx_plan* plan, const float* d_wave, int B, int Lw, int T, float* d_mag_slots, void* d_spec_slots, void* stream, int rule);
 static int stft_run(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots, void* stream, bool loop) {
   if (!plan || !d_wave || B <= 0) return fail(RFX_ERR_INVALID, loop ? "rfx_stft_loop: bad argument" : "rfx_stft: bad argument");
   if (loop) {
@@ -95,12 +97,20 @@ static int stft_run(const rfx_plan* plan, const float* d_wave, int B, int Lw, fl
     return fail(RFX_ERR_INVALID, "rfx_stft: reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
   }
   RFX_ON_DEVICE(plan->device);
-  const int T = fwd_frames(plan, Lw, loop);
+  return stft_launch(plan, d_wave, B, Lw, fwd_frames(plan, Lw, loop), d_mag_slots, d_spec_slots, stream, loop ? kFwdLoop : kFwdReflect);
+}
+// the engine's forward frame launch on checked arguments, by index rule.  kFwdZero (rfx::stft_zero_extended): the complex spectrum only
+static int stft_launch(const rfx_plan* plan, const float* d_wave, int B, int Lw, int T, float* d_mag_slots, void* d_spec_slots, void* stream, int rule) {
+  const bool loop = rule == kFwdLoop, zero = rule == kFwdZero;
   if (plan->fam_ok) {  // row-family kernels (rfx_fam.hip), same plain layout as the generic engine's
     FamFwdArgs fa = fam_fwd_args(plan, d_wave, B, Lw, T);
     fa.mag = d_mag_slots;
     fa.spec = (cf*)d_spec_slots;
     const int nblocks = frame_blocks(fam_slot_count(plan), B, fa.T);
+    if (zero) {
+      RFX_HIP(launch_fam_fwd_zero(fa, nblocks, (hipStream_t)stream));
+      return RFX_OK;
+    }
     const auto launch = loop ? launch_fam_fwd_loop : launch_fam_fwd;
     if (d_mag_slots) RFX_HIP(launch(0, fa, nblocks, (hipStream_t)stream));
     if (d_spec_slots) RFX_HIP(launch(1, fa, nblocks, (hipStream_t)stream));
@@ -118,9 +128,13 @@ static int stft_run(const rfx_plan* plan, const float* d_wave, int B, int Lw, fl
     g.T = T;
     g.Lw = Lw;
     if (plan->czt) {
-      const auto launch = loop ? launch_czt_stft_loop : launch_czt_stft;
+      const auto launch = zero ? launch_czt_stft_zero : loop ? launch_czt_stft_loop : launch_czt_stft;
       if (d_mag_slots) RFX_HIP(launch(0, g, plan->d_czt_c, plan->d_czt_h, plan->num_cus, (hipStream_t)stream));
       if (d_spec_slots) RFX_HIP(launch(1, g, plan->d_czt_c, plan->d_czt_h, plan->num_cus, (hipStream_t)stream));
+      return RFX_OK;
+    }
+    if (zero) {
+      RFX_HIP(launch_gen_stft_zero(g, plan->num_cus, (hipStream_t)stream));
       return RFX_OK;
     }
     const auto launch = loop ? launch_gen_stft_loop : launch_gen_stft;
@@ -143,8 +157,13 @@ static int stft_run(const rfx_plan* plan, const float* d_wave, int B, int Lw, fl
   if (fpb < 1) fpb = 1;
   if (fpb > 16) fpb = 16;
   a.frames_per_block = fpb;
-  RFX_HIP(loop ? launch_stft_loop(a, (hipStream_t)stream) : launch_stft(a, (hipStream_t)stream));
+  RFX_HIP(zero ? launch_stft_zero(a, (hipStream_t)stream) : loop ? launch_stft_loop(a, (hipStream_t)stream) : launch_stft(a, (hipStream_t)stream));
   return RFX_OK;
+}
+// the zero-extended analysis of rfx_istft_backward (rfx_api_istft.hip): `B` rows of L samples, T frames each - frame t, element i reads
+// sample hop t + i - n_fft / 2, an exact zero outside [0, L) - into d_spec_slots.  The caller has checked its arguments and set the device.
+int rfx::stft_zero_extended(const rfx_plan* plan, const float* d_rows, int B, int L, int T, void* d_spec_slots, void* stream) {
+  return stft_launch(plan, d_rows, B, L, T, nullptr, d_spec_slots, stream, kFwdZero);
 }
 int rfx_stft(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots, void* stream) {
   return stft_run(plan, d_wave, B, Lw, d_mag_slots, d_spec_slots, stream, false);

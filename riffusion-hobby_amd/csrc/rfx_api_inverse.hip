@@ -64,6 +64,10 @@ __global__ void out_scale_kernel(const float* __restrict__ win, float* __restric
   }
   out[p] = (2.0f / (float)kNfft) / env;
 }
+hipError_t launch_gl_out_scale(const float* win, float* out, int T, int L, hipStream_t stream) {
+  hipLaunchKernelGGL(out_scale_kernel, dim3((L + 255) / 256), dim3(256), 0, stream, win, out, T, L);
+  return hipGetLastError();
+}
 }  // namespace rfx
 
 static long long gl_slot_count(const rfx_plan* plan) { return (long long)plan->num_cus * plan->gl_wgs_per_cu; }

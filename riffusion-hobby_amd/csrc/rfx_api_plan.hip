@@ -141,6 +141,7 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
   if (geo.czt) RFX_HIP(prepare_czt_kernels(gg));
   if (geo.czt) RFX_HIP(prepare_czt_list_kernels(gg));
   if (geo.czt) RFX_HIP(prepare_czt_loop_kernels(gg));
+  if (geo.czt) RFX_HIP(prepare_czt_zero_kernels(gg));
   if (geo.fam_ok) {
     RFX_HIP(prepare_fam_kernels(geo.fam));
     pl->fam = geo.fam;

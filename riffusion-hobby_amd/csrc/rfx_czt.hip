@@ -14,7 +14,8 @@
 #define RFX_CZT_LIST_TU 0
 #endif
 // ... and a third time as rfx_czt_loop.hip (`#define RFX_CZT_LOOP_TU 1`, then this file), which holds only the forward kernels of a loop
-// call - czt_stft_loop_kernel, the row read modulo its length (include/rfx.h: rfx_stft_loop) - and their launcher.
+// call - czt_stft_loop_kernel, the row read modulo its length (include/rfx.h: rfx_stft_loop) - and their launcher; and a fourth time
+// as rfx_czt_zero.hip (`#define RFX_CZT_LOOP_TU 2`): the same unit over czt_stft_zero_kernel, the zero-extended row of rfx_istft_backward.
 #ifndef RFX_CZT_LOOP_TU
 #define RFX_CZT_LOOP_TU 0
 #endif
@@ -23,6 +24,7 @@
 #include "rfx_czt_core.h"
 #include "rfx_kernels.h"
 #include "rfx_loop_core.h"
+#include "rfx_istft_core.h"
 
 namespace rfx {
 
@@ -94,8 +96,9 @@ __device__ __forceinline__ void czt_conv(const GenGeom& g, const CztLds& l, cons
 
 // step 1 on the analysis frame t of x (- mom xp): windowed, zero-padded (reflect-padded signal like torch.stft center=True), packed
 // two reals per complex when n_fft is even, times the chirp.  Only the elements the window covers need loads; global loads of a
-// batch first, then its LDS stores.  LOOP (czt_stft_loop_kernel): the row is one period of L samples, read modulo L (rfx_loop_core.h).
-template <bool LOOP = false>
+// batch first, then its LDS stores.  RULE 1 (czt_stft_loop_kernel): the row is one period of L samples, read modulo L (rfx_loop_core.h);
+// RULE 2 (czt_stft_zero_kernel): the row is zero-extended (rfx_istft_core.h: zero_outside), an exact 0.0f outside [0, L).
+template <int RULE = 0>
 __device__ __forceinline__ void czt_load_frame(const GenGeom& g, cf* buf, const float* __restrict__ x, const float* __restrict__ xp, float mom, int L,
                                                int t, const float* __restrict__ win, const cf* __restrict__ c) {
   const int nthr = (int)blockDim.x, half = g.n_fft / 2;
@@ -118,9 +121,13 @@ __device__ __forceinline__ void czt_load_frame(const GenGeom& g, cf* buf, const 
           const int i = per * n + e;  // position inside the padded frame
           const int j = i - g.left;   // position inside the window
           if (j >= 0 && j < g.win) {
-            const int p = LOOP ? loop_read_index(g.hop * t + i - half, L) : reflect_index(g.hop * t + i - half, L);
-            xs[u][e] = x[p];
-            if (xp) ps[u][e] = xp[p];
+            if (RULE == 2) {
+              xs[u][e] = zero_outside_read(x, g.hop * t + i - half, L);
+            } else {
+              const int p = RULE == 1 ? loop_read_index(g.hop * t + i - half, L) : reflect_index(g.hop * t + i - half, L);
+              xs[u][e] = x[p];
+              if (xp) ps[u][e] = xp[p];
+            }
             ws[u][e] = win[j];
           }
         }
@@ -304,6 +311,12 @@ hipError_t launch_czt_gl_list(const GenGlArgs& a, const int* list, const cf* chi
   return hipGetLastError();
 }
 #elif RFX_CZT_LOOP_TU
+#if RFX_CZT_LOOP_TU == 2  // rfx_czt_zero.hip: the dispatch below over the zero-extension twins, under their own names
+#define czt_stft_loop_kernel czt_stft_zero_kernel
+#define czt_stft_loop_fn czt_stft_zero_fn
+#define prepare_czt_loop_kernels prepare_czt_zero_kernels
+#define launch_czt_stft_loop launch_czt_stft_zero
+#endif
 // the forward kernels of a loop call by (mode, radix class of the pass length)
 using CztStftFn = void (*)(GenStftArgs, CztTab);
 template <int MAXR>

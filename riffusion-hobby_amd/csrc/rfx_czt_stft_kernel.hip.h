@@ -2,7 +2,7 @@
 //   RFX_FWDK_LOOP 0  czt_stft_kernel<MODE, MAXR>       (rfx_czt.hip itself) the row is reflect-padded (torch.stft center=True): the text this kernel
 //                                                      always had
 //   RFX_FWDK_LOOP 1  czt_stft_loop_kernel<MODE, MAXR>  (rfx_czt_loop.hip) a loop forward call (include/rfx.h: rfx_stft_loop): the row of a.Lw = hop a.T
-//                                                      samples is one period and is read modulo a.Lw (czt_load_frame<true>; rfx_loop_core.h)
+//                                                      samples is one period and is read modulo a.Lw (czt_load_frame<1>; rfx_loop_core.h)
 // One text, chosen at compile time.  (The engine's Griffin-Lim kernels have no circular variant: it still refuses a loop DECODE.)
 // (two waves per SIMD = 256 VGPRs for every radix class: a kernel holds the forward AND the inverse passes - the Griffin-Lim kernel
 // two of each - and under the generic engine's 128-register bound of the 2 / 3 / 5 / 7 classes the compiler spilled 180 - 370 bytes per
@@ -10,7 +10,9 @@
 // engine is for - 137 KB at n_fft 17028 - leaves no room for a second one anyway)
 template <int MODE, int MAXR>
 __global__ void __launch_bounds__(kCztThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-#if RFX_FWDK_LOOP
+#if RFX_FWDK_LOOP == 2
+czt_stft_zero_kernel(GenStftArgs a, CztTab ct) {  // (rfx_czt_zero.hip) the row is zero-extended: rfx_istft_backward's analysis
+#elif RFX_FWDK_LOOP
 czt_stft_loop_kernel(GenStftArgs a, CztTab ct) {
 #else
 czt_stft_kernel(GenStftArgs a, CztTab ct) {
@@ -23,7 +25,7 @@ czt_stft_kernel(GenStftArgs a, CztTab ct) {
   for (long long fr = blockIdx.x; fr < nframes; fr += gridDim.x) {
     const int clip = (int)(fr / a.T), t = (int)(fr - (long long)clip * a.T);
     __syncthreads();  // previous frame's epilogue is done with the buffer
-    czt_load_frame<RFX_FWDK_LOOP != 0>(g, l.a, a.wave + (size_t)clip * a.wave_stride, nullptr, 0.f, a.Lw, t, a.tb.win, ct.c);
+    czt_load_frame<RFX_FWDK_LOOP>(g, l.a, a.wave + (size_t)clip * a.wave_stride, nullptr, 0.f, a.Lw, t, a.tb.win, ct.c);
     czt_conv<MAXR>(g, l, a.tb.tw, ct.h);
     const size_t base = (size_t)fr * g.fs;
     constexpr int UB = RFX_CZT_BATCH;

@@ -34,6 +34,7 @@
 #include "rfx_frame.hip.h"  // buffer-descriptor loads / stores (SRD in SGPRs + one 32-bit lane offset: no 64-bit per-lane addresses)
 #include "rfx_kernels.h"
 #include "rfx_loop_core.h"
+#include "rfx_istft_core.h"
 
 namespace rfx {
 
@@ -139,6 +140,9 @@ struct FamTwA {
 #include "rfx_fam_fwd_kernel.hip.h"
 #undef RFX_FWDK_LOOP
 #define RFX_FWDK_LOOP 1
+#include "rfx_fam_fwd_kernel.hip.h"
+#undef RFX_FWDK_LOOP
+#define RFX_FWDK_LOOP 2  // fam_fwd_zero_kernel: the zero-extended analysis of rfx_istft_backward
 #include "rfx_fam_fwd_kernel.hip.h"
 #undef RFX_FWDK_LOOP
 
@@ -299,6 +303,20 @@ static FamFwdFn fam_fwd_loop_fn(const FamGeom& g, int mode) {
   }
 }
 
+// ... and the zero-extension twin (complex spectrum only)
+static FamFwdFn fam_fwd_zero_fn(const FamGeom& g) {
+  if (g.nrad == 20) return g.h == 441 ? fam_fwd_zero_kernel<1, 21, 21, 20> : nullptr;  // 22.05 kHz
+  switch (g.h) {
+    case 80: return fam_fwd_zero_kernel<1, 10, 8>;
+    case 160: return fam_fwd_zero_kernel<1, 16, 10>;
+    case 240: return fam_fwd_zero_kernel<1, 16, 15>;
+    case 320: return fam_fwd_zero_kernel<1, 20, 16>;
+    case 441: return fam_fwd_zero_kernel<1, 21, 21>;
+    case 480: return fam_fwd_zero_kernel<1, 24, 20>;
+    default: return nullptr;
+  }
+}
+
 hipError_t launch_fam_fwd(int mode, const FamFwdArgs& a, int nblocks, hipStream_t stream) {
   hipLaunchKernelGGL(fam_fwd_fn(a.g, mode), dim3(nblocks), dim3(a.g.nthr), fam_lds_bytes(a.g), stream, a);
   return hipGetLastError();
@@ -309,7 +327,15 @@ hipError_t launch_fam_fwd_loop(int mode, const FamFwdArgs& a, int nblocks, hipSt
   return hipGetLastError();
 }
 
+hipError_t launch_fam_fwd_zero(const FamFwdArgs& a, int nblocks, hipStream_t stream) {
+  hipLaunchKernelGGL(fam_fwd_zero_fn(a.g), dim3(nblocks), dim3(a.g.nthr), fam_lds_bytes(a.g), stream, a);
+  return hipGetLastError();
+}
+
 hipError_t prepare_fam_kernels(const FamGeom& g) {
+  const FamFwdFn zf = fam_fwd_zero_fn(g);
+  if (!zf) return hipErrorInvalidValue;
+  if (const hipError_t ez = hipFuncSetAttribute((const void*)zf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fam_lds_bytes(g)); ez != hipSuccess) return ez;
   for (int mode = 0; mode < 3; ++mode) {
     const hipError_t e = hipFuncSetAttribute((const void*)fam_fwd_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fam_lds_bytes(g));
     if (e != hipSuccess) return e;

@@ -3,17 +3,23 @@
 //   RFX_FWDK_LOOP 1  fam_fwd_loop_kernel<MODE, RA, RB, NR>  a loop forward call (include/rfx.h: rfx_stft_loop): the row of a.Lw = hop a.T samples is one
 //                                                           period and is read modulo a.Lw (rfx_loop_core.h)
 // One text, chosen at compile time: the two differ in how a sample position is formed and in nothing else.
-#if RFX_FWDK_LOOP
-#define RFX_FWDK_POS(p, L) loop_read_index(p, L)
+//   RFX_FWDK_LOOP 2  fam_fwd_zero_kernel<MODE, RA, RB, NR>  the row of a.Lw samples is ZERO-EXTENDED (rfx_istft_core.h: zero_outside): the analysis of
+//                                                           rfx_istft_backward, a.T frames whatever a.Lw is; outside [0, a.Lw) an exact 0.0f
+#if RFX_FWDK_LOOP == 2
+#define RFX_FWDK_LD(x, p, L) ((unsigned)(p) < (unsigned)(L) ? ld1(x, (unsigned)(p) * 4u, 0) : 0.f)
+#elif RFX_FWDK_LOOP
+#define RFX_FWDK_LD(x, p, L) ld1(x, (unsigned)loop_read_index(p, L) * 4u, 0)
 #else
-#define RFX_FWDK_POS(p, L) reflect_index(p, L)
+#define RFX_FWDK_LD(x, p, L) ld1(x, (unsigned)reflect_index(p, L) * 4u, 0)
 #endif
 // ---- forward: Spectrogram(power=None) [+ abs] of the family geometries (spectrogram_converter.py:47-59, :179-182).  Same P1 /
 // A / B as above; the frame then changes places through LDS - once every row has been read the cube's memory becomes the
 // bin-ordered frame, each bin written by its primary slot (the direct one where a bin has two) - and leaves in whole lines, in
 // the plan's plain layout [B*T][fs] (what rfx_stft hands out and gen_mel_kernel reads).  MODE 0: |X|, MODE 1: X.
 template <int MODE, int RA, int RB, int NR = 40>
-#if RFX_FWDK_LOOP
+#if RFX_FWDK_LOOP == 2
+__global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu_waves_per_eu(4))) fam_fwd_zero_kernel(FamFwdArgs a) {
+#elif RFX_FWDK_LOOP
 __global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu_waves_per_eu(4))) fam_fwd_loop_kernel(FamFwdArgs a) {
 #else
 __global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu_waves_per_eu(4))) fam_fwd_kernel(FamFwdArgs a) {
@@ -67,7 +73,7 @@ __global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu
 #pragma unroll
     for (int j = 0; j < WH; ++j) {
       wv[j] = ld1(win, npr4, (unsigned)j * (H * 4u));
-      u[j] = ld1(x, (unsigned)RFX_FWDK_POS(a.g.hop * fr + a.g.off + j * H + npr, a.Lw) * 4u, 0);
+      u[j] = RFX_FWDK_LD(x, a.g.hop * fr + a.g.off + j * H + npr, a.Lw);
     }
   };
   if ((long long)blockIdx.x < nframes) load_frame_inputs(blockIdx.x);
@@ -156,4 +162,4 @@ __global__ void __launch_bounds__(fam_threads(RA, RB, NR)) __attribute__((amdgpu
     __syncthreads();  // the next frame's P1 overwrites the frame
   }
 }
-#undef RFX_FWDK_POS
+#undef RFX_FWDK_LD

@@ -3,10 +3,14 @@
 //   RFX_FWDK_LOOP 1  gen_stft_loop_kernel<MODE, MAXR>  a loop forward call (include/rfx.h: rfx_stft_loop): the row of a.Lw = hop a.T samples is one period
 //                                                      and is read modulo a.Lw (rfx_loop_core.h)
 // One text, chosen at compile time: the two differ in how a sample position is formed and in nothing else.
-#if RFX_FWDK_LOOP
-#define RFX_FWDK_POS(p, L) loop_read_index(p, L)
+//   RFX_FWDK_LOOP 2  gen_stft_zero_kernel<MODE, MAXR>  the row of a.Lw samples is ZERO-EXTENDED (rfx_istft_core.h: zero_outside): the analysis of
+//                                                      rfx_istft_backward, a.T frames whatever a.Lw is; outside [0, a.Lw) an exact 0.0f
+#if RFX_FWDK_LOOP == 2
+#define RFX_FWDK_READ(x, p, L) zero_outside_read(x, p, L)
+#elif RFX_FWDK_LOOP
+#define RFX_FWDK_READ(x, p, L) x[loop_read_index(p, L)]
 #else
-#define RFX_FWDK_POS(p, L) reflect_index(p, L)
+#define RFX_FWDK_READ(x, p, L) x[reflect_index(p, L)]
 #endif
 // (Prefetching the next frame's samples and the epilogue's |S| / tprev into register slots across the passes was tried:
 // 229 -> 245-257 ms per 64 tiles at 48 kHz - the slot arrays spill.  The simple loops below stay.)
@@ -15,7 +19,9 @@
 // the O(R^2) radix-11 / 13 class keeps its larger budget)
 template <int MODE, int MAXR>
 __global__ void __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(MAXR <= 7 ? 4 : 2)))
-#if RFX_FWDK_LOOP
+#if RFX_FWDK_LOOP == 2
+gen_stft_zero_kernel(GenStftArgs a) {
+#elif RFX_FWDK_LOOP
 gen_stft_loop_kernel(GenStftArgs a) {
 #else
 gen_stft_kernel(GenStftArgs a) {
@@ -37,7 +43,7 @@ gen_stft_kernel(GenStftArgs a) {
         if (!g.even && e == 1) break;
         const int i = g.even ? 2 * n + e : n;  // position inside the padded frame
         const int j = i - g.left;              // position inside the window
-        if (j >= 0 && j < g.win) v[e] = x[RFX_FWDK_POS(g.hop * t + i - half, a.Lw)] * a.tb.win[j];
+        if (j >= 0 && j < g.win) v[e] = RFX_FWDK_READ(x, g.hop * t + i - half, a.Lw) * a.tb.win[j];
       }
       l.a[RFX_GEN_INPLACE ? gen_ipad(n, g.pad_shift) : gen_pad(n)] = cf{v[0], v[1]};
     }
@@ -55,4 +61,4 @@ gen_stft_kernel(GenStftArgs a) {
     }
   }
 }
-#undef RFX_FWDK_POS
+#undef RFX_FWDK_READ

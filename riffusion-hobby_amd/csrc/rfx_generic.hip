@@ -17,6 +17,7 @@
 #include "rfx_gen_core.h"
 #include "rfx_kernels.h"
 #include "rfx_loop_core.h"
+#include "rfx_istft_core.h"
 
 namespace rfx {
 
@@ -104,6 +105,9 @@ enum GenStftMode { kGenMag = 0, kGenSpec = 1 };
 #include "rfx_gen_stft_kernel.hip.h"
 #undef RFX_FWDK_LOOP
 #define RFX_FWDK_LOOP 1
+#include "rfx_gen_stft_kernel.hip.h"
+#undef RFX_FWDK_LOOP
+#define RFX_FWDK_LOOP 2  // gen_stft_zero_kernel: the zero-extended analysis of rfx_istft_backward
 #include "rfx_gen_stft_kernel.hip.h"
 #undef RFX_FWDK_LOOP
 
@@ -348,6 +352,11 @@ static GenStftFn gen_stft_loop_fn(const GenGeom& g, int mode) {
   const int c = gen_radix_class(g.radix, g.nstages);
   return c == 5 ? gen_stft_loop_fn<5>(mode) : c == 7 ? gen_stft_loop_fn<7>(mode) : gen_stft_loop_fn<13>(mode);
 }
+// ... and the zero-extension twin (complex spectrum only)
+static GenStftFn gen_stft_zero_fn(const GenGeom& g) {
+  const int c = gen_radix_class(g.radix, g.nstages);
+  return c == 5 ? gen_stft_zero_kernel<kGenSpec, 5> : c == 7 ? gen_stft_zero_kernel<kGenSpec, 7> : gen_stft_zero_kernel<kGenSpec, 13>;
+}
 template <int MAXR>
 static GenGlFn gen_gl_fn(int mode) {
   return mode == 0 ? gen_gl_kernel<0, MAXR> : mode == 1 ? gen_gl_kernel<1, MAXR> : gen_gl_kernel<2, MAXR>;
@@ -375,6 +384,7 @@ hipError_t prepare_generic_kernels(const GenGeom& g) {
     if ((e = hipFuncSetAttribute((const void*)gen_stft_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   for (int mode = 0; mode < 2; ++mode)
     if ((e = hipFuncSetAttribute((const void*)gen_stft_loop_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute((const void*)gen_stft_zero_fn(g), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   for (int mode = 0; mode < 3; ++mode)
     if ((e = hipFuncSetAttribute((const void*)gen_gl_fn(g, mode), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)gen_gl_list_fn(g), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -389,6 +399,12 @@ hipError_t launch_gen_stft(int mode, const GenStftArgs& a, int num_cus, hipStrea
 hipError_t launch_gen_stft_loop(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream) {
   const int grid = gen_grid(a.g, num_cus, (long long)a.B * a.T);
   hipLaunchKernelGGL(gen_stft_loop_fn(a.g, mode), dim3(grid), dim3(a.g.nthr), gen_lds_bytes(a.g), stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_stft_zero(const GenStftArgs& a, int num_cus, hipStream_t stream) {
+  const int grid = gen_grid(a.g, num_cus, (long long)a.B * a.T);
+  hipLaunchKernelGGL(gen_stft_zero_fn(a.g), dim3(grid), dim3(a.g.nthr), gen_lds_bytes(a.g), stream, a);
   return hipGetLastError();
 }
 

@@ -136,6 +136,8 @@ struct StftArgs {
 hipError_t launch_stft(const StftArgs& a, hipStream_t stream);
 // a loop forward call (include/rfx.h: rfx_stft_loop): Lw = hop T is the row's period, read modulo Lw (rfx_loop_core.h: loop_read_index)
 hipError_t launch_stft_loop(const StftArgs& a, hipStream_t stream);
+// the zero-extension twin (rfx_istft_backward): rows of Lw samples, T frames each, outside [0, Lw) an exact zero; spec only
+hipError_t launch_stft_zero(const StftArgs& a, hipStream_t stream);
 
 // fused forward path: waveform -> framed transform -> |X| -> banded mel projection, nothing but the (B, M, T) mel
 // amplitudes leaves the chip.  Valid for banded filterbanks (every filter's support one contiguous run of bins).
@@ -345,6 +347,7 @@ hipError_t prepare_generic_kernels(const GenGeom& g);
 size_t gen_lds_bytes(const GenGeom& g);
 hipError_t launch_gen_stft(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream);  // mode 0 mag, 1 spec
 hipError_t launch_gen_stft_loop(int mode, const GenStftArgs& a, int num_cus, hipStream_t stream);  // a loop forward call: Lw = hop T, the row read modulo Lw
+hipError_t launch_gen_stft_zero(const GenStftArgs& a, int num_cus, hipStream_t stream);  // the zero-extension twin: a.spec from zero-extended rows of a.Lw samples, a.T frames
 hipError_t launch_gen_gl(int mode, const GenGlArgs& a, int num_cus, hipStream_t stream);      // mode 0 init, 1 first iteration, 2 iteration
 hipError_t launch_gen_gl_list(const GenGlArgs& a, const int* list, int num_cus, hipStream_t stream);  // mode 1 over a free-frame list (launch_gl_frame_list)
 hipError_t launch_gen_env(const float* win, float* env, const GenGeom& g, int T, int L, hipStream_t stream);  // env[p] = sum_t w[j]^2, once per call
@@ -372,6 +375,9 @@ hipError_t launch_czt_gl_list(const GenGlArgs& a, const int* list, const cf* chi
 // the forward kernels of a loop call (Lw = hop T, the row read modulo Lw); a translation unit of their own as well (rfx_czt_loop.hip)
 hipError_t prepare_czt_loop_kernels(const GenGeom& g);
 hipError_t launch_czt_stft_loop(int mode, const GenStftArgs& a, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);  // mode 0 mag, 1 spec
+// the forward kernels of the zero-extended analysis (rfx_istft_backward); a translation unit of their own too (rfx_czt_zero.hip)
+hipError_t prepare_czt_zero_kernels(const GenGeom& g);
+hipError_t launch_czt_stft_zero(int mode, const GenStftArgs& a, const cf* chirp, const cf* h, int num_cus, hipStream_t stream);  // mode 1 spec
 hipError_t launch_mel_transpose(const float* mel_tm, float* mel, int B, int T, int M, int Mpad, hipStream_t stream);
 
 // ---- row-family Griffin-Lim (rfx_fam.hip): n_fft = 40 h, win_length = 10 h; frames are folded by launch_gen_fold
@@ -418,6 +424,7 @@ struct FamFwdArgs {
 };
 hipError_t launch_fam_fwd(int mode, const FamFwdArgs& a, int nblocks, hipStream_t stream);
 hipError_t launch_fam_fwd_loop(int mode, const FamFwdArgs& a, int nblocks, hipStream_t stream);  // a loop forward call: Lw = hop T, the row read modulo Lw
+hipError_t launch_fam_fwd_zero(const FamFwdArgs& a, int nblocks, hipStream_t stream);  // the zero-extension twin, mode 1: a.spec from zero-extended rows of a.Lw samples
 hipError_t prepare_fam_kernels(const FamGeom& g);
 size_t fam_lds_bytes(const FamGeom& g);         // dynamic: the cube
 size_t fam_static_lds_bytes(const FamGeom& g);  // static: the pass-A twiddles where they fit
@@ -639,5 +646,32 @@ struct SpecLossSlotArgs {
 hipError_t launch_spec_loss_slots(const SpecLossSlotArgs& a, hipStream_t stream);
 // the circular adjoint fold of a loop row: MelBwdFoldArgs with Lw = hop T; no reflect partners, the chain of rfx_loop_core.h
 hipError_t launch_spec_loss_loop_fold(const MelBwdFoldArgs& a, hipStream_t stream);
+
+// inverse spectrogram (rfx_istft.hip, arithmetic in rfx_istft_core.h).  launch_istft_unit_slots: the magnitude slots S
+// [nframes][sstride] of a MODE 0 frame launch that synthesises the caller's spectrum as it is - 1 where pos_bin holds a bin, 0 in the
+// padding.  sstride a multiple of four, S 16-byte aligned.
+hipError_t launch_istft_unit_slots(float* S, const int* pos_bin, long long nframes, int sstride, hipStream_t stream);
+// the staging of the backward: g (rows, valid) -> u, `total` = rows * pitch floats: element col < valid of a row is g times (divide:
+// over) tab[col] (period == 0) or tab[col mod period]; the elements from valid to pitch are zeros.  u is 16-byte aligned and holds a
+// whole number of 16 bytes (up to three floats behind `total` are written as zeros)
+struct IstftStageArgs {
+  const float* g;
+  const float* tab;
+  float* u;
+  long long total;
+  int pitch, valid, period, divide;
+};
+hipError_t launch_istft_stage(const IstftStageArgs& a, hipStream_t stream);
+// the epilogue of the backward: frames t < T of `rows` rows of Tp analysis frames, spec [rows*Tp][xstride] -> out [rows*T][xstride]
+// times c_k unit, imaginary part 0 where c_k = 1, padding 0 (xpos_bin [xstride]: the bin of a position, -1 for padding).  xstride even,
+// spec and out 16-byte aligned.
+struct IstftGradArgs {
+  const cf* spec;
+  cf* out;
+  const int* xpos_bin;
+  int rows, T, Tp, xstride, n_fft;
+  float unit;  // istft_unit
+};
+hipError_t launch_istft_grad(const IstftGradArgs& a, hipStream_t stream);
 
 }  // namespace rfx

@@ -5,6 +5,7 @@
 #include "rfx_frame.hip.h"
 #include "rfx_kernels.h"
 #include "rfx_loop_core.h"
+#include "rfx_istft_core.h"
 
 namespace rfx {
 
@@ -118,6 +119,9 @@ constexpr bool kFwdIdxRegs = (RFX_FWD_OPT & 16) != 0;  // PK: the packed positio
 #define RFX_FWDK_LOOP 1
 #include "rfx_stft_kernels.hip.h"
 #undef RFX_FWDK_LOOP
+#define RFX_FWDK_LOOP 2  // stft_zero_kernel: the zero-extended analysis of rfx_istft_backward
+#include "rfx_stft_kernels.hip.h"
+#undef RFX_FWDK_LOOP
 
 // (B, T, Mpad) frame-major mel amplitudes -> the reference's (B, M, T): 64 x 64 tiles through LDS, both sides coalesced
 __global__ void __launch_bounds__(256) mel_transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int T, int M, int Mpad) {
@@ -175,7 +179,8 @@ hipError_t prepare_frame_kernels() {
   for (const void* fn : {(const void*)stft_kernel, (const void*)stft_mel_kernel, (const void*)stft_mel2_kernel<kKbMaskLow, true>,
                          (const void*)stft_mel2_kernel<kKbMaskLow, false>, (const void*)stft_mel2_kernel<kKbMaskAll, false>,
                          (const void*)stft_loop_kernel, (const void*)stft_mel_loop_kernel, (const void*)stft_mel2_loop_kernel<kKbMaskLow, true>,
-                         (const void*)stft_mel2_loop_kernel<kKbMaskLow, false>, (const void*)stft_mel2_loop_kernel<kKbMaskAll, false>}) {
+                         (const void*)stft_mel2_loop_kernel<kKbMaskLow, false>, (const void*)stft_mel2_loop_kernel<kKbMaskAll, false>,
+                         (const void*)stft_zero_kernel}) {
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kFrameDynLdsBytes);
     if (e != hipSuccess) return e;
   }
@@ -192,6 +197,12 @@ hipError_t launch_stft(const StftArgs& a, hipStream_t stream) {
 hipError_t launch_stft_loop(const StftArgs& a, hipStream_t stream) {
   const int chunks = (a.T + a.frames_per_block - 1) / a.frames_per_block;
   hipLaunchKernelGGL(stft_loop_kernel, dim3(a.B * chunks), dim3(kThreads), kFrameDynLdsBytes, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_stft_zero(const StftArgs& a, hipStream_t stream) {
+  const int chunks = (a.T + a.frames_per_block - 1) / a.frames_per_block;
+  hipLaunchKernelGGL(stft_zero_kernel, dim3(a.B * chunks), dim3(kThreads), kFrameDynLdsBytes, stream, a);
   return hipGetLastError();
 }
 

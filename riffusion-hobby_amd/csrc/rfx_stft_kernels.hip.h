@@ -5,13 +5,21 @@
 //                                                                                               a.Lw = hop a.T samples is one period and is read modulo a.Lw (rfx_loop_core.h)
 // One text, chosen at compile time: the two differ in how a sample position is formed and in nothing else - the product form's
 // prefetch of the next frame's hop block (load_x) included, so a run that reaches the row's end reads on at its start.
-#if RFX_FWDK_LOOP
+//   RFX_FWDK_LOOP 2  stft_zero_kernel alone: the row of a.Lw samples is ZERO-EXTENDED (rfx_istft_core.h: zero_outside) - the analysis of
+//                    rfx_istft_backward, a.T frames whatever a.Lw is; a position outside [0, a.Lw) contributes an exact 0.0f
+#if RFX_FWDK_LOOP == 2
+#define RFX_FWDK_READ(x, p, L) zero_outside_read(x, p, L)
+#elif RFX_FWDK_LOOP
 #define RFX_FWDK_POS(p, L) loop_read_index(p, L)
+#define RFX_FWDK_READ(x, p, L) x[RFX_FWDK_POS(p, L)]
 #else
 #define RFX_FWDK_POS(p, L) reflect_index(p, L)
+#define RFX_FWDK_READ(x, p, L) x[RFX_FWDK_POS(p, L)]
 #endif
 // ---- forward STFT: frame t of clip b is centred on sample 441*t of the reflect-padded waveform
-#if RFX_FWDK_LOOP
+#if RFX_FWDK_LOOP == 2
+__global__ void __launch_bounds__(kThreads) stft_zero_kernel(StftArgs a) {
+#elif RFX_FWDK_LOOP
 __global__ void __launch_bounds__(kThreads) stft_loop_kernel(StftArgs a) {
 #else
 __global__ void __launch_bounds__(kThreads) stft_kernel(StftArgs a) {
@@ -32,8 +40,7 @@ __global__ void __launch_bounds__(kThreads) stft_kernel(StftArgs a) {
     float u[10];
 #pragma unroll
     for (int j = 0; j < 10; ++j) {
-      const int p = RFX_FWDK_POS((fr + j - kHalfHops) * kHop + t.npr, a.Lw);
-      u[j] = x[p] * winp[j * kHop];
+      u[j] = RFX_FWDK_READ(x, (fr + j - kHalfHops) * kHop + t.npr, a.Lw) * winp[j * kHop];
     }
     cf R[21];
     frame_forward(u, R, f, t, [] {});
@@ -66,6 +73,7 @@ __global__ void __launch_bounds__(kThreads) stft_kernel(StftArgs a) {
   }
 }
 
+#if RFX_FWDK_LOOP != 2  // (the zero-extension twin is the plain transform alone)
 // ---- fused forward path (replaces Spectrogram(power=None) -> abs -> MelScale, spectrogram_converter.py:165-185):
 // the frame engine as above; the magnitudes of the frame are then parked in LDS (each thread's 21 in the cube
 // elements it has just consumed) and every thread forms the mel amplitudes of one or two filters as the banded dot product
@@ -490,4 +498,6 @@ __global__ void __launch_bounds__(kThreads, 4) stft_mel2_kernel(StftMelArgs a) {
     }
   }
 }
+#endif  // RFX_FWDK_LOOP != 2
 #undef RFX_FWDK_POS
+#undef RFX_FWDK_READ

@@ -11,6 +11,9 @@ The inverse members (InverseMelScale's SGD, Griffin-Lim) and the loop encode hav
 A fourth function, `SpectralLossFunction`, is the pair of the multi-resolution STFT loss - spectral convergence and log-magnitude L1 -
 fused with the transform (include/rfx.h, "FUSED SPECTRAL LOSSES"): the forward leaves three double sums per row, the backward is the
 fused backward with another per-bin factor.  It serves the circular STFT too: the loop STFT's only backward.
+
+A fifth, `IstftFunction`, is the inverse spectrogram (include/rfx.h, "INVERSE SPECTROGRAM"): complex STFT -> audio, plain and loop.  The
+map is linear, so it saves nothing and its backward is the adjoint.
 """
 import typing as T
 
@@ -121,6 +124,34 @@ def spectral_losses(plan: T.Any, wave: torch.Tensor, slots: torch.Tensor, log_fl
         return SpectralLossFunction.apply(plan, wave, slots, log_floor, loop, n)
     sums = plan.spectral_loss_sums(wave.detach(), slots, log_floor, loop)
     return convergence_from_sums(sums[:, 0], sums[:, 1]), sums[:, 2] / n
+
+
+class IstftFunction(torch.autograd.Function):
+    """(B, n_stft, T) complex64 -> (B, L) float32, torch.istft(center=True) or with `loop` the circular synthesis (include/rfx.h,
+    "INVERSE SPECTROGRAM").  The map is linear: nothing is saved, the backward is its adjoint (rfx_istft_backward) and returns torch's
+    complex gradient dL/dRe + i dL/dIm."""
+
+    @staticmethod
+    def forward(ctx: T.Any, plan: T.Any, spec: torch.Tensor, loop: bool) -> torch.Tensor:  # type: ignore[override]
+        B, _, Tn = spec.shape
+        ctx.plan, ctx.shape, ctx.loop = plan, (B, Tn), loop
+        return plan.istft(plan.pack_complex(spec), B, Tn, loop)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: T.Any, grad: torch.Tensor) -> T.Tuple[None, torch.Tensor, None]:  # type: ignore[override]
+        B, Tn = ctx.shape
+        slots = ctx.plan.istft_backward(grad.to(torch.float32).contiguous(), B, Tn, ctx.loop)
+        return None, ctx.plan.unpack_complex(slots, B, Tn), None
+
+
+def istft(plan: T.Any, spec: torch.Tensor, loop: bool = False) -> torch.Tensor:
+    """the (B, L) waveform of a (B, n_stft, T) complex64 spectrogram; with a spectrum that requires grad the result carries a
+    grad_fn, otherwise the forward call alone"""
+    if wants_grad(spec):
+        return IstftFunction.apply(plan, spec, loop)
+    B, _, Tn = spec.shape
+    return plan.istft(plan.pack_complex(spec.detach()), B, Tn, loop)
 
 
 def stft(plan: T.Any, wave: torch.Tensor) -> torch.Tensor:

@@ -405,6 +405,17 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_mel_from_waveform_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_mel_from_waveform_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_debug_mel_adjoint": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int32)]),
+    # inverse spectrogram (riffusion/_autograd.py: IstftFunction)
+    "rfx_istft_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_istft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_istft_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_istft_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_istft_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_istft_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_istft_backward_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_istft_backward_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_debug_istft_backward_padded_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_debug_istft_backward_padded": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     # fused spectral losses (riffusion/_autograd.py: SpectralLossFunction)
     "rfx_spectral_loss_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1134,6 +1145,54 @@ class Plan:
         with self._workspace(self.lib.rfx_mel_from_waveform_backward_workspace_bytes(self.handle, B, Lw)) as ws:
             check(self.lib.rfx_mel_from_waveform_backward(self.handle, wave.data_ptr(), g.data_ptr(), B, Lw, out.data_ptr(), ws.data_ptr(),
                                                           ws.numel(), self._stream()))
+        return out
+
+    # ---- inverse spectrogram (include/rfx.h "INVERSE SPECTROGRAM"; riffusion/_autograd.py: IstftFunction) ----
+    def _istft_samples(self, B: int, Tn: int, loop: bool) -> int:
+        """samples per row of an inverse-spectrogram call, or its refusal before any device work"""
+        if B < 0 or Tn < 1:
+            raise ValueError(f"expected B >= 0 rows of Tn >= 1 frames, got B = {B}, Tn = {Tn}")
+        if loop:
+            if self.griffinlim_engine == "chirp-z":
+                raise RuntimeError("the chirp-z engine has no loop synthesis (RFX_ERR_UNSUPPORTED)")
+            check_loop_frames(self.hop_length, self.n_fft, Tn)
+        L = self.output_samples(Tn, loop)
+        if L < 1:
+            raise ValueError(f"{Tn} frames give no sample: a plain call needs hop_length * (Tn - 1) + n_fft % 2 >= 1")
+        return L
+
+    def istft(self, spec_slots: torch.Tensor, B: int, Tn: int, loop: bool = False) -> torch.Tensor:
+        """rfx_istft, or with `loop` rfx_istft_loop: a complex spectrogram in slot layout (`pack_complex` of a (B, n_stft, Tn) tensor,
+        or what `stft` returns), B * Tn frames -> the (B, L) float32 waveform torch.istft(center=True) gives, L = `output_samples`."""
+        x = self._chk(spec_slots, torch.complex64)
+        L = self._istft_samples(B, Tn, loop)
+        if x.numel() != B * Tn * self.frame_stride:
+            raise ValueError(f"expected {B} * {Tn} frames of {self.frame_stride} complex slots, got {tuple(x.shape)}")
+        out = torch.empty((B, L), dtype=torch.float32, device=self.device)
+        query, entry = (self.lib.rfx_istft_loop_workspace_bytes, self.lib.rfx_istft_loop) if loop else (self.lib.rfx_istft_workspace_bytes, self.lib.rfx_istft)
+        if B:
+            with self._workspace(query(self.handle, B, Tn)) as ws:
+                check(entry(self.handle, x.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    def istft_backward(self, grad_wave: torch.Tensor, B: int, Tn: int, loop: bool = False, padded: bool = False) -> torch.Tensor:
+        """rfx_istft_backward (loop: rfx_istft_backward_loop): the (B, L) float32 gradient of `istft`'s result -> the gradient of the
+        spectrum in slot layout, B * Tn frames (`unpack_complex` gives torch's (B, n_stft, Tn) dL/dRe + i dL/dIm).  `padded` (tests,
+        plain form): rfx_debug_istft_backward_padded, the circular transform of the zero-padded rows in the zero-extension twin's
+        place - the same bytes."""
+        if padded and loop:
+            raise ValueError("padded is the plain form's test route")
+        g = self._chk(grad_wave, torch.float32)
+        L = self._istft_samples(B, Tn, loop)
+        if tuple(g.shape) != (B, L):
+            raise ValueError(f"expected a ({B}, {L}) gradient, got {tuple(g.shape)}")
+        out = torch.empty((B * Tn, self.frame_stride), dtype=torch.complex64, device=self.device)
+        query, entry = ((self.lib.rfx_istft_backward_loop_workspace_bytes, self.lib.rfx_istft_backward_loop) if loop
+                        else (self.lib.rfx_debug_istft_backward_padded_workspace_bytes, self.lib.rfx_debug_istft_backward_padded) if padded
+                        else (self.lib.rfx_istft_backward_workspace_bytes, self.lib.rfx_istft_backward))
+        if B:
+            with self._workspace(query(self.handle, B, Tn)) as ws:
+                check(entry(self.handle, g.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         return out
 
     # ---- fused spectral losses (include/rfx.h "FUSED SPECTRAL LOSSES"; riffusion/_autograd.py: SpectralLossFunction) ----

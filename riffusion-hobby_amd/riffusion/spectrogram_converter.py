@@ -366,6 +366,43 @@ class SpectrogramConverter:
                                magnitude_hint=magnitude_hint, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop, peak_start=peak_start)
         return (wave, lin_slots) if return_slots else wave
 
+    # ---- inverse spectrogram: complex STFT -> audio ----------------------------------------------------
+    def waveform_from_spectrogram(self, spec: torch.Tensor, length: T.Optional[int] = None, loop: bool = False) -> torch.Tensor:
+        """
+        (..., n_stft, T) complex64 -> (..., L) float32: torchaudio.transforms.InverseSpectrogram at this converter's parameters, the
+        way back from `spectrogram_func` - torch.istft(center=True) on the device (rfx_istft), L = hop * (T - 1) (+ 1 for an odd
+        n_fft).  For code that edits the complex spectrum - a time-frequency mask, a separator's ratio mask, bins spliced from
+        another source - and for models that predict STFT coefficients.  Leading dimensions and a CPU input are handled as
+        `spectrogram_func` handles them.
+        `length`: the result is cut, or zero-padded at its end, to that many samples with torch operations, so autograd composes.
+        A cut is torch.istft(length=)'s; past L torch keeps up to n_fft // 2 samples of its untrimmed tail, this member pads zeros.
+        `loop`: the T columns are one period of a loop and the synthesis is the circular one of a loop decode: hop * T samples
+        whose end runs into their start; T must reach n_fft / hop.  The inverse of `Plan.stft(loop=True)`.
+        Differentiable: with grad mode on and a `spec` that requires grad the result carries a grad_fn whose backward runs on the
+        device (rfx_istft_backward: the synthesis is linear, nothing is saved, the gradient is its adjoint); a double backward
+        raises.  Otherwise the forward call alone runs.  `inverse_spectrogram_func` stays Griffin-Lim, on magnitudes, without a
+        gradient.
+        """
+        if not isinstance(spec, torch.Tensor) or not spec.is_complex():
+            raise ValueError("waveform_from_spectrogram takes a complex (..., n_stft, T) spectrogram; magnitudes go to inverse_spectrogram_func")
+        if spec.dim() < 2:
+            raise ValueError(f"waveform_from_spectrogram takes (..., n_stft, T), got {tuple(spec.shape)}")
+        n_stft = self.p.n_fft // 2 + 1
+        if int(spec.shape[-2]) != n_stft:
+            raise ValueError(f"expected {n_stft} linear bins, got {int(spec.shape[-2])}")
+        if int(spec.shape[-1]) < 1:
+            raise ValueError("waveform_from_spectrogram: no frames")
+        if length is not None and (int(length) != length or int(length) < 0):
+            raise ValueError(f"length must be a non-negative integer, got {length!r}")
+        plan = self._plan()
+        lead = spec.shape[:-2]
+        x = spec.reshape(-1, spec.shape[-2], spec.shape[-1]).to(self.device).to(torch.complex64)
+        wave = _autograd.istft(plan, x, loop)
+        if length is not None:
+            L = int(wave.shape[-1])
+            wave = wave[:, : int(length)] if int(length) <= L else torch.nn.functional.pad(wave, (0, int(length) - L))
+        return wave.reshape(*lead, wave.shape[-1])
+
     # ---- quality of a decode ------------------------------------------------------------------------
     @staticmethod
     def convergence_from_sums(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
