@@ -13,6 +13,7 @@
 
 #include "../../include/rfx.h"
 #include "rfx_kernels.h"
+#include "rfx_loop_core.h"
 
 namespace rfx {
 int fail(int code, const std::string& msg);  // sets rfx_last_error's text (one thread-local string, rfx_api_plan.hip); returns code
@@ -146,14 +147,22 @@ hipError_t launch_gl_out_scale(const float* win, float* out, int T, int L, hipSt
 inline int stft_frames(const rfx_plan* plan, int Lw) {
   return 1 + (Lw + 2 * (plan->p.n_fft / 2) - plan->p.n_fft) / plan->p.hop_length;
 }
+// the two forms of a forward call - plain: the row is reflect-padded, loop: the row is one period (rfx_loop_core.h) - in frames ...
+inline int fwd_frames(const rfx_plan* plan, int Lw, bool loop) {
+  return loop ? loop_samples_frames(plan->p.hop_length, plan->p.n_fft, Lw) : stft_frames(plan, Lw);
+}
+// ... and in the row lengths they take
+inline bool fwd_length_ok(const rfx_plan* plan, int Lw, bool loop) {
+  return loop ? loop_samples_valid(plan->p.hop_length, plan->p.n_fft, Lw) : Lw > plan->p.n_fft / 2;
+}
 // workgroups of a kernel that walks frames: one per frame, at most one per resident slot of the chip
 inline int frame_blocks(long long slots, int B, int T) {
   const long long nframes = (long long)B * T;
   return (int)(nframes < slots ? nframes : slots);
 }
-// the refusal of a row length a loop forward call does not take, with the nearest lengths it does; RFX_OK for a legal one
-// (rfx_api_forward.hip; the loop loss backward of rfx_api_backward.hip words its refusal the same way)
-int loop_length_refusal(const rfx_plan* plan, int Lw, const char* who);
+// the refusal of a row length fwd_length_ok does not pass; RFX_OK for a legal one (rfx_api_forward.hip).  Plain: "reflect padding
+// needs more than n_fft/2 = N samples".  Loop: the refusal names the nearest legal lengths.
+int fwd_length_refusal(const rfx_plan* plan, int Lw, bool loop, const char* who);
 // the zero-extension twin of the plan's forward frame launch (rfx_api_forward.hip): rows of L samples, T frames, the complex spectrum
 int stft_zero_extended(const rfx_plan* plan, const float* d_rows, int B, int L, int T, void* d_spec_slots, void* stream);
 inline long long fam_slot_count(const rfx_plan* plan) { return (long long)plan->num_cus * plan->fam_wgs_per_cu; }
@@ -170,6 +179,12 @@ int peak_start_run(const rfx_plan* plan, int layout, const float* d_mag, int B, 
 // A workspace layout is a plain struct of byte offsets and `total`, returned by value from one function of (plan, shape): the
 // rfx_*_workspace_bytes query answers its total, the driver takes every pointer from its fields.  A shape the query answers 0
 // for gives the all-zero layout.  Carve deals the parts out: each starts on a 256-byte boundary.
+// Rows walked in groups of whole rows that fill at most `bytes`: the rows of a group - at least one, at most B, at most `cap`.
+inline int group_rows(size_t bytes, size_t row_bytes, int B, size_t cap = (size_t)-1) {
+  size_t rows = bytes / row_bytes;
+  rows = rows < 1 ? 1 : rows > cap ? cap : rows;
+  return (int)(rows > (size_t)B ? (size_t)B : rows);
+}
 struct Carve {
   size_t at = 0;
   size_t take(size_t bytes) {

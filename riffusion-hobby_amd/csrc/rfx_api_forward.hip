@@ -1,6 +1,6 @@
 // rfx_api_forward.hip - the C ABI of librfx.so (include/rfx.h), forward half: layout conversion, STFT, the mel projections and
-// the image of a waveform or of int16 clips, and the spectral error of a decode.  Host code only: the drivers that sequence
-// the kernels.
+// the image of a waveform or of int16 clips, and the per-row spectral sums (spectral error, spectral loss).  Host code only: the
+// drivers that sequence the kernels.
 #include "rfx_api.h"
 #include "rfx_loop_core.h"
 #include "rfx_spec_loss_core.h"
@@ -10,13 +10,7 @@ using namespace rfx;
 // ---- the two forms of every forward entry.  Plain: the row is reflect-padded by n_fft / 2 on both sides (torch.stft center=True) and
 // must be longer than that.  Loop (the *_loop entries; rfx_loop_core.h): the row is one period of exactly hop T samples and is read
 // modulo its length.  Each driver below is written once and takes the form as `loop`; the two differ in the frame count, the length
-// rule and the launcher (the loop twin of the same kernel).
-static int fwd_frames(const rfx_plan* plan, int Lw, bool loop) {
-  return loop ? loop_samples_frames(plan->p.hop_length, plan->p.n_fft, Lw) : stft_frames(plan, Lw);
-}
-static bool fwd_length_ok(const rfx_plan* plan, int Lw, bool loop) {
-  return loop ? loop_samples_valid(plan->p.hop_length, plan->p.n_fft, Lw) : Lw > plan->p.n_fft / 2;
-}
+// rule (fwd_frames, fwd_length_ok, fwd_length_refusal: rfx_api.h) and the launcher (the loop twin of the same kernel).
 // the refusal of a row length a loop forward call does not take, with the nearest lengths it does
 static int loop_samples_refusal(int hop, int n_fft, int Lw, const char* who) {
   if (loop_samples_valid(hop, n_fft, Lw)) return RFX_OK;
@@ -25,6 +19,13 @@ static int loop_samples_refusal(int hop, int n_fft, int Lw, const char* who) {
                                    std::to_string(hop) + ", n_fft " + std::to_string(n_fft) + "), got " + std::to_string(Lw) + ": the nearest legal lengths are " +
                                    (below ? std::to_string(below) + " (" + std::to_string(below / hop) + " frames)" : std::string("none")) + " below and " +
                                    std::to_string(above) + " (" + std::to_string(above / hop) + " frames) above");
+}
+// the refusal of a row length a forward call of either form does not take; RFX_OK for a legal one
+int rfx::fwd_length_refusal(const rfx_plan* plan, int Lw, bool loop, const char* who) {
+  if (loop) return loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who);
+  if (Lw > plan->p.n_fft / 2) return RFX_OK;
+  // torch.stft(center=True, pad_mode="reflect") raises when the pad n_fft/2 is not smaller than the input
+  return fail(RFX_ERR_INVALID, std::string(who) + ": reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
 }
 int rfx_debug_loop_samples(const rfx_params* params, int Lw) {
   if (!params || params->hop_length <= 0 || params->n_fft <= 0) return fail(RFX_ERR_INVALID, "rfx_debug_loop_samples: bad argument");
@@ -90,12 +91,7 @@ enum FwdRule { kFwdReflect = 0, kFwdLoop = 1, kFwdZero = 2 };
 static int stft_launch(const rfx_plan* plan, const float* d_wave, int B, int Lw, int T, float* d_mag_slots, void* d_spec_slots, void* stream, int rule);
 static int stft_run(const rfx_plan* plan, const float* d_wave, int B, int Lw, float* d_mag_slots, void* d_spec_slots, void* stream, bool loop) {
   if (!plan || !d_wave || B <= 0) return fail(RFX_ERR_INVALID, loop ? "rfx_stft_loop: bad argument" : "rfx_stft: bad argument");
-  if (loop) {
-    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, "rfx_stft_loop")) return rc;
-  } else if (Lw <= plan->p.n_fft / 2) {
-    // torch.stft(center=True, pad_mode="reflect") raises when the pad n_fft/2 is not smaller than the input
-    return fail(RFX_ERR_INVALID, "rfx_stft: reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
-  }
+  if (int rc = fwd_length_refusal(plan, Lw, loop, loop ? "rfx_stft_loop" : "rfx_stft")) return rc;
   RFX_ON_DEVICE(plan->device);
   return stft_launch(plan, d_wave, B, Lw, fwd_frames(plan, Lw, loop), d_mag_slots, d_spec_slots, stream, loop ? kFwdLoop : kFwdReflect);
 }
@@ -233,11 +229,9 @@ static int mel_forward(const rfx_plan* plan, const float* d_wave, int B, int Lw,
   const std::string who = loop ? "rfx_mel_from_waveform_loop" : "rfx_mel_from_waveform";
   if (!plan || !d_wave || !d_workspace || (!d_mel_out && !mel_tm_out)) return fail(RFX_ERR_INVALID, who + ": null argument");
   if (!plan->d_melfb) return fail(RFX_ERR_INVALID, who + ": plan was created without a mel filterbank");
-  if (loop)
-    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who.c_str())) return rc;
+  if (int rc = fwd_length_refusal(plan, Lw, loop, who.c_str())) return rc;
   const MelLayout w = mel_forward_layout(plan, B, Lw, loop);
-  if (workspace_bytes < w.total || !fwd_length_ok(plan, Lw, loop))
-    return fail(!fwd_length_ok(plan, Lw, loop) ? RFX_ERR_INVALID : RFX_ERR_WORKSPACE, who + ": input too short or workspace too small");
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, who + ": workspace too small");
   RFX_ON_DEVICE(plan->device);
   hipStream_t stream = (hipStream_t)stream_;
   float* mag = (float*)((char*)d_workspace + w.mag);
@@ -357,11 +351,7 @@ static int image_from_waveform_run(const rfx_plan* plan, const float* d_wave, in
   if (!plan || !d_wave || !d_thresholds255 || !d_clip_max || !d_img_out || !d_workspace || N <= 0)
     return fail(RFX_ERR_INVALID, who + ": bad argument");
   if (!plan->d_melfb) return fail(RFX_ERR_INVALID, who + ": plan was created without a mel filterbank");
-  if (loop) {
-    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who.c_str())) return rc;
-  } else if (Lw <= plan->p.n_fft / 2) {
-    return fail(RFX_ERR_INVALID, "rfx_image_from_waveform: input too short");
-  }
+  if (int rc = fwd_length_refusal(plan, Lw, loop, who.c_str())) return rc;
   const ImageFwdLayout w = image_from_waveform_layout(plan, N, stereo, Lw, loop);
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, who + ": workspace too small");
   RFX_ON_DEVICE(plan->device);
@@ -424,11 +414,7 @@ static int image_from_pcm16_clips_run(const rfx_plan* plan, const int16_t* d_pcm
   if (int rc = check_pcm_clips(who.c_str(), d_pcm, frames, in_channels, h_starts, N, Lw, C)) return rc;
   if (!plan || !d_starts || !d_thresholds255 || !d_clip_max || !d_img_out || !d_workspace)
     return fail(RFX_ERR_INVALID, who + ": null pointer");
-  if (loop) {
-    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who.c_str())) return rc;
-  } else if (Lw <= plan->p.n_fft / 2) {
-    return fail(RFX_ERR_INVALID, "rfx_image_from_pcm16_clips: clips too short");
-  }
+  if (int rc = fwd_length_refusal(plan, Lw, loop, who.c_str())) return rc;
   const ImagePcmLayout w = image_from_pcm16_clips_layout(plan, N, stereo, Lw, loop);
   if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, who + ": workspace too small");
   float* wave = reinterpret_cast<float*>((char*)d_workspace + w.wave);
@@ -469,36 +455,62 @@ int rfx_mel_scale(const rfx_plan* plan, const float* d_lin_bft, int B, int T, fl
   return mel_gemm(plan, mag, B, T, d_mel_out, stream);
 }
 
-// ---- spectral error of a decode: how far the magnitudes of a waveform are from the magnitudes it was made from -----------------
-// The plan's own forward transform of the rows into the workspace (rfx_stft: any of the three frame engines), then the reduction
-// of rfx_quality.hip over that tensor and the target.  The rows are walked in groups of whole rows whose magnitudes fill at most
-// kQualGroupBytes (at least one row), so the workspace does not grow with the batch: the transformed magnitudes of a group, then
-// the group's partial sums.  A row's result does not depend on the group it falls in (rfx_quality_core.h).
+// ---- the per-row spectral sums: how far the magnitudes of a waveform are from target magnitudes -----------------------------------
+// rfx_spectral_error[_loop] (two sums; the rows are a decode's, their length follows from T) and rfx_spectral_loss[_loop] (three sums
+// of rfx_quality_core.h; rows of any legal length) are two fronts of one driver: the plan's own forward transform of the rows into
+// the workspace (stft_run: any of the frame engines), then the reduction of rfx_quality.hip over that tensor and the target.  The
+// rows are walked in groups of whole rows whose magnitudes fill at most kQualGroupBytes (at least one row), so the workspace does not
+// grow with the batch: the transformed magnitudes of a group, then the group's partial sums.  A row's result does not depend on the
+// group it falls in (rfx_quality_core.h).
 constexpr size_t kQualGroupBytes = (size_t)128 << 20;
-struct SpectralErrorLayout {
+struct SumsLayout {
   size_t mag, partials, total;
   int group_rows;
 };
-static SpectralErrorLayout spectral_error_layout(const rfx_plan* plan, int B, int T, bool loop) {
-  SpectralErrorLayout l{};
-  if (B <= 0 || T < 2) return l;
-  if (loop && (!loop_valid(plan->p.hop_length, T, plan->p.n_fft) || (long long)plan->p.hop_length * T > 0x7fffffffLL)) return l;
+static SumsLayout sums_layout(const rfx_plan* plan, int B, int T, int nsums) {
+  SumsLayout l{};
   const size_t row_bytes = (size_t)T * plan->frame_stride * sizeof(float);
-  size_t rows = kQualGroupBytes / row_bytes;
-  rows = rows < 1 ? 1 : rows > (size_t)B ? (size_t)B : rows;
-  l.group_rows = (int)rows;
+  l.group_rows = group_rows(kQualGroupBytes, row_bytes, B);
   Carve c;
-  l.mag = c.take(rows * row_bytes);
-  l.partials = c.take(qual_partials_bytes(l.group_rows, T));
+  l.mag = c.take(l.group_rows * row_bytes);
+  l.partials = c.take(qual_partials_bytes(l.group_rows, T, nsums));
   l.total = c.at;
   return l;
 }
-size_t rfx_spectral_error_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? spectral_error_layout(plan, B, T, false).total : 0; }
-size_t rfx_spectral_error_loop_workspace_bytes(const rfx_plan* plan, int B, int T) { return plan ? spectral_error_layout(plan, B, T, true).total : 0; }
+// B > 0 rows of Lw samples, T frames each, on checked arguments: the workspace check and the walk
+static int sums_run(const std::string& who, const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, int T, int nsums,
+                    float log_floor, double* d_sums_out, void* d_workspace, size_t workspace_bytes, void* stream, bool loop) {
+  const SumsLayout w = sums_layout(plan, B, T, nsums);
+  if (workspace_bytes < w.total)
+    return fail(RFX_ERR_WORKSPACE, who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(w.total) + " needed)");
+  RFX_ON_DEVICE(plan->device);
+  float* mag = reinterpret_cast<float*>((char*)d_workspace + w.mag);
+  void* partials = (char*)d_workspace + w.partials;
+  const size_t row_elems = (size_t)T * plan->frame_stride;
+  for (int r0 = 0; r0 < B; r0 += w.group_rows) {
+    const int rows = B - r0 < w.group_rows ? B - r0 : w.group_rows;
+    if (int rc = stft_run(plan, d_wave + (size_t)r0 * Lw, rows, Lw, mag, nullptr, stream, loop)) return rc;
+    RFX_HIP(launch_spectral_sums(mag, d_mag_slots + (size_t)r0 * row_elems, rows, T, plan->frame_stride, plan->n_stft, plan->generic, nsums, log_floor,
+                                 partials, d_sums_out + (size_t)nsums * r0, (hipStream_t)stream));
+  }
+  return RFX_OK;
+}
+
+// rfx_spectral_error: T >= 2 frames, rows of the samples a decode of T frames gives
+static bool spectral_error_shape_ok(const rfx_plan* plan, int B, int T, bool loop) {
+  if (B <= 0 || T < 2) return false;
+  return !loop || (loop_valid(plan->p.hop_length, T, plan->p.n_fft) && (long long)plan->p.hop_length * T <= 0x7fffffffLL);
+}
+size_t rfx_spectral_error_workspace_bytes(const rfx_plan* plan, int B, int T) {
+  return plan && spectral_error_shape_ok(plan, B, T, false) ? sums_layout(plan, B, T, 2).total : 0;
+}
+size_t rfx_spectral_error_loop_workspace_bytes(const rfx_plan* plan, int B, int T) {
+  return plan && spectral_error_shape_ok(plan, B, T, true) ? sums_layout(plan, B, T, 2).total : 0;
+}
 
 // loop: d_wave rows are the hop T samples of a loop decode, transformed by the loop forward call (stft_run)
-static int spectral_error_run(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out, void* d_workspace,
-                              size_t workspace_bytes, void* stream, bool loop) {
+static int spectral_error_front(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out, void* d_workspace,
+                                size_t workspace_bytes, void* stream, bool loop) {
   const std::string who = loop ? "rfx_spectral_error_loop" : "rfx_spectral_error";
   if (B < 0) return fail(RFX_ERR_INVALID, who + ": B is negative");
   if (B == 0) return RFX_OK;
@@ -508,7 +520,7 @@ static int spectral_error_run(const rfx_plan* plan, const float* d_wave, const f
   if (loop) {
     const long long P = (long long)plan->p.hop_length * T;
     if (P > 0x7fffffffLL) return fail(RFX_ERR_INVALID, who + ": hop_length * T does not fit an int");
-    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, (int)P, who.c_str())) return rc;
+    if (int rc = fwd_length_refusal(plan, (int)P, true, who.c_str())) return rc;
     L = (int)P;
   } else {
     L = rfx_griffinlim_output_samples(plan, T);
@@ -518,92 +530,42 @@ static int spectral_error_run(const rfx_plan* plan, const float* d_wave, const f
   }
   if (((uintptr_t)d_mag_slots | (uintptr_t)d_workspace) & 15 || ((uintptr_t)d_sums_out & 7) || (plan->frame_stride & 3))
     return fail(RFX_ERR_INVALID, who + ": d_mag_slots and d_workspace must be 16-byte aligned, d_sums_out 8-byte aligned");
-  const SpectralErrorLayout w = spectral_error_layout(plan, B, T, loop);
-  if (workspace_bytes < w.total)
-    return fail(RFX_ERR_WORKSPACE, who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(w.total) + " needed)");
-  RFX_ON_DEVICE(plan->device);
-  float* mag = reinterpret_cast<float*>((char*)d_workspace + w.mag);
-  void* partials = (char*)d_workspace + w.partials;
-  const size_t row_elems = (size_t)T * plan->frame_stride;
-  for (int r0 = 0; r0 < B; r0 += w.group_rows) {
-    const int rows = B - r0 < w.group_rows ? B - r0 : w.group_rows;
-    if (int rc = stft_run(plan, d_wave + (size_t)r0 * L, rows, L, mag, nullptr, stream, loop)) return rc;
-    RFX_HIP(launch_spectral_sums(mag, d_mag_slots + (size_t)r0 * row_elems, rows, T, plan->frame_stride, plan->n_stft, plan->generic, partials,
-                                 d_sums_out + 2 * (size_t)r0, (hipStream_t)stream));
-  }
-  return RFX_OK;
+  return sums_run(who, plan, d_wave, d_mag_slots, B, L, T, 2, 0.f, d_sums_out, d_workspace, workspace_bytes, stream, loop);
 }
 int rfx_spectral_error(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out,
                        void* d_workspace, size_t workspace_bytes, void* stream) {
-  return spectral_error_run(plan, d_wave, d_mag_slots, B, T, d_sums_out, d_workspace, workspace_bytes, stream, false);
+  return spectral_error_front(plan, d_wave, d_mag_slots, B, T, d_sums_out, d_workspace, workspace_bytes, stream, false);
 }
 int rfx_spectral_error_loop(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int T, double* d_sums_out,
                             void* d_workspace, size_t workspace_bytes, void* stream) {
-  return spectral_error_run(plan, d_wave, d_mag_slots, B, T, d_sums_out, d_workspace, workspace_bytes, stream, true);
+  return spectral_error_front(plan, d_wave, d_mag_slots, B, T, d_sums_out, d_workspace, workspace_bytes, stream, true);
 }
 
-// ---- fused spectral losses, forward: the three sums of rfx_spec_loss_core.h ----------------------------------------------------------
-// rfx_spectral_error's sequence on rows of any legal length Lw: the plan's forward transform of a group of rows into the workspace,
-// then the reduction with the third sum.  Groups of whole rows of at most kQualGroupBytes of magnitudes, as above.
-int rfx::loop_length_refusal(const rfx_plan* plan, int Lw, const char* who) {
-  return loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who);
+// rfx_spectral_loss: rows of any legal length Lw, the log floor
+static size_t spectral_loss_bytes(const rfx_plan* plan, int B, int Lw, bool loop) {
+  return plan && B > 0 && fwd_length_ok(plan, Lw, loop) ? sums_layout(plan, B, fwd_frames(plan, Lw, loop), 3).total : 0;
 }
-struct SpectralLossLayout {
-  size_t mag, partials, total;
-  int group_rows, T;
-};
-static SpectralLossLayout spectral_loss_layout(const rfx_plan* plan, int B, int Lw, bool loop) {
-  SpectralLossLayout l{};
-  if (B <= 0 || !fwd_length_ok(plan, Lw, loop)) return l;
-  l.T = fwd_frames(plan, Lw, loop);
-  const size_t row_bytes = (size_t)l.T * plan->frame_stride * sizeof(float);
-  size_t rows = kQualGroupBytes / row_bytes;
-  rows = rows < 1 ? 1 : rows > (size_t)B ? (size_t)B : rows;
-  l.group_rows = (int)rows;
-  Carve c;
-  l.mag = c.take(rows * row_bytes);
-  l.partials = c.take(spec_loss_partials_bytes(l.group_rows, l.T));
-  l.total = c.at;
-  return l;
-}
-size_t rfx_spectral_loss_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? spectral_loss_layout(plan, B, Lw, false).total : 0; }
-size_t rfx_spectral_loss_loop_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return plan ? spectral_loss_layout(plan, B, Lw, true).total : 0; }
+size_t rfx_spectral_loss_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return spectral_loss_bytes(plan, B, Lw, false); }
+size_t rfx_spectral_loss_loop_workspace_bytes(const rfx_plan* plan, int B, int Lw) { return spectral_loss_bytes(plan, B, Lw, true); }
 
-static int spectral_loss_run(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor, double* d_sums_out,
-                             void* d_workspace, size_t workspace_bytes, void* stream, bool loop) {
+static int spectral_loss_front(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor, double* d_sums_out,
+                               void* d_workspace, size_t workspace_bytes, void* stream, bool loop) {
   const std::string who = loop ? "rfx_spectral_loss_loop" : "rfx_spectral_loss";
   if (B < 0) return fail(RFX_ERR_INVALID, who + ": B is negative");
   if (B == 0) return RFX_OK;
   if (!plan || !d_wave || !d_mag_slots || !d_sums_out || !d_workspace) return fail(RFX_ERR_INVALID, who + ": null argument");
-  if (loop) {
-    if (int rc = loop_samples_refusal(plan->p.hop_length, plan->p.n_fft, Lw, who.c_str())) return rc;
-  } else if (Lw <= plan->p.n_fft / 2) {
-    return fail(RFX_ERR_INVALID, who + ": reflect padding needs more than n_fft/2 = " + std::to_string(plan->p.n_fft / 2) + " samples");
-  }
+  if (int rc = fwd_length_refusal(plan, Lw, loop, who.c_str())) return rc;
   if (!spec_loss_floor_ok(log_floor))
     return fail(RFX_ERR_INVALID, who + ": log_floor must be 0 (no log term) or a finite value of at least 1e-18, got " + std::to_string(log_floor));
   if (((uintptr_t)d_mag_slots | (uintptr_t)d_workspace) & 15 || ((uintptr_t)d_sums_out & 7) || ((uintptr_t)d_wave & 3) || (plan->frame_stride & 3))
     return fail(RFX_ERR_INVALID, who + ": d_mag_slots and d_workspace must be 16-byte aligned, d_sums_out 8-byte and d_wave 4-byte aligned");
-  const SpectralLossLayout w = spectral_loss_layout(plan, B, Lw, loop);
-  if (workspace_bytes < w.total)
-    return fail(RFX_ERR_WORKSPACE, who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(w.total) + " needed)");
-  RFX_ON_DEVICE(plan->device);
-  float* mag = reinterpret_cast<float*>((char*)d_workspace + w.mag);
-  void* partials = (char*)d_workspace + w.partials;
-  const size_t row_elems = (size_t)w.T * plan->frame_stride;
-  for (int r0 = 0; r0 < B; r0 += w.group_rows) {
-    const int rows = B - r0 < w.group_rows ? B - r0 : w.group_rows;
-    if (int rc = stft_run(plan, d_wave + (size_t)r0 * Lw, rows, Lw, mag, nullptr, stream, loop)) return rc;
-    RFX_HIP(launch_spec_loss_sums(mag, d_mag_slots + (size_t)r0 * row_elems, rows, w.T, plan->frame_stride, plan->n_stft, plan->generic, log_floor,
-                                  partials, d_sums_out + 3 * (size_t)r0, (hipStream_t)stream));
-  }
-  return RFX_OK;
+  return sums_run(who, plan, d_wave, d_mag_slots, B, Lw, fwd_frames(plan, Lw, loop), 3, log_floor, d_sums_out, d_workspace, workspace_bytes, stream, loop);
 }
 int rfx_spectral_loss(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor, double* d_sums_out,
                       void* d_workspace, size_t workspace_bytes, void* stream) {
-  return spectral_loss_run(plan, d_wave, d_mag_slots, B, Lw, log_floor, d_sums_out, d_workspace, workspace_bytes, stream, false);
+  return spectral_loss_front(plan, d_wave, d_mag_slots, B, Lw, log_floor, d_sums_out, d_workspace, workspace_bytes, stream, false);
 }
 int rfx_spectral_loss_loop(const rfx_plan* plan, const float* d_wave, const float* d_mag_slots, int B, int Lw, float log_floor, double* d_sums_out,
                            void* d_workspace, size_t workspace_bytes, void* stream) {
-  return spectral_loss_run(plan, d_wave, d_mag_slots, B, Lw, log_floor, d_sums_out, d_workspace, workspace_bytes, stream, true);
+  return spectral_loss_front(plan, d_wave, d_mag_slots, B, Lw, log_floor, d_sums_out, d_workspace, workspace_bytes, stream, true);
 }

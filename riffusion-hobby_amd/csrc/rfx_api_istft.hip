@@ -31,10 +31,12 @@ static int istft_samples(const rfx_plan* plan, int T, bool loop) {
   const long long L = (long long)plan->p.hop_length * (T - 1) + (plan->p.n_fft & 1);
   return L > 0 && L + (long long)plan->p.n_fft + 4LL * plan->p.hop_length <= 0x7fffffffLL ? (int)L : 0;
 }
-static size_t istft_group_rows(size_t row_bytes, int B) {
-  size_t rows = kIstftGroupBytes / row_bytes;
-  rows = rows < 1 ? 1 : rows > kIstftGroupRows ? kIstftGroupRows : rows;
-  return rows > (size_t)B ? (size_t)B : rows;
+// the table both directions take once per call: the fold's of the forward, the staging's of the backward - L floats of the envelope
+// rule of the engine's own fold, loop: the hop floats of the period's
+static hipError_t istft_table(const rfx_plan* plan, float* tab, int T, int L, bool loop, hipStream_t stream) {
+  const bool spec = istft_specialised(plan);
+  if (loop) return launch_loop_renv(plan->d_win, tab, plan->p.n_fft, plan->p.win_length, plan->p.hop_length, spec ? 2.0f / (float)plan->p.n_fft : 1.f, stream);
+  return spec ? launch_gl_out_scale(plan->d_win, tab, T, L, stream) : launch_gen_env(plan->d_win, tab, plan->gg, T, L, stream);
 }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------------
@@ -49,7 +51,7 @@ static IstftLayout istft_layout(const rfx_plan* plan, int B, int T, bool loop) {
   l.L = istft_samples(plan, T, loop);
   if (l.L <= 0) return IstftLayout{};
   const size_t smag_row = (size_t)T * plan->mb_sstride * sizeof(float), frames_row = (size_t)T * mel_bwd_frame_pitch(plan) * sizeof(float);
-  l.group_rows = (int)istft_group_rows(smag_row + frames_row, B);
+  l.group_rows = group_rows(kIstftGroupBytes, smag_row + frames_row, B, kIstftGroupRows);
   Carve c;
   l.tab = c.take((size_t)(loop ? plan->p.hop_length : l.L) * sizeof(float));
   l.smag = c.take((size_t)l.group_rows * smag_row);
@@ -85,14 +87,12 @@ static int istft_run(const rfx_plan* plan, const void* d_spec_slots, int B, int 
     return fail(RFX_ERR_WORKSPACE, w + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(l.total) + " needed)");
   RFX_ON_DEVICE(plan->device);
   hipStream_t stream = (hipStream_t)stream_;
-  const int L = l.L, n_fft = plan->p.n_fft, win = plan->p.win_length, hop = plan->p.hop_length;
+  const int L = l.L;
   const bool spec = istft_specialised(plan);
   float* tab = reinterpret_cast<float*>((char*)d_workspace + l.tab);
   float* smag = reinterpret_cast<float*>((char*)d_workspace + l.smag);
   float* frames = reinterpret_cast<float*>((char*)d_workspace + l.frames);
-  if (loop) RFX_HIP(launch_loop_renv(plan->d_win, tab, n_fft, win, hop, spec ? 2.0f / (float)n_fft : 1.f, stream));
-  else if (spec) RFX_HIP(launch_gl_out_scale(plan->d_win, tab, T, L, stream));
-  else RFX_HIP(launch_gen_env(plan->d_win, tab, plan->gg, T, L, stream));
+  RFX_HIP(istft_table(plan, tab, T, L, loop, stream));
   const size_t row_slots = (size_t)T * plan->frame_stride;
   for (int r0 = 0; r0 < B; r0 += l.group_rows) {
     const int rows = B - r0 < l.group_rows ? B - r0 : l.group_rows;
@@ -133,7 +133,7 @@ static IstftBwdLayout istft_backward_layout(const rfx_plan* plan, int B, int T, 
   if (l.L <= 0) return IstftBwdLayout{};
   l.Tp = padded ? istft_pad_frames(plan->p.hop_length, plan->p.n_fft, l.L) : T;
   const size_t u_row = (padded ? (size_t)l.Tp * plan->p.hop_length : (size_t)l.L) * sizeof(float), spec_row = (size_t)l.Tp * plan->frame_stride * sizeof(cf);
-  l.group_rows = (int)istft_group_rows(u_row + spec_row, B);
+  l.group_rows = group_rows(kIstftGroupBytes, u_row + spec_row, B, kIstftGroupRows);
   Carve c;
   l.tab = c.take((size_t)(loop ? plan->p.hop_length : l.L) * sizeof(float));
   l.u = c.take((size_t)l.group_rows * u_row + 16);  // the staging writes whole 16 bytes
@@ -162,7 +162,7 @@ static int istft_backward_run(const rfx_plan* plan, const float* d_grad_wave, in
   const IstftBwdLayout l = istft_backward_layout(plan, B, T, loop, padded);
   if (workspace_bytes < l.total)
     return fail(RFX_ERR_WORKSPACE, w + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + std::to_string(l.total) + " needed)");
-  const int L = l.L, n_fft = plan->p.n_fft, win = plan->p.win_length, hop = plan->p.hop_length;
+  const int L = l.L, n_fft = plan->p.n_fft, hop = plan->p.hop_length;
   const int P = padded ? l.Tp * hop : L;  // samples per staged row; the circular forms: the period, a whole number of hops of at least n_fft
   // (the last refusal: nothing below this line answers anything but a HIP error - rfx_stft_loop's own length rule holds by the layout)
   if ((loop || padded) && !loop_samples_valid(hop, n_fft, P)) return fail(RFX_ERR_INVALID, w + ": the staged period is no whole loop");
@@ -172,9 +172,7 @@ static int istft_backward_run(const rfx_plan* plan, const float* d_grad_wave, in
   float* tab = reinterpret_cast<float*>((char*)d_workspace + l.tab);
   float* u = reinterpret_cast<float*>((char*)d_workspace + l.u);
   cf* X = reinterpret_cast<cf*>((char*)d_workspace + l.spec);
-  if (loop) RFX_HIP(launch_loop_renv(plan->d_win, tab, n_fft, win, hop, spec ? 2.0f / (float)n_fft : 1.f, stream));
-  else if (spec) RFX_HIP(launch_gl_out_scale(plan->d_win, tab, T, L, stream));
-  else RFX_HIP(launch_gen_env(plan->d_win, tab, plan->gg, T, L, stream));
+  RFX_HIP(istft_table(plan, tab, T, L, loop, stream));
   for (int r0 = 0; r0 < B; r0 += l.group_rows) {
     const int rows = B - r0 < l.group_rows ? B - r0 : l.group_rows;
     IstftStageArgs s{};

@@ -537,13 +537,15 @@ hipError_t launch_pcm_ratecv(const int16_t* in, int C_in, int64_t in_rate, int C
                              hipStream_t s);
 hipError_t launch_pcm_clips(const int16_t* pcm, int C_in, const int64_t* starts, int N, int64_t Lw, int C_out, float* wave, hipStream_t s);
 
-// spectral error (rfx_quality.hip, arithmetic and reduction shape in rfx_quality_core.h): `rows` rows of T frames of `a` and `m`,
-// fs floats per frame (a multiple of four; both tensors 16-byte aligned) -> sums[2 r] = sum (a - m)^2, sums[2 r + 1] = sum m^2
-// in double over the n_stft bins of every frame, each once (plain: bin-ordered frames, else the specialised slot layout).  Two
-// launches: one workgroup per four frames into `partials` (qual_partials_bytes), then one per row.  rows * ceil(T / 4) < 2^31.
-size_t qual_partials_bytes(int rows, int T);
-hipError_t launch_spectral_sums(const float* a, const float* m, int rows, int T, int fs, int n_stft, bool plain, void* partials, double* sums,
-                                hipStream_t s);
+// the per-row spectral sums (rfx_quality.hip, arithmetic and reduction shape in rfx_quality_core.h): `rows` rows of T frames of `a`
+// and `m`, fs floats per frame (a multiple of four; both tensors 16-byte aligned) -> sums[nsums r ..]: sum (a - m)^2, sum m^2 and,
+// with nsums == 3, sum | ln max(a, floor) - ln max(m, floor) | (floor == 0: no logarithm, 0), in double over the n_stft bins of every
+// frame, each once (plain: bin-ordered frames, else the specialised slot layout).  nsums is 2 (floor not read) or 3; the first two
+// sums are the same bits for either.  Two launches: one workgroup per four frames into `partials` (qual_partials_bytes), then one
+// per row.  rows * ceil(T / 4) < 2^31.
+size_t qual_partials_bytes(int rows, int T, int nsums);
+hipError_t launch_spectral_sums(const float* a, const float* m, int rows, int T, int fs, int n_stft, bool plain, int nsums, float floor, void* partials,
+                                double* sums, hipStream_t s);
 
 // guide staging of a guided Griffin-Lim call (rfx_guide.hip, arithmetic in rfx_guide_core.h): row r of guide (B rows of
 // guide_samples floats, `stride` elements apart), cut or zero-padded to L samples and times the power of two that brings its peak
@@ -611,21 +613,17 @@ hipError_t launch_mel_bwd_spec(const MelBwdSpecArgs& a, hipStream_t stream);
 hipError_t launch_mel_bwd_bank(const float* g_mel, float* out_bft, const int* first, const int* count, const float* wt, int width, int B, int M,
                                int T, int n_stft, hipStream_t stream);
 // the adjoint fold: frames [B*T][fpitch], window sample i of a frame at fshift + i -> out (B, Lw).  win: the plan's window where the
-// frames come un-windowed (specialised engine), null where the frame launch has applied it
+// frames come un-windowed (specialised engine), null where the frame launch has applied it.  circular: the fold of a loop row,
+// Lw = hop T - no reflect partners, the chain of rfx_loop_core.h
 struct MelBwdFoldArgs {
   const float* frames;
   const float* win;
   float* out;
   int fpitch, fshift, left, win_len, hop, h, B, T, Lw;
 };
-hipError_t launch_mel_bwd_fold(const MelBwdFoldArgs& a, hipStream_t stream);
+hipError_t launch_mel_bwd_fold(const MelBwdFoldArgs& a, bool circular, hipStream_t stream);
 
-// fused spectral losses (arithmetic in rfx_spec_loss_core.h).  launch_spec_loss_sums (rfx_quality.hip): launch_spectral_sums with a
-// third sum, sums[3 r + 2] = sum | ln max(a, floor) - ln max(m, floor) | (floor == 0: no logarithm, 0); the first two are
-// launch_spectral_sums' bit for bit; partials: spec_loss_partials_bytes.
-size_t spec_loss_partials_bytes(int rows, int T);
-hipError_t launch_spec_loss_sums(const float* a, const float* m, int rows, int T, int fs, int n_stft, bool plain, float floor, void* partials, double* sums,
-                                 hipStream_t s);
+// fused spectral losses (arithmetic in rfx_spec_loss_core.h; the sums are launch_spectral_sums with nsums == 3).
 // launch_spec_loss_slots (rfx_mel_bwd.hip): the magnitude slots S [B*T][sstride] of a MODE 0 frame launch that takes the spectrum
 // X [B*T][xstride] itself as its angles - weight[k] (dL/da) / a per slot, from a = |the complex value the slot will multiply|, the
 // target's slot and the row's coefficients coef[2 b] = c_sc, coef[2 b + 1] = c_lg.  target: [B*T][xstride] in the plan's magnitude
@@ -644,8 +642,6 @@ struct SpecLossSlotArgs {
   float floor;  // 0: no log term
 };
 hipError_t launch_spec_loss_slots(const SpecLossSlotArgs& a, hipStream_t stream);
-// the circular adjoint fold of a loop row: MelBwdFoldArgs with Lw = hop T; no reflect partners, the chain of rfx_loop_core.h
-hipError_t launch_spec_loss_loop_fold(const MelBwdFoldArgs& a, hipStream_t stream);
 
 // inverse spectrogram (rfx_istft.hip, arithmetic in rfx_istft_core.h).  launch_istft_unit_slots: the magnitude slots S
 // [nframes][sstride] of a MODE 0 frame launch that synthesises the caller's spectrum as it is - 1 where pos_bin holds a bin, 0 in the

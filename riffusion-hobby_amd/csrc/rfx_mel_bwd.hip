@@ -11,6 +11,8 @@
 //                         S' is the one-sided weights alone and the angles are the caller's gradient.
 //   mel_bwd_bank_kernel   step 1 alone into the reference's (B, n_stft, T) layout (rfx_mel_scale_backward)
 //   mel_bwd_fold_kernel   step 4: a gather per output sample, no envelope, no atomics; 4-wide where alignment allows
+// and, for the fused spectral losses, spec_loss_slots_kernel and spec_loss_loop_fold_kernel below.  The two slot kernels share one
+// launch helper, the two folds one launcher.
 #include <hip/hip_runtime.h>
 
 #include "rfx_kernels.h"
@@ -190,51 +192,24 @@ __global__ void __launch_bounds__(256) spec_loss_loop_fold_kernel(MelBwdFoldArgs
     out[m] = spec_loss_loop_sample(rows, (size_t)a.fpitch, a.fshift, a.win, m, a.h, a.left, a.win_len, a.hop, a.T);
 }
 
-hipError_t launch_spec_loss_slots(const SpecLossSlotArgs& a, hipStream_t stream) {
+// a slot kernel's launch: one frame per trip, at most 2^16 workgroups, `lds` bytes of dynamic LDS (the attribute where it is over 48 KiB)
+template <class Args>
+static hipError_t launch_slots(void (*kernel)(Args), const Args& a, size_t lds, hipStream_t stream) {
   const long long nframes = (long long)a.B * a.T;
   if (nframes <= 0) return hipSuccess;
-  const size_t lds = sizeof(float) * (size_t)a.xstride;
-  const void* fn = a.target_by_bin ? (const void*)spec_loss_slots_kernel<true> : (const void*)spec_loss_slots_kernel<false>;
   if (lds > 48u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
   const long long cap = 1 << 16;
-  const dim3 grid((unsigned)(nframes < cap ? nframes : cap));
-  if (a.target_by_bin) hipLaunchKernelGGL(spec_loss_slots_kernel<true>, grid, dim3(kMelBwdThreads), lds, stream, a);
-  else hipLaunchKernelGGL(spec_loss_slots_kernel<false>, grid, dim3(kMelBwdThreads), lds, stream, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(nframes < cap ? nframes : cap)), dim3(kMelBwdThreads), lds, stream, a);
   return hipGetLastError();
 }
-
-hipError_t launch_spec_loss_loop_fold(const MelBwdFoldArgs& a, hipStream_t stream) {
-  if (a.B <= 0 || a.Lw <= 0) return hipSuccess;
-  const bool vec = !a.win && a.fpitch % 4 == 0 && a.hop % 4 == 0 && (a.h - a.left + a.fshift) % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(a.frames) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
-  const unsigned gx = (unsigned)(((a.Lw + 3) / 4 + 255) / 256);
-  for (int b0 = 0; b0 < a.B; b0 += 65535) {  // blockIdx.y carries the row
-    MelBwdFoldArgs c = a;
-    c.B = a.B - b0 < 65535 ? a.B - b0 : 65535;
-    c.frames = a.frames + (size_t)b0 * a.T * a.fpitch;
-    c.out = a.out + (size_t)b0 * a.Lw;
-    if (vec) hipLaunchKernelGGL(spec_loss_loop_fold_kernel<true>, dim3(gx, c.B), dim3(256), 0, stream, c);
-    else hipLaunchKernelGGL(spec_loss_loop_fold_kernel<false>, dim3(gx, c.B), dim3(256), 0, stream, c);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
 hipError_t launch_mel_bwd_spec(const MelBwdSpecArgs& a, hipStream_t stream) {
-  const long long nframes = (long long)a.B * a.T;
-  if (nframes <= 0) return hipSuccess;
-  const size_t lds = sizeof(float) * ((size_t)a.xstride + (size_t)(a.M > 0 ? a.M : 0));
-  if (lds > 48u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute((const void*)mel_bwd_spec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const long long cap = 1 << 16;
-  hipLaunchKernelGGL(mel_bwd_spec_kernel, dim3((unsigned)(nframes < cap ? nframes : cap)), dim3(kMelBwdThreads), lds, stream, a);
-  return hipGetLastError();
+  return launch_slots(mel_bwd_spec_kernel, a, sizeof(float) * ((size_t)a.xstride + (size_t)(a.M > 0 ? a.M : 0)), stream);
+}
+hipError_t launch_spec_loss_slots(const SpecLossSlotArgs& a, hipStream_t stream) {
+  return launch_slots(a.target_by_bin ? spec_loss_slots_kernel<true> : spec_loss_slots_kernel<false>, a, sizeof(float) * (size_t)a.xstride, stream);
 }
 
 hipError_t launch_mel_bwd_bank(const float* g_mel, float* out_bft, const int* first, const int* count, const float* wt, int width, int B, int M,
@@ -250,19 +225,22 @@ hipError_t launch_mel_bwd_bank(const float* g_mel, float* out_bft, const int* fi
   return hipSuccess;
 }
 
-hipError_t launch_mel_bwd_fold(const MelBwdFoldArgs& a, hipStream_t stream) {
+hipError_t launch_mel_bwd_fold(const MelBwdFoldArgs& a, bool circular, hipStream_t stream) {
   if (a.B <= 0 || a.Lw <= 0) return hipSuccess;
+  // (the plain fold stores a group 16 bytes at once only where Lw is a multiple of four; the circular one's Lw = hop T always is)
+  const uintptr_t out = reinterpret_cast<uintptr_t>(a.out);
+  const bool out_ok = circular ? (out & 15) == 0 : (out & 3) == 0 && (a.Lw % 4 != 0 || (out & 15) == 0);
   const bool vec = !a.win && a.fpitch % 4 == 0 && a.hop % 4 == 0 && (a.h - a.left + a.fshift) % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(a.frames) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 3) == 0 &&
-                   (a.Lw % 4 != 0 || (reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
+                   (reinterpret_cast<uintptr_t>(a.frames) & 15) == 0 && out_ok;
+  const auto kernel = circular ? (vec ? spec_loss_loop_fold_kernel<true> : spec_loss_loop_fold_kernel<false>)
+                               : (vec ? mel_bwd_fold_kernel<true> : mel_bwd_fold_kernel<false>);
   const unsigned gx = (unsigned)(((a.Lw + 3) / 4 + 255) / 256);
   for (int b0 = 0; b0 < a.B; b0 += 65535) {  // blockIdx.y carries the row
     MelBwdFoldArgs c = a;
     c.B = a.B - b0 < 65535 ? a.B - b0 : 65535;
     c.frames = a.frames + (size_t)b0 * a.T * a.fpitch;
     c.out = a.out + (size_t)b0 * a.Lw;
-    if (vec) hipLaunchKernelGGL(mel_bwd_fold_kernel<true>, dim3(gx, c.B), dim3(256), 0, stream, c);
-    else hipLaunchKernelGGL(mel_bwd_fold_kernel<false>, dim3(gx, c.B), dim3(256), 0, stream, c);
+    hipLaunchKernelGGL(kernel, dim3(gx, c.B), dim3(256), 0, stream, c);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -1,22 +1,28 @@
-// rfx_quality_core.h - arithmetic of the spectral-error reduction (rfx_quality.hip), written once for the gfx950 kernels (hipcc)
-// and the host emulator of the CPU tests (tests/emu/rfx_quality_emu.cpp, g++).
+// rfx_quality_core.h - arithmetic of the per-row spectral sums (rfx_quality.hip), written once for the gfx950 kernels (hipcc) and
+// the host emulators of the CPU tests (tests/emu/rfx_quality_emu.cpp, tests/emu/rfx_spec_loss_emu.cpp, g++).
 //
-// For every row (clip-channel) of T frames two double sums over the n_stft bins of every frame, each bin once:
-//   num = sum (a - m)^2      den = sum m^2
+// For every row (clip-channel) of T frames N double sums over the n_stft bins of every frame, each bin once:
+//   num = sum (a - m)^2      den = sum m^2      N == 3: lsum = sum | ln max(a, f) - ln max(m, f) |
 // a: the magnitudes the plan's forward transform gives for the row's waveform, m: the target, both float32 in the plan's slot
-// layout.  a - m is formed in double (exact for two float32 values); squares and sums are double as well: the supported
-// magnitudes reach 1e33 (include/rfx.h, "Numeric range"), whose square float32 cannot hold.
+// layout, f the log floor.  N == 2 is rfx_spectral_error, N == 3 rfx_spectral_loss; the sums type (SpecSums<N>), the walk, the tree and the
+// combine are templates of N, so the two-sum instantiation carries two doubles and nothing else through registers, LDS and the
+// partials, and the first two sums of either are the same bits.  a - m is formed in double (exact for two float32 values);
+// squares and sums are double as well: the supported magnitudes reach 1e33 (include/rfx.h, "Numeric range"), whose square
+// float32 cannot hold.  Each term of lsum is formed in double from the two float32 values, max taken in float32 (exact), one
+// double logarithm each, their difference, its absolute value, one addition.  LOG == false (f == 0) evaluates no logarithm and
+// leaves lsum 0.
 //
-// The shape of a row's reduction is a function of (T, the plan's layout) alone, so that a row's 16 bytes are the same alone and
+// The shape of a row's reduction is a function of (T, the plan's layout) alone, so that a row's sums are the same alone and
 // inside any batch (the rule of rfx_kernels.h: kGlGroup):
 //   - the row is cut into chunks of kQualFrames consecutive frames (the last one shorter), one workgroup of kQualThreads each;
 //   - thread t of a chunk walks the chunk's frames in order and, within a frame, the 16-byte vectors t, t + kQualThreads, ...,
-//     adding the counted elements of a vector in order: one fma per element and sum (qual_thread_partial);
-//   - the workgroup's kQualThreads pairs are folded by the halving tree (qual_tree_step, strides 128 .. 1) into one partial;
+//     adding the counted elements of a vector in order: one fma per element and sum, one addition for lsum (qual_walk);
+//   - the workgroup's kQualThreads sums are folded by the halving tree (qual_tree_step, strides 128 .. 1) into one partial;
 //   - a second workgroup per row adds the row's partials, thread t taking partials t, t + kQualThreads, ... in order, and folds
 //     them with the same tree (qual_combine_partial).
 // No atomics, no dependence on the grid, on B or on the row's place in the call.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include "rfx_core.h"
 
@@ -25,9 +31,17 @@ namespace rfx {
 constexpr int kQualThreads = 256;  // a power of two: the tree halves it
 constexpr int kQualFrames = 4;     // frames per chunk: 147 KiB of each tensor per workgroup on the specialised layout
 
-struct QualSums {
+template <int N>
+struct SpecSums;
+template <>
+struct SpecSums<2> {
   double num, den;
 };
+template <>
+struct SpecSums<3> {
+  double num, den, lsum;
+};
+using QualSums = SpecSums<2>;  // rfx_spectral_error's
 struct alignas(16) QualVec {
   float v[4];
 };
@@ -73,22 +87,29 @@ RFX_HD unsigned qual_plain_counts4(int i, int n_stft) {
 }
 
 // ---- the sums ------------------------------------------------------------------------------------------------------------------
-RFX_HD void qual_accumulate(QualSums& s, float a, float m, bool counts) {
+template <int N, bool LOG>
+RFX_HD void qual_accumulate(SpecSums<N>& s, float a, float m, float f, bool counts) {
   const double d = (double)a - (double)m, mm = (double)m;
   const double num = fma(d, d, s.num), den = fma(mm, mm, s.den);
   s.num = counts ? num : s.num;
   s.den = counts ? den : s.den;
+  if constexpr (N == 3 && LOG) {
+    const double l = s.lsum + fabs(log((double)fmaxf(a, f)) - log((double)fmaxf(m, f)));
+    s.lsum = counts ? l : s.lsum;
+  }
 }
-RFX_HD void qual_add(QualSums& s, const QualSums& o) {
+template <int N>
+RFX_HD void qual_add(SpecSums<N>& s, const SpecSums<N>& o) {
   s.num += o.num;
   s.den += o.den;
+  if constexpr (N == 3) s.lsum += o.lsum;
 }
 
 // thread `tid` of the workgroup that owns frames [f0, f1) of a row; a_row / m_row: the row's first frame, fs floats per frame
 // (a multiple of four, frames 16-byte aligned).  A vector without a counted element is not loaded.
-template <bool PLAIN>
-RFX_HD QualSums qual_thread_partial(const float* a_row, const float* m_row, int f0, int f1, int fs, int n_stft, int tid) {
-  QualSums s{0.0, 0.0};
+template <int N, bool PLAIN, bool LOG>
+RFX_HD SpecSums<N> qual_walk(const float* a_row, const float* m_row, int f0, int f1, int fs, int n_stft, float floor, int tid) {
+  SpecSums<N> s{};
   const int nv = fs >> 2;
   for (int f = f0; f < f1; ++f) {
     const QualVec* A = reinterpret_cast<const QualVec*>(a_row + (size_t)f * fs);
@@ -98,18 +119,27 @@ RFX_HD QualSums qual_thread_partial(const float* a_row, const float* m_row, int 
       if (!bits) continue;
       const QualVec va = A[i], vm = M[i];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) qual_accumulate(s, va.v[e], vm.v[e], (bits >> e) & 1u);
+      for (int e = 0; e < 4; ++e) qual_accumulate<N, LOG>(s, va.v[e], vm.v[e], floor, (bits >> e) & 1u);
     }
   }
   return s;
 }
+// the two-sum walk under the name rfx_spectral_error's emulator calls it by
+template <bool PLAIN>
+RFX_HD QualSums qual_thread_partial(const float* a_row, const float* m_row, int f0, int f1, int fs, int n_stft, int tid) {
+  return qual_walk<2, PLAIN, false>(a_row, m_row, f0, f1, fs, n_stft, 0.f, tid);
+}
 
-// one level of the halving tree over kQualThreads pairs: the threads tid < stride run it, a barrier follows
-RFX_HD void qual_tree_step(QualSums* s, int tid, int stride) { qual_add(s[tid], s[tid + stride]); }
+// one level of the halving tree over kQualThreads sums: the threads tid < stride run it, a barrier follows
+template <int N>
+RFX_HD void qual_tree_step(SpecSums<N>* s, int tid, int stride) {
+  qual_add(s[tid], s[tid + stride]);
+}
 
 // thread `tid` of the workgroup that combines a row's `chunks` partials
-RFX_HD QualSums qual_combine_partial(const QualSums* partials, int chunks, int tid) {
-  QualSums s{0.0, 0.0};
+template <int N>
+RFX_HD SpecSums<N> qual_combine_partial(const SpecSums<N>* partials, int chunks, int tid) {
+  SpecSums<N> s{};
   for (int c = tid; c < chunks; c += kQualThreads) qual_add(s, partials[c]);
   return s;
 }

@@ -9,10 +9,8 @@
 // and then steps 2 to 4 of rfx_mel_bwd_core.h: the zero rule of torch.abs's backward, the frame adjoint (the engines' MODE 0 frame
 // launch) and the adjoint fold - for a loop row the circular chain of rfx_loop_core.h.
 //
-// THE SUMS.  num and den are rfx_quality_core.h's own: the same chunks, the same per-thread order (one fma per element and sum), the
-// same halving tree - bit for bit what rfx_spectral_error gives.  lsum rides the same walk: each term is formed in double from the
-// two float32 values, max taken in float32 (exact), one double logarithm each, their difference, its absolute value, one addition.
-// LOG == false (f == 0) evaluates no logarithm and leaves lsum 0.
+// THE SUMS are rfx_quality_core.h's reduction at N = 3: num and den are rfx_spectral_error's bits, lsum rides the same walk.  The
+// names below are that instantiation as the loss's emulator calls it; they hold no arithmetic.
 //
 // THE SLOT RULE.  A magnitude slot of the MODE 0 launch multiplies one complex value X = (re, im) of the re-analysed spectrum.  From
 // that very value
@@ -37,52 +35,14 @@ namespace rfx {
 // the floors an entry takes: 0 (no log term) or a finite f >= 1e-18
 RFX_HD bool spec_loss_floor_ok(float f) { return f == 0.f || (f >= 1e-18f && f <= 3.402823466e38f); }
 
-// ---- the sums --------------------------------------------------------------------------------------------------------------------
-struct SpecLossSums {
-  double num, den, lsum;
-};
-
-template <bool LOG>
-RFX_HD void spec_loss_accumulate(SpecLossSums& s, float a, float m, float f, bool counts) {
-  const double d = (double)a - (double)m, mm = (double)m;
-  const double num = fma(d, d, s.num), den = fma(mm, mm, s.den);
-  s.num = counts ? num : s.num;
-  s.den = counts ? den : s.den;
-  if (LOG) {
-    const double l = s.lsum + fabs(log((double)fmaxf(a, f)) - log((double)fmaxf(m, f)));
-    s.lsum = counts ? l : s.lsum;
-  }
-}
-RFX_HD void spec_loss_add(SpecLossSums& s, const SpecLossSums& o) {
-  s.num += o.num;
-  s.den += o.den;
-  s.lsum += o.lsum;
-}
-
-// qual_thread_partial with the third sum: thread `tid` of the workgroup that owns frames [f0, f1) of a row
+// ---- the sums: rfx_quality_core.h at N = 3 -----------------------------------------------------------------------------------------
+using SpecLossSums = SpecSums<3>;
 template <bool PLAIN, bool LOG>
 RFX_HD SpecLossSums spec_loss_thread_partial(const float* a_row, const float* m_row, int f0, int f1, int fs, int n_stft, float f, int tid) {
-  SpecLossSums s{0.0, 0.0, 0.0};
-  const int nv = fs >> 2;
-  for (int fr = f0; fr < f1; ++fr) {
-    const QualVec* A = reinterpret_cast<const QualVec*>(a_row + (size_t)fr * fs);
-    const QualVec* M = reinterpret_cast<const QualVec*>(m_row + (size_t)fr * fs);
-    for (int i = tid; i < nv; i += kQualThreads) {
-      const unsigned bits = PLAIN ? qual_plain_counts4(i, n_stft) : qual_slot_counts4(i);
-      if (!bits) continue;
-      const QualVec va = A[i], vm = M[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) spec_loss_accumulate<LOG>(s, va.v[e], vm.v[e], f, (bits >> e) & 1u);
-    }
-  }
-  return s;
+  return qual_walk<3, PLAIN, LOG>(a_row, m_row, f0, f1, fs, n_stft, f, tid);
 }
-RFX_HD void spec_loss_tree_step(SpecLossSums* s, int tid, int stride) { spec_loss_add(s[tid], s[tid + stride]); }
-RFX_HD SpecLossSums spec_loss_combine_partial(const SpecLossSums* partials, int chunks, int tid) {
-  SpecLossSums s{0.0, 0.0, 0.0};
-  for (int c = tid; c < chunks; c += kQualThreads) spec_loss_add(s, partials[c]);
-  return s;
-}
+RFX_HD void spec_loss_tree_step(SpecLossSums* s, int tid, int stride) { qual_tree_step(s, tid, stride); }
+RFX_HD SpecLossSums spec_loss_combine_partial(const SpecLossSums* partials, int chunks, int tid) { return qual_combine_partial(partials, chunks, tid); }
 
 // ---- the slot rule ---------------------------------------------------------------------------------------------------------------
 RFX_HD float spec_loss_abs(float re, float im) { return sqrtf(fmaf(re, re, im * im)); }

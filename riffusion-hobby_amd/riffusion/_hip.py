@@ -357,20 +357,11 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_stft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rfx_spectral_error_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_error": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    # loop encode: the forward entries on the circular STFT
+    # loop encode: the forward entries on the circular STFT (the loop twins of equal signature: LOOP_TWINS below)
     "rfx_stft_loop_frames": (c_int, [c_void_p, c_int]),
     "rfx_debug_loop_samples": (c_int, [c_void_p, c_int]),
     "rfx_debug_loop_nearest_samples": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
-    "rfx_stft_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rfx_mel_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_mel_from_waveform_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "rfx_image_from_waveform_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
-    "rfx_image_from_waveform_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "rfx_image_from_pcm16_clips_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
-    "rfx_image_from_pcm16_clips_loop": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "rfx_spectral_error_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_spectral_error_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_griffinlim_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_griffinlim_workspace_bytes_ex": (c_size_t, [c_void_p, c_int, c_int, c_void_p]),
     "rfx_peak_start_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
@@ -408,25 +399,16 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     # inverse spectrogram (riffusion/_autograd.py: IstftFunction)
     "rfx_istft_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_istft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "rfx_istft_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_istft_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_istft_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_istft_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "rfx_istft_backward_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_istft_backward_loop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_debug_istft_backward_padded_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_debug_istft_backward_padded": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     # fused spectral losses (riffusion/_autograd.py: SpectralLossFunction)
     "rfx_spectral_loss_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "rfx_spectral_loss_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_spectral_loss_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_spectral_loss_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t,
                                            c_void_p]),
-    "rfx_spectral_loss_backward_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "rfx_spectral_loss_backward_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t,
-                                                c_void_p]),
     "rfx_inverse_mel_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_inverse_mel": (
         c_int,
@@ -479,6 +461,11 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_png_encode_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rfx_png_encode_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
+# A loop twin takes what its plain form takes: rfx_<name>_loop, and rfx_<name>_loop_workspace_bytes where the plain form has a query
+for _name in ("stft", "mel_from_waveform", "image_from_waveform", "image_from_pcm16_clips", "spectral_error", "istft", "istft_backward", "spectral_loss", "spectral_loss_backward"):
+    SIGNATURES[f"rfx_{_name}_loop"] = SIGNATURES[f"rfx_{_name}"]
+    if f"rfx_{_name}_workspace_bytes" in SIGNATURES:
+        SIGNATURES[f"rfx_{_name}_loop_workspace_bytes"] = SIGNATURES[f"rfx_{_name}_workspace_bytes"]
 
 # rfx_png_encode_u8's modes (RFX_PNG_RGB, RFX_PNG_GRAY, RFX_PNG_AUTO)
 PNG_MODES = {"rgb": 0, "gray": 1, "auto": 2}
@@ -814,6 +801,17 @@ class Plan:
             raise RfxError(f"tensor on {t.device} handed to a plan that lives on {self.device}")
         return (t if dtype is None else t.to(dtype)).contiguous()
 
+    def _chk_slots(self, t: torch.Tensor, B: int, Tn: int, exact: bool = False) -> None:
+        """magnitudes in slot layout hold the B * Tn frames of a call (`exact`: and nothing more)"""
+        need = B * Tn * self.frame_stride
+        if (t.numel() != need) if exact else (t.numel() < need):
+            raise ValueError(f"magnitude slots hold {t.numel()} values, {B} x {Tn} frames {'are' if exact else 'need'} {need}")
+
+    def _pair(self, name: str, loop: bool = False) -> T.Tuple[T.Any, T.Any]:
+        """(workspace query, entry) of rfx_<name>, or with `loop` of its loop twin rfx_<name>_loop"""
+        name = f"rfx_{name}_loop" if loop else f"rfx_{name}"
+        return getattr(self.lib, name + "_workspace_bytes"), getattr(self.lib, name)
+
     def _chk_tiles(self, img: torch.Tensor) -> torch.Tensor:
         """tiles as the codec entries read them: an (N, H, W, 3) uint8 batch (`check_tiles`), contiguous, on the plan's device"""
         return self._chk(check_tiles(img))
@@ -979,8 +977,7 @@ class Plan:
         frequencies integrated over the hop.  A row depends on its magnitudes only."""
         mag_slots = self._chk(mag_slots, torch.float32)
         self._chk_peak_bins()
-        if mag_slots.numel() < B * Tn * self.frame_stride:
-            raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
+        self._chk_slots(mag_slots, B, Tn)
         out = torch.empty((B * Tn, self.frame_stride), dtype=torch.complex64, device=mag_slots.device)
         if B == 0:
             return out
@@ -1023,8 +1020,7 @@ class Plan:
         mag_slots = self._chk(mag_slots, torch.float32)
         opt, need, angles0_slots = self._inverse_call("griffinlim", (B, Tn), B, Tn, row_base, magnitude_hint, False, guide, hold, hold_bins, loop,
                                                       peak_start, angles0_slots)
-        if mag_slots.numel() < B * Tn * self.frame_stride:
-            raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
+        self._chk_slots(mag_slots, B, Tn)
         if workspace is not None:
             workspace = self._chk(workspace)
         out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mag_slots.device)
@@ -1063,13 +1059,11 @@ class Plan:
         L = self.output_samples(Tn, loop)
         if tuple(wave.shape) != (B, L):
             raise ValueError(f"{B} rows of {Tn} frames are waveforms of shape {(B, L)}, got {tuple(wave.shape)}")
-        if mag_slots.numel() < B * Tn * self.frame_stride:
-            raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames need {B * Tn * self.frame_stride}")
+        self._chk_slots(mag_slots, B, Tn)
         sums = torch.empty((B, 2), dtype=torch.float64, device=self.device)
         if B == 0:
             return sums
-        query, entry = ((self.lib.rfx_spectral_error_loop_workspace_bytes, self.lib.rfx_spectral_error_loop) if loop
-                        else (self.lib.rfx_spectral_error_workspace_bytes, self.lib.rfx_spectral_error))
+        query, entry = self._pair("spectral_error", loop)
         with self._workspace(max(1, query(self.handle, B, Tn))) as ws:
             check(entry(self.handle, wave.data_ptr(), mag_slots.data_ptr(), B, Tn, sums.data_ptr(), ws.data_ptr(),
                                               ws.numel(), self._stream()))
@@ -1169,7 +1163,7 @@ class Plan:
         if x.numel() != B * Tn * self.frame_stride:
             raise ValueError(f"expected {B} * {Tn} frames of {self.frame_stride} complex slots, got {tuple(x.shape)}")
         out = torch.empty((B, L), dtype=torch.float32, device=self.device)
-        query, entry = (self.lib.rfx_istft_loop_workspace_bytes, self.lib.rfx_istft_loop) if loop else (self.lib.rfx_istft_workspace_bytes, self.lib.rfx_istft)
+        query, entry = self._pair("istft", loop)
         if B:
             with self._workspace(query(self.handle, B, Tn)) as ws:
                 check(entry(self.handle, x.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
@@ -1187,9 +1181,7 @@ class Plan:
         if tuple(g.shape) != (B, L):
             raise ValueError(f"expected a ({B}, {L}) gradient, got {tuple(g.shape)}")
         out = torch.empty((B * Tn, self.frame_stride), dtype=torch.complex64, device=self.device)
-        query, entry = ((self.lib.rfx_istft_backward_loop_workspace_bytes, self.lib.rfx_istft_backward_loop) if loop
-                        else (self.lib.rfx_debug_istft_backward_padded_workspace_bytes, self.lib.rfx_debug_istft_backward_padded) if padded
-                        else (self.lib.rfx_istft_backward_workspace_bytes, self.lib.rfx_istft_backward))
+        query, entry = self._pair("debug_istft_backward_padded") if padded else self._pair("istft_backward", loop)
         if B:
             with self._workspace(query(self.handle, B, Tn)) as ws:
                 check(entry(self.handle, g.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
@@ -1201,8 +1193,7 @@ class Plan:
         mag_slots = self._chk(mag_slots, torch.float32)
         B, Lw = wave.shape
         Tn = self._forward_frames(Lw, wave.shape, loop)
-        if mag_slots.numel() != B * Tn * self.frame_stride:
-            raise ValueError(f"magnitude slots hold {mag_slots.numel()} values, {B} x {Tn} frames are {B * Tn * self.frame_stride}")
+        self._chk_slots(mag_slots, B, Tn, exact=True)
         return wave, mag_slots, B, Lw, Tn
 
     def spectral_loss_sums(self, wave: torch.Tensor, mag_slots: torch.Tensor, log_floor: float = 0.0, loop: bool = False) -> torch.Tensor:
@@ -1215,8 +1206,7 @@ class Plan:
         sums = torch.empty((B, 3), dtype=torch.float64, device=self.device)
         if B == 0:
             return sums
-        query, entry = ((self.lib.rfx_spectral_loss_loop_workspace_bytes, self.lib.rfx_spectral_loss_loop) if loop
-                        else (self.lib.rfx_spectral_loss_workspace_bytes, self.lib.rfx_spectral_loss))
+        query, entry = self._pair("spectral_loss", loop)
         with self._workspace(max(1, query(self.handle, B, Lw))) as ws:
             check(entry(self.handle, wave.data_ptr(), mag_slots.data_ptr(), B, Lw, f, sums.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         return sums
@@ -1234,8 +1224,7 @@ class Plan:
         out = torch.empty((B, Lw), dtype=torch.float32, device=self.device)
         if B == 0:
             return out
-        query, entry = ((self.lib.rfx_spectral_loss_backward_loop_workspace_bytes, self.lib.rfx_spectral_loss_backward_loop) if loop
-                        else (self.lib.rfx_spectral_loss_backward_workspace_bytes, self.lib.rfx_spectral_loss_backward))
+        query, entry = self._pair("spectral_loss_backward", loop)
         with self._workspace(max(1, query(self.handle, B, Lw))) as ws:
             check(entry(self.handle, wave.data_ptr(), mag_slots.data_ptr(), coef.data_ptr(), B, Lw, f, out.data_ptr(), ws.data_ptr(), ws.numel(),
                         self._stream()))
@@ -1546,8 +1535,7 @@ class Plan:
         N = NC // C
         img = torch.empty((N, self.n_mels, Tn, 3), dtype=torch.uint8, device=wave.device)
         mx = torch.empty((N,), dtype=torch.float32, device=wave.device)
-        query, entry = ((self.lib.rfx_image_from_waveform_loop_workspace_bytes, self.lib.rfx_image_from_waveform_loop) if loop
-                        else (self.lib.rfx_image_from_waveform_workspace_bytes, self.lib.rfx_image_from_waveform))
+        query, entry = self._pair("image_from_waveform", loop)
         with self._workspace(query(self.handle, N, int(stereo), Lw)) as ws:
             check(entry(self.handle, wave.data_ptr(), N, int(stereo), Lw, thresholds.data_ptr(), mx.data_ptr(),
                         img.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
@@ -1722,8 +1710,7 @@ class Plan:
         mx = torch.empty((N,), dtype=torch.float32, device=self.device)
         if N == 0:
             return img, mx
-        query, entry = ((self.lib.rfx_image_from_pcm16_clips_loop_workspace_bytes, self.lib.rfx_image_from_pcm16_clips_loop) if loop
-                        else (self.lib.rfx_image_from_pcm16_clips_workspace_bytes, self.lib.rfx_image_from_pcm16_clips))
+        query, entry = self._pair("image_from_pcm16_clips", loop)
         with self._workspace(query(self.handle, N, int(stereo), Lw)) as ws:
             check(entry(self.handle, pcm.data_ptr(), L, C, host.data_ptr(), dev.data_ptr(), N, Lw, int(stereo),
                         thresholds.data_ptr(), mx.data_ptr(), img.data_ptr(), ws.data_ptr(), ws.numel(),
