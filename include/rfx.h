@@ -196,6 +196,13 @@ typedef struct {
   char why[160];
 } rfx_lstsq_bank_report;
 int rfx_debug_lstsq_bank(const rfx_params* params, const float* h_melfb, rfx_lstsq_bank_report* report);
+/* The lists rfx_inverse_mel_lstsq_backward's collect walks, without a plan or a GPU (tests): CSR over the filters.  h_ptr
+ * [n_mels + 1]; entries h_ptr[m] .. h_ptr[m + 1] - 1 are filter m's bins in the order they are summed, ascending: the bin, the
+ * position of a frame (slot layout) it is read from - its FIRST slot where the layout holds it twice - and the weight
+ * melfb[bin][m].  *entries_out: the number of entries; every array is optional, and the three entry arrays need capacity >=
+ * *entries_out (call once with NULL arrays to learn it).  A bank rfx_debug_lstsq_bank refuses is refused here with its reason. */
+int rfx_debug_lstsq_collect(const rfx_params* params, const float* h_melfb, int32_t* h_ptr, int32_t* h_bin, int32_t* h_pos, float* h_weight,
+                            int capacity, int32_t* entries_out);
 /* frames torch.stft(center=True, pad_mode="reflect") makes of Lw samples: 1 + (Lw + 2*(n_fft/2) - n_fft) / hop, i.e.
  * 1 + Lw/hop for even n_fft and 1 + (Lw-1)/hop for odd n_fft; 0 when Lw <= n_fft/2 (the reference raises there).
  * Every forward entry point below produces exactly this many frames. */
@@ -859,6 +866,26 @@ int rfx_plan_lstsq_ok(const rfx_plan* plan);
 size_t rfx_inverse_mel_lstsq_workspace_bytes(const rfx_plan* plan, int B, int T);
 int rfx_inverse_mel_lstsq(const rfx_plan* plan, const float* d_mel, int B, int T, float* d_mag_slots, void* d_workspace,
                           size_t workspace_bytes, void* stream);
+
+/* Its backward, as torch autograd differentiates relu(lstsq(...).solution) with respect to mel: for a gradient gx over the linear
+ * bins, g_mel = G^-1 c with c = fb^T (gx where the relu is open) - G is symmetric, so the solve is the forward's on another
+ * right-hand side, same tables, same sweeps.  The gradient is 0 where the forward's value before the clamp is <= 0 (torch.relu's
+ * rule; the forward's `v > 0 ? v : 0` has it too).  The mask is not saved: the entry takes the forward's d_mel, runs the solve again
+ * into its workspace and forms the value before the clamp with the forward's own expression, so the mask is the forward's x > 0 bit
+ * for bit and a caller keeps (B, n_mels, T), not the slots.
+ * d_mel (B, n_mels, T), d_grad_slots [B * T][frame stride] -> d_grad_mel (B, n_mels, T).  d_grad_slots is what rfx_pack_magnitudes
+ * of torch's (B, n_stft, T) gradient holds.  EVERY BIN COUNTS ONCE: a bin the specialised layout stores twice is read from its first
+ * slot only (the one rfx_debug_lstsq_collect reports); the second slot, the padding positions and the bins no filter reaches are
+ * never read, whatever they hold.  c[m] sums filter m's bins in ascending bin order, one fmaf per bin, from 0 - no atomics; a frame's
+ * result is a function of that frame's mel column, its gradient and the plan alone, not of B, the row or the launch grid.
+ * Scale: linear in the gradient with power-of-two-exact roundings - d_grad_slots times 2^n gives d_grad_mel times 2^n bit for bit
+ * while no intermediate leaves float32's normal range.
+ * Refusals are the forward's: a null argument, a plan that is not rfx_plan_lstsq_ok (RFX_ERR_INVALID with the reason; the query
+ * returns 0), a bad shape, more than 2^31 - 1 frames, d_grad_slots not 16-byte aligned, a workspace that is too small
+ * (RFX_ERR_WORKSPACE).  Workspace: 2 * B * n_mels * T floats.  Inputs are not written. */
+size_t rfx_inverse_mel_lstsq_backward_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_inverse_mel_lstsq_backward(const rfx_plan* plan, const float* d_mel, const float* d_grad_slots, int B, int T, float* d_grad_mel,
+                                   void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- inverse, in one call: SpectrogramConverter.waveform_from_mel_amplitudes, spectrogram_converter.py:187-204
  * (`self.inverse_mel_scaler(amplitudes_mel)` :201 then `self.inverse_spectrogram_func(amplitudes_linear)` :204).

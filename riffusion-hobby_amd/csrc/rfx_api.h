@@ -84,6 +84,7 @@ struct rfx_plan {
   bool lstsq_ok = false;
   std::string lstsq_why;
   rfx::LsqTables lstsq{};
+  rfx::LsqCollectTables lstsq_collect{};  // its backward's collect (rfx_inverse_mel_lstsq_backward), uploaded with them
   // fused forward path (banded mel projection inside the STFT kernel), valid when fwd_ok
   bool fwd_ok = false;
   float* d_band_wt = nullptr;      // [band_rows][Mpad]

@@ -5,6 +5,7 @@
 #include "rfx_api.h"
 #include "rfx_guide_core.h"
 #include "rfx_holdmask_core.h"
+#include "rfx_imel_lstsq_core.h"
 #include "rfx_loop_core.h"
 #include "rfx_peak_core.h"
 
@@ -852,6 +853,45 @@ int rfx_inverse_mel_lstsq(const rfx_plan* plan, const float* d_mel, int B, int T
   float* zy = (float*)((char*)d_workspace + w.zy);
   RFX_HIP(launch_lsq_solve(plan->lstsq, d_mel, zy, B, plan->p.n_mels, T, stream));
   RFX_HIP(launch_lsq_expand(plan->lstsq, zy, d_mag_slots, B, plan->p.n_mels, T, plan->frame_stride, stream));
+  return RFX_OK;
+}
+
+// ---- its backward: the forward's solve again (the mask is recomputed, not saved), the collect, and the same solve on c ---------------
+struct LstsqBackwardLayout {
+  size_t y, c, total;  // (B, n_mels, T) floats each: y = G^-1 mel, and c = fb^T (gx where the relu is open)
+};
+static LstsqBackwardLayout inverse_mel_lstsq_backward_layout(const rfx_plan* plan, int B, int T) {
+  LstsqBackwardLayout l{};
+  if (!plan->lstsq_ok || B <= 0 || T <= 0) return l;
+  Carve c;
+  l.y = c.take((size_t)B * plan->p.n_mels * T * sizeof(float));
+  l.c = c.take((size_t)B * plan->p.n_mels * T * sizeof(float));
+  l.total = c.at;
+  return l;
+}
+size_t rfx_inverse_mel_lstsq_backward_workspace_bytes(const rfx_plan* plan, int B, int T) {
+  return plan ? inverse_mel_lstsq_backward_layout(plan, B, T).total : 0;
+}
+
+int rfx_inverse_mel_lstsq_backward(const rfx_plan* plan, const float* d_mel, const float* d_grad_slots, int B, int T, float* d_grad_mel,
+                                   void* d_workspace, size_t workspace_bytes, void* stream_) {
+  const char* who = "rfx_inverse_mel_lstsq_backward";
+  if (!plan || !d_mel || !d_grad_slots || !d_grad_mel || !d_workspace) return fail(RFX_ERR_INVALID, std::string(who) + ": null argument");
+  if (int rc = lstsq_refusal(plan, who)) return rc;
+  if (B <= 0 || T <= 0) return fail(RFX_ERR_INVALID, std::string(who) + ": bad shape");
+  if ((long long)B * T > 0x7fffffffLL) return fail(RFX_ERR_INVALID, std::string(who) + ": more than 2^31 - 1 frames in one call");
+  if (((uintptr_t)d_grad_slots & 15) || (plan->frame_stride & 3)) return fail(RFX_ERR_INVALID, std::string(who) + ": d_grad_slots must be 16-byte aligned");
+  if (plan->lstsq_collect.n_vecs > kLsqCollectVecs * kLsqCollectThreads)
+    return fail(RFX_ERR_INVALID, std::string(who) + ": more 16-byte vectors with a counted bin in a frame than the collect kernel holds");
+  const LstsqBackwardLayout w = inverse_mel_lstsq_backward_layout(plan, B, T);
+  if (workspace_bytes < w.total) return fail(RFX_ERR_WORKSPACE, std::string(who) + ": workspace too small");
+  RFX_ON_DEVICE(plan->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  float *y = (float*)((char*)d_workspace + w.y), *c = (float*)((char*)d_workspace + w.c);
+  const int M = plan->p.n_mels;
+  RFX_HIP(launch_lsq_solve(plan->lstsq, d_mel, y, B, M, T, stream));
+  RFX_HIP(launch_lsq_collect(plan->lstsq_collect, y, d_grad_slots, c, B, M, T, plan->frame_stride, stream));
+  RFX_HIP(launch_lsq_solve(plan->lstsq, c, d_grad_mel, B, M, T, stream));
   return RFX_OK;
 }
 

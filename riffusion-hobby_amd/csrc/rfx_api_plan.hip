@@ -292,6 +292,18 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
       RFX_HIP(upload(pl.get(), &d_w0, lsq.pos_w0));
       RFX_HIP(upload(pl.get(), &d_w1, lsq.pos_w1));
       pl->lstsq = LsqTables{d_nl, d_inv_d, d_m0, d_w0, d_w1};
+      // ... and the lists its backward's collect walks
+      const LstsqCollect col = bank_lstsq_collect(bank);
+      int *d_run, *d_first, *d_vec, *d_at;
+      float *d_wt, *d_vw0, *d_vw1;
+      RFX_HIP(upload(pl.get(), &d_wt, col.wt));
+      RFX_HIP(upload(pl.get(), &d_first, col.first));
+      RFX_HIP(upload(pl.get(), &d_run, col.run));
+      RFX_HIP(upload(pl.get(), &d_vec, col.vec));
+      RFX_HIP(upload(pl.get(), &d_at, col.vec_at));
+      RFX_HIP(upload(pl.get(), &d_vw0, col.vec_w0));
+      RFX_HIP(upload(pl.get(), &d_vw1, col.vec_w1));
+      pl->lstsq_collect = LsqCollectTables{d_wt, d_first, d_run, d_vec, d_at, d_vw0, d_vw1, (int)col.vec.size(), col.n_bins};
     }
   } else {
     pl->lstsq_why = "plan was created without a mel filterbank";
@@ -323,6 +335,33 @@ int rfx_debug_lstsq_bank(const rfx_params* params, const float* h_melfb, rfx_lst
   if (lsq.ok && r.h_neg_l) memcpy(r.h_neg_l, lsq.nl.data(), lsq.nl.size() * sizeof(float));
   if (lsq.ok && r.h_inv_d) memcpy(r.h_inv_d, lsq.inv_d.data(), lsq.inv_d.size() * sizeof(float));
   memcpy(report, &r, r.struct_size);
+  return RFX_OK;
+}
+
+int rfx_debug_lstsq_collect(const rfx_params* params, const float* h_melfb, int32_t* h_ptr, int32_t* h_bin, int32_t* h_pos, float* h_weight,
+                            int capacity, int32_t* entries_out) {
+  if (!params || !h_melfb || !entries_out) return fail(RFX_ERR_INVALID, "rfx_debug_lstsq_collect: null argument");
+  if (params->n_mels <= 0) return fail(RFX_ERR_INVALID, "rfx_plan_create: n_mels must be positive");
+  rfx_plan_options opt;
+  if (const int rc = resolve_options(nullptr, &opt)) return rc;
+  const PlanOverrides ov = plan_overrides();
+  PlanGeometry geo;
+  std::string err;
+  if (const int rc = plan_geometry(*params, opt, ov, &geo, &err)) return fail(rc, err);
+  const PlanBank bank = plan_bank(geo, params->n_mels, h_melfb, opt, ov);
+  const LstsqBank lsq = bank_lstsq(bank);
+  if (!lsq.ok) return fail(RFX_ERR_INVALID, "rfx_debug_lstsq_collect: the closed-form InverseMelScale does not serve this filterbank: " + lsq.why);
+  const LstsqCollect col = bank_lstsq_collect(bank);  // what plan creation uploads
+  const int n = (int)col.w.size();
+  *entries_out = n;
+  if (h_ptr) memcpy(h_ptr, col.ptr.data(), col.ptr.size() * sizeof(int32_t));
+  if (h_bin || h_pos || h_weight) {
+    if (capacity < n)
+      return fail(RFX_ERR_INVALID, "rfx_debug_lstsq_collect: the lists have " + std::to_string(n) + " entries, capacity is " + std::to_string(capacity));
+    if (h_bin) memcpy(h_bin, col.bin.data(), (size_t)n * sizeof(int32_t));
+    if (h_pos) memcpy(h_pos, col.pos.data(), (size_t)n * sizeof(int32_t));
+    if (h_weight) memcpy(h_weight, col.w.data(), (size_t)n * sizeof(float));
+  }
   return RFX_OK;
 }
 

@@ -11,6 +11,14 @@
 // filter and two weights from the plan's per-position tables, loaded once for all the staged frames - and writes one 16-byte
 // vector per frame: a wave stores 1 KiB of consecutive bytes.  Every position of the frame stride is written (padding and bins
 // without a filter: 0.0).
+// lsq_collect_kernel (the backward, rfx_inverse_mel_lstsq_backward): c = fb^T (gx where the relu is open), (B, M, T).  One workgroup
+// per lsq_expand_frames(M) consecutive frames of a row, y staged as in the expansion.  Per frame: every thread reads its share of
+// the frame's gx in whole 16-byte vectors - only the vectors that hold a counted position, their tables in registers for all the
+// staged frames, the next frame's loads in flight under this frame's sums - and puts the masked values in LDS in bin order; then
+// one lane per filter sums its run of bins there in ascending order (lsq_collect_sum; the weights transposed, [entry][filter], so
+// that a wave's 64 filters read one line per step).  c[m] of frame j takes the place of
+// y[m] of frame j in LDS, which the frame's mask was the last to read; at the end the block leaves as it was staged, a wave writing
+// runs of consecutive t.  HBM traffic: one read of the counted vectors of gx, y and c.  LDS: 33 KB of y and at most 36 KB of frame.
 #include <hip/hip_runtime.h>
 #include "rfx_kernels.h"
 #include "rfx_imel_lstsq_core.h"
@@ -63,7 +71,113 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_expand_kernel(const float* __
   }
 }
 
+// NV: 16-byte vectors of a frame per thread, ceil(n_vecs / kLsqCollectThreads) - 3 for the default bank, whose 4000 bins with a
+// filter sit in 1273 vectors; at most kLsqCollectVecs
+template <int NV>
+__global__ __launch_bounds__(kLsqCollectThreads) void lsq_collect_kernel(const float* __restrict__ y, const float* __restrict__ gx,
+                                                                          const LsqCollectTables tb, float* __restrict__ c, int M, int T,
+                                                                          int stride, int chunks, int FR) {
+  extern __shared__ __attribute__((aligned(16))) float ys[];  // [FR][lsq_y_stride(M)], then the frame: [n_bins]
+  const int tid = threadIdx.x, Ms = lsq_y_stride(M);
+  float* gs = ys + ((FR * Ms + 3) & ~3);
+  const size_t row = blockIdx.x / (unsigned)chunks;
+  const int t0 = (int)(blockIdx.x - row * (unsigned)chunks) * FR;
+  const int nfr = T - t0 < FR ? T - t0 : FR;
+  const float* yrow = y + row * (size_t)M * (size_t)T + (size_t)t0;
+  for (int i = tid; i < M * FR; i += kLsqCollectThreads) {
+    const int m = i / FR, j = i - m * FR;
+    if (j < nfr) ys[j * Ms + m] = yrow[(size_t)m * (size_t)T + j];
+  }
+  for (int i = tid; i < FR * (Ms - M); i += kLsqCollectThreads) {
+    const int j = i / (Ms - M), k = i - j * (Ms - M);
+    ys[j * Ms + M + k] = 0.f;
+  }
+  // this thread's vectors of a frame, and what their four positions need
+  int vec[NV];
+  LsqVecI at[NV];
+  LsqVecF w0[NV], w1[NV], g[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = k * kLsqCollectThreads + tid;
+    vec[k] = i < tb.n_vecs ? tb.vec[i] : -1;
+    if (vec[k] >= 0) {
+      at[k] = reinterpret_cast<const LsqVecI*>(tb.vec_at)[i];
+      w0[k] = reinterpret_cast<const LsqVecF*>(tb.vec_w0)[i];
+      w1[k] = reinterpret_cast<const LsqVecF*>(tb.vec_w1)[i];
+    }
+  }
+  // ... and its filters (a bank has at most 2 * kLsqCollectThreads): where the run starts in the staged frame, and its length
+  int first[2], run[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int m = tid + r * kLsqCollectThreads;
+    first[r] = m < M ? tb.first[m] : 0;
+    run[r] = m < M ? tb.run[m] : 0;
+  }
+  const float* grow = gx + (row * (size_t)T + (size_t)t0) * (size_t)stride;
+#pragma unroll
+  for (int k = 0; k < NV; ++k)
+    if (vec[k] >= 0) g[k] = reinterpret_cast<const LsqVecF*>(grow)[vec[k]];
+  __syncthreads();
+  for (int j = 0; j < nfr; ++j) {
+    float* yj = ys + j * Ms;
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+      if (vec[k] >= 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int dst = at[k].v[e] & 0xffff, m0 = at[k].v[e] >> 16;
+          if (dst != 0xffff) gs[dst] = lsq_collect_masked(w0[k].v[e], w1[k].v[e], yj[m0], yj[m0 + 1], g[k].v[e]);
+        }
+      }
+    if (j + 1 < nfr) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k)
+        if (vec[k] >= 0) g[k] = reinterpret_cast<const LsqVecF*>(grow + (size_t)(j + 1) * (size_t)stride)[vec[k]];
+    }
+    __syncthreads();  // the frame is whole, and nobody reads y of frame j any more
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int m = tid + r * kLsqCollectThreads;
+      if (m < M) yj[m] = lsq_collect_sum(tb.wt + m, (size_t)M, gs + first[r], run[r]);
+    }
+    __syncthreads();  // the next frame overwrites gs
+  }
+  float* crow = c + row * (size_t)M * (size_t)T + (size_t)t0;
+  for (int i = tid; i < M * FR; i += kLsqCollectThreads) {
+    const int m = i / FR, j = i - m * FR;
+    if (j < nfr) crow[(size_t)m * (size_t)T + j] = ys[j * Ms + m];
+  }
+}
+
 }  // namespace
+
+size_t lsq_collect_lds_bytes(int M, int n_bins) {
+  return ((size_t)((lsq_expand_frames(M) * lsq_y_stride(M) + 3) & ~3) + (size_t)n_bins) * sizeof(float);
+}
+
+template <int NV>
+static hipError_t launch_lsq_collect_nv(const LsqCollectTables& tb, const float* y, const float* gx, float* c, int B, int M, int T, int stride,
+                                        int chunks, int FR, size_t lds, hipStream_t s) {
+  const hipError_t e = hipFuncSetAttribute((const void*)lsq_collect_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(lsq_collect_kernel<NV>, dim3((unsigned)((size_t)B * chunks)), dim3(kLsqCollectThreads), lds, s, y, gx, tb, c, M, T, stride,
+                     chunks, FR);
+  return hipGetLastError();
+}
+
+// nrows * ceil(T / lsq_expand_frames(M)) must stay below 2^31 (the caller has checked B * T)
+hipError_t launch_lsq_collect(const LsqCollectTables& tb, const float* y, const float* gx, float* c, int B, int M, int T, int stride, hipStream_t s) {
+  const int FR = lsq_expand_frames(M), chunks = (T + FR - 1) / FR;
+  const size_t lds = lsq_collect_lds_bytes(M, tb.n_bins);  // above the 64 KB a kernel gets unasked
+  const int nv = (tb.n_vecs + kLsqCollectThreads - 1) / kLsqCollectThreads;
+  return nv <= 1   ? launch_lsq_collect_nv<1>(tb, y, gx, c, B, M, T, stride, chunks, FR, lds, s)
+         : nv == 2 ? launch_lsq_collect_nv<2>(tb, y, gx, c, B, M, T, stride, chunks, FR, lds, s)
+         : nv == 3 ? launch_lsq_collect_nv<3>(tb, y, gx, c, B, M, T, stride, chunks, FR, lds, s)
+         : nv == 4 ? launch_lsq_collect_nv<4>(tb, y, gx, c, B, M, T, stride, chunks, FR, lds, s)
+         : nv == 5 ? launch_lsq_collect_nv<kLsqCollectVecs>(tb, y, gx, c, B, M, T, stride, chunks, FR, lds, s)
+                   : hipErrorInvalidValue;
+}
 
 size_t lsq_expand_lds_bytes(int M) { return (size_t)lsq_expand_frames(M) * lsq_y_stride(M) * sizeof(float); }
 

@@ -92,4 +92,41 @@ RFX_HD void lsq_backward_sweep(const float* __restrict__ nl, const float* __rest
   }
 }
 
+// ---- backward: g_mel = G^-1 c, c = fb^T (gx where the relu is open) -------------------------------------------------------------------
+// G is symmetric, so the backward's solve is the two sweeps above on another right-hand side.  What is new is the collect:
+//   open[f] = fmaf(w1[f], y[m0[f] + 1], w0[f] y[m0[f]]) > 0     lsq_expand_value's own expression on the forward's y: the mask is
+//                                                               the forward's x > 0 bit for bit, and 0 where v <= 0 as torch.relu
+//   c[m]    = sum over the bins f of filter m, ASCENDING f, acc = fmaf(w(f, m), open[f] ? gx[f] : 0, acc), acc = 0 before the first
+// A filter's bins are one run (rfx_plan_core.h: bank_lstsq_collect), so the order is the plan's alone: first the bins whose first
+// filter is m - 1 (weight w1), then those whose first filter is m (weight w0).  A closed bin enters as +0.0 whatever gx holds there
+// (a NaN included); every bin is read from ONE position of the frame, its first slot.  No atomics: a c[m] is one lane's chain.
+// Linear in gx with power-of-two-exact roundings, as the sweeps are.
+constexpr int kLsqCollectThreads = 512;  // collect workgroup
+constexpr int kLsqCollectVecs = 5;       // 16-byte vectors of a frame one thread masks: bank_lstsq_collect admits at most 5 * 512
+
+RFX_HD float lsq_collect_masked(float w0, float w1, float y0, float y1, float gx) {
+  const float v = fmaf(w1, y1, w0 * y0);
+  return v > 0.f ? gx : 0.f;
+}
+// w: the n weights of a filter's run, `wstride` floats apart (1: the host lists; n_mels: the device's table, transposed so that the
+// lanes of a wave - consecutive filters - read one line per step); g: the masked gradient of its bins; both in ascending bin order.
+// Eight terms' inputs are loaded before their chain runs; the chain itself is one fmaf per term in that order.
+constexpr int kLsqCollectBatch = 8;
+RFX_HD float lsq_collect_sum(const float* __restrict__ w, size_t wstride, const float* g, int n) {
+  float acc = 0.f;
+  for (int i0 = 0; i0 < n; i0 += kLsqCollectBatch) {
+    float wv[kLsqCollectBatch], gv[kLsqCollectBatch];
+#pragma unroll
+    for (int k = 0; k < kLsqCollectBatch; ++k) {
+      const int i = i0 + k;
+      wv[k] = i < n ? w[(size_t)i * wstride] : 0.f;
+      gv[k] = i < n ? g[i] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < kLsqCollectBatch; ++k)
+      if (i0 + k < n) acc = fmaf(wv[k], gv[k], acc);
+  }
+  return acc;
+}
+
 }  // namespace rfx

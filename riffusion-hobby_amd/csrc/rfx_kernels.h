@@ -588,6 +588,21 @@ struct LsqTables {
 hipError_t launch_lsq_solve(const LsqTables& tb, const float* mel, float* zy, int B, int M, int T, hipStream_t s);
 // y (B, M, T) -> out [B * T][stride] (stride a multiple of four, out 16-byte aligned): max(0, w0 y[m0] + w1 y[m0 + 1]) per position
 hipError_t launch_lsq_expand(const LsqTables& tb, const float* y, float* out, int B, int M, int T, int stride, hipStream_t s);
+// backward of the closed form: the collect's tables (rfx_plan_core.h: bank_lstsq_collect)
+struct LsqCollectTables {
+  const float* wt;      // [longest run][M]: entry i of filter m's run at i * M + m
+  const int* first;     // [M]
+  const int* run;       // [M]
+  const int* vec;       // [n_vecs]
+  const int* vec_at;    // [n_vecs][4]
+  const float* vec_w0;  // [n_vecs][4]
+  const float* vec_w1;  // [n_vecs][4]
+  int n_vecs, n_bins;
+};
+size_t lsq_collect_lds_bytes(int M, int n_bins);
+// y (B, M, T), gx [B * T][stride] (stride a multiple of four, gx 16-byte aligned) -> c (B, M, T): the transposed filterbank of gx
+// where the forward's relu is open, every bin read once from its first slot.  n_vecs <= kLsqCollectVecs * kLsqCollectThreads.
+hipError_t launch_lsq_collect(const LsqCollectTables& tb, const float* y, const float* gx, float* c, int B, int M, int T, int stride, hipStream_t s);
 
 // backward of the forward path (rfx_mel_bwd.hip, arithmetic in rfx_mel_bwd_core.h).  launch_mel_bwd_spec: the magnitude slots
 // S [B*T][sstride] a MODE 0 frame launch reads - weight[k] gS[k] / |X[k]| with gS from g_mel (B, M, T) through the adjoint table

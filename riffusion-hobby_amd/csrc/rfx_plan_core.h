@@ -653,6 +653,73 @@ inline LstsqBank bank_lstsq(const PlanBank& b) {
   return q;
 }
 
+// Backward of the closed form (rfx_imel_lstsq.hip: lsq_collect_kernel; the order is rfx_imel_lstsq_core.h's): what the collect
+// c = fb^T (gx where the relu is open) walks.  A filter's bins are one run [band_lo, band_hi) of ascending bins, so the lists are
+// CSR over filters: ptr [M + 1], and per entry the bin, the weight fb[bin][m] (= bin_w0 of a bin whose first filter is m, bin_w1 of
+// one whose first filter is m - 1) and the position of the frame the bin is read from.  A bin counts ONCE: from its FIRST slot
+// (PlanBank::bin_pos; the specialised layout holds 440 bins a second time at bin_pos2, which the collect never reads, as it never
+// reads padding or a bin without a filter).
+// The kernel stages a frame's masked gradient in bin order, bins [f_lo, f_hi) at index bin - f_lo: `first` is a filter's run there,
+// and the frame's 16-byte vectors that hold at least one counted position are listed with, per element, where it goes and what the
+// mask needs: at = index | first filter << 16 (index 0xffff: not counted), and the bin's two weights.
+struct LstsqCollect {
+  std::vector<int> ptr, bin, pos;  // [M + 1], [nnz], [nnz]
+  std::vector<float> w;            // [nnz]
+  int n_bins = 0;                  // f_hi - f_lo: floats of the staged frame
+  std::vector<int> first, run;     // [M] where a filter's run starts in the staged frame, and its length
+  std::vector<float> wt;           // [longest run][M]: w transposed, entry i of filter m at i * M + m (0 behind a run's end)
+  std::vector<int> vec;            // [n_vecs] index of the 16-byte vector in a frame
+  std::vector<int> vec_at;         // [n_vecs][4]
+  std::vector<float> vec_w0, vec_w1;  // [n_vecs][4]
+};
+inline LstsqCollect bank_lstsq_collect(const PlanBank& b) {
+  LstsqCollect q;
+  const int M = b.M;
+  q.ptr.assign(M + 1, 0);
+  q.first.assign(M, 0);
+  for (int m = 0; m < M; ++m) {
+    q.ptr[m] = (int)q.w.size();
+    q.first[m] = b.band_lo[m] - b.f_lo;
+    for (int f = b.band_lo[m]; f < b.band_hi[m]; ++f) {
+      q.bin.push_back(f);
+      q.pos.push_back(b.bin_pos[f]);
+      q.w.push_back(b.csr_w[(size_t)b.csr_ptr[m] + (f - b.band_lo[m])]);
+    }
+  }
+  q.ptr[M] = (int)q.w.size();
+  q.n_bins = b.f_hi - b.f_lo;
+  q.run.assign(M, 0);
+  int longest = 0;
+  for (int m = 0; m < M; ++m) {
+    q.run[m] = q.ptr[m + 1] - q.ptr[m];
+    longest = q.run[m] > longest ? q.run[m] : longest;
+  }
+  q.wt.assign((size_t)longest * M, 0.f);
+  for (int m = 0; m < M; ++m)
+    for (int i = 0; i < q.run[m]; ++i) q.wt[(size_t)i * M + m] = q.w[(size_t)q.ptr[m] + i];
+  for (int v = 0; v < b.frame_stride / 4; ++v) {
+    int at[4];
+    float w0[4], w1[4];
+    bool any = false;
+    for (int e = 0; e < 4; ++e) {
+      const int p = 4 * v + e, f = b.pos_bin[p];
+      at[e] = 0xffff | (M << 16);
+      w0[e] = w1[e] = 0.f;
+      if (f < 0 || b.bin_m0[f] < 0 || b.bin_pos[f] != p) continue;
+      at[e] = (f - b.f_lo) | (b.bin_m0[f] << 16);
+      w0[e] = b.bin_w0[f];
+      w1[e] = b.bin_w1[f];
+      any = true;
+    }
+    if (!any) continue;
+    q.vec.push_back(v);
+    q.vec_at.insert(q.vec_at.end(), at, at + 4);
+    q.vec_w0.insert(q.vec_w0.end(), w0, w0 + 4);
+    q.vec_w1.insert(q.vec_w1.end(), w1, w1 + 4);
+  }
+  return q;
+}
+
 // everything plan creation derives from a dense filterbank fb [n_stft][n_mels] (n_mels > 0)
 inline PlanBank plan_bank(const PlanGeometry& g, int n_mels, const float* fb, const rfx_plan_options& opt, const PlanOverrides& ov) {
   PlanBank b;

@@ -6,7 +6,7 @@ and here their gradients run on the device (include/rfx.h, "BACKWARD of the forw
 Three `torch.autograd.Function`s over a `_hip.Plan`.  Each forward makes the call the member makes without autograd - the same
 bytes - and saves the least it can: the fused function saves the waveform only (the backward re-analyses it; a kept spectrum
 would be 2.3 GB at 64 stereo tiles).  The backwards are `once_differentiable`: a double backward raises.
-The inverse members (InverseMelScale's SGD, Griffin-Lim) and the loop encode have no backward.
+The iterative inverse members (InverseMelScale's SGD, Griffin-Lim) and the loop encode have no backward.
 
 A fourth function, `SpectralLossFunction`, is the pair of the multi-resolution STFT loss - spectral convergence and log-magnitude L1 -
 fused with the transform (include/rfx.h, "FUSED SPECTRAL LOSSES"): the forward leaves three double sums per row, the backward is the
@@ -14,6 +14,11 @@ fused backward with another per-bin factor.  It serves the circular STFT too: th
 
 A fifth, `IstftFunction`, is the inverse spectrogram (include/rfx.h, "INVERSE SPECTROGRAM"): complex STFT -> audio, plain and loop.  The
 map is linear, so it saves nothing and its backward is the adjoint.
+
+A sixth, `InverseMelLstsqFunction`, is the closed-form InverseMelScale (`inverse_mel_scaler(..., inverse_mel="lstsq")`; include/rfx.h,
+rfx_inverse_mel_lstsq_backward), differentiable as torchaudio >= 2.1's relu(lstsq(...)) is: a linear map and a relu.  It saves the mel
+input only; the relu's mask is formed again in the backward.  With it a loss on audio reaches a model's mel tiles:
+mel -> inverse_mel_scaler(lstsq) -> torch.polar(., phase) -> waveform_from_spectrogram -> spectral_losses.
 """
 import typing as T
 
@@ -152,6 +157,33 @@ def istft(plan: T.Any, spec: torch.Tensor, loop: bool = False) -> torch.Tensor:
         return IstftFunction.apply(plan, spec, loop)
     B, _, Tn = spec.shape
     return plan.istft(plan.pack_complex(spec.detach()), B, Tn, loop)
+
+
+class InverseMelLstsqFunction(torch.autograd.Function):
+    """(B, n_mels, T) float32 -> (B, n_stft, T): the closed-form InverseMelScale, relu(fb G^-1 mel).  Saves `mel` only; the backward
+    (rfx_inverse_mel_lstsq_backward) forms the relu's mask again from it, bit for bit the forward's."""
+
+    @staticmethod
+    def forward(ctx: T.Any, plan: T.Any, mel: torch.Tensor) -> torch.Tensor:  # type: ignore[override]
+        B, _, Tn = mel.shape
+        ctx.plan = plan
+        ctx.save_for_backward(mel)
+        return plan.unpack_magnitudes(plan.inverse_mel_lstsq(mel), B, Tn)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: T.Any, grad: torch.Tensor) -> T.Tuple[None, torch.Tensor]:  # type: ignore[override]
+        (mel,) = ctx.saved_tensors
+        return None, ctx.plan.inverse_mel_lstsq_backward(mel, ctx.plan.pack_magnitudes(grad.to(torch.float32).contiguous()))
+
+
+def inverse_mel_lstsq(plan: T.Any, mel: torch.Tensor) -> torch.Tensor:
+    """the (B, n_stft, T) closed-form InverseMelScale of (B, n_mels, T) `mel`; with a `mel` that requires grad the result carries a
+    grad_fn, otherwise the forward call alone, nothing saved"""
+    if wants_grad(mel):
+        return InverseMelLstsqFunction.apply(plan, mel)
+    B, _, Tn = mel.shape
+    return plan.unpack_magnitudes(plan.inverse_mel_lstsq(mel.detach()), B, Tn)
 
 
 def stft(plan: T.Any, wave: torch.Tensor) -> torch.Tensor:

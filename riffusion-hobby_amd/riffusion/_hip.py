@@ -302,6 +302,19 @@ def lstsq_bank_report(cp: RfxParams, melfb: torch.Tensor, tables: bool = False):
     return (report, (neg_l, inv_d) if report.ok else None) if tables else report
 
 
+def lstsq_collect_lists(cp: RfxParams, melfb: torch.Tensor) -> T.Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """rfx_debug_lstsq_collect (host only, no GPU) for the (n_stft, n_mels) float32 filterbank `melfb`: (ptr, bin, pos, weight), the
+    per-filter lists the backward of the closed-form InverseMelScale sums - CSR over filters, entries in summation order."""
+    melfb = melfb.to(torch.float32).contiguous()
+    lib, n = load_library(), ctypes.c_int32(0)
+    ptr = np.zeros(cp.n_mels + 1, np.int32)
+    check(lib.rfx_debug_lstsq_collect(ctypes.byref(cp), melfb.data_ptr(), ptr.ctypes.data, None, None, None, 0, ctypes.byref(n)))
+    bins, pos, w = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros(n.value, np.float32)
+    check(lib.rfx_debug_lstsq_collect(ctypes.byref(cp), melfb.data_ptr(), None, bins.ctypes.data, pos.ctypes.data, w.ctypes.data, n.value,
+                                      ctypes.byref(n)))
+    return ptr, bins, pos, w
+
+
 def bin_bands(cp: RfxParams, melfb: torch.Tensor) -> T.Tuple[np.ndarray, np.ndarray]:
     """rfx_debug_bin_bands (host only, no GPU) for the (n_stft, n_mels) float32 filterbank `melfb`: per linear bin the first and the
     last mel band with a nonzero weight, (n_stft,) int16 each, -1 / -1 for a bin no filter reaches - what `Plan.hold_bins_from_bands`
@@ -347,6 +360,9 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_plan_lstsq_ok": (c_int, [c_void_p]),
     "rfx_inverse_mel_lstsq_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_inverse_mel_lstsq": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_debug_lstsq_collect": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "rfx_inverse_mel_lstsq_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_inverse_mel_lstsq_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_stft_frames": (c_int, [c_void_p, c_int]),
     "rfx_plan_imel_kernel": (c_int, [c_void_p]),
     "rfx_plan_imel_unit_form": (c_int, [c_void_p]),
@@ -1289,6 +1305,26 @@ class Plan:
         out = torch.empty((B * Tn, self.frame_stride), dtype=torch.float32, device=mel.device)
         with self._workspace(max(1, self.lib.rfx_inverse_mel_lstsq_workspace_bytes(self.handle, B, Tn))) as ws:
             check(self.lib.rfx_inverse_mel_lstsq(self.handle, mel.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    def inverse_mel_lstsq_backward(self, mel: torch.Tensor, grad_slots: torch.Tensor) -> torch.Tensor:
+        """Gradient of `inverse_mel_lstsq` with respect to `mel` (rfx_inverse_mel_lstsq_backward): the forward's (B, n_mels, T) input
+        and a gradient over its output in slot layout (B*T, stride) - `pack_magnitudes` of torch's (B, n_stft, T) gradient - ->
+        (B, n_mels, T).  The relu's mask is formed again from `mel`; every bin counts once, from its first slot."""
+        self.require_lstsq()
+        mel = self._chk(mel, torch.float32)
+        grad_slots = self._chk(grad_slots, torch.float32)
+        B, M, Tn = mel.shape
+        if M != self.n_mels:
+            raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")
+        if tuple(grad_slots.shape) != (B * Tn, self.frame_stride):
+            raise ValueError(f"grad_slots must be (B*T, stride) = {(B * Tn, self.frame_stride)}, got {tuple(grad_slots.shape)}")
+        out = torch.empty((B, M, Tn), dtype=torch.float32, device=mel.device)
+        if B * Tn == 0:
+            return out
+        with self._workspace(max(1, self.lib.rfx_inverse_mel_lstsq_backward_workspace_bytes(self.handle, B, Tn))) as ws:
+            check(self.lib.rfx_inverse_mel_lstsq_backward(self.handle, mel.data_ptr(), grad_slots.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(),
+                                                          ws.numel(), self._stream()))
         return out
 
     # ---- codecs (no plan state needed, kept here for one binding site) -------------------------

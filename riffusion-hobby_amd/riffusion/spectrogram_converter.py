@@ -155,9 +155,23 @@ class SpectrogramConverter:
         return plan.mel_scale(x).reshape(*lead, plan.n_mels, x.shape[-1])
 
     def _inverse_mel_scale(
-        self, melspec: torch.Tensor, *, spec0: T.Optional[torch.Tensor] = None, seed: T.Optional[int] = None
+        self, melspec: torch.Tensor, *, spec0: T.Optional[torch.Tensor] = None, seed: T.Optional[int] = None, inverse_mel: str = "sgd"
     ) -> torch.Tensor:
-        """(B, n_mels, T) -> (B, n_stft, T)."""
+        """(B, n_mels, T) -> (B, n_stft, T).  `inverse_mel="lstsq"` (not in the reference's member; torchaudio >= 2.1's InverseMelScale):
+        the closed form relu(fb G^-1 mel) on the device, (..., n_mels, T) -> (..., n_stft, T) with leading dimensions as `mel_scaler`
+        takes them.  No random start: `spec0` and `seed` are refused.  Differentiable as torchaudio's is: a `melspec` that requires
+        grad gives a result with a grad_fn, the gradient runs on the device (riffusion/_autograd.py).  The default "sgd" is the
+        iterative solver, which has no gradient."""
+        from riffusion import _hip
+
+        if _hip.check_inverse_mel(inverse_mel):
+            if spec0 is not None or seed is not None:
+                raise ValueError('inverse_mel="lstsq" has no random start: spec0 and seed do not go with it')
+            plan = self._plan()
+            plan.require_lstsq()
+            lead = melspec.shape[:-2]
+            x = melspec.reshape(-1, melspec.shape[-2], melspec.shape[-1]).to(self.device)
+            return _autograd.inverse_mel_lstsq(plan, x.to(torch.float32)).reshape(*lead, plan.n_stft, x.shape[-1])
         plan = self._plan()
         B, _, Tn = melspec.shape
         spec0 = spec0.to(self.device) if spec0 is not None else None
