@@ -887,6 +887,58 @@ size_t rfx_inverse_mel_lstsq_backward_workspace_bytes(const rfx_plan* plan, int 
 int rfx_inverse_mel_lstsq_backward(const rfx_plan* plan, const float* d_mel, const float* d_grad_slots, int B, int T, float* d_grad_mel,
                                    void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- GUIDED DECODE, BACKWARD: the gradient of the zero-iteration phase-guided decode -------------------------------------------------
+ * A guided call (rfx_guided_call_options) with n_iter = 0 returns w = ISTFT(S u), u = a / (|a| + 1e-16) the unit phase of
+ * a = STFT(staged guide): linear in the magnitudes S, the guide a constant.  For an incoming g_w (B, L) float32, L the form's samples:
+ *     G   = rfx_istft_backward(g_w)  (loop: rfx_istft_backward_loop)         the synthesis adjoint, gradient slots
+ *     g_S = Re(conj(u) G) = u_re G_re + u_im G_im  per slot position         rfx_griffinlim_guided_backward: the STAGE entry
+ *     g_mel = rfx_inverse_mel_lstsq_backward(mel, g_S)                       rfx_waveform_from_mel_guided_backward: the FUSED entry
+ * The stage entry is the gradient of rfx_griffinlim_ex (guided, n_iter = 0) with respect to d_mag_slots; the fused entry that of
+ * rfx_waveform_from_mel_ex (RFX_CALL_INVERSE_MEL_LSTSQ, guided, n_iter = 0) with respect to d_mel, and is the stage entry followed by
+ * rfx_inverse_mel_lstsq_backward in one workspace - the same bytes.  Nothing but mel and the guide has to be kept from the forward:
+ * the guide is analysed again, as rfx_mel_from_waveform_backward forms its spectrum again.
+ *   THE GUIDE  d_guide (B, guide_samples) float32, contiguous rows, is staged as the forward stages it: cut to L samples or
+ *     zero-padded at its end to L (loop: L = hop T), times the power of two that brings the row's peak into [2^14, 2^15) - a shorter
+ *     guide equals the same guide zero-padded by the caller, guide * 2^m gives the same bytes - then transformed by the plan's forward
+ *     frame kernel (rfx_stft: reflect padding; loop: rfx_stft_loop).  u is the forward's projection rule in IEEE operations (fmaf,
+ *     sqrt, divide: a host emulator gives the device's bits); the forward's launch forms the same factor with one v_rsq_f32, 1 ulp
+ *     from it, and its epsilon is the same 1e-16 expressed in the units of the row's range factor.  a == 0 gives u = 0 in both: a
+ *     silent bin passes no gradient, a silent guide row gives a zero gradient row.  No gradient flows to the guide.
+ *   RANGE  the forward's power-of-two range factors (row_scale) cancel inside the forward and never enter its derivative; the backward
+ *     draws no range table and squares nothing of g_w, so g_w * 2^k gives g_S * 2^k and g_mel * 2^k bit for bit while no intermediate
+ *     leaves float32's normal range (the tests hold 2^+-40).
+ *   THE PROJECTION KERNEL  (rfx_guide_bwd.hip) reads G and a, two complex cubes in rfx_pack_complex's layout, 16 bytes per lane, and
+ *     writes g_S in rfx_pack_magnitudes' layout, 16 bytes per lane: EVERY float of every frame is written - padding positions 0, both
+ *     slots of a bin the specialised layout holds twice (each from the complex pair that slot multiplied), the bins no filter reaches -
+ *     although rfx_inverse_mel_lstsq_backward reads only the counted copy of a bin.  No atomics; a frame's bytes are a function of that
+ *     frame alone, not of B, the row's place or the grid.  It is bound by memory: 20 bytes per position.
+ * d_grad_mag_slots: [B * T][frame stride] float32.  d_mel, d_grad_mel: (B, n_mels, T).
+ * Contract: B == 0 is a no-op.  Refusals, all before any launch, outputs untouched: a NULL pointer; T < 2; B * T >= 2^31;
+ * guide_samples <= 0; the plain form where the L samples of T frames are not more than the reflect padding n_fft / 2 (the forward
+ * refuses such a guide); a loop form with hop T < n_fft, or on a chirp-z plan (RFX_ERR_UNSUPPORTED); the fused entries on a plan that
+ * is not rfx_plan_lstsq_ok (RFX_ERR_INVALID with the reason); d_workspace or d_grad_mag_slots not 16-byte aligned, a float tensor not
+ * 4-byte aligned; a workspace below the query (RFX_ERR_WORKSPACE).  A query answers 0 where the call would be refused.  BOUNDED
+ * WORKSPACE of the stage entry: rows are walked in groups of max(1, 256 MiB / row bytes) whole rows; the fused entry holds g_S of all
+ * B rows in front of it.  Inputs are not written. */
+size_t rfx_griffinlim_guided_backward_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_griffinlim_guided_backward(const rfx_plan* plan, const float* d_guide, int guide_samples, const float* d_grad_wave, int B, int T,
+                                   float* d_grad_mag_slots, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t rfx_griffinlim_guided_backward_loop_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_griffinlim_guided_backward_loop(const rfx_plan* plan, const float* d_guide, int guide_samples, const float* d_grad_wave, int B,
+                                        int T, float* d_grad_mag_slots, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t rfx_waveform_from_mel_guided_backward_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_waveform_from_mel_guided_backward(const rfx_plan* plan, const float* d_mel, const float* d_guide, int guide_samples,
+                                          const float* d_grad_wave, int B, int T, float* d_grad_mel, void* d_workspace,
+                                          size_t workspace_bytes, void* stream);
+size_t rfx_waveform_from_mel_guided_backward_loop_workspace_bytes(const rfx_plan* plan, int B, int T);
+int rfx_waveform_from_mel_guided_backward_loop(const rfx_plan* plan, const float* d_mel, const float* d_guide, int guide_samples,
+                                               const float* d_grad_wave, int B, int T, float* d_grad_mel, void* d_workspace,
+                                               size_t workspace_bytes, void* stream);
+/* The projection kernel's two position tables, without a plan or a GPU (tests): h_xpos_bin[x] the bin complex position x of a frame
+ * holds (-1: padding), h_s2x[p] the complex position magnitude slot p goes with (-1: padding).  *stride_out: positions per frame,
+ * the same for both; the arrays are optional and need capacity >= *stride_out (call once with NULL arrays to learn it). */
+int rfx_debug_guide_project_tables(const rfx_params* params, int32_t* h_xpos_bin, int32_t* h_s2x, int capacity, int32_t* stride_out);
+
 /* ---- inverse, in one call: SpectrogramConverter.waveform_from_mel_amplitudes, spectrogram_converter.py:187-204
  * (`self.inverse_mel_scaler(amplitudes_mel)` :201 then `self.inverse_spectrogram_func(amplitudes_linear)` :204).
  * d_mel (B, n_mels, T) -> d_wave_out (B, rfx_griffinlim_output_samples(plan, T)); clips of `channels_per_clip` rows as in

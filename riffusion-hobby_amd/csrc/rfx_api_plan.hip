@@ -365,6 +365,26 @@ int rfx_debug_lstsq_collect(const rfx_params* params, const float* h_melfb, int3
   return RFX_OK;
 }
 
+int rfx_debug_guide_project_tables(const rfx_params* params, int32_t* h_xpos_bin, int32_t* h_s2x, int capacity, int32_t* stride_out) {
+  if (!params || !stride_out) return fail(RFX_ERR_INVALID, "rfx_debug_guide_project_tables: null argument");
+  rfx_plan_options opt;
+  if (const int rc = resolve_options(nullptr, &opt)) return rc;
+  PlanGeometry geo;
+  std::string err;
+  if (const int rc = plan_geometry(*params, opt, plan_overrides(), &geo, &err)) return fail(rc, err);
+  const MelBwdTables mb = mel_bwd_tables(geo);
+  const std::vector<int>& s2x = geo.generic ? mb.xpos_bin : mb.s2x;  // (plain frames: a magnitude position is its bin's spectrum position)
+  const int n = (int)mb.xpos_bin.size();
+  *stride_out = n;
+  if (h_xpos_bin || h_s2x) {
+    if (capacity < n)
+      return fail(RFX_ERR_INVALID, "rfx_debug_guide_project_tables: a frame has " + std::to_string(n) + " positions, capacity is " + std::to_string(capacity));
+    if (h_xpos_bin) memcpy(h_xpos_bin, mb.xpos_bin.data(), (size_t)n * sizeof(int32_t));
+    if (h_s2x) memcpy(h_s2x, s2x.data(), (size_t)n * sizeof(int32_t));
+  }
+  return RFX_OK;
+}
+
 int rfx_hold_mask_words(const rfx_plan* plan) { return plan ? (plan->n_stft + 31) / 32 : 0; }
 
 int rfx_debug_bin_bands(const rfx_params* params, const float* h_melfb, int16_t* lo, int16_t* hi) {

@@ -538,8 +538,18 @@ RFX_HD void p3_inverse(cf* cube, cf (&Z)[21], TW tw2, int k1, int ka, STAGE stag
 // per row (GlRowScale: the row's magnitudes brought to the 2^25 the path was tuned and tested at), so that re^2 + im^2 can
 // neither overflow (|a| > 1.8e19 squared to inf, rsq gave 0: silence, at max_value 1e20) nor vanish; the factor S / (|a| + eps)
 // is the unscaled one up to that power of two, which the product with the scaled `a` cancels: the result is S * angles as before.
+// The rule in IEEE operations only (fmaf, a correctly rounded sqrt and divide): the host form of gl_project, and - on the device as
+// on the host, so that a host emulator gives the device's bits - the unit phase of the guided decode's backward (rfx_guide_core.h).
+RFX_HD cf gl_project_ieee(cf a, float S) {
+  const float mag = sqrtf(fmaf(a.re, a.re, a.im * a.im));
+  const float sc = S / (mag + 1e-16f);
+  return cf{a.re * sc, a.im * sc};
+}
 RFX_HD cf gl_project(cf a, float S, float eps2 = 1e-32f) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if !defined(__HIP_DEVICE_COMPILE__)
+  (void)eps2;
+  return gl_project_ieee(a, S);
+#else
 #ifndef RFX_PROJECT_SQRT_RCP
   // One quarter-rate instruction per bin: S / (|a| + 1e-16) = S * rsq(|a|^2 + 1e-32) up to fp32 rounding
   // whenever |a| > 1e-8 (the 1e-16 is then below half an ulp of |a|) and exactly 0 for a == 0, as in the
@@ -552,14 +562,11 @@ RFX_HD cf gl_project(cf a, float S, float eps2 = 1e-32f) {
   const float mag = __builtin_amdgcn_sqrtf(fmaf(a.re, a.re, a.im * a.im));
   const float sc = S * __builtin_amdgcn_rcpf(mag + 1e-16f);
 #endif
-#else
-  const float mag = sqrtf(fmaf(a.re, a.re, a.im * a.im));
-  const float sc = S / (mag + 1e-16f);
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && defined(RFX_PK)
+#if defined(RFX_PK)
   return pk_to(pk_of(a) * pk_bc(sc));
 #else
   return cf{a.re * sc, a.im * sc};
+#endif
 #endif
 }
 

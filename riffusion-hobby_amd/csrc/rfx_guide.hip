@@ -102,6 +102,54 @@ hipError_t launch_guide_stage(const float* guide, long long stride, int guide_sa
   return hipSuccess;
 }
 
+// The same staging for the guided decode's backward (rfx_api_guided.hip): rows of exactly L samples, L floats apart, as the plan's
+// forward transform takes them (rfx_stft, rfx_stft_loop) - such a row need not start on 16 bytes, so the stores are scalar.  No
+// kernel factor (c = 1).  The chunks here cover L samples; max is exact in any order, so the peak is the forward's.
+template <bool VEC>
+__global__ void __launch_bounds__(kGuideThreads) guide_stage_rows_kernel(const float* __restrict__ guide, long long stride, int n_valid, int L, int row0,
+                                                                         const float* __restrict__ peaks, float* __restrict__ dst) {
+  __shared__ float lds[kGuideThreads / 64];
+  const int chunk = blockIdx.x, chunks = gridDim.x, row = row0 + (int)blockIdx.y;
+  float peak = 0.f;
+  for (int c = threadIdx.x; c < chunks; c += kGuideThreads) peak = fmaxf(peak, peaks[(size_t)row * chunks + c]);
+  peak = block_max(peak, lds);
+  const GuideScale s = guide_scale(peak, 0.f);
+  const float* __restrict__ src = guide + (long long)row * stride;
+  float* __restrict__ out = dst + (size_t)row * L;
+#pragma unroll
+  for (int i = 0; i < kGuideVecsPerThread; ++i) {
+    const int p = guide_vec_at(chunk, i, threadIdx.x);
+    if (p >= L) continue;
+    v4 v = {0.f, 0.f, 0.f, 0.f};
+    if (p < n_valid) {
+      v = guide_load4<VEC>(src, n_valid, p);
+      v = v4{guide_apply(v.x, s), guide_apply(v.y, s), guide_apply(v.z, s), guide_apply(v.w, s)};
+    }
+    out[p] = v.x;
+    if (p + 1 < L) out[p + 1] = v.y;
+    if (p + 2 < L) out[p + 2] = v.z;
+    if (p + 3 < L) out[p + 3] = v.w;
+  }
+}
+
+hipError_t launch_guide_stage_rows(const float* guide, long long stride, int guide_samples, int B, int L, float* peaks, float* dst, hipStream_t stream) {
+  const int n_valid = guide_samples < L ? guide_samples : L;
+  const int chunks = guide_chunks(L);
+  const bool vec = ((uintptr_t)guide & 15) == 0 && (stride & 3) == 0;
+  for (int r0 = 0; r0 < B; r0 += 65535) {  // (grid y is 16 bits wide)
+    const int n = B - r0 < 65535 ? B - r0 : 65535;
+    const dim3 grid((unsigned)chunks, (unsigned)n);
+    if (vec) hipLaunchKernelGGL(guide_peak_kernel<true>, grid, dim3(kGuideThreads), 0, stream, guide, stride, n_valid, r0, peaks);
+    else hipLaunchKernelGGL(guide_peak_kernel<false>, grid, dim3(kGuideThreads), 0, stream, guide, stride, n_valid, r0, peaks);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (vec) hipLaunchKernelGGL(guide_stage_rows_kernel<true>, grid, dim3(kGuideThreads), 0, stream, guide, stride, n_valid, L, r0, peaks, dst);
+    else hipLaunchKernelGGL(guide_stage_rows_kernel<false>, grid, dim3(kGuideThreads), 0, stream, guide, stride, n_valid, L, r0, peaks, dst);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // ---- the free-frame list of a held call (rfx_guide_core.h): counts per chunk of rows, a scan over the chunks, the fill ----------------
 namespace {
 // exclusive prefix sum of one value per thread of a kHoldThreads workgroup; *total: the workgroup's sum.  lds: kHoldThreads / 64 ints

@@ -1,6 +1,6 @@
 // rfx_guide_core.h - arithmetic of the guide staging (rfx_guide.hip), written once for the gfx950 kernels (hipcc) and the host
-// emulators of the CPU tests (tests/emu/rfx_guide_emu.cpp, tests/emu/rfx_hold_emu.cpp, g++).  Below the staging: the held frames of a
-// guided call and the list of the frames that are not held.
+// emulators of the CPU tests (tests/emu/rfx_guide_emu.cpp, tests/emu/rfx_guide_bwd_emu.cpp, tests/emu/rfx_hold_emu.cpp, g++).  Below the
+// staging: the projection of the guided decode's backward; the held frames of a guided call and the list of the frames that are not held.
 //
 // A guided Griffin-Lim call (include/rfx.h: rfx_guided_call_options) starts from the phase of a caller's waveform instead of random
 // phases: its first launch is MODE 1 - a = STFT(x), normalise, ISTFT(|S| a / |a|) - with x the guide.  Staging brings row r of the
@@ -60,6 +60,24 @@ RFX_HD GuideScale guide_scale(float peak, float ks) {
   return s;
 }
 RFX_HD float guide_apply(float x, const GuideScale& s) { return ((x * s.a) * s.b) * s.c; }
+
+// ---- the guided decode's backward (include/rfx.h: rfx_griffinlim_guided_backward) -------------------------------------------------
+// At zero iterations a guided call returns w = ISTFT(S u), u = a / (|a| + 1e-16) the unit phase of a = STFT(staged guide): linear
+// in S.  For an incoming g_w, with G the gradient of the synthesis with respect to its complex input (rfx_istft_backward), the
+// gradient with respect to a magnitude is g_S = Re(conj(u) G) = u_re G_re + u_im G_im, per position of the slot cube: a conjugate
+// slot holds conj(a) and conj(G) and gives the same number.  u is the forward's projection rule at S = 1 (rfx_core.h: gl_project)
+// in its IEEE form, on the device too, so that tests/emu/rfx_guide_bwd_emu.cpp gives the kernel's bits; the forward's launch forms
+// the same factor with one v_rsq_f32 (1 ulp).  a == 0 gives u = 0 in both: a silent bin, and every bin of a silent guide row,
+// passes no gradient.  The guide is staged as the forward stages it - fit and range above - with no kernel factor (c = 1): the
+// forward's own factor row_scale[2 r] = 2^-j is a power of two that its analysis multiplies back in, so a is the forward's a whatever
+// the magnitudes' range is; its eps is the same 1e-16 times 2^-j (row_scale[2 r + 1]) and matters only for 0 < |a| within a few
+// orders of it, far below what a ranged guide's bins hold.  The backward takes 1e-16 itself and needs no range table.  g_S is linear
+// in g_w with power-of-two-exact roundings.
+RFX_HD cf guide_unit(cf a) { return gl_project_ieee(a, 1.f); }
+RFX_HD float guide_project(cf a, cf G) {
+  const cf u = guide_unit(a);
+  return fmaf(u.re, G.re, u.im * G.im);
+}
 
 // ---- held frames (include/rfx.h: rfx_held_call_options) -----------------------------------------------------------------------------
 // A guided call may hold the first `head` and the last `tail` frames of a row at the guide's phase: after every projection the

@@ -554,6 +554,21 @@ hipError_t launch_spectral_sums(const float* a, const float* m, int rows, int T,
 // Lpad a multiple of 64, dst and zero 16-byte aligned; the guide needs float alignment only.
 hipError_t launch_guide_stage(const float* guide, long long stride, int guide_samples, int B, int L, int Lpad, const float* row_scale,
                               float* peaks, float* dst, float* zero, hipStream_t stream);
+// the guided decode's backward (include/rfx.h: rfx_griffinlim_guided_backward).  The same fit and range, no kernel factor, into rows
+// of exactly L floats (dst[r][L], any float alignment: what rfx_stft and rfx_stft_loop read); peaks: B * guide_chunks(L) floats
+hipError_t launch_guide_stage_rows(const float* guide, long long stride, int guide_samples, int B, int L, float* peaks, float* dst, hipStream_t stream);
+// ... and the guide projection (rfx_guide_bwd.hip; guide_project of rfx_guide_core.h): G and A are B * T frames of xstride complex
+// slots (rfx_pack_complex's layout), out B * T frames of sstride floats (rfx_pack_magnitudes' layout).  xpos_bin [xstride]: the bin
+// a complex position holds, -1 for padding; s2x [sstride]: the complex position a magnitude slot goes with, -1 for padding
+struct GuideProjectArgs {
+  const cf* G;
+  const cf* A;
+  float* out;
+  const int* xpos_bin;
+  const int* s2x;
+  int B, T, xstride, sstride;
+};
+hipError_t launch_guide_project(const GuideProjectArgs& a, hipStream_t stream);
 // the free-frame list of a held call (rfx_guide_core.h): hold = (B, 2) {head, tail} per row, any values (clamped); list =
 // hold_list_words(B, T) ints: the indices row T + t of the frames that are not held, increasing, their count at list[B T], the
 // compaction's chunk offsets behind it.  Three launches, no atomics, nothing read back.

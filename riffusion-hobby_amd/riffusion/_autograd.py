@@ -19,6 +19,11 @@ A sixth, `InverseMelLstsqFunction`, is the closed-form InverseMelScale (`inverse
 rfx_inverse_mel_lstsq_backward), differentiable as torchaudio >= 2.1's relu(lstsq(...)) is: a linear map and a relu.  It saves the mel
 input only; the relu's mask is formed again in the backward.  With it a loss on audio reaches a model's mel tiles:
 mel -> inverse_mel_scaler(lstsq) -> torch.polar(., phase) -> waveform_from_spectrogram -> spectral_losses.
+
+A seventh, `GuidedDecodeFunction`, is that chain with the phase of a reference clip as ONE call: the phase-guided decode at zero
+Griffin-Lim iterations with the closed-form inverse, `waveform_from_mel_amplitudes(mel, guide=clip, inverse_mel="lstsq",
+griffin_lim_iters=0)` (include/rfx.h, "GUIDED DECODE, BACKWARD").  It saves `mel` and the guide; forward and backward stay in slot
+layout from end to end - no (B, n_stft, T) tensor, real or complex, is formed.  The guide is a constant.
 """
 import typing as T
 
@@ -184,6 +189,33 @@ def inverse_mel_lstsq(plan: T.Any, mel: torch.Tensor) -> torch.Tensor:
         return InverseMelLstsqFunction.apply(plan, mel)
     B, _, Tn = mel.shape
     return plan.unpack_magnitudes(plan.inverse_mel_lstsq(mel.detach()), B, Tn)
+
+
+class GuidedDecodeFunction(torch.autograd.Function):
+    """(B, n_mels, T) float32 mel, (B, Lg) float32 guide -> (B, L) float32: ISTFT(relu(lstsq(mel)) a / |a|), a = STFT(guide) - the
+    guided decode with no Griffin-Lim iteration, the bytes of `Plan.waveform_from_mel(..., lstsq=True, guide=guide, n_iter=0)`.  Saves
+    `mel` and the guide; the backward (rfx_waveform_from_mel_guided_backward) analyses the guide again and forms the relu's mask
+    again.  The guide gets no gradient."""
+
+    @staticmethod
+    def forward(ctx: T.Any, plan: T.Any, mel: torch.Tensor, guide: torch.Tensor, loop: bool, seed: int) -> torch.Tensor:  # type: ignore[override]
+        ctx.plan, ctx.loop = plan, loop
+        ctx.save_for_backward(mel, guide)
+        return plan.waveform_from_mel(mel, int(mel.shape[0]), 0, 0.99, seed=seed, lstsq=True, guide=guide, loop=loop)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: T.Any, grad: torch.Tensor) -> T.Tuple[None, torch.Tensor, None, None, None]:  # type: ignore[override]
+        mel, guide = ctx.saved_tensors
+        return None, ctx.plan.waveform_from_mel_guided_backward(mel, guide, grad.to(torch.float32).contiguous(), ctx.loop), None, None, None
+
+
+def guided_decode(plan: T.Any, mel: torch.Tensor, guide: torch.Tensor, loop: bool, seed: int) -> torch.Tensor:
+    """the (B, L) zero-iteration guided decode of a (B, n_mels, T) `mel` that requires grad; a guide that requires grad raises, as
+    the spectral losses' target does"""
+    if guide.requires_grad:
+        raise RuntimeError("waveform_from_mel_amplitudes: the guide receives no gradient; detach it")
+    return GuidedDecodeFunction.apply(plan, mel, guide, loop, seed)
 
 
 def stft(plan: T.Any, wave: torch.Tensor) -> torch.Tensor:

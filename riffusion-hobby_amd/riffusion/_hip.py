@@ -363,6 +363,16 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_debug_lstsq_collect": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int32)]),
     "rfx_inverse_mel_lstsq_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_inverse_mel_lstsq_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # (plan, [mel,] guide, guide_samples, grad_wave, B, T, out, workspace, workspace_bytes, stream)
+    "rfx_griffinlim_guided_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_griffinlim_guided_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_griffinlim_guided_backward_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_griffinlim_guided_backward_loop": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_waveform_from_mel_guided_backward_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_waveform_from_mel_guided_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_waveform_from_mel_guided_backward_loop_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rfx_waveform_from_mel_guided_backward_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_debug_guide_project_tables": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int32)]),
     "rfx_stft_frames": (c_int, [c_void_p, c_int]),
     "rfx_plan_imel_kernel": (c_int, [c_void_p]),
     "rfx_plan_imel_unit_form": (c_int, [c_void_p]),
@@ -1325,6 +1335,57 @@ class Plan:
         with self._workspace(max(1, self.lib.rfx_inverse_mel_lstsq_backward_workspace_bytes(self.handle, B, Tn))) as ws:
             check(self.lib.rfx_inverse_mel_lstsq_backward(self.handle, mel.data_ptr(), grad_slots.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(),
                                                           ws.numel(), self._stream()))
+        return out
+
+    # ---- guided decode, backward (include/rfx.h "GUIDED DECODE, BACKWARD"; riffusion/_autograd.py: GuidedDecodeFunction) ----
+    def _guided_backward_args(self, guide: torch.Tensor, grad_wave: torch.Tensor, B: int, Tn: int, loop: bool) -> T.Tuple[torch.Tensor, torch.Tensor]:
+        """the guide and the incoming gradient as the backward entries read them - contiguous (B, Lg) and (B, L) float32 - or the
+        refusal of a call the forward refuses, before any device work"""
+        if loop:
+            if self.griffinlim_engine == "chirp-z":
+                raise ValueError("a loop decode is not served on the chirp-z engine (RFX_ERR_UNSUPPORTED)")
+            check_loop_frames(self.hop_length, self.n_fft, Tn)
+        guide = self._chk_guide(guide).contiguous()
+        g = self._chk(grad_wave, torch.float32)
+        L = self.output_samples(Tn, loop)
+        if guide.shape[0] != B or guide.shape[1] < 1:
+            raise ValueError(f"guide must be ({B}, Lg >= 1), got {tuple(guide.shape)}")
+        if tuple(g.shape) != (B, L):
+            raise ValueError(f"expected a ({B}, {L}) gradient, got {tuple(g.shape)}")
+        return guide, g
+
+    def griffinlim_guided_backward(self, guide: torch.Tensor, grad_wave: torch.Tensor, Tn: int, loop: bool = False) -> torch.Tensor:
+        """rfx_griffinlim_guided_backward (loop: its loop twin): the gradient of `griffinlim(mag_slots, ..., n_iter=0, guide=guide)` with
+        respect to the magnitudes.  guide (B, Lg) float32, grad_wave (B, L) float32 -> (B*Tn, stride) float32 in slot layout, every
+        position written.  The guide is analysed again; no gradient flows to it."""
+        B = int(grad_wave.shape[0])
+        guide, g = self._guided_backward_args(guide, grad_wave, B, Tn, loop)
+        out = torch.empty((B * Tn, self.frame_stride), dtype=torch.float32, device=self.device)
+        if B == 0:
+            return out
+        query, entry = self._pair("griffinlim_guided_backward", loop)
+        with self._workspace(max(1, query(self.handle, B, Tn))) as ws:
+            check(entry(self.handle, guide.data_ptr(), guide.shape[1], g.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    def waveform_from_mel_guided_backward(self, mel: torch.Tensor, guide: torch.Tensor, grad_wave: torch.Tensor, loop: bool = False) -> torch.Tensor:
+        """rfx_waveform_from_mel_guided_backward (loop: its loop twin): the gradient of
+        `waveform_from_mel(mel, ..., n_iter=0, lstsq=True, guide=guide)` with respect to `mel` - `griffinlim_guided_backward`, then
+        `inverse_mel_lstsq_backward`, in one workspace: the same bytes.  mel (B, n_mels, T), guide (B, Lg), grad_wave (B, L) ->
+        (B, n_mels, T)."""
+        self.require_lstsq()
+        mel = self._chk(mel, torch.float32)
+        B, M, Tn = mel.shape
+        if M != self.n_mels:
+            raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")
+        guide, g = self._guided_backward_args(guide, grad_wave, B, Tn, loop)
+        out = torch.empty((B, M, Tn), dtype=torch.float32, device=self.device)
+        if B == 0:
+            return out
+        query, entry = self._pair("waveform_from_mel_guided_backward", loop)
+        with self._workspace(max(1, query(self.handle, B, Tn))) as ws:
+            check(entry(self.handle, mel.data_ptr(), guide.data_ptr(), guide.shape[1], g.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                        self._stream()))
         return out
 
     # ---- codecs (no plan state needed, kept here for one binding site) -------------------------

@@ -283,6 +283,7 @@ class SpectrogramConverter:
         hold_mask: T.Any = None,
         loop: bool = False,
         phase_start: str = "random",
+        griffin_lim_iters: T.Optional[int] = None,
     ) -> torch.Tensor:
         """
         (B, n_mels, T) -> (B, hop*(T-1)).  The reference treats the whole batch as ONE clip (the SGD
@@ -311,9 +312,19 @@ class SpectrogramConverter:
         magnitudes alone - the spectral peaks of every frame, their interpolated frequencies integrated over the hop
         (rfx_start_call_options).  No guide and no randomness in Griffin-Lim; it needs fewer iterations for the same spectral
         convergence at low iteration counts (README).  Not together with `angles0`, `guide`, `hold_frames` or `hold_mask`.
+        `griffin_lim_iters`: Griffin-Lim iterations in place of the params' count (None), as `audio_from_spectrogram_images` has it.
+        Differentiable in ONE form, the guided decode as a layer: with grad mode on and an `amplitudes_mel` that requires grad, the
+        call with `inverse_mel="lstsq"`, a `guide`, `griffin_lim_iters=0` and no `hold_frames`, `hold_mask`, `spec0` or `angles0`
+        (`loop` allowed) returns ISTFT(relu(lstsq(mel)) a / |a|), a = STFT(guide), with a grad_fn whose backward runs on the device
+        in slot layout from end to end (rfx_waveform_from_mel_guided_backward; `mel` and the guide are saved, the guide is analysed
+        again; a double backward raises).  The guide is a constant: one that requires grad raises.  Leading dimensions -
+        (..., n_mels, T) with a (..., Lg) guide - and a CPU leaf are handled as `inverse_mel_scaler` handles them.  Every other call
+        is the plain call, without a graph: Griffin-Lim iterations, the SGD and the held and masked forms have no gradient.
         """
         from riffusion import _hip
 
+        if griffin_lim_iters is not None and (int(griffin_lim_iters) != griffin_lim_iters or int(griffin_lim_iters) < 0):
+            raise ValueError(f"griffin_lim_iters must be a non-negative integer or None, got {griffin_lim_iters!r}")
         peaks = _hip.check_phase_start(phase_start)
         rules = functools.partial(_hip.check_call_rules, CALL_WORDING, loop=loop, peak_start=peaks, angles0=angles0, guide=guide,
                                   hold_frames=hold_frames, hold_mask=hold_mask)
@@ -322,9 +333,30 @@ class SpectrogramConverter:
         hold = hold_rows(hold_frames, B, frames) if hold_frames is not None else None
         rules("bins_need_guide", "bins_and_hold")
         bands = hold_mask_rows(hold_mask, B, n_mels, frames) if hold_mask is not None else None
+        n_iter = self.p.num_griffin_lim_iters if griffin_lim_iters is None else int(griffin_lim_iters)
+        if (_autograd.wants_grad(amplitudes_mel) and _hip.check_inverse_mel(inverse_mel) and guide is not None and n_iter == 0 and hold is None
+                and bands is None and spec0 is None and angles0 is None):
+            return self._guided_decode(amplitudes_mel, guide, seed, loop)
         return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
-                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, hold=hold, hold_bands=bands,
-                                       loop=loop, peak_start=peaks)
+                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, n_iter=griffin_lim_iters, hold=hold,
+                                       hold_bands=bands, loop=loop, peak_start=peaks)
+
+    def _guided_decode(self, amplitudes_mel: torch.Tensor, guide: torch.Tensor, seed: T.Optional[int], loop: bool) -> torch.Tensor:
+        """the differentiable form of `waveform_from_mel_amplitudes`: (..., n_mels, T) mel that requires grad, (..., Lg) guide"""
+        from riffusion import _hip
+
+        plan = self._plan()
+        plan.require_lstsq()
+        if amplitudes_mel.dim() < 3 or guide.dim() != amplitudes_mel.dim() - 1 or tuple(guide.shape[:-1]) != tuple(amplitudes_mel.shape[:-2]):
+            raise ValueError(f"expected (..., n_mels, T) mel amplitudes and a (..., Lg) guide with the same leading dimensions, got "
+                             f"{tuple(amplitudes_mel.shape)} and {tuple(guide.shape)}")
+        if loop:
+            _hip.check_loop_frames(self.p.hop_length, self.p.n_fft, int(amplitudes_mel.shape[-1]))
+        lead = amplitudes_mel.shape[:-2]
+        mel = amplitudes_mel.reshape(-1, amplitudes_mel.shape[-2], amplitudes_mel.shape[-1]).to(self.device).to(torch.float32)
+        g = guide.reshape(-1, guide.shape[-1]).to(self.device, torch.float32)
+        wave = _autograd.guided_decode(plan, mel, g, loop, self._seed(seed))
+        return wave.reshape(*lead, wave.shape[-1])
 
     def hold_frames_for(self, head_s: float = 0.0, tail_s: float = 0.0) -> T.Tuple[int, int]:
         """`SpectrogramParams.hold_frames_for` of this converter's params: the `hold_frames` pair for `head_s` / `tail_s` seconds
