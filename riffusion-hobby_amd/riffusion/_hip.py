@@ -11,6 +11,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes
+import dataclasses
 import functools
 import math
 import os
@@ -19,6 +20,8 @@ import typing as T
 
 import numpy as np
 import torch
+
+from riffusion._decode import DecodeExtras
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("RFX_LIB_PATH") or os.path.join(os.path.dirname(_PKG_DIR), "librfx.so")
@@ -962,21 +965,21 @@ class Plan:
         if self.n_stft > 10240:
             raise ValueError(f"the spectral-peak start is not served for n_stft = {self.n_stft} above 10240 (RFX_ERR_UNSUPPORTED: a frame must fit the LDS)")
 
-    def _inverse_call(self, entry: str, shape: T.Tuple[int, ...], rows: int, Tn: int, row_base: int, magnitude_hint: float, lstsq: bool,
-                      guide: T.Optional[torch.Tensor], hold: T.Optional[torch.Tensor], hold_bins: T.Optional[torch.Tensor], loop: bool,
-                      peak_start: bool, angles0_slots: T.Optional[torch.Tensor] = None) -> T.Tuple[T.Any, int, T.Optional[torch.Tensor]]:
+    def _inverse_call(self, entry: str, shape: T.Tuple[int, ...], rows: int, Tn: int, row_base: int, magnitude_hint: float,
+                      extras: DecodeExtras, angles0_slots: T.Optional[torch.Tensor] = None) -> T.Tuple[T.Any, int, T.Optional[torch.Tensor]]:
         """What `griffinlim`, `waveform_from_mel` and `audio_from_image` share: the combination rules and this plan's own refusals,
         the extras' tensors as the library reads them, and from them (the call's options, its workspace need in bytes, the injected
         angles as the library reads them).  `entry`: the C entry's name between rfx_ and _workspace_bytes_ex, `shape`: its query's
         arguments; `rows`: the call's Griffin-Lim rows."""
-        rules = functools.partial(check_call_rules, PLAN_WORDING, loop=loop, peak_start=peak_start, angles0_slots=angles0_slots, guide=guide, hold=hold,
-                                  hold_bins=hold_bins)
-        if loop:
+        terms = extras.starts_and_holds()
+        rules = functools.partial(check_call_rules, PLAN_WORDING, angles0_slots=angles0_slots, **terms)
+        guide, hold, hold_bins = extras.guide, extras.hold, extras.hold_bins
+        if extras.loop:
             rules("loop_holds")
             if self.griffinlim_engine == "chirp-z":
                 raise ValueError("a loop decode is not served on the chirp-z engine (RFX_ERR_UNSUPPORTED)")
             check_loop_frames(self.hop_length, self.n_fft, Tn)
-        if peak_start:
+        if extras.peak_start:
             rules("peak_start")
             self._chk_peak_bins()
         if angles0_slots is not None:
@@ -990,8 +993,8 @@ class Plan:
         if hold_bins is not None:
             rules("bins_need_guide", "bins_and_hold")
             hold_bins = self._chk_hold_bins(hold_bins, rows, Tn)
-        opt = call_options(rows=rows, row_base=row_base, magnitude_hint=magnitude_hint, lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins,
-                           loop=loop, peak_start=peak_start)
+        terms.update(guide=guide, hold=hold, hold_bins=hold_bins)  # (as the library reads them)
+        opt = call_options(rows=rows, row_base=row_base, magnitude_hint=magnitude_hint, lstsq=extras.lstsq, **terms)
         opt.keepalive = (guide, hold, hold_bins)  # (a copy `_chk_*` made lives as long as the options that point at it)
         # (0 for options the library refuses: the entry then reports its refusal itself)
         need = getattr(self.lib, f"rfx_{entry}_workspace_bytes_ex")(self.handle, *shape, ctypes.byref(opt))
@@ -1029,6 +1032,7 @@ class Plan:
         hold_bins: T.Optional[torch.Tensor] = None,
         loop: bool = False,
         peak_start: bool = False,
+        extras: T.Optional[DecodeExtras] = None,
     ) -> torch.Tensor:
         """GriffinLim on magnitudes in slot layout -> (B, samples).  `row_base`: index of the call's first row in the caller's
         whole batch (the random phases of row r are drawn from (seed, row_base + r): chunked and sharded batches get the starts
@@ -1042,14 +1046,16 @@ class Plan:
         `loop`: the Tn columns are one period of a loop (rfx_loop_call_options): circular transforms, (B, hop_length * Tn) samples whose
         end runs into their start; without `hold` / `hold_bins`, Tn at least `loop_min_frames`.
         `peak_start`: start from the spectral-peak phases of the magnitudes (rfx_start_call_options; `peak_start` below) instead of
-        random ones: no randomness, without `angles0_slots`, `guide`, `hold` or `hold_bins`."""
+        random ones: no randomness, without `angles0_slots`, `guide`, `hold` or `hold_bins`.
+        `extras`: the five as a ready `DecodeExtras` in place of the keywords (its `lstsq` is not Griffin-Lim's to read)."""
         mag_slots = self._chk(mag_slots, torch.float32)
-        opt, need, angles0_slots = self._inverse_call("griffinlim", (B, Tn), B, Tn, row_base, magnitude_hint, False, guide, hold, hold_bins, loop,
-                                                      peak_start, angles0_slots)
+        extras = DecodeExtras.fold(extras, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop, peak_start=peak_start)
+        extras = dataclasses.replace(extras, lstsq=False)  # (the library's Griffin-Lim refuses the flag)
+        opt, need, angles0_slots = self._inverse_call("griffinlim", (B, Tn), B, Tn, row_base, magnitude_hint, extras, angles0_slots)
         self._chk_slots(mag_slots, B, Tn)
         if workspace is not None:
             workspace = self._chk(workspace)
-        out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mag_slots.device)
+        out = torch.empty((B, self.output_samples(Tn, extras.loop)), dtype=torch.float32, device=mag_slots.device)
         # no (or too small a) caller-owned workspace: the plan's arena
         with (self._workspace(need) if workspace is None or workspace.numel() < need else contextlib.nullcontext(workspace)) as ws:
             check(
@@ -1560,22 +1566,24 @@ class Plan:
             f"rfx_png_decode_u8 took {N} {H} x {W} images of colour type {color_type} it reports no workspace for")
 
     def waveform_from_mel(self, mel: torch.Tensor, channels_per_clip: int, n_iter: int, momentum: float = 0.99, seed: int = 0,
-                          row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False,
-                          guide: T.Optional[torch.Tensor] = None, hold: T.Optional[torch.Tensor] = None,
-                          hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False, peak_start: bool = False) -> torch.Tensor:
+                          row_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None,
+                          hold: T.Optional[torch.Tensor] = None, hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False,
+                          peak_start: bool = False, extras: T.Optional[DecodeExtras] = None) -> torch.Tensor:
         """spectrogram_converter.py:187-204 in one call: (B, n_mels, T) -> (B, hop * (T - 1)); `inverse_mel` (seed) + `griffinlim`
         (seed + 1), same bits, the linear magnitudes stay in the workspace.  `lstsq`: `inverse_mel_lstsq` in place of the SGD.
         `guide`: (B, Lg) float32 waveforms, `hold`: (B, 2) int32 held frames, `hold_bins`: (B, T, hold_mask_words) int32 held bins, as in
         `griffinlim`; `loop`: a loop decode, (B, hop * T) samples, as in `griffinlim`; `peak_start`: Griffin-Lim starts from the
-        spectral-peak phases of the linear magnitudes (`peak_start`), as in `griffinlim`."""
-        if lstsq:
+        spectral-peak phases of the linear magnitudes (`peak_start`), as in `griffinlim`.  `extras`: the six as a ready `DecodeExtras`
+        in place of the keywords."""
+        extras = DecodeExtras.fold(extras, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop, peak_start=peak_start, lstsq=lstsq)
+        if extras.lstsq:
             self.require_lstsq()
         mel = self._chk(mel, torch.float32)
         B, M, Tn = mel.shape
         if M != self.n_mels:
             raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {M}")  # torchaudio's message
-        opt, need, _ = self._inverse_call("waveform_from_mel", (B, Tn), B, Tn, row_base, magnitude_hint, lstsq, guide, hold, hold_bins, loop, peak_start)
-        out = torch.empty((B, self.output_samples(Tn, loop)), dtype=torch.float32, device=mel.device)
+        opt, need, _ = self._inverse_call("waveform_from_mel", (B, Tn), B, Tn, row_base, magnitude_hint, extras)
+        out = torch.empty((B, self.output_samples(Tn, extras.loop)), dtype=torch.float32, device=mel.device)
         with self._workspace(need) as ws:
             check(self.lib.rfx_waveform_from_mel_ex(self.handle, mel.data_ptr(), B, Tn, channels_per_clip, seed & 0xFFFFFFFFFFFFFFFF, n_iter, momentum,
                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(), ctypes.byref(opt)))
@@ -1590,25 +1598,26 @@ class Plan:
                          normalize: bool = True, out: T.Optional[torch.Tensor] = None, workspace: T.Optional[torch.Tensor] = None,
                          clip_base: int = 0, magnitude_hint: float = 0.0, lstsq: bool = False, guide: T.Optional[torch.Tensor] = None,
                          hold: T.Optional[torch.Tensor] = None, hold_bins: T.Optional[torch.Tensor] = None, loop: bool = False,
-                         peak_start: bool = False):
+                         peak_start: bool = False, extras: T.Optional[DecodeExtras] = None):
         """spectrogram_image_converter.py:54-91 on the device in one call: (N, n_mels, T, 3) uint8 -> ((N, L, C) int16, per-clip peak (N,));
         `image_decode` + `waveform_from_mel` (clips of C rows) + `pcm16`, same bytes.  `out` as in `pcm16`.  `clip_base`: index of
         the call's first image in the caller's whole batch (row_base = clip_base * C); `magnitude_hint`: the image path's
         max_value (the largest entry of `lut`); `lstsq`: the closed-form InverseMelScale in place of the SGD; `guide`: (N * C, Lg)
         float32 waveforms, image after image and channel after channel, as in `griffinlim`; `hold`: (N * C, 2) int32 held frames, row
         for row with the guide; `hold_bins`: (N * C, T, hold_mask_words) int32 held bins, row for row as well; `loop`: a loop decode,
-        L = hop * T PCM frames per clip, as in `griffinlim`; `peak_start`: the spectral-peak start, as in `griffinlim`."""
+        L = hop * T PCM frames per clip, as in `griffinlim`; `peak_start`: the spectral-peak start, as in `griffinlim`.  `extras`: the
+        six as a ready `DecodeExtras` in place of the keywords."""
+        extras = DecodeExtras.fold(extras, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop, peak_start=peak_start, lstsq=lstsq)
         img = self._chk_tiles(img)
-        if lstsq:
+        if extras.lstsq:
             self.require_lstsq()
         lut = self._chk(lut, torch.float32)
         N, H, W, _ = img.shape
         if H != self.n_mels:
             raise ValueError(f"expected (N, {self.n_mels}, T, 3) uint8 images, got {tuple(img.shape)}")
         C = 2 if stereo else 1
-        opt, need, _ = self._inverse_call("audio_from_image", (N, int(stereo), W), N * C, W, clip_base * C, magnitude_hint, lstsq, guide, hold, hold_bins,
-                                       loop, peak_start)
-        L = self.output_samples(W, loop)
+        opt, need, _ = self._inverse_call("audio_from_image", (N, int(stereo), W), N * C, W, clip_base * C, magnitude_hint, extras)
+        L = self.output_samples(W, extras.loop)
         pcm = self._pcm_out(out, (N, L, C))
         if workspace is not None:
             workspace = self._chk(workspace)

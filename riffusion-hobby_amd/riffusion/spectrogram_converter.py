@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from riffusion import _autograd
+from riffusion._decode import ClipExtras
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import audio_util, torch_util
 
@@ -238,7 +239,7 @@ class SpectrogramConverter:
         peaks = _hip.check_phase_start(phase_start)
         amplitudes_mel = torch.from_numpy(np.ascontiguousarray(spectrogram)).to(self.device)
         plan = self._plan()
-        waveform = self._waveform_from_mel(plan, amplitudes_mel, loop=loop, peak_start=peaks)
+        waveform = self._waveform_from_mel(plan, amplitudes_mel, ClipExtras(loop=loop, peak_start=peaks))
         # peak-normalise + int16 truncation on the device (audio_util.py:22-28), one D2H of int16
         pcm, _ = plan.pcm16(waveform, channels=waveform.shape[0], normalize=True)
         host_filters = apply_filters and pcm.shape[1] * pcm.shape[2] >= audio_util.FILTER_EXACT_SAMPLES
@@ -337,9 +338,8 @@ class SpectrogramConverter:
         if (_autograd.wants_grad(amplitudes_mel) and _hip.check_inverse_mel(inverse_mel) and guide is not None and n_iter == 0 and hold is None
                 and bands is None and spec0 is None and angles0 is None):
             return self._guided_decode(amplitudes_mel, guide, seed, loop)
-        return self._waveform_from_mel(self._plan(), amplitudes_mel, spec0=spec0, angles0=angles0, seed=seed,
-                                       channels_per_clip=channels_per_clip, inverse_mel=inverse_mel, guide=guide, n_iter=griffin_lim_iters, hold=hold,
-                                       hold_bands=bands, loop=loop, peak_start=peaks)
+        clips = ClipExtras(guides=guide, holds=hold, bands=bands, loop=loop, peak_start=peaks, inverse_mel=inverse_mel, n_iter=n_iter)
+        return self._waveform_from_mel(self._plan(), amplitudes_mel, clips, spec0=spec0, angles0=angles0, seed=seed, channels_per_clip=channels_per_clip)
 
     def _guided_decode(self, amplitudes_mel: torch.Tensor, guide: torch.Tensor, seed: T.Optional[int], loop: bool) -> torch.Tensor:
         """the differentiable form of `waveform_from_mel_amplitudes`: (..., n_mels, T) mel that requires grad, (..., Lg) guide"""
@@ -363,28 +363,23 @@ class SpectrogramConverter:
         of known audio at a clip's two ends."""
         return self.p.hold_frames_for(head_s, tail_s)
 
-    def _waveform_from_mel(self, plan: T.Any, amplitudes_mel: torch.Tensor, *, spec0: T.Optional[torch.Tensor] = None,
+    def _waveform_from_mel(self, plan: T.Any, amplitudes_mel: torch.Tensor, clips: ClipExtras = ClipExtras(), *,
+                           tiles: T.Optional[T.Tuple[int, int, int]] = None, spec0: T.Optional[torch.Tensor] = None,
                            angles0: T.Optional[torch.Tensor] = None, seed: T.Optional[int] = None,
                            channels_per_clip: T.Optional[int] = None, row_base: int = 0, magnitude_hint: float = 0.0,
-                           return_slots: bool = False, inverse_mel: str = "sgd", guide: T.Optional[torch.Tensor] = None,
-                           n_iter: T.Optional[int] = None, hold: T.Optional[torch.Tensor] = None,
-                           hold_bands: T.Optional[torch.Tensor] = None, loop: bool = False, peak_start: bool = False) -> T.Any:
+                           return_slots: bool = False) -> T.Any:
         """`waveform_from_mel_amplitudes` on a plan the caller already holds (the batch entry points fetch it once per call,
         not once per chunk and stage: a fetch is a lock and a dictionary lookup, and after an eviction a rebuild).
         `return_slots=True` runs the two inverse stages separately - same bits as the one call - and returns
-        (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares.  `guide`: (B, Lg) float32 guide
-        waveforms (`waveform_from_mel_amplitudes`); `n_iter`: Griffin-Lim iterations in place of the params'; `hold`: (B, 2)
-        int32 held frames of a guided call (`hold_rows`); `hold_bands`: (B, n_mels, T) uint8 held mel bands of a masked call
-        (`hold_mask_rows`), expanded to bins on the device; `loop`: a loop decode (`waveform_from_mel_amplitudes`); `peak_start`: the
-        spectral-peak start (`phase_start="peaks"`)."""
+        (waveform, linear magnitudes in slot layout): what `Plan.spectral_error` compares.  `clips`: the call's guides, holds,
+        bands, flags and iterations, whose combination the caller has checked; `tiles=(a, b, C)`: the rows are the C channel rows
+        of its clips [a, b) (`ClipExtras.rows`), None: its entries are the rows."""
         from riffusion import _hip
 
-        _hip.check_call_rules(CALL_WORDING, "peak_start", "loop_holds", loop=loop, peak_start=peak_start, angles0=angles0, guide=guide,
-                              hold_frames=hold, hold_mask=hold_bands)
-        if loop:
+        if clips.loop:
             _hip.check_loop_frames(self.p.hop_length, self.p.n_fft, int(amplitudes_mel.shape[-1]))
 
-        lstsq = _hip.check_inverse_mel(inverse_mel)
+        lstsq = _hip.check_inverse_mel(clips.inverse_mel)
         if lstsq:
             if spec0 is not None:
                 raise ValueError('inverse_mel="lstsq" has no random start: spec0 does not go with it')
@@ -393,23 +388,17 @@ class SpectrogramConverter:
         B, _, Tn = mel.shape
         cpc = B if channels_per_clip is None else channels_per_clip
         s = self._seed(seed)
-        n_iter = self.p.num_griffin_lim_iters if n_iter is None else int(n_iter)
-        if guide is not None:
-            guide = guide.to(self.device, torch.float32)
-        if hold is not None:
-            hold = hold.to(self.device)
-        hold_bins = plan.hold_bins_from_bands(hold_bands.to(self.device)) if hold_bands is not None else None
+        n_iter = self.p.num_griffin_lim_iters if clips.n_iter is None else int(clips.n_iter)
+        extras = clips.rows(plan, tiles)
         if spec0 is None and angles0 is None and not return_slots:  # the production path: one call (rfx_waveform_from_mel), same bits as the two below
-            return plan.waveform_from_mel(mel, cpc, n_iter, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint,
-                                          lstsq=lstsq, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop, peak_start=peak_start)
+            return plan.waveform_from_mel(mel, cpc, n_iter, 0.99, seed=s, row_base=row_base, magnitude_hint=magnitude_hint, extras=extras)
         spec0 = spec0.to(self.device) if spec0 is not None else None
         if lstsq:
             lin_slots = plan.inverse_mel_lstsq(mel)
         else:
             lin_slots = plan.inverse_mel(mel, cpc, spec0=spec0, seed=s, row_base=row_base, magnitude_hint=magnitude_hint)
         a0 = plan.pack_complex(angles0.to(self.device)) if angles0 is not None else None
-        wave = plan.griffinlim(lin_slots, B, Tn, n_iter, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base,
-                               magnitude_hint=magnitude_hint, guide=guide, hold=hold, hold_bins=hold_bins, loop=loop, peak_start=peak_start)
+        wave = plan.griffinlim(lin_slots, B, Tn, n_iter, 0.99, angles0_slots=a0, seed=s + 1, row_base=row_base, magnitude_hint=magnitude_hint, extras=extras)
         return (wave, lin_slots) if return_slots else wave
 
     # ---- inverse spectrogram: complex STFT -> audio ----------------------------------------------------

@@ -18,6 +18,7 @@ import torch
 from PIL import Image
 
 from riffusion import _hip
+from riffusion._decode import ClipExtras
 from riffusion.spectrogram_converter import CALL_WORDING, SpectrogramConverter, hold_mask_rows, hold_rows
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import audio_util, image_util
@@ -26,6 +27,7 @@ from riffusion.util import audio_util, image_util
 # ... and of the batch entry points, whose guides are `guide_waveforms`
 BATCH_WORDING = {**CALL_WORDING, "hold_needs_guide": "hold_frames needs guide_waveforms: the frames are held at the guides' phase",
                  "bins_need_guide": "hold_mask needs guide_waveforms: the bins are held at the guides' phase"}
+_RANGE_MSG = "float images must be the pipeline's [0, 1] output (riffusion_pipeline.py:427-431); pass 0..255 pixel values as uint8"
 
 
 class _FileFormat(T.NamedTuple):
@@ -257,17 +259,13 @@ class SpectrogramImageConverter:
                               seed: T.Optional[int], return_device: bool, compression: bool, inverse_mel: str = "sgd") -> T.Any:
         """audio_from_spectrogram_image_sequence of tiles whose widths differ: clip i is decoded alone with the random starts of
         row i (clip_base), as it would be in one batch, filtered on the device, and the clips are stitched on the host."""
-        if compression and not apply_filters:
-            raise ValueError("compression=True is a mode of the filters: it needs apply_filters=True")
+        self._check_compression(compression, apply_filters)
         conv = self.converter
         plan = conv._plan()
         lstsq = _hip.check_inverse_mel(inverse_mel)
         if lstsq:
             plan.require_lstsq()
-        power, max_value = float(self.p.power_for_image), float(max_value)
-        if not (max_value > 0.0 and max_value < float("inf")):
-            raise ValueError(f"max_value must be a positive finite number, got {max_value}")
-        lut = plan.device_constant(("decode_lut", power, max_value), lambda: image_util.decode_lut(power, max_value))
+        lut, max_value = self._decode_lut(plan, max_value)
         base_seed = conv._seed(seed)
         segs = []
         for i, a in enumerate(arrays):
@@ -745,8 +743,7 @@ class SpectrogramImageConverter:
 
         if tiles_per_call < 1:
             raise ValueError(f"tiles_per_call must be >= 1, got {tiles_per_call}")
-        if compression and not apply_filters:
-            raise ValueError("compression=True is a mode of the filters: it needs apply_filters=True")
+        self._check_compression(compression, apply_filters)
         if return_waveform and apply_filters:
             raise ValueError("apply_filters works on int16 PCM: it does not go with return_waveform=True")
         if return_range_flag and not return_device:
@@ -757,69 +754,16 @@ class SpectrogramImageConverter:
             gather = batch_shard.default_gather(group)
         if gather not in batch_shard.GATHER_MODES:
             raise ValueError(f"gather must be one of {batch_shard.GATHER_MODES}, got {gather!r}")
+
+        # the arguments go together: what every chunk shares
         conv = self.converter
         plan = conv._plan()
         if lstsq:
             plan.require_lstsq()
-        imgs = torch.as_tensor(np.ascontiguousarray(images_u8) if isinstance(images_u8, np.ndarray) else images_u8)
-        range_msg = ("float images must be the pipeline's [0, 1] output (riffusion_pipeline.py:427-431); "
-                     "pass 0..255 pixel values as uint8")
-        range_ok = None  # device flag of a deferred range check
-        if imgs.is_floating_point():
-            if imgs.numel() and validate is not False:
-                ok = ((imgs >= 0) & (imgs <= 1.0 + 1e-6)).all()  # NaN compares false
-                if validate or not imgs.is_cuda:
-                    if not bool(ok):
-                        raise ValueError(range_msg)
-                else:
-                    range_ok = ok
-            imgs = self.quantize_pipeline_images(imgs)
+        imgs, range_ok = self._quantised(images_u8, validate)
         n_total = imgs.shape[0]
-        C = 2 if self.p.stereo else 1
-        n_iter = self.p.num_griffin_lim_iters if griffin_lim_iters is None else int(griffin_lim_iters)
-        if n_iter < 0:
-            raise ValueError(f"griffin_lim_iters must be >= 0, got {griffin_lim_iters}")
-        guides = None
-        if guide_waveforms is not None:
-            guides = torch.as_tensor(np.ascontiguousarray(guide_waveforms) if isinstance(guide_waveforms, np.ndarray) else guide_waveforms)
-            if guides.dim() != 3 or guides.shape[0] != n_total or guides.shape[1] not in (1, C) or guides.shape[2] < 1:
-                raise ValueError(f"guide_waveforms must be ({n_total}, {C} or 1, samples), got {tuple(guides.shape)}")
-            if guides.dtype not in (torch.float32, torch.int16):
-                raise ValueError(f"guide_waveforms must be float32 or int16, got {guides.dtype}")
-
-        rules("hold_needs_guide")
-        holds = hold_rows(hold_frames, n_total, int(size[0]) if size is not None else int(imgs.shape[2])) if hold_frames is not None else None
-        rules("bins_need_guide", "bins_and_hold")
-        bands = None
-        if hold_mask is not None:
-            if isinstance(hold_mask, Image.Image):
-                hold_mask = image_util.hold_mask_from_image(hold_mask)
-            bands = hold_mask_rows(hold_mask, n_total, plan.n_mels, int(size[0]) if size is not None else int(imgs.shape[2]))
-
-        def held_bins(a: int, b: int) -> T.Optional[torch.Tensor]:
-            """the held bins of tiles [a, b) as the (rows, T, words) device bit mask of the chunk's clip-channels: a clip's mask for
-            each of its channel rows"""
-            if bands is None:
-                return None
-            return plan.hold_bins_from_bands(bands[a:b].to(plan.device)).repeat_interleave(C, dim=0).contiguous()
-
-        def held_bands(a: int, b: int) -> T.Optional[torch.Tensor]:
-            return None if bands is None else bands[a:b].to(plan.device).repeat_interleave(C, dim=0).contiguous()
-
-        def held_rows(a: int, b: int) -> T.Optional[torch.Tensor]:
-            """the held frames of tiles [a, b) as the (rows, 2) int32 device tensor of the chunk's clip-channels: a clip's pair for each
-            of its channel rows"""
-            if holds is None:
-                return None
-            return holds[a:b].to(plan.device).repeat_interleave(C, dim=0).contiguous()
-
-        def guide_rows(a: int, b: int) -> T.Optional[torch.Tensor]:
-            """the guides of tiles [a, b) as the (rows, Lg) float32 device tensor of the chunk's clip-channels"""
-            if guides is None:
-                return None
-            g = guides[a:b].to(plan.device, torch.float32)
-            return g.expand(b - a, C, g.shape[2]).reshape((b - a) * C, g.shape[2])
-
+        clips = self._clip_extras(plan, rules, n_total, int(size[0]) if size is not None else int(imgs.shape[2]), guide_waveforms, hold_frames,
+                                  hold_mask, griffin_lim_iters, loop=loop, peak_start=peaks, inverse_mel=inverse_mel)
         if size is not None:
             size = (int(size[0]), int(size[1]))
         width = size[0] if size is not None else int(imgs.shape[2])
@@ -827,65 +771,122 @@ class SpectrogramImageConverter:
             _hip.check_loop_frames(plan.hop_length, plan.n_fft, width)
         L = plan.output_samples(width, loop)
         base_seed = conv._seed(seed)
-        power, max_value = float(self.p.power_for_image), float(max_value)
-        if not (max_value > 0.0 and max_value < float("inf")):
-            raise ValueError(f"max_value must be a positive finite number, got {max_value}")
-        lut = plan.device_constant(("decode_lut", power, max_value), lambda: image_util.decode_lut(power, max_value))
-        row_shape, dtype = ((C, L), torch.float32) if return_waveform else ((L, C), torch.int16)
-
+        lut, max_value = self._decode_lut(plan, max_value)
         pg = None if group is None else batch_shard._resolve_group(group)
         world = 1 if group is None else torch.distributed.get_world_size(pg)
         # a shard that takes part in a collective stays on the device until the collective has run
         collective = world > 1 and gather != "none"
 
-        error_sums: T.List[torch.Tensor] = []  # return_error: per chunk the (clips, 2) sums, a clip's channels added
-
-        def convert(lo: int, hi: int) -> torch.Tensor:
-            sink = batch_shard.ChunkSink(hi - lo, row_shape, dtype, plan.device, to_host=not (collective or return_device))
-            bounds = [(a, min(hi, a + tiles_per_call)) for a in range(lo, hi, tiles_per_call)]  # bounded working set: |S| alone is 19 MB per tile-channel
-            source = batch_shard.ChunkSource(imgs, bounds, plan.device)
-            # (the scratch space - 1.7 GB for 64 mono tiles - comes from the plan's arena: the same buffer chunk after chunk and call after call)
-            for i, (a, b) in enumerate(bounds):
-                tiles = source.get(i)
-                if size is not None:
-                    tiles = plan.resize_images(tiles, size[1], size[0], Image.BICUBIC)
-                if want_error:  # the stages one by one (same bytes as the fused calls below): the error needs both ends of Griffin-Lim
-                    mel = plan.image_decode(tiles, self.p.stereo, lut)
-                    wave, lin_slots = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C,
-                                                              magnitude_hint=max_value, return_slots=True, inverse_mel=inverse_mel,
-                                                              guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b),
-                                                              hold_bands=held_bands(a, b), loop=loop, peak_start=peaks)
-                    error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1]), loop=loop).reshape(b - a, C, 2).sum(1))
-                    if return_waveform:
-                        out = wave.reshape(b - a, C, -1)
-                    else:
-                        out = plan.pcm16(wave, C, normalize=True, out=sink.rows(a - lo, b - lo))[0]
-                        if apply_filters:
-                            out = self._filter_pcm(plan, out, compression)
-                elif return_waveform:
-                    mel = plan.image_decode(tiles, self.p.stereo, lut)
-                    wave = conv._waveform_from_mel(plan, mel, seed=base_seed, channels_per_clip=C, row_base=a * C, magnitude_hint=max_value,
-                                                   inverse_mel=inverse_mel, guide=guide_rows(a, b), n_iter=n_iter, hold=held_rows(a, b),
-                                                   hold_bands=held_bands(a, b), loop=loop, peak_start=peaks)
-                    out = wave.reshape(b - a, C, -1)
-                else:  # uint8 tiles -> int16 PCM in one call (rfx_audio_from_image_u8_ex), same bytes as the three calls above + pcm16
-                    dst = sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
-                    out = plan.audio_from_image(tiles, self.p.stereo, lut, n_iter, 0.99, seed=base_seed,
-                                                normalize=True, out=dst, clip_base=a, magnitude_hint=max_value, lstsq=lstsq,
-                                                guide=guide_rows(a, b), hold=held_rows(a, b), hold_bins=held_bins(a, b), loop=loop,
-                                                peak_start=peaks)[0]
-                    if apply_filters:
-                        out = self._filter_pcm(plan, out, compression)
-                # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them
-                source.prefetch(i + 1)
-                sink.put(a - lo, b - lo, out)
-            return sink.finish()  # a rank with an empty shard still joins the collective with 0 rows
-
+        # this rank's shard, chunk by chunk
+        error_sums: T.Optional[T.List[torch.Tensor]] = [] if want_error else None  # per chunk the (clips, 2) sums, a clip's channels added
+        convert = functools.partial(self._convert_shard, plan, imgs, clips, size=size, samples=L, lut=lut, max_value=max_value, seed=base_seed,
+                                    tiles_per_call=tiles_per_call, to_host=not (collective or return_device), return_waveform=return_waveform,
+                                    apply_filters=apply_filters, compression=compression, error_sums=error_sums)
         result = batch_shard.sharded_map(convert, n_total, group, gather)
         errors = None
         if want_error:
             sums = torch.cat(error_sums) if error_sums else torch.zeros((0, 2), dtype=torch.float64, device=plan.device)
             errors = conv.convergence_from_sums(sums[:, 0], sums[:, 1])
+        return self._deliver(plan, result, errors, range_ok, return_device, return_range_flag)
+
+    @staticmethod
+    def _check_compression(compression: bool, apply_filters: bool) -> None:
+        if compression and not apply_filters:
+            raise ValueError("compression=True is a mode of the filters: it needs apply_filters=True")
+
+    def _decode_lut(self, plan: T.Any, max_value: float) -> T.Tuple[torch.Tensor, float]:
+        """(the image path's lookup table for `max_value` on the plan's device, `max_value` as a float)"""
+        power, max_value = float(self.p.power_for_image), float(max_value)
+        if not (max_value > 0.0 and max_value < float("inf")):
+            raise ValueError(f"max_value must be a positive finite number, got {max_value}")
+        return plan.device_constant(("decode_lut", power, max_value), lambda: image_util.decode_lut(power, max_value)), max_value
+
+    def _quantised(self, images_u8: T.Any, validate: T.Optional[bool]) -> T.Tuple[torch.Tensor, T.Optional[torch.Tensor]]:
+        """`audio_from_spectrogram_images`' tiles as (the uint8 tensor, the device flag of a deferred range check or None)"""
+        imgs = torch.as_tensor(np.ascontiguousarray(images_u8) if isinstance(images_u8, np.ndarray) else images_u8)
+        range_ok = None
+        if imgs.is_floating_point():
+            if imgs.numel() and validate is not False:
+                ok = ((imgs >= 0) & (imgs <= 1.0 + 1e-6)).all()  # NaN compares false
+                if validate or not imgs.is_cuda:
+                    if not bool(ok):
+                        raise ValueError(_RANGE_MSG)
+                else:
+                    range_ok = ok
+            imgs = self.quantize_pipeline_images(imgs)
+        return imgs, range_ok
+
+    def _clip_extras(self, plan: T.Any, rules: T.Callable[..., None], n: int, width: int, guide_waveforms: T.Any, hold_frames: T.Any,
+                     hold_mask: T.Any, griffin_lim_iters: T.Optional[int], **flags: T.Any) -> ClipExtras:
+        """`audio_from_spectrogram_images`' per-clip arguments for n tiles of `width` columns as the value its chunks are lowered
+        from.  `rules`: the entry's combination rules, checked between the arguments' own checks in the entry's order."""
+        C = 2 if self.p.stereo else 1
+        n_iter = self.p.num_griffin_lim_iters if griffin_lim_iters is None else int(griffin_lim_iters)
+        if n_iter < 0:
+            raise ValueError(f"griffin_lim_iters must be >= 0, got {griffin_lim_iters}")
+        guides = None
+        if guide_waveforms is not None:
+            guides = torch.as_tensor(np.ascontiguousarray(guide_waveforms) if isinstance(guide_waveforms, np.ndarray) else guide_waveforms)
+            if guides.dim() != 3 or guides.shape[0] != n or guides.shape[1] not in (1, C) or guides.shape[2] < 1:
+                raise ValueError(f"guide_waveforms must be ({n}, {C} or 1, samples), got {tuple(guides.shape)}")
+            if guides.dtype not in (torch.float32, torch.int16):
+                raise ValueError(f"guide_waveforms must be float32 or int16, got {guides.dtype}")
+        rules("hold_needs_guide")
+        holds = hold_rows(hold_frames, n, width) if hold_frames is not None else None
+        rules("bins_need_guide", "bins_and_hold")
+        bands = None
+        if hold_mask is not None:
+            if isinstance(hold_mask, Image.Image):
+                hold_mask = image_util.hold_mask_from_image(hold_mask)
+            bands = hold_mask_rows(hold_mask, n, plan.n_mels, width)
+        return ClipExtras(guides=guides, holds=holds, bands=bands, n_iter=n_iter, **flags)
+
+    def _convert_shard(self, plan: T.Any, imgs: torch.Tensor, clips: ClipExtras, lo: int, hi: int, *, size: T.Optional[T.Tuple[int, int]],
+                       samples: int, lut: torch.Tensor, max_value: float, seed: int, tiles_per_call: int, to_host: bool, return_waveform: bool,
+                       apply_filters: bool, compression: bool, error_sums: T.Optional[T.List[torch.Tensor]]) -> torch.Tensor:
+        """Tiles [lo, hi) of `audio_from_spectrogram_images`, `tiles_per_call` at a time: the (hi - lo) clips of `samples` samples as
+        the entry delivers them.  One fused call per chunk (rfx_audio_from_image_u8_ex), or the stages one by one - same bytes -
+        where the caller wants what lies between them: the float waveform, or (`error_sums`, a list to append every chunk's
+        (clips, 2) sums to) both ends of Griffin-Lim."""
+        from riffusion import batch_shard
+
+        conv, stereo = self.converter, self.p.stereo
+        C = 2 if stereo else 1
+        staged = return_waveform or error_sums is not None
+        row_shape, dtype = ((C, samples), torch.float32) if return_waveform else ((samples, C), torch.int16)
+        sink = batch_shard.ChunkSink(hi - lo, row_shape, dtype, plan.device, to_host=to_host)
+        bounds = [(a, min(hi, a + tiles_per_call)) for a in range(lo, hi, tiles_per_call)]  # bounded working set: |S| alone is 19 MB per tile-channel
+        source = batch_shard.ChunkSource(imgs, bounds, plan.device)
+        # (the scratch space - 1.7 GB for 64 mono tiles - comes from the plan's arena: the same buffer chunk after chunk and call after call)
+        for i, (a, b) in enumerate(bounds):
+            tiles = source.get(i)
+            if size is not None:
+                tiles = plan.resize_images(tiles, size[1], size[0], Image.BICUBIC)
+            dst = None if return_waveform else sink.rows(a - lo, b - lo)  # device sink: the PCM kernel writes the batch rows in place
+            if staged:
+                mel = plan.image_decode(tiles, stereo, lut)
+                wave = conv._waveform_from_mel(plan, mel, clips, tiles=(a, b, C), seed=seed, channels_per_clip=C, row_base=a * C,
+                                               magnitude_hint=max_value, return_slots=error_sums is not None)
+                if error_sums is not None:
+                    wave, lin_slots = wave
+                    error_sums.append(plan.spectral_error(wave, lin_slots, (b - a) * C, int(mel.shape[-1]), loop=clips.loop).reshape(b - a, C, 2).sum(1))
+                out = wave.reshape(b - a, C, -1) if return_waveform else plan.pcm16(wave, C, normalize=True, out=dst)[0]
+            else:
+                out = plan.audio_from_image(tiles, stereo, lut, clips.n_iter, 0.99, seed=seed, normalize=True, out=dst, clip_base=a,
+                                            magnitude_hint=max_value, extras=clips.rows(plan, (a, b, C), bins_first=True))[0]
+            if apply_filters:  # (never with `return_waveform`)
+                out = self._filter_pcm(plan, out, compression)
+            # this chunk's kernels are queued: the host stages and uploads the next chunk underneath them
+            source.prefetch(i + 1)
+            sink.put(a - lo, b - lo, out)
+        return sink.finish()  # a rank with an empty shard still joins the collective with 0 rows
+
+    @staticmethod
+    def _deliver(plan: T.Any, result: torch.Tensor, errors: T.Optional[torch.Tensor], range_ok: T.Optional[torch.Tensor], return_device: bool,
+                 return_range_flag: bool) -> T.Any:
+        """What `audio_from_spectrogram_images` returns of a rank's `result`, its clips' `errors` (None: not asked for) and the
+        deferred range check's flag (None: nothing deferred)."""
+        want_error = errors is not None
         if return_device:
             if range_ok is not None:
                 # nothing on this path ever synchronises, so the deferred check cannot raise here: out-of-range (or NaN) input
@@ -905,5 +906,5 @@ class SpectrogramImageConverter:
             torch.cuda.current_stream(plan.device).synchronize()
             result = host
         if range_ok is not None and not bool(range_ok):  # the stream has been synchronised above / by the sink: no extra wait
-            raise ValueError(range_msg)
+            raise ValueError(_RANGE_MSG)
         return (result.numpy(), errors.cpu().numpy()) if want_error else result.numpy()

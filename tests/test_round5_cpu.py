@@ -119,7 +119,7 @@ def test_chunk_source_prefetch_is_optional_and_idempotent():
     from riffusion.spectrogram_converter import SpectrogramConverter
     from riffusion.spectrogram_image_converter import SpectrogramImageConverter
 
-    body = inspect.getsource(SpectrogramImageConverter.audio_from_spectrogram_images)
+    body = inspect.getsource(SpectrogramImageConverter._convert_shard)  # the batch entry's chunk loop
     assert body.index("conv._waveform_from_mel(plan") < body.index("source.prefetch(i + 1)") < body.index("sink.put(")
     assert "self._plan()" not in inspect.getsource(SpectrogramConverter._waveform_from_mel)
 
