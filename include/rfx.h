@@ -818,6 +818,41 @@ size_t rfx_debug_istft_backward_padded_workspace_bytes(const rfx_plan* plan, int
 int rfx_debug_istft_backward_padded(const rfx_plan* plan, const float* d_grad_wave, int B, int T, void* d_grad_spec_slots,
                                     void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- TIME STRETCH: the phase vocoder between rfx_stft and rfx_istft (torchaudio.transforms.TimeStretch) ----------------------------------
+ * rfx_phase_vocoder is torchaudio.functional.phase_vocoder(X, rate, phase_advance = linspace(0, pi hop_length, n_stft)) on a complex
+ * spectrogram in slot layout (what rfx_pack_complex and rfx_stft write): B * T frames in, B * T_out frames out, the same layout - both
+ * slots of a doubled bin filled with one trajectory, conjugate slots conjugated, padding 0 - so the result goes to rfx_istft as it is.
+ *   T_out   = ceil(T / rate) evaluated in double, the length of torch.arange(0, T, rate): rfx_phase_vocoder_frames (host only).
+ *   step i  reads frames i0 = floor(i rate) and i0 + 1, i rate formed in double, alpha = (float)(i rate - i0); frames at or past T are 0.
+ *   output  magnitude alpha |X[i0 + 1]| + (1 - alpha) |X[i0]|; phase angle(X[0]) at step 0, then the running sum of
+ *           wrap(angle(X[i0 + 1]) - angle(X[i0]) - adv_k) + adv_k.
+ * PHASES ARE TURNS: adv_k = (hop k mod D) / D with D = 2 (n_stft - 1) in integers, the accumulator wrapped to [-1/2, 1/2] after every
+ * step, sine and cosine taken of the wrapped turns.  Float32 torch sums the absolute phase - up to pi hop radians per frame - and loses
+ * about a bit per doubling of T; this form does not (tests/test_vocoder_cpu.py holds it ABOVE float32 torch at T = 512).
+ * rate == 1.0 copies the input bit for bit, as torchaudio returns it.  One rate per call.  No gradient and no loop form: the
+ * accumulated phase does not close over a period.
+ * One kernel, one thread per slot position, rows on the grid's second axis, a serial walk over the T_out frames (rfx_vocoder.hip).
+ * rfx_time_stretch is, per group of rows, exactly rfx_stft -> rfx_phase_vocoder -> rfx_istft: d_wave (B, Lw) float32 -> d_wave_out
+ * (B, rfx_time_stretch_samples(plan, Lw, rate)) float32, hop (T_out - 1) (+ n_fft % 2) samples per row with T = rfx_stft_frames(plan, Lw)
+ * - the same bytes as the three calls on all rows at once.  BOUNDED WORKSPACE: groups of max(1, 256 MiB / bytes of a row's two
+ * spectrograms) whole rows (at most 65535), plus what rfx_istft asks for a group.
+ * Contract: B == 0 is a no-op.  RFX_ERR_INVALID with a message, before any launch, the outputs untouched: a NULL pointer; a rate that
+ * is not finite or not positive; T < 1; a frame count past 2^31 - 1; slots off 8-byte alignment or d_out_slots == d_spec_slots; for
+ * rfx_time_stretch what rfx_stft refuses for Lw (Lw <= n_fft / 2) and rfx_istft for T_out (no sample), a workspace off 16-byte or a
+ * waveform off 4-byte alignment.  RFX_ERR_WORKSPACE: a workspace below the query.  A query answers 0 where the call would be refused. */
+int rfx_phase_vocoder_frames(int T, double rate, int* T_out);
+int rfx_phase_vocoder(const rfx_plan* plan, const void* d_spec_slots, int B, int T, double rate, void* d_out_slots, void* stream);
+size_t rfx_time_stretch_workspace_bytes(const rfx_plan* plan, int B, int Lw, double rate);
+int rfx_time_stretch_samples(const rfx_plan* plan, int Lw, double rate);
+int rfx_time_stretch(const rfx_plan* plan, const float* d_wave, int B, int Lw, double rate, float* d_wave_out, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
+/* The kernel's position table, without a plan or a GPU (tests; options NULL = defaults): per position of a frame of complex slots
+ * h_bin the bin it holds (-1: padding), h_src the PRIMARY position of that bin - the one rfx_unpack_complex reads; -1: padding -,
+ * h_advance the bin's advance in turns, frac(hop k / D), negated where the position holds the conjugate, h_conj 1 where it does.
+ * *stride_out: positions per frame; the arrays are optional and need capacity >= *stride_out. */
+int rfx_debug_vocoder_table(const rfx_params* params, const rfx_plan_options* options, int32_t* h_bin, int32_t* h_src, float* h_advance,
+                            uint8_t* h_conj, int capacity, int32_t* stride_out);
+
 /* ---- inverse: torchaudio.transforms.InverseMelScale (SGD, max_iter = params.max_mel_iters,
  * tolerance_loss 1e-5, tolerance_change 1e-8, lr 0.1, momentum 0.9), spectrogram_converter.py:87-99,
  * called at :201.  d_mel (B, n_mels, T); the B rows are grouped into clips of `channels_per_clip`

@@ -128,6 +128,7 @@ struct rfx_plan {
   int* d_mb_pos_bin = nullptr;   // [mb_sstride]
   int* d_mb_xpos_bin = nullptr;  // [frame_stride]
   int* d_mb_s2x = nullptr;       // [mb_sstride] position of the spectrum each magnitude slot goes with
+  int2* d_voc_table = nullptr;   // [frame_stride] the time stretch's position table (rfx_plan_core.h: VocoderTable::device)
   int mb_sstride = 0;
   int* d_mb_first = nullptr;     // [n_stft]
   int* d_mb_count = nullptr;     // [n_stft]
@@ -186,6 +187,9 @@ inline int group_rows(size_t bytes, size_t row_bytes, int B, size_t cap = (size_
   rows = rows < 1 ? 1 : rows > cap ? cap : rows;
   return (int)(rows > (size_t)B ? (size_t)B : rows);
 }
+// the cap of the grouped drivers that hold whole spectrogram rows in their workspace (rfx_api_istft.hip, rfx_api_vocoder.hip)
+constexpr size_t kIstftGroupBytes = (size_t)256 << 20;
+constexpr size_t kIstftGroupRows = 65535;  // the folds carry the row in blockIdx.y
 struct Carve {
   size_t at = 0;
   size_t take(size_t bytes) {

@@ -20,9 +20,6 @@
 
 using namespace rfx;
 
-constexpr size_t kIstftGroupBytes = (size_t)256 << 20;
-constexpr size_t kIstftGroupRows = 65535;  // the folds carry the row in blockIdx.y
-
 static bool istft_specialised(const rfx_plan* plan) { return !plan->generic; }
 // samples per row of T frames; 0: the form does not serve T
 static int istft_samples(const rfx_plan* plan, int T, bool loop) {

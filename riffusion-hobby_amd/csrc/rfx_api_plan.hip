@@ -198,6 +198,7 @@ int rfx_plan_create_ex(const rfx_params* params, const float* h_window, const fl
     RFX_HIP(upload(pl.get(), &pl->d_mb_pos_bin, mb.pos_bin));
     RFX_HIP(upload(pl.get(), &pl->d_mb_xpos_bin, mb.xpos_bin));
     RFX_HIP(upload(pl.get(), &pl->d_mb_s2x, mb.s2x));
+    RFX_HIP(upload(pl.get(), &pl->d_voc_table, vocoder_table(geo, params->hop_length).device()));
   }
   if (h_melfb) {
     const int F = geo.n_stft, M = params->n_mels;
@@ -381,6 +382,28 @@ int rfx_debug_guide_project_tables(const rfx_params* params, int32_t* h_xpos_bin
       return fail(RFX_ERR_INVALID, "rfx_debug_guide_project_tables: a frame has " + std::to_string(n) + " positions, capacity is " + std::to_string(capacity));
     if (h_xpos_bin) memcpy(h_xpos_bin, mb.xpos_bin.data(), (size_t)n * sizeof(int32_t));
     if (h_s2x) memcpy(h_s2x, s2x.data(), (size_t)n * sizeof(int32_t));
+  }
+  return RFX_OK;
+}
+
+int rfx_debug_vocoder_table(const rfx_params* params, const rfx_plan_options* options, int32_t* h_bin, int32_t* h_src, float* h_advance,
+                            uint8_t* h_conj, int capacity, int32_t* stride_out) {
+  if (!params || !stride_out) return fail(RFX_ERR_INVALID, "rfx_debug_vocoder_table: null argument");
+  rfx_plan_options opt;
+  if (const int rc = resolve_options(options, &opt)) return rc;
+  PlanGeometry geo;
+  std::string err;
+  if (const int rc = plan_geometry(*params, opt, plan_overrides(), &geo, &err)) return fail(rc, err);
+  const VocoderTable t = vocoder_table(geo, params->hop_length);  // what plan creation uploads
+  const int n = (int)t.src.size();
+  *stride_out = n;
+  if (h_bin || h_src || h_advance || h_conj) {
+    if (capacity < n)
+      return fail(RFX_ERR_INVALID, "rfx_debug_vocoder_table: a frame has " + std::to_string(n) + " positions, capacity is " + std::to_string(capacity));
+    if (h_bin) memcpy(h_bin, t.bin.data(), (size_t)n * sizeof(int32_t));
+    if (h_src) memcpy(h_src, t.src.data(), (size_t)n * sizeof(int32_t));
+    if (h_advance) memcpy(h_advance, t.adv.data(), (size_t)n * sizeof(float));
+    if (h_conj) memcpy(h_conj, t.conj.data(), (size_t)n);
   }
   return RFX_OK;
 }

@@ -700,4 +700,16 @@ struct IstftGradArgs {
 };
 hipError_t launch_istft_grad(const IstftGradArgs& a, hipStream_t stream);
 
+// time stretch (rfx_vocoder.hip, arithmetic in rfx_vocoder_core.h): in [rows*T][stride] -> out [rows*T_out][stride], complex slots;
+// table [stride]: per position the primary position of its bin (| kVocFlip; -1: padding) and the bits of its signed advance in turns
+// (rfx_plan_core.h: vocoder_table).  in and out 8-byte aligned and distinct; any number of rows.
+struct VocoderArgs {
+  const cf* in;
+  cf* out;
+  const int2* table;
+  int rows, T, T_out, stride;
+  double rate;
+};
+hipError_t launch_vocoder(const VocoderArgs& a, hipStream_t stream);
+
 }  // namespace rfx

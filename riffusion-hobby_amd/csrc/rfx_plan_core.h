@@ -14,6 +14,7 @@
 #include "rfx_czt_core.h"
 #include "rfx_kernels.h"
 #include "rfx_mel_bwd_core.h"
+#include "rfx_vocoder_core.h"
 
 namespace rfx {
 
@@ -762,6 +763,51 @@ inline MelBwdTables mel_bwd_tables(const PlanGeometry& g) {
     t.pos_bin = t.xpos_bin;
   }
   t.s2x = t.pos_bin;  // plain spectrum: position = bin (the row family's launch reads its angles by bin)
+  return t;
+}
+
+// ---- time stretch (rfx_vocoder.hip): the per-position table of the complex slots, beside MelBwdTables::xpos_bin ---------------------------
+// For every position of a frame as rfx_pack_complex lays it out: the bin it holds (-1: padding - the marker), whether it holds the
+// bin's conjugate, the PRIMARY position of that bin - the one rfx_unpack_complex reads, so that both slots of a doubled bin are
+// computed from the same input and leave as one trajectory - and the bin's advance in turns, frac(hop k / D) with D = 2 (n_stft - 1),
+// negated where the position holds the conjugate.  Specialised engine: slot_pos_c order, 440 bins twice; every other engine (row
+// family, generic, chirp-z): plain frames, position = bin, no conjugates.
+struct VocoderTable {
+  std::vector<int> bin, src;        // [frame_stride]; src -1 for padding
+  std::vector<float> adv;           // [frame_stride]
+  std::vector<unsigned char> conj;  // [frame_stride]
+  // the entries the kernel reads (rfx_vocoder_core.h: kVocFlip)
+  std::vector<int2> device() const {
+    std::vector<int2> t(src.size());
+    for (size_t p = 0; p < src.size(); ++p) {
+      int32_t bits;
+      memcpy(&bits, &adv[p], sizeof(bits));
+      t[p] = int2{src[p] < 0 ? -1 : src[p] | (conj[p] != conj[(size_t)src[p]] ? kVocFlip : 0), bits};
+    }
+    return t;
+  }
+};
+inline VocoderTable vocoder_table(const PlanGeometry& g, int hop) {
+  VocoderTable t;
+  t.bin = g.generic ? mel_bwd_pos_bin_plain(g.n_stft, g.frame_stride) : mel_bwd_xpos_bin_spec();
+  const size_t P = t.bin.size();
+  t.src.assign(P, -1);
+  t.adv.assign(P, 0.f);
+  t.conj.assign(P, 0);
+  if (!g.generic)
+    for (int q = 0; q < 441; ++q)
+      for (int kb = 0; kb < 21; ++kb) {
+        bool cj;
+        slot_bin(q / 21, q % 21, kb, &cj);
+        t.conj[(size_t)slot_pos_c(q, kb)] = cj;
+      }
+  for (size_t p = 0; p < P; ++p) {
+    const int k = t.bin[p];
+    if (k < 0) continue;
+    t.src[p] = g.generic ? k : voc_spec_primary(k, nullptr);
+    const float a = voc_advance_turns(hop, k, g.n_stft);
+    t.adv[p] = t.conj[p] ? -a : a;
+  }
   return t;
 }
 

@@ -337,6 +337,39 @@ OPT_IN_FRAME_ENGINES = {"chirp-z": 2}
 GL_ENGINE_NAMES = {0: "specialised", 1: "generic", 2: "row-family", 3: "chirp-z"}  # rfx_plan_griffinlim_engine
 
 
+def check_stretch_rate(rate: T.Any) -> float:
+    """the rate of a time stretch as the library takes it: a finite positive number (one rate per call)"""
+    import numbers
+
+    if isinstance(rate, bool) or not isinstance(rate, numbers.Real):
+        raise ValueError(f"rate must be one real number (one rate per call), got {type(rate).__name__}")
+    rate = float(rate)
+    if not (rate > 0.0) or rate == float("inf"):
+        raise ValueError(f"rate must be finite and positive, got {rate}")
+    return rate
+
+
+def phase_vocoder_frames(Tn: int, rate: float) -> int:
+    """rfx_phase_vocoder_frames (host only, no GPU): ceil(Tn / rate) in double, the length of torch.arange(0, Tn, rate)"""
+    n = c_int(0)
+    check(load_library().rfx_phase_vocoder_frames(int(Tn), float(rate), ctypes.byref(n)))
+    return n.value
+
+
+def vocoder_table(cp: RfxParams, frame_engine: str = "auto") -> T.Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """rfx_debug_vocoder_table (host only, no GPU): (bin, src, advance, conj) per position of a frame of complex slots - the bin it
+    holds (-1: padding), the primary position of that bin (-1: padding), the bin's signed advance in turns, and whether the position
+    holds the conjugate."""
+    lib, n = load_library(), ctypes.c_int32(0)
+    opt = RfxPlanOptions(ctypes.sizeof(RfxPlanOptions), 0, 0, {**FRAME_ENGINES, **OPT_IN_FRAME_ENGINES}[frame_engine], 0, 0)
+    check(lib.rfx_debug_vocoder_table(ctypes.byref(cp), ctypes.byref(opt), None, None, None, None, 0, ctypes.byref(n)))
+    bins, src = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+    adv, conj = np.zeros(n.value, np.float32), np.zeros(n.value, np.uint8)
+    check(lib.rfx_debug_vocoder_table(ctypes.byref(cp), ctypes.byref(opt), bins.ctypes.data, src.ctypes.data, adv.ctypes.data, conj.ctypes.data,
+                                      n.value, ctypes.byref(n)))
+    return bins, src, adv, conj
+
+
 class RfxError(RuntimeError):
     pass
 
@@ -432,6 +465,14 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_istft_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_debug_istft_backward_padded_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_debug_istft_backward_padded": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # time stretch: the phase vocoder between rfx_stft and rfx_istft
+    "rfx_phase_vocoder_frames": (c_int, [c_int, ctypes.c_double, ctypes.POINTER(c_int)]),
+    "rfx_phase_vocoder": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
+    "rfx_time_stretch_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, ctypes.c_double]),
+    "rfx_time_stretch_samples": (c_int, [c_void_p, c_int, ctypes.c_double]),
+    "rfx_time_stretch": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rfx_debug_vocoder_table": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                        ctypes.POINTER(ctypes.c_int32)]),
     # fused spectral losses (riffusion/_autograd.py: SpectralLossFunction)
     "rfx_spectral_loss_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1217,6 +1258,44 @@ class Plan:
         if B:
             with self._workspace(query(self.handle, B, Tn)) as ws:
                 check(entry(self.handle, g.data_ptr(), B, Tn, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    # ---- time stretch (include/rfx.h "TIME STRETCH") ----
+    def phase_vocoder(self, spec_slots: torch.Tensor, B: int, Tn: int, rate: float) -> T.Tuple[torch.Tensor, int]:
+        """rfx_phase_vocoder: a complex spectrogram in slot layout, B * Tn frames (`pack_complex`, or what `stft` returns) -> the
+        stretched one in the same layout and its frames per row, ceil(Tn / rate): torchaudio.functional.phase_vocoder with
+        TimeStretch's phase advance.  rate == 1 gives a copy."""
+        rate = check_stretch_rate(rate)
+        x = self._chk(spec_slots, torch.complex64)
+        if B < 0 or Tn < 1:
+            raise ValueError(f"expected B >= 0 rows of Tn >= 1 frames, got B = {B}, Tn = {Tn}")
+        if x.numel() != B * Tn * self.frame_stride:
+            raise ValueError(f"expected {B} * {Tn} frames of {self.frame_stride} complex slots, got {tuple(x.shape)}")
+        Tout = phase_vocoder_frames(Tn, rate)
+        out = torch.empty((B * Tout, self.frame_stride), dtype=torch.complex64, device=self.device)
+        if B:
+            check(self.lib.rfx_phase_vocoder(self.handle, x.data_ptr(), B, Tn, rate, out.data_ptr(), self._stream()))
+        return out, Tout
+
+    def time_stretch_samples(self, Lw: int, rate: float) -> int:
+        """samples per row `time_stretch` makes of rows of Lw samples, or the call's refusal before any device work"""
+        rate = check_stretch_rate(rate)
+        Tout = phase_vocoder_frames(self._forward_frames(Lw, (Lw,), False), rate)
+        return self._istft_samples(1, Tout, False)
+
+    def time_stretch(self, wave: torch.Tensor, rate: float) -> torch.Tensor:
+        """rfx_time_stretch: (B, Lw) float32 -> (B, hop * (T_out - 1) (+ n_fft % 2)) float32, exactly `istft(phase_vocoder(stft(wave)))`
+        on bounded groups of rows."""
+        rate = check_stretch_rate(rate)
+        wave = self._chk(wave, torch.float32)
+        if wave.dim() != 2:
+            raise ValueError(f"expected a (B, Lw) waveform, got {tuple(wave.shape)}")
+        B, Lw = wave.shape
+        L = self.time_stretch_samples(Lw, rate)
+        out = torch.empty((B, L), dtype=torch.float32, device=self.device)
+        if B:
+            with self._workspace(self.lib.rfx_time_stretch_workspace_bytes(self.handle, B, Lw, rate)) as ws:
+                check(self.lib.rfx_time_stretch(self.handle, wave.data_ptr(), B, Lw, rate, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         return out
 
     # ---- fused spectral losses (include/rfx.h "FUSED SPECTRAL LOSSES"; riffusion/_autograd.py: SpectralLossFunction) ----

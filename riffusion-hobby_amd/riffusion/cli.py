@@ -15,6 +15,7 @@ installed here); without pydub only 16-bit PCM wav files are read and only wav i
     python -m riffusion.cli print-exif --image tile.png
     python -m riffusion.cli images-to-audio-batch --image-dir tiles/ --output-dir wavs/
     python -m riffusion.cli audio-to-images-batch --audio-dir wavs/ --output-dir tiles/
+    python -m riffusion.cli time-stretch --audio clip.wav --output slower.wav --bpm-from 120 --bpm-to 100
 """
 import argparse
 import glob
@@ -403,12 +404,51 @@ def audio_to_images_batch(*, audio_dir: str, output_dir: str, image_extension: s
         flush(n_samples)
 
 
+def _stretch_rate(*, rate: float, bpm_from: float, bpm_to: float, **_: T.Any) -> float:
+    """the rate of time-stretch from its flags: --rate R, or --bpm-from A --bpm-to B (rate B / A); ValueError for flags that do not
+    go together (the function raises it, the parser reports it)"""
+    by_bpm = bool(bpm_from) or bool(bpm_to)
+    if bool(rate) == by_bpm:
+        raise ValueError("time-stretch takes either --rate R or --bpm-from A --bpm-to B")
+    if by_bpm:
+        if not (bpm_from > 0 and bpm_to > 0) or bpm_from == float("inf") or bpm_to == float("inf"):
+            raise ValueError("--bpm-from and --bpm-to must both be given, finite and positive")
+        return bpm_to / bpm_from
+    if not rate > 0 or rate == float("inf"):
+        raise ValueError("--rate must be finite and positive")
+    return rate
+
+
+def time_stretch(*, audio: str, output: str, rate: float = 0.0, bpm_from: float = 0.0, bpm_to: float = 0.0, device: str = "cuda",
+                 frame_engine: str = "auto") -> None:
+    """Play a clip faster or slower at the same pitch: the phase vocoder between the STFT and its inverse, on the device.
+    --rate R: R times as fast (1.25: a fifth shorter; 0.8: a quarter longer), or --bpm-from A --bpm-to B: a clip at A beats per
+    minute comes out at B (rate B / A).  The clip's channels are rows of one call; the result is peak-normalised into 16-bit PCM as a
+    decode's is.  The analysis runs at the clip's sample rate with the default window, hop and padding.  One rate for the whole clip;
+    a loop does not stay a loop (the accumulated phase does not close at the loop point)."""
+    import torch
+
+    from riffusion.spectrogram_converter import SpectrogramConverter
+
+    r = _stretch_rate(rate=rate, bpm_from=bpm_from, bpm_to=bpm_to)
+    segment = _load_segment(audio)
+    waveform = np.array([c.get_array_of_samples() for c in segment.split_to_mono()]).astype(np.float32)
+    params = SpectrogramParams(sample_rate=int(segment.frame_rate), stereo=waveform.shape[0] == 2)
+    converter = SpectrogramConverter(params=params, device=device, frame_engine=frame_engine)
+    stretched = converter.time_stretch(torch.from_numpy(waveform), r)
+    pcm, _ = converter._plan().pcm16(stretched, channels=stretched.shape[0], normalize=True)
+    out = audio_util.segment_from_pcm16(pcm[0].cpu().numpy(), params.sample_rate)
+    out.export(output, format=os.path.splitext(output)[1][1:] or "wav")
+    print(f"Wrote {output} ({out.duration_seconds:.2f} seconds, rate {r:.4f})")
+
+
 _COMMANDS: T.Dict[str, T.Callable[..., None]] = {
     "audio-to-image": audio_to_image,
     "image-to-audio": image_to_audio,
     "print-exif": print_exif,
     "images-to-audio-batch": images_to_audio_batch,
     "audio-to-images-batch": audio_to_images_batch,
+    "time-stretch": time_stretch,
 }
 
 
@@ -448,6 +488,11 @@ def main(argv: T.Optional[T.Sequence[str]] = None) -> None:
     if command in ("audio-to-image", "audio-to-images-batch"):
         try:
             _check_png_flags(args["png_writer"], args["png_mode"])
+        except ValueError as e:
+            parser.error(str(e))
+    if command == "time-stretch":
+        try:
+            _stretch_rate(**args)
         except ValueError as e:
             parser.error(str(e))
     if command == "images-to-audio-batch" and args["griffin_lim_iters"] < -1:

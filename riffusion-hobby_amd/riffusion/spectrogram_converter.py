@@ -438,6 +438,65 @@ class SpectrogramConverter:
             wave = wave[:, : int(length)] if int(length) <= L else torch.nn.functional.pad(wave, (0, int(length) - L))
         return wave.reshape(*lead, wave.shape[-1])
 
+    # ---- time stretch: the phase vocoder between the STFT and its inverse ------------------------------------
+    def _check_stretch(self, what: str, x: T.Any, rate: T.Any) -> float:
+        """the checks the two time-stretch members share, all before the plan is used: one finite positive rate, and no gradient"""
+        from riffusion import _hip
+
+        rate = _hip.check_stretch_rate(rate)
+        if isinstance(x, torch.Tensor) and _autograd.wants_grad(x):
+            raise RuntimeError(f"{what}: the time stretch has no backward; detach the input, or run under torch.no_grad()")
+        return rate
+
+    def time_stretch_spectrogram(self, spec: torch.Tensor, rate: float) -> torch.Tensor:
+        """
+        (..., n_stft, T) complex64 -> (..., n_stft, ceil(T / rate)) complex64: what
+        torchaudio.transforms.TimeStretch(hop_length, n_freq=n_stft)(spec, rate) returns - torchaudio.functional.phase_vocoder on the
+        device (rfx_phase_vocoder).  rate > 1 is faster and shorter, rate < 1 slower and longer; rate == 1 returns the input's
+        values.  Phases are carried as wrapped turns with each bin's advance an exact fraction, so the result does not lose accuracy
+        with T the way the float32 sum of absolute phase does.  One rate per call.  No gradient: a `spec` that requires grad while
+        grad mode is on raises before any device work.  No loop form: the accumulated phase does not close over a period.
+        """
+        rate = self._check_stretch("time_stretch_spectrogram", spec, rate)
+        if not isinstance(spec, torch.Tensor) or not spec.is_complex():
+            raise ValueError("time_stretch_spectrogram takes a complex (..., n_stft, T) spectrogram")
+        if spec.dim() < 2:
+            raise ValueError(f"time_stretch_spectrogram takes (..., n_stft, T), got {tuple(spec.shape)}")
+        n_stft = self.p.n_fft // 2 + 1
+        if int(spec.shape[-2]) != n_stft:
+            raise ValueError(f"expected {n_stft} linear bins, got {int(spec.shape[-2])}")
+        if int(spec.shape[-1]) < 1:
+            raise ValueError("time_stretch_spectrogram: no frames")
+        plan = self._plan()
+        lead = spec.shape[:-2]
+        x = spec.detach().reshape(-1, spec.shape[-2], spec.shape[-1]).to(self.device).to(torch.complex64)
+        B, _, Tn = x.shape
+        out, Tout = plan.phase_vocoder(plan.pack_complex(x), B, Tn, rate)
+        return plan.unpack_complex(out, B, Tout).reshape(*lead, n_stft, Tout)
+
+    def time_stretch(self, waveform: torch.Tensor, rate: float, length: T.Optional[int] = None) -> torch.Tensor:
+        """
+        (..., samples) float32 -> (..., L) float32, the clip played `rate` times as fast at the same pitch: `spectrogram_func`, the
+        phase vocoder and `waveform_from_spectrogram` in one call on the device (rfx_time_stretch), without the two layout passes the
+        composition pays.  L = hop * (T_out - 1) (+ 1 for an odd n_fft) with T_out = ceil(T / rate) of the clip's T frames; `length`
+        cuts the result or pads it with zeros at its end, as `waveform_from_spectrogram` does.  To match a clip generated at one
+        tempo to another: rate = bpm_to / bpm_from.  One rate per call, no gradient, no loop form (see `time_stretch_spectrogram`):
+        a stretched loop does not close at its loop point.
+        """
+        rate = self._check_stretch("time_stretch", waveform, rate)
+        if not isinstance(waveform, torch.Tensor) or waveform.is_complex() or waveform.dim() < 1:
+            raise ValueError("time_stretch takes a real (..., samples) waveform")
+        if length is not None and (int(length) != length or int(length) < 0):
+            raise ValueError(f"length must be a non-negative integer, got {length!r}")
+        plan = self._plan()
+        lead = waveform.shape[:-1]
+        w = waveform.detach().reshape(-1, waveform.shape[-1]).to(self.device).to(torch.float32)
+        wave = plan.time_stretch(w, rate)
+        if length is not None:
+            L = int(wave.shape[-1])
+            wave = wave[:, : int(length)] if int(length) <= L else torch.nn.functional.pad(wave, (0, int(length) - L))
+        return wave.reshape(*lead, wave.shape[-1])
+
     # ---- quality of a decode ------------------------------------------------------------------------
     @staticmethod
     def convergence_from_sums(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:

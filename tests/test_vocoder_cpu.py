@@ -1,0 +1,317 @@
+"""
+CPU checks of the time stretch (include/rfx.h, "TIME STRETCH"; csrc/rfx_vocoder_core.h, rfx_plan_core.h: vocoder_table).
+
+* tests/emu/rfx_vocoder_emu.cpp runs the core's own walk on the host, in float32 as the kernel does (its final sine and cosine in
+  double, rounded once: the host has no sincospif).  PARITY: every figure is an SNR against the float64 oracle (tests/vocoder_oracle.py, a
+  transcription of torchaudio.functional.phase_vocoder): `emu` the emulator's, `o32` the float32 oracle's on the same input; both printed.
+  X is seeded complex64 noise over the oracle STFT of helpers.synthetic_wave (tests/test_gpu_istft.py builds it so), the last row all
+  zero; T = 2 takes the first two frames of the T = 41 spectrogram (two frames' worth of samples are too few for torch.stft's reflect
+  padding).  Rates 1.25, 0.75, 1.1, 0.9; geometry: the four parameter sets of tests/test_gpu_loop_decode.py.
+    T = 41, T = 2            emu >= o32 - 6 dB    the project's rule (tests/test_gpu_held_frames.py)
+    T = 512, defaults, B = 1 emu >= o32           no allowance: phases as wrapped turns are the point of the formulation
+* Exact properties: the zero row leaves as zeros; rate = 1 returns the input's bits; a row alone gives the bits it gives in the batch;
+  rfx_phase_vocoder_frames is len(torch.arange(0, T, rate, dtype=float64)).
+* The position table, per engine, through rfx_debug_vocoder_table: one primary position per bin; every position points at the
+  primary of its own bin; every advance is +-frac(hop k / D) to one float32 rounding, the sign the conjugate flag's.  And the slot walk
+  of the emulator on that table: the result, read back bin by bin from the primary slots, equals the bin-order result, both
+  slots of a doubled bin agree, padding is zero.
+* Refusals of the entries without a device; include/rfx.h as C99; the requires_grad refusal; the command line's argument checks.
+* The emulator and a `main` of its own are also built as a stand-alone program with -fsanitize=address,undefined and run; nothing
+  sanitized is loaded into Python.
+"""
+import ctypes
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import istft_oracle as IO
+import vocoder_oracle as VO
+from helpers import snr_db, synthetic_wave
+from test_gpu_loop_decode import ENGINES
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_vocoder_emu.cpp")
+EMU_MAIN = os.path.join(ROOT, "tests", "emu", "rfx_vocoder_emu_main.cpp")
+RATES = [1.25, 0.75, 1.1, 0.9]
+_CASES = {}
+
+
+@pytest.fixture(scope="module")
+def O():
+    import riffusion_oracle
+
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    return riffusion_oracle
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("vocoder_emu") / "librfx_vocoder_emu.so")
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
+    lib = ctypes.CDLL(so)
+    vp, i, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+    lib.emu_voc_frames.argtypes, lib.emu_voc_frames.restype = [i, d], ctypes.c_longlong
+    lib.emu_voc_advance.argtypes, lib.emu_voc_advance.restype = [i, i, i], ctypes.c_float
+    lib.emu_vocoder.argtypes = [i, i, i, i, d, vp, vp]
+    lib.emu_vocoder_slots.argtypes = [i, vp, vp, vp, i, i, d, vp, vp]
+    return lib
+
+
+def _vr(x):
+    return torch.view_as_real(x.resolve_conj())
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.uint8).numpy().tobytes()
+
+
+def spectrogram(O, name, B, T):
+    """the input of a case (shared with tests/test_gpu_vocoder.py): (SpectrogramParams, oracle params, X (B, n_stft, T) complex64), made
+    once and left unchanged.  B > 1: the last row is all zero.  T = 2: the first two frames of the T = 41 spectrogram."""
+    from riffusion.spectrogram_params import SpectrogramParams
+
+    key = (name, B, T)
+    if key not in _CASES:
+        p = SpectrogramParams(**ENGINES[name][1])
+        op = O.params_from(p)
+        if T == 2:
+            X = spectrogram(O, name, B, 41)[2][..., :2].clone()
+        else:
+            gen = torch.Generator().manual_seed(77 + T + B)
+            X = IO.stft(O, synthetic_wave(B, IO.samples(op, T), seed=303), op, torch.float64)
+            assert X.shape[-1] == T
+            rms = float(X.abs().pow(2).mean().sqrt())
+            X = X + 0.7071 * rms * torch.complex(torch.randn(X.shape, generator=gen, dtype=torch.float64), torch.randn(X.shape, generator=gen, dtype=torch.float64))
+            X = X.to(torch.complex64)
+            if B > 1:
+                X[-1] = 0
+        _CASES[key] = (p, op, X)
+    return _CASES[key]
+
+
+def oracle_figures(O, name, B, T, rate):
+    """(float64 result, SNR of the float32 oracle against it), made once per case and rate"""
+    key = (name, B, T, rate)
+    if key not in _CASES:
+        _, op, X = spectrogram(O, name, B, T)
+        r64 = VO.phase_vocoder(X, rate, op.hop_length, torch.float64)
+        _CASES[key] = (r64, snr_db(_vr(r64), _vr(VO.phase_vocoder(X, rate, op.hop_length, torch.float32))))
+    return _CASES[key]
+
+
+def run_emu(emu, X, hop, rate):
+    B, F, T = X.shape
+    X = X.contiguous()
+    Y = torch.full((B, F, VO.frames(T, rate)), 123.0, dtype=torch.complex64)
+    assert emu.emu_vocoder(F, hop, B, T, rate, X.data_ptr(), Y.data_ptr()) == Y.shape[-1]
+    return Y
+
+
+# ---- parity ------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("T", [41, 2])
+@pytest.mark.parametrize("name", list(ENGINES))
+def test_parity_within_6_db_of_float32_torch(O, emu, name, T):
+    _, op, X = spectrogram(O, name, 3, T)
+    for rate in RATES:
+        r64, o32 = oracle_figures(O, name, 3, T, rate)
+        Y = run_emu(emu, X, op.hop_length, rate)
+        e = snr_db(_vr(r64), _vr(Y))
+        print(f"{name} T{T} rate {rate}: emu {e:.1f} dB, o32 {o32:.1f} dB")
+        assert tuple(Y.shape) == tuple(r64.shape) and torch.isfinite(_vr(Y)).all()
+        assert e >= o32 - 6.0, (name, T, rate, e, o32)
+        assert not _vr(Y[-1]).any()  # the zero row leaves as zeros
+
+
+def test_parity_above_float32_torch_at_512_frames(O, emu):
+    _, op, X = spectrogram(O, "specialised", 1, 512)
+    for rate in RATES:
+        r64, o32 = oracle_figures(O, "specialised", 1, 512, rate)
+        e = snr_db(_vr(r64), _vr(run_emu(emu, X, op.hop_length, rate)))
+        print(f"specialised T512 rate {rate}: emu {e:.1f} dB, o32 {o32:.1f} dB")
+        assert e >= o32, (rate, e, o32)
+
+
+# ---- exact properties ------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", list(ENGINES))
+def test_copy_at_rate_one_and_a_row_alone(O, emu, name):
+    _, op, X = spectrogram(O, name, 3, 41)
+    assert _bits(run_emu(emu, X, op.hop_length, 1.0)) == _bits(X)
+    for rate in (1.25, 0.9):
+        Y = run_emu(emu, X, op.hop_length, rate)
+        for r in (0, 2):
+            assert _bits(run_emu(emu, X[r:r + 1], op.hop_length, rate)) == _bits(Y[r:r + 1]), (rate, r)
+
+
+def test_frame_count_is_torch_aranges():
+    from riffusion import _hip
+
+    for rate in RATES + [0.5, 2.0, 3.7]:
+        for T in range(1, 601):
+            assert _hip.phase_vocoder_frames(T, rate) == len(torch.arange(0, T, rate, dtype=torch.float64)), (T, rate)
+
+
+# ---- the table ---------------------------------------------------------------------------------------------------------------------------
+
+def _table(name):
+    from riffusion import _hip
+    from riffusion.spectrogram_params import SpectrogramParams
+
+    _, kw, plan_kw = ENGINES[name]
+    p = SpectrogramParams(**kw)
+    cp = _hip.RfxParams(p.sample_rate, p.n_fft, p.win_length, p.hop_length, p.num_frequencies, p.max_mel_iters)
+    return p, _hip.vocoder_table(cp, **plan_kw)
+
+
+@pytest.mark.parametrize("name", list(ENGINES))
+def test_table_primary_positions_and_advances(name):
+    p, (bins, src, adv, conj) = _table(name)
+    n_stft, D = p.n_fft // 2 + 1, 2 * (p.n_fft // 2)
+    S = len(bins)
+    assert S >= n_stft and len(src) == len(adv) == len(conj) == S
+    pad = bins < 0
+    assert (src[pad] == -1).all() and not adv[pad].any() and not conj[pad].any()  # the padding marker
+    held = np.flatnonzero(~pad)
+    assert ((src[held] >= 0) & (src[held] < S)).all()
+    primary = held[src[held] == held]
+    assert sorted(bins[primary].tolist()) == list(range(n_stft))  # every bin has exactly one primary position
+    assert (bins[src[held]] == bins[held]).all() and (src[src[held]] == src[held]).all()  # ... and every position points at its own bin's
+    k = bins[held].astype(np.int64)
+    frac = ((p.hop_length * k) % D).astype(np.float64) / D
+    want = np.where(conj[held] != 0, -frac, frac).astype(np.float32)  # one float32 rounding of the exact fraction
+    assert np.array_equal(adv[held], want)
+    assert (np.signbit(adv[held]) == (conj[held] != 0)).all()  # the sign is the flag's, a zero advance included
+    # torchaudio's linspace step for even and odd n_fft alike: pi hop / (n_stft - 1) per bin is hop / D of a turn
+    lin = torch.linspace(0, math.pi * p.hop_length, n_stft, dtype=torch.float64).numpy() / (2 * math.pi)
+    assert np.abs((lin[k] - frac + 0.5) % 1.0 - 0.5).max() < 1e-9
+    if name == "specialised":
+        assert S == 9408 and len(held) == 9261 and len(primary) == 8821  # 440 bins a second time
+        assert conj[primary].any()  # a primary position can hold the conjugate itself
+    else:
+        assert np.array_equal(held, np.arange(n_stft)) and np.array_equal(src[held], held) and not conj.any()  # plain frames
+
+
+@pytest.mark.parametrize("name", list(ENGINES))
+def test_slot_walk_on_the_table_is_the_bin_walk(O, emu, name):
+    _, op, X = spectrogram(O, name, 3, 41)
+    _, (bins, src, adv, conj) = _table(name)
+    S, T = len(bins), X.shape[-1]
+    held = bins >= 0
+    Xn = X.numpy()
+    slots = np.full((3, T, S), 7 + 7j, np.complex64)  # what rfx_pack_complex writes, the padding left as junk: it is never read
+    slots[:, :, held] = np.transpose(Xn[:, bins[held], :], (0, 2, 1))
+    slots[:, :, conj != 0] = np.conj(slots[:, :, conj != 0])
+    for rate in (1.25, 0.75):
+        want = run_emu(emu, X, op.hop_length, rate).numpy()
+        Tout = want.shape[-1]
+        out = np.full((3, Tout, S), 123, np.complex64)
+        assert emu.emu_vocoder_slots(S, src.ctypes.data, adv.ctypes.data, conj.ctypes.data, 3, T, rate, slots.ctypes.data, out.ctypes.data) == Tout
+        assert not out[:, :, ~held].any()  # padding is written zero
+        primary = np.flatnonzero(held & (src == np.arange(S)))
+        got = np.transpose(out[:, :, primary], (0, 2, 1)).copy()  # rfx_unpack_complex: each bin from its primary slot
+        flip = conj[primary] != 0
+        got[:, flip, :] = np.conj(got[:, flip, :])
+        order = np.argsort(bins[primary])
+        # a conjugate trajectory is the conjugate of the plain one: equal as numbers (x - x is +0 in both, so the sign of an exact zero can differ)
+        assert np.array_equal(got[:, order, :], want)
+        # pack(unpack(out)) == out: every slot is its bin's value, conjugated where its own flag says so
+        again = np.empty_like(out)
+        again[:, :, ~held] = 0
+        byslot = np.transpose(got[:, order, :][:, bins[held], :], (0, 2, 1))
+        again[:, :, held] = np.where(conj[held] != 0, np.conj(byslot), byslot)
+        assert again.tobytes() == out.tobytes()
+
+
+# ---- the entries without a device ------------------------------------------------------------------------------------------------------------
+
+def test_refusals_without_a_device():
+    from riffusion import _hip
+
+    lib = _hip.load_library()
+    n = ctypes.c_int(-7)
+    for T, rate, word in ((41, 0.0, b"rate"), (41, -1.0, b"rate"), (41, float("nan"), b"rate"), (41, float("inf"), b"rate"), (0, 1.25, b"T must"),
+                          (2 ** 31 - 1, 0.5, b"2^31")):
+        assert lib.rfx_phase_vocoder_frames(T, rate, ctypes.byref(n)) == -1 and n.value == -7
+        assert b"rfx_phase_vocoder_frames: " in lib.rfx_last_error() and word in lib.rfx_last_error(), (T, rate)
+    assert lib.rfx_phase_vocoder_frames(41, 1.25, None) == -1
+    assert lib.rfx_phase_vocoder_frames(41, 1.25, ctypes.byref(n)) == 0 and n.value == 33
+    # B == 0 is a no-op, B < 0 and a NULL pointer are refusals, under the entry's name
+    assert lib.rfx_phase_vocoder(None, None, 0, 41, 1.25, None, None) == 0
+    assert lib.rfx_phase_vocoder(None, None, 1, 41, 1.25, None, None) == -1 and b"rfx_phase_vocoder: null" in lib.rfx_last_error()
+    assert lib.rfx_phase_vocoder(None, None, -1, 41, 1.25, None, None) == -1
+    assert lib.rfx_time_stretch(None, None, 0, 20000, 1.25, None, None, 0, None) == 0
+    assert lib.rfx_time_stretch(None, None, 1, 20000, 1.25, None, None, 0, None) == -1 and b"rfx_time_stretch: null" in lib.rfx_last_error()
+    assert lib.rfx_time_stretch(None, None, -1, 20000, 1.25, None, None, 0, None) == -1
+    assert lib.rfx_time_stretch_workspace_bytes(None, 1, 20000, 1.25) == 0 and lib.rfx_time_stretch_samples(None, 20000, 1.25) == 0
+    for bad in (0, -1.0, float("nan"), float("inf"), "1.25", True, torch.tensor(1.25), [1.25, 0.8]):
+        with pytest.raises(ValueError, match="rate"):
+            _hip.check_stretch_rate(bad)
+    assert _hip.check_stretch_rate(2) == 2.0
+
+
+def test_header_compiles_as_c99_with_the_entries(tmp_path):
+    src = tmp_path / "use.c"
+    src.write_text('#include "rfx.h"\n'
+                   "size_t q(const rfx_plan* p) { return rfx_time_stretch_workspace_bytes(p, 1, 20000, 1.25) + (size_t)rfx_time_stretch_samples(p, 20000, 1.25); }\n"
+                   "int r(const rfx_plan* p, void* x, float* y, void* ws, int* n) {\n"
+                   "  return rfx_phase_vocoder_frames(41, 1.25, n) + rfx_phase_vocoder(p, x, 1, 41, 1.25, ws, 0) + rfx_time_stretch(p, y, 1, 20000, 0.8, y, ws, 0, 0); }\n"
+                   "int t(const rfx_params* p, int32_t* a, float* f, uint8_t* c, int32_t* n) { return rfx_debug_vocoder_table(p, 0, a, a, f, c, 0, n); }\n")
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "use.o")],
+                   check=True)
+
+
+def test_an_input_that_requires_grad_is_refused_before_the_plan():
+    from riffusion.spectrogram_converter import SpectrogramConverter
+    from riffusion.spectrogram_params import SpectrogramParams
+
+    c = SpectrogramConverter(SpectrogramParams(), device="cpu")  # (no plan on the CPU: a call that reached for one would say so)
+    w = torch.zeros(2, 20000, requires_grad=True)
+    X = torch.zeros(2, 8821, 9, dtype=torch.complex64, requires_grad=True)
+    with pytest.raises(RuntimeError, match="no backward"):
+        c.time_stretch(w, 1.25)
+    with pytest.raises(RuntimeError, match="no backward"):
+        c.time_stretch_spectrogram(X, 1.25)
+    with torch.no_grad(), pytest.raises(RuntimeError, match="MI355X"):  # grad mode off: the rule does not apply, the call goes on to the plan
+        c.time_stretch(w, 1.25)
+    for bad in (0.0, float("nan"), torch.tensor(1.25)):
+        with pytest.raises(ValueError, match="rate"):
+            c.time_stretch(w.detach(), bad)
+    with pytest.raises(ValueError, match="linear bins"):
+        c.time_stretch_spectrogram(X.detach()[:, :-1], 1.25)
+    with pytest.raises(ValueError, match="complex"):
+        c.time_stretch_spectrogram(X.detach().abs(), 1.25)
+    with pytest.raises(ValueError, match="length"):
+        c.time_stretch(w.detach(), 1.25, length=-1)
+
+
+def test_command_line_argument_checks(capsys):
+    from riffusion import cli
+
+    assert cli._stretch_rate(rate=1.25, bpm_from=0.0, bpm_to=0.0) == 1.25
+    assert cli._stretch_rate(rate=0.0, bpm_from=120.0, bpm_to=100.0) == 100.0 / 120.0
+    for flags in ([], ["--rate", "1.25", "--bpm-from", "120", "--bpm-to", "100"], ["--bpm-from", "120"], ["--bpm-to", "100"], ["--rate", "-2"],
+                  ["--rate", "nan"], ["--rate", "inf"], ["--bpm-from", "120", "--bpm-to", "-1"]):
+        with pytest.raises(SystemExit) as e:
+            cli.main(["time-stretch", "--audio", "missing.wav", "--output", "out.wav"] + flags)
+        assert e.value.code == 2, flags
+        err = capsys.readouterr().err
+        assert "--rate" in err or "--bpm" in err, flags
+    with pytest.raises(SystemExit):  # --audio and --output are required
+        cli.main(["time-stretch", "--rate", "1.25"])
+
+
+# ---- the sanitized stand-alone program ---------------------------------------------------------------------------------------------------------
+
+def test_sanitized_stand_alone_emulator(tmp_path):
+    """the emulator with its own main, built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program; the sanitizers'
+    runtimes are linked statically, so the program carries them itself"""
+    exe = str(tmp_path / "rfx_vocoder_emu_asan")
+    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                    "-static-libasan", "-static-libubsan", "-o", exe, EMU_SRC, EMU_MAIN], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip().endswith("ok") and "ERROR" not in run.stderr, run.stdout + run.stderr
