@@ -853,6 +853,65 @@ int rfx_time_stretch(const rfx_plan* plan, const float* d_wave, int B, int Lw, d
 int rfx_debug_vocoder_table(const rfx_params* params, const rfx_plan_options* options, int32_t* h_bin, int32_t* h_src, float* h_advance,
                             uint8_t* h_conj, int capacity, int32_t* stride_out);
 
+/* ---- SINC RESAMPLE: torchaudio.functional.resample, band-limited, float32 (torchaudio.transforms.Resample) --------------------------------
+ * resample(waveform, orig, new, lowpass_filter_width = lpw, rolloff, resampling_method = "sinc_interp_hann") on rows of float32
+ * samples.  With g = gcd(orig, new), o = orig / g, n = new / g, base = min(o, n) rolloff, width = ceil(lpw o / base):
+ *   length  L samples in, K = ceil(n L / o) samples out, exact in integers: rfx_resample_sinc_frames (host only).  (torchaudio rounds
+ *           the quotient to float32 before the ceil; the two agree below 2^24 samples.)
+ *   output  j = q n + p, 0 <= p < n, is the sum over i of x[q o + i - width] k_p[i], x zero outside [0, L), with
+ *           k_p[i] = sinc(pi t) cos^2(pi t / (2 lpw)) base / o,  t = clamp((-p / n + (i - width) / o) base, -lpw, lpw).
+ * DROPPED TAPS: torchaudio's dense kernel has 2 width + o taps per phase; at all but about 2 lpw o / base + 1 of them (13 to 25) the
+ * clamp holds t at +-lpw, where the window is cos^2(pi / 2) - 4e-33 in float64, not 0.  This library drops the taps with
+ * |t| >= lpw: a difference below 1e-30 of a sample per tap.
+ * Only the Hann window is stated; there is no entry for torchaudio's "sinc_interp_kaiser".
+ * THE TABLE (rfx_resample_sinc_table, host only, no GPU; as rfx_image_resize_coefficients: the host computes, the caller uploads):
+ * h_first[p], p < n, the offset from q o of the first tap phase p keeps (negative at a row's start); h_taps[k n + p], k < ntaps, the
+ * weights TAP-MAJOR, computed in double and rounded once to float32 - the kernel torchaudio.transforms.Resample holds -, ntaps the
+ * longest run over the phases, shorter phases filled with 0.  `capacity` counts the floats of h_taps; h_first needs n entries.  With
+ * both arrays NULL the call answers *n_out and *ntaps_out alone.  RFX_ERR_UNSUPPORTED with a message where the table, 4 n ntaps
+ * bytes, would pass RFX_RESAMPLE_MAX_TABLE_BYTES: every integer semitone shift within +-12 at 8 to 96 kHz stays below 8.5 MiB.
+ * rfx_resample_sinc: d_in (B, L) float32 -> d_out (B, K) float32 on the device that owns d_out, d_first / d_taps the uploaded table of
+ * (orig, new).  One kernel (rfx_resample.hip): one thread per output sample and block of 4 rows, the taps accumulated in ascending
+ * order with one fmaf each; sample indices are 64-bit.  orig == new copies the input, as torchaudio returns it (the table is not read).
+ * Contract: B == 0 is a no-op.  RFX_ERR_INVALID with a message, before any launch, the outputs untouched: a NULL pointer; a
+ * frequency that is not positive; L < 1; K past 2^31 - 1; ntaps < 1; a pointer off 4-byte alignment; d_in and d_out overlapping;
+ * for the table a lowpass_filter_width < 1, a rolloff outside (0, 1], one array without the other or a capacity below n ntaps.  The
+ * kernel tests every index it forms from the table against the row, so a table of another pair gives wrong samples, not a fault. */
+#define RFX_RESAMPLE_MAX_TABLE_BYTES (16 << 20)
+int rfx_resample_sinc_frames(int L, int orig_freq, int new_freq, int* K);
+int rfx_resample_sinc_table(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int32_t* h_first, float* h_taps,
+                            int64_t capacity, int32_t* n_out, int32_t* ntaps_out);
+int rfx_resample_sinc(const float* d_in, int B, int L, int orig_freq, int new_freq, const int32_t* d_first, const float* d_taps, int ntaps,
+                      float* d_out, void* stream);
+
+/* ---- PITCH SHIFT: the time stretch, then the resampler back to the duration (torchaudio.transforms.PitchShift) ----------------------------
+ * rfx_pitch_shift is torchaudio.functional.pitch_shift(waveform, sample_rate, n_steps, bins_per_octave) at the plan's STFT parameters
+ * and sample rate: d_wave (B, Lw) float32 -> d_wave_out (B, Lw) float32, the key moved by n_steps / bins_per_octave octaves at the
+ * same tempo.  Per group of rows it is exactly
+ *   1. rfx_time_stretch at rate = 2^(-n_steps / bins_per_octave), Ls samples per row;
+ *   2. cut, or pad with zeros, to len_stretch = round(Lw / rate) (ties to even, as Python rounds);
+ *   3. rfx_resample_sinc from orig = int(sample_rate / rate) (rfx_pitch_shift_resample_freq, host only) to sample_rate, with the
+ *      caller's table of that pair at lowpass_filter_width 6, rolloff 0.99;
+ *   4. cut, or pad with zeros, to Lw
+ * - the same bytes as the separate calls on all rows at once.  Steps 2 and 4 make no pass of their own: the resampler reads zeros
+ * past min(Ls, len_stretch) and stores min(K, Lw) samples.  n_steps == 0 copies the input (no workspace, no table).  A shift so small
+ * that orig == sample_rate runs steps 1, 2 and 4 and does not read the table.
+ * ONE DEPARTURE: where len_stretch exceeds Ls = hop (T_out - 1) (+ n_fft % 2) - by less than one hop - torch.istft(length =
+ * len_stretch) keeps len_stretch - Ls samples of its untrimmed tail; this library pads zeros there, as rfx_istft's callers do
+ * everywhere else.  With o / n the reduced pair of step 3 and base = min(o, n) 0.99, the samples this can reach are the outputs
+ * j >= floor((Ls - 6 o / base) n / o): the last ceil((len_stretch - Ls) n / o + 6 n / base) + 1 of the K, less what step 4 cuts.
+ * BOUNDED WORKSPACE (rfx_pitch_shift_workspace_bytes): the stretched rows of a group, plus what rfx_time_stretch asks for the group;
+ * the groups are rfx_time_stretch's own.  No gradient, no loop form, one shift per call.
+ * Contract: B == 0 is a no-op.  RFX_ERR_INVALID with a message, before any launch, the output untouched: a NULL pointer; n_steps
+ * not finite; bins_per_octave < 1; what rfx_time_stretch refuses for Lw at the rate; len_stretch, orig or K past 2^31 - 1; what
+ * rfx_resample_sinc refuses of the table; a workspace off 16-byte or a waveform off 4-byte alignment; d_wave and d_wave_out
+ * overlapping.  RFX_ERR_UNSUPPORTED: a table past RFX_RESAMPLE_MAX_TABLE_BYTES.  RFX_ERR_WORKSPACE: a workspace below the query.
+ * A query answers 0 where the call would be refused, and for n_steps == 0. */
+size_t rfx_pitch_shift_workspace_bytes(const rfx_plan* plan, int B, int Lw, double n_steps, int bins_per_octave);
+int rfx_pitch_shift_resample_freq(const rfx_plan* plan, int Lw, double n_steps, int bins_per_octave);
+int rfx_pitch_shift(const rfx_plan* plan, const float* d_wave, int B, int Lw, double n_steps, int bins_per_octave, const int32_t* d_first,
+                    const float* d_taps, int ntaps, float* d_wave_out, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- inverse: torchaudio.transforms.InverseMelScale (SGD, max_iter = params.max_mel_iters,
  * tolerance_loss 1e-5, tolerance_change 1e-8, lr 0.1, momentum 0.9), spectrogram_converter.py:87-99,
  * called at :201.  d_mel (B, n_mels, T); the B rows are grouped into clips of `channels_per_clip`

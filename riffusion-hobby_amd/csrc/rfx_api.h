@@ -48,6 +48,8 @@ struct DeviceGuard {
 #define RFX_ON_DEVICE(dev)   \
   DeviceGuard guard_((dev)); \
   if (guard_.err != hipSuccess) return fail(RFX_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
+// device that owns a caller buffer, for the entry points that take no plan (rfx_api_codec.hip); RFX_ERR_INVALID: not a device pointer
+int device_of(const void* d_ptr, int* device);
 // the argument checks the two clip-gather entries share (rfx_api_codec.hip)
 int check_pcm_clips(const char* who, const int16_t* d_pcm, int64_t frames, int in_channels, const int64_t* h_starts, int N, int Lw,
                     int out_channels);
@@ -187,7 +189,7 @@ inline int group_rows(size_t bytes, size_t row_bytes, int B, size_t cap = (size_
   rows = rows < 1 ? 1 : rows > cap ? cap : rows;
   return (int)(rows > (size_t)B ? (size_t)B : rows);
 }
-// the cap of the grouped drivers that hold whole spectrogram rows in their workspace (rfx_api_istft.hip, rfx_api_vocoder.hip)
+// the cap of the grouped drivers that hold whole spectrogram rows in their workspace (rfx_api_istft.hip, rfx_api_vocoder.hip, rfx_api_resample.hip)
 constexpr size_t kIstftGroupBytes = (size_t)256 << 20;
 constexpr size_t kIstftGroupRows = 65535;  // the folds carry the row in blockIdx.y
 struct Carve {

@@ -13,8 +13,8 @@
 
 using namespace rfx;
 
-// device that owns a caller buffer (the codec entry points take no plan)
-static int device_of(const void* d_ptr, int* device) {
+// device that owns a caller buffer (the entry points that take no plan; declared in rfx_api.h)
+int rfx::device_of(const void* d_ptr, int* device) {
   hipPointerAttribute_t attr;
   const hipError_t e = hipPointerGetAttributes(&attr, d_ptr);
   if (e != hipSuccess) {

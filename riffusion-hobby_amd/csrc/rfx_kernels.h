@@ -712,4 +712,19 @@ struct VocoderArgs {
 };
 hipError_t launch_vocoder(const VocoderArgs& a, hipStream_t stream);
 
+// windowed-sinc resample (rfx_resample.hip, arithmetic in rfx_resample_core.h): `rows` rows of in, in_stride floats apart, read as
+// zero outside [0, valid) -> the first K outputs of each row, out_stride floats apart.  first [n] int32 and taps [ntaps][n] float32:
+// the polyphase table of the reduced pair o / n (rs_table).  valid <= in_stride, K <= out_stride; any number of rows.  Every index
+// the kernel forms from the table is tested against [0, valid), whatever the table holds.
+constexpr int kRsRows = 4;  // rows a thread carries for one output index
+struct ResampleArgs {
+  const float* in;
+  float* out;
+  const int32_t* first;
+  const float* taps;
+  int64_t in_stride, out_stride, valid, K;
+  int rows, o, n, ntaps;
+};
+hipError_t launch_resample_sinc(const ResampleArgs& a, hipStream_t stream);
+
 }  // namespace rfx

@@ -349,6 +349,21 @@ def check_stretch_rate(rate: T.Any) -> float:
     return rate
 
 
+def check_pitch_steps(n_steps: T.Any, bins_per_octave: T.Any = 12) -> T.Tuple[float, int]:
+    """the shift of a pitch shift as the library takes it: one finite number of steps (one shift per call) of 1 / bins_per_octave
+    octave, bins_per_octave a positive integer"""
+    import numbers
+
+    if isinstance(n_steps, bool) or not isinstance(n_steps, numbers.Real):
+        raise ValueError(f"n_steps must be one real number (one shift per call), got {type(n_steps).__name__}")
+    n_steps = float(n_steps)
+    if n_steps != n_steps or n_steps in (float("inf"), float("-inf")):
+        raise ValueError(f"n_steps must be finite, got {n_steps}")
+    if isinstance(bins_per_octave, bool) or not isinstance(bins_per_octave, numbers.Integral) or int(bins_per_octave) < 1:
+        raise ValueError(f"bins_per_octave must be a positive integer, got {bins_per_octave!r}")
+    return n_steps, int(bins_per_octave)
+
+
 def phase_vocoder_frames(Tn: int, rate: float) -> int:
     """rfx_phase_vocoder_frames (host only, no GPU): ceil(Tn / rate) in double, the length of torch.arange(0, Tn, rate)"""
     n = c_int(0)
@@ -473,6 +488,15 @@ SIGNATURES: T.Dict[str, T.Tuple[T.Any, T.List[T.Any]]] = {
     "rfx_time_stretch": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rfx_debug_vocoder_table": (c_int, [ctypes.POINTER(RfxParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                         ctypes.POINTER(ctypes.c_int32)]),
+    # sinc resample and pitch shift: the time stretch, then the resampler back to the duration
+    "rfx_resample_sinc_frames": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "rfx_resample_sinc_table": (c_int, [c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(ctypes.c_int32)]),
+    "rfx_resample_sinc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "rfx_pitch_shift_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, ctypes.c_double, c_int]),
+    "rfx_pitch_shift_resample_freq": (c_int, [c_void_p, c_int, ctypes.c_double, c_int]),
+    "rfx_pitch_shift": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
     # fused spectral losses (riffusion/_autograd.py: SpectralLossFunction)
     "rfx_spectral_loss_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rfx_spectral_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -645,6 +669,70 @@ def resolve_device(device: T.Union[str, torch.device]) -> torch.device:
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     return dev
+
+
+# ---- sinc resample (include/rfx.h "SINC RESAMPLE"): torchaudio.functional.resample with the Hann window -------------------------------
+RESAMPLE_LOWPASS_FILTER_WIDTH, RESAMPLE_ROLLOFF = 6, 0.99  # torchaudio's defaults
+_resample_tables: "collections.OrderedDict[T.Any, T.Any]" = collections.OrderedDict()
+_resample_lock = threading.Lock()
+
+
+def check_resample_method(resampling_method: str) -> None:
+    """only torchaudio's default window is stated"""
+    if resampling_method != "sinc_interp_hann":
+        raise ValueError(f"resampling_method {resampling_method!r} is not served: only 'sinc_interp_hann' (torchaudio's default) is; "
+                         "there is no kaiser window on the device")
+
+
+def resample_sinc_frames(L: int, orig_freq: int, new_freq: int) -> int:
+    """rfx_resample_sinc_frames (host only, no GPU): ceil(new L / orig) on the reduced pair, the samples L samples give"""
+    k = c_int(0)
+    check(load_library().rfx_resample_sinc_frames(int(L), int(orig_freq), int(new_freq), ctypes.byref(k)))
+    return k.value
+
+
+def resample_sinc_table(orig_freq: int, new_freq: int, lowpass_filter_width: int = RESAMPLE_LOWPASS_FILTER_WIDTH,
+                        rolloff: float = RESAMPLE_ROLLOFF, device: T.Optional[T.Union[str, torch.device]] = None) -> T.Tuple[T.Any, T.Any]:
+    """rfx_resample_sinc_table: (first (n,) int32, taps (ntaps, n) float32 - tap-major) of the reduced pair.  Without `device` the
+    host table as numpy arrays (no GPU); with one, the uploaded tensors, kept per (orig, new, lowpass_filter_width, rolloff, device)
+    - the 32 most recently used pairs."""
+    key = (int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), None if device is None else resolve_device(device))
+    with _resample_lock:
+        hit = _resample_tables.get(key)
+        if hit is not None:
+            _resample_tables.move_to_end(key)
+            return hit
+    lib, n, ntaps = load_library(), ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib.rfx_resample_sinc_table(key[0], key[1], key[2], key[3], None, None, 0, ctypes.byref(n), ctypes.byref(ntaps)))
+    first, taps = np.zeros(n.value, np.int32), np.zeros((ntaps.value, n.value), np.float32)
+    check(lib.rfx_resample_sinc_table(key[0], key[1], key[2], key[3], first.ctypes.data, taps.ctypes.data, taps.size, ctypes.byref(n), ctypes.byref(ntaps)))
+    if device is None:
+        return first, taps
+    table = (torch.from_numpy(first).to(key[4]), torch.from_numpy(taps).to(key[4]))
+    with _resample_lock:
+        _resample_tables[key] = table
+        while len(_resample_tables) > 32:
+            _resample_tables.popitem(last=False)
+    return table
+
+
+def resample_sinc(wave: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = RESAMPLE_LOWPASS_FILTER_WIDTH,
+                  rolloff: float = RESAMPLE_ROLLOFF) -> torch.Tensor:
+    """rfx_resample_sinc: (B, L) float32 on a GPU -> (B, ceil(new L / orig)) float32 there: torchaudio.functional.resample with the
+    Hann window.  orig == new gives a copy."""
+    if wave.device.type != "cuda" or wave.dtype != torch.float32 or wave.dim() != 2:
+        raise ValueError(f"expected a (B, L) float32 waveform on the GPU, got {tuple(wave.shape)} {wave.dtype} on {wave.device}")
+    wave = wave.contiguous()
+    B, L = wave.shape
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    K = resample_sinc_frames(L, orig_freq, new_freq)
+    first, taps = (None, None) if orig_freq == new_freq else resample_sinc_table(orig_freq, new_freq, lowpass_filter_width, rolloff, wave.device)
+    out = torch.empty((B, K), dtype=torch.float32, device=wave.device)
+    if B:
+        check(load_library().rfx_resample_sinc(wave.data_ptr(), B, L, orig_freq, new_freq, None if first is None else first.data_ptr(),
+                                               None if taps is None else taps.data_ptr(), 0 if taps is None else int(taps.shape[0]),
+                                               out.data_ptr(), current_stream(wave.device)))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1296,6 +1384,35 @@ class Plan:
         if B:
             with self._workspace(self.lib.rfx_time_stretch_workspace_bytes(self.handle, B, Lw, rate)) as ws:
                 check(self.lib.rfx_time_stretch(self.handle, wave.data_ptr(), B, Lw, rate, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    # ---- pitch shift (include/rfx.h "PITCH SHIFT") ----
+    def pitch_shift(self, wave: torch.Tensor, n_steps: float, bins_per_octave: int = 12) -> torch.Tensor:
+        """rfx_pitch_shift: (B, Lw) float32 -> (B, Lw) float32, torchaudio.functional.pitch_shift at the plan's STFT parameters and
+        sample rate: exactly `time_stretch` at rate 2^(-n_steps / bins_per_octave), cut or zero-padded to round(Lw / rate) samples,
+        `resample_sinc` from int(sample_rate / rate) to sample_rate, cut or zero-padded to Lw, on bounded groups of rows.
+        n_steps == 0 gives a copy.  Where round(Lw / rate) exceeds the stretched row the missing samples are zeros, not the
+        untrimmed tail torch.istft(length=) keeps (include/rfx.h states which output samples that can reach)."""
+        n_steps, bins_per_octave = check_pitch_steps(n_steps, bins_per_octave)
+        wave = self._chk(wave, torch.float32)
+        if wave.dim() != 2:
+            raise ValueError(f"expected a (B, Lw) waveform, got {tuple(wave.shape)}")
+        B, Lw = wave.shape
+        if n_steps == 0.0 or B == 0:
+            return wave.clone()
+        self._forward_frames(Lw, (Lw,), False)  # the refusal of a row too short, before any device work
+        orig = int(self.lib.rfx_pitch_shift_resample_freq(self.handle, Lw, n_steps, bins_per_octave))
+        need = int(self.lib.rfx_pitch_shift_workspace_bytes(self.handle, B, Lw, n_steps, bins_per_octave))
+        if orig < 1 or need < 1:
+            raise ValueError(f"pitch_shift: rows of {Lw} samples cannot be shifted by {n_steps} steps of 1/{bins_per_octave} octave "
+                             "(the stretched length, the resampler's frequency or its output passes 2^31 - 1, or the stretch gives no sample)")
+        sr = self.sample_rate
+        first, taps = (None, None) if orig == sr else resample_sinc_table(orig, sr, device=self.device)
+        out = torch.empty((B, Lw), dtype=torch.float32, device=self.device)
+        with self._workspace(need) as ws:
+            check(self.lib.rfx_pitch_shift(self.handle, wave.data_ptr(), B, Lw, n_steps, bins_per_octave, None if first is None else first.data_ptr(),
+                                           None if taps is None else taps.data_ptr(), 0 if taps is None else int(taps.shape[0]), out.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), self._stream()))
         return out
 
     # ---- fused spectral losses (include/rfx.h "FUSED SPECTRAL LOSSES"; riffusion/_autograd.py: SpectralLossFunction) ----

@@ -16,6 +16,7 @@ installed here); without pydub only 16-bit PCM wav files are read and only wav i
     python -m riffusion.cli images-to-audio-batch --image-dir tiles/ --output-dir wavs/
     python -m riffusion.cli audio-to-images-batch --audio-dir wavs/ --output-dir tiles/
     python -m riffusion.cli time-stretch --audio clip.wav --output slower.wav --bpm-from 120 --bpm-to 100
+    python -m riffusion.cli pitch-shift --audio clip.wav --output higher.wav --semitones 2
 """
 import argparse
 import glob
@@ -442,6 +443,39 @@ def time_stretch(*, audio: str, output: str, rate: float = 0.0, bpm_from: float 
     print(f"Wrote {output} ({out.duration_seconds:.2f} seconds, rate {r:.4f})")
 
 
+def _semitones(*, semitones: T.Union[str, float], **_: T.Any) -> float:
+    """the shift of pitch-shift from its flag (a required flag arrives as text): ValueError for one that is no finite number (the
+    function raises it, the parser reports it)"""
+    try:
+        n = float(semitones)
+    except (TypeError, ValueError):
+        raise ValueError(f"--semitones must be a number, got {semitones!r}") from None
+    if n != n or n in (float("inf"), float("-inf")):
+        raise ValueError("--semitones must be finite")
+    return n
+
+
+def pitch_shift(*, audio: str, output: str, semitones: T.Union[str, float], device: str = "cuda", frame_engine: str = "auto") -> None:
+    """Move a clip to another key at the same tempo and duration: the time stretch, then the band-limited resampler back to the
+    clip's length, on the device.  --semitones N: N semitones up (negative: down; 12 is an octave; fractions are allowed).  The
+    clip's channels are rows of one call; the result is peak-normalised into 16-bit PCM as a decode's is.  The analysis runs at
+    the clip's sample rate with the default window, hop and padding.  One shift for the whole clip; a loop does not stay a loop."""
+    import torch
+
+    from riffusion.spectrogram_converter import SpectrogramConverter
+
+    n = _semitones(semitones=semitones)
+    segment = _load_segment(audio)
+    waveform = np.array([c.get_array_of_samples() for c in segment.split_to_mono()]).astype(np.float32)
+    params = SpectrogramParams(sample_rate=int(segment.frame_rate), stereo=waveform.shape[0] == 2)
+    converter = SpectrogramConverter(params=params, device=device, frame_engine=frame_engine)
+    shifted = converter.pitch_shift(torch.from_numpy(waveform), n)
+    pcm, _ = converter._plan().pcm16(shifted, channels=shifted.shape[0], normalize=True)
+    out = audio_util.segment_from_pcm16(pcm[0].cpu().numpy(), params.sample_rate)
+    out.export(output, format=os.path.splitext(output)[1][1:] or "wav")
+    print(f"Wrote {output} ({out.duration_seconds:.2f} seconds, {n:+g} semitones)")
+
+
 _COMMANDS: T.Dict[str, T.Callable[..., None]] = {
     "audio-to-image": audio_to_image,
     "image-to-audio": image_to_audio,
@@ -449,6 +483,7 @@ _COMMANDS: T.Dict[str, T.Callable[..., None]] = {
     "images-to-audio-batch": images_to_audio_batch,
     "audio-to-images-batch": audio_to_images_batch,
     "time-stretch": time_stretch,
+    "pitch-shift": pitch_shift,
 }
 
 
@@ -493,6 +528,11 @@ def main(argv: T.Optional[T.Sequence[str]] = None) -> None:
     if command == "time-stretch":
         try:
             _stretch_rate(**args)
+        except ValueError as e:
+            parser.error(str(e))
+    if command == "pitch-shift":
+        try:
+            _semitones(**args)
         except ValueError as e:
             parser.error(str(e))
     if command == "images-to-audio-batch" and args["griffin_lim_iters"] < -1:

@@ -497,6 +497,35 @@ class SpectrogramConverter:
             wave = wave[:, : int(length)] if int(length) <= L else torch.nn.functional.pad(wave, (0, int(length) - L))
         return wave.reshape(*lead, wave.shape[-1])
 
+    # ---- pitch shift: the time stretch, then the resampler back to the duration -----------------------------
+    def pitch_shift(self, waveform: torch.Tensor, n_steps: float, bins_per_octave: int = 12) -> torch.Tensor:
+        """
+        (..., samples) float32 -> (..., samples) float32, the clip moved by `n_steps` steps of 1 / `bins_per_octave` octave at the same
+        tempo: what torchaudio.transforms.PitchShift(sample_rate, n_steps, bins_per_octave, n_fft, win_length, hop_length)(waveform)
+        computes at the converter's own STFT parameters, in one call on the device (rfx_pitch_shift): `time_stretch` at rate
+        2^(-n_steps / bins_per_octave), cut or zero-padded to round(samples / rate), the windowed-sinc resampler from
+        int(sample_rate / rate) back to sample_rate, cut or zero-padded to `samples`.  +12 is an octave up, -12 an octave down;
+        n_steps == 0 returns the input's values.  To put a generated clip in the key of the clip it is stitched to, shift it
+        by the difference in semitones.
+        One departure from torchaudio: where round(samples / rate) exceeds the stretched clip's hop * (T_out - 1) samples - by less
+        than one hop - torch.istft(length=) keeps samples of its untrimmed tail and this call pads zeros, as `waveform_from_spectrogram(
+        length=)` does.  With o / n the reduced pair int(sample_rate / rate) / sample_rate this reaches at most the last
+        ceil((round(samples / rate) - hop * (T_out - 1)) * n / o + 6 * n / (0.99 * min(o, n))) + 1 output samples.
+        One shift per call, no gradient (a `waveform` that requires grad while grad mode is on raises before any device work), no
+        loop form, for the reasons `time_stretch` gives.
+        """
+        from riffusion import _hip
+
+        n_steps, bins_per_octave = _hip.check_pitch_steps(n_steps, bins_per_octave)
+        if isinstance(waveform, torch.Tensor) and _autograd.wants_grad(waveform):
+            raise RuntimeError("pitch_shift: the pitch shift has no backward; detach the input, or run under torch.no_grad()")
+        if not isinstance(waveform, torch.Tensor) or waveform.is_complex() or waveform.dim() < 1:
+            raise ValueError("pitch_shift takes a real (..., samples) waveform")
+        plan = self._plan()
+        lead = waveform.shape[:-1]
+        w = waveform.detach().reshape(-1, waveform.shape[-1]).to(self.device).to(torch.float32)
+        return plan.pitch_shift(w, n_steps, bins_per_octave).reshape(*lead, waveform.shape[-1])
+
     # ---- quality of a decode ------------------------------------------------------------------------
     @staticmethod
     def convergence_from_sums(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:

@@ -279,6 +279,34 @@ class PcmSegment:
         return cls(data, rate)
 
 
+def resample_waveform(waveform: T.Any, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+                      resampling_method: str = "sinc_interp_hann", device: str = "cuda") -> T.Any:
+    """
+    (..., L) float waveform -> (..., ceil(new L / orig)) float32 on the GPU: torchaudio.functional.resample(waveform, orig_freq,
+    new_freq, lowpass_filter_width, rolloff) - torchaudio.transforms.Resample - with its default Hann-windowed sinc, band-limited, as
+    one HIP kernel over the taps inside the window (rfx_resample_sinc).  Leading dimensions are kept; an input on the CPU goes to
+    `device`, one on a GPU stays where it is, and the result stays on the GPU.  orig_freq == new_freq returns the input's values.
+    Only "sinc_interp_hann" is served: "sinc_interp_kaiser" raises ValueError.  No gradient.  (The int16 path of the encode,
+    `ratecv_np` / rfx_pcm16_resample, is audioop's two-point interpolation and stays what pydub's set_frame_rate computes.)
+    """
+    import torch
+
+    from riffusion import _hip
+
+    _hip.check_resample_method(resampling_method)
+    if not isinstance(waveform, torch.Tensor) or waveform.is_complex() or waveform.dim() < 1:
+        raise ValueError("resample_waveform takes a real (..., samples) tensor")
+    if int(orig_freq) != orig_freq or int(new_freq) != new_freq or int(orig_freq) < 1 or int(new_freq) < 1:
+        raise ValueError(f"frequencies must be positive integers, got {orig_freq!r} -> {new_freq!r}")
+    if torch.is_grad_enabled() and waveform.requires_grad:
+        raise RuntimeError("resample_waveform: the resampler has no backward; detach the input, or run under torch.no_grad()")
+    lead = waveform.shape[:-1]
+    w = waveform.detach().reshape(-1, waveform.shape[-1])
+    w = (w if w.device.type == "cuda" else w.to(_hip.resolve_device(device))).to(torch.float32)
+    out = _hip.resample_sinc(w, int(orig_freq), int(new_freq), lowpass_filter_width, rolloff)
+    return out.reshape(*lead, out.shape[-1])
+
+
 RATECV_RATE_LIMIT = 1 << 20  # reduced rates (rate / gcd) below this: audioop's double division is then the exact quotient
 
 
