@@ -826,6 +826,12 @@ int rfx_debug_istft_backward_padded(const rfx_plan* plan, const float* d_grad_wa
  *   step i  reads frames i0 = floor(i rate) and i0 + 1, i rate formed in double, alpha = (float)(i rate - i0); frames at or past T are 0.
  *   output  magnitude alpha |X[i0 + 1]| + (1 - alpha) |X[i0]|; phase angle(X[0]) at step 0, then the running sum of
  *           wrap(angle(X[i0 + 1]) - angle(X[i0]) - adv_k) + adv_k.
+ * STEP POSITIONS ARE THE DOUBLE PRODUCTS (double)i * rate, one rounding each, the same on every machine.  torchaudio takes them from
+ * torch.arange(0, T, rate) in the spectrogram's real dtype, whose value for step i is not that product: where i rate lies within
+ * rounding of an integer arange can choose the neighbouring frame pair - the same magnitude to rounding, another phase trajectory
+ * from that step on.  Of the 495 reduced fractions p/q in [0.25, 4] with q <= 24, p <= 48 at T = 512 the float64 CPU arange does so
+ * at 168 rates (2/3, 4/3, 0.3 and 1.2 among them) and the float32 CPU arange at 46 (tools/survey_vocoder_steps.py,
+ * profiles/time_stretch_steps.txt); tests/vocoder_oracle.py, the reference of every gate, takes the products.
  * PHASES ARE TURNS: adv_k = (hop k mod D) / D with D = 2 (n_stft - 1) in integers, the accumulator wrapped to [-1/2, 1/2] after every
  * step, sine and cosine taken of the wrapped turns.  Float32 torch sums the absolute phase - up to pi hop radians per frame - and loses
  * about a bit per doubling of T; this form does not (tests/test_vocoder_cpu.py holds it ABOVE float32 torch at T = 512).

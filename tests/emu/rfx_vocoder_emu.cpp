@@ -1,6 +1,7 @@
 // Host emulator of the time stretch's kernel (riffusion-hobby_amd/csrc/rfx_vocoder.hip): the arithmetic and the walk are
 // rfx_vocoder_core.h's own, compiled for the host (its sine and cosine in double, rounded once: the host has no sincospif).
 //   emu_vocoder        (B, n_stft, T) complex64 in bin order -> (B, n_stft, T_out), every bin with its advance frac(hop k / D)
+//   emu_voc_step       the frame pair and the weight of one output step (voc_step), for tests/test_vocoder_cpu.py to hold to i * rate
 //   emu_vocoder_slots  rows of T frames of `stride` complex slots -> rows of T_out frames, position by position as the kernel does it,
 //                      from the table rfx_debug_vocoder_table answers (bin's primary position, signed advance, conjugate flag)
 // rate == 1 copies, as the drivers do.  Built by tests/test_vocoder_cpu.py with -ffp-contract=off.
@@ -16,6 +17,9 @@ extern "C" {
 long long emu_voc_frames(int T, double rate) { return rfx::voc_frames(T, rate); }
 
 float emu_voc_advance(int hop, int k, int n_stft) { return rfx::voc_advance_turns(hop, k, n_stft); }
+
+// the frame pair of step i: i0 = floor((double)i * rate), clamped below 2^31 - 1, and alpha, the weight of frame i0 + 1
+int emu_voc_step(int i, double rate, float* alpha) { return rfx::voc_step(i, rate, alpha); }
 
 int emu_vocoder(int n_stft, int hop, int B, int T, double rate, const float* X, float* Y) {
   const long long n = rfx::voc_frames(T, rate);

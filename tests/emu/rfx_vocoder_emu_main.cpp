@@ -15,6 +15,7 @@
 extern "C" {
 long long emu_voc_frames(int T, double rate);
 float emu_voc_advance(int hop, int k, int n_stft);
+int emu_voc_step(int i, double rate, float* alpha);
 int emu_vocoder(int n_stft, int hop, int B, int T, double rate, const float* X, float* Y);
 int emu_vocoder_slots(int stride, const int32_t* src, const float* adv, const uint8_t* conj, int rows, int T, double rate, const float* X,
                       float* Y);
@@ -89,6 +90,12 @@ int main() {
   CHECK(emu_voc_frames(41, 0.0) == -1 && emu_voc_frames(41, -1.0) == -1 && emu_voc_frames(0, 1.25) == -1);
   CHECK(emu_voc_frames(41, std::nan("")) == -1 && emu_voc_frames(41, INFINITY) == -1 && emu_voc_frames(2147483647, 0.5) == -1);
   CHECK(emu_voc_frames(2147483647, 1.0) == 2147483647LL);
+  // a step's pair: the floor of the double product; a product past 2^31 is clamped before the conversion (no undefined cast), a NULL alpha is allowed
+  float al = -1.f;
+  CHECK(emu_voc_step(21, 2.0 / 3.0, &al) == 14 && al == 0.f);
+  CHECK(emu_voc_step(7, 0.3, &al) == 2 && al == (float)(7 * 0.3 - 2.0));
+  CHECK(emu_voc_step(1000, 1e7, &al) == 2147483646 && al == 0.f);
+  CHECK(emu_voc_step(2147483647, 1e300, nullptr) == 2147483646);
   CHECK(rfx::voc_wrap(0.75f) == -0.25f && rfx::voc_wrap(-0.75f) == 0.25f && rfx::voc_wrap(0.5f) == 0.5f && rfx::voc_wrap(-0.5f) == -0.5f);
   if (failures) return 1;
   std::printf("ok\n");

@@ -8,6 +8,11 @@ Composition, bit for bit, at n_steps +2, -5 and 0: Plan.pitch_shift(w, n) equals
 made of the separate members on all rows at once (n = 0: the input's bits); the same for one row more than a row group, the group's
 size read from the workspace query; SpectrogramConverter.pitch_shift equals it for a (1, 3, L) host input.  The output has the
 input's shape.
+The routes beside those: shifts too small to move the frequency (n_steps = +1e-9: int(sample_rate / rate) == sample_rate, the fused
+entry copies the stretched rows with other row pitches and reads no table - NULL tables accepted, canaries stay; n_steps = -1e-9:
+44099 -> 44100, 44100 phases, composition in bits and the chain gate), at 40 hops and at 41 hops less a sample; the octaves +-12 on
+the four engines (the vocoder at exactly 0.5 and 2.0, the resampler at 2/1 and 1/2: bits and the chain gate); +-24 (4/1, 1/4) and
+0.5 on the specialised engine in bits.
 Direction: a 440 Hz sine shifted by +12 on the specialised engine has its spectral peak within one bin of 880 Hz.
 PARITY against the float64 chain oracle STFT -> tests/vocoder_oracle.py -> torch.istft -> tests/resample_oracle.py, printed for the
 whole rows and gated on the samples outside the stated departure (where round(Lw / rate) exceeds the stretched row, torch.istft keeps
@@ -53,6 +58,8 @@ def _composition(plan, w, n_steps):
     rate, len_stretch, orig = _terms(plan.sample_rate, w.shape[1], n_steps)
     assert orig == plan.lib.rfx_pitch_shift_resample_freq(plan.handle, w.shape[1], float(n_steps), 12)
     stretched = _fix(plan.time_stretch(w, rate), len_stretch).contiguous()
+    if orig == plan.sample_rate:  # a shift too small to move int(sample_rate / rate): torchaudio's resample returns its input
+        return _fix(stretched, w.shape[1]).contiguous()
     return _fix(_hip.resample_sinc(stretched, orig, plan.sample_rate), w.shape[1]).contiguous()
 
 
@@ -80,6 +87,21 @@ def _chain(O, w, op, sr, n_steps, dtype):
     return _fix(r, Lw), Ls, len_stretch, orig
 
 
+def _chain_parity(O, name, plan, op, w, n_steps):
+    """the chain gate on rows w (the last one zero): dev >= f32 - 6 dB on the samples outside the stated departure; returns their count"""
+    sr, Lw = plan.sample_rate, w.shape[1]
+    r64, Ls, len_stretch, orig = _chain(O, w.cpu(), op, sr, n_steps, torch.float64)
+    r32 = _chain(O, w.cpu(), op, sr, n_steps, torch.float32)[0]
+    got = plan.pitch_shift(w, n_steps).cpu()
+    o, n, base, _ = RO.geometry(orig, sr)
+    clear = Lw if len_stretch <= Ls else min(Lw, max(0, math.floor((Ls - 6 * o / base) * n / o)))  # outputs the departure cannot reach
+    d, f = snr_db(r64[:-1, :clear], got[:-1, :clear]), snr_db(r64[:-1, :clear], r32[:-1, :clear])
+    print(f"{name} n_steps {n_steps:+.3g}: {orig} -> {sr}, Ls {Ls}, len_stretch {len_stretch}, {clear} of {Lw} samples outside the departure: "
+          f"dev {d:.1f} dB, float32 chain {f:.1f} dB; whole rows: dev {snr_db(r64[:-1], got[:-1]):.1f} dB, float32 chain {snr_db(r64[:-1], r32[:-1]):.1f} dB")
+    assert d >= f - 6.0, (name, n_steps, d, f)
+    return clear
+
+
 @pytest.mark.parametrize("name", list(ENGINES))
 def test_member_is_the_composition_and_parity(O, name):
     p, plan = _plan(name)
@@ -94,16 +116,79 @@ def test_member_is_the_composition_and_parity(O, name):
         assert got.data_ptr() != w.data_ptr() and _bits(got) == _bits(want), n_steps
         assert not got[-1].any()
     for n_steps in STEPS[:2]:
-        r64, Ls, len_stretch, orig = _chain(O, w.cpu(), op, sr, n_steps, torch.float64)
-        r32 = _chain(O, w.cpu(), op, sr, n_steps, torch.float32)[0]
-        got = plan.pitch_shift(w, n_steps).cpu()
-        o, n, base, _ = RO.geometry(orig, sr)
-        clear = Lw if len_stretch <= Ls else min(Lw, max(0, math.floor((Ls - 6 * o / base) * n / o)))  # outputs the departure cannot reach
-        d, f = snr_db(r64[:-1, :clear], got[:-1, :clear]), snr_db(r64[:-1, :clear], r32[:-1, :clear])
-        print(f"{name} n_steps {n_steps:+d}: {orig} -> {sr}, Ls {Ls}, len_stretch {len_stretch}, {clear} of {Lw} samples outside the departure: "
-              f"dev {d:.1f} dB, float32 chain {f:.1f} dB; whole rows: dev {snr_db(r64[:-1], got[:-1]):.1f} dB, float32 chain {snr_db(r64[:-1], r32[:-1]):.1f} dB")
-        assert clear > Lw // 2
-        assert d >= f - 6.0, (name, n_steps, d, f)
+        assert _chain_parity(O, name, plan, op, w, n_steps) > Lw // 2
+
+
+@pytest.mark.parametrize("n_steps", [12, -12])
+@pytest.mark.parametrize("name", list(ENGINES))
+def test_octaves_on_every_engine(O, name, n_steps):
+    """the vocoder at exactly 0.5 and 2.0, the resampler at 2/1 and 1/2 (5512/11025 an octave down at 11025 Hz): composition in bits and the chain gate.  Rows of 41 frames; of
+    61 where the departure would leave no more than half of a 41-frame row clear."""
+    p, plan = _plan(name)
+    op = O.params_from(p)
+    for frames in (41, 61):
+        Lw = IO.samples(op, frames)
+        rate, len_stretch, orig = _terms(p.sample_rate, Lw, n_steps)
+        assert rate == 2.0 ** (-n_steps // 12)
+        if n_steps > 0 or p.sample_rate % 2 == 0:  # (an octave down at 11025 Hz: int(11025 / 2) = 5512 -> 11025, 5512 phases' worth of a pair)
+            assert RO.geometry(orig, p.sample_rate)[:2] == ((2, 1) if n_steps > 0 else (1, 2))
+        w = synthetic_wave(3, Lw, seed=25).cuda()
+        w[-1] = 0
+        got = plan.pitch_shift(w, n_steps)
+        assert _bits(got) == _bits(_composition(plan, w, n_steps)) and not got[-1].any()
+        clear = _chain_parity(O, name, plan, op, w, n_steps)
+        if clear > Lw // 2:
+            break
+    assert clear > Lw // 2
+
+
+@pytest.mark.parametrize("n_steps", [24, -24, 0.5])
+def test_two_octaves_and_a_quarter_tone(n_steps):
+    """rates 0.25 and 4 with the pairs 4/1 and 1/4, and a shift that is no whole semitone: composition in bits"""
+    p, plan = _plan("specialised")
+    Lw = p.hop_length * 40
+    w = synthetic_wave(3, Lw, seed=26).cuda()
+    w[-1] = 0
+    orig = _terms(p.sample_rate, Lw, n_steps)[2]
+    if abs(n_steps) == 24:
+        assert RO.geometry(orig, p.sample_rate)[:2] == ((4, 1) if n_steps > 0 else (1, 4))
+    got = plan.pitch_shift(w, n_steps)
+    assert tuple(got.shape) == (3, Lw) and bool(torch.isfinite(got).all()) and bool(got[:-1].abs().sum(1).gt(0).all())
+    assert _bits(got) == _bits(_composition(plan, w, n_steps)) and not got[-1].any()
+
+
+@pytest.mark.parametrize("extra", [0, 1], ids=["40-hops", "41-hops-less-a-sample"])
+def test_shifts_too_small_to_move_the_frequency(O, extra):
+    """n_steps = +1e-9: int(sample_rate / rate) == sample_rate, the resampler returns its input and the fused entry copies the
+    stretched rows (row pitches differ: the stretched row has a frame more) - no table is read, so NULL tables are accepted.
+    n_steps = -1e-9: the frequency is sample_rate - 1, the pair 44099 -> 44100 of 44100 phases."""
+    p, plan = _plan("specialised")
+    op = O.params_from(p)
+    lib, h, sr = plan.lib, plan.handle, p.sample_rate
+    Lw = p.hop_length * 40 + extra * (p.hop_length - 1)
+    w = synthetic_wave(3, Lw, seed=27).cuda()
+    w[-1] = 0
+    # the copy route
+    up = 1e-9
+    assert lib.rfx_pitch_shift_resample_freq(h, Lw, up, 12) == sr == _terms(sr, Lw, up)[2]
+    want = _composition(plan, w, up)
+    got = plan.pitch_shift(w, up)
+    assert tuple(got.shape) == (3, Lw) and _bits(got) == _bits(want) and not got[-1].any() and bool(got[:-1].abs().sum(1).gt(0).all())
+    assert _bits(got) != _bits(w)  # (the vocoder ran: no copy of the input)
+    need = lib.rfx_pitch_shift_workspace_bytes(h, 3, Lw, up, 12)
+    assert need > 0
+    ws = torch.zeros(need, dtype=torch.uint8, device="cuda")
+    out = torch.full((3 * Lw + 16,), 7.0, device="cuda")  # 16 canary values behind the samples
+    s = torch.cuda.current_stream().cuda_stream
+    assert lib.rfx_pitch_shift(h, w.data_ptr(), 3, Lw, up, 12, None, None, 0, out.data_ptr(), ws.data_ptr(), need, s) == 0, lib.rfx_last_error()
+    torch.cuda.synchronize()
+    assert bool((out[3 * Lw:] == 7.0).all()) and _bits(out[:3 * Lw]) == _bits(want)
+    # one hertz down: the pair of 44100 phases
+    down = -1e-9
+    assert lib.rfx_pitch_shift_resample_freq(h, Lw, down, 12) == sr - 1 == _terms(sr, Lw, down)[2]
+    got = plan.pitch_shift(w, down)
+    assert _bits(got) == _bits(_composition(plan, w, down)) and not got[-1].any()
+    assert _chain_parity(O, "specialised", plan, op, w, down) > Lw // 2
 
 
 def test_composition_where_the_stretched_row_is_padded():

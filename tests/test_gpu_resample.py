@@ -11,6 +11,14 @@ PARITY: every figure is an SNR against the float64 oracle, all printed.
 Bits: dev == the host emulator; a row alone == the row in the batch, also at B = 5, one row more than a thread's four; x * 2^+-40
 gives the result * 2^+-40 exactly; the zero row leaves as zeros; orig == new is a copy; an input delayed by o samples gives the output
 delayed by n; `audio_util.resample_waveform` is the same call with leading dimensions kept and a host input moved to the device.
+The wider cases (WIDE_CASES of tests/test_resample_cpu.py, with its inputs and its two sparse float32 figures): integer decimation 4/1
+and 12/1 (n = 1: one phase, every lane reads the same weight, up to 145 taps), 1/4 and 1/12 (o = 1), 3/2, and 44099/44100 and
+44100/44099 (the pairs a tiny pitch shift produces: 44100 and 44099 phases, far more than outputs) at L = 1, 2, 255, 1000; the filters
+(lowpass_filter_width, rolloff) = (1, 0.99), (16, 0.99), (64, 0.9476), (6, 1.0), (6, 0.5) at 55/49, 1/2, 2/1; 160/147 at K = 255 .. 258
+around a workgroup's 256 outputs.  Bits == the emulator, the two parity gates, the zero row, a row alone.  Row blocks: B = 4, 8, 9
+(one full block of a thread's four rows, two, two and a row) at 3/2 against the emulator in bits.  THE LAUNCH SEAM: 65535 * 4 + 5 rows
+of 8 samples at 1/2 - the second trip of launch_resample_sinc's loop over 65535 row blocks - rows on both sides of the seam equal the
+same rows resampled alone.
 Contract: canary values past the output stay; NULL pointers, bad frequencies, an overlap and a misalignment are -1 and a table past
 the cap -4, the output untouched; B = 0 is a no-op.
 """
@@ -19,15 +27,15 @@ import torch
 
 import resample_oracle as RO
 from helpers import snr_db
-from test_resample_cpu import LENGTHS, PAIRS, _bits, emu, gates, run_emu, wave  # noqa: F401  (emu is a fixture)
+from test_resample_cpu import LENGTHS, PAIRS, WIDE_CASES, WIDE_IDS, _bits, emu, gates, run_emu, wave, wide_gates  # noqa: F401  (emu is a fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-def _dev(x, orig, new):
+def _dev(x, orig, new, lpw=6, rolloff=0.99):
     from riffusion import _hip
 
-    y = _hip.resample_sinc(x.cuda(), orig, new)
+    y = _hip.resample_sinc(x.cuda(), orig, new, lpw, rolloff)
     assert y.dtype == torch.float32 and tuple(y.shape) == (x.shape[0], RO.frames(x.shape[1], orig, new))
     return y.cpu()
 
@@ -57,6 +65,48 @@ def test_parity_and_bits(emu, orig, new, L):
         assert _bits(_dev(x * 2.0 ** e, orig, new)) == _bits(y * 2.0 ** e), e
     yd = _dev(torch.nn.functional.pad(x, (o, 0)), orig, new)  # delayed by o samples: the output is delayed by n
     assert yd.shape[1] == y.shape[1] + n and _bits(yd[:, n:]) == _bits(y)
+
+
+@pytest.mark.parametrize("orig,new,L,lpw,rolloff", WIDE_CASES, ids=WIDE_IDS)
+def test_parity_and_bits_at_the_wide_cases(emu, orig, new, L, lpw, rolloff):
+    r64, f32, k64 = wide_gates(orig, new, L, lpw, rolloff)
+    x = wave(L)
+    y = _dev(x, orig, new, lpw, rolloff)
+    d = snr_db(r64[:-1], y[:-1])
+    print(f"{orig}/{new} L{L} lpw {lpw} rolloff {rolloff:.4g}: K {y.shape[1]}, dev {d:.1f} dB, all-float32 {f32:.1f} dB, float32-rounded kernel {k64:.1f} dB")
+    assert tuple(y.shape) == tuple(r64.shape) and torch.isfinite(y).all()
+    assert _bits(y) == _bits(run_emu(emu, x, orig, new, lpw=lpw, rolloff=rolloff))  # the emulator, bit for bit
+    assert d >= f32, (orig, new, L, d, f32)
+    assert d >= k64 - 6.0, (orig, new, L, d, k64)
+    assert not y[-1].any()  # the zero row leaves as zeros
+    for r in (0, 2):
+        assert _bits(_dev(x[r:r + 1], orig, new, lpw, rolloff)) == _bits(y[r:r + 1]), r
+
+
+@pytest.mark.parametrize("B", [4, 8, 9])
+def test_row_blocks_are_the_emulators(emu, B):
+    """one full block of a thread's four rows, two, two and a row: the last block's clamped rows are read and not stored"""
+    x = wave(1000, B=B, seed=2)
+    y = _dev(x, 3, 2)
+    assert _bits(y) == _bits(run_emu(emu, x, 3, 2))
+    assert not y[-1].any() and bool(y[:-1].abs().sum(1).gt(0).all())
+
+
+def test_rows_past_one_launch():
+    """65535 * 4 + 5 rows: the kernel's second launch starts at row 262140 with its pointers moved on"""
+    from riffusion import _hip
+
+    B, L = 65535 * 4 + 5, 8
+    x = torch.randn(B, L, generator=torch.Generator().manual_seed(4321), dtype=torch.float32).cuda()  # every row its own content
+    y = _hip.resample_sinc(x, 1, 2)
+    assert tuple(y.shape) == (B, 16)
+    print(f"{B} rows: {x.numel() * 4 / 2 ** 20:.1f} MiB in, {y.numel() * 4 / 2 ** 20:.1f} MiB out")
+    for r in (0, 262139, 262140, 262141, B - 1):
+        alone = _hip.resample_sinc(x[r:r + 1], 1, 2)
+        assert bool(alone.any()) and _bits(alone.cpu()) == _bits(y[r:r + 1].cpu()), r
+    # ... and every row: two calls of fewer rows than one launch takes, the cut away from the seam
+    halves = torch.cat([_hip.resample_sinc(x[:200000], 1, 2), _hip.resample_sinc(x[200000:], 1, 2)])
+    assert torch.equal(halves.view(torch.int32), y.view(torch.int32))
 
 
 def test_equal_frequencies_copy_and_the_wrapper():

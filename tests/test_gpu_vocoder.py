@@ -15,13 +15,26 @@ The kernel, through pack_complex -> Plan.phase_vocoder -> unpack_complex.  Every
 Bits: pack_complex(unpack_complex(out)) == out - both slots of a doubled bin agree, conjugate slots are conjugates, padding is zero;
 a row alone equals the row in the batch; rate = 1 is a copy; the zero row leaves as zeros.
 
+The wide rates (RATES_WIDE of tests/test_vocoder_cpu.py: bpm ratios with near-integer products, rates >= 2, <= 0.5 and >= T), T = 41 on
+the four engines, T = 3 and T = 1 on two; the oracle's step positions are the double products i * rate, the header's definition.  The
+same gates and bits; X * 2^+-40 at 3.0 and 0.125 only.  T_out = 1 is gated against the emulator alone (dev >= emu - 6 dB) and its
+distance to o32 printed (-2.3 to -2.6 dB): the emulator itself is 4 - 5 dB below an o32 at float32's rounding floor, and the CPU test
+carries that gate.  The structured input and the noise-free analysis of tests/test_vocoder_cpu.py with both gates, on the whole and
+per slice; there a figure is capped at the float64 oracle's own rounding floor (319.1 dB) before the device is held to it - on the
+special bins at rate 3 the device's exact zeros score 319.5 dB, the oracle's own sin(pi), where the emulator repeats the oracle's
+error and scores 464.  THE LAUNCH SEAM: 65536 + 7 rows of two frames - the second trip of launch_vocoder's loop over 65535 rows - rows
+on both sides of the seam equal the same rows stretched alone.
+
 The member: Plan.time_stretch(w, rate) equals Plan.istft(Plan.phase_vocoder(Plan.stft(w))) bit for bit, for B = 3 and for one row more
 than a row group (the group's size read from the workspace query); SpectrogramConverter.time_stretch equals it for a (1, 3, L) input
-and under `length=`.  Its figure against the float64 chain stft -> oracle vocoder -> istft is printed and NOT gated: the analysis'
+and under `length=`; rates 1.25, 0.9, 1, 2/3 and 3.  A 440 Hz sine stretched at 2/3 and 3 keeps its spectral peak within one bin of
+440 Hz.  Its figure against the float64 chain stft -> oracle vocoder -> istft is printed and NOT gated: the analysis'
 rounding of near-silent bins feeds angle(), and the float32 chain differs there as well.
 
 Contract: a workspace one byte short is -3, NULL pointers are -1, canary bytes past both outputs stay, B = 0 is a no-op.
 """
+import math
+
 import pytest
 import torch
 
@@ -29,7 +42,8 @@ import istft_oracle as IO
 import vocoder_oracle as VO
 from helpers import snr_db, synthetic_wave
 from test_gpu_loop_decode import ENGINES, _bits, _plan
-from test_vocoder_cpu import RATES, O, _vr, emu, oracle_figures, run_emu, spectrogram  # noqa: F401  (O and emu are fixtures)
+from test_vocoder_cpu import (RATES, RATES_WIDE, REF_FLOOR_DB, SINE_RATES, STRUCTURED_RATES, WIDE_IDS, WIDE_SHAPES, O, _vr, emu, oracle_figures, oracle_pair,  # noqa: F401
+                              run_emu, sine_analysis, spectrogram, structured)  # (O and emu are fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +90,95 @@ def test_kernel_parity_scale_and_bits(O, emu, name, B, T):
     assert Tout == T and copy.data_ptr() != slots.data_ptr() and _bits(copy) == _bits(slots)
 
 
+@pytest.mark.parametrize("name,T", WIDE_SHAPES, ids=WIDE_IDS)
+def test_kernel_parity_at_the_wide_rates(O, emu, name, T):
+    """RATES_WIDE at T = 41 on the four engines, at T = 3 and T = 1 on two.  T_out = 1 is gated against the emulator alone: the emulator
+    itself sits 5 dB below a float32 oracle that is at float32's rounding floor (the CPU test carries that gate), which leaves no
+    room to ask 6 dB of the device's atan2f / hypotf / sincospif as well; its distance to o32 is printed."""
+    _, plan = _plan(name)
+    _, op, X = spectrogram(O, name, 3, T)
+    for rate in RATES_WIDE:
+        r64, o32 = oracle_figures(O, name, 3, T, rate)
+        e = snr_db(_vr(r64), _vr(run_emu(emu, X, op.hop_length, rate)))
+        out, Y = _stretch(plan, X, rate)
+        d = snr_db(_vr(r64), _vr(Y))
+        print(f"{name} T{T} rate {rate:.4g}: T_out {Y.shape[-1]}, dev {d:.1f} dB, o32 {o32:.1f} dB ({d - o32:+.1f}), emu {e:.1f} dB")
+        assert tuple(Y.shape) == tuple(r64.shape) and torch.isfinite(_vr(Y)).all()
+        if Y.shape[-1] > 1:
+            assert d >= o32 - 6.0, (name, T, rate, d, o32)
+        assert d >= e - 6.0, (name, T, rate, d, e)
+        assert _bits(plan.pack_complex(Y.cuda())) == _bits(out), rate
+        assert not _vr(Y[-1]).any()
+        for r in (0, 2):
+            assert _bits(_stretch(plan, X[r:r + 1], rate)[1]) == _bits(Y[r:r + 1]), (rate, r)
+        if rate in (3.0, 0.125):  # the scaled runs, at one rate above 2 and one below 1/2 only
+            for s in (-40, 40):
+                Ys = _stretch(plan, X * 2.0 ** s, rate)[1]
+                assert torch.isfinite(_vr(Ys)).all()
+                ds = snr_db(_vr(r64), _vr(Ys).double() * 2.0 ** -s)
+                print(f"    X * 2^{s}: dev {ds:.1f} dB")
+                assert (ds >= o32 - 6.0 or Y.shape[-1] == 1) and ds >= e - 6.0, (name, T, rate, s, ds, o32, e)
+
+
+def test_kernel_parity_on_structured_input(O, emu):
+    _, plan = _plan("specialised")
+    op, X, slices = structured(O)
+    for rate in STRUCTURED_RATES:
+        r64, r32 = oracle_pair(X, rate, op.hop_length)
+        E = run_emu(emu, X, op.hop_length, rate)
+        out, Y = _stretch(plan, X, rate)
+        assert tuple(Y.shape) == tuple(r64.shape) and torch.isfinite(_vr(Y)).all() and not _vr(Y[-1]).any()
+        for what, at in [("whole", (slice(None), slice(None)))] + list(slices.items()):
+            d, e, o32 = snr_db(_vr(r64[at]), _vr(Y[at])), snr_db(_vr(r64[at]), _vr(E[at])), snr_db(_vr(r64[at]), _vr(r32[at]))
+            print(f"structured rate {rate:.4g}, {what}: dev {d:.1f} dB, o32 {o32:.1f} dB, emu {e:.1f} dB")
+            assert d >= o32 - 6.0, (rate, what, d, o32)
+            assert d >= min(e, REF_FLOOR_DB) - 6.0, (rate, what, d, e)  # (capped at the float64 oracle's own rounding floor, 319.1 dB)
+        i0 = VO.pairs(41, rate)[0]
+        both = (i0 >= 10) & (i0 + 1 <= 19)  # a step whose two frames are both zero leaves with magnitude exactly 0
+        assert bool(both.any()) and not _vr(Y[0][:, both]).any(), rate
+        assert _bits(plan.pack_complex(Y.cuda())) == _bits(out), rate
+        for r in (0, 1):
+            assert _bits(_stretch(plan, X[r:r + 1], rate)[1]) == _bits(Y[r:r + 1]), (rate, r)
+
+
+def test_kernel_parity_on_a_noise_free_analysis(O, emu):
+    _, plan = _plan("specialised")
+    op, X = sine_analysis(O)
+    for rate in SINE_RATES:
+        r64, r32 = oracle_pair(X, rate, op.hop_length)
+        e, o32 = snr_db(_vr(r64), _vr(run_emu(emu, X, op.hop_length, rate))), snr_db(_vr(r64), _vr(r32))
+        Y = _stretch(plan, X, rate)[1]
+        d = snr_db(_vr(r64), _vr(Y))
+        print(f"440 Hz sine rate {rate:.4g}: dev {d:.1f} dB, o32 {o32:.1f} dB, emu {e:.1f} dB")
+        assert tuple(Y.shape) == tuple(r64.shape) and torch.isfinite(_vr(Y)).all()
+        assert d >= o32 - 6.0 and d >= e - 6.0, (rate, d, o32, e)
+
+
+def test_rows_past_one_launch():
+    """65536 + 7 rows of two frames at rate 0.75: the kernel's second launch starts at row 65535 with its pointers moved on.  The
+    engine is the one of the four with the smallest frame whose input plus output stay below 4 GiB; the noise is made in slot layout
+    on the device and passed through unpack -> pack once, so that the slots of a frame are consistent."""
+    B, T, rate = 65536 + 7, 2, 0.75
+    Tout = VO.frames(T, rate)
+    assert Tout == 3
+    for name in sorted(ENGINES, key=lambda n: _plan(n)[1].frame_stride):
+        plan = _plan(name)[1]
+        total = B * (T + Tout) * plan.frame_stride * 8
+        print(f"{name}: frame_stride {plan.frame_stride}, {B} rows: {B * T * plan.frame_stride * 8 / 2 ** 20:.0f} MiB in, {B * Tout * plan.frame_stride * 8 / 2 ** 20:.0f} MiB out")
+        if total <= 4 << 30:
+            break
+    else:
+        raise AssertionError("no engine's frames fit 4 GiB")
+    gen = torch.Generator(device="cuda").manual_seed(99)
+    slots = torch.view_as_complex(torch.randn((B * T, plan.frame_stride, 2), generator=gen, device="cuda", dtype=torch.float32))
+    slots = plan.pack_complex(plan.unpack_complex(slots, B, T))
+    out, n = plan.phase_vocoder(slots, B, T, rate)
+    assert n == Tout and tuple(out.shape) == (B * Tout, plan.frame_stride)
+    for r in (0, 1, 65534, 65535, 65536, B - 1):
+        alone, _ = plan.phase_vocoder(slots[r * T:(r + 1) * T], 1, T, rate)
+        assert bool(alone.abs().sum() > 0) and torch.equal(torch.view_as_real(alone).view(torch.int32), torch.view_as_real(out[r * Tout:(r + 1) * Tout]).view(torch.int32)), r
+
+
 def _composition(plan, w, rate):
     B = w.shape[0]
     _, spec, T = plan.stft(w, want_mag=False, want_spec=True)
@@ -98,7 +201,7 @@ def test_member_is_the_composition(O, name):
     Lw = IO.samples(op, 41)
     w = synthetic_wave(3, Lw, seed=11).cuda()
     w[-1] = 0
-    for rate in (1.25, 0.9, 1.0):
+    for rate in (1.25, 0.9, 1.0, 2 / 3, 3.0):
         want, T, Tout = _composition(plan, w, rate)
         got = plan.time_stretch(w, rate)
         assert T == 41 and tuple(got.shape) == (3, IO.samples(op, Tout)) == tuple(want.shape)
@@ -112,6 +215,22 @@ def test_member_is_the_composition(O, name):
         X32 = IO.stft(O, w.cpu(), op, torch.float32)
         o32 = IO.istft(O, VO.phase_vocoder(X32, rate, op.hop_length, torch.float32), op, torch.float32)
         print(f"{name} member rate {rate}: dev {snr_db(ref[:-1], plan.time_stretch(w, rate).cpu()[:-1]):.1f} dB, float32 chain {snr_db(ref[:-1], o32[:-1]):.1f} dB (not gated)")
+
+
+@pytest.mark.parametrize("rate", [2 / 3, 3.0], ids=["2/3", "3"])
+def test_member_keeps_a_sine_where_it_is(rate):
+    """a time stretch moves no frequency: the 440 Hz sine of tests/test_gpu_pitch_shift.py leaves with its spectral peak at 440 Hz"""
+    p, plan = _plan("specialised")
+    Lw, sr = p.hop_length * 40, p.sample_rate
+    t = torch.arange(Lw, dtype=torch.float64) / sr
+    w = (8000 * torch.sin(2 * math.pi * 440.0 * t)).float().reshape(1, Lw).cuda()
+    y = plan.time_stretch(w, rate).cpu().double()[0]
+    L = y.shape[0]
+    assert L == plan.time_stretch_samples(Lw, rate)
+    spec = torch.fft.rfft(y * torch.hann_window(L, dtype=torch.float64)).abs()
+    peak = float(spec.argmax()) * sr / L
+    print(f"rate {rate:.4g}: {L} samples, peak at {peak:.1f} Hz (bins of {sr / L:.2f} Hz)")
+    assert bool(torch.isfinite(y).all()) and abs(peak - 440.0) <= sr / L
 
 
 def test_member_over_two_row_groups_and_the_converter(O):

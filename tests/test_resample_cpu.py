@@ -16,6 +16,10 @@ csrc/rfx_resample_core.h).
   L = 5 (shorter than the filter), 2000 and 3001; B = 3, the last row all zero.  33037/44100 has no dense kernel (11.7 GB): its two
   float32 figures are the sparse float32 forms of tests/resample_oracle.py - the same kernels on the kept taps, a float32 sum in
   ascending order.  For the pairs that have both, the sparse figures are printed next to the dense ones.
+* THE WIDER CASES (WIDE_CASES, apart from PAIRS x LENGTHS): 4/1 and 12/1 (n = 1: one phase of 49 and 145 taps), 1/4 and 1/12 (o = 1),
+  3/2, 44099/44100 and 44100/44099 (44100 and 44099 phases) at L = 1, 2, 255, 1000; (lowpass_filter_width, rolloff) = (1, 0.99),
+  (16, 0.99), (64, 0.9476), (6, 1.0), (6, 0.5) at 55/49, 1/2 and 2/1, L = 1000 (3 to 271 taps); 160/147 at L = 277 .. 280, K = 255 .. 258
+  around a workgroup's 256 outputs.  The table assertions above, and the emulator's two gates against the sparse float32 forms.
 * Exact properties of the emulator: the zero row, a row alone, x * 2^+-40, the delay by o samples, a row read as zero past `valid`.
 * Refusals of the entries without a device; include/rfx.h as C99; the Python layers' refusals (kaiser, requires_grad, steps).
 * The emulator and a `main` of its own are also built as a stand-alone program with -fsanitize=address,undefined and run; nothing
@@ -40,6 +44,17 @@ DENSE_PAIRS = [(2, 1), (1, 2), (55, 49), (160, 147), (147, 160)]
 DENSE = DENSE_PAIRS + [(7787, 7350)]  # a dense kernel fits: 0.46 GB of float64 for the last
 PAIRS = DENSE + [(33037, 44100)]
 LENGTHS = [5, 2000, 3001]
+# The wider cases, kept apart from PAIRS x LENGTHS: (orig, new, L, lowpass_filter_width, rolloff)
+DEFAULT_FILTER = (6, 0.99)
+WIDE_PAIRS = [(4, 1), (12, 1), (1, 4), (1, 12), (3, 2), (44099, 44100), (44100, 44099)]  # n = 1: one phase; o = 1; far more phases than outputs
+WIDE_LENGTHS = [1, 2, 255, 1000]
+FILTER_PAIRS = [(55, 49), (1, 2), (2, 1)]
+FILTERS = [(1, 0.99), (16, 0.99), (64, 0.9475937167399596), (6, 1.0), (6, 0.5)]
+SEAM_LENGTHS = {277: 255, 278: 256, 279: 257, 280: 258}  # 160/147: K on both sides of a workgroup's 256 outputs
+WIDE_CASES = ([(o, n, L) + DEFAULT_FILTER for o, n in WIDE_PAIRS for L in WIDE_LENGTHS] + [(o, n, 1000) + f for o, n in FILTER_PAIRS for f in FILTERS]
+              + [(160, 147, L) + DEFAULT_FILTER for L in SEAM_LENGTHS])
+WIDE_IDS = [f"{o}/{n}-L{L}-lpw{lpw}-rolloff{ro:.4g}" for o, n, L, lpw, ro in WIDE_CASES]
+WIDE_TABLES = sorted({(o, n, lpw, ro) for o, n, _, lpw, ro in WIDE_CASES})
 _CACHE = {}
 
 
@@ -71,21 +86,31 @@ def wave(L, B=3, seed=0):
     return _CACHE[key]
 
 
-def table64(orig, new):
-    key = ("table", orig, new)
+def table64(orig, new, lpw=6, rolloff=0.99):
+    key = ("table", orig, new, lpw, rolloff)
     if key not in _CACHE:
-        _CACHE[key] = RO.sparse_table(orig, new)
+        _CACHE[key] = RO.sparse_table(orig, new, lpw, rolloff)
     return _CACHE[key]
 
 
-def sparse_figures(orig, new, L):
+def sparse_figures(orig, new, L, lpw=6, rolloff=0.99):
     """SNRs of the two sparse float32 forms against the float64 result"""
-    key = ("sfig", orig, new, L)
+    key = ("sfig", orig, new, L, lpw, rolloff)
     if key not in _CACHE:
-        x, tb = wave(L), table64(orig, new)
-        r64 = RO.sparse_resample(x, orig, new, table=tb)
-        _CACHE[key] = tuple(snr_db(r64[:-1], RO.sparse_resample_f32(x, orig, new, RO.sparse_weights(orig, new, dt, table=tb), tb)[:-1])
+        x, tb = wave(L), table64(orig, new, lpw, rolloff)
+        r64 = RO.sparse_resample(x, orig, new, lpw, rolloff, table=tb)
+        _CACHE[key] = tuple(snr_db(r64[:-1], RO.sparse_resample_f32(x, orig, new, RO.sparse_weights(orig, new, dt, lpw, rolloff, table=tb), tb)[:-1])
                             for dt in (torch.float32, torch.float64))
+    return _CACHE[key]
+
+
+def wide_gates(orig, new, L, lpw, rolloff):
+    """`gates` of a WIDE_CASES case: the float64 result and the two sparse float32 figures, as for 33037/44100 - these pairs either have
+    no dense kernel of sensible size or gain nothing from one"""
+    key = ("wfig", orig, new, L, lpw, rolloff)
+    if key not in _CACHE:
+        r64 = RO.sparse_resample(wave(L), orig, new, lpw, rolloff, table=table64(orig, new, lpw, rolloff))
+        _CACHE[key] = (r64,) + sparse_figures(orig, new, L, lpw, rolloff)
     return _CACHE[key]
 
 
@@ -103,12 +128,12 @@ def gates(orig, new, L):
     return _CACHE[key]
 
 
-def run_emu(emu, x, orig, new, valid=None):
+def run_emu(emu, x, orig, new, valid=None, lpw=6, rolloff=0.99):
     from riffusion import _hip
 
     if orig == new:
         return x.clone()
-    first, taps = _hip.resample_sinc_table(orig, new)
+    first, taps = _hip.resample_sinc_table(orig, new, lpw, rolloff)
     o, n, _, _ = RO.geometry(orig, new)
     x = x.contiguous()
     B, L = x.shape
@@ -151,15 +176,14 @@ def test_every_dropped_tap_is_below_1e_30(orig, new):
 
 # ---- the host entries ----------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("orig,new", PAIRS)
-def test_frames_and_table_are_the_oracles(emu, orig, new):
+def _frames_and_table(emu, orig, new, lpw=6, rolloff=0.99):
     from riffusion import _hip
 
     o, n, _, _ = RO.geometry(orig, new)
     for L in (1, 2, 5, 2000, 3001, 225351, 2 ** 24 + 1):
         assert _hip.resample_sinc_frames(L, orig, new) == RO.frames(L, orig, new) == emu.emu_rs_frames(L, orig, new), L
-    first64, count, w64 = table64(orig, new)
-    first, taps = _hip.resample_sinc_table(orig, new)
+    first64, count, w64 = table64(orig, new, lpw, rolloff)
+    first, taps = _hip.resample_sinc_table(orig, new, lpw, rolloff)
     assert first.dtype == np.int32 and taps.dtype == np.float32 and taps.shape == w64.shape == (int(count.max()), n)
     assert np.array_equal(first, first64)
     past = np.arange(taps.shape[0])[:, None] >= count[None, :]
@@ -171,8 +195,23 @@ def test_frames_and_table_are_the_oracles(emu, orig, new):
     # the emulator's table is the library's
     n2, nt2 = ctypes.c_int32(0), ctypes.c_int32(0)
     f2, t2 = np.zeros_like(first), np.zeros_like(taps)
-    assert emu.emu_rs_table(orig, new, 6, 0.99, f2.ctypes.data, t2.ctypes.data, ctypes.byref(n2), ctypes.byref(nt2)) == 0
+    assert emu.emu_rs_table(orig, new, lpw, rolloff, f2.ctypes.data, t2.ctypes.data, ctypes.byref(n2), ctypes.byref(nt2)) == 0
     assert (n2.value, nt2.value) == (n, taps.shape[0]) and f2.tobytes() == first.tobytes() and t2.tobytes() == taps.tobytes()
+    return taps.shape[0]
+
+
+@pytest.mark.parametrize("orig,new", PAIRS)
+def test_frames_and_table_are_the_oracles(emu, orig, new):
+    _frames_and_table(emu, orig, new)
+
+
+@pytest.mark.parametrize("orig,new,lpw,rolloff", WIDE_TABLES, ids=[f"{o}/{n}-lpw{w}-rolloff{r:.4g}" for o, n, w, r in WIDE_TABLES])
+def test_frames_and_table_of_the_wide_cases(emu, orig, new, lpw, rolloff):
+    """one phase (n = 1), o = 1, 44100 phases, and the filters other than 6 / 0.99: the same assertions"""
+    ntaps = _frames_and_table(emu, orig, new, lpw, rolloff)
+    print(f"{orig}/{new} lpw {lpw} rolloff {rolloff:.4g}: {RO.geometry(orig, new)[1]} phases of {ntaps} taps")
+    for L, K in SEAM_LENGTHS.items():
+        assert RO.frames(L, 160, 147) == K
 
 
 def test_every_semitone_shift_gets_a_table_below_the_cap():
@@ -270,6 +309,22 @@ def test_parity_of_the_emulator(emu, orig, new, L):
     assert not y[-1].any()  # the zero row leaves as zeros
     assert e >= f32, (orig, new, L, e, f32)
     assert e >= k64 - 6.0, (orig, new, L, e, k64)
+
+
+@pytest.mark.parametrize("orig,new,L,lpw,rolloff", WIDE_CASES, ids=WIDE_IDS)
+def test_parity_of_the_emulator_at_the_wide_cases(emu, orig, new, L, lpw, rolloff):
+    """the two gates of test_parity_of_the_emulator against the sparse float32 forms; several L = 1 and L = 2 cases are equalities"""
+    r64, f32, k64 = wide_gates(orig, new, L, lpw, rolloff)
+    x = wave(L)
+    y = run_emu(emu, x, orig, new, lpw=lpw, rolloff=rolloff)
+    e = snr_db(r64[:-1], y[:-1])
+    print(f"{orig}/{new} L{L} lpw {lpw} rolloff {rolloff:.4g}: K {y.shape[1]}, emu {e:.1f} dB, all-float32 {f32:.1f} dB, float32-rounded kernel {k64:.1f} dB")
+    assert tuple(y.shape) == tuple(r64.shape) == (3, RO.frames(L, orig, new)) and torch.isfinite(y).all()
+    assert not y[-1].any()  # the zero row leaves as zeros
+    assert e >= f32, (orig, new, L, e, f32)
+    assert e >= k64 - 6.0, (orig, new, L, e, k64)
+    for r in (0, 2):
+        assert _bits(run_emu(emu, x[r:r + 1], orig, new, lpw=lpw, rolloff=rolloff)) == _bits(y[r:r + 1]), r
 
 
 @pytest.mark.parametrize("orig,new", PAIRS)
