@@ -1,6 +1,16 @@
 """Shared helpers of the test-suite (seeded synthetic inputs of SURVEY.md 8(d), SNR)."""
+import os
+
 import numpy as np
 import torch
+
+
+def oracle():
+    """the CPU oracle (oracle/riffusion_oracle.py), with torch's thread pool sized for the comparisons the tests run on it"""
+    import riffusion_oracle
+
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    return riffusion_oracle
 
 
 def snr_db(ref: torch.Tensor, x: torch.Tensor) -> float:

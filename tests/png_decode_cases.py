@@ -10,19 +10,18 @@ import glob
 import io
 import os
 import struct
-import subprocess
-import tempfile
 import zlib
 
 import numpy as np
 from PIL import Image
 
 import deflate_writer as dw
+import emu_build
 from riffusion.util import image_util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_png_dec_emu.cpp")
+EMU_SRC = "rfx_png_dec_emu.cpp"
 SIZES = [(1, 1), (1, 2), (2, 3), (3, 5), (31, 7), (33, 50), (70, 87)]
 BPP = {0: 1, 2: 3, 3: 1, 6: 4}
 
@@ -30,9 +29,7 @@ BPP = {0: 1, 2: 3, 3: 1, 6: 4}
 # ---- the emulator -----------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=1)
 def emu():
-    so = os.path.join(tempfile.mkdtemp(prefix="png_dec_emu"), "librfx_png_dec_emu.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-std=c++17"))
     lib.emu_png_dec_workspace_bytes.restype = ctypes.c_int64
     lib.emu_png_dec_workspace_bytes.argtypes = [ctypes.c_int] * 4
     lib.emu_png_dec_inflate_shared_bytes.restype = ctypes.c_int64
@@ -63,7 +60,7 @@ def emu_decode(streams, H, W, color_type, palettes=None, entries=None):
     ws = np.zeros(max(1, lib.emu_png_dec_workspace_bytes(n, H, W, color_type)), np.uint8)
     rc = lib.emu_png_decode_batch(data.ctypes.data, offsets.ctypes.data, n, H, W, color_type, pal.ctypes.data, ent.ctypes.data, rgb.ctypes.data,
                                   status.ctypes.data, ws.ctypes.data)
-    assert rc == 0
+    assert rc == 0, rc
     return rgb, status
 
 
@@ -163,7 +160,7 @@ def device_writer_file(stream_of, rgb, mode):
 
 # ---- hand-built streams: one row of grey pixels behind a filter byte 0, so that any bytes are an image ----------------------------------
 def _one_row_file(body, raw):
-    assert raw[0] == 0 and len(raw) >= 2
+    assert raw[0] == 0 and len(raw) >= 2, (raw[0], len(raw))
     return image_util.png_file(len(raw) - 1, 1, 1, dw.zlib_stream(body, raw))
 
 

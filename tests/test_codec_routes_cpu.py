@@ -12,12 +12,12 @@ import pytest
 import torch
 from PIL import Image
 
+from jpeg_cases import _random
+from jpeg_decode_cases import _emu, pillow_jpeg
 from riffusion import _hip
 from riffusion.spectrogram_image_converter import SpectrogramImageConverter
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import image_util
-from test_jpeg_cpu import _random
-from test_jpeg_decode_cpu import _emu, pillow_jpeg
 
 
 class EmuPlan:

@@ -6,12 +6,11 @@ tests/emu/rfx_compress_emu.cpp) against the host, in both forms of the recurrenc
 """
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 from riffusion.util import audio_util
 from riffusion.util.audio_util import PcmSegment
 
@@ -20,7 +19,6 @@ try:
 except ImportError:  # pragma: no cover
     _ao = None
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I16P = ctypes.POINTER(ctypes.c_int16)
 U16P = ctypes.POINTER(ctypes.c_uint16)
 U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -204,11 +202,8 @@ def test_gain10_table_equals_pydub_expressions():
 
 # ---- the emulated kernels against the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("compress_emu") / "librfx_compress_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_compress_emu.cpp")],
-                   check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared("rfx_compress_emu.cpp", "-ffp-contract=off"))
     lib.emu_window_rms.argtypes = [I16P, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, U16P]
     lib.emu_attenuation.argtypes = [U16P, ctypes.c_int64, U8P, F64P, F64P, F64P, ctypes.c_int, ctypes.c_int64, F64P]
     lib.emu_attenuation.restype = ctypes.c_int

@@ -10,10 +10,11 @@ in tests/test_gen_core.py.  Every case prints what it measures; profiles/chirpz.
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+import emu_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FP = ctypes.POINTER(ctypes.c_float)
@@ -22,10 +23,8 @@ RADICES = {2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16}
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("cztemu") / "librfx_czt_emu.so")
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_czt_emu.cpp")], check=True)
-    return ctypes.CDLL(so)
+def emu():
+    return ctypes.CDLL(emu_build.shared("rfx_czt_emu.cpp"))
 
 
 def fft_len(n_fft):

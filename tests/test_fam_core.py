@@ -7,10 +7,11 @@ host with tests/emu/rfx_fam_emu.cpp, which loops the logical threads phase by ph
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+import emu_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FP = ctypes.POINTER(ctypes.c_float)
@@ -18,10 +19,8 @@ IP = ctypes.POINTER(ctypes.c_int)
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("famemu") / "librfx_fam_emu.so")
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_fam_emu.cpp")], check=True)
-    return ctypes.CDLL(so)
+def emu():
+    return ctypes.CDLL(emu_build.shared("rfx_fam_emu.cpp"))
 
 
 RATES = [48000, 32000, 24000, 16000, 8000, 44100, 22050]
@@ -123,4 +122,3 @@ def test_streamed_radix_24_pass_equals_the_plain_one_bit_for_bit(emu):
         emu.emu_fam_set_stream(1, 0)
     assert np.array_equal(res[(0, 0)][0].view(np.uint32), res[(1, 1)][0].view(np.uint32))
     assert np.array_equal(res[(0, 0)][1].view(np.uint32), res[(1, 1)][1].view(np.uint32))
-

@@ -5,23 +5,20 @@ by phase.  Every butterfly, twiddle, index map and the slot <-> bin corresponden
 numpy's FFT here, before any GPU time is spent.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import emu_build
+
 FP = ctypes.POINTER(ctypes.c_float)
 IP = ctypes.POINTER(ctypes.c_int)
 N, W, H = 17640, 4410, 441
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu") / "librfx_emu.so")
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_emu.cpp")], check=True)
-    return ctypes.CDLL(so)
+def emu():
+    return ctypes.CDLL(emu_build.shared("rfx_emu.cpp"))
 
 
 @pytest.fixture(scope="module")

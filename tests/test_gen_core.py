@@ -5,22 +5,19 @@ geometry the reference can be asked for (sample rate x the default 400 / 100 / 1
 compared with numpy's real FFT before any GPU time is spent.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import emu_build
+
 FP = ctypes.POINTER(ctypes.c_float)
 IP = ctypes.POINTER(ctypes.c_int)
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("genemu") / "librfx_gen_emu.so")
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_gen_emu.cpp")], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared("rfx_gen_emu.cpp"))
     lib.emu_gen_gl_update.argtypes = [FP, FP, ctypes.c_float, ctypes.c_float, FP]
     return lib
 

@@ -10,17 +10,14 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
+from helpers import oracle, snr_db, synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 @pytest.fixture(scope="module")

@@ -5,13 +5,11 @@ an even n_fft at the reference's default durations (42.57 kHz: 17028 = 4 * 9 * 1
 (4.73 kHz: 1892 = 4 * 11 * 43, win 473, hop 47) and an odd, prime one with win == n_fft (10.09 kHz at 100 / 100 ms: 1009).
 Gates are the generic engine's (tests/test_gpu_generic_geometry.py).
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from helpers import mask_ill_conditioned_bins, snr_db, synthetic_tiles_u8, synthetic_wave
+from helpers import mask_ill_conditioned_bins, oracle, snr_db, synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
@@ -24,10 +22,7 @@ GEOMETRIES = {
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _params(n_fft, **extra):

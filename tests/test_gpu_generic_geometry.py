@@ -4,13 +4,11 @@ spectrogram_params.py:62-81, and takes the rate from the input file, cli.py:43):
 (csrc/rfx_generic.hip) behind the same entry points.  Every stage is compared with the CPU oracle, and the generic engine
 is cross-checked against the specialised one on the default geometry.
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
+from helpers import oracle, snr_db, synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
@@ -19,10 +17,7 @@ RATES = [48000, 22050, 16000, 11025]  # 11.025 kHz (4410 / 1102 / 110) is in nei
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _params(**kw):

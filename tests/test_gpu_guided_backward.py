@@ -7,7 +7,7 @@ SpectrogramConverter.waveform_from_mel_amplitudes(..., inverse_mel="lstsq", guid
 Shapes, the smallest that can still go wrong: the default plan with B = 3, T = 37 (no multiple of 16 frames or 64 lanes; the slot
 cube with twice-held bins and padding), the same with mel_scale_norm = "slaney", one case on each other frame engine whose bank the
 closed form serves (row family at 48 kHz, generic at 11025 Hz; T >= 24 so that the guide outgrows the reflect padding), and the
-loop form on each of the three with T = 41 >= n_fft / hop, no multiple of 16.  The chirp-z plan of tests/test_gpu_loop_decode.py
+loop form on each of the three with T = 41 >= n_fft / hop, no multiple of 16.  The chirp-z plan of tests/engines.py
 has more filters than bins: the closed form does not serve it, so it takes the stage entry only.
 
 Inputs: seeded Gaussian guide rows (every bin's phase is well conditioned in float32), `_mel` of tests/test_gpu_imel_lstsq.py, a
@@ -21,14 +21,13 @@ edge (the positions float64 cannot decide for float32 pass no gradient, in all t
 import pytest
 import torch
 
+import guided_backward_cases as gcpu
+import imel_lstsq_bwd_cases as bcpu
+import imel_lstsq_cases as cpu
 import istft_oracle as IO
 import spec_loss_oracle as SLO
-import test_guided_backward_cpu as gcpu
-import test_imel_lstsq_bwd_cpu as bcpu
-import test_imel_lstsq_cpu as cpu
-from test_gpu_imel_lstsq import CANARY, _bits, _mel, _params
-from test_gpu_loop_decode import ENGINES
-from test_guided_backward_cpu import emu  # noqa: F401  (the module-scoped fixture that builds the host emulator)
+from engines import ENGINES
+from imel_lstsq_cases import CANARY, _bits, _mel, _params
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +41,11 @@ CASES = {  # name: (engine of ENGINES, SpectrogramParams keywords on top of the 
     "generic-11025-loop": ("generic-11025", dict(), 2, 41, True),
 }
 _cases = {}
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return gcpu.emulator()
 
 
 @pytest.fixture(scope="module")

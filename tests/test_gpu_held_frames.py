@@ -21,20 +21,11 @@ import torch
 
 import held_oracle
 import helpers
-from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
+from engines import B, CLIP2, ENGINES_BY_FORM as ENGINES, T, bits as _bits, plan_for as _plan, stft64 as _stft64
+from helpers import oracle, snr_db, synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
-CLIP2 = "clip_2_start_103694_ms_duration_5678_ms"
-B, T = 3, 33  # two whole groups of 16 frames plus one frame per row; lists that cross row boundaries
-
-ENGINES = {  # name: (rfx_plan_griffinlim_engine's answer, SpectrogramParams keywords, get_plan keywords)
-    "specialised-runs": ("specialised", dict(), dict(gl_form="runs")),
-    "specialised-frames": ("specialised", dict(), dict(gl_form="frames")),
-    "row-family-48k": ("row-family", dict(sample_rate=48000), dict()),
-    "generic-11025": ("generic", dict(sample_rate=11025, max_frequency=5512), dict()),
-    "chirp-z-1009": ("chirp-z", dict(sample_rate=10090, padded_duration_ms=100, window_duration_ms=100, max_frequency=4000), dict(frame_engine="chirp-z")),
-}
 HOLDS = [(0, 0), (7, 3), (33, 0)]      # nothing held, both ends held, everything held
 SPANS = [(12, 11), (7, 3), (0, 9)]     # rows with held-only samples at both ends, at the head, at the tail
 INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
@@ -42,30 +33,7 @@ INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
-
-
-def _plan(name):
-    from riffusion import _hip
-    from riffusion.spectrogram_params import SpectrogramParams
-
-    engine, kw, plan_kw = ENGINES[name]
-    p = SpectrogramParams(**kw)
-    plan = _hip.get_plan(p, "cuda", **plan_kw)
-    assert plan.griffinlim_engine == engine
-    return p, plan
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()
-
-
-def _stft64(x, op, O):
-    return torch.stft(x.double(), n_fft=op.n_fft, hop_length=op.hop_length, win_length=op.win_length, window=O.hann_window(op).double(),
-                      center=True, pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
+    return oracle()
 
 
 def _hold(pairs):

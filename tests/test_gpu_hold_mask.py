@@ -20,20 +20,17 @@ import numpy as np
 import pytest
 import torch
 
-import mask_oracle
 import helpers
-from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
-from test_gpu_held_frames import B, CLIP2, ENGINES, T, _bits, _plan, _stft64
+import mask_oracle
+from engines import B, CLIP2, ENGINES_BY_FORM as ENGINES, T, bits as _bits, plan_for as _plan, stft64 as _stft64
+from helpers import oracle, snr_db, synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _held(n_stft, frames=T):

@@ -20,38 +20,15 @@ import pytest
 import torch
 from PIL import Image
 
-import test_imel_lstsq_cpu as cpu
-from test_imel_lstsq_cpu import emu  # noqa: F401  (the module-scoped fixture that builds the host emulator)
+import imel_lstsq_cases as cpu
+from imel_lstsq_cases import CANARY, DEVICE_CASES as CASES, _bits, _mel, _params, _plan
 
 pytestmark = pytest.mark.gpu
 
-CASES = {
-    "default": (dict(), 3, 37),
-    "norm_slaney": (dict(mel_scale_norm="slaney"), 3, 37),
-    "8khz_64": (dict(sample_rate=8000, num_frequencies=64, max_frequency=4000), 2, 21),
-}
-CANARY = 4096
 
-
-def _params(**kw):
-    from riffusion.spectrogram_params import SpectrogramParams
-
-    return SpectrogramParams(**kw)
-
-
-def _plan(**kw):
-    from riffusion import _hip
-
-    return _hip.get_plan(_params(**kw), "cuda:0")
-
-
-def _bits(t: torch.Tensor) -> bytes:
-    return t.detach().cpu().contiguous().numpy().tobytes()
-
-
-def _mel(M, B, T, max_value=30e6, seed=3):
-    """B random uint8 tiles decoded as the image path does (B, M, T)"""
-    return torch.cat([cpu.image_mel(M, T, max_value=max_value, seed=seed + i) for i in range(B)]).contiguous()
+@pytest.fixture(scope="module")
+def emu():
+    return cpu.emulator()
 
 
 _cases = {}

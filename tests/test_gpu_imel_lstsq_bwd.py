@@ -17,14 +17,19 @@ import numpy as np
 import pytest
 import torch
 
+import imel_lstsq_bwd_cases as bcpu
+import imel_lstsq_cases as cpu
 import istft_oracle as IO
 import spec_loss_oracle as SLO
-import test_imel_lstsq_bwd_cpu as bcpu
-import test_imel_lstsq_cpu as cpu
-from test_gpu_imel_lstsq import CANARY, CASES, _bits, _mel, _params, _plan
-from test_imel_lstsq_bwd_cpu import emus  # noqa: F401  (the module-scoped fixture that builds the two host emulators)
+from imel_lstsq_cases import CANARY, DEVICE_CASES as CASES, _bits, _mel, _params, _plan
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def emus():
+    return bcpu.emulators()
+
 
 _cases = {}
 

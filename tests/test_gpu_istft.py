@@ -2,7 +2,7 @@
 The inverse spectrogram on the device (include/rfx.h, "INVERSE SPECTROGRAM": rfx_istft, rfx_istft_loop, rfx_istft_backward,
 rfx_istft_backward_loop; Plan.istft / istft_backward; SpectrogramConverter.waveform_from_spectrogram).
 
-Shapes: B = 3 rows of T = 41 frames on the four engines of tests/test_gpu_loop_decode.py (the chirp-z one gives the odd n_fft = 1009;
+Shapes: B = 3 rows of T = 41 frames on the four engines of tests/engines.py (the chirp-z one gives the odd n_fft = 1009;
 41 is the smallest T a loop takes on every engine and no multiple of 16); on the specialised engine also B = 5, T = 120, and loop at
 T = 40.  The last row is all zero.  X is the float64 oracle STFT of helpers.synthetic_wave rounded to complex64, with a seeded
 complex perturbation of the same size added (no consistent spectrogram: an edited one); g is a seeded randn.
@@ -17,14 +17,12 @@ The plain backward runs the zero-extension twin of the engine's forward frame ke
 twin on u padded with zeros to the period P' = hop ceil((L + n_fft) / hop).  The two must agree bit for bit, on all four engines (the
 chirp-z engine has a loop FORWARD transform, so nothing is skipped).
 """
-import os
-
 import pytest
 import torch
 
 import istft_oracle as IO
-from helpers import snr_db, synthetic_wave
-from test_gpu_loop_decode import ENGINES, LOOPING, _bits, _plan
+from engines import ENGINES, LOOPING, bits as _bits, plan_for as _plan
+from helpers import oracle, snr_db, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +33,7 @@ _CASES = {}
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _vr(x):

@@ -15,7 +15,7 @@ import torch
 from PIL import Image
 
 from helpers import synthetic_tiles_u8
-from test_jpeg_cpu import CONTENTS, QUALITIES, pillow_file
+from jpeg_cases import CONTENTS, QUALITIES, pillow_file
 
 pytestmark = pytest.mark.gpu
 

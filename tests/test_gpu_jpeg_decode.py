@@ -14,19 +14,12 @@ import pytest
 import torch
 from PIL import Image
 
-from test_jpeg_cpu import CONTENTS, STEREO_PNG, _golden, _random
-from test_jpeg_decode_cpu import DAMAGE_TILES, damaged_scans, pillow_jpeg, pillow_pixels
+from jpeg_cases import CONTENTS, STEREO_PNG, _golden, _random
+from jpeg_decode_cases import DAMAGE_TILES, _conv, _three, damaged_scans, pillow_jpeg, pillow_pixels
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(1, 1), (9, 17), (23, 37), (62, 33), (64, 96)]
-
-
-def _conv(stereo=False, **kw):
-    from riffusion.spectrogram_image_converter import SpectrogramImageConverter
-    from riffusion.spectrogram_params import SpectrogramParams
-
-    return SpectrogramImageConverter(SpectrogramParams(stereo=stereo, **kw), device="cuda")
 
 
 def _decode(files):
@@ -39,11 +32,6 @@ def _decode(files):
     rgb, status = plan.jpeg_decode([f[i.scan[0]:i.scan[1]] for f, i in zip(files, infos)], infos[0].height, infos[0].width,
                                    np.stack([i.qtables for i in infos]), np.stack([i.huffman for i in infos]))
     return rgb.cpu().numpy(), status
-
-
-def _three(h, w):
-    a = _random(h, w)
-    return [a, np.ascontiguousarray(a[::-1, ::-1] ^ 0x5A), np.repeat(a[:, :, :1] // 2, 3, axis=2)]
 
 
 @pytest.mark.parametrize("h,w", SIZES)

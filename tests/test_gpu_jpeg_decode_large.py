@@ -20,9 +20,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_jpeg_decode import _conv, _three
-from test_jpeg_decode_batch_cpu import (BAD_TABLES, L3_PLACES, Decoded, build_large, check_stages, emu, emu_batch, emulator_blocks, layout, one_image)
-from test_jpeg_decode_cpu import pillow_pixels
+from jpeg_decode_batch_cases import BAD_TABLES, Decoded, L3_PLACES, build_large, check_stages, emu, emu_batch, emulator_blocks, layout, one_image
+from jpeg_decode_cases import _conv, _three, pillow_pixels
 
 pytestmark = pytest.mark.gpu
 

@@ -21,8 +21,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_jpeg_decode_batch_cpu import BUILDERS, Decoded, build_case, check_stages, emu, emu_batch, layout
-from test_jpeg_decode_cpu import pillow_pixels
+from jpeg_decode_batch_cases import BUILDERS, Decoded, build_case, check_stages, emu, emu_batch, layout
+from jpeg_decode_cases import pillow_pixels
 
 pytestmark = pytest.mark.gpu
 

@@ -16,47 +16,21 @@ import numpy as np
 import pytest
 import torch
 
-import loop_oracle
 import helpers
-from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
+import loop_oracle
+from engines import CLIP2, LOOPING, bits as _bits, plan_for as _plan
+from helpers import oracle, snr_db, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
-CLIP2 = "clip_2_start_103694_ms_duration_5678_ms"
 B, T = 3, 41
-
-ENGINES = {  # name: (rfx_plan_griffinlim_engine's answer, SpectrogramParams keywords, get_plan keywords)
-    "specialised": ("specialised", dict(), dict()),
-    "row-family-48k": ("row-family", dict(sample_rate=48000), dict()),
-    "generic-11025": ("generic", dict(sample_rate=11025, max_frequency=5512), dict()),
-    "chirp-z-1009": ("chirp-z", dict(sample_rate=10090, padded_duration_ms=100, window_duration_ms=100, max_frequency=4000), dict(frame_engine="chirp-z")),
-}
-LOOPING = ["specialised", "row-family-48k", "generic-11025"]
 SHAPES = [(name, T) for name in LOOPING] + [("specialised", 40)]
 SHAPE_IDS = [f"{name}-T{t}" for name, t in SHAPES]
 
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
-
-
-def _plan(name):
-    from riffusion import _hip
-    from riffusion.spectrogram_params import SpectrogramParams
-
-    engine, kw, plan_kw = ENGINES[name]
-    p = SpectrogramParams(**kw)
-    plan = _hip.get_plan(p, "cuda", **plan_kw)
-    assert plan.griffinlim_engine == engine
-    return p, plan
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()
+    return oracle()
 
 
 _CASES = {}

@@ -17,12 +17,11 @@ import pytest
 import torch
 
 import loop_oracle
-from helpers import snr_db, synthetic_wave
-from test_gpu_loop_decode import ENGINES, _plan
+from engines import CLIP2, ENGINES, bits as _bits, plan_for as _plan
+from helpers import oracle, snr_db, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
-CLIP2 = "clip_2_start_103694_ms_duration_5678_ms"
 TILES = ["og_beat", "agile", "marim", "motorway", "vibes"]
 SHAPES = [(name, 3, 41) for name in ENGINES] + [("specialised", 3, 40), ("specialised", 5, 120)]
 SHAPE_IDS = [f"{name}-B{b}-T{t}" for name, b, t in SHAPES]
@@ -31,14 +30,7 @@ ALL = list(ENGINES)
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()
+    return oracle()
 
 
 _CASES = {}

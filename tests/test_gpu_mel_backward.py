@@ -2,7 +2,7 @@
 The forward path's backward on the device (include/rfx.h, "BACKWARD of the forward path": rfx_stft_backward,
 rfx_mel_scale_backward, rfx_mel_from_waveform_backward; riffusion/_autograd.py).
 
-Shapes are (engine, B, Lw): B = 3 rows of T = 41 frames on the four engines of tests/test_gpu_loop_decode.py; on the specialised
+Shapes are (engine, B, Lw): B = 3 rows of T = 41 frames on the four engines of tests/engines.py; on the specialised
 engine also B = 5, T = 120 (two frames per workgroup in the forward launch) and Lw = n_fft // 2 + 1 (both reflect partners reach
 every sample).  Inputs are helpers.synthetic_wave with the last row all zero, gradients come from a seeded torch.randn.
 
@@ -14,7 +14,6 @@ and requires dev >= o32 - 6 dB - max(0, fwd_o32 - fwd_dev).  The 6 dB is the rul
 tests; the second term lets the backward trail torch by as much as the forward already does on that input - the backward contains
 that forward, whose own distance the existing tests pin.  The four figures are printed.  The exact properties compare bits.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -22,18 +21,15 @@ import pytest
 import torch
 
 import mel_backward_oracle as MBO
-from helpers import snr_db, synthetic_wave
-from test_gpu_loop_decode import CLIP2, ENGINES, _bits, _plan
+from engines import CLIP2, ENGINES, bits as _bits, plan_for as _plan
+from helpers import oracle, snr_db, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _lw(name, frames):

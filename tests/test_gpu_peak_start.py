@@ -23,11 +23,12 @@ import torch
 import helpers
 import peak_start_inputs as inputs
 import peak_start_oracle
+from engines import CLIP2, bits as _bits
+from helpers import oracle
 
 pytestmark = pytest.mark.gpu
 
 TILES = ["og_beat", "vibes", "agile", "marim", "motorway"]
-CLIP2 = "clip_2_start_103694_ms_duration_5678_ms"
 
 ENGINES = {  # name: (rfx_plan_griffinlim_engine's answer, SpectrogramParams keywords, B, T)
     "specialised": ("specialised", dict(), 3, 37),
@@ -40,10 +41,7 @@ ENGINES = {  # name: (rfx_plan_griffinlim_engine's answer, SpectrogramParams key
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _plan(name):
@@ -55,10 +53,6 @@ def _plan(name):
     plan = _hip.get_plan(p, "cuda")
     assert plan.griffinlim_engine == engine and (name == "specialised") != bool(plan.generic)
     return p, plan, B, T
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()
 
 
 _CASES = {}

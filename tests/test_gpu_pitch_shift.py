@@ -1,6 +1,6 @@
 """
 The pitch shift on the device (include/rfx.h "PITCH SHIFT"; csrc/rfx_api_resample.hip) on the four frame engines of
-tests/test_gpu_loop_decode.py, rows of 41 frames, B = 3 with the last row all zero.
+tests/engines.py, rows of 41 frames, B = 3 with the last row all zero.
 
 Composition, bit for bit, at n_steps +2, -5 and 0: Plan.pitch_shift(w, n) equals
     time_stretch(w, 2^(-n / 12)) -> cut or zero-pad to round(Lw / rate) -> resample_sinc(int(sample_rate / rate) -> sample_rate)
@@ -31,12 +31,17 @@ import torch
 import istft_oracle as IO
 import resample_oracle as RO
 import vocoder_oracle as VO
-from helpers import snr_db, synthetic_wave
-from test_gpu_loop_decode import ENGINES, O, _bits, _plan  # noqa: F401  (O is a fixture)
+from engines import ENGINES, bits as _bits, plan_for as _plan
+from helpers import oracle, snr_db, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
 STEPS = [2, -5, 0]
+
+
+@pytest.fixture(scope="module")
+def O():
+    return oracle()
 
 
 def _fix(y, length):

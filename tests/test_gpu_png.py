@@ -15,7 +15,7 @@ import pytest
 import torch
 from PIL import Image
 
-from test_png_cpu import SIZES, STEREO_PNG, _tile, chunks, emu_stream
+from png_cases import SIZES, STEREO_PNG, _tile, chunks, emu_stream
 
 pytestmark = pytest.mark.gpu
 

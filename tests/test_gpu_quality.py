@@ -18,6 +18,8 @@ import pytest
 import torch
 from PIL import Image
 
+from helpers import oracle
+
 pytestmark = pytest.mark.gpu
 
 GIB = 1 << 30
@@ -38,15 +40,12 @@ GEOMETRIES = {
     "8k": dict(sample_rate=8000, max_frequency=4000),
     "odd3465": dict(sample_rate=34650, padded_duration_ms=100, window_duration_ms=100, max_frequency=8000),
 }
-ENGINES = {"44k": "specialised", "48k": "row-family", "8k": "row-family", "odd3465": "generic"}
+ENGINE_OF = {"44k": "specialised", "48k": "row-family", "8k": "row-family", "odd3465": "generic"}
 
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _params(**kw):
@@ -84,7 +83,7 @@ def _case(geom: str, which: str):
     key = (geom, which)
     if key not in _cases:
         plan = _plan(**GEOMETRIES[geom])
-        assert plan.griffinlim_engine == ENGINES[geom]
+        assert plan.griffinlim_engine == ENGINE_OF[geom]
         T = _smallest_T(plan) if which == "min" else 33
         B, L = 3, _samples(plan, T)
         assert L > plan.n_fft // 2 and plan.lib.rfx_stft_frames(plan.handle, L) == T

@@ -26,10 +26,16 @@ import pytest
 import torch
 
 import resample_oracle as RO
+from engines import bits as _bits
 from helpers import snr_db
-from test_resample_cpu import LENGTHS, PAIRS, WIDE_CASES, WIDE_IDS, _bits, emu, gates, run_emu, wave, wide_gates  # noqa: F401  (emu is a fixture)
+from resample_cases import LENGTHS, PAIRS, WIDE_CASES, WIDE_IDS, emulator, gates, run_emu, wave, wide_gates
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return emulator()
 
 
 def _dev(x, orig, new, lpw=6, rolloff=0.99):

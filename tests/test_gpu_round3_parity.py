@@ -19,7 +19,7 @@ import torch
 from PIL import Image
 from scipy.io import wavfile
 
-from helpers import snr_db, synthetic_tiles_u8, synthetic_wave
+from helpers import oracle, snr_db, synthetic_tiles_u8, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +28,7 @@ T_FULL = 512
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _plan(params, **kw):

@@ -8,13 +8,11 @@ squared |a| (zero phase factor once |a| > 1.8e19).  Now both work in a power of 
 the caller's magnitude_hint), which commutes with every rounding of the linear parts.  Everything goes through the C ABI; the
 oracle is the checker.
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from helpers import snr_db
+from helpers import oracle, snr_db
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +21,7 @@ MAX_VALUES = [1e-6, 1.0, 30e6, 1e12, 1e20]
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 @pytest.fixture(scope="module")

@@ -2,7 +2,7 @@
 The fused spectral losses on the device (include/rfx.h, "FUSED SPECTRAL LOSSES": rfx_spectral_loss, rfx_spectral_loss_backward and their
 loop forms; riffusion/_autograd.py: SpectralLossFunction; SpectrogramConverter.spectral_losses).
 
-Shapes: B = 3 rows of T = 41 frames on the four engines of tests/test_gpu_loop_decode.py, plain (Lw = hop * 40 + 17) and loop
+Shapes: B = 3 rows of T = 41 frames on the four engines of tests/engines.py, plain (Lw = hop * 40 + 17) and loop
 (Lw = hop * 41, all four engines); on the specialised engine also the loop minimum T = 40 and one plain batch that crosses the
 backward's 256 MiB group boundary (found from the size query; about 52 rows).  Inputs: helpers.synthetic_wave with the last row all
 zero; the target is the float64 oracle's magnitudes times a seeded U[0.5, 2) per bin, the silent row's target U[0, 1000);
@@ -19,15 +19,13 @@ Sums: num and den are Plan.spectral_error's bits; against numpy float64 on the d
 n 2^-52 relative and lsum within n 2^-52 + 4 * 2^-52 * sum(|ln a'| + |ln m'|) / lsum - the summation bound plus two logarithms per term at
 up to 2 ulp each (the device's and numpy's).  The exact properties compare bits.
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import spec_loss_oracle as SLO
-from helpers import snr_db, synthetic_wave
-from test_gpu_loop_decode import ENGINES, _bits, _plan
+from engines import ENGINES, bits as _bits, plan_for as _plan
+from helpers import oracle, snr_db, synthetic_wave
 
 pytestmark = pytest.mark.gpu
 
@@ -41,10 +39,7 @@ _CASES = {}
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 def _case(O, name, loop, frames):

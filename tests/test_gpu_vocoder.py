@@ -2,7 +2,7 @@
 The time stretch on the device (include/rfx.h, "TIME STRETCH": rfx_phase_vocoder, rfx_time_stretch; Plan.phase_vocoder / time_stretch;
 SpectrogramConverter.time_stretch_spectrogram / time_stretch).
 
-Shapes: B = 3 rows of T = 41 frames (no multiple of 16) and of T = 2 frames on the four engines of tests/test_gpu_loop_decode.py, and
+Shapes: B = 3 rows of T = 41 frames (no multiple of 16) and of T = 2 frames on the four engines of tests/engines.py, and
 B = 1, T = 512 on the specialised engine.  Inputs, oracle and emulator are those of tests/test_vocoder_cpu.py: X is seeded complex64
 noise over the oracle STFT of helpers.synthetic_wave, the last row all zero (B > 1); rates 1.25, 0.75, 1.1, 0.9.
 
@@ -40,12 +40,23 @@ import torch
 
 import istft_oracle as IO
 import vocoder_oracle as VO
-from helpers import snr_db, synthetic_wave
-from test_gpu_loop_decode import ENGINES, _bits, _plan
-from test_vocoder_cpu import (RATES, RATES_WIDE, REF_FLOOR_DB, SINE_RATES, STRUCTURED_RATES, WIDE_IDS, WIDE_SHAPES, O, _vr, emu, oracle_figures, oracle_pair,  # noqa: F401
-                              run_emu, sine_analysis, spectrogram, structured)  # (O and emu are fixtures)
+from engines import ENGINES, bits as _bits, plan_for as _plan
+from helpers import oracle, snr_db, synthetic_wave
+from vocoder_cases import (RATES, RATES_WIDE, REF_FLOOR_DB, SINE_RATES, STRUCTURED_RATES, WIDE_IDS, WIDE_SHAPES, _vr, emulator, oracle_figures,
+                           oracle_pair, run_emu, sine_analysis, spectrogram, structured)
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def O():
+    return oracle()
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return emulator()
+
 
 SHAPES = [(name, 3, T) for T in (41, 2) for name in ENGINES] + [("specialised", 1, 512)]
 SHAPE_IDS = [f"{name}-B{b}-T{t}" for name, b, t in SHAPES]

@@ -21,20 +21,16 @@ frame transform - the STFT of the staged guide, the synthesis adjoint G - and cl
 * The entries' null-argument refusals and queries without a GPU.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import imel_lstsq_bwd_cases as bcpu
+import imel_lstsq_cases as cpu
 import istft_oracle as IO
-import test_imel_lstsq_bwd_cpu as bcpu
-import test_imel_lstsq_cpu as cpu
-from test_imel_lstsq_bwd_cpu import emus  # noqa: F401  (the module-scoped fixture that builds the closed form's two host emulators)
+from guided_backward_cases import emu_project, emu_stage_rows, emulator, inputs, relu_guard, tables, torch_chain
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_guide_bwd_emu.cpp")
 CASES = {  # name: (SpectrogramParams keywords, B, T, loop)
     "default": (dict(), 2, 23, False),
     "8khz_64": (dict(sample_rate=8000, num_frequencies=64, max_frequency=4000), 2, 24, False),
@@ -50,82 +46,13 @@ def O():
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("guide_bwd_emu") / "librfx_guide_bwd_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
-    lib.emu_guide_stage_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    lib.emu_guide_project.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    return lib
+def emu():
+    return emulator()
 
 
-# ---- shared with the GPU tests ------------------------------------------------------------------------------------------------------
-def inputs(B, L, seed=23):
-    """seeded Gaussian guide rows (B, L) in about the units of a float waveform, and a seeded Gaussian g_w (B, L)"""
-    g = torch.Generator().manual_seed(seed + B + L)
-    return (0.1 * torch.randn((B, L), generator=g)).contiguous(), torch.randn((B, L), generator=g).contiguous()
-
-
-def tables(cp):
-    """(xpos_bin, s2x) of rfx_debug_guide_project_tables: int32 arrays of one frame's positions"""
-    from riffusion import _hip
-
-    lib = _hip.load_library()
-    n = ctypes.c_int32(0)
-    _hip.check(lib.rfx_debug_guide_project_tables(ctypes.byref(cp), None, None, 0, ctypes.byref(n)))
-    xpos_bin, s2x = np.full(n.value, -2, np.int32), np.full(n.value, -2, np.int32)
-    _hip.check(lib.rfx_debug_guide_project_tables(ctypes.byref(cp), xpos_bin.ctypes.data, s2x.ctypes.data, n.value, ctypes.byref(n)))
-    return xpos_bin, s2x
-
-
-def plain_tables(n_stft, stride):
-    """the tables of a plan with plain frames (position = bin), as every generic plan has them"""
-    t = np.full(stride, -1, np.int32)
-    t[:n_stft] = np.arange(n_stft, dtype=np.int32)
-    return t, t.copy()
-
-
-def emu_stage_rows(emu, guide, L):
-    """(B, Lg) float32 guide -> the (B, L) rows the backward's forward transform analyses"""
-    g = np.ascontiguousarray(guide.numpy(), dtype=np.float32)
-    out = np.full((g.shape[0], L), np.nan, np.float32)
-    emu.emu_guide_stage_rows(g.ctypes.data, g.shape[1], g.shape[0], L, out.ctypes.data)
-    return torch.from_numpy(out)
-
-
-def emu_project(emu, G, A, xpos_bin, s2x):
-    """G, A: (frames, stride) complex64 slot cubes -> g_S (frames, stride) float32 in the magnitude slot layout"""
-    g = np.ascontiguousarray(torch.view_as_real(G.contiguous()).numpy(), dtype=np.float32)
-    a = np.ascontiguousarray(torch.view_as_real(A.contiguous()).numpy(), dtype=np.float32)
-    frames, stride = G.shape
-    assert A.shape == G.shape and len(xpos_bin) == stride == len(s2x)
-    out = np.full((frames, stride), np.nan, np.float32)
-    emu.emu_guide_project(g.ctypes.data, a.ctypes.data, xpos_bin.ctypes.data, s2x.ctypes.data, frames, stride, stride, out.ctypes.data)
-    return torch.from_numpy(out)
-
-
-def relu_guard(fb, mel):
-    """(keep (B, F, T) bool, marked share): test_imel_lstsq_bwd_cpu.guarded_gradient's marking of the relu's undecided positions"""
-    gx, share, _ = bcpu.guarded_gradient(fb, mel)
-    return gx != 0, share
-
-
-def fit(guide, L):
-    """the guide cut or zero-padded at its end to L samples"""
-    return guide[:, :L] if guide.shape[1] >= L else torch.nn.functional.pad(guide, (0, L - guide.shape[1]))
-
-
-def torch_chain(O, op, fb, mel, guide, g_w, loop, dtype, keep):
-    """(g_S (B, F, T), g_mel (B, M, T)) of w = istft(x a / |a|), x = relu(lstsq(mel)) [times `keep`], a = stft(guide), by torch
-    autograd in `dtype`: g_S with respect to the magnitudes themselves (no guard), g_mel through the guarded relu"""
-    a = IO.stft(O, fit(guide, g_w.shape[1]).to(dtype), op, dtype, loop)
-    u = a / a.abs()
-    leaf = mel.to(dtype).clone().requires_grad_(True)
-    x = torch.relu(torch.linalg.lstsq(fb.T[None].to(dtype), leaf, driver="gels").solution)
-    S = x.detach().clone().requires_grad_(True)
-    IO.istft(O, S * u, op, dtype, loop).backward(g_w.to(dtype))
-    IO.istft(O, (x * keep.to(dtype)) * u, op, dtype, loop).backward(g_w.to(dtype))
-    return S.grad.detach(), leaf.grad.detach()
+@pytest.fixture(scope="module")
+def emus():
+    return bcpu.emulators()
 
 
 # ---- the emulator chain -------------------------------------------------------------------------------------------------------------

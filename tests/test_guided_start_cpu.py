@@ -11,26 +11,22 @@ CPU checks of the phase-guided Griffin-Lim start (include/rfx.h: rfx_guided_call
 * The layout of the grown options struct against the header, and the refusals that need no device.
 """
 import ctypes
-import os
 import subprocess
-import wave
 
 import numpy as np
 import pytest
 import torch
 
+import emu_build
 import helpers
+from engines import clip2_segment
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_guide_emu.cpp")
-CLIP2 = "clip_2_start_103694_ms_duration_5678_ms.wav"
+EMU_SRC = "rfx_guide_emu.cpp"
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("guide_emu") / "librfx_guide_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     lib.emu_guide_stage.argtypes = [ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     lib.emu_guide_stage.restype = None
     return lib
@@ -167,21 +163,9 @@ def test_a_staged_row_does_not_depend_on_its_batch(emu):
 
 # ---- the definition, on the oracle ------------------------------------------------------------------------------------------------------
 
-def _clip2(golden_dir, frames=64, start=44100):
-    import riffusion_oracle as O
-    from riffusion.spectrogram_params import SpectrogramParams
-
-    op = O.params_from(SpectrogramParams())
-    with wave.open(os.path.join(golden_dir, CLIP2)) as w:
-        assert w.getframerate() == op.sample_rate and w.getsampwidth() == 2 and w.getnchannels() == 2
-        pcm = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, 2)
-    seg = pcm[start:start + op.hop_length * (frames - 1)].astype(np.float32)
-    return O, op, torch.from_numpy(seg.T.copy())  # (2, L)
-
-
 @pytest.fixture(scope="module")
 def clip2(golden_dir):
-    return _clip2(golden_dir)
+    return clip2_segment(golden_dir)
 
 
 @pytest.mark.parametrize("stereo", [False, True], ids=["mono", "stereo"])
@@ -212,18 +196,15 @@ def test_oracle_guided_start_beats_the_random_start(clip2, stereo):
 def test_guided_options_layout_matches_the_header(repo_root, tmp_path):
     from riffusion import _hip
 
-    src = tmp_path / "layout.c"
-    src.write_text(
+    exe = emu_build.header_compiles_as_c99(
+        tmp_path,
         '#include <stddef.h>\n#include <stdio.h>\n#include "rfx.h"\n'
         "#define O(f) (int)offsetof(rfx_guided_call_options, f)\n"
         "int main(void) {\n"
         '  printf("%d %d %d %d %d %d %d %d %d %d %d\\n", (int)sizeof(rfx_call_options), (int)sizeof(rfx_guided_call_options), O(flags), O(row_base),\n'
         "         O(magnitude_hint), O(reserved), O(d_guide), O(guide_stride), O(guide_samples), O(reserved2), rfx_version());\n"
-        "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    lib_dir = os.path.dirname(_hip.library_path())
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(repo_root, "include"), str(src), "-o", str(exe),
-                    "-L", lib_dir, "-lrfx", f"-Wl,-rpath,{lib_dir}"], check=True)
+        "  return 0;\n}\n",
+        link=True, extra=("-Wextra",))
     got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     G, S = _hip.RfxGuidedCallOptions, _hip.RfxCallOptions
     assert got[:2] == [ctypes.sizeof(S), ctypes.sizeof(G)] == [24, 48]

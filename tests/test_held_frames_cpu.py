@@ -10,26 +10,24 @@ CPU checks of held frames (include/rfx.h: rfx_held_call_options): a guided Griff
 * The definition, on the oracle (tests/held_oracle.py): 64 frames of golden clip 2, the guide the clip with a span zeroed.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import emu_build
 import held_oracle
 import helpers
+from engines import clip2_segment
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_hold_emu.cpp")
+EMU_SRC = "rfx_hold_emu.cpp"
 SENTINEL = -0x12345678
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("hold_emu") / "librfx_hold_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     lib.emu_hold_list_words.argtypes = [ctypes.c_longlong, ctypes.c_int]
     lib.emu_hold_list_words.restype = ctypes.c_longlong
     lib.emu_hold_list.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
@@ -171,18 +169,15 @@ def test_hold_rows_takes_a_pair_or_an_array_and_clamps():
 def test_held_options_layout_matches_the_header(repo_root, tmp_path):
     from riffusion import _hip
 
-    src = tmp_path / "layout.c"
-    src.write_text(
+    exe = emu_build.header_compiles_as_c99(
+        tmp_path,
         '#include <stddef.h>\n#include <stdio.h>\n#include "rfx.h"\n'
         "#define O(f) (int)offsetof(rfx_held_call_options, f)\n"
         "int main(void) {\n"
         '  printf("%d %d %d %d %d %d %d %d %d %d %d %d %d\\n", (int)sizeof(rfx_guided_call_options), (int)sizeof(rfx_held_call_options), O(flags), O(row_base),\n'
         "         O(magnitude_hint), O(reserved), O(d_guide), O(guide_stride), O(guide_samples), O(reserved2), O(d_hold_frames), O(reserved3), rfx_version());\n"
-        "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    lib_dir = os.path.dirname(_hip.library_path())
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(repo_root, "include"), str(src), "-o", str(exe),
-                    "-L", lib_dir, "-lrfx", f"-Wl,-rpath,{lib_dir}"], check=True)
+        "  return 0;\n}\n",
+        link=True, extra=("-Wextra",))
     got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     H, G = _hip.RfxHeldCallOptions, _hip.RfxGuidedCallOptions
     assert got[:2] == [ctypes.sizeof(G), ctypes.sizeof(H)] == [48, 64]
@@ -261,9 +256,7 @@ HOLD = (16, 15)
 @pytest.fixture(scope="module")
 def clip2(golden_dir):
     """(oracle, params, true magnitudes (1, n_stft, 64) of the mono clip, a0 of the guide: the clip with [8820, 19404) zeroed)"""
-    import test_guided_start_cpu as guided
-
-    O, op, wav = guided._clip2(golden_dir, FRAMES, START)
+    O, op, wav = clip2_segment(golden_dir, FRAMES, START)
     x = wav.mean(dim=0, keepdim=True)
     mag = O.stft_complex(x, op).abs()
     guide = x.clone()

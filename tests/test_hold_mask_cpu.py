@@ -24,19 +24,17 @@ import numpy as np
 import pytest
 import torch
 
+import emu_build
 import helpers
 import mask_oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_holdmask_emu.cpp")
+EMU_SRC = "rfx_holdmask_emu.cpp"
 SPEC, PLAIN, TABLE = 0, 1, 2  # kHoldMaskSpec / kHoldMaskPlain / kHoldMaskTable
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("holdmask_emu") / "librfx_holdmask_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     lib.emu_holdmask_slot_bin.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.emu_holdmask_split.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5
     lib.emu_holdmask_split.restype = None
@@ -282,19 +280,16 @@ def test_bin_bands_refusals(lib):
 def test_masked_options_layout_matches_the_header(repo_root, tmp_path):
     from riffusion import _hip
 
-    src = tmp_path / "layout.c"
-    src.write_text(
+    exe = emu_build.header_compiles_as_c99(
+        tmp_path,
         '#include <stddef.h>\n#include <stdio.h>\n#include "rfx.h"\n'
         "#define O(f) (int)offsetof(rfx_masked_call_options, f)\n"
         "int main(void) {\n"
         '  printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\\n", (int)sizeof(rfx_held_call_options), (int)sizeof(rfx_masked_call_options), O(flags),\n'
         "         O(row_base), O(magnitude_hint), O(reserved), O(d_guide), O(guide_stride), O(guide_samples), O(reserved2), O(d_hold_frames), O(reserved3),\n"
         "         O(d_hold_bins), O(hold_words), O(reserved4));\n"
-        "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    lib_dir = os.path.dirname(_hip.library_path())
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(repo_root, "include"), str(src), "-o", str(exe),
-                    "-L", lib_dir, "-lrfx", f"-Wl,-rpath,{lib_dir}"], check=True)
+        "  return 0;\n}\n",
+        link=True, extra=("-Wextra",))
     got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     M, H = _hip.RfxMaskedCallOptions, _hip.RfxHeldCallOptions
     assert got[:2] == [ctypes.sizeof(H), ctypes.sizeof(M)] == [64, 80]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import emu_build
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import audio_util, image_util
 
@@ -233,25 +234,18 @@ def test_header_is_plain_c_and_links_from_c(repo_root, tmp_path):
 
     from riffusion import _hip
 
-    if shutil.which("gcc") is None:
+    if shutil.which(emu_build.CC) is None:
         pytest.skip("no gcc")
-    src = tmp_path / "abi.c"
-    src.write_text(
+    exe = emu_build.header_compiles_as_c99(
+        tmp_path,
         '#include <stdio.h>\n#include "rfx.h"\n'
         "int main(void) {\n"
         "  rfx_params p = {44100, 17640, 4410, 441, 512, 200};\n"
         "  rfx_plan* plan = 0;\n"
         "  int rc = rfx_plan_create(&p, 0, 0, 0, &plan); /* null window: must be refused, not crash */\n"
         '  printf("%d %d %d %d %s\\n", rfx_version() > 0, rfx_frame_stride(), rfx_num_bins(), rc, rfx_last_error());\n'
-        "  return 0;\n}\n"
-    )
-    exe = tmp_path / "abi"
-    lib_dir = os.path.dirname(_hip.library_path())
-    subprocess.run(
-        ["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(repo_root, "include"), str(src),
-         "-o", str(exe), "-L", lib_dir, "-lrfx", f"-Wl,-rpath,{lib_dir}"],
-        check=True,
-    )
+        "  return 0;\n}\n",
+        link=True, extra=("-Wextra",))
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split(maxsplit=4)
     assert out[:3] == ["1", "9408", "8821"]
     assert int(out[3]) < 0 and "rfx_plan_create" in out[4]

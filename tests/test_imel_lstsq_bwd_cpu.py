@@ -16,108 +16,33 @@ lsq_collect_kernel of csrc/rfx_imel_lstsq.hip between two solves).
 * The autograd routing on a fake plan; include/rfx.h as C99 with the new entries.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from test_imel_lstsq_cpu import EMU_SRC as FWD_EMU_SRC
-from test_imel_lstsq_cpu import bank, emu_run, image_mel, report
+import emu_build
+from imel_lstsq_bwd_cases import (EMU_SRC, GUARD_SHARE, distances, emu_backward, emulators, frame_stride, guarded_gradient, lists, to_slots,
+                                  torch_gradient)
+from imel_lstsq_cases import bank, emu_run, image_mel, report
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_imel_lstsq_bwd_emu.cpp")
-EMU_MAIN = os.path.join(ROOT, "tests", "emu", "rfx_imel_lstsq_bwd_emu_main.cpp")
+EMU_MAIN = "rfx_imel_lstsq_bwd_emu_main.cpp"
 CASES = {  # the banks and frame counts the gate is stated for
     "default": ({}, 9),
     "norm_slaney": (dict(mel_scale_norm="slaney"), 9),
     "8khz_64": (dict(sample_rate=8000, num_frequencies=64, max_frequency=4000), 21),
 }
-GUARD = 1e-3        # |v| < GUARD * (fb |y|): the relu's side is not decided in float32
-GUARD_SHARE = 5e-3  # ... which may hold for this share of the positions with a filter
 
 
 @pytest.fixture(scope="module")
-def emus(tmp_path_factory):
-    d = tmp_path_factory.mktemp("lstsq_bwd_emu")
-    libs = []
-    for name, src in (("fwd", FWD_EMU_SRC), ("bwd", EMU_SRC)):
-        so = str(d / f"librfx_imel_lstsq_{name}_emu.so")
-        subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, src], check=True)
-        libs.append(ctypes.CDLL(so))
-    fwd, bwd = libs
-    fwd.emu_inverse_mel_lstsq.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
-    bwd.emu_inverse_mel_lstsq_backward.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2
-    return fwd, bwd
-
-
-def lists(cp, fb):
-    from riffusion import _hip
-
-    return _hip.lstsq_collect_lists(cp, fb)
-
-
-def frame_stride(op):
-    from helpers import plan_bank_report
-
-    return int(plan_bank_report(op).frame_stride)
-
-
-def to_slots(g_bft: torch.Tensor, lst, stride: int, fill=np.nan) -> np.ndarray:
-    """(B, F, T) gradient -> [B * T][stride] with every bin at the position the lists name, `fill` everywhere else"""
-    ptr, bins, pos, w = lst
-    B, F, T = g_bft.shape
-    out = np.full((B * T, stride), fill, np.float32)
-    out[:, pos] = g_bft.permute(0, 2, 1).reshape(B * T, F).numpy()[:, bins]
-    return out
-
-
-def emu_backward(bwd, fb, tables, lst, mel, gx_slots):
-    """mel (B, M, T) float32 tensor, gx [B * T][stride] float32 array -> g_mel (B, M, T) float32 tensor by the emulator"""
-    neg_l, inv_d = tables
-    ptr, bins, pos, w = lst
-    F, M = fb.shape
-    B, _, T = mel.shape
-    mel = np.ascontiguousarray(mel.numpy(), dtype=np.float32)
-    fbn = np.ascontiguousarray(fb.numpy(), dtype=np.float32)
-    gx_slots = np.ascontiguousarray(gx_slots, dtype=np.float32)
-    assert gx_slots.shape[0] == B * T
-    out = np.full((B, M, T), np.nan, np.float32)
-    bwd.emu_inverse_mel_lstsq_backward(fbn.ctypes.data, neg_l.ctypes.data, inv_d.ctypes.data, ptr.ctypes.data, bins.ctypes.data, pos.ctypes.data,
-                                       w.ctypes.data, mel.ctypes.data, gx_slots.ctypes.data, B, F, M, T, gx_slots.shape[1], None, out.ctypes.data)
-    return torch.from_numpy(out)
+def emus():
+    return emulators()
 
 
 def tiles(M, T):
     """two image tiles (seeds 3 and 4): not in the range of fb^T, so a good share of the relu is closed"""
     return torch.cat([image_mel(M, T, seed=3), image_mel(M, T, seed=4)]).contiguous()
-
-
-def torch_gradient(fb, mel, gx, dtype):
-    """d <gx, relu(lstsq(fb.T, mel).solution)> / d mel by torch autograd in `dtype`, and the forward's result"""
-    m = mel.to(dtype).clone().requires_grad_(True)
-    x = torch.relu(torch.linalg.lstsq(fb.T[None].to(dtype), m, driver="gels").solution)
-    (g,) = torch.autograd.grad(x, m, gx.to(dtype))
-    return g, x.detach()
-
-
-def guarded_gradient(fb, mel, seed=11):
-    """a random (B, F, T) gradient, zero where float64 cannot tell float32 which side of the relu a position is on; the marked share"""
-    G = fb.double().T @ fb.double()
-    y = torch.linalg.solve(G, mel.double())
-    v, bound = fb.double() @ y, fb.double() @ y.abs()
-    reached = (fb != 0).any(dim=1)[None, :, None].expand_as(v)
-    marked = (v.abs() < GUARD * bound) & reached
-    gx = torch.randn(v.shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float32)
-    gx[marked] = 0.0
-    share = float(marked.sum()) / float(reached.sum())
-    return gx, share, (v > 0) & reached
-
-
-def distances(g, ref):
-    diff = g.double() - ref
-    return float(diff.norm() / ref.norm()), float((diff.norm(dim=1) / ref.norm(dim=1)).max())
 
 
 @pytest.fixture(scope="module")
@@ -232,12 +157,10 @@ def test_lists_of_a_refused_bank_are_refused():
     assert b"capacity" in lib.rfx_last_error() and n.value > 3
 
 
-def test_sanitized_stand_alone_emulator(tmp_path):
+def test_sanitized_stand_alone_emulator():
     """the emulator with its own main, built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program; the sanitizers'
     runtimes are linked statically, so the program carries them itself"""
-    exe = str(tmp_path / "rfx_imel_lstsq_bwd_emu_asan")
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                    "-static-libasan", "-static-libubsan", "-o", exe, EMU_SRC, EMU_MAIN], check=True)
+    exe = emu_build.sanitized_program([EMU_SRC, EMU_MAIN], "-ffp-contract=off", "-fno-omit-frame-pointer")
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok") and "ERROR" not in run.stderr, run.stdout + run.stderr
 
@@ -345,15 +268,14 @@ def test_keyword_refusals_and_the_default(converter):
 
 
 def test_header_compiles_as_c99_with_the_entries(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "rfx.h"\n'
-                   "size_t q(const rfx_plan* p) { return rfx_inverse_mel_lstsq_backward_workspace_bytes(p, 1, 41); }\n"
-                   "int r(const rfx_plan* p, const float* mel, const float* gx, float* g, void* ws) {\n"
-                   "  return rfx_inverse_mel_lstsq_backward(p, mel, gx, 1, 41, g, ws, 0, 0); }\n"
-                   "int s(const rfx_params* p, const float* fb, int32_t* a, float* w, int32_t* n) {\n"
-                   "  return rfx_debug_lstsq_collect(p, fb, a, a, a, w, 0, n); }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "use.o")],
-                   check=True)
+    emu_build.header_compiles_as_c99(
+        tmp_path,
+        '#include "rfx.h"\n'
+        "size_t q(const rfx_plan* p) { return rfx_inverse_mel_lstsq_backward_workspace_bytes(p, 1, 41); }\n"
+        "int r(const rfx_plan* p, const float* mel, const float* gx, float* g, void* ws) {\n"
+        "  return rfx_inverse_mel_lstsq_backward(p, mel, gx, 1, 41, g, ws, 0, 0); }\n"
+        "int s(const rfx_params* p, const float* fb, int32_t* a, float* w, int32_t* n) {\n"
+        "  return rfx_debug_lstsq_collect(p, fb, a, a, a, w, 0, n); }\n")
     from riffusion import _hip
 
     lib = _hip.load_library()

@@ -11,15 +11,12 @@ CPU checks of the closed-form InverseMelScale (csrc/rfx_imel_lstsq.hip, include/
   in the same test on the same input, overall and for the worst single frame.  (2: room for another fixed operation order.)
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_imel_lstsq_emu.cpp")
+from imel_lstsq_cases import bank, distances, emu_run, emulator, image_mel, lstsq_reference, report
 
 BANKS = {
     "default": {},
@@ -32,29 +29,8 @@ BANKS = {
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("lstsq_emu") / "librfx_imel_lstsq_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
-    lib.emu_inverse_mel_lstsq.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
-    return lib
-
-
-def bank(**kw):
-    """(oracle params, rfx_params, filterbank (n_stft, n_mels) float32) of a SpectrogramParams variation"""
-    import riffusion_oracle as O
-    from riffusion import _hip
-    from riffusion.spectrogram_params import SpectrogramParams
-
-    op = O.params_from(SpectrogramParams(**kw))
-    cp = _hip.RfxParams(op.sample_rate, op.n_fft, op.win_length, op.hop_length, op.num_frequencies, op.max_mel_iters)
-    return op, cp, O.mel_filterbank(op).to(torch.float32).contiguous()
-
-
-def report(cp, fb, tables=False):
-    from riffusion import _hip
-
-    return _hip.lstsq_bank_report(cp, fb, tables=tables)
+def emu():
+    return emulator()
 
 
 def ldl_float64(fb: torch.Tensor):
@@ -71,43 +47,10 @@ def ldl_float64(fb: torch.Tensor):
     return D, l, d, off
 
 
-def emu_run(emu, fb, tables, mel):
-    """mel (B, M, T) float32 tensor -> (B, F, T) float32 tensor by the emulator"""
-    neg_l, inv_d = tables
-    F, M = fb.shape
-    B, M2, T = mel.shape
-    assert M2 == M
-    mel = np.ascontiguousarray(mel.numpy(), dtype=np.float32)
-    fbn = np.ascontiguousarray(fb.numpy(), dtype=np.float32)
-    out = np.full((B, F, T), np.nan, np.float32)
-    emu.emu_inverse_mel_lstsq(fbn.ctypes.data, neg_l.ctypes.data, inv_d.ctypes.data, mel.ctypes.data, B, F, M, T, None, out.ctypes.data)
-    return torch.from_numpy(out)
-
-
-def lstsq_reference(fb, mel, dtype):
-    return torch.relu(torch.linalg.lstsq(fb.T[None].to(dtype), mel.to(dtype), driver="gels").solution)
-
-
-def distances(x, ref):
-    """relative L2 distance of x from ref (B, F, T): overall, and of the worst single frame"""
-    diff, ref = x.double() - ref, ref
-    per_frame = diff.norm(dim=1) / ref.norm(dim=1)
-    return float(diff.norm() / ref.norm()), float(per_frame.max())
-
-
 def consistent_mel(fb, T, seed=1):
     g = torch.Generator().manual_seed(seed)
     lin = torch.rand(fb.shape[0], T, generator=g) ** 4 * 3e7
     return (fb.T @ lin)[None].contiguous()
-
-
-def image_mel(M, T, max_value=30e6, seed=3):
-    """a uniform-random uint8 tile decoded as the image path does: not in the range of fb^T"""
-    import riffusion_oracle as O
-
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, size=(M, T, 3), dtype=np.uint8)
-    return torch.from_numpy(np.ascontiguousarray(O.spectrogram_from_image_u8(img, max_value=max_value, stereo=False))).to(torch.float32)
 
 
 # ---- the host analysis -------------------------------------------------------------------------------------------------------------

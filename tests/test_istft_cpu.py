@@ -19,18 +19,18 @@ CPU checks of the inverse spectrogram (include/rfx.h, "INVERSE SPECTROGRAM"; csr
 * include/rfx.h compiles as C99 with the new entries; the entries answer 0 or refuse without a plan.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import emu_build
 import istft_oracle as IO
+from helpers import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_istft_emu.cpp")
-EMU_MAIN = os.path.join(ROOT, "tests", "emu", "rfx_istft_emu_main.cpp")
+EMU_SRC = "rfx_istft_emu.cpp"
+EMU_MAIN = "rfx_istft_emu_main.cpp"
 GEOMETRIES = {
     "odd-nfft": dict(sample_rate=10010, padded_duration_ms=100, window_duration_ms=25.1, step_size_ms=2.6, max_frequency=5000),
     "even-nfft": dict(sample_rate=10000, padded_duration_ms=100, window_duration_ms=25, step_size_ms=2.6, max_frequency=5000),
@@ -43,17 +43,12 @@ GATE = 1e-10
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("istft_emu") / "librfx_istft_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     vp, i = ctypes.c_void_p, ctypes.c_int
     lib.emu_istft_samples.argtypes = [i, i, i, i]
     lib.emu_istft_pad_frames.argtypes = [i, i, i]
@@ -159,12 +154,10 @@ def test_backward_against_autograd_and_the_adjoint_identity(O, emu, geo, T, loop
     assert defect <= GATE
 
 
-def test_sanitized_stand_alone_emulator(tmp_path):
+def test_sanitized_stand_alone_emulator():
     """the emulator with its own main, built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program; the sanitizers'
     runtimes are linked statically, so the program carries them itself"""
-    exe = str(tmp_path / "rfx_istft_emu_asan")
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                    "-static-libasan", "-static-libubsan", "-o", exe, EMU_SRC, EMU_MAIN], check=True)
+    exe = emu_build.sanitized_program([EMU_SRC, EMU_MAIN], "-ffp-contract=off", "-fno-omit-frame-pointer")
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok") and "ERROR" not in run.stderr, run.stdout + run.stderr
     figures = [float(ln.split()[-1]) for ln in run.stdout.splitlines() if ln.startswith("defect ")]
@@ -285,12 +278,11 @@ def test_entries_without_a_plan():
 
 
 def test_header_compiles_as_c99_with_the_entries(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "rfx.h"\n'
-                   "size_t q(const rfx_plan* p) { return rfx_istft_workspace_bytes(p, 1, 41) + rfx_istft_loop_workspace_bytes(p, 1, 41)\n"
-                   "  + rfx_istft_backward_workspace_bytes(p, 1, 41) + rfx_istft_backward_loop_workspace_bytes(p, 1, 41); }\n"
-                   "int r(const rfx_plan* p, void* x, float* y, void* ws) {\n"
-                   "  return rfx_istft(p, x, 1, 41, y, ws, 0, 0) + rfx_istft_loop(p, x, 1, 41, y, ws, 0, 0)\n"
-                   "  + rfx_istft_backward(p, y, 1, 41, x, ws, 0, 0) + rfx_istft_backward_loop(p, y, 1, 41, x, ws, 0, 0); }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "use.o")],
-                   check=True)
+    emu_build.header_compiles_as_c99(
+        tmp_path,
+        '#include "rfx.h"\n'
+        "size_t q(const rfx_plan* p) { return rfx_istft_workspace_bytes(p, 1, 41) + rfx_istft_loop_workspace_bytes(p, 1, 41)\n"
+        "  + rfx_istft_backward_workspace_bytes(p, 1, 41) + rfx_istft_backward_loop_workspace_bytes(p, 1, 41); }\n"
+        "int r(const rfx_plan* p, void* x, float* y, void* ws) {\n"
+        "  return rfx_istft(p, x, 1, 41, y, ws, 0, 0) + rfx_istft_loop(p, x, 1, 41, y, ws, 0, 0)\n"
+        "  + rfx_istft_backward(p, y, 1, 41, x, ws, 0, 0) + rfx_istft_backward_loop(p, y, 1, 41, x, ws, 0, 0); }\n")

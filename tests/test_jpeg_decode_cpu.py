@@ -7,59 +7,22 @@ standard and with optimised Huffman tables; a file with the spectrogram EXIF; si
 replicates their chroma instead of filtering it).  Conditions on the set keep every path in the comparison.  Damaged scans go
 through a stand-alone sanitizer build of the emulator: a non-zero status and no read outside the buffers.
 """
-import ctypes
 import functools
 import io
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 from PIL import Image
 
+from jpeg_cases import CONTENTS, QUALITIES, STEREO_PNG, _golden, _random
+from jpeg_decode_cases import DAMAGE_TILES, SMALL, _emu, _sanitizer_program, damaged_scans, emu_decode, pillow_jpeg, pillow_pixels
 from riffusion.spectrogram_params import SpectrogramParams
 from riffusion.util import image_util
-from test_jpeg_cpu import CONTENTS, QUALITIES, STEREO_PNG, _golden, _random
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_jpeg_dec_emu.cpp")
 FULL = ("stereo_full", "og_beat")  # the two full-size golden tiles: quality 75 only
 CASES = [(name, q, opt) for name in CONTENTS for q in ((75,) if name in FULL else QUALITIES) for opt in (False, True)]
-SMALL = [(1, 2), (2, 1), (2, 2), (3, 2), (3, 3), (4, 4), (5, 3), (5, 4), (5, 5), (6, 5)]  # around W = 4: replicated / filtered chroma
-
-
-def pillow_jpeg(tile, quality, **kw):
-    buf = io.BytesIO()
-    Image.fromarray(np.ascontiguousarray(tile)).save(buf, "JPEG", quality=quality, **kw)
-    return buf.getvalue()
-
-
-def pillow_pixels(data):
-    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
-
-
-@functools.lru_cache(maxsize=1)
-def _emu():
-    so = os.path.join(tempfile.mkdtemp(prefix="jpeg_dec_emu"), "librfx_jpeg_dec_emu.so")
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
-    lib.emu_jpeg_decode_u8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_void_p, ctypes.c_void_p]
-    return lib
-
-
-def emu_decode(data):
-    """(status, pixels, [most rounds of a group, subsequences, groups, rounds in all], scan) of a file jpeg_parse gives to the device"""
-    info = image_util.jpeg_parse(data)
-    assert info.ok_for_device, info.reason
-    scan = np.frombuffer(data, np.uint8)[info.scan[0]:info.scan[1]].copy()
-    out = np.zeros((info.height, info.width, 3), np.uint8)
-    stats = np.zeros(4, np.int32)
-    qt, huff = np.ascontiguousarray(info.qtables), np.ascontiguousarray(info.huffman)
-    status = _emu().emu_jpeg_decode_u8(scan.ctypes.data, scan.size, info.height, info.width, qt.ctypes.data, huff.ctypes.data,
-                                       out.ctypes.data, stats.ctypes.data)
-    return status, out, stats, scan.tobytes()
 
 
 @functools.lru_cache(maxsize=None)
@@ -164,30 +127,6 @@ def test_parse_keeps_other_files_on_the_host():
 
 
 # ---- damaged scans: the stand-alone sanitizer program ---------------------------------------------------------------------------
-def damaged_scans(scan):
-    """the four damaged versions of a scan the issue names"""
-    third, two_thirds, mid = len(scan) // 3, 2 * len(scan) // 3, len(scan) // 2
-    return {
-        "truncated at a third": scan[:third],
-        "truncated at two thirds": scan[:two_thirds],
-        "one byte flipped mid-scan": scan[:mid] + bytes([scan[mid] ^ 0xFF]) + scan[mid + 1:],
-        "an all-0xFF tail": scan[:two_thirds] + b"\xff" * (len(scan) - two_thirds),
-    }
-
-
-# a dozen subsequences, some twenty, and more than a group.  (Not every flipped byte damages a scan: the one in the middle of
-# "stereo_crop" at quality 75 leaves a scan that codes another picture with the same number of blocks - the next test.)
-DAMAGE_TILES = {"random_32x40": 75, "random_62x33": 95, "og_beat": 75}
-
-
-@functools.lru_cache(maxsize=1)
-def _sanitizer_program():
-    exe = os.path.join(tempfile.mkdtemp(prefix="jpeg_dec_asan"), "rfx_jpeg_dec_emu_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DRFX_JPD_EMU_MAIN", "-o", exe, EMU_SRC],
-                   check=True)
-    return exe
-
-
 def _run_sanitized(info, scan, tmp_path, tag):
     path = os.path.join(tmp_path, f"{tag}.bin")
     with open(path, "wb") as f:

@@ -23,11 +23,11 @@ import numpy as np
 import pytest
 import torch
 
+import emu_build
 import helpers
 import loop_oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_loop_emu.cpp")
+EMU_SRC = "rfx_loop_emu.cpp"
 U = 2.0 ** -24
 
 # (n_fft, win, hop, T)
@@ -43,10 +43,8 @@ def O():
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("loop_emu") / "librfx_loop_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     vp, i = ctypes.c_void_p, ctypes.c_int
     lib.emu_loop_gather.argtypes = [i, i, i, i, i, vp]
     lib.emu_loop_gather_blocks.argtypes = [i, i, i, vp]
@@ -238,19 +236,16 @@ def test_loop_decode_has_an_ordinary_step_at_the_loop_point(O, default_params, g
 def test_loop_options_layout_matches_the_header(repo_root, tmp_path):
     from riffusion import _hip
 
-    src = tmp_path / "layout.c"
-    src.write_text(
+    exe = emu_build.header_compiles_as_c99(
+        tmp_path,
         '#include <stddef.h>\n#include <stdio.h>\n#include "rfx.h"\n'
         "#define O(f) (int)offsetof(rfx_loop_call_options, f)\n"
         "int main(void) {\n"
         '  printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\\n", (int)sizeof(rfx_masked_call_options), (int)sizeof(rfx_loop_call_options), O(flags),\n'
         "         O(row_base), O(magnitude_hint), O(reserved), O(d_guide), O(guide_stride), O(guide_samples), O(reserved2), O(d_hold_frames), O(reserved3),\n"
         "         O(d_hold_bins), O(hold_words), O(reserved4), O(loop), O(reserved5));\n"
-        "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    lib_dir = os.path.dirname(_hip.library_path())
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(repo_root, "include"), str(src), "-o", str(exe),
-                    "-L", lib_dir, "-lrfx", f"-Wl,-rpath,{lib_dir}"], check=True)
+        "  return 0;\n}\n",
+        link=True, extra=("-Wextra",))
     got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     Lp, M = _hip.RfxLoopCallOptions, _hip.RfxMaskedCallOptions
     assert got[:2] == [ctypes.sizeof(M), ctypes.sizeof(Lp)] == [80, 88]

@@ -15,18 +15,17 @@ P = hop T samples, frame t, element i reads x[(hop t + i - n_fft // 2) mod P].
 * The CLI flags and the keyword checks that need no device.
 """
 import ctypes
-import os
 import subprocess
 import types
 
 import numpy as np
 import pytest
 
+import emu_build
 import loop_oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_loop_fwd_emu.cpp")
-EMU_MAIN = os.path.join(ROOT, "tests", "emu", "rfx_loop_fwd_emu_main.cpp")
+EMU_SRC = "rfx_loop_fwd_emu.cpp"
+EMU_MAIN = "rfx_loop_fwd_emu_main.cpp"
 
 # (sample_rate, n_fft, win, hop): the default, 48 kHz, 11.025 kHz, one odd n_fft
 PARAMS = [(44100, 17640, 4410, 441), (48000, 19200, 4800, 480), (11025, 4410, 1102, 110), (10010, 1001, 251, 26)]
@@ -41,10 +40,8 @@ def lib():
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("loop_fwd_emu") / "librfx_loop_fwd_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     vp, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     lib.emu_loop_samples_valid.argtypes = lib.emu_loop_samples_frames.argtypes = [i, i, ll]
     lib.emu_loop_samples_below.argtypes = lib.emu_loop_samples_above.argtypes = [i, i, ll]
@@ -155,12 +152,10 @@ def test_every_engine_reads_the_oracles_samples(emu, n_fft, win, hop, T):
                 assert np.array_equal(run[:-8].reshape(f1 - f0, win), want[:, f0:f1].T) and (run[-8:] == -77).all(), (per, f0)
 
 
-def test_sanitized_stand_alone_emulator(tmp_path):
+def test_sanitized_stand_alone_emulator():
     """the emulator with its own main, built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program, in the
     environment the test itself runs in; the sanitizers' runtimes are linked statically, so the program carries them itself"""
-    exe = str(tmp_path / "rfx_loop_fwd_emu_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan",
-                    "-static-libubsan", "-o", exe, EMU_SRC, EMU_MAIN], check=True)
+    exe = emu_build.sanitized_program([EMU_SRC, EMU_MAIN], "-fno-omit-frame-pointer")
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok") and "ERROR" not in run.stderr, run.stdout + run.stderr
 

@@ -14,18 +14,18 @@ CPU checks of the forward path's backward (include/rfx.h, "BACKWARD of the forwa
 * include/rfx.h compiles as C99 with the new entries; the entries answer 0 or refuse without a plan.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import emu_build
 import mel_backward_oracle as MBO
+from helpers import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_mel_bwd_emu.cpp")
-EMU_MAIN = os.path.join(ROOT, "tests", "emu", "rfx_mel_bwd_emu_main.cpp")
+EMU_SRC = "rfx_mel_bwd_emu.cpp"
+EMU_MAIN = "rfx_mel_bwd_emu_main.cpp"
 
 # OracleParams keywords of the four geometries of tests/test_loop_encode_cpu.py: (n_fft, win, hop) = (17640, 4410, 441),
 # (19200, 4800, 480), (4410, 1102, 110), (1001, 251, 26); 64 bands keep the float64 reference quick
@@ -41,10 +41,7 @@ GATE = 1e-10
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 @pytest.fixture(scope="module")
@@ -55,10 +52,8 @@ def lib():
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("mel_bwd_emu") / "librfx_mel_bwd_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     vp, i, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     lib.emu_mel_bwd_frames.argtypes = [i, i, i, i]
     lib.emu_mel_from_waveform_backward.argtypes = [i, i, i, i, i, vp, vp, vp, vp, vp, vp, i, vp, vp]
@@ -185,12 +180,10 @@ def test_entries_answer_zero_or_refuse_without_a_plan(lib):
     assert lib.rfx_mel_from_waveform_backward(None, None, None, 0, 17657, None, None, 0, None) == 0
 
 
-def test_sanitized_stand_alone_emulator(emu, tmp_path):
+def test_sanitized_stand_alone_emulator(emu):
     """the emulator with its own main, built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program; the sanitizers'
     runtimes are linked statically, so the program carries them itself.  Its figures are the unsanitized build's."""
-    exe = str(tmp_path / "rfx_mel_bwd_emu_asan")
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                    "-static-libasan", "-static-libubsan", "-o", exe, EMU_SRC, EMU_MAIN], check=True)
+    exe = emu_build.sanitized_program([EMU_SRC, EMU_MAIN], "-ffp-contract=off", "-fno-omit-frame-pointer")
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok") and "ERROR" not in run.stderr, run.stdout + run.stderr
     lines = [ln.split() for ln in run.stdout.splitlines() if ln.startswith("defect ")]
@@ -202,15 +195,14 @@ def test_sanitized_stand_alone_emulator(emu, tmp_path):
 
 
 def test_header_compiles_as_c99_with_the_new_entries(tmp_path):
-    src = tmp_path / "use_rfx.c"
-    src.write_text('#include "rfx.h"\n'
-                   "size_t q(const rfx_plan* p) { return rfx_stft_backward_workspace_bytes(p, 1, 17657) + rfx_mel_scale_backward_workspace_bytes(p, 1, 41)\n"
-                   "    + rfx_mel_from_waveform_backward_workspace_bytes(p, 1, 17657); }\n"
-                   "int f(const rfx_plan* p, const float* w, const float* g, float* o, void* ws, int32_t* n) {\n"
-                   "  return rfx_mel_from_waveform_backward(p, w, g, 1, 17657, o, ws, 0, 0) + rfx_stft_backward(p, ws, 1, 17657, o, ws, 0, 0)\n"
-                   "    + rfx_mel_scale_backward(p, g, 1, 41, o, 0, 0, 0) + rfx_debug_mel_adjoint(0, w, n, n, o, 2, n); }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "use_rfx.o")],
-                   check=True)
+    emu_build.header_compiles_as_c99(
+        tmp_path,
+        '#include "rfx.h"\n'
+        "size_t q(const rfx_plan* p) { return rfx_stft_backward_workspace_bytes(p, 1, 17657) + rfx_mel_scale_backward_workspace_bytes(p, 1, 41)\n"
+        "    + rfx_mel_from_waveform_backward_workspace_bytes(p, 1, 17657); }\n"
+        "int f(const rfx_plan* p, const float* w, const float* g, float* o, void* ws, int32_t* n) {\n"
+        "  return rfx_mel_from_waveform_backward(p, w, g, 1, 17657, o, ws, 0, 0) + rfx_stft_backward(p, ws, 1, 17657, o, ws, 0, 0)\n"
+        "    + rfx_mel_scale_backward(p, g, 1, 41, o, 0, 0, 0) + rfx_debug_mel_adjoint(0, w, n, n, o, 2, n); }\n")
 
 
 def test_autograd_routing_needs_no_device():

@@ -6,12 +6,11 @@ here as well.
 """
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 from riffusion.util import audio_util
 from riffusion.util.audio_util import PcmSegment
 
@@ -20,18 +19,14 @@ try:
 except ImportError:  # pragma: no cover
     _ao = None
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I16P = ctypes.POINTER(ctypes.c_int16)
 F64P = ctypes.POINTER(ctypes.c_double)
 needs_audioop = pytest.mark.skipif(_ao is None, reason="audioop removed from this interpreter")
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pcm_emu") / "librfx_pcm_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_pcm_emu.cpp")],
-                   check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared("rfx_pcm_emu.cpp", "-ffp-contract=off"))
     lib.emu_mul.argtypes, lib.emu_mul.restype = [ctypes.c_int, ctypes.c_double], ctypes.c_int
     lib.emu_add.argtypes, lib.emu_add.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_int
     lib.emu_rms.argtypes, lib.emu_rms.restype = [I16P, ctypes.c_int64], ctypes.c_uint

@@ -9,11 +9,11 @@ slicing it plans; and the C ABI's argument checks, which need no GPU.
 import ctypes
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 from riffusion.util import audio_util
 from riffusion.util.audio_util import PcmSegment
 
@@ -30,11 +30,8 @@ LENGTHS = [1, 2, 3, 7, 8, 9, 63, 64, 65, 1000, 4410, 50001]  # (7 -> 1048573 sto
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pcm_in_emu") / "librfx_pcm_in_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_pcm_in_emu.cpp")],
-                   check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared("rfx_pcm_in_emu.cpp", "-ffp-contract=off"))
     lib.emu_ratecv_frames.argtypes, lib.emu_ratecv_frames.restype = [ctypes.c_int64] * 3, ctypes.c_int64
     lib.emu_ratecv.argtypes = [I16P, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, I16P, ctypes.c_int64]
     lib.emu_clips.argtypes = [I16P, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]

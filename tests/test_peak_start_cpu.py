@@ -15,36 +15,31 @@ the magnitudes alone.
   without a plan, the CLI flags.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import emu_build
 import helpers
 import peak_start_inputs as inputs
 import peak_start_oracle
+from helpers import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_peak_emu.cpp")
+EMU_SRC = "rfx_peak_emu.cpp"
 SPEC, PLAIN, TABLE = 0, 1, 2
 TILES = ["og_beat", "vibes", "agile", "marim", "motorway"]
 
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("peak_emu") / "librfx_peak_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     vp, i = ctypes.c_void_p, ctypes.c_int
     lib.emu_peak_in_bin.argtypes = [i, i, i, vp]
     lib.emu_peak_out_bin.argtypes = [i, i, i, ctypes.POINTER(i)]
@@ -211,19 +206,16 @@ def test_peak_start_beats_the_random_start_at_few_iterations(quality, name):
 def test_start_options_layout_matches_the_header(repo_root, tmp_path):
     from riffusion import _hip
 
-    src = tmp_path / "layout.c"
-    src.write_text(
+    exe = emu_build.header_compiles_as_c99(
+        tmp_path,
         '#include <stddef.h>\n#include <stdio.h>\n#include "rfx.h"\n'
         "#define O(f) (int)offsetof(rfx_start_call_options, f)\n"
         "int main(void) {\n"
         '  printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\\n", (int)sizeof(rfx_loop_call_options), (int)sizeof(rfx_start_call_options), O(flags),\n'
         "         O(row_base), O(magnitude_hint), O(reserved), O(d_guide), O(guide_stride), O(guide_samples), O(reserved2), O(d_hold_frames), O(reserved3),\n"
         "         O(d_hold_bins), O(hold_words), O(reserved4), O(loop), O(reserved5), O(start), O(reserved6));\n"
-        "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    lib_dir = os.path.dirname(_hip.library_path())
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(repo_root, "include"), str(src), "-o", str(exe),
-                    "-L", lib_dir, "-lrfx", f"-Wl,-rpath,{lib_dir}"], check=True)
+        "  return 0;\n}\n",
+        link=True, extra=("-Wextra",))
     got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     S, Lp = _hip.RfxStartCallOptions, _hip.RfxLoopCallOptions
     assert got[:2] == [ctypes.sizeof(Lp), ctypes.sizeof(S)] == [88, 96]

@@ -18,9 +18,10 @@ import pytest
 from PIL import Image
 
 import deflate_writer as dw
+import emu_build
 import png_decode_cases as C
+from png_cases import emu_file
 from riffusion.util import image_util
-from test_png_cpu import emu_file
 
 
 def decode_one(data):
@@ -240,12 +241,9 @@ def test_random_corruptions_never_give_other_pixels():
 # ---- the sanitizer build ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
-    d = tmp_path_factory.mktemp("png_dec_programs")
-    plain, sanitized = str(d / "emu_plain"), str(d / "emu_san")
-    base = ["g++", "-O1", "-g", "-std=c++17", "-DRFX_PNGD_EMU_MAIN", C.EMU_SRC]
-    subprocess.run(base + ["-o", plain], check=True)
-    subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", sanitized], check=True)
-    return d, plain, sanitized
+    flags = ("-std=c++17", "-DRFX_PNGD_EMU_MAIN")
+    return (tmp_path_factory.mktemp("png_dec_programs"), emu_build.program(C.EMU_SRC, "-O1", "-g", *flags),
+            emu_build.sanitized_program(C.EMU_SRC, *flags, static=False))
 
 
 def run_program(program, directory, name, case):

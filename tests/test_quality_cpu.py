@@ -19,17 +19,16 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_quality_emu.cpp")
+import emu_build
+
+EMU_SRC = "rfx_quality_emu.cpp"
 SCALES = [1e-6, 30e6, 1e20]
 SPEC = dict(fs=9408, n_stft=8821, plain=0)  # the default geometry's slot layout (rfx_core.h)
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("quality_emu") / "librfx_quality_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     lib.emu_qual_mask.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p]
     lib.emu_spectral_error.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p]
     return lib
@@ -89,12 +88,10 @@ def geometry(rate=None, **kw):
 
 
 # ---- the mask ------------------------------------------------------------------------------------------------------------------
-def test_mask_counts_every_bin_once_on_the_slot_layout(emu, tmp_path):
+def test_mask_counts_every_bin_once_on_the_slot_layout(emu):
     fs, n_stft, plain, engine = geometry()
     assert (fs, n_stft, plain, engine) == (SPEC["fs"], SPEC["n_stft"], 0, 0)
-    so = str(tmp_path / "librfx_emu.so")
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_emu.cpp")], check=True)
-    core = ctypes.CDLL(so)
+    core = ctypes.CDLL(emu_build.shared("rfx_emu.cpp"))
     maps = [np.zeros(9261, np.int32) for _ in range(4)]
     core.emu_slot_maps(*[x.ctypes.data_as(ctypes.c_void_p) for x in maps])
     slot_bin, _, _, pos_f = maps
@@ -204,9 +201,7 @@ int main(int argc, char** argv) {
 def test_emulator_under_address_and_undefined_sanitizers(emu, tmp_path):
     main = tmp_path / "quality_san.cpp"
     main.write_text(SAN_MAIN)
-    exe = str(tmp_path / "quality_san")
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
-                    "-I", os.path.join(ROOT, "tests", "emu"), "-o", exe, str(main)], check=True)
+    exe = emu_build.sanitized_program(str(main), "-ffp-contract=off", "-static-libasan", "-I", emu_build.EMU_DIR, static=False)
     rng = np.random.default_rng(5)
     env = dict(os.environ, ASAN_OPTIONS="verify_asan_link_order=0:detect_leaks=0")
     for B, T, geom in ((2, 1, SPEC), (1, 5, SPEC), (3, 7, dict(fs=320, n_stft=257, plain=1))):

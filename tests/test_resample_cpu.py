@@ -26,121 +26,25 @@ csrc/rfx_resample_core.h).
   sanitized is loaded into Python.
 """
 import ctypes
-import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import emu_build
 import resample_oracle as RO
+from engines import bits as _bits
 from helpers import snr_db
+from resample_cases import (DENSE, DENSE_PAIRS, EMU_SRC, LENGTHS, PAIRS, SEAM_LENGTHS, WIDE_CASES, WIDE_IDS, WIDE_TABLES, emulator, gates, run_emu,
+                            sparse_figures, table64, wave, wide_gates)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_resample_emu.cpp")
-EMU_MAIN = os.path.join(ROOT, "tests", "emu", "rfx_resample_emu_main.cpp")
-DENSE_PAIRS = [(2, 1), (1, 2), (55, 49), (160, 147), (147, 160)]
-DENSE = DENSE_PAIRS + [(7787, 7350)]  # a dense kernel fits: 0.46 GB of float64 for the last
-PAIRS = DENSE + [(33037, 44100)]
-LENGTHS = [5, 2000, 3001]
-# The wider cases, kept apart from PAIRS x LENGTHS: (orig, new, L, lowpass_filter_width, rolloff)
-DEFAULT_FILTER = (6, 0.99)
-WIDE_PAIRS = [(4, 1), (12, 1), (1, 4), (1, 12), (3, 2), (44099, 44100), (44100, 44099)]  # n = 1: one phase; o = 1; far more phases than outputs
-WIDE_LENGTHS = [1, 2, 255, 1000]
-FILTER_PAIRS = [(55, 49), (1, 2), (2, 1)]
-FILTERS = [(1, 0.99), (16, 0.99), (64, 0.9475937167399596), (6, 1.0), (6, 0.5)]
-SEAM_LENGTHS = {277: 255, 278: 256, 279: 257, 280: 258}  # 160/147: K on both sides of a workgroup's 256 outputs
-WIDE_CASES = ([(o, n, L) + DEFAULT_FILTER for o, n in WIDE_PAIRS for L in WIDE_LENGTHS] + [(o, n, 1000) + f for o, n in FILTER_PAIRS for f in FILTERS]
-              + [(160, 147, L) + DEFAULT_FILTER for L in SEAM_LENGTHS])
-WIDE_IDS = [f"{o}/{n}-L{L}-lpw{lpw}-rolloff{ro:.4g}" for o, n, L, lpw, ro in WIDE_CASES]
-WIDE_TABLES = sorted({(o, n, lpw, ro) for o, n, _, lpw, ro in WIDE_CASES})
-_CACHE = {}
+EMU_MAIN = "rfx_resample_emu_main.cpp"
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("resample_emu") / "librfx_resample_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
-    vp, i, ll, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double
-    lib.emu_rs_frames.argtypes, lib.emu_rs_frames.restype = [ll, i, i], ll
-    lib.emu_rs_table.argtypes = [i, i, i, d, vp, vp, vp, vp]
-    lib.emu_resample.argtypes, lib.emu_resample.restype = [vp, i, ll, ll, i, i, vp, vp, i, vp, ll, ll], None
-    return lib
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.uint8).numpy().tobytes()
-
-
-def wave(L, B=3, seed=0):
-    """the input of a case (shared with tests/test_gpu_resample.py): seeded float32 noise of unit variance, the last row all zero; made
-    once and left unchanged"""
-    key = ("wave", L, B, seed)
-    if key not in _CACHE:
-        x = torch.randn(B, L, generator=torch.Generator().manual_seed(1234 + L + seed), dtype=torch.float32)
-        if B > 1:
-            x[-1] = 0
-        _CACHE[key] = x
-    return _CACHE[key]
-
-
-def table64(orig, new, lpw=6, rolloff=0.99):
-    key = ("table", orig, new, lpw, rolloff)
-    if key not in _CACHE:
-        _CACHE[key] = RO.sparse_table(orig, new, lpw, rolloff)
-    return _CACHE[key]
-
-
-def sparse_figures(orig, new, L, lpw=6, rolloff=0.99):
-    """SNRs of the two sparse float32 forms against the float64 result"""
-    key = ("sfig", orig, new, L, lpw, rolloff)
-    if key not in _CACHE:
-        x, tb = wave(L), table64(orig, new, lpw, rolloff)
-        r64 = RO.sparse_resample(x, orig, new, lpw, rolloff, table=tb)
-        _CACHE[key] = tuple(snr_db(r64[:-1], RO.sparse_resample_f32(x, orig, new, RO.sparse_weights(orig, new, dt, lpw, rolloff, table=tb), tb)[:-1])
-                            for dt in (torch.float32, torch.float64))
-    return _CACHE[key]
-
-
-def wide_gates(orig, new, L, lpw, rolloff):
-    """`gates` of a WIDE_CASES case: the float64 result and the two sparse float32 figures, as for 33037/44100 - these pairs either have
-    no dense kernel of sensible size or gain nothing from one"""
-    key = ("wfig", orig, new, L, lpw, rolloff)
-    if key not in _CACHE:
-        r64 = RO.sparse_resample(wave(L), orig, new, lpw, rolloff, table=table64(orig, new, lpw, rolloff))
-        _CACHE[key] = (r64,) + sparse_figures(orig, new, L, lpw, rolloff)
-    return _CACHE[key]
-
-
-def gates(orig, new, L):
-    """(float64 result, SNR of the all-float32 oracle: to reach outright, SNR of the float32-rounded-kernel oracle: to reach within
-    6 dB) of a case, made once.  The dense transcriptions where their kernel fits, the sparse float32 forms for 33037/44100."""
-    key = ("fig", orig, new, L)
-    if key not in _CACHE:
-        x = wave(L)
-        r64 = RO.sparse_resample(x, orig, new, table=table64(orig, new))
-        if (orig, new) in DENSE:
-            _CACHE[key] = (r64, snr_db(r64[:-1], RO.resample_f32(x, orig, new)[:-1]), snr_db(r64[:-1], RO.resample_f32_kernel64(x, orig, new)[:-1]))
-        else:
-            _CACHE[key] = (r64,) + sparse_figures(orig, new, L)
-    return _CACHE[key]
-
-
-def run_emu(emu, x, orig, new, valid=None, lpw=6, rolloff=0.99):
-    from riffusion import _hip
-
-    if orig == new:
-        return x.clone()
-    first, taps = _hip.resample_sinc_table(orig, new, lpw, rolloff)
-    o, n, _, _ = RO.geometry(orig, new)
-    x = x.contiguous()
-    B, L = x.shape
-    K = RO.frames(L, orig, new)
-    y = torch.full((B, K), 123.0)
-    emu.emu_resample(x.data_ptr(), B, L, L if valid is None else valid, o, n, first.ctypes.data, taps.ctypes.data, taps.shape[0], y.data_ptr(), K, K)
-    return y
+def emu():
+    return emulator()
 
 
 # ---- the oracles ---------------------------------------------------------------------------------------------------------------------------
@@ -284,15 +188,14 @@ def test_refusals_without_a_device():
 
 
 def test_header_compiles_as_c99_with_the_entries(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "rfx.h"\n'
-                   "size_t q(const rfx_plan* p) { return rfx_pitch_shift_workspace_bytes(p, 1, 20000, 2.0, 12) + (size_t)rfx_pitch_shift_resample_freq(p, 20000, 2.0, 12)"
-                   " + RFX_RESAMPLE_MAX_TABLE_BYTES; }\n"
-                   "int r(int32_t* f, float* t, int32_t* n, int* k) {\n"
-                   "  return rfx_resample_sinc_frames(5, 2, 1, k) + rfx_resample_sinc_table(2, 1, 6, 0.99, f, t, 25, n, n) + rfx_resample_sinc(t, 1, 5, 2, 1, f, t, 25, t, 0); }\n"
-                   "int s(const rfx_plan* p, float* x, int32_t* f, void* ws) { return rfx_pitch_shift(p, x, 1, 20000, -5.0, 12, f, x, 13, x, ws, 0, 0); }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "use.o")],
-                   check=True)
+    emu_build.header_compiles_as_c99(
+        tmp_path,
+        '#include "rfx.h"\n'
+        "size_t q(const rfx_plan* p) { return rfx_pitch_shift_workspace_bytes(p, 1, 20000, 2.0, 12) + (size_t)rfx_pitch_shift_resample_freq(p, 20000, 2.0, 12)"
+        " + RFX_RESAMPLE_MAX_TABLE_BYTES; }\n"
+        "int r(int32_t* f, float* t, int32_t* n, int* k) {\n"
+        "  return rfx_resample_sinc_frames(5, 2, 1, k) + rfx_resample_sinc_table(2, 1, 6, 0.99, f, t, 25, n, n) + rfx_resample_sinc(t, 1, 5, 2, 1, f, t, 25, t, 0); }\n"
+        "int s(const rfx_plan* p, float* x, int32_t* f, void* ws) { return rfx_pitch_shift(p, x, 1, 20000, -5.0, 12, f, x, 13, x, ws, 0, 0); }\n")
 
 
 # ---- the emulator --------------------------------------------------------------------------------------------------------------------------
@@ -390,11 +293,9 @@ def test_command_line_argument_checks(capsys):
 
 # ---- the sanitized stand-alone program ---------------------------------------------------------------------------------------------------------
 
-def test_sanitized_stand_alone_emulator(tmp_path):
+def test_sanitized_stand_alone_emulator():
     """the emulator with its own main, built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program; the sanitizers'
     runtimes are linked statically, so the program carries them itself"""
-    exe = str(tmp_path / "rfx_resample_emu_asan")
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                    "-static-libasan", "-static-libubsan", "-o", exe, EMU_SRC, EMU_MAIN], check=True)
+    exe = emu_build.sanitized_program([EMU_SRC, EMU_MAIN], "-ffp-contract=off", "-fno-omit-frame-pointer")
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok") and "ERROR" not in run.stderr, run.stdout + run.stderr

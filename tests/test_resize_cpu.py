@@ -7,12 +7,12 @@ host-only coefficient entry against the emulator's tables, and audio_util's port
 import ctypes
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 from PIL import Image
 
+import emu_build
 from riffusion.util import audio_util
 from riffusion.util.audio_util import PcmSegment
 
@@ -26,11 +26,8 @@ SIZES = [((501, 512), (512, 512)), ((512, 512), (501, 512)), ((500, 512), (512, 
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("resize_emu") / "librfx_resize_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_resize_emu.cpp")],
-                   check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared("rfx_resize_emu.cpp", "-ffp-contract=off"))
     lib.emu_resize_u8.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_void_p]
     lib.emu_resize_ksize.argtypes = [ctypes.c_int] * 3

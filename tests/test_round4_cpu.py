@@ -11,14 +11,13 @@ Round 4, CPU side: independent pins and host logic that need no GPU.
 """
 import collections
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import emu_build
+
 FP = ctypes.POINTER(ctypes.c_float)
 
 
@@ -48,10 +47,8 @@ def test_filterbanks_match_an_independent_implementation(rate, scale, norm):
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu4") / "librfx_emu.so")
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "emu", "rfx_emu.cpp")], check=True)
-    return ctypes.CDLL(so)
+def emu():
+    return ctypes.CDLL(emu_build.shared("rfx_emu.cpp"))
 
 
 def test_counter_rng_statistics(emu):

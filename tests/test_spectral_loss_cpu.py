@@ -2,7 +2,7 @@
 CPU checks of the fused spectral losses (include/rfx.h, "FUSED SPECTRAL LOSSES"; csrc/rfx_spec_loss_core.h).
 
 * tests/emu/rfx_spec_loss_emu.cpp runs the core's slot rule, the plain fold and the circular fold in double over the four geometries of
-  tests/test_gpu_loop_decode.ENGINES, at Lw = hop * 40 + 17 (plain) and hop * 41 (loop), and must agree with float64 torch.autograd
+  tests/engines.ENGINES, at Lw = hop * 40 + 17 (plain) and hop * 41 (loop), and must agree with float64 torch.autograd
   (tests/spec_loss_oracle.py) to the relative L2 of tests/test_mel_backward_cpu.py, 1e-10: the same statement up to the order of the
   sums.  Each term alone and both together; the silent row is exact zeros.
 * The circular fold is the adjoint of loop_oracle's circular framing: the defect <A x, y> - <x, A^T y> relative to |A x| |y| stays
@@ -15,29 +15,26 @@ CPU checks of the fused spectral losses (include/rfx.h, "FUSED SPECTRAL LOSSES";
 * The autograd routing, on a fake plan that needs no device.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import emu_build
 import loop_oracle
 import spec_loss_oracle as SLO
-from test_gpu_loop_decode import ENGINES
+from engines import ENGINES
+from helpers import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "rfx_spec_loss_emu.cpp")
-EMU_MAIN = os.path.join(ROOT, "tests", "emu", "rfx_spec_loss_emu_main.cpp")
+EMU_SRC = "rfx_spec_loss_emu.cpp"
+EMU_MAIN = "rfx_spec_loss_emu_main.cpp"
 GATE = 1e-10
 
 
 @pytest.fixture(scope="module")
 def O():
-    import riffusion_oracle
-
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    return riffusion_oracle
+    return oracle()
 
 
 @pytest.fixture(scope="module")
@@ -48,10 +45,8 @@ def lib():
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("spec_loss_emu") / "librfx_spec_loss_emu.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, EMU_SRC], check=True)
-    lib = ctypes.CDLL(so)
+def emu():
+    lib = ctypes.CDLL(emu_build.shared(EMU_SRC, "-ffp-contract=off"))
     vp, i, d, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float
     lib.emu_spec_loss_frames.argtypes = [i, i, i, i, i]
     lib.emu_spec_loss_backward.argtypes = [i, i, i, i, i, vp, vp, vp, vp, d, d, d, vp]
@@ -167,12 +162,10 @@ def test_three_sums_on_the_logical_threads(emu):
     assert ok == [1, 1, 1, 1, 0, 0, 0, 0]
 
 
-def test_sanitized_stand_alone_emulator(emu, tmp_path):
+def test_sanitized_stand_alone_emulator(emu):
     """the emulator with its own main, built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program; the sanitizers'
     runtimes are linked statically, so the program carries them itself.  Its figures are the unsanitized build's."""
-    exe = str(tmp_path / "rfx_spec_loss_emu_asan")
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                    "-static-libasan", "-static-libubsan", "-o", exe, EMU_SRC, EMU_MAIN], check=True)
+    exe = emu_build.sanitized_program([EMU_SRC, EMU_MAIN], "-ffp-contract=off", "-fno-omit-frame-pointer")
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok") and "ERROR" not in run.stderr, run.stdout + run.stderr
     lines = [ln.split() for ln in run.stdout.splitlines() if ln.startswith("defect ")]
@@ -183,16 +176,15 @@ def test_sanitized_stand_alone_emulator(emu, tmp_path):
 
 
 def test_header_compiles_as_c99_with_the_new_entries(tmp_path):
-    src = tmp_path / "use_rfx.c"
-    src.write_text('#include "rfx.h"\n'
-                   "size_t q(const rfx_plan* p) { return rfx_spectral_loss_workspace_bytes(p, 1, 17657) + rfx_spectral_loss_loop_workspace_bytes(p, 1, 18081)\n"
-                   "    + rfx_spectral_loss_backward_workspace_bytes(p, 1, 17657) + rfx_spectral_loss_backward_loop_workspace_bytes(p, 1, 18081); }\n"
-                   "int f(const rfx_plan* p, const float* w, const float* m, const float* c, double* s, float* o, void* ws) {\n"
-                   "  return rfx_spectral_loss(p, w, m, 1, 17657, 0.5f, s, ws, 0, 0) + rfx_spectral_loss_loop(p, w, m, 1, 18081, 0.0f, s, ws, 0, 0)\n"
-                   "    + rfx_spectral_loss_backward(p, w, m, c, 1, 17657, 0.5f, o, ws, 0, 0)\n"
-                   "    + rfx_spectral_loss_backward_loop(p, w, m, c, 1, 18081, 0.5f, o, ws, 0, 0); }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "use_rfx.o")],
-                   check=True)
+    emu_build.header_compiles_as_c99(
+        tmp_path,
+        '#include "rfx.h"\n'
+        "size_t q(const rfx_plan* p) { return rfx_spectral_loss_workspace_bytes(p, 1, 17657) + rfx_spectral_loss_loop_workspace_bytes(p, 1, 18081)\n"
+        "    + rfx_spectral_loss_backward_workspace_bytes(p, 1, 17657) + rfx_spectral_loss_backward_loop_workspace_bytes(p, 1, 18081); }\n"
+        "int f(const rfx_plan* p, const float* w, const float* m, const float* c, double* s, float* o, void* ws) {\n"
+        "  return rfx_spectral_loss(p, w, m, 1, 17657, 0.5f, s, ws, 0, 0) + rfx_spectral_loss_loop(p, w, m, 1, 18081, 0.0f, s, ws, 0, 0)\n"
+        "    + rfx_spectral_loss_backward(p, w, m, c, 1, 17657, 0.5f, o, ws, 0, 0)\n"
+        "    + rfx_spectral_loss_backward_loop(p, w, m, c, 1, 18081, 0.5f, o, ws, 0, 0); }\n")
 
 
 def test_entries_answer_zero_or_refuse_without_a_plan(lib):

@@ -71,7 +71,7 @@ def device_stages(conv, files):
 
 
 def emulator_rounds(files):
-    from test_jpeg_decode_cpu import _emu, emu_decode
+    from jpeg_decode_cases import _emu, emu_decode
 
     stats = np.array([emu_decode(f)[2] for f in files])
     return _emu().emu_jpeg_dec_sub_bits(), _emu().emu_jpeg_dec_group(), stats

@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "riffusion-hobby_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import test_png_cpu as cpu  # noqa: E402
+import png_cases as cpu  # noqa: E402
 
 SEEDS = ("agile.png", "marim.png", "motorway.png", "vibes.png")
 

@@ -140,7 +140,7 @@ def main():
     import spec_loss_oracle as SLO
     from helpers import snr_db, synthetic_wave
     from riffusion import _autograd, _hip
-    from test_gpu_loop_decode import ENGINES
+    from engines import ENGINES
 
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     lines.append("end to end against float64 autograd through the oracle's STFT, B = 3, T = 41 (dB; dev = the device, o32 = float32 torch):")
